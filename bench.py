@@ -27,6 +27,16 @@ collective; `value` is the whole-job aggregate.  Under torchrun
 (WORLD_SIZE set) it is one process per GPU; launched directly with --gpus N it
 drives N devices from this process (one set and stream per device, host-side
 sums) and REFUSES to run if fewer than N devices are visible.
+
+A plain run does only what the headline needs: set up, warm up, time the K
+steps, print the line.  `--full` adds everything else, as before: the numpy
+gate before timing, the CPU baseline, the single-launch / other-dispatch /
+L3 / footprint figures, config 4 as a whole job and the side legs, with the
+full record in `--legs-out`.  `--dump-outputs DIR` writes what the last timed
+step computed (a fixed, seeded sample of the commit indices and vote outcomes,
+and every member's tallies) as .npy files, so two builds can be compared
+output for output: the inputs are counter-based, the same for the same
+arguments.
 """
 from __future__ import annotations
 
@@ -1774,6 +1784,60 @@ def run_side_legs(args, device, timeout_s=900):
     return res
 
 
+DUMP_LIMIT_BYTES = 64 * 2**20  # everything --dump-outputs writes, all shards together
+DUMP_SAMPLE = 1 << 21  # sampled groups per job: 20 B each (commit f64, outcome f32, index f64) = 40 MiB
+DUMP_SEED = 0x5EED0DD5
+
+
+def dump_sample_index(total: int, shard: int, n_shards: int) -> np.ndarray:
+    """The flat indices (member * G + group) of a shard's outputs that --dump-outputs writes: all of them when they fit,
+    else a fixed, seeded, sorted sample.  Depends on the arguments only, so every run of the same command picks the same."""
+    size = DUMP_SAMPLE // max(1, n_shards)
+    if total <= size:
+        return np.arange(total, dtype=np.int64)
+    rng = np.random.default_rng([DUMP_SEED, shard])
+    return np.sort(rng.choice(total, size=size, replace=False)).astype(np.int64)
+
+
+def dump_outputs(out_dir, sets, cfg, shards, n_shards):
+    """What the last timed step handed its caller, per set: every member's tallies (n_changed / n_won / n_lost) and, at the
+    sampled groups, the new commit indices (float64: exact below 2^53) and the vote outcomes (float32).  One GPU's files are
+    <name>.npy, several GPUs' <name>_gpu<shard>.npy.  -> {file name: bytes}"""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for s, shard in zip(sets, shards):
+        per, _ = s.wait(want_counts=True)  # the tallies of every member's LAST sweep: the last timed step
+        G, members = cfg["G"], len(s.engines)
+        idx = dump_sample_index(members * G, shard, n_shards)
+        cut = np.searchsorted(idx, np.arange(members + 1, dtype=np.int64) * G)
+        committed = np.empty(idx.size, np.float64)
+        outcome = np.empty(idx.size, np.float32) if cfg["votes"] else None
+        for b, e in enumerate(s.engines):
+            lo, hi = cut[b], cut[b + 1]
+            if lo == hi:
+                continue
+            g = idx[lo:hi] - b * G
+            c = e.read_committed()[g]
+            if c.size and int(c.max()) >= 1 << 53:
+                raise SystemExit(f"--dump-outputs: member {b}: a commit index above 2^53 has no exact float64")
+            committed[lo:hi] = c
+            if outcome is not None:
+                outcome[lo:hi] = e.read_outcome()[g]
+        sfx = "" if n_shards == 1 else f"_gpu{shard}"
+        arrays["committed" + sfx] = committed
+        if outcome is not None:
+            arrays["outcome" + sfx] = outcome
+        arrays["sample_index" + sfx] = idx.astype(np.float64)
+        for k in ("n_changed", "n_won", "n_lost"):
+            arrays[k + sfx] = np.array([getattr(c, k) for c in per], np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes would exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name + ".npy": a.nbytes for name, a in arrays.items()}
+
+
 def plan_devices(gpus: int, forced_device, visible: int, world_size: int, local_rank: int) -> list[int]:
     """The GPU indices THIS process drives.  Under torchrun: one (its local rank).  Launched directly:
     all `gpus` of them.  Never fewer than asked for: a job that cannot get its GPUs fails loudly.
@@ -1796,7 +1860,7 @@ def plan_devices(gpus: int, forced_device, visible: int, world_size: int, local_
     return list(range(gpus))
 
 
-def main():
+def make_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
@@ -1818,10 +1882,26 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the side measurements")
     ap.add_argument("--side-legs-child", default=None, metavar="OUT.json",
                     help="(internal) run the side legs only, on --device, and write their objects to OUT.json")
-    ap.add_argument("--legs-out", default=os.path.join(ROOT, "gpurun_out", "bench_legs.json"),
+    ap.add_argument("--legs-out", default=None,
                     help="where the FULL record goes (every side leg's objects): stdout carries one line of at "
-                         "most 4 KB with the contract's keys and a few scalars per leg")
+                         "most 4 KB with the contract's keys and a few scalars per leg (default: bench_out/bench_legs.json "
+                         "under --full, none in a plain run)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the numpy gate before timing, the CPU baseline, the "
+                         "other launch shapes, sizes and configs, and the side legs (each still subject to --no-extras / "
+                         "--no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32 / float64, "
+                         "a fixed, seeded sample of at most 64 MB in all)")
+    return ap
+
+
+def main():
+    ap = make_parser()
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    legs_out = args.legs_out or (os.path.join(ROOT, "bench_out", "bench_legs.json") if args.full else None)
 
     import torch
 
@@ -1860,9 +1940,10 @@ def main():
         s = SweepSet(engines)
         s.set_mode(_lib.SET_PERSISTENT if args.mode == "persistent" else _lib.SET_GRID)
         sets.append(s)
-        # correctness gate before any timing, on every device of every rank: every member's tally and the whole result
-        # arrays of member 0, one clone and the last member, against numpy
-        gates.append(gate_set(cfg, s, engines, states, flags, f"rank {world.rank} device {d}"))
+        if args.full:
+            # correctness gate before any timing, on every device of every rank: every member's tally and the whole result
+            # arrays of every member, against numpy
+            gates.append(gate_set(cfg, s, engines, states, flags, f"rank {world.rank} device {d}"))
     distinct = max(1, min(args.distinct, n_batches))
     # the tallies of the whole job, summed over ranks (host side, a few bytes -- the job's only reduction besides the clock)
     local_changed = sum(g["n_changed_total"] for g in gates)
@@ -1881,6 +1962,10 @@ def main():
                                               "launch_us": [ms * 1e3 / args.steps for ms in ev_ms]})
     if n_gpus != job_sets:
         raise SystemExit(f"{n_gpus} GPUs' worth asked for, {job_sets} sets were swept")
+    dumped = None
+    if args.dump_outputs:
+        shards = [world.rank * len(devices) + i for i in range(len(devices))]
+        dumped = dump_outputs(args.dump_outputs, sets, cfg, shards, n_gpus)
 
     groups_per_gpu = cfg["G"] * n_batches
     decisions = groups_per_gpu * args.steps * n_gpus
@@ -1947,11 +2032,14 @@ def main():
             "frac_per_gpu": [bytes_per_launch / (u * 1e-6) / 1e9 / HBM_PEAK_GBPS for r in per_rank for u in r["launch_us"]],
             "wall_ms_per_rank": [r["wall_ms"] for r in per_rank],
         },
-        "gate": {"what": "before timing, on every device of every rank: every member's tally and the whole commit / outcome "
-                         "arrays of member 0, the first clone and the last member, against numpy",
-                 "sets_gated": job_sets, "members_compared_in_full_per_set": gates[0]["members_compared_in_full"],
-                 "groups_advanced_per_step_whole_job": job_changed},
     }
+    if args.full:
+        out["gate"] = {"what": "before timing, on every device of every rank: every member's tally and the whole commit / outcome "
+                               "arrays of member 0, the first clone and the last member, against numpy",
+                       "sets_gated": job_sets, "members_compared_in_full_per_set": gates[0]["members_compared_in_full"],
+                       "groups_advanced_per_step_whole_job": job_changed}
+    if dumped is not None:
+        out["outputs_dumped"] = {"dir": args.dump_outputs, "files": dumped}
     pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
     if os.path.exists(pmc):
         # PMC traffic is measured in separate rocprofv3 --pmc passes (tools/pmc_traffic.py); it is only quoted
@@ -1967,7 +2055,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             out["roofline"]["traffic_note"] = f"pmc_traffic.json unreadable: {e}"
 
-    extras = world.rank == 0 and not args.no_extras
+    extras = world.rank == 0 and args.full and not args.no_extras
     if extras:
         s0, e0, d0 = sets[0], all_engines[0], devices[0]
         k = max(2, min(args.steps, 40))
@@ -2011,7 +2099,7 @@ def main():
             "launch_us": us3, "decisions_per_s": cfg["G"] * 1000 / w3, "GBps": batch_bytes / (us3 * 1e-6) / 1e9,
             "note": "one 65 MB batch re-swept: served from Infinity Cache, NOT an HBM figure",
         }
-    if world.rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if world.rank == 0 and n_gpus == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, st0)
     elif world.rank == 0:
         out["cpu_baseline"] = None
@@ -2042,7 +2130,7 @@ def main():
             e.close()
     sets, all_engines = [], []
 
-    if n_gpus > 1 and not args.no_extras:
+    if n_gpus > 1 and args.full and not args.no_extras:
         # BASELINE configs[3] as a whole job: 2M groups x 7 peers per GPU (16M x 7 over 8), same step definition
         c4 = CONFIGS[4]
         rd4, wr4 = bytes_per_decision(c4)
@@ -2073,7 +2161,7 @@ def main():
                 "GBps_per_gpu": (rd4 + wr4) * c4["G"] * nb4 / (us4 * 1e-6) / 1e9,
                 "frac_per_gpu": (rd4 + wr4) * c4["G"] * nb4 / (us4 * 1e-6) / 1e9 / HBM_PEAK_GBPS,
             }
-    if world.rank == 0 and n_gpus == 1 and not args.no_extras:
+    if world.rank == 0 and n_gpus == 1 and args.full and not args.no_extras:
         # The side legs run in a CHILD process (this script with --side-legs-child): a leg that takes the process down with it --
         # a GPU memory fault aborts, it does not raise -- costs its own numbers, never the headline line (round 4's line was lost
         # to its size; a line lost to a crashed leg would be the same empty record).  This process holds no device memory by now.
@@ -2081,15 +2169,16 @@ def main():
     dist.barrier(world)
     if world.rank == 0:
         legs_file = None
-        try:
-            os.makedirs(os.path.dirname(os.path.abspath(args.legs_out)), exist_ok=True)
-            with open(args.legs_out, "w") as f:
-                json.dump(out, f, indent=1)
-                f.write("\n")
-            legs_file = os.path.relpath(args.legs_out, ROOT) if os.path.abspath(args.legs_out).startswith(ROOT) else args.legs_out
-        except OSError as e:
-            print(f"bench.py: could not write {args.legs_out}: {e}", file=sys.stderr)
-        print(f"bench.py: full record (every side leg) -> {legs_file}", file=sys.stderr, flush=True)
+        if legs_out:
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(legs_out)), exist_ok=True)
+                with open(legs_out, "w") as f:
+                    json.dump(out, f, indent=1)
+                    f.write("\n")
+                legs_file = os.path.relpath(legs_out, ROOT) if os.path.abspath(legs_out).startswith(ROOT) else legs_out
+            except OSError as e:
+                print(f"bench.py: could not write {legs_out}: {e}", file=sys.stderr)
+            print(f"bench.py: full record (every side leg) -> {legs_file}", file=sys.stderr, flush=True)
         sys.stdout.flush()
         print(contract_line(out, legs_file), flush=True)
     dist.shutdown(world)

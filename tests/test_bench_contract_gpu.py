@@ -87,7 +87,7 @@ def check_line(d, n_gpus, steps, warmup, sharing=1):
 
 
 def test_bench_at_the_drivers_arguments(gpu_engine_cls):
-    d = run_bench("--gpus", "1", "--steps", "20", "--warmup", "5", "--no-extras")
+    d = run_bench("--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-extras")
     cfg, r = check_line(d, 1, 20, 5)
     # the timed region is the kernel: one launch per step, issued from C, events on the set's own stream
     assert abs(r["kernel_time_over_wall"] - r["launch_us"] / (d["ms_per_step"] * 1e3 / cfg["launches_per_step"])) < 1e-9
@@ -99,7 +99,7 @@ def test_bench_at_the_drivers_arguments(gpu_engine_cls):
 
 
 def test_bench_extras_and_other_configs(gpu_engine_cls):
-    d = run_bench("--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--batches", "20")
+    d = run_bench("--steps", "10", "--warmup", "2", "--full", "--no-cpu-baseline", "--batches", "20")
     check_line(d, 1, 10, 2)
     assert d["cpu_baseline"] is None
     assert d["single_launch"]["launches_per_step"] == 20 and d["single_launch"]["launch_us"] > d["roofline"]["per_batch_us"] * 0.9
@@ -145,6 +145,43 @@ def test_bench_extras_and_other_configs(gpu_engine_cls):
     assert 0.3 < d["single_launch"]["frac_read_of_peak"] < 1.0
 
 
+def test_plain_bench_is_lean_and_dumps_its_last_step(gpu_engine_cls, tmp_path):
+    """Without --full the run sets up, warms up, times its steps and prints the line: no gate, no CPU baseline, no extras, no side
+    legs.  --dump-outputs writes what the last timed step computed; here it is checked against numpy on the same inputs."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from raftsql_amd import synth
+
+    out = tmp_path / "outputs"
+    d = run_bench("--steps", "7", "--warmup", "1", "--batches", "20", "--distinct", "3", "--dump-outputs", str(out))
+    check_line(d, 1, 7, 1)
+    assert d["cpu_baseline"] is None and "gate" not in d and d["_line"]["legs"] == {}
+    for k in ("single_launch", "other_dispatch", "l3_resident", "footprint_curve", "config4_whole_job", *bench.SIDE_LEGS):
+        assert k not in d, k
+    files = {p.name: np.load(p) for p in out.iterdir()}
+    assert set(files) == {"committed.npy", "outcome.npy", "sample_index.npy", "n_changed.npy", "n_won.npy", "n_lost.npy"}
+    assert set(d["outputs_dumped"]["files"]) == set(files)
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 * 2**20
+    cfg = bench.CONFIGS[3]
+    G, members = cfg["G"], 20
+    idx = files["sample_index.npy"].astype(np.int64)
+    assert np.array_equal(idx, bench.dump_sample_index(members * G, 0, 1)) and idx.size == bench.DUMP_SAMPLE
+    want = [bench.numpy_expectation(cfg, synth.make_groups(G, cfg["N"], seed=synth.SEED_BASE + 3, group_offset=b * G))
+            for b in range(3)]  # member b holds distinct batch b % 3
+    m, g = idx // G, idx % G
+    for b in range(3):
+        sel = (m % 3) == b
+        new, oc, n_changed = want[b]
+        assert np.array_equal(files["committed.npy"][sel], new[g[sel]].astype(np.float64)), b
+        assert np.array_equal(files["outcome.npy"][sel], oc[g[sel]].astype(np.float32)), b
+        for k in range(b, members, 3):
+            assert files["n_changed.npy"][k] == n_changed, k
+            assert (files["n_won.npy"][k], files["n_lost.npy"][k]) == ((oc == 1).sum(), (oc == 2).sum()), k
+
+
 def test_bench_gated_config_as_headline(gpu_engine_cls):
     d = run_bench("--steps", "10", "--warmup", "2", "--config", "5", "--no-extras", "--no-cpu-baseline", "--batches", "20")
     assert "config5" in d["config"]["workload"] and d["roofline"]["bytes_per_decision"] == {"read": 56, "write": 8}
@@ -156,7 +193,7 @@ def test_bench_four_gpus_worth_from_one_process_and_refusal(gpu_engine_cls):
     must fail loudly instead of printing n_gpus: 1.  --device maps all four onto GPU 0 (testing only)."""
     import torch
 
-    d = run_bench("--gpus", "4", "--device", "0", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--batches", "20")
+    d = run_bench("--gpus", "4", "--device", "0", "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline", "--batches", "20")
     cfg, r = check_line(d, 4, 6, 2, sharing=4)
     assert "one process" in cfg["parallelism"] and "config4_whole_job" in d
     assert d["config4_whole_job"]["decisions_per_s"] > 1e9
@@ -192,7 +229,7 @@ def _torchrun_bench(nproc, _port_hint, *args):
 def test_bench_four_ranks_under_torchrun_on_one_gpu(gpu_engine_cls):
     """The driver's N > 1 launch line (torch.distributed.run, one process per GPU) at its default arguments for the
     rendezvous: gloo group + shared-memory barrier, no RCCL anywhere.  All four ranks on GPU 0 (testing only)."""
-    d = _torchrun_bench(4, 29533, "--steps", "6", "--warmup", "2", "--device", "0", "--no-extras", "--batches", "20")
+    d = _torchrun_bench(4, 29533, "--steps", "6", "--warmup", "2", "--device", "0", "--full", "--no-extras", "--batches", "20")
     cfg, r = check_line(d, 4, 6, 2, sharing=4)
     assert "torchrun" in cfg["parallelism"] and cfg["ranks_seen"] == [0, 1, 2, 3]
     assert cfg["rendezvous"] == {"backend": "gloo", "barrier": "shm", "note": ""}
@@ -200,9 +237,9 @@ def test_bench_four_ranks_under_torchrun_on_one_gpu(gpu_engine_cls):
 
 
 def test_bench_two_ranks_under_torchrun_with_the_side_legs(gpu_engine_cls):
-    """The driver's N > 1 command line has no --no-extras: rank 0 then measures its side legs while the other ranks wait at
-    the next barrier, and every rank takes part in config 4's whole job.  Two ranks on GPU 0, a small resident set."""
-    d = _torchrun_bench(2, 29536, "--steps", "4", "--warmup", "1", "--device", "0", "--batches", "10", "--no-cpu-baseline")
+    """--full with N > 1 and no --no-extras: rank 0 then measures its side legs while the other ranks wait at the next
+    barrier, and every rank takes part in config 4's whole job.  Two ranks on GPU 0, a small resident set."""
+    d = _torchrun_bench(2, 29536, "--steps", "4", "--warmup", "1", "--device", "0", "--batches", "10", "--full", "--no-cpu-baseline")
     assert d["n_gpus"] == 2 and d["config"]["ranks_seen"] == [0, 1] and d["gate"]["sets_gated"] == 2
     assert d["config4_whole_job"]["decisions_per_s"] > 1e9 and "2 GPU(s)" in d["config4_whole_job"]["workload"]
     assert d["single_launch"]["launches_per_step"] == 10 and d["other_dispatch"]["dispatch"] == "persistent"

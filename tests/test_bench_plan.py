@@ -109,3 +109,76 @@ def test_bench_py_names_resolve():
             known.add(n.name)
     missing = sorted({n.id for n in ast.walk(tree) if isinstance(n, ast.Name) and isinstance(n.ctx, ast.Load) and n.id not in known})
     assert not missing, missing
+
+
+def test_plain_run_is_the_default_and_full_is_opt_in():
+    """A plain `--gpus 1 --steps N --warmup W` runs only what the headline needs; everything else waits for --full."""
+    import bench
+
+    a = bench.make_parser().parse_args(["--gpus", "1", "--steps", "13", "--warmup", "3"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs, a.legs_out) == (13, 3, False, None, None)
+    a = bench.make_parser().parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    import numpy as np
+
+    import bench
+
+    assert bench.DUMP_SAMPLE * (8 + 4 + 8) <= bench.DUMP_LIMIT_BYTES
+    a = bench.dump_sample_index(33 << 20, 0, 1)
+    assert a.size == bench.DUMP_SAMPLE and np.array_equal(a, bench.dump_sample_index(33 << 20, 0, 1))
+    assert np.all(np.diff(a) > 0) and a[0] >= 0 and a[-1] < 33 << 20
+    assert not np.array_equal(bench.dump_sample_index(33 << 20, 1, 2), bench.dump_sample_index(33 << 20, 0, 2))
+    assert bench.dump_sample_index(33 << 20, 1, 4).size == bench.DUMP_SAMPLE // 4
+    assert np.array_equal(bench.dump_sample_index(1000, 0, 1), np.arange(1000))  # small outputs are written whole
+
+
+def test_dump_outputs_writes_what_the_members_hold(tmp_path):
+    """bench.dump_outputs on stand-in members: the sampled commit indices and outcomes of the right member and group, and every
+    member's tallies, as float64 / float32 .npy files; several GPUs' files carry their shard."""
+    from collections import namedtuple
+
+    import numpy as np
+
+    import bench
+
+    Counts = namedtuple("Counts", "n_changed n_won n_lost")
+
+    class Member:
+        def __init__(self, b, G):
+            self.c = (np.arange(G, dtype=np.uint64) * 7 + np.uint64(b) * (1 << 40))
+            self.o = ((np.arange(G) + b) % 3).astype(np.uint8)
+
+        def read_committed(self):
+            return self.c.copy()
+
+        def read_outcome(self):
+            return self.o.copy()
+
+    class Set:
+        def __init__(self, n, G, base):
+            self.engines = [Member(base + b, G) for b in range(n)]
+
+        def wait(self, want_counts=False):
+            per = [Counts(10 + b, 20 + b, 30 + b) for b in range(len(self.engines))]
+            return per, Counts(0, 0, 0)
+
+    G = 1 << 20
+    cfg = dict(bench.CONFIGS[3])
+    files = bench.dump_outputs(str(tmp_path / "one"), [Set(3, G, 0)], cfg, [0], 1)
+    assert set(files) == {"committed.npy", "outcome.npy", "sample_index.npy", "n_changed.npy", "n_won.npy", "n_lost.npy"}
+    got = {k: np.load(tmp_path / "one" / k) for k in files}
+    idx = got["sample_index.npy"].astype(np.int64)
+    assert got["committed.npy"].dtype == np.float64 and got["outcome.npy"].dtype == np.float32
+    assert np.array_equal(idx, bench.dump_sample_index(3 * G, 0, 1))
+    m, g = idx // G, idx % G
+    assert np.array_equal(got["committed.npy"], (g * 7 + m * (1 << 40)).astype(np.float64))
+    assert np.array_equal(got["outcome.npy"], ((g + m) % 3).astype(np.float32))
+    assert got["n_changed.npy"].tolist() == [10, 11, 12] and got["n_lost.npy"].tolist() == [30, 31, 32]
+    # two GPUs' worth, commit only (no outcome file)
+    cfg["votes"] = False
+    files = bench.dump_outputs(str(tmp_path / "two"), [Set(2, G, 0), Set(2, G, 2)], cfg, [0, 1], 2)
+    assert "outcome_gpu0.npy" not in files and {"committed_gpu0.npy", "committed_gpu1.npy", "n_won_gpu1.npy"} <= set(files)
+    assert sum(files.values()) <= bench.DUMP_LIMIT_BYTES

@@ -5,7 +5,7 @@
 set -u
 ROUND=${ROUND:-r06}
 P=gpurun_out/$ROUND; mkdir -p $P; export TMPDIR=/tmp
-BENCH="python bench.py --gpus 1 --steps 20 --warmup 5"
+BENCH="python bench.py --gpus 1 --steps 20 --warmup 5 --full"
 for step in "$@"; do
   echo "== $step ($(date +%T))"
   case $step in
