@@ -24,6 +24,16 @@ func Quorum(peers uint32) uint32 { return uint32(C.raftq_quorum(C.uint32_t(peers
 func (e *Engine) NGroups() uint64 { return uint64(C.raftq_groups(e.h)) }
 func (e *Engine) NPeers() uint32  { return uint32(C.raftq_peers(e.h)) }
 
+// SelfMax is the peer slot whose match row the device knows to be every group's largest (the commit sweep does not
+// read that row), or -1 when none is known.
+func (e *Engine) SelfMax() (int, error) {
+	var slot C.int32_t
+	if err := e.err(C.raftq_self_max(e.h, &slot)); err != nil {
+		return -1, err
+	}
+	return int(slot), nil
+}
+
 // SetStream installs a caller-owned hipStream_t; Stream returns the one in use.
 func (e *Engine) SetStream(stream unsafe.Pointer) error { return e.err(C.raftq_set_stream(e.h, stream)) }
 func (e *Engine) Stream() unsafe.Pointer                { return C.raftq_get_stream(e.h) }

@@ -187,6 +187,9 @@ int raftq_vote_tally(raftq_t* h, uint8_t* outcome_out /*[G]|NULL*/,
 int raftq_read_committed(raftq_t* h, uint64_t* committed_out /*[G]*/);
 int raftq_read_outcome(raftq_t* h, uint8_t* outcome_out /*[G]*/);
 int raftq_read_match(raftq_t* h, uint64_t* match_out /*[N][G]*/);
+/* the peer slot whose match row the device knows to be the largest of every
+ * group (the sweep then does not read that row), or -1 when none is known. */
+int raftq_self_max(raftq_t* h, int32_t* slot_out);
 int raftq_read_votes(raftq_t* h, uint8_t* votes_out /*[N][G]*/);
 /* compacted list of the groups the last RAFTQ_SWEEP_CHANGED sweep advanced,
  * in ascending group order; returns the count in *n (<= cap entries stored). */

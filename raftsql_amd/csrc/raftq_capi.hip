@@ -317,6 +317,22 @@ int ensure_adv(raftq_t* h, uint64_t entries) {
 }
 
 }  // namespace
+// The self-max word's full check (raftq_kernels.hpp): kSelfMaxValid | self slot is stored, then a pass over the rows
+// clears it if any group breaks the fact.  On the handle's stream, behind whatever wrote the rows.  With Step batches in
+// flight (raftq_set_self does not refuse them) the rows may still move: then the word is only cleared, which is always safe.
+int raftq_detail::self_max_check(raftq_t* h) {
+  if (int rc = use_device(h)) return rc;
+  if (h->step_collected != h->step_submitted) {
+    HIPCHK(h, hipMemsetAsync(h->self_max, 0, sizeof(uint32_t), h->stream));
+    return RAFTQ_OK;
+  }
+  HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)h->self_max, (int)(kSelfMaxValid | h->self_peer), 1, h->stream));
+  const uint64_t blocks = std::min<uint64_t>((h->G + kBlock - 1) / kBlock, 4096);
+  hipLaunchKernelGGL(self_max_check_kernel, dim3((unsigned)std::max<uint64_t>(blocks, 1)), dim3(kBlock), 0, h->stream,
+                     (const uint64_t*)h->match, h->ld, h->G, h->N, h->self_peer, h->self_max);
+  HIPCHK(h, hipGetLastError());
+  return RAFTQ_OK;
+}
 int raftq_detail::use_device(raftq_t* h) {
   if (!h) return fail(nullptr, RAFTQ_EINVAL, "null handle");
   HIPCHK(h, hipSetDevice(h->device));
@@ -436,6 +452,10 @@ int raftq_create(int device, uint64_t n_groups, uint32_t n_peers, raftq_t** out)
     if ((rc = alloc((void**)&h->partials, h->max_partials * sizeof(uint4)))) break;
     if ((rc = alloc((void**)&h->offsets, (h->max_partials + 1) * 8))) break;
     if ((rc = alloc((void**)&h->compact_arrived, 64))) break;
+    // the self-max word (raftq_kernels.hpp): every row is zero, so row 0 (the default self slot) is the largest
+    if ((rc = alloc((void**)&h->self_max, 64))) break;
+    e = hipMemsetD32Async((hipDeviceptr_t)h->self_max, (int)(kSelfMaxValid | 0u), 1, h->stream);
+    if (e != hipSuccess) { rc = fail(h, RAFTQ_EHIP, std::string("hipMemsetD32Async: ") + hipGetErrorString(e)); break; }
     e = hipHostMalloc((void**)&h->h_partials, h->max_partials * sizeof(uint4), hipHostMallocDefault);
     if (e != hipSuccess) { rc = fail(h, RAFTQ_ENOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(e)); break; }
     e = hipHostMalloc((void**)&h->h_total, 64, hipHostMallocMapped | host_coherence_flag());
@@ -489,6 +509,7 @@ void raftq_destroy(raftq_t* h) {
   if (h->seg_h) (void)hipHostFree(h->seg_h);
   (void)hipFree(h->offsets);
   (void)hipFree(h->compact_arrived);
+  (void)hipFree(h->self_max);
   (void)hipFree(h->claim);
   (void)hipFree(h->delta_dev);
   (void)hipFree(h->delta_bad);
@@ -536,9 +557,11 @@ int raftq_load_match(raftq_t* h, const uint64_t* match, const uint64_t* committe
   if (int rc = use_device_idle(h, "raftq_load_match")) return rc;
   if (!match && !committed) return fail(h, RAFTQ_EINVAL, "raftq_load_match: nothing to load");
   // one copy per peer row: a row of a large handle is wider than the 2D copy's pitch limit (2^31 - 1 bytes)
-  if (match)
+  if (match) {
     for (uint32_t p = 0; p < h->N; ++p)
       HIPCHK(h, hipMemcpyAsync(h->match + (size_t)p * h->ld, match + (size_t)p * h->G, h->G * 8, hipMemcpyHostToDevice, h->stream));
+    if (int rc = raftq_detail::self_max_check(h)) return rc;
+  }
   dense_changed(h);
   if (committed)
     HIPCHK(h, hipMemcpyAsync(h->committed[h->cur], committed, h->G * 8, hipMemcpyHostToDevice, h->stream));
@@ -668,7 +691,7 @@ static int enqueue_ingest(raftq_t* h, const AbiRec* d, uint64_t n, const raftq_v
   if (n) dense_changed(h);  // (match words move under Step's records)
   if (n && trusted)
     hipLaunchKernelGGL((deltas_in_apply_kernel<Rec>), gm, dim3(kBlock), 0, h->stream, (const Rec*)h->ingest_d, n, h->match, h->ld,
-                       h->G, h->N, h->delta_bad, h->d_total + 1, em);
+                       h->G, h->N, h->delta_bad, h->d_total + 1, em, h->self_max);
   else if (n)
     hipLaunchKernelGGL((deltas_in_kernel<Rec>), gm, dim3(kBlock), 0, h->stream, (const Rec*)h->ingest_d, dev_m, n, h->G, h->N,
                        h->delta_bad, h->d_total + 1, em);
@@ -678,7 +701,7 @@ static int enqueue_ingest(raftq_t* h, const AbiRec* d, uint64_t n, const raftq_v
                        h->d_total + 2, ev);
   if (n && !trusted)
     hipLaunchKernelGGL((apply_deltas_kernel<Rec>), gm, dim3(kBlock), 0, h->stream, h->match, h->ld, (const Rec*)dev_m, n, bad, em,
-                       ev);
+                       ev, h->self_max);
   if (nv) {
     // trusted match deltas are dropped one by one, never as a batch: their verdict does not gate the votes
     const unsigned long long em_gate = trusted ? kNoEpoch : em;
@@ -775,6 +798,7 @@ static SweepArgs sweep_args(const raftq_t* h, int cur, bool want_bits) {
   a.changed_bits = want_bits ? h->changed_bits : nullptr;
   a.partials = h->partials;
   a.ld = h->ld;
+  a.self_max = h->self_max;
   return a;
 }
 
@@ -916,6 +940,16 @@ int raftq_read_outcome(raftq_t* h, uint8_t* out) {
   HIPCHK(h, hipMemcpyAsync(packed.data(), h->outcome, packed.size(), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   for (uint64_t g = 0; g < h->G; ++g) out[g] = (uint8_t)((packed[g >> 2] >> (2 * (g & 3))) & 3u);  // 2 bits per group
+  return RAFTQ_OK;
+}
+
+int raftq_self_max(raftq_t* h, int32_t* slot) {
+  if (int rc = use_device_idle(h, "raftq_self_max")) return rc;
+  if (!slot) return fail(h, RAFTQ_EINVAL, "raftq_self_max: null argument");
+  uint32_t w = 0;
+  HIPCHK(h, hipMemcpyAsync(&w, h->self_max, sizeof w, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  *slot = (w & kSelfMaxValid) ? (int32_t)(w & 0xffu) : -1;
   return RAFTQ_OK;
 }
 
@@ -2053,6 +2087,8 @@ int raftq_clone_state(raftq_t* dst, raftq_t* src) {
   HIPCHK(dst, hipMemcpyAsync(dst->first_idx, src->first_idx, ld * 8, hipMemcpyDeviceToDevice, dst->stream));
   HIPCHK(dst, hipMemcpyAsync(dst->votes, src->votes, (size_t)vote_word_bytes((int)dst->N) * ld, hipMemcpyDeviceToDevice,
                              dst->stream));
+  // the rows are the source's, so is what is known about them (the word names its slot: it holds whatever dst's self is)
+  HIPCHK(dst, hipMemcpyAsync(dst->self_max, src->self_max, sizeof(uint32_t), hipMemcpyDeviceToDevice, dst->stream));
   HIPCHK(dst, hipStreamSynchronize(dst->stream));
   dst->have_terms = src->have_terms;
   dense_changed(dst);

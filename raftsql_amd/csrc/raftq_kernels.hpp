@@ -39,7 +39,16 @@ struct SweepArgs {
   uint64_t* changed_bits;      // [ld/64] lane-ordered bitmap, or nullptr
   uint4* partials;             // [ld/kTile * kWaves] {changed, won, lost, 0}
   uint64_t ld;
+  const uint32_t* self_max = nullptr;  // the handle's self-max word (below), or nullptr = never skip a row
 };
+
+// The self-max word of a handle (one device u32): kSelfMaxValid | slot when row `slot` of match is known to be the
+// largest of its group in EVERY group, else 0.  Raft's leader holds its own last index in Progress.Match and a
+// follower's Match only comes from acks of entries the leader sent, so for the leader's own slot the fact is the
+// rule.  While it holds, the q-th largest of the N values of a group is the (q-1)-th largest of the other N-1
+// (q >= 2, ties included), and the sweep does not read that row at all.  Set only by a full
+// check over the rows (self_max_check_kernel); cleared by every writer of match that may break it.
+constexpr uint32_t kSelfMaxValid = 0x80000000u;
 
 // ---------------------------------------------------------------------------
 // uint64 compare-exchange, descending: a <- max, b <- min.  gfx950 has no
@@ -85,6 +94,34 @@ __device__ __forceinline__ uint64_t select_quorum_network(uint64_t (&v)[N]) {
   }
 #undef CE
   return v[N / 2];
+}
+
+// The same selection with the self row left out: v[0 .. N-1) are the OTHER peers' values of a group whose own
+// (skipped) value is its maximum; -> the (q-1)-th largest of them, element N/2 - 1 of their descending order.  The
+// comparator lists are the sorting networks of N - 1 inputs above, cut back to the comparators that can reach that
+// element (0-1-principle checked in tests/test_self_max_networks.py).  v[N-1] is not read.
+template <int N>
+__device__ __forceinline__ uint64_t select_other_network(uint64_t (&v)[N]) {
+#define CE(i, j) ce_desc(v[i], v[j])
+  if constexpr (N == 3) { CE(0, 1); }
+  if constexpr (N == 4) { CE(0, 2); CE(0, 1); CE(1, 2); }
+  if constexpr (N == 5) { CE(0, 2); CE(1, 3); CE(0, 1); CE(2, 3); CE(1, 2); }
+  if constexpr (N == 6) {
+    CE(0, 3); CE(1, 4); CE(0, 2); CE(1, 3); CE(0, 1); CE(2, 4); CE(1, 2); CE(3, 4); CE(2, 3);
+  }
+  if constexpr (N == 7) {
+    CE(0, 5); CE(1, 3); CE(2, 4); CE(1, 2); CE(3, 4); CE(0, 3); CE(2, 5); CE(0, 1); CE(2, 3); CE(1, 2);
+  }
+  if constexpr (N == 8) {
+    CE(0, 6); CE(2, 3); CE(4, 5); CE(0, 2); CE(1, 4); CE(3, 6); CE(0, 1);
+    CE(2, 5); CE(3, 4); CE(1, 2); CE(4, 6); CE(2, 3); CE(4, 5); CE(3, 4);
+  }
+  if constexpr (N == 9) {
+    CE(0, 2); CE(1, 3); CE(4, 6); CE(5, 7); CE(0, 4); CE(1, 5); CE(2, 6); CE(3, 7); CE(0, 1);
+    CE(2, 3); CE(4, 5); CE(6, 7); CE(2, 4); CE(3, 5); CE(1, 4); CE(3, 6); CE(3, 4);
+  }
+#undef CE
+  return v[N / 2 - 1];
 }
 
 // Odd-even transposition sort (N rounds of neighbour exchanges): the network
@@ -211,14 +248,31 @@ struct TileRegs {
   u64x2 c[COMMIT ? kRounds : 1];
   u64x2 f[COMMIT && GATED ? kRounds : 1];
   u32x4p vw[VOTES ? (N <= 8 ? 1 : 2) : 1];  // the 8 vote words of the lane's 8 groups
+  uint32_t skip = 0;  // self_max_skip() of the tile's handle (wave-uniform): which row tile_load<SKIP = true> leaves out
 };
 
-template <int N, int GPL, bool COMMIT, bool GATED, bool VOTES, int POLICY, int BLOCK = kBlock>
+// The row a sweep of this handle may leave out: 0 = none (read all N rows), else self slot + 1.  The word is read
+// once per workgroup and made wave-uniform; a commit sweep of N >= 2 (q >= 2) is the only one that can use it.
+template <int N, bool COMMIT>
+__device__ __forceinline__ uint32_t self_max_skip(const SweepArgs& a) {
+  if constexpr (!COMMIT || N < 2) {
+    return 0;
+  } else {
+    if (a.self_max == nullptr) return 0;
+    const uint32_t w = __builtin_amdgcn_readfirstlane(ldg<false>(a.self_max));
+    return (w & kSelfMaxValid) != 0 ? (w & 0xffu) + 1 : 0;
+  }
+}
+
+// SKIP (with r.skip = self slot + 1): the tile's commit part reads the N - 1 rows other than the self row into
+// r.m[j][0 .. N-1), in slot order; tile_finish then selects with select_other_network.  Without it, every row.
+template <int N, int GPL, bool COMMIT, bool GATED, bool VOTES, int POLICY, int BLOCK = kBlock, bool SKIP = false>
 __device__ __forceinline__ void tile_load(TileRegs<N, GPL, COMMIT, GATED, VOTES>& r, const SweepArgs& a,
                                           const uint32_t tile) {
   constexpr bool NT = (POLICY & kLdNT) != 0;
   constexpr int kTile = BLOCK * GPL;
   constexpr int kRounds = GPL / 2;
+  constexpr int kRows = SKIP && N >= 2 ? N - 1 : N;  // (a handle of one peer never skips: self_max_skip)
   const uint32_t tid = threadIdx.x;
   const uint64_t tile0 = (uint64_t)tile * kTile;
   // vote words first: their loads fly while the commit part computes
@@ -231,12 +285,18 @@ __device__ __forceinline__ void tile_load(TileRegs<N, GPL, COMMIT, GATED, VOTES>
     }
   }
   if constexpr (COMMIT) {
+    const uint64_t* row[kRows];  // wave-uniform
+#pragma unroll
+    for (int p = 0; p < kRows; ++p) {
+      const uint32_t slot = SKIP ? (uint32_t)p + ((uint32_t)p + 1 >= r.skip ? 1u : 0u) : (uint32_t)p;
+      row[p] = a.match + (uint64_t)slot * a.ld;
+    }
 #pragma unroll
     for (int j = 0; j < kRounds; ++j) {
       const uint64_t g = tile0 + (uint64_t)(tid >> 6) * (64 * GPL) + (uint64_t)j * 128 + 2 * (tid & 63);
 #pragma unroll
-      for (int p = 0; p < N; ++p) {
-        r.m[j][p] = ldg<NT>(reinterpret_cast<const u64x2*>(a.match + (uint64_t)p * a.ld + g));
+      for (int p = 0; p < kRows; ++p) {
+        r.m[j][p] = ldg<NT>(reinterpret_cast<const u64x2*>(row[p] + g));
       }
       r.c[j] = ldg<NT>(reinterpret_cast<const u64x2*>(a.committed + g));
       if constexpr (GATED) r.f[j] = ldg<NT>(reinterpret_cast<const u64x2*>(a.first_idx + g));
@@ -244,7 +304,15 @@ __device__ __forceinline__ void tile_load(TileRegs<N, GPL, COMMIT, GATED, VOTES>
   }
 }
 
-template <int N, int GPL, bool COMMIT, bool GATED, bool VOTES, int POLICY, bool BITS, int BLOCK = kBlock>
+// The quorum index of one group from the tile's registers: v[0 .. kRows) as tile_load<SKIP> left them.
+template <int N, bool SKIP>
+__device__ __forceinline__ uint64_t quorum_select(uint64_t (&v)[N]) {
+  if constexpr (N == 1) return v[0];
+  else if constexpr (SKIP) return select_other_network<N>(v);
+  else return select_quorum_network<N>(v);
+}
+
+template <int N, int GPL, bool COMMIT, bool GATED, bool VOTES, int POLICY, bool BITS, int BLOCK = kBlock, bool SKIP = false>
 __device__ __forceinline__ void tile_finish(const TileRegs<N, GPL, COMMIT, GATED, VOTES>& r, const SweepArgs& a,
                                             const uint32_t tile) {
   constexpr bool STNT = (POLICY & kStNT) != 0;
@@ -266,9 +334,10 @@ __device__ __forceinline__ void tile_finish(const TileRegs<N, GPL, COMMIT, GATED
 #pragma unroll
     for (int j = 0; j < kRounds; ++j) {
       const uint64_t g = tile0 + (uint64_t)(tid >> 6) * (64 * GPL) + (uint64_t)j * 128 + 2 * (tid & 63);
+      constexpr int kRows = SKIP && N >= 2 ? N - 1 : N;
       uint64_t v0[N], v1[N];
 #pragma unroll
-      for (int p = 0; p < N; ++p) {
+      for (int p = 0; p < kRows; ++p) {
         v0[p] = r.m[j][p].x;
         v1[p] = r.m[j][p].y;
       }
@@ -277,16 +346,13 @@ __device__ __forceinline__ void tile_finish(const TileRegs<N, GPL, COMMIT, GATED
         mci0 = v0[0];
         mci1 = v1[0];
 #pragma unroll
-        for (int p = 1; p < N; ++p) {
+        for (int p = 1; p < kRows; ++p) {
           mci0 ^= v0[p];
           mci1 ^= v1[p];
         }
-      } else if constexpr (N == 1) {
-        mci0 = v0[0];
-        mci1 = v1[0];
       } else {
-        mci0 = select_quorum_network<N>(v0);
-        mci1 = select_quorum_network<N>(v1);
+        mci0 = quorum_select<N, SKIP>(v0);
+        mci1 = quorum_select<N, SKIP>(v1);
       }
       u64x2 o;
       if constexpr ((POLICY & kNoCompute) != 0) {
@@ -362,8 +428,15 @@ __device__ __forceinline__ void tile_finish(const TileRegs<N, GPL, COMMIT, GATED
 template <int N, int GPL, bool COMMIT, bool GATED, bool VOTES, int POLICY, bool BITS, int BLOCK = kBlock>
 __device__ __forceinline__ void sweep_tile(const SweepArgs& a, const uint32_t tile) {
   TileRegs<N, GPL, COMMIT, GATED, VOTES> r;
-  tile_load<N, GPL, COMMIT, GATED, VOTES, POLICY, BLOCK>(r, a, tile);
-  tile_finish<N, GPL, COMMIT, GATED, VOTES, POLICY, BITS, BLOCK>(r, a, tile);
+  r.skip = self_max_skip<N, COMMIT>(a);
+  // one uniform branch per tile: each arm is the straight-line load-all-then-finish of one row count
+  if (r.skip != 0) {
+    tile_load<N, GPL, COMMIT, GATED, VOTES, POLICY, BLOCK, true>(r, a, tile);
+    tile_finish<N, GPL, COMMIT, GATED, VOTES, POLICY, BITS, BLOCK, true>(r, a, tile);
+  } else {
+    tile_load<N, GPL, COMMIT, GATED, VOTES, POLICY, BLOCK>(r, a, tile);
+    tile_finish<N, GPL, COMMIT, GATED, VOTES, POLICY, BITS, BLOCK>(r, a, tile);
+  }
 }
 
 // One handle per launch: blockIdx.x = tile.
@@ -401,6 +474,16 @@ static __global__ __launch_bounds__(kBlock, MINW) void sweep_persist_kernel(cons
     a = tab[m];
     if (!want_bits) a.changed_bits = nullptr;
   };
+  // a member's tiles with and without its self row (uniform branches; a set may mix flagged and unflagged members)
+  auto load = [&](Regs& r, const SweepArgs& a, uint32_t tile) {
+    r.skip = self_max_skip<N, COMMIT>(a);
+    if (r.skip != 0) tile_load<N, GPL, COMMIT, GATED, VOTES, POLICY, kBlock, true>(r, a, tile);
+    else tile_load<N, GPL, COMMIT, GATED, VOTES, POLICY>(r, a, tile);
+  };
+  auto finish = [&](const Regs& r, const SweepArgs& a, uint32_t tile) {
+    if (r.skip != 0) tile_finish<N, GPL, COMMIT, GATED, VOTES, POLICY, BITS, kBlock, true>(r, a, tile);
+    else tile_finish<N, GPL, COMMIT, GATED, VOTES, POLICY, BITS>(r, a, tile);
+  };
   // Two register sets, A and B, used alternately (no copies: a copy would have to wait for the data), and every
   // finish is preceded in straight-line code by the other set's loads, so the wait in front of a tile's
   // arithmetic is vmcnt(one tile of loads), never vmcnt(0) -- a lane always has a tile of requests in flight.
@@ -408,24 +491,24 @@ static __global__ __launch_bounds__(kBlock, MINW) void sweep_persist_kernel(cons
   SweepArgs aA, aB;
   uint32_t tileA, tileB;
   locate(t, aA, tileA);
-  tile_load<N, GPL, COMMIT, GATED, VOTES, POLICY>(A, aA, tileA);
+  load(A, aA, tileA);
   while (true) {
     t += stride;
     if (t >= total_tiles) {
-      tile_finish<N, GPL, COMMIT, GATED, VOTES, POLICY, BITS>(A, aA, tileA);
+      finish(A, aA, tileA);
       break;
     }
     locate(t, aB, tileB);
-    tile_load<N, GPL, COMMIT, GATED, VOTES, POLICY>(B, aB, tileB);
-    tile_finish<N, GPL, COMMIT, GATED, VOTES, POLICY, BITS>(A, aA, tileA);
+    load(B, aB, tileB);
+    finish(A, aA, tileA);
     t += stride;
     if (t >= total_tiles) {
-      tile_finish<N, GPL, COMMIT, GATED, VOTES, POLICY, BITS>(B, aB, tileB);
+      finish(B, aB, tileB);
       break;
     }
     locate(t, aA, tileA);
-    tile_load<N, GPL, COMMIT, GATED, VOTES, POLICY>(A, aA, tileA);
-    tile_finish<N, GPL, COMMIT, GATED, VOTES, POLICY, BITS>(B, aB, tileB);
+    load(A, aA, tileA);
+    finish(B, aB, tileB);
   }
 }
 
@@ -606,6 +689,35 @@ __device__ __forceinline__ bool batch_is_bad(const unsigned long long* bad, unsi
   return bad[0] == epoch_match || bad[1] == epoch_votes;
 }
 
+// The self-max word's full check: the host has just stored kSelfMaxValid | slot into *word (same stream); every wave
+// that finds a group in which another row holds more than row `slot` clears it.  Grid-stride over the G groups.
+static __global__ __launch_bounds__(kBlock) void self_max_check_kernel(const uint64_t* __restrict__ match, uint64_t ld,
+                                                                       uint64_t n_groups, uint32_t n_peers, uint32_t slot,
+                                                                       uint32_t* word) {
+  bool broken = false;
+  for (uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x; g < n_groups; g += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t own = match[(uint64_t)slot * ld + g];
+    for (uint32_t p = 0; p < n_peers; ++p) broken |= match[(uint64_t)p * ld + g] > own;
+  }
+  if (__ballot(broken) != 0 && (threadIdx.x & 63) == 0) *word = 0u;
+}
+
+// An ingest kernel's share of the rule: a match record for peer `peer` that raises that row above the self row of
+// its group breaks the fact.  `w` is the word as the kernel found it (read once, before any record is applied).
+// Within one batch the self row only rises (atomic max), so a value read here is at most what the row ends at: a
+// record that is not above it cannot end above the row.  -> whether this record breaks the fact.
+__device__ __forceinline__ bool breaks_self_max(uint32_t w, const uint64_t* match, uint64_t ld, uint64_t group, uint32_t peer,
+                                                uint64_t value) {
+  if ((w & kSelfMaxValid) == 0) return false;
+  const uint32_t slot = w & 0xffu;
+  return peer != slot && value > match[(uint64_t)slot * ld + group];
+}
+// one store per wave that saw a breaking record (the lowest such lane)
+__device__ __forceinline__ void clear_self_max_if(bool broken, uint32_t* word) {
+  const uint64_t b = __ballot(broken);
+  if (b != 0 && (threadIdx.x & 63) == (uint32_t)(__ffsll((unsigned long long)b) - 1)) *word = 0u;
+}
+
 // Progress.maybeUpdate only ever raises Match, so a batch of MsgAppResp
 // deltas is an order-independent atomic max.
 // Ingest, pass 1: the records sit in pinned, device-mapped host memory (the caller's batch buffer); one coalesced
@@ -637,15 +749,19 @@ template <typename Rec>
 static __global__ __launch_bounds__(kBlock) void deltas_in_apply_kernel(const Rec* __restrict__ src, uint64_t n, uint64_t* match,
                                                                         uint64_t ld, uint64_t n_groups, uint32_t n_peers,
                                                                         unsigned long long* bad_epoch, uint64_t* bad_host,
-                                                                        unsigned long long epoch) {
+                                                                        unsigned long long epoch, uint32_t* self_max) {
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-  bool bad = false;
+  const uint32_t w = *self_max;
+  bool bad = false, broken = false;
   if (i < n) {
     const Rec r = src[i];
     bad = r.group >= n_groups || r.peer >= n_peers;
-    if (!bad)
+    if (!bad) {
+      broken = breaks_self_max(w, match, ld, r.group, r.peer, r.match);
       atomicMax(reinterpret_cast<unsigned long long*>(match + (uint64_t)r.peer * ld + r.group), (unsigned long long)r.match);
+    }
   }
+  clear_self_max_if(broken, self_max);
   if (__ballot(bad) != 0 && (threadIdx.x & 63) == 0) {
     atomicMax(bad_epoch, epoch);
     *bad_host = epoch;
@@ -656,13 +772,19 @@ template <typename Rec>
 static __global__ __launch_bounds__(kBlock) void apply_deltas_kernel(uint64_t* match, uint64_t ld,
                                                               const Rec* __restrict__ d, uint64_t n,
                                                               const unsigned long long* bad,
-                                                              unsigned long long epoch_match, unsigned long long epoch_votes) {
+                                                              unsigned long long epoch_match, unsigned long long epoch_votes,
+                                                              uint32_t* self_max) {
   if (batch_is_bad(bad, epoch_match, epoch_votes)) return;  // a record of this call is out of range: nothing is applied
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  const Rec r = d[i];
-  atomicMax(reinterpret_cast<unsigned long long*>(match + (uint64_t)r.peer * ld + r.group),
-            (unsigned long long)r.match);
+  const uint32_t w = *self_max;
+  bool broken = false;
+  if (i < n) {
+    const Rec r = d[i];
+    broken = breaks_self_max(w, match, ld, r.group, r.peer, r.match);
+    atomicMax(reinterpret_cast<unsigned long long*>(match + (uint64_t)r.peer * ld + r.group),
+              (unsigned long long)r.match);
+  }
+  clear_self_max_if(broken, self_max);
 }
 
 // Sparse term update: a group's leader changed term (became leader / appended
@@ -961,7 +1083,9 @@ static __global__ __launch_bounds__(kBlock) void sweep_segments_kernel(SweepArgs
   __shared__ uint32_t wave_cnt[kWaves];
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, tile = blockIdx.x;
   TileRegs<N, GPL, true, GATED, false> r;
-  tile_load<N, GPL, true, GATED, false, POLICY>(r, a, tile);
+  r.skip = self_max_skip<N, true>(a);
+  if (r.skip != 0) tile_load<N, GPL, true, GATED, false, POLICY, kBlock, true>(r, a, tile);
+  else tile_load<N, GPL, true, GATED, false, POLICY>(r, a, tile);
   const uint64_t tile0 = (uint64_t)tile * kTile;
   u64x2 nw[kRounds];
   uint64_t even[kRounds], odd[kRounds];  // wave-uniform ballots
@@ -975,8 +1099,14 @@ static __global__ __launch_bounds__(kBlock) void sweep_segments_kernel(SweepArgs
       v0[p] = r.m[j][p].x;
       v1[p] = r.m[j][p].y;
     }
-    const uint64_t mci0 = N == 1 ? v0[0] : select_quorum_network<N>(v0);
-    const uint64_t mci1 = N == 1 ? v1[0] : select_quorum_network<N>(v1);
+    uint64_t mci0, mci1;
+    if (r.skip != 0) {  // (v[N-1] holds no row then and is not read)
+      mci0 = quorum_select<N, true>(v0);
+      mci1 = quorum_select<N, true>(v1);
+    } else {
+      mci0 = quorum_select<N, false>(v0);
+      mci1 = quorum_select<N, false>(v1);
+    }
     u64x2 o;
     o.x = maybe_commit<GATED>(mci0, r.c[j].x, GATED ? r.f[j].x : 0);
     o.y = maybe_commit<GATED>(mci1, r.c[j].y, GATED ? r.f[j].y : 0);

@@ -75,6 +75,7 @@ NodeArrays node_arrays(raftq_t* h, uint8_t recs = raftqk::kRecsCaller) {
   a.msg_flags = h->step_msg_flags;
   a.recs = recs;
   a.n_groups = h->G;
+  a.self_max = h->self_max;
   return a;
 }
 
@@ -326,7 +327,7 @@ int raftq_set_self(raftq_t* h, uint32_t self_peer) {
   if (!h) return fail(nullptr, RAFTQ_EINVAL, "null handle");
   if (self_peer >= h->N) return fail(h, RAFTQ_EINVAL, "raftq_set_self: self_peer out of range");
   h->self_peer = self_peer;
-  return RAFTQ_OK;
+  return raftq_detail::self_max_check(h);  // the sweep's skipped row follows the handle's own slot
 }
 
 int raftq_load_node(raftq_t* h, const uint64_t* term, const uint32_t* vote, const uint32_t* lead,

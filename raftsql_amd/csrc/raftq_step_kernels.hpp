@@ -88,6 +88,7 @@ struct NodeArrays {
   uint8_t recs;     // whose records the batch holds: kRecsCaller, kRecsWire (raftq_step_submit_wire: the decoder's, strict) or
                     // kRecsFrames (raftq_step_frames: the decoder's, with RAFTQ_MSGF_* set by it)
   uint64_t n_groups;
+  uint32_t* self_max = nullptr;  // the handle's self-max word (raftq_kernels.hpp): a store that breaks the fact clears it
 };
 constexpr uint8_t kRecsCaller = 0, kRecsWire = 1, kRecsFrames = 2;
 
@@ -272,6 +273,17 @@ struct Node {
 #pragma unroll
     for (int p = 0; p < kMaxPeers; ++p)
       if ((mt_dirty >> p) & 1u) a.match[(uint64_t)p * a.ld + g] = mt[p];
+    // the group's rows as they now stand are all in mt[]: a peer above the word's slot breaks the self-max fact
+    if (mt_dirty != 0 && a.self_max != nullptr) {
+      const uint32_t w = *a.self_max;
+      if ((w & kSelfMaxValid) != 0) {
+        const uint64_t own = match(w & 0xffu);
+        bool broken = false;
+#pragma unroll
+        for (uint32_t p = 0; p < (uint32_t)kMaxPeers; ++p) broken |= p < a.n_peers && mt[p] > own;
+        if (broken) *a.self_max = 0u;
+      }
+    }
     if (elapsed_reset) a.elapsed[g] = 0;
     if (vw_dirty) {
       if (a.n_peers <= 8) reinterpret_cast<uint16_t*>(a.votes)[g] = (uint16_t)vw;

@@ -368,6 +368,13 @@ class QuorumEngine:
         self._chk(self._lib.raftq_read_match(self._h, _ptr(out)))
         return out
 
+    def self_max(self) -> int:
+        """raftq_self_max: the peer slot whose match row the device knows to be every group's largest (the commit sweep then
+        does not read that row), -1 when none is known"""
+        s = C.c_int32(-1)
+        self._chk(self._lib.raftq_self_max(self._h, C.byref(s)))
+        return int(s.value)
+
     def read_votes(self) -> np.ndarray:
         out = np.empty((self.n_peers, self.n_groups), dtype=np.uint8)
         self._chk(self._lib.raftq_read_votes(self._h, _ptr(out)))
