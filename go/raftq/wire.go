@@ -230,6 +230,60 @@ func (e *Engine) StepFrames(stream []byte, frameOff []uint64, tailAppends bool, 
 	return uint64(c.n_ents), uint64(c.n_malformed), e.err(rc)
 }
 
+// StepFramesRespond is StepFrames plus the messages its results call for, built and marshalled on the device
+// (raftq_step_frames_respond; raft.go:268-270 -> :227-230): MsgAppResp / MsgVoteResp / MsgHeartbeatResp to the senders and the
+// commit broadcast of a group whose at-tail bit is set (atTail: one bit per group, nil = none).  out receives rafthttp frames,
+// peer-major: peerOff[p] .. peerOff[p+1] (len N + 1) are peer p's frames, respOff (nil, or len >= n*(N-1)+1) their byte
+// offsets.  A result flagged OutfAnswered is answered: send nothing for it.  len(out) must be at least
+// n*(N-1)*RespondFrameMax.  Every slice must be page-locked (HostAlloc).
+func (e *Engine) StepFramesRespond(stream []byte, frameOff []uint64, tailAppends bool, msgs []WireMsg, ents []WireEnt, atTail []uint64,
+	out []byte, respOff, peerOff []uint64) (nEnts, nResp, respBytes uint64, err error) {
+	n := len(frameOff) - 1
+	if n <= 0 {
+		return 0, 0, 0, nil
+	}
+	if len(msgs) < n {
+		return 0, 0, 0, fmt.Errorf("raftq: StepFramesRespond: %d frames, room for %d records", n, len(msgs))
+	}
+	// the library writes peerOff and respOff and the walk reads atTail where they lie: a short slice would be overrun
+	if uint64(len(peerOff)) < uint64(e.Peers)+1 {
+		return 0, 0, 0, fmt.Errorf("raftq: StepFramesRespond: peerOff has %d words, needs Peers + 1 = %d", len(peerOff), e.Peers+1)
+	}
+	if atTail != nil && uint64(len(atTail)) < (e.Groups+63)/64 {
+		return 0, 0, 0, fmt.Errorf("raftq: StepFramesRespond: atTail has %d words, needs ceil(Groups / 64) = %d", len(atTail), (e.Groups+63)/64)
+	}
+	if respOff != nil && uint64(len(respOff)) < uint64(n)*uint64(e.Peers-1)+1 {
+		return 0, 0, 0, fmt.Errorf("raftq: StepFramesRespond: respOff has %d words, needs n * (Peers - 1) + 1 = %d", len(respOff),
+			uint64(n)*uint64(e.Peers-1)+1)
+	}
+	var pe *C.raftq_wire_ent_t
+	if len(ents) > 0 {
+		pe = (*C.raftq_wire_ent_t)(unsafe.Pointer(&ents[0]))
+	}
+	var pt, pr *C.uint64_t
+	if len(atTail) > 0 {
+		pt = (*C.uint64_t)(unsafe.Pointer(&atTail[0]))
+	}
+	if len(respOff) > 0 {
+		pr = (*C.uint64_t)(unsafe.Pointer(&respOff[0]))
+	}
+	ta := C.int(0)
+	if tailAppends {
+		ta = 1
+	}
+	var c, rcnt C.raftq_wire_counts_t
+	rc := C.raftq_step_frames_respond(e.h, bytesPtr(stream), C.uint64_t(len(stream)), (*C.uint64_t)(unsafe.Pointer(&frameOff[0])), C.uint64_t(n), ta,
+		(*C.raftq_wire_msg_t)(unsafe.Pointer(&msgs[0])), pe, C.uint64_t(len(ents)), pt, bytesPtr(out), C.uint64_t(len(out)), pr,
+		(*C.uint64_t)(unsafe.Pointer(&peerOff[0])), &c, &rcnt)
+	return uint64(c.n_ents), uint64(rcnt.n_msgs), uint64(rcnt.bytes), e.err(rc)
+}
+
+// OutfAnswered / RespondFrameMax: RAFTQ_OUTF_ANSWERED, RAFTQ_RESPOND_FRAME_MAX (include/raftq_wire.h)
+const (
+	OutfAnswered    = 0x10
+	RespondFrameMax = 83
+)
+
 // WalSaveBegin / WalSaveEnd: rc.wal.Save (raft.go:228) in two halves, so that a turn's WAL encode and its outbound marshal
 // are one submission: Begin enqueues (raftq_wal_encode_begin; page-locked buffers), the wait of the WireEncode called next
 // covers it, End reports what WalSave would have.  out is not to be read, nor recs / pool reused, before End.

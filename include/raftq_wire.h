@@ -167,6 +167,43 @@ int raftq_step_frames(raftq_t* h, const void* stream, uint64_t nbytes, const uin
                       raftq_wire_msg_t* msgs /*[n]*/, raftq_wire_ent_t* ents /*[ents_cap]|NULL*/, uint64_t ents_cap,
                       raftq_wire_counts_t* counts /*|NULL*/);
 
+/* raftq_step_frames + the messages its results call for, built and marshalled on the device (raft.go:268-270 -> :227-230:
+ * rc.node.Step's responses and the commit broadcast, then rc.transport.Send) -- ONE submission with one wait (a batch that stalls
+ * into the sorted walk, > 32 frames of one group, waits three times: the call, the replay, the answers laid out again).  Everything the caller can see apart from `out` is what
+ * raftq_step_frames gives on the same input -- records, entry headers, results, counts, the state after, the preconditions --
+ * except that a result whose messages were built carries RAFTQ_OUTF_ANSWERED in its flags: the host sends nothing for it.
+ * Built, for results 0 .. n-1 (every message From = self, Group = the result's; every other field zero):
+ *   RAFTQ_OUT_APPENDED          MsgAppResp{Term, Index: lastnewi} to the sender
+ *   RAFTQ_OUT_VOTE_RESP         MsgVoteResp{Term, Reject} to the sender
+ *   RAFTQ_OUT_HEARTBEAT_RESP    MsgHeartbeatResp{Term} to the sender
+ *   RAFTQ_OUT_PROGRESS + RAFTQ_OUTF_COMMITTED after a non-rejecting MsgAppResp, at_tail bit still set (bcastAppend with every
+ *                               follower at the tail): N - 1 empty MsgApp{Term, Index: lastIndex, LogTerm: lastTerm, Commit},
+ *                               lastIndex / lastTerm / Commit as they stand AT THAT MESSAGE
+ * Everything else stays the caller's and is not flagged: RAFTQ_OUT_APPEND, RAFTQ_OUT_BECAME_LEADER, resends and reject
+ * backoff, HELD / DEFERRED / SKIPPED / NONE.  A result the caller may have to answer itself (any of those that sends, a
+ * MsgAppResp while the group's bit is clear) ends its group's device-answered prefix: the group's later results of the batch
+ * are not answered either, so per (peer, group) the frames keep the order the host's own answers would have.
+ * at_tail ([ceil(G / 64)] words, bit g = group g; NULL = all clear): the caller's word that it leads g and every follower's
+ * Progress.Next is lastIndex + 1 now (Next is the caller's, raftq_step.h).  A wrong set bit is the caller's bug, a clear one
+ * only costs speed.  The device clears g's bit from g's first message on that makes the host move a Next away from the tail:
+ * a rejecting MsgAppResp with Index > Match, a MsgHeartbeatResp that leaves Match < lastIndex, a step-down.
+ * out: rafthttp stream frames, peer-major -- for every peer slot p != self, ascending, the frames addressed to p in result order
+ * (a broadcast puts one frame in every follower's slice).  peer_off[p] .. peer_off[p + 1] are frame indices (N + 1 words; self's
+ * slice is empty, peer_off[N] = n_resp); resp_off (NULL, or room for n * (N - 1) + 1 words) gets byte offsets into out as
+ * raftq_wire_encode's frame_off, entries n_resp .. n * (N - 1) all holding the total.  resp_counts: n_msgs = n_resp, bytes.
+ * cap must be at least n * (N - 1) * RAFTQ_RESPOND_FRAME_MAX (the largest payload-free frame: 8-byte length, type / to / from of
+ * one byte each, term / log_term / index / commit / group of ten, reject_hint 0, the empty snapshot): below it, or with any array
+ * not page-locked and 16-byte aligned (at_tail, out, resp_off and peer_off included), or N < 2, RAFTQ_EINVAL before anything
+ * is enqueued -- nothing is applied.  The response records are written into the encoder's input in HBM; they never exist in
+ * host memory. */
+#define RAFTQ_OUTF_ANSWERED 0x10u /* result flag: the messages this result calls for are in `out` (built on the device) */
+#define RAFTQ_RESPOND_FRAME_MAX 83u
+int raftq_step_frames_respond(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off /*[n+1]*/, uint64_t n, int tail_appends,
+                              raftq_wire_msg_t* msgs /*[n]*/, raftq_wire_ent_t* ents /*[ents_cap]|NULL*/, uint64_t ents_cap,
+                              const uint64_t* at_tail /*[ceil(G/64)] bitmap | NULL*/, void* out, uint64_t cap,
+                              uint64_t* resp_off /*[n*(N-1)+1] | NULL*/, uint64_t* peer_off /*[N+1]*/,
+                              raftq_wire_counts_t* counts /*inbound, as raftq_step_frames | NULL*/, raftq_wire_counts_t* resp_counts /*| NULL*/);
+
 /* A node's OUTBOUND half of a turn for what it was asked to propose (round 6; raft.go:211-215 -> :227-230: rc.node.Propose ->
  * appendEntry -> bcastAppend -> rc.transport.Send) as ONE submission with one wait: for every record of props[] the leader's
  * appendEntry (lastIndex += n_ents, lastTerm = Term, its own Progress.Match) on the device-resident state, and bcastAppend --

@@ -208,6 +208,13 @@ struct raftq {
   uint32_t wire_chunk_base = 0, wire_chunk_pending = 0;  // the readers' chunk tickets (the head's fourth word), accounted like the tiles'
   bool wire_chunk_unknown = false;           // the last launch had no reader workgroups: how far its chunk ticket got is not known
   unsigned int prop_stamp = 0;               // raftq_propose_frames: the call's stamp (its validation's verdict word holds it when a record was refused)
+  // raftq_step_frames_respond: the walk's response records + the layout's counts (device), and what the walk reads while the
+  // call is on (resp_on): the call's stamp, the caller's at-tail bitmap as the device addresses it
+  void* resp_dev = nullptr;
+  size_t resp_dev_bytes = 0;
+  bool resp_on = false;
+  uint32_t resp_stamp = 0;
+  const uint64_t* resp_at_tail_d = nullptr;
   hipStream_t wire_copy_stream = nullptr;    // RAFTQ_WIRE_SDMA=1 (A/B only): the runtime's copies bring the decoder's input in
   hipEvent_t wire_copy_ev = nullptr;
   // raftq_wal_encode_begin .. _end: enqueued, its totals in wire_pin[8 ..]; `done`: a later wait has covered it and what _end
@@ -279,6 +286,20 @@ void free_wire_state(raftq_t* h);               // raftq_wire.hip's allocations 
 int wire_frames_enqueue(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off, uint64_t n, void* msgs, void* ents,
                         uint64_t ents_cap, void* msgs_d, int tail_appends, void* zero2 /* two device words left zero, or nullptr */);
 int wire_frames_finish(raftq_t* h, const uint64_t* frame_off, uint64_t n, bool have_ents, uint64_t ents_cap, ::raftq_wire_counts* counts);
+// raftq_step_frames_respond (raftq_step.hip): the checks that come before anything is enqueued (every array page-locked and
+// 16-byte aligned, the scratch allocated), then -- behind the Step chain, on the handle's stream -- the layout of the responses
+// and their marshal; RespPlan carries the device views between them.  respond_finish reads the encoder's totals after the wait.
+struct RespPlan {
+  uint64_t n = 0, n_max = 0, cap = 0;  // results, frames the encoder is launched for (n * (N - 1)), out's size
+  void* v_out = nullptr;
+  uint64_t* v_resp_off = nullptr;
+  uint64_t* peer_off = nullptr;        // the caller's (host) array, N + 1 words
+};
+int respond_prepare(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off, const void* msgs, const void* ents,
+                    const uint64_t* at_tail, void* out, uint64_t cap, uint64_t* resp_off, uint64_t* peer_off, uint64_t n, RespPlan* p);
+int respond_enqueue(raftq_t* h, const RespPlan& p);
+int respond_finish(raftq_t* h, const RespPlan& p, ::raftq_wire_counts* resp_counts);
+int respond_pass_ok(raftq_t* h);  // a pass of the marshal whose totals are about to be replaced (a stalled batch's first): it did not give up
 // The wait that ends a call whose results the kernels wrote into page-locked memory themselves (the streaming codecs,
 // raftq_step_frames): a one-thread kernel raises the handle's completion word behind everything enqueued so far and the host
 // polls it (raftq_cycle's wait, raftq_capi.hip wait_turn) -- a stream synchronisation costs 15-20 us more than the word does.

@@ -405,6 +405,17 @@ struct raftq_node {
   std::vector<uint32_t> prop_slot;       // [group] index of the group's record in prop_recs, valid where prop_mark == the turn's epoch
   std::vector<uint32_t> prop_mark;       // [group] epoch | kind: the group proposes this turn through the device (fast) or the host (slow)
   uint64_t prop_cap = 0;                 // upper bound of the device-built frames' bytes, per addressee
+  // RAFTQ_NODE_RESPOND_DEVICE=1 (off by default): the fused inbound round is raftq_step_frames_respond -- the responses and commit
+  // broadcasts its results call for are built and marshalled on the device; apply_result skips only the sends of an ANSWERED
+  // result, and the per-peer slices go onto the queues ahead of the turn's host-built frames, where and when those are published.
+  // at_tail: bit g = this node leads g and every follower's Next is lastIndex + 1 -- set where the fast proposals leave every Next
+  // at the tail, cleared on every other write of a Next or of a leader's log tail.  RAFTQ_NODE_RESPOND_CHECK=1: the bitmap is
+  // re-derived from prog[] before every call and a set bit that is wrong poisons the node (RAFTQ_ESTATE).
+  bool respond_device = false, respond_check = false;
+  PinU64 at_tail;                        // [ceil(G / 64)], page-locked: the walk reads it in place
+  PinBuf resp_out;                       // the device-built frames of this turn's inbound round
+  PinU64 resp_off, resp_peer;            // their byte offsets, peer slices ([N + 1] frame indices)
+  bool resp_pending = false;             // resp_* hold frames not yet on the queues
   bool fuse_inbound = true;       // a turn's frames are decoded AND stepped by one submission (raftq_step_frames) whenever nothing was
                                   // raised locally ahead of them (RAFTQ_NODE_FUSE_INBOUND=0: raftq_wire_decode, then the staged rounds)
   bool broken = false;            // the engine's view of a log and the log itself disagree: advance() ends in ESTATE
@@ -466,6 +477,12 @@ struct raftq_node {
   std::vector<uint64_t> delta_commit;
   uint64_t& next_of(uint64_t g, uint32_t peer) { return prog[(g * N + peer) * 2]; }
   uint64_t& match_of(uint64_t g, uint32_t peer) { return prog[(g * N + peer) * 2 + 1]; }
+  void tail_clear(uint64_t g) {
+    if (respond_device) at_tail.data()[g >> 6] &= ~(1ull << (g & 63));
+  }
+  void tail_set(uint64_t g) {
+    if (respond_device) at_tail.data()[g >> 6] |= 1ull << (g & 63);
+  }
 };
 
 struct PhaseClock {  // accumulates wall time into n->prof[which] when RAFTQ_PROFILE is set
@@ -632,6 +649,7 @@ void note_commit(raftq_node_t* n, Group& g, uint64_t commit) {
 // index.  Optimistic cursor (ProgressStateReplicate): Next jumps past what was sent.
 void send_append(raftq_node_t* n, uint64_t gi, Group& g, uint32_t to) {
   const uint64_t last = g.log.size();
+  n->tail_clear(gi);
   uint64_t& next = n->next_of(gi, to);
   uint64_t nx = std::max<uint64_t>(next, 1);
   if (nx > last + 1) nx = last + 1;
@@ -675,7 +693,10 @@ bool handle_proposal(raftq_node_t* n, uint64_t gi, Group& g, const Entry* ents, 
       }
       g.log.push_back(n->pool, Entry{g.term, at, ents[i].len});
     }
-    if (n_ents) wal_touch(n, gi, g);
+    if (n_ents) {
+      n->tail_clear(gi);
+      wal_touch(n, gi, g);
+    }
     return n_ents != 0;
   }
   if (g.lead != 0 && (uint32_t)(g.lead - 1) != n->self) {  // stepFollower MsgProp: `m.To = r.lead; r.send(m)`
@@ -690,6 +711,7 @@ bool handle_proposal(raftq_node_t* n, uint64_t gi, Group& g, const Entry* ents, 
 // RAFTQ_OUT_APPENDED: Step found the MsgApp on the log's tail and did raftLog.maybeAppend's bookkeeping; the entries
 // themselves go into the log here.  false: they could not be stored (the node poisons itself at the end of the turn).
 bool store_at_tail(raftq_node_t* n, uint64_t gi, Group& g, const raftq_wire_msg_t& m) {
+  n->tail_clear(gi);
   if (m.index != g.log.size()) {  // the engine's tail and the log's have parted: nothing this node says can be trusted
     n->broken = true;
     return false;
@@ -710,6 +732,7 @@ bool store_at_tail(raftq_node_t* n, uint64_t gi, Group& g, const raftq_wire_msg_
 
 // handleAppendEntries on the log's owner, after Step accepted the header (RAFTQ_OUT_APPEND)
 void follower_append(raftq_node_t* n, uint64_t gi, Group& g, const raftq_wire_msg_t& m) {
+  n->tail_clear(gi);
   const raftq_wire_ent_t* ents = n->cur_ents + m.ent_first;
   raftq_wire_msg_t& r = send(n, m.from, gi, RAFTQ_MSG_APP_RESP, g.term);
   if (m.index < g.committed) {  // `if m.Index < r.raftLog.committed { send MsgAppResp{Index: committed} }`
@@ -836,8 +859,13 @@ void apply_result(raftq_node_t* n, const raftq_step_out_t& o, const raftq_wire_m
       n->stats.hard_states++;  // wal.Save(rd.HardState, ...) (raft.go:228)
       wal_touch(n, gi, g);
     }
-    if (o.flags & RAFTQ_OUTF_STEPPED_DOWN) g.leading = false;
+    if (o.flags & RAFTQ_OUTF_STEPPED_DOWN) {
+      g.leading = false;
+      n->tail_clear(gi);
+    }
   }
+  // the device built what this result sends (raftq_step_frames_respond): every state change below still happens, the sends do not
+  const bool answered = (o.flags & RAFTQ_OUTF_ANSWERED) != 0;
   // Step appended the message's entries at the tail itself (RAFTQ_MSGF_ENTRIES): they go into the log BEFORE the commit
   // index it reports is published
   bool stored = true;
@@ -845,13 +873,13 @@ void apply_result(raftq_node_t* n, const raftq_step_out_t& o, const raftq_wire_m
   note_commit(n, g, o.commit);
   switch (o.type) {
     case RAFTQ_OUT_APPENDED:
-      if (stored) send(n, o.to, gi, RAFTQ_MSG_APP_RESP, o.term).index = o.index;  // MsgAppResp{Index: lastnewi}
+      if (stored && !answered) send(n, o.to, gi, RAFTQ_MSG_APP_RESP, o.term).index = o.index;  // MsgAppResp{Index: lastnewi}
       break;
     case RAFTQ_OUT_VOTE_RESP:
-      send(n, o.to, gi, RAFTQ_MSG_VOTE_RESP, o.term).reject = o.reject;
+      if (!answered) send(n, o.to, gi, RAFTQ_MSG_VOTE_RESP, o.term).reject = o.reject;
       break;
     case RAFTQ_OUT_HEARTBEAT_RESP:
-      send(n, o.to, gi, RAFTQ_MSG_HEARTBEAT_RESP, o.term);
+      if (!answered) send(n, o.to, gi, RAFTQ_MSG_HEARTBEAT_RESP, o.term);
       break;
     case RAFTQ_OUT_CAMPAIGN:
       for (uint32_t p = 0; p < n->N; ++p) {
@@ -863,6 +891,7 @@ void apply_result(raftq_node_t* n, const raftq_step_out_t& o, const raftq_wire_m
       break;
     case RAFTQ_OUT_BECAME_LEADER:
       // becomeLeader's appendEntry(pb.Entry{Data: nil}): the engine already counted it
+      n->tail_clear(gi);
       g.log.truncate(o.index - 1);
       g.wal_upto = std::min<uint64_t>(g.wal_upto, g.log.size());
       n->shared_group = ~0ull;
@@ -885,16 +914,24 @@ void apply_result(raftq_node_t* n, const raftq_step_out_t& o, const raftq_wire_m
       if (im.type == RAFTQ_MSG_APP_RESP && im.reject) {
         // Progress.maybeDecrTo: a stale rejection is ignored, else back off to the hint
         if (im.index > match) {
+          n->tail_clear(gi);
           next = std::max<uint64_t>(std::min(im.index, im.reject_hint + 1), match + 1);
           send_append(n, gi, g, o.to);
         }
       } else {
         match = o.index;
-        if (next < o.index + 1) next = o.index + 1;
+        if (next < o.index + 1) {
+          n->tail_clear(gi);
+          next = o.index + 1;
+        }
         if (im.type == RAFTQ_MSG_APP_RESP) {
-          if (o.flags & RAFTQ_OUTF_COMMITTED) bcast_append(n, gi, g);  // `if r.maybeCommit() { r.bcastAppend() }`
+          // `if r.maybeCommit() { r.bcastAppend() }` -- with every Next at the tail: N - 1 empty MsgApps, built on the device when answered
+          if (o.flags & RAFTQ_OUTF_COMMITTED) {
+            if (!answered) bcast_append(n, gi, g);
+          }
           else if (next <= g.log.size()) send_append(n, gi, g, o.to);
         } else if (o.index < g.log.size()) {  // MsgHeartbeatResp: `if pr.Match < lastIndex { sendAppend }`
+          n->tail_clear(gi);
           if (next > o.index + 1) next = o.index + 1;  // whatever was in flight is lost: resend
           send_append(n, gi, g, o.to);
         }
@@ -967,6 +1004,29 @@ int flush_wal_end(raftq_node_t* n, std::unique_lock<std::mutex>& lk) {
   return RAFTQ_OK;
 }
 
+// the inbound round's device-built frames (raftq_step_frames_respond) onto peer p's queue, or every peer's (p = ~0u); the last peer
+// ends what is pending.  Called where the turn's frames are published, after its WAL.
+void publish_responses(raftq_node_t* n, uint32_t only) {
+  if (!n->resp_pending) return;
+  const uint64_t* off = n->resp_off.data();
+  const uint64_t* po = n->resp_peer.data();
+  for (uint32_t p = 0; p < n->N; ++p) {
+    if (only != ~0u && p != only) continue;
+    const uint64_t k0 = po[p], k1 = po[p + 1];
+    if (k1 == k0) continue;
+    PeerQueue& q = n->outbound[p];
+    if (q.bytes.empty()) q.reuse_spares();
+    const uint64_t from = off[k0], base = q.bytes.size();
+    q.bytes.append((const char*)n->resp_out.p + from, (size_t)(off[k1] - from));
+    if (q.ends_ok) {
+      const size_t at = q.ends.size();
+      q.ends.resize(at + (size_t)(k1 - k0));
+      for (uint64_t k = k0; k < k1; ++k) q.ends[at + (k - k0)] = base + (off[k + 1] - from);
+    }
+  }
+  if (only == ~0u || only == n->N - 1) n->resp_pending = false;
+}
+
 // rc.transport.Send(rd.Messages) (raft.go:230) for the whole turn: one batched marshal on the GPU, then
 // every peer's slice of the stream goes onto its queue.  Lock convention as flush_deltas.
 int flush_outbound(raftq_node_t* n, std::unique_lock<std::mutex>& lk) {
@@ -981,7 +1041,21 @@ int flush_outbound(raftq_node_t* n, std::unique_lock<std::mutex>& lk) {
   const size_t n_props = n->prop_recs.count<raftq_prop_t>(), n_pents = n->prop_ents.count<raftq_prop_ent_t>();
   const size_t n_dev = n_props * (n->N - 1);
   cap += n_props ? n->prop_cap * (n->N - 1) : 0;
-  if (nm + n_dev == 0) return RAFTQ_OK;
+  if (nm + n_dev == 0) {
+    if (!n->resp_pending) return RAFTQ_OK;
+    // only device-built responses this turn: the WAL first, then the frames (wal.Save before transport.Send)
+    lk.unlock();
+    int rc;
+    {
+      DevCall dev(n, raftq_node::kPhDevEncode);
+      rc = wal_end_device(n);
+    }
+    if (rc != RAFTQ_OK) return rc;
+    lk.lock();
+    wal_publish(n);
+    publish_responses(n, ~0u);
+    return RAFTQ_OK;
+  }
   if (n->out_oom) {
     lk.unlock();
     return RAFTQ_ENOMEM;
@@ -1047,6 +1121,7 @@ int flush_outbound(raftq_node_t* n, std::unique_lock<std::mutex>& lk) {
   uint32_t run = 0;
   for (uint32_t p = 0; p < n->N; ++p) {
     PeerQueue& q = n->outbound[p];
+    publish_responses(n, p);  // the device-built answers of the inbound round come first
     take(q, first[p], first[p + 1]);
     if (n_props && p != n->self) {
       take(q, nm + (uint64_t)run * n_props, nm + (uint64_t)(run + 1) * n_props);
@@ -1154,6 +1229,7 @@ int flush_wal_begin(raftq_node_t* n, std::unique_lock<std::mutex>& lk) {
 bool log_put(raftq_node_t* n, Group& g, uint64_t index, uint64_t term, const char* data, uint32_t len) {
   if (index == 0 || index > g.log.size() + 1) return false;
   if (index <= g.log.size()) g.log.truncate(index - 1);
+  n->tail_clear((uint64_t)(&g - n->groups.data()));
   const char* at = n->arena.put(data, len);
   if (!at) return false;
   g.log.push_back(n->pool, Entry{term, at, len});
@@ -1189,9 +1265,15 @@ int raftq_node_create(int device, uint64_t n_groups, uint32_t n_peers, uint32_t 
   if (const char* sw = std::getenv("RAFTQ_NODE_SPLIT_WAL")) n->split_wal = std::atoi(sw) != 0;
   if (const char* pd = std::getenv("RAFTQ_NODE_PROPOSE_DEVICE")) n->propose_device = std::atoi(pd) != 0;
   if (n_peers < 2) n->propose_device = false;  // (a single-peer group commits what it appends: the report has to come back)
+  if (const char* rd = std::getenv("RAFTQ_NODE_RESPOND_DEVICE")) n->respond_device = std::atoi(rd) != 0 && n_peers >= 2;
+  if (const char* rk = std::getenv("RAFTQ_NODE_RESPOND_CHECK")) n->respond_check = std::atoi(rk) != 0;
   if (const char* ev = std::getenv("RAFTQ_PROFILE_EVERY")) n->prof_every = std::strtoull(ev, nullptr, 10);
   try {
     n->groups.resize(n_groups);
+    if (n->respond_device) {
+      if (!n->at_tail.resize((n_groups + 63) / 64)) throw std::bad_alloc();
+      std::memset(n->at_tail.data(), 0, n->at_tail.size() * 8);
+    }
     n->outbound.resize(n_peers);
     n->out_lane.resize(n_peers);
     n->tick_list.resize(std::min<uint64_t>(n_groups, 4096));
@@ -1527,6 +1609,7 @@ static int node_advance_impl(raftq_node_t* n, uint64_t* n_published) {
   uint64_t nf = in_off.size() > 1 ? in_off.size() - 1 : 0;
   const raftq_wire_msg_t* wm = nullptr;
   const raftq_step_out_s_t* fused_outs = nullptr;  // != nullptr: round 1 has been stepped, out[i] answers frame i
+  uint64_t resp_frames = 0;                         // frames raftq_step_frames_respond built for this turn
   if (nf) {
     lk.unlock();
     ph.next(raftq_node::kPhDecode);
@@ -1538,8 +1621,35 @@ static int node_advance_impl(raftq_node_t* n, uint64_t* n_published) {
     raftq_wire_ent_t* we = n->turn_ents.as<raftq_wire_ent_t>();
     raftq_wire_counts_t cnt;
     const bool fuse = n->fuse_inbound && local.empty();
-    int rc = fuse ? raftq_step_frames(n->h, in_bytes.p, in_bytes.size, in_off.data(), nf, n->tail_appends ? 1 : 0, out, we, ents_cap, &cnt)
-                  : raftq_wire_decode(n->h, in_bytes.p, in_bytes.size, in_off.data(), nf, out, we, ents_cap, &cnt);
+    int rc;
+    if (fuse && n->respond_device) {
+      // the responses and commit broadcasts on the device as well (raftq_step_frames_respond): room for the worst case
+      const uint64_t n_max = nf * (n->N - 1);
+      if (!n->resp_out.reserve(n_max * RAFTQ_RESPOND_FRAME_MAX) || !n->resp_off.resize(n_max + 1) || !n->resp_peer.resize(n->N + 1))
+        return poison(n, RAFTQ_ENOMEM, "step_frames_respond (page-locked response buffers)");
+      if (n->respond_check) {  // a set bit must be true: this node leads the group and every follower's Next is lastIndex + 1
+        for (uint64_t gi = 0; gi < n->G; ++gi) {
+          if (!((n->at_tail.data()[gi >> 6] >> (gi & 63)) & 1)) continue;
+          const Group& g = n->groups[gi];
+          bool ok = g.leading && g.role == RAFTQ_ROLE_LEADER;
+          for (uint32_t p = 0; ok && p < n->N; ++p)
+            if (p != n->self) ok = n->next_of(gi, p) == g.log.size() + 1;
+          if (!ok) return poison(n, RAFTQ_ESTATE, "respond check: group " + std::to_string(gi) + " is marked at the tail and is not");
+        }
+      }
+      raftq_wire_counts_t rcnt;
+      n->resp_pending = false;
+      rc = raftq_step_frames_respond(n->h, in_bytes.p, in_bytes.size, in_off.data(), nf, n->tail_appends ? 1 : 0, out, we, ents_cap,
+                                     n->at_tail.data(), n->resp_out.p, n_max * RAFTQ_RESPOND_FRAME_MAX, n->resp_off.data(),
+                                     n->resp_peer.data(), &cnt, &rcnt);
+      if (rc == RAFTQ_OK && rcnt.n_msgs) {
+        n->resp_pending = true;  // onto the queues where the turn's frames are published (flush_outbound)
+        resp_frames = rcnt.n_msgs;
+      }
+    } else {
+      rc = fuse ? raftq_step_frames(n->h, in_bytes.p, in_bytes.size, in_off.data(), nf, n->tail_appends ? 1 : 0, out, we, ents_cap, &cnt)
+                : raftq_wire_decode(n->h, in_bytes.p, in_bytes.size, in_off.data(), nf, out, we, ents_cap, &cnt);
+    }
     if ((rc == RAFTQ_OK || rc == RAFTQ_EINVAL) && cnt.n_ents > ents_cap) {
       // more entries than messages + 1024: grow once, decode again (after raftq_step_frames only for the headers: the frames
       // have been stepped, and what the plain decode writes over the records is what Step read minus the flags it was given)
@@ -1558,6 +1668,8 @@ static int node_advance_impl(raftq_node_t* n, uint64_t* n_published) {
     n->cur_ents = we;
     n->cur_bytes = in_bytes.p;
     lk.lock();
+    n->stats.msgs_sent += resp_frames;
+    n->stats.msgs_built_on_device += resp_frames;
   }
   ph.next(raftq_node::kPhInbound);
   // what this turn works through, in order: the locally raised messages, then the inbound ones as they arrived
@@ -1815,6 +1927,7 @@ static int node_advance_impl(raftq_node_t* n, uint64_t* n_published) {
           const uint64_t next = g.log.size() + 1;  // bcastAppend's optimistic cursor
           for (uint32_t p = 0; p < n->N; ++p)
             if (p != n->self) n->next_of(gi, p) = next;
+          n->tail_set(gi);  // every follower at the tail the device's appendEntry leaves
           wal_touch(n, gi, g);
         } else {
           bool grew = false;
@@ -1943,6 +2056,7 @@ static int node_advance_impl(raftq_node_t* n, uint64_t* n_published) {
       const uint64_t next = g.log.size() + 1;
       for (uint32_t p = 0; p < n->N; ++p)
         if (p != n->self) n->next_of(gi, p) = next;
+      n->tail_set(gi);
       wal_touch(n, gi, g);
     }
     n->stats.msgs_sent += n_fast * (n->N - 1);

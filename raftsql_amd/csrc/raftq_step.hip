@@ -76,6 +76,11 @@ NodeArrays node_arrays(raftq_t* h, uint8_t recs = raftqk::kRecsCaller) {
   a.recs = recs;
   a.n_groups = h->G;
   a.self_max = h->self_max;
+  if (h->resp_on) {  // raftq_step_frames_respond: the walks (the list walk, the sorted one, a stalled batch's replay) answer too
+    a.resp = (raftqk::RespRec*)h->resp_dev;
+    a.at_tail = h->resp_at_tail_d;
+    a.resp_stamp = h->resp_stamp;
+  }
   return a;
 }
 
@@ -928,6 +933,71 @@ int raftq_step_frames(raftq_t* h, const void* stream, uint64_t nbytes, const uin
     return rc_dec;
   }
   return rc_step;
+}
+
+int raftq_step_frames_respond(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off, uint64_t n, int tail_appends,
+                              raftq_wire_msg_t* msgs, raftq_wire_ent_t* ents, uint64_t ents_cap, const uint64_t* at_tail, void* out, uint64_t cap,
+                              uint64_t* resp_off, uint64_t* peer_off, raftq_wire_counts_t* counts, raftq_wire_counts_t* resp_counts) {
+  const char* who = "raftq_step_frames_respond";
+  if (int rc = use_device(h)) return rc;
+  if (counts) *counts = raftq_wire_counts_t{0, 0, 0, 0};
+  if (resp_counts) *resp_counts = raftq_wire_counts_t{0, 0, 0, 0};
+  if (h->step_collected != h->step_submitted)
+    return fail(h, RAFTQ_ESTATE, std::string(who) + ": submitted batches are still in flight; collect them first");
+  h->step_last_out = nullptr;
+  h->step_last_n = 0;
+  if (!peer_off) return fail(h, RAFTQ_EINVAL, std::string(who) + ": null argument");
+  if (n == 0) {
+    for (uint32_t p = 0; p <= h->N; ++p) peer_off[p] = 0;
+    if (resp_off) resp_off[0] = 0;
+    return RAFTQ_OK;
+  }
+  if ((!stream && nbytes) || !frame_off || !msgs || !out) return fail(h, RAFTQ_EINVAL, std::string(who) + ": null argument");
+  if (!h->step_msg_flags)
+    return fail(h, RAFTQ_ESTATE, std::string(who) + ": the handle has not opted in to RAFTQ_MSGF_* (raftq_step_set_msg_flags)");
+  if (h->N < 2) return fail(h, RAFTQ_EINVAL, std::string(who) + ": a single-peer group has nobody to answer -- use raftq_step_frames");
+  // the exact worst case: every result a commit broadcast (N - 1 frames) of RAFTQ_RESPOND_FRAME_MAX bytes -- refused before
+  // anything runs, so a call that has stepped never fails for output space
+  const uint64_t n_max = n * (h->N - 1);
+  if (n_max > 0x7ffffffeull || n_max > (((uint64_t)1 << 31) / RAFTQ_RESPOND_FRAME_MAX))
+    return fail(h, RAFTQ_EINVAL, std::string(who) + ": batch too large (n * (N - 1) * RAFTQ_RESPOND_FRAME_MAX must stay within 2^31 bytes)");
+  if (cap < n_max * RAFTQ_RESPOND_FRAME_MAX)
+    return fail(h, RAFTQ_EINVAL, std::string(who) + ": cap is below n * (N - 1) * RAFTQ_RESPOND_FRAME_MAX = " +
+                                     std::to_string(n_max * RAFTQ_RESPOND_FRAME_MAX) + " bytes -- nothing was applied");
+  raftq_detail::RespPlan rp;
+  if (int rc = raftq_detail::respond_prepare(h, stream, nbytes, frame_off, msgs, ents, at_tail, out, cap, resp_off, peer_off, n, &rp)) return rc;
+  // from here on: raftq_step_frames, with the walks answering (node_arrays), then the layout and the marshal behind them
+  h->resp_on = true;
+  WireSrc w{stream, nbytes, frame_off, true, msgs, ents, ents ? ents_cap : 0, tail_appends};
+  int rc = submit_impl(h, nullptr, n, &w, who);
+  if (rc == RAFTQ_OK) rc = raftq_detail::respond_enqueue(h, rp);
+  if (rc != RAFTQ_OK) {
+    h->resp_on = false;
+    return rc;
+  }
+  // one wait for the decode, the walk, the result copy, the layout and the marshal
+  if (hipError_t e = raftq_detail::wait_call(h); e != hipSuccess) {
+    h->resp_on = false;
+    return fail(h, RAFTQ_EHIP, std::string(who) + ": " + hipGetErrorString(e));
+  }
+  const uint64_t replays = h->step_replays;
+  int rc_step = raftq_step_collect(h, nullptr, nullptr);
+  // a stalled batch (a run longer than the list walk takes) was applied by the collect's replay (its own wait): its answers are
+  // laid out and marshalled again (a third) -- the first pass, which found nothing answered, must not have given up either
+  if (rc_step == RAFTQ_OK && h->step_replays != replays) {
+    rc_step = raftq_detail::respond_pass_ok(h);
+    if (rc_step == RAFTQ_OK) rc_step = raftq_detail::respond_enqueue(h, rp);
+    if (rc_step == RAFTQ_OK && raftq_detail::wait_call(h) != hipSuccess) rc_step = fail(h, RAFTQ_EHIP, std::string(who) + ": the replay's marshal failed");
+  }
+  h->resp_on = false;
+  const int rc_dec = raftq_detail::wire_frames_finish(h, frame_off, n, ents != nullptr, ents_cap, counts);
+  if (rc_dec != RAFTQ_OK) {
+    h->step_last_out = nullptr;
+    h->step_last_n = 0;
+    return rc_dec;
+  }
+  if (rc_step != RAFTQ_OK) return rc_step;
+  return raftq_detail::respond_finish(h, rp, resp_counts);
 }
 
 // wait = false (raftq_apply_log_deltas_nowait): the same kernels from a staging area of their own, enqueued and left

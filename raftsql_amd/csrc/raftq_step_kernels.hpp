@@ -89,6 +89,11 @@ struct NodeArrays {
                     // kRecsFrames (raftq_step_frames: the decoder's, with RAFTQ_MSGF_* set by it)
   uint64_t n_groups;
   uint32_t* self_max = nullptr;  // the handle's self-max word (raftq_kernels.hpp): a store that breaks the fact clears it
+  // raftq_step_frames_respond only (nullptr otherwise): the walk writes resp[i] for every message it steps, stamped resp_stamp,
+  // and reads the caller's at-tail bitmap (page-locked host memory, one word per 64 groups; nullptr = all clear)
+  struct RespRec* resp = nullptr;
+  const uint64_t* at_tail = nullptr;
+  uint32_t resp_stamp = 0;
 };
 constexpr uint8_t kRecsCaller = 0, kRecsWire = 1, kRecsFrames = 2;
 
@@ -99,6 +104,17 @@ constexpr uint8_t kOutNone = 0, kOutVoteResp = 1, kOutHeartbeatResp = 2, kOutCam
                   kOutHeld = 11;
 constexpr uint8_t kMsgfEntries = 0x80, kMsgfBarrier = 0x40, kMsgfHold = 0x20, kMsgfSkip = 0x10;  // raftq_msg_t._pad[1]: RAFTQ_MSGF_*
 constexpr uint8_t kFlagHardState = 1, kFlagCommitted = 2, kFlagUpdated = 4, kFlagSteppedDown = 8;
+constexpr uint8_t kFlagAnswered = 0x10;  // RAFTQ_OUTF_ANSWERED: the messages the result calls for were built on the device
+
+// What result i calls for, as the walk lane that stepped it saw the group (raftq_step_frames_respond; raftq_respond_kernels.hpp
+// lays the frames out).  kind = the raftpb type of the message(s) to send, 0 = none built on the device; kMsgApp is the commit
+// broadcast: one empty MsgApp to every peer but self.  Valid only with this call's stamp (stale records read as "none").
+struct RespRec {
+  uint64_t group, term, index, log_term, commit;
+  uint32_t stamp;
+  uint8_t kind, reject, to, pad;
+};
+static_assert(sizeof(RespRec) == 48, "record layout");
 constexpr uint8_t kFollower = 0, kCandidate = 1, kLeader = 2;
 
 // result record i, in the handle's format.  Compact drops group and addressee (= msgs[i].group / .from) and folds
@@ -236,6 +252,9 @@ struct Node {
   uint32_t lst_head, lst_cnt, lst_min;  // the record's list words as loaded (the walk empties them when it stores)
   uint8_t role;
   bool held = false;  // this batch only: a MsgApp with RAFTQ_MSGF_BARRIER was left to the caller -- the group's later messages wait
+  // raftq_step_frames_respond: the caller's at-tail bit as it still holds at this point of the batch, and whether an earlier
+  // result of the group was left to the host (which ends the group's device-answered prefix)
+  bool at_tail = false, host_owns = false;
   // what has to be written to the dense arrays besides the record (which always is, list words emptied)
   uint64_t committed0, first_idx0;
   uint8_t role0;
@@ -251,6 +270,7 @@ struct Node {
     role = role0 = r.role;
 #pragma unroll
     for (int p = 0; p < kMaxPeers; ++p) mt[p] = r.match[p];
+    if (a.at_tail != nullptr) at_tail = ((a.at_tail[g >> 6] >> (g & 63)) & 1ull) != 0;
   }
   // list_reset: the walk hands the group's list back empty (log_deltas_kernel leaves the words as they are)
   __device__ void store(bool list_reset = true) const {
@@ -414,6 +434,46 @@ struct Node {
     }
   }
 
+  // raftq_step_frames_respond: after step(m, o) for batch position i -- what the host's apply_result would send for this result
+  // (raftq_node.cpp), when it is a message of the table in include/raftq_wire.h, as resp[i]; o gets RAFTQ_OUTF_ANSWERED.
+  // The at-tail bit goes with every message that makes the host move some Next away from the tail (a rejection it backs off
+  // for, a heartbeat response below lastIndex, a step-down); a result the host may answer itself ends the group's prefix.
+  __device__ void respond(const MsgRec& m, StepOutRec& o, uint64_t i) {
+    if (a.resp == nullptr) return;
+    if (role != kLeader) at_tail = false;
+    RespRec r;
+    r.group = g; r.term = o.term; r.index = 0; r.log_term = 0; r.commit = 0;
+    r.stamp = a.resp_stamp; r.kind = 0; r.reject = 0; r.to = (uint8_t)m.from; r.pad = 0;
+    if (o.type == kOutProgress) {
+      if (m.type == kMsgAppResp && m.reject) {
+        if (m.index > o.index) at_tail = false;  // Progress.maybeDecrTo: the host backs Next off and resends
+      } else if (m.type == kMsgHeartbeatResp) {
+        if (o.index < last_index) at_tail = false;  // `if pr.Match < lastIndex { sendAppend }`
+      }
+    }
+    if (!host_owns) {
+      switch (o.type) {
+        case kOutAppended: r.kind = kMsgAppResp; r.index = o.index; break;
+        case kOutVoteResp: r.kind = kMsgVoteResp; r.reject = o.reject; break;
+        case kOutHeartbeatResp: r.kind = kMsgHeartbeatResp; break;
+        case kOutProgress:
+          if (m.type == kMsgAppResp && !m.reject) {
+            if (!at_tail) host_owns = true;  // the host knows Next: it may send
+            else if (o.flags & kFlagCommitted) {  // bcastAppend with every follower at the tail: N - 1 empty MsgApps
+              r.kind = kMsgApp; r.index = last_index; r.log_term = last_term; r.commit = committed;
+            }
+          } else if (m.type == kMsgAppResp ? m.index > o.index : o.index < last_index) {
+            host_owns = true;  // a resend
+          }
+          break;
+        case kOutNone: case kOutSkipped: break;
+        default: host_owns = true;  // MsgApp left to the log's owner, a new leader's broadcast, held / deferred messages
+      }
+    }
+    if (r.kind != 0) o.flags |= kFlagAnswered;
+    a.resp[i] = r;
+  }
+
   __device__ void step(const MsgRec& m, StepOutRec& o) {
     const uint64_t term0 = term, commit0 = committed;
     const uint32_t vote0 = vote;
@@ -532,6 +592,7 @@ static __global__ __launch_bounds__(kBlock) void step_kernel(NodeArrays a, const
     const MsgRec m = msgs[i];
     StepOutRec o;
     node.step(m, o);
+    node.respond(m, o, i);
     put_result(out, i, o, compact);
   }
   node.store();
@@ -633,7 +694,9 @@ static __global__ __launch_bounds__(kBlock) void step_lists_kernel(NodeArrays a,
   const uint32_t c = node.lst_cnt;
   if (c == 1) {
     StepOutRec o;
-    node.step(msgs[i], o);
+    const MsgRec m = msgs[i];
+    node.step(m, o);
+    node.respond(m, o, i);
     put_result(out, i, o, compact);
   } else {
     uint32_t pos[kMaxRun];
@@ -651,6 +714,7 @@ static __global__ __launch_bounds__(kBlock) void step_lists_kernel(NodeArrays a,
       const MsgRec m = msgs[pos[k]];
       StepOutRec o;
       node.step(m, o);
+      node.respond(m, o, pos[k]);
       put_result(out, pos[k], o, compact);
     }
   }

@@ -15,6 +15,7 @@
 
 #include "raftq_internal.hpp"
 #include "raftq_propose_kernels.hpp"
+#include "raftq_respond_kernels.hpp"
 #include "raftq_wire_kernels.hpp"
 
 using namespace raftqk;
@@ -270,6 +271,9 @@ void raftq_detail::free_wire_state(raftq_t* h) {
   (void)hipFree(h->wire_out);
   (void)hipFree(h->wire_flags);
   (void)hipFree(h->wire_lb);
+  (void)hipFree(h->resp_dev);
+  h->resp_dev = nullptr;
+  h->resp_dev_bytes = 0;
   if (h->wire_copy_stream) (void)hipStreamDestroy(h->wire_copy_stream);
   if (h->wire_copy_ev) (void)hipEventDestroy(h->wire_copy_ev);
   h->wire_copy_stream = nullptr;
@@ -572,6 +576,133 @@ int raftq_detail::wire_frames_enqueue(raftq_t* h, const void* stream, uint64_t n
   const FrameFilter ff{1u, h->N, h->self_peer, tail_appends ? 1u : 0u, h->G, (unsigned long long*)zero2};
   return decode_streaming_enqueue(h, v_stream, nbytes, v_off, n, v_msgs, v_ents, ents ? ents_cap : 0, (WireMsg*)msgs_d, ff);
 }
+// ---- raftq_step_frames_respond ----------------------------------------------------------------------------------------
+namespace {
+constexpr uint32_t kRespPin = 16;  // the encoder's totals go to wire_pin[16 ..]: [0 .. 3] are the decoder's, [8 ..] a pending WAL encode's
+struct RespScratch {
+  size_t o_blk_cnt, o_blk_off, o_peer_off, bytes;
+};
+RespScratch resp_scratch(uint64_t n) {
+  const uint64_t blocks = (n + kBlock - 1) / kBlock;
+  RespScratch r;
+  r.o_blk_cnt = align256((size_t)n * sizeof(RespRec));
+  r.o_blk_off = r.o_blk_cnt + align256((size_t)blocks * kMaxPeers * 4);
+  r.o_peer_off = r.o_blk_off + align256((size_t)blocks * kMaxPeers * 8);
+  r.bytes = r.o_peer_off + 256;
+  return r;
+}
+}  // namespace
+
+int raftq_detail::respond_prepare(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off, const void* msgs, const void* ents,
+                                  const uint64_t* at_tail, void* out, uint64_t cap, uint64_t* resp_off, uint64_t* peer_off, uint64_t n, RespPlan* p) {
+  const char* who = "raftq_step_frames_respond";
+  if (n > kMaxItems) return fail(h, RAFTQ_EINVAL, std::string(who) + ": batch too large");
+  if (int rc = ensure_pin(h)) return rc;
+  // what raftq_step_frames' decoder takes, and what this call adds: all of it checked here, before anything is enqueued
+  void *v_stream = nullptr, *v_off = nullptr, *v_msgs = nullptr, *v_ents = nullptr, *v_tail = nullptr, *v_out = nullptr, *v_roff = nullptr,
+       *v_poff = nullptr;
+  const bool mapped = (nbytes == 0 || (v_stream = dev_view(stream)) != nullptr) && (v_off = dev_view(frame_off)) != nullptr &&
+                      (v_msgs = dev_view(msgs)) != nullptr && (!ents || (v_ents = dev_view(ents)) != nullptr) &&
+                      (!at_tail || (v_tail = dev_view(at_tail)) != nullptr) && (v_out = dev_view(out)) != nullptr &&
+                      (!resp_off || (v_roff = dev_view(resp_off)) != nullptr) && (v_poff = dev_view(peer_off)) != nullptr;
+  if (!(mapped && nbytes < (1ull << (kLbValueBits - 1)) && aligned16(v_stream) && aligned16(v_off) && aligned16(v_msgs) && aligned16(v_ents) &&
+        aligned16(v_tail) && aligned16(v_out) && aligned16(v_roff) && aligned16(v_poff)))
+    return fail(h, RAFTQ_EINVAL, std::string(who) + ": every array must be page-locked (raftq_host_alloc, hipHostMalloc, hipHostRegister) and "
+                                                    "16-byte aligned -- nothing was applied");
+  const RespScratch rs = resp_scratch(n);
+  if (rs.bytes > h->resp_dev_bytes) {
+    if (h->resp_dev) {
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+      HIPCHK(h, hipFree(h->resp_dev));
+      h->resp_dev = nullptr;
+      h->resp_dev_bytes = 0;
+    }
+    const size_t bytes = std::max(rs.bytes + rs.bytes / 2, (size_t)1 << 20);
+    HIPCHK(h, hipMalloc(&h->resp_dev, bytes));
+    HIPCHK(h, hipMemsetAsync(h->resp_dev, 0, bytes, h->stream));  // stamp 0: no call's
+    h->resp_dev_bytes = bytes;
+  }
+  p->n = n;
+  p->n_max = n * (h->N - 1);
+  p->cap = std::min<uint64_t>(cap, p->n_max * RAFTQ_RESPOND_FRAME_MAX);  // what the encoder may write: never more than the worst case
+  // everything the layout and the marshal will need is allocated NOW, before anything is stepped: a call that has stepped cannot
+  // fail for memory (the calls behind the step find the control block, the scratch and the output buffer big enough)
+  if (p->n_max != 0) {
+    const uint32_t n_tiles = blocks_for(p->n_max);
+    TileCtl ctl;
+    if (int rc = tile_ctl(h, n_tiles, &ctl)) return rc;
+    Carver fc;
+    const void* const src[3] = {nullptr, nullptr, nullptr};
+    const uint64_t sizes[3] = {0, 0, 0};
+    const uint64_t extra[3] = {p->n_max * sizeof(WireMsg), 0, 0};
+    (void)plan_feed(fc, src, sizes, h->wire_lb_tiles, 48u, extra);
+    if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, fc.off)) return rc;
+    if (int rc = grow(h, &h->wire_out, &h->wire_out_bytes, p->cap + 16)) return rc;
+  }
+  if (++h->resp_stamp == 0) h->resp_stamp = 1;
+  h->resp_at_tail_d = (const uint64_t*)v_tail;
+  p->v_out = v_out;
+  p->v_resp_off = (uint64_t*)v_roff;
+  p->peer_off = peer_off;
+  return RAFTQ_OK;
+}
+
+int raftq_detail::respond_enqueue(raftq_t* h, const RespPlan& p) {
+  const RespScratch rs = resp_scratch(p.n);
+  uint8_t* rd = (uint8_t*)h->resp_dev;
+  const uint32_t blocks = blocks_for(p.n);
+  RespLayout L{(const RespRec*)rd, p.n, h->N, h->self_peer, h->resp_stamp, (uint32_t*)(rd + rs.o_blk_cnt), (uint64_t*)(rd + rs.o_blk_off),
+               (uint64_t*)(rd + rs.o_peer_off)};
+  hipLaunchKernelGGL(resp_count_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L);
+  hipLaunchKernelGGL(resp_scan_kernel, dim3(1), dim3(kBlock), 0, h->stream, L, blocks);
+  HIPCHK(h, hipGetLastError());
+  if (p.n_max != 0) {
+    // the records go where the encoder's readers would have put a caller's messages: the scratch behind an empty feed
+    const uint32_t n_tiles = blocks_for(p.n_max);
+    const unsigned workers = fused_grid(n_tiles);
+    Carver fc;
+    const void* const src[3] = {nullptr, nullptr, nullptr};
+    const uint64_t sizes[3] = {0, 0, 0};
+    const uint64_t extra[3] = {p.n_max * sizeof(WireMsg), 0, 0};
+    TileCtl ctl;
+    if (int rc = tile_ctl(h, n_tiles, &ctl)) return rc;
+    FeedPlan plan = plan_feed(fc, src, sizes, h->wire_lb_tiles, 48u, extra);
+    if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, fc.off)) return rc;
+    if (int rc = grow(h, &h->wire_out, &h->wire_out_bytes, p.cap + 16)) return rc;
+    if (int rc = bind_feed(h, plan, (uint8_t*)h->wire_dev, ctl.status[kLbFlags])) return rc;
+    WireMsg* enc = (WireMsg*)plan.in.seg[0].dst;
+    hipLaunchKernelGGL(resp_scatter_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, enc, p.n_max);
+    hipLaunchKernelGGL(wire_enc_fused_kernel, dim3(plan.in.readers + workers), dim3(kBlock), 0, h->stream, plan.in, p.n_max, (uint64_t)0, (uint64_t)0,
+                       (uint8_t*)h->wire_out, (uint8_t*)p.v_out, p.cap, p.v_resp_off, ctl, h->wire_pin_d + kRespPin, (const unsigned int*)nullptr, 0u);
+    HIPCHK(h, hipGetLastError());
+    tile_ctl_launched(h, n_tiles, workers);
+  }
+  // the slices' bounds: a copy of the runtime's (no new kernel writes host memory)
+  HIPCHK(h, hipMemcpyAsync(p.peer_off, rd + rs.o_peer_off, (size_t)(h->N + 1) * 8, hipMemcpyDeviceToHost, h->stream));
+  return RAFTQ_OK;
+}
+
+int raftq_detail::respond_pass_ok(raftq_t* h) { return tile_ctl_check(h, "raftq_step_frames_respond", kRespPin); }
+
+int raftq_detail::respond_finish(raftq_t* h, const RespPlan& p, raftq_wire_counts_t* resp_counts) {
+  const uint64_t frames = p.peer_off[h->N];
+  uint64_t bytes = 0;
+  if (p.n_max != 0) {
+    if (int rc = tile_ctl_check(h, "raftq_step_frames_respond", kRespPin)) return rc;
+    bytes = h->wire_pin[kRespPin];
+    // every record past the last frame is a filler the encoder refuses; any other refusal, or bytes beyond the bound, is a bug here
+    if (h->wire_pin[kRespPin + 1] != p.n_max - frames || bytes > p.cap)
+      return fail(h, RAFTQ_EHIP, "raftq_step_frames_respond: the marshal of the responses disagrees with their layout; the output is not valid");
+  }
+  if (resp_counts) {
+    resp_counts->n_msgs = frames;
+    resp_counts->n_ents = 0;
+    resp_counts->n_malformed = 0;
+    resp_counts->bytes = bytes;
+  }
+  return RAFTQ_OK;
+}
+
 int raftq_detail::wire_frames_finish(raftq_t* h, const uint64_t* frame_off, uint64_t n, bool have_ents, uint64_t ents_cap, raftq_wire_counts_t* counts) {
   return decode_streaming_finish(h, "raftq_step_frames", frame_off, n, have_ents, ents_cap, false, counts);
 }

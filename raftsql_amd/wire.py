@@ -33,6 +33,8 @@ WAL_REC_DT = np.dtype([("group", "<u8"), ("term", "<u8"), ("index", "<u8"), ("da
                        ("vote", "<u4"), ("crc", "<u4"), ("kind", "u1"), ("entry_type", "u1"), ("flags", "u1"),
                        ("_pad", "u1")])
 assert WIRE_MSG_DT.itemsize == 64 and WIRE_ENT_DT.itemsize == 32 and WAL_REC_DT.itemsize == 48
+OUTF_ANSWERED = 0x10  # result flag of raftq_step_frames_respond: the messages the result calls for were built on the device
+RESPOND_FRAME_MAX = 83  # bytes of the largest payload-free frame: cap >= n * (N - 1) * RESPOND_FRAME_MAX
 
 
 def _u8(b) -> np.ndarray:
@@ -139,6 +141,39 @@ class WireEngine(NodeEngine):
             outs = outs.copy()
         got_ents = ents[: min(int(c.n_ents), len(ents))] if ents is not None else np.zeros(0, WIRE_ENT_DT)
         return msgs[:n], got_ents, outs, c
+
+    def respond_cap(self, n: int) -> int:
+        """the `out` size raftq_step_frames_respond needs for n frames (the exact worst case)"""
+        return int(n) * (self.n_peers - 1) * RESPOND_FRAME_MAX
+
+    def step_frames_respond(self, stream: np.ndarray, frame_off: np.ndarray, msgs: np.ndarray, ents: np.ndarray | None, at_tail: np.ndarray | None,
+                            out: np.ndarray, resp_off: np.ndarray | None, peer_off: np.ndarray, tail_appends: bool = True, copy: bool = True):
+        """raftq_step_frames_respond: step_frames + the responses and commit broadcasts its results call for, built and marshalled on
+        the device, one submission and one wait.  All arrays page-locked (engine.pinned_empty / pinned_copy); at_tail: uint64
+        [ceil(G / 64)] or None; out: uint8 of at least respond_cap(n) bytes; resp_off: uint64 [n * (N - 1) + 1] or None; peer_off:
+        uint64 [N + 1].  -> (msgs[:n], ents, outs, response bytes (a view of out), resp_off[:n_resp + 1] | None, peer_off, counts,
+        resp_counts)"""
+        n = len(frame_off) - 1
+        assert stream.dtype == np.uint8 and frame_off.dtype == np.uint64 and msgs.dtype == WIRE_MSG_DT and len(msgs) >= n
+        assert out.dtype == np.uint8 and peer_off.dtype == np.uint64 and len(peer_off) >= self.n_peers + 1
+        assert resp_off is None or (resp_off.dtype == np.uint64 and len(resp_off) >= n * (self.n_peers - 1) + 1)
+        assert at_tail is None or (at_tail.dtype == np.uint64 and len(at_tail) >= (self.n_groups + 63) // 64)
+        c, rc_ = _lib.WireCounts(), _lib.WireCounts()
+        self._chk(self._lib.raftq_step_frames_respond(
+            self._h, stream.ctypes.data if len(stream) else None, len(stream), frame_off.ctypes.data, n, 1 if tail_appends else 0,
+            msgs.ctypes.data, ents.ctypes.data if ents is not None else None, len(ents) if ents is not None else 0,
+            at_tail.ctypes.data if at_tail is not None else None, out.ctypes.data, len(out),
+            resp_off.ctypes.data if resp_off is not None else None, peer_off.ctypes.data, C.byref(c), C.byref(rc_)))
+        p, k = C.c_void_p(None), C.c_uint64(0)
+        dt, fn = self._results_form()
+        self._chk(fn(self._h, C.byref(p), C.byref(k)))
+        outs = np.frombuffer((C.c_char * (k.value * dt.itemsize)).from_address(p.value), dtype=dt, count=k.value) if k.value else np.zeros(0, dt)
+        if copy:
+            outs = outs.copy()
+        got_ents = ents[: min(int(c.n_ents), len(ents))] if ents is not None else np.zeros(0, WIRE_ENT_DT)
+        n_resp = int(rc_.n_msgs)
+        return (msgs[:n], got_ents, outs, out[: int(rc_.bytes)], resp_off[: n_resp + 1] if resp_off is not None else None,
+                peer_off[: self.n_peers + 1], c, rc_)
 
     def propose_frames(self, props: np.ndarray, prop_ents: np.ndarray, msgs: np.ndarray, ents: np.ndarray, pool: np.ndarray, out: np.ndarray,
                        off: np.ndarray | None = None):
