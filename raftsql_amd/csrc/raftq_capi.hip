@@ -133,31 +133,31 @@ hipError_t launch_n(const SweepLaunch& L, unsigned flags, int nt, hipStream_t s)
 // the segmented turn's sweep (sweep_segments_kernel): commit-only sweeps of one handle
 template <int N>
 hipError_t launch_segments_n(const SweepArgs& a, uint32_t n_tiles, bool gated, int nt, Advance16* list, unsigned int* counts_host, unsigned int* counts_dev,
-                             hipStream_t s, const Arrival& ar) {
+                             hipStream_t s) {
   const dim3 grid(n_tiles), block(kBlock);
   if (gated) {
-    if (nt == 3) hipLaunchKernelGGL((sweep_segments_kernel<N, kGPL, true, kLdNT | kStNT>), grid, block, 0, s, a, list, counts_host, counts_dev, ar);
-    else if (nt == 1) hipLaunchKernelGGL((sweep_segments_kernel<N, kGPL, true, kLdNT>), grid, block, 0, s, a, list, counts_host, counts_dev, ar);
-    else hipLaunchKernelGGL((sweep_segments_kernel<N, kGPL, true, 0>), grid, block, 0, s, a, list, counts_host, counts_dev, ar);
+    if (nt == 3) hipLaunchKernelGGL((sweep_segments_kernel<N, kGPL, true, kLdNT | kStNT>), grid, block, 0, s, a, list, counts_host, counts_dev);
+    else if (nt == 1) hipLaunchKernelGGL((sweep_segments_kernel<N, kGPL, true, kLdNT>), grid, block, 0, s, a, list, counts_host, counts_dev);
+    else hipLaunchKernelGGL((sweep_segments_kernel<N, kGPL, true, 0>), grid, block, 0, s, a, list, counts_host, counts_dev);
   } else {
-    if (nt == 3) hipLaunchKernelGGL((sweep_segments_kernel<N, kGPL, false, kLdNT | kStNT>), grid, block, 0, s, a, list, counts_host, counts_dev, ar);
-    else if (nt == 1) hipLaunchKernelGGL((sweep_segments_kernel<N, kGPL, false, kLdNT>), grid, block, 0, s, a, list, counts_host, counts_dev, ar);
-    else hipLaunchKernelGGL((sweep_segments_kernel<N, kGPL, false, 0>), grid, block, 0, s, a, list, counts_host, counts_dev, ar);
+    if (nt == 3) hipLaunchKernelGGL((sweep_segments_kernel<N, kGPL, false, kLdNT | kStNT>), grid, block, 0, s, a, list, counts_host, counts_dev);
+    else if (nt == 1) hipLaunchKernelGGL((sweep_segments_kernel<N, kGPL, false, kLdNT>), grid, block, 0, s, a, list, counts_host, counts_dev);
+    else hipLaunchKernelGGL((sweep_segments_kernel<N, kGPL, false, 0>), grid, block, 0, s, a, list, counts_host, counts_dev);
   }
   return hipGetLastError();
 }
 hipError_t launch_segments(uint32_t N, const SweepArgs& a, uint32_t n_tiles, bool gated, int nt, Advance16* list, unsigned int* counts_host,
-                           unsigned int* counts_dev, hipStream_t s, const Arrival& ar) {
+                           unsigned int* counts_dev, hipStream_t s) {
   switch (N) {
-    case 1: return launch_segments_n<1>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s, ar);
-    case 2: return launch_segments_n<2>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s, ar);
-    case 3: return launch_segments_n<3>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s, ar);
-    case 4: return launch_segments_n<4>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s, ar);
-    case 5: return launch_segments_n<5>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s, ar);
-    case 6: return launch_segments_n<6>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s, ar);
-    case 7: return launch_segments_n<7>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s, ar);
-    case 8: return launch_segments_n<8>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s, ar);
-    case 9: return launch_segments_n<9>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s, ar);
+    case 1: return launch_segments_n<1>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s);
+    case 2: return launch_segments_n<2>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s);
+    case 3: return launch_segments_n<3>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s);
+    case 4: return launch_segments_n<4>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s);
+    case 5: return launch_segments_n<5>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s);
+    case 6: return launch_segments_n<6>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s);
+    case 7: return launch_segments_n<7>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s);
+    case 8: return launch_segments_n<8>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s);
+    case 9: return launch_segments_n<9>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s);
     default: return hipErrorInvalidValue;
   }
 }
@@ -285,21 +285,10 @@ inline void publish_ingest(const raftq_t* h) {
 #endif
 }
 
-}  // namespace
 // The buffers a kernel writes for the host to read while the kernel may still be running (the advance list, the totals,
-// the completion flag) are fine-grained: the device's stores go out over PCIe as they are issued instead of sitting in
-// its L2 until the end-of-kernel write-back.  Stated explicitly -- without the flag the choice is the runtime's
-// (HIP_HOST_COHERENT).  RAFTQ_HOST_COHERENT=0 leaves it to the runtime (A/B).
-unsigned raftq_detail::host_coherence_flag() {
-  static const unsigned f = [] {
-    const char* e = std::getenv("RAFTQ_HOST_COHERENT");
-    return e && e[0] == '0' ? 0u : (unsigned)hipHostMallocCoherent;
-  }();
-  return f;
-}
-using raftq_detail::host_coherence_flag;
-namespace {
-
+// the completion flag) are allocated hipHostMallocCoherent (fine-grained): the device's stores go out over PCIe as they are
+// issued instead of sitting in its L2 until the end-of-kernel write-back.  Stated explicitly -- without the flag the choice
+// is the runtime's (HIP_HOST_COHERENT).
 int ensure_adv(raftq_t* h, uint64_t entries) {
   if (entries <= h->adv_cap) return RAFTQ_OK;
   uint64_t want = std::max<uint64_t>(entries, h->adv_cap * 2);
@@ -310,7 +299,7 @@ int ensure_adv(raftq_t* h, uint64_t entries) {
     h->adv_h = h->adv_d = nullptr;
     h->adv_cap = 0;
   }
-  HIPCHK(h, hipHostMalloc((void**)&h->adv_h, want * sizeof(Advance), hipHostMallocMapped | host_coherence_flag()));
+  HIPCHK(h, hipHostMalloc((void**)&h->adv_h, want * sizeof(Advance), hipHostMallocMapped | hipHostMallocCoherent));
   HIPCHK(h, hipHostGetDevicePointer((void**)&h->adv_d, h->adv_h, 0));
   h->adv_cap = want;
   return RAFTQ_OK;
@@ -451,14 +440,13 @@ int raftq_create(int device, uint64_t n_groups, uint32_t n_peers, raftq_t** out)
     if ((rc = alloc((void**)&h->changed_bits, h->gpad / 8))) break;
     if ((rc = alloc((void**)&h->partials, h->max_partials * sizeof(uint4)))) break;
     if ((rc = alloc((void**)&h->offsets, (h->max_partials + 1) * 8))) break;
-    if ((rc = alloc((void**)&h->compact_arrived, 64))) break;
     // the self-max word (raftq_kernels.hpp): every row is zero, so row 0 (the default self slot) is the largest
     if ((rc = alloc((void**)&h->self_max, 64))) break;
     e = hipMemsetD32Async((hipDeviceptr_t)h->self_max, (int)(kSelfMaxValid | 0u), 1, h->stream);
     if (e != hipSuccess) { rc = fail(h, RAFTQ_EHIP, std::string("hipMemsetD32Async: ") + hipGetErrorString(e)); break; }
     e = hipHostMalloc((void**)&h->h_partials, h->max_partials * sizeof(uint4), hipHostMallocDefault);
     if (e != hipSuccess) { rc = fail(h, RAFTQ_ENOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(e)); break; }
-    e = hipHostMalloc((void**)&h->h_total, 64, hipHostMallocMapped | host_coherence_flag());
+    e = hipHostMalloc((void**)&h->h_total, 64, hipHostMallocMapped | hipHostMallocCoherent);
     if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&h->d_total, h->h_total, 0);
     if (e != hipSuccess) { rc = fail(h, RAFTQ_ENOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(e)); break; }
     e = hipEventCreate(&h->ev0);
@@ -508,7 +496,6 @@ void raftq_destroy(raftq_t* h) {
   (void)hipFree(h->seg_d);
   if (h->seg_h) (void)hipHostFree(h->seg_h);
   (void)hipFree(h->offsets);
-  (void)hipFree(h->compact_arrived);
   (void)hipFree(h->self_max);
   (void)hipFree(h->claim);
   (void)hipFree(h->delta_dev);
@@ -528,7 +515,6 @@ void raftq_destroy(raftq_t* h) {
   if (h->tl_h) (void)hipHostFree(h->tl_h);
   if (h->h_partials) (void)hipHostFree(h->h_partials);
   if (h->h_total) (void)hipHostFree(h->h_total);
-  if (h->arrive_count) (void)hipFree(h->arrive_count);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->many_aux) {
@@ -855,18 +841,10 @@ int raftq_step_async(raftq_t* h, unsigned flags) {
 // and one auxiliary stream (fork once, join once): 11.97 -> 10.58 us per launch, read 0.547 -> 0.619 of 8 TB/s
 // (profiles/r04/single_launch_ab.jsonl; four streams, 512-group tiles and hipGraph replay are all within noise of, or
 // slower than, the plain loop).  Only for pairwise distinct handles: the same handle twice is a dependency chain.
-// RAFTQ_MANY_STREAMS=1 keeps everything on the one stream (A/B).
-static bool many_alternates() {
-  static const bool on = [] {
-    const char* e = std::getenv("RAFTQ_MANY_STREAMS");
-    return !(e && e[0] == '1' && e[1] == 0);
-  }();
-  return on;
-}
 
 int raftq_sweep_many_async(raftq_t* const* handles, uint32_t n, unsigned flags) {
   if (!handles && n) return fail(nullptr, RAFTQ_EINVAL, "raftq_sweep_many_async: null handle array");
-  bool alternate = n >= 2 && many_alternates();
+  bool alternate = n >= 2;
   for (uint32_t i = 0; alternate && i < n; ++i) {
     if (!handles[i] || handles[i]->stream != handles[0]->stream || handles[i]->device != handles[0]->device) alternate = false;
     for (uint32_t j = 0; alternate && j < i; ++j)
@@ -1016,10 +994,7 @@ int raftq_detail::ensure_tick_state(raftq_t* h) {
 }
 
 static int ensure_tick_offsets2(raftq_t* h, uint64_t nw);
-static int flag_mode();
 static hipError_t wait_turn(raftq_t* h, uint64_t flag_epoch, int kind = 0);
-static int flag_mode();
-static int ensure_arrive(raftq_t* h);
 
 extern "C" {
 
@@ -1145,7 +1120,7 @@ int raftq_tick_collect_lists(raftq_t* h, unsigned flags, uint64_t hup_cap, uint6
       h->tl_bytes = 0;
     }
     const uint64_t want = std::max<uint64_t>(need, 1 << 16);
-    HIPCHK(h, hipHostMalloc((void**)&h->tl_h, want, hipHostMallocMapped | host_coherence_flag()));
+    HIPCHK(h, hipHostMalloc((void**)&h->tl_h, want, hipHostMallocMapped | hipHostMallocCoherent));
     HIPCHK(h, hipHostGetDevicePointer((void**)&h->tl_d, h->tl_h, 0));
     h->tl_bytes = want;
   }
@@ -1166,72 +1141,46 @@ int raftq_tick_collect_lists(raftq_t* h, unsigned flags, uint64_t hup_cap, uint6
   uint32_t* const hup_d = h->tl_d;
   uint32_t* const beat_d = h->tl_d + beat_at;
   uint64_t* const map_d = (uint64_t*)((uint8_t*)h->tl_d + map_off);
-  // blocks of 1,024 groups per workgroup of the lists kernel: 1.  Four (runs of ~1,600 ids instead of ~400 at the bench's density,
-  // RAFTQ_TICK_LISTS_BPW=4, read per call) measured no better: 47.1 against 46.5 us a call -- 1.6 MB of ids take the link 34 us
-  // however they are cut
-  int bpw = 1;
-  if (const char* e = std::getenv("RAFTQ_TICK_LISTS_BPW")) bpw = std::atoi(e) == 4 ? 4 : 1;
-  const uint64_t per_wg = (uint64_t)kWaves * bpw;
-  const dim3 grid((unsigned)((nw + per_wg - 1) / per_wg));
+  // one block of 1,024 groups per workgroup of the lists kernel.  Four (runs of ~1,600 ids instead of ~400 at the bench's density)
+  // measured no better: 47.1 against 46.5 us a call -- 1.6 MB of ids take the link 34 us however they are cut
+  const dim3 grid((unsigned)((nw + kWaves - 1) / kWaves));
   // the completion word: a one-thread kernel behind the lists (only a kernel boundary orders eight XCDs' stores to host memory
-  // before it -- raftq_cycle's finding), polled by the host; RAFTQ_CYCLE_FLAG=arrive: the lists kernel's last workgroup to arrive
-  // raises it itself, =packet: the runtime's write-value packet; the blocking wait where the word cannot be had
-  uint64_t epoch = 0;
-  Arrival ar{nullptr, nullptr, 0};
-  if (h->stream_write_ok) {
-    epoch = ++h->compact_epoch;
-    if ((uint32_t)epoch == 0) epoch = ++h->compact_epoch;
-    h->flag_mask = ~0ull;
-    if (flag_mode() == 3) {
-      if (int rc = ensure_arrive(h)) return rc;
-      epoch &= 0xffffffffull;  // (the arrival form's word carries 32 bits of epoch)
-      ar = Arrival{(unsigned long long*)(h->d_total + 3), h->arrive_count, (uint32_t)epoch};
-    }
-  }
-#define RAFTQ_TICK_LISTS_LAUNCH(BM, B)                                                                                                       \
-  hipLaunchKernelGGL((tick_lists32_kernel<BM, B>), grid, dim3(kBlock), 0, h->stream, (const uint64_t*)h->hup_bits, (const uint64_t*)h->beat_bits, \
-                     (const uint4*)h->tick_partials, nw, hup_d, cap_h, beat_d, cap_b, map_d, h->d_total, off_h, off_b, ar)
-  if (bitmap) {
-    if (bpw == 1) RAFTQ_TICK_LISTS_LAUNCH(true, 1);
-    else RAFTQ_TICK_LISTS_LAUNCH(true, 4);
-  } else {
-    if (bpw == 1) RAFTQ_TICK_LISTS_LAUNCH(false, 1);
-    else RAFTQ_TICK_LISTS_LAUNCH(false, 4);
-  }
-#undef RAFTQ_TICK_LISTS_LAUNCH
+  // before it -- raftq_cycle's finding), polled by the host
+  uint64_t epoch = ++h->compact_epoch;
+  if ((uint32_t)epoch == 0) epoch = ++h->compact_epoch;
+  h->flag_mask = ~0ull;
+  if (bitmap)
+    hipLaunchKernelGGL((tick_lists32_kernel<true>), grid, dim3(kBlock), 0, h->stream, (const uint64_t*)h->hup_bits, (const uint64_t*)h->beat_bits,
+                       (const uint4*)h->tick_partials, nw, hup_d, cap_h, beat_d, cap_b, map_d, h->d_total, off_h, off_b);
+  else
+    hipLaunchKernelGGL((tick_lists32_kernel<false>), grid, dim3(kBlock), 0, h->stream, (const uint64_t*)h->hup_bits, (const uint64_t*)h->beat_bits,
+                       (const uint4*)h->tick_partials, nw, hup_d, cap_h, beat_d, cap_b, map_d, h->d_total, off_h, off_b);
   HIPCHK(h, hipGetLastError());
-  if (epoch && flag_mode() == 1) {
-    hipLaunchKernelGGL(raise_flag_kernel, dim3(1), dim3(64), 0, h->stream, h->d_total + 3, epoch);
-    HIPCHK(h, hipGetLastError());
-  } else if (epoch && flag_mode() == 2 && hipStreamWriteValue64(h->stream, (void*)(h->d_total + 3), epoch, 0) != hipSuccess) {
-    (void)hipGetLastError();
-    epoch = 0;  // not supported here: the blocking wait
-  }
+  hipLaunchKernelGGL(raise_flag_kernel, dim3(1), dim3(64), 0, h->stream, h->d_total + 3, epoch);
+  HIPCHK(h, hipGetLastError());
   HIPCHK(h, wait_turn(h, epoch, 1));
-  if (epoch) {
-    // RAFTQ_CYCLE_CHECK=1 (tests, soaks): what the host reads when the word lands -- the two totals, the ids, the bitmap -- must be
-    // what it reads after a full stream synchronisation
-    static const bool check = [] { const char* e = std::getenv("RAFTQ_CYCLE_CHECK"); return e && e[0] == '1'; }();
-    if (check) {
-      auto digest = [&]() {
-        const volatile uint64_t* tot = (const volatile uint64_t*)h->h_total;
-        const uint64_t t0 = tot[0], t1 = tot[1];
-        uint64_t d = (t0 * 0x9E3779B97F4A7C15ull) ^ t1;
-        const volatile uint32_t* ids = (const volatile uint32_t*)h->tl_h;
-        const uint64_t nh = std::min<uint64_t>(t0, cap_h), nb = std::min<uint64_t>(t1, cap_b);
-        for (uint64_t i = 0; i < nh; ++i) d = (d ^ ids[i]) * 0xBF58476D1CE4E5B9ull;
-        for (uint64_t i = 0; i < nb; ++i) d = (d ^ ids[beat_at + i]) * 0xBF58476D1CE4E5B9ull;
-        if (bitmap) {
-          const volatile uint64_t* mw = (const volatile uint64_t*)((const uint8_t*)h->tl_h + map_off);
-          for (uint64_t i = 0; i < h->gpad / 64; ++i) d = (d ^ mw[i]) * 0xBF58476D1CE4E5B9ull;
-        }
-        return d;
-      };
-      const uint64_t at_flag = digest();
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      if (digest() != at_flag)
-        return fail(h, RAFTQ_EHIP, "raftq_tick_collect_lists: the completion word arrived before the lists it announces (RAFTQ_CYCLE_CHECK)");
-    }
+  // RAFTQ_CYCLE_CHECK=1 (tests, soaks): what the host reads when the word lands -- the two totals, the ids, the bitmap -- must be
+  // what it reads after a full stream synchronisation
+  static const bool check = [] { const char* e = std::getenv("RAFTQ_CYCLE_CHECK"); return e && e[0] == '1'; }();
+  if (check) {
+    auto digest = [&]() {
+      const volatile uint64_t* tot = (const volatile uint64_t*)h->h_total;
+      const uint64_t t0 = tot[0], t1 = tot[1];
+      uint64_t d = (t0 * 0x9E3779B97F4A7C15ull) ^ t1;
+      const volatile uint32_t* ids = (const volatile uint32_t*)h->tl_h;
+      const uint64_t nh = std::min<uint64_t>(t0, cap_h), nb = std::min<uint64_t>(t1, cap_b);
+      for (uint64_t i = 0; i < nh; ++i) d = (d ^ ids[i]) * 0xBF58476D1CE4E5B9ull;
+      for (uint64_t i = 0; i < nb; ++i) d = (d ^ ids[beat_at + i]) * 0xBF58476D1CE4E5B9ull;
+      if (bitmap) {
+        const volatile uint64_t* mw = (const volatile uint64_t*)((const uint8_t*)h->tl_h + map_off);
+        for (uint64_t i = 0; i < h->gpad / 64; ++i) d = (d ^ mw[i]) * 0xBF58476D1CE4E5B9ull;
+      }
+      return d;
+    };
+    const uint64_t at_flag = digest();
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (digest() != at_flag)
+      return fail(h, RAFTQ_EHIP, "raftq_tick_collect_lists: the completion word arrived before the lists it announces (RAFTQ_CYCLE_CHECK)");
   }
   *n_hup = h->tl_n_hup = h->h_total[0];
   *n_beat = h->tl_n_beat = h->h_total[1];
@@ -1337,22 +1286,8 @@ int raftq_campaign(raftq_t* h, const uint64_t* groups, uint64_t n, uint32_t self
 // scan-free compaction of the last RAFTQ_SWEEP_CHANGED sweep (compact_changed_kernel computes its own offsets):
 // total and up to `take_cap` entries go straight into pinned host memory.  want_flag: also publish a completion
 // flag the host can poll (its value is left in h->compact_epoch_armed): a one-thread kernel of ours behind the
-// compaction (default), or the runtime's stream write-value packet (RAFTQ_CYCLE_FLAG=packet: a 3.4 us kernel that
-// starts 5 us after the compaction ends, profiles/r03/cycle_kernel_trace_before.txt).
-static int flag_mode() {  // 1 = raise_flag_kernel, 2 = write-value packet, 3 = the last workgroup to arrive raises it (where a kernel can: the segmented turn, the tick lists)
-  static const int m = [] {
-    const char* e = std::getenv("RAFTQ_CYCLE_FLAG");
-    return e && std::strcmp(e, "packet") == 0 ? 2 : e && std::strcmp(e, "arrive") == 0 ? 3 : 1;
-  }();
-  return m;
-}
-// the arrival counter of mode 3: a device word of the handle, zero between kernels
-static int ensure_arrive(raftq_t* h) {
-  if (h->arrive_count) return RAFTQ_OK;
-  HIPCHK(h, hipMalloc((void**)&h->arrive_count, 64));
-  HIPCHK(h, hipMemsetAsync(h->arrive_count, 0, 64, h->stream));
-  return RAFTQ_OK;
-}
+// compaction.  (The runtime's stream write-value packet was measured instead: a 3.4 us kernel that starts 5 us after the
+// compaction ends, profiles/r03/cycle_kernel_trace_before.txt; equal or slower in round 6's A/B, profiles/r06/flag_ab.txt.)
 
 template <typename Adv>
 static int enqueue_collect(raftq_t* h, uint64_t take_cap, bool want_flag) {
@@ -1385,29 +1320,23 @@ static int enqueue_collect(raftq_t* h, uint64_t take_cap, bool want_flag) {
   }
   HIPCHK(h, hipGetLastError());
   h->compact_epoch_armed = 0;
-  if (want_flag && h->stream_write_ok) {
+  if (want_flag) {
     const uint64_t epoch = ++h->compact_epoch;
-    if (flag_mode() == 1) {
-      hipLaunchKernelGGL(raise_flag_kernel, dim3(1), dim3(64), 0, h->stream, h->d_total + 3, epoch);
-      HIPCHK(h, hipGetLastError());
-      h->compact_epoch_armed = epoch;
-    } else if (hipStreamWriteValue64(h->stream, (void*)(h->d_total + 3), epoch, 0) == hipSuccess) {
-      h->compact_epoch_armed = epoch;
-    } else {
-      h->stream_write_ok = false;  // not supported here: turns end in the blocking wait
-    }
+    hipLaunchKernelGGL(raise_flag_kernel, dim3(1), dim3(64), 0, h->stream, h->d_total + 3, epoch);
+    HIPCHK(h, hipGetLastError());
+    h->compact_epoch_armed = epoch;
   }
   return RAFTQ_OK;
 }
 
 // RAFTQ_CYCLE_SEGMENTED: can this turn's sweep write the advance list itself (sweep_segments_kernel)?  A commit sweep (gated or
-// not) with no vote tally and no A/B variant asked for, on a stack where the completion word reaches the host.
+// not) with no vote tally and no A/B variant asked for.
 constexpr uint64_t kSegmentsMaxGroups = 1ull << 22;  // the pinned list has a slot per group: 16 B x 4M groups = 64 MB at most (larger handles: the contiguous list)
 static bool segments_ok(const raftq_t* h, unsigned flags) {
   if (const char* e = std::getenv("RAFTQ_CYCLE_SEGMENTS"))  // =0: every turn produces the contiguous list (A/B; the tests' way to a consumer's fallback)
     if (e[0] == '0') return false;
   const unsigned allowed = RAFTQ_SWEEP_COMMIT | RAFTQ_SWEEP_GATED | RAFTQ_SWEEP_CHANGED | RAFTQ_SWEEP_NO_ADOPT | RAFTQ_SWEEP_STREAM | RAFTQ_SWEEP_CACHED;
-  return (flags & (RAFTQ_SWEEP_COMMIT | RAFTQ_SWEEP_GATED)) && !(flags & ~allowed) && h->gpad <= kSegmentsMaxGroups && h->stream_write_ok;
+  return (flags & (RAFTQ_SWEEP_COMMIT | RAFTQ_SWEEP_GATED)) && !(flags & ~allowed) && h->gpad <= kSegmentsMaxGroups;
 }
 // sweep + list + flag, two kernels; leaves the handle as sweep_on + enqueue_collect would
 static int enqueue_sweep_segments(raftq_t* h, unsigned flags) {
@@ -1422,7 +1351,7 @@ static int enqueue_sweep_segments(raftq_t* h, unsigned flags) {
       h->seg_d = nullptr;
       h->seg_cap = 0;
     }
-    HIPCHK(h, hipHostMalloc((void**)&h->seg_h, (size_t)n_tiles * 4, hipHostMallocMapped | host_coherence_flag()));
+    HIPCHK(h, hipHostMalloc((void**)&h->seg_h, (size_t)n_tiles * 4, hipHostMallocMapped | hipHostMallocCoherent));
     HIPCHK(h, hipHostGetDevicePointer((void**)&h->seg_hd, h->seg_h, 0));
     HIPCHK(h, hipMalloc((void**)&h->seg_d, (size_t)n_tiles * 4));
     h->seg_cap = n_tiles;
@@ -1430,16 +1359,10 @@ static int enqueue_sweep_segments(raftq_t* h, unsigned flags) {
   const SweepArgs a = sweep_args(h, h->cur, true);
   uint64_t epoch = ++h->compact_epoch;
   if ((uint32_t)epoch == 0) epoch = ++h->compact_epoch;  // (the word's top half is never 0 for a turn in flight)
-  Arrival ar{nullptr, nullptr, (uint32_t)epoch};
-  if (flag_mode() == 3) {  // RAFTQ_CYCLE_FLAG=arrive: no flag kernel -- the sweep's last workgroup to arrive raises the word
-    if (int rc = ensure_arrive(h)) return rc;
-    ar.flag = (unsigned long long*)(h->d_total + 3);
-    ar.count = h->arrive_count;
-  }
   HIPCHK(h, launch_segments(h->N, a, n_tiles, (flags & RAFTQ_SWEEP_GATED) != 0, sweep_policy(flags, sweep_footprint(h)), (Advance16*)h->adv_d, h->seg_hd,
-                            h->seg_d, h->stream, ar));
+                            h->seg_d, h->stream));
   sweep_done(h, flags, kGPL);
-  if (ar.flag == nullptr) hipLaunchKernelGGL(raise_flag_segments_kernel, dim3(1), dim3(kBlock), 0, h->stream, h->d_total + 3, (uint32_t)epoch, h->seg_d, n_tiles);
+  hipLaunchKernelGGL(raise_flag_segments_kernel, dim3(1), dim3(kBlock), 0, h->stream, h->d_total + 3, (uint32_t)epoch, h->seg_d, n_tiles);
   HIPCHK(h, hipGetLastError());
   h->compact_epoch_armed = (uint64_t)(uint32_t)epoch << 32;
   h->flag_mask = 0xffffffff00000000ull;
@@ -1499,21 +1422,16 @@ int raftq_last_advances(raftq_t* h, const raftq_advance_t** list, uint64_t* n_li
 
 // The end of a batching turn.  A turn is ~55 us of device work, so the wake-up of a blocking
 // hipStreamSynchronize (interrupt + reschedule, ~8 us) is a visible slice of it.  When the turn ends in a
-// compaction, a stream write-value packet behind that kernel stores a completion epoch into pinned host memory:
+// compaction, a one-thread kernel behind it stores a completion epoch into pinned host memory:
 // the host polls the word -- bounded, then falls back to the blocking wait.
 // (Polling hipStreamQuery instead was measured SLOWER than blocking: 88 vs 80 us per turn, profiles/r02.)
-// RAFTQ_CYCLE_WAIT=block restores the plain blocking wait.
 static hipError_t wait_turn(raftq_t* h, uint64_t flag_epoch, int kind) {
-  static const bool poll = [] {
-    const char* e = std::getenv("RAFTQ_CYCLE_WAIT");
-    return !(e && std::strcmp(e, "block") == 0);
-  }();
   // A miss (the flag did not land within 2 ms; a turn is ~50 us) is either a slow turn -- a huge handle, a contended
   // GPU, a profiler -- or a stack on which the flag never reaches the host.  One slow turn must not change the handle's
   // steady state, so the wake-up is only given up after kMisses misses IN A ROW, and then tried again every
   // kRetry turns; RAFTQ_PROFILE prints how many turns fell back to the blocking wait.
   constexpr uint32_t kMisses = 8, kRetry = 1024;
-  const bool try_flag = poll && flag_epoch && (h->flag_misses[kind] < kMisses || (++h->flag_rested[kind] % kRetry) == 0);
+  const bool try_flag = flag_epoch && (h->flag_misses[kind] < kMisses || (++h->flag_rested[kind] % kRetry) == 0);
   if (try_flag) {
     volatile uint64_t* flag = h->h_total + 3;
     const auto t0 = std::chrono::steady_clock::now();
@@ -1537,17 +1455,9 @@ static hipError_t wait_turn(raftq_t* h, uint64_t flag_epoch, int kind) {
 }
 
 hipError_t raftq_detail::wait_call(raftq_t* h) {
-  static const bool block = [] {
-    const char* e = std::getenv("RAFTQ_CALL_WAIT");
-    return e && std::strcmp(e, "block") == 0;
-  }();
   hipError_t e;
-  if (block || !h->stream_write_ok || !h->d_total) {
+  if (!h->d_total) {
     e = hipStreamSynchronize(h->stream);
-  } else if (flag_mode() == 2) {  // RAFTQ_CYCLE_FLAG=packet (A/B): the runtime's write-value packet behind the call's kernels
-    const uint64_t epoch = ++h->compact_epoch;
-    h->flag_mask = ~0ull;
-    e = hipStreamWriteValue64(h->stream, (void*)(h->d_total + 3), epoch, 0) != hipSuccess ? hipStreamSynchronize(h->stream) : wait_turn(h, epoch, 1);
   } else {
     const uint64_t epoch = ++h->compact_epoch;
     h->flag_mask = ~0ull;
@@ -1642,7 +1552,7 @@ static int cycle_impl(raftq_t* h, const char* who, const AbiRec* deltas, uint64_
       HIPCHK(h, hipStreamSynchronize(h->stream));
       if (digest() != at_flag)
         return fail(h, RAFTQ_EHIP, std::string(who) + ": the completion flag arrived before the advance list it announces "
-                                                      "(RAFTQ_CYCLE_CHECK); set RAFTQ_CYCLE_WAIT=block on this stack");
+                                                      "(RAFTQ_CYCLE_CHECK)");
     }
   }
   const auto t4 = clk::now();
@@ -1839,7 +1749,6 @@ int raftq_set_create(raftq_t* const* handles, uint32_t n, raftq_set_t** out) {
   s->device = handles[0]->device;
   s->N = handles[0]->N;
   s->gpad = handles[0]->gpad;
-  if (const char* e = std::getenv("RAFTQ_SET_MODE")) s->mode = std::atoi(e) == 1 ? 1 : 0;
   try {  // everything the set's calls will ever push into: no allocation (and no exception) after this point
     s->members.reserve(n);
     s->tab_host.reserve(n);
@@ -1884,7 +1793,6 @@ int raftq_set_create(raftq_t* const* handles, uint32_t n, raftq_set_t** out) {
   int cus = 0;
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device);
   s->persist_wgs = (uint32_t)std::max(cus, 1) * 3u;  // 3 resident 256-thread workgroups per CU (144 VGPRs: profiles/r03/isa_sweep.txt)
-  if (const char* w = std::getenv("RAFTQ_SET_PERSIST_WGS")) s->persist_wgs = (uint32_t)std::max(1, std::atoi(w));
   *out = s;
   return RAFTQ_OK;
 }

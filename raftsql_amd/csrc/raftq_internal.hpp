@@ -72,16 +72,13 @@ struct raftq {
   unsigned int* seg_d = nullptr;  // device copy (the flag kernel adds them up)
   uint32_t seg_cap = 0, seg_tiles = 0, seg_stride = 0, seg_one = 0;  // seg_one: the count of a contiguous list presented as one segment
   uint64_t flag_mask = ~0ull;  // which bits of the completion word are the epoch the turn's wait compares (segmented: the top half)
-  unsigned int* compact_arrived = nullptr;  // (spare device word)
   uint32_t* self_max = nullptr;  // device: the self-max word (raftq_kernels.hpp) -- which match row is every group's largest
   uint64_t compact_epoch = 0;  // completion-flag values handed to hipStreamWriteValue64 (h_total[3])
   uint64_t compact_epoch_armed = 0;  // epoch the current turn's wait may poll for (0 = blocking wait)
-  bool stream_write_ok = true; // hipStreamWriteValue64 works on this stack
   // wait_turn: consecutive waits whose flag did not land in time and waits sat out since -- per KIND of wait ([0] the batching
   // turn, [1] every other call that ends on the completion word: codecs, tick lists): a codec call under a profiler must not
   // switch the turn's wake-up off
   uint32_t flag_misses[2] = {0, 0}, flag_rested[2] = {0, 0};
-  unsigned int* arrive_count = nullptr;       // RAFTQ_CYCLE_FLAG=arrive: the arrival counter (device, zero between kernels)
   uint64_t flag_fallbacks = 0;                // turns that ended in the blocking wait although a flag was armed
   uint32_t* claim = nullptr;    // u32 [N][ld] vote-slot claims, lazily allocated
   // sparse ingest: device copy of the batch (validated on the way in) and the "bad batch" epoch words
@@ -145,7 +142,7 @@ struct raftq {
     void* out_d = nullptr;         // device alias of out_h
     size_t out_bytes = 0;
     uint64_t n = 0;
-    hipEvent_t ev_in = nullptr, ev_comp = nullptr, ev_out = nullptr;
+    hipEvent_t ev_in = nullptr, ev_out = nullptr;
     bool busy = false;
     bool lists = false;            // submitted through the sort-free walk
     bool replayed = false;         // already re-run through the sorted path (after a stall)
@@ -180,9 +177,7 @@ struct raftq {
   } step_slot[kStepSlots];
   int step_last_slot = -1;         // slot of the last collected batch
   uint64_t step_submitted = 0, step_collected = 0;  // slot of batch k = k % kStepSlots
-  hipStream_t step_s_in = nullptr, step_s_out = nullptr;
-  int step_stream_mode = 2;
-  int step_link_share = 25;        // per cent of a carried result copy that rides in the link kernel (the rest: the walk kernel)
+  hipStream_t step_s_in = nullptr, step_s_out = nullptr;  // the inbound DMA; fetch_wire's copies (not behind the batch in flight)
   bool step_defer_copy = true;     // RAFTQ_STEP_DEFER_COPY=0: every batch launches its own result copy (round 1's form; for A/B)
   const void* step_last_out = nullptr;  // results of the last collected batch
   uint64_t step_last_n = 0;
@@ -203,7 +198,6 @@ struct raftq {
   // the streaming codec kernels (raftq_wire_kernels.hpp "the streaming form"): ticket word + per-tile look-back status
   unsigned long long* wire_lb = nullptr;     // device: kLbHead words {ticket, gave-up flag | landed waves | - | chunk ticket}, then kLbArrays status arrays of wire_lb_tiles words
   uint64_t wire_lb_tiles = 0;
-  uint32_t wire_last_tiles = 0;              // tiles of the streaming decode enqueued last (measurement builds dump its stamps)
   uint32_t wire_ticket_base = 0, wire_epoch = 0;
   uint32_t wire_chunk_base = 0, wire_chunk_pending = 0;  // the readers' chunk tickets (the head's fourth word), accounted like the tiles'
   bool wire_chunk_unknown = false;           // the last launch had no reader workgroups: how far its chunk ticket got is not known
@@ -215,8 +209,6 @@ struct raftq {
   bool resp_on = false;
   uint32_t resp_stamp = 0;
   const uint64_t* resp_at_tail_d = nullptr;
-  hipStream_t wire_copy_stream = nullptr;    // RAFTQ_WIRE_SDMA=1 (A/B only): the runtime's copies bring the decoder's input in
-  hipEvent_t wire_copy_ev = nullptr;
   // raftq_wal_encode_begin .. _end: enqueued, its totals in wire_pin[8 ..]; `done`: a later wait has covered it and what _end
   // will report is kept here
   bool wal_pending = false, wal_pending_done = false;
@@ -251,7 +243,7 @@ struct raftq_set {
   bool swept = false;
   bool broken = false;                // a member was destroyed under the set
   unsigned last_flags = 0;
-  int mode = 0;                       // 0 = K-deep grid, 1 = persistent walk (RAFTQ_SET_MODE / raftq_set_mode)
+  int mode = 0;                       // 0 = K-deep grid, 1 = persistent walk (raftq_set_mode)
   uint32_t persist_wgs = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // raftq_set_tick: device table of the members' TickArgs (as of tick_host), set ticks dispatched since it was built
@@ -276,7 +268,6 @@ int self_max_check(raftq_t* h);                 // the self-max word re-derived 
 int ensure_staging(raftq_t* h, size_t bytes);   // pinned, device-mapped staging (term deltas, campaign lists, log deltas)
 bool host_can_write(void* p, size_t bytes);     // [p, p + bytes) is mapped writable into this process (/proc/self/maps)
 int ensure_ingest(raftq_t* h, size_t bytes);    // the ack buffer of the batching turn: device memory behind a large BAR, else pinned
-unsigned host_coherence_flag();                 // hipHostMallocCoherent unless RAFTQ_HOST_COHERENT=0
 int ensure_tick_state(raftq_t* h);              // role / elapsed / action (+ hup bitmap)
 void free_node_state(raftq_t* h);               // raftq_step.hip's allocations (called by raftq_destroy)
 void free_wire_state(raftq_t* h);               // raftq_wire.hip's allocations (called by raftq_destroy)
@@ -303,7 +294,7 @@ int respond_pass_ok(raftq_t* h);  // a pass of the marshal whose totals are abou
 // The wait that ends a call whose results the kernels wrote into page-locked memory themselves (the streaming codecs,
 // raftq_step_frames): a one-thread kernel raises the handle's completion word behind everything enqueued so far and the host
 // polls it (raftq_cycle's wait, raftq_capi.hip wait_turn) -- a stream synchronisation costs 15-20 us more than the word does.
-// The blocking wait where the word cannot be had or RAFTQ_CALL_WAIT=block.
+// The blocking wait where the word cannot be had.
 hipError_t wait_call(raftq_t* h);
 }  // namespace raftq_detail
 

@@ -951,8 +951,7 @@ static __global__ __launch_bounds__(1024) void scan_partials_kernel(const uint4*
 // issued eight at a time), which is cheaper than the 5 us single-workgroup scan kernel plus the launch boundary it
 // replaces.  The last workgroup also publishes the total.  (A first form had every workgroup
 // __threadfence_system() and count itself in so that the last one could raise a completion flag for the host:
-// the fence writes back and invalidates the L2 -- 127 us instead of 13.  The flag is now a stream write-value
-// packet behind the kernel, raftq_capi.hip wait_turn.)
+// the fence writes back and invalidates the L2 -- 127 us instead of 13.  The flag went behind the kernel: see below.)
 // Round 3 tried the other shape VERDICT r02 item 4 names -- 256 workgroups of 16 sweep-waves each, every bitmap word
 // loaded at entry, the old / new pairs of all rounds gathered in one batch, the records staged in LDS and written out as
 // one contiguous run of lane-consecutive 16-byte stores -- and measured it SLOWER: 14.5 us against this kernel's 12.7 for
@@ -1050,33 +1049,12 @@ static __global__ void raise_flag_kernel(uint64_t* flag, uint64_t epoch) {
 // list[t * tile groups ...] -- a tile cannot have more changed groups than groups -- and its count at counts[t]: the list
 // is ascending when its segments are walked in order (raftq_last_advance_segments).  The changed bitmap and the per-wave
 // counts are written as by sweep_kernel: raftq_collect_changed still works afterwards.
-// VERDICT r05 item 6, candidate (b): the completion word WITHOUT a kernel of its own.  Every workgroup makes its stores -- records
-// and counts in page-locked host memory among them -- performed system-wide (`__threadfence_system()` by every thread, then the
-// workgroup's barrier) BEFORE it counts itself in (one agent-scope atomic); the workgroup that finds itself last adds up what the
-// others left (agent-scope loads: they may sit in another XCD's L2) and stores the word with system-scope release, and hands the
-// counter back zero.  Round 3's attempt had the compaction's last workgroup raise the flag with NO fence in the other workgroups:
-// the word overtook the data in 8 of 15 tests.  RAFTQ_CYCLE_FLAG=arrive selects this form; profiles/r06/flag_ab.txt has what
-// RAFTQ_CYCLE_CHECK made of it over 16,000 turns and what it costs beside the one-thread kernel and the runtime's write-value packet.
-struct Arrival {
-  unsigned long long* flag;  // the completion word as the device addresses it, or nullptr: the flag is somebody else's (a kernel behind this one)
-  unsigned int* count;       // device word, zero between kernels
-  uint32_t epoch;
-};
-// ALL threads of the workgroup call it, behind their last store.  -> true in every thread of the LAST workgroup to arrive.
-__device__ __forceinline__ bool arrive_last(const Arrival& ar, uint32_t* slot /*LDS*/) {
-  __threadfence_system();
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned int seen = __hip_atomic_fetch_add(ar.count, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    *slot = seen == gridDim.x * gridDim.y - 1 ? 1u : 0u;
-  }
-  __syncthreads();
-  return *slot != 0;
-}
-
+// The completion word is raised by a kernel of its own behind this one (raise_flag_segments_kernel).  Round 6 measured the
+// alternatives (profiles/r06/flag_ab.txt): the runtime's write-value packet was equal or slower, and this kernel's last workgroup
+// to arrive raising the word itself (every workgroup's stores fenced system-wide before it counts itself in) was safe over 16,000
+// checked turns and 5x slower.  Both were removed.
 template <int N, int GPL, bool GATED, int POLICY>
-static __global__ __launch_bounds__(kBlock) void sweep_segments_kernel(SweepArgs a, Advance16* list, unsigned int* counts_host, unsigned int* counts_dev,
-                                                                       Arrival ar) {
+static __global__ __launch_bounds__(kBlock) void sweep_segments_kernel(SweepArgs a, Advance16* list, unsigned int* counts_host, unsigned int* counts_dev) {
   constexpr bool STNT = (POLICY & kStNT) != 0;
   constexpr int kTile = kBlock * GPL;
   constexpr int kRounds = GPL / 2;
@@ -1148,24 +1126,6 @@ static __global__ __launch_bounds__(kBlock) void sweep_segments_kernel(SweepArgs
     if (e) list[pos + rank] = make_advance((Advance16*)nullptr, g0 + 2 * lane, r.c[j].x, nw[j].x);
     if (o) list[pos + rank + (e ? 1 : 0)] = make_advance((Advance16*)nullptr, g0 + 2 * lane + 1, r.c[j].y, nw[j].y);
     pos += __popcll(even[j]) + __popcll(odd[j]);
-  }
-  if (ar.flag != nullptr) {  // RAFTQ_CYCLE_FLAG=arrive: the last workgroup to arrive is the flag kernel
-    __shared__ uint32_t last_slot;
-    __shared__ uint32_t red[kWaves];
-    if (!arrive_last(ar, &last_slot)) return;
-    uint32_t acc = 0;
-    for (uint32_t i = tid; i < gridDim.x; i += kBlock) acc += __hip_atomic_load(counts_dev + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if (lane == 0) red[wave] = acc;
-    __syncthreads();
-    if (tid == 0) {
-      uint32_t total = 0;
-#pragma unroll
-      for (int k = 0; k < kWaves; ++k) total += red[k];
-      __hip_atomic_store(ar.count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(ar.flag, ((unsigned long long)ar.epoch << 32) | total, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
   }
 }
 
@@ -1540,19 +1500,18 @@ __device__ __forceinline__ void run_out(uint32_t* out, uint64_t cap, uint64_t po
   if (tid < n - done) out[pos + done + tid] = ids[done + tid];
 }
 
-// BPW: 1,024-group blocks per workgroup.  A workgroup's ids leave as ONE run per list; longer runs (BPW = 4) were measured no
-// faster than BPW = 1 (1M groups, 400K ids: 34 us of kernel either way -- 1.6 MB at the link's 47 GB/s for this pattern).
-template <bool BEAT_BITMAP, int BPW>
+// One 1,024-group block per workgroup.  A workgroup's ids leave as ONE run per list; longer runs (four blocks per workgroup)
+// were measured no faster (1M groups, 400K ids: 34 us of kernel either way -- 1.6 MB at the link's 47 GB/s for this pattern).
+template <bool BEAT_BITMAP>
 static __global__ __launch_bounds__(kBlock) void tick_lists32_kernel(const uint64_t* __restrict__ hup_bits, const uint64_t* __restrict__ beat_bits,
                                                                       const uint4* __restrict__ partials, uint64_t n_chunks /* gpad / 256 */,
                                                                       uint32_t* hup_out, uint64_t hup_cap, uint32_t* beat_out, uint64_t beat_cap,
                                                                       uint64_t* beat_map, uint64_t* totals /*[2]*/,
-                                                                      const uint64_t* __restrict__ wave_off_hup, const uint64_t* __restrict__ wave_off_beat,
-                                                                      Arrival ar) {
-  constexpr int kC = kWaves * BPW;  // 256-group chunks (a tick wave's share) per workgroup
+                                                                      const uint64_t* __restrict__ wave_off_hup, const uint64_t* __restrict__ wave_off_beat) {
+  constexpr int kC = kWaves;  // 256-group chunks (a tick wave's share) per workgroup
   __shared__ uint64_t red[2][kWaves];
   __shared__ uint32_t mine[2][kC];
-  __shared__ uint32_t ids[2][kBlock * 4 * BPW];
+  __shared__ uint32_t ids[2][kBlock * 4];
   __shared__ uint64_t map_words[kC * 4];
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint64_t first_wave = (uint64_t)blockIdx.x * kC;
@@ -1609,11 +1568,9 @@ static __global__ __launch_bounds__(kBlock) void tick_lists32_kernel(const uint6
     totals[1] = pos_b + tot_b;
   }
   const uint64_t below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-#pragma unroll
-  for (int b = 0; b < BPW; ++b) {
-    const uint32_t ci = (uint32_t)b * kWaves + wave;  // this wave's chunk of the round
-    const uint64_t wv = first_wave + ci;
-    if (wv >= n_chunks) continue;  // wave-uniform
+  const uint32_t ci = wave;  // this wave's chunk
+  const uint64_t wv = first_wave + ci;
+  if (wv < n_chunks) {  // wave-uniform
     uint32_t loc_h = 0, loc_b = 0;  // this chunk's first id inside the workgroup's runs
 #pragma unroll
     for (int k = 0; k < kC; ++k) {
@@ -1653,13 +1610,6 @@ static __global__ __launch_bounds__(kBlock) void tick_lists32_kernel(const uint6
     run_out(beat_out, beat_cap, pos_b, ids[1], tot_b, tid);
   } else if (tid < kC * 4 && first_wave * 4 + tid < n_chunks * 4) {
     beat_map[first_wave * 4 + tid] = map_words[tid];
-  }
-  if (ar.flag != nullptr) {  // RAFTQ_CYCLE_FLAG=arrive (see sweep_segments_kernel): the totals are among the stores fenced before the count
-    __shared__ uint32_t last_slot;
-    if (arrive_last(ar, &last_slot) && tid == 0) {
-      __hip_atomic_store(ar.count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(ar.flag, (unsigned long long)ar.epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
   }
 }
 

@@ -35,8 +35,7 @@ namespace {
 // 2 MB-aligned memory for the node's arena and pool chunks, with a transparent huge page asked for per 2 MB: when 32,768
 // groups outgrow a block size in the same turn the pool hands out 8-32 MB of memory nobody has touched yet, and with 4 KB
 // pages that turn takes 8,000 page faults -- measured as waves of 8 / 11 / 15 ms among waves of 5.4 (bench.py -> node,
-// ms_per_wave_each; profiles/r03/node_chunk_ab.txt: 4.98 -> 5.66e6 proposals/s with huge pages).  RAFTQ_NODE_THP=0 turns the
-// request off (a VM whose huge-page fault compacts memory synchronously took twice as long per turn with it).
+// ms_per_wave_each; profiles/r03/node_chunk_ab.txt: 4.98 -> 5.66e6 proposals/s with huge pages).
 // (Its own mapping, not aligned_alloc: memory the allocator has had before comes back with its 4 KB pages already in place, and
 // the request then changes nothing until khugepaged gets round to it -- inside bench.py, after the other legs had freed
 // hundreds of MB, the node leg ran as if huge pages were off.)
@@ -45,17 +44,13 @@ inline size_t huge_round(size_t bytes) { return (bytes + kHugePage - 1) / kHugeP
 inline void* huge_alloc(size_t bytes) {
   bytes = huge_round(bytes);
 #if defined(__linux__)
-  static const bool thp = [] {
-    const char* e = std::getenv("RAFTQ_NODE_THP");
-    return !(e && e[0] == '0');
-  }();
   char* raw = (char*)mmap(nullptr, bytes + kHugePage, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
   if (raw == (char*)MAP_FAILED) return nullptr;
   char* p = (char*)(((uintptr_t)raw + kHugePage - 1) & ~(uintptr_t)(kHugePage - 1));
   if (p != raw) (void)munmap(raw, (size_t)(p - raw));
   const size_t tail = (size_t)(raw + bytes + kHugePage - (p + bytes));
   if (tail) (void)munmap(p + bytes, tail);
-  if (thp) (void)madvise(p, bytes, MADV_HUGEPAGE);
+  (void)madvise(p, bytes, MADV_HUGEPAGE);
   return p;
 #else
   return std::aligned_alloc(kHugePage, bytes);
@@ -390,8 +385,6 @@ struct raftq_node {
   Pool pool;                      // the groups' log and commit-channel arrays
   bool oom = false;               // an arena or queue allocation failed this turn: advance() ends in ENOMEM
   bool tail_appends = true;       // MsgApps are staged with RAFTQ_MSGF_ENTRIES (RAFTQ_NODE_TAIL_APPENDS=0: headers only, as round 2)
-  bool deltas_nowait = true;      // RAFTQ_NODE_DELTAS_NOWAIT=0: every tail report is waited for
-  bool split_wal = true;          // RAFTQ_NODE_SPLIT_WAL=0: raftq_wal_encode as a call of its own, waited for, ahead of the outbound marshal
   bool deltas_need_result = false;  // a report in n->deltas may move the commit index (a follower's): flush_deltas waits
   bool wal_begun = false;         // flush_wal_begin .. flush_wal_end
   size_t wal_inflight = 0;
@@ -788,7 +781,7 @@ void follower_append(raftq_node_t* n, uint64_t gi, Group& g, const raftq_wire_ms
 // can poison()), on success with it held again.
 int flush_deltas(raftq_node_t* n, std::unique_lock<std::mutex>& lk) {
   if (n->deltas.empty()) return RAFTQ_OK;
-  if (n->deltas_nowait && n->N > 1 && !n->deltas_need_result) {
+  if (n->N > 1 && !n->deltas_need_result) {
     // every report is a leader's appendEntry and there is more than one peer: raftLog.committed cannot move (the leader's own
     // Match is the largest, the quorum-th largest is somebody else's) -- enqueued and left (raftq_apply_log_deltas_nowait);
     // the engine's state has moved by the time the next Step runs
@@ -1214,9 +1207,9 @@ int flush_wal_begin(raftq_node_t* n, std::unique_lock<std::mutex>& lk) {
   }
   const uint32_t prev = n->wal_crc;
   lk.unlock();
-  int rc = n->split_wal ? raftq_wal_encode_begin(n->h, recs.as<raftq_wal_rec_t>(), n_recs, pool.p, pool.size, prev, n->wal_enc.p, cap, nullptr) : RAFTQ_EINVAL;
+  int rc = raftq_wal_encode_begin(n->h, recs.as<raftq_wal_rec_t>(), n_recs, pool.p, pool.size, prev, n->wal_enc.p, cap, nullptr);
   n->wal_begun = rc == RAFTQ_OK;
-  if (rc == RAFTQ_EINVAL) {  // buffers the device cannot address (or RAFTQ_NODE_SPLIT_WAL=0): the whole call, now
+  if (rc == RAFTQ_EINVAL) {  // buffers the device cannot address: the whole call, now
     rc = raftq_wal_encode(n->h, recs.as<raftq_wal_rec_t>(), n_recs, pool.p, pool.size, prev, n->wal_enc.p, cap, nullptr, &n->wal_cnt);
   }
   if (rc != RAFTQ_OK) return rc;
@@ -1261,8 +1254,6 @@ int raftq_node_create(int device, uint64_t n_groups, uint32_t n_peers, uint32_t 
   n->profiling = std::getenv("RAFTQ_PROFILE") != nullptr;
   if (const char* ta = std::getenv("RAFTQ_NODE_TAIL_APPENDS")) n->tail_appends = std::atoi(ta) != 0;
   if (const char* fi = std::getenv("RAFTQ_NODE_FUSE_INBOUND")) n->fuse_inbound = std::atoi(fi) != 0;
-  if (const char* dn = std::getenv("RAFTQ_NODE_DELTAS_NOWAIT")) n->deltas_nowait = std::atoi(dn) != 0;
-  if (const char* sw = std::getenv("RAFTQ_NODE_SPLIT_WAL")) n->split_wal = std::atoi(sw) != 0;
   if (const char* pd = std::getenv("RAFTQ_NODE_PROPOSE_DEVICE")) n->propose_device = std::atoi(pd) != 0;
   if (n_peers < 2) n->propose_device = false;  // (a single-peer group commits what it appends: the report has to come back)
   if (const char* rd = std::getenv("RAFTQ_NODE_RESPOND_DEVICE")) n->respond_device = std::atoi(rd) != 0 && n_peers >= 2;

@@ -136,21 +136,17 @@ int ensure_slot(raftq_t* h, raftq::StepSlot& sl, uint64_t n, int end_bit, Scratc
   if (!h->step_s_in) {
     HIPCHK(h, hipStreamCreateWithFlags(&h->step_s_in, hipStreamNonBlocking));
     HIPCHK(h, hipStreamCreateWithFlags(&h->step_s_out, hipStreamNonBlocking));
-    // Stream topology.  Default 2: the H2D DMA on its own stream (overlaps the previous batch's kernels),
-    // the result copy on the handle's stream.  Measured on MI355X (profiles/r01/step_pipeline_trace.txt):
-    // a kernel that writes to host memory over PCIe keeps every other queue's NEXT kernel from starting
-    // until it retires (a kernel that merely spins does not), so a third stream for the D2H buys nothing
-    // (3: 186 us per 64K batch, 2: 176 us, 1 = everything on one stream: 426 us, 4 = copies share a stream: 459 us).
-    // Round 2 of that A/B (profiles/r01/step_result_copy_ab.txt): the runtime's own D2H memcpy instead of our kernel
-    // (382-394 us), the copy split into 2-32 short kernels (177-185 us), the walk writing straight into mapped host
-    // memory (186 us) -- none beat 2; those variants are no longer in the code.  RAFTQ_STEP_STREAMS = 1..4 overrides.
-    if (const char* m = std::getenv("RAFTQ_STEP_STREAMS")) h->step_stream_mode = std::atoi(m);
+    // Stream topology: the H2D DMA on its own stream (overlaps the previous batch's kernels), the result copy on the
+    // handle's stream.  Measured on MI355X (profiles/r01/step_pipeline_trace.txt): a kernel that writes to host memory over
+    // PCIe keeps every other queue's NEXT kernel from starting until it retires (a kernel that merely spins does not), so a
+    // third stream for the D2H buys nothing (176 us per 64K batch; a third stream 186 us, everything on one stream 426 us,
+    // copies sharing a stream 459 us).  Round 2 of that A/B (profiles/r01/step_result_copy_ab.txt): the runtime's own D2H
+    // memcpy instead of our kernel (382-394 us), the copy split into 2-32 short kernels (177-185 us), the walk writing
+    // straight into mapped host memory (186 us) -- none beat this form; those variants are no longer in the code.
     if (const char* m = std::getenv("RAFTQ_STEP_DEFER_COPY")) h->step_defer_copy = std::atoi(m) != 0;
-    if (const char* m = std::getenv("RAFTQ_STEP_LINK_SHARE")) h->step_link_share = std::min(100, std::max(0, std::atoi(m)));
   }
   if (!sl.ev_in) {
     HIPCHK(h, hipEventCreateWithFlags(&sl.ev_in, hipEventDisableTiming));
-    HIPCHK(h, hipEventCreateWithFlags(&sl.ev_comp, hipEventDisableTiming));
     HIPCHK(h, hipEventCreateWithFlags(&sl.ev_out, hipEventDisableTiming));
   }
   (void)end_bit;
@@ -315,7 +311,6 @@ void raftq_detail::free_node_state(raftq_t* h) {
     if (sl.out_h) (void)hipHostFree(sl.out_h);
     if (sl.w_pin) (void)hipHostFree(sl.w_pin);
     if (sl.ev_in) (void)hipEventDestroy(sl.ev_in);
-    if (sl.ev_comp) (void)hipEventDestroy(sl.ev_comp);
     if (sl.ev_out) (void)hipEventDestroy(sl.ev_out);
   }
   for (auto& q : h->ld_nowait) {
@@ -459,10 +454,11 @@ static int enqueue_list_walk(raftq_t* h, const Scratch& s, uint64_t n, uint8_t r
   unsigned int* bad = (unsigned int*)(s.n_heads + 1);
   unsigned int* skipped = bad + 1;  // the last word of the 16-byte tail behind the result records
   const unsigned blocks = (unsigned)((n + kBlock - 1) / kBlock);
-  // the carried copy is split over this batch's two kernels roughly as their own durations are (link ~ 1/5 of the chain)
+  // the carried copy is split over this batch's two kernels roughly as their own durations are (link ~ 1/5 of the chain):
+  // 25 per cent of it rides in the link kernel, the rest in the walk kernel
   raftqk::CopyRide in_link{nullptr, nullptr, 0, 0, 0, 0}, in_walk = in_link;
   if (carry) {
-    const uint64_t quads = carry->out_quads, cut = quads * (uint64_t)h->step_link_share / 100;
+    const uint64_t quads = carry->out_quads, cut = quads * 25 / 100;
     in_link = {(const u64x2*)carry->outs_d, (u64x2*)carry->out_d, 0, cut, quads - 1, cut ? d2h_blocks(cut) : 0u};
     in_walk = {(const u64x2*)carry->outs_d, (u64x2*)carry->out_d, cut, quads, quads - 1, d2h_blocks(quads - cut)};
   }
@@ -567,11 +563,9 @@ static int submit_impl(raftq_t* h, const void* msgs, uint64_t n, const WireSrc* 
   // Step moves the live commit index: a what-if (NO_ADOPT) sweep's shadow values are no longer what
   // raftq_read_committed should hand out
   h->last_flags &= ~RAFTQ_SWEEP_NO_ADOPT;
-  // copy-in stream -> compute stream (the handle's: state changes stay ordered with every other
-  // call on the handle) -> copy-out stream, chained by events
-  const int mode = h->step_stream_mode;
-  hipStream_t s_in = mode == 1 ? h->stream : h->step_s_in;
-  hipStream_t s_out = (mode == 1 || mode == 2) ? h->stream : mode == 4 ? h->step_s_in : h->step_s_out;
+  // copy-in stream -> the handle's stream (state changes stay ordered with every other call on the handle; the result copy
+  // follows the compute there), chained by an event
+  hipStream_t s_in = h->step_s_in;
   // in: one DMA over PCIe from the pinned staging.  A batch the producer wrote straight into device memory needs neither
   // a DMA nor a copy: the kernels read it where it lies (the slot's staging stays untouched until the slot's next batch,
   // which is after this one's collect -- the replay path reads it there as well).  Round 2 first kept a device-to-device
@@ -594,10 +588,8 @@ static int submit_impl(raftq_t* h, const void* msgs, uint64_t n, const WireSrc* 
     if (wire->nbytes)
       HIPCHK(h, hipMemcpyAsync(s.w_stream, (const uint8_t*)sl.in_h + sl.w_stage_stream_off, (size_t)wire->nbytes,
                                hipMemcpyHostToDevice, s_in));
-    if (s_in != h->stream) {
-      HIPCHK(h, hipEventRecord(sl.ev_in, s_in));
-      HIPCHK(h, hipStreamWaitEvent(h->stream, sl.ev_in, 0));
-    }
+    HIPCHK(h, hipEventRecord(sl.ev_in, s_in));
+    HIPCHK(h, hipStreamWaitEvent(h->stream, sl.ev_in, 0));
   } else if (own_staging) {
     if (packed) packed_src = device_src;
     else {
@@ -609,17 +601,13 @@ static int submit_impl(raftq_t* h, const void* msgs, uint64_t n, const WireSrc* 
     // this batch is in flight, so the records are copied into this slot's scratch, device to device
     void* in_dst = packed ? s.msgs40 : (void*)s.msgs;
     HIPCHK(h, hipMemcpyAsync(in_dst, device_src, in_bytes, hipMemcpyDeviceToDevice, s_in));
-    if (s_in != h->stream) {
-      HIPCHK(h, hipEventRecord(sl.ev_in, s_in));
-      HIPCHK(h, hipStreamWaitEvent(h->stream, sl.ev_in, 0));
-    }
+    HIPCHK(h, hipEventRecord(sl.ev_in, s_in));
+    HIPCHK(h, hipStreamWaitEvent(h->stream, sl.ev_in, 0));
   } else {
     void* in_dst = wire ? (void*)s.w_off : packed ? s.msgs40 : (void*)s.msgs;
     HIPCHK(h, hipMemcpyAsync(in_dst, sl.in_h, in_bytes, hipMemcpyHostToDevice, s_in));
-    if (s_in != h->stream) {
-      HIPCHK(h, hipEventRecord(sl.ev_in, s_in));
-      HIPCHK(h, hipStreamWaitEvent(h->stream, sl.ev_in, 0));
-    }
+    HIPCHK(h, hipEventRecord(sl.ev_in, s_in));
+    HIPCHK(h, hipStreamWaitEvent(h->stream, sl.ev_in, 0));
   }
   // touched count + bad + skipped: the default result copy leaves them zeroed behind it (step_d2h_kernel zero_tail)
   const uint32_t rec = result_rec_bytes(h);
@@ -658,7 +646,7 @@ static int submit_impl(raftq_t* h, const void* msgs, uint64_t n, const WireSrc* 
   // DMA is better off with its own copy kernel -- the DMA of the batch after next cannot start while a kernel is writing
   // to host memory either, and the fused kernel writes for longer (measured: caller-owned arrays 157 us per batch with
   // their own copy kernels, 189 us deferred; staged batches 101 -> 77 us; profiles/r02/step_deferred_copy_ab.txt).
-  const bool defer = s_out == h->stream && h->step_defer_copy && staged_in_device;
+  const bool defer = h->step_defer_copy && staged_in_device;
   raftq::StepSlot* carry = nullptr;
   if (h->step_submitted > h->step_collected) {
     raftq::StepSlot& prev = h->step_slot[(h->step_submitted - 1) % raftq::kStepSlots];
@@ -675,12 +663,8 @@ static int submit_impl(raftq_t* h, const void* msgs, uint64_t n, const WireSrc* 
   sl.out_quads = tail_off(n, rec) / 16 + 1;  // records + the 16-byte tail
   if (defer) {
     sl.copy_pending = true;
-  } else {
-    if (s_out != h->stream) {
-      HIPCHK(h, hipEventRecord(sl.ev_comp, h->stream));
-      HIPCHK(h, hipStreamWaitEvent(s_out, sl.ev_comp, 0));
-    }
-    if (int rc = enqueue_result_copy(h, sl, s_out)) return rc;
+  } else if (int rc = enqueue_result_copy(h, sl, h->stream)) {
+    return rc;
   }
   sl.tail_zeroed = true;  // (once the copy has run) holds for the next batch of the same size and format in the same scratch
   sl.tail_n = n;

@@ -91,39 +91,27 @@ bool streaming_on() {  // RAFTQ_WIRE_STREAMING=0: the copying form even for page
 }
 // Worker workgroups of a streaming kernel (RAFTQ_WIRE_WGS overrides): a tile is ~25 us of dependent work (flags, scratch
 // reads, the parse at one wave per SIMD, the look-back), the link moves a tile every ~0.3 us.
-// `fit`: what is resident at once beside the readers when the caller knows better than 208 (the decoder: its LDS per workgroup)
-unsigned fused_grid(uint32_t n_tiles, unsigned fit = 208u) {
+unsigned fused_grid(uint32_t n_tiles) {
   const char* e = std::getenv("RAFTQ_WIRE_WGS");  // read per call: the tests drive tiny grids through one process
   const long v = e ? std::strtol(e, nullptr, 10) : 0;
-  return std::min<unsigned>(v > 0 && v <= 4096 ? (unsigned)v : fit, n_tiles);
+  return std::min<unsigned>(v > 0 && v <= 4096 ? (unsigned)v : 208u, n_tiles);
 }
-// frames per tile = threads per workgroup of the streaming decoder (RAFTQ_WIRE_TILE=128|256; raftq_wire_kernels.hpp wire_dec_fused_kernel)
-unsigned dec_tile() {
-  const char* e = std::getenv("RAFTQ_WIRE_TILE");  // read per call: the tests run both
-  const long v = e ? std::strtol(e, nullptr, 10) : 0;
-  return v == 128 ? 128u : 256u;  // measured (profiles/r06/wire_tile_ab.jsonl): 256 frames 172 us a call, 128 frames 186
-}
+// frames per tile = threads per workgroup of the streaming decoder (raftq_wire_kernels.hpp wire_dec_fused_kernel)
+constexpr unsigned kDecTile = 256;
 
 constexpr uint64_t kLbHead = 4;  // words in front of the status arrays
 // reader workgroups of a streaming kernel (RAFTQ_WIRE_READERS overrides): 48 pull a caller's array at 55 GB/s, more are slower
 // RAFTQ_WIRE_READERS=0: NO reader workgroups -- every chunk is brought in by a worker that found nobody else doing it (the
-// liveness argument's limit case, tests/test_wire_gpu.py::test_streaming_codecs_without_readers).  `dflt`: 48 workgroups of 256
-// threads; the 128-thread decoder launches 96 for the same bytes in flight.
-unsigned fused_readers(uint32_t chunks, unsigned dflt = 48u) {
+// liveness argument's limit case, tests/test_wire_gpu.py::test_streaming_codecs_without_readers).
+unsigned fused_readers(uint32_t chunks) {
   const char* e = std::getenv("RAFTQ_WIRE_READERS");
   char* end = nullptr;
   const long v = e ? std::strtol(e, &end, 10) : -1;
   if (e && end != e && v == 0) return 0;
-  return std::min<unsigned>(v > 0 && v <= 1024 ? (unsigned)v : dflt, chunks);
+  return std::min<unsigned>(v > 0 && v <= 1024 ? (unsigned)v : 48u, chunks);
 }
-// bytes of all arrays together that a reader brings in before it raises a flag (RAFTQ_WIRE_CHUNK overrides)
-uint64_t sdma_chunk();
-uint64_t feed_chunk() {
-  if (const uint64_t s = sdma_chunk()) return s;
-  const char* e = std::getenv("RAFTQ_WIRE_CHUNK");
-  const long v = e ? std::strtol(e, nullptr, 10) : 0;
-  return v >= 1024 && v <= (1 << 20) ? (uint64_t)v : 8192;
-}
+// bytes of all arrays together that a reader brings in before it raises a flag
+constexpr uint64_t kFeedChunk = 8192;
 
 // The readers' plan for up to three caller arrays (device views `src`, all 16-byte aligned): where they go in the scratch
 // (carved behind `c`), how many chunks, how many bytes of every array per chunk.  max_chunks: flags available.
@@ -132,12 +120,11 @@ struct FeedPlan {
   size_t off[3];
 };
 // extra[k]: bytes of array k that follow, in the scratch, what the readers bring (records a kernel writes there itself)
-FeedPlan plan_feed(Carver& c, const void* const src[3], const uint64_t bytes[3], uint64_t max_chunks, unsigned readers_dflt = 48u,
-                   const uint64_t* extra = nullptr) {
+FeedPlan plan_feed(Carver& c, const void* const src[3], const uint64_t bytes[3], uint64_t max_chunks, const uint64_t* extra = nullptr) {
   FeedPlan p{};
   uint64_t total = 0;
   for (int k = 0; k < 3; ++k) total += bytes[k];
-  const uint64_t chunks = std::max<uint64_t>(1, std::min<uint64_t>(max_chunks, (total + feed_chunk() - 1) / feed_chunk()));
+  const uint64_t chunks = std::max<uint64_t>(1, std::min<uint64_t>(max_chunks, (total + kFeedChunk - 1) / kFeedChunk));
   for (int k = 0; k < 3; ++k) {
     p.off[k] = c.take(bytes[k] + (extra ? extra[k] : 0));
     p.in.seg[k].src = (const uint8_t*)src[k];
@@ -145,14 +132,14 @@ FeedPlan plan_feed(Carver& c, const void* const src[3], const uint64_t bytes[3],
     p.in.seg[k].per_chunk = std::max<uint64_t>(256, ((bytes[k] + chunks - 1) / chunks + 255) / 256 * 256);
   }
   p.in.chunks = (uint32_t)chunks;
-  p.in.readers = fused_readers(p.in.chunks, readers_dflt);
+  p.in.readers = fused_readers(p.in.chunks);
   return p;
 }
 // (called once per launch, after tile_ctl: the chunk tickets of the launch are accounted for in tile_ctl_launched)
 // The chunk ticket is monotonic across calls: a launch with reader workgroups draws exactly chunks + readers tickets whoever
 // copies what (a worker that serves itself claims by compare-and-swap and never draws past the end; the readers draw the rest
-// and one beyond each), so the next call's base is known without asking the device.  A launch with NO readers (RAFTQ_WIRE_READERS=0,
-// RAFTQ_WIRE_SDMA) only claims the chunks somebody waited for -- a chunk past every array's end, or one that holds bytes no tile
+// and one beyond each), so the next call's base is known without asking the device.  A launch with NO readers (RAFTQ_WIRE_READERS=0)
+// only claims the chunks somebody waited for -- a chunk past every array's end, or one that holds bytes no tile
 // names, stays unclaimed -- so its count is not known: the ticket word is zeroed in front of such a launch and in front of the
 // first launch after one (a 4-byte memset in the stream: test and A/B shapes only).
 int bind_feed(raftq_t* h, FeedPlan& p, uint8_t* base, unsigned long long* flags) {
@@ -165,18 +152,8 @@ int bind_feed(raftq_t* h, FeedPlan& p, uint8_t* base, unsigned long long* flags)
     h->wire_chunk_unknown = p.in.readers == 0;
   }
   p.in.chunk_base = h->wire_chunk_base;
-  p.in.no_serve = 0;
   h->wire_chunk_pending = p.in.readers ? p.in.chunks + p.in.readers : 0;  // every reader workgroup draws exactly one ticket beyond the chunks
   return RAFTQ_OK;
-}
-// RAFTQ_WIRE_SDMA=<chunk KiB> (A/B only; VERDICT r04 / r05 item 1: "build the SDMA-reader A/B instead of citing the old probe"): the
-// decoder's input is brought in by the RUNTIME's copies on a second stream -- one hipMemcpyAsync per array and chunk, the chunk's
-// flag raised behind it by hipStreamWriteValue64 -- and the kernel is launched with no reader workgroups and workers that only
-// wait.  profiles/r06/wire_tile_ab.jsonl has what it measured (2.0 ms with 64 KB chunks, 0.35 ms with 1 MB chunks, against 0.17 ms).
-uint64_t sdma_chunk() {
-  const char* e = std::getenv("RAFTQ_WIRE_SDMA");
-  const long v = e ? std::strtol(e, nullptr, 10) : 0;
-  return v >= 1 && v <= 65536 ? (uint64_t)v << 10 : 0;
 }
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
@@ -205,10 +182,6 @@ int tile_ctl(raftq_t* h, uint64_t n_tiles, TileCtl* ctl) {
   }
   ctl->ticket = reinterpret_cast<unsigned int*>(h->wire_lb);
   ctl->ticket_base = h->wire_ticket_base;
-  ctl->ablate = 0;
-#if defined(RAFTQ_WIRE_TRACE)
-  if (const char* e = std::getenv("RAFTQ_WIRE_ABLATE")) ctl->ablate = (uint32_t)std::strtol(e, nullptr, 10);
-#endif
   ctl->epoch = h->wire_epoch;
   for (int k = 0; k < kLbArrays; ++k) ctl->status[k] = h->wire_lb + kLbHead + (uint64_t)k * h->wire_lb_tiles;
   return RAFTQ_OK;
@@ -219,25 +192,6 @@ void tile_ctl_launched(raftq_t* h, uint32_t n_tiles, unsigned workers) {
   h->wire_chunk_base += h->wire_chunk_pending;
   h->wire_chunk_pending = 0;
 }
-#if defined(RAFTQ_WIRE_TRACE)
-// RAFTQ_TRACE_STAMP's rows of the call just waited for -> stderr (once every 16th call): per tile, microseconds since the
-// earliest stamp of the launch
-void trace_dump(raftq_t* h, const char* what, uint32_t n_tiles) {
-  static int calls = 0;
-  static const bool dump = std::getenv("RAFTQ_WIRE_TRACE_DUMP") != nullptr;
-  if (!dump || (calls++ & 15) != 15 || n_tiles * 8ull > h->wire_lb_tiles) return;
-  std::vector<unsigned long long> t(n_tiles * 8ull);
-  if (hipMemcpy(t.data(), h->wire_lb + kLbHead + kLbSpare * h->wire_lb_tiles, t.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return;
-  unsigned long long t0 = ~0ull;
-  for (uint32_t i = 0; i < n_tiles; ++i) t0 = std::min(t0, t[i * 8ull]);
-  std::fprintf(stderr, "[trace %s] tile: claimed offs_in dma_issued frames_in parsed lookback ents_out recs_out (us)\n", what);
-  for (uint32_t i = 0; i < n_tiles; i += (n_tiles > 64 ? n_tiles / 32 : 1)) {
-    std::fprintf(stderr, "[trace %s] %5u:", what, i);
-    for (int k = 0; k < 8; ++k) std::fprintf(stderr, " %7.1f", (double)(t[i * 8ull + k] - t0) / 100.0);
-    std::fprintf(stderr, "\n");
-  }
-}
-#endif
 // after the call's wait: did a look-back give up (wire_pin[3], copied from the control block by the last tile)?
 int tile_ctl_check(raftq_t* h, const char* who, uint32_t pin_base = 0) {
   if (h->wire_pin[pin_base + 3] == 0) return RAFTQ_OK;
@@ -274,10 +228,6 @@ void raftq_detail::free_wire_state(raftq_t* h) {
   (void)hipFree(h->resp_dev);
   h->resp_dev = nullptr;
   h->resp_dev_bytes = 0;
-  if (h->wire_copy_stream) (void)hipStreamDestroy(h->wire_copy_stream);
-  if (h->wire_copy_ev) (void)hipEventDestroy(h->wire_copy_ev);
-  h->wire_copy_stream = nullptr;
-  h->wire_copy_ev = nullptr;
   h->wire_flags = nullptr;
   h->wire_lb = nullptr;
   h->wire_lb_tiles = 0;
@@ -333,7 +283,7 @@ int raftq_wire_encode(raftq_t* h, const raftq_wire_msg_t* msgs, uint64_t n, cons
     const void* const src[3] = {v_msgs, v_ents, v_pool};
     const uint64_t sizes[3] = {n * sizeof(WireMsg), n_ents * sizeof(WireEnt), pool_bytes};
     TileCtl ctl;
-    if (int rc = tile_ctl(h, std::max<uint64_t>(n_tiles, (sizes[0] + sizes[1] + sizes[2]) / feed_chunk() + 1), &ctl)) return rc;
+    if (int rc = tile_ctl(h, std::max<uint64_t>(n_tiles, (sizes[0] + sizes[1] + sizes[2]) / kFeedChunk + 1), &ctl)) return rc;
     FeedPlan plan = plan_feed(fc, src, sizes, h->wire_lb_tiles);
     if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, fc.off)) return rc;
     if (int rc = grow(h, &h->wire_out, &h->wire_out_bytes, cap + 16)) return rc;
@@ -437,8 +387,8 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
   const uint64_t sizes[3] = {n_msgs * sizeof(WireMsg), n_ents * sizeof(WireEnt), pool_bytes};
   const uint64_t extra[3] = {n_dev * sizeof(WireMsg), n_prop_ents * sizeof(WireEnt), 0};
   TileCtl ctl;
-  if (int rc = tile_ctl(h, std::max<uint64_t>(n_tiles, (sizes[0] + sizes[1] + sizes[2]) / feed_chunk() + 1), &ctl)) return rc;
-  FeedPlan plan = plan_feed(fc, src, sizes, h->wire_lb_tiles, 48u, extra);
+  if (int rc = tile_ctl(h, std::max<uint64_t>(n_tiles, (sizes[0] + sizes[1] + sizes[2]) / kFeedChunk + 1), &ctl)) return rc;
+  FeedPlan plan = plan_feed(fc, src, sizes, h->wire_lb_tiles, extra);
   const size_t o_props = fc.take(n_props * sizeof(PropRec)), o_pe = fc.take(n_prop_ents * sizeof(PropEnt));  // the check kernel's copies of the records
   if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, fc.off)) return rc;
   if (int rc = grow(h, &h->wire_out, &h->wire_out_bytes, cap + 16)) return rc;
@@ -491,64 +441,30 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
 // v_*: the caller's arrays as the device addresses them.  msgs_d / ff: see wire_dec_fused_kernel (raftq_step_frames).
 static int decode_streaming_enqueue(raftq_t* h, const void* v_stream, uint64_t nbytes, const void* v_off, uint64_t n, void* v_msgs, void* v_ents,
                                     uint64_t ents_cap, WireMsg* msgs_d, FrameFilter ff) {
-  const unsigned tb = dec_tile();
-  const uint32_t n_tiles = (uint32_t)((n + tb - 1) / tb);
-  // 128-frame tiles: every workgroup that fits (34 KB of LDS: four per CU, the readers' share taken off).  256-frame tiles: 208, one per
-  // CU beside the readers as in round 5 -- at 68 KB two fit, but 464 workers measured SLOWER than 208 (173.9 against 167.6 us a call,
-  // profiles/r06/wire_tile_ab.jsonl): with 256 tiles in a 64K-frame call every tile has its own waiting worker at 208 already, and
-  // twice the workgroups are twice the pollers of the chunk flags
-  const unsigned workers = fused_grid(n_tiles, tb == 128 ? 1024u - 96u : 208u);
+  const uint32_t n_tiles = (uint32_t)((n + kDecTile - 1) / kDecTile);
+  // 208 workers, one per CU beside the readers as in round 5 -- at 68 KB two fit, but 464 workers measured SLOWER than 208 (173.9
+  // against 167.6 us a call, profiles/r06/wire_tile_ab.jsonl): with 256 tiles in a 64K-frame call every tile has its own waiting
+  // worker at 208 already, and twice the workgroups are twice the pollers of the chunk flags
+  const unsigned workers = fused_grid(n_tiles);
   Carver c;
   const void* const src[3] = {v_off, v_stream, nullptr};
   const uint64_t bytes[3] = {(n + 1) * 8, nbytes, 0};
   TileCtl ctl;
-  if (int rc = tile_ctl(h, std::max<uint64_t>(n_tiles, (bytes[0] + bytes[1]) / feed_chunk() + 1), &ctl)) return rc;
-  FeedPlan plan = plan_feed(c, src, bytes, h->wire_lb_tiles, tb == 128 ? 96u : 48u);
-  const size_t o_spill = c.take((size_t)n_tiles * tb * kEntQ * sizeof(WireEnt));  // a slot of kEntQ entry headers per lane
+  if (int rc = tile_ctl(h, std::max<uint64_t>(n_tiles, (bytes[0] + bytes[1]) / kFeedChunk + 1), &ctl)) return rc;
+  FeedPlan plan = plan_feed(c, src, bytes, h->wire_lb_tiles);
+  const size_t o_spill = c.take((size_t)n_tiles * kDecTile * kEntQ * sizeof(WireEnt));  // a slot of kEntQ entry headers per lane
   if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, c.off)) return rc;
-  const bool sdma = sdma_chunk() != 0;
-  if (sdma) plan.in.readers = 0;
   if (int rc = bind_feed(h, plan, (uint8_t*)h->wire_dev, ctl.status[kLbFlags])) return rc;
   WireEnt* spill = (WireEnt*)((uint8_t*)h->wire_dev + o_spill);
-  if (sdma) {
-    plan.in.no_serve = 1;  // nobody draws a chunk ticket
-    if (!h->wire_copy_stream) {
-      HIPCHK(h, hipStreamCreateWithFlags(&h->wire_copy_stream, hipStreamNonBlocking));
-      HIPCHK(h, hipEventCreateWithFlags(&h->wire_copy_ev, hipEventDisableTiming));
-    }
-    HIPCHK(h, hipEventRecord(h->wire_copy_ev, h->stream));  // the scratch's previous user is done before a copy lands in it
-    HIPCHK(h, hipStreamWaitEvent(h->wire_copy_stream, h->wire_copy_ev, 0));
-  }
-  if (tb == 128)
-    hipLaunchKernelGGL(wire_dec_fused_kernel<128>, dim3(plan.in.readers + workers), dim3(128), 0, h->stream, plan.in, nbytes, n, (WireMsg*)v_msgs,
-                       (WireEnt*)v_ents, ents_cap, ctl, h->wire_pin_d, msgs_d, ff, spill);
-  else
-    hipLaunchKernelGGL(wire_dec_fused_kernel<256>, dim3(plan.in.readers + workers), dim3(256), 0, h->stream, plan.in, nbytes, n, (WireMsg*)v_msgs,
-                       (WireEnt*)v_ents, ents_cap, ctl, h->wire_pin_d, msgs_d, ff, spill);
+  hipLaunchKernelGGL(wire_dec_fused_kernel<kDecTile>, dim3(plan.in.readers + workers), dim3(kDecTile), 0, h->stream, plan.in, nbytes, n, (WireMsg*)v_msgs,
+                     (WireEnt*)v_ents, ents_cap, ctl, h->wire_pin_d, msgs_d, ff, spill);
   HIPCHK(h, hipGetLastError());
   tile_ctl_launched(h, n_tiles, workers);
-  h->wire_last_tiles = n_tiles;
-  if (sdma) {  // behind the launch: the kernel's workers are already waiting for the flags
-    const uint64_t word = lb_word(ctl.epoch, kLbInclusive, 0);
-    for (uint32_t ck = 0; ck < plan.in.chunks; ++ck) {
-      for (int k = 0; k < 2; ++k) {
-        const FeedSeg& sg = plan.in.seg[k];
-        const uint64_t lo = (uint64_t)ck * sg.per_chunk;
-        if (sg.bytes == 0 || lo >= sg.bytes) continue;
-        const uint64_t len = std::min<uint64_t>(sg.per_chunk, sg.bytes - lo);
-        HIPCHK(h, hipMemcpyAsync(sg.dst + lo, sg.src + lo, len, hipMemcpyDefault, h->wire_copy_stream));
-      }
-      HIPCHK(h, hipStreamWriteValue64(h->wire_copy_stream, (void*)(plan.in.flag + ck), word, 0));
-    }
-  }
   return RAFTQ_OK;
 }
 // ... after the wait that covers it.  too_many_is_error: raftq_wire_decode's contract; raftq_step_frames only reports the count.
 static int decode_streaming_finish(raftq_t* h, const char* who, const uint64_t* frame_off, uint64_t n, bool have_ents, uint64_t ents_cap,
                                    bool too_many_is_error, raftq_wire_counts_t* counts) {
-#if defined(RAFTQ_WIRE_TRACE)
-  trace_dump(h, "wire_dec", h->wire_last_tiles);
-#endif
   if (int rc = tile_ctl_check(h, who)) return rc;
   const uint64_t total = h->wire_pin[0];
   if (counts) {
@@ -635,7 +551,7 @@ int raftq_detail::respond_prepare(raftq_t* h, const void* stream, uint64_t nbyte
     const void* const src[3] = {nullptr, nullptr, nullptr};
     const uint64_t sizes[3] = {0, 0, 0};
     const uint64_t extra[3] = {p->n_max * sizeof(WireMsg), 0, 0};
-    (void)plan_feed(fc, src, sizes, h->wire_lb_tiles, 48u, extra);
+    (void)plan_feed(fc, src, sizes, h->wire_lb_tiles, extra);
     if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, fc.off)) return rc;
     if (int rc = grow(h, &h->wire_out, &h->wire_out_bytes, p->cap + 16)) return rc;
   }
@@ -666,7 +582,7 @@ int raftq_detail::respond_enqueue(raftq_t* h, const RespPlan& p) {
     const uint64_t extra[3] = {p.n_max * sizeof(WireMsg), 0, 0};
     TileCtl ctl;
     if (int rc = tile_ctl(h, n_tiles, &ctl)) return rc;
-    FeedPlan plan = plan_feed(fc, src, sizes, h->wire_lb_tiles, 48u, extra);
+    FeedPlan plan = plan_feed(fc, src, sizes, h->wire_lb_tiles, extra);
     if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, fc.off)) return rc;
     if (int rc = grow(h, &h->wire_out, &h->wire_out_bytes, p.cap + 16)) return rc;
     if (int rc = bind_feed(h, plan, (uint8_t*)h->wire_dev, ctl.status[kLbFlags])) return rc;
@@ -784,7 +700,7 @@ static int wal_streaming_enqueue(raftq_t* h, const void* v_recs, uint64_t n, con
   const void* const src[3] = {v_recs, v_pool, nullptr};
   const uint64_t sizes[3] = {n * sizeof(WalRec), pool_bytes, 0};
   TileCtl ctl;
-  if (int rc = tile_ctl(h, std::max<uint64_t>(n_tiles, (sizes[0] + sizes[1]) / feed_chunk() + 1), &ctl)) return rc;
+  if (int rc = tile_ctl(h, std::max<uint64_t>(n_tiles, (sizes[0] + sizes[1]) / kFeedChunk + 1), &ctl)) return rc;
   FeedPlan plan = plan_feed(fc, src, sizes, h->wire_lb_tiles);
   if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, fc.off)) return rc;
   if (int rc = grow(h, &h->wire_out, &h->wire_out_bytes, cap + 16)) return rc;
@@ -970,7 +886,7 @@ int raftq_wal_decode(raftq_t* h, const void* bytes, uint64_t nbytes, const uint6
       const void* const src[3] = {f_off, f_bytes, nullptr};
       const uint64_t sizes[3] = {(n + 1) * 8, nbytes, 0};
       TileCtl ctl;
-      if (int rc = tile_ctl(h, std::max<uint64_t>(n_tiles, (sizes[0] + sizes[1]) / feed_chunk() + 1), &ctl)) return rc;
+      if (int rc = tile_ctl(h, std::max<uint64_t>(n_tiles, (sizes[0] + sizes[1]) / kFeedChunk + 1), &ctl)) return rc;
       FeedPlan plan = plan_feed(c, src, sizes, h->wire_lb_tiles);
       if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, c.off)) return rc;
       if (int rc = bind_feed(h, plan, (uint8_t*)h->wire_dev, ctl.status[kLbFlags])) return rc;

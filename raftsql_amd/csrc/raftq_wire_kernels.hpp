@@ -659,8 +659,8 @@ static __global__ __launch_bounds__(kBlock) void wire_dec_ents_kernel(const uint
 // Tickets (not blockIdx) order the tiles, and readers are the launch's first workgroups: whatever a worker waits for has
 // been claimed by a running workgroup, so nothing deadlocks however few workgroups are resident.
 constexpr int kLbValueBits = 46, kLbFlagShift = 46, kLbEpochShift = 48;
-constexpr int kLbArrays = 6;  // [0..3] running sums of a kernel, [4] spare (measurement builds: phase stamps), [5] the readers' chunk flags
-constexpr int kLbFlags = 5, kLbSpare = 4;
+constexpr int kLbArrays = 5;  // [0..3] running sums of a kernel, [4] the readers' chunk flags
+constexpr int kLbFlags = 4;
 constexpr uint64_t kLbValueMask = (1ull << kLbValueBits) - 1;
 constexpr uint32_t kLbAggregate = 1, kLbInclusive = 2;
 
@@ -668,7 +668,6 @@ struct TileCtl {
   unsigned int* ticket;            // monotonic across calls: tile = ticket - ticket_base; ticket[1] = "a wait gave up"
   uint32_t ticket_base;
   uint32_t epoch;                  // 1 .. 0xffff: status words of older calls read as "not yet"
-  uint32_t ablate;                 // measurement builds (RAFTQ_WIRE_TRACE) only: bit 0 = records stay, bit 1 = entry headers stay
   unsigned long long* status[kLbArrays];  // [n_tiles] each: independent running sums (a kernel uses the first two or three)
 };
 
@@ -736,23 +735,15 @@ struct InFeed {
   // readers there were dispatched before it.
   unsigned int* chunk_ticket;
   uint32_t chunk_base;
-  uint32_t no_serve;  // the chunks are not the kernel's to bring in at all (RAFTQ_WIRE_SDMA: the runtime's copy engine does): workers only wait
 };
 
 // Agent-scope write-through of one 16-byte quad as ONE store instruction (`global_store_dwordx4 ... sc1`).  Round 4 split the
 // quad into two 8-byte agent-scope atomic stores -- the widest store the atomic builtins express -- and every 8 bytes became a
 // 32-byte write request: the scratch hop's HBM traffic was x2.5-x3 of its bytes (profiles/pmc_traffic_legs.json, r04).  Four
 // lanes now fill a 64-byte request.  The compiler does not count an asm store in its vmcnt bookkeeping: whoever publishes the
-// bytes waits with an explicit s_waitcnt vmcnt(0) (reader_role does, before the chunk's flag).  RAFTQ_WIRE_SC1_SPLIT builds
-// the old form for an A/B.
+// bytes waits with an explicit s_waitcnt vmcnt(0) (reader_role does, before the chunk's flag).
 __device__ __forceinline__ void sc1_store16(uint8_t* dst, u32x4 v) {
-#if defined(RAFTQ_WIRE_SC1_SPLIT)
-  unsigned long long lo = ((unsigned long long)v.y << 32) | v.x, hi = ((unsigned long long)v.w << 32) | v.z;
-  __hip_atomic_store(reinterpret_cast<unsigned long long*>(dst), lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(reinterpret_cast<unsigned long long*>(dst) + 1, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
   asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(dst), "v"(v) : "memory");
-#endif
 }
 
 // chunk c of the call, host -> scratch, by the whole workgroup; its flag once every byte has reached the coherence point
@@ -790,18 +781,12 @@ template <int TB = kBlock>
 __device__ inline void reader_role(const InFeed& in, uint32_t epoch) {
   __shared__ uint32_t chunk_slot;
   const uint32_t tid = threadIdx.x;
-#if defined(RAFTQ_WIRE_STATIC_CHUNKS)  // round 4's assignment, for the A/B that shows what it does under several resident launches
-  for (uint32_t c = blockIdx.x;; c += in.readers) {
-    if (c >= in.chunks) return;
-    (void)chunk_slot;  // (the ticket word is not used in this build)
-#else
   for (;;) {
     __syncthreads();  // (the previous round's readers of chunk_slot are done)
     if (tid == 0) chunk_slot = atomicAdd(in.chunk_ticket, 1u) - in.chunk_base;
     __syncthreads();
     const uint32_t c = chunk_slot;
     if (c >= in.chunks) return;  // every reader workgroup draws exactly one ticket beyond the chunks
-#endif
     feed_copy_chunk<TB>(in, c, epoch);
   }
 }
@@ -821,8 +806,8 @@ __device__ inline void reader_role(const InFeed& in, uint32_t epoch) {
 // waits are for chunks and for tiles below its own -- by induction over the tile index no worker waits for work that no
 // resident workgroup holds, whatever the dispatcher does, down to a launch with NO reader workgroups at all
 // (RAFTQ_WIRE_READERS=0, tests/test_wire_gpu.py::test_streaming_codecs_without_readers).  The normal path is unchanged: the
-// ticket moves all the time, no worker ever serves.  (RAFTQ_WIRE_STATIC_CHUNKS -- round 4's ownership by position, kept for
-// the soak's A/B -- has no ticket to claim: it waits as it did, and still fails the soak.)
+// ticket moves all the time, no worker ever serves.  (Round 4's ownership by position has no ticket to claim: its workers
+// waited as round 5's did, and failed the soak; it was measured and removed.)
 constexpr uint32_t kFeedLookEvery = 16, kFeedStall = 64;
 constexpr uint32_t kFeedReady = 0, kFeedGaveUp = 1, kFeedServe = 2;  // kFeedServe + c: copy chunk c, then ask again
 // ONE lane
@@ -832,8 +817,7 @@ __device__ inline uint32_t feed_poll(const InFeed& in, uint32_t epoch, uint32_t 
   for (uint32_t spin = 0; spin < (1u << 23); ++spin) {
     const uint64_t s = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if ((uint32_t)(s >> kLbEpochShift) == epoch && ((s >> kLbFlagShift) & 3u) != 0) return kFeedReady;
-#if !defined(RAFTQ_WIRE_STATIC_CHUNKS)
-    if (!in.no_serve && (eager || (spin & (kFeedLookEvery - 1)) == kFeedLookEvery - 1)) {
+    if (eager || (spin & (kFeedLookEvery - 1)) == kFeedLookEvery - 1) {
       const uint32_t raw = __hip_atomic_load(in.chunk_ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       const uint32_t t = raw - in.chunk_base;  // chunks claimed so far (readers draw past the end: may exceed in.chunks)
       if (t > c) {
@@ -849,7 +833,6 @@ __device__ inline uint32_t feed_poll(const InFeed& in, uint32_t epoch, uint32_t 
         still = 0;  // somebody else moved it
       }
     }
-#endif
     __builtin_amdgcn_s_sleep(2);
   }
   atomicOr(stuck, 1u);
@@ -980,17 +963,6 @@ __device__ __forceinline__ WaveStage stage_wave_frames_dma(const uint8_t* stream
   return st;
 }
 
-// -DRAFTQ_WIRE_TRACE (measurement builds only): lane 0 of every tile leaves wall-clock stamps (100 MHz) of its phases in
-// the spare status array, raftq_wire.hip prints them after the call; RAFTQ_WIRE_ABLATE drops outputs
-#if defined(RAFTQ_WIRE_TRACE)
-#define RAFTQ_TRACE_STAMP(ctl, tile, k) \
-  do { if (threadIdx.x == 0) (ctl).status[kLbSpare][(uint64_t)(tile) * 8 + (k)] = wall_clock64(); } while (0)
-#define RAFTQ_ABLATE(ctl, bit) (((ctl).ablate >> (bit)) & 1u)
-#else
-#define RAFTQ_TRACE_STAMP(ctl, tile, k) do { } while (0)
-#define RAFTQ_ABLATE(ctl, bit) false
-#endif
-
 // raftq_wire_decode on page-locked buffers: everything in one launch (see above).  Readers bring the frame boundaries
 // (array 0) and the stream (array 1) into the scratch; msgs_h / ents_h are the caller's result arrays as the device
 // addresses them.  pin[0] = entries found, pin[1] = malformed frames (written by the worker of the last tile, whose
@@ -1012,12 +984,11 @@ constexpr uint8_t kFrameSkip = 0x10, kFrameHold = 0x20, kFrameBarrier = 0x40, kF
 // fields' file (34 KB), the frames' stage (32 KB), four entry headers per lane (32 KB): ONE workgroup per CU, one wave per SIMD,
 // and every reader workgroup of the launch paid for the same 102 KB.  Now the entry headers a lane meets on its one walk go to
 // a slot of its own in device scratch (`ent_spill`: 15 % of the lanes write one to three 32-byte headers; they are read back,
-// L2-resident, when the tile's run is gathered behind the look-back), and the tile is a template parameter: 128 frames =
-// 34.3 KB (four workgroups per CU, every tile of a 64K-frame call resident at once, each waiting for its own bytes);
-// 256 frames = 68.5 KB (two per CU).  RAFTQ_WIRE_TILE picks.  MEASURED (profiles/r06/wire_tile_ab.jsonl, 64K frames, one box, one
-// process): 256 frames 172 us a call, 128 frames 186 -- residency is not what bounds a call (every tile has a worker waiting
-// for its bytes either way; the call is its input over the link plus ONE tile's chain), and twice the tiles are twice the
-// look-back words, barriers and status traffic.  256 is the default; both are tested.
+// L2-resident, when the tile's run is gathered behind the look-back): 256 frames = 68.5 KB (two per CU).  A 128-frame tile
+// (34.3 KB, four per CU, every tile of a 64K-frame call resident at once) was MEASURED (profiles/r06/wire_tile_ab.jsonl, 64K
+// frames, one box, one process): 256 frames 172 us a call, 128 frames 186 -- residency is not what bounds a call (every tile
+// has a worker waiting for its bytes either way; the call is its input over the link plus ONE tile's chain), and twice the
+// tiles are twice the look-back words, barriers and status traffic.  It was removed; only <256> is launched.
 template <int TB>
 static __global__ __launch_bounds__(TB) void wire_dec_fused_kernel(InFeed in, uint64_t nbytes, uint64_t n, WireMsg* msgs_h, WireEnt* ents_h,
                                                                    uint64_t ents_cap, TileCtl ctl, uint64_t* __restrict__ pin,
@@ -1034,16 +1005,6 @@ static __global__ __launch_bounds__(TB) void wire_dec_fused_kernel(InFeed in, ui
   __shared__ uint64_t prefix[2];
   __shared__ uint32_t wave_bad[W];
   __shared__ uint32_t tile_slot, feed_slot;
-#if defined(RAFTQ_WIRE_LDS_PAD)
-  // measurement builds only (tools/gpurun_trip.sh soakpad*): round 5's LDS footprint back -- 102 KB, ONE workgroup per CU -- so that
-  // several handles' launches oversubscribe the chip again and the soak meets the residency that starved round 4's readers
-  __shared__ uint32_t lds_pad[RAFTQ_WIRE_LDS_PAD / 4];
-  if (n == ~0ull) {  // (never true: a store and a load the compiler cannot fold keep the array)
-    lds_pad[(threadIdx.x * 977u + ctl.epoch) % (RAFTQ_WIRE_LDS_PAD / 4)] = threadIdx.x;
-    __syncthreads();
-    pin[4 + (threadIdx.x & 1)] = lds_pad[(threadIdx.x * 331u + ctl.ticket_base) % (RAFTQ_WIRE_LDS_PAD / 4)];
-  }
-#endif
   const uint64_t* off = reinterpret_cast<const uint64_t*>(in.seg[0].dst);
   const uint8_t* stream = in.seg[1].dst;
   const uint64_t readable = (nbytes + 15) & ~15ull;
@@ -1054,14 +1015,12 @@ static __global__ __launch_bounds__(TB) void wire_dec_fused_kernel(InFeed in, ui
   for (;;) {
     const uint32_t cur = next_tile(ctl, &tile_slot);
     if (cur >= n_tiles) return;
-    RAFTQ_TRACE_STAMP(ctl, cur, 0);
     const uint64_t tile0 = (uint64_t)cur * TB, i = tile0 + tid;
     const uint64_t last = tile0 + TB < n ? tile0 + TB : n;
     bool fed = feed_wait<TB>(in, ctl.epoch, 0, tile0 * 8, (last + 1) * 8, stuck, &feed_slot);  // the tile's TB + 1 boundaries are in the scratch
     if (i <= n) offs[tid] = __hip_atomic_load(off + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (tid == 0) offs[TB] = __hip_atomic_load(off + last, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
-    RAFTQ_TRACE_STAMP(ctl, cur, 1);
     const bool live = i < n;
     const uint64_t a = live ? offs[tid] : 0, b = live ? offs[tid + 1] : 0;
     // ... and so are its frames: [first boundary, last boundary) when the boundaries ascend inside the buffer, else (garbage
@@ -1070,9 +1029,7 @@ static __global__ __launch_bounds__(TB) void wire_dec_fused_kernel(InFeed in, ui
     if (ordered) fed &= feed_wait<TB>(in, ctl.epoch, 1, offs[0], offs[last - tile0], stuck, &feed_slot);
     else fed &= feed_wait_all<TB>(in, ctl.epoch, stuck, &feed_slot);
     const WaveStage st = stage_wave_frames_dma(stream, nbytes, readable, a, b, live && fed, stage[wave]);
-    RAFTQ_TRACE_STAMP(ctl, cur, 2);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    RAFTQ_TRACE_STAMP(ctl, cur, 3);
     WireMsg m;
     bool malformed = false;
     LdsFileT<TB> f{file + tid};
@@ -1109,7 +1066,6 @@ static __global__ __launch_bounds__(TB) void wire_dec_fused_kernel(InFeed in, ui
     if ((tid & 63) == 0) wave_bad[wave] = (uint32_t)__popcll(mb);
     uint64_t tile_ents;
     const uint64_t local = block_exclusive_u32<W>(cnt, wave_tot, &tile_ents);  // (its barrier publishes wave_bad too)
-    RAFTQ_TRACE_STAMP(ctl, cur, 4);
     if (tid == 0) {
       uint32_t tile_bad = 0;
       for (int k = 0; k < W; ++k) tile_bad += wave_bad[k];
@@ -1123,7 +1079,6 @@ static __global__ __launch_bounds__(TB) void wire_dec_fused_kernel(InFeed in, ui
       }
     }
     __syncthreads();
-    RAFTQ_TRACE_STAMP(ctl, cur, 5);
     const uint64_t first = prefix[0] + local;
     if (cnt != 0) m.ent_first = (uint32_t)first;
     if (cnt > kEntQ && ents_h != nullptr) {  // a frame with more entries than a lane keeps: walked again, headers straight out
@@ -1142,10 +1097,8 @@ static __global__ __launch_bounds__(TB) void wire_dec_fused_kernel(InFeed in, ui
       for (uint32_t k = 0; k < kEntQ; ++k)
         if (k < cnt) ent_run[local + k] = my_ents[k];
     }
-    tile_records_out<WireMsg, TB>(m, live && !RAFTQ_ABLATE(ctl, 0), reinterpret_cast<u32x4*>(file), RAFTQ_ABLATE(ctl, 0) ? msgs_h - tile0 : msgs_h, tile0,
-                                  RAFTQ_ABLATE(ctl, 0) ? tile0 + 1 : n, msgs_d);  // (its barrier publishes ent_run too)
-    RAFTQ_TRACE_STAMP(ctl, cur, 6);
-    if (ents_h != nullptr && tile_ents != 0 && !RAFTQ_ABLATE(ctl, 1)) {
+    tile_records_out<WireMsg, TB>(m, live, reinterpret_cast<u32x4*>(file), msgs_h, tile0, n, msgs_d);  // (its barrier publishes ent_run too)
+    if (ents_h != nullptr && tile_ents != 0) {
       const uint64_t run0 = prefix[0];
       if (run_staged) {
         const uint64_t room = run0 < ents_cap ? ents_cap - run0 : 0;
@@ -1158,7 +1111,6 @@ static __global__ __launch_bounds__(TB) void wire_dec_fused_kernel(InFeed in, ui
           if (first + k < ents_cap) ents_h[first + k] = my_ents[k];
       }
     }
-    RAFTQ_TRACE_STAMP(ctl, cur, 7);
   }
 }
 

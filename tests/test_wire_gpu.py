@@ -314,7 +314,7 @@ def _form(monkeypatch, form):
     monkeypatch.setenv("RAFTQ_WIRE_STREAMING", "1" if form == "streaming" else "0")
 
 
-@pytest.mark.parametrize("copies", ["streaming", "streaming-128", "copying"])
+@pytest.mark.parametrize("copies", ["streaming", "copying"])
 @pytest.mark.parametrize("seed,n,big", [(171, 1, 0), (172, 900, 4), (173, 6000, 0), (174, 333, 1)])
 def test_codecs_on_page_locked_buffers(seed, n, big, copies, monkeypatch):
     """What a node hands the codecs every turn: every buffer page-locked.  The call is then ONE launch with ONE wait and has to
@@ -327,9 +327,6 @@ def test_codecs_on_page_locked_buffers(seed, n, big, copies, monkeypatch):
     from raftsql_amd.engine import pinned_copy, pinned_empty
     from raftsql_amd.wire import WireEngine
 
-    if copies == "streaming-128":  # the decoder's 128-frame tile (34 KB of LDS, four workgroups per CU; the default is 256 frames, 68 KB)
-        monkeypatch.setenv("RAFTQ_WIRE_TILE", "128")
-        copies = "streaming"
     _form(monkeypatch, copies)
     rng = np.random.default_rng(seed)
     with WireEngine(4096, 5, self_peer=0) as eng:
@@ -437,7 +434,7 @@ def test_wal_codecs_on_page_locked_buffers(seed, n, big, prev, copies, monkeypat
             assert (gnv, gl) == (wnv, wl) and gr.tobytes() == wr.tobytes()
 
 
-@pytest.mark.parametrize("tile", [128, 256])
+@pytest.mark.parametrize("tile", [256])  # frames per tile = threads per decoder workgroup
 @pytest.mark.parametrize("wgs", [5, 64, 160, 1024])
 def test_streaming_decode_at_bench_size(wgs, tile, monkeypatch):
     """The one-kernel form of raftq_wire_decode (page-locked buffers) at the bench's size -- 65,536 frames, a MsgApp share with
@@ -447,7 +444,6 @@ def test_streaming_decode_at_bench_size(wgs, tile, monkeypatch):
     from raftsql_amd.wire import WireEngine
 
     monkeypatch.setenv("RAFTQ_WIRE_WGS", str(wgs))
-    monkeypatch.setenv("RAFTQ_WIRE_TILE", str(tile))  # frames per tile = threads per decoder workgroup (256 is the default)
     rng = np.random.default_rng(1900 + wgs)
     n = 65536
     m, e, pool = _wiregen.random_msgs(rng, n, big_every=0, ent_frac=0.15)
@@ -467,7 +463,7 @@ def test_streaming_decode_at_bench_size(wgs, tile, monkeypatch):
             _same(ge, we, "ents")
 
 
-@pytest.mark.parametrize("tile", [128, 256])
+@pytest.mark.parametrize("tile", [256])
 @pytest.mark.parametrize("wgs", [7, 0])
 def test_streaming_codecs_without_readers(wgs, tile, monkeypatch):
     """liveness of a codec call is structural, not a property of the dispatcher.  RAFTQ_WIRE_READERS=0
@@ -479,7 +475,6 @@ def test_streaming_codecs_without_readers(wgs, tile, monkeypatch):
     from raftsql_amd.wire import WireEngine
 
     monkeypatch.setenv("RAFTQ_WIRE_READERS", "0")
-    monkeypatch.setenv("RAFTQ_WIRE_TILE", str(tile))
     if wgs:
         monkeypatch.setenv("RAFTQ_WIRE_WGS", str(wgs))
     rng = np.random.default_rng(6100 + wgs + tile)

@@ -62,20 +62,10 @@ SUPP
     tests)     timeout 1500 python -m pytest tests -m gpu -x -q --timeout 300 > $P/gpu_tests.log 2>&1; echo "rc=$? $(tail -1 $P/gpu_tests.log)" ;;
     wiretests) timeout 900 python -m pytest tests/test_wire_gpu.py -m gpu -x -q --timeout 240 > $P/gpu_tests_wire.log 2>&1; echo "rc=$? $(tail -3 $P/gpu_tests_wire.log)" ;;
     ticktests) timeout 600 python -m pytest tests/test_parity_gpu.py tests/test_set_gpu.py tests/test_abi_gpu.py -m gpu -x -q -k "tick or election or abi or drive" > $P/gpu_tests_tick.log 2>&1; echo "rc=$? $(tail -3 $P/gpu_tests_tick.log)" ;;
-    tileab)    # the streaming decoder's launch shapes, one process: tile 128 / 256, readers, chunk, no readers at all, the SDMA-reader form
+    tileab)    # the streaming decoder's launch shapes, one process: the default, the grid, readers, no readers at all
       timeout 600 python tools/probe/wire_tile_ab.py > $P/wire_tile_ab.jsonl 2> $P/wire_tile_ab.err; echo "rc=$?"; cut -c1-220 $P/wire_tile_ab.jsonl ;;
     soak400)   # the bench's node legs 400 times, a fresh process each, 0 give-ups wanted
       timeout 3000 python tools/probe/node_legs_soak.py ${SOAK_RUNS:-400} > $P/node_legs_soak.txt 2>&1; echo "rc=$?"; tail -3 $P/node_legs_soak.txt ;;
-    soakstatic) # ... and with round 4's chunk ownership by position (libraftq_static_chunks.so, built by raftsql_amd/build.py build_lib(variant=)):
-               # the soak must still be able to see the bug it guards against
-      RAFTQ_LIB=$PWD/raftsql_amd/libraftq_static_chunks.so timeout 1500 python tools/probe/node_legs_soak.py ${SOAK_STATIC_RUNS:-120} > $P/node_legs_soak_static_chunks.txt 2>&1; echo "rc=$?"; grep -c FAILED $P/node_legs_soak_static_chunks.txt; tail -2 $P/node_legs_soak_static_chunks.txt ;;
-    soakpad)   # the same soak under ROUND 5's residency (decoder workgroups padded back to 102 KB of LDS: one per CU), where round 4's chunk
-               # ownership starved: libraftq_pad_static.so (pad + RAFTQ_WIRE_STATIC_CHUNKS: must FAIL some runs -- the soak sees the bug)
-               # and libraftq_pad.so (pad only: tickets + workers that serve themselves -- must not)
-      RAFTQ_LIB=$PWD/raftsql_amd/libraftq_pad_static.so timeout 1500 python tools/probe/node_legs_soak.py ${SOAK_PAD_RUNS:-100} > $P/node_legs_soak_pad_static_chunks.txt 2>&1; echo "static rc=$? failed: $(grep -c FAILED $P/node_legs_soak_pad_static_chunks.txt)"; tail -1 $P/node_legs_soak_pad_static_chunks.txt
-      RAFTQ_LIB=$PWD/raftsql_amd/libraftq_pad.so timeout 1500 python tools/probe/node_legs_soak.py ${SOAK_PAD_RUNS:-100} > $P/node_legs_soak_pad.txt 2>&1; echo "tickets + self-serve rc=$? failed: $(grep -c FAILED $P/node_legs_soak_pad.txt)"; tail -1 $P/node_legs_soak_pad.txt ;;
-    flagab)    # the completion word three ways (one-thread kernel | write-value packet | last workgroup to arrive), checked and timed
-      timeout 1500 bash tools/probe/flag_ab.sh > $P/flag_ab.txt 2>&1; echo "rc=$?"; cat $P/flag_ab.txt ;;
     steptests) timeout 900 python -m pytest tests/test_step_gpu.py tests/test_envelope_gpu.py tests/test_parity_gpu.py -m gpu -x -q --timeout 300 > $P/gpu_tests_step.log 2>&1; echo "rc=$? $(tail -3 $P/gpu_tests_step.log)" ;;
     nodetests) timeout 900 python -m pytest tests/test_node_gpu.py tests/test_node_scenarios_gpu.py tests/test_pipe_gpu.py -m gpu -x -q > $P/gpu_tests_node.log 2>&1; echo "rc=$? $(tail -3 $P/gpu_tests_node.log)" ;;
     bench)     # the driver's command: stdout = the ONE contract line (<= 4 KB), the full record (every side leg) beside it
@@ -94,8 +84,6 @@ PY
     onenode)   # one node on one GPU, scripted peers (bench.one_node_measure), as one handle and as four shard handles; with the phase clock
       SHARDS=1,4 timeout 300 python tools/profile_one_node.py > $P/one_node.json 2> $P/one_node.err; echo "rc=$?"
       RAFTQ_PROFILE=1 SHARDS=1 timeout 300 python tools/profile_one_node.py 2>&1 | grep "advance phases" | cut -c1-400 > $P/one_node_phases.txt; cat $P/one_node_phases.txt ;;
-    ablate)    # the streaming decoder with its outputs taken away (measurement build libraftq_wiretrace.so: build_lib(variant="wiretrace", defines={"RAFTQ_WIRE_TRACE": 1}))
-      RAFTQ_LIB=$PWD/raftsql_amd/libraftq_wiretrace.so timeout 300 python tools/probe/wire_ablate.py > $P/wire_ablate.jsonl 2> $P/wire_ablate.err; echo "rc=$?"; cut -c1-230 $P/wire_ablate.jsonl; tail -3 $P/wire_ablate.err ;;
     nodeab)    # the three-node leg with the proposals' MsgApps built on the device (shipped) and on the host (round 5's way), alternated
       for v in 1 0 1 0 1 0; do
         echo "RAFTQ_NODE_PROPOSE_DEVICE=$v $(RAFTQ_NODE_PROPOSE_DEVICE=$v timeout 300 python tools/profile_node.py 2>&1 | grep -o "'proposals_committed_everywhere_per_s': [0-9.e+]*" | head -1)"

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """raftq_tick_collect_lists + raftq_last_tick_lists at 1M groups (a third of them leaders: 350K MsgBeat groups, ~50K timers firing),
-the beats as a list and as a bitmap, timed around the library's calls -- for tools/probe/flag_ab.sh (RAFTQ_CYCLE_FLAG = kernel |
-packet | arrive; with RAFTQ_CYCLE_CHECK=1 every call cross-checks what it read at the flag against a full synchronisation)."""
+the beats as a list and as a bitmap, timed around the library's calls (with RAFTQ_CYCLE_CHECK=1 every call cross-checks what it
+read at the flag against a full synchronisation)."""
 import ctypes as C
 import json
 import os

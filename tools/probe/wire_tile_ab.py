@@ -1,10 +1,9 @@
 #!/usr/bin/env python3
 """A/B of the streaming decoder's launch shapes on the bench's traffic (65,536 frames, 15 % MsgApp with 1-3 entries), one process,
-one box: frames per tile / threads per workgroup (RAFTQ_WIRE_TILE = 128 | 256), reader workgroups, and the SDMA-reader form
-(RAFTQ_WIRE_SDMA = chunk KiB: the runtime's copies + hipStreamWriteValue64 bring the input in, the kernel only waits) that VERDICT
-r04 / r05 asked to be BUILT rather than argued from the link probe.  Every variant's records and entry headers are compared with
-the default form's (itself held to the oracle by tests/test_wire_gpu.py) before it is timed.  One JSON line per variant.
-  python tools/probe/wire_tile_ab.py > profiles/r06/wire_tile_ab.jsonl"""
+one box: worker and reader workgroups.  Every variant's records and entry headers are compared with the default form's (itself held
+to the oracle by tests/test_wire_gpu.py) before it is timed.  One JSON line per variant.  (Round 6 also ran 128-frame tiles, other
+chunk sizes and an SDMA-reader form through this tool, profiles/r06/wire_tile_ab.jsonl; all lost to the default and were removed.)
+  python tools/probe/wire_tile_ab.py > wire_tile_ab.jsonl"""
 import ctypes as C
 import json
 import os
@@ -41,25 +40,12 @@ ents["data_len"] = rng.integers(40, 120, ne)
 ents["data_off"] = np.cumsum(ents["data_len"]) - ents["data_len"]
 pool = rng.integers(0, 256, max(1, int(ents["data_len"].sum())), dtype=np.uint8)
 
-T128 = {"RAFTQ_WIRE_TILE": "128"}
 VARIANTS = [
     ("tile256 (default)", {}),
-    ("tile128", T128),
     ("tile256 workers208 (round 5's grid)", {"RAFTQ_WIRE_WGS": "208"}),
-    ("tile256 chunk4K", {"RAFTQ_WIRE_CHUNK": "4096"}),
-    ("tile256 chunk6K", {"RAFTQ_WIRE_CHUNK": "6144"}),
-    ("tile256 chunk16K", {"RAFTQ_WIRE_CHUNK": "16384"}),
     ("tile256 readers32", {"RAFTQ_WIRE_READERS": "32"}),
     ("tile256 readers96", {"RAFTQ_WIRE_READERS": "96"}),
-    ("tile128 readers48", dict(T128, RAFTQ_WIRE_READERS="48")),
-    ("tile128 readers144", dict(T128, RAFTQ_WIRE_READERS="144")),
-    ("tile128 chunk4K", dict(T128, RAFTQ_WIRE_CHUNK="4096")),
-    ("tile128 workers416", dict(T128, RAFTQ_WIRE_WGS="416")),
     ("tile256 no readers (every chunk self-served)", {"RAFTQ_WIRE_READERS": "0"}),
-    ("tile256 sdma 64K", {"RAFTQ_WIRE_SDMA": "64"}),
-    ("tile256 sdma 256K", {"RAFTQ_WIRE_SDMA": "256"}),
-    ("tile256 sdma 1M", {"RAFTQ_WIRE_SDMA": "1024"}),
-    ("tile256 sdma 4M (one copy per array)", {"RAFTQ_WIRE_SDMA": "4096"}),
 ]
 KEYS = sorted({k for _, env in VARIANTS for k in env})
 if os.environ.get("ONLY"):  # tools/pmc_legs.py's `decode` leg: the shipped form alone, nothing else of that kernel's name in the process
