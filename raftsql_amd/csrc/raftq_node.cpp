@@ -701,6 +701,20 @@ bool handle_proposal(raftq_node_t* n, uint64_t gi, Group& g, const Entry* ents, 
   return false;
 }
 
+// entries [k, n_ents) of the inbound message m onto g's log, their payloads into the arena; false: out of memory (n->oom)
+bool store_entries(raftq_node_t* n, Group& g, const raftq_wire_msg_t& m, size_t k) {
+  const raftq_wire_ent_t* ents = n->cur_ents + m.ent_first;
+  for (; k < m.n_ents; ++k) {
+    const char* at = n->arena.put(n->cur_bytes + ents[k].data_off, ents[k].data_len);
+    if (!at) {
+      n->oom = true;
+      return false;
+    }
+    g.log.push_back(n->pool, Entry{ents[k].term, at, ents[k].data_len});
+  }
+  return true;
+}
+
 // RAFTQ_OUT_APPENDED: Step found the MsgApp on the log's tail and did raftLog.maybeAppend's bookkeeping; the entries
 // themselves go into the log here.  false: they could not be stored (the node poisons itself at the end of the turn).
 bool store_at_tail(raftq_node_t* n, uint64_t gi, Group& g, const raftq_wire_msg_t& m) {
@@ -710,15 +724,7 @@ bool store_at_tail(raftq_node_t* n, uint64_t gi, Group& g, const raftq_wire_msg_
     return false;
   }
   if (m.n_ents == 0) return true;
-  const raftq_wire_ent_t* ents = n->cur_ents + m.ent_first;
-  for (uint32_t k = 0; k < m.n_ents; ++k) {
-    const char* at = n->arena.put(n->cur_bytes + ents[k].data_off, ents[k].data_len);
-    if (!at) {
-      n->oom = true;
-      return false;
-    }
-    g.log.push_back(n->pool, Entry{ents[k].term, at, ents[k].data_len});
-  }
+  if (!store_entries(n, g, m, 0)) return false;
   wal_touch(n, gi, g);
   return true;
 }
@@ -749,15 +755,10 @@ void follower_append(raftq_node_t* n, uint64_t gi, Group& g, const raftq_wire_ms
         break;
       }
     }
-    for (; k < m.n_ents; ++k) {
-      const char* at = n->arena.put(n->cur_bytes + ents[k].data_off, ents[k].data_len);
-      if (!at) {  // out of memory: the node poisons itself at the end of this turn; do not acknowledge what is not stored
-        n->oom = true;
-        n->out_lane[m.from].msgs.pop_back();
-        n->stats.msgs_sent--;
-        return;
-      }
-      g.log.push_back(n->pool, Entry{ents[k].term, at, ents[k].data_len});
+    if (!store_entries(n, g, m, k)) {  // out of memory: the node poisons itself at the end of this turn; do not acknowledge what is not stored
+      n->out_lane[m.from].msgs.pop_back();
+      n->stats.msgs_sent--;
+      return;
     }
     wal_touch(n, gi, g);
     const uint64_t lastnewi = m.index + m.n_ents;
@@ -776,37 +777,33 @@ void follower_append(raftq_node_t* n, uint64_t gi, Group& g, const raftq_wire_ms
   }
 }
 
-// report log tails to the engine, then publish whatever the reports committed.  Called with
-// `lk` held; the device call runs unlocked.  On failure returns with `lk` RELEASED (so the caller
-// can poison()), on success with it held again.
+// THE LOCK RULE of a turn.  `lk` is the turn's hold of n->mu.  Every function below that takes it (as an argument or inside a
+// Turn) is called with `lk` held and returns with `lk` held, whatever it returns; what runs with mu released -- every device
+// call -- runs inside the scope of an `Unlocked`.  poison() takes mu itself: a turn calls it in one place, at the end of
+// node_advance_impl, after unlocking; a phase that fails only returns its code (and its label, see fail()).
+struct Unlocked {
+  std::unique_lock<std::mutex>& lk;
+  explicit Unlocked(std::unique_lock<std::mutex>& l) : lk(l) { lk.unlock(); }
+  ~Unlocked() { lk.lock(); }
+};
+
+// report log tails to the engine, then publish whatever the reports committed
 int flush_deltas(raftq_node_t* n, std::unique_lock<std::mutex>& lk) {
   if (n->deltas.empty()) return RAFTQ_OK;
-  if (n->N > 1 && !n->deltas_need_result) {
-    // every report is a leader's appendEntry and there is more than one peer: raftLog.committed cannot move (the leader's own
-    // Match is the largest, the quorum-th largest is somebody else's) -- enqueued and left (raftq_apply_log_deltas_nowait);
-    // the engine's state has moved by the time the next Step runs
-    lk.unlock();
-    int rc;
-    {
-      DevCall dev(n, raftq_node::kPhDevDeltas);
-      rc = raftq_apply_log_deltas_nowait(n->h, n->deltas.data(), n->deltas.size());
-    }
-    if (rc != RAFTQ_OK) return rc;
-    lk.lock();
-    n->deltas.clear();
-    return RAFTQ_OK;
-  }
+  // every report is a leader's appendEntry and there is more than one peer: raftLog.committed cannot move (the leader's own
+  // Match is the largest, the quorum-th largest is somebody else's) -- enqueued and left (raftq_apply_log_deltas_nowait);
+  // the engine's state has moved by the time the next Step runs
+  const bool nowait = n->N > 1 && !n->deltas_need_result;
   n->deltas_need_result = false;
-  n->delta_commit.resize(n->deltas.size());
-  lk.unlock();
-  int rc;
+  if (!nowait) n->delta_commit.resize(n->deltas.size());
   {
+    Unlocked u(lk);
     DevCall dev(n, raftq_node::kPhDevDeltas);
-    rc = raftq_apply_log_deltas(n->h, n->deltas.data(), n->deltas.size(), n->delta_commit.data());
+    if (const int rc = nowait ? raftq_apply_log_deltas_nowait(n->h, n->deltas.data(), n->deltas.size())
+                              : raftq_apply_log_deltas(n->h, n->deltas.data(), n->deltas.size(), n->delta_commit.data()))
+      return rc;
   }
-  if (rc != RAFTQ_OK) return rc;
-  lk.lock();
-  const size_t nd = n->deltas.size();
+  const size_t nd = nowait ? 0 : n->deltas.size();
   for (size_t i = 0; i < nd; ++i) {
     if (i + 16 < nd) __builtin_prefetch(&n->groups[n->deltas[i + 16].group]);
     if (i + 8 < nd) ahead_of_publish(n->groups[n->deltas[i + 8].group]);
@@ -888,7 +885,7 @@ void apply_result(raftq_node_t* n, const raftq_step_out_t& o, const raftq_wire_m
       g.log.truncate(o.index - 1);
       g.wal_upto = std::min<uint64_t>(g.wal_upto, g.log.size());
       n->shared_group = ~0ull;
-        g.log.push_back(n->pool, Entry{o.term, "", 0});
+      g.log.push_back(n->pool, Entry{o.term, "", 0});
       wal_touch(n, gi, g);
       for (uint32_t p = 0; p < n->N; ++p) {  // reset(): Next = lastIndex + 1 (before the empty entry)
         n->next_of(gi, p) = o.index;
@@ -967,61 +964,52 @@ int poll_queue(raftq_node_t* n, PeerQueue& q, bool big_endian, void* buf, uint64
   return RAFTQ_OK;
 }
 
-// The second half of the WAL encode, in two steps so that a turn's WAL bytes are PUBLISHED BEFORE its outbound frames
-// (wal.Save before transport.Send, raft.go:228-230; the poll calls may run on a transport thread during advance(): a
-// thread that takes turn T's MsgAppResp off raftq_node_poll must find T's HardState / entries in raftq_node_wal_poll).
-// wal_end_device: the device wait, with mu released; wal_publish: the bytes onto wal_out, with mu held.
-int wal_end_device(raftq_node_t* n) {
-  if (n->wal_inflight == 0 || !n->wal_begun) return RAFTQ_OK;
-  const int rc = raftq_wal_encode_end(n->h, &n->wal_cnt);
-  n->wal_begun = false;
-  return rc;
-}
-void wal_publish(raftq_node_t* n) {
-  if (n->wal_inflight == 0) return;
+// The second half of the WAL encode.  A turn's WAL bytes are PUBLISHED BEFORE its outbound frames (wal.Save before
+// transport.Send, raft.go:228-230; the poll calls may run on a transport thread during advance(): a thread that takes turn T's
+// MsgAppResp off raftq_node_poll must find T's HardState / entries in raftq_node_wal_poll): the device wait runs with mu released (its time goes to
+// `bucket`), the bytes go onto wal_out with mu held again -- and the caller publishes the turn's frames under that same hold.
+int wal_end(raftq_node_t* n, std::unique_lock<std::mutex>& lk, int bucket) {
+  if (n->wal_inflight == 0) return RAFTQ_OK;
+  if (n->wal_begun) {
+    Unlocked u(lk);
+    DevCall dev(n, bucket);
+    const int rc = raftq_wal_encode_end(n->h, &n->wal_cnt);
+    n->wal_begun = false;
+    if (rc != RAFTQ_OK) return rc;
+  }
   n->wal_out.bytes.append((const char*)n->wal_enc.p, (size_t)n->wal_cnt.bytes);
   n->wal_crc = n->wal_cnt.last_crc;
   n->wal_head_written = true;
   n->stats.wal_records += n->wal_inflight;
   n->wal_inflight = 0;
-}
-// a turn with nothing to send: the WAL encode's wait is its own
-int flush_wal_end(raftq_node_t* n, std::unique_lock<std::mutex>& lk) {
-  if (n->wal_inflight == 0) return RAFTQ_OK;
-  if (n->wal_begun) {
-    lk.unlock();
-    if (const int rc = wal_end_device(n)) return rc;
-    lk.lock();
-  }
-  wal_publish(n);
   return RAFTQ_OK;
+}
+
+// frames [k0, k1) of an encoder's stream (`bytes`, frame k at [off[k], off[k + 1])) onto q, with their ends
+void append_frames(PeerQueue& q, const uint8_t* bytes, const uint64_t* off, uint64_t k0, uint64_t k1) {
+  if (k1 == k0) return;
+  if (q.bytes.empty()) q.reuse_spares();
+  const uint64_t from = off[k0], base = q.bytes.size();
+  q.bytes.append((const char*)bytes + from, (size_t)(off[k1] - from));
+  if (q.ends_ok) {
+    const size_t at = q.ends.size();
+    q.ends.resize(at + (size_t)(k1 - k0));
+    for (uint64_t k = k0; k < k1; ++k) q.ends[at + (k - k0)] = base + (off[k + 1] - from);
+  }
 }
 
 // the inbound round's device-built frames (raftq_step_frames_respond) onto peer p's queue, or every peer's (p = ~0u); the last peer
 // ends what is pending.  Called where the turn's frames are published, after its WAL.
 void publish_responses(raftq_node_t* n, uint32_t only) {
   if (!n->resp_pending) return;
-  const uint64_t* off = n->resp_off.data();
   const uint64_t* po = n->resp_peer.data();
-  for (uint32_t p = 0; p < n->N; ++p) {
-    if (only != ~0u && p != only) continue;
-    const uint64_t k0 = po[p], k1 = po[p + 1];
-    if (k1 == k0) continue;
-    PeerQueue& q = n->outbound[p];
-    if (q.bytes.empty()) q.reuse_spares();
-    const uint64_t from = off[k0], base = q.bytes.size();
-    q.bytes.append((const char*)n->resp_out.p + from, (size_t)(off[k1] - from));
-    if (q.ends_ok) {
-      const size_t at = q.ends.size();
-      q.ends.resize(at + (size_t)(k1 - k0));
-      for (uint64_t k = k0; k < k1; ++k) q.ends[at + (k - k0)] = base + (off[k + 1] - from);
-    }
-  }
+  for (uint32_t p = 0; p < n->N; ++p)
+    if (only == ~0u || p == only) append_frames(n->outbound[p], n->resp_out.p, n->resp_off.data(), po[p], po[p + 1]);
   if (only == ~0u || only == n->N - 1) n->resp_pending = false;
 }
 
 // rc.transport.Send(rd.Messages) (raft.go:230) for the whole turn: one batched marshal on the GPU, then
-// every peer's slice of the stream goes onto its queue.  Lock convention as flush_deltas.
+// every peer's slice of the stream goes onto its queue -- behind the turn's WAL bytes (wal_end).
 int flush_outbound(raftq_node_t* n, std::unique_lock<std::mutex>& lk) {
   size_t nm = 0;
   uint64_t cap = 0;  // an upper bound of the stream, kept by send() / attach()
@@ -1036,29 +1024,16 @@ int flush_outbound(raftq_node_t* n, std::unique_lock<std::mutex>& lk) {
   cap += n_props ? n->prop_cap * (n->N - 1) : 0;
   if (nm + n_dev == 0) {
     if (!n->resp_pending) return RAFTQ_OK;
-    // only device-built responses this turn: the WAL first, then the frames (wal.Save before transport.Send)
-    lk.unlock();
-    int rc;
-    {
-      DevCall dev(n, raftq_node::kPhDevEncode);
-      rc = wal_end_device(n);
-    }
-    if (rc != RAFTQ_OK) return rc;
-    lk.lock();
-    wal_publish(n);
+    // only device-built responses this turn: the WAL first, then the frames
+    if (const int rc = wal_end(n, lk, raftq_node::kPhDevEncode)) return rc;
     publish_responses(n, ~0u);
     return RAFTQ_OK;
   }
-  if (n->out_oom) {
-    lk.unlock();
-    return RAFTQ_ENOMEM;
-  }
+  if (n->out_oom) return RAFTQ_ENOMEM;
   // the lanes back to back: per-peer order is the order of the sends, and every peer's frames are one slice of the stream
   n->enc_msgs.clear();
-  if (!n->enc_off.resize(nm + n_dev + 1) || !n->enc_msgs.reserve(std::max<size_t>(nm, 1) * sizeof(raftq_wire_msg_t)) || !n->enc_out.reserve(cap)) {
-    lk.unlock();
+  if (!n->enc_off.resize(nm + n_dev + 1) || !n->enc_msgs.reserve(std::max<size_t>(nm, 1) * sizeof(raftq_wire_msg_t)) || !n->enc_out.reserve(cap))
     return RAFTQ_ENOMEM;
-  }
   std::vector<uint64_t>& first = n->lane_first;
   first.assign(n->N + 1, 0);
   for (uint32_t p = 0; p < n->N; ++p) {
@@ -1073,51 +1048,32 @@ int flush_outbound(raftq_node_t* n, std::unique_lock<std::mutex>& lk) {
   const size_t n_ents = n->out_ents.count<raftq_wire_ent_t>();
   n->shared_group = ~0ull;
   raftq_wire_counts_t cnt;
-  lk.unlock();  // send() only runs inside advance(), which this thread holds (turn_mu): out_* are safe to read unlocked
-  int rc;
   {
+    Unlocked u(lk);  // send() only runs inside advance(), which this thread holds (turn_mu): out_* are safe to read unlocked
     DevCall dev(n, raftq_node::kPhDevEncode);
-    if (n_props)
-      rc = raftq_propose_frames(n->h, n->prop_recs.as<raftq_prop_t>(), n_props, n->prop_ents.as<raftq_prop_ent_t>(), n_pents, nm ? sorted : nullptr, nm,
-                                n_ents ? ents : nullptr, n_ents, n->out_pool.p, n->out_pool.size, n->enc_out.p, cap, n->enc_off.data(), &cnt);
-    else
-      rc = raftq_wire_encode(n->h, sorted, nm, ents, n_ents, n->out_pool.p, n->out_pool.size, n->enc_out.p, cap, n->enc_off.data(), &cnt);
+    const int rc =
+        n_props ? raftq_propose_frames(n->h, n->prop_recs.as<raftq_prop_t>(), n_props, n->prop_ents.as<raftq_prop_ent_t>(), n_pents,
+                                       nm ? sorted : nullptr, nm, n_ents ? ents : nullptr, n_ents, n->out_pool.p, n->out_pool.size, n->enc_out.p,
+                                       cap, n->enc_off.data(), &cnt)
+                : raftq_wire_encode(n->h, sorted, nm, ents, n_ents, n->out_pool.p, n->out_pool.size, n->enc_out.p, cap, n->enc_off.data(), &cnt);
+    if (rc != RAFTQ_OK) return rc;
   }
-  if (rc != RAFTQ_OK) return rc;
-  // the marshal's wait covered the WAL encode enqueued in front of it: take its verdict now, still unlocked, and publish the
-  // WAL bytes first, the frames second, under ONE hold of mu (the frames used to be visible a device call earlier)
-  {
-    DevCall dev(n, raftq_node::kPhDevEncode);
-    rc = wal_end_device(n);
-  }
-  if (rc != RAFTQ_OK) return rc;
-  lk.lock();
-  wal_publish(n);
+  // the marshal's wait covered the WAL encode enqueued in front of it: its verdict, then the WAL bytes first and the frames
+  // second under ONE hold of mu
+  if (const int rc = wal_end(n, lk, raftq_node::kPhDevEncode)) return rc;
   n->out_ents.clear();
   n->out_pool.clear();
   n->prop_recs.clear();
   n->prop_ents.clear();
-  const uint64_t* off = n->enc_off.data();
   // peer p's bytes: the slice of what the host queued for it, then (p != self) its run of the device-built MsgApps -- the order
   // of the sends: the proposals are the turn's last
-  auto take = [&](PeerQueue& q, uint64_t k0, uint64_t k1) {
-    if (k1 == k0) return;
-    if (q.bytes.empty()) q.reuse_spares();
-    const uint64_t from = off[k0], base = q.bytes.size();
-    q.bytes.append((const char*)n->enc_out.p + from, (size_t)(off[k1] - from));
-    if (q.ends_ok) {
-      const size_t at = q.ends.size();
-      q.ends.resize(at + (size_t)(k1 - k0));
-      for (uint64_t k = k0; k < k1; ++k) q.ends[at + (k - k0)] = base + (off[k + 1] - from);
-    }
-  };
   uint32_t run = 0;
   for (uint32_t p = 0; p < n->N; ++p) {
     PeerQueue& q = n->outbound[p];
     publish_responses(n, p);  // the device-built answers of the inbound round come first
-    take(q, first[p], first[p + 1]);
+    append_frames(q, n->enc_out.p, n->enc_off.data(), first[p], first[p + 1]);
     if (n_props && p != n->self) {
-      take(q, nm + (uint64_t)run * n_props, nm + (uint64_t)(run + 1) * n_props);
+      append_frames(q, n->enc_out.p, n->enc_off.data(), nm + (uint64_t)run * n_props, nm + (uint64_t)(run + 1) * n_props);
       ++run;
     }
   }
@@ -1176,21 +1132,22 @@ int flush_wal_begin(raftq_node_t* n, std::unique_lock<std::mutex>& lk) {
     put(RAFTQ_WAL_METADATA, 0, 0, 0, 0, nullptr);
     put(RAFTQ_WAL_SNAPSHOT, 0, 0, 0, 0, nullptr);
   }
-  for (uint64_t w = n->wal_lo; n->wal_n_dirty != 0 && w <= n->wal_hi; ++w)
-   for (uint64_t bits = n->wal_bits[w]; bits != 0; bits &= bits - 1) {  // groups ascending (wal.Save's order within a group: entries, then HardState)
-    const uint64_t gi = w * 64 + (uint64_t)__builtin_ctzll(bits);
-    Group& g = n->groups[gi];
-    g.wal_dirty = false;
-    if (!room(g.log.size() - std::min<uint64_t>(g.wal_upto, g.log.size()) + 1)) break;
-    for (uint64_t idx = g.wal_upto + 1; idx <= g.log.size(); ++idx) {
-      const Entry& e = g.log[idx - 1];
-      put(RAFTQ_WAL_ENTRY, gi, e.term, idx, 0, &e);
-    }
-    g.wal_upto = g.log.size();
-    const bool empty_hs = g.term == 0 && g.vote == 0 && g.committed == 0;  // `if !raft.IsEmptyHardState(st)`
-    if (!empty_hs && (g.term != g.wal_term || g.vote != g.wal_vote || g.committed != g.wal_commit)) {
-      // raft IDs are 1-based peer positions (raft.go:148-151), 0 = None: Vote goes out as it is
-      put(RAFTQ_WAL_STATE, gi, g.wal_term = g.term, g.wal_commit = g.committed, g.wal_vote = g.vote, nullptr);
+  for (uint64_t w = n->wal_lo; n->wal_n_dirty != 0 && w <= n->wal_hi; ++w) {
+    for (uint64_t bits = n->wal_bits[w]; bits != 0; bits &= bits - 1) {  // groups ascending (wal.Save's order within a group: entries, then HardState)
+      const uint64_t gi = w * 64 + (uint64_t)__builtin_ctzll(bits);
+      Group& g = n->groups[gi];
+      g.wal_dirty = false;
+      if (!room(g.log.size() - std::min<uint64_t>(g.wal_upto, g.log.size()) + 1)) break;
+      for (uint64_t idx = g.wal_upto + 1; idx <= g.log.size(); ++idx) {
+        const Entry& e = g.log[idx - 1];
+        put(RAFTQ_WAL_ENTRY, gi, e.term, idx, 0, &e);
+      }
+      g.wal_upto = g.log.size();
+      const bool empty_hs = g.term == 0 && g.vote == 0 && g.committed == 0;  // `if !raft.IsEmptyHardState(st)`
+      if (!empty_hs && (g.term != g.wal_term || g.vote != g.wal_vote || g.committed != g.wal_commit)) {
+        // raft IDs are 1-based peer positions (raft.go:148-151), 0 = None: Vote goes out as it is
+        put(RAFTQ_WAL_STATE, gi, g.wal_term = g.term, g.wal_commit = g.committed, g.wal_vote = g.vote, nullptr);
+      }
     }
   }
   for (uint64_t w = n->wal_lo; n->wal_n_dirty != 0 && w <= n->wal_hi; ++w) n->wal_bits[w] = 0;
@@ -1201,19 +1158,17 @@ int flush_wal_begin(raftq_node_t* n, std::unique_lock<std::mutex>& lk) {
   const size_t n_recs = n_put;
   if (n_recs == 0) return RAFTQ_OK;
   const uint64_t cap = (uint64_t)n_recs * 80 + pool.size;
-  if (oom || !n->wal_enc.reserve(cap)) {
-    lk.unlock();
-    return RAFTQ_ENOMEM;
-  }
+  if (oom || !n->wal_enc.reserve(cap)) return RAFTQ_ENOMEM;
   const uint32_t prev = n->wal_crc;
-  lk.unlock();
-  int rc = raftq_wal_encode_begin(n->h, recs.as<raftq_wal_rec_t>(), n_recs, pool.p, pool.size, prev, n->wal_enc.p, cap, nullptr);
-  n->wal_begun = rc == RAFTQ_OK;
-  if (rc == RAFTQ_EINVAL) {  // buffers the device cannot address: the whole call, now
-    rc = raftq_wal_encode(n->h, recs.as<raftq_wal_rec_t>(), n_recs, pool.p, pool.size, prev, n->wal_enc.p, cap, nullptr, &n->wal_cnt);
+  {
+    Unlocked u(lk);
+    int rc = raftq_wal_encode_begin(n->h, recs.as<raftq_wal_rec_t>(), n_recs, pool.p, pool.size, prev, n->wal_enc.p, cap, nullptr);
+    n->wal_begun = rc == RAFTQ_OK;
+    if (rc == RAFTQ_EINVAL) {  // buffers the device cannot address: the whole call, now
+      rc = raftq_wal_encode(n->h, recs.as<raftq_wal_rec_t>(), n_recs, pool.p, pool.size, prev, n->wal_enc.p, cap, nullptr, &n->wal_cnt);
+    }
+    if (rc != RAFTQ_OK) return rc;
   }
-  if (rc != RAFTQ_OK) return rc;
-  lk.lock();
   n->wal_inflight = n_recs;
   return RAFTQ_OK;
 }
@@ -1227,6 +1182,593 @@ bool log_put(raftq_node_t* n, Group& g, uint64_t index, uint64_t term, const cha
   if (!at) return false;
   g.log.push_back(n->pool, Entry{term, at, len});
   return true;
+}
+
+// what the phases of one turn share, on node_advance_impl's stack (the lists it works through are the handle's: n->work, ...)
+struct Turn {
+  raftq_node_t* n;
+  std::unique_lock<std::mutex>& lk;  // the turn's hold of n->mu: THE LOCK RULE, above flush_deltas
+  PhaseClock& ph;
+  Turn(raftq_node_t* node, std::unique_lock<std::mutex>& l, PhaseClock& p) : n(node), lk(l), ph(p) {}
+  uint32_t ticks = 0;
+  uint64_t nf = 0;                                 // inbound frames of the turn
+  const raftq_wire_msg_t* wm = nullptr;            // their decoded records
+  const raftq_step_out_s_t* fused_outs = nullptr;  // != nullptr: round 1 has been stepped, out[i] answers frame i
+  uint64_t dropped = 0;                            // frames that were nobody's
+  std::string what;                                // the failed phase's label, for poison()
+};
+
+int fail(Turn& t, int rc, const std::string& what) {
+  t.what = what;
+  return rc;
+}
+
+// the helpers of the per-message and per-statement loops are forced inline: those loops bound the one-node leg (README, "host side of a turn")
+#define RAFTQ_HOT __attribute__((always_inline)) inline
+
+// the turn's message at position ix (see kLocal): a locally raised one (n->local) or a decoded one (Turn::wm)
+RAFTQ_HOT const raftq_wire_msg_t& msg_at(const raftq_wire_msg_t* local, const raftq_wire_msg_t* wm, uint32_t ix) { return (ix & kLocal) ? local[ix & ~kLocal] : wm[ix]; }
+
+constexpr uint32_t kSlowBit = 0x80000000u;  // on a prop_mark: the group's proposals of this turn are the host's
+
+// a fresh value no mark holds
+uint32_t next_epoch(raftq_node_t* n) {
+  if (++n->epoch >= kSlowBit) {  // (below 2^31: the proposals' marks use the top bit)
+    std::fill(n->blocked_mark.begin(), n->blocked_mark.end(), 0u);
+    std::fill(n->dirty_mark.begin(), n->dirty_mark.end(), 0u);
+    std::fill(n->defer_mark.begin(), n->defer_mark.end(), 0u);
+    std::fill(n->prop_mark.begin(), n->prop_mark.end(), 0u);
+    n->epoch = 1;
+  }
+  return n->epoch;
+}
+
+// the group's log grew in the round / the proposals of epoch `ep`: listed once for flush_dirty
+RAFTQ_HOT void mark_dirty(raftq_node_t* n, uint64_t gi, uint32_t ep) {
+  if (n->dirty_mark[gi] != ep) {
+    n->dirty_mark[gi] = ep;
+    n->dirty_list.push_back(gi);
+  }
+}
+
+// the views of one inbound MsgProp's entries (payloads stay in the receive buffer)
+const Entry* prop_entries(raftq_node_t* n, const raftq_wire_msg_t& im) {
+  n->ent_tmp.clear();
+  for (uint32_t k = 0; k < im.n_ents; ++k) {
+    const raftq_wire_ent_t& e = n->cur_ents[im.ent_first + k];
+    n->ent_tmp.push_back(Entry{e.term, (const char*)n->cur_bytes + e.data_off, e.data_len});
+  }
+  return n->ent_tmp.data();
+}
+
+// report the grown logs' tails (n->dirty_list), publish what that committed, then bcastAppend
+int flush_dirty(raftq_node_t* n, std::unique_lock<std::mutex>& lk) {
+  const std::vector<uint64_t>& dirty = n->dirty_list;
+  const size_t nd = dirty.size();
+  for (size_t i = 0; i < nd; ++i) {
+    if (i + 16 < nd) __builtin_prefetch(&n->groups[dirty[i + 16]]);
+    const Group& g = n->groups[dirty[i]];
+    n->deltas.push_back(raftq_log_delta_t{dirty[i], g.log.size(), g.term, 0});
+  }
+  if (int rc = flush_deltas(n, lk)) return rc;
+  for (size_t i = 0; i < nd; ++i) {  // bcastAppend: the group's line, its Progress and the entry before Next
+    if (i + 16 < nd) __builtin_prefetch(&n->groups[dirty[i + 16]]);
+    if (i + 8 < nd) {
+      const Group& ahead = n->groups[dirty[i + 8]];
+      __builtin_prefetch(&n->prog[dirty[i + 8] * n->N * 2], 1);
+      if (!ahead.log.empty()) __builtin_prefetch(&ahead.log.back());
+    }
+    bcast_append(n, dirty[i], n->groups[dirty[i]]);
+  }
+  return RAFTQ_OK;
+}
+
+// this node leads the group and every follower's Progress.Next is lastIndex + 1: what bcastAppend leaves behind, every group
+// outside a catch-up.  Such a group's proposals may go through the device, and only such a group's bit may be set in at_tail.
+RAFTQ_HOT bool group_at_tail(raftq_node_t* n, uint64_t gi, const Group& g) {
+  bool ok = g.role == RAFTQ_ROLE_LEADER && g.leading;
+  const uint64_t tail = g.log.size() + 1;
+  for (uint32_t p = 0; ok && p < n->N; ++p)
+    if (p != n->self) ok = n->next_of(gi, p) == tail;
+  return ok;
+}
+
+// the turn's inputs, taken from under mu.  Non-zero: the node never started, or is in error already -- nothing to poison.
+int take_inputs(Turn& t) {
+  raftq_node_t* n = t.n;
+  if (!n->started) return RAFTQ_ESTATE;
+  if (n->error) return n->error;
+  n->work.clear();
+  n->local.clear();
+  n->turn_props.clear();
+  n->cur_ents = nullptr;
+  n->cur_bytes = nullptr;
+  n->turn_bytes.clear();  // the half of the inbound double buffer this turn decodes
+  n->turn_off.clear();
+  n->turn_bytes.swap(n->in_bytes);
+  n->turn_off.swap(n->in_off);
+  std::swap(n->turn_props, n->proposals);
+  t.ticks = n->pending_ticks;
+  n->pending_ticks = 0;
+  n->turn_hups.clear();
+  n->turn_hups.swap(n->pending_hups);
+  return RAFTQ_OK;
+}
+
+// -- rc.node.Tick() (raft.go:223-224) for every group: the engine advances the clocks and says
+// which groups' election timers fired (MsgHup -> through Step) and which leaders owe a heartbeat
+int tick(Turn& t) {
+  raftq_node_t* n = t.n;
+  std::vector<raftq_wire_msg_t>& local = n->local;
+  for (uint64_t gi : n->turn_hups)  // rc.node.Campaign: MsgHup through Step, ahead of what the timers raise
+    local.push_back(local_msg(n, gi, RAFTQ_MSG_HUP));
+  for (uint32_t k = 0; k < t.ticks; ++k) {
+    uint64_t n_beat = 0, map_words = 0;
+    const uint64_t* beat_map = nullptr;
+    {
+      Unlocked u(t.lk);
+      // the device compacts the two short lists (ascending group ids); no G-byte read-back and no loop over every
+      // group under the lock (O(G) host work per 100 ms tick at 1M groups)
+      // one call: the Tick and both of its lists (two launches, one wait).  A list that does not fit is fetched again alone.
+      // (raftq_tick_collect_lists: 4-byte ids read where the device left them, the MsgBeat groups as a bitmap -- with
+      // HeartbeatTick 1 the beat list is the set of groups this node leads, every tick)
+      uint64_t n_hup = 0, n_listed = 0;
+      int rc = raftq_tick_collect_lists(n->h, RAFTQ_TICK_BEAT_BITMAP, n->tick_list.size(), 0, &n_hup, &n_beat);
+      const uint32_t* hups = nullptr;
+      if (rc == RAFTQ_OK) rc = raftq_last_tick_lists(n->h, &hups, &n_listed, nullptr, nullptr, &beat_map, &map_words);
+      if (rc == RAFTQ_OK && n_hup > n_listed) {  // more timers fired than the list was sized for: fetch them again, alone
+        n->tick_list.resize(n_hup);
+        rc = raftq_collect_hups(n->h, n->tick_list.data(), n->tick_list.size(), &n_hup);
+        if (rc == RAFTQ_OK)
+          for (uint64_t i = 0; i < n_hup; ++i) local.push_back(local_msg(n, n->tick_list[i], RAFTQ_MSG_HUP));
+      } else if (rc == RAFTQ_OK) {
+        for (uint64_t i = 0; i < n_hup; ++i) local.push_back(local_msg(n, hups[i], RAFTQ_MSG_HUP));
+      }
+      if (rc != RAFTQ_OK) return fail(t, rc, "tick");
+    }
+    if (n_beat) {
+      for (uint64_t w = 0; w < map_words; ++w) {
+        for (uint64_t bits = beat_map[w]; bits; bits &= bits - 1) {
+          const uint64_t gi = w * 64 + (uint64_t)__builtin_ctzll(bits);
+          if (n->groups[gi].role == RAFTQ_ROLE_LEADER) bcast_heartbeat(n, gi, n->groups[gi]);  // stepLeader MsgBeat: host only
+        }
+      }
+    }
+  }
+  if (local.size() >= kLocal) return fail(t, RAFTQ_EINVAL, "more than 2^31 local messages in one turn");
+  return RAFTQ_OK;
+}
+
+// the device calls of the inbound half of a turn, with mu released: the frames decoded, and -- when nothing was raised locally
+// ahead of them -- stepped by the same submission.  *resp_frames: the frames raftq_step_frames_respond built.
+int decode_frames(Turn& t, uint64_t* resp_frames) {
+  raftq_node_t* n = t.n;
+  Unlocked u(t.lk);
+  t.ph.next(raftq_node::kPhDecode);
+  const PinBuf& in_bytes = n->turn_bytes;
+  PinU64& in_off = n->turn_off;
+  const uint64_t nf = t.nf;
+  if (nf >= kLocal) return fail(t, RAFTQ_EINVAL, "more than 2^31 frames in one turn");
+  uint64_t ents_cap = std::max<uint64_t>(nf + 1024, n->turn_ents.cap / sizeof(raftq_wire_ent_t));
+  if (!n->turn_msgs.reserve(nf * sizeof(raftq_wire_msg_t)) || !n->turn_ents.reserve(ents_cap * sizeof(raftq_wire_ent_t)))
+    return fail(t, RAFTQ_ENOMEM, "wire_decode (page-locked result buffers)");
+  raftq_wire_msg_t* out = n->turn_msgs.as<raftq_wire_msg_t>();
+  raftq_wire_ent_t* we = n->turn_ents.as<raftq_wire_ent_t>();
+  raftq_wire_counts_t cnt;
+  const bool fuse = n->fuse_inbound && n->local.empty();
+  int rc;
+  if (fuse && n->respond_device) {
+    // the responses and commit broadcasts on the device as well (raftq_step_frames_respond): room for the worst case
+    const uint64_t n_max = nf * (n->N - 1);
+    if (!n->resp_out.reserve(n_max * RAFTQ_RESPOND_FRAME_MAX) || !n->resp_off.resize(n_max + 1) || !n->resp_peer.resize(n->N + 1))
+      return fail(t, RAFTQ_ENOMEM, "step_frames_respond (page-locked response buffers)");
+    for (uint64_t gi = 0; n->respond_check && gi < n->G; ++gi) {  // a set bit must be true
+      if (((n->at_tail.data()[gi >> 6] >> (gi & 63)) & 1) && !group_at_tail(n, gi, n->groups[gi]))
+        return fail(t, RAFTQ_ESTATE, "respond check: group " + std::to_string(gi) + " is marked at the tail and is not");
+    }
+    raftq_wire_counts_t rcnt;
+    n->resp_pending = false;
+    rc = raftq_step_frames_respond(n->h, in_bytes.p, in_bytes.size, in_off.data(), nf, n->tail_appends ? 1 : 0, out, we, ents_cap,
+                                   n->at_tail.data(), n->resp_out.p, n_max * RAFTQ_RESPOND_FRAME_MAX, n->resp_off.data(),
+                                   n->resp_peer.data(), &cnt, &rcnt);
+    if (rc == RAFTQ_OK && rcnt.n_msgs) {
+      n->resp_pending = true;  // onto the queues where the turn's frames are published (flush_outbound)
+      *resp_frames = rcnt.n_msgs;
+    }
+  } else {
+    rc = fuse ? raftq_step_frames(n->h, in_bytes.p, in_bytes.size, in_off.data(), nf, n->tail_appends ? 1 : 0, out, we, ents_cap, &cnt)
+              : raftq_wire_decode(n->h, in_bytes.p, in_bytes.size, in_off.data(), nf, out, we, ents_cap, &cnt);
+  }
+  if ((rc == RAFTQ_OK || rc == RAFTQ_EINVAL) && cnt.n_ents > ents_cap) {
+    // more entries than messages + 1024: grow once, decode again (after raftq_step_frames only for the headers: the frames
+    // have been stepped, and what the plain decode writes over the records is what Step read minus the flags it was given)
+    ents_cap = cnt.n_ents;
+    if (!n->turn_ents.reserve(ents_cap * sizeof(raftq_wire_ent_t))) return fail(t, RAFTQ_ENOMEM, "wire_decode (entries)");
+    we = n->turn_ents.as<raftq_wire_ent_t>();
+    rc = raftq_wire_decode(n->h, in_bytes.p, in_bytes.size, in_off.data(), nf, out, we, ents_cap, &cnt);
+  }
+  if (rc != RAFTQ_OK) return fail(t, rc, fuse ? "step_frames" : "wire_decode");
+  if (fuse) {
+    uint64_t n_out = 0;
+    rc = raftq_step_results_s(n->h, &t.fused_outs, &n_out);
+    if (rc != RAFTQ_OK || n_out != nf || !t.fused_outs) return fail(t, rc != RAFTQ_OK ? rc : RAFTQ_ESTATE, "step_frames (results)");
+  }
+  t.wm = out;
+  n->cur_ents = we;
+  n->cur_bytes = in_bytes.p;
+  return RAFTQ_OK;
+}
+
+// -- rafthttp's messageDecoder + Message.Unmarshal for everything received since the last turn, on the GPU.  Frames that
+// do not parse, are not addressed to this node's slot, come from no peer of the cluster or are of a kind a peer never sends
+// are dropped and counted -- rafthttp would log and drop the stream; a raft node must survive any bytes a peer throws at it.
+// When nothing was raised locally ahead of them (no campaign, no timer: every turn of steady-state replication) the same
+// submission also makes those checks and steps every frame, in arrival order (raftq_step_frames: one wait for the inbound
+// half of the turn); otherwise the frames are decoded here (raftq_wire_decode) and stepped in the staged rounds, behind
+// the local messages.  Leaves n->work: what this turn works through, in order.
+int message_decoder(Turn& t) {
+  raftq_node_t* n = t.n;
+  t.nf = n->turn_off.size() > 1 ? n->turn_off.size() - 1 : 0;
+  uint64_t resp_frames = 0;
+  if (int rc = t.nf ? decode_frames(t, &resp_frames) : RAFTQ_OK) return rc;
+  n->stats.msgs_sent += resp_frames;
+  n->stats.msgs_built_on_device += resp_frames;
+  t.ph.next(raftq_node::kPhInbound);
+  // the locally raised messages, then the inbound ones as they arrived
+  const size_t nl = n->local.size();
+  n->work.resize(nl + (size_t)t.nf);
+  for (size_t i = 0; i < nl; ++i) n->work[i] = kLocal | (uint32_t)i;
+  for (uint64_t i = 0; i < t.nf; ++i) n->work[nl + i] = (uint32_t)i;
+  return RAFTQ_OK;
+}
+
+// One staged round, with mu released: what of n->work cannot go yet is deferred, the rest (n->batch) is written where the GPU reads
+// it (raftq_step_stage: device memory behind a large BAR; the decoder's 64-byte record IS Step's record) and stepped: *n_step results in *outs.
+int stage_round(Turn& t, uint32_t ep, bool first_round, const raftq_step_out_s_t** outs, size_t* n_step) {
+  raftq_node_t* n = t.n;
+  static_assert(sizeof(raftq_msg_t) == sizeof(raftq_wire_msg_t), "the decoder's record is Step's record");
+  Unlocked u(t.lk);
+  raftq_msg_t* staged = nullptr;
+  if (int rc = raftq_step_stage(n->h, n->work.size(), &staged)) return fail(t, rc, "step_stage");
+  const raftq_wire_msg_t *local = n->local.data(), *wm = t.wm;
+  size_t ns = 0;
+  for (const uint32_t ix : n->work) {
+    const raftq_wire_msg_t& m = msg_at(local, wm, ix);
+    if (first_round && !(ix & kLocal)) {
+      const bool kind_ok = m.type == RAFTQ_MSG_PROP || m.type == RAFTQ_MSG_APP || m.type == RAFTQ_MSG_APP_RESP ||
+                           m.type == RAFTQ_MSG_VOTE || m.type == RAFTQ_MSG_VOTE_RESP || m.type == RAFTQ_MSG_HEARTBEAT ||
+                           m.type == RAFTQ_MSG_HEARTBEAT_RESP;
+      if ((m.flags & RAFTQ_WIRE_F_MALFORMED) || !kind_ok || m.group >= n->G || m.from >= n->N || m.to != n->self) {
+        ++t.dropped;
+        continue;
+      }
+    }
+    uint32_t& mark = n->blocked_mark[m.group];
+    if (mark == ep) {
+      n->deferred.push_back(ix);
+      continue;
+    }
+    if (m.type == RAFTQ_MSG_PROP) {  // MsgProp never reaches Step; everything else does, in arrival order
+      mark = ep;
+    } else if (m.type == RAFTQ_MSG_APP) {
+      // a MsgApp says what it carries (RAFTQ_MSGF_ENTRIES): one that lands on the log's tail -- replication's common
+      // case -- is then appended and committed by Step itself, with no raftq_apply_log_deltas round trip behind it; one
+      // that Step has to leave to this log (a gap, a conflict) holds back what follows it for the group
+      // (RAFTQ_MSGF_BARRIER -> RAFTQ_OUT_DEFERRED): those come round again, after the log has changed
+      raftq_msg_t s;
+      std::memcpy(&s, &m, sizeof(s));
+      s._pad[0] = 0;
+      s._pad[1] = RAFTQ_MSGF_BARRIER | (n->tail_appends ? RAFTQ_MSGF_ENTRIES : 0);
+      s._resv = m.n_ents;
+      s.reject_hint = m.n_ents ? n->cur_ents[m.ent_first + m.n_ents - 1].term : 0;
+      std::memcpy(&staged[ns++], &s, sizeof(s));
+    } else {
+      std::memcpy(&staged[ns++], &m, sizeof(raftq_msg_t));
+    }
+    n->batch.push_back(ix);
+  }
+  *n_step = ns;
+  if (ns) {
+    t.ph.next(raftq_node::kPhStep);
+    int rc = raftq_step_batch(n->h, staged, ns, nullptr, nullptr);
+    uint64_t n_out = 0;
+    if (rc == RAFTQ_OK) rc = raftq_step_results_s(n->h, outs, &n_out);
+    if (rc != RAFTQ_OK) return fail(t, rc, "step_batch");
+  }
+  return RAFTQ_OK;
+}
+
+// The consequences of one round, in arrival order (stepped results and proposals interleaved as they came).  `fused`: stepped by the submission that
+// decoded it (raftq_step_frames), every frame of n->work: what is nobody's was skipped, a MsgProp held its group, a MsgApp was a barrier -- outs[i] answers frame i.
+void apply_round(Turn& t, uint32_t ep, bool fused, const raftq_step_out_s_t* outs) {
+  raftq_node_t* n = t.n;
+  const std::vector<uint32_t>& batch = n->batch;
+  std::vector<uint32_t>& deferred = n->deferred;
+  const size_t kept_back = deferred.size();  // (behind a MsgProp: decided while staging; what Step defers is added below)
+  // The groups of a batch are scattered over tens of MB of per-group state: the line of the group 16 messages ahead
+  // and, 8 ahead (its line has arrived by then), its Progress and the tail of its log are asked for now.
+  // (a skipped frame's group field may hold anything: in a fused round result `at` answers frame `at`)
+  const raftq_wire_msg_t *local = n->local.data(), *wm = t.wm;
+  const size_t nb = batch.size();
+  size_t k = 0;
+  for (size_t bi = 0; bi < nb; ++bi) {
+    if (bi + 16 < nb && (!fused || outs[bi + 16].type != RAFTQ_OUT_SKIPPED)) __builtin_prefetch(&n->groups[msg_at(local, wm, batch[bi + 16]).group]);
+    if (bi + 8 < nb && (!fused || outs[bi + 8].type != RAFTQ_OUT_SKIPPED)) {
+      const uint64_t g8 = msg_at(local, wm, batch[bi + 8]).group;
+      const Group& ahead = n->groups[g8];
+      if (ahead.leading) __builtin_prefetch(&n->prog[g8 * n->N * 2], 1);
+      if (!ahead.log.empty()) __builtin_prefetch(&ahead.log.back(), 1);  // term_at(prev), and where the next entry goes
+      ahead_of_publish(ahead);
+    }
+    const raftq_wire_msg_t& im = msg_at(local, wm, batch[bi]);
+    if (fused && outs[k].type == RAFTQ_OUT_SKIPPED) {  // not a message for this node (the checks are the decoder's there)
+      ++t.dropped;
+      n->stats.msgs_stepped--;
+      ++k;
+      continue;
+    }
+    if (im.type == RAFTQ_MSG_PROP) {
+      if (fused) {  // (answered RAFTQ_OUT_HELD: a result slot of its own)
+        n->stats.msgs_stepped--;
+        ++k;
+      }
+      if (n->defer_mark[im.group] == ep) {
+        // something of this group that arrived earlier waits for the next round (Step deferred it behind a hold or a
+        // barrier): the proposal waits behind it -- a group's messages are worked off in arrival order whichever way the
+        // round was stepped ([MsgProp, MsgAppResp, MsgProp] used to run the second proposal first)
+        deferred.push_back(batch[bi]);
+        continue;
+      }
+      if (handle_proposal(n, im.group, n->groups[im.group], prop_entries(n, im), im.n_ents)) mark_dirty(n, im.group, ep);
+    } else if (outs[k].type == RAFTQ_OUT_DEFERRED) {  // behind a MsgApp this log has to work out first: next round
+      deferred.push_back(batch[bi]);
+      n->defer_mark[im.group] = ep;
+      n->stats.msgs_stepped--;
+      ++k;
+    } else {
+      apply_result(n, widen(outs[k++], im), im);
+    }
+  }
+  if (deferred.size() != kept_back && kept_back != 0) std::sort(deferred.begin(), deferred.end());  // arrival order
+}
+
+// -- rc.Process -> Step, in rounds.  What follows a message that changes a group's log has to see the new log tail: a MsgProp
+// (which never reaches Step) keeps the rest of its group for the next round; a MsgApp only when Step could not finish it
+// itself (RAFTQ_MSGF_BARRIER).  In steady-state replication everything goes in the first round.
+int process(Turn& t) {
+  raftq_node_t* n = t.n;
+  bool first_round = true;
+  while (!n->work.empty()) {
+    t.ph.next(raftq_node::kPhStage);
+    n->batch.clear();
+    n->deferred.clear();
+    n->dirty_list.clear();
+    const uint32_t ep = next_epoch(n);
+    const raftq_step_out_s_t* outs = nullptr;
+    size_t n_step = 0;
+    const bool fused = first_round && t.fused_outs != nullptr;
+    if (fused) {
+      n->batch.assign(n->work.begin(), n->work.end());
+      outs = t.fused_outs;
+    } else if (int rc = stage_round(t, ep, first_round, &outs, &n_step)) {
+      return rc;
+    }
+    first_round = false;
+    t.ph.next(raftq_node::kPhApply);
+    n->stats.msgs_stepped += fused ? n->batch.size() : n_step;
+    apply_round(t, ep, fused, outs);
+    t.ph.next(raftq_node::kPhDeltas);
+    if (int rc = flush_dirty(n, t.lk)) return fail(t, rc, "apply_log_deltas");
+    n->work.swap(n->deferred);
+  }
+  n->stats.frames_dropped += t.dropped;
+  return RAFTQ_OK;
+}
+
+// appendEntry for one statement on the device path: the payload once into the log's arena and once into the turn's page-locked pool (where the encoder's
+// readers find it), the log's entry, 16 bytes (`pe`) that say where the payload is.  false: the arena is out of memory (n->oom), nothing was appended.
+RAFTQ_HOT bool append_for_device(raftq_node_t* n, Group& g, const char* src, uint32_t len, raftq_prop_ent_t& pe) {
+  const char* at = n->arena.put(src, len);
+  if (!at) {
+    n->oom = true;
+    return false;
+  }
+  g.log.push_back(n->pool, Entry{g.term, at, len});
+  pe.data_off = len ? n->out_pool.size : 0;
+  pe.data_len = len;
+  pe.type = 0;
+  if (!n->out_pool.append(src, len)) n->out_oom = true;
+  n->prop_cap += 48 + len;
+  return true;
+}
+
+// what bcastAppend leaves on the host for a group whose MsgApps the device builds: every Progress.Next past what is being sent
+// (the optimistic cursor) -- every follower at the tail the device's appendEntry leaves --, the WAL's dirty mark
+RAFTQ_HOT void sent_by_device(raftq_node_t* n, uint64_t gi, Group& g) {
+  const uint64_t next = g.log.size() + 1;
+  for (uint32_t p = 0; p < n->N; ++p)
+    if (p != n->self) n->next_of(gi, p) = next;
+  n->tail_set(gi);
+  wal_touch(n, gi, g);
+}
+
+struct PropCounts {  // what a shape of the queue wrote: device records (n->prop_recs) and their entries (n->prop_ents)
+  size_t n_fast, n_pents;
+};
+
+// Are every group's statements of this turn NEXT TO EACH OTHER in the queue (the common shapes: one statement per group, or
+// a client's run of statements for one group)?  One look at the queue's group ids -- no group state is touched -- says so.
+bool in_runs(raftq_node_t* n, const PropBuf& props) {
+  const uint32_t seen = next_epoch(n);
+  std::vector<uint32_t>& mk = n->prop_mark;
+  for (size_t i = 0; i < props.size(); ++i) {
+    const uint64_t gi = props.group[i];
+    if (i && gi == props.group[i - 1]) continue;
+    if (mk[gi] == seen) return false;
+    mk[gi] = seen;
+  }
+  return true;
+}
+
+// The queue in runs: a group is dealt with ONCE, while its lines are in cache: classified, its statements stored, its Progress moved.
+PropCounts propose_runs(raftq_node_t* n, const PropBuf& props, uint32_t ep, bool dev) {
+  const size_t np = props.size();
+  size_t n_fast = 0, n_pents = 0;
+  raftq_prop_t* recs = n->prop_recs.as<raftq_prop_t>();
+  raftq_prop_ent_t* pents = n->prop_ents.as<raftq_prop_ent_t>();
+  for (size_t i = 0; i < np && !n->oom;) {
+    // (the queue is in arrival order; a run's first statement is a good enough place to look ahead from)
+    if (i + 16 < np) __builtin_prefetch(&n->groups[props.group[i + 16]]);
+    if (i + 8 < np) {
+      const uint64_t g8 = props.group[i + 8];
+      const Group& ahead = n->groups[g8];
+      __builtin_prefetch(&n->prog[g8 * n->N * 2], 1);
+      if (ahead.log.p) __builtin_prefetch(ahead.log.p + ahead.log.n, 1);  // appendEntry writes behind the log's last entry
+    }
+    const uint64_t gi = props.group[i];
+    size_t j = i + 1;
+    while (j < np && props.group[j] == gi) ++j;
+    const uint64_t bytes = props.off[j] - props.off[i];
+    Group& g = n->groups[gi];
+    // through the device: a group at the tail, one message's worth of statements (raft.Config.MaxSizePerMsg, raft.go:157)
+    if (dev && j - i <= kMaxEntriesPerMsg && bytes < kMaxBytesPerMsg && group_at_tail(n, gi, g)) {
+      recs[n_fast++] = raftq_prop_t{gi, (uint32_t)n_pents, (uint32_t)(j - i)};
+      for (size_t k = i; k < j; ++k) {
+        if (!append_for_device(n, g, props.blob.data() + props.off[k], (uint32_t)(props.off[k + 1] - props.off[k]), pents[n_pents])) break;
+        ++n_pents;
+      }
+      sent_by_device(n, gi, g);
+    } else {
+      for (size_t k = i; k < j; ++k) {
+        const Entry one{0, props.blob.data() + props.off[k], (uint32_t)(props.off[k + 1] - props.off[k])};
+        if (handle_proposal(n, gi, g, &one, 1)) mark_dirty(n, gi, ep);
+      }
+    }
+    i = j;
+  }
+  return PropCounts{n_fast, n_pents};
+}
+
+// Pass 1 of the general shape: which groups go through the device.  A group at the tail gets ONE raftq_prop_t for the turn, in
+// the order of its first proposal -- the order its MsgApps take in every peer's stream -- and a count; everybody else takes
+// handle_proposal's way (a follower forwards, a leader with a lagging follower sends from its own log).
+// prop_mark[g] == ep: through the device, prop_slot[g] = its record; == ep | kSlowBit: decided, host.  Returns the records written.
+size_t pick_device_groups(raftq_node_t* n, const PropBuf& props, uint32_t ep) {
+  const size_t np = props.size();
+  std::vector<uint32_t>& pmark = n->prop_mark;
+  const uint32_t ep_fast = ep, ep_slow = ep | kSlowBit;  // (epochs stay below 2^31: next_epoch)
+  raftq_prop_t* recs = n->prop_recs.as<raftq_prop_t>();
+  size_t n_fast = 0;
+  for (size_t i = 0; i < np; ++i) {
+    if (i + 16 < np) __builtin_prefetch(&n->groups[props.group[i + 16]]);
+    if (i + 8 < np) __builtin_prefetch(&n->prog[props.group[i + 8] * n->N * 2]);
+    const uint64_t gi = props.group[i];
+    uint32_t& mk = pmark[gi];
+    if (mk == ep_slow) continue;
+    const uint64_t len = props.off[i + 1] - props.off[i];
+    if (mk == ep_fast) {  // another statement for a group already on its way: one MsgApp carries them all, within raft.Config.MaxSizePerMsg
+      raftq_prop_t& r = recs[n->prop_slot[gi]];
+      r.n_ents++;
+      r.ent_first = (uint32_t)std::min<uint64_t>((uint64_t)r.ent_first + len, 0xffffffffull);  // (the payload bytes so far; the entries' place comes below)
+      continue;
+    }
+    if (!group_at_tail(n, gi, n->groups[gi])) {
+      mk = ep_slow;
+      continue;
+    }
+    mk = ep_fast;
+    n->prop_slot[gi] = (uint32_t)n_fast;
+    recs[n_fast++] = raftq_prop_t{gi, (uint32_t)std::min<uint64_t>(len, 0xffffffffull), 1};
+  }
+  // a group whose statements outgrow one message (raft.Config.MaxSizePerMsg, raft.go:157: sendAppend would cut it) is the host's
+  uint32_t ent_at = 0;
+  size_t kept = 0;
+  for (size_t k = 0; k < n_fast; ++k) {
+    raftq_prop_t r = recs[k];
+    if (r.n_ents > kMaxEntriesPerMsg || r.ent_first >= kMaxBytesPerMsg) {
+      pmark[r.group] = ep_slow;
+      continue;
+    }
+    r.ent_first = ent_at;
+    ent_at += r.n_ents;
+    r.n_ents = 0;  // (filled again, entry by entry, by the second pass)
+    n->prop_slot[r.group] = (uint32_t)kept;
+    recs[kept++] = r;
+  }
+  return kept;
+}
+
+// The general shape (a group's statements interleaved with other groups'), two passes: pick_device_groups, then every statement
+// in arrival order.
+PropCounts propose_interleaved(raftq_node_t* n, const PropBuf& props, uint32_t ep, bool dev) {
+  const size_t np = props.size(), n_fast = dev ? pick_device_groups(n, props, ep) : 0;
+  size_t n_pents = 0;
+  raftq_prop_t* recs = n->prop_recs.as<raftq_prop_t>();
+  raftq_prop_ent_t* pents = n->prop_ents.as<raftq_prop_ent_t>();
+  for (size_t i = 0; i < np; ++i) {
+    if (i + 16 < np) __builtin_prefetch(&n->groups[props.group[i + 16]]);
+    if (i + 8 < np) {  // appendEntry writes behind the log's last entry
+      const Group& ahead = n->groups[props.group[i + 8]];
+      if (ahead.log.p) __builtin_prefetch(ahead.log.p + ahead.log.n, 1);
+    }
+    const uint64_t gi = props.group[i];
+    const Entry one{0, props.blob.data() + props.off[i], (uint32_t)(props.off[i + 1] - props.off[i])};
+    if (n_fast != 0 && n->prop_mark[gi] == ep) {
+      raftq_prop_t& r = recs[n->prop_slot[gi]];
+      if (!append_for_device(n, n->groups[gi], one.data, one.len, pents[r.ent_first + r.n_ents])) break;
+      ++r.n_ents;
+      ++n_pents;
+      continue;
+    }
+    if (handle_proposal(n, gi, n->groups[gi], &one, 1)) mark_dirty(n, gi, ep);
+  }
+  for (size_t k = 0; k < n_fast; ++k) {
+    if (k + 8 < n_fast) __builtin_prefetch(&n->prog[recs[k + 8].group * n->N * 2], 1);
+    sent_by_device(n, recs[k].group, n->groups[recs[k].group]);
+  }
+  return PropCounts{n_fast, n_pents};
+}
+
+// -- proposeC (raft.go:211-215): through the device (records for flush_outbound's raftq_propose_frames) or handle_proposal + bcastAppend
+int propose(Turn& t) {
+  raftq_node_t* n = t.n;
+  const PropBuf& props = n->turn_props;
+  t.ph.next(raftq_node::kPhProps);
+  n->prop_recs.clear();
+  n->prop_ents.clear();
+  n->prop_cap = 0;
+  if (props.size() == 0) return RAFTQ_OK;
+  n->dirty_list.clear();
+  // RAFTQ_NODE_PROPOSE_DEVICE=0, or no page-locked memory for the records (the turn then ends in ENOMEM where it marshals): the host's way
+  const bool dev = n->propose_device && n->prop_recs.reserve(props.size() * sizeof(raftq_prop_t)) && n->prop_ents.reserve(props.size() * sizeof(raftq_prop_ent_t));
+  if (n->propose_device && !dev) n->out_oom = true;
+  const bool runs = in_runs(n, props);
+  const uint32_t ep = next_epoch(n);
+  const PropCounts c = runs ? propose_runs(n, props, ep, dev) : propose_interleaved(n, props, ep, dev);
+  n->stats.msgs_sent += c.n_fast * (n->N - 1);
+  n->stats.msgs_built_on_device += c.n_fast * (n->N - 1);
+  n->prop_cap += c.n_fast * 160;  // (per addressee: flush_outbound multiplies)
+  n->prop_recs.size = c.n_fast * sizeof(raftq_prop_t);
+  n->prop_ents.size = c.n_pents * sizeof(raftq_prop_ent_t);
+  if (n->oom) {  // (a device record without its log entry must not go out)
+    n->prop_recs.clear();
+    n->prop_ents.clear();
+  }
+  if (int rc = flush_dirty(n, t.lk)) return fail(t, rc, "apply_log_deltas");
+  return RAFTQ_OK;
+}
+
+// -- wal.Save before transport.Send (raft.go:228-230): the caller persists what raftq_node_wal_poll
+// hands out before it transmits what raftq_node_poll hands out
+int save_and_send(Turn& t) {
+  raftq_node_t* n = t.n;
+  t.ph.next(raftq_node::kPhWal);
+  if (int rc = flush_wal_begin(n, t.lk)) return fail(t, rc, "wal_encode");
+  t.ph.next(raftq_node::kPhEncode);
+  if (int rc = flush_outbound(n, t.lk)) return fail(t, rc, "wire_encode");
+  t.ph.next(raftq_node::kPhWal);
+  if (int rc = wal_end(n, t.lk, raftq_node::kPhWal)) return fail(t, rc, "wal_encode");  // a turn with nothing to send: the wait is its own
+  return RAFTQ_OK;
 }
 
 }  // namespace
@@ -1513,571 +2055,29 @@ void dump_profile(raftq_node_t* n) {
 }
 }  // namespace
 
+// One turn, in the order of the reference's Ready loop.  The commit channels, the status mirror and the outbound queues are only written under mu.
 static int node_advance_impl(raftq_node_t* n, uint64_t* n_published) {
   if (!n) return RAFTQ_EINVAL;
   std::lock_guard<std::mutex> turn(n->turn_mu);
   PhaseClock ph(n, raftq_node::kPhDecode);
   if (n->profiling) n->prof_turns++;
-  std::vector<uint32_t>& work = n->work;
-  work.clear();
-  n->local.clear();
-  PropBuf& props = n->turn_props;
-  props.clear();
-  n->cur_ents = nullptr;
-  n->cur_bytes = nullptr;
-  PinBuf& in_bytes = n->turn_bytes;  // the half of the inbound double buffer this turn decodes
-  PinU64& in_off = n->turn_off;
-  in_bytes.clear();
-  in_off.clear();
-  uint32_t ticks = 0;
-  {
-    std::lock_guard<std::mutex> lk(n->mu);
-    if (!n->started) return RAFTQ_ESTATE;
-    if (n->error) return n->error;
-    in_bytes.swap(n->in_bytes);
-    in_off.swap(n->in_off);
-    std::swap(props, n->proposals);
-    ticks = n->pending_ticks;
-    n->pending_ticks = 0;
-    n->turn_hups.clear();
-    n->turn_hups.swap(n->pending_hups);
-  }
-  ph.next(raftq_node::kPhTick);
-  // The commit channels, the status mirror and the outbound queues are only written below, under
-  // mu, one short critical section per phase.
   std::unique_lock<std::mutex> lk(n->mu);
+  Turn t(n, lk, ph);
+  if (int rc = take_inputs(t)) return rc;
+  ph.next(raftq_node::kPhTick);
   const uint64_t published0 = n->stats.entries_published;
-  bool did = in_off.size() > 1 || props.size() != 0 || ticks != 0 || !n->turn_hups.empty();
-
-  // -- rc.node.Tick() (raft.go:223-224) for every group: the engine advances the clocks and says
-  // which groups' election timers fired (MsgHup -> through Step) and which leaders owe a heartbeat
-  std::vector<raftq_wire_msg_t>& local = n->local;
-  for (uint64_t gi : n->turn_hups)  // rc.node.Campaign: MsgHup through Step, ahead of what the timers raise
-    local.push_back(local_msg(n, gi, RAFTQ_MSG_HUP));
-  for (uint32_t t = 0; t < ticks; ++t) {
+  const bool did = n->turn_off.size() > 1 || n->turn_props.size() != 0 || t.ticks != 0 || !n->turn_hups.empty();
+  int rc = tick(t);
+  if (!rc) rc = message_decoder(t);
+  if (!rc) rc = process(t);
+  if (!rc) rc = propose(t);
+  if (!rc && n->oom) rc = fail(t, RAFTQ_ENOMEM, "entry storage");
+  if (!rc && n->broken) rc = fail(t, RAFTQ_ESTATE, "the engine's log tail and the node's log disagree");
+  if (!rc) rc = save_and_send(t);
+  if (rc) {  // the one place a turn poisons the node: poison() takes mu
     lk.unlock();
-    // the device compacts the two short lists (ascending group ids); no G-byte read-back and no loop over every
-    // group under the lock (O(G) host work per 100 ms tick at 1M groups)
-    // one call: the Tick and both of its lists (two launches, one wait).  A list that does not fit is fetched again alone.
-    // (raftq_tick_collect_lists: 4-byte ids read where the device left them, the MsgBeat groups as a bitmap -- with
-    // HeartbeatTick 1 the beat list is the set of groups this node leads, every tick)
-    uint64_t n_hup = 0, n_beat = 0;
-    int rc = raftq_tick_collect_lists(n->h, RAFTQ_TICK_BEAT_BITMAP, n->tick_list.size(), 0, &n_hup, &n_beat);
-    const uint32_t* hups = nullptr;
-    const uint64_t* beat_map = nullptr;
-    uint64_t n_listed = 0, map_words = 0;
-    if (rc == RAFTQ_OK) rc = raftq_last_tick_lists(n->h, &hups, &n_listed, nullptr, nullptr, &beat_map, &map_words);
-    if (rc == RAFTQ_OK && n_hup > n_listed) {  // more timers fired than the list was sized for: fetch them again, alone
-      n->tick_list.resize(n_hup);
-      rc = raftq_collect_hups(n->h, n->tick_list.data(), n->tick_list.size(), &n_hup);
-      if (rc == RAFTQ_OK)
-        for (uint64_t i = 0; i < n_hup; ++i) local.push_back(local_msg(n, n->tick_list[i], RAFTQ_MSG_HUP));
-    } else if (rc == RAFTQ_OK) {
-      for (uint64_t i = 0; i < n_hup; ++i) local.push_back(local_msg(n, hups[i], RAFTQ_MSG_HUP));
-    }
-    if (rc != RAFTQ_OK) return poison(n, rc, "tick");
-    lk.lock();
-    if (n_beat) {
-      for (uint64_t w = 0; w < map_words; ++w) {
-        for (uint64_t bits = beat_map[w]; bits; bits &= bits - 1) {
-          const uint64_t gi = w * 64 + (uint64_t)__builtin_ctzll(bits);
-          if (n->groups[gi].role == RAFTQ_ROLE_LEADER) bcast_heartbeat(n, gi, n->groups[gi]);  // stepLeader MsgBeat: host only
-        }
-      }
-    }
+    return poison(n, rc, t.what);
   }
-  if (local.size() >= kLocal) {
-    lk.unlock();
-    return poison(n, RAFTQ_EINVAL, "more than 2^31 local messages in one turn");
-  }
-  // -- rafthttp's messageDecoder + Message.Unmarshal for everything received since the last turn, on the GPU.  Frames that
-  // do not parse, are not addressed to this node's slot, come from no peer of the cluster or are of a kind a peer never sends
-  // are dropped and counted -- rafthttp would log and drop the stream; a raft node must survive any bytes a peer throws at it.
-  // When nothing was raised locally ahead of them (no campaign, no timer: every turn of steady-state replication) the same
-  // submission also makes those checks and steps every frame, in arrival order (raftq_step_frames: one wait for the inbound
-  // half of the turn); otherwise the frames are decoded here (raftq_wire_decode) and stepped in the staged rounds below, behind
-  // the local messages.
-  uint64_t nf = in_off.size() > 1 ? in_off.size() - 1 : 0;
-  const raftq_wire_msg_t* wm = nullptr;
-  const raftq_step_out_s_t* fused_outs = nullptr;  // != nullptr: round 1 has been stepped, out[i] answers frame i
-  uint64_t resp_frames = 0;                         // frames raftq_step_frames_respond built for this turn
-  if (nf) {
-    lk.unlock();
-    ph.next(raftq_node::kPhDecode);
-    if (nf >= kLocal) return poison(n, RAFTQ_EINVAL, "more than 2^31 frames in one turn");
-    uint64_t ents_cap = std::max<uint64_t>(nf + 1024, n->turn_ents.cap / sizeof(raftq_wire_ent_t));
-    if (!n->turn_msgs.reserve(nf * sizeof(raftq_wire_msg_t)) || !n->turn_ents.reserve(ents_cap * sizeof(raftq_wire_ent_t)))
-      return poison(n, RAFTQ_ENOMEM, "wire_decode (page-locked result buffers)");
-    raftq_wire_msg_t* out = n->turn_msgs.as<raftq_wire_msg_t>();
-    raftq_wire_ent_t* we = n->turn_ents.as<raftq_wire_ent_t>();
-    raftq_wire_counts_t cnt;
-    const bool fuse = n->fuse_inbound && local.empty();
-    int rc;
-    if (fuse && n->respond_device) {
-      // the responses and commit broadcasts on the device as well (raftq_step_frames_respond): room for the worst case
-      const uint64_t n_max = nf * (n->N - 1);
-      if (!n->resp_out.reserve(n_max * RAFTQ_RESPOND_FRAME_MAX) || !n->resp_off.resize(n_max + 1) || !n->resp_peer.resize(n->N + 1))
-        return poison(n, RAFTQ_ENOMEM, "step_frames_respond (page-locked response buffers)");
-      if (n->respond_check) {  // a set bit must be true: this node leads the group and every follower's Next is lastIndex + 1
-        for (uint64_t gi = 0; gi < n->G; ++gi) {
-          if (!((n->at_tail.data()[gi >> 6] >> (gi & 63)) & 1)) continue;
-          const Group& g = n->groups[gi];
-          bool ok = g.leading && g.role == RAFTQ_ROLE_LEADER;
-          for (uint32_t p = 0; ok && p < n->N; ++p)
-            if (p != n->self) ok = n->next_of(gi, p) == g.log.size() + 1;
-          if (!ok) return poison(n, RAFTQ_ESTATE, "respond check: group " + std::to_string(gi) + " is marked at the tail and is not");
-        }
-      }
-      raftq_wire_counts_t rcnt;
-      n->resp_pending = false;
-      rc = raftq_step_frames_respond(n->h, in_bytes.p, in_bytes.size, in_off.data(), nf, n->tail_appends ? 1 : 0, out, we, ents_cap,
-                                     n->at_tail.data(), n->resp_out.p, n_max * RAFTQ_RESPOND_FRAME_MAX, n->resp_off.data(),
-                                     n->resp_peer.data(), &cnt, &rcnt);
-      if (rc == RAFTQ_OK && rcnt.n_msgs) {
-        n->resp_pending = true;  // onto the queues where the turn's frames are published (flush_outbound)
-        resp_frames = rcnt.n_msgs;
-      }
-    } else {
-      rc = fuse ? raftq_step_frames(n->h, in_bytes.p, in_bytes.size, in_off.data(), nf, n->tail_appends ? 1 : 0, out, we, ents_cap, &cnt)
-                : raftq_wire_decode(n->h, in_bytes.p, in_bytes.size, in_off.data(), nf, out, we, ents_cap, &cnt);
-    }
-    if ((rc == RAFTQ_OK || rc == RAFTQ_EINVAL) && cnt.n_ents > ents_cap) {
-      // more entries than messages + 1024: grow once, decode again (after raftq_step_frames only for the headers: the frames
-      // have been stepped, and what the plain decode writes over the records is what Step read minus the flags it was given)
-      ents_cap = cnt.n_ents;
-      if (!n->turn_ents.reserve(ents_cap * sizeof(raftq_wire_ent_t))) return poison(n, RAFTQ_ENOMEM, "wire_decode (entries)");
-      we = n->turn_ents.as<raftq_wire_ent_t>();
-      rc = raftq_wire_decode(n->h, in_bytes.p, in_bytes.size, in_off.data(), nf, out, we, ents_cap, &cnt);
-    }
-    if (rc != RAFTQ_OK) return poison(n, rc, fuse ? "step_frames" : "wire_decode");
-    if (fuse) {
-      uint64_t n_out = 0;
-      rc = raftq_step_results_s(n->h, &fused_outs, &n_out);
-      if (rc != RAFTQ_OK || n_out != nf || !fused_outs) return poison(n, rc != RAFTQ_OK ? rc : RAFTQ_ESTATE, "step_frames (results)");
-    }
-    wm = out;
-    n->cur_ents = we;
-    n->cur_bytes = in_bytes.p;
-    lk.lock();
-    n->stats.msgs_sent += resp_frames;
-    n->stats.msgs_built_on_device += resp_frames;
-  }
-  ph.next(raftq_node::kPhInbound);
-  // what this turn works through, in order: the locally raised messages, then the inbound ones as they arrived
-  work.resize(local.size() + (size_t)nf);
-  for (size_t i = 0; i < local.size(); ++i) work[i] = kLocal | (uint32_t)i;
-  for (uint64_t i = 0; i < nf; ++i) work[local.size() + i] = (uint32_t)i;
-  auto msg_at = [&](uint32_t ix) -> const raftq_wire_msg_t& { return (ix & kLocal) ? local[ix & ~kLocal] : wm[ix]; };
-
-  // -- rc.Process -> Step, in rounds.  What follows a message that changes a group's log has to see the new log tail: a MsgProp
-  // (which never reaches Step) keeps the rest of its group for the next round; a MsgApp only when Step could not finish it
-  // itself (RAFTQ_MSGF_BARRIER).  In steady-state replication everything goes in the first round.
-  std::vector<uint32_t>& batch = n->batch;
-  std::vector<uint32_t>& deferred = n->deferred;
-  std::vector<uint64_t>& dirty = n->dirty_list;
-  auto next_epoch = [&] {  // a fresh value no mark holds
-    if (++n->epoch >= 0x80000000u) {  // (below 2^31: the proposals' marks use the top bit)
-      std::fill(n->blocked_mark.begin(), n->blocked_mark.end(), 0u);
-      std::fill(n->dirty_mark.begin(), n->dirty_mark.end(), 0u);
-      std::fill(n->defer_mark.begin(), n->defer_mark.end(), 0u);
-      std::fill(n->prop_mark.begin(), n->prop_mark.end(), 0u);
-      n->epoch = 1;
-    }
-    return n->epoch;
-  };
-  // the views of one inbound MsgProp's entries (payloads stay in the receive buffer)
-  auto prop_entries = [&](const raftq_wire_msg_t& im) -> const Entry* {
-    n->ent_tmp.clear();
-    for (uint32_t k = 0; k < im.n_ents; ++k) {
-      const raftq_wire_ent_t& e = n->cur_ents[im.ent_first + k];
-      n->ent_tmp.push_back(Entry{e.term, (const char*)n->cur_bytes + e.data_off, e.data_len});
-    }
-    return n->ent_tmp.data();
-  };
-  // report the grown logs' tails, publish what that committed, then bcastAppend
-  auto flush_dirty = [&]() -> int {
-    const size_t nd = dirty.size();
-    for (size_t i = 0; i < nd; ++i) {
-      if (i + 16 < nd) __builtin_prefetch(&n->groups[dirty[i + 16]]);
-      const uint64_t gi = dirty[i];
-      Group& g = n->groups[gi];
-      raftq_log_delta_t d{gi, g.log.size(), g.term, 0};
-      n->deltas.push_back(d);
-    }
-    if (int rc = flush_deltas(n, lk)) return rc;
-    for (size_t i = 0; i < nd; ++i) {  // bcastAppend: the group's line, its Progress and the entry before Next
-      if (i + 16 < nd) __builtin_prefetch(&n->groups[dirty[i + 16]]);
-      if (i + 8 < nd) {
-        const Group& ahead = n->groups[dirty[i + 8]];
-        __builtin_prefetch(&n->prog[dirty[i + 8] * n->N * 2], 1);
-        if (!ahead.log.empty()) __builtin_prefetch(&ahead.log.back());
-      }
-      bcast_append(n, dirty[i], n->groups[dirty[i]]);
-    }
-    return RAFTQ_OK;
-  };
-  bool first_round = true;
-  uint64_t dropped = 0;
-  while (!work.empty()) {
-    ph.next(raftq_node::kPhStage);
-    batch.clear();
-    deferred.clear();
-    dirty.clear();
-    const uint32_t ep = next_epoch();
-    // one pass: what cannot go yet is deferred, the rest is written where the GPU reads it (raftq_step_stage: device
-    // memory behind a large BAR) -- the decoder's 64-byte record IS Step's record
-    raftq_msg_t* staged = nullptr;
-    static_assert(sizeof(raftq_msg_t) == sizeof(raftq_wire_msg_t), "the decoder's record is Step's record");
-    size_t n_step = 0;
-    const raftq_step_out_s_t* outs = nullptr;
-    const bool fused = first_round && fused_outs != nullptr;
-    if (fused) {
-      // round 1 has been stepped already, every frame of it, by the submission that decoded them (raftq_step_frames): what is
-      // nobody's was skipped, a MsgProp held its group, a MsgApp was a barrier -- out[i] answers frame i
-      batch.assign(work.begin(), work.end());
-      outs = fused_outs;
-      first_round = false;
-    } else {
-    lk.unlock();
-    if (int rc = raftq_step_stage(n->h, work.size(), &staged)) return poison(n, rc, "step_stage");
-    for (const uint32_t ix : work) {
-      const raftq_wire_msg_t& m = msg_at(ix);
-      if (first_round && !(ix & kLocal)) {
-        const bool kind_ok = m.type == RAFTQ_MSG_PROP || m.type == RAFTQ_MSG_APP || m.type == RAFTQ_MSG_APP_RESP ||
-                             m.type == RAFTQ_MSG_VOTE || m.type == RAFTQ_MSG_VOTE_RESP || m.type == RAFTQ_MSG_HEARTBEAT ||
-                             m.type == RAFTQ_MSG_HEARTBEAT_RESP;
-        if ((m.flags & RAFTQ_WIRE_F_MALFORMED) || !kind_ok || m.group >= n->G || m.from >= n->N || m.to != n->self) {
-          ++dropped;
-          continue;
-        }
-      }
-      uint32_t& mark = n->blocked_mark[m.group];
-      if (mark == ep) {
-        deferred.push_back(ix);
-        continue;
-      }
-      if (m.type == RAFTQ_MSG_PROP) {  // MsgProp never reaches Step; everything else does, in arrival order
-        mark = ep;
-      } else if (m.type == RAFTQ_MSG_APP) {
-        // a MsgApp says what it carries (RAFTQ_MSGF_ENTRIES): one that lands on the log's tail -- replication's common
-        // case -- is then appended and committed by Step itself, with no raftq_apply_log_deltas round trip behind it; one
-        // that Step has to leave to this log (a gap, a conflict) holds back what follows it for the group
-        // (RAFTQ_MSGF_BARRIER -> RAFTQ_OUT_DEFERRED): those come round again below, after the log has changed
-        raftq_msg_t t;
-        std::memcpy(&t, &m, sizeof(t));
-        t._pad[0] = 0;
-        t._pad[1] = RAFTQ_MSGF_BARRIER | (n->tail_appends ? RAFTQ_MSGF_ENTRIES : 0);
-        t._resv = m.n_ents;
-        t.reject_hint = m.n_ents ? n->cur_ents[m.ent_first + m.n_ents - 1].term : 0;
-        std::memcpy(&staged[n_step++], &t, sizeof(t));
-      } else {
-        std::memcpy(&staged[n_step++], &m, sizeof(raftq_msg_t));
-      }
-      batch.push_back(ix);
-    }
-    first_round = false;
-    if (n_step) {
-      ph.next(raftq_node::kPhStep);
-      int rc = raftq_step_batch(n->h, staged, n_step, nullptr, nullptr);
-      uint64_t n_out = 0;
-      if (rc == RAFTQ_OK) rc = raftq_step_results_s(n->h, &outs, &n_out);
-      if (rc != RAFTQ_OK) return poison(n, rc, "step_batch");
-    }
-    lk.lock();
-    }
-    ph.next(raftq_node::kPhApply);
-    n->stats.msgs_stepped += fused ? batch.size() : n_step;
-    const size_t kept_back = deferred.size();  // (behind a MsgProp: decided while staging; what Step defers is added below)
-    // consequences, in arrival order (stepped results and proposals interleaved as they came)
-    // The groups of a batch are scattered over tens of MB of per-group state: the line of the group 16 messages ahead
-    // and, 8 ahead (its line has arrived by then), its Progress and the tail of its log are asked for now.
-    const size_t nb = batch.size();
-    auto group_of = [&](size_t at) { return msg_at(batch[at]).group; };
-    // (a skipped frame's group field may hold anything: in a fused round result `at` answers frame `at`)
-    auto live_at = [&](size_t at) { return !fused || outs[at].type != RAFTQ_OUT_SKIPPED; };
-    size_t k = 0;
-    for (size_t bi = 0; bi < nb; ++bi) {
-      if (bi + 16 < nb && live_at(bi + 16)) __builtin_prefetch(&n->groups[group_of(bi + 16)]);
-      if (bi + 8 < nb && live_at(bi + 8)) {
-        const uint64_t g8 = group_of(bi + 8);
-        const Group& ahead = n->groups[g8];
-        if (ahead.leading) __builtin_prefetch(&n->prog[g8 * n->N * 2], 1);
-        if (!ahead.log.empty()) __builtin_prefetch(&ahead.log.back(), 1);  // term_at(prev), and where the next entry goes
-        ahead_of_publish(ahead);
-      }
-      const raftq_wire_msg_t& im = msg_at(batch[bi]);
-      if (fused && outs[k].type == RAFTQ_OUT_SKIPPED) {  // not a message for this node (the checks are the decoder's there)
-        ++dropped;
-        n->stats.msgs_stepped--;
-        ++k;
-        continue;
-      }
-      if (im.type == RAFTQ_MSG_PROP) {
-        if (fused) {  // (answered RAFTQ_OUT_HELD: a result slot of its own)
-          n->stats.msgs_stepped--;
-          ++k;
-        }
-        if (n->defer_mark[im.group] == ep) {
-          // something of this group that arrived earlier waits for the next round (Step deferred it behind a hold or a
-          // barrier): the proposal waits behind it -- a group's messages are worked off in arrival order whichever way the
-          // round was stepped ([MsgProp, MsgAppResp, MsgProp] used to run the second proposal first)
-          deferred.push_back(batch[bi]);
-          continue;
-        }
-        Group& g = n->groups[im.group];
-        if (handle_proposal(n, im.group, g, prop_entries(im), im.n_ents) && n->dirty_mark[im.group] != ep) {
-          n->dirty_mark[im.group] = ep;
-          dirty.push_back(im.group);
-        }
-      } else if (outs[k].type == RAFTQ_OUT_DEFERRED) {  // behind a MsgApp this log has to work out first: next round
-        deferred.push_back(batch[bi]);
-        n->defer_mark[im.group] = ep;
-        n->stats.msgs_stepped--;
-        ++k;
-      } else {
-        apply_result(n, widen(outs[k++], im), im);
-      }
-    }
-    if (deferred.size() != kept_back && kept_back != 0) std::sort(deferred.begin(), deferred.end());  // arrival order
-    ph.next(raftq_node::kPhDeltas);
-    if (int rc = flush_dirty()) return poison(n, rc, "apply_log_deltas");
-    work.swap(deferred);
-  }
-  n->stats.frames_dropped += dropped;
-  ph.next(raftq_node::kPhProps);
-
-  // -- proposeC (raft.go:211-215)
-  n->prop_recs.clear();
-  n->prop_ents.clear();
-  n->prop_cap = 0;
-  if (props.size()) {
-    dirty.clear();
-    const size_t np_ = props.size();
-    // Are every group's statements of this turn NEXT TO EACH OTHER in the queue (the common shapes: one statement per group, or
-    // a client's run of statements for one group)?  One look at the queue's group ids -- no group state is touched -- says so; then
-    // a group is dealt with ONCE, while its lines are in cache: classified, its statements stored, its Progress moved.
-    bool runs = true;
-    {
-      const uint32_t seen = next_epoch();
-      std::vector<uint32_t>& mk = n->prop_mark;
-      for (size_t i = 0; i < np_; ++i) {
-        const uint64_t gi = props.group[i];
-        if (i && gi == props.group[i - 1]) continue;
-        if (mk[gi] == seen) {
-          runs = false;
-          break;
-        }
-        mk[gi] = seen;
-      }
-    }
-    const uint32_t ep = next_epoch();
-    if (runs) {
-      const bool dev = n->propose_device;
-      bool pin_oom = dev && (!n->prop_recs.reserve(np_ * sizeof(raftq_prop_t)) || !n->prop_ents.reserve(np_ * sizeof(raftq_prop_ent_t)));
-      raftq_prop_t* recs = n->prop_recs.as<raftq_prop_t>();
-      raftq_prop_ent_t* pents = n->prop_ents.as<raftq_prop_ent_t>();
-      size_t n_fast = 0, n_pents = 0;
-      for (size_t i = 0; i < np_ && !n->oom;) {
-        // (the queue is in arrival order; a run's first statement is a good enough place to look ahead from)
-        if (i + 16 < np_) __builtin_prefetch(&n->groups[props.group[i + 16]]);
-        if (i + 8 < np_) {
-          const uint64_t g8 = props.group[i + 8];
-          const Group& ahead = n->groups[g8];
-          __builtin_prefetch(&n->prog[g8 * n->N * 2], 1);
-          if (ahead.log.p) __builtin_prefetch(ahead.log.p + ahead.log.n, 1);  // appendEntry writes behind the log's last entry
-        }
-        const uint64_t gi = props.group[i];
-        size_t j = i + 1;
-        while (j < np_ && props.group[j] == gi) ++j;
-        const uint64_t bytes = props.off[j] - props.off[i];
-        Group& g = n->groups[gi];
-        // through the device: a group this node leads, every follower's Progress.Next at the log's tail (what bcastAppend leaves
-        // behind: every group outside a catch-up), one message's worth of statements (raft.Config.MaxSizePerMsg, raft.go:157)
-        bool fast = dev && !pin_oom && g.role == RAFTQ_ROLE_LEADER && g.leading && j - i <= kMaxEntriesPerMsg && bytes < kMaxBytesPerMsg;
-        const uint64_t tail = g.log.size() + 1;
-        for (uint32_t p = 0; fast && p < n->N; ++p)
-          if (p != n->self) fast = n->next_of(gi, p) == tail;
-        if (fast) {
-          recs[n_fast++] = raftq_prop_t{gi, (uint32_t)n_pents, (uint32_t)(j - i)};
-          for (size_t k = i; k < j; ++k) {
-            const uint32_t len = (uint32_t)(props.off[k + 1] - props.off[k]);
-            const char* src = props.blob.data() + props.off[k];
-            const char* at = n->arena.put(src, len);
-            if (!at) {
-              n->oom = true;
-              break;
-            }
-            g.log.push_back(n->pool, Entry{g.term, at, len});
-            raftq_prop_ent_t& pe = pents[n_pents++];
-            pe.data_off = len ? n->out_pool.size : 0;
-            pe.data_len = len;
-            pe.type = 0;
-            if (!n->out_pool.append(src, len)) n->out_oom = true;
-            n->prop_cap += 48 + len;
-          }
-          const uint64_t next = g.log.size() + 1;  // bcastAppend's optimistic cursor
-          for (uint32_t p = 0; p < n->N; ++p)
-            if (p != n->self) n->next_of(gi, p) = next;
-          n->tail_set(gi);  // every follower at the tail the device's appendEntry leaves
-          wal_touch(n, gi, g);
-        } else {
-          bool grew = false;
-          for (size_t k = i; k < j; ++k) {
-            const Entry one{0, props.blob.data() + props.off[k], (uint32_t)(props.off[k + 1] - props.off[k])};
-            grew |= handle_proposal(n, gi, g, &one, 1);
-          }
-          if (grew && n->dirty_mark[gi] != ep) {
-            n->dirty_mark[gi] = ep;
-            dirty.push_back(gi);
-          }
-        }
-        i = j;
-      }
-      if (pin_oom) n->out_oom = true;
-      n->stats.msgs_sent += n_fast * (n->N - 1);
-      n->stats.msgs_built_on_device += n_fast * (n->N - 1);
-      n->prop_cap += n_fast * 160;  // (per addressee: flush_outbound multiplies)
-      n->prop_recs.size = n_fast * sizeof(raftq_prop_t);
-      n->prop_ents.size = n_pents * sizeof(raftq_prop_ent_t);
-      if (n->oom) {  // (a device record without its log entry must not go out)
-        n->prop_recs.clear();
-        n->prop_ents.clear();
-      }
-      if (int rc = flush_dirty()) return poison(n, rc, "apply_log_deltas");
-    } else {
-    // The general shape (a group's statements interleaved with other groups'), two passes.
-    // Pass 1 (round 6): which groups go through the device.  A group this node leads whose followers all have Progress.Next at
-    // the log's tail (what bcastAppend leaves behind: every group outside a catch-up) gets ONE raftq_prop_t for the turn, in the
-    // order of its first proposal -- the order its MsgApps take in every peer's stream -- and a count; everybody else takes
-    // round 5's way below (handle_proposal: a follower forwards, a leader with a lagging follower sends from its own log).
-    // prop_mark[g] == ep: through the device, prop_slot[g] = its record; == ep with the top bit set aside: decided, host.
-    std::vector<uint32_t>& pmark = n->prop_mark;
-    constexpr uint32_t kSlowBit = 0x80000000u;
-    const uint32_t ep_fast = ep, ep_slow = ep | kSlowBit;  // (epochs stay below 2^31: next_epoch)
-    size_t n_fast = 0;
-    if (n->propose_device) {
-      bool pin_oom = !n->prop_recs.reserve(np_ * sizeof(raftq_prop_t)) || !n->prop_ents.reserve(np_ * sizeof(raftq_prop_ent_t));
-      raftq_prop_t* recs = n->prop_recs.as<raftq_prop_t>();
-      for (size_t i = 0; i < np_ && !pin_oom; ++i) {
-        if (i + 16 < np_) __builtin_prefetch(&n->groups[props.group[i + 16]]);
-        if (i + 8 < np_) __builtin_prefetch(&n->prog[props.group[i + 8] * n->N * 2]);
-        const uint64_t gi = props.group[i];
-        uint32_t& mk = pmark[gi];
-        if (mk == ep_slow) continue;
-        const uint64_t len = props.off[i + 1] - props.off[i];
-        if (mk == ep_fast) {  // another statement for a group already on its way: one MsgApp carries them all, within raft.Config.MaxSizePerMsg
-          raftq_prop_t& r = recs[n->prop_slot[gi]];
-          r.n_ents++;
-          r.ent_first = (uint32_t)std::min<uint64_t>((uint64_t)r.ent_first + len, 0xffffffffull);  // (the payload bytes so far; the entries' place comes below)
-          continue;
-        }
-        const Group& g = n->groups[gi];
-        bool fast = g.role == RAFTQ_ROLE_LEADER && g.leading;
-        const uint64_t tail = g.log.size() + 1;
-        for (uint32_t p = 0; fast && p < n->N; ++p)
-          if (p != n->self) fast = n->next_of(gi, p) == tail;
-        if (!fast) {
-          mk = ep_slow;
-          continue;
-        }
-        mk = ep_fast;
-        n->prop_slot[gi] = (uint32_t)n_fast;
-        recs[n_fast++] = raftq_prop_t{gi, (uint32_t)std::min<uint64_t>(len, 0xffffffffull), 1};
-      }
-      // a group whose statements outgrow one message (raft.Config.MaxSizePerMsg, raft.go:157: sendAppend would cut it) is the host's
-      uint32_t ent_at = 0;
-      size_t kept = 0;
-      for (size_t k = 0; k < n_fast; ++k) {
-        raftq_prop_t r = recs[k];
-        if (r.n_ents > kMaxEntriesPerMsg || r.ent_first >= kMaxBytesPerMsg) {
-          pmark[r.group] = ep_slow;
-          continue;
-        }
-        r.ent_first = ent_at;
-        ent_at += r.n_ents;
-        r.n_ents = 0;  // (filled again, entry by entry, by the second pass)
-        n->prop_slot[r.group] = (uint32_t)kept;
-        recs[kept++] = r;
-      }
-      n_fast = kept;
-      if (pin_oom) n->out_oom = true;
-    }
-    raftq_prop_t* recs = n->prop_recs.as<raftq_prop_t>();
-    raftq_prop_ent_t* pents = n->prop_ents.as<raftq_prop_ent_t>();
-    size_t n_pents = 0;
-    // Pass 2: every statement, in arrival order.  Through the device: the payload once into the log's arena and once into the
-    // turn's page-locked pool (where the encoder's readers find it), the log's entry, 16 bytes that say where the payload is.
-    for (size_t i = 0; i < np_; ++i) {
-      if (i + 16 < np_) __builtin_prefetch(&n->groups[props.group[i + 16]]);
-      if (i + 8 < np_) {  // appendEntry writes behind the log's last entry
-        const Group& ahead = n->groups[props.group[i + 8]];
-        if (ahead.log.p) __builtin_prefetch(ahead.log.p + ahead.log.n, 1);
-      }
-      const uint64_t gi = props.group[i];
-      const Entry one{0, props.blob.data() + props.off[i], (uint32_t)(props.off[i + 1] - props.off[i])};
-      if (n_fast != 0 && pmark[gi] == ep_fast) {
-        Group& g = n->groups[gi];
-        const char* at = n->arena.put(one.data, one.len);
-        if (!at) {
-          n->oom = true;
-          break;
-        }
-        g.log.push_back(n->pool, Entry{g.term, at, one.len});
-        raftq_prop_t& r = recs[n->prop_slot[gi]];
-        raftq_prop_ent_t& pe = pents[r.ent_first + r.n_ents++];
-        pe.data_off = one.len ? n->out_pool.size : 0;
-        pe.data_len = one.len;
-        pe.type = 0;
-        ++n_pents;
-        if (!n->out_pool.append(one.data, one.len)) n->out_oom = true;
-        n->prop_cap += 48 + one.len;
-        continue;
-      }
-      if (handle_proposal(n, gi, n->groups[gi], &one, 1) && n->dirty_mark[gi] != ep) {
-        n->dirty_mark[gi] = ep;
-        dirty.push_back(gi);
-      }
-    }
-    // what bcastAppend leaves on the host for the groups that went through the device: Progress.Next past what is being sent
-    // (the optimistic cursor), the WAL's dirty mark, the count of sends
-    for (size_t k = 0; k < n_fast; ++k) {
-      if (k + 8 < n_fast) __builtin_prefetch(&n->prog[recs[k + 8].group * n->N * 2], 1);
-      const uint64_t gi = recs[k].group;
-      Group& g = n->groups[gi];
-      const uint64_t next = g.log.size() + 1;
-      for (uint32_t p = 0; p < n->N; ++p)
-        if (p != n->self) n->next_of(gi, p) = next;
-      n->tail_set(gi);
-      wal_touch(n, gi, g);
-    }
-    n->stats.msgs_sent += n_fast * (n->N - 1);
-    n->stats.msgs_built_on_device += n_fast * (n->N - 1);
-    n->prop_cap += n_fast * 160;  // (per addressee: flush_outbound multiplies)
-    n->prop_recs.size = n_fast * sizeof(raftq_prop_t);
-    n->prop_ents.size = n_pents * sizeof(raftq_prop_ent_t);
-    if (n->oom) {  // (a device record without its log entry must not go out)
-      n->prop_recs.clear();
-      n->prop_ents.clear();
-    }
-    if (int rc = flush_dirty()) return poison(n, rc, "apply_log_deltas");
-    }
-  }
-  if (n->oom) {
-    lk.unlock();
-    return poison(n, RAFTQ_ENOMEM, "entry storage");
-  }
-  if (n->broken) {
-    lk.unlock();
-    return poison(n, RAFTQ_ESTATE, "the engine's log tail and the node's log disagree");
-  }
-  // -- wal.Save before transport.Send (raft.go:228-230): the caller persists what raftq_node_wal_poll
-  // hands out before it transmits what raftq_node_poll hands out
-  ph.next(raftq_node::kPhWal);
-  if (int rc = flush_wal_begin(n, lk)) return poison(n, rc, "wal_encode");
-  ph.next(raftq_node::kPhEncode);
-  if (int rc = flush_outbound(n, lk)) return poison(n, rc, "wire_encode");
-  ph.next(raftq_node::kPhWal);
-  if (int rc = flush_wal_end(n, lk)) return poison(n, rc, "wal_encode");
   if (did) n->stats.turns++;
   const uint64_t pub = n->stats.entries_published - published0;
   lk.unlock();

@@ -1,4 +1,4 @@
-"""CPU: the host C++ of the library -- raftq_node.cpp and raftq_pipe.cpp, 1,900 lines of mutexes, condition variables, a
+"""CPU: the host C++ of the library -- raftq_node.cpp and raftq_pipe.cpp, 3,000 lines of mutexes, condition variables, a
 background thread, arenas and queues -- under AddressSanitizer + UBSan, driven by the very suites the GPU box runs against
 libraftq.so (tests/test_node_gpu.py, tests/test_node_scenarios_gpu.py, tests/test_pipe_gpu.py).
 
