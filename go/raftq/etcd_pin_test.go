@@ -11,6 +11,7 @@ package raftq
 import (
 	"math/rand"
 	"testing"
+	"unsafe"
 
 	"github.com/coreos/etcd/raft"
 	pb "github.com/coreos/etcd/raft/raftpb"
@@ -268,3 +269,98 @@ func TestFramesAgainstGogoProto(t *testing.T) {
 //
 // (Left as the procedure in PIN.md rather than code: wal.Create's on-disk head differs between v2.2 and v2.3 -- the range PIN.md
 // says to try -- and a test that cannot be compiled here should not guess which.)
+
+// TestDecodePackedAgainstDecode: etcd's own bytes through the decoder's narrow forms (DecodePacked) give what DecodeMessages
+// gives -- a narrow frame field by field (WireMsg40: all of them; WireHead: the routing word), a wide one as wide[k].
+func TestDecodePackedAgainstDecode(t *testing.T) {
+	e, err := New(0, 4, 3)
+	if err != nil {
+		t.Skip(err)
+	}
+	defer e.Close()
+	rng := rand.New(rand.NewSource(0x9AC4ED))
+	const n = 300
+	var raw []byte
+	offs := []uint64{0}
+	for i := 0; i < n; i++ {
+		m := pb.Message{Type: pb.MessageType(rng.Intn(10)), To: uint64(1 + rng.Intn(2)), From: uint64(1 + rng.Intn(3)), Term: uint64(rng.Int63n(1 << 40)),
+			Index: uint64(rng.Int63n(1 << 50)), Commit: uint64(rng.Int63n(1 << 30)), Reject: rng.Intn(4) == 0}
+		if m.Type == pb.MsgAppResp {
+			m.RejectHint = uint64(rng.Int63n(1 << 10))
+		} else {
+			m.LogTerm = uint64(rng.Int63n(1 << 20))
+		}
+		if m.Type == pb.MsgApp && rng.Intn(2) == 0 {
+			m.Entries = []pb.Entry{{Term: m.Term, Index: m.Index + 1, Data: []byte{byte(i)}}}
+		}
+		b, err := m.Marshal()
+		if err != nil {
+			t.Fatal(err)
+		}
+		var l [8]byte
+		for k := 0; k < 8; k++ {
+			l[k] = byte(uint64(len(b)) >> (56 - 8*k))
+		}
+		raw = append(append(raw, l[:]...), b...)
+		offs = append(offs, uint64(len(raw)))
+	}
+	// page-locked copies: the narrow forms exist in the streaming form only
+	alloc := func(bytes int) []byte {
+		b, err := HostAlloc(bytes)
+		if err != nil {
+			t.Fatal(err)
+		}
+		return b
+	}
+	stream := alloc(len(raw))
+	copy(stream, raw)
+	offB := alloc(8 * len(offs))
+	off := unsafe.Slice((*uint64)(unsafe.Pointer(&offB[0])), len(offs))
+	copy(off, offs)
+	full := unsafe.Slice((*WireMsg)(unsafe.Pointer(&alloc(64 * n)[0])), n)
+	wide := unsafe.Slice((*WireMsg)(unsafe.Pointer(&alloc(64 * n)[0])), n)
+	n40 := unsafe.Slice((*WireMsg40)(unsafe.Pointer(&alloc(40 * n)[0])), n)
+	heads := unsafe.Slice((*WireHead)(unsafe.Pointer(&alloc(8 * n)[0])), n)
+	ents := unsafe.Slice((*WireEnt)(unsafe.Pointer(&alloc(32 * n)[0])), n)
+	if _, bad, err := e.DecodeMessages(stream, off, full, ents); err != nil || bad != 0 {
+		t.Fatal(err, bad)
+	}
+	const toSlot = 0
+	const respKinds = 1<<uint(pb.MsgAppResp) | 1<<uint(pb.MsgVoteResp) | 1<<uint(pb.MsgHeartbeatResp)
+	for _, form := range []int{WireForm40, WireFormHead} {
+		_, _, nWide, err := e.DecodePacked(stream, off, form, respKinds, toSlot, n40, heads, wide, ents)
+		if err != nil {
+			t.Fatal(err)
+		}
+		k := uint64(0)
+		for i := 0; i < n; i++ {
+			h := WireHead{n40[i].Group, n40[i].From, n40[i].Type, n40[i].Reject, n40[i].Flags}
+			if form == WireFormHead {
+				h = heads[i]
+			}
+			f := full[i]
+			if h.Flags&WireWide != 0 {
+				if wide[k] != f || (form == WireForm40 && n40[i].Aux != k) {
+					t.Fatalf("form %d frame %d: wide[%d] = %+v, decoded %+v", form, i, k, wide[k], f)
+				}
+				k++
+				continue
+			}
+			if uint64(h.Group) != f.Group || uint32(h.From) != f.From || h.Type != f.Type || h.Reject != f.Reject || h.Flags != f.Flags || f.To != toSlot || f.NEnts != 0 {
+				t.Fatalf("form %d frame %d: head %+v, decoded %+v", form, i, h, f)
+			}
+			if form == WireForm40 {
+				aux := f.LogTerm
+				if f.Type == uint8(pb.MsgAppResp) {
+					aux = f.RejectHint
+				}
+				if m := n40[i]; m.Term != f.Term || m.Index != f.Index || m.Commit != f.Commit || m.Aux != aux {
+					t.Fatalf("frame %d: narrow %+v, decoded %+v", i, m, f)
+				}
+			}
+		}
+		if k != nWide {
+			t.Fatalf("form %d: %d wide records met, %d reported", form, k, nWide)
+		}
+	}
+}

@@ -230,6 +230,115 @@ func (e *Engine) StepFrames(stream []byte, frameOff []uint64, tailAppends bool, 
 	return uint64(c.n_ents), uint64(c.n_malformed), e.err(rc)
 }
 
+// WireMsg40 / WireHead: the decoder's narrow records (raftq_wire_msg40_t -- Msg40's layout with the flags in its pad byte --
+// and raftq_wire_head_t, include/raftq_wire.h).  A record whose Flags carry WireWide stands for a frame whose full WireMsg is
+// in wide[]; in WireMsg40 its Aux is the position there.
+type WireMsg40 struct {
+	Group  uint32
+	From   uint8 // 0xFF = absent
+	Type   uint8
+	Reject uint8
+	Flags  uint8
+	Term   uint64
+	Index  uint64
+	Aux    uint64 // RejectHint on MsgAppResp, LogTerm on every other kind, the position in wide[] under WireWide
+	Commit uint64
+}
+
+type WireHead struct {
+	Group  uint32
+	From   uint8
+	Type   uint8
+	Reject uint8
+	Flags  uint8
+}
+
+// WireWide / WireForm40 / WireFormHead: RAFTQ_WIRE_F_WIDE, RAFTQ_WIRE_FORM_40, RAFTQ_WIRE_FORM_HEAD
+const (
+	WireWide     = 0x08
+	WireForm40   = 40
+	WireFormHead = 8
+)
+
+// narrowPtr: the narrow array of a packed call (exactly one of n40 / heads is used, by form) and the check that it holds n records
+func narrowPtr(who string, form, n int, n40 []WireMsg40, heads []WireHead) (unsafe.Pointer, error) {
+	switch form {
+	case WireForm40:
+		if len(n40) < n {
+			return nil, fmt.Errorf("raftq: %s: %d frames, room for %d 40-byte records", who, n, len(n40))
+		}
+		return unsafe.Pointer(&n40[0]), nil
+	case WireFormHead:
+		if len(heads) < n {
+			return nil, fmt.Errorf("raftq: %s: %d frames, room for %d heads", who, n, len(heads))
+		}
+		return unsafe.Pointer(&heads[0]), nil
+	}
+	return nil, fmt.Errorf("raftq: %s: form %d is neither WireForm40 nor WireFormHead", who, form)
+}
+
+// DecodePacked is DecodeMessages with narrow records (raftq_wire_decode_packed): every frame gets a WireMsg40 (form
+// WireForm40, in n40) or a WireHead (WireFormHead, in heads; headTypes: bit t = frames of type t may travel as heads), and
+// only a frame the narrow record cannot express exactly -- addressed to another slot than toSlot, carrying entries, ... --
+// also its full WireMsg, in frame order, in wide.  nWide may exceed len(wide): the call then fails, the first len(wide) are
+// written.  Every slice must be page-locked (HostAlloc); no Step batch may be in flight.
+func (e *Engine) DecodePacked(stream []byte, frameOff []uint64, form int, headTypes uint32, toSlot uint32, n40 []WireMsg40, heads []WireHead,
+	wide []WireMsg, ents []WireEnt) (nEnts, nMalformed, nWide uint64, err error) {
+	n := len(frameOff) - 1
+	if n <= 0 {
+		return 0, 0, 0, nil
+	}
+	pn, err := narrowPtr("DecodePacked", form, n, n40, heads)
+	if err != nil {
+		return 0, 0, 0, err
+	}
+	var pw *C.raftq_wire_msg_t
+	if len(wide) > 0 {
+		pw = (*C.raftq_wire_msg_t)(unsafe.Pointer(&wide[0]))
+	}
+	var pe *C.raftq_wire_ent_t
+	if len(ents) > 0 {
+		pe = (*C.raftq_wire_ent_t)(unsafe.Pointer(&ents[0]))
+	}
+	var c C.raftq_wire_counts_t
+	var nw C.uint64_t
+	rc := C.raftq_wire_decode_packed(e.h, bytesPtr(stream), C.uint64_t(len(stream)), (*C.uint64_t)(unsafe.Pointer(&frameOff[0])), C.uint64_t(n),
+		C.int(form), C.uint32_t(headTypes), C.uint32_t(toSlot), pn, pw, C.uint64_t(len(wide)), pe, C.uint64_t(len(ents)), &c, &nw)
+	return uint64(c.n_ents), uint64(c.n_malformed), uint64(nw), e.err(rc)
+}
+
+// StepFramesPacked is StepFrames with narrow records (raftq_step_frames_packed; toSlot is the engine's own slot): results,
+// state and ents as StepFrames gives them, the link carries the narrow array and the wide frames only.  nWide may exceed
+// len(wide): the frames have been stepped all the same, DecodeMessages fetches the rest.
+func (e *Engine) StepFramesPacked(stream []byte, frameOff []uint64, tailAppends bool, form int, headTypes uint32, n40 []WireMsg40, heads []WireHead,
+	wide []WireMsg, ents []WireEnt) (nEnts, nMalformed, nWide uint64, err error) {
+	n := len(frameOff) - 1
+	if n <= 0 {
+		return 0, 0, 0, nil
+	}
+	pn, err := narrowPtr("StepFramesPacked", form, n, n40, heads)
+	if err != nil {
+		return 0, 0, 0, err
+	}
+	var pw *C.raftq_wire_msg_t
+	if len(wide) > 0 {
+		pw = (*C.raftq_wire_msg_t)(unsafe.Pointer(&wide[0]))
+	}
+	var pe *C.raftq_wire_ent_t
+	if len(ents) > 0 {
+		pe = (*C.raftq_wire_ent_t)(unsafe.Pointer(&ents[0]))
+	}
+	ta := C.int(0)
+	if tailAppends {
+		ta = 1
+	}
+	var c C.raftq_wire_counts_t
+	var nw C.uint64_t
+	rc := C.raftq_step_frames_packed(e.h, bytesPtr(stream), C.uint64_t(len(stream)), (*C.uint64_t)(unsafe.Pointer(&frameOff[0])), C.uint64_t(n), ta,
+		C.int(form), C.uint32_t(headTypes), pn, pw, C.uint64_t(len(wide)), pe, C.uint64_t(len(ents)), &c, &nw)
+	return uint64(c.n_ents), uint64(c.n_malformed), uint64(nw), e.err(rc)
+}
+
 // StepFramesRespond is StepFrames plus the messages its results call for, built and marshalled on the device
 // (raftq_step_frames_respond; raft.go:268-270 -> :227-230): MsgAppResp / MsgVoteResp / MsgHeartbeatResp to the senders and the
 // commit broadcast of a group whose at-tail bit is set (atTail: one bit per group, nil = none).  out receives rafthttp frames,

@@ -124,6 +124,69 @@ int raftq_wire_decode(raftq_t* h, const void* stream, uint64_t nbytes, const uin
                       raftq_wire_msg_t* msgs /*[n]*/, raftq_wire_ent_t* ents /*[ents_cap]|NULL*/, uint64_t ents_cap,
                       raftq_wire_counts_t* counts /*|NULL*/);
 
+/* ---- the narrow output forms of the streaming decoder ----------------------------------------------------------------
+ * The 64-byte records are the largest block of bytes a decode sends over the link, and a node reads 7 of them from an
+ * acknowledgement once Step has consumed the rest on the device.  The two calls below give EVERY frame a fixed-size narrow
+ * record -- raftq_wire_msg40_t (RAFTQ_WIRE_FORM_40, lossless) or raftq_wire_head_t (RAFTQ_WIRE_FORM_HEAD, the routing word) --
+ * and only a frame the narrow record cannot express exactly ("wide") ALSO its full raftq_wire_msg_t, compacted in frame
+ * order into a second, short array wide[].
+ *
+ * A frame is NARROW when all of these hold:
+ *   - it is malformed (the all-zero record plus RAFTQ_WIRE_F_MALFORMED: always narrow), or it parsed and
+ *   - group < 2^32;
+ *   - from <= 254, or from is absent (0xFFFFFFFF in the full record, written as 0xFF);
+ *   - to == to_slot;
+ *   - n_ents == 0;
+ *   - the one of log_term / reject_hint its kind does not carry is 0: log_term for MsgAppResp, reject_hint for every other
+ *     kind (evaluated after raftq_step_frames has overwritten a MsgApp's reject_hint);
+ *   - RAFTQ_WIRE_FORM_HEAD only: the bit of its type is set in the caller's head_types mask (bit t = type t, t < 32) and
+ *     reject == 0.  term, index, log_term, commit and reject_hint of such a frame are NOT delivered: the caller's declared
+ *     choice, for the kinds whose fields it has had consumed on the device.
+ * Every other frame is WIDE: its narrow record carries RAFTQ_WIRE_F_WIDE, its other fields are the full record's truncated
+ * to their width, and in RAFTQ_WIRE_FORM_40 aux = k, the frame's position in wide[].  wide[] is in ascending frame order
+ * in both forms, so k is also the number of WIDE records in front of this one.
+ *
+ * Expansion is exact: from the narrow array, wide[], to_slot and the form every 64-byte record raftq_wire_decode would have
+ * written is recovered byte for byte (RAFTQ_WIRE_FORM_HEAD: in the delivered fields) -- a wide frame's from wide[k]; a narrow
+ * one's as group, from (0xFF -> 0xFFFFFFFF), type, reject, flags, term, index, commit as they stand, to = to_slot,
+ * ent_first = n_ents = 0, aux -> reject_hint (MsgAppResp) or log_term (every other kind), the other one 0; a malformed one's
+ * as all-zero but the flags.  flags includes the SNAPSHOT and GROUP bits and Step's RAFTQ_MSGF_*; the bit RAFTQ_WIRE_F_WIDE
+ * exists only in the narrow record. */
+#define RAFTQ_WIRE_F_WIDE 0x08u /* narrow record: this frame's full record is in wide[] (the one flag bit that is free: 0x01-0x04 are RAFTQ_WIRE_F_*, 0x10-0x80 RAFTQ_MSGF_*) */
+#define RAFTQ_WIRE_FORM_40 40   /* lossless */
+#define RAFTQ_WIRE_FORM_HEAD 8  /* routing word only: for a caller that has had the fields consumed on the device */
+
+typedef struct raftq_wire_msg40 { /* raftq_msg40_t's layout, flags in its pad byte */
+  uint32_t group;
+  uint8_t from; /* 0xFF = absent */
+  uint8_t type;
+  uint8_t reject;
+  uint8_t flags; /* RAFTQ_WIRE_F_* | RAFTQ_MSGF_* */
+  uint64_t term;
+  uint64_t index;
+  uint64_t aux; /* reject_hint on MsgAppResp, log_term on every other kind; WIDE: position in wide[] */
+  uint64_t commit;
+} raftq_wire_msg40_t; /* 40 bytes */
+typedef struct raftq_wire_head {
+  uint32_t group;
+  uint8_t from;
+  uint8_t type;
+  uint8_t reject;
+  uint8_t flags;
+} raftq_wire_head_t; /* 8 bytes */
+
+/* raftq_wire_decode with narrow records.  ents, counts and the preconditions are raftq_wire_decode's on the same input.
+ * narrow: n records of `form` bytes; wide: room for wide_cap records (NULL with wide_cap = 0); *n_wide (may be NULL): how
+ * many wide frames there are.  More of them than wide_cap: the narrow records and the first wide_cap wide records are
+ * written, RAFTQ_EINVAL (the ents_cap rule) -- nothing at or behind wide[wide_cap] or narrow[n] is ever written.
+ * Streaming form only: every array must be page-locked and 16-byte aligned, form one of the two, to_slot < 255 --
+ * RAFTQ_EINVAL otherwise, before anything is enqueued.  RAFTQ_ESTATE while a Step batch is in flight on the handle (a
+ * precondition plain raftq_wire_decode does not have: the call shares the in-flight batch's control words). */
+int raftq_wire_decode_packed(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off /*[n+1]*/, uint64_t n,
+                             int form, uint32_t head_types, uint32_t to_slot,
+                             void* narrow /*[n] records of `form` bytes*/, raftq_wire_msg_t* wide /*[wide_cap]*/, uint64_t wide_cap,
+                             raftq_wire_ent_t* ents /*|NULL*/, uint64_t ents_cap, raftq_wire_counts_t* counts /*|NULL*/, uint64_t* n_wide /*|NULL*/);
+
 /* Walk the length words of a byte buffer (host side; pointer chasing, inherently serial):
  * off[0..n] for the n whole frames found.  big_endian = 1 for rafthttp streams, 0 for WAL files.
  * *n_frames = whole frames; *consumed = bytes they cover (a torn tail is left to the caller). */
@@ -166,6 +229,18 @@ int raftq_step_wire_entries(raftq_t* h, const raftq_wire_ent_t** ents, uint64_t*
 int raftq_step_frames(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off /*[n+1]*/, uint64_t n, int tail_appends,
                       raftq_wire_msg_t* msgs /*[n]*/, raftq_wire_ent_t* ents /*[ents_cap]|NULL*/, uint64_t ents_cap,
                       raftq_wire_counts_t* counts /*|NULL*/);
+
+/* raftq_step_frames with narrow records (see raftq_wire_decode_packed): results, state afterwards, ents, counts and the
+ * preconditions are exactly raftq_step_frames' on the same input; to_slot is the handle's own slot (raftq_set_self).  Step
+ * still reads the full 64-byte records, from the decoder's copy in HBM -- what crosses the link is the narrow array and the
+ * wide frames (MsgApp / MsgProp with entries, rejections in RAFTQ_WIRE_FORM_HEAD, anything odd).  More wide frames than
+ * wide_cap is NOT an error here -- the frames have been stepped: *n_wide says how many there are, the first wide_cap are
+ * written, raftq_wire_decode fetches the rest.  A refusal (an array not page-locked and 16-byte aligned, a bad form, an own
+ * slot >= 255: RAFTQ_EINVAL; a batch in flight: RAFTQ_ESTATE) comes before anything is enqueued: nothing is applied. */
+int raftq_step_frames_packed(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off /*[n+1]*/, uint64_t n, int tail_appends,
+                             int form, uint32_t head_types,
+                             void* narrow /*[n] records of `form` bytes*/, raftq_wire_msg_t* wide /*[wide_cap]*/, uint64_t wide_cap,
+                             raftq_wire_ent_t* ents /*[ents_cap]|NULL*/, uint64_t ents_cap, raftq_wire_counts_t* counts /*|NULL*/, uint64_t* n_wide /*|NULL*/);
 
 /* raftq_step_frames + the messages its results call for, built and marshalled on the device (raft.go:268-270 -> :227-230:
  * rc.node.Step's responses and the commit broadcast, then rc.transport.Send) -- ONE submission with one wait (a batch that stalls

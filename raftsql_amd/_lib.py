@@ -170,6 +170,10 @@ _WIRE_SIGS = [
     ("raftq_step_submit_wire", C.c_int, [_H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
     ("raftq_step_frames", C.c_int, [_H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64,
                                     C.c_void_p]),
+    ("raftq_wire_decode_packed", C.c_int, [_H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p,
+                                           C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(WireCounts), C.POINTER(C.c_uint64)]),
+    ("raftq_step_frames_packed", C.c_int, [_H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_uint32, C.c_void_p,
+                                           C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(WireCounts), C.POINTER(C.c_uint64)]),
     ("raftq_step_frames_respond", C.c_int, [_H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64,
                                             C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(WireCounts),
                                             C.POINTER(WireCounts)]),

@@ -274,8 +274,18 @@ void free_wire_state(raftq_t* h);               // raftq_wire.hip's allocations 
 // raftq_wire.hip, for raftq_step_frames (raftq_step.hip): the streaming decode with a node's checks, enqueued on the handle's
 // stream and not waited for (the records also go to msgs_d, in HBM, for the Step kernels enqueued behind it); and what the
 // decode has to say once the call's one wait is over.  RAFTQ_EINVAL when an array is not page-locked and 16-byte aligned.
+// packed (raftq_step_frames_packed): `msgs` is the caller's array of narrow records of `form` bytes, wide[] gets the rest
+// (to_slot = the handle's own); wire_frames_n_wide after the wait: how many wide records there were.
+struct PackedDst {
+  int form;  // RAFTQ_WIRE_FORM_40 | RAFTQ_WIRE_FORM_HEAD
+  uint32_t head_types;
+  void* wide;
+  uint64_t wide_cap;
+};
 int wire_frames_enqueue(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off, uint64_t n, void* msgs, void* ents,
-                        uint64_t ents_cap, void* msgs_d, int tail_appends, void* zero2 /* two device words left zero, or nullptr */);
+                        uint64_t ents_cap, void* msgs_d, int tail_appends, void* zero2 /* two device words left zero, or nullptr */,
+                        const PackedDst* packed = nullptr);
+uint64_t wire_frames_n_wide(raftq_t* h);
 int wire_frames_finish(raftq_t* h, const uint64_t* frame_off, uint64_t n, bool have_ents, uint64_t ents_cap, ::raftq_wire_counts* counts);
 // raftq_step_frames_respond (raftq_step.hip): the checks that come before anything is enqueued (every array page-locked and
 // 16-byte aligned, the scratch allocated), then -- behind the Step chain, on the handle's stream -- the layout of the responses

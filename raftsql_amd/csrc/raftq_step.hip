@@ -426,6 +426,7 @@ struct WireSrc {
   void* ents_h = nullptr;
   uint64_t ents_cap = 0;
   int tail_appends = 0;
+  const raftq_detail::PackedDst* packed = nullptr;  // raftq_step_frames_packed: msgs_h is the narrow array
 };
 
 // key -> stable radix sort -> walk, on the handle's stream (the path that takes runs of any length)
@@ -623,7 +624,7 @@ static int submit_impl(raftq_t* h, const void* msgs, uint64_t n, const WireSrc* 
     // one kernel: readers pull boundaries + stream, workers parse, check, flag (RAFTQ_MSGF_*) and push records + entry headers
     // to the caller's arrays and the records once more into this slot's scratch
     if (int rc = raftq_detail::wire_frames_enqueue(h, wire->stream, wire->nbytes, wire->frame_off, n, wire->msgs_h, wire->ents_h,
-                                                   wire->ents_cap, s.msgs, wire->tail_appends, s.n_heads))
+                                                   wire->ents_cap, s.msgs, wire->tail_appends, s.n_heads, wire->packed))
       return rc;
   } else if (wire) {
     // frames -> the batch's message records, in HBM: the 64-byte records never cross PCIe.  (s.w_bad only counts
@@ -916,6 +917,37 @@ int raftq_step_frames(raftq_t* h, const void* stream, uint64_t nbytes, const uin
     h->step_last_n = 0;
     return rc_dec;
   }
+  return rc_step;
+}
+
+int raftq_step_frames_packed(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off, uint64_t n, int tail_appends, int form,
+                             uint32_t head_types, void* narrow, raftq_wire_msg_t* wide, uint64_t wide_cap, raftq_wire_ent_t* ents, uint64_t ents_cap,
+                             raftq_wire_counts_t* counts, uint64_t* n_wide) {
+  const char* who = "raftq_step_frames_packed";
+  if (int rc = use_device(h)) return rc;
+  if (counts) *counts = raftq_wire_counts_t{0, 0, 0, 0};
+  if (n_wide) *n_wide = 0;
+  if (h->step_collected != h->step_submitted)
+    return fail(h, RAFTQ_ESTATE, std::string(who) + ": submitted batches are still in flight; collect them first");
+  h->step_last_out = nullptr;
+  h->step_last_n = 0;
+  if (form != RAFTQ_WIRE_FORM_40 && form != RAFTQ_WIRE_FORM_HEAD)
+    return fail(h, RAFTQ_EINVAL, std::string(who) + ": form is neither RAFTQ_WIRE_FORM_40 nor RAFTQ_WIRE_FORM_HEAD");
+  if (h->self_peer >= 255) return fail(h, RAFTQ_EINVAL, std::string(who) + ": the handle's own slot must be a peer slot (< 255)");
+  if (n == 0) return RAFTQ_OK;
+  if ((!stream && nbytes) || !frame_off || !narrow || (wide_cap && !wide)) return fail(h, RAFTQ_EINVAL, std::string(who) + ": null argument");
+  const raftq_detail::PackedDst pd{form, head_types, wide, wide_cap};
+  WireSrc w{stream, nbytes, frame_off, true, narrow, ents, ents ? ents_cap : 0, tail_appends, &pd};
+  if (int rc = submit_impl(h, nullptr, n, &w, who)) return rc;
+  // one wait, as raftq_step_frames
+  const int rc_step = raftq_step_collect(h, nullptr, nullptr);
+  const int rc_dec = raftq_detail::wire_frames_finish(h, frame_off, n, ents != nullptr, ents_cap, counts);
+  if (rc_dec != RAFTQ_OK) {
+    h->step_last_out = nullptr;
+    h->step_last_n = 0;
+    return rc_dec;
+  }
+  if (n_wide) *n_wide = raftq_detail::wire_frames_n_wide(h);  // more than wide_cap is no error here: the frames have been stepped
   return rc_step;
 }
 

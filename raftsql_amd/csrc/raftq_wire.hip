@@ -439,8 +439,9 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
 
 // The streaming decode (raftq_wire_kernels.hpp "the streaming form"), enqueued on the handle's stream and NOT waited for;
 // v_*: the caller's arrays as the device addresses them.  msgs_d / ff: see wire_dec_fused_kernel (raftq_step_frames).
+// form: 0 -- v_msgs receives 64-byte records; RAFTQ_WIRE_FORM_40 / _HEAD -- v_msgs is the narrow array, pk the wide one.
 static int decode_streaming_enqueue(raftq_t* h, const void* v_stream, uint64_t nbytes, const void* v_off, uint64_t n, void* v_msgs, void* v_ents,
-                                    uint64_t ents_cap, WireMsg* msgs_d, FrameFilter ff) {
+                                    uint64_t ents_cap, WireMsg* msgs_d, FrameFilter ff, int form = 0, PackedOut pk = PackedOut{nullptr, 0, 0, 0}) {
   const uint32_t n_tiles = (uint32_t)((n + kDecTile - 1) / kDecTile);
   // 208 workers, one per CU beside the readers as in round 5 -- at 68 KB two fit, but 464 workers measured SLOWER than 208 (173.9
   // against 167.6 us a call, profiles/r06/wire_tile_ab.jsonl): with 256 tiles in a 64K-frame call every tile has its own waiting
@@ -456,8 +457,16 @@ static int decode_streaming_enqueue(raftq_t* h, const void* v_stream, uint64_t n
   if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, c.off)) return rc;
   if (int rc = bind_feed(h, plan, (uint8_t*)h->wire_dev, ctl.status[kLbFlags])) return rc;
   WireEnt* spill = (WireEnt*)((uint8_t*)h->wire_dev + o_spill);
-  hipLaunchKernelGGL(wire_dec_fused_kernel<kDecTile>, dim3(plan.in.readers + workers), dim3(kDecTile), 0, h->stream, plan.in, nbytes, n, (WireMsg*)v_msgs,
-                     (WireEnt*)v_ents, ents_cap, ctl, h->wire_pin_d, msgs_d, ff, spill);
+  const dim3 grid(plan.in.readers + workers);
+  if (form == RAFTQ_WIRE_FORM_40)
+    hipLaunchKernelGGL((wire_dec_fused_kernel<kDecTile, RAFTQ_WIRE_FORM_40>), grid, dim3(kDecTile), 0, h->stream, plan.in, nbytes, n, (WireMsg*)v_msgs,
+                       (WireEnt*)v_ents, ents_cap, ctl, h->wire_pin_d, msgs_d, ff, spill, pk);
+  else if (form == RAFTQ_WIRE_FORM_HEAD)
+    hipLaunchKernelGGL((wire_dec_fused_kernel<kDecTile, RAFTQ_WIRE_FORM_HEAD>), grid, dim3(kDecTile), 0, h->stream, plan.in, nbytes, n, (WireMsg*)v_msgs,
+                       (WireEnt*)v_ents, ents_cap, ctl, h->wire_pin_d, msgs_d, ff, spill, pk);
+  else
+    hipLaunchKernelGGL((wire_dec_fused_kernel<kDecTile, 0>), grid, dim3(kDecTile), 0, h->stream, plan.in, nbytes, n, (WireMsg*)v_msgs,
+                       (WireEnt*)v_ents, ents_cap, ctl, h->wire_pin_d, msgs_d, ff, spill, pk);
   HIPCHK(h, hipGetLastError());
   tile_ctl_launched(h, n_tiles, workers);
   return RAFTQ_OK;
@@ -480,18 +489,25 @@ static int decode_streaming_finish(raftq_t* h, const char* who, const uint64_t* 
 
 }  // extern "C"
 int raftq_detail::wire_frames_enqueue(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off, uint64_t n, void* msgs, void* ents,
-                                      uint64_t ents_cap, void* msgs_d, int tail_appends, void* zero2) {
+                                      uint64_t ents_cap, void* msgs_d, int tail_appends, void* zero2, const PackedDst* packed) {
   if (n > kMaxItems) return fail(h, RAFTQ_EINVAL, "raftq_step_frames: batch too large");
   if (int rc = ensure_pin(h)) return rc;
-  void *v_stream = nullptr, *v_off = nullptr, *v_msgs = nullptr, *v_ents = nullptr;
+  void *v_stream = nullptr, *v_off = nullptr, *v_msgs = nullptr, *v_ents = nullptr, *v_wide = nullptr;
+  const bool wide = packed && packed->wide_cap != 0;
   const bool mapped = (nbytes == 0 || (v_stream = dev_view(stream)) != nullptr) && (v_off = dev_view(frame_off)) != nullptr &&
-                      (v_msgs = dev_view(msgs)) != nullptr && (!ents || (v_ents = dev_view(ents)) != nullptr);
-  if (!(mapped && nbytes < (1ull << (kLbValueBits - 1)) && aligned16(v_stream) && aligned16(v_off) && aligned16(v_msgs) && aligned16(v_ents)))
+                      (v_msgs = dev_view(msgs)) != nullptr && (!ents || (v_ents = dev_view(ents)) != nullptr) &&
+                      (!wide || (v_wide = dev_view(packed->wide)) != nullptr);
+  if (!(mapped && nbytes < (1ull << (kLbValueBits - 1)) && aligned16(v_stream) && aligned16(v_off) && aligned16(v_msgs) && aligned16(v_ents) &&
+        aligned16(v_wide)))
     return fail(h, RAFTQ_EINVAL, "raftq_step_frames: the stream, the boundaries and the result arrays must be page-locked (raftq_host_alloc, "
                                  "hipHostMalloc, hipHostRegister) and 16-byte aligned -- decode and step in two calls otherwise");
   const FrameFilter ff{1u, h->N, h->self_peer, tail_appends ? 1u : 0u, h->G, (unsigned long long*)zero2};
+  if (packed)
+    return decode_streaming_enqueue(h, v_stream, nbytes, v_off, n, v_msgs, v_ents, ents ? ents_cap : 0, (WireMsg*)msgs_d, ff, packed->form,
+                                    PackedOut{(WireMsg*)v_wide, wide ? packed->wide_cap : 0, packed->head_types, h->self_peer});
   return decode_streaming_enqueue(h, v_stream, nbytes, v_off, n, v_msgs, v_ents, ents ? ents_cap : 0, (WireMsg*)msgs_d, ff);
 }
+uint64_t raftq_detail::wire_frames_n_wide(raftq_t* h) { return h->wire_pin[2]; }
 // ---- raftq_step_frames_respond ----------------------------------------------------------------------------------------
 namespace {
 constexpr uint32_t kRespPin = 16;  // the encoder's totals go to wire_pin[16 ..]: [0 .. 3] are the decoder's, [8 ..] a pending WAL encode's
@@ -687,6 +703,41 @@ int raftq_wire_decode(raftq_t* h, const void* stream, uint64_t nbytes, const uin
     if (int rc = d2h(h, ents, d_ents, total * sizeof(WireEnt))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
   }
+  return RAFTQ_OK;
+}
+
+int raftq_wire_decode_packed(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off, uint64_t n, int form, uint32_t head_types,
+                             uint32_t to_slot, void* narrow, raftq_wire_msg_t* wide, uint64_t wide_cap, raftq_wire_ent_t* ents, uint64_t ents_cap,
+                             raftq_wire_counts_t* counts, uint64_t* n_wide) {
+  const char* who = "raftq_wire_decode_packed";
+  if (int rc = raftq_detail::use_device_idle(h, who)) return rc;  // (pin[2] and the scratch are a Step batch's while one is in flight)
+  if (counts) *counts = raftq_wire_counts_t{0, 0, 0, 0};
+  if (n_wide) *n_wide = 0;
+  if (form != RAFTQ_WIRE_FORM_40 && form != RAFTQ_WIRE_FORM_HEAD) return fail(h, RAFTQ_EINVAL, std::string(who) + ": form is neither RAFTQ_WIRE_FORM_40 nor RAFTQ_WIRE_FORM_HEAD");
+  if (to_slot >= 255) return fail(h, RAFTQ_EINVAL, std::string(who) + ": to_slot must be a peer slot (< 255)");
+  if (n == 0) return RAFTQ_OK;
+  if ((!stream && nbytes) || !frame_off || !narrow || (wide_cap && !wide)) return fail(h, RAFTQ_EINVAL, std::string(who) + ": null argument");
+  if (n > kMaxItems) return fail(h, RAFTQ_EINVAL, std::string(who) + ": batch too large");
+  if (!ents) ents_cap = 0;
+  if (int rc = ensure_pin(h)) return rc;
+  void *v_stream = nullptr, *v_off = nullptr, *v_narrow = nullptr, *v_wide = nullptr, *v_ents = nullptr;
+  const bool mapped = (nbytes == 0 || (v_stream = dev_view(stream)) != nullptr) && (v_off = dev_view(frame_off)) != nullptr &&
+                      (v_narrow = dev_view(narrow)) != nullptr && (wide_cap == 0 || (v_wide = dev_view(wide)) != nullptr) &&
+                      (!ents || (v_ents = dev_view(ents)) != nullptr);
+  if (!(mapped && nbytes < (1ull << (kLbValueBits - 1)) && aligned16(v_stream) && aligned16(v_off) && aligned16(v_narrow) && aligned16(v_wide) &&
+        aligned16(v_ents)))
+    return fail(h, RAFTQ_EINVAL, std::string(who) + ": every array must be page-locked (raftq_host_alloc, hipHostMalloc, hipHostRegister) and "
+                                                    "16-byte aligned -- the narrow forms exist in the streaming form only");
+  if (int rc = decode_streaming_enqueue(h, v_stream, nbytes, v_off, n, v_narrow, v_ents, ents_cap, nullptr, FrameFilter{0, 0, 0, 0, 0, nullptr}, form,
+                                        PackedOut{(WireMsg*)v_wide, wide_cap, head_types, to_slot}))
+    return rc;
+  HIPCHK(h, raftq_detail::wait_call(h));
+  const int rc = decode_streaming_finish(h, who, frame_off, n, ents != nullptr, ents_cap, true, counts);
+  if (rc == RAFTQ_EHIP) return rc;  // a look-back gave up: no total is to be trusted
+  const uint64_t total_wide = h->wire_pin[2];
+  if (n_wide) *n_wide = total_wide;
+  if (rc != RAFTQ_OK) return rc;
+  if (total_wide > wide_cap) return fail(h, RAFTQ_EINVAL, std::string(who) + ": more wide frames than wide_cap (*n_wide is the number needed)");
   return RAFTQ_OK;
 }
 

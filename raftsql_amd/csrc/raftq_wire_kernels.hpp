@@ -963,6 +963,80 @@ __device__ __forceinline__ WaveStage stage_wave_frames_dma(const uint8_t* stream
   return st;
 }
 
+// ---- the narrow output forms of the streaming decoder (raftq_wire_decode_packed / raftq_step_frames_packed, raftq_wire.h) ----
+// Two thirds of what the decoder sends over the link nobody reads: every frame gets a narrow record of NARROW bytes
+// (40: raftq_wire_msg40_t, lossless; 8: raftq_wire_head_t, the routing word), and only a frame the narrow record cannot express
+// exactly ("wide") also gets its 64-byte record, compacted in frame order into wide[].
+struct PackedOut {
+  WireMsg* wide_h;      // the caller's wide[] as the device addresses it (16-byte aligned), or nullptr with wide_cap == 0
+  uint64_t wide_cap;
+  uint32_t head_types;  // NARROW == 8: bit t = frames of type t may travel as heads
+  uint32_t to_slot;     // the addressee every narrow frame has
+};
+constexpr uint8_t kWireWide = 0x08;  // == RAFTQ_WIRE_F_WIDE
+// the rule of raftq_wire.h "When a frame is narrow", negated
+template <int NARROW>
+__device__ __forceinline__ bool packed_is_wide(const WireMsg& m, const PackedOut& pk) {
+  if (m.flags & kWireMalformed) return false;  // the all-zero record: always narrow
+  const uint64_t unused = m.type == 4 ? m.log_term : m.reject_hint;  // (MsgAppResp carries reject_hint, every other kind log_term)
+  bool wide = (m.group >> 32) != 0 || (m.from > 254u && m.from != 0xffffffffu) || m.to != pk.to_slot || m.n_ents != 0 || unused != 0;
+  if (NARROW == 8) wide = wide || m.type >= 32 || ((pk.head_types >> (m.type & 31)) & 1u) == 0 || m.reject != 0;
+  return wide;
+}
+// {group, from, type, reject, flags}: the first 8 bytes of either narrow record
+__device__ __forceinline__ uint64_t packed_head_word(const WireMsg& m, bool wide) {
+  const uint32_t hi = (m.from & 0xffu) | ((uint32_t)m.type << 8) | ((uint32_t)m.reject << 16) | ((uint32_t)(uint8_t)(m.flags | (wide ? kWireWide : 0)) << 24);
+  return (uint64_t)(uint32_t)m.group | ((uint64_t)hi << 32);
+}
+// The tile's way out in a narrow form, by the whole workgroup.  lds: the scalar fields' file, free by now -- the narrow records
+// (TB * NARROW bytes) and behind them the tile's wide records in frame order (<= TB * 64): 26 KB of its 34.  wide_at: this
+// lane's position among the tile's wide records; wide0: the number of wide records in the tiles before this one.
+template <int NARROW, int TB>
+__device__ __forceinline__ void tile_packed_out(const WireMsg& m, bool live, bool wide, uint32_t wide_at, uint32_t tile_wide, uint64_t wide0,
+                                                uint8_t* lds, uint8_t* narrow_h, const PackedOut& pk, uint64_t tile0, uint64_t n, WireMsg* msgs_d) {
+  static_assert(NARROW == 8 || NARROW == 40, "raftq_wire_head_t or raftq_wire_msg40_t");
+  static_assert((TB * NARROW) % 16 == 0, "a tile's narrow run starts on a quad");
+  const uint32_t tid = threadIdx.x;
+  if (live) {
+    uint64_t* rec = reinterpret_cast<uint64_t*>(lds + tid * NARROW);
+    rec[0] = packed_head_word(m, wide);
+    if (NARROW == 40) {
+      rec[1] = m.term;
+      rec[2] = m.index;
+      rec[3] = wide ? wide0 + wide_at : m.type == 4 ? m.reject_hint : m.log_term;
+      rec[4] = m.commit;
+    }
+    u32x4 q[4];
+    __builtin_memcpy(q, &m, sizeof(WireMsg));
+    if (wide) {
+      u32x4* w = reinterpret_cast<u32x4*>(lds + TB * NARROW) + wide_at * 4;
+#pragma unroll
+      for (uint32_t k = 0; k < 4; ++k) w[k] = q[k];
+    }
+    if (msgs_d != nullptr) {  // Step's copy stays 64 bytes a frame: a whole line per lane, it never leaves HBM
+      u32x4* dd = reinterpret_cast<u32x4*>(msgs_d + tile0 + tid);
+#pragma unroll
+      for (uint32_t k = 0; k < 4; ++k) dd[k] = q[k];
+    }
+  }
+  __syncthreads();
+  // the narrow run: one contiguous stretch of the caller's array, whole quads; an odd count of 8-byte halves leaves ONE half at
+  // the very end of the array (the last tile only) -- stored as 8 bytes, never rounded up
+  const uint64_t live_recs = n - tile0 < (uint64_t)TB ? n - tile0 : (uint64_t)TB;
+  const uint32_t bytes = (uint32_t)live_recs * NARROW, quads = bytes >> 4;
+  uint8_t* dst = narrow_h + tile0 * NARROW;
+  const u32x4* src_q = reinterpret_cast<const u32x4*>(lds);
+  for (uint32_t q = tid; q < quads; q += TB) __builtin_nontemporal_store(src_q[q], reinterpret_cast<u32x4*>(dst) + q);
+  if ((bytes & 8u) != 0 && tid == 0)
+    __builtin_nontemporal_store(*reinterpret_cast<const uint64_t*>(lds + (quads << 4)), reinterpret_cast<uint64_t*>(dst + (quads << 4)));
+  // the wide run: whole 64-byte records at wide[wide0 ..], cut at wide_cap
+  const uint64_t room = wide0 < pk.wide_cap ? pk.wide_cap - wide0 : 0;
+  const uint32_t wquads = (uint32_t)(tile_wide < room ? tile_wide : room) * 4;
+  const u32x4* wsrc = reinterpret_cast<const u32x4*>(lds + TB * NARROW);
+  u32x4* wdst = reinterpret_cast<u32x4*>(pk.wide_h + wide0);
+  for (uint32_t q = tid; q < wquads; q += TB) __builtin_nontemporal_store(wsrc[q], wdst + q);
+}
+
 // raftq_wire_decode on page-locked buffers: everything in one launch (see above).  Readers bring the frame boundaries
 // (array 0) and the stream (array 1) into the scratch; msgs_h / ents_h are the caller's result arrays as the device
 // addresses them.  pin[0] = entries found, pin[1] = malformed frames (written by the worker of the last tile, whose
@@ -989,10 +1063,12 @@ constexpr uint8_t kFrameSkip = 0x10, kFrameHold = 0x20, kFrameBarrier = 0x40, kF
 // frames, one box, one process): 256 frames 172 us a call, 128 frames 186 -- residency is not what bounds a call (every tile
 // has a worker waiting for its bytes either way; the call is its input over the link plus ONE tile's chain), and twice the
 // tiles are twice the look-back words, barriers and status traffic.  It was removed; only <256> is launched.
-template <int TB>
+// NARROW (round 7): 0 -- msgs_h receives the 64-byte records (the body below is what it was); 40 / 8 -- msgs_h is the caller's
+// array of narrow records, pk says where the wide ones go; pin[2] = wide records found (the third look-back word, status[2]).
+template <int TB, int NARROW = 0>
 static __global__ __launch_bounds__(TB) void wire_dec_fused_kernel(InFeed in, uint64_t nbytes, uint64_t n, WireMsg* msgs_h, WireEnt* ents_h,
                                                                    uint64_t ents_cap, TileCtl ctl, uint64_t* __restrict__ pin,
-                                                                   WireMsg* msgs_d, FrameFilter ff, WireEnt* __restrict__ ent_spill) {
+                                                                   WireMsg* msgs_d, FrameFilter ff, WireEnt* __restrict__ ent_spill, PackedOut pk) {
   constexpr int W = TB / 64;
   if (blockIdx.x < in.readers) {
     reader_role<TB>(in, ctl.epoch);
@@ -1063,15 +1139,33 @@ static __global__ __launch_bounds__(TB) void wire_dec_fused_kernel(InFeed in, ui
     }
     const uint32_t cnt = live ? m.n_ents : 0u;
     const uint64_t mb = __ballot(malformed);
-    if ((tid & 63) == 0) wave_bad[wave] = (uint32_t)__popcll(mb);
+    // narrow forms: the lane's record is final (ent_first is not part of the rule) -- wide lanes are ranked inside the wave by
+    // ballot, the wave's count rides in the upper half of its wave_bad word (a wave has 64 lanes: either count fits 16 bits)
+    bool wide = false;
+    uint32_t wide_at = 0;
+    if constexpr (NARROW != 0) {
+      wide = live && packed_is_wide<NARROW>(m, pk);
+      const uint64_t wb = __ballot(wide);
+      wide_at = (uint32_t)__popcll(wb & ((1ull << (tid & 63)) - 1));
+      if ((tid & 63) == 0) wave_bad[wave] = (uint32_t)__popcll(mb) | ((uint32_t)__popcll(wb) << 16);
+    } else {
+      if ((tid & 63) == 0) wave_bad[wave] = (uint32_t)__popcll(mb);
+    }
     uint64_t tile_ents;
     const uint64_t local = block_exclusive_u32<W>(cnt, wave_tot, &tile_ents);  // (its barrier publishes wave_bad too)
     if (tid == 0) {
       uint32_t tile_bad = 0;
-      for (int k = 0; k < W; ++k) tile_bad += wave_bad[k];
+      for (int k = 0; k < W; ++k) tile_bad += NARROW != 0 ? wave_bad[k] & 0xffffu : wave_bad[k];
       const uint64_t pe = lb_exclusive(ctl.status[0], ctl.epoch, cur, tile_ents, stuck);
       const uint64_t pb = lb_exclusive(ctl.status[1], ctl.epoch, cur, tile_bad, stuck);
       prefix[0] = pe;
+      if constexpr (NARROW != 0) {
+        uint32_t tw = 0;
+        for (int k = 0; k < W; ++k) tw += wave_bad[k] >> 16;
+        const uint64_t pw = lb_exclusive(ctl.status[2], ctl.epoch, cur, tw, stuck);
+        offs[0] = pw;  // (the tile's boundaries have been in registers since the stage: no LDS is added for the narrow forms)
+        if (cur == n_tiles - 1) pin[2] = pw + tw;
+      }
       if (cur == n_tiles - 1) {
         pin[0] = pe + tile_ents;
         pin[1] = pb + tile_bad;
@@ -1097,7 +1191,18 @@ static __global__ __launch_bounds__(TB) void wire_dec_fused_kernel(InFeed in, ui
       for (uint32_t k = 0; k < kEntQ; ++k)
         if (k < cnt) ent_run[local + k] = my_ents[k];
     }
-    tile_records_out<WireMsg, TB>(m, live, reinterpret_cast<u32x4*>(file), msgs_h, tile0, n, msgs_d);  // (its barrier publishes ent_run too)
+    if constexpr (NARROW != 0) {
+      uint32_t tile_wide = 0;
+      for (uint32_t k = 0; k < (uint32_t)W; ++k) {
+        const uint32_t c = wave_bad[k] >> 16;
+        wide_at += k < wave ? c : 0;
+        tile_wide += c;
+      }
+      tile_packed_out<NARROW, TB>(m, live, wide, wide_at, tile_wide, offs[0], reinterpret_cast<uint8_t*>(file), reinterpret_cast<uint8_t*>(msgs_h), pk,
+                                  tile0, n, msgs_d);  // (its barrier publishes ent_run too)
+    } else {
+      tile_records_out<WireMsg, TB>(m, live, reinterpret_cast<u32x4*>(file), msgs_h, tile0, n, msgs_d);  // (its barrier publishes ent_run too)
+    }
     if (ents_h != nullptr && tile_ents != 0) {
       const uint64_t run0 = prefix[0];
       if (run_staged) {

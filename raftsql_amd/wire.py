@@ -33,6 +33,14 @@ WAL_REC_DT = np.dtype([("group", "<u8"), ("term", "<u8"), ("index", "<u8"), ("da
                        ("vote", "<u4"), ("crc", "<u4"), ("kind", "u1"), ("entry_type", "u1"), ("flags", "u1"),
                        ("_pad", "u1")])
 assert WIRE_MSG_DT.itemsize == 64 and WIRE_ENT_DT.itemsize == 32 and WAL_REC_DT.itemsize == 48
+# the decoder's narrow output forms (raftq_wire_decode_packed / raftq_step_frames_packed)
+F_WIDE = 0x08  # narrow record only: the frame's full record is in wide[]
+FORM_40, FORM_HEAD = 40, 8
+WIRE_HEAD_DT = np.dtype([("group", "<u4"), ("from", "u1"), ("type", "u1"), ("reject", "u1"), ("flags", "u1")])  # == raftq_wire_head_t
+WIRE_MSG40_DT = np.dtype(WIRE_HEAD_DT.descr + [("term", "<u8"), ("index", "<u8"), ("aux", "<u8"), ("commit", "<u8")])  # == raftq_wire_msg40_t
+assert WIRE_MSG40_DT.itemsize == 40 and WIRE_HEAD_DT.itemsize == 8
+_FORM_DT = {FORM_40: WIRE_MSG40_DT, FORM_HEAD: WIRE_HEAD_DT}
+MSG_APP_RESP = 4
 OUTF_ANSWERED = 0x10  # result flag of raftq_step_frames_respond: the messages the result calls for were built on the device
 RESPOND_FRAME_MAX = 83  # bytes of the largest payload-free frame: cap >= n * (N - 1) * RESPOND_FRAME_MAX
 
@@ -58,6 +66,33 @@ def scan_frames(buf, big_endian: bool, cap: int | None = None):
     if rc != 0:
         raise _lib.RaftqError(rc, (lib.raftq_last_error(None) or b"?").decode())
     return off[: n.value + 1].copy(), int(used.value)
+
+
+def expand_packed(narrow: np.ndarray, wide: np.ndarray, to_slot: int, form: int) -> np.ndarray:
+    """The 64-byte records raftq_wire_decode would have written, from the narrow array and wide[] (raftq_wire.h "Expansion is
+    exact").  FORM_HEAD: a narrow frame's term / index / log_term / commit / reject_hint were not delivered and come out 0."""
+    nar = np.asarray(narrow)
+    assert nar.dtype == _FORM_DT[form] and np.asarray(wide).dtype == WIRE_MSG_DT
+    out = np.zeros(len(nar), WIRE_MSG_DT)
+    is_wide = (nar["flags"] & F_WIDE) != 0
+    k = np.cumsum(is_wide) - 1  # wide[] is in frame order
+    if form == FORM_40:
+        assert np.array_equal(nar["aux"][is_wide], k[is_wide].astype(np.uint64)), "aux of a wide frame is its position in wide[]"
+    assert int(is_wide.sum()) <= len(wide), "wide[] is shorter than the narrow array says"
+    out[is_wide] = wide[k[is_wide]]
+    plain = ~is_wide & ((nar["flags"] & F_MALFORMED) == 0)
+    for f in ("group", "type", "reject"):
+        out[f][plain] = nar[f][plain]
+    out["from"][plain] = np.where(nar["from"][plain] == 0xFF, 0xFFFFFFFF, nar["from"][plain].astype(np.uint32))
+    out["to"][plain] = to_slot
+    if form == FORM_40:
+        for f in ("term", "index", "commit"):
+            out[f][plain] = nar[f][plain]
+        resp = plain & (nar["type"] == MSG_APP_RESP)
+        out["reject_hint"][resp] = nar["aux"][resp]
+        out["log_term"][plain & ~resp] = nar["aux"][plain & ~resp]
+    out["flags"][~is_wide] = nar["flags"][~is_wide]  # (a malformed frame: every other field 0)
+    return out
 
 
 class WireEngine(NodeEngine):
@@ -114,6 +149,27 @@ class WireEngine(NodeEngine):
             self._chk(rc)
             return msgs, ents[: int(c.n_ents)].copy(), int(c.n_malformed)
 
+    def wire_decode_packed(self, stream: np.ndarray, frame_off: np.ndarray, form: int, to_slot: int, narrow: np.ndarray, wide: np.ndarray | None,
+                           ents: np.ndarray | None = None, head_types: int = 0, check: bool = True):
+        """raftq_wire_decode_packed: every array page-locked (engine.pinned_empty / pinned_copy); narrow: WIRE_MSG40_DT / WIRE_HEAD_DT
+        [>= n]; wide: WIRE_MSG_DT [wide_cap] or None.  -> (narrow[:n], wide[:min(n_wide, cap)], ents, counts, n_wide, rc);
+        check=False: a refusal is returned as rc instead of raised"""
+        n = len(frame_off) - 1
+        assert stream.dtype == np.uint8 and frame_off.dtype == np.uint64 and len(narrow) >= n
+        assert form not in _FORM_DT or narrow.dtype == _FORM_DT[form]
+        assert wide is None or wide.dtype == WIRE_MSG_DT
+        c, nw = _lib.WireCounts(), C.c_uint64(0)
+        cap = len(wide) if wide is not None else 0
+        rc = self._lib.raftq_wire_decode_packed(self._h, stream.ctypes.data if len(stream) else None, len(stream), frame_off.ctypes.data, n, int(form),
+                                                int(head_types), int(to_slot), narrow.ctypes.data, wide.ctypes.data if wide is not None else None, cap,
+                                                ents.ctypes.data if ents is not None else None, len(ents) if ents is not None else 0, C.byref(c),
+                                                C.byref(nw))
+        if check:
+            self._chk(rc)
+        got_ents = ents[: min(int(c.n_ents), len(ents))] if ents is not None else np.zeros(0, WIRE_ENT_DT)
+        got_wide = wide[: min(int(nw.value), cap)] if wide is not None else np.zeros(0, WIRE_MSG_DT)
+        return narrow[:n], got_wide, got_ents, c, int(nw.value), rc
+
     # -- Step from the wire -------------------------------------------------------------------
     def step_submit_wire(self, stream, frame_off) -> None:
         s = _u8(stream)
@@ -141,6 +197,30 @@ class WireEngine(NodeEngine):
             outs = outs.copy()
         got_ents = ents[: min(int(c.n_ents), len(ents))] if ents is not None else np.zeros(0, WIRE_ENT_DT)
         return msgs[:n], got_ents, outs, c
+
+    def step_frames_packed(self, stream: np.ndarray, frame_off: np.ndarray, form: int, narrow: np.ndarray, wide: np.ndarray | None,
+                           ents: np.ndarray | None = None, head_types: int = 0, tail_appends: bool = True, copy: bool = True):
+        """raftq_step_frames_packed: step_frames with narrow records (to_slot = the handle's own slot).
+        -> (narrow[:n], wide[:min(n_wide, cap)], ents, outs, counts, n_wide)"""
+        n = len(frame_off) - 1
+        assert stream.dtype == np.uint8 and frame_off.dtype == np.uint64 and len(narrow) >= n
+        assert form not in _FORM_DT or narrow.dtype == _FORM_DT[form]
+        assert wide is None or wide.dtype == WIRE_MSG_DT
+        c, nw = _lib.WireCounts(), C.c_uint64(0)
+        cap = len(wide) if wide is not None else 0
+        self._chk(self._lib.raftq_step_frames_packed(self._h, stream.ctypes.data if len(stream) else None, len(stream), frame_off.ctypes.data, n,
+                                                     1 if tail_appends else 0, int(form), int(head_types), narrow.ctypes.data,
+                                                     wide.ctypes.data if wide is not None else None, cap, ents.ctypes.data if ents is not None else None,
+                                                     len(ents) if ents is not None else 0, C.byref(c), C.byref(nw)))
+        p, k = C.c_void_p(None), C.c_uint64(0)
+        dt, fn = self._results_form()
+        self._chk(fn(self._h, C.byref(p), C.byref(k)))
+        outs = np.frombuffer((C.c_char * (k.value * dt.itemsize)).from_address(p.value), dtype=dt, count=k.value) if k.value else np.zeros(0, dt)
+        if copy:
+            outs = outs.copy()
+        got_ents = ents[: min(int(c.n_ents), len(ents))] if ents is not None else np.zeros(0, WIRE_ENT_DT)
+        got_wide = wide[: min(int(nw.value), cap)] if wide is not None else np.zeros(0, WIRE_MSG_DT)
+        return narrow[:n], got_wide, got_ents, outs, c, int(nw.value)
 
     def respond_cap(self, n: int) -> int:
         """the `out` size raftq_step_frames_respond needs for n frames (the exact worst case)"""
