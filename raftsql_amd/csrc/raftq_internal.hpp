@@ -189,10 +189,10 @@ struct raftq {
   // wire / WAL codecs (raftq_wire.hip): growable device scratch (inputs + temporaries), device
   // output buffer, a small pinned block for totals / flags
   void* wire_dev = nullptr;
-  size_t wire_dev_bytes = 0;
+  uint64_t wire_dev_bytes = 0;
   void* wire_out = nullptr;
-  size_t wire_out_bytes = 0;
-  uint64_t* wire_pin = nullptr;    // pinned, 256 bytes
+  uint64_t wire_out_bytes = 0;
+  uint64_t* wire_pin = nullptr;    // pinned, 256 bytes: four result words behind each of kPinCall / kPinWalPending / kPinRespond (raftq_wire.hip)
   uint64_t* wire_pin_d = nullptr;  // the same block as the device addresses it (the codecs' last kernel writes totals / flags there)
   unsigned long long* wire_flags = nullptr;  // device, 64 bytes, zero between calls: the codecs' malformed counters / bad flags
   // the streaming codec kernels (raftq_wire_kernels.hpp "the streaming form"): ticket word + per-tile look-back status
@@ -205,11 +205,11 @@ struct raftq {
   // raftq_step_frames_respond: the walk's response records + the layout's counts (device), and what the walk reads while the
   // call is on (resp_on): the call's stamp, the caller's at-tail bitmap as the device addresses it
   void* resp_dev = nullptr;
-  size_t resp_dev_bytes = 0;
+  uint64_t resp_dev_bytes = 0;
   bool resp_on = false;
   uint32_t resp_stamp = 0;
   const uint64_t* resp_at_tail_d = nullptr;
-  // raftq_wal_encode_begin .. _end: enqueued, its totals in wire_pin[8 ..]; `done`: a later wait has covered it and what _end
+  // raftq_wal_encode_begin .. _end: enqueued, its totals in wire_pin[kPinWalPending ..]; `done`: a later wait has covered it and what _end
   // will report is kept here
   bool wal_pending = false, wal_pending_done = false;
   bool wal_pending_waited = false;  // a wait on the handle's stream has come back since the begin: its kernel has run

@@ -11,7 +11,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <vector>
 
 #include "raftq_internal.hpp"
 #include "raftq_propose_kernels.hpp"
@@ -30,6 +29,20 @@ namespace {
 
 constexpr uint64_t kMaxItems = 0x7ffffffeull;  // batch positions travel as 31-bit values
 
+// The pinned result block (h->wire_pin, 32 words; h->wire_pin_d as the device addresses it).  Up to three users have results in
+// it at a time, each four words behind its base; a kernel is handed wire_pin_d + base and knows the words as pin[0 .. 3].
+enum : uint32_t {
+  kPinCall = 0,        // the call that is waiting (raftq_step_frames_respond: its decoder)
+  kPinWalPending = 8,  // a raftq_wal_encode_begin whose _end has not come: the call enqueued behind it uses the words at kPinCall
+  kPinRespond = 16,    // raftq_step_frames_respond's encoder
+};
+enum : uint32_t {
+  kPinTotal = 0,    // bytes written (encoders), entry headers found (raftq_wire_decode*), valid records (raftq_wal_decode)
+  kPinRefused = 1,  // records refused (encoders), malformed frames (raftq_wire_decode*); raftq_wal_decode: the running CRC
+  kPinThird = 2,    // the chain's last CRC (WAL encoders), wide records (the narrow decode forms)
+  kPinGaveUp = 3,   // streaming kernels only: a look-back waited a second and gave up (tile_ctl_check)
+};
+
 size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
 struct Carver {
@@ -41,7 +54,22 @@ struct Carver {
   }
 };
 
-int grow(raftq_t* h, void** buf, size_t* have, size_t want) {
+constexpr uint64_t kLbHead = 4;  // words in front of the look-back block's status arrays
+
+// How a device buffer of the handle grows.  Capacity is counted in the buffer's own units: bytes, or status words per array of
+// the look-back block.
+struct GrowRule {
+  uint64_t least;     // smallest capacity ever allocated
+  size_t unit, head;  // bytes = head + capacity * unit
+  bool zero;          // a fresh buffer is zeroed (on the stream)
+};
+constexpr GrowRule kGrowBytes{(uint64_t)1 << 20, 1, 0, false};
+constexpr GrowRule kGrowBytesZeroed{(uint64_t)1 << 20, 1, 0, true};
+constexpr GrowRule kGrowLookBack{4096, kLbArrays * 8, kLbHead * 8, true};
+
+// *buf holds at least `want` units.  A buffer that is too small is freed after a stream synchronisation (kernels of earlier
+// calls may still use it) and replaced by one half as large again; its contents are not kept.
+int grow(raftq_t* h, void** buf, uint64_t* have, uint64_t want, const GrowRule& rule = kGrowBytes) {
   if (want <= *have) return RAFTQ_OK;
   if (*buf) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -49,9 +77,11 @@ int grow(raftq_t* h, void** buf, size_t* have, size_t want) {
     *buf = nullptr;
     *have = 0;
   }
-  const size_t bytes = std::max(want + want / 2, (size_t)1 << 20);
+  const uint64_t cap = std::max(want + want / 2, rule.least);
+  const size_t bytes = rule.head + cap * rule.unit;
   HIPCHK(h, hipMalloc(buf, bytes));
-  *have = bytes;
+  if (rule.zero) HIPCHK(h, hipMemsetAsync(*buf, 0, bytes, h->stream));
+  *have = cap;
   return RAFTQ_OK;
 }
 
@@ -75,14 +105,26 @@ void* dev_view(const void* p) {
   return d;
 }
 
-// totals / flags of the call -> wire_pin[0], wire_pin[1] (read after the next hipStreamSynchronize)
-int tail_to_pin(raftq_t* h, const uint64_t* total, unsigned long long* flag) {
-  hipLaunchKernelGGL(wire_tail_kernel, dim3(1), dim3(64), 0, h->stream, total, flag, h->wire_pin_d);
-  HIPCHK(h, hipGetLastError());
-  return RAFTQ_OK;
-}
+// The caller's arrays as the device addresses them, and whether the streaming form can take them: `ok` stays true while every
+// array asked for is page-locked, mapped and 16-byte aligned (the kernels move whole 16-byte quads -- raftq_wire.h "odd
+// alignment").  `pre`: the call's own conditions (its size limits, RAFTQ_WIRE_STREAMING); nothing is looked up once ok is false.
+struct Views {
+  bool ok;
+  explicit Views(bool pre = true) : ok(pre) {}
+  // an array the call reads or writes; used == false: the call does not touch it (an empty input, an output nobody wants)
+  void* add(const void* p, bool used = true) {
+    if (!used || !ok) return nullptr;
+    void* v = dev_view(p);
+    ok = v != nullptr && ((uintptr_t)v & 15) == 0;
+    return v;
+  }
+  void* opt(const void* p) { return add(p, p != nullptr); }  // an array the caller may leave out
+};
 
 unsigned blocks_for(uint64_t lanes) { return (unsigned)((lanes + kBlock - 1) / kBlock); }
+
+// the stream's length as the boundaries give it
+uint64_t span_of(const uint64_t* frame_off, uint64_t n) { return frame_off[n] >= frame_off[0] ? frame_off[n] - frame_off[0] : 0; }
 
 // ---- the streaming form (one persistent kernel per call; raftq_wire_kernels.hpp) -----------------------------------
 bool streaming_on() {  // RAFTQ_WIRE_STREAMING=0: the copying form even for page-locked buffers (for A/B and the tests)
@@ -99,7 +141,6 @@ unsigned fused_grid(uint32_t n_tiles) {
 // frames per tile = threads per workgroup of the streaming decoder (raftq_wire_kernels.hpp wire_dec_fused_kernel)
 constexpr unsigned kDecTile = 256;
 
-constexpr uint64_t kLbHead = 4;  // words in front of the status arrays
 // reader workgroups of a streaming kernel (RAFTQ_WIRE_READERS overrides): 48 pull a caller's array at 55 GB/s, more are slower
 // RAFTQ_WIRE_READERS=0: NO reader workgroups -- every chunk is brought in by a worker that found nobody else doing it (the
 // liveness argument's limit case, tests/test_wire_gpu.py::test_streaming_codecs_without_readers).
@@ -113,69 +154,30 @@ unsigned fused_readers(uint32_t chunks) {
 // bytes of all arrays together that a reader brings in before it raises a flag
 constexpr uint64_t kFeedChunk = 8192;
 
-// The readers' plan for up to three caller arrays (device views `src`, all 16-byte aligned): where they go in the scratch
-// (carved behind `c`), how many chunks, how many bytes of every array per chunk.  max_chunks: flags available.
-struct FeedPlan {
-  InFeed in;
-  size_t off[3];
+// One launch of a streaming kernel: what the caller asks for, and what stream_prepare answers.
+struct StreamCall {
+  // -- the request --
+  uint32_t n_tiles = 0;
+  struct Seg {
+    const void* src;  // the caller's array as the device addresses it (16-byte aligned), or nullptr
+    uint64_t bytes;   // ... and its size: what the readers bring into the scratch
+    uint64_t extra;   // bytes that follow it in the scratch: records a kernel of the call writes there itself
+  } seg[3] = {};
+  size_t carve[2] = {0, 0};  // further scratch of the call's kernels, n_carves pieces
+  int n_carves = 0;
+  uint64_t out_bytes = 0;  // what h->wire_out has to hold (0: the kernel does not use it)
+  // -- the answer --
+  InFeed in{};
+  TileCtl ctl;
+  unsigned workers = 0;
+  dim3 grid;           // readers + workers
+  uint8_t* carved[2];  // the pieces asked for
+  size_t off[5];       // (where the segments and the pieces lie in h->wire_dev)
 };
-// extra[k]: bytes of array k that follow, in the scratch, what the readers bring (records a kernel writes there itself)
-FeedPlan plan_feed(Carver& c, const void* const src[3], const uint64_t bytes[3], uint64_t max_chunks, const uint64_t* extra = nullptr) {
-  FeedPlan p{};
-  uint64_t total = 0;
-  for (int k = 0; k < 3; ++k) total += bytes[k];
-  const uint64_t chunks = std::max<uint64_t>(1, std::min<uint64_t>(max_chunks, (total + kFeedChunk - 1) / kFeedChunk));
-  for (int k = 0; k < 3; ++k) {
-    p.off[k] = c.take(bytes[k] + (extra ? extra[k] : 0));
-    p.in.seg[k].src = (const uint8_t*)src[k];
-    p.in.seg[k].bytes = bytes[k];
-    p.in.seg[k].per_chunk = std::max<uint64_t>(256, ((bytes[k] + chunks - 1) / chunks + 255) / 256 * 256);
-  }
-  p.in.chunks = (uint32_t)chunks;
-  p.in.readers = fused_readers(p.in.chunks);
-  return p;
-}
-// (called once per launch, after tile_ctl: the chunk tickets of the launch are accounted for in tile_ctl_launched)
-// The chunk ticket is monotonic across calls: a launch with reader workgroups draws exactly chunks + readers tickets whoever
-// copies what (a worker that serves itself claims by compare-and-swap and never draws past the end; the readers draw the rest
-// and one beyond each), so the next call's base is known without asking the device.  A launch with NO readers (RAFTQ_WIRE_READERS=0)
-// only claims the chunks somebody waited for -- a chunk past every array's end, or one that holds bytes no tile
-// names, stays unclaimed -- so its count is not known: the ticket word is zeroed in front of such a launch and in front of the
-// first launch after one (a 4-byte memset in the stream: test and A/B shapes only).
-int bind_feed(raftq_t* h, FeedPlan& p, uint8_t* base, unsigned long long* flags) {
-  for (int k = 0; k < 3; ++k) p.in.seg[k].dst = base + p.off[k];
-  p.in.flag = flags;
-  p.in.chunk_ticket = reinterpret_cast<unsigned int*>(h->wire_lb + 3);  // the head's fourth word
-  if (p.in.readers == 0 || h->wire_chunk_unknown) {
-    HIPCHK(h, hipMemsetAsync(p.in.chunk_ticket, 0, 4, h->stream));
-    h->wire_chunk_base = 0;
-    h->wire_chunk_unknown = p.in.readers == 0;
-  }
-  p.in.chunk_base = h->wire_chunk_base;
-  h->wire_chunk_pending = p.in.readers ? p.in.chunks + p.in.readers : 0;  // every reader workgroup draws exactly one ticket beyond the chunks
-  return RAFTQ_OK;
-}
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-// ticket word + status arrays for a call of n_tiles tiles; a new call is a new epoch (the words of older calls read as
-// "not published yet"), the arrays are zeroed when they are (re)allocated and when the 16-bit epoch wraps
-int tile_ctl(raftq_t* h, uint64_t n_tiles, TileCtl* ctl) {
-  if (n_tiles > h->wire_lb_tiles) {
-    if (h->wire_lb) {
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      HIPCHK(h, hipFree(h->wire_lb));
-      h->wire_lb = nullptr;
-      h->wire_lb_tiles = 0;
-    }
-    const uint64_t tiles = std::max<uint64_t>(n_tiles + n_tiles / 2, 4096);
-    HIPCHK(h, hipMalloc((void**)&h->wire_lb, (kLbHead + kLbArrays * tiles) * 8));
-    HIPCHK(h, hipMemsetAsync(h->wire_lb, 0, (kLbHead + kLbArrays * tiles) * 8, h->stream));
-    h->wire_lb_tiles = tiles;
-    h->wire_ticket_base = 0;
-    h->wire_chunk_base = 0;
-    h->wire_chunk_unknown = false;
-    h->wire_epoch = 0;
-  }
+// ticket word + status arrays for one launch: a new launch is a new epoch (the words of older ones read as "not published
+// yet"); the arrays are zeroed again when the 16-bit epoch wraps
+int tile_ctl(raftq_t* h, TileCtl* ctl) {
   if (++h->wire_epoch > 0xffffu) {
     HIPCHK(h, hipMemsetAsync(h->wire_lb + kLbHead, 0, kLbArrays * h->wire_lb_tiles * 8, h->stream));
     h->wire_epoch = 1;
@@ -192,11 +194,96 @@ void tile_ctl_launched(raftq_t* h, uint32_t n_tiles, unsigned workers) {
   h->wire_chunk_base += h->wire_chunk_pending;
   h->wire_chunk_pending = 0;
 }
-// after the call's wait: did a look-back give up (wire_pin[3], copied from the control block by the last tile)?
-int tile_ctl_check(raftq_t* h, const char* who, uint32_t pin_base = 0) {
-  if (h->wire_pin[pin_base + 3] == 0) return RAFTQ_OK;
+// after the call's wait: did a look-back give up (kPinGaveUp, copied from the control block by the last tile)?
+int tile_ctl_check(raftq_t* h, const char* who, uint32_t pin_base) {
+  if (h->wire_pin[pin_base + kPinGaveUp] == 0) return RAFTQ_OK;
   h->wire_lb_tiles = 0;  // the control block is not trusted any more: the next call allocates a fresh one
   return fail(h, RAFTQ_EHIP, std::string(who) + ": a workgroup waited a second for its predecessor's tile and gave up; the results are not valid");
+}
+
+// The readers' plan for the call's arrays: how many chunks (at most max_chunks, the flags available), how many bytes of every
+// array per chunk.
+void plan_feed(StreamCall& sc, uint64_t max_chunks) {
+  uint64_t total = 0;
+  for (int k = 0; k < 3; ++k) total += sc.seg[k].bytes;
+  const uint64_t chunks = std::max<uint64_t>(1, std::min<uint64_t>(max_chunks, (total + kFeedChunk - 1) / kFeedChunk));
+  for (int k = 0; k < 3; ++k) {
+    sc.in.seg[k].src = (const uint8_t*)sc.seg[k].src;
+    sc.in.seg[k].bytes = sc.seg[k].bytes;
+    sc.in.seg[k].per_chunk = std::max<uint64_t>(256, ((sc.seg[k].bytes + chunks - 1) / chunks + 255) / 256 * 256);
+  }
+  sc.in.chunks = (uint32_t)chunks;
+  sc.in.readers = fused_readers(sc.in.chunks);
+}
+// The chunk ticket is monotonic across calls: a launch with reader workgroups draws exactly chunks + readers tickets whoever
+// copies what (a worker that serves itself claims by compare-and-swap and never draws past the end; the readers draw the rest
+// and one beyond each), so the next call's base is known without asking the device.  A launch with NO readers (RAFTQ_WIRE_READERS=0)
+// only claims the chunks somebody waited for -- a chunk past every array's end, or one that holds bytes no tile
+// names, stays unclaimed -- so its count is not known: the ticket word is zeroed in front of such a launch and in front of the
+// first launch after one (a 4-byte memset in the stream: test and A/B shapes only).
+int bind_feed(raftq_t* h, StreamCall& sc) {
+  for (int k = 0; k < 3; ++k) sc.in.seg[k].dst = (uint8_t*)h->wire_dev + sc.off[k];
+  sc.in.flag = sc.ctl.status[kLbFlags];
+  sc.in.chunk_ticket = reinterpret_cast<unsigned int*>(h->wire_lb + 3);  // the head's fourth word
+  if (sc.in.readers == 0 || h->wire_chunk_unknown) {
+    HIPCHK(h, hipMemsetAsync(sc.in.chunk_ticket, 0, 4, h->stream));
+    h->wire_chunk_base = 0;
+    h->wire_chunk_unknown = sc.in.readers == 0;
+  }
+  sc.in.chunk_base = h->wire_chunk_base;
+  h->wire_chunk_pending = sc.in.readers ? sc.in.chunks + sc.in.readers : 0;  // every reader workgroup draws exactly one ticket beyond the chunks
+  return RAFTQ_OK;
+}
+
+// The launch sequence of every streaming call: stream_prepare, the call's own kernels, stream_launch.  Its order is a protocol:
+//   1. the control block is sized first (a status word per tile and a flag per kFeedChunk of input): plan_feed takes its
+//      number of chunks from h->wire_lb_tiles;
+//   2. the scratch is carved -- the segments with their extras, the call's own pieces behind them -- and, with the output
+//      buffer, grown: that may move either, so nothing holds an address into them before;
+//   3. only then is the launch's epoch drawn and the feed bound to the scratch (tile_ctl, bind_feed);
+//   4. the launch is accounted for exactly once, with its own tile and worker counts (tile_ctl_launched): the tile and chunk
+//      tickets are monotonic across calls, and a launch counted wrongly derails every later call on the handle.
+// stream_reserve is steps 1 and 2 alone: after it, a stream_prepare of the same request (or a smaller one) allocates nothing.
+int stream_reserve(raftq_t* h, StreamCall& sc) {
+  uint64_t total = 0;
+  for (int k = 0; k < 3; ++k) total += sc.seg[k].bytes;
+  const uint64_t n_status = std::max<uint64_t>(sc.n_tiles, total / kFeedChunk + 1);
+  if (n_status > h->wire_lb_tiles) {  // a fresh control block is all zero: tickets and epochs start over
+    if (int rc = grow(h, (void**)&h->wire_lb, &h->wire_lb_tiles, n_status, kGrowLookBack)) return rc;
+    h->wire_ticket_base = h->wire_chunk_base = h->wire_epoch = 0;
+    h->wire_chunk_unknown = false;
+  }
+  Carver c;
+  for (int k = 0; k < 3; ++k) sc.off[k] = c.take(sc.seg[k].bytes + sc.seg[k].extra);
+  for (int k = 0; k < sc.n_carves; ++k) sc.off[3 + k] = c.take(sc.carve[k]);
+  if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, c.off)) return rc;
+  return grow(h, &h->wire_out, &h->wire_out_bytes, sc.out_bytes);
+}
+int stream_prepare(raftq_t* h, StreamCall& sc) {
+  if (int rc = stream_reserve(h, sc)) return rc;
+  if (int rc = tile_ctl(h, &sc.ctl)) return rc;
+  plan_feed(sc, h->wire_lb_tiles);
+  if (int rc = bind_feed(h, sc)) return rc;
+  for (int k = 0; k < sc.n_carves; ++k) sc.carved[k] = (uint8_t*)h->wire_dev + sc.off[3 + k];
+  sc.workers = fused_grid(sc.n_tiles);
+  sc.grid = dim3(sc.in.readers + sc.workers);
+  return RAFTQ_OK;
+}
+// the streaming kernel itself, enqueued on the handle's stream behind whatever the call launched in front of it
+template <class Kernel, class... Args>
+int stream_launch(raftq_t* h, const StreamCall& sc, Kernel kernel, unsigned block, Args... args) {
+  hipLaunchKernelGGL(kernel, sc.grid, dim3(block), 0, h->stream, args...);
+  HIPCHK(h, hipGetLastError());
+  tile_ctl_launched(h, sc.n_tiles, sc.workers);
+  return RAFTQ_OK;
+}
+
+// ---- the copying form (pageable caller memory: the runtime's copies, a chain of plain kernels) -------------------------
+// totals / flags of the call -> wire_pin[kPinTotal], [kPinRefused] (read after the next hipStreamSynchronize)
+int tail_to_pin(raftq_t* h, const uint64_t* total, unsigned long long* flag) {
+  hipLaunchKernelGGL(wire_tail_kernel, dim3(1), dim3(64), 0, h->stream, total, flag, h->wire_pin_d + kPinCall);
+  HIPCHK(h, hipGetLastError());
+  return RAFTQ_OK;
 }
 
 // chain[i] = pair[0] . pair[1] . ... . pair[i]; tot: scratch for ceil(n / kBlock) pairs
@@ -218,6 +305,160 @@ int d2h(raftq_t* h, void* dst, const void* src, size_t bytes) {
   return RAFTQ_OK;
 }
 
+// ---- raftq_wire_encode ------------------------------------------------------------------------------------------------
+// What either form of an encoder learns once the sizes are known: a refusal (`state`: what that means for out), the size for the
+// caller, out too small.  who: raftq_wire_encode, or a WAL encoder with its own `what`.
+template <class Counts>
+int encode_sized(raftq_t* h, const char* who, const char* what, const char* state, uint64_t total, uint64_t refused, uint64_t cap, Counts* counts,
+                 const Counts& sized) {
+  if (refused) return fail(h, RAFTQ_EINVAL, std::string(who) + what + state);
+  if (counts) *counts = sized;
+  if (total > cap) return fail(h, RAFTQ_EINVAL, std::string(who) + ": out is too small (counts->bytes is the size needed)");
+  return RAFTQ_OK;
+}
+constexpr const char* kWireEncRefused = ": a message has to / from >= 255, an entry range outside ents[], or a payload outside the pool; ";
+constexpr const char* kWalEncRefused = ": a record has an unknown kind or a payload outside the pool; ";
+
+// page-locked caller buffers (v_*: as the device addresses them): readers | workers in one launch (raftq_wire_kernels.hpp)
+int wire_encode_streaming(raftq_t* h, const void* v_msgs, uint64_t n, const void* v_ents, uint64_t n_ents, const void* v_pool, uint64_t pool_bytes,
+                          void* v_out, uint64_t cap, void* v_off, raftq_wire_counts_t* counts) {
+  StreamCall sc;
+  sc.n_tiles = blocks_for(n);
+  sc.seg[0] = {v_msgs, n * sizeof(WireMsg), 0};
+  sc.seg[1] = {v_ents, n_ents * sizeof(WireEnt), 0};
+  sc.seg[2] = {v_pool, pool_bytes, 0};
+  sc.out_bytes = cap + 16;
+  if (int rc = stream_prepare(h, sc)) return rc;
+  if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, n, n_ents, pool_bytes, (uint8_t*)h->wire_out, (uint8_t*)v_out, cap,
+                             (uint64_t*)v_off, sc.ctl, h->wire_pin_d + kPinCall, (const unsigned int*)nullptr, 0u))
+    return rc;
+  HIPCHK(h, raftq_detail::wait_call(h));
+  if (int rc = tile_ctl_check(h, "raftq_wire_encode", kPinCall)) return rc;
+  const uint64_t total = h->wire_pin[kPinCall + kPinTotal];
+  return encode_sized(h, "raftq_wire_encode", kWireEncRefused, "the output is not valid", total, h->wire_pin[kPinCall + kPinRefused], cap, counts,
+                      raftq_wire_counts_t{n, n_ents, 0, total});
+}
+
+// the runtime's copies, a wait in the middle to learn the size
+int wire_encode_copying(raftq_t* h, const raftq_wire_msg_t* msgs, uint64_t n, const raftq_wire_ent_t* ents, uint64_t n_ents, const void* pool,
+                        uint64_t pool_bytes, void* out, uint64_t cap, uint64_t* frame_off, raftq_wire_counts_t* counts) {
+  const size_t scan_bytes = scan_sum_scratch_bytes(n + 1);  // tile totals of the hand-written scan
+  Carver c;
+  const size_t o_msgs = c.take(n * sizeof(WireMsg)), o_ents = c.take(n_ents * sizeof(WireEnt)),
+               o_pool = c.take(pool_bytes), o_sizes = c.take((n + 1) * 8), o_off = c.take((n + 1) * 8), o_scan = c.take(scan_bytes);
+  if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, c.off)) return rc;
+  uint8_t* base = (uint8_t*)h->wire_dev;
+  WireMsg* d_msgs = (WireMsg*)(base + o_msgs);
+  WireEnt* d_ents = (WireEnt*)(base + o_ents);
+  uint8_t* d_pool = base + o_pool;
+  uint64_t *d_sizes = (uint64_t*)(base + o_sizes), *d_off = (uint64_t*)(base + o_off);
+  unsigned int* d_bad = (unsigned int*)(h->wire_flags + 0);
+  if (int rc = h2d(h, d_msgs, msgs, n * sizeof(WireMsg))) return rc;
+  if (int rc = h2d(h, d_ents, ents, n_ents * sizeof(WireEnt))) return rc;
+  if (int rc = h2d(h, d_pool, pool, pool_bytes)) return rc;
+  hipLaunchKernelGGL(wire_enc_size_kernel, dim3(blocks_for(n + 1)), dim3(kBlock), 0, h->stream, (const WireMsg*)d_msgs, n,
+                     (const WireEnt*)d_ents, n_ents, pool_bytes, d_sizes, d_bad);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, exclusive_sum_u64((const uint64_t*)d_sizes, d_off, n + 1, (uint64_t*)(base + o_scan), h->stream));
+  if (int rc = tail_to_pin(h, d_off + n, h->wire_flags + 0)) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  const uint64_t total = h->wire_pin[kPinCall + kPinTotal];
+  if (int rc = encode_sized(h, "raftq_wire_encode", kWireEncRefused, "nothing was written", total, (uint32_t)h->wire_pin[kPinCall + kPinRefused], cap,
+                            counts, raftq_wire_counts_t{n, n_ents, 0, total}))
+    return rc;
+  if (int rc = grow(h, &h->wire_out, &h->wire_out_bytes, total + 16)) return rc;
+  uint8_t* d_out = (uint8_t*)h->wire_out;
+  hipLaunchKernelGGL(wire_enc_write_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, h->stream, (const WireMsg*)d_msgs, n,
+                     (const WireEnt*)d_ents, (const uint64_t*)d_off, d_out);
+  if (n_ents)
+    hipLaunchKernelGGL(wire_enc_payload_kernel, dim3(blocks_for(n * 64)), dim3(kBlock), 0, h->stream,
+                       (const WireMsg*)d_msgs, n, (const WireEnt*)d_ents, (const uint64_t*)d_off,
+                       (const uint8_t*)d_pool, d_out);
+  HIPCHK(h, hipGetLastError());
+  if (int rc = d2h(h, out, d_out, total)) return rc;
+  if (frame_off)
+    if (int rc = d2h(h, frame_off, d_off, (n + 1) * 8)) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return RAFTQ_OK;
+}
+
+// ---- raftq_wire_decode, raftq_wire_decode_packed, raftq_step_frames' decoder ------------------------------------------------
+// The streaming decode (raftq_wire_kernels.hpp "the streaming form"), enqueued on the handle's stream and NOT waited for;
+// v_*: the caller's arrays as the device addresses them.  msgs_d / ff: see wire_dec_fused_kernel (raftq_step_frames).
+// form: 0 -- v_msgs receives 64-byte records; RAFTQ_WIRE_FORM_40 / _HEAD -- v_msgs is the narrow array, pk the wide one.
+int decode_streaming_enqueue(raftq_t* h, const void* v_stream, uint64_t nbytes, const void* v_off, uint64_t n, void* v_msgs, void* v_ents,
+                             uint64_t ents_cap, WireMsg* msgs_d, FrameFilter ff, int form = 0, PackedOut pk = PackedOut{nullptr, 0, 0, 0}) {
+  // (the default of 208 workers, one per CU beside the readers as in round 5 -- at 68 KB two fit, but 464 workers measured SLOWER
+  // than 208 (173.9 against 167.6 us a call, profiles/r06/wire_tile_ab.jsonl): with 256 tiles in a 64K-frame call every tile has
+  // its own waiting worker at 208 already, and twice the workgroups are twice the pollers of the chunk flags)
+  StreamCall sc;
+  sc.n_tiles = (uint32_t)((n + kDecTile - 1) / kDecTile);
+  sc.seg[0] = {v_off, (n + 1) * 8, 0};
+  sc.seg[1] = {v_stream, nbytes, 0};
+  sc.carve[0] = (size_t)sc.n_tiles * kDecTile * kEntQ * sizeof(WireEnt);  // a slot of kEntQ entry headers per lane
+  sc.n_carves = 1;
+  if (int rc = stream_prepare(h, sc)) return rc;
+  const auto kernel = form == RAFTQ_WIRE_FORM_40     ? wire_dec_fused_kernel<kDecTile, RAFTQ_WIRE_FORM_40>
+                      : form == RAFTQ_WIRE_FORM_HEAD ? wire_dec_fused_kernel<kDecTile, RAFTQ_WIRE_FORM_HEAD>
+                                                     : wire_dec_fused_kernel<kDecTile, 0>;
+  return stream_launch(h, sc, kernel, kDecTile, sc.in, nbytes, n, (WireMsg*)v_msgs, (WireEnt*)v_ents, ents_cap, sc.ctl, h->wire_pin_d + kPinCall, msgs_d, ff,
+                       (WireEnt*)sc.carved[0], pk);
+}
+// What either form of a decode reports once its totals are in the pinned words.  too_many_is_error: raftq_wire_decode's
+// contract; raftq_step_frames only reports the count.
+int decode_counted(raftq_t* h, const char* who, const uint64_t* frame_off, uint64_t n, bool have_ents, uint64_t ents_cap, bool too_many_is_error,
+                   raftq_wire_counts_t* counts) {
+  const uint64_t total = h->wire_pin[kPinCall + kPinTotal];
+  if (counts) *counts = raftq_wire_counts_t{n, total, h->wire_pin[kPinCall + kPinRefused], span_of(frame_off, n)};
+  if (too_many_is_error && have_ents && total > ents_cap)
+    return fail(h, RAFTQ_EINVAL, std::string(who) + ": more entries than ents_cap (counts->n_ents is the number needed)");
+  return RAFTQ_OK;
+}
+// ... the streaming form, after the wait that covers it
+int decode_streaming_finish(raftq_t* h, const char* who, const uint64_t* frame_off, uint64_t n, bool have_ents, uint64_t ents_cap,
+                            bool too_many_is_error, raftq_wire_counts_t* counts) {
+  if (int rc = tile_ctl_check(h, who, kPinCall)) return rc;
+  return decode_counted(h, who, frame_off, n, have_ents, ents_cap, too_many_is_error, counts);
+}
+
+int wire_decode_copying(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off, uint64_t n, raftq_wire_msg_t* msgs,
+                        raftq_wire_ent_t* ents, uint64_t ents_cap, raftq_wire_counts_t* counts) {
+  // an entry costs its message at least two bytes (tag, length), so this many can never be exceeded
+  const uint64_t dev_cap = std::min<uint64_t>(ents_cap, nbytes / 2 + 1);
+  const size_t scan_bytes = scan_sum_scratch_bytes(n + 1);  // tile totals of the hand-written scan
+  Carver c;
+  const size_t o_stream = c.take(nbytes), o_off = c.take((n + 1) * 8), o_msgs = c.take(n * sizeof(WireMsg)),
+               o_cnt = c.take((n + 1) * 8), o_base = c.take((n + 1) * 8), o_scan = c.take(scan_bytes);
+  if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, c.off)) return rc;
+  if (int rc = grow(h, &h->wire_out, &h->wire_out_bytes, dev_cap * sizeof(WireEnt) + 16)) return rc;
+  uint8_t* base = (uint8_t*)h->wire_dev;
+  uint8_t* d_stream = base + o_stream;
+  uint64_t *d_off = (uint64_t*)(base + o_off), *d_cnt = (uint64_t*)(base + o_cnt), *d_base = (uint64_t*)(base + o_base);
+  WireMsg* d_msgs = (WireMsg*)(base + o_msgs);
+  WireEnt* d_ents = (WireEnt*)h->wire_out;
+  unsigned long long* d_bad = h->wire_flags + 1;
+  if (int rc = h2d(h, d_stream, stream, nbytes)) return rc;
+  if (int rc = h2d(h, d_off, frame_off, (n + 1) * 8)) return rc;
+  hipLaunchKernelGGL(wire_dec_kernel, dim3(blocks_for(n + 1)), dim3(kBlock), 0, h->stream, (const uint8_t*)d_stream,
+                     nbytes, (const uint64_t*)d_off, n, d_msgs, d_cnt, d_bad);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, exclusive_sum_u64((const uint64_t*)d_cnt, d_base, n + 1, (uint64_t*)(base + o_scan), h->stream));
+  hipLaunchKernelGGL(wire_dec_ents_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, h->stream, (const uint8_t*)d_stream,
+                     nbytes, (const uint64_t*)d_off, n, d_msgs, (const uint64_t*)d_base, dev_cap ? d_ents : (WireEnt*)nullptr,
+                     dev_cap);
+  HIPCHK(h, hipGetLastError());
+  if (int rc = tail_to_pin(h, d_base + n, d_bad)) return rc;
+  if (int rc = d2h(h, msgs, d_msgs, n * sizeof(WireMsg))) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (int rc = decode_counted(h, "raftq_wire_decode", frame_off, n, ents != nullptr, ents_cap, true, counts)) return rc;
+  const uint64_t total = h->wire_pin[kPinCall + kPinTotal];
+  if (ents && total) {
+    if (int rc = d2h(h, ents, d_ents, total * sizeof(WireEnt))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  return RAFTQ_OK;
+}
+
 }  // namespace
 
 void raftq_detail::free_wire_state(raftq_t* h) {
@@ -236,6 +477,7 @@ void raftq_detail::free_wire_state(raftq_t* h) {
   h->wire_pin = nullptr;
 }
 
+// ---- raftpb.Message stream frames: the entry points ---------------------------------------------------------------------------
 extern "C" {
 
 int raftq_wire_scan_frames(const void* buf, uint64_t nbytes, int big_endian, uint64_t* off, uint64_t cap,
@@ -271,90 +513,10 @@ int raftq_wire_encode(raftq_t* h, const raftq_wire_msg_t* msgs, uint64_t n, cons
   if (n > kMaxItems || n_ents > kMaxItems) return fail(h, RAFTQ_EINVAL, "raftq_wire_encode: batch too large");
   if (int rc = ensure_pin(h)) return rc;
   // page-locked caller buffers (what a node passes every turn) take the streaming form; anything else the copying form
-  void *v_msgs = nullptr, *v_ents = nullptr, *v_pool = nullptr, *v_out = nullptr, *v_off = nullptr;
-  const bool mapped = streaming_on() && cap != 0 && cap <= ((uint64_t)1 << 31) && (v_msgs = dev_view(msgs)) != nullptr &&
-                      (n_ents == 0 || (v_ents = dev_view(ents)) != nullptr) && (pool_bytes == 0 || (v_pool = dev_view(pool)) != nullptr) &&
-                      (v_out = dev_view(out)) != nullptr && (!frame_off || (v_off = dev_view(frame_off)) != nullptr);
-  if (mapped && aligned16(v_msgs) && aligned16(v_ents) && aligned16(v_pool) && aligned16(v_out) && aligned16(v_off)) {
-    // page-locked caller buffers: the streaming form (readers | workers in one launch; raftq_wire_kernels.hpp)
-    const uint32_t n_tiles = blocks_for(n);
-    const unsigned workers = fused_grid(n_tiles);
-    Carver fc;
-    const void* const src[3] = {v_msgs, v_ents, v_pool};
-    const uint64_t sizes[3] = {n * sizeof(WireMsg), n_ents * sizeof(WireEnt), pool_bytes};
-    TileCtl ctl;
-    if (int rc = tile_ctl(h, std::max<uint64_t>(n_tiles, (sizes[0] + sizes[1] + sizes[2]) / kFeedChunk + 1), &ctl)) return rc;
-    FeedPlan plan = plan_feed(fc, src, sizes, h->wire_lb_tiles);
-    if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, fc.off)) return rc;
-    if (int rc = grow(h, &h->wire_out, &h->wire_out_bytes, cap + 16)) return rc;
-    if (int rc = bind_feed(h, plan, (uint8_t*)h->wire_dev, ctl.status[kLbFlags])) return rc;
-    hipLaunchKernelGGL(wire_enc_fused_kernel, dim3(plan.in.readers + workers), dim3(kBlock), 0, h->stream, plan.in, n, n_ents, pool_bytes,
-                       (uint8_t*)h->wire_out, (uint8_t*)v_out, cap, (uint64_t*)v_off, ctl, h->wire_pin_d, (const unsigned int*)nullptr, 0u);
-    HIPCHK(h, hipGetLastError());
-    tile_ctl_launched(h, n_tiles, workers);
-    HIPCHK(h, raftq_detail::wait_call(h));
-    if (int rc = tile_ctl_check(h, "raftq_wire_encode")) return rc;
-    const uint64_t total = h->wire_pin[0];
-    if (h->wire_pin[1])
-      return fail(h, RAFTQ_EINVAL,
-                  "raftq_wire_encode: a message has to / from >= 255, an entry range outside ents[], or a payload outside "
-                  "the pool; the output is not valid");
-    if (counts) {
-      counts->n_msgs = n;
-      counts->n_ents = n_ents;
-      counts->bytes = total;
-    }
-    if (total > cap) return fail(h, RAFTQ_EINVAL, "raftq_wire_encode: out is too small (counts->bytes is the size needed)");
-    return RAFTQ_OK;
-  }
-  // the copying form: the runtime's copies, a wait in the middle to learn the size
-  const size_t scan_bytes = scan_sum_scratch_bytes(n + 1);  // tile totals of the hand-written scan
-  Carver c;
-  const size_t o_msgs = c.take(n * sizeof(WireMsg)), o_ents = c.take(n_ents * sizeof(WireEnt)),
-               o_pool = c.take(pool_bytes), o_sizes = c.take((n + 1) * 8), o_off = c.take((n + 1) * 8),
-               o_bad = c.take(8), o_scan = c.take(scan_bytes);
-  if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, c.off)) return rc;
-  uint8_t* base = (uint8_t*)h->wire_dev;
-  WireMsg* d_msgs = (WireMsg*)(base + o_msgs);
-  WireEnt* d_ents = (WireEnt*)(base + o_ents);
-  uint8_t* d_pool = base + o_pool;
-  uint64_t *d_sizes = (uint64_t*)(base + o_sizes), *d_off = (uint64_t*)(base + o_off);
-  unsigned int* d_bad = (unsigned int*)(h->wire_flags + 0);  // (o_bad: unused since the flags have a block of their own)
-  (void)o_bad;
-  if (int rc = h2d(h, d_msgs, msgs, n * sizeof(WireMsg))) return rc;
-  if (int rc = h2d(h, d_ents, ents, n_ents * sizeof(WireEnt))) return rc;
-  if (int rc = h2d(h, d_pool, pool, pool_bytes)) return rc;
-  hipLaunchKernelGGL(wire_enc_size_kernel, dim3(blocks_for(n + 1)), dim3(kBlock), 0, h->stream, (const WireMsg*)d_msgs, n,
-                     (const WireEnt*)d_ents, n_ents, pool_bytes, d_sizes, d_bad);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, exclusive_sum_u64((const uint64_t*)d_sizes, d_off, n + 1, (uint64_t*)(base + o_scan), h->stream));
-  if (int rc = tail_to_pin(h, d_off + n, h->wire_flags + 0)) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  const uint64_t total = h->wire_pin[0];
-  if ((uint32_t)h->wire_pin[1])
-    return fail(h, RAFTQ_EINVAL,
-                "raftq_wire_encode: a message has to / from >= 255, an entry range outside ents[], or a payload outside "
-                "the pool; nothing was written");
-  if (counts) {
-    counts->n_msgs = n;
-    counts->n_ents = n_ents;
-    counts->bytes = total;
-  }
-  if (total > cap) return fail(h, RAFTQ_EINVAL, "raftq_wire_encode: out is too small (counts->bytes is the size needed)");
-  if (int rc = grow(h, &h->wire_out, &h->wire_out_bytes, total + 16)) return rc;
-  uint8_t* d_out = (uint8_t*)h->wire_out;
-  hipLaunchKernelGGL(wire_enc_write_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, h->stream, (const WireMsg*)d_msgs, n,
-                     (const WireEnt*)d_ents, (const uint64_t*)d_off, d_out);
-  if (n_ents)
-    hipLaunchKernelGGL(wire_enc_payload_kernel, dim3(blocks_for(n * 64)), dim3(kBlock), 0, h->stream,
-                       (const WireMsg*)d_msgs, n, (const WireEnt*)d_ents, (const uint64_t*)d_off,
-                       (const uint8_t*)d_pool, d_out);
-  HIPCHK(h, hipGetLastError());
-  if (int rc = d2h(h, out, d_out, total)) return rc;
-  if (frame_off)
-    if (int rc = d2h(h, frame_off, d_off, (n + 1) * 8)) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return RAFTQ_OK;
+  Views v(streaming_on() && cap != 0 && cap <= ((uint64_t)1 << 31));
+  void *v_msgs = v.add(msgs), *v_ents = v.add(ents, n_ents != 0), *v_pool = v.add(pool, pool_bytes != 0), *v_out = v.add(out), *v_off = v.opt(frame_off);
+  if (v.ok) return wire_encode_streaming(h, v_msgs, n, v_ents, n_ents, v_pool, pool_bytes, v_out, cap, v_off, counts);
+  return wire_encode_copying(h, msgs, n, ents, n_ents, pool, pool_bytes, out, cap, frame_off, counts);
 }
 
 int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props, const raftq_prop_ent_t* prop_ents, uint64_t n_prop_ents,
@@ -371,52 +533,48 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
   const uint64_t n_dev = n_props * (h->N - 1), n = n_msgs + n_dev, n_e = n_ents + n_prop_ents;
   if (n > kMaxItems || n_e > kMaxItems) return fail(h, RAFTQ_EINVAL, "raftq_propose_frames: batch too large");
   if (int rc = ensure_pin(h)) return rc;
-  void *v_props = dev_view(props), *v_pe = dev_view(prop_ents), *v_msgs = n_msgs ? dev_view(msgs) : nullptr, *v_ents = n_ents ? dev_view(ents) : nullptr,
-       *v_pool = pool_bytes ? dev_view(pool) : nullptr, *v_out = dev_view(out), *v_off = frame_off ? dev_view(frame_off) : nullptr;
-  const bool mapped = v_props && v_pe && (!n_msgs || v_msgs) && (!n_ents || v_ents) && (!pool_bytes || v_pool) && v_out && (!frame_off || v_off) &&
-                      cap <= ((uint64_t)1 << 31);
-  if (!(mapped && aligned16(v_props) && aligned16(v_pe) && aligned16(v_msgs) && aligned16(v_ents) && aligned16(v_pool) && aligned16(v_out) && aligned16(v_off)))
+  Views v(cap <= ((uint64_t)1 << 31));
+  void *v_props = v.add(props), *v_pe = v.add(prop_ents), *v_msgs = v.add(msgs, n_msgs != 0), *v_ents = v.add(ents, n_ents != 0),
+       *v_pool = v.add(pool, pool_bytes != 0), *v_out = v.add(out), *v_off = v.opt(frame_off);
+  if (!v.ok)
     return fail(h, RAFTQ_EINVAL, "raftq_propose_frames: every array must be page-locked (raftq_host_alloc, hipHostMalloc, hipHostRegister) and "
                                  "16-byte aligned -- append with raftq_apply_log_deltas and marshal with raftq_wire_encode otherwise");
   NodeArrays na;
   if (int rc = raftq_detail::node_arrays_of(h, &na)) return rc;
-  const uint32_t n_tiles = blocks_for(n);
-  const unsigned workers = fused_grid(n_tiles);
-  Carver fc;
-  const void* const src[3] = {v_msgs, v_ents, v_pool};
-  const uint64_t sizes[3] = {n_msgs * sizeof(WireMsg), n_ents * sizeof(WireEnt), pool_bytes};
-  const uint64_t extra[3] = {n_dev * sizeof(WireMsg), n_prop_ents * sizeof(WireEnt), 0};
-  TileCtl ctl;
-  if (int rc = tile_ctl(h, std::max<uint64_t>(n_tiles, (sizes[0] + sizes[1] + sizes[2]) / kFeedChunk + 1), &ctl)) return rc;
-  FeedPlan plan = plan_feed(fc, src, sizes, h->wire_lb_tiles, extra);
-  const size_t o_props = fc.take(n_props * sizeof(PropRec)), o_pe = fc.take(n_prop_ents * sizeof(PropEnt));  // the check kernel's copies of the records
-  if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, fc.off)) return rc;
-  if (int rc = grow(h, &h->wire_out, &h->wire_out_bytes, cap + 16)) return rc;
-  if (int rc = bind_feed(h, plan, (uint8_t*)h->wire_dev, ctl.status[kLbFlags])) return rc;
+  const uint64_t msgs_bytes = n_msgs * sizeof(WireMsg), ents_bytes = n_ents * sizeof(WireEnt);
+  StreamCall sc;
+  sc.n_tiles = blocks_for(n);
+  sc.seg[0] = {v_msgs, msgs_bytes, n_dev * sizeof(WireMsg)};
+  sc.seg[1] = {v_ents, ents_bytes, n_prop_ents * sizeof(WireEnt)};
+  sc.seg[2] = {v_pool, pool_bytes, 0};
+  sc.carve[0] = n_props * sizeof(PropRec);  // the check kernel's copies of the records
+  sc.carve[1] = n_prop_ents * sizeof(PropEnt);
+  sc.n_carves = 2;
+  sc.out_bytes = cap + 16;
+  if (int rc = stream_prepare(h, sc)) return rc;
   // appendEntry + bcastAppend on the device, INTO the encoder's input (the scratch behind what its readers bring) ...
   // the validation's verdict: a word that holds THIS call's stamp when a record was refused (no memset in the chain: a stamp
   // of an earlier call reads as "fine")
   unsigned int* bad = (unsigned int*)(h->wire_flags + 2);
   if (++h->prop_stamp == 0) h->prop_stamp = 1;
   const unsigned int stamp = h->prop_stamp;
-  WireMsg* msgs_dev = (WireMsg*)(plan.in.seg[0].dst + sizes[0]);
-  WireEnt* ents_dev = (WireEnt*)(plan.in.seg[1].dst + sizes[1]);
+  WireMsg* msgs_dev = (WireMsg*)(sc.in.seg[0].dst + msgs_bytes);
+  WireEnt* ents_dev = (WireEnt*)(sc.in.seg[1].dst + ents_bytes);
   const dim3 pg((unsigned)((n_props + kBlock - 1) / kBlock)), cg((unsigned)((std::max(n_props, n_prop_ents) + kBlock - 1) / kBlock));
-  PropRec* props_d = (PropRec*)((uint8_t*)h->wire_dev + o_props);
-  PropEnt* pe_d = (PropEnt*)((uint8_t*)h->wire_dev + o_pe);
+  PropRec* props_d = (PropRec*)sc.carved[0];
+  PropEnt* pe_d = (PropEnt*)sc.carved[1];
   hipLaunchKernelGGL(propose_check_kernel, cg, dim3(kBlock), 0, h->stream, na, (const PropRec*)v_props, n_props, (const PropEnt*)v_pe, n_prop_ents, pool_bytes, bad,
                      stamp, props_d, pe_d, h->wire_flags + 3);
   hipLaunchKernelGGL(propose_apply_kernel, pg, dim3(kBlock), 0, h->stream, na, (const PropRec*)props_d, n_props, (const PropEnt*)pe_d,
                      (const unsigned int*)bad, stamp, msgs_dev, ents_dev, (uint32_t)n_ents);
   // ... and the marshal of everything right behind it: one wait
-  hipLaunchKernelGGL(wire_enc_fused_kernel, dim3(plan.in.readers + workers), dim3(kBlock), 0, h->stream, plan.in, n, n_e, pool_bytes, (uint8_t*)h->wire_out,
-                     (uint8_t*)v_out, cap, (uint64_t*)v_off, ctl, h->wire_pin_d, (const unsigned int*)bad, stamp);
-  HIPCHK(h, hipGetLastError());
-  tile_ctl_launched(h, n_tiles, workers);
+  if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, n, n_e, pool_bytes, (uint8_t*)h->wire_out, (uint8_t*)v_out, cap, (uint64_t*)v_off,
+                             sc.ctl, h->wire_pin_d + kPinCall, (const unsigned int*)bad, stamp))
+    return rc;
   HIPCHK(h, raftq_detail::wait_call(h));
-  if (int rc = tile_ctl_check(h, "raftq_propose_frames")) return rc;
-  const uint64_t total = h->wire_pin[0];
-  if (h->wire_pin[1]) {
+  if (int rc = tile_ctl_check(h, "raftq_propose_frames", kPinCall)) return rc;
+  const uint64_t total = h->wire_pin[kPinCall + kPinTotal];
+  if (h->wire_pin[kPinCall + kPinRefused]) {
     // which record, and why (the check kernel left the largest (stamp, reason, record) it met; an older call's stamp: the marshal refused)
     unsigned long long why = 0;
     (void)hipMemcpy(&why, h->wire_flags + 3, 8, hipMemcpyDeviceToHost);
@@ -428,77 +586,75 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
     return fail(h, RAFTQ_EINVAL, "raftq_propose_frames: a queued message has to / from >= 255, an entry range outside ents[] or a payload outside the pool; the "
                                  "proposals WERE appended, the output is not valid");
   }
-  if (counts) {
-    counts->n_msgs = n;
-    counts->n_ents = n_e;
-    counts->bytes = total;
-  }
+  if (counts) *counts = raftq_wire_counts_t{n, n_e, 0, total};
   if (total > cap) return fail(h, RAFTQ_EINVAL, "raftq_propose_frames: out is too small (counts->bytes is the size needed); the proposals WERE appended");
   return RAFTQ_OK;
 }
 
-// The streaming decode (raftq_wire_kernels.hpp "the streaming form"), enqueued on the handle's stream and NOT waited for;
-// v_*: the caller's arrays as the device addresses them.  msgs_d / ff: see wire_dec_fused_kernel (raftq_step_frames).
-// form: 0 -- v_msgs receives 64-byte records; RAFTQ_WIRE_FORM_40 / _HEAD -- v_msgs is the narrow array, pk the wide one.
-static int decode_streaming_enqueue(raftq_t* h, const void* v_stream, uint64_t nbytes, const void* v_off, uint64_t n, void* v_msgs, void* v_ents,
-                                    uint64_t ents_cap, WireMsg* msgs_d, FrameFilter ff, int form = 0, PackedOut pk = PackedOut{nullptr, 0, 0, 0}) {
-  const uint32_t n_tiles = (uint32_t)((n + kDecTile - 1) / kDecTile);
-  // 208 workers, one per CU beside the readers as in round 5 -- at 68 KB two fit, but 464 workers measured SLOWER than 208 (173.9
-  // against 167.6 us a call, profiles/r06/wire_tile_ab.jsonl): with 256 tiles in a 64K-frame call every tile has its own waiting
-  // worker at 208 already, and twice the workgroups are twice the pollers of the chunk flags
-  const unsigned workers = fused_grid(n_tiles);
-  Carver c;
-  const void* const src[3] = {v_off, v_stream, nullptr};
-  const uint64_t bytes[3] = {(n + 1) * 8, nbytes, 0};
-  TileCtl ctl;
-  if (int rc = tile_ctl(h, std::max<uint64_t>(n_tiles, (bytes[0] + bytes[1]) / kFeedChunk + 1), &ctl)) return rc;
-  FeedPlan plan = plan_feed(c, src, bytes, h->wire_lb_tiles);
-  const size_t o_spill = c.take((size_t)n_tiles * kDecTile * kEntQ * sizeof(WireEnt));  // a slot of kEntQ entry headers per lane
-  if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, c.off)) return rc;
-  if (int rc = bind_feed(h, plan, (uint8_t*)h->wire_dev, ctl.status[kLbFlags])) return rc;
-  WireEnt* spill = (WireEnt*)((uint8_t*)h->wire_dev + o_spill);
-  const dim3 grid(plan.in.readers + workers);
-  if (form == RAFTQ_WIRE_FORM_40)
-    hipLaunchKernelGGL((wire_dec_fused_kernel<kDecTile, RAFTQ_WIRE_FORM_40>), grid, dim3(kDecTile), 0, h->stream, plan.in, nbytes, n, (WireMsg*)v_msgs,
-                       (WireEnt*)v_ents, ents_cap, ctl, h->wire_pin_d, msgs_d, ff, spill, pk);
-  else if (form == RAFTQ_WIRE_FORM_HEAD)
-    hipLaunchKernelGGL((wire_dec_fused_kernel<kDecTile, RAFTQ_WIRE_FORM_HEAD>), grid, dim3(kDecTile), 0, h->stream, plan.in, nbytes, n, (WireMsg*)v_msgs,
-                       (WireEnt*)v_ents, ents_cap, ctl, h->wire_pin_d, msgs_d, ff, spill, pk);
-  else
-    hipLaunchKernelGGL((wire_dec_fused_kernel<kDecTile, 0>), grid, dim3(kDecTile), 0, h->stream, plan.in, nbytes, n, (WireMsg*)v_msgs,
-                       (WireEnt*)v_ents, ents_cap, ctl, h->wire_pin_d, msgs_d, ff, spill, pk);
-  HIPCHK(h, hipGetLastError());
-  tile_ctl_launched(h, n_tiles, workers);
-  return RAFTQ_OK;
+int raftq_wire_decode(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off, uint64_t n,
+                      raftq_wire_msg_t* msgs, raftq_wire_ent_t* ents, uint64_t ents_cap, raftq_wire_counts_t* counts) {
+  if (int rc = use_device(h)) return rc;
+  if (counts) *counts = raftq_wire_counts_t{0, 0, 0, 0};
+  if (n == 0) return RAFTQ_OK;
+  if ((!stream && nbytes) || !frame_off || !msgs) return fail(h, RAFTQ_EINVAL, "raftq_wire_decode: null argument");
+  if (n > kMaxItems) return fail(h, RAFTQ_EINVAL, "raftq_wire_decode: batch too large");
+  if (!ents) ents_cap = 0;
+  if (int rc = ensure_pin(h)) return rc;
+  // page-locked caller buffers: ONE kernel -- readers bring boundaries and stream into the scratch in order, workers parse
+  // tile by tile behind them and push records and entry headers out (raftq_wire_kernels.hpp "the streaming form")
+  Views v(streaming_on() && nbytes < (1ull << (kLbValueBits - 1)));
+  void *v_stream = v.add(stream, nbytes != 0), *v_off = v.add(frame_off), *v_msgs = v.add(msgs), *v_ents = v.opt(ents);
+  if (!v.ok) return wire_decode_copying(h, stream, nbytes, frame_off, n, msgs, ents, ents_cap, counts);
+  if (int rc = decode_streaming_enqueue(h, v_stream, nbytes, v_off, n, v_msgs, v_ents, ents_cap, nullptr, FrameFilter{0, 0, 0, 0, 0, nullptr})) return rc;
+  HIPCHK(h, raftq_detail::wait_call(h));
+  return decode_streaming_finish(h, "raftq_wire_decode", frame_off, n, ents != nullptr, ents_cap, true, counts);
 }
-// ... after the wait that covers it.  too_many_is_error: raftq_wire_decode's contract; raftq_step_frames only reports the count.
-static int decode_streaming_finish(raftq_t* h, const char* who, const uint64_t* frame_off, uint64_t n, bool have_ents, uint64_t ents_cap,
-                                   bool too_many_is_error, raftq_wire_counts_t* counts) {
-  if (int rc = tile_ctl_check(h, who)) return rc;
-  const uint64_t total = h->wire_pin[0];
-  if (counts) {
-    counts->n_msgs = n;
-    counts->n_ents = total;
-    counts->n_malformed = h->wire_pin[1];
-    counts->bytes = frame_off[n] >= frame_off[0] ? frame_off[n] - frame_off[0] : 0;
-  }
-  if (too_many_is_error && have_ents && total > ents_cap)
-    return fail(h, RAFTQ_EINVAL, std::string(who) + ": more entries than ents_cap (counts->n_ents is the number needed)");
+
+int raftq_wire_decode_packed(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off, uint64_t n, int form, uint32_t head_types,
+                             uint32_t to_slot, void* narrow, raftq_wire_msg_t* wide, uint64_t wide_cap, raftq_wire_ent_t* ents, uint64_t ents_cap,
+                             raftq_wire_counts_t* counts, uint64_t* n_wide) {
+  const char* who = "raftq_wire_decode_packed";
+  if (int rc = raftq_detail::use_device_idle(h, who)) return rc;  // (kPinThird and the scratch are a Step batch's while one is in flight)
+  if (counts) *counts = raftq_wire_counts_t{0, 0, 0, 0};
+  if (n_wide) *n_wide = 0;
+  if (form != RAFTQ_WIRE_FORM_40 && form != RAFTQ_WIRE_FORM_HEAD) return fail(h, RAFTQ_EINVAL, std::string(who) + ": form is neither RAFTQ_WIRE_FORM_40 nor RAFTQ_WIRE_FORM_HEAD");
+  if (to_slot >= 255) return fail(h, RAFTQ_EINVAL, std::string(who) + ": to_slot must be a peer slot (< 255)");
+  if (n == 0) return RAFTQ_OK;
+  if ((!stream && nbytes) || !frame_off || !narrow || (wide_cap && !wide)) return fail(h, RAFTQ_EINVAL, std::string(who) + ": null argument");
+  if (n > kMaxItems) return fail(h, RAFTQ_EINVAL, std::string(who) + ": batch too large");
+  if (!ents) ents_cap = 0;
+  if (int rc = ensure_pin(h)) return rc;
+  Views v(nbytes < (1ull << (kLbValueBits - 1)));
+  void *v_stream = v.add(stream, nbytes != 0), *v_off = v.add(frame_off), *v_narrow = v.add(narrow), *v_wide = v.add(wide, wide_cap != 0),
+       *v_ents = v.opt(ents);
+  if (!v.ok)
+    return fail(h, RAFTQ_EINVAL, std::string(who) + ": every array must be page-locked (raftq_host_alloc, hipHostMalloc, hipHostRegister) and "
+                                                    "16-byte aligned -- the narrow forms exist in the streaming form only");
+  if (int rc = decode_streaming_enqueue(h, v_stream, nbytes, v_off, n, v_narrow, v_ents, ents_cap, nullptr, FrameFilter{0, 0, 0, 0, 0, nullptr}, form,
+                                        PackedOut{(WireMsg*)v_wide, wide_cap, head_types, to_slot}))
+    return rc;
+  HIPCHK(h, raftq_detail::wait_call(h));
+  const int rc = decode_streaming_finish(h, who, frame_off, n, ents != nullptr, ents_cap, true, counts);
+  if (rc == RAFTQ_EHIP) return rc;  // a look-back gave up: no total is to be trusted
+  const uint64_t total_wide = h->wire_pin[kPinCall + kPinThird];
+  if (n_wide) *n_wide = total_wide;
+  if (rc != RAFTQ_OK) return rc;
+  if (total_wide > wide_cap) return fail(h, RAFTQ_EINVAL, std::string(who) + ": more wide frames than wide_cap (*n_wide is the number needed)");
   return RAFTQ_OK;
 }
 
 }  // extern "C"
+
+// ---- raftq_step_frames*: the decoder in front of Step (raftq_step.hip) --------------------------------------------------------
 int raftq_detail::wire_frames_enqueue(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off, uint64_t n, void* msgs, void* ents,
                                       uint64_t ents_cap, void* msgs_d, int tail_appends, void* zero2, const PackedDst* packed) {
   if (n > kMaxItems) return fail(h, RAFTQ_EINVAL, "raftq_step_frames: batch too large");
   if (int rc = ensure_pin(h)) return rc;
-  void *v_stream = nullptr, *v_off = nullptr, *v_msgs = nullptr, *v_ents = nullptr, *v_wide = nullptr;
   const bool wide = packed && packed->wide_cap != 0;
-  const bool mapped = (nbytes == 0 || (v_stream = dev_view(stream)) != nullptr) && (v_off = dev_view(frame_off)) != nullptr &&
-                      (v_msgs = dev_view(msgs)) != nullptr && (!ents || (v_ents = dev_view(ents)) != nullptr) &&
-                      (!wide || (v_wide = dev_view(packed->wide)) != nullptr);
-  if (!(mapped && nbytes < (1ull << (kLbValueBits - 1)) && aligned16(v_stream) && aligned16(v_off) && aligned16(v_msgs) && aligned16(v_ents) &&
-        aligned16(v_wide)))
+  Views v(nbytes < (1ull << (kLbValueBits - 1)));
+  void *v_stream = v.add(stream, nbytes != 0), *v_off = v.add(frame_off), *v_msgs = v.add(msgs), *v_ents = v.opt(ents),
+       *v_wide = v.add(wide ? packed->wide : nullptr, wide);
+  if (!v.ok)
     return fail(h, RAFTQ_EINVAL, "raftq_step_frames: the stream, the boundaries and the result arrays must be page-locked (raftq_host_alloc, "
                                  "hipHostMalloc, hipHostRegister) and 16-byte aligned -- decode and step in two calls otherwise");
   const FrameFilter ff{1u, h->N, h->self_peer, tail_appends ? 1u : 0u, h->G, (unsigned long long*)zero2};
@@ -507,10 +663,14 @@ int raftq_detail::wire_frames_enqueue(raftq_t* h, const void* stream, uint64_t n
                                     PackedOut{(WireMsg*)v_wide, wide ? packed->wide_cap : 0, packed->head_types, h->self_peer});
   return decode_streaming_enqueue(h, v_stream, nbytes, v_off, n, v_msgs, v_ents, ents ? ents_cap : 0, (WireMsg*)msgs_d, ff);
 }
-uint64_t raftq_detail::wire_frames_n_wide(raftq_t* h) { return h->wire_pin[2]; }
+uint64_t raftq_detail::wire_frames_n_wide(raftq_t* h) { return h->wire_pin[kPinCall + kPinThird]; }
+
+int raftq_detail::wire_frames_finish(raftq_t* h, const uint64_t* frame_off, uint64_t n, bool have_ents, uint64_t ents_cap, raftq_wire_counts_t* counts) {
+  return decode_streaming_finish(h, "raftq_step_frames", frame_off, n, have_ents, ents_cap, false, counts);
+}
+
 // ---- raftq_step_frames_respond ----------------------------------------------------------------------------------------
 namespace {
-constexpr uint32_t kRespPin = 16;  // the encoder's totals go to wire_pin[16 ..]: [0 .. 3] are the decoder's, [8 ..] a pending WAL encode's
 struct RespScratch {
   size_t o_blk_cnt, o_blk_off, o_peer_off, bytes;
 };
@@ -523,6 +683,15 @@ RespScratch resp_scratch(uint64_t n) {
   r.bytes = r.o_peer_off + 256;
   return r;
 }
+// the marshal of the responses: the records go where the encoder's readers would have put a caller's messages -- the scratch
+// behind an empty feed
+StreamCall resp_marshal_call(const raftq_detail::RespPlan& p) {
+  StreamCall sc;
+  sc.n_tiles = blocks_for(p.n_max);
+  sc.seg[0] = {nullptr, 0, p.n_max * sizeof(WireMsg)};
+  sc.out_bytes = p.cap + 16;
+  return sc;
+}
 }  // namespace
 
 int raftq_detail::respond_prepare(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off, const void* msgs, const void* ents,
@@ -531,45 +700,22 @@ int raftq_detail::respond_prepare(raftq_t* h, const void* stream, uint64_t nbyte
   if (n > kMaxItems) return fail(h, RAFTQ_EINVAL, std::string(who) + ": batch too large");
   if (int rc = ensure_pin(h)) return rc;
   // what raftq_step_frames' decoder takes, and what this call adds: all of it checked here, before anything is enqueued
-  void *v_stream = nullptr, *v_off = nullptr, *v_msgs = nullptr, *v_ents = nullptr, *v_tail = nullptr, *v_out = nullptr, *v_roff = nullptr,
-       *v_poff = nullptr;
-  const bool mapped = (nbytes == 0 || (v_stream = dev_view(stream)) != nullptr) && (v_off = dev_view(frame_off)) != nullptr &&
-                      (v_msgs = dev_view(msgs)) != nullptr && (!ents || (v_ents = dev_view(ents)) != nullptr) &&
-                      (!at_tail || (v_tail = dev_view(at_tail)) != nullptr) && (v_out = dev_view(out)) != nullptr &&
-                      (!resp_off || (v_roff = dev_view(resp_off)) != nullptr) && (v_poff = dev_view(peer_off)) != nullptr;
-  if (!(mapped && nbytes < (1ull << (kLbValueBits - 1)) && aligned16(v_stream) && aligned16(v_off) && aligned16(v_msgs) && aligned16(v_ents) &&
-        aligned16(v_tail) && aligned16(v_out) && aligned16(v_roff) && aligned16(v_poff)))
+  Views v(nbytes < (1ull << (kLbValueBits - 1)));
+  v.add(stream, nbytes != 0), v.add(frame_off), v.add(msgs), v.opt(ents);
+  void *v_tail = v.opt(at_tail), *v_out = v.add(out), *v_roff = v.opt(resp_off);
+  v.add(peer_off);
+  if (!v.ok)
     return fail(h, RAFTQ_EINVAL, std::string(who) + ": every array must be page-locked (raftq_host_alloc, hipHostMalloc, hipHostRegister) and "
                                                     "16-byte aligned -- nothing was applied");
-  const RespScratch rs = resp_scratch(n);
-  if (rs.bytes > h->resp_dev_bytes) {
-    if (h->resp_dev) {
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      HIPCHK(h, hipFree(h->resp_dev));
-      h->resp_dev = nullptr;
-      h->resp_dev_bytes = 0;
-    }
-    const size_t bytes = std::max(rs.bytes + rs.bytes / 2, (size_t)1 << 20);
-    HIPCHK(h, hipMalloc(&h->resp_dev, bytes));
-    HIPCHK(h, hipMemsetAsync(h->resp_dev, 0, bytes, h->stream));  // stamp 0: no call's
-    h->resp_dev_bytes = bytes;
-  }
+  if (int rc = grow(h, &h->resp_dev, &h->resp_dev_bytes, resp_scratch(n).bytes, kGrowBytesZeroed)) return rc;  // (zeroed: stamp 0 is no call's)
   p->n = n;
   p->n_max = n * (h->N - 1);
   p->cap = std::min<uint64_t>(cap, p->n_max * RAFTQ_RESPOND_FRAME_MAX);  // what the encoder may write: never more than the worst case
   // everything the layout and the marshal will need is allocated NOW, before anything is stepped: a call that has stepped cannot
   // fail for memory (the calls behind the step find the control block, the scratch and the output buffer big enough)
   if (p->n_max != 0) {
-    const uint32_t n_tiles = blocks_for(p->n_max);
-    TileCtl ctl;
-    if (int rc = tile_ctl(h, n_tiles, &ctl)) return rc;
-    Carver fc;
-    const void* const src[3] = {nullptr, nullptr, nullptr};
-    const uint64_t sizes[3] = {0, 0, 0};
-    const uint64_t extra[3] = {p->n_max * sizeof(WireMsg), 0, 0};
-    (void)plan_feed(fc, src, sizes, h->wire_lb_tiles, extra);
-    if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, fc.off)) return rc;
-    if (int rc = grow(h, &h->wire_out, &h->wire_out_bytes, p->cap + 16)) return rc;
+    StreamCall sc = resp_marshal_call(*p);
+    if (int rc = stream_reserve(h, sc)) return rc;
   }
   if (++h->resp_stamp == 0) h->resp_stamp = 1;
   h->resp_at_tail_d = (const uint64_t*)v_tail;
@@ -589,238 +735,78 @@ int raftq_detail::respond_enqueue(raftq_t* h, const RespPlan& p) {
   hipLaunchKernelGGL(resp_scan_kernel, dim3(1), dim3(kBlock), 0, h->stream, L, blocks);
   HIPCHK(h, hipGetLastError());
   if (p.n_max != 0) {
-    // the records go where the encoder's readers would have put a caller's messages: the scratch behind an empty feed
-    const uint32_t n_tiles = blocks_for(p.n_max);
-    const unsigned workers = fused_grid(n_tiles);
-    Carver fc;
-    const void* const src[3] = {nullptr, nullptr, nullptr};
-    const uint64_t sizes[3] = {0, 0, 0};
-    const uint64_t extra[3] = {p.n_max * sizeof(WireMsg), 0, 0};
-    TileCtl ctl;
-    if (int rc = tile_ctl(h, n_tiles, &ctl)) return rc;
-    FeedPlan plan = plan_feed(fc, src, sizes, h->wire_lb_tiles, extra);
-    if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, fc.off)) return rc;
-    if (int rc = grow(h, &h->wire_out, &h->wire_out_bytes, p.cap + 16)) return rc;
-    if (int rc = bind_feed(h, plan, (uint8_t*)h->wire_dev, ctl.status[kLbFlags])) return rc;
-    WireMsg* enc = (WireMsg*)plan.in.seg[0].dst;
-    hipLaunchKernelGGL(resp_scatter_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, enc, p.n_max);
-    hipLaunchKernelGGL(wire_enc_fused_kernel, dim3(plan.in.readers + workers), dim3(kBlock), 0, h->stream, plan.in, p.n_max, (uint64_t)0, (uint64_t)0,
-                       (uint8_t*)h->wire_out, (uint8_t*)p.v_out, p.cap, p.v_resp_off, ctl, h->wire_pin_d + kRespPin, (const unsigned int*)nullptr, 0u);
-    HIPCHK(h, hipGetLastError());
-    tile_ctl_launched(h, n_tiles, workers);
+    StreamCall sc = resp_marshal_call(p);
+    if (int rc = stream_prepare(h, sc)) return rc;  // (allocates nothing: respond_prepare reserved this very request)
+    hipLaunchKernelGGL(resp_scatter_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, (WireMsg*)sc.in.seg[0].dst, p.n_max);
+    if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, p.n_max, (uint64_t)0, (uint64_t)0, (uint8_t*)h->wire_out, (uint8_t*)p.v_out,
+                               p.cap, p.v_resp_off, sc.ctl, h->wire_pin_d + kPinRespond, (const unsigned int*)nullptr, 0u))
+      return rc;
   }
   // the slices' bounds: a copy of the runtime's (no new kernel writes host memory)
   HIPCHK(h, hipMemcpyAsync(p.peer_off, rd + rs.o_peer_off, (size_t)(h->N + 1) * 8, hipMemcpyDeviceToHost, h->stream));
   return RAFTQ_OK;
 }
 
-int raftq_detail::respond_pass_ok(raftq_t* h) { return tile_ctl_check(h, "raftq_step_frames_respond", kRespPin); }
+int raftq_detail::respond_pass_ok(raftq_t* h) { return tile_ctl_check(h, "raftq_step_frames_respond", kPinRespond); }
 
 int raftq_detail::respond_finish(raftq_t* h, const RespPlan& p, raftq_wire_counts_t* resp_counts) {
   const uint64_t frames = p.peer_off[h->N];
   uint64_t bytes = 0;
   if (p.n_max != 0) {
-    if (int rc = tile_ctl_check(h, "raftq_step_frames_respond", kRespPin)) return rc;
-    bytes = h->wire_pin[kRespPin];
+    if (int rc = tile_ctl_check(h, "raftq_step_frames_respond", kPinRespond)) return rc;
+    bytes = h->wire_pin[kPinRespond + kPinTotal];
     // every record past the last frame is a filler the encoder refuses; any other refusal, or bytes beyond the bound, is a bug here
-    if (h->wire_pin[kRespPin + 1] != p.n_max - frames || bytes > p.cap)
+    if (h->wire_pin[kPinRespond + kPinRefused] != p.n_max - frames || bytes > p.cap)
       return fail(h, RAFTQ_EHIP, "raftq_step_frames_respond: the marshal of the responses disagrees with their layout; the output is not valid");
   }
-  if (resp_counts) {
-    resp_counts->n_msgs = frames;
-    resp_counts->n_ents = 0;
-    resp_counts->n_malformed = 0;
-    resp_counts->bytes = bytes;
-  }
+  if (resp_counts) *resp_counts = raftq_wire_counts_t{frames, 0, 0, bytes};
   return RAFTQ_OK;
 }
 
-int raftq_detail::wire_frames_finish(raftq_t* h, const uint64_t* frame_off, uint64_t n, bool have_ents, uint64_t ents_cap, raftq_wire_counts_t* counts) {
-  return decode_streaming_finish(h, "raftq_step_frames", frame_off, n, have_ents, ents_cap, false, counts);
-}
-extern "C" {
+// ---- walpb.Record WAL frames --------------------------------------------------------------------------------------------------
+namespace {
 
-int raftq_wire_decode(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off, uint64_t n,
-                      raftq_wire_msg_t* msgs, raftq_wire_ent_t* ents, uint64_t ents_cap, raftq_wire_counts_t* counts) {
-  if (int rc = use_device(h)) return rc;
-  if (counts) *counts = raftq_wire_counts_t{0, 0, 0, 0};
-  if (n == 0) return RAFTQ_OK;
-  if ((!stream && nbytes) || !frame_off || !msgs) return fail(h, RAFTQ_EINVAL, "raftq_wire_decode: null argument");
-  if (n > kMaxItems) return fail(h, RAFTQ_EINVAL, "raftq_wire_decode: batch too large");
-  if (!ents) ents_cap = 0;
-  if (int rc = ensure_pin(h)) return rc;
-  // an entry costs its message at least two bytes (tag, length), so this many can never be exceeded
-  const uint64_t dev_cap = std::min<uint64_t>(ents_cap, nbytes / 2 + 1);
-  void *v_stream = nullptr, *v_off = nullptr, *v_msgs = nullptr, *v_ents = nullptr;
-  const bool mapped = streaming_on() && (nbytes == 0 || (v_stream = dev_view(stream)) != nullptr) && (v_off = dev_view(frame_off)) != nullptr &&
-                      (v_msgs = dev_view(msgs)) != nullptr && (!ents || (v_ents = dev_view(ents)) != nullptr);
-  // (every array, inputs and outputs: the workers store whole 16-byte quads into msgs / ents -- raftq_wire.h "odd alignment")
-  if (mapped && nbytes < (1ull << (kLbValueBits - 1)) && aligned16(v_stream) && aligned16(v_off) && aligned16(v_msgs) && aligned16(v_ents)) {
-    // page-locked caller buffers: ONE kernel -- readers bring boundaries and stream into the scratch in order, workers parse
-    // tile by tile behind them and push records and entry headers out (raftq_wire_kernels.hpp "the streaming form")
-    if (int rc = decode_streaming_enqueue(h, v_stream, nbytes, v_off, n, v_msgs, v_ents, ents_cap, nullptr, FrameFilter{0, 0, 0, 0, 0, nullptr})) return rc;
-    HIPCHK(h, raftq_detail::wait_call(h));
-    return decode_streaming_finish(h, "raftq_wire_decode", frame_off, n, ents != nullptr, ents_cap, true, counts);
-  }
-  const size_t scan_bytes = scan_sum_scratch_bytes(n + 1);  // tile totals of the hand-written scan
-  Carver c;
-  const size_t o_stream = c.take(nbytes), o_off = c.take((n + 1) * 8), o_msgs = c.take(n * sizeof(WireMsg)),
-               o_cnt = c.take((n + 1) * 8), o_base = c.take((n + 1) * 8), o_bad = c.take(8), o_scan = c.take(scan_bytes);
-  if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, c.off)) return rc;
-  if (int rc = grow(h, &h->wire_out, &h->wire_out_bytes, dev_cap * sizeof(WireEnt) + 16)) return rc;
-  uint8_t* base = (uint8_t*)h->wire_dev;
-  uint8_t* d_stream = base + o_stream;
-  uint64_t *d_off = (uint64_t*)(base + o_off), *d_cnt = (uint64_t*)(base + o_cnt), *d_base = (uint64_t*)(base + o_base);
-  WireMsg* d_msgs = (WireMsg*)(base + o_msgs);
-  WireEnt* d_ents = (WireEnt*)h->wire_out;
-  unsigned long long* d_bad = h->wire_flags + 1;  // (o_bad: unused since the flags have a block of their own)
-  (void)o_bad;
-  if (int rc = h2d(h, d_stream, stream, nbytes)) return rc;
-  if (int rc = h2d(h, d_off, frame_off, (n + 1) * 8)) return rc;
-  
-  hipLaunchKernelGGL(wire_dec_kernel, dim3(blocks_for(n + 1)), dim3(kBlock), 0, h->stream, (const uint8_t*)d_stream,
-                     nbytes, (const uint64_t*)d_off, n, d_msgs, d_cnt, d_bad);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, exclusive_sum_u64((const uint64_t*)d_cnt, d_base, n + 1, (uint64_t*)(base + o_scan), h->stream));
-  hipLaunchKernelGGL(wire_dec_ents_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, h->stream, (const uint8_t*)d_stream,
-                     nbytes, (const uint64_t*)d_off, n, d_msgs, (const uint64_t*)d_base, dev_cap ? d_ents : (WireEnt*)nullptr,
-                     dev_cap);
-  HIPCHK(h, hipGetLastError());
-  if (int rc = tail_to_pin(h, d_base + n, d_bad)) return rc;
-  if (int rc = d2h(h, msgs, d_msgs, n * sizeof(WireMsg))) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  const uint64_t total = h->wire_pin[0];
-  if (counts) {
-    counts->n_msgs = n;
-    counts->n_ents = total;
-    counts->n_malformed = h->wire_pin[1];
-    counts->bytes = frame_off[n] >= frame_off[0] ? frame_off[n] - frame_off[0] : 0;
-  }
-  if (!ents) return RAFTQ_OK;  // headers only
-  if (total > ents_cap)
-    return fail(h, RAFTQ_EINVAL, "raftq_wire_decode: more entries than ents_cap (counts->n_ents is the number needed)");
-  if (total) {
-    if (int rc = d2h(h, ents, d_ents, total * sizeof(WireEnt))) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  return RAFTQ_OK;
+// The streaming WAL encode, enqueued and NOT waited for; its totals go to the pinned words behind pin_base (raftq_wal_encode:
+// kPinCall; raftq_wal_encode_begin: kPinWalPending).
+int wal_streaming_enqueue(raftq_t* h, const void* v_recs, uint64_t n, const void* v_pool, uint64_t pool_bytes, uint32_t prev_crc, void* v_out,
+                          uint64_t cap, void* v_off, uint32_t pin_base) {
+  StreamCall sc;
+  sc.n_tiles = blocks_for(n);
+  sc.seg[0] = {v_recs, n * sizeof(WalRec), 0};
+  sc.seg[1] = {v_pool, pool_bytes, 0};
+  sc.out_bytes = cap + 16;
+  if (int rc = stream_prepare(h, sc)) return rc;
+  return stream_launch(h, sc, wal_enc_fused_kernel, kBlock, sc.in, n, pool_bytes, prev_crc, (uint8_t*)h->wire_out, (uint8_t*)v_out, cap, (uint64_t*)v_off,
+                       sc.ctl, h->wire_pin_d + pin_base);
 }
-
-int raftq_wire_decode_packed(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off, uint64_t n, int form, uint32_t head_types,
-                             uint32_t to_slot, void* narrow, raftq_wire_msg_t* wide, uint64_t wide_cap, raftq_wire_ent_t* ents, uint64_t ents_cap,
-                             raftq_wire_counts_t* counts, uint64_t* n_wide) {
-  const char* who = "raftq_wire_decode_packed";
-  if (int rc = raftq_detail::use_device_idle(h, who)) return rc;  // (pin[2] and the scratch are a Step batch's while one is in flight)
-  if (counts) *counts = raftq_wire_counts_t{0, 0, 0, 0};
-  if (n_wide) *n_wide = 0;
-  if (form != RAFTQ_WIRE_FORM_40 && form != RAFTQ_WIRE_FORM_HEAD) return fail(h, RAFTQ_EINVAL, std::string(who) + ": form is neither RAFTQ_WIRE_FORM_40 nor RAFTQ_WIRE_FORM_HEAD");
-  if (to_slot >= 255) return fail(h, RAFTQ_EINVAL, std::string(who) + ": to_slot must be a peer slot (< 255)");
-  if (n == 0) return RAFTQ_OK;
-  if ((!stream && nbytes) || !frame_off || !narrow || (wide_cap && !wide)) return fail(h, RAFTQ_EINVAL, std::string(who) + ": null argument");
-  if (n > kMaxItems) return fail(h, RAFTQ_EINVAL, std::string(who) + ": batch too large");
-  if (!ents) ents_cap = 0;
-  if (int rc = ensure_pin(h)) return rc;
-  void *v_stream = nullptr, *v_off = nullptr, *v_narrow = nullptr, *v_wide = nullptr, *v_ents = nullptr;
-  const bool mapped = (nbytes == 0 || (v_stream = dev_view(stream)) != nullptr) && (v_off = dev_view(frame_off)) != nullptr &&
-                      (v_narrow = dev_view(narrow)) != nullptr && (wide_cap == 0 || (v_wide = dev_view(wide)) != nullptr) &&
-                      (!ents || (v_ents = dev_view(ents)) != nullptr);
-  if (!(mapped && nbytes < (1ull << (kLbValueBits - 1)) && aligned16(v_stream) && aligned16(v_off) && aligned16(v_narrow) && aligned16(v_wide) &&
-        aligned16(v_ents)))
-    return fail(h, RAFTQ_EINVAL, std::string(who) + ": every array must be page-locked (raftq_host_alloc, hipHostMalloc, hipHostRegister) and "
-                                                    "16-byte aligned -- the narrow forms exist in the streaming form only");
-  if (int rc = decode_streaming_enqueue(h, v_stream, nbytes, v_off, n, v_narrow, v_ents, ents_cap, nullptr, FrameFilter{0, 0, 0, 0, 0, nullptr}, form,
-                                        PackedOut{(WireMsg*)v_wide, wide_cap, head_types, to_slot}))
-    return rc;
-  HIPCHK(h, raftq_detail::wait_call(h));
-  const int rc = decode_streaming_finish(h, who, frame_off, n, ents != nullptr, ents_cap, true, counts);
-  if (rc == RAFTQ_EHIP) return rc;  // a look-back gave up: no total is to be trusted
-  const uint64_t total_wide = h->wire_pin[2];
-  if (n_wide) *n_wide = total_wide;
-  if (rc != RAFTQ_OK) return rc;
-  if (total_wide > wide_cap) return fail(h, RAFTQ_EINVAL, std::string(who) + ": more wide frames than wide_cap (*n_wide is the number needed)");
-  return RAFTQ_OK;
-}
-
-// The streaming WAL encode, enqueued and NOT waited for; its totals go to wire_pin[pin_base ..] (raftq_wal_encode: 0;
-// raftq_wal_encode_begin: 8, so that the call enqueued behind it can use the words at 0).
-static int wal_streaming_enqueue(raftq_t* h, const void* v_recs, uint64_t n, const void* v_pool, uint64_t pool_bytes, uint32_t prev_crc, void* v_out,
-                                 uint64_t cap, void* v_off, uint32_t pin_base) {
-  const uint32_t n_tiles = blocks_for(n);
-  const unsigned workers = fused_grid(n_tiles);
-  Carver fc;
-  const void* const src[3] = {v_recs, v_pool, nullptr};
-  const uint64_t sizes[3] = {n * sizeof(WalRec), pool_bytes, 0};
-  TileCtl ctl;
-  if (int rc = tile_ctl(h, std::max<uint64_t>(n_tiles, (sizes[0] + sizes[1]) / kFeedChunk + 1), &ctl)) return rc;
-  FeedPlan plan = plan_feed(fc, src, sizes, h->wire_lb_tiles);
-  if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, fc.off)) return rc;
-  if (int rc = grow(h, &h->wire_out, &h->wire_out_bytes, cap + 16)) return rc;
-  if (int rc = bind_feed(h, plan, (uint8_t*)h->wire_dev, ctl.status[kLbFlags])) return rc;
-  hipLaunchKernelGGL(wal_enc_fused_kernel, dim3(plan.in.readers + workers), dim3(kBlock), 0, h->stream, plan.in, n, pool_bytes, prev_crc,
-                     (uint8_t*)h->wire_out, (uint8_t*)v_out, cap, (uint64_t*)v_off, ctl, h->wire_pin_d + pin_base);
-  HIPCHK(h, hipGetLastError());
-  tile_ctl_launched(h, n_tiles, workers);
-  return RAFTQ_OK;
-}
-static int wal_streaming_finish(raftq_t* h, const char* who, uint64_t n, uint64_t cap, uint32_t prev_crc, uint32_t pin_base, raftq_wal_counts_t* counts) {
-  if (counts) {
-    *counts = raftq_wal_counts_t{0, 0, 0, 0, 0};
-    counts->last_crc = prev_crc;
-  }
+int wal_streaming_finish(raftq_t* h, const char* who, uint64_t n, uint64_t cap, uint32_t prev_crc, uint32_t pin_base, raftq_wal_counts_t* counts) {
+  if (counts) *counts = raftq_wal_counts_t{0, 0, 0, prev_crc, 0};
   if (int rc = tile_ctl_check(h, who, pin_base)) return rc;
   const uint64_t* pin = h->wire_pin + pin_base;
-  const uint64_t total = pin[0];
-  if (pin[1])
-    return fail(h, RAFTQ_EINVAL, std::string(who) + ": a record has an unknown kind or a payload outside the pool; the output is not valid");
-  if (counts) {
-    counts->n_recs = n;
-    counts->bytes = total;
-  }
-  if (total > cap) return fail(h, RAFTQ_EINVAL, std::string(who) + ": out is too small (counts->bytes is the size needed)");
+  if (int rc = encode_sized(h, who, kWalEncRefused, "the output is not valid", pin[kPinTotal], pin[kPinRefused], cap, counts,
+                            raftq_wal_counts_t{n, 0, pin[kPinTotal], prev_crc, 0}))
+    return rc;
   if (counts) {
     counts->n_valid = n;
-    counts->last_crc = (uint32_t)pin[2];
+    counts->last_crc = (uint32_t)pin[kPinThird];
   }
   return RAFTQ_OK;
 }
 // a raftq_wal_encode_begin whose _end has not come yet: wait for it and keep what _end will report (called by whatever else
 // is about to use its pinned words' neighbours' scratch from the host side)
-static int wal_pending_complete(raftq_t* h) {
+int wal_pending_complete(raftq_t* h) {
   if (!h->wal_pending || h->wal_pending_done) return RAFTQ_OK;
   // (the wait of the marshal called in between has usually covered it: then there is nothing to wait for, and nothing to launch)
   if (!h->wal_pending_waited) HIPCHK(h, raftq_detail::wait_call(h));
-  h->wal_pending_rc = wal_streaming_finish(h, "raftq_wal_encode_begin", h->wal_pending_n, h->wal_pending_cap, h->wal_pending_prev, 8, &h->wal_pending_counts);
+  h->wal_pending_rc =
+      wal_streaming_finish(h, "raftq_wal_encode_begin", h->wal_pending_n, h->wal_pending_cap, h->wal_pending_prev, kPinWalPending, &h->wal_pending_counts);
   if (h->wal_pending_rc != RAFTQ_OK) h->wal_pending_err = h->err;
   h->wal_pending_done = true;
   return RAFTQ_OK;
 }
 
-int raftq_wal_encode(raftq_t* h, const raftq_wal_rec_t* recs, uint64_t n, const void* pool, uint64_t pool_bytes,
-                     uint32_t prev_crc, void* out, uint64_t cap, uint64_t* frame_off, raftq_wal_counts_t* counts) {
-  if (int rc = use_device(h)) return rc;
-  if (counts) {
-    *counts = raftq_wal_counts_t{0, 0, 0, 0, 0};
-    counts->last_crc = prev_crc;
-  }
-  if (n == 0) {
-    if (frame_off) frame_off[0] = 0;
-    return RAFTQ_OK;
-  }
-  if (!recs || (pool_bytes && !pool) || (cap && !out)) return fail(h, RAFTQ_EINVAL, "raftq_wal_encode: null argument");
-  if (n > kMaxItems) return fail(h, RAFTQ_EINVAL, "raftq_wal_encode: batch too large");
-  if (int rc = ensure_pin(h)) return rc;
-  // page-locked caller buffers take the streaming form; anything else the copying form
-  void *v_recs = nullptr, *v_pool = nullptr, *v_out = nullptr, *v_off = nullptr;
-  const bool mapped = streaming_on() && cap != 0 && cap <= ((uint64_t)1 << 31) && (v_recs = dev_view(recs)) != nullptr &&
-                      (pool_bytes == 0 || (v_pool = dev_view(pool)) != nullptr) && (v_out = dev_view(out)) != nullptr &&
-                      (!frame_off || (v_off = dev_view(frame_off)) != nullptr);
-  if (mapped && aligned16(v_recs) && aligned16(v_pool) && aligned16(v_out) && aligned16(v_off)) {
-    // page-locked caller buffers: the streaming form (readers | workers in one launch; raftq_wire_kernels.hpp)
-    if (int rc = wal_pending_complete(h)) return rc;  // (a raftq_wal_encode_begin nobody ended: its results are kept for its _end)
-    if (int rc = wal_streaming_enqueue(h, v_recs, n, v_pool, pool_bytes, prev_crc, v_out, cap, v_off, 0)) return rc;
-    HIPCHK(h, raftq_detail::wait_call(h));
-    return wal_streaming_finish(h, "raftq_wal_encode", n, cap, prev_crc, 0, counts);
-  }
+int wal_encode_copying(raftq_t* h, const raftq_wal_rec_t* recs, uint64_t n, const void* pool, uint64_t pool_bytes, uint32_t prev_crc, void* out,
+                       uint64_t cap, uint64_t* frame_off, raftq_wal_counts_t* counts) {
   const size_t scan_bytes = scan_sum_scratch_bytes(n + 1);  // tile totals of the hand-written scan
   Carver c;
   const size_t o_recs = c.take(n * sizeof(WalRec)), o_pool = c.take(pool_bytes), o_pcrc = c.take(n * 4),
@@ -836,10 +822,10 @@ int raftq_wal_encode(raftq_t* h, const raftq_wal_rec_t* recs, uint64_t n, const 
   uint64_t *d_sizes = (uint64_t*)(base + o_sizes), *d_off = (uint64_t*)(base + o_off);
   uint32_t* d_last = (uint32_t*)(base + o_flags) + 1;
   unsigned int* d_bad = (unsigned int*)(base + o_flags);
+  uint64_t* pin = h->wire_pin + kPinCall;
   if (int rc = h2d(h, d_recs, recs, n * sizeof(WalRec))) return rc;
   if (int rc = h2d(h, d_pool, pool, pool_bytes)) return rc;
   HIPCHK(h, hipMemsetAsync(d_bad, 0, 8, h->stream));
-  
   hipLaunchKernelGGL(wal_enc_payload_crc_kernel, dim3(blocks_for(n * 64)), dim3(kBlock), 0, h->stream,
                      (const WalRec*)d_recs, n, (const uint8_t*)d_pool, pool_bytes, d_pcrc);
   hipLaunchKernelGGL(wal_enc_crc_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, h->stream, (const WalRec*)d_recs, n,
@@ -850,17 +836,13 @@ int raftq_wal_encode(raftq_t* h, const raftq_wal_rec_t* recs, uint64_t n, const 
                      (const CrcPair*)d_chain, d_sizes);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, exclusive_sum_u64((const uint64_t*)d_sizes, d_off, n + 1, (uint64_t*)(base + o_scan), h->stream));
-  if (int rc = d2h(h, &h->wire_pin[0], d_off + n, 8)) return rc;
-  if (int rc = d2h(h, &h->wire_pin[1], d_bad, 4)) return rc;
+  if (int rc = d2h(h, &pin[kPinTotal], d_off + n, 8)) return rc;
+  if (int rc = d2h(h, &pin[kPinRefused], d_bad, 4)) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  const uint64_t total = h->wire_pin[0];
-  if ((uint32_t)h->wire_pin[1])
-    return fail(h, RAFTQ_EINVAL, "raftq_wal_encode: a record has an unknown kind or a payload outside the pool; nothing was written");
-  if (counts) {
-    counts->n_recs = n;
-    counts->bytes = total;
-  }
-  if (total > cap) return fail(h, RAFTQ_EINVAL, "raftq_wal_encode: out is too small (counts->bytes is the size needed)");
+  const uint64_t total = pin[kPinTotal];
+  if (int rc = encode_sized(h, "raftq_wal_encode", kWalEncRefused, "nothing was written", total, (uint32_t)pin[kPinRefused], cap, counts,
+                            raftq_wal_counts_t{n, 0, total, prev_crc, 0}))
+    return rc;
   if (int rc = grow(h, &h->wire_out, &h->wire_out_bytes, total + 16)) return rc;
   uint8_t* d_out = (uint8_t*)h->wire_out;
   hipLaunchKernelGGL(wal_enc_write_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, h->stream, (const WalRec*)d_recs, n,
@@ -873,13 +855,95 @@ int raftq_wal_encode(raftq_t* h, const raftq_wal_rec_t* recs, uint64_t n, const 
   if (int rc = d2h(h, out, d_out, total)) return rc;
   if (frame_off)
     if (int rc = d2h(h, frame_off, d_off, (n + 1) * 8)) return rc;
-  if (int rc = d2h(h, &h->wire_pin[2], d_last, 4)) return rc;
+  if (int rc = d2h(h, &pin[kPinThird], d_last, 4)) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (counts) {
     counts->n_valid = n;
-    counts->last_crc = (uint32_t)h->wire_pin[2];
+    counts->last_crc = (uint32_t)pin[kPinThird];
   }
   return RAFTQ_OK;
+}
+
+// what either form of raftq_wal_decode reports: records before the first bad one (kPinTotal), the running CRC there (kPinRefused's word)
+void wal_decode_counted(raftq_t* h, const uint64_t* frame_off, uint64_t n, raftq_wal_counts_t* counts) {
+  const uint64_t* pin = h->wire_pin + kPinCall;
+  if (counts) *counts = raftq_wal_counts_t{n, pin[kPinTotal], span_of(frame_off, n), (uint32_t)pin[kPinRefused], 0};
+}
+
+// page-locked caller buffers (v_*: as the device addresses them): readers | workers in one launch
+int wal_decode_streaming(raftq_t* h, const void* v_bytes, uint64_t nbytes, const uint64_t* frame_off, const void* v_off, uint64_t n, uint32_t prev_crc,
+                         void* v_recs, raftq_wal_counts_t* counts) {
+  StreamCall sc;
+  sc.n_tiles = blocks_for(n);
+  sc.seg[0] = {v_off, (n + 1) * 8, 0};
+  sc.seg[1] = {v_bytes, nbytes, 0};
+  if (int rc = stream_prepare(h, sc)) return rc;
+  if (int rc = stream_launch(h, sc, wal_dec_fused_kernel, kBlock, sc.in, nbytes, n, prev_crc, (WalRec*)v_recs, sc.ctl, h->wire_pin_d + kPinCall)) return rc;
+  HIPCHK(h, raftq_detail::wait_call(h));
+  if (int rc = tile_ctl_check(h, "raftq_wal_decode", kPinCall)) return rc;
+  wal_decode_counted(h, frame_off, n, counts);
+  return RAFTQ_OK;
+}
+
+int wal_decode_copying(raftq_t* h, const void* bytes, uint64_t nbytes, const uint64_t* frame_off, uint64_t n, uint32_t prev_crc, raftq_wal_rec_t* recs,
+                       raftq_wal_counts_t* counts) {
+  Carver c;
+  const size_t o_bytes = c.take(nbytes), o_off = c.take((n + 1) * 8), o_recs = c.take(n * sizeof(WalRec)),
+               o_span = c.take(n * sizeof(WalSpan)), o_pair = c.take(n * 8), o_chain = c.take(n * 8),
+               o_tail = c.take(32), o_tot = c.take((size_t)blocks_for(n) * sizeof(CrcPair));
+  if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, c.off)) return rc;
+  uint8_t* base = (uint8_t*)h->wire_dev;
+  uint8_t* d_bytes = base + o_bytes;
+  uint64_t* d_off = (uint64_t*)(base + o_off);
+  WalRec* d_recs = (WalRec*)(base + o_recs);
+  WalSpan* d_span = (WalSpan*)(base + o_span);
+  CrcPair *d_pair = (CrcPair*)(base + o_pair), *d_chain = (CrcPair*)(base + o_chain);
+  unsigned long long* d_first_bad = (unsigned long long*)(base + o_tail);
+  uint64_t* d_tail = (uint64_t*)(base + o_tail) + 1;
+  if (int rc = h2d(h, d_bytes, bytes, nbytes)) return rc;
+  if (int rc = h2d(h, d_off, frame_off, (n + 1) * 8)) return rc;
+  HIPCHK(h, hipMemsetAsync(d_first_bad, 0xff, 8, h->stream));
+  hipLaunchKernelGGL(wal_dec_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, h->stream, (const uint8_t*)d_bytes, nbytes,
+                     (const uint64_t*)d_off, n, prev_crc, d_recs, d_span, d_pair);
+  hipLaunchKernelGGL(wal_dec_long_crc_kernel, dim3(blocks_for(n * 64)), dim3(kBlock), 0, h->stream,
+                     (const uint8_t*)d_bytes, n, (const WalSpan*)d_span, prev_crc, d_pair);
+  HIPCHK(h, hipGetLastError());
+  if (int rc = crc_chain_scan(h, d_pair, d_chain, n, (CrcPair*)(base + o_tot))) return rc;
+  hipLaunchKernelGGL(wal_dec_check_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, h->stream, d_recs, n,
+                     (const CrcPair*)d_chain, prev_crc, d_first_bad);
+  hipLaunchKernelGGL(wal_dec_tail_kernel, dim3(1), dim3(64), 0, h->stream, (const CrcPair*)d_chain, n, prev_crc,
+                     (const unsigned long long*)d_first_bad, d_tail);
+  HIPCHK(h, hipGetLastError());
+  if (int rc = d2h(h, recs, d_recs, n * sizeof(WalRec))) return rc;
+  if (int rc = d2h(h, h->wire_pin + kPinCall, d_tail, 16)) return rc;  // kPinTotal and the word behind it
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  wal_decode_counted(h, frame_off, n, counts);
+  return RAFTQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int raftq_wal_encode(raftq_t* h, const raftq_wal_rec_t* recs, uint64_t n, const void* pool, uint64_t pool_bytes,
+                     uint32_t prev_crc, void* out, uint64_t cap, uint64_t* frame_off, raftq_wal_counts_t* counts) {
+  if (int rc = use_device(h)) return rc;
+  if (counts) *counts = raftq_wal_counts_t{0, 0, 0, prev_crc, 0};
+  if (n == 0) {
+    if (frame_off) frame_off[0] = 0;
+    return RAFTQ_OK;
+  }
+  if (!recs || (pool_bytes && !pool) || (cap && !out)) return fail(h, RAFTQ_EINVAL, "raftq_wal_encode: null argument");
+  if (n > kMaxItems) return fail(h, RAFTQ_EINVAL, "raftq_wal_encode: batch too large");
+  if (int rc = ensure_pin(h)) return rc;
+  // page-locked caller buffers take the streaming form; anything else the copying form
+  Views v(streaming_on() && cap != 0 && cap <= ((uint64_t)1 << 31));
+  void *v_recs = v.add(recs), *v_pool = v.add(pool, pool_bytes != 0), *v_out = v.add(out), *v_off = v.opt(frame_off);
+  if (!v.ok) return wal_encode_copying(h, recs, n, pool, pool_bytes, prev_crc, out, cap, frame_off, counts);
+  if (int rc = wal_pending_complete(h)) return rc;  // (a raftq_wal_encode_begin nobody ended: its results are kept for its _end)
+  if (int rc = wal_streaming_enqueue(h, v_recs, n, v_pool, pool_bytes, prev_crc, v_out, cap, v_off, kPinCall)) return rc;
+  HIPCHK(h, raftq_detail::wait_call(h));
+  return wal_streaming_finish(h, "raftq_wal_encode", n, cap, prev_crc, kPinCall, counts);
 }
 
 int raftq_wal_encode_begin(raftq_t* h, const raftq_wal_rec_t* recs, uint64_t n, const void* pool, uint64_t pool_bytes, uint32_t prev_crc,
@@ -889,13 +953,12 @@ int raftq_wal_encode_begin(raftq_t* h, const raftq_wal_rec_t* recs, uint64_t n, 
   if (n == 0 || !recs || (pool_bytes && !pool) || !out || cap == 0) return fail(h, RAFTQ_EINVAL, "raftq_wal_encode_begin: null argument or empty batch");
   if (n > kMaxItems) return fail(h, RAFTQ_EINVAL, "raftq_wal_encode_begin: batch too large");
   if (int rc = ensure_pin(h)) return rc;
-  void *v_recs = nullptr, *v_pool = nullptr, *v_out = nullptr, *v_off = nullptr;
-  const bool mapped = cap <= ((uint64_t)1 << 31) && (v_recs = dev_view(recs)) != nullptr && (pool_bytes == 0 || (v_pool = dev_view(pool)) != nullptr) &&
-                      (v_out = dev_view(out)) != nullptr && (!frame_off || (v_off = dev_view(frame_off)) != nullptr);
-  if (!(mapped && aligned16(v_recs) && aligned16(v_pool) && aligned16(v_out) && aligned16(v_off)))
+  Views v(cap <= ((uint64_t)1 << 31));
+  void *v_recs = v.add(recs), *v_pool = v.add(pool, pool_bytes != 0), *v_out = v.add(out), *v_off = v.opt(frame_off);
+  if (!v.ok)
     return fail(h, RAFTQ_EINVAL, "raftq_wal_encode_begin: the records, the pool and the output must be page-locked (raftq_host_alloc, hipHostMalloc, "
                                  "hipHostRegister) and 16-byte aligned -- raftq_wal_encode otherwise");
-  if (int rc = wal_streaming_enqueue(h, v_recs, n, v_pool, pool_bytes, prev_crc, v_out, cap, v_off, 8)) return rc;
+  if (int rc = wal_streaming_enqueue(h, v_recs, n, v_pool, pool_bytes, prev_crc, v_out, cap, v_off, kPinWalPending)) return rc;
   h->wal_pending = true;
   h->wal_pending_done = false;
   h->wal_pending_waited = false;
@@ -918,86 +981,15 @@ int raftq_wal_encode_end(raftq_t* h, raftq_wal_counts_t* counts) {
 int raftq_wal_decode(raftq_t* h, const void* bytes, uint64_t nbytes, const uint64_t* frame_off, uint64_t n,
                      uint32_t prev_crc, raftq_wal_rec_t* recs, raftq_wal_counts_t* counts) {
   if (int rc = use_device(h)) return rc;
-  if (counts) {
-    *counts = raftq_wal_counts_t{0, 0, 0, 0, 0};
-    counts->last_crc = prev_crc;
-  }
+  if (counts) *counts = raftq_wal_counts_t{0, 0, 0, prev_crc, 0};
   if (n == 0) return RAFTQ_OK;
   if ((!bytes && nbytes) || !frame_off || !recs) return fail(h, RAFTQ_EINVAL, "raftq_wal_decode: null argument");
   if (n > kMaxItems) return fail(h, RAFTQ_EINVAL, "raftq_wal_decode: batch too large");
   if (int rc = ensure_pin(h)) return rc;
-  {
-    void *f_bytes = nullptr, *f_off = nullptr, *f_recs = nullptr;
-    if (streaming_on() && nbytes < (1ull << (kLbValueBits - 1)) && (nbytes == 0 || (f_bytes = dev_view(bytes)) != nullptr) &&
-        (f_off = dev_view(frame_off)) != nullptr && (f_recs = dev_view(recs)) != nullptr && aligned16(f_bytes) && aligned16(f_off) && aligned16(f_recs)) {
-      // page-locked caller buffers: the streaming form (readers | workers in one launch)
-      const uint32_t n_tiles = blocks_for(n);
-      const unsigned workers = fused_grid(n_tiles);
-      Carver c;
-      const void* const src[3] = {f_off, f_bytes, nullptr};
-      const uint64_t sizes[3] = {(n + 1) * 8, nbytes, 0};
-      TileCtl ctl;
-      if (int rc = tile_ctl(h, std::max<uint64_t>(n_tiles, (sizes[0] + sizes[1]) / kFeedChunk + 1), &ctl)) return rc;
-      FeedPlan plan = plan_feed(c, src, sizes, h->wire_lb_tiles);
-      if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, c.off)) return rc;
-      if (int rc = bind_feed(h, plan, (uint8_t*)h->wire_dev, ctl.status[kLbFlags])) return rc;
-      hipLaunchKernelGGL(wal_dec_fused_kernel, dim3(plan.in.readers + workers), dim3(kBlock), 0, h->stream, plan.in, nbytes, n, prev_crc,
-                         (WalRec*)f_recs, ctl, h->wire_pin_d);
-      HIPCHK(h, hipGetLastError());
-      tile_ctl_launched(h, n_tiles, workers);
-      HIPCHK(h, raftq_detail::wait_call(h));
-      if (int rc = tile_ctl_check(h, "raftq_wal_decode")) return rc;
-      if (counts) {
-        counts->n_recs = n;
-        counts->n_valid = h->wire_pin[0];
-        counts->bytes = frame_off[n] >= frame_off[0] ? frame_off[n] - frame_off[0] : 0;
-        counts->last_crc = (uint32_t)h->wire_pin[1];
-      }
-      return RAFTQ_OK;
-    }
-  }
-  Carver c;
-  const size_t o_bytes = c.take(nbytes), o_off = c.take((n + 1) * 8), o_recs = c.take(n * sizeof(WalRec)),
-               o_span = c.take(n * sizeof(WalSpan)), o_pair = c.take(n * 8), o_chain = c.take(n * 8),
-               o_tail = c.take(32), o_tot = c.take((size_t)blocks_for(n) * sizeof(CrcPair));
-  if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, c.off)) return rc;
-  uint8_t* base = (uint8_t*)h->wire_dev;
-  uint8_t* d_bytes = base + o_bytes;
-  uint64_t* d_off = (uint64_t*)(base + o_off);
-  WalRec* d_recs = (WalRec*)(base + o_recs);
-  WalSpan* d_span = (WalSpan*)(base + o_span);
-  CrcPair *d_pair = (CrcPair*)(base + o_pair), *d_chain = (CrcPair*)(base + o_chain);
-  unsigned long long* d_first_bad = (unsigned long long*)(base + o_tail);
-  uint64_t* d_tail = (uint64_t*)(base + o_tail) + 1;
-  void *v_bytes = nullptr, *v_off = nullptr, *v_recs = nullptr;
-  const bool mapped = streaming_on() && (nbytes == 0 || (v_bytes = dev_view(bytes)) != nullptr) && (v_off = dev_view(frame_off)) != nullptr &&
-                      (v_recs = dev_view(recs)) != nullptr;
-  if (int rc = h2d(h, d_bytes, bytes, nbytes)) return rc;
-  if (int rc = h2d(h, d_off, frame_off, (n + 1) * 8)) return rc;
-  
-  HIPCHK(h, hipMemsetAsync(d_first_bad, 0xff, 8, h->stream));
-  hipLaunchKernelGGL(wal_dec_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, h->stream, (const uint8_t*)d_bytes, nbytes,
-                     (const uint64_t*)d_off, n, prev_crc, d_recs, d_span, d_pair);
-  hipLaunchKernelGGL(wal_dec_long_crc_kernel, dim3(blocks_for(n * 64)), dim3(kBlock), 0, h->stream,
-                     (const uint8_t*)d_bytes, n, (const WalSpan*)d_span, prev_crc, d_pair);
-  HIPCHK(h, hipGetLastError());
-  if (int rc = crc_chain_scan(h, d_pair, d_chain, n, (CrcPair*)(base + o_tot))) return rc;
-  hipLaunchKernelGGL(wal_dec_check_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, h->stream, d_recs, n,
-                     (const CrcPair*)d_chain, prev_crc, d_first_bad);
-  hipLaunchKernelGGL(wal_dec_tail_kernel, dim3(1), dim3(64), 0, h->stream, (const CrcPair*)d_chain, n, prev_crc,
-                     (const unsigned long long*)d_first_bad, d_tail);
-  HIPCHK(h, hipGetLastError());
-  if (int rc = d2h(h, recs, d_recs, n * sizeof(WalRec))) return rc;
-  if (int rc = d2h(h, &h->wire_pin[0], d_tail, 16)) return rc;
-  
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (counts) {
-    counts->n_recs = n;
-    counts->n_valid = h->wire_pin[0];
-    counts->bytes = frame_off[n] >= frame_off[0] ? frame_off[n] - frame_off[0] : 0;
-    counts->last_crc = (uint32_t)h->wire_pin[1];
-  }
-  return RAFTQ_OK;
+  Views v(streaming_on() && nbytes < (1ull << (kLbValueBits - 1)));
+  void *v_bytes = v.add(bytes, nbytes != 0), *v_off = v.add(frame_off), *v_recs = v.add(recs);
+  if (v.ok) return wal_decode_streaming(h, v_bytes, nbytes, frame_off, v_off, n, prev_crc, v_recs, counts);
+  return wal_decode_copying(h, bytes, nbytes, frame_off, n, prev_crc, recs, counts);
 }
 
 }  // extern "C"

@@ -628,6 +628,90 @@ def test_streaming_wal_codecs_at_bench_size(wgs, monkeypatch):
             _same(gr, wr, "recs")
 
 
+def test_buffers_and_control_block_regrow_between_calls_of_different_kinds():
+    """One handle: small calls of every kind, then a WAL segment whose input is past 4,096 chunks of 8,192 bytes -- more than
+    the first control block has flags for, so the block (and the scratch, and the output buffer) is replaced and tickets and
+    epochs start over --, then the small calls again.  Everything on page-locked buffers, everything the oracle's."""
+    from raftsql_amd.engine import pinned_copy, pinned_empty
+    from raftsql_amd.wire import WireEngine
+
+    rng = np.random.default_rng(4100)
+    m, e, pool = _wiregen.random_msgs(rng, 1, ent_frac=1.0)
+    want_s, want_soff = W.wire_encode(m, e, pool)
+    want_m, want_e, _ = W.wire_decode(want_s, want_soff)
+    r, rpool = _wiregen.random_wal(rng, 300, big_every=9)
+    want_w, want_woff, want_wlast = W.wal_encode(r, rpool, 5)
+    want_r, want_nv, want_rlast = W.wal_decode(want_w, want_woff, 5)
+
+    def small_calls(eng):
+        got, goff = eng.wire_encode(m, e, pool)
+        assert got.tobytes() == want_s.tobytes() and np.array_equal(goff, want_soff)
+        gm, ge, bad = eng.wire_decode(want_s, want_soff)
+        assert bad == 0 and gm.tobytes() == want_m.tobytes() and ge.tobytes() == want_e.tobytes()
+        got, goff, glast = eng.wal_encode(r, rpool, 5)
+        assert got.tobytes() == want_w.tobytes() and np.array_equal(goff, want_woff) and glast == want_wlast
+        gr, gnv, gl = eng.wal_decode(want_w, want_woff, 5)
+        assert (gnv, gl) == (want_nv, want_rlast) == (300, want_wlast) and gr.tobytes() == want_r.tobytes()
+
+    n, ln = 1800, 20000  # 36 MB of payload: 4,405 chunks
+    big = np.zeros(n, W.WAL_REC_DT)
+    big["kind"], big["term"], big["index"], big["group"] = W.WAL_ENTRY, 3, 1 + np.arange(n), np.arange(n) % 7
+    big["data_len"], big["data_off"] = ln, np.arange(n, dtype=np.uint64) * ln
+    big[0] = np.zeros(1, W.WAL_REC_DT)[0]
+    big["kind"][0] = W.WAL_CRC
+    bpool = rng.integers(0, 256, n * ln, dtype=np.uint8)
+    assert big.nbytes + len(bpool) > 4096 * 8192
+    want_b, want_boff, want_blast = W.wal_encode(big, bpool, 0)
+    want_br, want_bnv, want_brlast = W.wal_decode(want_b, want_boff, 0)
+    with WireEngine(4096, 5, self_peer=0) as e0:
+        eng = _PinnedCalls(e0)
+        small_calls(eng)
+        out, off = pinned_empty(len(want_b) + 64, np.uint8), pinned_empty(n + 1, np.uint64)
+        got, goff, glast = e0.wal_encode(pinned_copy(big), pinned_copy(bpool), 0, out=out, off=off)
+        assert np.array_equal(goff, want_boff) and glast == want_blast and got.tobytes() == want_b.tobytes()
+        gr, gnv, gl = e0.wal_decode(out[: len(want_b)], off, 0, recs=pinned_empty(n, W.WAL_REC_DT))
+        assert (gnv, gl) == (want_bnv, want_brlast) == (n, want_blast)
+        _same(gr, want_br, "recs")
+        small_calls(eng)
+
+
+def test_look_back_epoch_wraps():
+    """The look-back status words carry a 16-bit epoch: the 65,536th streaming call on a handle clears the arrays and starts
+    again at epoch 1.  The first call leaves epoch-1 words for tiles 1 and 2; the call at the wrap decodes OTHER frames over three
+    tiles -- had the arrays not been cleared, its tile 1 would take tile 0's prefix from the first call's words."""
+    import ctypes as C
+
+    from raftsql_amd import _lib
+    from raftsql_amd.engine import pinned_copy, pinned_empty
+    from raftsql_amd.wire import WireEngine
+
+    def batch(seed, ent_frac):
+        m, e, pool = _wiregen.random_msgs(np.random.default_rng(seed), 600, ent_frac=ent_frac)
+        s, off = W.wire_encode(m, e, pool)
+        return pinned_copy(s), pinned_copy(off), W.wire_decode(s, off)
+
+    first, at_wrap, after = batch(4201, 0.2), batch(4202, 0.7), batch(4203, 0.4)
+    assert len({len(b[2][1]) for b in (first, at_wrap, after)}) == 3  # different entry counts: different look-back prefixes
+    one_s, one_off = pinned_copy(first[0][: int(first[1][1])]), pinned_copy(first[1][:2])
+    with WireEngine(4096, 5, self_peer=0) as eng:
+        dm, de = pinned_empty(600, W.WIRE_MSG_DT), pinned_empty(max(len(b[2][1]) for b in (first, at_wrap, after)) + 1, W.WIRE_ENT_DT)
+
+        def check(b):
+            gm, ge, bad = eng.wire_decode(b[0], b[1], msgs=dm, ents=de)
+            wm, we, wbad = b[2]
+            assert bad == wbad
+            _same(gm, wm, "msgs")
+            _same(ge, we, "ents")
+
+        check(first)  # epoch 1
+        c = _lib.WireCounts()
+        fn, args = eng._lib.raftq_wire_decode, (eng._h, one_s.ctypes.data, len(one_s), one_off.ctypes.data, 1, dm.ctypes.data, de.ctypes.data, len(de), C.byref(c))
+        for _ in range(65534):  # epochs 2 .. 65,535
+            assert fn(*args) == 0
+        check(at_wrap)
+        check(after)
+
+
 def _wiregen_u8(pool):
     return np.ascontiguousarray(np.frombuffer(bytes(pool), np.uint8) if not isinstance(pool, np.ndarray) else pool.view(np.uint8))
 
