@@ -285,3 +285,36 @@ func (e *Engine) CollectBeats(out []uint64) (uint64, error) {
 	rc := C.raftq_collect_beats(e.h, p, C.uint64_t(len(out)), &n)
 	return uint64(n), e.err(rc)
 }
+
+// VoterDelta is one applied conf change of one group (raftq_voter_delta_t: group, the new voter mask, the slots to reset).
+// Voters bit p set = peer slot p votes in the group; Reset bit p set = the slot's Match is zeroed and its vote cleared.
+type VoterDelta struct {
+	Group  uint64
+	Voters uint16
+	Reset  uint16
+	_      uint32
+}
+
+// LoadVoters sets every group's voter mask: the rpeers StartNode is given (raft.go:148-164).  nil drops the masks, and
+// every slot votes in every group again (raftq_load_voters).
+func (e *Engine) LoadVoters(voters []uint16) error {
+	var p *C.uint16_t
+	if voters != nil {
+		p = (*C.uint16_t)(unsafe.Pointer(&voters[0]))
+	}
+	return e.err(C.raftq_load_voters(e.h, p))
+}
+
+// ApplyVoterDeltas applies conf changes: what ApplyConfChange does for the entries publishEntries passes by (raft.go:84-86).
+// The last record of a group wins; one bad record and nothing is applied (raftq_apply_voter_deltas).
+func (e *Engine) ApplyVoterDeltas(d []VoterDelta) error {
+	if len(d) == 0 {
+		return nil
+	}
+	return e.err(C.raftq_apply_voter_deltas(e.h, (*C.raftq_voter_delta_t)(unsafe.Pointer(&d[0])), C.uint64_t(len(d))))
+}
+
+// ReadVoters copies every group's voter mask; all N bits everywhere when none are loaded (raftq_read_voters).
+func (e *Engine) ReadVoters(out []uint16) error {
+	return e.err(C.raftq_read_voters(e.h, (*C.uint16_t)(unsafe.Pointer(&out[0]))))
+}

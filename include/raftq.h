@@ -170,6 +170,42 @@ int raftq_apply_vote_deltas(raftq_t* h, const raftq_vote_delta_t* d, uint64_t n)
 /* later records of the same group win (applied in order on the host side) */
 int raftq_apply_term_deltas(raftq_t* h, const raftq_term_delta_t* d, uint64_t n);
 
+/* ---- per-group voter sets ------------------------------------------------
+ * A handle has N peer SLOTS; which of them vote is a property of each group.  etcd's q() is len(r.prs)/2 + 1 over the
+ * group's own r.prs, which changes whenever a conf change is applied.  voters[g] is a 16-bit mask: bit p set = slot p is a
+ * voting member of group g (a bit at or above N: RAFTQ_EINVAL).  With n_g = popcount(voters[g]) and q_g = n_g/2 + 1:
+ *   - the commit candidate is the q_g-th largest match[p][g] over the voters only; raftLog.maybeCommit then runs as
+ *     always (gated or not), and the commit index never decreases;
+ *   - the tally counts granted and rejected over the voters only: won if granted >= q_g, else lost if rejected >= q_g,
+ *     else pending.
+ * Match and vote words of non-voters are stored, ingested and read back as always; the decisions ignore them.  An EMPTY
+ * mask marks an unused group slot: its candidate is 0, so nothing commits, and its outcome stays pending (upstream has no
+ * such state: a raft with no peers does not exist there).
+ * With masks loaded, raftq_step_async / raftq_commit_advance / raftq_vote_tally / raftq_collect_changed / raftq_cycle /
+ * raftq_cycle_packed run the masked sweep under every flag but RAFTQ_SWEEP_LDS (RAFTQ_EINVAL: the A/B variant has no masked
+ * form).  Not built, and refused with RAFTQ_ESTATE and a message that says so: a sweep set with a masked member
+ * (raftq_set_create; raftq_load_voters / raftq_apply_voter_deltas on a member), and every entry point of raftq_step.h /
+ * raftq_wire.h that runs Step's maybeCommit or poll on the device.  A handle with no masks loaded is exactly the handle it
+ * always was, kernels included. */
+typedef struct raftq_voter_delta {
+  uint64_t group;
+  uint16_t voters; /* the group's new mask */
+  uint16_t reset;  /* slots whose Match is zeroed and whose vote is cleared: a slot reused for a new replica */
+  uint32_t _pad;
+} raftq_voter_delta_t;
+/* The first membership of every group: the rpeers of raft.go:148-164 (StartNode(c, rpeers), itself a run of
+ * ConfChangeAddNode entries).  voters[G]; NULL drops the masks: every slot votes again, the unmasked kernels. */
+int raftq_load_voters(raftq_t* h, const uint16_t* voters);
+/* Conf changes applied: the entries publishEntries passes by at raft.go:84-86, where upstream raftexample calls
+ * ApplyConfChange.  Per record: the group's mask is replaced and, for every bit of `reset`, match[p][group] is zeroed and
+ * peer p's vote cleared (deltas only ever raise Match: a reused slot must not inherit its predecessor's).  The last record
+ * of a group wins.  All-or-nothing: one record with group >= G or a bit >= N and nothing is applied, RAFTQ_EINVAL.  On a
+ * handle with no masks loaded the records change "every slot votes". */
+int raftq_apply_voter_deltas(raftq_t* h, const raftq_voter_delta_t* d, uint64_t n);
+/* the masks as the device holds them (r.prs of every group, raft.go:84-86 / 148-164); (1 << N) - 1 everywhere when none are
+ * loaded.  voters_out[G]. */
+int raftq_read_voters(raftq_t* h, uint16_t* voters_out);
+
 /* ---- the sweep ---------------------------------------------------------- */
 /* enqueue one pass over all G groups on the handle's stream. */
 int raftq_step_async(raftq_t* h, unsigned flags);
@@ -296,7 +332,7 @@ int raftq_last_advances_packed(raftq_t* h, const raftq_advance16_t** list, uint6
  * completion word per turn instead of four.  Read them with raftq_last_advance_segments: segment s holds counts[s] records
  * at recs + s * stride, and walking the segments in order IS the ascending list raftq_last_advances_packed would have
  * returned (n_advanced is the same total).  A turn that cannot take that form (a vote tally or counts asked for, the list
- * copied out, the A/B sweep, a handle of more than 4M groups -- the pinned list has a slot per group) produces the contiguous
+ * copied out, the A/B sweep, a handle with voter masks loaded, a handle of more than 4M groups -- the pinned list has a slot per group) produces the contiguous
  * list as always, `cap` records of it at most, and raftq_last_advance_segments presents it as ONE segment: a consumer that
  * passes the flag reads segments, whatever happened (and compares counts[0] with n_advanced when there is one).  Valid until the next raftq_cycle* /
  * raftq_collect_changed on the handle. */
@@ -349,9 +385,10 @@ int raftq_set_timer_end(raftq_set_t* s, float* elapsed_ms);
  * one, forked and joined inside the call, so that consecutive launches overlap their
  * boundaries; everything is ordered behind / in front of the shared stream as before. */
 int raftq_sweep_many_async(raftq_t* const* handles, uint32_t n, unsigned flags);
-/* device-to-device copy of the quorum state (match, commit index, term gate, votes) of
- * `src` into `dst` (same device, groups and peers): fork a population without a host
- * round trip.  Tick / Step node state is not copied. */
+/* device-to-device copy of the quorum state (match, commit index, term gate, votes, voter masks)
+ * of `src` into `dst` (same device, groups and peers): fork a population without a host
+ * round trip.  `dst` ends with src's masks, or with none when src has none.  Tick / Step node
+ * state is not copied. */
 int raftq_clone_state(raftq_t* dst, raftq_t* src);
 
 /* ---- measurement hooks (bench harness) --------------------------------- */

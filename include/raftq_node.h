@@ -47,8 +47,10 @@
  * save-then-send order, raft.go:228-230).  raftq_node_replay_wal() is
  * replayWAL (raft.go:122-134) from such bytes.
  *
- * Not built (same as raftq_step.h): snapshots / log compaction, conf changes,
- * the inflight window.  The log lives in host memory, like the reference's
+ * Not built (same as raftq_step.h): snapshots / log compaction, conf changes
+ * through Step and the node (the quorum arithmetic over a group's own members
+ * exists in the sweep: raftq.h "per-group voter sets"; a node never loads
+ * masks, every slot votes), joint consensus, the inflight window.  The log lives in host memory, like the reference's
  * raft.MemoryStorage (raft.go:70).
  *
  * Thread-safety: propose / deliver / tick / recv / poll / status from any

@@ -49,6 +49,10 @@ class VoteDelta(C.Structure):
     _fields_ = [("group", C.c_uint64), ("peer", C.c_uint32), ("vote", C.c_uint8), ("_pad", C.c_uint8 * 3)]
 
 
+class VoterDelta(C.Structure):
+    _fields_ = [("group", C.c_uint64), ("voters", C.c_uint16), ("reset", C.c_uint16), ("_pad", C.c_uint32)]
+
+
 class Advance(C.Structure):
     _fields_ = [("group", C.c_uint64), ("old_commit", C.c_uint64), ("new_commit", C.c_uint64)]
 
@@ -72,6 +76,9 @@ _SIGS = [
     ("raftq_apply_deltas", C.c_int, [_H, C.c_void_p, C.c_uint64]),
     ("raftq_apply_vote_deltas", C.c_int, [_H, C.c_void_p, C.c_uint64]),
     ("raftq_apply_term_deltas", C.c_int, [_H, C.c_void_p, C.c_uint64]),
+    ("raftq_load_voters", C.c_int, [_H, C.c_void_p]),
+    ("raftq_apply_voter_deltas", C.c_int, [_H, C.c_void_p, C.c_uint64]),
+    ("raftq_read_voters", C.c_int, [_H, C.c_void_p]),
     ("raftq_step_async", C.c_int, [_H, C.c_uint]),
     ("raftq_wait", C.c_int, [_H, C.POINTER(Counts)]),
     ("raftq_commit_advance", C.c_int, [_H, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]),

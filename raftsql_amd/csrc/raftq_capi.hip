@@ -162,6 +162,47 @@ hipError_t launch_segments(uint32_t N, const SweepArgs& a, uint32_t n_tiles, boo
   }
 }
 
+// The masked sweep of one handle (sweep_voters_kernel).  Groups per lane by peer count, read off the register report
+// (profiles/r09/isa_voters.txt): the full network keeps all N values of a group live where sweep_kernel's
+// pruned one drops those that cannot reach the median.  4 groups per lane while that leaves 6 or more waves per SIMD
+// (N <= 6: 48-73 VGPRs); from N = 7 it would be 80-113 VGPRs and 4-5 waves, so 2 groups per lane (46-63 VGPRs, 8 waves).
+constexpr int voters_gpl(int n_peers) { return n_peers <= 6 ? 4 : 2; }
+
+template <int N, bool COMMIT, bool GATED, bool VOTES>
+hipError_t launch_voters_reg(const VoterSweepArgs& a, uint64_t gpad, int nt, hipStream_t s) {
+  constexpr int G = voters_gpl(N);
+  const dim3 grid((unsigned)(gpad / ((uint64_t)kBlock * G))), block(kBlock);
+  if (nt == 3) hipLaunchKernelGGL((sweep_voters_kernel<N, G, COMMIT, GATED, VOTES, kLdNT | kStNT>), grid, block, 0, s, a);
+  else if (nt == 1) hipLaunchKernelGGL((sweep_voters_kernel<N, G, COMMIT, GATED, VOTES, kLdNT>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((sweep_voters_kernel<N, G, COMMIT, GATED, VOTES, 0>), grid, block, 0, s, a);
+  return hipGetLastError();
+}
+
+template <int N>
+hipError_t launch_voters_n(const VoterSweepArgs& a, uint64_t gpad, unsigned flags, int nt, hipStream_t s) {
+  const bool commit = flags & (RAFTQ_SWEEP_COMMIT | RAFTQ_SWEEP_GATED);
+  const bool gated = flags & RAFTQ_SWEEP_GATED;
+  const bool votes = flags & RAFTQ_SWEEP_VOTES;
+  if (commit && gated) return votes ? launch_voters_reg<N, true, true, true>(a, gpad, nt, s) : launch_voters_reg<N, true, true, false>(a, gpad, nt, s);
+  if (commit) return votes ? launch_voters_reg<N, true, false, true>(a, gpad, nt, s) : launch_voters_reg<N, true, false, false>(a, gpad, nt, s);
+  return launch_voters_reg<N, false, false, true>(a, gpad, nt, s);
+}
+
+hipError_t launch_voters(uint32_t N, const VoterSweepArgs& a, uint64_t gpad, unsigned flags, int nt, hipStream_t s) {
+  switch (N) {
+    case 1: return launch_voters_n<1>(a, gpad, flags, nt, s);
+    case 2: return launch_voters_n<2>(a, gpad, flags, nt, s);
+    case 3: return launch_voters_n<3>(a, gpad, flags, nt, s);
+    case 4: return launch_voters_n<4>(a, gpad, flags, nt, s);
+    case 5: return launch_voters_n<5>(a, gpad, flags, nt, s);
+    case 6: return launch_voters_n<6>(a, gpad, flags, nt, s);
+    case 7: return launch_voters_n<7>(a, gpad, flags, nt, s);
+    case 8: return launch_voters_n<8>(a, gpad, flags, nt, s);
+    case 9: return launch_voters_n<9>(a, gpad, flags, nt, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
 hipError_t launch_sweep(uint32_t N, const SweepLaunch& L, unsigned flags, int nt, hipStream_t s) {
   switch (N) {
     case 1: return launch_n<1>(L, flags, nt, s);
@@ -490,6 +531,7 @@ void raftq_destroy(raftq_t* h) {
   (void)hipFree(h->committed[1]);
   (void)hipFree(h->first_idx);
   (void)hipFree(h->votes);
+  (void)hipFree(h->voters);
   (void)hipFree(h->outcome);
   (void)hipFree(h->changed_bits);
   (void)hipFree(h->partials);
@@ -754,6 +796,106 @@ int raftq_apply_vote_deltas(raftq_t* h, const raftq_vote_delta_t* d, uint64_t n)
   return check_deltas(h);
 }
 
+}  // extern "C"
+
+// ---- per-group voter masks (include/raftq.h "per-group voter sets") ----------------------------------------
+// the masks' array exists (zeroed: no slot votes anywhere until it is filled)
+static int ensure_voters(raftq_t* h) {
+  if (h->voters) return RAFTQ_OK;
+  uint16_t* p = nullptr;
+  HIPCHK(h, hipMalloc((void**)&p, h->ld * sizeof(uint16_t)));
+  if (const hipError_t e = hipMemsetAsync(p, 0, h->ld * sizeof(uint16_t), h->stream); e != hipSuccess) {
+    (void)hipFree(p);
+    HIPCHK(h, e);
+  }
+  h->voters = p;
+  return RAFTQ_OK;
+}
+// back to "every slot votes": the unmasked kernels
+static int drop_voters(raftq_t* h) {
+  if (!h->voters) return RAFTQ_OK;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipFree(h->voters));
+  h->voters = nullptr;
+  return RAFTQ_OK;
+}
+static int voters_not_in_set(raftq_t* h, const char* who) {
+  if (!h->in_set) return RAFTQ_OK;
+  return fail(h, RAFTQ_ESTATE, std::string(who) + ": the handle is a member of a sweep set, whose dispatches count every slot "
+                                                  "(voter masks on set members are out of scope)");
+}
+int raftq_detail::refuse_voters(raftq_t* h, const char* who) {
+  if (!h || !h->voters) return RAFTQ_OK;
+  return fail(h, RAFTQ_ESTATE, std::string(who) + ": the handle has voter masks loaded; Step's maybeCommit / poll on the device "
+                                                  "count every slot (out of scope: raftq_load_voters(h, NULL) first)");
+}
+
+extern "C" {
+
+int raftq_load_voters(raftq_t* h, const uint16_t* voters) {
+  if (int rc = use_device_idle(h, "raftq_load_voters")) return rc;
+  if (int rc = voters_not_in_set(h, "raftq_load_voters")) return rc;
+  if (!voters) return drop_voters(h);
+  const uint32_t beyond = 0xffffu & ~((1u << h->N) - 1u);
+  for (uint64_t g = 0; g < h->G; ++g)
+    if (voters[g] & beyond) return fail(h, RAFTQ_EINVAL, "raftq_load_voters: a mask names a peer slot >= N; nothing loaded");
+  if (int rc = ensure_voters(h)) return rc;
+  HIPCHK(h, hipMemcpyAsync(h->voters, voters, h->G * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return RAFTQ_OK;
+}
+
+int raftq_read_voters(raftq_t* h, uint16_t* voters_out) {
+  if (int rc = use_device_idle(h, "raftq_read_voters")) return rc;
+  if (!voters_out) return fail(h, RAFTQ_EINVAL, "raftq_read_voters: null argument");
+  if (!h->voters) {
+    std::fill(voters_out, voters_out + h->G, (uint16_t)((1u << h->N) - 1u));
+    return RAFTQ_OK;
+  }
+  HIPCHK(h, hipMemcpyAsync(voters_out, h->voters, h->G * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return RAFTQ_OK;
+}
+
+int raftq_apply_voter_deltas(raftq_t* h, const raftq_voter_delta_t* d, uint64_t n) {
+  static_assert(sizeof(VoterDeltaRec) == sizeof(raftq_voter_delta_t), "ABI struct mismatch");
+  if (int rc = use_device_idle(h, "raftq_apply_voter_deltas")) return rc;
+  if (int rc = voters_not_in_set(h, "raftq_apply_voter_deltas")) return rc;
+  if (n == 0) return RAFTQ_OK;
+  if (!d) return fail(h, RAFTQ_EINVAL, "raftq_apply_voter_deltas: null argument");
+  const uint32_t beyond = 0xffffu & ~((1u << h->N) - 1u);
+  for (uint64_t i = 0; i < n; ++i)
+    if (d[i].group >= h->G || ((d[i].voters | d[i].reset) & beyond))
+      return fail(h, RAFTQ_EINVAL, "a voter delta is out of range (group >= G or a bit >= N); nothing applied");
+  if (int rc = ensure_staging(h, (size_t)n * sizeof(raftq_voter_delta_t))) return rc;
+  // keep only the last record per group so the scatter has no write-write race (as raftq_apply_term_deltas)
+  raftq_voter_delta_t* dst = (raftq_voter_delta_t*)h->stage_h;
+  uint64_t m = 0;
+  try {
+    std::unordered_set<uint64_t> seen;
+    seen.reserve((size_t)n * 2);
+    std::vector<uint64_t> keep;
+    keep.reserve(n);
+    for (uint64_t i = n; i-- > 0;)
+      if (seen.insert(d[i].group).second) keep.push_back(i);
+    for (auto it = keep.rbegin(); it != keep.rend(); ++it) dst[m++] = d[*it];
+  } catch (...) {
+    return fail(h, RAFTQ_ENOMEM, "raftq_apply_voter_deltas: host allocation failed");
+  }
+  if (!h->voters) {  // no masks so far = every slot votes everywhere: that is what the records change
+    if (int rc = ensure_voters(h)) return rc;
+    hipLaunchKernelGGL(fill_voters_kernel, dim3((unsigned)((h->G + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, h->voters, h->G,
+                       (uint16_t)((1u << h->N) - 1u));
+    HIPCHK(h, hipGetLastError());
+  }
+  dense_changed(h);  // (match words are zeroed under Step's records)
+  hipLaunchKernelGGL(apply_voter_deltas_kernel, dim3((unsigned)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, h->voters, h->match,
+                     h->ld, h->votes, h->N > 8 ? 1 : 0, h->N, (const VoterDeltaRec*)h->stage_d, m, h->self_max);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // the staging area is reused by the next call
+  return RAFTQ_OK;
+}
+
 // ---- one sweep = validate flags -> fill SweepArgs -> launch -> per-handle bookkeeping.  The three host-side
 // pieces are shared by raftq_step_async (one handle per launch) and raftq_set_sweep_async (a set per launch).
 static int sweep_check(raftq_t* h, unsigned flags, const char* who) {
@@ -770,6 +912,8 @@ static int sweep_check(raftq_t* h, unsigned flags, const char* who) {
     return fail(h, RAFTQ_EINVAL, w + ": RAFTQ_SWEEP_STREAM and RAFTQ_SWEEP_CACHED are exclusive");
   if ((flags & RAFTQ_SWEEP_CHANGED) && !commit)
     return fail(h, RAFTQ_EINVAL, w + ": RAFTQ_SWEEP_CHANGED needs a commit sweep");
+  if ((flags & RAFTQ_SWEEP_LDS) && h->voters)
+    return fail(h, RAFTQ_EINVAL, w + ": RAFTQ_SWEEP_LDS has no form for a handle with voter masks loaded (the A/B variant counts every slot)");
   return RAFTQ_OK;
 }
 
@@ -788,7 +932,7 @@ static SweepArgs sweep_args(const raftq_t* h, int cur, bool want_bits) {
   return a;
 }
 
-static uint64_t sweep_footprint(const raftq_t* h) { return h->ld * (8ull * h->N + 24 + vote_word_bytes((int)h->N) + 1); }
+static uint64_t sweep_footprint(const raftq_t* h) { return h->ld * (8ull * h->N + 24 + vote_word_bytes((int)h->N) + 1 + (h->voters ? 2 : 0)); }
 
 // Streaming policy (profiles/r01/tune_policy_ld_vs_ldst.txt): loads always non-temporal; stores too only
 // once the state outgrows ~128 MiB (2M x 7: -1.7 % with NT stores; 1M x 3/5/9: +1-2 % without them,
@@ -821,6 +965,14 @@ static int sweep_on(raftq_t* h, unsigned flags, hipStream_t s, const char* who) 
   if (int rc = sweep_check(h, flags, who)) return rc;
   const bool commit = flags & (RAFTQ_SWEEP_COMMIT | RAFTQ_SWEEP_GATED);
   const SweepArgs a = sweep_args(h, h->cur, flags & RAFTQ_SWEEP_CHANGED);
+  if (h->voters) {  // quorum over each group's own voters: the masked kernel, whatever else the flags ask for
+    VoterSweepArgs va;
+    va.s = a;
+    va.voters = h->voters;
+    HIPCHK(h, launch_voters(h->N, va, h->gpad, flags, sweep_policy(flags, sweep_footprint(h)), s));
+    sweep_done(h, flags, voters_gpl((int)h->N));
+    return RAFTQ_OK;
+  }
   const bool lds = (flags & RAFTQ_SWEEP_LDS) && commit;
   SweepLaunch L;
   L.one = &a;
@@ -1336,6 +1488,7 @@ static bool segments_ok(const raftq_t* h, unsigned flags) {
   if (const char* e = std::getenv("RAFTQ_CYCLE_SEGMENTS"))  // =0: every turn produces the contiguous list (A/B; the tests' way to a consumer's fallback)
     if (e[0] == '0') return false;
   const unsigned allowed = RAFTQ_SWEEP_COMMIT | RAFTQ_SWEEP_GATED | RAFTQ_SWEEP_CHANGED | RAFTQ_SWEEP_NO_ADOPT | RAFTQ_SWEEP_STREAM | RAFTQ_SWEEP_CACHED;
+  if (h->voters) return false;  // sweep_segments_kernel counts every slot: a masked turn produces the contiguous list
   return (flags & (RAFTQ_SWEEP_COMMIT | RAFTQ_SWEEP_GATED)) && !(flags & ~allowed) && h->gpad <= kSegmentsMaxGroups;
 }
 // sweep + list + flag, two kernels; leaves the handle as sweep_on + enqueue_collect would
@@ -1741,6 +1894,9 @@ int raftq_set_create(raftq_t* const* handles, uint32_t n, raftq_set_t** out) {
                    "raftq_set_create: members must share the device, the peer count and the (padded) group count");
     if (h->step_collected != h->step_submitted)
       return sfail(nullptr, RAFTQ_ESTATE, "raftq_set_create: a member has Step batches in flight");
+    if (h->voters)
+      return sfail(nullptr, RAFTQ_ESTATE, "raftq_set_create: a handle has voter masks loaded; the set dispatches count every slot "
+                                          "(out of scope: sweep it on its own, or raftq_load_voters(h, NULL) first)");
     for (uint32_t k = 0; k < i; ++k)
       if (handles[k] == h) return sfail(nullptr, RAFTQ_EINVAL, "raftq_set_create: duplicate member");
   }
@@ -1988,6 +2144,14 @@ int raftq_clone_state(raftq_t* dst, raftq_t* src) {
     return fail(dst, RAFTQ_EINVAL, "raftq_clone_state: source and destination must have the same device, groups and peers");
   if (src->step_collected != src->step_submitted)
     return fail(dst, RAFTQ_ESTATE, "raftq_clone_state: the source has Step batches in flight");
+  if (src->voters && dst->in_set)
+    return fail(dst, RAFTQ_ESTATE, "raftq_clone_state: the source has voter masks loaded and the destination is a member of a sweep "
+                                   "set, whose dispatches count every slot (out of scope)");
+  if (src->voters) {
+    if (int rc = ensure_voters(dst)) return rc;
+  } else if (int rc = drop_voters(dst)) {
+    return rc;
+  }
   HIPCHK(dst, hipStreamSynchronize(src->stream));
   const uint64_t ld = dst->ld;
   HIPCHK(dst, hipMemcpyAsync(dst->match, src->match, (size_t)dst->N * ld * 8, hipMemcpyDeviceToDevice, dst->stream));
@@ -1997,6 +2161,7 @@ int raftq_clone_state(raftq_t* dst, raftq_t* src) {
                              dst->stream));
   // the rows are the source's, so is what is known about them (the word names its slot: it holds whatever dst's self is)
   HIPCHK(dst, hipMemcpyAsync(dst->self_max, src->self_max, sizeof(uint32_t), hipMemcpyDeviceToDevice, dst->stream));
+  if (src->voters) HIPCHK(dst, hipMemcpyAsync(dst->voters, src->voters, ld * sizeof(uint16_t), hipMemcpyDeviceToDevice, dst->stream));
   HIPCHK(dst, hipStreamSynchronize(dst->stream));
   dst->have_terms = src->have_terms;
   dense_changed(dst);

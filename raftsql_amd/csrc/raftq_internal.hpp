@@ -22,6 +22,9 @@ struct raftq {
   int cur = 0;
   uint64_t* first_idx = nullptr;
   uint8_t* votes = nullptr;
+  // per-group voter masks (raftq_load_voters / raftq_apply_voter_deltas): u16 [ld], bit p = slot p votes in the group; nullptr =
+  // none loaded: every slot votes in every group and the sweeps are the unmasked kernels
+  uint16_t* voters = nullptr;
   uint8_t* outcome = nullptr;
   uint64_t* changed_bits = nullptr;
   uint4* partials = nullptr;
@@ -264,6 +267,8 @@ int node_arrays_of(raftq_t* h, raftqk::NodeArrays* out);
 int fail(raftq_t* h, int code, const std::string& msg);
 int use_device(raftq_t* h);
 int use_device_idle(raftq_t* h, const char* who);  // + no Step batch in flight (RAFTQ_ESTATE otherwise)
+// Step's maybeCommit / poll on the device count every slot: RAFTQ_ESTATE for a handle with voter masks loaded (include/raftq.h)
+int refuse_voters(raftq_t* h, const char* who);
 int self_max_check(raftq_t* h);                 // the self-max word re-derived from the rows for h->self_peer (enqueued)
 int ensure_staging(raftq_t* h, size_t bytes);   // pinned, device-mapped staging (term deltas, campaign lists, log deltas)
 bool host_can_write(void* p, size_t bytes);     // [p, p + bytes) is mapped writable into this process (/proc/self/maps)

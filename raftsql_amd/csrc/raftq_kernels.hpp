@@ -20,6 +20,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <utility>
+
 namespace raftqk {
 
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
@@ -1145,6 +1147,203 @@ static __global__ __launch_bounds__(kBlock) void raise_flag_segments_kernel(uint
     for (int k = 0; k < kWaves; ++k) total += red[k];
     __hip_atomic_store(flag, ((uint64_t)epoch << 32) | total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
+}
+
+// ---------------------------------------------------------------------------
+// Per-group voter sets (raftq_load_voters / raftq_apply_voter_deltas; raft.go:84-86, 148-164): voters[g] is a 16-bit mask,
+// bit p = peer slot p votes in group g.  n_g = popcount, q_g = n_g / 2 + 1, and both decisions run over the voters only:
+//   mci     = the q_g-th largest match[p][g] over the voters          outcome = poll over the voters' fields of the vote word
+// A handle with no masks never launches this kernel (raftq_capi.hip sweep_on); the kernels above are not touched by it.
+//
+// Selection: a non-voter's value is replaced by 0 and the FULL network of N inputs sorts the N values (descending); element
+// q_g - 1 of that order is the answer.  Match values are >= 0, so the n_g largest of the N values include every voter's
+// value, and position q_g - 1 < n_g (n_g >= 1) is the voters' q_g-th largest, ties included; an empty mask (an unused group
+// slot; etcd has no such state) leaves N zeros: the candidate is 0, nothing commits.  Which element is a per-group value,
+// so every output of the network stays live, and it is taken with a chain of selects over the N registers: a register
+// array indexed at run time would live in scratch.  All N rows are read: the self-max row skip (SweepArgs::self_max) does
+// not apply, because the self slot need not be a voter.
+struct VoterSweepArgs {
+  SweepArgs s;
+  const uint16_t* voters;  // [ld], padding groups hold 0
+};
+
+// a select between two VALUES.  `c ? v[i] : r` written in place reads v[i] on one arm only; the compiler turns that into a
+// read through a selected address, which keeps the whole array in scratch (64-80 bytes per lane for N >= 6).
+__device__ __forceinline__ uint64_t sel_u64(bool c, uint64_t a, uint64_t b) { return c ? a : b; }
+
+// v[] is in descending order: -> v[idx], idx < N, by a chain of selects over the N registers (a fold over constant
+// indices: a register array indexed at run time would live in scratch)
+template <int N, int... I>
+__device__ __forceinline__ uint64_t pick_sorted(const uint64_t (&v)[N], uint32_t idx, std::integer_sequence<int, I...>) {
+  uint64_t r = v[0];
+  ((r = sel_u64(idx == (uint32_t)(I + 1), v[I + 1], r)), ...);
+  return r;
+}
+template <int N, int... I>
+__device__ __forceinline__ void zero_non_voters(uint64_t (&v)[N], uint32_t mask, std::integer_sequence<int, I...>) {
+  ((v[I] = sel_u64(((mask >> I) & 1u) != 0, v[I], 0ull)), ...);
+}
+
+// raft.maybeCommit's candidate of one group over its voters: v[] are the N match values, mask the group's voters
+template <int N>
+__device__ __forceinline__ uint64_t select_quorum_voters(uint64_t (&v)[N], uint32_t mask) {
+  zero_non_voters<N>(v, mask, std::make_integer_sequence<int, N>{});
+  if constexpr (N >= 2) (void)select_quorum_network<N>(v);  // the whole network: v[] ends sorted
+  return pick_sorted<N>(v, (uint32_t)__popc(mask) >> 1, std::make_integer_sequence<int, N - 1>{});  // q_g - 1 = n_g / 2
+}
+
+// the mask's bits 0..15 moved to the even bit positions 0, 2, .. 30: poll_word's kLow of this group
+__device__ __forceinline__ uint32_t spread_even(uint32_t m) {
+  m = (m | (m << 8)) & 0x00ff00ffu;
+  m = (m | (m << 4)) & 0x0f0f0f0fu;
+  m = (m | (m << 2)) & 0x33333333u;
+  return (m | (m << 1)) & 0x55555555u;
+}
+
+// raft.poll over the voters' fields of one group's vote word -> 2-bit outcome (0 pending, 1 won, 2 lost)
+__device__ __forceinline__ uint32_t poll_word_voters(uint32_t w, uint32_t mask) {
+  const uint32_t low = spread_even(mask);
+  const uint32_t q = ((uint32_t)__popc(mask) >> 1) + 1u;
+  const uint32_t granted = __popc(w & ~(w >> 1) & low);
+  const uint32_t rejected = __popc((w >> 1) & ~w & low);
+  const uint32_t won = granted >= q ? 1u : 0u;
+  const uint32_t lost = (won == 0u && rejected >= q) ? 2u : 0u;
+  return won | lost;
+}
+
+// One handle per launch, blockIdx.x = tile; tile and lane shape, loads and every output (shadow commit buffer, 2-bit
+// outcomes, lane-ordered changed bitmap, per-wave partials) as sweep_kernel's, so the compaction, the counts and the turn's
+// flag work behind either.  Masks: the commit part's lane loads the two masks of its pair {g, g+1} as one dword per round
+// (256 B per wave instruction), the vote part's lane the eight masks of its eight groups as one 16-byte load; they are
+// issued with the tile's other loads, before the first compare.
+template <int N, int GPL, bool COMMIT, bool GATED, bool VOTES, int POLICY>
+static __global__ __launch_bounds__(kBlock) void sweep_voters_kernel(VoterSweepArgs va) {
+  constexpr bool NT = (POLICY & kLdNT) != 0;
+  constexpr bool STNT = (POLICY & kStNT) != 0;
+  constexpr int kTile = kBlock * GPL;
+  constexpr int kRounds = GPL / 2;
+  constexpr int kVoteLanes = kTile / 8;
+  const SweepArgs& a = va.s;
+  const uint32_t tid = threadIdx.x, tile = blockIdx.x;
+  const uint64_t tile0 = (uint64_t)tile * kTile;
+  const bool vote_lane = VOTES && tid < kVoteLanes;  // wave-uniform (kVoteLanes % 64 == 0)
+
+  TileRegs<N, GPL, COMMIT, GATED, VOTES> r;
+  u32x4p vmask;                          // the 8 masks of the vote lane's 8 groups
+  uint32_t cmask[COMMIT ? kRounds : 1];  // the 2 masks of the lane's pair, per round
+  if constexpr (VOTES) {
+    if (vote_lane) vmask = ldg<NT>(reinterpret_cast<const u32x4p*>(va.voters + tile0 + 8ull * tid));
+  }
+  tile_load<N, GPL, COMMIT, GATED, VOTES, POLICY>(r, a, tile);  // every row: r.skip stays 0
+  if constexpr (COMMIT) {
+#pragma unroll
+    for (int j = 0; j < kRounds; ++j) {
+      const uint64_t g = tile0 + (uint64_t)(tid >> 6) * (64 * GPL) + (uint64_t)j * 128 + 2 * (tid & 63);
+      cmask[j] = ldg<NT>(reinterpret_cast<const uint32_t*>(va.voters + g));
+    }
+  }
+
+  uint32_t n_changed = 0;  // wave-uniform
+  uint32_t won_lost = 0;   // per lane: won | lost << 16
+  if constexpr (COMMIT) {
+#pragma unroll
+    for (int j = 0; j < kRounds; ++j) {
+      const uint64_t g = tile0 + (uint64_t)(tid >> 6) * (64 * GPL) + (uint64_t)j * 128 + 2 * (tid & 63);
+      uint64_t v0[N], v1[N];
+#pragma unroll
+      for (int p = 0; p < N; ++p) {
+        v0[p] = r.m[j][p].x;
+        v1[p] = r.m[j][p].y;
+      }
+      const uint64_t mci0 = select_quorum_voters<N>(v0, cmask[j] & 0xffffu);
+      const uint64_t mci1 = select_quorum_voters<N>(v1, cmask[j] >> 16);
+      u64x2 o;
+      o.x = maybe_commit<GATED>(mci0, r.c[j].x, GATED ? r.f[j].x : 0);
+      o.y = maybe_commit<GATED>(mci1, r.c[j].y, GATED ? r.f[j].y : 0);
+      const uint64_t b0 = __ballot(o.x != r.c[j].x);
+      const uint64_t b1 = __ballot(o.y != r.c[j].y);
+      n_changed += __popcll(b0) + __popcll(b1);
+      if (a.changed_bits != nullptr && (tid & 63) == 0) {  // word 2k = even groups, 2k+1 = odd groups of the k-th 128-group run
+        u64x2 w;
+        w.x = b0;
+        w.y = b1;
+        stg<false>(reinterpret_cast<u64x2*>(a.changed_bits + (g >> 6)), w);
+      }
+      stg<STNT>(reinterpret_cast<u64x2*>(a.committed_out + g), o);
+    }
+  }
+
+  if constexpr (VOTES) {
+    if (vote_lane) {
+      const uint64_t g = tile0 + 8ull * tid;
+      uint32_t out = 0, n_won = 0, n_lost = 0;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        uint32_t w;
+        if constexpr (N <= 8) {
+          const uint32_t pair = k < 2 ? r.vw[0].x : k < 4 ? r.vw[0].y : k < 6 ? r.vw[0].z : r.vw[0].w;
+          w = (k & 1) ? pair >> 16 : pair & 0xffffu;
+        } else {
+          w = k == 0 ? r.vw[0].x : k == 1 ? r.vw[0].y : k == 2 ? r.vw[0].z : k == 3 ? r.vw[0].w
+            : k == 4 ? r.vw[1].x : k == 5 ? r.vw[1].y : k == 6 ? r.vw[1].z : r.vw[1].w;
+        }
+        const uint32_t mpair = k < 2 ? vmask.x : k < 4 ? vmask.y : k < 6 ? vmask.z : vmask.w;
+        const uint32_t oc = poll_word_voters(w, (k & 1) ? mpair >> 16 : mpair & 0xffffu);
+        out |= oc << (2 * k);
+        n_won += oc & 1u;
+        n_lost += oc >> 1;
+      }
+      stg<STNT>(reinterpret_cast<uint16_t*>(a.outcome + (g >> 2)), (uint16_t)out);  // 8 groups = 16 bits
+      won_lost = n_won | (n_lost << 16);
+    }
+  }
+
+  const uint32_t wl = VOTES ? wave_sum_u32(won_lost) : 0u;
+  if ((tid & 63) == 0) {
+    uint4 t;
+    t.x = n_changed;
+    t.y = wl & 0xffffu;
+    t.z = wl >> 16;
+    t.w = 0;
+    stg_u4(a.partials + ((uint64_t)tile * kWaves + (tid >> 6)), t);
+  }
+}
+
+// "every slot votes" written out, for a handle whose first masks arrive as deltas: groups [0, n_groups) get `full`
+static __global__ __launch_bounds__(kBlock) void fill_voters_kernel(uint16_t* voters, uint64_t n_groups, uint16_t full) {
+  const uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (g < n_groups) voters[g] = full;
+}
+
+// A conf change applied (raft.go:84-86: the entries publishEntries passes by; upstream's ApplyConfChange): one thread per
+// record, records unique per group within a batch (the host keeps the last of a group).  The group's mask is replaced; for
+// every bit of `reset` the slot's Match is zeroed and its field of the group's vote word cleared -- a slot reused for a new
+// replica must not inherit its predecessor's Match, and deltas only ever raise it.  A zeroed entry of the self row may end
+// the self-max fact: a batch that resets anything clears the word (always safe; the next full check restores it).
+struct VoterDeltaRec {  // == raftq_voter_delta_t
+  uint64_t group;
+  uint16_t voters, reset;
+  uint32_t pad;
+};
+static __global__ __launch_bounds__(kBlock) void apply_voter_deltas_kernel(uint16_t* voters, uint64_t* match, uint64_t ld, uint8_t* votes,
+                                                                           int wide, uint32_t n_peers, const VoterDeltaRec* __restrict__ d,
+                                                                           uint64_t n, uint32_t* self_max) {
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  bool resets = false;
+  if (i < n) {
+    const VoterDeltaRec r = d[i];
+    voters[r.group] = r.voters;
+    resets = r.reset != 0;
+    if (resets) {
+      const uint32_t fields = spread_even(r.reset) * 3u;  // both bits of every reset slot's field
+      for (uint32_t p = 0; p < n_peers; ++p)
+        if ((r.reset >> p) & 1u) match[(uint64_t)p * ld + r.group] = 0ull;
+      // the group's word is this thread's alone: one record per group, and a 16-bit word is stored as 16 bits
+      if (wide) reinterpret_cast<uint32_t*>(votes)[r.group] &= ~fields;
+      else reinterpret_cast<uint16_t*>(votes)[r.group] &= (uint16_t)~fields;
+    }
+  }
+  clear_self_max_if(resets, self_max);
 }
 
 // ---------------------------------------------------------------------------

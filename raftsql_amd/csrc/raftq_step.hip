@@ -97,6 +97,7 @@ int ensure_mirror(raftq_t* h) {
 
 }  // namespace
 int raftq_detail::node_arrays_of(raftq_t* h, raftqk::NodeArrays* out) {
+  if (int rc = raftq_detail::refuse_voters(h, "raftq_propose_frames")) return rc;
   if (int rc = ensure_node_state(h)) return rc;
   if (int rc = ensure_mirror(h)) return rc;
   *out = node_arrays(h);
@@ -491,6 +492,7 @@ static int submit_impl(raftq_t* h, const void* msgs, uint64_t n, const WireSrc* 
                        size_t rec_bytes = sizeof(raftq_msg_t)) {
   const bool packed = rec_bytes != sizeof(raftq_msg_t);
   if (int rc = use_device(h)) return rc;
+  if (int rc = raftq_detail::refuse_voters(h, who)) return rc;
   if (n == 0 || (!wire && !msgs)) return fail(h, RAFTQ_EINVAL, std::string(who) + ": empty batch");
   if (n > 0x7ffffffeull) return fail(h, RAFTQ_EINVAL, std::string(who) + ": batch too large (2^31 - 2 messages at most)");
   if (wire && ((!wire->stream && wire->nbytes) || !wire->frame_off))
@@ -1019,6 +1021,7 @@ int raftq_step_frames_respond(raftq_t* h, const void* stream, uint64_t nbytes, c
 // wait = false (raftq_apply_log_deltas_nowait): the same kernels from a staging area of their own, enqueued and left
 static int log_deltas_impl(raftq_t* h, const raftq_log_delta_t* d, uint64_t n, uint64_t* committed_out, bool wait) {
   if (int rc = raftq_detail::use_device_idle(h, wait ? "raftq_apply_log_deltas" : "raftq_apply_log_deltas_nowait")) return rc;
+  if (int rc = raftq_detail::refuse_voters(h, wait ? "raftq_apply_log_deltas" : "raftq_apply_log_deltas_nowait")) return rc;
   if (n == 0) return RAFTQ_OK;
   if (!d) return fail(h, RAFTQ_EINVAL, "raftq_apply_log_deltas: null argument");
   for (uint64_t i = 0; i < n; ++i)

@@ -174,6 +174,39 @@ class QuorumEngine:
         a["group"], a["cur_term"], a["first_idx"] = group, cur_term, first_idx_cur_term
         self._chk(self._lib.raftq_apply_term_deltas(self._h, _ptr(a) if len(a) else None, len(a)))
 
+    # -- per-group voter sets (raftq_load_voters / raftq_apply_voter_deltas / raftq_read_voters) ------------
+    _VOTER_DELTA_DT = np.dtype([("group", "<u8"), ("voters", "<u2"), ("reset", "<u2"), ("_pad", "<u4")])
+
+    def load_voters(self, voters: Optional[np.ndarray]) -> None:
+        """voters[g]: bit p set = peer slot p votes in group g.  None drops the masks (every slot votes: the unmasked kernels)."""
+        if voters is None:
+            self._chk(self._lib.raftq_load_voters(self._h, None))
+            return
+        v = np.ascontiguousarray(voters, dtype=np.uint16)
+        if v.shape != (self.n_groups,):
+            raise ValueError("voters must be [G]")
+        self._chk(self._lib.raftq_load_voters(self._h, _ptr(v)))
+
+    @classmethod
+    def pack_voter_deltas(cls, group, voters, reset=0) -> np.ndarray:
+        """AoS array layout-identical to raftq_voter_delta_t[]: the group's new mask and the slots to reset."""
+        a = np.zeros(len(group), dtype=cls._VOTER_DELTA_DT)
+        a["group"], a["voters"], a["reset"] = group, voters, reset
+        return a
+
+    def apply_voter_deltas(self, deltas: np.ndarray) -> None:
+        """Conf changes applied (pack_voter_deltas): the last record of a group wins; all-or-nothing on a bad record."""
+        n = len(deltas)
+        if n:
+            assert deltas.dtype == self._VOTER_DELTA_DT and deltas.flags.c_contiguous
+        self._chk(self._lib.raftq_apply_voter_deltas(self._h, _ptr(deltas) if n else None, n))
+
+    def read_voters(self) -> np.ndarray:
+        """-> voters [G] u16; (1 << N) - 1 everywhere when no masks are loaded"""
+        out = np.empty(self.n_groups, dtype=np.uint16)
+        self._chk(self._lib.raftq_read_voters(self._h, _ptr(out)))
+        return out
+
     _DELTA_DT = np.dtype([("group", "<u8"), ("match", "<u8"), ("peer", "<u4"), ("_pad", "<u4")])
     _VDELTA_DT = np.dtype([("group", "<u8"), ("peer", "<u4"), ("vote", "u1"), ("_pad", "u1", (3,))])
     _ADV_DT = np.dtype([("group", "<u8"), ("old_commit", "<u8"), ("new_commit", "<u8")])

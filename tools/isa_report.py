@@ -2,7 +2,8 @@
 """Per-kernel resource usage of the sweep kernels as compiled for gfx950 (VGPR / SGPR / scratch / LDS / occupancy),
 with the toolchain and the exact command line -- the tracked evidence behind DESIGN.md's ISA claims.
 
-usage: tools/isa_report.py [out.txt]      (default profiles/r02/isa_sweep.txt)
+usage: tools/isa_report.py [out.txt [kernel-regex]]      (default profiles/r02/isa_sweep.txt, the sweep / ingest / tick kernels;
+                                                          e.g. `profiles/r09/isa_voters.txt "raftqk::.*voters"` for the masked sweep)
 Compiles raftsql_amd/csrc/raftq_capi.hip (device side) with -Rpass-analysis=kernel-resource-usage; no GPU needed.
 """
 import os
@@ -13,6 +14,19 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from raftsql_amd import build as b  # noqa: E402
+
+
+def shown_command(cmd):
+    """The command line as the report prints it: the compiler by name and the tree's files relative to its root, so
+    the same tree gives the same line wherever it is checked out."""
+    shown = [os.path.basename(cmd[0])]
+    for a in cmd[1:]:
+        for pre in ("-I", ""):
+            if a.startswith(pre + ROOT + os.sep):
+                a = pre + os.path.relpath(a[len(pre):], ROOT)
+                break
+        shown.append(a)
+    return " ".join(shown)
 
 
 def main():
@@ -38,12 +52,14 @@ def main():
     tc = b.toolchain()
     head = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
     dirty = subprocess.run(["git", "-C", ROOT, "status", "--porcelain", "raftsql_amd/csrc"], capture_output=True, text=True).stdout.strip()
-    lines = ["# gfx950 resource usage of the sweep kernels (raftq_capi.hip), from -Rpass-analysis=kernel-resource-usage",
+    lines = ["# gfx950 resource usage of the %s (raftq_capi.hip), from -Rpass-analysis=kernel-resource-usage" % ("kernels matching /%s/" % sys.argv[2] if len(sys.argv) > 2 else "sweep kernels"),
              "# tree: %s%s" % (head, " + uncommitted changes under raftsql_amd/csrc" if dirty else ""),
-             "# " + " | ".join(tc["version"][:2]), "# " + " ".join(cmd), "#",
+             "# " + " | ".join(tc["version"][:2]), "# " + shown_command(cmd), "#",
              "# %-6s %-6s %-6s %-8s %-5s %-4s kernel" % ("VGPR", "AGPR", "SGPR", "scratch", "LDS", "occ")]
     want = re.compile(r"raftqk::(sweep_kernel|sweep_set_kernel|sweep_persist_kernel|sweep_lds_kernel|set_counts_kernel|sweep_segments_kernel|tick_set_wide_kernel|tick_set_kernel|tick_lists32_kernel|"
                       r"deltas_in|apply_deltas|scan_partials|compact_changed|tick_kernel)")
+    if len(sys.argv) > 2:
+        want = re.compile(sys.argv[2])
     rows = []
     for k, n in zip(kernels, names):
         if not want.search(n):
