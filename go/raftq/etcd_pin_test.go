@@ -108,6 +108,19 @@ func TestStepAgainstEtcd(t *testing.T) {
 				if !raft.IsEmptyHardState(rd.HardState) {
 					st.SetHardState(rd.HardState)
 				}
+				for _, m := range rd.Messages { // the rule raftq_tick_frames restates: a heartbeat's Commit is min(Progress[to].Match, committed)
+					if m.Type != pb.MsgHeartbeat {
+						continue
+					}
+					s := rn.Status()
+					want := s.Commit
+					if mt := s.Progress[m.To].Match; mt < want {
+						want = mt
+					}
+					if m.Commit != want {
+						t.Fatalf("N=%d: MsgHeartbeat to %d carries Commit %d, want min(Match %d, committed %d)", n, m.To, m.Commit, s.Progress[m.To].Match, s.Commit)
+					}
+				}
 				rn.Advance(rd)
 			}
 		}
@@ -170,6 +183,8 @@ func TestStepAgainstEtcd(t *testing.T) {
 			default:
 				step(pb.Message{Type: pb.MsgAppResp, From: p, To: 1, Term: term, Index: uint64(rng.Int63n(int64(last) + 1))}, "MsgAppResp")
 			}
+			rn.Tick() // HeartbeatTick 1: the leader's bcastHeartbeat, checked in drain
+			drain()
 		}
 		if n > 1 { // a candidate of a higher term with an up-to-date log deposes the leader and gets the vote
 			step(pb.Message{Type: pb.MsgVote, From: 2, To: 1, Term: term + 5, LogTerm: term + 1, Index: last + 10}, "MsgVote(higher term)")

@@ -387,6 +387,51 @@ func (e *Engine) StepFramesRespond(stream []byte, frameOff []uint64, tailAppends
 	return uint64(c.n_ents), uint64(rcnt.n_msgs), uint64(rcnt.bytes), e.err(rc)
 }
 
+// TickFrames is TickCollectLists plus the heartbeat round the Tick calls for, built and marshalled on the device
+// (raftq_tick_frames; raft.go:223-224 -> :230: rc.node.Tick -> tickHeartbeat -> Step(MsgBeat) -> bcastHeartbeat ->
+// rc.transport.Send): for each of the first min(NBeat, beatCap) MsgBeat groups, ascending, and every peer slot p != self one
+// MsgHeartbeat{Term, Commit: min(Match[p], committed)}.  out receives rafthttp frames, peer-major: peerOff[p] .. peerOff[p+1]
+// (len Peers + 1) are peer p's frames in ascending group order, frameOff (nil, or len >= beatCap*(Peers-1)+1) their byte offsets.
+// Groups beyond beatCap are the caller's (they are in the bitmap or the list).  len(out) must be at least
+// beatCap*(Peers-1)*RespondFrameMax; out, frameOff and peerOff must be page-locked (HostAlloc).  A refused call has not ticked.
+func (e *Engine) TickFrames(flags uint, hupCap, beatCap uint64, out []byte, frameOff, peerOff []uint64) (t TickLists, nFrames, nBytes uint64, err error) {
+	if uint64(len(peerOff)) < uint64(e.Peers)+1 {
+		return TickLists{}, 0, 0, fmt.Errorf("raftq: TickFrames: peerOff has %d words, needs Peers + 1 = %d", len(peerOff), e.Peers+1)
+	}
+	if frameOff != nil && uint64(len(frameOff)) < beatCap*uint64(e.Peers-1)+1 {
+		return TickLists{}, 0, 0, fmt.Errorf("raftq: TickFrames: frameOff has %d words, needs beatCap * (Peers - 1) + 1 = %d", len(frameOff),
+			beatCap*uint64(e.Peers-1)+1)
+	}
+	var pf *C.uint64_t
+	if len(frameOff) > 0 {
+		pf = (*C.uint64_t)(unsafe.Pointer(&frameOff[0]))
+	}
+	var nh, nb C.uint64_t
+	var c C.raftq_wire_counts_t
+	rc := C.raftq_tick_frames(e.h, C.uint(flags), C.uint64_t(hupCap), C.uint64_t(beatCap), &nh, &nb, bytesPtr(out), C.uint64_t(len(out)), pf,
+		(*C.uint64_t)(unsafe.Pointer(&peerOff[0])), &c)
+	if err := e.err(rc); err != nil {
+		return TickLists{}, 0, 0, err
+	}
+	var ph, pb *C.uint32_t
+	var pm *C.uint64_t
+	var lh, lb, lm C.uint64_t
+	if err := e.err(C.raftq_last_tick_lists(e.h, &ph, &lh, &pb, &lb, &pm, &lm)); err != nil {
+		return TickLists{}, 0, 0, err
+	}
+	t = TickLists{NHup: uint64(nh), NBeat: uint64(nb)}
+	if lh > 0 {
+		t.Hups = unsafe.Slice((*uint32)(unsafe.Pointer(ph)), int(lh))
+	}
+	if lb > 0 {
+		t.Beats = unsafe.Slice((*uint32)(unsafe.Pointer(pb)), int(lb))
+	}
+	if lm > 0 {
+		t.BeatBitmap = unsafe.Slice((*uint64)(unsafe.Pointer(pm)), int(lm))
+	}
+	return t, uint64(c.n_msgs), uint64(c.bytes), nil
+}
+
 // OutfAnswered / RespondFrameMax: RAFTQ_OUTF_ANSWERED, RAFTQ_RESPOND_FRAME_MAX (include/raftq_wire.h)
 const (
 	OutfAnswered    = 0x10

@@ -100,7 +100,14 @@ typedef struct raftq_node_stats {
   uint64_t frames_dropped;    /* inbound frames that did not parse / were not for this node */
   uint64_t wal_records;       /* walpb.Records produced (raftq_node_wal_enable) */
   uint64_t msgs_built_on_device; /* of msgs_sent: MsgApps of proposals that raftq_propose_frames built in HBM (round 6), and with
-                                  * RAFTQ_NODE_RESPOND_DEVICE=1 the responses / commit broadcasts raftq_step_frames_respond built */
+                                  * RAFTQ_NODE_RESPOND_DEVICE=1 the responses / commit broadcasts raftq_step_frames_respond built;
+                                  * with RAFTQ_NODE_BEAT_DEVICE=1 the heartbeats raftq_tick_frames built.  Both switches are read
+                                  * from the environment at raftq_node_create and are off by default.  RAFTQ_NODE_BEAT_DEVICE=1:
+                                  * every tick of a turn is raftq_tick_frames (raftq_wire.h) with beat_cap = the number of groups
+                                  * this node leads, rounded up; the per-peer slices go onto the peer queues ahead of everything
+                                  * else the turn sends, after the turn's WAL bytes; a MsgBeat group beyond beat_cap gets its
+                                  * heartbeats from the host as before.  Per peer the stream is the host path's, frame for frame
+                                  * (unless RAFTQ_NODE_RESPOND_DEVICE=1 moves its answers in front of such a group's heartbeats). */
 } raftq_node_stats_t;
 
 int raftq_node_create(int device, uint64_t n_groups, uint32_t n_peers, uint32_t self_peer, raftq_node_t** out);

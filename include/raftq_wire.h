@@ -314,6 +314,39 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
                          uint64_t pool_bytes, void* out, uint64_t cap, uint64_t* frame_off /*[n_msgs + (N-1) n_props + 1]|NULL*/,
                          raftq_wire_counts_t* counts /*|NULL*/);
 
+/* A node's heartbeat round (raft.go:223-224 -> :230: rc.node.Tick() -> tickHeartbeat -> Step(MsgBeat) -> bcastHeartbeat ->
+ * rc.transport.Send) as ONE submission with one wait: the Tick, its lists, and the heartbeats the Tick calls for, built and
+ * marshalled on the device.
+ *
+ * The Tick is exactly raftq_tick_collect_lists(h, flags, hup_cap, beat_cap, n_hup, n_beat) (raftq.h): the timers, the action bytes,
+ * the counts -- *n_hup and *n_beat are the totals -- and what raftq_last_tick_lists hands out afterwards, the MsgHup ids and the
+ * MsgBeat ids or, with RAFTQ_TICK_BEAT_BITMAP, the bitmap.
+ *
+ * The heartbeats: let n_built = min(*n_beat, beat_cap) -- beat_cap counts here with the bitmap flag too, as the bound on what
+ * is built.  For each of the first n_built MsgBeat groups g, ascending, and every peer slot p != self (raftq_set_self), one frame
+ *   MsgHeartbeat{to = p, from = self, group = g, term = Term(g), commit = min(match[p][g], committed(g))}, every other field zero
+ * -- etcd's bcastHeartbeat / sendHeartbeat, `commit := min(r.prs[to].Match, r.raftLog.committed)` -- from the group's state as it
+ * stands after this Tick (Step(MsgBeat) changes none of it).  Groups beyond beat_cap are the caller's: it finds them in the
+ * bitmap or the list and sends for them itself.
+ *
+ * out: rafthttp stream frames, peer-major -- for every p != self, ascending, the n_built frames to p in ascending group order.
+ * peer_off[p] .. peer_off[p + 1] are frame indices (N + 1 words; self's slice is empty, peer_off[N] = n_built * (N - 1));
+ * frame_off (NULL, or room for beat_cap * (N - 1) + 1 words) gets byte offsets into out as raftq_wire_encode's, the entries past
+ * the last frame all holding the total.  counts: n_msgs = n_built * (N - 1), bytes.  Byte for byte what raftq_wire_encode makes
+ * of the same raftq_wire_msg_t records built on the host; the records are written into the encoder's input in HBM and never exist
+ * in host memory.
+ *
+ * Refused before anything is enqueued -- a refused call has not ticked:
+ *   RAFTQ_EINVAL  cap < beat_cap * (N - 1) * RAFTQ_RESPOND_FRAME_MAX (the largest payload-free frame, above);
+ *                 out, frame_off or peer_off not page-locked and 16-byte aligned; N < 2; an unknown flag;
+ *                 beat_cap * (N - 1) >= 2^31, or beat_cap * (N - 1) * RAFTQ_RESPOND_FRAME_MAX beyond 2^31 bytes
+ *   RAFTQ_ESTATE  a Step batch in flight; no node state on the handle (neither raftq_set_self nor raftq_load_node was ever
+ *                 called); voter masks loaded (the round goes to every slot, not to the group's own membership)
+ * Every allocation is made before the tick kernel is enqueued (the rule raftq_tick_collect_lists follows). */
+int raftq_tick_frames(raftq_t* h, unsigned flags, uint64_t hup_cap, uint64_t beat_cap, uint64_t* n_hup, uint64_t* n_beat,
+                      void* out, uint64_t cap, uint64_t* frame_off /*[beat_cap*(N-1)+1] | NULL*/, uint64_t* peer_off /*[N+1]*/,
+                      raftq_wire_counts_t* counts /*| NULL*/);
+
 /* ---- WAL ------------------------------------------------------------------------------------ */
 
 /* walpb record types (wal/wal.go) */

@@ -1249,14 +1249,16 @@ int raftq_tick_collect(raftq_t* h, uint64_t* hups, uint64_t hup_cap, uint64_t* n
   return RAFTQ_OK;
 }
 
+}  // extern "C"
+
 // Tick + both lists as they are meant to be read: 4-byte group ids LEFT IN PLACE in page-locked memory
 // (raftq_last_tick_lists: no copy into caller arrays -- 110 of the 172 us raftq_tick_collect took at 1M groups / 400K entries),
 // the MsgBeat groups as a group-order bitmap when the caller asks for it (RAFTQ_TICK_BEAT_BITMAP), and the wait on the turn's
 // completion word instead of a stream synchronisation.  Three launches (tick, lists, flag), one wait.
-int raftq_tick_collect_lists(raftq_t* h, unsigned flags, uint64_t hup_cap, uint64_t beat_cap, uint64_t* n_hup, uint64_t* n_beat) {
-  if (int rc = use_device_idle(h, "raftq_tick_collect_lists")) return rc;
-  if (!n_hup || !n_beat) return fail(h, RAFTQ_EINVAL, "raftq_tick_collect_lists: null count");
-  if (flags & ~RAFTQ_TICK_BEAT_BITMAP) return fail(h, RAFTQ_EINVAL, "raftq_tick_collect_lists: unknown flag");
+// In three steps (raftq_detail::tick_lists_*, raftq_internal.hpp), so that raftq_tick_frames (raftq_wire.hip) can put its own
+// kernels between the lists and the flag: what is checked and allocated, what is enqueued, the wait and what it leaves.
+int raftq_detail::tick_lists_prepare(raftq_t* h, const char* who, unsigned flags, uint64_t hup_cap, uint64_t beat_cap, TickLists* tl) {
+  if (flags & ~RAFTQ_TICK_BEAT_BITMAP) return fail(h, RAFTQ_EINVAL, std::string(who) + ": unknown flag");
   if (int rc = ensure_tick_state(h)) return rc;
   const bool bitmap = flags & RAFTQ_TICK_BEAT_BITMAP;
   const uint64_t cap_h = std::min<uint64_t>(hup_cap, h->G), cap_b = bitmap ? 0 : std::min<uint64_t>(beat_cap, h->G);
@@ -1278,9 +1280,16 @@ int raftq_tick_collect_lists(raftq_t* h, unsigned flags, uint64_t hup_cap, uint6
   }
   // every allocation is made BEFORE the Tick is enqueued: a call that fails has not ticked (an allocation failure
   // behind the tick kernel left the timers advanced and the MsgHup / MsgBeat groups of that tick unreported)
+  if (h->gpad / 256 > (1u << 14))
+    if (int rc = ensure_tick_offsets2(h, h->gpad / 256)) return rc;
+  *tl = TickLists{flags, cap_h, cap_b, beat_at, map_off, nullptr};
+  return RAFTQ_OK;
+}
+
+int raftq_detail::tick_lists_enqueue(raftq_t* h, TickLists* tl) {
+  const bool bitmap = tl->flags & RAFTQ_TICK_BEAT_BITMAP;
+  const uint64_t cap_h = tl->cap_h, cap_b = tl->cap_b;
   const uint64_t nw = h->gpad / 256;
-  if (nw > (1u << 14))
-    if (int rc = ensure_tick_offsets2(h, nw)) return rc;
   hipLaunchKernelGGL(tick_kernel, dim3((unsigned)(h->gpad / 1024)), dim3(kBlock), 0, h->stream, tick_args(h, h->tick_no++));
   h->ticked = true;
   const uint64_t *off_h = nullptr, *off_b = nullptr;
@@ -1290,17 +1299,13 @@ int raftq_tick_collect_lists(raftq_t* h, unsigned flags, uint64_t hup_cap, uint6
     off_h = h->offsets;
     off_b = h->tick_offsets2;
   }
+  tl->off_beat = off_b;
   uint32_t* const hup_d = h->tl_d;
-  uint32_t* const beat_d = h->tl_d + beat_at;
-  uint64_t* const map_d = (uint64_t*)((uint8_t*)h->tl_d + map_off);
+  uint32_t* const beat_d = h->tl_d + tl->beat_at;
+  uint64_t* const map_d = (uint64_t*)((uint8_t*)h->tl_d + tl->map_off);
   // one block of 1,024 groups per workgroup of the lists kernel.  Four (runs of ~1,600 ids instead of ~400 at the bench's density)
   // measured no better: 47.1 against 46.5 us a call -- 1.6 MB of ids take the link 34 us however they are cut
   const dim3 grid((unsigned)((nw + kWaves - 1) / kWaves));
-  // the completion word: a one-thread kernel behind the lists (only a kernel boundary orders eight XCDs' stores to host memory
-  // before it -- raftq_cycle's finding), polled by the host
-  uint64_t epoch = ++h->compact_epoch;
-  if ((uint32_t)epoch == 0) epoch = ++h->compact_epoch;
-  h->flag_mask = ~0ull;
   if (bitmap)
     hipLaunchKernelGGL((tick_lists32_kernel<true>), grid, dim3(kBlock), 0, h->stream, (const uint64_t*)h->hup_bits, (const uint64_t*)h->beat_bits,
                        (const uint4*)h->tick_partials, nw, hup_d, cap_h, beat_d, cap_b, map_d, h->d_total, off_h, off_b);
@@ -1308,6 +1313,17 @@ int raftq_tick_collect_lists(raftq_t* h, unsigned flags, uint64_t hup_cap, uint6
     hipLaunchKernelGGL((tick_lists32_kernel<false>), grid, dim3(kBlock), 0, h->stream, (const uint64_t*)h->hup_bits, (const uint64_t*)h->beat_bits,
                        (const uint4*)h->tick_partials, nw, hup_d, cap_h, beat_d, cap_b, map_d, h->d_total, off_h, off_b);
   HIPCHK(h, hipGetLastError());
+  return RAFTQ_OK;
+}
+
+int raftq_detail::tick_lists_finish(raftq_t* h, const char* who, const TickLists& tl, uint64_t* n_hup, uint64_t* n_beat) {
+  const bool bitmap = tl.flags & RAFTQ_TICK_BEAT_BITMAP;
+  const uint64_t cap_h = tl.cap_h, cap_b = tl.cap_b, beat_at = tl.beat_at, map_off = tl.map_off;
+  // the completion word: a one-thread kernel behind the lists (only a kernel boundary orders eight XCDs' stores to host memory
+  // before it -- raftq_cycle's finding), polled by the host
+  uint64_t epoch = ++h->compact_epoch;
+  if ((uint32_t)epoch == 0) epoch = ++h->compact_epoch;
+  h->flag_mask = ~0ull;
   hipLaunchKernelGGL(raise_flag_kernel, dim3(1), dim3(64), 0, h->stream, h->d_total + 3, epoch);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, wait_turn(h, epoch, 1));
@@ -1332,7 +1348,7 @@ int raftq_tick_collect_lists(raftq_t* h, unsigned flags, uint64_t hup_cap, uint6
     const uint64_t at_flag = digest();
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (digest() != at_flag)
-      return fail(h, RAFTQ_EHIP, "raftq_tick_collect_lists: the completion word arrived before the lists it announces (RAFTQ_CYCLE_CHECK)");
+      return fail(h, RAFTQ_EHIP, std::string(who) + ": the completion word arrived before the lists it announces (RAFTQ_CYCLE_CHECK)");
   }
   *n_hup = h->tl_n_hup = h->h_total[0];
   *n_beat = h->tl_n_beat = h->h_total[1];
@@ -1340,9 +1356,21 @@ int raftq_tick_collect_lists(raftq_t* h, unsigned flags, uint64_t hup_cap, uint6
   h->tl_beat_cap = cap_b;
   h->tl_beat_at = beat_at;
   h->tl_map_off = map_off;
-  h->tl_flags = flags;
+  h->tl_flags = tl.flags;
   h->tl_valid = true;
   return RAFTQ_OK;
+}
+
+extern "C" {
+
+int raftq_tick_collect_lists(raftq_t* h, unsigned flags, uint64_t hup_cap, uint64_t beat_cap, uint64_t* n_hup, uint64_t* n_beat) {
+  const char* who = "raftq_tick_collect_lists";
+  if (int rc = use_device_idle(h, who)) return rc;
+  if (!n_hup || !n_beat) return fail(h, RAFTQ_EINVAL, std::string(who) + ": null count");
+  raftq_detail::TickLists tl;
+  if (int rc = raftq_detail::tick_lists_prepare(h, who, flags, hup_cap, beat_cap, &tl)) return rc;
+  if (int rc = raftq_detail::tick_lists_enqueue(h, &tl)) return rc;
+  return raftq_detail::tick_lists_finish(h, who, tl, n_hup, n_beat);
 }
 
 int raftq_last_tick_lists(raftq_t* h, const uint32_t** hups, uint64_t* n_hups, const uint32_t** beats, uint64_t* n_beats,

@@ -116,6 +116,7 @@ struct raftq {
   const uint64_t* last_new = nullptr;
   // batched Step node state (raftq_step.hip), lazily allocated
   uint32_t self_peer = 0;
+  bool self_set = false;  // raftq_set_self has been called: the handle is a node's (raftq_tick_frames asks)
   // the records' copies of the dense arrays (role, committed, first_idx, match) are what those arrays hold: false after anything but
   // Step / tail reports / proposals wrote them; the next Step-family call re-reads them first (raftq_step.hip ensure_mirror)
   bool node_mirror_fresh = false;
@@ -305,6 +306,20 @@ int respond_prepare(raftq_t* h, const void* stream, uint64_t nbytes, const uint6
                     const uint64_t* at_tail, void* out, uint64_t cap, uint64_t* resp_off, uint64_t* peer_off, uint64_t n, RespPlan* p);
 int respond_enqueue(raftq_t* h, const RespPlan& p);
 int respond_finish(raftq_t* h, const RespPlan& p, ::raftq_wire_counts* resp_counts);
+// raftq_tick_collect_lists in three steps (raftq_capi.hip), for raftq_tick_frames (raftq_wire.hip), which puts its kernels between
+// the lists and the completion word: _prepare checks the flags and makes EVERY allocation of the Tick (a call that fails there has
+// not ticked); _enqueue launches the tick kernel, the scans of a large handle and the lists kernel; _finish raises the completion
+// word, waits for it and records what raftq_last_tick_lists hands out.  The caller has made sure no Step batch is in flight.
+struct TickLists {
+  unsigned flags;
+  uint64_t cap_h, cap_b, beat_at, map_off;  // the in-place lists' layout (raftq_t::tl_*)
+  const uint64_t* off_beat;                 // after _enqueue: scan_partials_kernel's MsgBeat offsets (more than 16K waves), or nullptr
+};
+int tick_lists_prepare(raftq_t* h, const char* who, unsigned flags, uint64_t hup_cap, uint64_t beat_cap, TickLists* tl);
+int tick_lists_enqueue(raftq_t* h, TickLists* tl);
+int tick_lists_finish(raftq_t* h, const char* who, const TickLists& tl, uint64_t* n_hup, uint64_t* n_beat);
+// raftq_step.hip, for raftq_tick_frames: the handle's records exist and are fresh (ensure_mirror), voter masks refused
+int node_records_of(raftq_t* h, const char* who, raftqk::NodeArrays* out);
 int respond_pass_ok(raftq_t* h);  // a pass of the marshal whose totals are about to be replaced (a stalled batch's first): it did not give up
 // The wait that ends a call whose results the kernels wrote into page-locked memory themselves (the streaming codecs,
 // raftq_step_frames): a one-thread kernel raises the handle's completion word behind everything enqueued so far and the host

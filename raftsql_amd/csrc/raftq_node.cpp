@@ -17,8 +17,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <memory>
+#include <mutex>
 #include <new>
 #include <string>
 #include <thread>
@@ -409,6 +409,21 @@ struct raftq_node {
   PinBuf resp_out;                       // the device-built frames of this turn's inbound round
   PinU64 resp_off, resp_peer;            // their byte offsets, peer slices ([N + 1] frame indices)
   bool resp_pending = false;             // resp_* hold frames not yet on the queues
+  // RAFTQ_NODE_BEAT_DEVICE=1 (off by default): every tick of a turn is raftq_tick_frames instead of raftq_tick_collect_lists -- the
+  // heartbeats of the first beat_cap MsgBeat groups are built and marshalled on the device, one BeatRound of frames per tick; the
+  // per-peer slices go onto the queues ahead of everything else the turn sends (the tick is the turn's first sender on the host
+  // path too), where and when the turn's frames are published.  beat_cap is the number of groups this node leads (n_leading),
+  // rounded up so that the rounds' buffers are not reallocated as it moves; groups beyond it get their heartbeats from
+  // bcast_heartbeat as before.  RAFTQ_NODE_BEAT_CAP=k (tests): beat_cap is never more than k.
+  bool beat_device = false;
+  struct BeatRound {
+    PinBuf out;         // the device-built frames of one tick
+    PinU64 off, peer;   // their byte offsets, peer slices ([N + 1] frame indices)
+  };
+  std::vector<std::unique_ptr<BeatRound>> beat_rounds;  // reused turn after turn; a turn usually ticks once
+  size_t beat_pending = 0;                // rounds of this turn whose frames are not on the queues yet
+  uint64_t beat_cap_limit = ~0ull;
+  uint64_t n_leading = 0;                 // groups with Group::leading set
   bool fuse_inbound = true;       // a turn's frames are decoded AND stepped by one submission (raftq_step_frames) whenever nothing was
                                   // raised locally ahead of them (RAFTQ_NODE_FUSE_INBOUND=0: raftq_wire_decode, then the staged rounds)
   bool broken = false;            // the engine's view of a log and the log itself disagree: advance() ends in ESTATE
@@ -850,6 +865,7 @@ void apply_result(raftq_node_t* n, const raftq_step_out_t& o, const raftq_wire_m
       wal_touch(n, gi, g);
     }
     if (o.flags & RAFTQ_OUTF_STEPPED_DOWN) {
+      n->n_leading -= g.leading ? 1 : 0;
       g.leading = false;
       n->tail_clear(gi);
     }
@@ -891,6 +907,7 @@ void apply_result(raftq_node_t* n, const raftq_step_out_t& o, const raftq_wire_m
         n->next_of(gi, p) = o.index;
         n->match_of(gi, p) = 0;
       }
+      n->n_leading += g.leading ? 0 : 1;
       g.leading = true;
       n->match_of(gi, n->self) = o.index;
       n->next_of(gi, n->self) = o.index + 1;
@@ -1008,6 +1025,21 @@ void publish_responses(raftq_node_t* n, uint32_t only) {
   if (only == ~0u || only == n->N - 1) n->resp_pending = false;
 }
 
+// the ticks' device-built heartbeats (raftq_tick_frames, RAFTQ_NODE_BEAT_DEVICE) onto peer p's queue, or every peer's (p = ~0u),
+// tick after tick; the last peer ends what is pending.  Called in front of publish_responses: a turn's heartbeats are its first sends.
+void publish_beats(raftq_node_t* n, uint32_t only) {
+  if (!n->beat_pending) return;
+  for (uint32_t p = 0; p < n->N; ++p) {
+    if (only != ~0u && p != only) continue;
+    for (size_t r = 0; r < n->beat_pending; ++r) {
+      raftq_node::BeatRound& br = *n->beat_rounds[r];
+      const uint64_t* po = br.peer.data();
+      append_frames(n->outbound[p], br.out.p, br.off.data(), po[p], po[p + 1]);
+    }
+  }
+  if (only == ~0u || only == n->N - 1) n->beat_pending = 0;
+}
+
 // rc.transport.Send(rd.Messages) (raft.go:230) for the whole turn: one batched marshal on the GPU, then
 // every peer's slice of the stream goes onto its queue -- behind the turn's WAL bytes (wal_end).
 int flush_outbound(raftq_node_t* n, std::unique_lock<std::mutex>& lk) {
@@ -1023,9 +1055,10 @@ int flush_outbound(raftq_node_t* n, std::unique_lock<std::mutex>& lk) {
   const size_t n_dev = n_props * (n->N - 1);
   cap += n_props ? n->prop_cap * (n->N - 1) : 0;
   if (nm + n_dev == 0) {
-    if (!n->resp_pending) return RAFTQ_OK;
-    // only device-built responses this turn: the WAL first, then the frames
+    if (!n->resp_pending && !n->beat_pending) return RAFTQ_OK;
+    // only device-built heartbeats / responses this turn: the WAL first, then the frames
     if (const int rc = wal_end(n, lk, raftq_node::kPhDevEncode)) return rc;
+    publish_beats(n, ~0u);
     publish_responses(n, ~0u);
     return RAFTQ_OK;
   }
@@ -1070,7 +1103,8 @@ int flush_outbound(raftq_node_t* n, std::unique_lock<std::mutex>& lk) {
   uint32_t run = 0;
   for (uint32_t p = 0; p < n->N; ++p) {
     PeerQueue& q = n->outbound[p];
-    publish_responses(n, p);  // the device-built answers of the inbound round come first
+    publish_beats(n, p);      // the ticks' device-built heartbeats come first, as on the host path
+    publish_responses(n, p);  // the device-built answers of the inbound round next
     append_frames(q, n->enc_out.p, n->enc_off.data(), first[p], first[p + 1]);
     if (n_props && p != n->self) {
       append_frames(q, n->enc_out.p, n->enc_off.data(), nm + (uint64_t)run * n_props, nm + (uint64_t)(run + 1) * n_props);
@@ -1297,6 +1331,25 @@ int take_inputs(Turn& t) {
 
 // -- rc.node.Tick() (raft.go:223-224) for every group: the engine advances the clocks and says
 // which groups' election timers fired (MsgHup -> through Step) and which leaders owe a heartbeat
+// One tick through raftq_tick_frames (RAFTQ_NODE_BEAT_DEVICE), with mu released: the Tick and its lists as raftq_tick_collect_lists
+// leaves them, and the heartbeats of the first *n_built MsgBeat groups in the turn's next BeatRound.
+int beat_round(raftq_node_t* n, uint64_t* n_hup, uint64_t* n_beat, uint64_t* n_built, uint64_t* n_frames) {
+  if (n->beat_pending == n->beat_rounds.size()) n->beat_rounds.emplace_back(new raftq_node::BeatRound());
+  raftq_node::BeatRound& br = *n->beat_rounds[n->beat_pending];
+  // the groups this node leads, rounded up (a node whose count moves a little keeps its buffers), never more than there are
+  const uint64_t cap = std::min(std::min<uint64_t>((n->n_leading + 1023) / 1024 * 1024, n->G), n->beat_cap_limit);
+  const uint64_t n_max = cap * (n->N - 1);
+  if (!br.out.reserve(std::max<uint64_t>(n_max * RAFTQ_RESPOND_FRAME_MAX, 16)) || !br.off.resize(n_max + 1) || !br.peer.resize(n->N + 1)) return RAFTQ_ENOMEM;
+  raftq_wire_counts_t cnt;
+  if (const int rc = raftq_tick_frames(n->h, RAFTQ_TICK_BEAT_BITMAP, n->tick_list.size(), cap, n_hup, n_beat, br.out.p, n_max * RAFTQ_RESPOND_FRAME_MAX,
+                                       br.off.data(), br.peer.data(), &cnt))
+    return rc;
+  *n_built = std::min(*n_beat, cap);
+  *n_frames = cnt.n_msgs;
+  if (cnt.n_msgs) ++n->beat_pending;  // onto the queues where the turn's frames are published (flush_outbound)
+  return RAFTQ_OK;
+}
+
 int tick(Turn& t) {
   raftq_node_t* n = t.n;
   std::vector<raftq_wire_msg_t>& local = n->local;
@@ -1304,6 +1357,7 @@ int tick(Turn& t) {
     local.push_back(local_msg(n, gi, RAFTQ_MSG_HUP));
   for (uint32_t k = 0; k < t.ticks; ++k) {
     uint64_t n_beat = 0, map_words = 0;
+    uint64_t n_built = 0, n_frames = 0;  // RAFTQ_NODE_BEAT_DEVICE: the first n_built MsgBeat groups' heartbeats are the device's, n_frames frames
     const uint64_t* beat_map = nullptr;
     {
       Unlocked u(t.lk);
@@ -1313,7 +1367,8 @@ int tick(Turn& t) {
       // (raftq_tick_collect_lists: 4-byte ids read where the device left them, the MsgBeat groups as a bitmap -- with
       // HeartbeatTick 1 the beat list is the set of groups this node leads, every tick)
       uint64_t n_hup = 0, n_listed = 0;
-      int rc = raftq_tick_collect_lists(n->h, RAFTQ_TICK_BEAT_BITMAP, n->tick_list.size(), 0, &n_hup, &n_beat);
+      int rc = n->beat_device ? beat_round(n, &n_hup, &n_beat, &n_built, &n_frames)
+                              : raftq_tick_collect_lists(n->h, RAFTQ_TICK_BEAT_BITMAP, n->tick_list.size(), 0, &n_hup, &n_beat);
       const uint32_t* hups = nullptr;
       if (rc == RAFTQ_OK) rc = raftq_last_tick_lists(n->h, &hups, &n_listed, nullptr, nullptr, &beat_map, &map_words);
       if (rc == RAFTQ_OK && n_hup > n_listed) {  // more timers fired than the list was sized for: fetch them again, alone
@@ -1326,11 +1381,23 @@ int tick(Turn& t) {
       }
       if (rc != RAFTQ_OK) return fail(t, rc, "tick");
     }
-    if (n_beat) {
+    n->stats.msgs_sent += n_frames;
+    n->stats.msgs_built_on_device += n_frames;
+    if (n_beat > n_built) {  // stepLeader MsgBeat on the host: every MsgBeat group, or the ones behind the device's first n_built
+      uint64_t skip = n_built;
       for (uint64_t w = 0; w < map_words; ++w) {
-        for (uint64_t bits = beat_map[w]; bits; bits &= bits - 1) {
+        uint64_t bits = beat_map[w];
+        if (skip) {
+          const uint64_t here = (uint64_t)__builtin_popcountll(bits);
+          if (here <= skip) {
+            skip -= here;
+            continue;
+          }
+          for (; skip; --skip) bits &= bits - 1;
+        }
+        for (; bits; bits &= bits - 1) {
           const uint64_t gi = w * 64 + (uint64_t)__builtin_ctzll(bits);
-          if (n->groups[gi].role == RAFTQ_ROLE_LEADER) bcast_heartbeat(n, gi, n->groups[gi]);  // stepLeader MsgBeat: host only
+          if (n->groups[gi].role == RAFTQ_ROLE_LEADER) bcast_heartbeat(n, gi, n->groups[gi]);
         }
       }
     }
@@ -1800,6 +1867,8 @@ int raftq_node_create(int device, uint64_t n_groups, uint32_t n_peers, uint32_t 
   if (n_peers < 2) n->propose_device = false;  // (a single-peer group commits what it appends: the report has to come back)
   if (const char* rd = std::getenv("RAFTQ_NODE_RESPOND_DEVICE")) n->respond_device = std::atoi(rd) != 0 && n_peers >= 2;
   if (const char* rk = std::getenv("RAFTQ_NODE_RESPOND_CHECK")) n->respond_check = std::atoi(rk) != 0;
+  if (const char* bd = std::getenv("RAFTQ_NODE_BEAT_DEVICE")) n->beat_device = std::atoi(bd) != 0 && n_peers >= 2;
+  if (const char* bc = std::getenv("RAFTQ_NODE_BEAT_CAP")) n->beat_cap_limit = std::strtoull(bc, nullptr, 10);
   if (const char* ev = std::getenv("RAFTQ_PROFILE_EVERY")) n->prof_every = std::strtoull(ev, nullptr, 10);
   try {
     n->groups.resize(n_groups);

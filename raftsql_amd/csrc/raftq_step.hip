@@ -96,11 +96,15 @@ int ensure_mirror(raftq_t* h) {
 }
 
 }  // namespace
-int raftq_detail::node_arrays_of(raftq_t* h, raftqk::NodeArrays* out) {
-  if (int rc = raftq_detail::refuse_voters(h, "raftq_propose_frames")) return rc;
+int raftq_detail::node_records_of(raftq_t* h, const char* who, raftqk::NodeArrays* out) {
+  if (int rc = raftq_detail::refuse_voters(h, who)) return rc;
   if (int rc = ensure_node_state(h)) return rc;
   if (int rc = ensure_mirror(h)) return rc;
   *out = node_arrays(h);
+  return RAFTQ_OK;
+}
+int raftq_detail::node_arrays_of(raftq_t* h, raftqk::NodeArrays* out) {
+  if (int rc = node_records_of(h, "raftq_propose_frames", out)) return rc;
   h->last_flags &= ~RAFTQ_SWEEP_NO_ADOPT;  // as in raftq_step_submit: the live state moves
   return RAFTQ_OK;
 }
@@ -328,6 +332,7 @@ int raftq_set_self(raftq_t* h, uint32_t self_peer) {
   if (!h) return fail(nullptr, RAFTQ_EINVAL, "null handle");
   if (self_peer >= h->N) return fail(h, RAFTQ_EINVAL, "raftq_set_self: self_peer out of range");
   h->self_peer = self_peer;
+  h->self_set = true;
   return raftq_detail::self_max_check(h);  // the sweep's skipped row follows the handle's own slot
 }
 

@@ -12,6 +12,7 @@
 #include <cstring>
 #include <string>
 
+#include "raftq_beat_kernels.hpp"
 #include "raftq_internal.hpp"
 #include "raftq_propose_kernels.hpp"
 #include "raftq_respond_kernels.hpp"
@@ -760,6 +761,88 @@ int raftq_detail::respond_finish(raftq_t* h, const RespPlan& p, raftq_wire_count
       return fail(h, RAFTQ_EHIP, "raftq_step_frames_respond: the marshal of the responses disagrees with their layout; the output is not valid");
   }
   if (resp_counts) *resp_counts = raftq_wire_counts_t{frames, 0, 0, bytes};
+  return RAFTQ_OK;
+}
+
+// ---- raftq_tick_frames ------------------------------------------------------------------------------------------------
+namespace {
+// the marshal of the heartbeats: as resp_marshal_call, the records go into the scratch behind an empty feed
+StreamCall beat_marshal_call(uint64_t n_max, uint64_t cap) {
+  StreamCall sc;
+  sc.n_tiles = blocks_for(n_max);
+  sc.seg[0] = {nullptr, 0, n_max * sizeof(WireMsg)};
+  sc.out_bytes = cap + 16;
+  return sc;
+}
+}  // namespace
+
+extern "C" int raftq_tick_frames(raftq_t* h, unsigned flags, uint64_t hup_cap, uint64_t beat_cap, uint64_t* n_hup, uint64_t* n_beat, void* out,
+                                 uint64_t cap, uint64_t* frame_off, uint64_t* peer_off, raftq_wire_counts_t* counts) {
+  const char* who = "raftq_tick_frames";
+  if (int rc = raftq_detail::use_device_idle(h, who)) return rc;
+  if (counts) *counts = raftq_wire_counts_t{0, 0, 0, 0};
+  if (!n_hup || !n_beat || !peer_off) return fail(h, RAFTQ_EINVAL, std::string(who) + ": null argument");
+  if (flags & ~RAFTQ_TICK_BEAT_BITMAP) return fail(h, RAFTQ_EINVAL, std::string(who) + ": unknown flag");
+  if (h->N < 2) return fail(h, RAFTQ_EINVAL, std::string(who) + ": a single-peer group has nobody to send a heartbeat to -- use raftq_tick_collect_lists");
+  // the exact worst case: beat_cap groups, N - 1 frames of RAFTQ_RESPOND_FRAME_MAX bytes each -- refused before anything runs, so a
+  // call that has ticked never fails for output space
+  const uint64_t slices = h->N - 1;
+  if (beat_cap >= ((uint64_t)1 << 31) || beat_cap * slices > kMaxItems || beat_cap * slices > (((uint64_t)1 << 31) / RAFTQ_RESPOND_FRAME_MAX))
+    return fail(h, RAFTQ_EINVAL, std::string(who) + ": beat_cap too large (beat_cap * (N - 1) * RAFTQ_RESPOND_FRAME_MAX must stay within 2^31 bytes)");
+  const uint64_t n_max = beat_cap * slices;
+  if (cap < n_max * RAFTQ_RESPOND_FRAME_MAX)
+    return fail(h, RAFTQ_EINVAL, std::string(who) + ": cap is below beat_cap * (N - 1) * RAFTQ_RESPOND_FRAME_MAX = " +
+                                     std::to_string(n_max * RAFTQ_RESPOND_FRAME_MAX) + " bytes -- the call has not ticked");
+  if (n_max != 0 && !out) return fail(h, RAFTQ_EINVAL, std::string(who) + ": null argument");
+  if (!h->node_rec && !h->self_set)
+    return fail(h, RAFTQ_ESTATE, std::string(who) + ": the handle holds no node state (raftq_set_self / raftq_load_node first)");
+  if (int rc = ensure_pin(h)) return rc;
+  Views v;
+  void *v_out = v.opt(out), *v_off = v.opt(frame_off);
+  v.add(peer_off);
+  if (!v.ok)
+    return fail(h, RAFTQ_EINVAL, std::string(who) + ": out, frame_off and peer_off must be page-locked (raftq_host_alloc, hipHostMalloc, hipHostRegister) "
+                                                    "and 16-byte aligned -- the call has not ticked");
+  // every allocation before the tick kernel: the records (and, where something other than Step wrote the dense arrays, their
+  // refresh), the Tick's lists, the encoder's control block, scratch and output buffer
+  NodeArrays na;
+  if (int rc = raftq_detail::node_records_of(h, who, &na)) return rc;
+  raftq_detail::TickLists tl;
+  if (int rc = raftq_detail::tick_lists_prepare(h, who, flags, hup_cap, beat_cap, &tl)) return rc;
+  const uint64_t enc_cap = n_max * RAFTQ_RESPOND_FRAME_MAX;  // what the encoder may write: never more than the worst case
+  StreamCall sc = beat_marshal_call(n_max, enc_cap);
+  if (n_max != 0)
+    if (int rc = stream_prepare(h, sc)) return rc;  // (the launch's epoch and feed: nothing of it runs before the encoder below)
+  // Tick -> lists -> beat_build -> encoder -> flag, back to back; one wait
+  if (int rc = raftq_detail::tick_lists_enqueue(h, &tl)) return rc;
+  if (n_max != 0) {
+    const uint64_t nw = h->gpad / 256;
+    BeatArgs ba{(const uint64_t*)h->beat_bits, (const uint4*)h->tick_partials, nw, tl.off_beat, (const uint64_t*)h->d_total, na.rec, h->G, h->N,
+                h->self_peer, beat_cap, (WireMsg*)sc.in.seg[0].dst};
+    hipLaunchKernelGGL(beat_build_kernel, dim3((unsigned)((nw + kWaves - 1) / kWaves)), dim3(kBlock), 0, h->stream, ba);
+    HIPCHK(h, hipGetLastError());
+    if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, n_max, (uint64_t)0, (uint64_t)0, (uint8_t*)h->wire_out, (uint8_t*)v_out, enc_cap,
+                               (uint64_t*)v_off, sc.ctl, h->wire_pin_d + kPinCall, (const unsigned int*)nullptr, 0u))
+      return rc;
+  }
+  if (int rc = raftq_detail::tick_lists_finish(h, who, tl, n_hup, n_beat)) return rc;
+  const uint64_t n_built = std::min(*n_beat, beat_cap), frames = n_built * slices;
+  uint64_t at = 0;
+  for (uint32_t p = 0; p <= h->N; ++p) {
+    peer_off[p] = at;
+    if (p < h->N && p != h->self_peer) at += n_built;
+  }
+  uint64_t bytes = 0;
+  if (n_max != 0) {
+    if (int rc = tile_ctl_check(h, who, kPinCall)) return rc;
+    bytes = h->wire_pin[kPinCall + kPinTotal];
+    // every record past the last frame is a filler the encoder refuses; any other refusal, or bytes beyond the bound, is a bug here
+    if (h->wire_pin[kPinCall + kPinRefused] != n_max - frames || bytes > enc_cap)
+      return fail(h, RAFTQ_EHIP, std::string(who) + ": the marshal of the heartbeats disagrees with their layout; the output is not valid");
+  } else if (frame_off) {
+    frame_off[0] = 0;
+  }
+  if (counts) *counts = raftq_wire_counts_t{frames, 0, 0, bytes};
   return RAFTQ_OK;
 }
 

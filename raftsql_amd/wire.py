@@ -255,6 +255,37 @@ class WireEngine(NodeEngine):
         return (msgs[:n], got_ents, outs, out[: int(rc_.bytes)], resp_off[: n_resp + 1] if resp_off is not None else None,
                 peer_off[: self.n_peers + 1], c, rc_)
 
+    def tick_frames(self, out: np.ndarray, frame_off: np.ndarray | None, peer_off: np.ndarray, beat_cap: int, hup_cap: int | None = None,
+                    beat_bitmap: bool = False, cap: int | None = None):
+        """raftq_tick_frames: the Tick, its lists (as tick_collect_lists) and the heartbeats of the first beat_cap MsgBeat groups built
+        and marshalled on the device -- one submission, one wait.  out: uint8 of at least respond_cap(beat_cap) bytes (cap: what the
+        call is told instead of len(out)); frame_off: uint64 [beat_cap * (N - 1) + 1] or None; peer_off: uint64 [N + 1]; all page-locked
+        (engine.pinned_empty).  -> (heartbeat bytes (a view of out), frame_off[:n_frames + 1] | None, peer_off, counts, hups view u32,
+        n_hup, beats view u32 | bitmap view u64, n_beat); the list views are the library's memory, valid until the next Tick call"""
+        assert peer_off.dtype == np.uint64 and len(peer_off) >= self.n_peers + 1
+        assert out is None or out.dtype == np.uint8
+        assert frame_off is None or (frame_off.dtype == np.uint64 and len(frame_off) >= int(beat_cap) * (self.n_peers - 1) + 1)
+        hc = self.n_groups if hup_cap is None else int(hup_cap)
+        nh, nb, c = C.c_uint64(0), C.c_uint64(0), _lib.WireCounts()
+        self._chk(self._lib.raftq_tick_frames(self._h, _lib.TICK_BEAT_BITMAP if beat_bitmap else 0, hc, int(beat_cap), C.byref(nh), C.byref(nb),
+                                              out.ctypes.data if out is not None and len(out) else None,
+                                              (len(out) if out is not None else 0) if cap is None else int(cap),
+                                              frame_off.ctypes.data if frame_off is not None else None, peer_off.ctypes.data, C.byref(c)))
+        ph, pb, pm = C.c_void_p(None), C.c_void_p(None), C.c_void_p(None)
+        lh, lb, lm = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._lib.raftq_last_tick_lists(self._h, C.byref(ph), C.byref(lh), C.byref(pb), C.byref(lb), C.byref(pm), C.byref(lm)))
+
+        def view(p, n, dt):
+            if not n:
+                return np.empty(0, dtype=dt)
+            return np.frombuffer((C.c_char * (int(n) * np.dtype(dt).itemsize)).from_address(p.value), dtype=dt)
+
+        hups = view(ph, lh.value, np.uint32)
+        second = view(pm, lm.value, np.uint64) if beat_bitmap else view(pb, lb.value, np.uint32)
+        n_frames = int(c.n_msgs)
+        return (out[: int(c.bytes)] if out is not None else np.zeros(0, np.uint8), frame_off[: n_frames + 1] if frame_off is not None else None,
+                peer_off[: self.n_peers + 1], c, hups, int(nh.value), second, int(nb.value))
+
     def propose_frames(self, props: np.ndarray, prop_ents: np.ndarray, msgs: np.ndarray, ents: np.ndarray, pool: np.ndarray, out: np.ndarray,
                        off: np.ndarray | None = None):
         """raftq_propose_frames: appendEntry + bcastAppend for props[] on the device, written into the encoder's input, and the

@@ -2,9 +2,10 @@
 """Per-kernel resource usage of the sweep kernels as compiled for gfx950 (VGPR / SGPR / scratch / LDS / occupancy),
 with the toolchain and the exact command line -- the tracked evidence behind DESIGN.md's ISA claims.
 
-usage: tools/isa_report.py [out.txt [kernel-regex]]      (default profiles/r02/isa_sweep.txt, the sweep / ingest / tick kernels;
-                                                          e.g. `profiles/r09/isa_voters.txt "raftqk::.*voters"` for the masked sweep)
-Compiles raftsql_amd/csrc/raftq_capi.hip (device side) with -Rpass-analysis=kernel-resource-usage; no GPU needed.
+usage: tools/isa_report.py [out.txt [kernel-regex [unit.hip]]]  (default profiles/r02/isa_sweep.txt, the sweep / ingest / tick kernels;
+                                                          e.g. `profiles/r09/isa_voters.txt "raftqk::.*voters"` for the masked sweep,
+                                                          `profiles/r10/isa_tick_frames.txt "raftqk::beat_build" raftq_wire.hip`)
+Compiles raftsql_amd/csrc/raftq_capi.hip, or the unit named, (device side) with -Rpass-analysis=kernel-resource-usage; no GPU needed.
 """
 import os
 import re
@@ -31,7 +32,8 @@ def shown_command(cmd):
 
 def main():
     out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r02", "isa_sweep.txt")
-    src = os.path.join(b.CSRC, "raftq_capi.hip")
+    unit = sys.argv[3] if len(sys.argv) > 3 else "raftq_capi.hip"
+    src = os.path.join(b.CSRC, unit)
     cmd = [b._hipcc()] + b._flags() + ["--cuda-device-only", "-c", src, "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"]
     p = subprocess.run(cmd, capture_output=True, text=True)
     if p.returncode != 0:
@@ -52,7 +54,7 @@ def main():
     tc = b.toolchain()
     head = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip()
     dirty = subprocess.run(["git", "-C", ROOT, "status", "--porcelain", "raftsql_amd/csrc"], capture_output=True, text=True).stdout.strip()
-    lines = ["# gfx950 resource usage of the %s (raftq_capi.hip), from -Rpass-analysis=kernel-resource-usage" % ("kernels matching /%s/" % sys.argv[2] if len(sys.argv) > 2 else "sweep kernels"),
+    lines = ["# gfx950 resource usage of the %s (%s), from -Rpass-analysis=kernel-resource-usage" % ("kernels matching /%s/" % sys.argv[2] if len(sys.argv) > 2 else "sweep kernels", unit),
              "# tree: %s%s" % (head, " + uncommitted changes under raftsql_amd/csrc" if dirty else ""),
              "# " + " | ".join(tc["version"][:2]), "# " + shown_command(cmd), "#",
              "# %-6s %-6s %-6s %-8s %-5s %-4s kernel" % ("VGPR", "AGPR", "SGPR", "scratch", "LDS", "occ")]
