@@ -45,6 +45,7 @@ def lib_sources() -> list[str]:
         os.path.join(CSRC, "raftq_kernels.hpp"),
         os.path.join(CSRC, "raftq_step_kernels.hpp"),
         os.path.join(CSRC, "raftq_internal.hpp"),
+        os.path.join(CSRC, "raftq_buffers.hpp"),
         os.path.join(CSRC, "raftq_wire_kernels.hpp"),
         os.path.join(CSRC, "raftq_wire_parse.hpp"),
         os.path.join(CSRC, "raftq_propose_kernels.hpp"),

@@ -7,10 +7,6 @@
 
 #include <hip/hip_runtime.h>
 
-#include <fcntl.h>
-#include <unistd.h>
-#include <cerrno>
-
 #include <algorithm>
 #include <atomic>
 #include <mutex>
@@ -224,125 +220,24 @@ hipError_t launch_sweep(uint32_t N, const SweepLaunch& L, unsigned flags, int nt
 static inline void dense_changed(raftq_t* h) { h->node_mirror_fresh = false; }
 
 int raftq_detail::ensure_staging(raftq_t* h, size_t bytes) {
-  if (bytes <= h->stage_bytes) return RAFTQ_OK;
-  size_t want = std::max(bytes, h->stage_bytes * 2);
-  want = std::max<size_t>(want, 1 << 20);
-  if (h->stage_h) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipHostFree(h->stage_h));
-    h->stage_h = h->stage_d = nullptr;
-    h->stage_bytes = 0;
-  }
-  HIPCHK(h, hipHostMalloc(&h->stage_h, want, hipHostMallocMapped));
-  HIPCHK(h, hipHostGetDevicePointer(&h->stage_d, h->stage_h, 0));
-  h->stage_bytes = want;
+  HIPCHK(h, h->stage.grow(bytes, std::max({bytes, h->stage.cap * 2, (size_t)1 << 20}), &h->stream));
   return RAFTQ_OK;
 }
 
-// Can this process really store into `p` (device memory behind the BAR)?  hipDeviceAttributeIsLargeBar says the aperture
-// exists; whether the allocation is mapped writable into THIS process is read off /proc/self/maps -- no store is tried
-// and no signal handler is touched.  (Round 2 probed with a guarded store and a temporary SIGSEGV / SIGBUS handler that
-// siglongjmp'd out of the fault: undefined behaviour in a host with other threads that use those signals -- the Go
-// runtime this library is meant to sit under requires SA_ONSTACK handlers, a JVM installs its own)
-bool raftq_detail::host_can_write(void* p, size_t bytes) {
-  const uintptr_t lo = (uintptr_t)p, hi = lo + bytes;
-  std::FILE* f = std::fopen("/proc/self/maps", "r");
-  if (!f) return false;  // cannot tell: stay on pinned host memory
-  char line[512];
-  uintptr_t covered = lo;  // [lo, covered) is mapped writable so far (maps is sorted by address)
-  while (covered < hi && std::fgets(line, sizeof line, f)) {
-    unsigned long long a = 0, b = 0;
-    char perms[8] = {0};
-    if (std::sscanf(line, "%llx-%llx %7s", &a, &b, perms) != 3) continue;
-    if ((uintptr_t)b <= covered) continue;
-    if ((uintptr_t)a > covered) break;           // a hole in front of the next mapping
-    if (perms[0] != 'r' || perms[1] != 'w') break;  // mapped, but not for stores
-    covered = (uintptr_t)b;
-  }
-  std::fclose(f);
-  if (covered < hi) return false;
-  // Mapped "rw" is not yet "a store works": in some containers / VMs the aperture is mapped and a store to it still faults
-  // (ADVICE r03).  Try one without risking a signal: a one-byte pwrite through /proc/self/mem goes through the kernel's
-  // access path and FAILS (EFAULT / EIO) where a store would have raised SIGBUS.  The buffer is fresh and about to be
-  // overwritten by its producer, so the byte written does not matter.  Three outcomes: written -> device staging;
-  // refused with EFAULT -> pinned host staging; the probe itself unavailable (no /proc/self/mem, EPERM, EIO: the mapping
-  // has no access method) -> the maps answer stands.  RAFTQ_STAGE=host forces pinned staging whatever is found here.
-  const int fd = ::open("/proc/self/mem", O_WRONLY | O_CLOEXEC);
-  if (fd < 0) return true;
-  const char zero = 0;
-  bool ok = true;
-  for (const uintptr_t at : {lo, hi - 1}) {
-    if (::pwrite(fd, &zero, 1, (off_t)at) == 1) continue;
-    if (errno == EFAULT) ok = false;
-    break;
-  }
-  ::close(fd);
-  return ok;
-}
-
 int raftq_detail::ensure_ingest(raftq_t* h, size_t bytes) {
-  if (bytes <= h->ingest_bytes) return RAFTQ_OK;
-  size_t want = std::max(bytes, h->ingest_bytes * 2);
-  want = std::max<size_t>(want, 1 << 20);
-  if (h->ingest_h) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->ingest_in_device) HIPCHK(h, hipFree(h->ingest_h));
-    else HIPCHK(h, hipHostFree(h->ingest_h));
-    h->ingest_h = h->ingest_d = nullptr;
-    h->ingest_bytes = 0;
-  }
-  if (h->bar_staging) {
-    void* p = nullptr;
-    if (hipExtMallocWithFlags(&p, want, hipDeviceMallocFinegrained) == hipSuccess) {
-      if (h->bar_probed || host_can_write(p, want)) {
-        h->bar_probed = true;
-        h->ingest_h = h->ingest_d = p;
-        h->ingest_in_device = true;
-        h->ingest_bytes = want;
-        return RAFTQ_OK;
-      }
-      (void)hipFree(p);
-    }
-    (void)hipGetLastError();
-    h->bar_staging = false;  // no host-writable device memory here: pinned host memory from now on
-    if (std::getenv("RAFTQ_PROFILE"))
-      std::fprintf(stderr, "[raftq] the ack / inbound staging stays in pinned host memory: device memory behind the BAR is not "
-                           "host-writable here (RAFTQ_STAGE=host asks for this outright)\n");
-  }
-  HIPCHK(h, hipHostMalloc(&h->ingest_h, want, hipHostMallocMapped));
-  HIPCHK(h, hipHostGetDevicePointer(&h->ingest_d, h->ingest_h, 0));
-  h->ingest_in_device = false;
-  h->ingest_bytes = want;
+  HIPCHK(h, h->ingest.grow(bytes, std::max({bytes, h->ingest.cap * 2, (size_t)1 << 20}), &h->stream, h->bar));
   return RAFTQ_OK;
 }
 
 namespace {
-// the producer's stores into a device-resident ack buffer are write-combined: drain them before the doorbell
-inline void publish_ingest(const raftq_t* h) {
-#if defined(__x86_64__)
-  if (h->ingest_in_device) __builtin_ia32_sfence();
-#else
-  (void)h;
-#endif
-}
-
 // The buffers a kernel writes for the host to read while the kernel may still be running (the advance list, the totals,
-// the completion flag) are allocated hipHostMallocCoherent (fine-grained): the device's stores go out over PCIe as they are
+// the completion flag) are fine-grained (raftq_buf::Kind::mapped_coherent): the device's stores go out over PCIe as they are
 // issued instead of sitting in its L2 until the end-of-kernel write-back.  Stated explicitly -- without the flag the choice
 // is the runtime's (HIP_HOST_COHERENT).
 int ensure_adv(raftq_t* h, uint64_t entries) {
-  if (entries <= h->adv_cap) return RAFTQ_OK;
-  uint64_t want = std::max<uint64_t>(entries, h->adv_cap * 2);
-  want = std::min<uint64_t>(std::max<uint64_t>(want, 4096), h->gpad);
-  if (h->adv_h) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipHostFree(h->adv_h));
-    h->adv_h = h->adv_d = nullptr;
-    h->adv_cap = 0;
-  }
-  HIPCHK(h, hipHostMalloc((void**)&h->adv_h, want * sizeof(Advance), hipHostMallocMapped | hipHostMallocCoherent));
-  HIPCHK(h, hipHostGetDevicePointer((void**)&h->adv_d, h->adv_h, 0));
-  h->adv_cap = want;
+  const uint64_t have = h->adv.cap / sizeof(Advance);
+  const uint64_t want = std::min<uint64_t>(std::max<uint64_t>({entries, have * 2, 4096}), h->gpad);
+  HIPCHK(h, h->adv.grow(entries * sizeof(Advance), want * sizeof(Advance), &h->stream));
   return RAFTQ_OK;
 }
 
@@ -455,11 +350,6 @@ int raftq_create(int device, uint64_t n_groups, uint32_t n_peers, raftq_t** out)
   // the finest tile any variant uses bounds the number of per-wave partials
   h->max_partials = h->gpad / (kBlock * 2) * kWaves;
   int rc = RAFTQ_OK;
-  auto alloc = [&](void** p, size_t bytes) -> int {
-    HIPCHK(h, hipMalloc(p, bytes));
-    HIPCHK(h, hipMemsetAsync(*p, 0, bytes, h->stream));
-    return RAFTQ_OK;
-  };
   do {
     if ((rc = use_device(h))) break;
     hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
@@ -469,27 +359,31 @@ int raftq_create(int device, uint64_t n_groups, uint32_t n_peers, raftq_t** out)
       int large_bar = 0;
       (void)hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, device);
       const char* st = std::getenv("RAFTQ_STAGE");
-      h->bar_staging = large_bar == 1 && !(st && std::strcmp(st, "host") == 0);
+      h->bar.staging = large_bar == 1 && !(st && std::strcmp(st, "host") == 0);
     }
-    if ((rc = alloc((void**)&h->match, (size_t)n_peers * ld * 8))) break;
-    if ((rc = alloc((void**)&h->committed[0], ld * 8))) break;
-    if ((rc = alloc((void**)&h->committed[1], ld * 8))) break;
-    if ((rc = alloc((void**)&h->first_idx, ld * 8))) break;
-    // RequestVote state: one packed word per group (2 bits per peer), outcomes 2 bits per group
-    if ((rc = alloc((void**)&h->votes, (size_t)vote_word_bytes((int)n_peers) * ld))) break;
-    if ((rc = alloc((void**)&h->outcome, ld / 4 + 64))) break;
-    if ((rc = alloc((void**)&h->changed_bits, h->gpad / 8))) break;
-    if ((rc = alloc((void**)&h->partials, h->max_partials * sizeof(uint4)))) break;
-    if ((rc = alloc((void**)&h->offsets, (h->max_partials + 1) * 8))) break;
-    // the self-max word (raftq_kernels.hpp): every row is zero, so row 0 (the default self slot) is the largest
-    if ((rc = alloc((void**)&h->self_max, 64))) break;
+    e = raftq_buf::alloc_group({{(void**)&h->match, (size_t)n_peers * ld * 8},
+                                {(void**)&h->committed[0], ld * 8},
+                                {(void**)&h->committed[1], ld * 8},
+                                {(void**)&h->first_idx, ld * 8},
+                                // RequestVote state: one packed word per group (2 bits per peer), outcomes 2 bits per group
+                                {(void**)&h->votes, (size_t)vote_word_bytes((int)n_peers) * ld},
+                                {(void**)&h->outcome, ld / 4 + 64},
+                                {(void**)&h->changed_bits, h->gpad / 8},
+                                {(void**)&h->partials, h->max_partials * sizeof(uint4)},
+                                {(void**)&h->offsets, (h->max_partials + 1) * 8},
+                                // the self-max word (raftq_kernels.hpp): every row is zero, so row 0 (the default self slot) is the largest
+                                {(void**)&h->self_max, 64}},
+                               h->stream);
+    if (e != hipSuccess) {
+      rc = fail(h, e == hipErrorOutOfMemory ? RAFTQ_ENOMEM : RAFTQ_EHIP, std::string("device arrays: ") + hipGetErrorString(e));
+      break;
+    }
     e = hipMemsetD32Async((hipDeviceptr_t)h->self_max, (int)(kSelfMaxValid | 0u), 1, h->stream);
     if (e != hipSuccess) { rc = fail(h, RAFTQ_EHIP, std::string("hipMemsetD32Async: ") + hipGetErrorString(e)); break; }
-    e = hipHostMalloc((void**)&h->h_partials, h->max_partials * sizeof(uint4), hipHostMallocDefault);
-    if (e != hipSuccess) { rc = fail(h, RAFTQ_ENOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(e)); break; }
-    e = hipHostMalloc((void**)&h->h_total, 64, hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&h->d_total, h->h_total, 0);
-    if (e != hipSuccess) { rc = fail(h, RAFTQ_ENOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(e)); break; }
+    e = raftq_buf::alloc_group({{(void**)&h->h_partials, h->max_partials * sizeof(uint4), raftq_buf::Kind::pinned},
+                                {(void**)&h->h_total, 64, raftq_buf::Kind::mapped_coherent, (void**)&h->d_total}},
+                               h->stream);
+    if (e != hipSuccess) { rc = fail(h, RAFTQ_ENOMEM, std::string("page-locked memory: ") + hipGetErrorString(e)); break; }
     e = hipEventCreate(&h->ev0);
     if (e == hipSuccess) e = hipEventCreate(&h->ev1);
     if (e != hipSuccess) { rc = fail(h, RAFTQ_EHIP, std::string("hipEventCreate: ") + hipGetErrorString(e)); break; }
@@ -526,47 +420,26 @@ void raftq_destroy(raftq_t* h) {
                  h->prof[3] / h->prof_n, h->prof[4] / h->prof_n, h->prof[5] / h->prof_n, (unsigned long long)h->flag_fallbacks);
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  (void)hipFree(h->match);
-  (void)hipFree(h->committed[0]);
-  (void)hipFree(h->committed[1]);
-  (void)hipFree(h->first_idx);
-  (void)hipFree(h->votes);
-  (void)hipFree(h->voters);
-  (void)hipFree(h->outcome);
-  (void)hipFree(h->changed_bits);
-  (void)hipFree(h->partials);
-  (void)hipFree(h->seg_d);
-  if (h->seg_h) (void)hipHostFree(h->seg_h);
-  (void)hipFree(h->offsets);
-  (void)hipFree(h->self_max);
-  (void)hipFree(h->claim);
-  (void)hipFree(h->delta_dev);
-  (void)hipFree(h->delta_bad);
-  (void)hipFree(h->role);
-  (void)hipFree(h->elapsed);
-  (void)hipFree(h->action);
-  (void)hipFree(h->hup_bits);
-  (void)hipFree(h->beat_bits);
-  (void)hipFree(h->tick_partials);
-  (void)hipFree(h->tick_offsets2);
-  raftq_detail::free_node_state(h);
+  if (h->many_aux) (void)hipStreamSynchronize(h->many_aux);
+  raftq_detail::free_node_state(h);  // (waits for the slots' events first)
   raftq_detail::free_wire_state(h);
-  if (h->stage_h) (void)hipHostFree(h->stage_h);
-  if (h->ingest_h) (void)(h->ingest_in_device ? hipFree(h->ingest_h) : hipHostFree(h->ingest_h));
-  if (h->adv_h) (void)hipHostFree(h->adv_h);
-  if (h->tl_h) (void)hipHostFree(h->tl_h);
-  if (h->h_partials) (void)hipHostFree(h->h_partials);
-  if (h->h_total) (void)hipHostFree(h->h_total);
+  // every wait is over: memory may go
+  raftq_buf::free_device(h->match, h->committed[0], h->committed[1], h->first_idx, h->votes, h->voters, h->outcome, h->changed_bits,
+                         h->partials, h->offsets, h->self_max, h->claim, h->delta_bad, h->role, h->elapsed, h->action, h->hup_bits,
+                         h->beat_bits, h->tick_partials, h->tick_offsets2);
+  raftq_buf::free_host(h->h_partials, h->h_total);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->many_aux) {
-    (void)hipStreamSynchronize(h->many_aux);
     (void)hipEventDestroy(h->many_fork);
     (void)hipEventDestroy(h->many_join);
-    (void)hipStreamDestroy(h->many_aux);
   }
-  if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
+  // The order of teardown holds by construction: every buffer object is a member of the handle, so `delete h` releases them all
+  // -- after the waits above, before any stream of the handle's is destroyed.
+  const hipStream_t streams[4] = {h->many_aux, h->step_s_in, h->step_s_out, h->own_stream ? h->stream : nullptr};
   delete h;
+  for (hipStream_t st : streams)
+    if (st) (void)hipStreamDestroy(st);
 }
 
 int raftq_set_stream(raftq_t* h, void* stream) {
@@ -638,20 +511,8 @@ int raftq_load_votes(raftq_t* h, const uint8_t* votes) {
 // enqueue only (no sync): validate, copy into the pinned staging area at byte
 // offset `off`, launch the scatter.  Shared by raftq_apply_* and raftq_cycle.
 static int ensure_delta_dev(raftq_t* h, size_t bytes) {
-  if (!h->delta_bad) {
-    HIPCHK(h, hipMalloc((void**)&h->delta_bad, 64));
-    HIPCHK(h, hipMemsetAsync(h->delta_bad, 0, 64, h->stream));
-  }
-  if (bytes <= h->delta_dev_bytes) return RAFTQ_OK;
-  if (h->delta_dev) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipFree(h->delta_dev));
-    h->delta_dev = nullptr;
-    h->delta_dev_bytes = 0;
-  }
-  const size_t want = std::max(bytes * 2, (size_t)1 << 20);
-  HIPCHK(h, hipMalloc(&h->delta_dev, want));
-  h->delta_dev_bytes = want;
+  if (!h->delta_bad) HIPCHK(h, raftq_buf::alloc_zeroed((void**)&h->delta_bad, 64, h->stream));
+  HIPCHK(h, h->delta_dev.grow(bytes, std::max(bytes * 2, (size_t)1 << 20), &h->stream));
   return RAFTQ_OK;
 }
 
@@ -685,47 +546,45 @@ static int enqueue_ingest(raftq_t* h, const AbiRec* d, uint64_t n, const raftq_v
   // staged with other counts (or through the other layout's raftq_stage*) would overlap their own destination, and
   // reading them back out of a device-resident buffer crosses the uncached BAR.
   auto inside = [&](const void* q) {
-    return (const uint8_t*)q >= (const uint8_t*)h->ingest_h && (const uint8_t*)q < (const uint8_t*)h->ingest_h + h->ingest_bytes;
+    return (const uint8_t*)q >= (const uint8_t*)h->ingest.h && (const uint8_t*)q < (const uint8_t*)h->ingest.h + h->ingest.cap;
   };
   if (n) {
-    AbiRec* dst = (AbiRec*)h->ingest_h;
+    AbiRec* dst = (AbiRec*)h->ingest.h;
     if ((const void*)d != (const void*)dst) {
       if (inside(d)) return fail(h, RAFTQ_EINVAL, "match deltas staged with other counts / another record layout than this call's");
       std::memcpy(dst, d, (size_t)n * sizeof(AbiRec));
     }
   }
   if (nv) {
-    raftq_vote_delta_t* dst = (raftq_vote_delta_t*)((uint8_t*)h->ingest_h + off_votes);
+    raftq_vote_delta_t* dst = (raftq_vote_delta_t*)((uint8_t*)h->ingest.h + off_votes);
     if ((const void*)vd != (const void*)dst) {
       if (inside(vd)) return fail(h, RAFTQ_EINVAL, "vote deltas staged with other counts / another record layout than this call's");
       std::memcpy(dst, vd, (size_t)nv * sizeof(raftq_vote_delta_t));
     }
     if (!h->claim) {
-      const size_t bytes = (size_t)h->N * h->ld * sizeof(uint32_t);
-      HIPCHK(h, hipMalloc((void**)&h->claim, bytes));
-      HIPCHK(h, hipMemsetAsync(h->claim, 0xff, bytes, h->stream));
+      HIPCHK(h, raftq_buf::alloc_filled((void**)&h->claim, (size_t)h->N * h->ld * sizeof(uint32_t), 0xff, h->stream));
     }
   }
   // match and vote records share the device buffer: votes go behind the matches (same offsets as in staging)
-  publish_ingest(h);
-  if (int rc = ensure_delta_dev(h, h->ingest_bytes)) return rc;
+  h->ingest.publish();
+  if (int rc = ensure_delta_dev(h, h->ingest.cap)) return rc;
   const unsigned long long em = n ? ++h->delta_epoch : kNoEpoch, ev = nv ? ++h->delta_epoch : kNoEpoch;
   h->delta_check[0] = n ? em : 0;
   h->delta_check[1] = nv ? ev : 0;
-  Rec* dev_m = (Rec*)h->delta_dev;
-  VoteDeltaRec* dev_v = (VoteDeltaRec*)((uint8_t*)h->delta_dev + off_votes);
+  Rec* dev_m = (Rec*)h->delta_dev.d;
+  VoteDeltaRec* dev_v = (VoteDeltaRec*)((uint8_t*)h->delta_dev.d + off_votes);
   const unsigned long long* bad = h->delta_bad;
   const dim3 gm((unsigned)((n + kBlock - 1) / kBlock)), gv((unsigned)((nv + kBlock - 1) / kBlock));
   if (n) dense_changed(h);  // (match words move under Step's records)
   if (n && trusted)
-    hipLaunchKernelGGL((deltas_in_apply_kernel<Rec>), gm, dim3(kBlock), 0, h->stream, (const Rec*)h->ingest_d, n, h->match, h->ld,
+    hipLaunchKernelGGL((deltas_in_apply_kernel<Rec>), gm, dim3(kBlock), 0, h->stream, (const Rec*)h->ingest.d, n, h->match, h->ld,
                        h->G, h->N, h->delta_bad, h->d_total + 1, em, h->self_max);
   else if (n)
-    hipLaunchKernelGGL((deltas_in_kernel<Rec>), gm, dim3(kBlock), 0, h->stream, (const Rec*)h->ingest_d, dev_m, n, h->G, h->N,
+    hipLaunchKernelGGL((deltas_in_kernel<Rec>), gm, dim3(kBlock), 0, h->stream, (const Rec*)h->ingest.d, dev_m, n, h->G, h->N,
                        h->delta_bad, h->d_total + 1, em);
   if (nv)
     hipLaunchKernelGGL(vote_deltas_in_kernel, gv, dim3(kBlock), 0, h->stream,
-                       (const VoteDeltaRec*)((uint8_t*)h->ingest_d + off_votes), dev_v, nv, h->G, h->N, h->delta_bad + 1,
+                       (const VoteDeltaRec*)((uint8_t*)h->ingest.d + off_votes), dev_v, nv, h->G, h->N, h->delta_bad + 1,
                        h->d_total + 2, ev);
   if (n && !trusted)
     hipLaunchKernelGGL((apply_deltas_kernel<Rec>), gm, dim3(kBlock), 0, h->stream, h->match, h->ld, (const Rec*)dev_m, n, bad, em,
@@ -765,7 +624,7 @@ int raftq_apply_term_deltas(raftq_t* h, const raftq_term_delta_t* d, uint64_t n)
     if (d[i].group >= h->G) return fail(h, RAFTQ_EINVAL, "a term delta is out of range; nothing applied");
   if (int rc = ensure_staging(h, (size_t)n * sizeof(raftq_term_delta_t))) return rc;
   // keep only the last record per group so the scatter has no write-write race
-  raftq_term_delta_t* dst = (raftq_term_delta_t*)h->stage_h;
+  raftq_term_delta_t* dst = (raftq_term_delta_t*)h->stage.h;
   uint64_t m = 0;
   {
     std::unordered_set<uint64_t> seen;
@@ -779,7 +638,7 @@ int raftq_apply_term_deltas(raftq_t* h, const raftq_term_delta_t* d, uint64_t n)
   const dim3 grid((unsigned)((m + kBlock - 1) / kBlock));
   dense_changed(h);
   hipLaunchKernelGGL(apply_term_deltas_kernel, grid, dim3(kBlock), 0, h->stream, h->first_idx,
-                     (const TermDeltaRec*)h->stage_d, m);
+                     (const TermDeltaRec*)h->stage.d, m);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->have_terms = true;
@@ -802,21 +661,14 @@ int raftq_apply_vote_deltas(raftq_t* h, const raftq_vote_delta_t* d, uint64_t n)
 // the masks' array exists (zeroed: no slot votes anywhere until it is filled)
 static int ensure_voters(raftq_t* h) {
   if (h->voters) return RAFTQ_OK;
-  uint16_t* p = nullptr;
-  HIPCHK(h, hipMalloc((void**)&p, h->ld * sizeof(uint16_t)));
-  if (const hipError_t e = hipMemsetAsync(p, 0, h->ld * sizeof(uint16_t), h->stream); e != hipSuccess) {
-    (void)hipFree(p);
-    HIPCHK(h, e);
-  }
-  h->voters = p;
+  HIPCHK(h, raftq_buf::alloc_zeroed((void**)&h->voters, h->ld * sizeof(uint16_t), h->stream));
   return RAFTQ_OK;
 }
 // back to "every slot votes": the unmasked kernels
 static int drop_voters(raftq_t* h) {
   if (!h->voters) return RAFTQ_OK;
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  HIPCHK(h, hipFree(h->voters));
-  h->voters = nullptr;
+  raftq_buf::free_device(h->voters);
   return RAFTQ_OK;
 }
 static int voters_not_in_set(raftq_t* h, const char* who) {
@@ -869,7 +721,7 @@ int raftq_apply_voter_deltas(raftq_t* h, const raftq_voter_delta_t* d, uint64_t 
       return fail(h, RAFTQ_EINVAL, "a voter delta is out of range (group >= G or a bit >= N); nothing applied");
   if (int rc = ensure_staging(h, (size_t)n * sizeof(raftq_voter_delta_t))) return rc;
   // keep only the last record per group so the scatter has no write-write race (as raftq_apply_term_deltas)
-  raftq_voter_delta_t* dst = (raftq_voter_delta_t*)h->stage_h;
+  raftq_voter_delta_t* dst = (raftq_voter_delta_t*)h->stage.h;
   uint64_t m = 0;
   try {
     std::unordered_set<uint64_t> seen;
@@ -890,7 +742,7 @@ int raftq_apply_voter_deltas(raftq_t* h, const raftq_voter_delta_t* d, uint64_t 
   }
   dense_changed(h);  // (match words are zeroed under Step's records)
   hipLaunchKernelGGL(apply_voter_deltas_kernel, dim3((unsigned)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, h->voters, h->match,
-                     h->ld, h->votes, h->N > 8 ? 1 : 0, h->N, (const VoterDeltaRec*)h->stage_d, m, h->self_max);
+                     h->ld, h->votes, h->N > 8 ? 1 : 0, h->N, (const VoterDeltaRec*)h->stage.d, m, h->self_max);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipStreamSynchronize(h->stream));  // the staging area is reused by the next call
   return RAFTQ_OK;
@@ -1131,17 +983,14 @@ int raftq_vote_tally(raftq_t* h, uint8_t* outcome_out, raftq_counts_t* counts) {
 
 int raftq_detail::ensure_tick_state(raftq_t* h) {
   if (h->role) return RAFTQ_OK;
-  auto alloc = [&](void** p, size_t bytes) -> int {
-    HIPCHK(h, hipMalloc(p, bytes));
-    HIPCHK(h, hipMemsetAsync(*p, 0, bytes, h->stream));
-    return RAFTQ_OK;
-  };
-  if (int rc = alloc((void**)&h->role, h->ld)) return rc;
-  if (int rc = alloc((void**)&h->elapsed, h->ld * 4)) return rc;
-  if (int rc = alloc((void**)&h->action, h->ld)) return rc;
-  if (int rc = alloc((void**)&h->hup_bits, h->gpad / 8)) return rc;
-  if (int rc = alloc((void**)&h->beat_bits, h->gpad / 8)) return rc;
-  if (int rc = alloc((void**)&h->tick_partials, h->gpad / 256 * sizeof(uint4))) return rc;
+  // all six or none: `role` stands for the group
+  HIPCHK(h, raftq_buf::alloc_group({{(void**)&h->role, h->ld},
+                                    {(void**)&h->elapsed, h->ld * 4},
+                                    {(void**)&h->action, h->ld},
+                                    {(void**)&h->hup_bits, h->gpad / 8},
+                                    {(void**)&h->beat_bits, h->gpad / 8},
+                                    {(void**)&h->tick_partials, h->gpad / 256 * sizeof(uint4)}},
+                                   h->stream));
   return RAFTQ_OK;
 }
 
@@ -1235,14 +1084,14 @@ int raftq_tick_collect(raftq_t* h, uint64_t* hups, uint64_t hup_cap, uint64_t* n
     off_h = h->offsets;
     off_b = h->tick_offsets2;
   }
-  uint64_t* list_d = (uint64_t*)h->adv_d;
+  uint64_t* list_d = (uint64_t*)h->adv.d;
   hipLaunchKernelGGL(tick_lists_kernel, dim3((unsigned)(h->gpad / 1024)), dim3(kBlock), 0, h->stream, (const uint64_t*)h->hup_bits,
                      (const uint64_t*)h->beat_bits, (const uint4*)h->tick_partials, list_d, cap_h, list_d + cap_h, cap_b, h->d_total, off_h, off_b);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipStreamSynchronize(h->stream));
   *n_hup = h->h_total[0];
   *n_beat = h->h_total[1];
-  const uint64_t* list_h = (const uint64_t*)h->adv_h;
+  const uint64_t* list_h = (const uint64_t*)h->adv.h;
   if (const uint64_t take = std::min(*n_hup, cap_h)) std::memcpy(hups, list_h, take * 8);
   if (const uint64_t take = std::min(*n_beat, cap_b)) std::memcpy(beats, list_h + cap_h, take * 8);
   h->adv_listed = 0;
@@ -1266,18 +1115,7 @@ int raftq_detail::tick_lists_prepare(raftq_t* h, const char* who, unsigned flags
   const uint64_t map_off = ((beat_at + cap_b) * 4 + 255) / 256 * 256;
   const uint64_t need = map_off + h->gpad / 8 + 256;
   h->tl_valid = false;
-  if (need > h->tl_bytes) {
-    if (h->tl_h) {
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      HIPCHK(h, hipHostFree(h->tl_h));
-      h->tl_h = h->tl_d = nullptr;
-      h->tl_bytes = 0;
-    }
-    const uint64_t want = std::max<uint64_t>(need, 1 << 16);
-    HIPCHK(h, hipHostMalloc((void**)&h->tl_h, want, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(h, hipHostGetDevicePointer((void**)&h->tl_d, h->tl_h, 0));
-    h->tl_bytes = want;
-  }
+  HIPCHK(h, h->tl.grow(need, std::max<uint64_t>(need, 1 << 16), &h->stream));
   // every allocation is made BEFORE the Tick is enqueued: a call that fails has not ticked (an allocation failure
   // behind the tick kernel left the timers advanced and the MsgHup / MsgBeat groups of that tick unreported)
   if (h->gpad / 256 > (1u << 14))
@@ -1300,9 +1138,9 @@ int raftq_detail::tick_lists_enqueue(raftq_t* h, TickLists* tl) {
     off_b = h->tick_offsets2;
   }
   tl->off_beat = off_b;
-  uint32_t* const hup_d = h->tl_d;
-  uint32_t* const beat_d = h->tl_d + tl->beat_at;
-  uint64_t* const map_d = (uint64_t*)((uint8_t*)h->tl_d + tl->map_off);
+  uint32_t* const hup_d = h->tl.d;
+  uint32_t* const beat_d = h->tl.d + tl->beat_at;
+  uint64_t* const map_d = (uint64_t*)((uint8_t*)h->tl.d + tl->map_off);
   // one block of 1,024 groups per workgroup of the lists kernel.  Four (runs of ~1,600 ids instead of ~400 at the bench's density)
   // measured no better: 47.1 against 46.5 us a call -- 1.6 MB of ids take the link 34 us however they are cut
   const dim3 grid((unsigned)((nw + kWaves - 1) / kWaves));
@@ -1335,12 +1173,12 @@ int raftq_detail::tick_lists_finish(raftq_t* h, const char* who, const TickLists
       const volatile uint64_t* tot = (const volatile uint64_t*)h->h_total;
       const uint64_t t0 = tot[0], t1 = tot[1];
       uint64_t d = (t0 * 0x9E3779B97F4A7C15ull) ^ t1;
-      const volatile uint32_t* ids = (const volatile uint32_t*)h->tl_h;
+      const volatile uint32_t* ids = (const volatile uint32_t*)h->tl.h;
       const uint64_t nh = std::min<uint64_t>(t0, cap_h), nb = std::min<uint64_t>(t1, cap_b);
       for (uint64_t i = 0; i < nh; ++i) d = (d ^ ids[i]) * 0xBF58476D1CE4E5B9ull;
       for (uint64_t i = 0; i < nb; ++i) d = (d ^ ids[beat_at + i]) * 0xBF58476D1CE4E5B9ull;
       if (bitmap) {
-        const volatile uint64_t* mw = (const volatile uint64_t*)((const uint8_t*)h->tl_h + map_off);
+        const volatile uint64_t* mw = (const volatile uint64_t*)((const uint8_t*)h->tl.h + map_off);
         for (uint64_t i = 0; i < h->gpad / 64; ++i) d = (d ^ mw[i]) * 0xBF58476D1CE4E5B9ull;
       }
       return d;
@@ -1378,11 +1216,11 @@ int raftq_last_tick_lists(raftq_t* h, const uint32_t** hups, uint64_t* n_hups, c
   if (!h) return fail(nullptr, RAFTQ_EINVAL, "null handle");
   if (!h->tl_valid) return fail(h, RAFTQ_ESTATE, "raftq_last_tick_lists: no raftq_tick_collect_lists before it");
   const bool bitmap = h->tl_flags & RAFTQ_TICK_BEAT_BITMAP;
-  if (hups) *hups = h->tl_h;
+  if (hups) *hups = h->tl.h;
   if (n_hups) *n_hups = std::min(h->tl_n_hup, h->tl_hup_cap);
-  if (beats) *beats = bitmap ? nullptr : h->tl_h + h->tl_beat_at;
+  if (beats) *beats = bitmap ? nullptr : h->tl.h + h->tl_beat_at;
   if (n_beats) *n_beats = bitmap ? 0 : std::min(h->tl_n_beat, h->tl_beat_cap);
-  if (beat_bitmap) *beat_bitmap = bitmap ? (const uint64_t*)((const uint8_t*)h->tl_h + h->tl_map_off) : nullptr;
+  if (beat_bitmap) *beat_bitmap = bitmap ? (const uint64_t*)((const uint8_t*)h->tl.h + h->tl_map_off) : nullptr;
   if (bitmap_words) *bitmap_words = bitmap ? (h->G + 63) / 64 : 0;
   return RAFTQ_OK;
 }
@@ -1391,7 +1229,7 @@ int raftq_last_tick_lists(raftq_t* h, const uint32_t** hups, uint64_t* n_hups, c
 static int ensure_tick_offsets2(raftq_t* h, uint64_t nw) {
   if (h->tick_offsets2) return RAFTQ_OK;
   (void)nw;
-  HIPCHK(h, hipMalloc((void**)&h->tick_offsets2, (h->gpad / 256 + 1) * 8));
+  HIPCHK(h, raftq_buf::alloc_device((void**)&h->tick_offsets2, (h->gpad / 256 + 1) * 8));
   return RAFTQ_OK;
 }
 extern "C" {
@@ -1421,13 +1259,13 @@ static int collect_tick_list(raftq_t* h, const char* who, int field, uint64_t* g
                      h->d_total, field);
   if (take_cap)
     hipLaunchKernelGGL(compact_hups_kernel, dim3((unsigned)(h->gpad / 1024)), dim3(kBlock), 0, h->stream,
-                       field ? h->beat_bits : h->hup_bits, h->offsets, (uint64_t*)h->adv_d, take_cap);
+                       field ? h->beat_bits : h->hup_bits, h->offsets, (uint64_t*)h->adv.d, take_cap);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipStreamSynchronize(h->stream));
   const uint64_t total = *h->h_total;
   *n = total;
   const uint64_t take = std::min(total, take_cap);
-  if (take) std::memcpy(groups, h->adv_h, take * 8);
+  if (take) std::memcpy(groups, h->adv.h, take * 8);
   h->adv_listed = 0;
   return RAFTQ_OK;
 }
@@ -1450,9 +1288,9 @@ int raftq_campaign(raftq_t* h, const uint64_t* groups, uint64_t n, uint32_t self
   if (bad) return fail(h, RAFTQ_EINVAL, "raftq_campaign: a group is out of range; nothing applied");
   if (int rc = ensure_tick_state(h)) return rc;
   if (int rc = ensure_staging(h, (size_t)n * 8)) return rc;
-  std::memcpy(h->stage_h, groups, n * 8);
+  std::memcpy(h->stage.h, groups, n * 8);
   hipLaunchKernelGGL(campaign_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream,
-                     h->role, h->elapsed, h->votes, h->N, self_peer, (const uint64_t*)h->stage_d, n);
+                     h->role, h->elapsed, h->votes, h->N, self_peer, (const uint64_t*)h->stage.d, n);
   dense_changed(h);  // (role)
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1474,7 +1312,7 @@ static int enqueue_collect(raftq_t* h, uint64_t take_cap, bool want_flag) {
   static_assert(sizeof(Advance) == sizeof(raftq_advance_t) && sizeof(Advance16) == sizeof(raftq_advance16_t), "ABI struct mismatch");
   const int gpl = h->last_gpl;
   const dim3 grid((unsigned)(h->gpad / ((uint64_t)kBlock * gpl)));
-  Adv* out = (Adv*)h->adv_d;  // the pinned list holds either layout (sized for the larger one)
+  Adv* out = (Adv*)h->adv.d;  // the pinned list holds either layout (sized for the larger one)
   // Up to 16K waves (4M groups at 256 per wave) every compaction workgroup sums its predecessors' counts itself;
   // beyond that the quadratic total would show, so the one-workgroup scan runs first and hands in the offsets.
   const uint64_t* wave_offsets = nullptr;
@@ -1523,27 +1361,15 @@ static bool segments_ok(const raftq_t* h, unsigned flags) {
 static int enqueue_sweep_segments(raftq_t* h, unsigned flags) {
   const uint32_t n_tiles = (uint32_t)(h->gpad / kTile);
   if (int rc = ensure_adv(h, (h->gpad * sizeof(Advance16) + sizeof(Advance) - 1) / sizeof(Advance))) return rc;  // a segment per tile, a 16-byte slot per group
-  if (h->seg_cap < n_tiles) {
-    if (h->seg_h) {
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      HIPCHK(h, hipHostFree(h->seg_h));
-      HIPCHK(h, hipFree(h->seg_d));
-      h->seg_h = h->seg_hd = nullptr;
-      h->seg_d = nullptr;
-      h->seg_cap = 0;
-    }
-    HIPCHK(h, hipHostMalloc((void**)&h->seg_h, (size_t)n_tiles * 4, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(h, hipHostGetDevicePointer((void**)&h->seg_hd, h->seg_h, 0));
-    HIPCHK(h, hipMalloc((void**)&h->seg_d, (size_t)n_tiles * 4));
-    h->seg_cap = n_tiles;
-  }
+  HIPCHK(h, h->seg_h.grow((size_t)n_tiles * 4, (size_t)n_tiles * 4, &h->stream));
+  HIPCHK(h, h->seg_d.grow((size_t)n_tiles * 4, (size_t)n_tiles * 4, &h->stream));
   const SweepArgs a = sweep_args(h, h->cur, true);
   uint64_t epoch = ++h->compact_epoch;
   if ((uint32_t)epoch == 0) epoch = ++h->compact_epoch;  // (the word's top half is never 0 for a turn in flight)
-  HIPCHK(h, launch_segments(h->N, a, n_tiles, (flags & RAFTQ_SWEEP_GATED) != 0, sweep_policy(flags, sweep_footprint(h)), (Advance16*)h->adv_d, h->seg_hd,
-                            h->seg_d, h->stream));
+  HIPCHK(h, launch_segments(h->N, a, n_tiles, (flags & RAFTQ_SWEEP_GATED) != 0, sweep_policy(flags, sweep_footprint(h)), (Advance16*)h->adv.d, h->seg_h.d,
+                            h->seg_d.d, h->stream));
   sweep_done(h, flags, kGPL);
-  hipLaunchKernelGGL(raise_flag_segments_kernel, dim3(1), dim3(kBlock), 0, h->stream, h->d_total + 3, (uint32_t)epoch, h->seg_d, n_tiles);
+  hipLaunchKernelGGL(raise_flag_segments_kernel, dim3(1), dim3(kBlock), 0, h->stream, h->d_total + 3, (uint32_t)epoch, h->seg_d.d, n_tiles);
   HIPCHK(h, hipGetLastError());
   h->compact_epoch_armed = (uint64_t)(uint32_t)epoch << 32;
   h->flag_mask = 0xffffffff00000000ull;
@@ -1571,7 +1397,7 @@ int raftq_collect_changed(raftq_t* h, raftq_advance_t* out, uint64_t cap, uint64
   h->adv_listed = take;
   h->adv_packed = false;
   h->adv_segmented = false;
-  if (take) std::memcpy(out, h->adv_h, take * sizeof(Advance));
+  if (take) std::memcpy(out, h->adv.h, take * sizeof(Advance));
   return RAFTQ_OK;
 }
 
@@ -1584,8 +1410,8 @@ int raftq_stage(raftq_t* h, uint64_t n_deltas, uint64_t n_vote_deltas, raftq_del
   if (int rc = use_device_idle(h, "raftq_stage")) return rc;
   const size_t off_votes = vote_stage_offset(n_deltas);
   if (int rc = ensure_ingest(h, off_votes + (size_t)n_vote_deltas * sizeof(raftq_vote_delta_t) + 256)) return rc;
-  if (deltas) *deltas = (raftq_delta_t*)h->ingest_h;
-  if (vote_deltas) *vote_deltas = (raftq_vote_delta_t*)((uint8_t*)h->ingest_h + off_votes);
+  if (deltas) *deltas = (raftq_delta_t*)h->ingest.h;
+  if (vote_deltas) *vote_deltas = (raftq_vote_delta_t*)((uint8_t*)h->ingest.h + off_votes);
   return RAFTQ_OK;
 }
 
@@ -1594,7 +1420,7 @@ int raftq_last_advances(raftq_t* h, const raftq_advance_t** list, uint64_t* n_li
   if (!list || !n_listed) return fail(h, RAFTQ_EINVAL, "raftq_last_advances: null argument");
   if (h->adv_listed && h->adv_packed)
     return fail(h, RAFTQ_ESTATE, "raftq_last_advances: the last list was produced in the packed layout");
-  *list = (const raftq_advance_t*)h->adv_h;
+  *list = (const raftq_advance_t*)h->adv.h;
   *n_listed = h->adv_listed;
   return RAFTQ_OK;
 }
@@ -1668,10 +1494,10 @@ static int cycle_impl(raftq_t* h, const char* who, const AbiRec* deltas, uint64_
   {
     const size_t need = off_votes + (size_t)n_vote_deltas * sizeof(raftq_vote_delta_t) + 256;
     auto staged = [&](const void* q) {
-      return q && h->ingest_h && (const uint8_t*)q >= (const uint8_t*)h->ingest_h &&
-             (const uint8_t*)q < (const uint8_t*)h->ingest_h + h->ingest_bytes;
+      return q && h->ingest.h && (const uint8_t*)q >= (const uint8_t*)h->ingest.h &&
+             (const uint8_t*)q < (const uint8_t*)h->ingest.h + h->ingest.cap;
     };
-    if (need > h->ingest_bytes && (staged(deltas) || staged(vote_deltas)))  // growing would free what the caller points into
+    if (need > h->ingest.cap && (staged(deltas) || staged(vote_deltas)))  // growing would free what the caller points into
       return fail(h, RAFTQ_EINVAL, std::string(who) + ": the staged arrays were sized for fewer records than this call names");
     if (int rc = ensure_ingest(h, need)) return rc;
   }
@@ -1713,11 +1539,11 @@ static int cycle_impl(raftq_t* h, const char* who, const AbiRec* deltas, uint64_
     static const bool check = [] { const char* e = std::getenv("RAFTQ_CYCLE_CHECK"); return e && e[0] == '1'; }();
     if (check) {
       auto digest = [&]() {
-        const volatile uint64_t* w = (const volatile uint64_t*)h->adv_h;
+        const volatile uint64_t* w = (const volatile uint64_t*)h->adv.h;
         if (segmented) {  // every segment's count and records
           uint64_t d = (h->h_total[3] & 0xffffffffull) * 0x9E3779B97F4A7C15ull;
           for (uint32_t t = 0; t < h->seg_tiles; ++t) {
-            const uint32_t c = ((const volatile uint32_t*)h->seg_h)[t];
+            const uint32_t c = ((const volatile uint32_t*)h->seg_h.h)[t];
             d = (d ^ c) * 0xBF58476D1CE4E5B9ull;
             for (uint64_t i = 0; i < (uint64_t)c * 2; ++i) d = (d ^ w[(uint64_t)t * h->seg_stride * 2 + i]) * 0xBF58476D1CE4E5B9ull;
           }
@@ -1777,7 +1603,7 @@ static int cycle_impl(raftq_t* h, const char* who, const AbiRec* deltas, uint64_
     h->adv_listed = take;
     h->adv_packed = sizeof(Adv) == sizeof(Advance16);
     // advances_out == NULL: the caller reads the pinned list in place (raftq_last_advances*)
-    if (take && advances_out) std::memcpy(advances_out, h->adv_h, take * sizeof(Adv));
+    if (take && advances_out) std::memcpy(advances_out, h->adv.h, take * sizeof(Adv));
   }
   return verdict;  // RAFTQ_CYCLE_TRUSTED: a dropped record is still reported, with every output filled in
 }
@@ -1805,8 +1631,8 @@ int raftq_stage_packed(raftq_t* h, uint64_t n_deltas, uint64_t n_vote_deltas, ra
   if (int rc = use_device_idle(h, "raftq_stage_packed")) return rc;
   const size_t off_votes = ((size_t)n_deltas * sizeof(raftq_delta16_t) + 255) / 256 * 256;
   if (int rc = ensure_ingest(h, off_votes + (size_t)n_vote_deltas * sizeof(raftq_vote_delta_t) + 256)) return rc;
-  if (deltas) *deltas = (raftq_delta16_t*)h->ingest_h;
-  if (vote_deltas) *vote_deltas = (raftq_vote_delta_t*)((uint8_t*)h->ingest_h + off_votes);
+  if (deltas) *deltas = (raftq_delta16_t*)h->ingest.h;
+  if (vote_deltas) *vote_deltas = (raftq_vote_delta_t*)((uint8_t*)h->ingest.h + off_votes);
   return RAFTQ_OK;
 }
 
@@ -1817,7 +1643,7 @@ int raftq_last_advances_packed(raftq_t* h, const raftq_advance16_t** list, uint6
     return fail(h, RAFTQ_ESTATE, "raftq_last_advances_packed: the last list was produced in the 24-byte layout");
   if (h->adv_segmented)
     return fail(h, RAFTQ_ESTATE, "raftq_last_advances_packed: the last list lies in segments (raftq_last_advance_segments)");
-  *list = (const raftq_advance16_t*)h->adv_h;
+  *list = (const raftq_advance16_t*)h->adv.h;
   *n_listed = h->adv_listed;
   return RAFTQ_OK;
 }
@@ -1827,9 +1653,9 @@ int raftq_last_advance_segments(raftq_t* h, const raftq_advance16_t** recs, cons
   if (!recs || !counts || !n_segments || !stride) return fail(h, RAFTQ_EINVAL, "raftq_last_advance_segments: null argument");
   if (h->adv_listed && !h->adv_packed)
     return fail(h, RAFTQ_ESTATE, "raftq_last_advance_segments: the last list was produced in the 24-byte layout");
-  *recs = (const raftq_advance16_t*)h->adv_h;
+  *recs = (const raftq_advance16_t*)h->adv.h;
   if (h->adv_segmented) {
-    *counts = h->seg_h;
+    *counts = h->seg_h.h;
     *n_segments = h->seg_tiles;
     *stride = h->seg_stride;
   } else {  // a contiguous list is one segment

@@ -9,6 +9,7 @@
 #include "raftq.h"
 #include "raftq_wire.h"
 #include "raftq_kernels.hpp"
+#include "raftq_buffers.hpp"
 
 struct raftq {
   int device = 0;
@@ -33,47 +34,35 @@ struct raftq {
   uint64_t max_partials = 0;
   uint64_t* offsets = nullptr;  // [max_partials + 1]; last = total
   uint64_t* h_total = nullptr;  // pinned
-  // pinned, device-mapped host buffers: deltas go in, advances come out, both
-  // accessed by the kernels directly over PCIe (no staging memcpy launches)
-  void* stage_h = nullptr;      // delta staging (host pointer)
-  void* stage_d = nullptr;      // same memory, device pointer
-  size_t stage_bytes = 0;
-  // The batching turn's ack buffer (raftq_stage*, raftq_cycle*, raftq_apply_[vote_]deltas).  On a device whose memory
-  // the host can address (large BAR) it lives IN HBM: the producer's stores are posted PCIe writes that land in device
-  // memory as the acks arrive (45 GB/s measured from one core), and the ingest kernel reads HBM instead of pulling the
-  // batch over PCIe in 64-byte requests (35 GB/s, 30 of a turn's 52 kernel-us).  Fine-grained, so the GPU never serves
-  // it from a stale L2 line.  The host only ever WRITES it (reads over the BAR are uncached and slow), which is why
-  // calls that read results back from staging keep the pinned buffer above.  Elsewhere it is pinned host memory.
-  void* ingest_h = nullptr;     // what the host writes
-  void* ingest_d = nullptr;     // what the kernels read (same pointer when the buffer is device memory)
-  size_t ingest_bytes = 0;
-  bool ingest_in_device = false;
-  bool bar_staging = false;     // decided at create: large BAR present and not disabled (RAFTQ_STAGE=host)
-  bool bar_probed = false;      // such memory has been found mapped writable into this process (/proc/self/maps)
+  // The buffers below own their memory (raftq_buffers.hpp): members of the handle, released when it is deleted -- after
+  // raftq_destroy's waits and before it destroys the handle's streams.
+  // Delta staging the kernels access directly over PCIe (no staging memcpy launches); calls that read results back use it.
+  raftq_buf::Buffer<> stage{raftq_buf::Kind::mapped};
+  // The batching turn's ack buffer (raftq_stage*, raftq_cycle*, raftq_apply_[vote_]deltas).  Behind a large BAR it lives IN
+  // HBM: posted PCIe writes land there as the acks arrive (45 GB/s measured from one core) and the ingest kernel reads HBM
+  // instead of pulling the batch over PCIe in 64-byte requests (35 GB/s, 30 of a turn's 52 kernel-us).  The host only ever
+  // WRITES it (reads over the BAR are uncached and slow).
+  raftq_buf::HostWritable ingest;
+  raftq_buf::BarRule bar;       // .staging decided at create: large BAR present and not disabled (RAFTQ_STAGE=host)
   // raftq_apply_log_deltas' host bookkeeping, kept across calls: per-group (epoch << 32 | records seen this call)
   std::vector<uint64_t> ld_mark, ld_start;
   // raftq_apply_log_deltas_nowait: two pinned staging areas taken in turn, an event each (the kernels that read it have run)
   struct LdNowait {
-    void* host = nullptr;
-    void* dev = nullptr;
-    size_t bytes = 0;
+    raftq_buf::Buffer<> buf{raftq_buf::Kind::mapped};
     hipEvent_t ev = nullptr;
   };
   LdNowait ld_nowait[2];
   uint32_t ld_nowait_next = 0;
   std::vector<uint32_t> ld_round, ld_pos;
   uint32_t ld_epoch = 0;
-  raftqk::Advance* adv_h = nullptr;     // compacted advance list (host pointer)
-  raftqk::Advance* adv_d = nullptr;
-  uint64_t adv_cap = 0;
-  uint64_t adv_listed = 0;     // entries of adv_h valid after the last collect / cycle
+  raftq_buf::Buffer<raftqk::Advance> adv{raftq_buf::Kind::mapped_coherent};  // compacted advance list
+  uint64_t adv_listed = 0;     // entries of adv.h valid after the last collect / cycle
   bool adv_packed = false;     // ... in the 16-byte layout (raftq_cycle_packed)
-  // RAFTQ_CYCLE_SEGMENTED: the last list lies in adv_h as one segment of seg_stride records per sweep tile, seg_h[t] of them valid
+  // RAFTQ_CYCLE_SEGMENTED: the last list lies in adv.h as one segment of seg_stride records per sweep tile, seg_h.h[t] of them valid
   bool adv_segmented = false;
-  uint32_t* seg_h = nullptr;   // pinned [seg_cap] per-tile counts
-  uint32_t* seg_hd = nullptr;  // ... as the device addresses them
-  unsigned int* seg_d = nullptr;  // device copy (the flag kernel adds them up)
-  uint32_t seg_cap = 0, seg_tiles = 0, seg_stride = 0, seg_one = 0;  // seg_one: the count of a contiguous list presented as one segment
+  raftq_buf::Buffer<uint32_t> seg_h{raftq_buf::Kind::mapped_coherent};  // per-tile counts
+  raftq_buf::Buffer<unsigned int> seg_d{raftq_buf::Kind::device};       // device copy (the flag kernel adds them up)
+  uint32_t seg_tiles = 0, seg_stride = 0, seg_one = 0;  // seg_one: the count of a contiguous list presented as one segment
   uint64_t flag_mask = ~0ull;  // which bits of the completion word are the epoch the turn's wait compares (segmented: the top half)
   uint32_t* self_max = nullptr;  // device: the self-max word (raftq_kernels.hpp) -- which match row is every group's largest
   uint64_t compact_epoch = 0;  // completion-flag values handed to hipStreamWriteValue64 (h_total[3])
@@ -85,8 +74,7 @@ struct raftq {
   uint64_t flag_fallbacks = 0;                // turns that ended in the blocking wait although a flag was armed
   uint32_t* claim = nullptr;    // u32 [N][ld] vote-slot claims, lazily allocated
   // sparse ingest: device copy of the batch (validated on the way in) and the "bad batch" epoch words
-  void* delta_dev = nullptr;
-  size_t delta_dev_bytes = 0;
+  raftq_buf::Buffer<> delta_dev{raftq_buf::Kind::device};
   unsigned long long* delta_bad = nullptr;  // device: [0] match deltas, [1] vote deltas -- epoch of the last bad batch
   unsigned long long delta_epoch = 0;       // batches enqueued so far
   unsigned long long delta_check[2] = {0, 0};  // epochs whose host-visible flag (h_total[1], [2]) is still to be checked
@@ -98,9 +86,8 @@ struct raftq {
   uint64_t* beat_bits = nullptr; // [gpad/64]
   uint4* tick_partials = nullptr;  // [gpad/256]
   // raftq_tick_collect_lists: the two lists left in place (page-locked; 4-byte group ids; MsgBeat optionally as a bitmap)
-  uint32_t* tl_h = nullptr;     // pinned: [tl_hup_cap] MsgHup ids | [tl_beat_cap] MsgBeat ids | beat bitmap (gpad / 64 words, 16-byte aligned)
-  uint32_t* tl_d = nullptr;     // ... as the device addresses it
-  uint64_t tl_bytes = 0, tl_hup_cap = 0, tl_beat_cap = 0, tl_beat_at = 0, tl_map_off = 0;  // tl_beat_at: index of the first MsgBeat id; tl_map_off: byte offset of the bitmap
+  raftq_buf::Buffer<uint32_t> tl{raftq_buf::Kind::mapped_coherent};  // [tl_hup_cap] MsgHup ids | [tl_beat_cap] MsgBeat ids | beat bitmap (gpad / 64 words, 16-byte aligned)
+  uint64_t tl_hup_cap = 0, tl_beat_cap = 0, tl_beat_at = 0, tl_map_off = 0;  // tl_beat_at: index of the first MsgBeat id; tl_map_off: byte offset of the bitmap
   uint64_t tl_n_hup = 0, tl_n_beat = 0;
   unsigned tl_flags = 0;
   bool tl_valid = false;
@@ -136,15 +123,12 @@ struct raftq {
   // device AND be handing over batch k+2 -- with two slots that form lost to round 1's (profiles/r02/step_deferred_copy_ab.txt).
   static constexpr int kStepSlots = 3;
   struct StepSlot {
-    void* in_h = nullptr;          // pinned staging: the copying forms (caller-owned arrays, received frames) go through it
-    size_t in_bytes = 0;
-    void* in_bar = nullptr;        // what raftq_step_stage hands out behind a large BAR: fine-grained DEVICE memory the
-    size_t in_bar_bytes = 0;       // producer writes in place (posted PCIe writes); the batch then never needs a DMA
-    void* dev = nullptr;           // device scratch: msgs, keys, order, outs, sort temp, flags
-    size_t dev_bytes = 0;
-    void* out_h = nullptr;         // pinned, device-mapped result records + {touched-group count, bad flag}
-    void* out_d = nullptr;         // device alias of out_h
-    size_t out_bytes = 0;
+    raftq_buf::Buffer<> in_h{raftq_buf::Kind::pinned};  // staging: the copying forms (caller-owned arrays, received frames) go through it
+    // what raftq_step_stage hands out behind a large BAR: fine-grained DEVICE memory the producer writes in place (posted PCIe
+    // writes); the batch then never needs a DMA.  Device memory or empty: without a BAR the slot stages in in_h
+    raftq_buf::HostWritable in_bar;
+    raftq_buf::Buffer<> dev{raftq_buf::Kind::device};  // scratch: msgs, keys, order, outs, sort temp, flags
+    raftq_buf::Buffer<> out{raftq_buf::Kind::mapped};  // result records + {touched-group count, bad flag}
     uint64_t n = 0;
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
     bool busy = false;
@@ -174,8 +158,7 @@ struct raftq {
     void* w_ents_d = nullptr;      // raftq_wire_ent_t [w_ents_cap]
     const uint64_t* w_ent_total_d = nullptr;
     uint64_t w_ents_cap = 0;
-    void* w_pin = nullptr;         // pinned: msgs, then entries
-    size_t w_pin_bytes = 0;
+    raftq_buf::Buffer<> w_pin{raftq_buf::Kind::pinned};  // msgs, then entries
     bool w_msgs_fetched = false, w_ents_fetched = false;
     uint64_t w_n_ents = 0;
   } step_slot[kStepSlots];
@@ -192,24 +175,21 @@ struct raftq {
   hipEvent_t many_fork = nullptr, many_join = nullptr;
   // wire / WAL codecs (raftq_wire.hip): growable device scratch (inputs + temporaries), device
   // output buffer, a small pinned block for totals / flags
-  void* wire_dev = nullptr;
-  uint64_t wire_dev_bytes = 0;
-  void* wire_out = nullptr;
-  uint64_t wire_out_bytes = 0;
+  raftq_buf::Buffer<> wire_dev{raftq_buf::Kind::device};
+  raftq_buf::Buffer<> wire_out{raftq_buf::Kind::device};
   uint64_t* wire_pin = nullptr;    // pinned, 256 bytes: four result words behind each of kPinCall / kPinWalPending / kPinRespond (raftq_wire.hip)
   uint64_t* wire_pin_d = nullptr;  // the same block as the device addresses it (the codecs' last kernel writes totals / flags there)
   unsigned long long* wire_flags = nullptr;  // device, 64 bytes, zero between calls: the codecs' malformed counters / bad flags
   // the streaming codec kernels (raftq_wire_kernels.hpp "the streaming form"): ticket word + per-tile look-back status
-  unsigned long long* wire_lb = nullptr;     // device: kLbHead words {ticket, gave-up flag | landed waves | - | chunk ticket}, then kLbArrays status arrays of wire_lb_tiles words
-  uint64_t wire_lb_tiles = 0;
+  raftq_buf::Buffer<unsigned long long> wire_lb{raftq_buf::Kind::device};  // kLbHead words {ticket, gave-up flag | landed waves | - | chunk ticket}, then kLbArrays status arrays of wire_lb_tiles words
+  uint64_t wire_lb_tiles = 0;                // words per status array; 0: no block, or one that is not trusted any more
   uint32_t wire_ticket_base = 0, wire_epoch = 0;
   uint32_t wire_chunk_base = 0, wire_chunk_pending = 0;  // the readers' chunk tickets (the head's fourth word), accounted like the tiles'
   bool wire_chunk_unknown = false;           // the last launch had no reader workgroups: how far its chunk ticket got is not known
   unsigned int prop_stamp = 0;               // raftq_propose_frames: the call's stamp (its validation's verdict word holds it when a record was refused)
   // raftq_step_frames_respond: the walk's response records + the layout's counts (device), and what the walk reads while the
   // call is on (resp_on): the call's stamp, the caller's at-tail bitmap as the device addresses it
-  void* resp_dev = nullptr;
-  uint64_t resp_dev_bytes = 0;
+  raftq_buf::Buffer<> resp_dev{raftq_buf::Kind::device};
   bool resp_on = false;
   uint32_t resp_stamp = 0;
   const uint64_t* resp_at_tail_d = nullptr;
@@ -272,7 +252,6 @@ int use_device_idle(raftq_t* h, const char* who);  // + no Step batch in flight 
 int refuse_voters(raftq_t* h, const char* who);
 int self_max_check(raftq_t* h);                 // the self-max word re-derived from the rows for h->self_peer (enqueued)
 int ensure_staging(raftq_t* h, size_t bytes);   // pinned, device-mapped staging (term deltas, campaign lists, log deltas)
-bool host_can_write(void* p, size_t bytes);     // [p, p + bytes) is mapped writable into this process (/proc/self/maps)
 int ensure_ingest(raftq_t* h, size_t bytes);    // the ack buffer of the batching turn: device memory behind a large BAR, else pinned
 int ensure_tick_state(raftq_t* h);              // role / elapsed / action (+ hup bitmap)
 void free_node_state(raftq_t* h);               // raftq_step.hip's allocations (called by raftq_destroy)

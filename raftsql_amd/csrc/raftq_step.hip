@@ -38,24 +38,20 @@ uint32_t result_rec_bytes(const raftq_t* h) {
 int ensure_node_state(raftq_t* h) {
   if (h->node_rec) return RAFTQ_OK;
   if (int rc = ensure_tick_state(h)) return rc;  // role, elapsed
-  auto alloc = [&](void** p, size_t bytes) -> int {
-    HIPCHK(h, hipMalloc(p, bytes));
-    HIPCHK(h, hipMemsetAsync(*p, 0, bytes, h->stream));
-    return RAFTQ_OK;
-  };
-  if (!h->step_stall)  // (a retry after a failed launch below finds it allocated: ADVICE r05, 256 bytes leaked per failed attempt)
-    if (int rc = alloc((void**)&h->step_stall, 256)) return rc;
   if (const char* w = std::getenv("RAFTQ_STEP_WALK")) h->step_walk_mode = std::strcmp(w, "sort") == 0 ? 0 : 1;
   // h->node_rec marks the state complete: it is assigned only once the records have been allocated AND their initialisation has
-  // been launched (a failed launch used to leave the pointer set, and the next call stepped uninitialised records)
+  // been launched (a failed launch used to leave the pointer set, and the next call stepped uninitialised records).
+  // The stall word and the records come as a pair or not at all (256 bytes leaked per failed attempt).
   void* rec = nullptr;
-  HIPCHK(h, hipMalloc(&rec, h->ld * sizeof(NodeRec)));
+  void* stall = nullptr;
+  HIPCHK(h, raftq_buf::alloc_group({{&stall, 256}, {&rec, h->ld * sizeof(NodeRec), raftq_buf::Kind::device, nullptr, /*zero=*/false}}, h->stream));
   hipLaunchKernelGGL(node_init_kernel, dim3((unsigned)((h->ld + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, (NodeRec*)rec, h->ld);
   if (const hipError_t e = hipGetLastError(); e != hipSuccess) {
-    (void)hipFree(rec);
+    raftq_buf::free_device(rec, stall);
     HIPCHK(h, e);
   }
-  h->node_rec = (decltype(h->node_rec))rec;
+  h->step_stall = (unsigned int*)stall;
+  h->node_rec = rec;
   h->have_terms = true;  // Step maintains the current-term gate itself (closed = 0 until a group leads)
   return RAFTQ_OK;
 }
@@ -77,7 +73,7 @@ NodeArrays node_arrays(raftq_t* h, uint8_t recs = raftqk::kRecsCaller) {
   a.n_groups = h->G;
   a.self_max = h->self_max;
   if (h->resp_on) {  // raftq_step_frames_respond: the walks (the list walk, the sorted one, a stalled batch's replay) answer too
-    a.resp = (raftqk::RespRec*)h->resp_dev;
+    a.resp = (raftqk::RespRec*)h->resp_dev.d;
     a.at_tail = h->resp_at_tail_d;
     a.resp_stamp = h->resp_stamp;
   }
@@ -136,7 +132,7 @@ size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 // result area: n records of `rec` bytes, then (16-byte aligned) the {touched count, bad, skipped} tail
 size_t tail_off(uint64_t n, uint32_t rec) { return ((size_t)n * rec + 15) / 16 * 16; }
 
-int ensure_slot(raftq_t* h, raftq::StepSlot& sl, uint64_t n, int end_bit, Scratch* s, bool wire = false,
+int ensure_slot(raftq_t* h, raftq::StepSlot& sl, uint64_t n, Scratch* s, bool wire = false,
                 uint64_t wire_nbytes = 0) {
   if (!h->step_s_in) {
     HIPCHK(h, hipStreamCreateWithFlags(&h->step_s_in, hipStreamNonBlocking));
@@ -154,7 +150,6 @@ int ensure_slot(raftq_t* h, raftq::StepSlot& sl, uint64_t n, int end_bit, Scratc
     HIPCHK(h, hipEventCreateWithFlags(&sl.ev_in, hipEventDisableTiming));
     HIPCHK(h, hipEventCreateWithFlags(&sl.ev_out, hipEventDisableTiming));
   }
-  (void)end_bit;
   const size_t sort_bytes = raftqk::radix_plan(n).bytes;  // digit counts of the hand-written radix sort (raftq_sort_kernels.hpp)
   size_t off = 0;
   auto carve = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
@@ -175,31 +170,12 @@ int ensure_slot(raftq_t* h, raftq::StepSlot& sl, uint64_t n, int end_bit, Scratc
     o_wents = carve(w_ents_cap * sizeof(WireEnt));
     o_wscan = carve(w_scan_bytes);
   }
-  if (off > sl.dev_bytes) {  // the slot is idle (its previous batch was collected): safe to regrow
-    if (sl.dev) {
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      HIPCHK(h, hipFree(sl.dev));
-      sl.dev = nullptr;
-      sl.dev_bytes = 0;
-    }
-    const size_t want = std::max(off, (size_t)1 << 20) * 2;
-    HIPCHK(h, hipMalloc(&sl.dev, want));
-    sl.dev_bytes = want;
-  }
+  // the slot is idle (its previous batch was collected): safe to regrow
+  HIPCHK(h, sl.dev.grow(off, std::max(off, (size_t)1 << 20) * 2, &h->stream));
   const size_t out_bytes = (size_t)n * sizeof(StepOutRec) + 16;
-  if (out_bytes > sl.out_bytes) {
-    if (sl.out_h) {
-      if (h->step_last_out == sl.out_h) h->step_last_out = nullptr, h->step_last_n = 0;
-      HIPCHK(h, hipHostFree(sl.out_h));
-      sl.out_h = sl.out_d = nullptr;
-      sl.out_bytes = 0;
-    }
-    const size_t want = std::max(out_bytes * 2, (size_t)1 << 20);
-    HIPCHK(h, hipHostMalloc(&sl.out_h, want, hipHostMallocMapped));
-    HIPCHK(h, hipHostGetDevicePointer(&sl.out_d, sl.out_h, 0));
-    sl.out_bytes = want;
-  }
-  uint8_t* base = (uint8_t*)sl.dev;
+  if (out_bytes > sl.out.cap && sl.out.h && h->step_last_out == sl.out.h) h->step_last_out = nullptr, h->step_last_n = 0;
+  HIPCHK(h, sl.out.grow(out_bytes, std::max(out_bytes * 2, (size_t)1 << 20), nullptr));
+  uint8_t* base = (uint8_t*)sl.dev.d;
   s->msgs = (MsgRec*)(base + o_msgs);
   s->msgs40 = base + o_m40;
   s->outs = base + o_outs;
@@ -225,48 +201,22 @@ int ensure_slot(raftq_t* h, raftq::StepSlot& sl, uint64_t n, int end_bit, Scratc
 
 int ensure_slot_staging(raftq_t* h, raftq::StepSlot& sl, uint64_t n, size_t raw_bytes = 0) {
   const size_t bytes = raw_bytes ? raw_bytes : (size_t)std::max<uint64_t>(n, 1) * sizeof(raftq_msg_t);
-  if (bytes <= sl.in_bytes) return RAFTQ_OK;
-  if (sl.in_h) {
-    HIPCHK(h, hipHostFree(sl.in_h));
-    sl.in_h = nullptr;
-    sl.in_bytes = 0;
-  }
-  const size_t want = std::max(bytes * 2, (size_t)1 << 20);
-  HIPCHK(h, hipHostMalloc(&sl.in_h, want, hipHostMallocDefault));
-  sl.in_bytes = want;
+  HIPCHK(h, sl.in_h.grow(bytes, std::max(bytes * 2, (size_t)1 << 20), nullptr));
   return RAFTQ_OK;
 }
 
 // the in-place staging of raftq_step_stage: device memory the host can write (large BAR), else the pinned buffer
 int ensure_slot_bar(raftq_t* h, raftq::StepSlot& sl, uint64_t n, void** out, size_t raw_bytes = 0) {
   const size_t bytes = raw_bytes ? raw_bytes : (size_t)std::max<uint64_t>(n, 1) * sizeof(raftq_msg_t);
-  if (h->bar_staging) {
-    if (bytes > sl.in_bar_bytes) {
-      if (sl.in_bar) {
-        HIPCHK(h, hipFree(sl.in_bar));
-        sl.in_bar = nullptr;
-        sl.in_bar_bytes = 0;
-      }
-      const size_t want = std::max(bytes * 2, (size_t)1 << 20);
-      void* p = nullptr;
-      if (hipExtMallocWithFlags(&p, want, hipDeviceMallocFinegrained) == hipSuccess &&
-          (h->bar_probed || raftq_detail::host_can_write(p, want))) {
-        h->bar_probed = true;
-        sl.in_bar = p;
-        sl.in_bar_bytes = want;
-      } else {
-        if (p) (void)hipFree(p);
-        (void)hipGetLastError();
-        h->bar_staging = false;
-      }
-    }
-    if (sl.in_bar) {
-      *out = sl.in_bar;
+  if (h->bar.staging) {
+    HIPCHK(h, sl.in_bar.grow_bar(bytes, std::max(bytes * 2, (size_t)1 << 20), nullptr, h->bar));
+    if (sl.in_bar.h) {
+      *out = sl.in_bar.h;
       return RAFTQ_OK;
     }
   }
   if (int rc = ensure_slot_staging(h, sl, n, raw_bytes)) return rc;
-  *out = sl.in_h;
+  *out = sl.in_h.h;
   return RAFTQ_OK;
 }
 
@@ -304,26 +254,15 @@ int node_fields(raftq_t* h, bool put, uint64_t* term, uint32_t* vote, uint32_t* 
 }  // namespace
 
 void raftq_detail::free_node_state(raftq_t* h) {
-  (void)hipFree(h->node_rec);
-  h->node_rec = nullptr;
-  (void)hipFree(h->step_stall);
   for (auto& sl : h->step_slot) {
     if (sl.busy && sl.copy_pending && h->stream) (void)hipStreamSynchronize(h->stream);  // its kernels; the copy never ran
     else if (sl.ev_out && sl.busy) (void)hipEventSynchronize(sl.ev_out);
-    (void)hipFree(sl.dev);
-    if (sl.in_h) (void)hipHostFree(sl.in_h);
-    if (sl.in_bar) (void)hipFree(sl.in_bar);
-    if (sl.out_h) (void)hipHostFree(sl.out_h);
-    if (sl.w_pin) (void)hipHostFree(sl.w_pin);
     if (sl.ev_in) (void)hipEventDestroy(sl.ev_in);
     if (sl.ev_out) (void)hipEventDestroy(sl.ev_out);
   }
-  for (auto& q : h->ld_nowait) {
+  for (auto& q : h->ld_nowait)
     if (q.ev) (void)hipEventDestroy(q.ev);
-    if (q.host) (void)hipHostFree(q.host);
-  }
-  if (h->step_s_in) (void)hipStreamDestroy(h->step_s_in);
-  if (h->step_s_out) (void)hipStreamDestroy(h->step_s_out);
+  raftq_buf::free_device(h->node_rec, h->step_stall);
 }
 
 extern "C" {
@@ -466,8 +405,8 @@ static int enqueue_list_walk(raftq_t* h, const Scratch& s, uint64_t n, uint8_t r
   raftqk::CopyRide in_link{nullptr, nullptr, 0, 0, 0, 0}, in_walk = in_link;
   if (carry) {
     const uint64_t quads = carry->out_quads, cut = quads * 25 / 100;
-    in_link = {(const u64x2*)carry->outs_d, (u64x2*)carry->out_d, 0, cut, quads - 1, cut ? d2h_blocks(cut) : 0u};
-    in_walk = {(const u64x2*)carry->outs_d, (u64x2*)carry->out_d, cut, quads, quads - 1, d2h_blocks(quads - cut)};
+    in_link = {(const u64x2*)carry->outs_d, (u64x2*)carry->out.d, 0, cut, quads - 1, cut ? d2h_blocks(cut) : 0u};
+    in_walk = {(const u64x2*)carry->outs_d, (u64x2*)carry->out.d, cut, quads, quads - 1, d2h_blocks(quads - cut)};
   }
   hipLaunchKernelGGL(step_link_kernel, dim3(blocks + in_link.blocks), dim3(kBlock), 0, h->stream, (const MsgRec*)s.msgs, n, h->G,
                      h->N, h->step_msg_flags, recs, (NodeRec*)h->node_rec, s.next, bad, h->step_stall, s.outs, h->step_compact, in_link);
@@ -484,7 +423,7 @@ static int enqueue_list_walk(raftq_t* h, const Scratch& s, uint64_t n, uint8_t r
 
 // the slot's result records (and tail) -> its pinned host buffer, as a kernel of its own
 static int enqueue_result_copy(raftq_t* h, raftq::StepSlot& sl, hipStream_t st) {
-  hipLaunchKernelGGL(step_d2h_kernel, dim3(d2h_blocks(sl.out_quads)), dim3(kBlock), 0, st, (const u64x2*)sl.outs_d, (u64x2*)sl.out_d,
+  hipLaunchKernelGGL(step_d2h_kernel, dim3(d2h_blocks(sl.out_quads)), dim3(kBlock), 0, st, (const u64x2*)sl.outs_d, (u64x2*)sl.out.d,
                      sl.out_quads, true);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipEventRecord(sl.ev_out, st));
@@ -529,19 +468,17 @@ static int submit_impl(raftq_t* h, const void* msgs, uint64_t n, const WireSrc* 
       return b && fo == b && sb == b + sl.w_stage_stream_off && sl.w_stage_stream_off >= (size_t)(n + 1) * 8 &&
              sl.w_stage_stream_off + (size_t)wire->nbytes <= cap;
     };
-    if (inside(sl.in_bar, sl.in_bar_bytes)) {
+    if (inside(sl.in_bar.h, sl.in_bar.cap)) {
       wire_staged = staged_in_device = true;
-      device_src = sl.in_bar;
-#if defined(__x86_64__)
-      __builtin_ia32_sfence();
-#endif
-    } else if (inside(sl.in_h, sl.in_bytes)) {
+      device_src = sl.in_bar.h;
+      sl.in_bar.publish();
+    } else if (inside(sl.in_h.h, sl.in_h.cap)) {
       wire_staged = true;
     } else {
       // staging = [frame offsets][stream bytes]: one DMA moves both
       if (int rc = ensure_slot_staging(h, sl, n, in_bytes)) return rc;
-      std::memcpy(sl.in_h, wire->frame_off, (size_t)(n + 1) * 8);
-      if (wire->nbytes) std::memcpy((uint8_t*)sl.in_h + (size_t)(n + 1) * 8, wire->stream, (size_t)wire->nbytes);
+      std::memcpy(sl.in_h.h, wire->frame_off, (size_t)(n + 1) * 8);
+      if (wire->nbytes) std::memcpy((uint8_t*)sl.in_h.h + (size_t)(n + 1) * 8, wire->stream, (size_t)wire->nbytes);
     }
   } else {
     in_bytes = (size_t)n * rec_bytes;
@@ -549,25 +486,20 @@ static int submit_impl(raftq_t* h, const void* msgs, uint64_t n, const WireSrc* 
     // (either slot's device staging counts: a caller that keeps filling the buffer raftq_step_stage gave it for an
     // earlier batch must not be served by a host memcpy that READS device memory over the BAR -- 43 ms for 4 MB)
     for (const raftq::StepSlot& t : h->step_slot)
-      if (t.in_bar && (const uint8_t*)msgs >= (const uint8_t*)t.in_bar &&
-          (const uint8_t*)msgs + in_bytes <= (const uint8_t*)t.in_bar + t.in_bar_bytes)
-        device_src = msgs;
+      if (t.in_bar.holds_in_device(msgs, in_bytes)) device_src = msgs, t.in_bar.publish();
     if (device_src) {
       staged_in_device = true;
-#if defined(__x86_64__)
-      __builtin_ia32_sfence();  // the producer's write-combined stores into device memory, before the doorbell
-#endif
-    } else if ((const void*)msgs != sl.in_h) {
+    } else if ((const void*)msgs != sl.in_h.h) {
       if (int rc = ensure_slot_staging(h, sl, n)) return rc;
-      std::memcpy(sl.in_h, msgs, in_bytes);
-    } else if (in_bytes > sl.in_bytes) {
+      std::memcpy(sl.in_h.h, msgs, in_bytes);
+    } else if (in_bytes > sl.in_h.cap) {
       return fail(h, RAFTQ_EINVAL, std::string(who) + ": more messages than were staged");
     }
   }
   if (h->step_last_slot == slot_no) h->step_last_slot = -1;  // that batch's decoded records are about to be overwritten
   sl.wire = false;
   Scratch s;
-  if (int rc = ensure_slot(h, sl, n, end_bit, &s, wire != nullptr && !frames, wire && !frames ? wire->nbytes : 0)) return rc;
+  if (int rc = ensure_slot(h, sl, n, &s, wire != nullptr && !frames, wire && !frames ? wire->nbytes : 0)) return rc;
   // Step moves the live commit index: a what-if (NO_ADOPT) sweep's shadow values are no longer what
   // raftq_read_committed should hand out
   h->last_flags &= ~RAFTQ_SWEEP_NO_ADOPT;
@@ -582,8 +514,7 @@ static int submit_impl(raftq_t* h, const void* msgs, uint64_t n, const WireSrc* 
   sl.msgs_in_place = nullptr;
   sl.w_off_in_place = sl.w_stream_in_place = nullptr;
   const void* packed_src = s.msgs40;
-  const bool own_staging = staged_in_device && (const uint8_t*)device_src >= (const uint8_t*)sl.in_bar &&
-                           (const uint8_t*)device_src + in_bytes <= (const uint8_t*)sl.in_bar + sl.in_bar_bytes;
+  const bool own_staging = staged_in_device && sl.in_bar.holds_in_device(device_src, in_bytes);
   if (frames) {
     // (enqueued below, on the handle's stream, in front of Step's kernels)
   } else if (wire && wire_staged && staged_in_device) {
@@ -592,9 +523,9 @@ static int submit_impl(raftq_t* h, const void* msgs, uint64_t n, const WireSrc* 
     sl.w_off_in_place = s.w_off;
     sl.w_stream_in_place = s.w_stream;
   } else if (wire && wire_staged) {
-    HIPCHK(h, hipMemcpyAsync(s.w_off, sl.in_h, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s_in));
+    HIPCHK(h, hipMemcpyAsync(s.w_off, sl.in_h.h, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s_in));
     if (wire->nbytes)
-      HIPCHK(h, hipMemcpyAsync(s.w_stream, (const uint8_t*)sl.in_h + sl.w_stage_stream_off, (size_t)wire->nbytes,
+      HIPCHK(h, hipMemcpyAsync(s.w_stream, (const uint8_t*)sl.in_h.h + sl.w_stage_stream_off, (size_t)wire->nbytes,
                                hipMemcpyHostToDevice, s_in));
     HIPCHK(h, hipEventRecord(sl.ev_in, s_in));
     HIPCHK(h, hipStreamWaitEvent(h->stream, sl.ev_in, 0));
@@ -613,14 +544,17 @@ static int submit_impl(raftq_t* h, const void* msgs, uint64_t n, const WireSrc* 
     HIPCHK(h, hipStreamWaitEvent(h->stream, sl.ev_in, 0));
   } else {
     void* in_dst = wire ? (void*)s.w_off : packed ? s.msgs40 : (void*)s.msgs;
-    HIPCHK(h, hipMemcpyAsync(in_dst, sl.in_h, in_bytes, hipMemcpyHostToDevice, s_in));
+    HIPCHK(h, hipMemcpyAsync(in_dst, sl.in_h.h, in_bytes, hipMemcpyHostToDevice, s_in));
     HIPCHK(h, hipEventRecord(sl.ev_in, s_in));
     HIPCHK(h, hipStreamWaitEvent(h->stream, sl.ev_in, 0));
   }
   // touched count + bad + skipped: the default result copy leaves them zeroed behind it (step_d2h_kernel zero_tail)
   const uint32_t rec = result_rec_bytes(h);
   // (a frames batch: the decoder that heads the chain zeroes them)
-  if (!frames && (!sl.tail_zeroed || sl.tail_n != n || sl.tail_rec != rec || sl.dev != sl.tail_dev)) hipLaunchKernelGGL(step_reset_kernel, dim3(1), dim3(64), 0, h->stream, s.n_heads);
+  if (!frames && (!sl.tail_zeroed || sl.tail_n != n || sl.tail_rec != rec || sl.dev.d != sl.tail_dev)) {
+    hipLaunchKernelGGL(step_reset_kernel, dim3(1), dim3(64), 0, h->stream, s.n_heads);
+    HIPCHK(h, hipGetLastError());
+  }
   sl.tail_zeroed = false;
   if (packed) {
     hipLaunchKernelGGL(raftqk::step_unpack40_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream,
@@ -677,7 +611,7 @@ static int submit_impl(raftq_t* h, const void* msgs, uint64_t n, const WireSrc* 
   sl.tail_zeroed = true;  // (once the copy has run) holds for the next batch of the same size and format in the same scratch
   sl.tail_n = n;
   sl.tail_rec = rec;
-  sl.tail_dev = sl.dev;
+  sl.tail_dev = sl.dev.d;
   sl.n = n;
   sl.busy = true;
   sl.lists = lists;
@@ -747,7 +681,7 @@ static int fetch_wire(raftq_t* h, bool want_ents, const char* who, raftq::StepSl
     // first request for this batch: the decoder's second pass (entry counts -> exclusive scan -> entry headers in
     // message order, ent_first of every message), kept out of the Step chain because Step does not need it
     Scratch s;
-    if (int rc = ensure_slot(h, sl, sl.n, sl.end_bit, &s, true, sl.w_nbytes)) return rc;
+    if (int rc = ensure_slot(h, sl, sl.n, &s, true, sl.w_nbytes)) return rc;
     if (sl.w_off_in_place) {  // the batch was decoded where the producer wrote it; so are its entries
       s.w_off = (uint64_t*)const_cast<void*>(sl.w_off_in_place);
       s.w_stream = (uint8_t*)const_cast<void*>(sl.w_stream_in_place);
@@ -764,22 +698,15 @@ static int fetch_wire(raftq_t* h, bool want_ents, const char* who, raftq::StepSl
     HIPCHK(h, hipStreamSynchronize(st));
     if (total > sl.w_ents_cap) total = sl.w_ents_cap;  // cannot happen: the cap is the worst case
     const size_t need = align256(msg_bytes) + (size_t)total * sizeof(WireEnt);
-    if (need > sl.w_pin_bytes) {
-      if (sl.w_pin) HIPCHK(h, hipHostFree(sl.w_pin));
-      sl.w_pin = nullptr;
-      sl.w_pin_bytes = 0;
-      const size_t want = std::max(need * 2, (size_t)1 << 20);
-      HIPCHK(h, hipHostMalloc(&sl.w_pin, want, hipHostMallocDefault));
-      sl.w_pin_bytes = want;
-    }
-    HIPCHK(h, hipMemcpyAsync(sl.w_pin, sl.w_msgs_d, msg_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, sl.w_pin.grow(need, std::max(need * 2, (size_t)1 << 20), nullptr));
+    HIPCHK(h, hipMemcpyAsync(sl.w_pin.h, sl.w_msgs_d, msg_bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
     sl.w_n_ents = total;
     sl.w_msgs_fetched = true;
   }
   if (want_ents && !sl.w_ents_fetched) {
     if (sl.w_n_ents) {
-      HIPCHK(h, hipMemcpyAsync((uint8_t*)sl.w_pin + align256(msg_bytes), sl.w_ents_d,
+      HIPCHK(h, hipMemcpyAsync((uint8_t*)sl.w_pin.h + align256(msg_bytes), sl.w_ents_d,
                                (size_t)sl.w_n_ents * sizeof(WireEnt), hipMemcpyDeviceToHost, st));
       HIPCHK(h, hipStreamSynchronize(st));
     }
@@ -794,7 +721,7 @@ int raftq_step_wire_msgs(raftq_t* h, const raftq_wire_msg_t** msgs, uint64_t* n)
   if (!msgs || !n) return fail(h, RAFTQ_EINVAL, "raftq_step_wire_msgs: null argument");
   raftq::StepSlot* sl = nullptr;
   if (int rc = fetch_wire(h, false, "raftq_step_wire_msgs", &sl)) return rc;
-  *msgs = (const raftq_wire_msg_t*)sl->w_pin;
+  *msgs = (const raftq_wire_msg_t*)sl->w_pin.h;
   *n = sl->n;
   return RAFTQ_OK;
 }
@@ -804,7 +731,7 @@ int raftq_step_wire_entries(raftq_t* h, const raftq_wire_ent_t** ents, uint64_t*
   if (!ents || !n_ents) return fail(h, RAFTQ_EINVAL, "raftq_step_wire_entries: null argument");
   raftq::StepSlot* sl = nullptr;
   if (int rc = fetch_wire(h, true, "raftq_step_wire_entries", &sl)) return rc;
-  *ents = (const raftq_wire_ent_t*)((const uint8_t*)sl->w_pin + align256((size_t)sl->n * sizeof(WireMsg)));
+  *ents = (const raftq_wire_ent_t*)((const uint8_t*)sl->w_pin.h + align256((size_t)sl->n * sizeof(WireMsg)));
   *n_ents = sl->w_n_ents;
   return RAFTQ_OK;
 }
@@ -821,13 +748,13 @@ static int replay_stalled(raftq_t* h, uint64_t first) {
       if (!sl.copy_pending) HIPCHK(h, hipEventSynchronize(sl.ev_out));
     }
     Scratch s;
-    if (int rc = ensure_slot(h, sl, sl.n, sl.end_bit, &s, sl.wire, sl.w_nbytes)) return rc;
+    if (int rc = ensure_slot(h, sl, sl.n, &s, sl.wire, sl.w_nbytes)) return rc;
     if (sl.msgs_in_place) s.msgs = (MsgRec*)const_cast<void*>(sl.msgs_in_place);
     hipLaunchKernelGGL(step_reset_kernel, dim3(1), dim3(64), 0, h->stream, s.n_heads);
     if (int rc = enqueue_sorted_walk(h, s, sl.n, sl.end_bit, sl.recs, s.outs)) return rc;
     const uint64_t out_quads = tail_off(sl.n, sl.rec) / 16 + 1;
     hipLaunchKernelGGL(step_d2h_kernel, dim3(d2h_blocks(out_quads)), dim3(kBlock), 0, h->stream, (const u64x2*)s.outs,
-                       (u64x2*)sl.out_d, out_quads);
+                       (u64x2*)sl.out.d, out_quads);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(sl.ev_out, h->stream));
     sl.copy_pending = false;
@@ -852,7 +779,7 @@ int raftq_step_collect(raftq_t* h, raftq_step_out_t* out, raftq_step_counts_t* c
   h->step_last_slot = (int)(h->step_collected % raftq::kStepSlots);
   h->step_collected++;
   const uint64_t n = sl.n;
-  const uint8_t* tail = (const uint8_t*)sl.out_h + tail_off(n, sl.rec);
+  const uint8_t* tail = (const uint8_t*)sl.out.h + tail_off(n, sl.rec);
   unsigned long long heads;
   unsigned int bad_h, skipped_h;
   std::memcpy(&skipped_h, tail + 12, 4);
@@ -873,13 +800,13 @@ int raftq_step_collect(raftq_t* h, raftq_step_out_t* out, raftq_step_counts_t* c
                 "raftq_step: a message is malformed (group or from out of range, or a type Step does not take); "
                 "nothing of that batch was applied");
   }
-  h->step_last_out = sl.out_h;
+  h->step_last_out = sl.out.h;
   h->step_last_n = n;
   h->step_last_rec = sl.rec;
   if (out) {
     if (sl.rec != sizeof(StepOutRec))
       return fail(h, RAFTQ_EINVAL, "raftq_step_collect: compact result records are read in place (raftq_step_results_c), pass out = NULL");
-    std::memcpy(out, sl.out_h, (size_t)n * sizeof(StepOutRec));
+    std::memcpy(out, sl.out.h, (size_t)n * sizeof(StepOutRec));
   }
   if (counts) {
     counts->n_msgs = n;
@@ -1039,8 +966,8 @@ static int log_deltas_impl(raftq_t* h, const raftq_log_delta_t* d, uint64_t n, u
   hipEvent_t stage_ev = nullptr;
   if (wait) {
     if (int rc = ensure_staging(h, off_out + (size_t)n * 8)) return rc;
-    stage_h = h->stage_h;
-    stage_d = h->stage_d;
+    stage_h = h->stage.h;
+    stage_d = h->stage.d;
   } else {
     // two pinned areas taken in turn: the host may not write into one before the kernels that read it have run -- which they
     // have, two calls later, in anything but a pathological queue (the event says so)
@@ -1048,17 +975,9 @@ static int log_deltas_impl(raftq_t* h, const raftq_log_delta_t* d, uint64_t n, u
     if (q.ev) HIPCHK(h, hipEventSynchronize(q.ev));
     else HIPCHK(h, hipEventCreateWithFlags(&q.ev, hipEventDisableTiming));
     const size_t need = (size_t)n * sizeof(raftq_log_delta_t);
-    if (need > q.bytes) {
-      if (q.host) HIPCHK(h, hipHostFree(q.host));
-      q.host = q.dev = nullptr;
-      q.bytes = 0;
-      const size_t want = std::max(need * 2, (size_t)1 << 16);
-      HIPCHK(h, hipHostMalloc(&q.host, want, hipHostMallocMapped));
-      HIPCHK(h, hipHostGetDevicePointer(&q.dev, q.host, 0));
-      q.bytes = want;
-    }
-    stage_h = q.host;
-    stage_d = q.dev;
+    HIPCHK(h, q.buf.grow(need, std::max(need * 2, (size_t)1 << 16), nullptr));  // (its event has been waited for)
+    stage_h = q.buf.h;
+    stage_d = q.buf.d;
     stage_ev = q.ev;
   }
   // The common batch names every group once: one round, caller order, no bookkeeping.  Whether it does is found

@@ -57,41 +57,19 @@ struct Carver {
 
 constexpr uint64_t kLbHead = 4;  // words in front of the look-back block's status arrays
 
-// How a device buffer of the handle grows.  Capacity is counted in the buffer's own units: bytes, or status words per array of
-// the look-back block.
-struct GrowRule {
-  uint64_t least;     // smallest capacity ever allocated
-  size_t unit, head;  // bytes = head + capacity * unit
-  bool zero;          // a fresh buffer is zeroed (on the stream)
-};
-constexpr GrowRule kGrowBytes{(uint64_t)1 << 20, 1, 0, false};
-constexpr GrowRule kGrowBytesZeroed{(uint64_t)1 << 20, 1, 0, true};
-constexpr GrowRule kGrowLookBack{4096, kLbArrays * 8, kLbHead * 8, true};
-
-// *buf holds at least `want` units.  A buffer that is too small is freed after a stream synchronisation (kernels of earlier
-// calls may still use it) and replaced by one half as large again; its contents are not kept.
-int grow(raftq_t* h, void** buf, uint64_t* have, uint64_t want, const GrowRule& rule = kGrowBytes) {
-  if (want <= *have) return RAFTQ_OK;
-  if (*buf) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-  }
-  const uint64_t cap = std::max(want + want / 2, rule.least);
-  const size_t bytes = rule.head + cap * rule.unit;
-  HIPCHK(h, hipMalloc(buf, bytes));
-  if (rule.zero) HIPCHK(h, hipMemsetAsync(*buf, 0, bytes, h->stream));
-  *have = cap;
+// How the codecs' device buffers grow: half as large again as what is asked for, a megabyte at least; a buffer that is too small
+// is freed after a stream synchronisation (kernels of earlier calls may still use it), its contents are not kept.
+size_t grown(size_t want) { return std::max(want + want / 2, (size_t)1 << 20); }
+int grow(raftq_t* h, raftq_buf::Buffer<>& buf, size_t want) {
+  HIPCHK(h, buf.grow(want, grown(want), &h->stream));
   return RAFTQ_OK;
 }
 
 int ensure_pin(raftq_t* h) {
   if (h->wire_pin) return RAFTQ_OK;
-  HIPCHK(h, hipHostMalloc((void**)&h->wire_pin, 256, hipHostMallocMapped));
-  HIPCHK(h, hipHostGetDevicePointer((void**)&h->wire_pin_d, h->wire_pin, 0));
-  HIPCHK(h, hipMalloc((void**)&h->wire_flags, 64));
-  HIPCHK(h, hipMemsetAsync(h->wire_flags, 0, 64, h->stream));  // wire_tail_kernel leaves a used word zero again
+  // both or neither (wire_tail_kernel leaves a used word of wire_flags zero again)
+  HIPCHK(h, raftq_buf::alloc_group({{(void**)&h->wire_pin, 256, raftq_buf::Kind::mapped, (void**)&h->wire_pin_d}, {(void**)&h->wire_flags, 64}},
+                                   h->stream));
   return RAFTQ_OK;
 }
 
@@ -166,27 +144,27 @@ struct StreamCall {
   } seg[3] = {};
   size_t carve[2] = {0, 0};  // further scratch of the call's kernels, n_carves pieces
   int n_carves = 0;
-  uint64_t out_bytes = 0;  // what h->wire_out has to hold (0: the kernel does not use it)
+  uint64_t out_bytes = 0;  // what h->wire_out.d has to hold (0: the kernel does not use it)
   // -- the answer --
   InFeed in{};
   TileCtl ctl;
   unsigned workers = 0;
   dim3 grid;           // readers + workers
   uint8_t* carved[2];  // the pieces asked for
-  size_t off[5];       // (where the segments and the pieces lie in h->wire_dev)
+  size_t off[5];       // (where the segments and the pieces lie in h->wire_dev.d)
 };
 
 // ticket word + status arrays for one launch: a new launch is a new epoch (the words of older ones read as "not published
 // yet"); the arrays are zeroed again when the 16-bit epoch wraps
 int tile_ctl(raftq_t* h, TileCtl* ctl) {
   if (++h->wire_epoch > 0xffffu) {
-    HIPCHK(h, hipMemsetAsync(h->wire_lb + kLbHead, 0, kLbArrays * h->wire_lb_tiles * 8, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->wire_lb.d + kLbHead, 0, kLbArrays * h->wire_lb_tiles * 8, h->stream));
     h->wire_epoch = 1;
   }
-  ctl->ticket = reinterpret_cast<unsigned int*>(h->wire_lb);
+  ctl->ticket = reinterpret_cast<unsigned int*>(h->wire_lb.d);
   ctl->ticket_base = h->wire_ticket_base;
   ctl->epoch = h->wire_epoch;
-  for (int k = 0; k < kLbArrays; ++k) ctl->status[k] = h->wire_lb + kLbHead + (uint64_t)k * h->wire_lb_tiles;
+  for (int k = 0; k < kLbArrays; ++k) ctl->status[k] = h->wire_lb.d + kLbHead + (uint64_t)k * h->wire_lb_tiles;
   return RAFTQ_OK;
 }
 // every worker of a launch draws exactly one ticket beyond the tiles
@@ -223,9 +201,9 @@ void plan_feed(StreamCall& sc, uint64_t max_chunks) {
 // names, stays unclaimed -- so its count is not known: the ticket word is zeroed in front of such a launch and in front of the
 // first launch after one (a 4-byte memset in the stream: test and A/B shapes only).
 int bind_feed(raftq_t* h, StreamCall& sc) {
-  for (int k = 0; k < 3; ++k) sc.in.seg[k].dst = (uint8_t*)h->wire_dev + sc.off[k];
+  for (int k = 0; k < 3; ++k) sc.in.seg[k].dst = (uint8_t*)h->wire_dev.d + sc.off[k];
   sc.in.flag = sc.ctl.status[kLbFlags];
-  sc.in.chunk_ticket = reinterpret_cast<unsigned int*>(h->wire_lb + 3);  // the head's fourth word
+  sc.in.chunk_ticket = reinterpret_cast<unsigned int*>(h->wire_lb.d + 3);  // the head's fourth word
   if (sc.in.readers == 0 || h->wire_chunk_unknown) {
     HIPCHK(h, hipMemsetAsync(sc.in.chunk_ticket, 0, 4, h->stream));
     h->wire_chunk_base = 0;
@@ -250,22 +228,32 @@ int stream_reserve(raftq_t* h, StreamCall& sc) {
   for (int k = 0; k < 3; ++k) total += sc.seg[k].bytes;
   const uint64_t n_status = std::max<uint64_t>(sc.n_tiles, total / kFeedChunk + 1);
   if (n_status > h->wire_lb_tiles) {  // a fresh control block is all zero: tickets and epochs start over
-    if (int rc = grow(h, (void**)&h->wire_lb, &h->wire_lb_tiles, n_status, kGrowLookBack)) return rc;
+    // capacity in status words per array: bytes = head + arrays x words x 8, zeroed.  The block in hand is replaced whatever its
+    // size: it is too small, or not trusted any more (tile_ctl_check)
+    const uint64_t words = std::max<uint64_t>(n_status + n_status / 2, 4096);
+    const size_t bytes = kLbHead * 8 + words * kLbArrays * 8;
+    h->wire_lb_tiles = 0;
+    if (h->wire_lb.d) {
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+      HIPCHK(h, h->wire_lb.release());
+    }
+    HIPCHK(h, h->wire_lb.grow_zeroed(bytes, bytes, h->stream));
+    h->wire_lb_tiles = words;
     h->wire_ticket_base = h->wire_chunk_base = h->wire_epoch = 0;
     h->wire_chunk_unknown = false;
   }
   Carver c;
   for (int k = 0; k < 3; ++k) sc.off[k] = c.take(sc.seg[k].bytes + sc.seg[k].extra);
   for (int k = 0; k < sc.n_carves; ++k) sc.off[3 + k] = c.take(sc.carve[k]);
-  if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, c.off)) return rc;
-  return grow(h, &h->wire_out, &h->wire_out_bytes, sc.out_bytes);
+  if (int rc = grow(h, h->wire_dev, c.off)) return rc;
+  return grow(h, h->wire_out, sc.out_bytes);
 }
 int stream_prepare(raftq_t* h, StreamCall& sc) {
   if (int rc = stream_reserve(h, sc)) return rc;
   if (int rc = tile_ctl(h, &sc.ctl)) return rc;
   plan_feed(sc, h->wire_lb_tiles);
   if (int rc = bind_feed(h, sc)) return rc;
-  for (int k = 0; k < sc.n_carves; ++k) sc.carved[k] = (uint8_t*)h->wire_dev + sc.off[3 + k];
+  for (int k = 0; k < sc.n_carves; ++k) sc.carved[k] = (uint8_t*)h->wire_dev.d + sc.off[3 + k];
   sc.workers = fused_grid(sc.n_tiles);
   sc.grid = dim3(sc.in.readers + sc.workers);
   return RAFTQ_OK;
@@ -330,7 +318,7 @@ int wire_encode_streaming(raftq_t* h, const void* v_msgs, uint64_t n, const void
   sc.seg[2] = {v_pool, pool_bytes, 0};
   sc.out_bytes = cap + 16;
   if (int rc = stream_prepare(h, sc)) return rc;
-  if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, n, n_ents, pool_bytes, (uint8_t*)h->wire_out, (uint8_t*)v_out, cap,
+  if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, n, n_ents, pool_bytes, (uint8_t*)h->wire_out.d, (uint8_t*)v_out, cap,
                              (uint64_t*)v_off, sc.ctl, h->wire_pin_d + kPinCall, (const unsigned int*)nullptr, 0u))
     return rc;
   HIPCHK(h, raftq_detail::wait_call(h));
@@ -347,8 +335,8 @@ int wire_encode_copying(raftq_t* h, const raftq_wire_msg_t* msgs, uint64_t n, co
   Carver c;
   const size_t o_msgs = c.take(n * sizeof(WireMsg)), o_ents = c.take(n_ents * sizeof(WireEnt)),
                o_pool = c.take(pool_bytes), o_sizes = c.take((n + 1) * 8), o_off = c.take((n + 1) * 8), o_scan = c.take(scan_bytes);
-  if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, c.off)) return rc;
-  uint8_t* base = (uint8_t*)h->wire_dev;
+  if (int rc = grow(h, h->wire_dev, c.off)) return rc;
+  uint8_t* base = (uint8_t*)h->wire_dev.d;
   WireMsg* d_msgs = (WireMsg*)(base + o_msgs);
   WireEnt* d_ents = (WireEnt*)(base + o_ents);
   uint8_t* d_pool = base + o_pool;
@@ -367,8 +355,8 @@ int wire_encode_copying(raftq_t* h, const raftq_wire_msg_t* msgs, uint64_t n, co
   if (int rc = encode_sized(h, "raftq_wire_encode", kWireEncRefused, "nothing was written", total, (uint32_t)h->wire_pin[kPinCall + kPinRefused], cap,
                             counts, raftq_wire_counts_t{n, n_ents, 0, total}))
     return rc;
-  if (int rc = grow(h, &h->wire_out, &h->wire_out_bytes, total + 16)) return rc;
-  uint8_t* d_out = (uint8_t*)h->wire_out;
+  if (int rc = grow(h, h->wire_out, total + 16)) return rc;
+  uint8_t* d_out = (uint8_t*)h->wire_out.d;
   hipLaunchKernelGGL(wire_enc_write_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, h->stream, (const WireMsg*)d_msgs, n,
                      (const WireEnt*)d_ents, (const uint64_t*)d_off, d_out);
   if (n_ents)
@@ -430,13 +418,13 @@ int wire_decode_copying(raftq_t* h, const void* stream, uint64_t nbytes, const u
   Carver c;
   const size_t o_stream = c.take(nbytes), o_off = c.take((n + 1) * 8), o_msgs = c.take(n * sizeof(WireMsg)),
                o_cnt = c.take((n + 1) * 8), o_base = c.take((n + 1) * 8), o_scan = c.take(scan_bytes);
-  if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, c.off)) return rc;
-  if (int rc = grow(h, &h->wire_out, &h->wire_out_bytes, dev_cap * sizeof(WireEnt) + 16)) return rc;
-  uint8_t* base = (uint8_t*)h->wire_dev;
+  if (int rc = grow(h, h->wire_dev, c.off)) return rc;
+  if (int rc = grow(h, h->wire_out, dev_cap * sizeof(WireEnt) + 16)) return rc;
+  uint8_t* base = (uint8_t*)h->wire_dev.d;
   uint8_t* d_stream = base + o_stream;
   uint64_t *d_off = (uint64_t*)(base + o_off), *d_cnt = (uint64_t*)(base + o_cnt), *d_base = (uint64_t*)(base + o_base);
   WireMsg* d_msgs = (WireMsg*)(base + o_msgs);
-  WireEnt* d_ents = (WireEnt*)h->wire_out;
+  WireEnt* d_ents = (WireEnt*)h->wire_out.d;
   unsigned long long* d_bad = h->wire_flags + 1;
   if (int rc = h2d(h, d_stream, stream, nbytes)) return rc;
   if (int rc = h2d(h, d_off, frame_off, (n + 1) * 8)) return rc;
@@ -463,19 +451,8 @@ int wire_decode_copying(raftq_t* h, const void* stream, uint64_t nbytes, const u
 }  // namespace
 
 void raftq_detail::free_wire_state(raftq_t* h) {
-  (void)hipFree(h->wire_dev);
-  (void)hipFree(h->wire_out);
-  (void)hipFree(h->wire_flags);
-  (void)hipFree(h->wire_lb);
-  (void)hipFree(h->resp_dev);
-  h->resp_dev = nullptr;
-  h->resp_dev_bytes = 0;
-  h->wire_flags = nullptr;
-  h->wire_lb = nullptr;
-  h->wire_lb_tiles = 0;
-  if (h->wire_pin) (void)hipHostFree(h->wire_pin);
-  h->wire_dev = h->wire_out = nullptr;
-  h->wire_pin = nullptr;
+  raftq_buf::free_device(h->wire_flags);
+  raftq_buf::free_host(h->wire_pin);
 }
 
 // ---- raftpb.Message stream frames: the entry points ---------------------------------------------------------------------------
@@ -569,7 +546,7 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
   hipLaunchKernelGGL(propose_apply_kernel, pg, dim3(kBlock), 0, h->stream, na, (const PropRec*)props_d, n_props, (const PropEnt*)pe_d,
                      (const unsigned int*)bad, stamp, msgs_dev, ents_dev, (uint32_t)n_ents);
   // ... and the marshal of everything right behind it: one wait
-  if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, n, n_e, pool_bytes, (uint8_t*)h->wire_out, (uint8_t*)v_out, cap, (uint64_t*)v_off,
+  if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, n, n_e, pool_bytes, (uint8_t*)h->wire_out.d, (uint8_t*)v_out, cap, (uint64_t*)v_off,
                              sc.ctl, h->wire_pin_d + kPinCall, (const unsigned int*)bad, stamp))
     return rc;
   HIPCHK(h, raftq_detail::wait_call(h));
@@ -708,7 +685,8 @@ int raftq_detail::respond_prepare(raftq_t* h, const void* stream, uint64_t nbyte
   if (!v.ok)
     return fail(h, RAFTQ_EINVAL, std::string(who) + ": every array must be page-locked (raftq_host_alloc, hipHostMalloc, hipHostRegister) and "
                                                     "16-byte aligned -- nothing was applied");
-  if (int rc = grow(h, &h->resp_dev, &h->resp_dev_bytes, resp_scratch(n).bytes, kGrowBytesZeroed)) return rc;  // (zeroed: stamp 0 is no call's)
+  const size_t resp_bytes = resp_scratch(n).bytes;
+  HIPCHK(h, h->resp_dev.grow_zeroed(resp_bytes, grown(resp_bytes), h->stream));  // (zeroed: stamp 0 is no call's)
   p->n = n;
   p->n_max = n * (h->N - 1);
   p->cap = std::min<uint64_t>(cap, p->n_max * RAFTQ_RESPOND_FRAME_MAX);  // what the encoder may write: never more than the worst case
@@ -728,7 +706,7 @@ int raftq_detail::respond_prepare(raftq_t* h, const void* stream, uint64_t nbyte
 
 int raftq_detail::respond_enqueue(raftq_t* h, const RespPlan& p) {
   const RespScratch rs = resp_scratch(p.n);
-  uint8_t* rd = (uint8_t*)h->resp_dev;
+  uint8_t* rd = (uint8_t*)h->resp_dev.d;
   const uint32_t blocks = blocks_for(p.n);
   RespLayout L{(const RespRec*)rd, p.n, h->N, h->self_peer, h->resp_stamp, (uint32_t*)(rd + rs.o_blk_cnt), (uint64_t*)(rd + rs.o_blk_off),
                (uint64_t*)(rd + rs.o_peer_off)};
@@ -739,7 +717,7 @@ int raftq_detail::respond_enqueue(raftq_t* h, const RespPlan& p) {
     StreamCall sc = resp_marshal_call(p);
     if (int rc = stream_prepare(h, sc)) return rc;  // (allocates nothing: respond_prepare reserved this very request)
     hipLaunchKernelGGL(resp_scatter_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, (WireMsg*)sc.in.seg[0].dst, p.n_max);
-    if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, p.n_max, (uint64_t)0, (uint64_t)0, (uint8_t*)h->wire_out, (uint8_t*)p.v_out,
+    if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, p.n_max, (uint64_t)0, (uint64_t)0, (uint8_t*)h->wire_out.d, (uint8_t*)p.v_out,
                                p.cap, p.v_resp_off, sc.ctl, h->wire_pin_d + kPinRespond, (const unsigned int*)nullptr, 0u))
       return rc;
   }
@@ -821,7 +799,7 @@ extern "C" int raftq_tick_frames(raftq_t* h, unsigned flags, uint64_t hup_cap, u
                 h->self_peer, beat_cap, (WireMsg*)sc.in.seg[0].dst};
     hipLaunchKernelGGL(beat_build_kernel, dim3((unsigned)((nw + kWaves - 1) / kWaves)), dim3(kBlock), 0, h->stream, ba);
     HIPCHK(h, hipGetLastError());
-    if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, n_max, (uint64_t)0, (uint64_t)0, (uint8_t*)h->wire_out, (uint8_t*)v_out, enc_cap,
+    if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, n_max, (uint64_t)0, (uint64_t)0, (uint8_t*)h->wire_out.d, (uint8_t*)v_out, enc_cap,
                                (uint64_t*)v_off, sc.ctl, h->wire_pin_d + kPinCall, (const unsigned int*)nullptr, 0u))
       return rc;
   }
@@ -859,7 +837,7 @@ int wal_streaming_enqueue(raftq_t* h, const void* v_recs, uint64_t n, const void
   sc.seg[1] = {v_pool, pool_bytes, 0};
   sc.out_bytes = cap + 16;
   if (int rc = stream_prepare(h, sc)) return rc;
-  return stream_launch(h, sc, wal_enc_fused_kernel, kBlock, sc.in, n, pool_bytes, prev_crc, (uint8_t*)h->wire_out, (uint8_t*)v_out, cap, (uint64_t*)v_off,
+  return stream_launch(h, sc, wal_enc_fused_kernel, kBlock, sc.in, n, pool_bytes, prev_crc, (uint8_t*)h->wire_out.d, (uint8_t*)v_out, cap, (uint64_t*)v_off,
                        sc.ctl, h->wire_pin_d + pin_base);
 }
 int wal_streaming_finish(raftq_t* h, const char* who, uint64_t n, uint64_t cap, uint32_t prev_crc, uint32_t pin_base, raftq_wal_counts_t* counts) {
@@ -896,8 +874,8 @@ int wal_encode_copying(raftq_t* h, const raftq_wal_rec_t* recs, uint64_t n, cons
                o_pair = c.take(n * 8), o_chain = c.take(n * 8), o_sizes = c.take((n + 1) * 8),
                o_off = c.take((n + 1) * 8), o_flags = c.take(8), o_scan = c.take(scan_bytes),
                o_tot = c.take((size_t)blocks_for(n) * sizeof(CrcPair));
-  if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, c.off)) return rc;
-  uint8_t* base = (uint8_t*)h->wire_dev;
+  if (int rc = grow(h, h->wire_dev, c.off)) return rc;
+  uint8_t* base = (uint8_t*)h->wire_dev.d;
   WalRec* d_recs = (WalRec*)(base + o_recs);
   uint8_t* d_pool = base + o_pool;
   uint32_t* d_pcrc = (uint32_t*)(base + o_pcrc);
@@ -926,8 +904,8 @@ int wal_encode_copying(raftq_t* h, const raftq_wal_rec_t* recs, uint64_t n, cons
   if (int rc = encode_sized(h, "raftq_wal_encode", kWalEncRefused, "nothing was written", total, (uint32_t)pin[kPinRefused], cap, counts,
                             raftq_wal_counts_t{n, 0, total, prev_crc, 0}))
     return rc;
-  if (int rc = grow(h, &h->wire_out, &h->wire_out_bytes, total + 16)) return rc;
-  uint8_t* d_out = (uint8_t*)h->wire_out;
+  if (int rc = grow(h, h->wire_out, total + 16)) return rc;
+  uint8_t* d_out = (uint8_t*)h->wire_out.d;
   hipLaunchKernelGGL(wal_enc_write_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, h->stream, (const WalRec*)d_recs, n,
                      (const CrcPair*)d_chain, (const uint64_t*)d_off, d_out, d_last);
   if (pool_bytes)
@@ -974,8 +952,8 @@ int wal_decode_copying(raftq_t* h, const void* bytes, uint64_t nbytes, const uin
   const size_t o_bytes = c.take(nbytes), o_off = c.take((n + 1) * 8), o_recs = c.take(n * sizeof(WalRec)),
                o_span = c.take(n * sizeof(WalSpan)), o_pair = c.take(n * 8), o_chain = c.take(n * 8),
                o_tail = c.take(32), o_tot = c.take((size_t)blocks_for(n) * sizeof(CrcPair));
-  if (int rc = grow(h, &h->wire_dev, &h->wire_dev_bytes, c.off)) return rc;
-  uint8_t* base = (uint8_t*)h->wire_dev;
+  if (int rc = grow(h, h->wire_dev, c.off)) return rc;
+  uint8_t* base = (uint8_t*)h->wire_dev.d;
   uint8_t* d_bytes = base + o_bytes;
   uint64_t* d_off = (uint64_t*)(base + o_off);
   WalRec* d_recs = (WalRec*)(base + o_recs);
