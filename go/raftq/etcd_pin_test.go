@@ -109,6 +109,15 @@ func TestStepAgainstEtcd(t *testing.T) {
 					st.SetHardState(rd.HardState)
 				}
 				for _, m := range rd.Messages { // the rule raftq_tick_frames restates: a heartbeat's Commit is min(Progress[to].Match, committed)
+					if m.Type == pb.MsgVote { // the round raftq_tick_elect_frames restates: campaign()'s MsgVote{Term: the new term, Index: lastIndex, LogTerm: lastTerm}
+						li, _ := st.LastIndex()
+						ltm, _ := st.Term(li)
+						if s := rn.Status(); m.Term != s.Term || m.Index != li || m.LogTerm != ltm || m.Commit != 0 || m.Reject || len(m.Entries) != 0 ||
+							s.RaftState != raft.StateCandidate || s.Vote != 1 {
+							t.Fatalf("N=%d: MsgVote to %d carries {Term %d Index %d LogTerm %d}, want {%d %d %d} from a candidate that voted for itself (state %v, vote %d)",
+								n, m.To, m.Term, m.Index, m.LogTerm, s.Term, li, ltm, s.RaftState, s.Vote)
+						}
+					}
 					if m.Type != pb.MsgHeartbeat {
 						continue
 					}

@@ -432,7 +432,61 @@ func (e *Engine) TickFrames(flags uint, hupCap, beatCap uint64, out []byte, fram
 	return t, uint64(c.n_msgs), uint64(c.bytes), nil
 }
 
-// OutfAnswered / RespondFrameMax: RAFTQ_OUTF_ANSWERED, RAFTQ_RESPOND_FRAME_MAX (include/raftq_wire.h)
+// TickElectFrames is TickFrames plus the election round the Tick calls for (raftq_tick_elect_frames; raft.go:223-224 -> :230:
+// rc.node.Tick -> tickElection -> Step(MsgHup) -> campaign -> Peers-1 MsgVote -> rc.transport.Send): Step(MsgHup) is applied on
+// the device to the first min(NHup, hupCap) MsgHup groups, camp[r] (len >= hupCap) is the compact result of hup id r -- the
+// HardState to persist; the caller sends nothing for it -- and out receives the heartbeat section as TickFrames lays it out,
+// then the vote section: for every peer slot p != self, ascending, one MsgVote{Term, Index: lastIndex, LogTerm: lastTerm} per
+// campaigned group in ascending group order.  peerOff (len 2*(Peers+1)): the heartbeat section's frame indices, then the vote
+// section's; frameOff (nil, or len >= (beatCap+hupCap)*(Peers-1)+1) the byte offsets.  MsgHup groups beyond hupCap are the
+// caller's.  len(out) must be at least (beatCap+hupCap)*(Peers-1)*RespondFrameMax; camp, out, frameOff and peerOff must be
+// page-locked (HostAlloc).  A refused call has neither ticked nor campaigned.
+func (e *Engine) TickElectFrames(flags uint, hupCap, beatCap uint64, camp []StepOutS, out []byte, frameOff, peerOff []uint64) (t TickLists, nFrames, nBytes uint64, err error) {
+	if uint64(len(peerOff)) < 2*(uint64(e.Peers)+1) {
+		return TickLists{}, 0, 0, fmt.Errorf("raftq: TickElectFrames: peerOff has %d words, needs 2 * (Peers + 1) = %d", len(peerOff), 2*(e.Peers+1))
+	}
+	nMax := (beatCap + hupCap) * uint64(e.Peers-1)
+	if frameOff != nil && uint64(len(frameOff)) < nMax+1 {
+		return TickLists{}, 0, 0, fmt.Errorf("raftq: TickElectFrames: frameOff has %d words, needs (beatCap + hupCap) * (Peers - 1) + 1 = %d", len(frameOff), nMax+1)
+	}
+	if uint64(len(camp)) < hupCap {
+		return TickLists{}, 0, 0, fmt.Errorf("raftq: TickElectFrames: camp has %d records, needs hupCap = %d", len(camp), hupCap)
+	}
+	var pf *C.uint64_t
+	if len(frameOff) > 0 {
+		pf = (*C.uint64_t)(unsafe.Pointer(&frameOff[0]))
+	}
+	var pc *C.raftq_step_out_s_t
+	if len(camp) > 0 {
+		pc = (*C.raftq_step_out_s_t)(unsafe.Pointer(&camp[0]))
+	}
+	var nh, nb C.uint64_t
+	var c C.raftq_wire_counts_t
+	rc := C.raftq_tick_elect_frames(e.h, C.uint(flags), C.uint64_t(hupCap), C.uint64_t(beatCap), &nh, &nb, pc, bytesPtr(out), C.uint64_t(len(out)), pf,
+		(*C.uint64_t)(unsafe.Pointer(&peerOff[0])), &c)
+	if err := e.err(rc); err != nil {
+		return TickLists{}, 0, 0, err
+	}
+	var ph, pb *C.uint32_t
+	var pm *C.uint64_t
+	var lh, lb, lm C.uint64_t
+	if err := e.err(C.raftq_last_tick_lists(e.h, &ph, &lh, &pb, &lb, &pm, &lm)); err != nil {
+		return TickLists{}, 0, 0, err
+	}
+	t = TickLists{NHup: uint64(nh), NBeat: uint64(nb)}
+	if lh > 0 {
+		t.Hups = unsafe.Slice((*uint32)(unsafe.Pointer(ph)), int(lh))
+	}
+	if lb > 0 {
+		t.Beats = unsafe.Slice((*uint32)(unsafe.Pointer(pb)), int(lb))
+	}
+	if lm > 0 {
+		t.BeatBitmap = unsafe.Slice((*uint64)(unsafe.Pointer(pm)), int(lm))
+	}
+	return t, uint64(c.n_msgs), uint64(c.bytes), nil
+}
+
+// OutfAnswered / RespondFrameMax:RAFTQ_OUTF_ANSWERED, RAFTQ_RESPOND_FRAME_MAX (include/raftq_wire.h)
 const (
 	OutfAnswered    = 0x10
 	RespondFrameMax = 83

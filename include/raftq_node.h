@@ -107,7 +107,18 @@ typedef struct raftq_node_stats {
                                   * this node leads, rounded up; the per-peer slices go onto the peer queues ahead of everything
                                   * else the turn sends, after the turn's WAL bytes; a MsgBeat group beyond beat_cap gets its
                                   * heartbeats from the host as before.  Per peer the stream is the host path's, frame for frame
-                                  * (unless RAFTQ_NODE_RESPOND_DEVICE=1 moves its answers in front of such a group's heartbeats). */
+                                  * (unless RAFTQ_NODE_RESPOND_DEVICE=1 moves its answers in front of such a group's heartbeats).
+                                  * RAFTQ_NODE_ELECT_DEVICE=1 (read at raftq_node_create, off by default): every tick of a turn is
+                                  * raftq_tick_elect_frames (raftq_wire.h) -- the groups whose election timers fired campaign on
+                                  * the device, no local MsgHup is raised for them, and msgs_sent / msgs_built_on_device count
+                                  * their MsgVotes.  beat_cap is RAFTQ_NODE_BEAT_DEVICE's when that is on, else 0 (the host
+                                  * beats); hup_cap is the node's list size, grown on demand (RAFTQ_NODE_ELECT_CAP=k caps it, for
+                                  * the tests): MsgHup groups behind it, and raftq_node_campaign's, go through Step as before.
+                                  * Each peer's MsgVotes go onto its queue directly behind the ticks' heartbeats (the device's and
+                                  * the ones the host queued) and ahead of everything else -- where the host path's MsgVotes stand
+                                  * -- after the turn's WAL bytes (the HardState with the new term and vote).  The device campaigns at the tick
+                                  * that fired; the host path steps the MsgHup after the turn's last tick, so in a turn of several
+                                  * ticks such a group's timer may differ between the two by the ticks in between. */
 } raftq_node_stats_t;
 
 int raftq_node_create(int device, uint64_t n_groups, uint32_t n_peers, uint32_t self_peer, raftq_node_t** out);

@@ -347,6 +347,45 @@ int raftq_tick_frames(raftq_t* h, unsigned flags, uint64_t hup_cap, uint64_t bea
                       void* out, uint64_t cap, uint64_t* frame_off /*[beat_cap*(N-1)+1] | NULL*/, uint64_t* peer_off /*[N+1]*/,
                       raftq_wire_counts_t* counts /*| NULL*/);
 
+/* raftq_tick_frames plus a node's election round (raft.go:223-224 -> :230: rc.node.Tick() -> tickElection -> Step(MsgHup) ->
+ * campaign() -> N - 1 MsgVote -> rc.transport.Send), still ONE submission with one wait: the Tick, its lists, the heartbeats and
+ * the campaigns the Tick calls for, applied, built and marshalled on the device.
+ *
+ * The Tick is exactly raftq_tick_collect_lists(h, flags, hup_cap, beat_cap, n_hup, n_beat): the timers, the action bytes, the
+ * totals, and what raftq_last_tick_lists hands out afterwards.
+ *
+ * The heartbeats are exactly raftq_tick_frames' for the first n_bb = min(*n_beat, beat_cap) MsgBeat groups.
+ *
+ * The campaigns: let n_vb = min(*n_hup, hup_cap) -- hup_cap bounds the list and what is campaigned.  For each of the first n_vb
+ * MsgHup groups, ascending, the device applies Step(MsgHup) to the device-resident state; the result is what raftq_step_batch
+ * would leave had that local message been stepped at this point, in the record AND the dense arrays: term + 1, vote = self, role =
+ * candidate, lead = None, first_idx = 0, elapsed = 0, reset()'s match rows (self = lastIndex, the others 0), the vote word cleared
+ * and self's grant recorded, the self-max word cleared if the store breaks it.  camp[r] answers hup id r of the list: the 32-byte
+ * record raftq_step_set_compact(h, 2) would give for that message -- type = RAFTQ_OUT_CAMPAIGN, index = lastIndex, commit = the
+ * candidate's lastTerm, flags = RAFTQ_OUTF_HARDSTATE | RAFTQ_OUTF_ANSWERED -- whatever result format the handle is set to.  The
+ * caller persists the HardState and sends nothing.  MsgHup groups of rank >= hup_cap are the caller's: nothing of them is
+ * touched, and the caller steps their MsgHup itself.
+ *
+ * out: two sections of rafthttp stream frames, back to back.  The heartbeat section is exactly raftq_tick_frames'.  The vote
+ * section follows: for every peer slot p != self, ascending, one frame per campaigned group in ascending group order,
+ *   MsgVote{to = p, from = self, group, term = the new Term, index = lastIndex, log_term = lastTerm}, every other field zero.
+ * Frames are numbered through both sections.  peer_off[0 .. N] are the heartbeat section's frame indices as raftq_tick_frames
+ * gives them; peer_off[N + 1 .. 2 N + 1] are the vote section's, the first n_bb * (N - 1), the last (n_bb + n_vb) * (N - 1).
+ * frame_off (NULL, or room for (beat_cap + hup_cap) * (N - 1) + 1 words) is as raftq_wire_encode's, the entries past the last
+ * frame all holding the total.  counts: n_msgs = (n_bb + n_vb) * (N - 1), bytes.  Byte for byte what raftq_wire_encode makes of
+ * the same raftq_wire_msg_t records built on the host.
+ *
+ * Refused before anything is enqueued -- a refused call has neither ticked nor campaigned:
+ *   RAFTQ_EINVAL  cap < (beat_cap + hup_cap) * (N - 1) * RAFTQ_RESPOND_FRAME_MAX; camp, out, frame_off or peer_off not page-locked
+ *                 and 16-byte aligned (camp may be NULL only when hup_cap == 0); N < 2; an unknown flag;
+ *                 (beat_cap + hup_cap) * (N - 1) >= 2^31, or that many frames beyond 2^31 bytes
+ *   RAFTQ_ESTATE  a Step batch in flight; no node state on the handle; voter masks loaded
+ * Every allocation is made before the tick kernel is enqueued.  With hup_cap == 0 the call is raftq_tick_frames. */
+int raftq_tick_elect_frames(raftq_t* h, unsigned flags, uint64_t hup_cap, uint64_t beat_cap, uint64_t* n_hup, uint64_t* n_beat,
+                            raftq_step_out_s_t* camp /*[hup_cap]*/, void* out, uint64_t cap,
+                            uint64_t* frame_off /*[(beat_cap + hup_cap)*(N-1)+1] | NULL*/, uint64_t* peer_off /*[2*(N+1)]*/,
+                            raftq_wire_counts_t* counts /*| NULL*/);
+
 /* ---- WAL ------------------------------------------------------------------------------------ */
 
 /* walpb record types (wal/wal.go) */

@@ -51,6 +51,7 @@ def lib_sources() -> list[str]:
         os.path.join(CSRC, "raftq_propose_kernels.hpp"),
         os.path.join(CSRC, "raftq_respond_kernels.hpp"),
         os.path.join(CSRC, "raftq_beat_kernels.hpp"),
+        os.path.join(CSRC, "raftq_elect_kernels.hpp"),
         os.path.join(ROOT, "include", "raftq.h"),
         os.path.join(ROOT, "include", "raftq_step.h"),
         os.path.join(ROOT, "include", "raftq_pipe.h"),

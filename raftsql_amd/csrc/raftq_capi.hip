@@ -1138,6 +1138,7 @@ int raftq_detail::tick_lists_enqueue(raftq_t* h, TickLists* tl) {
     off_b = h->tick_offsets2;
   }
   tl->off_beat = off_b;
+  tl->off_h = off_h;
   uint32_t* const hup_d = h->tl.d;
   uint32_t* const beat_d = h->tl.d + tl->beat_at;
   uint64_t* const map_d = (uint64_t*)((uint8_t*)h->tl.d + tl->map_off);

@@ -1,0 +1,150 @@
+// raftq_elect_kernels.hpp -- raftq_tick_elect_frames' election round (include/raftq_wire.h): Step(MsgHup) -> campaign() for the
+// groups the Tick in front of it flagged MsgHup, applied to the device-resident state where the Tick has just flagged them, and
+// the N - 1 MsgVotes of each written into the encoder's input in HBM behind the heartbeat records, peer-major -- for every peer
+// slot p != self, ascending, one MsgVote per campaigned group in ascending group order.
+//
+// A campaign is a function of one 128-byte line, as a heartbeat is (raftq_beat_kernels.hpp): term + 1, vote = self, candidate,
+// reset()'s match rows, the vote word with self's grant.  All of it is stated ONCE, in Node (raftq_step_kernels.hpp): a lane
+// loads its group through Node, calls become_candidate() + poll(self, granted) -- the two calls step() makes for a local MsgHup
+// -- and store(), which writes the record and, where they changed, the dense arrays the sweep, the tally and the Tick read.
+// N >= 2 means a quorum of at least two: the candidate's own grant never wins, so becomeLeader is not reachable here.
+//
+// Order comes from the Tick's own per-wave counts and popcounts, beat_build_kernel's shape: a workgroup owns one 1,024-group
+// block, ranks its MsgHup bits behind the sum of the earlier waves' counts (or the scan's offsets past 16K waves), compacts the
+// ids in LDS, and one lane works per MsgHup group of rank < n_vb = min(MsgHup groups of this Tick, hup_cap).  No atomics, the
+// same layout on every run.  Groups of rank >= hup_cap are the caller's: nothing of them is touched.
+//
+// The result record the host applies (the HardState to persist) is the 32-byte raftq_step_out_s_t whatever format the handle is
+// set to: two 16-byte stores to page-locked host memory per campaign.  A vote record is four 16-byte stores (beat_store's
+// pattern), neighbouring lanes to neighbouring records of a peer's slice.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "raftq_step_kernels.hpp"
+#include "raftq_wire_kernels.hpp"
+
+namespace raftqk {
+
+struct ElectArgs {
+  const uint64_t* hup_bits;      // [gpad / 64] the Tick's MsgHup bits: word 4 w + k, bit l = group 256 w + 4 l + k
+  const uint4* partials;         // [gpad / 256] the Tick's per-wave {MsgHup, MsgBeat} counts
+  uint64_t n_chunks;             // gpad / 256
+  const uint64_t* wave_off_hup;  // scan_partials_kernel's exclusive MsgHup offsets (handles of more than 16K waves), or nullptr
+  const uint64_t* totals;        // [2] the lists kernel's totals: {MsgHup, MsgBeat} groups of this Tick
+  NodeArrays a;                  // the handle's records and dense arrays (no response records, no at-tail bitmap)
+  uint64_t hup_cap, beat_cap;    // groups campaigned / beaten at most; enc holds (beat_cap + hup_cap) * (n_peers - 1) records
+  StepOutS* camp;                // [hup_cap] page-locked host memory: the result of hup id r of the list
+  WireMsg* enc;                  // the encoder's input: the heartbeat records first (beat_build_kernel), the votes behind them
+};
+
+__device__ __forceinline__ void vote_store(WireMsg* dst, uint64_t group, uint64_t term, uint64_t log_term, uint64_t index, uint32_t from, uint32_t to) {
+  uint4* q = reinterpret_cast<uint4*>(dst);
+  q[0] = make_uint4((uint32_t)group, (uint32_t)(group >> 32), (uint32_t)term, (uint32_t)(term >> 32));
+  q[1] = make_uint4((uint32_t)log_term, (uint32_t)(log_term >> 32), (uint32_t)index, (uint32_t)(index >> 32));
+  q[2] = make_uint4(0u, 0u, 0u, 0u);                                   // commit, reject_hint
+  q[3] = make_uint4(from, (uint32_t)kMsgVote | (to << 16), 0u, 0u);    // from | type, reject, to, flags | ent_first | n_ents
+}
+
+// One workgroup per 1,024-group block of the Tick (its four waves' 256-group chunks).
+static __global__ __launch_bounds__(kBlock) void elect_build_kernel(ElectArgs e) {
+  __shared__ uint64_t red[kWaves];
+  __shared__ uint32_t mine[kWaves];
+  __shared__ uint32_t ids[kBlock * 4];
+  __shared__ uint64_t n_hup_s, n_beat_s;
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint64_t first_wave = (uint64_t)blockIdx.x * kWaves;
+  // the block's exclusive offset among the MsgHup groups: the sum of the earlier waves' counts, or the scan's offsets
+  uint64_t acc = 0;
+  if (e.wave_off_hup == nullptr) {
+    uint32_t b0 = 0, b1 = 0;
+    uint64_t i = tid;
+    for (; i + kBlock < first_wave; i += 2 * kBlock) {
+      b0 += e.partials[i].x;
+      b1 += e.partials[i + kBlock].x;
+    }
+    if (i < first_wave) b0 += e.partials[i].x;
+    acc = (uint64_t)b0 + b1;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  } else if (lane == 0 && wave == 0) {
+    acc = e.wave_off_hup[first_wave];
+  }
+  if (lane == 0) red[wave] = acc;
+  if (tid < (uint32_t)kWaves) mine[tid] = first_wave + tid < e.n_chunks ? e.partials[first_wave + tid].x : 0u;
+  if (tid == 0) {
+    n_hup_s = e.totals[0];
+    n_beat_s = e.totals[1];
+  }
+  __syncthreads();
+  uint64_t pos = 0;  // rank of this block's first MsgHup group
+  uint32_t tot = 0;  // MsgHup groups of this block
+#pragma unroll
+  for (int k = 0; k < kWaves; ++k) {
+    pos += red[k];
+    tot += mine[k];
+  }
+  const uint64_t n_vb = n_hup_s < e.hup_cap ? n_hup_s : e.hup_cap;
+  const uint64_t n_bb = n_beat_s < e.beat_cap ? n_beat_s : e.beat_cap;
+  const uint64_t n_slices = e.a.n_peers - 1;
+  const uint64_t wv = first_wave + wave;
+  if (wv < e.n_chunks && pos < n_vb) {  // wave-uniform
+    uint32_t loc = 0;
+#pragma unroll
+    for (int k = 0; k < kWaves; ++k) loc += (uint32_t)k < wave ? mine[k] : 0u;
+    const uint64_t below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    uint64_t hb[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) hb[k] = e.hup_bits[wv * 4 + k];
+    uint32_t r = loc + __popcll(hb[0] & below) + __popcll(hb[1] & below) + __popcll(hb[2] & below) + __popcll(hb[3] & below);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if ((hb[k] >> lane) & 1) ids[r++] = (uint32_t)(wv * 256 + 4ull * lane + k);
+  }
+  __syncthreads();
+  if (pos < n_vb) {
+    const uint64_t left = n_vb - pos;
+    const uint32_t take = left < tot ? (uint32_t)left : tot;  // this block's groups of rank < n_vb
+    WireMsg* const votes = e.enc + n_bb * n_slices;
+    for (uint32_t r = tid; r < take; r += kBlock) {
+      const uint64_t g = ids[r];
+      const uint64_t at = pos + r;
+      const bool known = g < e.a.n_groups;  // (the Tick flags no padding group)
+      uint64_t term = 0, last_index = 0, last_term = 0;
+      u64x2 c0, c1;
+      c0.x = c0.y = c1.x = c1.y = 0;
+      if (known) {
+        Node node(e.a, g);
+        // Step(MsgHup) -> campaign(): the two calls Node::step makes (a quorum is at least two: the own grant does not win)
+        node.become_candidate();
+        uint32_t granted, recorded;
+        node.poll(e.a.self, true, granted, recorded);
+        node.store();
+        term = node.term; last_index = node.last_index; last_term = node.last_term;
+        // == put_result(kFmtS32) of step()'s record: commit carries the candidate's lastTerm
+        c0.x = term; c0.y = last_index;
+        c1.x = last_term;
+        c1.y = (uint64_t)(uint8_t)node.vote | ((uint64_t)kOutCampaign << 16) | ((uint64_t)(kFlagHardState | kFlagAnswered) << 32) |
+               ((uint64_t)node.role << 40);
+      }
+      u64x2* cq = reinterpret_cast<u64x2*>(e.camp + at);
+      cq[0] = c0;
+      cq[1] = c1;
+#pragma unroll
+      for (uint32_t p = 0; p < (uint32_t)kMaxPeers; ++p) {
+        if (p >= e.a.n_peers || p == e.a.self) continue;
+        const uint64_t slice = p < e.a.self ? p : p - 1;
+        vote_store(votes + slice * n_vb + at, g, term, last_term, last_index, e.a.self, known ? p : 0xffu);
+      }
+    }
+  }
+  // fillers behind both sections: the encoder counts them as refused and writes nothing for them
+  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+  for (uint64_t k = (n_bb + n_vb) * n_slices + (uint64_t)blockIdx.x * kBlock + tid; k < (e.beat_cap + e.hup_cap) * n_slices; k += stride) {
+    WireMsg f{};
+    f.to = 0xff;
+    e.enc[k] = f;
+  }
+}
+
+}  // namespace raftqk

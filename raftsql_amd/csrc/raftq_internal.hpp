@@ -293,6 +293,7 @@ struct TickLists {
   unsigned flags;
   uint64_t cap_h, cap_b, beat_at, map_off;  // the in-place lists' layout (raftq_t::tl_*)
   const uint64_t* off_beat;                 // after _enqueue: scan_partials_kernel's MsgBeat offsets (more than 16K waves), or nullptr
+  const uint64_t* off_h = nullptr;          // ... and its MsgHup offsets (raftq_tick_elect_frames)
 };
 int tick_lists_prepare(raftq_t* h, const char* who, unsigned flags, uint64_t hup_cap, uint64_t beat_cap, TickLists* tl);
 int tick_lists_enqueue(raftq_t* h, TickLists* tl);

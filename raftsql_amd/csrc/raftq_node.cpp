@@ -416,9 +416,21 @@ struct raftq_node {
   // rounded up so that the rounds' buffers are not reallocated as it moves; groups beyond it get their heartbeats from
   // bcast_heartbeat as before.  RAFTQ_NODE_BEAT_CAP=k (tests): beat_cap is never more than k.
   bool beat_device = false;
+  // RAFTQ_NODE_ELECT_DEVICE=1 (off by default): every tick of a turn is raftq_tick_elect_frames -- the campaigns of the groups whose
+  // election timers fired are applied on the device where the Tick flagged them, their MsgVotes are marshalled behind the tick's
+  // heartbeats (beat_cap as above with RAFTQ_NODE_BEAT_DEVICE=1, else 0: the host beats), and no local MsgHup is raised for them:
+  // n->local stays empty unless raftq_node_campaign was called, so the turn's inbound frames keep the fused path.  The 32-byte
+  // results (BeatRound::camp) go through apply_result right after the tick -- ahead of everything else the turn applies, where
+  // their local messages stood: term, vote, role, the HardState to persist.  hup_cap = tick_list.size(), grown on demand as
+  // before; RAFTQ_NODE_ELECT_CAP=k (tests): never more than k -- groups behind it get their local MsgHup as before.
+  bool elect_device = false;
+  uint64_t elect_cap_limit = ~0ull;
+  std::vector<uint64_t> tick_head;  // [peer] messages the turn's ticks queued on the host (heartbeats): the device's votes go behind them
   struct BeatRound {
     PinBuf out;         // the device-built frames of one tick
-    PinU64 off, peer;   // their byte offsets, peer slices ([N + 1] frame indices)
+    PinU64 off, peer;   // their byte offsets, peer slices ([N + 1] frame indices; with votes [2 (N + 1)]: the heartbeats', the votes')
+    PinBuf camp;        // raftq_step_out_s_t[hup_cap]: the campaigns' results (RAFTQ_NODE_ELECT_DEVICE)
+    bool votes = false; // peer holds the vote section's slices too
   };
   std::vector<std::unique_ptr<BeatRound>> beat_rounds;  // reused turn after turn; a turn usually ticks once
   size_t beat_pending = 0;                // rounds of this turn whose frames are not on the queues yet
@@ -888,7 +900,7 @@ void apply_result(raftq_node_t* n, const raftq_step_out_t& o, const raftq_wire_m
       if (!answered) send(n, o.to, gi, RAFTQ_MSG_HEARTBEAT_RESP, o.term);
       break;
     case RAFTQ_OUT_CAMPAIGN:
-      for (uint32_t p = 0; p < n->N; ++p) {
+      for (uint32_t p = 0; p < n->N && !answered; ++p) {  // (answered: the MsgVotes are in the tick's BeatRound)
         if (p == n->self) continue;
         raftq_wire_msg_t& r = send(n, p, gi, RAFTQ_MSG_VOTE, o.term);
         r.index = o.index;
@@ -1026,7 +1038,7 @@ void publish_responses(raftq_node_t* n, uint32_t only) {
 }
 
 // the ticks' device-built heartbeats (raftq_tick_frames, RAFTQ_NODE_BEAT_DEVICE) onto peer p's queue, or every peer's (p = ~0u),
-// tick after tick; the last peer ends what is pending.  Called in front of publish_responses: a turn's heartbeats are its first sends.
+// tick after tick.  Called in front of publish_responses: a turn's heartbeats are its first sends.
 void publish_beats(raftq_node_t* n, uint32_t only) {
   if (!n->beat_pending) return;
   for (uint32_t p = 0; p < n->N; ++p) {
@@ -1035,6 +1047,22 @@ void publish_beats(raftq_node_t* n, uint32_t only) {
       raftq_node::BeatRound& br = *n->beat_rounds[r];
       const uint64_t* po = br.peer.data();
       append_frames(n->outbound[p], br.out.p, br.off.data(), po[p], po[p + 1]);
+    }
+  }
+  if (!n->elect_device && (only == ~0u || only == n->N - 1)) n->beat_pending = 0;
+}
+
+// the ticks' device-built MsgVotes (raftq_tick_elect_frames, RAFTQ_NODE_ELECT_DEVICE) onto peer p's queue, or every peer's: behind
+// the ticks' heartbeats -- the device's and the ones the host queued -- and ahead of everything else, the place the host path's own
+// MsgVotes have (the local MsgHups are a turn's first messages through Step); the last peer ends what is pending
+void publish_votes(raftq_node_t* n, uint32_t only) {
+  if (!n->beat_pending || !n->elect_device) return;
+  for (uint32_t p = 0; p < n->N; ++p) {
+    if (only != ~0u && p != only) continue;
+    for (size_t r = 0; r < n->beat_pending; ++r) {
+      raftq_node::BeatRound& br = *n->beat_rounds[r];
+      const uint64_t* po = br.peer.data();
+      if (br.votes) append_frames(n->outbound[p], br.out.p, br.off.data(), po[n->N + 1 + p], po[n->N + 2 + p]);
     }
   }
   if (only == ~0u || only == n->N - 1) n->beat_pending = 0;
@@ -1059,6 +1087,7 @@ int flush_outbound(raftq_node_t* n, std::unique_lock<std::mutex>& lk) {
     // only device-built heartbeats / responses this turn: the WAL first, then the frames
     if (const int rc = wal_end(n, lk, raftq_node::kPhDevEncode)) return rc;
     publish_beats(n, ~0u);
+    publish_votes(n, ~0u);
     publish_responses(n, ~0u);
     return RAFTQ_OK;
   }
@@ -1104,8 +1133,12 @@ int flush_outbound(raftq_node_t* n, std::unique_lock<std::mutex>& lk) {
   for (uint32_t p = 0; p < n->N; ++p) {
     PeerQueue& q = n->outbound[p];
     publish_beats(n, p);      // the ticks' device-built heartbeats come first, as on the host path
+    // RAFTQ_NODE_ELECT_DEVICE: the heartbeats the ticks queued on the host (the head of the lane), then the device-built MsgVotes
+    const uint64_t head = n->elect_device && p < n->tick_head.size() ? std::min<uint64_t>(n->tick_head[p], first[p + 1] - first[p]) : 0;
+    append_frames(q, n->enc_out.p, n->enc_off.data(), first[p], first[p] + head);
+    publish_votes(n, p);
     publish_responses(n, p);  // the device-built answers of the inbound round next
-    append_frames(q, n->enc_out.p, n->enc_off.data(), first[p], first[p + 1]);
+    append_frames(q, n->enc_out.p, n->enc_off.data(), first[p] + head, first[p + 1]);
     if (n_props && p != n->self) {
       append_frames(q, n->enc_out.p, n->enc_off.data(), nm + (uint64_t)run * n_props, nm + (uint64_t)(run + 1) * n_props);
       ++run;
@@ -1341,10 +1374,35 @@ int beat_round(raftq_node_t* n, uint64_t* n_hup, uint64_t* n_beat, uint64_t* n_b
   const uint64_t n_max = cap * (n->N - 1);
   if (!br.out.reserve(std::max<uint64_t>(n_max * RAFTQ_RESPOND_FRAME_MAX, 16)) || !br.off.resize(n_max + 1) || !br.peer.resize(n->N + 1)) return RAFTQ_ENOMEM;
   raftq_wire_counts_t cnt;
+  br.votes = false;
   if (const int rc = raftq_tick_frames(n->h, RAFTQ_TICK_BEAT_BITMAP, n->tick_list.size(), cap, n_hup, n_beat, br.out.p, n_max * RAFTQ_RESPOND_FRAME_MAX,
                                        br.off.data(), br.peer.data(), &cnt))
     return rc;
   *n_built = std::min(*n_beat, cap);
+  *n_frames = cnt.n_msgs;
+  if (cnt.n_msgs) ++n->beat_pending;  // onto the queues where the turn's frames are published (flush_outbound)
+  return RAFTQ_OK;
+}
+
+// One tick through raftq_tick_elect_frames (RAFTQ_NODE_ELECT_DEVICE), with mu released: beat_round plus the campaigns of the first
+// *n_camp MsgHup groups, applied on the device; their results are (*camp)[0 .. *n_camp), their MsgVotes in the same BeatRound.
+int elect_round(raftq_node_t* n, uint64_t* n_hup, uint64_t* n_beat, uint64_t* n_built, uint64_t* n_camp, const raftq_step_out_s_t** camp, uint64_t* n_frames) {
+  if (n->beat_pending == n->beat_rounds.size()) n->beat_rounds.emplace_back(new raftq_node::BeatRound());
+  raftq_node::BeatRound& br = *n->beat_rounds[n->beat_pending];
+  const uint64_t cap = n->beat_device ? std::min(std::min<uint64_t>((n->n_leading + 1023) / 1024 * 1024, n->G), n->beat_cap_limit) : 0;
+  const uint64_t hup_cap = std::min<uint64_t>(n->tick_list.size(), n->elect_cap_limit);
+  const uint64_t n_max = (cap + hup_cap) * (n->N - 1);
+  if (!br.out.reserve(std::max<uint64_t>(n_max * RAFTQ_RESPOND_FRAME_MAX, 16)) || !br.off.resize(n_max + 1) || !br.peer.resize(2 * (n->N + 1)) ||
+      !br.camp.reserve(std::max<uint64_t>(hup_cap * sizeof(raftq_step_out_s_t), 16)))
+    return RAFTQ_ENOMEM;
+  raftq_wire_counts_t cnt;
+  br.votes = true;
+  if (const int rc = raftq_tick_elect_frames(n->h, RAFTQ_TICK_BEAT_BITMAP, hup_cap, cap, n_hup, n_beat, hup_cap ? br.camp.as<raftq_step_out_s_t>() : nullptr,
+                                             br.out.p, n_max * RAFTQ_RESPOND_FRAME_MAX, br.off.data(), br.peer.data(), &cnt))
+    return rc;
+  *n_built = std::min(*n_beat, cap);
+  *n_camp = std::min(*n_hup, hup_cap);
+  *camp = br.camp.as<raftq_step_out_s_t>();
   *n_frames = cnt.n_msgs;
   if (cnt.n_msgs) ++n->beat_pending;  // onto the queues where the turn's frames are published (flush_outbound)
   return RAFTQ_OK;
@@ -1359,6 +1417,10 @@ int tick(Turn& t) {
     uint64_t n_beat = 0, map_words = 0;
     uint64_t n_built = 0, n_frames = 0;  // RAFTQ_NODE_BEAT_DEVICE: the first n_built MsgBeat groups' heartbeats are the device's, n_frames frames
     const uint64_t* beat_map = nullptr;
+    // RAFTQ_NODE_ELECT_DEVICE: the first n_camp MsgHup groups (camp_ids, the head of the Tick's list) have campaigned on the device
+    uint64_t n_camp = 0;
+    const raftq_step_out_s_t* camp = nullptr;
+    const uint32_t* camp_ids = nullptr;
     {
       Unlocked u(t.lk);
       // the device compacts the two short lists (ascending group ids); no G-byte read-back and no loop over every
@@ -1367,20 +1429,30 @@ int tick(Turn& t) {
       // (raftq_tick_collect_lists: 4-byte ids read where the device left them, the MsgBeat groups as a bitmap -- with
       // HeartbeatTick 1 the beat list is the set of groups this node leads, every tick)
       uint64_t n_hup = 0, n_listed = 0;
-      int rc = n->beat_device ? beat_round(n, &n_hup, &n_beat, &n_built, &n_frames)
-                              : raftq_tick_collect_lists(n->h, RAFTQ_TICK_BEAT_BITMAP, n->tick_list.size(), 0, &n_hup, &n_beat);
+      int rc = n->elect_device  ? elect_round(n, &n_hup, &n_beat, &n_built, &n_camp, &camp, &n_frames)
+               : n->beat_device ? beat_round(n, &n_hup, &n_beat, &n_built, &n_frames)
+                                : raftq_tick_collect_lists(n->h, RAFTQ_TICK_BEAT_BITMAP, n->tick_list.size(), 0, &n_hup, &n_beat);
       const uint32_t* hups = nullptr;
       if (rc == RAFTQ_OK) rc = raftq_last_tick_lists(n->h, &hups, &n_listed, nullptr, nullptr, &beat_map, &map_words);
+      camp_ids = hups;  // (n_listed >= n_camp: the list and the campaigns share hup_cap; valid until the next Tick)
+      // the MsgHup groups behind the device's first n_camp get their local message as before
       if (rc == RAFTQ_OK && n_hup > n_listed) {  // more timers fired than the list was sized for: fetch them again, alone
         n->tick_list.resize(n_hup);
         rc = raftq_collect_hups(n->h, n->tick_list.data(), n->tick_list.size(), &n_hup);
         if (rc == RAFTQ_OK)
-          for (uint64_t i = 0; i < n_hup; ++i) local.push_back(local_msg(n, n->tick_list[i], RAFTQ_MSG_HUP));
+          for (uint64_t i = n_camp; i < n_hup; ++i) local.push_back(local_msg(n, n->tick_list[i], RAFTQ_MSG_HUP));
       } else if (rc == RAFTQ_OK) {
-        for (uint64_t i = 0; i < n_hup; ++i) local.push_back(local_msg(n, hups[i], RAFTQ_MSG_HUP));
+        for (uint64_t i = n_camp; i < n_hup; ++i) local.push_back(local_msg(n, hups[i], RAFTQ_MSG_HUP));
       }
       if (rc != RAFTQ_OK) return fail(t, rc, "tick");
     }
+    // the device's campaigns: Step has run, their MsgVotes are built -- what is left is apply_result's bookkeeping (term, vote, role,
+    // the HardState to persist), ahead of everything else the turn applies
+    for (uint64_t r = 0; r < n_camp; ++r) {
+      const raftq_wire_msg_t im = local_msg(n, camp_ids[r], RAFTQ_MSG_HUP);
+      apply_result(n, widen(camp[r], im), im);
+    }
+    n->stats.msgs_stepped += n_camp;
     n->stats.msgs_sent += n_frames;
     n->stats.msgs_built_on_device += n_frames;
     if (n_beat > n_built) {  // stepLeader MsgBeat on the host: every MsgBeat group, or the ones behind the device's first n_built
@@ -1403,6 +1475,10 @@ int tick(Turn& t) {
     }
   }
   if (local.size() >= kLocal) return fail(t, RAFTQ_EINVAL, "more than 2^31 local messages in one turn");
+  if (n->elect_device) {  // what the ticks queued on the host: every peer's heartbeats of the groups the device did not beat for
+    n->tick_head.resize(n->N);
+    for (uint32_t p = 0; p < n->N; ++p) n->tick_head[p] = n->out_lane[p].msgs.size();
+  }
   return RAFTQ_OK;
 }
 
@@ -1869,6 +1945,8 @@ int raftq_node_create(int device, uint64_t n_groups, uint32_t n_peers, uint32_t 
   if (const char* rk = std::getenv("RAFTQ_NODE_RESPOND_CHECK")) n->respond_check = std::atoi(rk) != 0;
   if (const char* bd = std::getenv("RAFTQ_NODE_BEAT_DEVICE")) n->beat_device = std::atoi(bd) != 0 && n_peers >= 2;
   if (const char* bc = std::getenv("RAFTQ_NODE_BEAT_CAP")) n->beat_cap_limit = std::strtoull(bc, nullptr, 10);
+  if (const char* ed = std::getenv("RAFTQ_NODE_ELECT_DEVICE")) n->elect_device = std::atoi(ed) != 0 && n_peers >= 2;
+  if (const char* ec = std::getenv("RAFTQ_NODE_ELECT_CAP")) n->elect_cap_limit = std::strtoull(ec, nullptr, 10);
   if (const char* ev = std::getenv("RAFTQ_PROFILE_EVERY")) n->prof_every = std::strtoull(ev, nullptr, 10);
   try {
     n->groups.resize(n_groups);

@@ -13,6 +13,7 @@
 #include <string>
 
 #include "raftq_beat_kernels.hpp"
+#include "raftq_elect_kernels.hpp"
 #include "raftq_internal.hpp"
 #include "raftq_propose_kernels.hpp"
 #include "raftq_respond_kernels.hpp"
@@ -817,6 +818,98 @@ extern "C" int raftq_tick_frames(raftq_t* h, unsigned flags, uint64_t hup_cap, u
     // every record past the last frame is a filler the encoder refuses; any other refusal, or bytes beyond the bound, is a bug here
     if (h->wire_pin[kPinCall + kPinRefused] != n_max - frames || bytes > enc_cap)
       return fail(h, RAFTQ_EHIP, std::string(who) + ": the marshal of the heartbeats disagrees with their layout; the output is not valid");
+  } else if (frame_off) {
+    frame_off[0] = 0;
+  }
+  if (counts) *counts = raftq_wire_counts_t{frames, 0, 0, bytes};
+  return RAFTQ_OK;
+}
+
+// ---- raftq_tick_elect_frames ------------------------------------------------------------------------------------------
+// raftq_tick_frames with the election round behind the heartbeat round: Tick -> lists -> beat_build -> elect_build -> encoder ->
+// flag.  The encoder's input holds (beat_cap + hup_cap) * (N - 1) records: beat_build_kernel runs as in raftq_tick_frames over the
+// first beat_cap * (N - 1) (its fillers start where the heartbeats end), elect_build_kernel, behind it in stream order, puts the
+// votes directly behind the heartbeats and the fillers behind both.
+extern "C" int raftq_tick_elect_frames(raftq_t* h, unsigned flags, uint64_t hup_cap, uint64_t beat_cap, uint64_t* n_hup, uint64_t* n_beat,
+                                       raftq_step_out_s_t* camp, void* out, uint64_t cap, uint64_t* frame_off, uint64_t* peer_off,
+                                       raftq_wire_counts_t* counts) {
+  const char* who = "raftq_tick_elect_frames";
+  if (int rc = raftq_detail::use_device_idle(h, who)) return rc;
+  if (counts) *counts = raftq_wire_counts_t{0, 0, 0, 0};
+  if (!n_hup || !n_beat || !peer_off) return fail(h, RAFTQ_EINVAL, std::string(who) + ": null argument");
+  if (flags & ~RAFTQ_TICK_BEAT_BITMAP) return fail(h, RAFTQ_EINVAL, std::string(who) + ": unknown flag");
+  if (h->N < 2) return fail(h, RAFTQ_EINVAL, std::string(who) + ": a single-peer group has nobody to ask for a vote -- use raftq_tick_collect_lists");
+  // the exact worst case: beat_cap + hup_cap groups, N - 1 frames of RAFTQ_RESPOND_FRAME_MAX bytes each -- refused before anything
+  // runs, so a call that has ticked never fails for output space
+  const uint64_t slices = h->N - 1;
+  const uint64_t frames_cap = ((uint64_t)1 << 31) / RAFTQ_RESPOND_FRAME_MAX;
+  if (beat_cap >= ((uint64_t)1 << 31) || hup_cap >= ((uint64_t)1 << 31) || (beat_cap + hup_cap) * slices > kMaxItems || (beat_cap + hup_cap) * slices > frames_cap)
+    return fail(h, RAFTQ_EINVAL, std::string(who) + ": beat_cap + hup_cap too large ((beat_cap + hup_cap) * (N - 1) * RAFTQ_RESPOND_FRAME_MAX must stay within 2^31 bytes)");
+  const uint64_t n_max = (beat_cap + hup_cap) * slices;
+  if (cap < n_max * RAFTQ_RESPOND_FRAME_MAX)
+    return fail(h, RAFTQ_EINVAL, std::string(who) + ": cap is below (beat_cap + hup_cap) * (N - 1) * RAFTQ_RESPOND_FRAME_MAX = " +
+                                     std::to_string(n_max * RAFTQ_RESPOND_FRAME_MAX) + " bytes -- the call has not ticked");
+  if ((n_max != 0 && !out) || (hup_cap != 0 && !camp)) return fail(h, RAFTQ_EINVAL, std::string(who) + ": null argument");
+  if (!h->node_rec && !h->self_set)
+    return fail(h, RAFTQ_ESTATE, std::string(who) + ": the handle holds no node state (raftq_set_self / raftq_load_node first)");
+  if (int rc = ensure_pin(h)) return rc;
+  Views v;
+  void *v_out = v.opt(out), *v_off = v.opt(frame_off), *v_camp = v.add(camp, hup_cap != 0);
+  v.add(peer_off);
+  if (!v.ok)
+    return fail(h, RAFTQ_EINVAL, std::string(who) + ": camp, out, frame_off and peer_off must be page-locked (raftq_host_alloc, hipHostMalloc, "
+                                                    "hipHostRegister) and 16-byte aligned -- the call has neither ticked nor campaigned");
+  // every allocation before the tick kernel: the records (and, where something other than Step wrote the dense arrays, their
+  // refresh), the Tick's lists, the encoder's control block, scratch and output buffer
+  NodeArrays na;
+  if (int rc = raftq_detail::node_records_of(h, who, &na)) return rc;
+  raftq_detail::TickLists tl;
+  if (int rc = raftq_detail::tick_lists_prepare(h, who, flags, hup_cap, beat_cap, &tl)) return rc;
+  const uint64_t enc_cap = n_max * RAFTQ_RESPOND_FRAME_MAX;  // what the encoder may write: never more than the worst case
+  StreamCall sc = beat_marshal_call(n_max, enc_cap);
+  if (n_max != 0)
+    if (int rc = stream_prepare(h, sc)) return rc;  // (the launch's epoch and feed: nothing of it runs before the encoder below)
+  if (hup_cap != 0) h->last_flags &= ~RAFTQ_SWEEP_NO_ADOPT;  // as in raftq_step_submit: the live state moves
+  // Tick -> lists -> beat_build -> elect_build -> encoder -> flag, back to back; one wait
+  if (int rc = raftq_detail::tick_lists_enqueue(h, &tl)) return rc;
+  if (n_max != 0) {
+    const uint64_t nw = h->gpad / 256;
+    const dim3 grid((unsigned)((nw + kWaves - 1) / kWaves));
+    WireMsg* const enc = (WireMsg*)sc.in.seg[0].dst;
+    if (beat_cap != 0) {
+      BeatArgs ba{(const uint64_t*)h->beat_bits, (const uint4*)h->tick_partials, nw, tl.off_beat, (const uint64_t*)h->d_total, na.rec, h->G, h->N,
+                  h->self_peer, beat_cap, enc};
+      hipLaunchKernelGGL(beat_build_kernel, grid, dim3(kBlock), 0, h->stream, ba);
+    }
+    // (hup_cap == 0: the fillers behind beat_cap * (N - 1) are beat_build_kernel's own -- the call is raftq_tick_frames)
+    if (hup_cap != 0) {
+      ElectArgs ea{(const uint64_t*)h->hup_bits, (const uint4*)h->tick_partials, nw, tl.off_h, (const uint64_t*)h->d_total, na, hup_cap, beat_cap,
+                   (StepOutS*)v_camp, enc};
+      hipLaunchKernelGGL(elect_build_kernel, grid, dim3(kBlock), 0, h->stream, ea);
+    }
+    HIPCHK(h, hipGetLastError());
+    if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, n_max, (uint64_t)0, (uint64_t)0, (uint8_t*)h->wire_out.d, (uint8_t*)v_out, enc_cap,
+                               (uint64_t*)v_off, sc.ctl, h->wire_pin_d + kPinCall, (const unsigned int*)nullptr, 0u))
+      return rc;
+  }
+  if (int rc = raftq_detail::tick_lists_finish(h, who, tl, n_hup, n_beat)) return rc;
+  const uint64_t n_bb = std::min(*n_beat, beat_cap), n_vb = std::min(*n_hup, hup_cap), frames = (n_bb + n_vb) * slices;
+  uint64_t at = 0;
+  for (uint32_t p = 0; p <= h->N; ++p) {  // the heartbeat section's slices, then the vote section's
+    peer_off[p] = at;
+    if (p < h->N && p != h->self_peer) at += n_bb;
+  }
+  for (uint32_t p = 0; p <= h->N; ++p) {
+    peer_off[h->N + 1 + p] = at;
+    if (p < h->N && p != h->self_peer) at += n_vb;
+  }
+  uint64_t bytes = 0;
+  if (n_max != 0) {
+    if (int rc = tile_ctl_check(h, who, kPinCall)) return rc;
+    bytes = h->wire_pin[kPinCall + kPinTotal];
+    // every record past the last frame is a filler the encoder refuses; any other refusal, or bytes beyond the bound, is a bug here
+    if (h->wire_pin[kPinCall + kPinRefused] != n_max - frames || bytes > enc_cap)
+      return fail(h, RAFTQ_EHIP, std::string(who) + ": the marshal of the heartbeats and votes disagrees with their layout; the output is not valid");
   } else if (frame_off) {
     frame_off[0] = 0;
   }

@@ -286,6 +286,45 @@ class WireEngine(NodeEngine):
         return (out[: int(c.bytes)] if out is not None else np.zeros(0, np.uint8), frame_off[: n_frames + 1] if frame_off is not None else None,
                 peer_off[: self.n_peers + 1], c, hups, int(nh.value), second, int(nb.value))
 
+    def tick_elect_frames(self, camp: np.ndarray | None, out: np.ndarray, frame_off: np.ndarray | None, peer_off: np.ndarray, hup_cap: int,
+                          beat_cap: int, beat_bitmap: bool = False, cap: int | None = None):
+        """raftq_tick_elect_frames: tick_frames plus the election round -- Step(MsgHup) applied on the device to the first hup_cap
+        MsgHup groups and their N - 1 MsgVotes marshalled behind the heartbeats; one submission, one wait.  camp: STEP_OUT_S_DT
+        [hup_cap] (None only when hup_cap == 0); out: uint8 of at least respond_cap(beat_cap + hup_cap) bytes (cap: what the call is
+        told instead of len(out)); frame_off: uint64 [(beat_cap + hup_cap) * (N - 1) + 1] or None; peer_off: uint64 [2 * (N + 1)];
+        all page-locked (engine.pinned_empty).  -> (bytes (a view of out), frame_off[:n_frames + 1] | None, peer_off, counts,
+        camp[:min(n_hup, hup_cap)], hups view u32, n_hup, beats view u32 | bitmap view u64, n_beat); the list views are the
+        library's memory, valid until the next Tick call"""
+        from .step import OUT_S_DT
+
+        n_max = (int(beat_cap) + int(hup_cap)) * (self.n_peers - 1)
+        assert peer_off.dtype == np.uint64 and len(peer_off) >= 2 * (self.n_peers + 1)
+        assert out is None or out.dtype == np.uint8
+        assert frame_off is None or (frame_off.dtype == np.uint64 and len(frame_off) >= n_max + 1)
+        assert camp is None or (camp.dtype == OUT_S_DT and len(camp) >= int(hup_cap))
+        nh, nb, c = C.c_uint64(0), C.c_uint64(0), _lib.WireCounts()
+        self._chk(self._lib.raftq_tick_elect_frames(self._h, _lib.TICK_BEAT_BITMAP if beat_bitmap else 0, int(hup_cap), int(beat_cap), C.byref(nh),
+                                                    C.byref(nb), camp.ctypes.data if camp is not None and len(camp) else None,
+                                                    out.ctypes.data if out is not None and len(out) else None,
+                                                    (len(out) if out is not None else 0) if cap is None else int(cap),
+                                                    frame_off.ctypes.data if frame_off is not None else None, peer_off.ctypes.data, C.byref(c)))
+        ph, pb, pm = C.c_void_p(None), C.c_void_p(None), C.c_void_p(None)
+        lh, lb, lm = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._lib.raftq_last_tick_lists(self._h, C.byref(ph), C.byref(lh), C.byref(pb), C.byref(lb), C.byref(pm), C.byref(lm)))
+
+        def view(p, n, dt):
+            if not n:
+                return np.empty(0, dtype=dt)
+            return np.frombuffer((C.c_char * (int(n) * np.dtype(dt).itemsize)).from_address(p.value), dtype=dt)
+
+        hups = view(ph, lh.value, np.uint32)
+        second = view(pm, lm.value, np.uint64) if beat_bitmap else view(pb, lb.value, np.uint32)
+        n_frames = int(c.n_msgs)
+        n_vb = min(int(nh.value), int(hup_cap))
+        return (out[: int(c.bytes)] if out is not None else np.zeros(0, np.uint8), frame_off[: n_frames + 1] if frame_off is not None else None,
+                peer_off[: 2 * (self.n_peers + 1)], c, camp[:n_vb] if camp is not None else np.zeros(0, OUT_S_DT), hups, int(nh.value), second,
+                int(nb.value))
+
     def propose_frames(self, props: np.ndarray, prop_ents: np.ndarray, msgs: np.ndarray, ents: np.ndarray, pool: np.ndarray, out: np.ndarray,
                        off: np.ndarray | None = None):
         """raftq_propose_frames: appendEntry + bcastAppend for props[] on the device, written into the encoder's input, and the
