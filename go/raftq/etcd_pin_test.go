@@ -388,3 +388,96 @@ func TestDecodePackedAgainstDecode(t *testing.T) {
 		}
 	}
 }
+
+// TestStepVotersAgainstEtcd: the masked rules of raftq_step_set_voters (include/raftq_step.h) beside a real raft whose `prs` map IS
+// the mask.  The engine has N = 5 peer slots; the group's members are the raft IDs in `members` (slot = ID - 1), so etcd's q() is
+// len(prs)/2 + 1 = popcount(mask)/2 + 1.  Same messages to both; {term, vote, commit, lead, role} compared after every one.  A
+// message from a slot that is no member goes to the engine only where etcd would ignore it as well (an ack of a peer without
+// Progress is dropped upstream; the engine stores its Match and does not count it -- the commit index must not move).
+func TestStepVotersAgainstEtcd(t *testing.T) {
+	const n = 5
+	for _, members := range [][]uint64{{1}, {1, 2}, {1, 2, 4}, {1, 3, 4, 5}, {1, 2, 3, 4, 5}} {
+		rng := rand.New(rand.NewSource(int64(0x707E25 + len(members))))
+		mask := uint16(0)
+		peers := make([]raft.Peer, len(members))
+		for i, id := range members {
+			peers[i] = raft.Peer{ID: id}
+			mask |= 1 << (id - 1)
+		}
+		st := raft.NewMemoryStorage()
+		c := &raft.Config{ID: 1, ElectionTick: 10, HeartbeatTick: 1, Storage: st, MaxSizePerMsg: 1 << 20, MaxInflightMsgs: 256}
+		rn, err := raft.NewRawNode(c, peers)
+		if err != nil {
+			t.Fatal(err)
+		}
+		drain := func() {
+			for rn.HasReady() {
+				rd := rn.Ready()
+				st.Append(rd.Entries)
+				if !raft.IsEmptyHardState(rd.HardState) {
+					st.SetHardState(rd.HardState)
+				}
+				rn.Advance(rd)
+			}
+		}
+		drain()
+		e, err := New(0, 1, n)
+		if err != nil {
+			t.Skip(err) // no GPU here
+		}
+		defer e.Close()
+		if err := e.LoadVoters([]uint16{mask}); err != nil {
+			t.Fatal(err)
+		}
+		if err := e.SetStepVoters(true); err != nil {
+			t.Fatal(err)
+		}
+		last, _ := st.LastIndex()
+		lt, _ := st.Term(last)
+		if err := e.LoadNode([]uint64{rn.Status().Term}, []uint32{0}, []uint32{0}, []uint64{last}, []uint64{lt}); err != nil {
+			t.Fatal(err)
+		}
+		check := func(what string) {
+			s := rn.Status()
+			ns, err := e.ReadNode()
+			if err != nil {
+				t.Fatal(err)
+			}
+			role := map[raft.StateType]uint8{raft.StateFollower: 0, raft.StateCandidate: 1, raft.StateLeader: 2}[s.RaftState]
+			if ns.Term[0] != s.Term || uint64(ns.Vote[0]) != s.Vote || ns.Committed[0] != s.Commit || uint64(ns.Lead[0]) != s.Lead || ns.Role[0] != role {
+				t.Fatalf("members %v after %s: etcd {term %d vote %d commit %d lead %d state %v}, restatement {term %d vote %d commit %d lead %d role %d}",
+					members, what, s.Term, s.Vote, s.Commit, s.Lead, s.RaftState, ns.Term[0], ns.Vote[0], ns.Committed[0], ns.Lead[0], ns.Role[0])
+			}
+		}
+		step := func(m pb.Message, toEtcd bool, what string) {
+			if toEtcd {
+				rn.Step(m)
+				drain()
+			}
+			rec := Msg{Group: 0, Term: m.Term, LogTerm: m.LogTerm, Index: m.Index, Commit: m.Commit, From: uint32(m.From - 1), Type: uint8(m.Type)}
+			if m.Reject {
+				rec.Reject = 1
+			}
+			if _, err := e.StepBatch([]Msg{rec}, make([]StepOut, 1)); err != nil {
+				t.Fatal(err)
+			}
+			check(what)
+		}
+		rn.Campaign()
+		drain()
+		if _, err := e.StepBatch([]Msg{{Group: 0, Type: uint8(pb.MsgHup)}}, make([]StepOut, 1)); err != nil {
+			t.Fatal(err)
+		}
+		check("MsgHup") // a one-voter group {self} is leader already: q_g = 1
+		term := rn.Status().Term
+		isMember := func(id uint64) bool { return mask&(1<<(id-1)) != 0 }
+		for id := uint64(2); id <= n; id++ { // a non-member's grant is recorded by the engine and counts nowhere
+			step(pb.Message{Type: pb.MsgVoteResp, From: id, To: 1, Term: term}, isMember(id), "MsgVoteResp")
+		}
+		last, _ = st.LastIndex()
+		for i := 0; i < 200; i++ {
+			id := uint64(2 + rng.Intn(n-1))
+			step(pb.Message{Type: pb.MsgAppResp, From: id, To: 1, Term: term, Index: uint64(rng.Int63n(int64(last) + 1))}, isMember(id), "MsgAppResp")
+		}
+	}
+}

@@ -52,6 +52,18 @@ func (e *Engine) SetMsgFlags(on bool) error {
 	return e.err(C.raftq_step_set_msg_flags(e.h, v))
 }
 
+// SetStepVoters opts the engine in to (or out of) Step over each group's own voters: with voter masks loaded (LoadVoters /
+// ApplyVoterDeltas) StepBatch, StepSubmit*, StepFrames* and ApplyLogDeltas* then run instead of returning ErrState, with
+// quorum, maybeCommit and poll over the group's membership (include/raftq_step.h).  The device-built broadcasts stay refused.
+// A property of the engine, like SetMsgFlags; no batch may be in flight.
+func (e *Engine) SetStepVoters(on bool) error {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	return e.err(C.raftq_step_set_voters(e.h, v))
+}
+
 // StepOut is layout-identical to raftq_step_out_t (64 bytes).
 type StepOut struct {
 	Group, Term, Index, LogTerm, Commit, LastIndex uint64

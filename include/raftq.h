@@ -183,10 +183,14 @@ int raftq_apply_term_deltas(raftq_t* h, const raftq_term_delta_t* d, uint64_t n)
  * such state: a raft with no peers does not exist there).
  * With masks loaded, raftq_step_async / raftq_commit_advance / raftq_vote_tally / raftq_collect_changed / raftq_cycle /
  * raftq_cycle_packed run the masked sweep under every flag but RAFTQ_SWEEP_LDS (RAFTQ_EINVAL: the A/B variant has no masked
- * form).  Not built, and refused with RAFTQ_ESTATE and a message that says so: a sweep set with a masked member
- * (raftq_set_create; raftq_load_voters / raftq_apply_voter_deltas on a member), and every entry point of raftq_step.h /
- * raftq_wire.h that runs Step's maybeCommit or poll on the device.  A handle with no masks loaded is exactly the handle it
- * always was, kernels included. */
+ * form).  Step (raftq_step.h / raftq_wire.h) runs over each group's own voters on a handle that opted in with
+ * raftq_step_set_voters(h, 1) -- raftq_step_batch, raftq_step_submit / _collect, raftq_step_submit_packed, raftq_step_submit_wire,
+ * raftq_step_frames / _frames_packed, raftq_apply_log_deltas / _nowait; raftq_step.h restates these rules for quorum(),
+ * maybeCommit and poll -- and refuses a masked handle that did not (RAFTQ_ESTATE, the default).  Not built, and refused with
+ * RAFTQ_ESTATE and a message that says so whatever that switch says: a sweep set with a masked member (raftq_set_create;
+ * raftq_load_voters / raftq_apply_voter_deltas on a member), and the calls that build a broadcast on the device --
+ * raftq_step_frames_respond, raftq_propose_frames, raftq_tick_frames, raftq_tick_elect_frames: their frames go to N - 1 slots,
+ * not to a membership.  A handle with no masks loaded is exactly the handle it always was, kernels included. */
 typedef struct raftq_voter_delta {
   uint64_t group;
   uint16_t voters; /* the group's new mask */

@@ -48,9 +48,10 @@
  * replayWAL (raft.go:122-134) from such bytes.
  *
  * Not built (same as raftq_step.h): snapshots / log compaction, conf changes
- * through Step and the node (the quorum arithmetic over a group's own members
- * exists in the sweep: raftq.h "per-group voter sets"; a node never loads
- * masks, every slot votes), joint consensus, the inflight window.  The log lives in host memory, like the reference's
+ * through the node (the quorum arithmetic over a group's own members exists in
+ * the sweep, raftq.h "per-group voter sets", and in Step for a handle that
+ * opted in, raftq_step_set_voters; a node never loads masks, every slot votes,
+ * and its device-built broadcasts go to N - 1 slots), joint consensus, the inflight window.  The log lives in host memory, like the reference's
  * raft.MemoryStorage (raft.go:70).
  *
  * Thread-safety: propose / deliver / tick / recv / poll / status from any

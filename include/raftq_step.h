@@ -69,6 +69,37 @@ typedef struct raftq_msg {
  * unconditionally: stale staging bytes could be read as "this MsgApp carries N entries".) */
 int raftq_step_set_msg_flags(raftq_t* h, int on);
 
+/* Step over each group's own voters (raftq.h "per-group voter sets": raftq_load_voters / raftq_apply_voter_deltas).
+ * 0 (default): a handle with voter masks loaded is refused by every Step-family call, as before.
+ * 1: those calls run over each group's own voters.  No batch in flight (RAFTQ_ESTATE); on other than 0 / 1: RAFTQ_EINVAL.
+ *
+ * The calls the switch opens: raftq_step_batch, raftq_step_submit / _collect, raftq_step_submit_packed, raftq_step_submit_wire,
+ * raftq_step_frames / raftq_step_frames_packed (raftq_wire.h), raftq_apply_log_deltas / _nowait.  With on = 1 and no masks
+ * loaded the handle launches exactly the kernels it launches otherwise.  The switch is a property of the handle, like the
+ * message flags: raftq_clone_state does not copy it and raftq_load_voters(h, NULL) does not clear it.
+ *
+ * The rules with masks loaded are the sweep's, restated for Step (CHOICE marks what upstream has no counterpart for: its
+ * `prs` map IS the membership, so there a non-member simply has no entry):
+ *   quorum()       q_g = popcount(voters[g]) / 2 + 1.
+ *   maybeCommit    the largest index held by >= q_g VOTERS, then the compact current-term gate as always.  An empty mask
+ *                  gives candidate 0: nothing commits (CHOICE).  A one-voter group whose voter is the leader commits on its
+ *                  own append: raftq_apply_log_deltas on a leader, and becomeLeader's empty entry.
+ *   poll           every sender's first response is recorded as always; granted / recorded count voters only.
+ *   win and loss   keep upstream's EQUALITY (`switch r.q()`): granted == q_g wins, recorded - granted == q_g loses.  A
+ *                  mask that shrinks in the middle of an election can step over the equal count; that is upstream's
+ *                  behaviour (a conf change applied mid-election) and the election timer's to repair.
+ *   non-voters     their words are stored and read as always (CHOICE): an ack from a non-voter moves its Match and sets
+ *                  RAFTQ_OUTF_UPDATED, a MsgVote from a non-voter is answered by the usual rule.
+ *   reset()        writes all N slots as always -- self = lastIndex, the others 0 -- whether or not self is a voter.
+ *   MsgHup         on a group in which self does not vote campaigns (CHOICE: promotable() is not modelled, Tick does not
+ *                  read masks): the own grant is recorded but not counted, so the result is RAFTQ_OUT_CAMPAIGN.
+ *
+ * What stays refused (RAFTQ_ESTATE, "voter masks" in the text) whatever the switch says: raftq_step_frames_respond,
+ * raftq_propose_frames, raftq_tick_frames, raftq_tick_elect_frames -- their broadcasts go to N - 1 slots, not to a
+ * membership, and the proposal path relies on "maybeCommit cannot move with more than one peer", which a one-voter group
+ * breaks.  Sweep sets with a masked member and raftq_node (which never loads masks) are as before. */
+int raftq_step_set_voters(raftq_t* h, int on);
+
 /* raftq_msg_t._pad[1] once the handle opted in.  RAFTQ_MSGF_ENTRIES on a MsgApp: the caller says what the message carries -- the low 32 bits of
  * _resv = its number of entries, reject_hint (a field MsgApp does not use) = the Term of the last one (unused with no
  * entries).  Step then runs raftLog.maybeAppend itself whenever the message appends at the TAIL of the log (m.Index ==

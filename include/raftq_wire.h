@@ -341,7 +341,10 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
  *                 out, frame_off or peer_off not page-locked and 16-byte aligned; N < 2; an unknown flag;
  *                 beat_cap * (N - 1) >= 2^31, or beat_cap * (N - 1) * RAFTQ_RESPOND_FRAME_MAX beyond 2^31 bytes
  *   RAFTQ_ESTATE  a Step batch in flight; no node state on the handle (neither raftq_set_self nor raftq_load_node was ever
- *                 called); voter masks loaded (the round goes to every slot, not to the group's own membership)
+ *                 called); voter masks loaded (the round goes to every slot, not to the group's own membership --
+ *                 whatever raftq_step_set_voters says: that switch opens raftq_step_submit_wire, raftq_step_frames and
+ *                 raftq_step_frames_packed to a masked handle, not raftq_step_frames_respond, raftq_propose_frames,
+ *                 raftq_tick_frames or raftq_tick_elect_frames)
  * Every allocation is made before the tick kernel is enqueued (the rule raftq_tick_collect_lists follows). */
 int raftq_tick_frames(raftq_t* h, unsigned flags, uint64_t hup_cap, uint64_t beat_cap, uint64_t* n_hup, uint64_t* n_beat,
                       void* out, uint64_t cap, uint64_t* frame_off /*[beat_cap*(N-1)+1] | NULL*/, uint64_t* peer_off /*[N+1]*/,

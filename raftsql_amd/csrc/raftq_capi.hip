@@ -676,8 +676,13 @@ static int voters_not_in_set(raftq_t* h, const char* who) {
   return fail(h, RAFTQ_ESTATE, std::string(who) + ": the handle is a member of a sweep set, whose dispatches count every slot "
                                                   "(voter masks on set members are out of scope)");
 }
-int raftq_detail::refuse_voters(raftq_t* h, const char* who) {
+int raftq_detail::refuse_voters(raftq_t* h, const char* who, bool step_family) {
   if (!h || !h->voters) return RAFTQ_OK;
+  if (h->step_voters) {
+    if (step_family) return RAFTQ_OK;
+    return fail(h, RAFTQ_ESTATE, std::string(who) + ": the handle has voter masks loaded; the broadcasts built on the device go to N - 1 slots, "
+                                                    "not to a group's membership (out of scope, whatever raftq_step_set_voters says)");
+  }
   return fail(h, RAFTQ_ESTATE, std::string(who) + ": the handle has voter masks loaded; Step's maybeCommit / poll on the device "
                                                   "count every slot (out of scope: raftq_load_voters(h, NULL) first)");
 }

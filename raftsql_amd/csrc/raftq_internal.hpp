@@ -112,6 +112,8 @@ struct raftq {
   unsigned int* step_stall = nullptr;  // device word: a batch needs the sorted path; later batches wait for the replay
   uint8_t step_compact = 0;        // result records: 0 = 64 bytes, 1 = 40, 2 = 32 (raftq_step_set_compact)
   bool step_msg_flags = false;     // raftq_msg_t._pad[1] / _resv carry RAFTQ_MSGF_* (raftq_step_set_msg_flags); padding otherwise
+  bool step_voters = false;        // raftq_step_set_voters: with masks loaded the Step family runs the *_voters_kernel twins (a property of
+                                   // the handle: raftq_clone_state and raftq_load_voters(h, NULL) leave it alone)
   int step_walk_mode = 1;          // 1 = lists (default), 0 = always the sorted walk (RAFTQ_STEP_WALK=sort)
   uint32_t step_stalls_in_a_row = 0, step_sorted_left = 0;  // back-off from the list walk under hot-group traffic
   uint64_t step_replays = 0;       // batches that went through the sorted path after a stall
@@ -248,8 +250,10 @@ int node_arrays_of(raftq_t* h, raftqk::NodeArrays* out);
 int fail(raftq_t* h, int code, const std::string& msg);
 int use_device(raftq_t* h);
 int use_device_idle(raftq_t* h, const char* who);  // + no Step batch in flight (RAFTQ_ESTATE otherwise)
-// Step's maybeCommit / poll on the device count every slot: RAFTQ_ESTATE for a handle with voter masks loaded (include/raftq.h)
-int refuse_voters(raftq_t* h, const char* who);
+// RAFTQ_ESTATE for a handle with voter masks loaded.  step_family (raftq_step_batch / _submit* / _frames / _frames_packed,
+// raftq_apply_log_deltas*): let through once the handle opted in (raftq_step_set_voters) -- those calls then run over each group's
+// own voters.  Everything else (the device-built broadcasts: their frames go to N - 1 slots, not to a membership) is always refused.
+int refuse_voters(raftq_t* h, const char* who, bool step_family = false);
 int self_max_check(raftq_t* h);                 // the self-max word re-derived from the rows for h->self_peer (enqueued)
 int ensure_staging(raftq_t* h, size_t bytes);   // pinned, device-mapped staging (term deltas, campaign lists, log deltas)
 int ensure_ingest(raftq_t* h, size_t bytes);    // the ack buffer of the batching turn: device memory behind a large BAR, else pinned

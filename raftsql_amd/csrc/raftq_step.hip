@@ -349,6 +349,13 @@ int raftq_step_set_msg_flags(raftq_t* h, int on) {
   return RAFTQ_OK;
 }
 
+int raftq_step_set_voters(raftq_t* h, int on) {
+  if (int rc = raftq_detail::use_device_idle(h, "raftq_step_set_voters")) return rc;
+  if (on != 0 && on != 1) return fail(h, RAFTQ_EINVAL, "raftq_step_set_voters: 0 (a masked handle is refused) or 1 (Step over each group's own voters)");
+  h->step_voters = on == 1;
+  return RAFTQ_OK;
+}
+
 int raftq_step_set_compact(raftq_t* h, int on) {
   if (int rc = raftq_detail::use_device_idle(h, "raftq_step_set_compact")) return rc;
   if (on < 0 || on > 2) return fail(h, RAFTQ_EINVAL, "raftq_step_set_compact: 0 (64-byte records), 1 (40-byte) or 2 (32-byte)");
@@ -374,6 +381,9 @@ struct WireSrc {
   const raftq_detail::PackedDst* packed = nullptr;  // raftq_step_frames_packed: msgs_h is the narrow array
 };
 
+// raftq_step_set_voters on a handle with masks loaded: the walks and the tail reports launch the *_voters_kernel twins
+static bool masked_step(const raftq_t* h) { return h->voters != nullptr && h->step_voters; }
+
 // key -> stable radix sort -> walk, on the handle's stream (the path that takes runs of any length)
 static int enqueue_sorted_walk(raftq_t* h, const Scratch& s, uint64_t n, int end_bit, uint8_t recs, void* outs) {
   if (int rc = ensure_mirror(h)) return rc;
@@ -384,9 +394,14 @@ static int enqueue_sorted_walk(raftq_t* h, const Scratch& s, uint64_t n, int end
   HIPCHK(h, hipGetLastError());
   int in_b = 0;  // which pair of buffers the sorted (group, batch position) pairs end up in
   HIPCHK(h, raftqk::radix_sort_pairs(h->stream, s.sort_scratch, s.keys_in, s.order_in, s.keys_out, s.order_out, n, end_bit, &in_b));
-  hipLaunchKernelGGL(step_kernel, grid, dim3(kBlock), 0, h->stream, node_arrays(h, recs), (const MsgRec*)s.msgs,
-                     (const uint64_t*)(in_b ? s.keys_out : s.keys_in), (const uint32_t*)(in_b ? s.order_out : s.order_in), outs,
-                     h->step_compact, n, s.n_heads, (const unsigned int*)bad);
+  if (masked_step(h))
+    hipLaunchKernelGGL(step_voters_kernel, grid, dim3(kBlock), 0, h->stream, node_arrays(h, recs), (const MsgRec*)s.msgs,
+                       (const uint64_t*)(in_b ? s.keys_out : s.keys_in), (const uint32_t*)(in_b ? s.order_out : s.order_in), outs,
+                       h->step_compact, n, s.n_heads, (const unsigned int*)bad, (const uint16_t*)h->voters);
+  else
+    hipLaunchKernelGGL(step_kernel, grid, dim3(kBlock), 0, h->stream, node_arrays(h, recs), (const MsgRec*)s.msgs,
+                       (const uint64_t*)(in_b ? s.keys_out : s.keys_in), (const uint32_t*)(in_b ? s.order_out : s.order_in), outs,
+                       h->step_compact, n, s.n_heads, (const unsigned int*)bad);
   HIPCHK(h, hipGetLastError());
   return RAFTQ_OK;
 }
@@ -410,9 +425,16 @@ static int enqueue_list_walk(raftq_t* h, const Scratch& s, uint64_t n, uint8_t r
   }
   hipLaunchKernelGGL(step_link_kernel, dim3(blocks + in_link.blocks), dim3(kBlock), 0, h->stream, (const MsgRec*)s.msgs, n, h->G,
                      h->N, h->step_msg_flags, recs, (NodeRec*)h->node_rec, s.next, bad, h->step_stall, s.outs, h->step_compact, in_link);
-  hipLaunchKernelGGL(step_lists_kernel, dim3(blocks + in_walk.blocks), dim3(kBlock), 0, h->stream, node_arrays(h, recs),
-                     (const MsgRec*)s.msgs, s.outs, h->step_compact, n, h->G, (const uint32_t*)s.next, s.n_heads,
-                     skipped, (const unsigned int*)bad, (const unsigned int*)h->step_stall, in_walk);
+  if (masked_step(h)) {
+    HIPCHK(h, hipGetLastError());  // (the link kernel's, before the twin's launch can hide it)
+    hipLaunchKernelGGL(step_lists_voters_kernel, dim3(blocks + in_walk.blocks), dim3(kBlock), 0, h->stream, node_arrays(h, recs),
+                       (const MsgRec*)s.msgs, s.outs, h->step_compact, n, h->G, (const uint32_t*)s.next, s.n_heads,
+                       skipped, (const unsigned int*)bad, (const unsigned int*)h->step_stall, in_walk, (const uint16_t*)h->voters);
+  } else {
+    hipLaunchKernelGGL(step_lists_kernel, dim3(blocks + in_walk.blocks), dim3(kBlock), 0, h->stream, node_arrays(h, recs),
+                       (const MsgRec*)s.msgs, s.outs, h->step_compact, n, h->G, (const uint32_t*)s.next, s.n_heads,
+                       skipped, (const unsigned int*)bad, (const unsigned int*)h->step_stall, in_walk);
+  }
   HIPCHK(h, hipGetLastError());
   if (carry) {
     HIPCHK(h, hipEventRecord(carry->ev_out, h->stream));
@@ -436,7 +458,7 @@ static int submit_impl(raftq_t* h, const void* msgs, uint64_t n, const WireSrc* 
                        size_t rec_bytes = sizeof(raftq_msg_t)) {
   const bool packed = rec_bytes != sizeof(raftq_msg_t);
   if (int rc = use_device(h)) return rc;
-  if (int rc = raftq_detail::refuse_voters(h, who)) return rc;
+  if (int rc = raftq_detail::refuse_voters(h, who, !h->resp_on)) return rc;  // (raftq_step_frames_respond broadcasts: never let through)
   if (n == 0 || (!wire && !msgs)) return fail(h, RAFTQ_EINVAL, std::string(who) + ": empty batch");
   if (n > 0x7ffffffeull) return fail(h, RAFTQ_EINVAL, std::string(who) + ": batch too large (2^31 - 2 messages at most)");
   if (wire && ((!wire->stream && wire->nbytes) || !wire->frame_off))
@@ -953,7 +975,7 @@ int raftq_step_frames_respond(raftq_t* h, const void* stream, uint64_t nbytes, c
 // wait = false (raftq_apply_log_deltas_nowait): the same kernels from a staging area of their own, enqueued and left
 static int log_deltas_impl(raftq_t* h, const raftq_log_delta_t* d, uint64_t n, uint64_t* committed_out, bool wait) {
   if (int rc = raftq_detail::use_device_idle(h, wait ? "raftq_apply_log_deltas" : "raftq_apply_log_deltas_nowait")) return rc;
-  if (int rc = raftq_detail::refuse_voters(h, wait ? "raftq_apply_log_deltas" : "raftq_apply_log_deltas_nowait")) return rc;
+  if (int rc = raftq_detail::refuse_voters(h, wait ? "raftq_apply_log_deltas" : "raftq_apply_log_deltas_nowait", true)) return rc;
   if (n == 0) return RAFTQ_OK;
   if (!d) return fail(h, RAFTQ_EINVAL, "raftq_apply_log_deltas: null argument");
   for (uint64_t i = 0; i < n; ++i)
@@ -1016,9 +1038,14 @@ static int log_deltas_impl(raftq_t* h, const raftq_log_delta_t* d, uint64_t n, u
   uint64_t* out_h = (uint64_t*)((uint8_t*)stage_h + off_out);
   uint64_t* out_d = (uint64_t*)((uint8_t*)stage_d + off_out);
   auto launch = [&](uint64_t start, uint64_t m) {
-    hipLaunchKernelGGL(log_deltas_kernel, dim3((unsigned)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream,
-                       node_arrays(h), (const LogDeltaRec*)stage_d + start, m,
-                       committed_out ? out_d + start : (uint64_t*)nullptr);
+    if (masked_step(h))
+      hipLaunchKernelGGL(log_deltas_voters_kernel, dim3((unsigned)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream,
+                         node_arrays(h), (const LogDeltaRec*)stage_d + start, m,
+                         committed_out ? out_d + start : (uint64_t*)nullptr, (const uint16_t*)h->voters);
+    else
+      hipLaunchKernelGGL(log_deltas_kernel, dim3((unsigned)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream,
+                         node_arrays(h), (const LogDeltaRec*)stage_d + start, m,
+                         committed_out ? out_d + start : (uint64_t*)nullptr);
   };
   if (n_rounds == 1) {
     std::memcpy(dst, d, (size_t)n * sizeof(raftq_log_delta_t));

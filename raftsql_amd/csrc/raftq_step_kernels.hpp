@@ -241,7 +241,15 @@ static __global__ __launch_bounds__(kBlock) void step_keys_kernel(const MsgRec* 
 constexpr uint32_t kMaxRun = 32;
 constexpr uint32_t kNil = 0xffffffffu;
 
-struct Node {
+// MASKED (raftq_step_set_voters on a handle with voter masks loaded): quorum(), maybe_commit() and poll() run over the group's
+// own voters -- include/raftq.h "per-group voter sets", the sweep's rules (sweep_voters_kernel) restated for Step.  The mask is
+// ONE register, read from the dense `voters` array (authoritative; NodeRec has no room for nine bits and a copy would be one
+// more thing to keep fresh) beside the record's loads: its address depends on g alone, so it adds a 32-byte sector per touched
+// group and no dependent latency.  Everything else -- what is stored, reset()'s N slots, whose words are recorded -- is the
+// unmasked form's: a non-voter's Match and vote are kept as always and merely do not count.
+// `Node` stays the name of the unmasked form (elect_build_kernel, propose_apply_kernel, the respond path).
+template <bool MASKED>
+struct NodeT {
   const NodeArrays& a;
   uint64_t g;
   uint64_t term, last_index, last_term, committed, first_idx;
@@ -259,8 +267,10 @@ struct Node {
   uint64_t committed0, first_idx0;
   uint8_t role0;
   bool vw_known = false, vw_dirty = false, elapsed_reset = false;
+  uint32_t vmask = 0;  // MASKED only: voters[g], bit p = slot p votes in this group
 
-  __device__ Node(const NodeArrays& arr, uint64_t group) : a(arr), g(group) {
+  __device__ NodeT(const NodeArrays& arr, uint64_t group, const uint16_t* voters = nullptr) : a(arr), g(group) {
+    if constexpr (MASKED) vmask = voters[g];
     const NodeRec r = a.rec[g];  // one line: eight 16-byte loads
     term = r.term; last_index = r.last_index; last_term = r.last_term;
     vote = r.vote; lead = r.lead;
@@ -335,7 +345,17 @@ struct Node {
     for (uint32_t k = 0; k < (uint32_t)kMaxPeers; ++k) mt[k] = k == p ? v : mt[k];
     mt_dirty |= 1u << p;
   }
-  __device__ uint32_t quorum() const { return a.n_peers / 2 + 1; }
+  // CHOICE where upstream has no counterpart (its prs map IS the membership): q_g = popcount(voters[g]) / 2 + 1; an empty mask
+  // gives 1, which nothing reaches (no candidate, no counted grant)
+  __device__ uint32_t quorum() const {
+    if constexpr (MASKED) return ((uint32_t)__popc(vmask) >> 1) + 1u;
+    else return a.n_peers / 2 + 1;
+  }
+  // slot p counts: it is a peer and, in the masked form, a voter of this group (a mask names no slot >= N: raftq_load_voters)
+  __device__ bool counts(uint32_t p, uint32_t n) const {
+    if constexpr (MASKED) return ((vmask >> p) & 1u) != 0;
+    else return p < n;
+  }
 
   // raft.reset(term)
   __device__ void reset(uint64_t t) {
@@ -364,19 +384,20 @@ struct Node {
     set_first_idx(0);
   }
   // raft.maybeCommit + raftLog.maybeCommit: the largest index held by >= q peers (counting form),
-  // then the compact current-term gate
+  // then the compact current-term gate.  MASKED: by >= q_g VOTERS -- a non-voter neither counts nor is a candidate, so an
+  // empty mask commits nothing and a one-voter group whose voter is the leader commits on its own append
   __device__ bool maybe_commit() {
     uint64_t m[kMaxPeers];
     const uint32_t n = a.n_peers, q = quorum();
 #pragma unroll
-    for (uint32_t p = 0; p < kMaxPeers; ++p) m[p] = p < n ? mt[p] : 0;
+    for (uint32_t p = 0; p < kMaxPeers; ++p) m[p] = counts(p, n) ? mt[p] : 0;
     uint64_t mci = 0;
 #pragma unroll
     for (uint32_t c = 0; c < kMaxPeers; ++c) {
       uint32_t ge = 0;
 #pragma unroll
-      for (uint32_t p = 0; p < kMaxPeers; ++p) ge += (p < n && m[p] >= m[c]) ? 1u : 0u;
-      if (c < n && ge >= q && m[c] > mci) mci = m[c];
+      for (uint32_t p = 0; p < kMaxPeers; ++p) ge += (counts(p, n) && m[p] >= m[c]) ? 1u : 0u;
+      if (counts(c, n) && ge >= q && m[c] > mci) mci = m[c];
     }
     if (mci > committed) {  // (the gate's word is only read when there is something to gate)
       const uint64_t fi = get_first_idx();
@@ -398,7 +419,8 @@ struct Node {
     set_match(a.self, last_index);
     (void)maybe_commit();
   }
-  // raft.poll: the first response of a peer wins; returns {granted, recorded}
+  // raft.poll: the first response of a peer wins; returns {granted, recorded}.  MASKED: every sender's first response is
+  // recorded as always; the two counts are over the voters' fields only (poll_word_voters' form)
   __device__ void poll(uint32_t from, bool granted, uint32_t& n_granted, uint32_t& n_recorded) {
     uint32_t w = get_votes();
     const uint32_t cur = (w >> (2 * from)) & 3u;
@@ -406,7 +428,9 @@ struct Node {
       w = (w & ~(3u << (2 * from))) | ((granted ? 1u : 2u) << (2 * from));
       set_votes(w);
     }
-    const uint32_t low = 0x55555555u & ((1u << (2 * a.n_peers)) - 1u);
+    uint32_t low;
+    if constexpr (MASKED) low = spread_even(vmask);
+    else low = 0x55555555u & ((1u << (2 * a.n_peers)) - 1u);
     const uint32_t g1 = w & ~(w >> 1) & low, r1 = (w >> 1) & ~w & low;
     n_granted = __popc(g1);
     n_recorded = __popc(g1 | r1);
@@ -538,6 +562,8 @@ struct Node {
         } else if (m.type == kMsgVoteResp) {
           uint32_t gr, rec;
           poll(m.from, !m.reject, gr, rec);
+          // upstream's equality (`switch r.q()`), MASKED too: a mask that shrinks in the middle of an election can step over the
+          // equal count -- upstream's behaviour, and the election timer's to repair
           if (gr == q) {
             become_leader();
             o.type = kOutBecameLeader; o.index = last_index; o.log_term = last_term;
@@ -569,34 +595,7 @@ struct Node {
     if (role0 != kFollower && role == kFollower) o.flags |= kFlagSteppedDown;
   }
 };
-
-static __global__ __launch_bounds__(kBlock) void step_kernel(NodeArrays a, const MsgRec* __restrict__ msgs,
-                                                      const uint64_t* __restrict__ keys_sorted,
-                                                      const uint32_t* __restrict__ order, void* __restrict__ out,
-                                                      uint8_t compact, uint64_t n, unsigned long long* n_heads,
-                                                      const unsigned int* bad) {
-  if (*bad) return;  // a malformed record somewhere in the batch: nothing is applied
-  const uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-  bool head = false;
-  uint64_t g = 0;
-  if (k < n) {
-    g = keys_sorted[k];
-    head = (k == 0 || keys_sorted[k - 1] != g) && g < a.n_groups;  // (key n_groups: the RAFTQ_MSGF_SKIP records, answered by step_keys_kernel)
-  }
-  const uint64_t hb = __ballot(head);
-  if ((threadIdx.x & 63) == 0 && hb) atomicAdd(n_heads, (unsigned long long)__popcll(hb));
-  if (!head) return;
-  Node node(a, g);
-  for (uint64_t j = k; j < n && keys_sorted[j] == g; ++j) {
-    const uint32_t i = order[j];
-    const MsgRec m = msgs[i];
-    StepOutRec o;
-    node.step(m, o);
-    node.respond(m, o, i);
-    put_result(out, i, o, compact);
-  }
-  node.store();
-}
+using Node = NodeT<false>;
 
 // ---- (2b, 3b) the same walk WITHOUT the sort.  Inbound traffic rarely brings more than a few messages
 // of one group in one batch, so grouping by a full stable sort (4-12 launches, 40-60 us of a 95 us kernel
@@ -658,70 +657,26 @@ static __global__ __launch_bounds__(kBlock) void step_link_kernel(const MsgRec* 
   if (__ballot(too_long) != 0 && (threadIdx.x & 63) == 0) atomicOr(stall, 1u);
 }
 
-static __global__ __launch_bounds__(kBlock) void step_lists_kernel(NodeArrays a, const MsgRec* __restrict__ msgs,
-                                                                   void* __restrict__ out, uint8_t compact, uint64_t n,
-                                                                   uint64_t n_groups,
-                                                                   const uint32_t* __restrict__ next,
-                                                                   unsigned long long* n_heads, unsigned int* tail_skipped,
-                                                                   const unsigned int* bad, const unsigned int* stall, CopyRide ride) {
-  if (blockIdx.x < ride.blocks) {  // the rest of the previous batch's results (see CopyRide)
-    copy_ride(ride);
-    return;
-  }
-  const uint64_t i = (uint64_t)(blockIdx.x - ride.blocks) * kBlock + threadIdx.x;
-  const bool stalled = *stall != 0;  // this batch, or one before it that has not been replayed yet, needs the sorted path
-  if (stalled || *bad) {             // (*bad: a malformed record somewhere in the batch) -- nothing is applied;
-    if (stalled && i == 0) *tail_skipped = 1u;
-    if (i < n && classify(msgs[i], n_groups, a.n_peers, a.msg_flags, a.recs) == kTake) {  // every message empties its group's list words (idempotent)
-      NodeRec* r = a.rec + msgs[i].group;
-      r->lst_head = kNil;
-      r->lst_cnt = 0;
-      r->lst_min = kNil;
-    }
-    return;
-  }
-  uint64_t g = 0;
-  bool owner = false;
-  if (i < n) {
-    g = msgs[i].group;
-    // (a RAFTQ_MSGF_SKIP record belongs to no group -- its group field may hold anything -- and was answered by the link kernel)
-    owner = !(a.msg_flags && (msgs[i].pad[1] & kMsgfSkip)) && a.rec[g].lst_min == (uint32_t)i;
-  }
-  const uint64_t ob = __ballot(owner);
-  if ((threadIdx.x & 63) == 0 && ob) atomicAdd(n_heads, (unsigned long long)__popcll(ob));
-  if (!owner) return;
-  Node node(a, g);  // (the record's line is in the L1 already: the owner test read it)
-  const uint32_t c = node.lst_cnt;
-  if (c == 1) {
-    StepOutRec o;
-    const MsgRec m = msgs[i];
-    node.step(m, o);
-    node.respond(m, o, i);
-    put_result(out, i, o, compact);
-  } else {
-    uint32_t pos[kMaxRun];
-    uint32_t p = node.lst_head;
-    for (uint32_t k = 0; k < c; ++k) {  // gather, inserting in ascending order of batch position
-      uint32_t j = k;
-      while (j > 0 && pos[j - 1] > p) {
-        pos[j] = pos[j - 1];
-        --j;
-      }
-      pos[j] = p;
-      p = next[p];
-    }
-    for (uint32_t k = 0; k < c; ++k) {
-      const MsgRec m = msgs[pos[k]];
-      StepOutRec o;
-      node.step(m, o);
-      node.respond(m, o, pos[k]);
-      put_result(out, pos[k], o, compact);
-    }
-  }
-  // the record goes back with the group's list empty for the next batch.  Other lanes of this group only compare lst_min
-  // with their own position to learn that they are not the owner: kNil tells them the same.
-  node.store();
-}
+// ---- (3, 3b) the walks and the tail reports, each under its name over every slot and as *_voters_kernel over each group's own
+// voters (raftq_step_set_voters): one text, expanded twice
+#define RAFTQ_WALK_KERNEL(stem) stem##_kernel
+#define RAFTQ_WALK_MASKED false
+#define RAFTQ_WALK_PARAM
+#define RAFTQ_WALK_VOTERS
+#include "raftq_step_walk_kernels.inc"
+#undef RAFTQ_WALK_KERNEL
+#undef RAFTQ_WALK_MASKED
+#undef RAFTQ_WALK_PARAM
+#undef RAFTQ_WALK_VOTERS
+#define RAFTQ_WALK_KERNEL(stem) stem##_voters_kernel
+#define RAFTQ_WALK_MASKED true
+#define RAFTQ_WALK_PARAM , const uint16_t* __restrict__ voters
+#define RAFTQ_WALK_VOTERS , voters
+#include "raftq_step_walk_kernels.inc"
+#undef RAFTQ_WALK_KERNEL
+#undef RAFTQ_WALK_MASKED
+#undef RAFTQ_WALK_PARAM
+#undef RAFTQ_WALK_VOTERS
 
 // ---- the record array's bulk paths (raftq_load_node / raftq_read_node: set-up and test traffic, not the hot path) ----------
 static __global__ __launch_bounds__(kBlock) void node_init_kernel(NodeRec* rec, uint64_t n) {
@@ -779,26 +734,6 @@ static __global__ __launch_bounds__(kBlock) void step_d2h_kernel(const u64x2* __
     __builtin_nontemporal_store(v, dst + i);
     if (zero_tail && i == n_quads - 1) const_cast<u64x2*>(src)[i] = u64x2{0, 0};
   }
-}
-
-// the log owner's tail reports; records are unique per group within a launch (the host splits
-// repeated groups into successive launches)
-static __global__ __launch_bounds__(kBlock) void log_deltas_kernel(NodeArrays a, const LogDeltaRec* __restrict__ d,
-                                                                   uint64_t n, uint64_t* __restrict__ committed_out) {
-  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  const LogDeltaRec r = d[i];
-  Node node(a, r.group);
-  node.last_index = r.last_index;
-  node.last_term = r.last_term;
-  if (node.role == kLeader) {
-    if (node.match(a.self) < node.last_index) node.set_match(a.self, node.last_index);
-    (void)node.maybe_commit();
-  } else if (r.commit_to != 0) {
-    node.commit_to(r.commit_to);
-  }
-  node.store(false);
-  if (committed_out) committed_out[i] = node.committed;
 }
 
 }  // namespace raftqk

@@ -137,6 +137,11 @@ class NodeEngine(QuorumEngine):
         self._chk(self._lib.raftq_step_set_compact(self._h, int(on)))
         self.compact = int(on)
 
+    def set_step_voters(self, on=True) -> None:
+        """raftq_step_set_voters: with voter masks loaded (load_voters / apply_voter_deltas) the Step-family calls run over each
+        group's own voters instead of being refused; a property of the handle (no batch may be in flight)"""
+        self._chk(self._lib.raftq_step_set_voters(self._h, int(on)))
+
     def load_node(self, term=None, vote=None, lead=None, last_index=None, last_term=None) -> None:
         def arr(x, dt):
             if x is None:
