@@ -34,6 +34,19 @@ func (e *Engine) SelfMax() (int, error) {
 	return int(slot), nil
 }
 
+// Narrow reports whether the device holds a valid 32-bit mirror of the match rows (a per-group anchor and one offset per
+// row); a commit sweep of 3 or more peers then reads the mirror instead of the rows.
+func (e *Engine) Narrow() (bool, error) {
+	var valid C.int32_t
+	if err := e.err(C.raftq_narrow(e.h, &valid)); err != nil {
+		return false, err
+	}
+	return valid != 0, nil
+}
+
+// NarrowRebuild runs the mirror's build pass on demand.
+func (e *Engine) NarrowRebuild() error { return e.err(C.raftq_narrow_rebuild(e.h)) }
+
 // SetStream installs a caller-owned hipStream_t; Stream returns the one in use.
 func (e *Engine) SetStream(stream unsafe.Pointer) error { return e.err(C.raftq_set_stream(e.h, stream)) }
 func (e *Engine) Stream() unsafe.Pointer                { return C.raftq_get_stream(e.h) }

@@ -230,6 +230,15 @@ int raftq_read_match(raftq_t* h, uint64_t* match_out /*[N][G]*/);
 /* the peer slot whose match row the device knows to be the largest of every
  * group (the sweep then does not read that row), or -1 when none is known. */
 int raftq_self_max(raftq_t* h, int32_t* slot_out);
+/* The narrow mirror: a per-group anchor (u64) and one 32-bit offset per match row, match[p][g] == anchor[g] + offset[p][g]
+ * for every row of every group.  While the device knows that to hold, a commit sweep of 3 or more peers reads the mirror
+ * (8 + 4N bytes a group) instead of the rows (8N).  raftq_load_match builds it; the batching turn's ingest keeps it true;
+ * Step, a voter delta that resets a slot and an ack 2^32 or more above its group's anchor end it until the next build.
+ * Costs 8 + 4N bytes a group; RAFTQ_NARROW=0 in the environment at raftq_create keeps a handle from ever having one.
+ * raftq_narrow: *valid_out = 1 while the mirror holds, 0 otherwise.  raftq_narrow_rebuild: the build pass on demand (the
+ * word stays 0 where a group's values spread over 2^32 or more, no memory can be had, or the handle was created without). */
+int raftq_narrow(raftq_t* h, int32_t* valid_out);
+int raftq_narrow_rebuild(raftq_t* h);
 int raftq_read_votes(raftq_t* h, uint8_t* votes_out /*[N][G]*/);
 /* compacted list of the groups the last RAFTQ_SWEEP_CHANGED sweep advanced,
  * in ascending group order; returns the count in *n (<= cap entries stored). */

@@ -258,6 +258,34 @@ int raftq_detail::self_max_check(raftq_t* h) {
   HIPCHK(h, hipGetLastError());
   return RAFTQ_OK;
 }
+// The narrow word's full build (raftq_kernels.hpp): kNarrowValid is stored, then a pass over the rows writes the anchors and
+// the offsets and clears the word if a group's values spread too far.  On the handle's stream, behind whatever wrote the rows;
+// with Step batches in flight only the clear, as above.  The arrays are allocated here, once; a handle that cannot have them
+// (or was created under RAFTQ_NARROW=0) keeps its word 0 and sweeps the rows.
+int raftq_detail::narrow_build(raftq_t* h) {
+  if (int rc = use_device(h)) return rc;
+  if (h->narrow_off) return RAFTQ_OK;
+  if (h->step_collected != h->step_submitted) {
+    HIPCHK(h, hipMemsetAsync(h->narrow_word(), 0, sizeof(uint32_t), h->stream));
+    return RAFTQ_OK;
+  }
+  if (!h->anchor) {
+    const hipError_t e = raftq_buf::alloc_group({{(void**)&h->anchor, h->ld * sizeof(uint64_t)},
+                                                 {(void**)&h->moff, (size_t)h->N * h->ld * sizeof(uint32_t)}},
+                                                h->stream);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();  // no room for a mirror: not an error of the handle's
+      return RAFTQ_OK;
+    }
+    if (h->in_set) h->in_set->tab_stale = true;  // the set's tables hold the members' array pointers
+  }
+  HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)h->narrow_word(), (int)kNarrowValid, 1, h->stream));
+  const uint64_t blocks = std::min<uint64_t>((h->G + kBlock - 1) / kBlock, 4096);
+  hipLaunchKernelGGL(narrow_build_kernel, dim3((unsigned)std::max<uint64_t>(blocks, 1)), dim3(kBlock), 0, h->stream,
+                     (const uint64_t*)h->match, h->ld, h->G, h->N, h->anchor, h->moff, h->narrow_word());
+  HIPCHK(h, hipGetLastError());
+  return RAFTQ_OK;
+}
 int raftq_detail::use_device(raftq_t* h) {
   if (!h) return fail(nullptr, RAFTQ_EINVAL, "null handle");
   HIPCHK(h, hipSetDevice(h->device));
@@ -378,6 +406,11 @@ int raftq_create(int device, uint64_t n_groups, uint32_t n_peers, raftq_t** out)
       rc = fail(h, e == hipErrorOutOfMemory ? RAFTQ_ENOMEM : RAFTQ_EHIP, std::string("device arrays: ") + hipGetErrorString(e));
       break;
     }
+    {  // for A/B runs with one library, and for callers who want the mirror's memory back
+      const char* nr = std::getenv("RAFTQ_NARROW");
+      h->narrow_off = nr && std::strcmp(nr, "0") == 0;
+    }
+    // (the narrow word, self_max[1], stays 0: there is no mirror yet)
     e = hipMemsetD32Async((hipDeviceptr_t)h->self_max, (int)(kSelfMaxValid | 0u), 1, h->stream);
     if (e != hipSuccess) { rc = fail(h, RAFTQ_EHIP, std::string("hipMemsetD32Async: ") + hipGetErrorString(e)); break; }
     e = raftq_buf::alloc_group({{(void**)&h->h_partials, h->max_partials * sizeof(uint4), raftq_buf::Kind::pinned},
@@ -425,7 +458,7 @@ void raftq_destroy(raftq_t* h) {
   raftq_detail::free_wire_state(h);
   // every wait is over: memory may go
   raftq_buf::free_device(h->match, h->committed[0], h->committed[1], h->first_idx, h->votes, h->voters, h->outcome, h->changed_bits,
-                         h->partials, h->offsets, h->self_max, h->claim, h->delta_bad, h->role, h->elapsed, h->action, h->hup_bits,
+                         h->partials, h->offsets, h->self_max, h->anchor, h->moff, h->claim, h->delta_bad, h->role, h->elapsed, h->action, h->hup_bits,
                          h->beat_bits, h->tick_partials, h->tick_offsets2);
   raftq_buf::free_host(h->h_partials, h->h_total);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -462,6 +495,7 @@ int raftq_load_match(raftq_t* h, const uint64_t* match, const uint64_t* committe
     for (uint32_t p = 0; p < h->N; ++p)
       HIPCHK(h, hipMemcpyAsync(h->match + (size_t)p * h->ld, match + (size_t)p * h->G, h->G * 8, hipMemcpyHostToDevice, h->stream));
     if (int rc = raftq_detail::self_max_check(h)) return rc;
+    if (int rc = raftq_detail::narrow_build(h)) return rc;
   }
   dense_changed(h);
   if (committed)
@@ -578,7 +612,7 @@ static int enqueue_ingest(raftq_t* h, const AbiRec* d, uint64_t n, const raftq_v
   if (n) dense_changed(h);  // (match words move under Step's records)
   if (n && trusted)
     hipLaunchKernelGGL((deltas_in_apply_kernel<Rec>), gm, dim3(kBlock), 0, h->stream, (const Rec*)h->ingest.d, n, h->match, h->ld,
-                       h->G, h->N, h->delta_bad, h->d_total + 1, em, h->self_max);
+                       h->G, h->N, h->delta_bad, h->d_total + 1, em, h->self_max, h->narrow_mirror());
   else if (n)
     hipLaunchKernelGGL((deltas_in_kernel<Rec>), gm, dim3(kBlock), 0, h->stream, (const Rec*)h->ingest.d, dev_m, n, h->G, h->N,
                        h->delta_bad, h->d_total + 1, em);
@@ -588,7 +622,7 @@ static int enqueue_ingest(raftq_t* h, const AbiRec* d, uint64_t n, const raftq_v
                        h->d_total + 2, ev);
   if (n && !trusted)
     hipLaunchKernelGGL((apply_deltas_kernel<Rec>), gm, dim3(kBlock), 0, h->stream, h->match, h->ld, (const Rec*)dev_m, n, bad, em,
-                       ev, h->self_max);
+                       ev, h->self_max, h->narrow_mirror());
   if (nv) {
     // trusted match deltas are dropped one by one, never as a batch: their verdict does not gate the votes
     const unsigned long long em_gate = trusted ? kNoEpoch : em;
@@ -747,7 +781,7 @@ int raftq_apply_voter_deltas(raftq_t* h, const raftq_voter_delta_t* d, uint64_t 
   }
   dense_changed(h);  // (match words are zeroed under Step's records)
   hipLaunchKernelGGL(apply_voter_deltas_kernel, dim3((unsigned)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, h->voters, h->match,
-                     h->ld, h->votes, h->N > 8 ? 1 : 0, h->N, (const VoterDeltaRec*)h->stage.d, m, h->self_max);
+                     h->ld, h->votes, h->N > 8 ? 1 : 0, h->N, (const VoterDeltaRec*)h->stage.d, m, h->self_max, h->narrow_word());
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipStreamSynchronize(h->stream));  // the staging area is reused by the next call
   return RAFTQ_OK;
@@ -786,6 +820,9 @@ static SweepArgs sweep_args(const raftq_t* h, int cur, bool want_bits) {
   a.partials = h->partials;
   a.ld = h->ld;
   a.self_max = h->self_max;
+  a.narrow = h->anchor ? h->narrow_word() : nullptr;
+  a.anchor = h->anchor;
+  a.moff = h->moff;
   return a;
 }
 
@@ -937,6 +974,23 @@ int raftq_self_max(raftq_t* h, int32_t* slot) {
   HIPCHK(h, hipMemcpyAsync(&w, h->self_max, sizeof w, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   *slot = (w & kSelfMaxValid) ? (int32_t)(w & 0xffu) : -1;
+  return RAFTQ_OK;
+}
+
+int raftq_narrow(raftq_t* h, int32_t* valid) {
+  if (int rc = use_device_idle(h, "raftq_narrow")) return rc;
+  if (!valid) return fail(h, RAFTQ_EINVAL, "raftq_narrow: null argument");
+  uint32_t w = 0;
+  HIPCHK(h, hipMemcpyAsync(&w, h->narrow_word(), sizeof w, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  *valid = w == kNarrowValid ? 1 : 0;
+  return RAFTQ_OK;
+}
+
+int raftq_narrow_rebuild(raftq_t* h) {
+  if (int rc = use_device_idle(h, "raftq_narrow_rebuild")) return rc;
+  if (int rc = raftq_detail::narrow_build(h)) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
   return RAFTQ_OK;
 }
 
@@ -1858,6 +1912,16 @@ int raftq_set_sweep_async(raftq_set_t* s, unsigned flags) {
     footprint += sweep_footprint(h);
     if (h->cur != cur) cur = -1;
   }
+  if (s->tab_stale) {
+    // A member's mirror arrays came into being: both standing tables name them from now on.  As in raftq_set_create; the call
+    // that allocated them (raftq_load_match, raftq_narrow_rebuild, raftq_clone_state) ended with a wait on this stream, and
+    // no set sweep has been enqueued since, so no kernel is reading the tables.
+    for (int k = 0; k < 2; ++k) {
+      set_fill_table(s, k, s->tab_host);
+      SETCHK(s, hipMemcpy(s->tab[k], s->tab_host.data(), s->tab_host.size() * sizeof(SweepArgs), hipMemcpyHostToDevice));
+    }
+    s->tab_stale = false;
+  }
   const SweepArgs* tab = s->tab[cur < 0 ? 2 : cur];
   if (cur < 0) {  // members disagree on which commit buffer is current: build this launch's table
     set_fill_table(s, -1, s->tab_host);
@@ -2021,6 +2085,21 @@ int raftq_clone_state(raftq_t* dst, raftq_t* src) {
                              dst->stream));
   // the rows are the source's, so is what is known about them (the word names its slot: it holds whatever dst's self is)
   HIPCHK(dst, hipMemcpyAsync(dst->self_max, src->self_max, sizeof(uint32_t), hipMemcpyDeviceToDevice, dst->stream));
+  // ... and the mirror with its word, where the source has one and the destination may: otherwise dst has none (word 0)
+  if (src->anchor && !dst->narrow_off && !dst->anchor) {
+    if (raftq_buf::alloc_group({{(void**)&dst->anchor, ld * sizeof(uint64_t), raftq_buf::Kind::device, nullptr, false},
+                                {(void**)&dst->moff, (size_t)dst->N * ld * sizeof(uint32_t), raftq_buf::Kind::device, nullptr, false}},
+                               dst->stream) != hipSuccess)
+      (void)hipGetLastError();
+    else if (dst->in_set) dst->in_set->tab_stale = true;
+  }
+  if (src->anchor && dst->anchor && !dst->narrow_off) {
+    HIPCHK(dst, hipMemcpyAsync(dst->anchor, src->anchor, ld * sizeof(uint64_t), hipMemcpyDeviceToDevice, dst->stream));
+    HIPCHK(dst, hipMemcpyAsync(dst->moff, src->moff, (size_t)dst->N * ld * sizeof(uint32_t), hipMemcpyDeviceToDevice, dst->stream));
+    HIPCHK(dst, hipMemcpyAsync(dst->narrow_word(), src->narrow_word(), sizeof(uint32_t), hipMemcpyDeviceToDevice, dst->stream));
+  } else {
+    HIPCHK(dst, hipMemsetAsync(dst->narrow_word(), 0, sizeof(uint32_t), dst->stream));
+  }
   if (src->voters) HIPCHK(dst, hipMemcpyAsync(dst->voters, src->voters, ld * sizeof(uint16_t), hipMemcpyDeviceToDevice, dst->stream));
   HIPCHK(dst, hipStreamSynchronize(dst->stream));
   dst->have_terms = src->have_terms;

@@ -65,6 +65,13 @@ struct raftq {
   uint32_t seg_tiles = 0, seg_stride = 0, seg_one = 0;  // seg_one: the count of a contiguous list presented as one segment
   uint64_t flag_mask = ~0ull;  // which bits of the completion word are the epoch the turn's wait compares (segmented: the top half)
   uint32_t* self_max = nullptr;  // device: the self-max word (raftq_kernels.hpp) -- which match row is every group's largest
+  // The narrow mirror (raftq_kernels.hpp kNarrowValid): its word is self_max[1], always there and 0 until a build pass; the
+  // arrays are allocated by the first build (both or neither: a handle that cannot have them simply has no mirror).
+  uint64_t* anchor = nullptr;    // device u64 [ld]
+  uint32_t* moff = nullptr;      // device u32 [N][ld]
+  bool narrow_off = false;       // RAFTQ_NARROW=0 at raftq_create: never build the mirror
+  uint32_t* narrow_word() const { return self_max + 1; }
+  raftqk::NarrowMirror narrow_mirror() const { return raftqk::NarrowMirror{self_max + 1, anchor, moff}; }
   uint64_t compact_epoch = 0;  // completion-flag values handed to hipStreamWriteValue64 (h_total[3])
   uint64_t compact_epoch_armed = 0;  // epoch the current turn's wait may poll for (0 = blocking wait)
   // wait_turn: consecutive waits whose flag did not land in time and waits sat out since -- per KIND of wait ([0] the batching
@@ -228,6 +235,7 @@ struct raftq_set {
   uint64_t* counts_h = nullptr;       // pinned
   bool swept = false;
   bool broken = false;                // a member was destroyed under the set
+  bool tab_stale = false;             // a member allocated its narrow mirror since tab[0] / tab[1] were filled
   unsigned last_flags = 0;
   int mode = 0;                       // 0 = K-deep grid, 1 = persistent walk (raftq_set_mode)
   uint32_t persist_wgs = 0;
@@ -255,6 +263,7 @@ int use_device_idle(raftq_t* h, const char* who);  // + no Step batch in flight 
 // own voters.  Everything else (the device-built broadcasts: their frames go to N - 1 slots, not to a membership) is always refused.
 int refuse_voters(raftq_t* h, const char* who, bool step_family = false);
 int self_max_check(raftq_t* h);                 // the self-max word re-derived from the rows for h->self_peer (enqueued)
+int narrow_build(raftq_t* h);                   // the narrow mirror and its word re-derived from the rows (enqueued)
 int ensure_staging(raftq_t* h, size_t bytes);   // pinned, device-mapped staging (term deltas, campaign lists, log deltas)
 int ensure_ingest(raftq_t* h, size_t bytes);    // the ack buffer of the batching turn: device memory behind a large BAR, else pinned
 int ensure_tick_state(raftq_t* h);              // role / elapsed / action (+ hup bitmap)

@@ -42,6 +42,10 @@ struct SweepArgs {
   uint4* partials;             // [ld/kTile * kWaves] {changed, won, lost, 0}
   uint64_t ld;
   const uint32_t* self_max = nullptr;  // the handle's self-max word (below), or nullptr = never skip a row
+  // the handle's narrow word and the mirror it vouches for (below): anchor u64 [ld], moff u32 [N][ld]; nullptr = no mirror
+  const uint32_t* narrow = nullptr;
+  const uint64_t* anchor = nullptr;
+  const uint32_t* moff = nullptr;
 };
 
 // The self-max word of a handle (one device u32): kSelfMaxValid | slot when row `slot` of match is known to be the
@@ -52,14 +56,25 @@ struct SweepArgs {
 // check over the rows (self_max_check_kernel); cleared by every writer of match that may break it.
 constexpr uint32_t kSelfMaxValid = 0x80000000u;
 
+// The narrow word of a handle (one device u32, the word behind the self-max word): kNarrowValid when for every group g and
+// every row p  match[p][g] == anchor[g] + moff[p][g], else 0.  Match is u64 because a log index may be large; inside one
+// group the N values sit close together, so a 32-bit offset from one per-group base carries the same information in
+// 8 + 4N bytes instead of 8N.  While the word holds, a commit sweep of N >= 3 reads the mirror, selects over the offsets
+// (they share the anchor: order and ties are those of the values) and adds the anchor back.  The rule
+// is the self-max word's: set only by a full build pass (narrow_build_kernel); cleared by every writer of match that
+// may break it -- the ingest kernels keep the mirror true instead while they can.  A clear costs speed, never correctness.
+constexpr uint32_t kNarrowValid = 1u;
+
 // ---------------------------------------------------------------------------
 // uint64 compare-exchange, descending: a <- max, b <- min.  gfx950 has no
 // v_max_u64; this is one v_cmp_gt_u64 + 4 v_cndmask_b32, and the dead half of
 // a CE whose other output is never read is removed by the compiler.
-__device__ __forceinline__ void ce_desc(uint64_t& a, uint64_t& b) {
+// At 32 bits (the narrow path's offsets) the same source is one v_max_u32 + one v_min_u32.
+template <typename T>
+__device__ __forceinline__ void ce_desc(T& a, T& b) {
   const bool gt = a > b;
-  const uint64_t hi = gt ? a : b;
-  const uint64_t lo = gt ? b : a;
+  const T hi = gt ? a : b;
+  const T lo = gt ? b : a;
   a = hi;
   b = lo;
 }
@@ -68,8 +83,8 @@ __device__ __forceinline__ void ce_desc(uint64_t& a, uint64_t& b) {
 // tests/test_networks.py against the same comparator lists).  Only element
 // q-1 = N/2 of the descending order is consumed, so the compiler prunes the
 // comparators (and halves of comparators) that cannot reach it.
-template <int N>
-__device__ __forceinline__ uint64_t select_quorum_network(uint64_t (&v)[N]) {
+template <int N, typename T = uint64_t>
+__device__ __forceinline__ T select_quorum_network(T (&v)[N]) {
 #define CE(i, j) ce_desc(v[i], v[j])
   if constexpr (N == 2) { CE(0, 1); }
   if constexpr (N == 3) { CE(0, 2); CE(0, 1); CE(1, 2); }
@@ -250,8 +265,16 @@ struct TileRegs {
   u64x2 c[COMMIT ? kRounds : 1];
   u64x2 f[COMMIT && GATED ? kRounds : 1];
   u32x4p vw[VOTES ? (N <= 8 ? 1 : 2) : 1];  // the 8 vote words of the lane's 8 groups
-  uint32_t skip = 0;  // self_max_skip() of the tile's handle (wave-uniform): which row tile_load<SKIP = true> leaves out
+  // tile_body() of the tile's handle (wave-uniform): 0 = every row, slot + 1 = tile_load<kBodySkip> leaves that row out,
+  // kSkipNarrow = tile_load<kBodyNarrow> reads the mirror
+  uint32_t skip = 0;
 };
+
+// The three straight-line bodies of a tile's commit part.  kBodyNarrow keeps its inputs in the SAME registers (so a
+// persistent kernel's two register sets do not grow): the u64 of row p's offset pair {g, g + 1} is word p of the round's
+// m[] seen as 2N u64 words, the anchor pair is m[j][N - 1] -- N + 2 <= 2N words from N = 2.
+constexpr int kBodyAll = 0, kBodySkip = 1, kBodyNarrow = 2;
+constexpr uint32_t kSkipNarrow = 0x100u;
 
 // The row a sweep of this handle may leave out: 0 = none (read all N rows), else self slot + 1.  The word is read
 // once per workgroup and made wave-uniform; a commit sweep of N >= 2 (q >= 2) is the only one that can use it.
@@ -266,15 +289,35 @@ __device__ __forceinline__ uint32_t self_max_skip(const SweepArgs& a) {
   }
 }
 
-// SKIP (with r.skip = self slot + 1): the tile's commit part reads the N - 1 rows other than the self row into
-// r.m[j][0 .. N-1), in slot order; tile_finish then selects with select_other_network.  Without it, every row.
-template <int N, int GPL, bool COMMIT, bool GATED, bool VOTES, int POLICY, int BLOCK = kBlock, bool SKIP = false>
+// Which body a tile of this handle takes: the one that moves the fewest bytes, a compile-time rule on N.  The narrow body
+// reads 8 + 4N bytes of match data per group, the self-row skip 8(N - 1), every row 8N: narrow beats the skip from N = 5
+// and every row from N = 3; N = 3 and 4 with a valid self-max word keep the skip.  (Both at once would be 8 + 4(N - 1):
+// left out)  The narrow word is read once per workgroup, wave-uniform, and only where it can decide.
+template <int N, bool COMMIT>
+__device__ __forceinline__ uint32_t tile_body(const SweepArgs& a) {
+  const uint32_t skip = self_max_skip<N, COMMIT>(a);
+  if constexpr (!COMMIT || N < 3) {
+    return skip;
+  } else {
+    if (N < 5 && skip != 0) return skip;
+    if (a.narrow == nullptr) return skip;
+    const uint32_t w = __builtin_amdgcn_readfirstlane(ldg<false>(a.narrow));
+    return w == kNarrowValid ? kSkipNarrow : skip;
+  }
+}
+
+// BODY = kBodySkip (with r.skip = self slot + 1): the tile's commit part reads the N - 1 rows other than the self row into
+// r.m[j][0 .. N-1), in slot order; tile_finish then selects with select_other_network.  kBodyNarrow: the N offset pairs
+// (8-byte loads) and the anchor pair.  kBodyAll: every row.
+template <int N, int GPL, bool COMMIT, bool GATED, bool VOTES, int POLICY, int BLOCK = kBlock, int BODY = kBodyAll>
 __device__ __forceinline__ void tile_load(TileRegs<N, GPL, COMMIT, GATED, VOTES>& r, const SweepArgs& a,
                                           const uint32_t tile) {
   constexpr bool NT = (POLICY & kLdNT) != 0;
   constexpr int kTile = BLOCK * GPL;
   constexpr int kRounds = GPL / 2;
+  constexpr bool SKIP = BODY == kBodySkip;
   constexpr int kRows = SKIP && N >= 2 ? N - 1 : N;  // (a handle of one peer never skips: self_max_skip)
+  static_assert(BODY != kBodyNarrow || N >= 3, "the narrow body is chosen from N = 3 (tile_body)");
   const uint32_t tid = threadIdx.x;
   const uint64_t tile0 = (uint64_t)tile * kTile;
   // vote words first: their loads fly while the commit part computes
@@ -296,9 +339,19 @@ __device__ __forceinline__ void tile_load(TileRegs<N, GPL, COMMIT, GATED, VOTES>
 #pragma unroll
     for (int j = 0; j < kRounds; ++j) {
       const uint64_t g = tile0 + (uint64_t)(tid >> 6) * (64 * GPL) + (uint64_t)j * 128 + 2 * (tid & 63);
+      if constexpr (BODY == kBodyNarrow) {
 #pragma unroll
-      for (int p = 0; p < kRows; ++p) {
-        r.m[j][p] = ldg<NT>(reinterpret_cast<const u64x2*>(row[p] + g));
+        for (int p = 0; p < N; ++p) {  // g is even: the pair of 32-bit offsets is one aligned 8-byte load
+          const uint64_t w = ldg<NT>(reinterpret_cast<const uint64_t*>(a.moff + (uint64_t)p * a.ld + g));
+          if (p & 1) r.m[j][p >> 1].y = w;
+          else r.m[j][p >> 1].x = w;
+        }
+        r.m[j][N - 1] = ldg<NT>(reinterpret_cast<const u64x2*>(a.anchor + g));
+      } else {
+#pragma unroll
+        for (int p = 0; p < kRows; ++p) {
+          r.m[j][p] = ldg<NT>(reinterpret_cast<const u64x2*>(row[p] + g));
+        }
       }
       r.c[j] = ldg<NT>(reinterpret_cast<const u64x2*>(a.committed + g));
       if constexpr (GATED) r.f[j] = ldg<NT>(reinterpret_cast<const u64x2*>(a.first_idx + g));
@@ -314,7 +367,59 @@ __device__ __forceinline__ uint64_t quorum_select(uint64_t (&v)[N]) {
   else return select_quorum_network<N>(v);
 }
 
-template <int N, int GPL, bool COMMIT, bool GATED, bool VOTES, int POLICY, bool BITS, int BLOCK = kBlock, bool SKIP = false>
+// The quorum indices of the lane's two groups of round j, from the registers as tile_load<BODY> left them.  The narrow body
+// selects over the 32-bit offsets and adds the group's anchor to the one selected.  XOR (the tuner's kNoCompute): the same
+// operands folded with no selection.
+template <int N, int BODY, bool XOR, typename Regs>
+__device__ __forceinline__ void tile_mci(const Regs& r, const int j, uint64_t& mci0, uint64_t& mci1) {
+  if constexpr (BODY == kBodyNarrow) {
+    uint32_t v0[N], v1[N];
+#pragma unroll
+    for (int p = 0; p < N; ++p) {
+      const uint64_t w = (p & 1) ? r.m[j][p >> 1].y : r.m[j][p >> 1].x;
+      v0[p] = (uint32_t)w;
+      v1[p] = (uint32_t)(w >> 32);
+    }
+    uint32_t s0, s1;
+    if constexpr (XOR) {
+      s0 = v0[0];
+      s1 = v1[0];
+#pragma unroll
+      for (int p = 1; p < N; ++p) {
+        s0 ^= v0[p];
+        s1 ^= v1[p];
+      }
+    } else {
+      s0 = select_quorum_network<N, uint32_t>(v0);
+      s1 = select_quorum_network<N, uint32_t>(v1);
+    }
+    mci0 = r.m[j][N - 1].x + s0;
+    mci1 = r.m[j][N - 1].y + s1;
+  } else {
+    constexpr bool SKIP = BODY == kBodySkip;
+    constexpr int kRows = SKIP && N >= 2 ? N - 1 : N;
+    uint64_t v0[N], v1[N];
+#pragma unroll
+    for (int p = 0; p < kRows; ++p) {
+      v0[p] = r.m[j][p].x;
+      v1[p] = r.m[j][p].y;
+    }
+    if constexpr (XOR) {
+      mci0 = v0[0];
+      mci1 = v1[0];
+#pragma unroll
+      for (int p = 1; p < kRows; ++p) {
+        mci0 ^= v0[p];
+        mci1 ^= v1[p];
+      }
+    } else {
+      mci0 = quorum_select<N, SKIP>(v0);
+      mci1 = quorum_select<N, SKIP>(v1);
+    }
+  }
+}
+
+template <int N, int GPL, bool COMMIT, bool GATED, bool VOTES, int POLICY, bool BITS, int BLOCK = kBlock, int BODY = kBodyAll>
 __device__ __forceinline__ void tile_finish(const TileRegs<N, GPL, COMMIT, GATED, VOTES>& r, const SweepArgs& a,
                                             const uint32_t tile) {
   constexpr bool STNT = (POLICY & kStNT) != 0;
@@ -336,26 +441,8 @@ __device__ __forceinline__ void tile_finish(const TileRegs<N, GPL, COMMIT, GATED
 #pragma unroll
     for (int j = 0; j < kRounds; ++j) {
       const uint64_t g = tile0 + (uint64_t)(tid >> 6) * (64 * GPL) + (uint64_t)j * 128 + 2 * (tid & 63);
-      constexpr int kRows = SKIP && N >= 2 ? N - 1 : N;
-      uint64_t v0[N], v1[N];
-#pragma unroll
-      for (int p = 0; p < kRows; ++p) {
-        v0[p] = r.m[j][p].x;
-        v1[p] = r.m[j][p].y;
-      }
       uint64_t mci0, mci1;
-      if constexpr ((POLICY & kNoCompute) != 0) {
-        mci0 = v0[0];
-        mci1 = v1[0];
-#pragma unroll
-        for (int p = 1; p < kRows; ++p) {
-          mci0 ^= v0[p];
-          mci1 ^= v1[p];
-        }
-      } else {
-        mci0 = quorum_select<N, SKIP>(v0);
-        mci1 = quorum_select<N, SKIP>(v1);
-      }
+      tile_mci<N, BODY, (POLICY & kNoCompute) != 0>(r, j, mci0, mci1);
       u64x2 o;
       if constexpr ((POLICY & kNoCompute) != 0) {
         o.x = mci0 ^ r.c[j].x;
@@ -430,11 +517,18 @@ __device__ __forceinline__ void tile_finish(const TileRegs<N, GPL, COMMIT, GATED
 template <int N, int GPL, bool COMMIT, bool GATED, bool VOTES, int POLICY, bool BITS, int BLOCK = kBlock>
 __device__ __forceinline__ void sweep_tile(const SweepArgs& a, const uint32_t tile) {
   TileRegs<N, GPL, COMMIT, GATED, VOTES> r;
-  r.skip = self_max_skip<N, COMMIT>(a);
-  // one uniform branch per tile: each arm is the straight-line load-all-then-finish of one row count
+  r.skip = tile_body<N, COMMIT>(a);
+  // one uniform branch per tile: each arm is the straight-line load-all-then-finish of one body
+  if constexpr (COMMIT && N >= 3) {
+    if (r.skip == kSkipNarrow) {
+      tile_load<N, GPL, COMMIT, GATED, VOTES, POLICY, BLOCK, kBodyNarrow>(r, a, tile);
+      tile_finish<N, GPL, COMMIT, GATED, VOTES, POLICY, BITS, BLOCK, kBodyNarrow>(r, a, tile);
+      return;
+    }
+  }
   if (r.skip != 0) {
-    tile_load<N, GPL, COMMIT, GATED, VOTES, POLICY, BLOCK, true>(r, a, tile);
-    tile_finish<N, GPL, COMMIT, GATED, VOTES, POLICY, BITS, BLOCK, true>(r, a, tile);
+    tile_load<N, GPL, COMMIT, GATED, VOTES, POLICY, BLOCK, kBodySkip>(r, a, tile);
+    tile_finish<N, GPL, COMMIT, GATED, VOTES, POLICY, BITS, BLOCK, kBodySkip>(r, a, tile);
   } else {
     tile_load<N, GPL, COMMIT, GATED, VOTES, POLICY, BLOCK>(r, a, tile);
     tile_finish<N, GPL, COMMIT, GATED, VOTES, POLICY, BITS, BLOCK>(r, a, tile);
@@ -478,12 +572,24 @@ static __global__ __launch_bounds__(kBlock, MINW) void sweep_persist_kernel(cons
   };
   // a member's tiles with and without its self row (uniform branches; a set may mix flagged and unflagged members)
   auto load = [&](Regs& r, const SweepArgs& a, uint32_t tile) {
-    r.skip = self_max_skip<N, COMMIT>(a);
-    if (r.skip != 0) tile_load<N, GPL, COMMIT, GATED, VOTES, POLICY, kBlock, true>(r, a, tile);
+    r.skip = tile_body<N, COMMIT>(a);
+    if constexpr (COMMIT && N >= 3) {
+      if (r.skip == kSkipNarrow) {
+        tile_load<N, GPL, COMMIT, GATED, VOTES, POLICY, kBlock, kBodyNarrow>(r, a, tile);
+        return;
+      }
+    }
+    if (r.skip != 0) tile_load<N, GPL, COMMIT, GATED, VOTES, POLICY, kBlock, kBodySkip>(r, a, tile);
     else tile_load<N, GPL, COMMIT, GATED, VOTES, POLICY>(r, a, tile);
   };
   auto finish = [&](const Regs& r, const SweepArgs& a, uint32_t tile) {
-    if (r.skip != 0) tile_finish<N, GPL, COMMIT, GATED, VOTES, POLICY, BITS, kBlock, true>(r, a, tile);
+    if constexpr (COMMIT && N >= 3) {
+      if (r.skip == kSkipNarrow) {
+        tile_finish<N, GPL, COMMIT, GATED, VOTES, POLICY, BITS, kBlock, kBodyNarrow>(r, a, tile);
+        return;
+      }
+    }
+    if (r.skip != 0) tile_finish<N, GPL, COMMIT, GATED, VOTES, POLICY, BITS, kBlock, kBodySkip>(r, a, tile);
     else tile_finish<N, GPL, COMMIT, GATED, VOTES, POLICY, BITS>(r, a, tile);
   };
   // Two register sets, A and B, used alternately (no copies: a copy would have to wait for the data), and every
@@ -720,6 +826,55 @@ __device__ __forceinline__ void clear_self_max_if(bool broken, uint32_t* word) {
   if (b != 0 && (threadIdx.x & 63) == (uint32_t)(__ffsll((unsigned long long)b) - 1)) *word = 0u;
 }
 
+// The narrow word's full build: the host has just stored kNarrowValid into *word (same stream).  Per group the anchor is
+// the smallest of its N values and row p's offset what the row holds above it; a wave that finds a group whose values
+// spread over 2^32 or more clears the word (its offsets are then not written: nobody will read them).  Grid-stride over
+// the G groups; the padding keeps the zeros it was allocated with (anchor 0, offsets 0 = the rows' own padding).
+static __global__ __launch_bounds__(kBlock) void narrow_build_kernel(const uint64_t* __restrict__ match, uint64_t ld,
+                                                                     uint64_t n_groups, uint32_t n_peers,
+                                                                     uint64_t* __restrict__ anchor, uint32_t* __restrict__ moff,
+                                                                     uint32_t* word) {
+  bool broken = false;
+  for (uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x; g < n_groups; g += (uint64_t)gridDim.x * kBlock) {
+    uint64_t lo = match[g], hi = lo;
+    for (uint32_t p = 1; p < n_peers; ++p) {
+      const uint64_t v = match[(uint64_t)p * ld + g];
+      lo = v < lo ? v : lo;
+      hi = v > hi ? v : hi;
+    }
+    anchor[g] = lo;
+    if (hi - lo > 0xffffffffull) {
+      broken = true;
+    } else {
+      for (uint32_t p = 0; p < n_peers; ++p) moff[(uint64_t)p * ld + g] = (uint32_t)(match[(uint64_t)p * ld + g] - lo);
+    }
+  }
+  if (__ballot(broken) != 0 && (threadIdx.x & 63) == 0) *word = 0u;
+}
+
+// The handle's mirror as an ingest kernel sees it: the word (written by the kernel that clears it), the anchors (read only)
+// and the offset rows.
+struct NarrowMirror {
+  uint32_t* word;
+  const uint64_t* anchor;
+  uint32_t* moff;
+};
+// An ingest kernel's share of the narrow rule: it keeps the mirror true while it can.  `w` is the word as the kernel found
+// it (read once).  A value below the group's anchor is below the row as well -- the wide atomic max is a no-op, so is this.
+// One at or above anchor + 2^32 has no offset: -> true, the caller clears the word.  Otherwise the same atomic max at 32 bits
+// on the offset next to the one on the row: match == anchor + offset holds before and after, whatever the order of records.
+__device__ __forceinline__ bool narrow_follow(uint32_t w, const NarrowMirror& m, uint64_t ld, uint64_t group, uint32_t peer,
+                                              uint64_t value) {
+  if (w != kNarrowValid) return false;
+  const uint64_t base = m.anchor[group];
+  if (value < base) return false;
+  if (value - base > 0xffffffffull) return true;
+  atomicMax(m.moff + (uint64_t)peer * ld + group, (uint32_t)(value - base));
+  return false;
+}
+// one store per wave that met such a record (the lowest such lane), as clear_self_max_if
+__device__ __forceinline__ void clear_narrow_if(bool broken, uint32_t* word) { clear_self_max_if(broken, word); }
+
 // Progress.maybeUpdate only ever raises Match, so a batch of MsgAppResp
 // deltas is an order-independent atomic max.
 // Ingest, pass 1: the records sit in pinned, device-mapped host memory (the caller's batch buffer); one coalesced
@@ -751,19 +906,23 @@ template <typename Rec>
 static __global__ __launch_bounds__(kBlock) void deltas_in_apply_kernel(const Rec* __restrict__ src, uint64_t n, uint64_t* match,
                                                                         uint64_t ld, uint64_t n_groups, uint32_t n_peers,
                                                                         unsigned long long* bad_epoch, uint64_t* bad_host,
-                                                                        unsigned long long epoch, uint32_t* self_max) {
+                                                                        unsigned long long epoch, uint32_t* self_max,
+                                                                        NarrowMirror mirror) {
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   const uint32_t w = *self_max;
-  bool bad = false, broken = false;
+  const uint32_t nw = *mirror.word;
+  bool bad = false, broken = false, wide = false;
   if (i < n) {
     const Rec r = src[i];
     bad = r.group >= n_groups || r.peer >= n_peers;
     if (!bad) {
       broken = breaks_self_max(w, match, ld, r.group, r.peer, r.match);
+      wide = narrow_follow(nw, mirror, ld, r.group, r.peer, r.match);
       atomicMax(reinterpret_cast<unsigned long long*>(match + (uint64_t)r.peer * ld + r.group), (unsigned long long)r.match);
     }
   }
   clear_self_max_if(broken, self_max);
+  clear_narrow_if(wide, mirror.word);
   if (__ballot(bad) != 0 && (threadIdx.x & 63) == 0) {
     atomicMax(bad_epoch, epoch);
     *bad_host = epoch;
@@ -775,18 +934,21 @@ static __global__ __launch_bounds__(kBlock) void apply_deltas_kernel(uint64_t* m
                                                               const Rec* __restrict__ d, uint64_t n,
                                                               const unsigned long long* bad,
                                                               unsigned long long epoch_match, unsigned long long epoch_votes,
-                                                              uint32_t* self_max) {
+                                                              uint32_t* self_max, NarrowMirror mirror) {
   if (batch_is_bad(bad, epoch_match, epoch_votes)) return;  // a record of this call is out of range: nothing is applied
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   const uint32_t w = *self_max;
-  bool broken = false;
+  const uint32_t nw = *mirror.word;
+  bool broken = false, wide = false;
   if (i < n) {
     const Rec r = d[i];
     broken = breaks_self_max(w, match, ld, r.group, r.peer, r.match);
+    wide = narrow_follow(nw, mirror, ld, r.group, r.peer, r.match);
     atomicMax(reinterpret_cast<unsigned long long*>(match + (uint64_t)r.peer * ld + r.group),
               (unsigned long long)r.match);
   }
   clear_self_max_if(broken, self_max);
+  clear_narrow_if(wide, mirror.word);
 }
 
 // Sparse term update: a group's leader changed term (became leader / appended
@@ -1063,9 +1225,15 @@ static __global__ __launch_bounds__(kBlock) void sweep_segments_kernel(SweepArgs
   __shared__ uint32_t wave_cnt[kWaves];
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, tile = blockIdx.x;
   TileRegs<N, GPL, true, GATED, false> r;
-  r.skip = self_max_skip<N, true>(a);
-  if (r.skip != 0) tile_load<N, GPL, true, GATED, false, POLICY, kBlock, true>(r, a, tile);
-  else tile_load<N, GPL, true, GATED, false, POLICY>(r, a, tile);
+  r.skip = tile_body<N, true>(a);
+  const bool narrow = N >= 3 && r.skip == kSkipNarrow;  // wave-uniform
+  if (narrow) {
+    if constexpr (N >= 3) tile_load<N, GPL, true, GATED, false, POLICY, kBlock, kBodyNarrow>(r, a, tile);
+  } else if (r.skip != 0) {
+    tile_load<N, GPL, true, GATED, false, POLICY, kBlock, kBodySkip>(r, a, tile);
+  } else {
+    tile_load<N, GPL, true, GATED, false, POLICY>(r, a, tile);
+  }
   const uint64_t tile0 = (uint64_t)tile * kTile;
   u64x2 nw[kRounds];
   uint64_t even[kRounds], odd[kRounds];  // wave-uniform ballots
@@ -1073,19 +1241,13 @@ static __global__ __launch_bounds__(kBlock) void sweep_segments_kernel(SweepArgs
 #pragma unroll
   for (int j = 0; j < kRounds; ++j) {
     const uint64_t g = tile0 + (uint64_t)wave * (64 * GPL) + (uint64_t)j * 128 + 2 * lane;
-    uint64_t v0[N], v1[N];
-#pragma unroll
-    for (int p = 0; p < N; ++p) {
-      v0[p] = r.m[j][p].x;
-      v1[p] = r.m[j][p].y;
-    }
-    uint64_t mci0, mci1;
-    if (r.skip != 0) {  // (v[N-1] holds no row then and is not read)
-      mci0 = quorum_select<N, true>(v0);
-      mci1 = quorum_select<N, true>(v1);
+    uint64_t mci0 = 0, mci1 = 0;
+    if (narrow) {
+      if constexpr (N >= 3) tile_mci<N, kBodyNarrow, false>(r, j, mci0, mci1);
+    } else if (r.skip != 0) {
+      tile_mci<N, kBodySkip, false>(r, j, mci0, mci1);
     } else {
-      mci0 = quorum_select<N, false>(v0);
-      mci1 = quorum_select<N, false>(v1);
+      tile_mci<N, kBodyAll, false>(r, j, mci0, mci1);
     }
     u64x2 o;
     o.x = maybe_commit<GATED>(mci0, r.c[j].x, GATED ? r.f[j].x : 0);
@@ -1319,7 +1481,8 @@ static __global__ __launch_bounds__(kBlock) void fill_voters_kernel(uint16_t* vo
 // record, records unique per group within a batch (the host keeps the last of a group).  The group's mask is replaced; for
 // every bit of `reset` the slot's Match is zeroed and its field of the group's vote word cleared -- a slot reused for a new
 // replica must not inherit its predecessor's Match, and deltas only ever raise it.  A zeroed entry of the self row may end
-// the self-max fact: a batch that resets anything clears the word (always safe; the next full check restores it).
+// the self-max fact: a batch that resets anything clears the word (always safe; the next full check restores it) -- and the
+// narrow word with it.
 struct VoterDeltaRec {  // == raftq_voter_delta_t
   uint64_t group;
   uint16_t voters, reset;
@@ -1327,7 +1490,7 @@ struct VoterDeltaRec {  // == raftq_voter_delta_t
 };
 static __global__ __launch_bounds__(kBlock) void apply_voter_deltas_kernel(uint16_t* voters, uint64_t* match, uint64_t ld, uint8_t* votes,
                                                                            int wide, uint32_t n_peers, const VoterDeltaRec* __restrict__ d,
-                                                                           uint64_t n, uint32_t* self_max) {
+                                                                           uint64_t n, uint32_t* self_max, uint32_t* narrow) {
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   bool resets = false;
   if (i < n) {
@@ -1344,6 +1507,7 @@ static __global__ __launch_bounds__(kBlock) void apply_voter_deltas_kernel(uint1
     }
   }
   clear_self_max_if(resets, self_max);
+  clear_narrow_if(resets, narrow);  // (a zeroed row entry may lie below its group's anchor)
 }
 
 // ---------------------------------------------------------------------------

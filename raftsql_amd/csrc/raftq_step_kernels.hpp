@@ -314,6 +314,8 @@ struct NodeT {
         if (broken) *a.self_max = 0u;
       }
     }
+    // ... and Step does not keep the narrow mirror (the word behind the self-max word): a stored row ends it
+    if (mt_dirty != 0 && a.self_max != nullptr && a.self_max[1] != 0u) a.self_max[1] = 0u;
     if (elapsed_reset) a.elapsed[g] = 0;
     if (vw_dirty) {
       if (a.n_peers <= 8) reinterpret_cast<uint16_t*>(a.votes)[g] = (uint16_t)vw;

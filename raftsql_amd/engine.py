@@ -408,6 +408,18 @@ class QuorumEngine:
         self._chk(self._lib.raftq_self_max(self._h, C.byref(s)))
         return int(s.value)
 
+    def narrow(self) -> bool:
+        """raftq_narrow: the device knows match[p][g] == anchor[g] + offset[p][g] everywhere (a commit sweep of 3 or more peers
+        then reads the 32-bit mirror instead of the rows)"""
+        v = C.c_int32(0)
+        self._chk(self._lib.raftq_narrow(self._h, C.byref(v)))
+        return bool(v.value)
+
+    def narrow_rebuild(self) -> bool:
+        """raftq_narrow_rebuild: the mirror's build pass on demand -> narrow()"""
+        self._chk(self._lib.raftq_narrow_rebuild(self._h))
+        return self.narrow()
+
     def read_votes(self) -> np.ndarray:
         out = np.empty((self.n_peers, self.n_groups), dtype=np.uint8)
         self._chk(self._lib.raftq_read_votes(self._h, _ptr(out)))
