@@ -64,6 +64,19 @@ func (e *Engine) SetStepVoters(on bool) error {
 	return e.err(C.raftq_step_set_voters(e.h, v))
 }
 
+// SetTickVoters opts the engine in to (or out of) Tick and its device-built rounds over each group's own members: with voter
+// masks loaded, Tick, TickCollect and TickCollectLists then apply upstream's promotable() -- a group in which this node does not
+// vote raises no MsgHup and keeps its timer at 0 -- and TickFrames / TickElectFrames run instead of returning ErrState, their
+// heartbeats and MsgVotes going to the group's members only (the other peers' slots are frames of zero length; include/raftq.h
+// "batched Tick", include/raftq_wire.h).  Independent of SetStepVoters; no batch may be in flight.
+func (e *Engine) SetTickVoters(on bool) error {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	return e.err(C.raftq_tick_set_voters(e.h, v))
+}
+
 // StepOut is layout-identical to raftq_step_out_t (64 bytes).
 type StepOut struct {
 	Group, Term, Index, LogTerm, Commit, LastIndex uint64

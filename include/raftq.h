@@ -186,11 +186,14 @@ int raftq_apply_term_deltas(raftq_t* h, const raftq_term_delta_t* d, uint64_t n)
  * form).  Step (raftq_step.h / raftq_wire.h) runs over each group's own voters on a handle that opted in with
  * raftq_step_set_voters(h, 1) -- raftq_step_batch, raftq_step_submit / _collect, raftq_step_submit_packed, raftq_step_submit_wire,
  * raftq_step_frames / _frames_packed, raftq_apply_log_deltas / _nowait; raftq_step.h restates these rules for quorum(),
- * maybeCommit and poll -- and refuses a masked handle that did not (RAFTQ_ESTATE, the default).  Not built, and refused with
- * RAFTQ_ESTATE and a message that says so whatever that switch says: a sweep set with a masked member (raftq_set_create;
- * raftq_load_voters / raftq_apply_voter_deltas on a member), and the calls that build a broadcast on the device --
- * raftq_step_frames_respond, raftq_propose_frames, raftq_tick_frames, raftq_tick_elect_frames: their frames go to N - 1 slots,
- * not to a membership.  A handle with no masks loaded is exactly the handle it always was, kernels included. */
+ * maybeCommit and poll -- and refuses a masked handle that did not (RAFTQ_ESTATE, the default).  Tick and the two rounds it
+ * starts on the device have a switch of their own, raftq_tick_set_voters(h, 1) ("batched Tick" below): promotable() in
+ * raftq_tick / raftq_tick_collect / raftq_tick_collect_lists, and raftq_tick_frames / raftq_tick_elect_frames (raftq_wire.h)
+ * over each group's own members; without it Tick reads no mask and those two calls refuse a masked handle (RAFTQ_ESTATE, the
+ * default).  Not built, and refused with RAFTQ_ESTATE and a message that says so whatever the switches say: a sweep set with a
+ * masked member (raftq_set_create; raftq_load_voters / raftq_apply_voter_deltas on a member), and raftq_step_frames_respond and
+ * raftq_propose_frames, whose frames go to N - 1 slots, not to a membership.  A handle with no masks loaded is exactly the
+ * handle it always was, kernels included. */
 typedef struct raftq_voter_delta {
   uint64_t group;
   uint16_t voters; /* the group's new mask */
@@ -257,7 +260,22 @@ int raftq_collect_changed(raftq_t* h, raftq_advance_t* out, uint64_t cap, uint64
  *   rnd = fin32(lo32(group) ^ hi32(group) ^ lo32(key)) ^ hi32(key)             per group,
  *         fin32(x): x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^ x >> 16
  * and a timer fires when elapsed - election_tick > rnd % election_tick
- * (etcd's isElectionTimeout with its rand.Int() replaced by rnd). */
+ * (etcd's isElectionTimeout with its rand.Int() replaced by rnd).
+ *
+ * promotable().  Upstream's tickElection begins `if !r.promotable() { r.elapsed = 0; return }`: a node that is not in a
+ * group's r.prs never campaigns for it.  By default Tick reads no voter mask ("per-group voter sets" above) and a removed node
+ * keeps raising MsgHup.  raftq_tick_set_voters(h, 1) opts the handle in: with masks loaded, raftq_tick, raftq_tick_collect,
+ * raftq_tick_collect_lists and the Tick inside raftq_tick_frames / raftq_tick_elect_frames (raftq_wire.h) apply, with
+ * mine = bit `self` (raftq_set_self, raftq_step.h) of voters[g]:
+ *   a leader                    unchanged -- tickHeartbeat does not ask
+ *   a non-leader, mine set      unchanged -- the same elapsed + 1, the same draw from the same stream, the same MsgHup
+ *   a non-leader, mine clear    elapsed = 0, action 0, never flagged (an empty mask, an unused slot, is this case)
+ * The masked Tick needs to know `self`: RAFTQ_ESTATE on a handle with neither raftq_set_self nor raftq_load_node.  The switch
+ * also opens raftq_tick_frames and raftq_tick_elect_frames to a masked handle -- their rounds then go to each group's own
+ * members.  0 is the default (Tick asks nobody, the two calls refuse a masked handle); anything but 0 or 1 is RAFTQ_EINVAL; the
+ * handle must be idle (RAFTQ_ESTATE with a Step batch in flight).  A property of the handle: raftq_clone_state does not copy it
+ * and raftq_load_voters(h, NULL) does not clear it; with no masks loaded the handle launches what it always did, whatever the
+ * switch says.  Independent of raftq_step_set_voters.  raftq_set_tick is untouched: set members cannot hold masks. */
 #define RAFTQ_ROLE_FOLLOWER 0
 #define RAFTQ_ROLE_CANDIDATE 1
 #define RAFTQ_ROLE_LEADER 2
@@ -267,6 +285,7 @@ typedef struct raftq_tick_counts {
 } raftq_tick_counts_t;
 int raftq_set_timers(raftq_t* h, uint32_t election_tick, uint32_t heartbeat_tick, uint64_t seed);
 int raftq_load_roles(raftq_t* h, const uint8_t* role /*[G]*/, const uint32_t* elapsed /*[G]|NULL = 0*/);
+int raftq_tick_set_voters(raftq_t* h, int on);
 /* one Tick for every group; synchronous when counts != NULL, else enqueued */
 int raftq_tick(raftq_t* h, raftq_tick_counts_t* counts);
 /* any of the outputs may be NULL */

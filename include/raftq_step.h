@@ -91,13 +91,16 @@ int raftq_step_set_msg_flags(raftq_t* h, int on);
  *   non-voters     their words are stored and read as always (CHOICE): an ack from a non-voter moves its Match and sets
  *                  RAFTQ_OUTF_UPDATED, a MsgVote from a non-voter is answered by the usual rule.
  *   reset()        writes all N slots as always -- self = lastIndex, the others 0 -- whether or not self is a voter.
- *   MsgHup         on a group in which self does not vote campaigns (CHOICE: promotable() is not modelled, Tick does not
- *                  read masks): the own grant is recorded but not counted, so the result is RAFTQ_OUT_CAMPAIGN.
+ *   MsgHup         on a group in which self does not vote campaigns (CHOICE: Step does not ask promotable(); the Tick of a
+ *                  handle that opted in to raftq_tick_set_voters, raftq.h, raises no MsgHup for such a group): the own
+ *                  grant is recorded but not counted, so the result is RAFTQ_OUT_CAMPAIGN.
  *
- * What stays refused (RAFTQ_ESTATE, "voter masks" in the text) whatever the switch says: raftq_step_frames_respond,
- * raftq_propose_frames, raftq_tick_frames, raftq_tick_elect_frames -- their broadcasts go to N - 1 slots, not to a
- * membership, and the proposal path relies on "maybeCommit cannot move with more than one peer", which a one-voter group
- * breaks.  Sweep sets with a masked member and raftq_node (which never loads masks) are as before. */
+ * What stays refused (RAFTQ_ESTATE, "voter masks" in the text) whatever this switch says: raftq_step_frames_respond,
+ * raftq_propose_frames -- always -- and raftq_tick_frames, raftq_tick_elect_frames unless raftq_tick_set_voters (raftq.h
+ * "batched Tick") opted the handle in, which sends their rounds to each group's own members.  The broadcasts of the first
+ * two go to N - 1 slots, not to a membership, and the proposal path relies on "maybeCommit cannot move with more than one
+ * peer", which a one-voter group breaks.  Sweep sets with a masked member and raftq_node (which never loads masks) are as
+ * before. */
 int raftq_step_set_voters(raftq_t* h, int on);
 
 /* raftq_msg_t._pad[1] once the handle opted in.  RAFTQ_MSGF_ENTRIES on a MsgApp: the caller says what the message carries -- the low 32 bits of

@@ -336,15 +336,24 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
  * of the same raftq_wire_msg_t records built on the host; the records are written into the encoder's input in HBM and never exist
  * in host memory.
  *
+ * Over each group's own members (raftq_tick_set_voters(h, 1), raftq.h "batched Tick", on a handle with voter masks loaded): the
+ * Tick applies promotable(), and of the frames above only those to a slot p whose bit is set in voters[g] exist -- upstream's
+ * bcastHeartbeat ranges over r.prs.  The layout stays POSITIONAL: peer_off is exactly what it is without masks, n_built slots per
+ * slice, frame_off keeps its beat_cap * (N - 1) + 1 entries, and the slot of a peer that is no member of its group is a frame of
+ * ZERO length, frame_off[k + 1] == frame_off[k].  Peer p's bytes are out[frame_off[peer_off[p]] .. frame_off[peer_off[p + 1]]):
+ * what raftq_wire_encode makes of the member records alone, in group order.  counts->n_msgs is the number of frames that have
+ * bytes.  Whether self is a member is not asked: a leader whose own bit is clear still beats its members.  A built group with an
+ * empty mask gives no frame.  With the switch on and no masks loaded the call is what it always was.
+ *
  * Refused before anything is enqueued -- a refused call has not ticked:
  *   RAFTQ_EINVAL  cap < beat_cap * (N - 1) * RAFTQ_RESPOND_FRAME_MAX (the largest payload-free frame, above);
  *                 out, frame_off or peer_off not page-locked and 16-byte aligned; N < 2; an unknown flag;
  *                 beat_cap * (N - 1) >= 2^31, or beat_cap * (N - 1) * RAFTQ_RESPOND_FRAME_MAX beyond 2^31 bytes
  *   RAFTQ_ESTATE  a Step batch in flight; no node state on the handle (neither raftq_set_self nor raftq_load_node was ever
- *                 called); voter masks loaded (the round goes to every slot, not to the group's own membership --
- *                 whatever raftq_step_set_voters says: that switch opens raftq_step_submit_wire, raftq_step_frames and
- *                 raftq_step_frames_packed to a masked handle, not raftq_step_frames_respond, raftq_propose_frames,
- *                 raftq_tick_frames or raftq_tick_elect_frames)
+ *                 called); voter masks loaded on a handle that did not opt in with raftq_tick_set_voters (the round would go to
+ *                 every slot, not to the group's own membership -- whatever raftq_step_set_voters says: that switch opens
+ *                 raftq_step_submit_wire, raftq_step_frames and raftq_step_frames_packed to a masked handle, not
+ *                 raftq_step_frames_respond, raftq_propose_frames, raftq_tick_frames or raftq_tick_elect_frames)
  * Every allocation is made before the tick kernel is enqueued (the rule raftq_tick_collect_lists follows). */
 int raftq_tick_frames(raftq_t* h, unsigned flags, uint64_t hup_cap, uint64_t beat_cap, uint64_t* n_hup, uint64_t* n_beat,
                       void* out, uint64_t cap, uint64_t* frame_off /*[beat_cap*(N-1)+1] | NULL*/, uint64_t* peer_off /*[N+1]*/,
@@ -378,11 +387,24 @@ int raftq_tick_frames(raftq_t* h, unsigned flags, uint64_t hup_cap, uint64_t bea
  * frame all holding the total.  counts: n_msgs = (n_bb + n_vb) * (N - 1), bytes.  Byte for byte what raftq_wire_encode makes of
  * the same raftq_wire_msg_t records built on the host.
  *
+ * Over each group's own voters (raftq_tick_set_voters(h, 1) on a handle with voter masks loaded): the Tick applies promotable(),
+ * so self votes in every MsgHup group; the heartbeat section is raftq_tick_frames' over members; and Step(MsgHup) is the masked
+ * Step's (raftq_step.h raftq_step_set_voters, whether or not that switch is on), with its two arms:
+ *   self is the group's ONLY voter (the own grant is the quorum): the group becomes leader at once.  camp[r] is Step's record
+ *     for that message -- type = RAFTQ_OUT_BECAME_LEADER, index = the empty entry's, commit = the commit index (a one-voter
+ *     group commits its own append: RAFTQ_OUTF_COMMITTED), RAFTQ_OUTF_HARDSTATE and NOT RAFTQ_OUTF_ANSWERED: the caller
+ *     appends the empty entry as it does after Step.  Nobody is asked for a vote: every vote slot of the group has zero length.
+ *   otherwise: RAFTQ_OUT_CAMPAIGN exactly as above, and a MsgVote to every member p != self -- upstream's campaign ranges over
+ *     r.prs; the slots of the other peers have zero length.
+ * Both sections stay positional, as raftq_tick_frames says: peer_off[0 .. 2 N + 1] is what it is without masks, frame_off keeps
+ * (beat_cap + hup_cap) * (N - 1) + 1 entries, counts->n_msgs is the number of frames that have bytes.
+ *
  * Refused before anything is enqueued -- a refused call has neither ticked nor campaigned:
  *   RAFTQ_EINVAL  cap < (beat_cap + hup_cap) * (N - 1) * RAFTQ_RESPOND_FRAME_MAX; camp, out, frame_off or peer_off not page-locked
  *                 and 16-byte aligned (camp may be NULL only when hup_cap == 0); N < 2; an unknown flag;
  *                 (beat_cap + hup_cap) * (N - 1) >= 2^31, or that many frames beyond 2^31 bytes
- *   RAFTQ_ESTATE  a Step batch in flight; no node state on the handle; voter masks loaded
+ *   RAFTQ_ESTATE  a Step batch in flight; no node state on the handle; voter masks loaded on a handle that did not opt in with
+ *                 raftq_tick_set_voters
  * Every allocation is made before the tick kernel is enqueued.  With hup_cap == 0 the call is raftq_tick_frames. */
 int raftq_tick_elect_frames(raftq_t* h, unsigned flags, uint64_t hup_cap, uint64_t beat_cap, uint64_t* n_hup, uint64_t* n_beat,
                             raftq_step_out_s_t* camp /*[hup_cap]*/, void* out, uint64_t cap,

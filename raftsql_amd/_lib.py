@@ -93,6 +93,7 @@ _SIGS = [
     ("raftq_collect_changed", C.c_int, [_H, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("raftq_set_timers", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint64]),
     ("raftq_load_roles", C.c_int, [_H, C.c_void_p, C.c_void_p]),
+    ("raftq_tick_set_voters", C.c_int, [_H, C.c_int]),
     ("raftq_tick", C.c_int, [_H, C.POINTER(TickCounts)]),
     ("raftq_read_tick", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("raftq_collect_hups", C.c_int, [_H, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),

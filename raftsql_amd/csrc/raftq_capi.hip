@@ -710,8 +710,9 @@ static int voters_not_in_set(raftq_t* h, const char* who) {
   return fail(h, RAFTQ_ESTATE, std::string(who) + ": the handle is a member of a sweep set, whose dispatches count every slot "
                                                   "(voter masks on set members are out of scope)");
 }
-int raftq_detail::refuse_voters(raftq_t* h, const char* who, bool step_family) {
+int raftq_detail::refuse_voters(raftq_t* h, const char* who, bool step_family, bool tick_rounds) {
   if (!h || !h->voters) return RAFTQ_OK;
+  if (tick_rounds && h->tick_voters) return RAFTQ_OK;
   if (h->step_voters) {
     if (step_family) return RAFTQ_OK;
     return fail(h, RAFTQ_ESTATE, std::string(who) + ": the handle has voter masks loaded; the broadcasts built on the device go to N - 1 slots, "
@@ -1099,11 +1100,36 @@ static TickArgs tick_args(const raftq_t* h, uint64_t tick_no) {
   return a;
 }
 
+// promotable() needs to know which slot this node is: the masked Tick is a node's, the plain one is anybody's
+static int tick_voters_ready(raftq_t* h, const char* who) {
+  if (!raftq_detail::masked_tick(h) || h->node_rec || h->self_set) return RAFTQ_OK;
+  return fail(h, RAFTQ_ESTATE, std::string(who) + ": raftq_tick_set_voters is on and voter masks are loaded, but the handle holds no node state "
+                                                  "(raftq_set_self / raftq_load_node first): promotable() asks whether THIS node votes");
+}
+// Every Tick launch of the handle: tick_kernel, or -- raftq_tick_set_voters with masks loaded -- its masked twin
+static void launch_tick(raftq_t* h) {
+  const dim3 grid((unsigned)(h->gpad / 1024));
+  if (raftq_detail::masked_tick(h))
+    hipLaunchKernelGGL(tick_voters_kernel, grid, dim3(kBlock), 0, h->stream, tick_args(h, h->tick_no++), (const uint16_t*)h->voters, h->self_peer);
+  else
+    hipLaunchKernelGGL(tick_kernel, grid, dim3(kBlock), 0, h->stream, tick_args(h, h->tick_no++));
+}
+
+int raftq_tick_set_voters(raftq_t* h, int on) {
+  if (int rc = use_device_idle(h, "raftq_tick_set_voters")) return rc;
+  if (on != 0 && on != 1)
+    return fail(h, RAFTQ_EINVAL, "raftq_tick_set_voters: 0 (Tick asks nobody, the device-built rounds refuse a masked handle) or 1 (promotable() in Tick, "
+                                 "rounds over each group's own members)");
+  h->tick_voters = on == 1;
+  return RAFTQ_OK;
+}
+
 int raftq_tick(raftq_t* h, raftq_tick_counts_t* counts) {
   if (int rc = use_device_idle(h, "raftq_tick")) return rc;
+  if (int rc = tick_voters_ready(h, "raftq_tick")) return rc;
   if (int rc = ensure_tick_state(h)) return rc;
   h->tl_valid = false;  // (raftq_last_tick_lists must not hand out an older tick's lists as the last one's)
-  hipLaunchKernelGGL(tick_kernel, dim3((unsigned)(h->gpad / 1024)), dim3(kBlock), 0, h->stream, tick_args(h, h->tick_no++));
+  launch_tick(h);
   HIPCHK(h, hipGetLastError());
   h->ticked = true;
   if (counts) {
@@ -1127,6 +1153,7 @@ int raftq_tick_collect(raftq_t* h, uint64_t* hups, uint64_t hup_cap, uint64_t* n
   if (int rc = use_device_idle(h, "raftq_tick_collect")) return rc;
   if (!n_hup || !n_beat) return fail(h, RAFTQ_EINVAL, "raftq_tick_collect: null count");
   if ((hup_cap && !hups) || (beat_cap && !beats)) return fail(h, RAFTQ_EINVAL, "raftq_tick_collect: null list with cap > 0");
+  if (int rc = tick_voters_ready(h, "raftq_tick_collect")) return rc;
   if (int rc = ensure_tick_state(h)) return rc;
   const uint64_t cap_h = std::min<uint64_t>(hup_cap, h->G), cap_b = std::min<uint64_t>(beat_cap, h->G);
   if (int rc = ensure_adv(h, (cap_h + cap_b + 2) / 3 + 2)) return rc;
@@ -1134,7 +1161,7 @@ int raftq_tick_collect(raftq_t* h, uint64_t* hups, uint64_t hup_cap, uint64_t* n
   if (nw > (1u << 14))
     if (int rc = ensure_tick_offsets2(h, nw)) return rc;  // (before the Tick: a call that fails has not ticked)
   h->tl_valid = false;  // raftq_last_tick_lists hands out the lists of the LAST tick, and this is a newer one
-  hipLaunchKernelGGL(tick_kernel, dim3((unsigned)(h->gpad / 1024)), dim3(kBlock), 0, h->stream, tick_args(h, h->tick_no++));
+  launch_tick(h);
   h->ticked = true;
   const uint64_t *off_h = nullptr, *off_b = nullptr;
   if (nw > (1u << 14)) {  // past 16K waves every workgroup summing its predecessors itself would show: scan first
@@ -1167,6 +1194,7 @@ int raftq_tick_collect(raftq_t* h, uint64_t* hups, uint64_t hup_cap, uint64_t* n
 // kernels between the lists and the flag: what is checked and allocated, what is enqueued, the wait and what it leaves.
 int raftq_detail::tick_lists_prepare(raftq_t* h, const char* who, unsigned flags, uint64_t hup_cap, uint64_t beat_cap, TickLists* tl) {
   if (flags & ~RAFTQ_TICK_BEAT_BITMAP) return fail(h, RAFTQ_EINVAL, std::string(who) + ": unknown flag");
+  if (int rc = tick_voters_ready(h, who)) return rc;
   if (int rc = ensure_tick_state(h)) return rc;
   const bool bitmap = flags & RAFTQ_TICK_BEAT_BITMAP;
   const uint64_t cap_h = std::min<uint64_t>(hup_cap, h->G), cap_b = bitmap ? 0 : std::min<uint64_t>(beat_cap, h->G);
@@ -1187,7 +1215,7 @@ int raftq_detail::tick_lists_enqueue(raftq_t* h, TickLists* tl) {
   const bool bitmap = tl->flags & RAFTQ_TICK_BEAT_BITMAP;
   const uint64_t cap_h = tl->cap_h, cap_b = tl->cap_b;
   const uint64_t nw = h->gpad / 256;
-  hipLaunchKernelGGL(tick_kernel, dim3((unsigned)(h->gpad / 1024)), dim3(kBlock), 0, h->stream, tick_args(h, h->tick_no++));
+  launch_tick(h);
   h->ticked = true;
   const uint64_t *off_h = nullptr, *off_b = nullptr;
   if (nw > (1u << 14)) {  // past 16K waves every workgroup summing its predecessors itself would show: scan first

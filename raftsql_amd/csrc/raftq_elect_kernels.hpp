@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "raftq_beat_kernels.hpp"
 #include "raftq_step_kernels.hpp"
 #include "raftq_wire_kernels.hpp"
 
@@ -145,6 +146,83 @@ static __global__ __launch_bounds__(kBlock) void elect_build_kernel(ElectArgs e)
     f.to = 0xff;
     e.enc[k] = f;
   }
+}
+
+// elect_build_kernel over voters (raftq_tick_set_voters on a handle with voter masks loaded; raftq_beat_kernels.hpp says what the
+// twins share and why the sections stay positional).  Every MsgHup group is promotable -- tick_voters_kernel flags no other --
+// and the lane runs the masked Node, the one step_voters_kernel uses: become_candidate(), poll(self, granted), then exactly the
+// two arms of Node::step's MsgHup case.
+//   granted == q_g: the group's only voter is self.  become_leader(), and camp[r] is Step's RAFTQ_OUT_BECAME_LEADER record for
+//     that message: index = the empty entry's, commit = committed (a one-voter group commits its own append), RAFTQ_OUTF_HARDSTATE
+//     (and _COMMITTED when the commit moved) and NOT RAFTQ_OUTF_ANSWERED -- the caller appends the empty entry, as after Step.
+//     Nobody is asked: every vote slot of the group is a filler.
+//   otherwise: RAFTQ_OUT_CAMPAIGN as in elect_build_kernel, a MsgVote to every member p != self, fillers in the other slots.
+static __global__ __launch_bounds__(kBlock) void elect_build_voters_kernel(ElectArgs e, const uint16_t* __restrict__ voters, unsigned long long* members) {
+  __shared__ uint64_t red[kWaves];
+  __shared__ uint32_t mine[kWaves];
+  __shared__ uint32_t ids[kBlock * 4];
+  const uint32_t tid = threadIdx.x;
+  const uint64_t n_hup = e.totals[0], n_beat = e.totals[1];
+  const uint64_t n_vb = n_hup < e.hup_cap ? n_hup : e.hup_cap;
+  const uint64_t n_bb = n_beat < e.beat_cap ? n_beat : e.beat_cap;
+  const uint64_t n_slices = e.a.n_peers - 1;
+  uint64_t pos;  // rank of this block's first MsgHup group
+  uint32_t tot;  // MsgHup groups of this block
+  members_rank<0>(e.hup_bits, e.partials, e.n_chunks, e.wave_off_hup, n_vb, red, mine, ids, pos, tot);
+  uint32_t wrote = 0;
+  if (pos < n_vb) {
+    const uint64_t left = n_vb - pos;
+    const uint32_t take = left < tot ? (uint32_t)left : tot;  // this block's groups of rank < n_vb
+    WireMsg* const votes = e.enc + n_bb * n_slices;
+    for (uint32_t r = tid; r < take; r += kBlock) {
+      const uint64_t g = ids[r];
+      const uint64_t at = pos + r;
+      uint64_t term = 0, last_index = 0, last_term = 0;
+      uint32_t ask = 0;  // the slots a MsgVote goes to
+      u64x2 c0, c1;
+      c0.x = c0.y = c1.x = c1.y = 0;
+      if (g < e.a.n_groups) {  // (the Tick flags no padding group)
+        NodeT<true> node(e.a, g, voters);
+        const uint64_t commit0 = node.committed;
+        // Step(MsgHup) -> campaign(): the calls Node::step makes
+        node.become_candidate();
+        uint32_t granted, recorded;
+        node.poll(e.a.self, true, granted, recorded);
+        const bool won = granted == node.quorum();  // the own grant is a quorum: self is the group's only voter
+        if (won) node.become_leader();
+        node.store();
+        term = node.term; last_index = node.last_index; last_term = node.last_term;
+        // == put_result(kFmtS32) of step()'s record: a campaign's commit carries the candidate's lastTerm
+        uint32_t flags = kFlagHardState;  // (the term moved)
+        if (won) flags |= node.committed != commit0 ? kFlagCommitted : 0u;
+        else flags |= kFlagAnswered;
+        c0.x = term; c0.y = last_index;
+        c1.x = won ? node.committed : last_term;
+        c1.y = (uint64_t)(uint8_t)node.vote | ((uint64_t)(uint8_t)node.lead << 8) | ((uint64_t)(won ? kOutBecameLeader : kOutCampaign) << 16) |
+               ((uint64_t)flags << 32) | ((uint64_t)node.role << 40);
+        ask = won ? 0u : node.vmask;
+      }
+      u64x2* cq = reinterpret_cast<u64x2*>(e.camp + at);
+      cq[0] = c0;
+      cq[1] = c1;
+#pragma unroll
+      for (uint32_t p = 0; p < (uint32_t)kMaxPeers; ++p) {
+        if (p >= e.a.n_peers || p == e.a.self) continue;
+        const uint64_t slice = p < e.a.self ? p : p - 1;
+        const bool member = ((ask >> p) & 1u) != 0;
+        vote_store(votes + slice * n_vb + at, g, term, last_term, last_index, e.a.self, member ? p : 0xffu);
+        wrote += member ? 1u : 0u;
+      }
+    }
+  }
+  // fillers behind both sections, as in elect_build_kernel
+  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+  for (uint64_t k = (n_bb + n_vb) * n_slices + (uint64_t)blockIdx.x * kBlock + tid; k < (e.beat_cap + e.hup_cap) * n_slices; k += stride) {
+    WireMsg f{};
+    f.to = 0xff;
+    e.enc[k] = f;
+  }
+  members_add(wrote, red, members);
 }
 
 }  // namespace raftqk

@@ -121,6 +121,8 @@ struct raftq {
   bool step_msg_flags = false;     // raftq_msg_t._pad[1] / _resv carry RAFTQ_MSGF_* (raftq_step_set_msg_flags); padding otherwise
   bool step_voters = false;        // raftq_step_set_voters: with masks loaded the Step family runs the *_voters_kernel twins (a property of
                                    // the handle: raftq_clone_state and raftq_load_voters(h, NULL) leave it alone)
+  bool tick_voters = false;        // raftq_tick_set_voters: with masks loaded Tick runs tick_voters_kernel (promotable()) and the two
+                                   // device-built rounds go to each group's own members (the same kind of property as step_voters)
   int step_walk_mode = 1;          // 1 = lists (default), 0 = always the sorted walk (RAFTQ_STEP_WALK=sort)
   uint32_t step_stalls_in_a_row = 0, step_sorted_left = 0;  // back-off from the list walk under hot-group traffic
   uint64_t step_replays = 0;       // batches that went through the sorted path after a stall
@@ -260,8 +262,12 @@ int use_device(raftq_t* h);
 int use_device_idle(raftq_t* h, const char* who);  // + no Step batch in flight (RAFTQ_ESTATE otherwise)
 // RAFTQ_ESTATE for a handle with voter masks loaded.  step_family (raftq_step_batch / _submit* / _frames / _frames_packed,
 // raftq_apply_log_deltas*): let through once the handle opted in (raftq_step_set_voters) -- those calls then run over each group's
-// own voters.  Everything else (the device-built broadcasts: their frames go to N - 1 slots, not to a membership) is always refused.
-int refuse_voters(raftq_t* h, const char* who, bool step_family = false);
+// own voters.  tick_rounds (raftq_tick_frames, raftq_tick_elect_frames): let through once the handle opted in to
+// raftq_tick_set_voters -- their rounds then go to each group's own members.  Everything else (the other device-built broadcasts:
+// their frames go to N - 1 slots, not to a membership) is always refused.
+int refuse_voters(raftq_t* h, const char* who, bool step_family = false, bool tick_rounds = false);
+// raftq_tick_set_voters on a handle with masks loaded: every Tick launch is tick_voters_kernel's, the rounds are the twins'
+inline bool masked_tick(const raftq_t* h) { return h->voters != nullptr && h->tick_voters; }
 int self_max_check(raftq_t* h);                 // the self-max word re-derived from the rows for h->self_peer (enqueued)
 int narrow_build(raftq_t* h);                   // the narrow mirror and its word re-derived from the rows (enqueued)
 int ensure_staging(raftq_t* h, size_t bytes);   // pinned, device-mapped staging (term deltas, campaign lists, log deltas)
@@ -311,8 +317,9 @@ struct TickLists {
 int tick_lists_prepare(raftq_t* h, const char* who, unsigned flags, uint64_t hup_cap, uint64_t beat_cap, TickLists* tl);
 int tick_lists_enqueue(raftq_t* h, TickLists* tl);
 int tick_lists_finish(raftq_t* h, const char* who, const TickLists& tl, uint64_t* n_hup, uint64_t* n_beat);
-// raftq_step.hip, for raftq_tick_frames: the handle's records exist and are fresh (ensure_mirror), voter masks refused
-int node_records_of(raftq_t* h, const char* who, raftqk::NodeArrays* out);
+// raftq_step.hip, for raftq_tick_frames: the handle's records exist and are fresh (ensure_mirror), voter masks refused --
+// tick_rounds: unless the handle opted in to raftq_tick_set_voters (the two tick calls pass true)
+int node_records_of(raftq_t* h, const char* who, raftqk::NodeArrays* out, bool tick_rounds = false);
 int respond_pass_ok(raftq_t* h);  // a pass of the marshal whose totals are about to be replaced (a stalled batch's first): it did not give up
 // The wait that ends a call whose results the kernels wrote into page-locked memory themselves (the streaming codecs,
 // raftq_step_frames): a one-thread kernel raises the handle's completion word behind everything enqueued so far and the host

@@ -1649,6 +1649,54 @@ __device__ __forceinline__ void tick_tile(const TickArgs& a, uint64_t n_blocks) 
 }
 static __global__ __launch_bounds__(kBlock) void tick_kernel(TickArgs a) { tick_tile<1>(a, gridDim.x); }
 
+// tick_kernel with upstream's promotable() (raftq_tick_set_voters on a handle with voter masks loaded; include/raftq.h "batched
+// Tick"): tickElection returns with elapsed = 0 when this node is not among the group's voters -- mine = (voters[g] >> self) & 1.
+// A leader is not asked (tickHeartbeat), a non-leader with `mine` set ticks exactly as in tick_kernel -- the same elapsed + 1, the
+// same draw from the same stream -- and a non-leader without it gets elapsed = 0, action 0 and no bit anywhere (an empty mask
+// is an unused slot: covered).  Bitmaps, action bytes and per-wave counts keep tick_kernel's layout: whatever reads them
+// (tick_lists*_kernel, the build kernels) does not know which of the two ran.
+// A lane's four masks are ONE 8-byte load beside its 16-byte elapsed load: 12 B per group where tick_kernel moves 10.  The bit
+// test is folded into `hup` in front of the ballot that decides whether the wave draws at all; no second pass, no LDS.
+// A kernel of its own, tick_tile<1>'s text restated, not a flag of tick_tile: the parents (tick_kernel, tick_set_kernel) keep
+// their assembly (profiles/r13/isa_unchanged.txt).
+static __global__ __launch_bounds__(kBlock) void tick_voters_kernel(TickArgs a, const uint16_t* __restrict__ voters /* [ld] */, uint32_t self) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint64_t key = tick_key(a.seed, a.tick_no);  // wave-uniform
+  const uint64_t blk = blockIdx.x;
+  const uint64_t g = (blk * kBlock + tid) * 4;
+  const uint32_t roles = ldg<false>(reinterpret_cast<const uint32_t*>(a.role + g));
+  const u32x4 el = ldg<false>(reinterpret_cast<const u32x4*>(a.elapsed + g));
+  const uint64_t vm = ldg<false>(reinterpret_cast<const uint64_t*>(voters + g));  // (padding groups hold 0: they never act anyway)
+  uint32_t e[4] = {el.x, el.y, el.z, el.w};
+  uint32_t acts = 0;
+  uint32_t n_hup = 0, n_beat = 0;  // wave-uniform
+  uint64_t hb[4], bb[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint32_t role = (roles >> (8 * k)) & 0xffu;
+    const bool valid = g + k < a.n_groups;
+    const bool mine = (((uint32_t)(vm >> (16 * k)) >> self) & 1u) != 0;
+    const bool idle = role != 2u && !mine;  // tickElection: `if !r.promotable() { r.elapsed = 0; return }`
+    uint32_t v = e[k] + 1;
+    const bool beat = role == 2u && v >= a.heartbeat_tick;
+    const int64_t d = (int64_t)v - (int64_t)a.election_tick;
+    bool hup = role != 2u && mine && d >= 0;
+    if (__ballot(hup) != 0) hup = hup && d > (int64_t)tick_mod(tick_rand(key, (uint32_t)g + k), a.election_tick, a.et_magic);
+    const uint32_t act = !valid ? 0u : (hup ? 1u : (beat ? 2u : 0u));
+    e[k] = !valid ? e[k] : ((act || idle) ? 0u : v);
+    acts |= act << (8 * k);
+    hb[k] = __ballot(act == 1u);
+    bb[k] = __ballot(act == 2u);
+    n_hup += __popcll(hb[k]);
+    n_beat += __popcll(bb[k]);
+  }
+  u32x4 out;
+  out.x = e[0]; out.y = e[1]; out.z = e[2]; out.w = e[3];
+  stg<false>(reinterpret_cast<u32x4*>(a.elapsed + g), out);
+  stg<false>(reinterpret_cast<uint32_t*>(a.action + g), acts);
+  tick_chunk_out(a, blk * kWaves + wave, lane, hb, bb, n_hup, n_beat);
+}
+
 // The set dispatch at the sweep's access shape: a WAVE owns whole 1,024-group blocks -- the four
 // 256-group chunks tick_tile gives to four waves -- so that every global access of a lane is 16 bytes and every wave
 // instruction 1 KB: ONE 16-byte role load and ONE 16-byte action store per lane for the block's 1,024 groups (16 groups per

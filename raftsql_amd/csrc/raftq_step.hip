@@ -92,8 +92,8 @@ int ensure_mirror(raftq_t* h) {
 }
 
 }  // namespace
-int raftq_detail::node_records_of(raftq_t* h, const char* who, raftqk::NodeArrays* out) {
-  if (int rc = raftq_detail::refuse_voters(h, who)) return rc;
+int raftq_detail::node_records_of(raftq_t* h, const char* who, raftqk::NodeArrays* out, bool tick_rounds) {
+  if (int rc = raftq_detail::refuse_voters(h, who, false, tick_rounds)) return rc;
   if (int rc = ensure_node_state(h)) return rc;
   if (int rc = ensure_mirror(h)) return rc;
   *out = node_arrays(h);

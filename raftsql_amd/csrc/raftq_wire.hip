@@ -43,6 +43,7 @@ enum : uint32_t {
   kPinRefused = 1,  // records refused (encoders), malformed frames (raftq_wire_decode*); raftq_wal_decode: the running CRC
   kPinThird = 2,    // the chain's last CRC (WAL encoders), wide records (the narrow decode forms)
   kPinGaveUp = 3,   // streaming kernels only: a look-back waited a second and gave up (tile_ctl_check)
+  kPinMembers = 4,  // behind kPinCall only: the frames raftq_tick_frames / raftq_tick_elect_frames built for members (members_tail_kernel)
 };
 
 size_t align256(size_t x) { return (x + 255) / 256 * 256; }
@@ -745,6 +746,19 @@ int raftq_detail::respond_finish(raftq_t* h, const RespPlan& p, raftq_wire_count
 
 // ---- raftq_tick_frames ------------------------------------------------------------------------------------------------
 namespace {
+// Rounds over each group's own members (raftq_tick_set_voters with masks loaded; raftq_beat_kernels.hpp): the twins add the frames
+// they built for members to the fifth word of wire_flags, zeroed here in the same submission in front of them ...
+unsigned long long* members_word(raftq_t* h) { return h->wire_flags + 4; }
+int members_begin(raftq_t* h) {
+  HIPCHK(h, hipMemsetAsync(members_word(h), 0, 8, h->stream));
+  return RAFTQ_OK;
+}
+// ... and behind the encoder the sum goes to the pinned block, where the host reads it beside the encoder's totals
+int members_end(raftq_t* h) {
+  hipLaunchKernelGGL(members_tail_kernel, dim3(1), dim3(64), 0, h->stream, members_word(h), h->wire_pin_d + kPinCall + kPinMembers);
+  HIPCHK(h, hipGetLastError());
+  return RAFTQ_OK;
+}
 // the marshal of the heartbeats: as resp_marshal_call, the records go into the scratch behind an empty feed
 StreamCall beat_marshal_call(uint64_t n_max, uint64_t cap) {
   StreamCall sc;
@@ -785,7 +799,8 @@ extern "C" int raftq_tick_frames(raftq_t* h, unsigned flags, uint64_t hup_cap, u
   // every allocation before the tick kernel: the records (and, where something other than Step wrote the dense arrays, their
   // refresh), the Tick's lists, the encoder's control block, scratch and output buffer
   NodeArrays na;
-  if (int rc = raftq_detail::node_records_of(h, who, &na)) return rc;
+  if (int rc = raftq_detail::node_records_of(h, who, &na, true)) return rc;
+  const bool members = raftq_detail::masked_tick(h);  // the round goes to each group's own members (beat_build_voters_kernel)
   raftq_detail::TickLists tl;
   if (int rc = raftq_detail::tick_lists_prepare(h, who, flags, hup_cap, beat_cap, &tl)) return rc;
   const uint64_t enc_cap = n_max * RAFTQ_RESPOND_FRAME_MAX;  // what the encoder may write: never more than the worst case
@@ -796,16 +811,26 @@ extern "C" int raftq_tick_frames(raftq_t* h, unsigned flags, uint64_t hup_cap, u
   if (int rc = raftq_detail::tick_lists_enqueue(h, &tl)) return rc;
   if (n_max != 0) {
     const uint64_t nw = h->gpad / 256;
+    const dim3 grid((unsigned)((nw + kWaves - 1) / kWaves));
     BeatArgs ba{(const uint64_t*)h->beat_bits, (const uint4*)h->tick_partials, nw, tl.off_beat, (const uint64_t*)h->d_total, na.rec, h->G, h->N,
                 h->self_peer, beat_cap, (WireMsg*)sc.in.seg[0].dst};
-    hipLaunchKernelGGL(beat_build_kernel, dim3((unsigned)((nw + kWaves - 1) / kWaves)), dim3(kBlock), 0, h->stream, ba);
+    if (members) {
+      if (int rc = members_begin(h)) return rc;
+      hipLaunchKernelGGL(beat_build_voters_kernel, grid, dim3(kBlock), 0, h->stream, ba, (const uint16_t*)h->voters, members_word(h));
+    } else {
+      hipLaunchKernelGGL(beat_build_kernel, grid, dim3(kBlock), 0, h->stream, ba);
+    }
     HIPCHK(h, hipGetLastError());
     if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, n_max, (uint64_t)0, (uint64_t)0, (uint8_t*)h->wire_out.d, (uint8_t*)v_out, enc_cap,
                                (uint64_t*)v_off, sc.ctl, h->wire_pin_d + kPinCall, (const unsigned int*)nullptr, 0u))
       return rc;
+    if (members)
+      if (int rc = members_end(h)) return rc;
   }
   if (int rc = raftq_detail::tick_lists_finish(h, who, tl, n_hup, n_beat)) return rc;
-  const uint64_t n_built = std::min(*n_beat, beat_cap), frames = n_built * slices;
+  const uint64_t n_built = std::min(*n_beat, beat_cap);
+  // the frames that have bytes: every slot of the section, or -- over members -- what the build kernel counted
+  const uint64_t frames = !members ? n_built * slices : n_max != 0 ? h->wire_pin[kPinCall + kPinMembers] : 0;
   uint64_t at = 0;
   for (uint32_t p = 0; p <= h->N; ++p) {
     peer_off[p] = at;
@@ -815,7 +840,8 @@ extern "C" int raftq_tick_frames(raftq_t* h, unsigned flags, uint64_t hup_cap, u
   if (n_max != 0) {
     if (int rc = tile_ctl_check(h, who, kPinCall)) return rc;
     bytes = h->wire_pin[kPinCall + kPinTotal];
-    // every record past the last frame is a filler the encoder refuses; any other refusal, or bytes beyond the bound, is a bug here
+    // every record past the last frame is a filler the encoder refuses, and so is -- over members -- every slot of a peer that is
+    // no member of its group; any other refusal, or bytes beyond the bound, is a bug here
     if (h->wire_pin[kPinCall + kPinRefused] != n_max - frames || bytes > enc_cap)
       return fail(h, RAFTQ_EHIP, std::string(who) + ": the marshal of the heartbeats disagrees with their layout; the output is not valid");
   } else if (frame_off) {
@@ -862,7 +888,8 @@ extern "C" int raftq_tick_elect_frames(raftq_t* h, unsigned flags, uint64_t hup_
   // every allocation before the tick kernel: the records (and, where something other than Step wrote the dense arrays, their
   // refresh), the Tick's lists, the encoder's control block, scratch and output buffer
   NodeArrays na;
-  if (int rc = raftq_detail::node_records_of(h, who, &na)) return rc;
+  if (int rc = raftq_detail::node_records_of(h, who, &na, true)) return rc;
+  const bool members = raftq_detail::masked_tick(h);  // both rounds go to each group's own members (the *_voters_kernel twins)
   raftq_detail::TickLists tl;
   if (int rc = raftq_detail::tick_lists_prepare(h, who, flags, hup_cap, beat_cap, &tl)) return rc;
   const uint64_t enc_cap = n_max * RAFTQ_RESPOND_FRAME_MAX;  // what the encoder may write: never more than the worst case
@@ -876,24 +903,32 @@ extern "C" int raftq_tick_elect_frames(raftq_t* h, unsigned flags, uint64_t hup_
     const uint64_t nw = h->gpad / 256;
     const dim3 grid((unsigned)((nw + kWaves - 1) / kWaves));
     WireMsg* const enc = (WireMsg*)sc.in.seg[0].dst;
+    if (members)
+      if (int rc = members_begin(h)) return rc;
     if (beat_cap != 0) {
       BeatArgs ba{(const uint64_t*)h->beat_bits, (const uint4*)h->tick_partials, nw, tl.off_beat, (const uint64_t*)h->d_total, na.rec, h->G, h->N,
                   h->self_peer, beat_cap, enc};
-      hipLaunchKernelGGL(beat_build_kernel, grid, dim3(kBlock), 0, h->stream, ba);
+      if (members) hipLaunchKernelGGL(beat_build_voters_kernel, grid, dim3(kBlock), 0, h->stream, ba, (const uint16_t*)h->voters, members_word(h));
+      else hipLaunchKernelGGL(beat_build_kernel, grid, dim3(kBlock), 0, h->stream, ba);
     }
     // (hup_cap == 0: the fillers behind beat_cap * (N - 1) are beat_build_kernel's own -- the call is raftq_tick_frames)
     if (hup_cap != 0) {
       ElectArgs ea{(const uint64_t*)h->hup_bits, (const uint4*)h->tick_partials, nw, tl.off_h, (const uint64_t*)h->d_total, na, hup_cap, beat_cap,
                    (StepOutS*)v_camp, enc};
-      hipLaunchKernelGGL(elect_build_kernel, grid, dim3(kBlock), 0, h->stream, ea);
+      if (members) hipLaunchKernelGGL(elect_build_voters_kernel, grid, dim3(kBlock), 0, h->stream, ea, (const uint16_t*)h->voters, members_word(h));
+      else hipLaunchKernelGGL(elect_build_kernel, grid, dim3(kBlock), 0, h->stream, ea);
     }
     HIPCHK(h, hipGetLastError());
     if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, n_max, (uint64_t)0, (uint64_t)0, (uint8_t*)h->wire_out.d, (uint8_t*)v_out, enc_cap,
                                (uint64_t*)v_off, sc.ctl, h->wire_pin_d + kPinCall, (const unsigned int*)nullptr, 0u))
       return rc;
+    if (members)
+      if (int rc = members_end(h)) return rc;
   }
   if (int rc = raftq_detail::tick_lists_finish(h, who, tl, n_hup, n_beat)) return rc;
-  const uint64_t n_bb = std::min(*n_beat, beat_cap), n_vb = std::min(*n_hup, hup_cap), frames = (n_bb + n_vb) * slices;
+  const uint64_t n_bb = std::min(*n_beat, beat_cap), n_vb = std::min(*n_hup, hup_cap);
+  // the frames that have bytes: every slot of both sections, or -- over members -- what the build kernels counted
+  const uint64_t frames = !members ? (n_bb + n_vb) * slices : n_max != 0 ? h->wire_pin[kPinCall + kPinMembers] : 0;
   uint64_t at = 0;
   for (uint32_t p = 0; p <= h->N; ++p) {  // the heartbeat section's slices, then the vote section's
     peer_off[p] = at;
@@ -907,7 +942,8 @@ extern "C" int raftq_tick_elect_frames(raftq_t* h, unsigned flags, uint64_t hup_
   if (n_max != 0) {
     if (int rc = tile_ctl_check(h, who, kPinCall)) return rc;
     bytes = h->wire_pin[kPinCall + kPinTotal];
-    // every record past the last frame is a filler the encoder refuses; any other refusal, or bytes beyond the bound, is a bug here
+    // every record past the last frame is a filler the encoder refuses, and so is -- over members -- every slot of a peer that is
+    // not asked; any other refusal, or bytes beyond the bound, is a bug here
     if (h->wire_pin[kPinCall + kPinRefused] != n_max - frames || bytes > enc_cap)
       return fail(h, RAFTQ_EHIP, std::string(who) + ": the marshal of the heartbeats and votes disagrees with their layout; the output is not valid");
   } else if (frame_off) {

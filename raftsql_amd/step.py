@@ -142,6 +142,12 @@ class NodeEngine(QuorumEngine):
         group's own voters instead of being refused; a property of the handle (no batch may be in flight)"""
         self._chk(self._lib.raftq_step_set_voters(self._h, int(on)))
 
+    def set_tick_voters(self, on=True) -> None:
+        """raftq_tick_set_voters: with voter masks loaded the Tick applies promotable() (a group in which this node does not vote
+        raises no MsgHup, its timer stays 0) and tick_frames / tick_elect_frames go to each group's own members instead of being
+        refused; a property of the handle, independent of set_step_voters (no batch may be in flight)"""
+        self._chk(self._lib.raftq_tick_set_voters(self._h, int(on)))
+
     def load_node(self, term=None, vote=None, lead=None, last_index=None, last_term=None) -> None:
         def arr(x, dt):
             if x is None:

@@ -261,7 +261,9 @@ class WireEngine(NodeEngine):
         and marshalled on the device -- one submission, one wait.  out: uint8 of at least respond_cap(beat_cap) bytes (cap: what the
         call is told instead of len(out)); frame_off: uint64 [beat_cap * (N - 1) + 1] or None; peer_off: uint64 [N + 1]; all page-locked
         (engine.pinned_empty).  -> (heartbeat bytes (a view of out), frame_off[:n_frames + 1] | None, peer_off, counts, hups view u32,
-        n_hup, beats view u32 | bitmap view u64, n_beat); the list views are the library's memory, valid until the next Tick call"""
+        n_hup, beats view u32 | bitmap view u64, n_beat); the list views are the library's memory, valid until the next Tick call.
+        With voter masks loaded and set_tick_voters on, the frames go to each group's members only: frame_off stays positional (one
+        entry per slot, a non-member's slot has zero length) and counts.n_msgs is the number of frames that have bytes"""
         assert peer_off.dtype == np.uint64 and len(peer_off) >= self.n_peers + 1
         assert out is None or out.dtype == np.uint8
         assert frame_off is None or (frame_off.dtype == np.uint64 and len(frame_off) >= int(beat_cap) * (self.n_peers - 1) + 1)
@@ -282,7 +284,7 @@ class WireEngine(NodeEngine):
 
         hups = view(ph, lh.value, np.uint32)
         second = view(pm, lm.value, np.uint64) if beat_bitmap else view(pb, lb.value, np.uint32)
-        n_frames = int(c.n_msgs)
+        n_frames = int(peer_off[self.n_peers])  # the slots: c.n_msgs of them have bytes (all, unless the round went to members only)
         return (out[: int(c.bytes)] if out is not None else np.zeros(0, np.uint8), frame_off[: n_frames + 1] if frame_off is not None else None,
                 peer_off[: self.n_peers + 1], c, hups, int(nh.value), second, int(nb.value))
 
@@ -319,7 +321,7 @@ class WireEngine(NodeEngine):
 
         hups = view(ph, lh.value, np.uint32)
         second = view(pm, lm.value, np.uint64) if beat_bitmap else view(pb, lb.value, np.uint32)
-        n_frames = int(c.n_msgs)
+        n_frames = int(peer_off[2 * self.n_peers + 1])  # the slots of both sections: c.n_msgs of them have bytes
         n_vb = min(int(nh.value), int(hup_cap))
         return (out[: int(c.bytes)] if out is not None else np.zeros(0, np.uint8), frame_off[: n_frames + 1] if frame_off is not None else None,
                 peer_off[: 2 * (self.n_peers + 1)], c, camp[:n_vb] if camp is not None else np.zeros(0, OUT_S_DT), hups, int(nh.value), second,
