@@ -339,6 +339,19 @@ func (e *Engine) StepFramesPacked(stream []byte, frameOff []uint64, tailAppends 
 	return uint64(c.n_ents), uint64(c.n_malformed), uint64(nw), e.err(rc)
 }
 
+// SetBcastVoters opts the engine in to (or out of) the two device-built broadcasts over each group's own members: with voter masks
+// loaded, StepFramesRespond's commit broadcast and ProposeFrames' MsgApps then go to the group's members only instead of the calls
+// returning ErrState (include/raftq_wire.h: StepFramesRespond stays compact; ProposeFrames stays positional, a non-member's slot is a
+// frame of zero length, and a record whose append would move the commit index is refused).  Independent of SetStepVoters and
+// SetTickVoters; no batch may be in flight.
+func (e *Engine) SetBcastVoters(on bool) error {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	return e.err(C.raftq_bcast_set_voters(e.h, v))
+}
+
 // StepFramesRespond is StepFrames plus the messages its results call for, built and marshalled on the device
 // (raftq_step_frames_respond; raft.go:268-270 -> :227-230): MsgAppResp / MsgVoteResp / MsgHeartbeatResp to the senders and the
 // commit broadcast of a group whose at-tail bit is set (atTail: one bit per group, nil = none).  out receives rafthttp frames,

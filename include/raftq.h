@@ -190,10 +190,13 @@ int raftq_apply_term_deltas(raftq_t* h, const raftq_term_delta_t* d, uint64_t n)
  * starts on the device have a switch of their own, raftq_tick_set_voters(h, 1) ("batched Tick" below): promotable() in
  * raftq_tick / raftq_tick_collect / raftq_tick_collect_lists, and raftq_tick_frames / raftq_tick_elect_frames (raftq_wire.h)
  * over each group's own members; without it Tick reads no mask and those two calls refuse a masked handle (RAFTQ_ESTATE, the
+ * default).  The other two calls that build a broadcast on the device, raftq_step_frames_respond (the commit broadcast) and
+ * raftq_propose_frames (bcastAppend), have the third switch, raftq_bcast_set_voters(h, 1) (raftq_wire.h): their MsgApps then go
+ * to each group's own members, and a proposal whose append would move the commit index -- a one-voter group, a membership that
+ * shrank -- is refused and pointed to raftq_apply_log_deltas; without it both refuse a masked handle (RAFTQ_ESTATE, the
  * default).  Not built, and refused with RAFTQ_ESTATE and a message that says so whatever the switches say: a sweep set with a
- * masked member (raftq_set_create; raftq_load_voters / raftq_apply_voter_deltas on a member), and raftq_step_frames_respond and
- * raftq_propose_frames, whose frames go to N - 1 slots, not to a membership.  A handle with no masks loaded is exactly the
- * handle it always was, kernels included. */
+ * masked member (raftq_set_create; raftq_load_voters / raftq_apply_voter_deltas on a member).  A handle with no masks loaded is
+ * exactly the handle it always was, kernels included. */
 typedef struct raftq_voter_delta {
   uint64_t group;
   uint16_t voters; /* the group's new mask */

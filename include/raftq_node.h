@@ -51,9 +51,10 @@
  * through the node (the quorum arithmetic over a group's own members exists in
  * the sweep, raftq.h "per-group voter sets", and in Step for a handle that
  * opted in, raftq_step_set_voters, and in Tick and the rounds it starts for a
- * handle that opted in, raftq_tick_set_voters; a node never loads masks and
- * turns neither switch on: every slot votes, every timer runs, and its
- * device-built broadcasts go to N - 1 slots), joint consensus, the inflight window.  The log lives in host memory, like the reference's
+ * handle that opted in, raftq_tick_set_voters, and in the commit broadcast
+ * and bcastAppend for a handle that opted in, raftq_bcast_set_voters; a node
+ * never loads masks and turns none of the switches on: every slot votes, every
+ * timer runs, and its device-built broadcasts go to N - 1 slots), joint consensus, the inflight window.  The log lives in host memory, like the reference's
  * raft.MemoryStorage (raft.go:70).
  *
  * Thread-safety: propose / deliver / tick / recv / poll / status from any

@@ -96,11 +96,13 @@ int raftq_step_set_msg_flags(raftq_t* h, int on);
  *                  grant is recorded but not counted, so the result is RAFTQ_OUT_CAMPAIGN.
  *
  * What stays refused (RAFTQ_ESTATE, "voter masks" in the text) whatever this switch says: raftq_step_frames_respond,
- * raftq_propose_frames -- always -- and raftq_tick_frames, raftq_tick_elect_frames unless raftq_tick_set_voters (raftq.h
- * "batched Tick") opted the handle in, which sends their rounds to each group's own members.  The broadcasts of the first
- * two go to N - 1 slots, not to a membership, and the proposal path relies on "maybeCommit cannot move with more than one
- * peer", which a one-voter group breaks.  Sweep sets with a masked member and raftq_node (which never loads masks) are as
- * before. */
+ * raftq_propose_frames unless raftq_bcast_set_voters (raftq_wire.h) opted the handle in, and raftq_tick_frames,
+ * raftq_tick_elect_frames unless raftq_tick_set_voters (raftq.h "batched Tick") did: each of those switches sends its calls'
+ * broadcasts to each group's own members.  Without them the broadcasts go to N - 1 slots, not to a membership, and the
+ * proposal path relies on "maybeCommit cannot move with more than one peer", which a one-voter group breaks -- over members
+ * raftq_propose_frames refuses a record whose append would move the commit index.  raftq_step_frames_respond with
+ * raftq_bcast_set_voters on runs the rules above whether or not this switch is on.  Sweep sets with a masked member and
+ * raftq_node (which never loads masks) are as before. */
 int raftq_step_set_voters(raftq_t* h, int on);
 
 /* raftq_msg_t._pad[1] once the handle opted in.  RAFTQ_MSGF_ENTRIES on a MsgApp: the caller says what the message carries -- the low 32 bits of

@@ -270,7 +270,18 @@ int raftq_step_frames_packed(raftq_t* h, const void* stream, uint64_t nbytes, co
  * one byte each, term / log_term / index / commit / group of ten, reject_hint 0, the empty snapshot): below it, or with any array
  * not page-locked and 16-byte aligned (at_tail, out, resp_off and peer_off included), or N < 2, RAFTQ_EINVAL before anything
  * is enqueued -- nothing is applied.  The response records are written into the encoder's input in HBM; they never exist in
- * host memory. */
+ * host memory.
+ *
+ * Over each group's own members (raftq_bcast_set_voters(h, 1), below, on a handle with voter masks loaded): Step is the masked
+ * Step's (raftq_step.h raftq_step_set_voters, whether or not that switch is on), and ONLY the commit broadcast changes -- it is
+ * one empty MsgApp to every slot p != self whose bit is set in voters[g]: upstream's bcastAppend ranges over r.prs.  The
+ * responses to a sender (MsgAppResp, MsgVoteResp, MsgHeartbeatResp) go to whoever sent, member or not, as upstream answers.
+ * at_tail then reads "every MEMBER's Progress.Next is lastIndex + 1".  The layout stays COMPACT: peer-major, result order inside
+ * a slice, fillers only behind the total; peer_off, resp_off and resp_counts keep their meaning.  A committing ack in a group
+ * with no member other than self is flagged RAFTQ_OUTF_ANSWERED and builds ZERO frames -- the host would have sent to nobody
+ * either.  The device-answered prefix, the clearing of at_tail bits, stalls and the replay are untouched.  With the switch on
+ * and no masks loaded the call is what it always was.  RAFTQ_ESTATE, before anything is applied: voter masks loaded on a handle
+ * that did not opt in with raftq_bcast_set_voters -- whatever raftq_step_set_voters and raftq_tick_set_voters say. */
 #define RAFTQ_OUTF_ANSWERED 0x10u /* result flag: the messages this result calls for are in `out` (built on the device) */
 #define RAFTQ_RESPOND_FRAME_MAX 83u
 int raftq_step_frames_respond(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off /*[n+1]*/, uint64_t n, int tail_appends,
@@ -298,7 +309,28 @@ int raftq_step_frames_respond(raftq_t* h, const void* stream, uint64_t nbytes, c
  * Byte for byte what raftq_wire_encode makes of the same messages built on the host (tests/test_wire_gpu.py::
  * test_propose_frames_*).  Every array must be page-locked and 16-byte aligned (RAFTQ_EINVAL otherwise), no Step batch may be
  * in flight.  A call that fails has applied nothing (a validation kernel runs first); `out` is unspecified after a refusal, as
- * with the streaming raftq_wire_encode.  raftq_node's turn is raftq_step_frames + this. */
+ * with the streaming raftq_wire_encode.  raftq_node's turn is raftq_step_frames + this.
+ *
+ * Over each group's own members (raftq_bcast_set_voters(h, 1), below, on a handle with voter masks loaded): bcastAppend ranges
+ * over r.prs -- of the N - 1 MsgApps of a record only those to a slot p whose bit is set in voters[g] exist.  The layout stays
+ * POSITIONAL, as raftq_tick_frames': (N - 1) runs of n_props slots where they always were, frame_off keeps its n_msgs +
+ * (N - 1) * n_props + 1 entries, and the slot of a peer that is no member of its group is a frame of ZERO length, frame_off[k + 1]
+ * == frame_off[k].  The bytes are what raftq_wire_encode makes of msgs[] and the member MsgApps alone.  counts->n_msgs is n_msgs
+ * plus the number of frames that have bytes; the entry headers are written for every record.  The state changes are what they
+ * always were.  Two more records fail the call, nothing applied, as the others do:
+ *   - this node is no member of its group: self's bit is clear in voters[g].  (Upstream v2.2 would dereference a missing
+ *     Progress.  CHOICE: refuse.)
+ *   - its append would move the commit index.  Without masks maybeCommit cannot move on an append -- the leader's own Match is the
+ *     largest, the quorum-th largest is somebody else's.  Over members it can: a ONE-VOTER group commits on its own append, and
+ *     under the 2015-era removeNode, which does not call maybeCommit, so does a group whose membership SHRANK since its last
+ *     acknowledgement (N = 5, Match 10, 8, 5, 5, 5, committed 5, voters {0, 1, 2}: the append commits 8).  Evaluated exactly: with
+ *     Match[self] raised to lastIndex + n_ents, the masked maybeCommit including the current-term gate would return true.  This
+ *     call has no channel for a commit; raftq_apply_log_deltas has.  The recipe: a caller that loaded the masks knows its
+ *     one-voter groups and appends for them with raftq_apply_log_deltas; after a voter delta that shrinks a led group, a tail
+ *     report with the UNCHANGED tail runs maybeCommit over the new membership and reports the commit.  Once the commit is
+ *     settled maybeCommit cannot move on an append -- self is a voter and holds the largest Match -- and the proposal passes.
+ * RAFTQ_ESTATE, before anything is applied: voter masks loaded on a handle that did not opt in with raftq_bcast_set_voters --
+ * whatever raftq_step_set_voters and raftq_tick_set_voters say. */
 typedef struct raftq_prop {
   uint64_t group;
   uint32_t ent_first; /* into prop_ents[] */
@@ -313,6 +345,18 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
                          const raftq_wire_msg_t* msgs, uint64_t n_msgs, const raftq_wire_ent_t* ents, uint64_t n_ents, const void* pool,
                          uint64_t pool_bytes, void* out, uint64_t cap, uint64_t* frame_off /*[n_msgs + (N-1) n_props + 1]|NULL*/,
                          raftq_wire_counts_t* counts /*|NULL*/);
+
+/* The switch of the two calls above: raftq_step_frames_respond's commit broadcast and raftq_propose_frames' bcastAppend over each
+ * group's own members ("per-group voter sets", raftq.h).  0, the default: both calls refuse a handle with voter masks loaded
+ * (RAFTQ_ESTATE, "voter masks" in the text), whatever raftq_step_set_voters and raftq_tick_set_voters say.  1: both run over
+ * voters[g], as their paragraphs "Over each group's own members" say.  Anything but 0 or 1 is RAFTQ_EINVAL; the handle must be
+ * idle (RAFTQ_ESTATE with a Step batch in flight); a NULL handle returns an error without touching a device.  A property of the
+ * handle, like the other two switches: raftq_clone_state does not copy it and raftq_load_voters(h, NULL) does not clear it; with
+ * no masks loaded the handle launches exactly the kernels it always did, whatever the switch says.  Independent of
+ * raftq_tick_set_voters and of raftq_step_set_voters: raftq_step_frames_respond with this switch on runs the masked Step on its
+ * own authority, as raftq_tick_elect_frames does.  With all three switches on every frame a node builds on the device goes to a
+ * group's members; what remains of conf changes is host work (ConfChange entries through raftq_node: not built). */
+int raftq_bcast_set_voters(raftq_t* h, int on);
 
 /* A node's heartbeat round (raft.go:223-224 -> :230: rc.node.Tick() -> tickHeartbeat -> Step(MsgBeat) -> bcastHeartbeat ->
  * rc.transport.Send) as ONE submission with one wait: the Tick, its lists, and the heartbeats the Tick calls for, built and

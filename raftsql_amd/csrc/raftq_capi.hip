@@ -710,9 +710,15 @@ static int voters_not_in_set(raftq_t* h, const char* who) {
   return fail(h, RAFTQ_ESTATE, std::string(who) + ": the handle is a member of a sweep set, whose dispatches count every slot "
                                                   "(voter masks on set members are out of scope)");
 }
-int raftq_detail::refuse_voters(raftq_t* h, const char* who, bool step_family, bool tick_rounds) {
+int raftq_detail::refuse_voters(raftq_t* h, const char* who, bool step_family, bool tick_rounds, bool bcast) {
   if (!h || !h->voters) return RAFTQ_OK;
   if (tick_rounds && h->tick_voters) return RAFTQ_OK;
+  if (bcast) {
+    if (h->bcast_voters) return RAFTQ_OK;
+    return fail(h, RAFTQ_ESTATE, std::string(who) + ": the handle has voter masks loaded and did not opt in with raftq_bcast_set_voters; its broadcast "
+                                                    "would go to N - 1 slots, not to a group's membership (whatever raftq_step_set_voters and "
+                                                    "raftq_tick_set_voters say)");
+  }
   if (h->step_voters) {
     if (step_family) return RAFTQ_OK;
     return fail(h, RAFTQ_ESTATE, std::string(who) + ": the handle has voter masks loaded; the broadcasts built on the device go to N - 1 slots, "
@@ -1121,6 +1127,15 @@ int raftq_tick_set_voters(raftq_t* h, int on) {
     return fail(h, RAFTQ_EINVAL, "raftq_tick_set_voters: 0 (Tick asks nobody, the device-built rounds refuse a masked handle) or 1 (promotable() in Tick, "
                                  "rounds over each group's own members)");
   h->tick_voters = on == 1;
+  return RAFTQ_OK;
+}
+
+int raftq_bcast_set_voters(raftq_t* h, int on) {
+  if (int rc = use_device_idle(h, "raftq_bcast_set_voters")) return rc;
+  if (on != 0 && on != 1)
+    return fail(h, RAFTQ_EINVAL, "raftq_bcast_set_voters: 0 (raftq_step_frames_respond and raftq_propose_frames refuse a masked handle) or 1 (their "
+                                 "broadcasts go to each group's own members)");
+  h->bcast_voters = on == 1;
   return RAFTQ_OK;
 }
 

@@ -123,6 +123,8 @@ struct raftq {
                                    // the handle: raftq_clone_state and raftq_load_voters(h, NULL) leave it alone)
   bool tick_voters = false;        // raftq_tick_set_voters: with masks loaded Tick runs tick_voters_kernel (promotable()) and the two
                                    // device-built rounds go to each group's own members (the same kind of property as step_voters)
+  bool bcast_voters = false;       // raftq_bcast_set_voters: with masks loaded raftq_step_frames_respond's commit broadcast and
+                                   // raftq_propose_frames' bcastAppend go to each group's own members (the same kind of property)
   int step_walk_mode = 1;          // 1 = lists (default), 0 = always the sorted walk (RAFTQ_STEP_WALK=sort)
   uint32_t step_stalls_in_a_row = 0, step_sorted_left = 0;  // back-off from the list walk under hot-group traffic
   uint64_t step_replays = 0;       // batches that went through the sorted path after a stall
@@ -263,11 +265,15 @@ int use_device_idle(raftq_t* h, const char* who);  // + no Step batch in flight 
 // RAFTQ_ESTATE for a handle with voter masks loaded.  step_family (raftq_step_batch / _submit* / _frames / _frames_packed,
 // raftq_apply_log_deltas*): let through once the handle opted in (raftq_step_set_voters) -- those calls then run over each group's
 // own voters.  tick_rounds (raftq_tick_frames, raftq_tick_elect_frames): let through once the handle opted in to
-// raftq_tick_set_voters -- their rounds then go to each group's own members.  Everything else (the other device-built broadcasts:
-// their frames go to N - 1 slots, not to a membership) is always refused.
-int refuse_voters(raftq_t* h, const char* who, bool step_family = false, bool tick_rounds = false);
+// raftq_tick_set_voters -- their rounds then go to each group's own members.  bcast (raftq_step_frames_respond,
+// raftq_propose_frames): let through once the handle opted in to raftq_bcast_set_voters -- their broadcasts then go to each group's
+// own members.  Each of the three switches opens its own calls and no others.
+int refuse_voters(raftq_t* h, const char* who, bool step_family = false, bool tick_rounds = false, bool bcast = false);
 // raftq_tick_set_voters on a handle with masks loaded: every Tick launch is tick_voters_kernel's, the rounds are the twins'
 inline bool masked_tick(const raftq_t* h) { return h->voters != nullptr && h->tick_voters; }
+// raftq_bcast_set_voters on a handle with masks loaded: raftq_step_frames_respond walks with the masked Node and lays its answers
+// out with the resp_*_voters_kernel twins, raftq_propose_frames runs propose_check_voters_kernel / propose_apply_voters_kernel
+inline bool masked_bcast(const raftq_t* h) { return h->voters != nullptr && h->bcast_voters; }
 int self_max_check(raftq_t* h);                 // the self-max word re-derived from the rows for h->self_peer (enqueued)
 int narrow_build(raftq_t* h);                   // the narrow mirror and its word re-derived from the rows (enqueued)
 int ensure_staging(raftq_t* h, size_t bytes);   // pinned, device-mapped staging (term deltas, campaign lists, log deltas)
@@ -318,8 +324,9 @@ int tick_lists_prepare(raftq_t* h, const char* who, unsigned flags, uint64_t hup
 int tick_lists_enqueue(raftq_t* h, TickLists* tl);
 int tick_lists_finish(raftq_t* h, const char* who, const TickLists& tl, uint64_t* n_hup, uint64_t* n_beat);
 // raftq_step.hip, for raftq_tick_frames: the handle's records exist and are fresh (ensure_mirror), voter masks refused --
-// tick_rounds: unless the handle opted in to raftq_tick_set_voters (the two tick calls pass true)
-int node_records_of(raftq_t* h, const char* who, raftqk::NodeArrays* out, bool tick_rounds = false);
+// tick_rounds: unless the handle opted in to raftq_tick_set_voters (the two tick calls pass true); bcast: unless it opted in to
+// raftq_bcast_set_voters (raftq_propose_frames passes true)
+int node_records_of(raftq_t* h, const char* who, raftqk::NodeArrays* out, bool tick_rounds = false, bool bcast = false);
 int respond_pass_ok(raftq_t* h);  // a pass of the marshal whose totals are about to be replaced (a stalled batch's first): it did not give up
 // The wait that ends a call whose results the kernels wrote into page-locked memory themselves (the streaming codecs,
 // raftq_step_frames): a one-thread kernel raises the handle's completion word behind everything enqueued so far and the host

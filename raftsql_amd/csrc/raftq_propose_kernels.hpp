@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "raftq_beat_kernels.hpp"
 #include "raftq_step_kernels.hpp"
 #include "raftq_wire_parse.hpp"
 
@@ -114,6 +115,120 @@ static __global__ __launch_bounds__(kBlock) void propose_apply_kernel(NodeArrays
     msgs_out[(uint64_t)run * n + i] = m;
     ++run;
   }
+}
+
+// ---- proposals over each group's own members (raftq_bcast_set_voters on a handle with voter masks loaded) ----------------------
+// Twins of the two kernels above, the masks as a last argument behind the parents'.  Kernels of their own: the parents keep
+// their assembly (profiles/r14/isa_unchanged.txt).
+constexpr uint32_t kPropNoMember = 7, kPropCommits = 8;
+
+// propose_check_kernel plus two reasons, both read off the masked Node loaded from the record line the check touches anyway
+// (its lst_cnt is the "seen" mark):
+//   kPropNoMember  self's bit is clear in voters[g].  Upstream v2.2's appendEntry would dereference a missing Progress
+//                  (r.prs[r.id]); CHOICE: refuse.
+//   kPropCommits   apply's sentence "maybeCommit cannot move anything with more than one peer" does not hold over members: a
+//                  one-voter group commits on its own append, and under the 2015-era removeNode (which does not call
+//                  maybeCommit) so does a group whose membership shrank since its last acknowledgement.  Evaluated exactly --
+//                  Match[self] raised to last_index + n_ents as apply will, then the masked maybe_commit() with its current-term
+//                  gate -- on the lane's copy, which is never stored.  The call has no channel for a commit:
+//                  raftq_apply_log_deltas has, and a tail report with the unchanged tail settles the commit first.
+// Both after the six old reasons, so a record sound by the old rules is marked (lst_cnt) whatever the new ones say; a refused
+// call's apply takes every mark off again.
+static __global__ __launch_bounds__(kBlock) void propose_check_voters_kernel(NodeArrays a, const PropRec* __restrict__ props, uint64_t n,
+                                                                             const PropEnt* __restrict__ pe, uint64_t n_pe, uint64_t pool_bytes,
+                                                                             unsigned int* bad, unsigned int stamp, PropRec* __restrict__ props_d,
+                                                                             PropEnt* __restrict__ pe_d, unsigned long long* why,
+                                                                             const uint16_t* __restrict__ voters) {
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  uint32_t reason = 0;
+  if (i < n_pe) {
+    const PropEnt e = pe[i];
+    pe_d[i] = e;
+    if (e.data_len != 0 && (e.data_off > pool_bytes || e.data_len > pool_bytes - e.data_off)) reason = kPropPayload;
+  }
+  if (i < n) {
+    const PropRec p = props[i];
+    props_d[i] = p;
+    if (p.group >= a.n_groups) reason = kPropGroup;
+    else if (p.n_ents == 0 || p.n_ents > kPropMaxEnts) reason = kPropCount;
+    else if ((uint64_t)p.ent_first + p.n_ents > n_pe) reason = kPropRange;
+    else if (a.role[p.group] != kLeader) reason = kPropNotLeader;
+    else if (atomicAdd(&a.rec[p.group].lst_cnt, 1u) != 0) reason = kPropTwice;
+    else {
+      NodeT<true> node(a, p.group, voters);
+      if (((node.vmask >> a.self) & 1u) == 0) reason = kPropNoMember;
+      else {
+        const uint64_t tail = node.last_index + p.n_ents;
+        if (node.match(a.self) < tail) node.set_match(a.self, tail);
+        if (node.maybe_commit()) reason = kPropCommits;
+      }
+    }
+  }
+  if (reason) atomicMax(why, ((unsigned long long)(stamp & 0xffffffu) << 40) | ((unsigned long long)reason << 32) | (uint32_t)i);
+  if (__ballot(reason != 0) != 0 && (threadIdx.x & 63) == 0) atomicExch(bad, stamp);
+}
+
+// propose_apply_kernel over members: the state changes and the entry headers are the parent's; of the N - 1 MsgApps only those
+// to a slot whose bit is set in voters[g] exist.  The encoder's input stays POSITIONAL, as in beat_build_voters_kernel
+// (raftq_beat_kernels.hpp): (N - 1) runs of n records where the parent puts them, and the slot of a peer that is no member of
+// its group holds a filler (to = 0xff), which the encoder counts as refused and gives zero bytes.  The workgroup's member frames
+// are summed and added once to *members (members_add): the host checks `refused == n_dev - member frames`.
+static __global__ __launch_bounds__(kBlock) void propose_apply_voters_kernel(NodeArrays a, const PropRec* __restrict__ props, uint64_t n,
+                                                                             const PropEnt* __restrict__ pe, const unsigned int* __restrict__ bad,
+                                                                             unsigned int stamp, WireMsg* __restrict__ msgs_out, WireEnt* __restrict__ ents_out,
+                                                                             uint32_t ent_base, const uint16_t* __restrict__ voters, unsigned long long* members) {
+  __shared__ uint64_t red[kWaves];
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool refused = *bad == stamp;  // workgroup-uniform
+  uint32_t wrote = 0;
+  if (i < n && refused) {  // the marks of the check come off, nothing else happens
+    const PropRec p = props[i];
+    if (p.group < a.n_groups) a.rec[p.group].lst_cnt = 0;
+  } else if (i < n) {
+    const PropRec p = props[i];
+    NodeT<true> node(a, p.group, voters);
+    const uint64_t old_last = node.last_index, old_term = node.last_term;
+    // appendEntry, as in propose_apply_kernel (the check made sure maybeCommit does not move over this group's members)
+    node.last_index = old_last + p.n_ents;
+    node.last_term = node.term;
+    if (node.match(a.self) < node.last_index) node.set_match(a.self, node.last_index);
+    node.lst_cnt = 0;
+    node.store();
+    for (uint32_t k = 0; k < p.n_ents; ++k) {
+      const PropEnt e = pe[p.ent_first + k];
+      WireEnt w;
+      w.term = node.term;
+      w.index = old_last + 1 + k;
+      w.data_len = e.data_len;
+      w.data_off = e.data_len ? e.data_off : 0;
+      w.type = e.type;
+      ents_out[p.ent_first + k] = w;
+    }
+    // bcastAppend over r.prs
+    WireMsg m;
+    m.group = p.group;
+    m.term = node.term;
+    m.log_term = old_term;
+    m.index = old_last;
+    m.commit = node.committed;
+    m.reject_hint = 0;
+    m.from = a.self;
+    m.type = kMsgApp;
+    m.reject = 0;
+    m.flags = 0;
+    m.ent_first = ent_base + p.ent_first;
+    m.n_ents = p.n_ents;
+    uint32_t run = 0;
+    for (uint32_t to = 0; to < a.n_peers; ++to) {
+      if (to == a.self) continue;
+      const bool member = ((node.vmask >> to) & 1u) != 0;
+      m.to = member ? (uint8_t)to : (uint8_t)0xff;  // (a filler is any record addressed to 0xff, as beat_store's)
+      msgs_out[(uint64_t)run * n + i] = m;
+      wrote += member ? 1u : 0u;
+      ++run;
+    }
+  }
+  members_add(wrote, red, members);
 }
 
 }  // namespace raftqk

@@ -130,4 +130,98 @@ static __global__ __launch_bounds__(kBlock) void resp_scatter_kernel(RespLayout 
   }
 }
 
+// ---- the layout over each group's own members (raftq_bcast_set_voters on a handle with voter masks loaded) ------------------------
+// Twins of (1) and (3); (2) is shared.  One rule changes: the commit broadcast (kind == kMsgApp) goes to slot p only if p's bit
+// is set in voters[group] -- upstream's bcastAppend ranges over r.prs, which IS the membership.  A response to a sender goes to
+// r.to as always, member or not: upstream answers whoever sent.  Everything else is the parents': peer-major, result order inside
+// a slice, fillers only behind the total; a broadcast of a group with no member but self has no frame at all.
+// The mask is a 2-byte gather of the dense `voters` array by the record's group, issued by broadcast records only.  (The walk lane
+// holds the mask in a register and could have written it into the record's `to` / `pad` bytes, which a broadcast does not use;
+// that would have changed NodeT<true>::respond and with it the assembly of the masked walks -- profiles/r14/isa_unchanged.txt
+// keeps them what they were, and the gather costs one 32-byte sector per broadcast.)
+// Kernels of their own, with the masks as an argument behind the parents': RespLayout keeps its members and the parents their
+// kernarg offsets and their assembly.
+
+// the slots result r sends a frame to, as a bit mask (bit p: resp_to's verdict over members)
+__device__ __forceinline__ uint32_t resp_to_voters(const RespRec& r, bool valid, const RespLayout& L, const uint16_t* __restrict__ voters) {
+  if (!valid) return 0u;
+  const uint32_t peers = ((1u << L.n_peers) - 1u) & ~(1u << L.self);
+  const uint32_t want = r.kind == kMsgApp ? (uint32_t)voters[r.group] : (1u << r.to);
+  return want & peers;
+}
+
+// (1) over members
+static __global__ __launch_bounds__(kBlock) void resp_count_voters_kernel(RespLayout L, const uint16_t* __restrict__ voters) {
+  __shared__ uint32_t wc[kWaves][kMaxPeers];
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  RespRec r{};
+  if (i < L.n) r = L.resp[i];
+  const bool valid = i < L.n && r.stamp == L.stamp && r.kind != 0;
+  const uint32_t to = resp_to_voters(r, valid, L, voters);
+#pragma unroll
+  for (uint32_t p = 0; p < (uint32_t)kMaxPeers; ++p) {
+    const uint64_t b = __ballot(((to >> p) & 1u) != 0);
+    if (lane == 0) wc[wave][p] = (uint32_t)__popcll(b);
+  }
+  __syncthreads();
+  if (threadIdx.x < (uint32_t)kMaxPeers) {
+    uint32_t t = 0;
+    for (int w = 0; w < kWaves; ++w) t += wc[w][threadIdx.x];
+    L.blk_cnt[(uint64_t)blockIdx.x * kMaxPeers + threadIdx.x] = t;
+  }
+}
+
+// (3) over members
+static __global__ __launch_bounds__(kBlock) void resp_scatter_voters_kernel(RespLayout L, WireMsg* __restrict__ enc, uint64_t n_max,
+                                                                            const uint16_t* __restrict__ voters) {
+  __shared__ uint32_t wc[kWaves][kMaxPeers];
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  RespRec r{};
+  if (i < L.n) r = L.resp[i];
+  const bool valid = i < L.n && r.stamp == L.stamp && r.kind != 0;
+  const uint32_t to = resp_to_voters(r, valid, L, voters);
+  const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
+  uint32_t in_wave[kMaxPeers];
+#pragma unroll
+  for (uint32_t p = 0; p < (uint32_t)kMaxPeers; ++p) {
+    const uint64_t b = __ballot(((to >> p) & 1u) != 0);
+    in_wave[p] = (uint32_t)__popcll(b & below);
+    if (lane == 0) wc[wave][p] = (uint32_t)__popcll(b);
+  }
+  __syncthreads();
+  if (to != 0) {
+    WireMsg m;
+    m.group = r.group;
+    m.term = r.term;
+    m.log_term = r.log_term;
+    m.index = r.index;
+    m.commit = r.commit;
+    m.reject_hint = 0;
+    m.from = L.self;
+    m.type = r.kind;
+    m.reject = r.reject;
+    m.flags = 0;
+    m.ent_first = 0;
+    m.n_ents = 0;
+#pragma unroll
+    for (uint32_t p = 0; p < (uint32_t)kMaxPeers; ++p) {
+      if (((to >> p) & 1u) == 0) continue;
+      uint64_t at = L.peer_off[p] + L.blk_off[(uint64_t)blockIdx.x * kMaxPeers + p] + in_wave[p];
+      for (uint32_t w = 0; w < wave; ++w) at += wc[w][p];
+      m.to = (uint8_t)p;
+      enc[at] = m;
+    }
+  }
+  // fillers: the encoder counts them as refused and writes nothing for them
+  const uint64_t total = L.peer_off[L.n_peers];
+  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+  for (uint64_t k = total + i; k < n_max; k += stride) {
+    WireMsg f{};
+    f.to = 0xff;
+    enc[k] = f;
+  }
+}
+
 }  // namespace raftqk

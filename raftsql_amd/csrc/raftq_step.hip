@@ -92,15 +92,15 @@ int ensure_mirror(raftq_t* h) {
 }
 
 }  // namespace
-int raftq_detail::node_records_of(raftq_t* h, const char* who, raftqk::NodeArrays* out, bool tick_rounds) {
-  if (int rc = raftq_detail::refuse_voters(h, who, false, tick_rounds)) return rc;
+int raftq_detail::node_records_of(raftq_t* h, const char* who, raftqk::NodeArrays* out, bool tick_rounds, bool bcast) {
+  if (int rc = raftq_detail::refuse_voters(h, who, false, tick_rounds, bcast)) return rc;
   if (int rc = ensure_node_state(h)) return rc;
   if (int rc = ensure_mirror(h)) return rc;
   *out = node_arrays(h);
   return RAFTQ_OK;
 }
 int raftq_detail::node_arrays_of(raftq_t* h, raftqk::NodeArrays* out) {
-  if (int rc = node_records_of(h, "raftq_propose_frames", out)) return rc;
+  if (int rc = node_records_of(h, "raftq_propose_frames", out, false, true)) return rc;
   h->last_flags &= ~RAFTQ_SWEEP_NO_ADOPT;  // as in raftq_step_submit: the live state moves
   return RAFTQ_OK;
 }
@@ -381,8 +381,10 @@ struct WireSrc {
   const raftq_detail::PackedDst* packed = nullptr;  // raftq_step_frames_packed: msgs_h is the narrow array
 };
 
-// raftq_step_set_voters on a handle with masks loaded: the walks and the tail reports launch the *_voters_kernel twins
-static bool masked_step(const raftq_t* h) { return h->voters != nullptr && h->step_voters; }
+// raftq_step_set_voters on a handle with masks loaded: the walks and the tail reports launch the *_voters_kernel twins.  So do the
+// walks of a raftq_step_frames_respond call (resp_on: the first pass and a stalled batch's replay) on a handle that opted in to
+// raftq_bcast_set_voters -- on its own authority, as raftq_tick_elect_frames uses the masked Step
+static bool masked_step(const raftq_t* h) { return h->voters != nullptr && (h->step_voters || (h->resp_on && h->bcast_voters)); }
 
 // key -> stable radix sort -> walk, on the handle's stream (the path that takes runs of any length)
 static int enqueue_sorted_walk(raftq_t* h, const Scratch& s, uint64_t n, int end_bit, uint8_t recs, void* outs) {
@@ -458,7 +460,7 @@ static int submit_impl(raftq_t* h, const void* msgs, uint64_t n, const WireSrc* 
                        size_t rec_bytes = sizeof(raftq_msg_t)) {
   const bool packed = rec_bytes != sizeof(raftq_msg_t);
   if (int rc = use_device(h)) return rc;
-  if (int rc = raftq_detail::refuse_voters(h, who, !h->resp_on)) return rc;  // (raftq_step_frames_respond broadcasts: never let through)
+  if (int rc = raftq_detail::refuse_voters(h, who, !h->resp_on, false, h->resp_on)) return rc;  // (raftq_step_frames_respond: raftq_bcast_set_voters' call)
   if (n == 0 || (!wire && !msgs)) return fail(h, RAFTQ_EINVAL, std::string(who) + ": empty batch");
   if (n > 0x7ffffffeull) return fail(h, RAFTQ_EINVAL, std::string(who) + ": batch too large (2^31 - 2 messages at most)");
   if (wire && ((!wire->stream && wire->nbytes) || !wire->frame_off))

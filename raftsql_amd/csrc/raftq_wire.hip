@@ -43,7 +43,7 @@ enum : uint32_t {
   kPinRefused = 1,  // records refused (encoders), malformed frames (raftq_wire_decode*); raftq_wal_decode: the running CRC
   kPinThird = 2,    // the chain's last CRC (WAL encoders), wide records (the narrow decode forms)
   kPinGaveUp = 3,   // streaming kernels only: a look-back waited a second and gave up (tile_ctl_check)
-  kPinMembers = 4,  // behind kPinCall only: the frames raftq_tick_frames / raftq_tick_elect_frames built for members (members_tail_kernel)
+  kPinMembers = 4,  // behind kPinCall only: the frames raftq_tick_frames / raftq_tick_elect_frames / raftq_propose_frames built for members (members_tail_kernel)
 };
 
 size_t align256(size_t x) { return (x + 255) / 256 * 256; }
@@ -450,6 +450,20 @@ int wire_decode_copying(raftq_t* h, const void* stream, uint64_t nbytes, const u
   return RAFTQ_OK;
 }
 
+// Broadcasts over each group's own members (raftq_tick_set_voters / raftq_bcast_set_voters with masks loaded; raftq_beat_kernels.hpp,
+// raftq_propose_kernels.hpp): the twins add the frames they built for members to the fifth word of wire_flags, zeroed here in the same submission in front of them ...
+unsigned long long* members_word(raftq_t* h) { return h->wire_flags + 4; }
+int members_begin(raftq_t* h) {
+  HIPCHK(h, hipMemsetAsync(members_word(h), 0, 8, h->stream));
+  return RAFTQ_OK;
+}
+// ... and behind the encoder the sum goes to the pinned block, where the host reads it beside the encoder's totals
+int members_end(raftq_t* h) {
+  hipLaunchKernelGGL(members_tail_kernel, dim3(1), dim3(64), 0, h->stream, members_word(h), h->wire_pin_d + kPinCall + kPinMembers);
+  HIPCHK(h, hipGetLastError());
+  return RAFTQ_OK;
+}
+
 }  // namespace
 
 void raftq_detail::free_wire_state(raftq_t* h) {
@@ -543,30 +557,52 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
   const dim3 pg((unsigned)((n_props + kBlock - 1) / kBlock)), cg((unsigned)((std::max(n_props, n_prop_ents) + kBlock - 1) / kBlock));
   PropRec* props_d = (PropRec*)sc.carved[0];
   PropEnt* pe_d = (PropEnt*)sc.carved[1];
-  hipLaunchKernelGGL(propose_check_kernel, cg, dim3(kBlock), 0, h->stream, na, (const PropRec*)v_props, n_props, (const PropEnt*)v_pe, n_prop_ents, pool_bytes, bad,
-                     stamp, props_d, pe_d, h->wire_flags + 3);
-  hipLaunchKernelGGL(propose_apply_kernel, pg, dim3(kBlock), 0, h->stream, na, (const PropRec*)props_d, n_props, (const PropEnt*)pe_d,
-                     (const unsigned int*)bad, stamp, msgs_dev, ents_dev, (uint32_t)n_ents);
+  const bool members = raftq_detail::masked_bcast(h);  // the MsgApps go to each group's own members (the propose_*_voters_kernel twins)
+  if (members) {
+    if (int rc = members_begin(h)) return rc;
+    hipLaunchKernelGGL(propose_check_voters_kernel, cg, dim3(kBlock), 0, h->stream, na, (const PropRec*)v_props, n_props, (const PropEnt*)v_pe, n_prop_ents,
+                       pool_bytes, bad, stamp, props_d, pe_d, h->wire_flags + 3, (const uint16_t*)h->voters);
+    hipLaunchKernelGGL(propose_apply_voters_kernel, pg, dim3(kBlock), 0, h->stream, na, (const PropRec*)props_d, n_props, (const PropEnt*)pe_d,
+                       (const unsigned int*)bad, stamp, msgs_dev, ents_dev, (uint32_t)n_ents, (const uint16_t*)h->voters, members_word(h));
+  } else {
+    hipLaunchKernelGGL(propose_check_kernel, cg, dim3(kBlock), 0, h->stream, na, (const PropRec*)v_props, n_props, (const PropEnt*)v_pe, n_prop_ents, pool_bytes,
+                       bad, stamp, props_d, pe_d, h->wire_flags + 3);
+    hipLaunchKernelGGL(propose_apply_kernel, pg, dim3(kBlock), 0, h->stream, na, (const PropRec*)props_d, n_props, (const PropEnt*)pe_d,
+                       (const unsigned int*)bad, stamp, msgs_dev, ents_dev, (uint32_t)n_ents);
+  }
   // ... and the marshal of everything right behind it: one wait
   if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, n, n_e, pool_bytes, (uint8_t*)h->wire_out.d, (uint8_t*)v_out, cap, (uint64_t*)v_off,
                              sc.ctl, h->wire_pin_d + kPinCall, (const unsigned int*)bad, stamp))
     return rc;
+  if (members)
+    if (int rc = members_end(h)) return rc;
   HIPCHK(h, raftq_detail::wait_call(h));
   if (int rc = tile_ctl_check(h, "raftq_propose_frames", kPinCall)) return rc;
   const uint64_t total = h->wire_pin[kPinCall + kPinTotal];
-  if (h->wire_pin[kPinCall + kPinRefused]) {
+  // the MsgApps that have bytes: every slot, or -- over members -- what the apply kernel counted
+  const uint64_t frames = members ? h->wire_pin[kPinCall + kPinMembers] : n_dev;
+  // over members a non-member's slot is a filler the encoder refuses.  A refused call counted no member frame (its apply built
+  // nothing), so a count above zero that accounts for every refusal needs no look at the check's word
+  const uint64_t refused = h->wire_pin[kPinCall + kPinRefused];
+  const bool fillers_only = members && refused == n_dev - frames;
+  if (refused != 0 && !(fillers_only && frames != 0)) {
     // which record, and why (the check kernel left the largest (stamp, reason, record) it met; an older call's stamp: the marshal refused)
     unsigned long long why = 0;
     (void)hipMemcpy(&why, h->wire_flags + 3, 8, hipMemcpyDeviceToHost);
     static const char* const kWhy[] = {"?", "an entry's payload lies outside the pool", "its group is out of range", "it carries no entries (or more than 1024)",
-                                       "its entries lie outside prop_ents[]", "this node does not lead its group", "its group is named twice"};
+                                       "its entries lie outside prop_ents[]", "this node does not lead its group", "its group is named twice",
+                                       "this node is no member of its group",
+                                       "its append would move the commit index (a one-voter group, or a membership that shrank since the last "
+                                       "acknowledgement): raftq_apply_log_deltas reports that"};
     const uint32_t reason = (uint32_t)(why >> 32) & 0xffu;
-    if ((why >> 40) == (stamp & 0xffffffu) && reason >= 1 && reason <= 6)
+    if ((why >> 40) == (stamp & 0xffffffu) && reason >= 1 && reason <= 8)
       return fail(h, RAFTQ_EINVAL, std::string("raftq_propose_frames: record ") + std::to_string((uint32_t)why) + ": " + kWhy[reason] + " -- nothing was appended");
-    return fail(h, RAFTQ_EINVAL, "raftq_propose_frames: a queued message has to / from >= 255, an entry range outside ents[] or a payload outside the pool; the "
-                                 "proposals WERE appended, the output is not valid");
+    // (over members: proposals whose groups have no member but this node build no frame at all)
+    if (!fillers_only)
+      return fail(h, RAFTQ_EINVAL, "raftq_propose_frames: a queued message has to / from >= 255, an entry range outside ents[] or a payload outside the pool; the "
+                                   "proposals WERE appended, the output is not valid");
   }
-  if (counts) *counts = raftq_wire_counts_t{n, n_e, 0, total};
+  if (counts) *counts = raftq_wire_counts_t{n_msgs + frames, n_e, 0, total};
   if (total > cap) return fail(h, RAFTQ_EINVAL, "raftq_propose_frames: out is too small (counts->bytes is the size needed); the proposals WERE appended");
   return RAFTQ_OK;
 }
@@ -712,13 +748,18 @@ int raftq_detail::respond_enqueue(raftq_t* h, const RespPlan& p) {
   const uint32_t blocks = blocks_for(p.n);
   RespLayout L{(const RespRec*)rd, p.n, h->N, h->self_peer, h->resp_stamp, (uint32_t*)(rd + rs.o_blk_cnt), (uint64_t*)(rd + rs.o_blk_off),
                (uint64_t*)(rd + rs.o_peer_off)};
-  hipLaunchKernelGGL(resp_count_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L);
+  const bool members = raftq_detail::masked_bcast(h);  // the commit broadcasts go to each group's own members (the resp_*_voters_kernel twins)
+  if (members) hipLaunchKernelGGL(resp_count_voters_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, (const uint16_t*)h->voters);
+  else hipLaunchKernelGGL(resp_count_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L);
   hipLaunchKernelGGL(resp_scan_kernel, dim3(1), dim3(kBlock), 0, h->stream, L, blocks);
   HIPCHK(h, hipGetLastError());
   if (p.n_max != 0) {
     StreamCall sc = resp_marshal_call(p);
     if (int rc = stream_prepare(h, sc)) return rc;  // (allocates nothing: respond_prepare reserved this very request)
-    hipLaunchKernelGGL(resp_scatter_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, (WireMsg*)sc.in.seg[0].dst, p.n_max);
+    if (members)
+      hipLaunchKernelGGL(resp_scatter_voters_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, (WireMsg*)sc.in.seg[0].dst, p.n_max, (const uint16_t*)h->voters);
+    else
+      hipLaunchKernelGGL(resp_scatter_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, (WireMsg*)sc.in.seg[0].dst, p.n_max);
     if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, p.n_max, (uint64_t)0, (uint64_t)0, (uint8_t*)h->wire_out.d, (uint8_t*)p.v_out,
                                p.cap, p.v_resp_off, sc.ctl, h->wire_pin_d + kPinRespond, (const unsigned int*)nullptr, 0u))
       return rc;
@@ -746,19 +787,6 @@ int raftq_detail::respond_finish(raftq_t* h, const RespPlan& p, raftq_wire_count
 
 // ---- raftq_tick_frames ------------------------------------------------------------------------------------------------
 namespace {
-// Rounds over each group's own members (raftq_tick_set_voters with masks loaded; raftq_beat_kernels.hpp): the twins add the frames
-// they built for members to the fifth word of wire_flags, zeroed here in the same submission in front of them ...
-unsigned long long* members_word(raftq_t* h) { return h->wire_flags + 4; }
-int members_begin(raftq_t* h) {
-  HIPCHK(h, hipMemsetAsync(members_word(h), 0, 8, h->stream));
-  return RAFTQ_OK;
-}
-// ... and behind the encoder the sum goes to the pinned block, where the host reads it beside the encoder's totals
-int members_end(raftq_t* h) {
-  hipLaunchKernelGGL(members_tail_kernel, dim3(1), dim3(64), 0, h->stream, members_word(h), h->wire_pin_d + kPinCall + kPinMembers);
-  HIPCHK(h, hipGetLastError());
-  return RAFTQ_OK;
-}
 // the marshal of the heartbeats: as resp_marshal_call, the records go into the scratch behind an empty feed
 StreamCall beat_marshal_call(uint64_t n_max, uint64_t cap) {
   StreamCall sc;

@@ -222,6 +222,13 @@ class WireEngine(NodeEngine):
         got_wide = wide[: min(int(nw.value), cap)] if wide is not None else np.zeros(0, WIRE_MSG_DT)
         return narrow[:n], got_wide, got_ents, outs, c, int(nw.value)
 
+    def set_bcast_voters(self, on=True) -> None:
+        """raftq_bcast_set_voters: with voter masks loaded step_frames_respond's commit broadcast and propose_frames' MsgApps go to
+        each group's own members instead of the calls being refused (propose_frames: positional, a non-member's slot has zero length;
+        a record whose append would move the commit index is refused); a property of the handle, independent of set_step_voters and
+        set_tick_voters (no batch may be in flight)"""
+        self._chk(self._lib.raftq_bcast_set_voters(self._h, int(on)))
+
     def respond_cap(self, n: int) -> int:
         """the `out` size raftq_step_frames_respond needs for n frames (the exact worst case)"""
         return int(n) * (self.n_peers - 1) * RESPOND_FRAME_MAX
