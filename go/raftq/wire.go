@@ -549,7 +549,9 @@ type PropEnt struct {
 // MsgApps of bcastAppend, written into the encoder's input in HBM -- they never exist in host memory --, then the marshal of
 // msgs (what the caller queued itself this turn) followed by those MsgApps, one run per peer slot != self, ascending.  The
 // caller still owns the log (it appends the entries itself) and Progress.Next (it names only groups whose followers are all at
-// the tail, and moves Next past the new entries).  Every slice must be page-locked (HostAlloc).  SOURCE ONLY (round 6).
+// the tail, and moves Next past the new entries).  Every slice must be page-locked (HostAlloc).  A call that fails has appended
+// nothing: when out is too small, need is the size the stream takes and the same call with len(out) >= need is safe -- it appends
+// once.  SOURCE ONLY (round 6).
 func (e *Engine) ProposeFrames(props []Prop, propEnts []PropEnt, msgs []WireMsg, ents []WireEnt, pool, out []byte, frameOff []uint64) (need uint64, err error) {
 	var pp *C.raftq_prop_t
 	var ppe *C.raftq_prop_ent_t

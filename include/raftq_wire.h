@@ -308,8 +308,13 @@ int raftq_step_frames_respond(raftq_t* h, const void* stream, uint64_t nbytes, c
  * p in props[] order -- frame_off (may be NULL) gets n_msgs + (N - 1) * n_props + 1 offsets; peer p's MsgApps are ONE slice.
  * Byte for byte what raftq_wire_encode makes of the same messages built on the host (tests/test_wire_gpu.py::
  * test_propose_frames_*).  Every array must be page-locked and 16-byte aligned (RAFTQ_EINVAL otherwise), no Step batch may be
- * in flight.  A call that fails has applied nothing (a validation kernel runs first); `out` is unspecified after a refusal, as
- * with the streaming raftq_wire_encode.  raftq_node's turn is raftq_step_frames + this.
+ * in flight.  A call that fails has applied nothing (a validation kernel runs first, and appendEntry's stores run behind the
+ * marshal, once its verdict is in): a record refused, a message of msgs[] the marshal refuses (to / from >= 255, an entry range
+ * outside ents[], a payload outside the pool) and an `out` that is too small all leave the handle as it was.  In the last case
+ * counts->bytes is the size the stream needs, and the same call with cap >= counts->bytes appends once and succeeds -- cap ==
+ * counts->bytes exactly included.  `out` and frame_off are unspecified after a refusal, as with the streaming raftq_wire_encode
+ * (nothing is written at or behind out[cap], nor behind frame_off's n_msgs + (N - 1) * n_props + 1 words).  raftq_node's turn is
+ * raftq_step_frames + this.
  *
  * Over each group's own members (raftq_bcast_set_voters(h, 1), below, on a handle with voter masks loaded): bcastAppend ranges
  * over r.prs -- of the N - 1 MsgApps of a record only those to a slot p whose bit is set in voters[g] exist.  The layout stays

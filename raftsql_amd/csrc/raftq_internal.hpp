@@ -272,7 +272,7 @@ int refuse_voters(raftq_t* h, const char* who, bool step_family = false, bool ti
 // raftq_tick_set_voters on a handle with masks loaded: every Tick launch is tick_voters_kernel's, the rounds are the twins'
 inline bool masked_tick(const raftq_t* h) { return h->voters != nullptr && h->tick_voters; }
 // raftq_bcast_set_voters on a handle with masks loaded: raftq_step_frames_respond walks with the masked Node and lays its answers
-// out with the resp_*_voters_kernel twins, raftq_propose_frames runs propose_check_voters_kernel / propose_apply_voters_kernel
+// out with the resp_*_voters_kernel twins, raftq_propose_frames runs propose_check_voters_kernel / propose_build_voters_kernel
 inline bool masked_bcast(const raftq_t* h) { return h->voters != nullptr && h->bcast_voters; }
 int self_max_check(raftq_t* h);                 // the self-max word re-derived from the rows for h->self_peer (enqueued)
 int narrow_build(raftq_t* h);                   // the narrow mirror and its word re-derived from the rows (enqueued)

@@ -31,7 +31,7 @@ constexpr uint32_t kPropPayload = 1, kPropGroup = 2, kPropCount = 3, kPropRange 
 constexpr uint32_t kPropMaxEnts = 1024;  // raft.Config.MaxSizePerMsg's share of entries (raft.go:157): more go out as the caller's own sends
 
 // Nothing is applied unless every record is sound: a group of this handle, led by this node, named once (the group's list
-// count word doubles as the "seen" mark: the apply kernel hands it back zero), 1 .. kPropMaxEnts entries inside prop_ents[],
+// count word doubles as the "seen" mark: propose_commit_kernel hands it back zero), 1 .. kPropMaxEnts entries inside prop_ents[],
 // every entry's payload inside the pool.
 // The records lie in page-locked HOST memory: this kernel reads them there ONCE, coalesced (16 bytes a lane: 1 KB a wave
 // instruction over the link), and leaves a copy in device scratch for the kernel behind it -- round 6's first form had both
@@ -61,29 +61,24 @@ static __global__ __launch_bounds__(kBlock) void propose_check_kernel(NodeArrays
   if (__ballot(reason != 0) != 0 && (threadIdx.x & 63) == 0) atomicExch(bad, stamp);  // (the word holds this call's stamp: refused)
 }
 
+// The call has TWO verdicts -- this check's, and the marshal's (a queued message it refuses, a stream that does not fit `out`) --
+// and a failed call has applied nothing (include/raftq_wire.h), so appendEntry is split around the encoder: propose_build_kernel
+// in front of it reads the state and writes what bcastAppend sends into the encoder's input, storing NOTHING to the node;
+// propose_commit_kernel behind it stores the new tail once both verdicts are on the device.
+//
 // props / pe: the check kernel's copies in device memory.  msgs_out: the device part of the encoder's message array -- (N - 1) runs of n records, run r = the MsgApps for the r-th peer
 // slot other than this node's; ents_out: the device part of its entry-header array, whose first element is entry `ent_base` of
 // the whole array (a message's ent_first counts from the array's start).
-static __global__ __launch_bounds__(kBlock) void propose_apply_kernel(NodeArrays a, const PropRec* __restrict__ props, uint64_t n,
+static __global__ __launch_bounds__(kBlock) void propose_build_kernel(NodeArrays a, const PropRec* __restrict__ props, uint64_t n,
                                                                       const PropEnt* __restrict__ pe, const unsigned int* __restrict__ bad,
                                                                       unsigned int stamp, WireMsg* __restrict__ msgs_out, WireEnt* __restrict__ ents_out, uint32_t ent_base) {
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
+  if (*bad == stamp) return;  // refused: nothing is built (the encoder counts every message as refused, the commit kernel takes the marks off)
   const PropRec p = props[i];
-  if (*bad == stamp) {  // refused: the marks of the check come off, nothing else happens
-    if (p.group < a.n_groups) a.rec[p.group].lst_cnt = 0;
-    return;
-  }
-  Node node(a, p.group);
+  const Node node(a, p.group);
   const uint64_t old_last = node.last_index, old_term = node.last_term;
-  // appendEntry: `es[i].Term = r.Term; es[i].Index = li + 1 + i; r.raftLog.append(es...); r.prs[r.id].maybeUpdate(lastIndex)`.
-  // (`r.maybeCommit()` cannot move anything with more than one peer: the leader's own Match is the largest, the quorum-th
-  // largest is somebody else's and did not change -- the host wrapper refuses a single-peer handle.)
-  node.last_index = old_last + p.n_ents;
-  node.last_term = node.term;
-  if (node.match(a.self) < node.last_index) node.set_match(a.self, node.last_index);
-  node.lst_cnt = 0;
-  node.store();  // (list words back to empty: the check's mark with them)
+  // appendEntry's entries: `es[i].Term = r.Term; es[i].Index = li + 1 + i` (the append itself: propose_commit_kernel)
   for (uint32_t k = 0; k < p.n_ents; ++k) {
     const PropEnt e = pe[p.ent_first + k];
     WireEnt w;
@@ -117,8 +112,40 @@ static __global__ __launch_bounds__(kBlock) void propose_apply_kernel(NodeArrays
   }
 }
 
+// appendEntry's state change, behind the encoder on the same stream: `r.raftLog.append(es...); r.prs[r.id].maybeUpdate(lastIndex)`.
+// (`r.maybeCommit()` cannot move anything with more than one peer: the leader's own Match is the largest, the quorum-th largest
+// is somebody else's and did not change -- the host wrapper refuses a single-peer handle; over members the check refuses a
+// record whose append would commit.)  One lane per record, for both forms: what is stored does not depend on the mask.
+// Every lane reads the same four words, so every lane takes the same verdict BEFORE any lane stores:
+//   *bad == stamp                 the check refused a record
+//   pin[1] != fillers             the marshal refused a queued message (pin: the encoder's totals, raftq_wire_kernels.hpp; fillers:
+//                                 the slots of non-members, n_dev - *members over members, none otherwise)
+//   pin[0] > cap                  the stream does not fit `out`
+//   pin[3] != 0                   a wait of the encoder gave up
+// the conditions raftq_propose_frames fails on once the host has the same words.  Either way the check's marks come off.
+// pin == nullptr: the encoder could not be launched -- the call fails, and this kernel only takes the marks off.
+static __global__ __launch_bounds__(kBlock) void propose_commit_kernel(NodeArrays a, const PropRec* __restrict__ props, uint64_t n,
+                                                                       const unsigned int* __restrict__ bad, unsigned int stamp,
+                                                                       const uint64_t* __restrict__ pin, uint64_t cap, uint64_t n_dev,
+                                                                       const unsigned long long* __restrict__ members) {
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t fillers = members != nullptr ? n_dev - *members : 0;
+  const bool whole = pin != nullptr && *bad != stamp && pin[1] == fillers && pin[0] <= cap && pin[3] == 0;
+  const PropRec p = props[i];
+  if (!whole) {
+    if (p.group < a.n_groups) a.rec[p.group].lst_cnt = 0;
+    return;
+  }
+  Node node(a, p.group);
+  node.last_index += p.n_ents;
+  node.last_term = node.term;
+  if (node.match(a.self) < node.last_index) node.set_match(a.self, node.last_index);
+  node.store();  // (list words back to empty: the check's mark with them)
+}
+
 // ---- proposals over each group's own members (raftq_bcast_set_voters on a handle with voter masks loaded) ----------------------
-// Twins of the two kernels above, the masks as a last argument behind the parents'.  Kernels of their own: the parents keep
+// Twins of the check and the build kernel, the masks as a last argument behind the parents' (propose_commit_kernel serves both).  Kernels of their own: the parents keep
 // their assembly (profiles/r14/isa_unchanged.txt).
 constexpr uint32_t kPropNoMember = 7, kPropCommits = 8;
 
@@ -126,14 +153,14 @@ constexpr uint32_t kPropNoMember = 7, kPropCommits = 8;
 // (its lst_cnt is the "seen" mark):
 //   kPropNoMember  self's bit is clear in voters[g].  Upstream v2.2's appendEntry would dereference a missing Progress
 //                  (r.prs[r.id]); CHOICE: refuse.
-//   kPropCommits   apply's sentence "maybeCommit cannot move anything with more than one peer" does not hold over members: a
+//   kPropCommits   the commit kernel's sentence "maybeCommit cannot move anything with more than one peer" does not hold over members: a
 //                  one-voter group commits on its own append, and under the 2015-era removeNode (which does not call
 //                  maybeCommit) so does a group whose membership shrank since its last acknowledgement.  Evaluated exactly --
-//                  Match[self] raised to last_index + n_ents as apply will, then the masked maybe_commit() with its current-term
+//                  Match[self] raised to last_index + n_ents as the commit will, then the masked maybe_commit() with its current-term
 //                  gate -- on the lane's copy, which is never stored.  The call has no channel for a commit:
 //                  raftq_apply_log_deltas has, and a tail report with the unchanged tail settles the commit first.
 // Both after the six old reasons, so a record sound by the old rules is marked (lst_cnt) whatever the new ones say; a refused
-// call's apply takes every mark off again.
+// call's commit kernel takes every mark off again.
 static __global__ __launch_bounds__(kBlock) void propose_check_voters_kernel(NodeArrays a, const PropRec* __restrict__ props, uint64_t n,
                                                                              const PropEnt* __restrict__ pe, uint64_t n_pe, uint64_t pool_bytes,
                                                                              unsigned int* bad, unsigned int stamp, PropRec* __restrict__ props_d,
@@ -168,12 +195,12 @@ static __global__ __launch_bounds__(kBlock) void propose_check_voters_kernel(Nod
   if (__ballot(reason != 0) != 0 && (threadIdx.x & 63) == 0) atomicExch(bad, stamp);
 }
 
-// propose_apply_kernel over members: the state changes and the entry headers are the parent's; of the N - 1 MsgApps only those
+// propose_build_kernel over members: the entry headers are the parent's; of the N - 1 MsgApps only those
 // to a slot whose bit is set in voters[g] exist.  The encoder's input stays POSITIONAL, as in beat_build_voters_kernel
 // (raftq_beat_kernels.hpp): (N - 1) runs of n records where the parent puts them, and the slot of a peer that is no member of
 // its group holds a filler (to = 0xff), which the encoder counts as refused and gives zero bytes.  The workgroup's member frames
 // are summed and added once to *members (members_add): the host checks `refused == n_dev - member frames`.
-static __global__ __launch_bounds__(kBlock) void propose_apply_voters_kernel(NodeArrays a, const PropRec* __restrict__ props, uint64_t n,
+static __global__ __launch_bounds__(kBlock) void propose_build_voters_kernel(NodeArrays a, const PropRec* __restrict__ props, uint64_t n,
                                                                              const PropEnt* __restrict__ pe, const unsigned int* __restrict__ bad,
                                                                              unsigned int stamp, WireMsg* __restrict__ msgs_out, WireEnt* __restrict__ ents_out,
                                                                              uint32_t ent_base, const uint16_t* __restrict__ voters, unsigned long long* members) {
@@ -181,19 +208,11 @@ static __global__ __launch_bounds__(kBlock) void propose_apply_voters_kernel(Nod
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   const bool refused = *bad == stamp;  // workgroup-uniform
   uint32_t wrote = 0;
-  if (i < n && refused) {  // the marks of the check come off, nothing else happens
+  if (i < n && !refused) {  // (refused: nothing is built, no member frame counted)
     const PropRec p = props[i];
-    if (p.group < a.n_groups) a.rec[p.group].lst_cnt = 0;
-  } else if (i < n) {
-    const PropRec p = props[i];
-    NodeT<true> node(a, p.group, voters);
+    const NodeT<true> node(a, p.group, voters);
     const uint64_t old_last = node.last_index, old_term = node.last_term;
-    // appendEntry, as in propose_apply_kernel (the check made sure maybeCommit does not move over this group's members)
-    node.last_index = old_last + p.n_ents;
-    node.last_term = node.term;
-    if (node.match(a.self) < node.last_index) node.set_match(a.self, node.last_index);
-    node.lst_cnt = 0;
-    node.store();
+    // appendEntry's entries, as in propose_build_kernel
     for (uint32_t k = 0; k < p.n_ents; ++k) {
       const PropEnt e = pe[p.ent_first + k];
       WireEnt w;

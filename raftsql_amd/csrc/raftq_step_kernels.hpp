@@ -247,7 +247,7 @@ constexpr uint32_t kNil = 0xffffffffu;
 // more thing to keep fresh) beside the record's loads: its address depends on g alone, so it adds a 32-byte sector per touched
 // group and no dependent latency.  Everything else -- what is stored, reset()'s N slots, whose words are recorded -- is the
 // unmasked form's: a non-voter's Match and vote are kept as always and merely do not count.
-// `Node` stays the name of the unmasked form (elect_build_kernel, propose_apply_kernel, the respond path).
+// `Node` stays the name of the unmasked form (elect_build_kernel, propose_build_kernel / propose_commit_kernel, the respond path).
 template <bool MASKED>
 struct NodeT {
   const NodeArrays& a;

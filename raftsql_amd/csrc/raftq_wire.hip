@@ -546,7 +546,7 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
   sc.n_carves = 2;
   sc.out_bytes = cap + 16;
   if (int rc = stream_prepare(h, sc)) return rc;
-  // appendEntry + bcastAppend on the device, INTO the encoder's input (the scratch behind what its readers bring) ...
+  // what appendEntry + bcastAppend send, built on the device INTO the encoder's input (the scratch behind what its readers bring) ...
   // the validation's verdict: a word that holds THIS call's stamp when a record was refused (no memset in the chain: a stamp
   // of an earlier call reads as "fine")
   unsigned int* bad = (unsigned int*)(h->wire_flags + 2);
@@ -562,26 +562,38 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
     if (int rc = members_begin(h)) return rc;
     hipLaunchKernelGGL(propose_check_voters_kernel, cg, dim3(kBlock), 0, h->stream, na, (const PropRec*)v_props, n_props, (const PropEnt*)v_pe, n_prop_ents,
                        pool_bytes, bad, stamp, props_d, pe_d, h->wire_flags + 3, (const uint16_t*)h->voters);
-    hipLaunchKernelGGL(propose_apply_voters_kernel, pg, dim3(kBlock), 0, h->stream, na, (const PropRec*)props_d, n_props, (const PropEnt*)pe_d,
+    hipLaunchKernelGGL(propose_build_voters_kernel, pg, dim3(kBlock), 0, h->stream, na, (const PropRec*)props_d, n_props, (const PropEnt*)pe_d,
                        (const unsigned int*)bad, stamp, msgs_dev, ents_dev, (uint32_t)n_ents, (const uint16_t*)h->voters, members_word(h));
   } else {
     hipLaunchKernelGGL(propose_check_kernel, cg, dim3(kBlock), 0, h->stream, na, (const PropRec*)v_props, n_props, (const PropEnt*)v_pe, n_prop_ents, pool_bytes,
                        bad, stamp, props_d, pe_d, h->wire_flags + 3);
-    hipLaunchKernelGGL(propose_apply_kernel, pg, dim3(kBlock), 0, h->stream, na, (const PropRec*)props_d, n_props, (const PropEnt*)pe_d,
+    hipLaunchKernelGGL(propose_build_kernel, pg, dim3(kBlock), 0, h->stream, na, (const PropRec*)props_d, n_props, (const PropEnt*)pe_d,
                        (const unsigned int*)bad, stamp, msgs_dev, ents_dev, (uint32_t)n_ents);
   }
-  // ... and the marshal of everything right behind it: one wait
+  // ... the marshal of everything right behind it ...
+  const unsigned long long* members_d = members ? (const unsigned long long*)members_word(h) : nullptr;
   if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, n, n_e, pool_bytes, (uint8_t*)h->wire_out.d, (uint8_t*)v_out, cap, (uint64_t*)v_off,
-                             sc.ctl, h->wire_pin_d + kPinCall, (const unsigned int*)bad, stamp))
+                             sc.ctl, h->wire_pin_d + kPinCall, (const unsigned int*)bad, stamp)) {
+    // no marshal, no verdict: the check's marks still come off (a null `pin` makes every lane of the commit kernel refuse)
+    hipLaunchKernelGGL(propose_commit_kernel, pg, dim3(kBlock), 0, h->stream, na, (const PropRec*)props_d, n_props, (const unsigned int*)bad, stamp,
+                       (const uint64_t*)nullptr, cap, n_dev, members_d);
+    (void)hipGetLastError();
     return rc;
+  }
+  // ... and appendEntry's stores behind both verdicts, the check's and the marshal's, which the encoder's last tile has left in the
+  // pinned words: a call that fails has applied nothing.  Still one submission and one wait
+  hipLaunchKernelGGL(propose_commit_kernel, pg, dim3(kBlock), 0, h->stream, na, (const PropRec*)props_d, n_props, (const unsigned int*)bad, stamp,
+                     (const uint64_t*)(h->wire_pin_d + kPinCall), cap, n_dev, members_d);
+  HIPCHK(h, hipGetLastError());
   if (members)
     if (int rc = members_end(h)) return rc;
   HIPCHK(h, raftq_detail::wait_call(h));
   if (int rc = tile_ctl_check(h, "raftq_propose_frames", kPinCall)) return rc;
+  // (from here on the host reads the words propose_commit_kernel decided on: it fails exactly where that kernel stored nothing)
   const uint64_t total = h->wire_pin[kPinCall + kPinTotal];
-  // the MsgApps that have bytes: every slot, or -- over members -- what the apply kernel counted
+  // the MsgApps that have bytes: every slot, or -- over members -- what the build kernel counted
   const uint64_t frames = members ? h->wire_pin[kPinCall + kPinMembers] : n_dev;
-  // over members a non-member's slot is a filler the encoder refuses.  A refused call counted no member frame (its apply built
+  // over members a non-member's slot is a filler the encoder refuses.  A refused call counted no member frame (its build kernel built
   // nothing), so a count above zero that accounts for every refusal needs no look at the check's word
   const uint64_t refused = h->wire_pin[kPinCall + kPinRefused];
   const bool fillers_only = members && refused == n_dev - frames;
@@ -599,11 +611,11 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
       return fail(h, RAFTQ_EINVAL, std::string("raftq_propose_frames: record ") + std::to_string((uint32_t)why) + ": " + kWhy[reason] + " -- nothing was appended");
     // (over members: proposals whose groups have no member but this node build no frame at all)
     if (!fillers_only)
-      return fail(h, RAFTQ_EINVAL, "raftq_propose_frames: a queued message has to / from >= 255, an entry range outside ents[] or a payload outside the pool; the "
-                                   "proposals WERE appended, the output is not valid");
+      return fail(h, RAFTQ_EINVAL, "raftq_propose_frames: a queued message has to / from >= 255, an entry range outside ents[] or a payload outside the pool -- "
+                                   "nothing was appended, the output is not valid");
   }
   if (counts) *counts = raftq_wire_counts_t{n_msgs + frames, n_e, 0, total};
-  if (total > cap) return fail(h, RAFTQ_EINVAL, "raftq_propose_frames: out is too small (counts->bytes is the size needed); the proposals WERE appended");
+  if (total > cap) return fail(h, RAFTQ_EINVAL, "raftq_propose_frames: out is too small (counts->bytes is the size needed) -- nothing was appended");
   return RAFTQ_OK;
 }
 

@@ -1759,7 +1759,7 @@ __device__ inline void tile_bytes_out(const uint8_t* __restrict__ src, uint8_t* 
 // pin[0] = bytes the stream takes, pin[1] = messages refused (to / from >= 255, ranges outside ents[] / the pool: they
 // count as empty frames), pin[3] = a wait gave up.
 // raftq_propose_frames: msgs / ents go on in the scratch behind the caller's (in.seg[0] / [1].bytes: what the readers bring) with
-// the records propose_apply_kernel wrote there -- n and n_ents count both parts; *ext_bad == ext_stamp (its validation refused the call):
+// the records propose_build_kernel wrote there -- n and n_ents count both parts; *ext_bad == ext_stamp (its validation refused the call):
 // every message counts as refused, nothing is built.
 static __global__ __launch_bounds__(kBlock) void wire_enc_fused_kernel(InFeed in, uint64_t n, uint64_t n_ents, uint64_t pool_bytes, uint8_t* d_out,
                                                                        uint8_t* out_h, uint64_t cap, uint64_t* off_h, TileCtl ctl,

@@ -335,12 +335,13 @@ class WireEngine(NodeEngine):
                 int(nb.value))
 
     def propose_frames(self, props: np.ndarray, prop_ents: np.ndarray, msgs: np.ndarray, ents: np.ndarray, pool: np.ndarray, out: np.ndarray,
-                       off: np.ndarray | None = None):
+                       off: np.ndarray | None = None, counts=None):
         """raftq_propose_frames: appendEntry + bcastAppend for props[] on the device, written into the encoder's input, and the
         marshal of msgs[] + those MsgApps -- one submission, one wait.  All arrays page-locked (engine.pinned_*).
-        -> (stream view of out, frame_off | None, counts)"""
+        -> (stream view of out, frame_off | None, counts).  A call that raises has appended nothing; pass `counts` (a
+        _lib.WireCounts) to learn counts.bytes, the size needed, when out was too small: retrying with an out of that size is safe"""
         assert props.dtype == PROP_DT and prop_ents.dtype == PROP_ENT_DT and msgs.dtype == WIRE_MSG_DT and ents.dtype == WIRE_ENT_DT
-        c = _lib.WireCounts()
+        c = _lib.WireCounts() if counts is None else counts
         self._chk(self._lib.raftq_propose_frames(self._h, props.ctypes.data if len(props) else None, len(props),
                                                  prop_ents.ctypes.data if len(prop_ents) else None, len(prop_ents),
                                                  msgs.ctypes.data if len(msgs) else None, len(msgs), ents.ctypes.data if len(ents) else None, len(ents),

@@ -526,9 +526,10 @@ int raftq_wire_encode(raftq_t* h, const raftq_wire_msg_t* msgs, uint64_t n, cons
   rq_wire_encode(msgs, n, ents, (const uint8_t*)pool, (uint8_t*)out, cap, frame_off);
   return RAFTQ_OK;
 }
-// raftq_propose_frames from its parts, as include/raftq_wire.h states it: the records are validated (nothing applied on a
-// refusal), then for every group appendEntry -- the oracle's raftq_apply_log_deltas with the new tail -- and the N - 1 MsgApps
-// bcastAppend sends, built the way raftq_node.cpp's send_append builds them; then the oracle's encoder over msgs[] + those.
+// raftq_propose_frames from its parts, as include/raftq_wire.h states it: the records are validated, the N - 1 MsgApps bcastAppend
+// sends are built off the UNCHANGED state the way raftq_node.cpp's send_append builds them, the oracle's encoder sizes, validates
+// and marshals msgs[] + those -- and only a call that got this far appends: for every group appendEntry, the oracle's
+// raftq_apply_log_deltas with the new tail.  A call that fails has applied nothing, whichever check fails it.
 int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props, const raftq_prop_ent_t* prop_ents, uint64_t n_prop_ents,
                          const raftq_wire_msg_t* msgs, uint64_t n_msgs, const raftq_wire_ent_t* ents, uint64_t n_ents, const void* pool,
                          uint64_t pool_bytes, void* out, uint64_t cap, uint64_t* frame_off, raftq_wire_counts_t* counts) {
@@ -558,9 +559,6 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
   for (uint64_t i = 0; i < n_props; ++i) {
     const raftq_prop_t& p = props[i];
     const uint64_t g = p.group, old_last = h->last_index[g], old_term = h->last_term[g];
-    raftq_log_delta_t d{g, old_last + p.n_ents, h->term[g], 0};
-    rq_node_state_t s = h->state();
-    rq_oracle_apply_log_deltas(&s, &d, 1, nullptr);
     for (uint32_t k = 0; k < p.n_ents; ++k) {
       const raftq_prop_ent_t& e = prop_ents[p.ent_first + k];
       raftq_wire_ent_t& w = all_e[n_ents + p.ent_first + k];
@@ -589,7 +587,14 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
       ++run;
     }
   }
-  return raftq_wire_encode(h, all.data(), all.size(), all_e.data(), all_e.size(), pool, pool_bytes, out, cap, frame_off, counts);
+  if (int rc = raftq_wire_encode(h, all.data(), all.size(), all_e.data(), all_e.size(), pool, pool_bytes, out, cap, frame_off, counts)) return rc;
+  for (uint64_t i = 0; i < n_props; ++i) {  // both verdicts are in: appendEntry
+    const raftq_prop_t& p = props[i];
+    raftq_log_delta_t d{p.group, h->last_index[p.group] + p.n_ents, h->term[p.group], 0};
+    rq_node_state_t s = h->state();
+    rq_oracle_apply_log_deltas(&s, &d, 1, nullptr);
+  }
+  return RAFTQ_OK;
 }
 int raftq_wire_decode(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off, uint64_t n, raftq_wire_msg_t* msgs,
                       raftq_wire_ent_t* ents, uint64_t ents_cap, raftq_wire_counts_t* counts) {

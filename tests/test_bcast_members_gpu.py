@@ -1,5 +1,5 @@
 """GPU: the two device-built broadcasts over each group's own members (raftq_bcast_set_voters; resp_count_voters_kernel,
-resp_scatter_voters_kernel, propose_check_voters_kernel, propose_apply_voters_kernel) against tests/ref_bcast_members.py, whose
+resp_scatter_voters_kernel, propose_check_voters_kernel, propose_build_voters_kernel) against tests/ref_bcast_members.py, whose
 inputs tests/test_bcast_members_ref.py checks on the CPU.
 
 Masks are ref_bcast_members.masks(): uniform in [1, 2^N) with a few groups forced empty and a few forced to one voter; the respond

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """raftq_propose_frames and raftq_step_frames_respond over each group's own members (raftq_bcast_set_voters:
-propose_check_voters_kernel, propose_apply_voters_kernel, resp_count_voters_kernel, resp_scatter_voters_kernel) against the same
+propose_check_voters_kernel, propose_build_voters_kernel, resp_count_voters_kernel, resp_scatter_voters_kernel) against the same
 calls on a handle without masks -- the parent's path.  Three handles of one shape in the same state, in one process:
   none     no masks loaded (the parent's kernels)
   full     every slot votes, the switch on (the twins, the same frames)
