@@ -28,8 +28,8 @@ static int raftq_device_count_msg(int* n, char* msg, size_t cap) {
   if (rc != RAFTQ_OK && cap) { strncpy(msg, raftq_last_error(NULL), cap - 1); msg[cap - 1] = 0; }
   return rc;
 }
-static int raftq_set_create_msg(raftq_t* const* hs, uint32_t n, raftq_set_t** out, char* msg, size_t cap) {
-  int rc = raftq_set_create(hs, n, out);
+static int raftq_set_create_msg(raftq_t* const* hs, uint32_t n, raftq_set_t** out, int voters, char* msg, size_t cap) {
+  int rc = voters ? raftq_set_create_voters(hs, n, out) : raftq_set_create(hs, n, out);
   if (rc != RAFTQ_OK && cap) { strncpy(msg, raftq_set_last_error(NULL), cap - 1); msg[cap - 1] = 0; }
   return rc;
 }
@@ -216,8 +216,15 @@ type Set struct {
 	Members []*Engine
 }
 
-// NewSet re-homes every member onto the set's stream (raftq_set_create).
-func NewSet(members []*Engine) (*Set, error) {
+// NewSet re-homes every member onto the set's stream (raftq_set_create).  No member may hold voter masks.
+func NewSet(members []*Engine) (*Set, error) { return newSet(members, 0) }
+
+// NewSetVoters is NewSet for members that may hold voter masks (raftq_set_create_voters): masked and unmasked members may be
+// mixed, LoadVoters / ApplyVoterDeltas stay allowed on a member while the set lives, and SweepAsync and Tick treat every member
+// as StepAsync and Tick on it alone would.
+func NewSetVoters(members []*Engine) (*Set, error) { return newSet(members, 1) }
+
+func newSet(members []*Engine, voters C.int) (*Set, error) {
 	if len(members) == 0 {
 		return nil, errors.New("raftq: empty set")
 	}
@@ -229,7 +236,7 @@ func NewSet(members []*Engine) (*Set, error) {
 	}
 	var s *C.raftq_set_t
 	var msg [256]C.char
-	if rc := C.raftq_set_create_msg((**C.raftq_t)(unsafe.Pointer(arr)), C.uint32_t(len(members)), &s, &msg[0], 256); rc != C.RAFTQ_OK {
+	if rc := C.raftq_set_create_msg((**C.raftq_t)(unsafe.Pointer(arr)), C.uint32_t(len(members)), &s, voters, &msg[0], 256); rc != C.RAFTQ_OK {
 		return nil, fmt.Errorf("raftq: %d: %s", int(rc), C.GoString(&msg[0]))
 	}
 	return &Set{s: s, Members: members}, nil

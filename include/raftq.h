@@ -194,9 +194,11 @@ int raftq_apply_term_deltas(raftq_t* h, const raftq_term_delta_t* d, uint64_t n)
  * raftq_propose_frames (bcastAppend), have the third switch, raftq_bcast_set_voters(h, 1) (raftq_wire.h): their MsgApps then go
  * to each group's own members, and a proposal whose append would move the commit index -- a one-voter group, a membership that
  * shrank -- is refused and pointed to raftq_apply_log_deltas; without it both refuse a masked handle (RAFTQ_ESTATE, the
- * default).  Not built, and refused with RAFTQ_ESTATE and a message that says so whatever the switches say: a sweep set with a
- * masked member (raftq_set_create; raftq_load_voters / raftq_apply_voter_deltas on a member).  A handle with no masks loaded is
- * exactly the handle it always was, kernels included. */
+ * default).  Sweep sets ("sweep sets" below) have a constructor of their own for this: a set from raftq_set_create_voters takes
+ * masked members, lets raftq_load_voters / raftq_apply_voter_deltas change them while it lives, and sweeps and ticks every member
+ * over its own voters; a set from raftq_set_create refuses a masked handle, and those two calls on one of its members, with
+ * RAFTQ_ESTATE and a message that says so, whatever the switches say.  A handle with no masks loaded is exactly the handle it
+ * always was, kernels included. */
 typedef struct raftq_voter_delta {
   uint64_t group;
   uint16_t voters; /* the group's new mask */
@@ -278,7 +280,8 @@ int raftq_collect_changed(raftq_t* h, raftq_advance_t* out, uint64_t cap, uint64
  * members.  0 is the default (Tick asks nobody, the two calls refuse a masked handle); anything but 0 or 1 is RAFTQ_EINVAL; the
  * handle must be idle (RAFTQ_ESTATE with a Step batch in flight).  A property of the handle: raftq_clone_state does not copy it
  * and raftq_load_voters(h, NULL) does not clear it; with no masks loaded the handle launches what it always did, whatever the
- * switch says.  Independent of raftq_step_set_voters.  raftq_set_tick is untouched: set members cannot hold masks. */
+ * switch says.  Independent of raftq_step_set_voters.  raftq_set_tick applies the same rule member by member in a set from
+ * raftq_set_create_voters ("sweep sets" below); in a set from raftq_set_create no member holds masks and nothing changes. */
 #define RAFTQ_ROLE_FOLLOWER 0
 #define RAFTQ_ROLE_CANDIDATE 1
 #define RAFTQ_ROLE_LEADER 2
@@ -393,16 +396,33 @@ int raftq_last_advance_segments(raftq_t* h, const raftq_advance16_t** recs, cons
  *   - flags are raftq_step_async's (RAFTQ_SWEEP_LDS excepted), applied to every member;
  *     a gated sweep needs terms loaded on every member.
  *   - like a handle, a set is not thread-safe, and its members must not be used from
- *     another thread while the set is. */
+ *     another thread while the set is.
+ *   - voter masks ("per-group voter sets" above).  raftq_set_create refuses a handle with masks loaded, and its members
+ *     refuse raftq_load_voters / raftq_apply_voter_deltas / raftq_clone_state from a masked source (RAFTQ_ESTATE).
+ *     raftq_set_create_voters is raftq_set_create in every other respect -- the same shape rules, the same re-homing, the same
+ *     refusals of null, duplicate, already-in-a-set and Step-in-flight members -- and admits them: members with and without
+ *     masks may be mixed, and raftq_load_voters (NULL included), raftq_apply_voter_deltas and raftq_clone_state from a masked
+ *     source are allowed on a member while the set lives.  raftq_set_sweep_async then leaves every member exactly as
+ *     raftq_step_async(member, flags) would -- a masked member decides over its voters, an unmasked one over every slot:
+ *     commit buffers, outcomes, the changed bitmap / raftq_collect_changed, the counts of raftq_set_wait and of raftq_wait.
+ *     A dispatch in which no member holds masks launches exactly what a plain set launches (persistent mode, the narrow and
+ *     the self-row bodies included); a dispatch with at least one masked member is one K-deep grid of the masked kernel, and
+ *     RAFTQ_SET_PERSISTENT then runs that grid form too (there is no persistent masked walk).  RAFTQ_SWEEP_LDS stays refused.
+ *     raftq_set_tick: a member with masks loaded and raftq_tick_set_voters on gets promotable() ("batched Tick" above) exactly
+ *     as raftq_tick applies it, every other member -- no masks, or the switch off -- ticks as it always did, all in one
+ *     dispatch; RAFTQ_TICK_SHAPE does not apply to a dispatch with such a member.  A switched-on masked member that does not
+ *     know its self slot makes the call fail with RAFTQ_ESTATE before anything is launched: no member has ticked. */
 typedef struct raftq_set raftq_set_t;
 #define RAFTQ_SET_GRID 0       /* one K-deep grid: blockIdx.y = member (default) */
 #define RAFTQ_SET_PERSISTENT 1 /* resident workgroups walk all K x tiles, next tile's loads in flight */
 int raftq_set_create(raftq_t* const* handles, uint32_t n, raftq_set_t** out);
+int raftq_set_create_voters(raftq_t* const* handles, uint32_t n, raftq_set_t** out);
 void raftq_set_destroy(raftq_set_t* s);
 uint32_t raftq_set_size(const raftq_set_t* s);
 const char* raftq_set_last_error(const raftq_set_t* s); /* s may be NULL: global */
 void* raftq_set_get_stream(const raftq_set_t* s);
-/* launch shape of the set's sweeps; persist_workgroups 0 keeps the current / default count */
+/* launch shape of the set's sweeps; persist_workgroups 0 keeps the current / default count.  A dispatch with a masked member
+ * (raftq_set_create_voters) runs the grid form whatever the mode. */
 int raftq_set_mode(raftq_set_t* s, int mode, uint32_t persist_workgroups);
 /* enqueue one pass over every member on the set's stream */
 int raftq_set_sweep_async(raftq_set_t* s, unsigned flags);

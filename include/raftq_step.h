@@ -101,8 +101,9 @@ int raftq_step_set_msg_flags(raftq_t* h, int on);
  * broadcasts to each group's own members.  Without them the broadcasts go to N - 1 slots, not to a membership, and the
  * proposal path relies on "maybeCommit cannot move with more than one peer", which a one-voter group breaks -- over members
  * raftq_propose_frames refuses a record whose append would move the commit index.  raftq_step_frames_respond with
- * raftq_bcast_set_voters on runs the rules above whether or not this switch is on.  Sweep sets with a masked member and
- * raftq_node (which never loads masks) are as before. */
+ * raftq_bcast_set_voters on runs the rules above whether or not this switch is on.  A sweep set takes masked members
+ * when it is made with raftq_set_create_voters (raftq.h "sweep sets"; its sweeps and ticks then run over each member's own
+ * voters) and refuses them when made with raftq_set_create; raftq_node (which never loads masks) is as before. */
 int raftq_step_set_voters(raftq_t* h, int on);
 
 /* raftq_msg_t._pad[1] once the handle opted in.  RAFTQ_MSGF_ENTRIES on a MsgApp: the caller says what the message carries -- the low 32 bits of

@@ -113,6 +113,7 @@ _SIGS = [
     ("raftq_last_advances_packed", C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     ("raftq_last_advance_segments", C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     ("raftq_set_create", C.c_int, [C.POINTER(_H), C.c_uint32, C.POINTER(_H)]),
+    ("raftq_set_create_voters", C.c_int, [C.POINTER(_H), C.c_uint32, C.POINTER(_H)]),
     ("raftq_set_destroy", None, [_H]),
     ("raftq_set_size", C.c_uint32, [_H]),
     ("raftq_set_last_error", C.c_char_p, [_H]),

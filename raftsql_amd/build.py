@@ -45,6 +45,8 @@ def lib_sources() -> list[str]:
         os.path.join(CSRC, "raftq_kernels.hpp"),
         os.path.join(CSRC, "raftq_step_kernels.hpp"),
         os.path.join(CSRC, "raftq_step_walk_kernels.inc"),
+        os.path.join(CSRC, "raftq_sweep_voters_tile.inc"),
+        os.path.join(CSRC, "raftq_tick_voters_block.inc"),
         os.path.join(CSRC, "raftq_internal.hpp"),
         os.path.join(CSRC, "raftq_buffers.hpp"),
         os.path.join(CSRC, "raftq_wire_kernels.hpp"),

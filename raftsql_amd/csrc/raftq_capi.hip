@@ -199,6 +199,48 @@ hipError_t launch_voters(uint32_t N, const VoterSweepArgs& a, uint64_t gpad, uns
   }
 }
 
+// The masked sweep of a set (sweep_set_voters_kernel): sweep_voters_kernel's tile and groups per lane, blockIdx.y = member.
+struct VoterSetLaunch {
+  const VoterSweepArgs* tab;
+  uint32_t members, want_bits;
+  uint64_t gpad;
+};
+
+template <int N, bool COMMIT, bool GATED, bool VOTES>
+hipError_t launch_set_voters_reg(const VoterSetLaunch& L, int nt, hipStream_t s) {
+  constexpr int G = voters_gpl(N);
+  const dim3 grid((unsigned)(L.gpad / ((uint64_t)kBlock * G)), L.members), block(kBlock);
+  if (nt == 3) hipLaunchKernelGGL((sweep_set_voters_kernel<N, G, COMMIT, GATED, VOTES, kLdNT | kStNT>), grid, block, 0, s, L.tab, L.want_bits);
+  else if (nt == 1) hipLaunchKernelGGL((sweep_set_voters_kernel<N, G, COMMIT, GATED, VOTES, kLdNT>), grid, block, 0, s, L.tab, L.want_bits);
+  else hipLaunchKernelGGL((sweep_set_voters_kernel<N, G, COMMIT, GATED, VOTES, 0>), grid, block, 0, s, L.tab, L.want_bits);
+  return hipGetLastError();
+}
+
+template <int N>
+hipError_t launch_set_voters_n(const VoterSetLaunch& L, unsigned flags, int nt, hipStream_t s) {
+  const bool commit = flags & (RAFTQ_SWEEP_COMMIT | RAFTQ_SWEEP_GATED);
+  const bool gated = flags & RAFTQ_SWEEP_GATED;
+  const bool votes = flags & RAFTQ_SWEEP_VOTES;
+  if (commit && gated) return votes ? launch_set_voters_reg<N, true, true, true>(L, nt, s) : launch_set_voters_reg<N, true, true, false>(L, nt, s);
+  if (commit) return votes ? launch_set_voters_reg<N, true, false, true>(L, nt, s) : launch_set_voters_reg<N, true, false, false>(L, nt, s);
+  return launch_set_voters_reg<N, false, false, true>(L, nt, s);
+}
+
+hipError_t launch_set_voters(uint32_t N, const VoterSetLaunch& L, unsigned flags, int nt, hipStream_t s) {
+  switch (N) {
+    case 1: return launch_set_voters_n<1>(L, flags, nt, s);
+    case 2: return launch_set_voters_n<2>(L, flags, nt, s);
+    case 3: return launch_set_voters_n<3>(L, flags, nt, s);
+    case 4: return launch_set_voters_n<4>(L, flags, nt, s);
+    case 5: return launch_set_voters_n<5>(L, flags, nt, s);
+    case 6: return launch_set_voters_n<6>(L, flags, nt, s);
+    case 7: return launch_set_voters_n<7>(L, flags, nt, s);
+    case 8: return launch_set_voters_n<8>(L, flags, nt, s);
+    case 9: return launch_set_voters_n<9>(L, flags, nt, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
 hipError_t launch_sweep(uint32_t N, const SweepLaunch& L, unsigned flags, int nt, hipStream_t s) {
   switch (N) {
     case 1: return launch_n<1>(L, flags, nt, s);
@@ -696,17 +738,19 @@ int raftq_apply_vote_deltas(raftq_t* h, const raftq_vote_delta_t* d, uint64_t n)
 static int ensure_voters(raftq_t* h) {
   if (h->voters) return RAFTQ_OK;
   HIPCHK(h, raftq_buf::alloc_zeroed((void**)&h->voters, h->ld * sizeof(uint16_t), h->stream));
+  if (h->in_set) h->in_set->tab_stale = true;  // (a set from raftq_set_create_voters: its tables hold the members' mask pointers)
   return RAFTQ_OK;
 }
 // back to "every slot votes": the unmasked kernels
 static int drop_voters(raftq_t* h) {
   if (!h->voters) return RAFTQ_OK;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // (a member's stream is its set's: no set dispatch is reading the masks either)
   raftq_buf::free_device(h->voters);
+  if (h->in_set) h->in_set->tab_stale = true;
   return RAFTQ_OK;
 }
 static int voters_not_in_set(raftq_t* h, const char* who) {
-  if (!h->in_set) return RAFTQ_OK;
+  if (!h->in_set || h->in_set->allow_voters) return RAFTQ_OK;
   return fail(h, RAFTQ_ESTATE, std::string(who) + ": the handle is a member of a sweep set, whose dispatches count every slot "
                                                   "(voter masks on set members are out of scope)");
 }
@@ -1833,42 +1877,64 @@ void set_fill_table(const raftq_set_t* s, int cur, std::vector<SweepArgs>& t) {
   for (size_t i = 0; i < s->members.size(); ++i)
     t[i] = sweep_args(s->members[i], cur < 0 ? s->members[i]->cur : cur, true);
 }
-}  // namespace
+// the members' VoterSweepArgs: the same SweepArgs, and the mask pointer each member holds now (null: none loaded)
+void set_fill_vtable(const raftq_set_t* s, int cur, std::vector<VoterSweepArgs>& t) {
+  t.resize(s->members.size());
+  for (size_t i = 0; i < s->members.size(); ++i) {
+    t[i].s = sweep_args(s->members[i], cur < 0 ? s->members[i]->cur : cur, true);
+    t[i].voters = s->members[i]->voters;
+  }
+}
+// the standing tables, written while no kernel can be reading them: the caller has just waited on the set's stream, or no
+// dispatch was ever enqueued (raftq_set_create*)
+hipError_t set_write_tables(raftq_set_t* s) {
+  const size_t n = s->members.size();
+  for (int k = 0; k < 2; ++k) {
+    set_fill_table(s, k, s->tab_host);
+    if (hipError_t e = hipMemcpy(s->tab[k], s->tab_host.data(), n * sizeof(SweepArgs), hipMemcpyHostToDevice)) return e;
+    if (!s->allow_voters) continue;
+    set_fill_vtable(s, k, s->vtab_host);
+    if (hipError_t e = hipMemcpy(s->vtab[k], s->vtab_host.data(), n * sizeof(VoterSweepArgs), hipMemcpyHostToDevice)) return e;
+  }
+  return hipSuccess;
+}
 
-extern "C" {
-
-int raftq_set_create(raftq_t* const* handles, uint32_t n, raftq_set_t** out) {
-  if (!out) return sfail(nullptr, RAFTQ_EINVAL, "raftq_set_create: null out");
+// raftq_set_create and raftq_set_create_voters: one constructor, which differs in whether a member may hold voter masks
+int set_create(raftq_t* const* handles, uint32_t n, raftq_set_t** out, bool allow_voters, const std::string& who) {
+  if (!out) return sfail(nullptr, RAFTQ_EINVAL, who + ": null out");
   *out = nullptr;
-  if (!handles || n == 0) return sfail(nullptr, RAFTQ_EINVAL, "raftq_set_create: empty set");
-  if (n > 65535) return sfail(nullptr, RAFTQ_EINVAL, "raftq_set_create: at most 65535 members");
+  if (!handles || n == 0) return sfail(nullptr, RAFTQ_EINVAL, who + ": empty set");
+  if (n > 65535) return sfail(nullptr, RAFTQ_EINVAL, who + ": at most 65535 members");
   for (uint32_t i = 0; i < n; ++i) {
     raftq_t* h = handles[i];
-    if (!h) return sfail(nullptr, RAFTQ_EINVAL, "raftq_set_create: null member");
-    if (h->in_set) return sfail(nullptr, RAFTQ_ESTATE, "raftq_set_create: a handle is already a member of a set");
+    if (!h) return sfail(nullptr, RAFTQ_EINVAL, who + ": null member");
+    if (h->in_set) return sfail(nullptr, RAFTQ_ESTATE, who + ": a handle is already a member of a set");
     if (h->device != handles[0]->device || h->N != handles[0]->N || h->gpad != handles[0]->gpad)
       return sfail(nullptr, RAFTQ_EINVAL,
-                   "raftq_set_create: members must share the device, the peer count and the (padded) group count");
+                   who + ": members must share the device, the peer count and the (padded) group count");
     if (h->step_collected != h->step_submitted)
-      return sfail(nullptr, RAFTQ_ESTATE, "raftq_set_create: a member has Step batches in flight");
-    if (h->voters)
-      return sfail(nullptr, RAFTQ_ESTATE, "raftq_set_create: a handle has voter masks loaded; the set dispatches count every slot "
+      return sfail(nullptr, RAFTQ_ESTATE, who + ": a member has Step batches in flight");
+    if (h->voters && !allow_voters)
+      return sfail(nullptr, RAFTQ_ESTATE, who + ": a handle has voter masks loaded; the set dispatches count every slot "
                                           "(out of scope: sweep it on its own, or raftq_load_voters(h, NULL) first)");
     for (uint32_t k = 0; k < i; ++k)
-      if (handles[k] == h) return sfail(nullptr, RAFTQ_EINVAL, "raftq_set_create: duplicate member");
+      if (handles[k] == h) return sfail(nullptr, RAFTQ_EINVAL, who + ": duplicate member");
   }
   raftq_set_t* s = new (std::nothrow) raftq_set();
-  if (!s) return sfail(nullptr, RAFTQ_ENOMEM, "raftq_set_create: host allocation failed");
+  if (!s) return sfail(nullptr, RAFTQ_ENOMEM, who + ": host allocation failed");
   s->device = handles[0]->device;
   s->N = handles[0]->N;
   s->gpad = handles[0]->gpad;
+  s->allow_voters = allow_voters;
   try {  // everything the set's calls will ever push into: no allocation (and no exception) after this point
     s->members.reserve(n);
     s->tab_host.reserve(n);
     s->np_host.reserve(n);
+    if (allow_voters) s->vtab_host.reserve(n);
+    if (allow_voters) s->tick_vhost.reserve(n);
   } catch (...) {
     delete s;
-    return sfail(nullptr, RAFTQ_ENOMEM, "raftq_set_create: host allocation failed");
+    return sfail(nullptr, RAFTQ_ENOMEM, who + ": host allocation failed");
   }
   auto bail = [&](int rc) {
     std::string keep = s->err;
@@ -1879,35 +1945,42 @@ int raftq_set_create(raftq_t* const* handles, uint32_t n, raftq_set_t** out) {
   hipError_t e = hipSetDevice(s->device);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
   for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipMalloc((void**)&s->tab[k], (size_t)n * sizeof(SweepArgs));
+  for (int k = 0; k < 3 && e == hipSuccess && allow_voters; ++k) e = hipMalloc((void**)&s->vtab[k], (size_t)n * sizeof(VoterSweepArgs));
   if (e == hipSuccess) e = hipMalloc((void**)&s->counts_d, (size_t)n * 32);
   if (e == hipSuccess) e = hipMalloc((void**)&s->np_d, (size_t)n * 8);
   if (e == hipSuccess) e = hipHostMalloc((void**)&s->counts_h, (size_t)n * 32, hipHostMallocDefault);
   if (e == hipSuccess) e = hipEventCreate(&s->ev0);
   if (e == hipSuccess) e = hipEventCreate(&s->ev1);
   if (e != hipSuccess)
-    return bail(sfail(s, e == hipErrorOutOfMemory ? RAFTQ_ENOMEM : RAFTQ_EHIP, std::string("raftq_set_create: ") + hipGetErrorString(e)));
+    return bail(sfail(s, e == hipErrorOutOfMemory ? RAFTQ_ENOMEM : RAFTQ_EHIP, who + ": " + hipGetErrorString(e)));
   // re-home every member onto the set's stream: loads, deltas and per-member read-backs stay ordered with the
   // set's sweeps without any event traffic
   for (uint32_t i = 0; i < n; ++i) {
     raftq_t* h = handles[i];
     e = hipStreamSynchronize(h->stream);
     if (e == hipSuccess && h->own_stream) e = hipStreamDestroy(h->stream);
-    if (e != hipSuccess) return bail(sfail(s, RAFTQ_EHIP, std::string("raftq_set_create: ") + hipGetErrorString(e)));
+    if (e != hipSuccess) return bail(sfail(s, RAFTQ_EHIP, who + ": " + hipGetErrorString(e)));
     h->stream = s->stream;
     h->own_stream = false;
     h->in_set = s;
     s->members.push_back(h);
   }
-  for (int cur = 0; cur < 2; ++cur) {
-    set_fill_table(s, cur, s->tab_host);
-    e = hipMemcpy(s->tab[cur], s->tab_host.data(), (size_t)n * sizeof(SweepArgs), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return bail(sfail(s, RAFTQ_EHIP, std::string("raftq_set_create: ") + hipGetErrorString(e)));
-  }
+  e = set_write_tables(s);
+  if (e != hipSuccess) return bail(sfail(s, RAFTQ_EHIP, who + ": " + hipGetErrorString(e)));
   int cus = 0;
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device);
   s->persist_wgs = (uint32_t)std::max(cus, 1) * 3u;  // 3 resident 256-thread workgroups per CU (144 VGPRs: profiles/r03/isa_sweep.txt)
   *out = s;
   return RAFTQ_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int raftq_set_create(raftq_t* const* handles, uint32_t n, raftq_set_t** out) { return set_create(handles, n, out, false, "raftq_set_create"); }
+// ... whose members may hold voter masks, and load, change and drop them while the set lives (include/raftq.h "sweep sets")
+int raftq_set_create_voters(raftq_t* const* handles, uint32_t n, raftq_set_t** out) {
+  return set_create(handles, n, out, true, "raftq_set_create_voters");
 }
 
 void raftq_set_destroy(raftq_set_t* s) {
@@ -1921,6 +1994,8 @@ void raftq_set_destroy(raftq_set_t* s) {
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess) h->own_stream = true;
   }
   for (int k = 0; k < 3; ++k) (void)hipFree(s->tab[k]);
+  for (int k = 0; k < 3; ++k) (void)hipFree(s->vtab[k]);
+  (void)hipFree(s->tick_vtab);
   (void)hipFree(s->counts_d);
   (void)hipFree(s->np_d);
   (void)hipFree(s->tick_tab);
@@ -1948,22 +2023,43 @@ int raftq_set_sweep_async(raftq_set_t* s, unsigned flags) {
   if (flags & RAFTQ_SWEEP_LDS) return sfail(s, RAFTQ_EINVAL, "raftq_set_sweep_async: RAFTQ_SWEEP_LDS sweeps one handle at a time");
   uint64_t footprint = 0;
   int cur = s->members[0]->cur;
+  bool masked = false;  // (only ever in a set from raftq_set_create_voters)
   for (raftq_t* h : s->members) {
     if (h->step_collected != h->step_submitted)
       return sfail(s, RAFTQ_ESTATE, "raftq_set_sweep_async: a member has Step batches in flight; collect them first");
     if (int rc = sweep_check(h, flags, "raftq_set_sweep_async")) return sfail(s, rc, h->err);
     footprint += sweep_footprint(h);
     if (h->cur != cur) cur = -1;
+    masked = masked || h->voters != nullptr;
   }
   if (s->tab_stale) {
-    // A member's mirror arrays came into being: both standing tables name them from now on.  As in raftq_set_create; the call
-    // that allocated them (raftq_load_match, raftq_narrow_rebuild, raftq_clone_state) ended with a wait on this stream, and
-    // no set sweep has been enqueued since, so no kernel is reading the tables.
-    for (int k = 0; k < 2; ++k) {
-      set_fill_table(s, k, s->tab_host);
-      SETCHK(s, hipMemcpy(s->tab[k], s->tab_host.data(), s->tab_host.size() * sizeof(SweepArgs), hipMemcpyHostToDevice));
-    }
+    // A member's mirror arrays came into being, or its mask array came or went: the standing tables name what the members hold
+    // from now on.  The call that allocated or freed them (raftq_load_match, raftq_narrow_rebuild, raftq_clone_state,
+    // raftq_load_voters, raftq_apply_voter_deltas) ended with a wait on this stream, and no set sweep has been enqueued since;
+    // the wait here says so again for a call that failed half way.  No kernel reads a table or a mask array while it is
+    // rewritten or freed.
+    SETCHK(s, hipStreamSynchronize(s->stream));
+    SETCHK(s, set_write_tables(s));
     s->tab_stale = false;
+  }
+  // a streaming set streams its stores too: with many members in one dispatch non-temporal stores are worth
+  // 5-9 % (profiles/r02/tune3_focus_*.jsonl: 10.92 vs 11.78 us per batch), unlike one 1M-group launch at a time
+  int nt = sweep_policy(flags, footprint);
+  if (nt == 1) nt = 3;
+  if (masked) {
+    // At least one member decides over its own voters: every member goes through sweep_set_voters_kernel, the unmasked ones with
+    // a null mask pointer.  The grid form whatever raftq_set_mode says (a persistent masked walk is not built).
+    if (cur < 0) {  // members disagree on which commit buffer is current: build this launch's table
+      set_fill_vtable(s, -1, s->vtab_host);
+      SETCHK(s, hipMemcpyAsync(s->vtab[2], s->vtab_host.data(), s->vtab_host.size() * sizeof(VoterSweepArgs), hipMemcpyHostToDevice,
+                               s->stream));
+    }
+    const VoterSetLaunch V{s->vtab[cur < 0 ? 2 : cur], (uint32_t)s->members.size(), (flags & RAFTQ_SWEEP_CHANGED) ? 1u : 0u, s->gpad};
+    SETCHK(s, launch_set_voters(s->N, V, flags, nt, s->stream));
+    for (raftq_t* h : s->members) sweep_done(h, flags, voters_gpl((int)s->N));
+    s->swept = true;
+    s->last_flags = flags;
+    return RAFTQ_OK;
   }
   const SweepArgs* tab = s->tab[cur < 0 ? 2 : cur];
   if (cur < 0) {  // members disagree on which commit buffer is current: build this launch's table
@@ -1977,15 +2073,54 @@ int raftq_set_sweep_async(raftq_set_t* s, unsigned flags) {
   L.want_bits = (flags & RAFTQ_SWEEP_CHANGED) ? 1u : 0u;
   L.persist_wgs = s->mode == RAFTQ_SET_PERSISTENT ? s->persist_wgs : 0u;
   L.gpad = s->gpad;
-  // a set that streams, streams its stores too: with many members in one dispatch non-temporal stores are worth
-  // 5-9 % (profiles/r02/tune3_focus_*.jsonl: 10.92 vs 11.78 us per batch), unlike one 1M-group launch at a time
-  int nt = sweep_policy(flags, footprint);
-  if (nt == 1) nt = 3;
   SETCHK(s, launch_sweep(s->N, L, flags, nt, s->stream));
   const int gpl = s->mode == RAFTQ_SET_PERSISTENT ? kGPL : set_gpl((int)s->N);
   for (raftq_t* h : s->members) sweep_done(h, flags, gpl);
   s->swept = true;
   s->last_flags = flags;
+  return RAFTQ_OK;
+}
+
+// raftq_set_tick when at least one member asks promotable(): tick_set_voters_kernel over a table of the members' TickArgs, mask
+// pointer and self slot.  A member that does not ask -- no masks, or the switch off -- has a null pointer there and ticks as
+// tick_kernel would.  The table is rebuilt whenever what it was built from differs from what the members hold now: a member
+// re-configured or ticked on its own (or by the plain dispatch), masks loaded, re-allocated or dropped, the switch or the self
+// slot changed.  It is written on the set's stream, behind every dispatch that read it.  RAFTQ_TICK_SHAPE does not apply.
+static int set_tick_voters(raftq_set_t* s) {
+  const size_t K = s->members.size();
+  for (raftq_t* h : s->members)
+    if (int rc = ensure_tick_state(h)) return sfail(s, rc, h->err);
+  auto entry = [](const raftq_t* h) {
+    TickVotersArgs a;
+    a.t = tick_args(h, h->tick_no);
+    a.voters = raftq_detail::masked_tick(h) ? h->voters : nullptr;
+    a.self = h->self_peer;
+    a.pad = 0;
+    return a;
+  };
+  bool stale = s->tick_vtab == nullptr || s->tick_vhost.size() != K;
+  for (size_t m = 0; m < K && !stale; ++m) {
+    const TickVotersArgs now = entry(s->members[m]), &was = s->tick_vhost[m];
+    stale = now.t.role != was.t.role || now.t.seed != was.t.seed || now.t.election_tick != was.t.election_tick ||
+            now.t.heartbeat_tick != was.t.heartbeat_tick || now.t.tick_no != was.t.tick_no + s->tick_vsince || now.voters != was.voters ||
+            now.self != was.self;
+  }
+  if (stale) {
+    if (!s->tick_vtab) SETCHK(s, hipMalloc((void**)&s->tick_vtab, K * sizeof(TickVotersArgs)));
+    s->tick_vhost.resize(K);
+    for (size_t m = 0; m < K; ++m) s->tick_vhost[m] = entry(s->members[m]);
+    SETCHK(s, hipMemcpyAsync(s->tick_vtab, s->tick_vhost.data(), K * sizeof(TickVotersArgs), hipMemcpyHostToDevice, s->stream));  // (pageable: staged before it returns)
+    s->tick_vsince = 0;
+  }
+  hipLaunchKernelGGL(tick_set_voters_kernel, dim3((unsigned)(s->gpad / 1024), (unsigned)K), dim3(kBlock), 0, s->stream,
+                     (const TickVotersArgs*)s->tick_vtab, s->tick_vsince);
+  SETCHK(s, hipGetLastError());
+  ++s->tick_vsince;
+  for (raftq_t* h : s->members) {
+    h->tl_valid = false;
+    ++h->tick_no;
+    h->ticked = true;
+  }
   return RAFTQ_OK;
 }
 
@@ -1995,6 +2130,16 @@ int raftq_set_sweep_async(raftq_set_t* s, unsigned flags) {
 int raftq_set_tick(raftq_set_t* s) {
   if (int rc = set_ready(s, "raftq_set_tick")) return rc;
   const size_t K = s->members.size();
+  // promotable(): a member with masks loaded and raftq_tick_set_voters on (only ever in a set from raftq_set_create_voters).
+  // Checked for every member before anything is allocated or launched: a call that fails has ticked nobody.
+  bool masked = false;
+  for (raftq_t* h : s->members) {
+    if (h->step_collected != h->step_submitted)
+      return sfail(s, RAFTQ_ESTATE, "raftq_set_tick: a member has Step batches in flight; collect them first");
+    if (int rc = tick_voters_ready(h, "raftq_set_tick")) return sfail(s, rc, h->err);
+    masked = masked || raftq_detail::masked_tick(h);
+  }
+  if (masked) return set_tick_voters(s);
   bool stale = s->tick_tab == nullptr || s->tick_host.size() != K;
   for (size_t m = 0; m < K; ++m) {
     raftq_t* h = s->members[m];
@@ -2111,7 +2256,7 @@ int raftq_clone_state(raftq_t* dst, raftq_t* src) {
     return fail(dst, RAFTQ_EINVAL, "raftq_clone_state: source and destination must have the same device, groups and peers");
   if (src->step_collected != src->step_submitted)
     return fail(dst, RAFTQ_ESTATE, "raftq_clone_state: the source has Step batches in flight");
-  if (src->voters && dst->in_set)
+  if (src->voters && dst->in_set && !dst->in_set->allow_voters)
     return fail(dst, RAFTQ_ESTATE, "raftq_clone_state: the source has voter masks loaded and the destination is a member of a sweep "
                                    "set, whose dispatches count every slot (out of scope)");
   if (src->voters) {

@@ -239,7 +239,14 @@ struct raftq_set {
   uint64_t* counts_h = nullptr;       // pinned
   bool swept = false;
   bool broken = false;                // a member was destroyed under the set
-  bool tab_stale = false;             // a member allocated its narrow mirror since tab[0] / tab[1] were filled
+  bool tab_stale = false;             // a member allocated its narrow mirror -- or, in a set that admits masks, its mask array came
+                                      // or went -- since tab[0] / tab[1] (and vtab[0] / vtab[1]) were filled
+  // raftq_set_create_voters: members may hold voter masks.  vtab[k] is tab[k] with every member's mask pointer beside its
+  // SweepArgs (null: no masks loaded); a dispatch with at least one masked member reads it (sweep_set_voters_kernel), every
+  // other dispatch reads tab[k] and launches what a plain set launches.  nullptr in a set from raftq_set_create.
+  bool allow_voters = false;
+  raftqk::VoterSweepArgs* vtab[3] = {nullptr, nullptr, nullptr};
+  std::vector<raftqk::VoterSweepArgs> vtab_host;
   unsigned last_flags = 0;
   int mode = 0;                       // 0 = K-deep grid, 1 = persistent walk (raftq_set_mode)
   uint32_t persist_wgs = 0;
@@ -248,6 +255,11 @@ struct raftq_set {
   raftqk::TickArgs* tick_tab = nullptr;
   std::vector<raftqk::TickArgs> tick_host;
   uint64_t tick_since = 0;
+  // ... and of their TickVotersArgs, for the set ticks in which a member asks promotable() (tick_set_voters_kernel): a table and
+  // a count of its own, so either dispatch finds the other's table stale by the tick numbers alone
+  raftqk::TickVotersArgs* tick_vtab = nullptr;
+  std::vector<raftqk::TickVotersArgs> tick_vhost;
+  uint64_t tick_vsince = 0;
   std::string err;
 };
 

@@ -1378,97 +1378,74 @@ __device__ __forceinline__ uint32_t poll_word_voters(uint32_t w, uint32_t mask) 
 // flag work behind either.  Masks: the commit part's lane loads the two masks of its pair {g, g+1} as one dword per round
 // (256 B per wave instruction), the vote part's lane the eight masks of its eight groups as one 16-byte load; they are
 // issued with the tile's other loads, before the first compare.
+// The tile's statements live in raftq_sweep_voters_tile.inc, which is expanded here and in sweep_set_voters_kernel below.
 template <int N, int GPL, bool COMMIT, bool GATED, bool VOTES, int POLICY>
 static __global__ __launch_bounds__(kBlock) void sweep_voters_kernel(VoterSweepArgs va) {
-  constexpr bool NT = (POLICY & kLdNT) != 0;
-  constexpr bool STNT = (POLICY & kStNT) != 0;
-  constexpr int kTile = kBlock * GPL;
-  constexpr int kRounds = GPL / 2;
-  constexpr int kVoteLanes = kTile / 8;
-  const SweepArgs& a = va.s;
+#define RAFTQ_VT_PROLOGUE      \
+  const SweepArgs& a = va.s; \
   const uint32_t tid = threadIdx.x, tile = blockIdx.x;
-  const uint64_t tile0 = (uint64_t)tile * kTile;
-  const bool vote_lane = VOTES && tid < kVoteLanes;  // wave-uniform (kVoteLanes % 64 == 0)
+#define RAFTQ_VT_VMASK(at) ldg<NT>(reinterpret_cast<const u32x4p*>(va.voters + at))
+#define RAFTQ_VT_CMASK(j, at) ldg<NT>(reinterpret_cast<const uint32_t*>(va.voters + at))
+#include "raftq_sweep_voters_tile.inc"
+#undef RAFTQ_VT_PROLOGUE
+#undef RAFTQ_VT_VMASK
+#undef RAFTQ_VT_CMASK
+}
 
-  TileRegs<N, GPL, COMMIT, GATED, VOTES> r;
-  u32x4p vmask;                          // the 8 masks of the vote lane's 8 groups
-  uint32_t cmask[COMMIT ? kRounds : 1];  // the 2 masks of the lane's pair, per round
-  if constexpr (VOTES) {
-    if (vote_lane) vmask = ldg<NT>(reinterpret_cast<const u32x4p*>(va.voters + tile0 + 8ull * tid));
-  }
-  tile_load<N, GPL, COMMIT, GATED, VOTES, POLICY>(r, a, tile);  // every row: r.skip stays 0
-  if constexpr (COMMIT) {
-#pragma unroll
-    for (int j = 0; j < kRounds; ++j) {
-      const uint64_t g = tile0 + (uint64_t)(tid >> 6) * (64 * GPL) + (uint64_t)j * 128 + 2 * (tid & 63);
-      cmask[j] = ldg<NT>(reinterpret_cast<const uint32_t*>(va.voters + g));
+// A set of handles per launch whose members may hold masks (raftq_set_create_voters): blockIdx.y = member, blockIdx.x = tile,
+// the member's VoterSweepArgs from a device-resident table (wave-uniform: scalar loads) -- SweepArgs itself stays as it is, its
+// size is the stride of sweep_set_kernel's table.  A member with no masks loaded has a null mask pointer: ONE uniform branch per
+// tile either issues the tile's mask loads (in front of its other loads) or takes the constant "every slot votes", (1 << N) - 1
+// in both halves of every mask dword, and issues none; the arithmetic behind it is the same text either way, and the comment
+// above select_quorum_voters argues that the full mask gives the unmasked answer bit for bit.  (Two tile bodies, one per arm
+// with the constant folded into the second, cost up to 40 VGPRs and three waves per SIMD: the compiler hoists both arms' row
+// loads above the branch -- profiles/r16/README.md.)  Outputs, partials and the changed bitmap are sweep_voters_kernel's at the
+// same GPL, so whatever reads a member afterwards cannot tell which of the two ran.  The host launches this only when at least
+// one member holds masks (raftq_capi.hip); a dispatch without one is sweep_set_kernel's or sweep_persist_kernel's, as in a
+// plain set.
+template <int GPL, bool COMMIT>
+struct TileMasks {
+  u32x4p v;                        // the 8 masks of the vote lane's 8 groups
+  uint32_t c[COMMIT ? GPL / 2 : 1];  // the 2 masks of the commit lane's pair, per round
+};
+template <int N, int GPL, bool COMMIT, bool VOTES, bool NT>
+__device__ __forceinline__ void tile_masks(TileMasks<GPL, COMMIT>& m, const uint16_t* voters /* wave-uniform */, const uint32_t tile) {
+  constexpr int kTile = kBlock * GPL;
+  constexpr uint32_t kFullPair = ((1u << N) - 1u) * 0x10001u;
+  const uint32_t tid = threadIdx.x;
+  if (voters != nullptr) {
+    const uint16_t* const base = voters + (uint64_t)tile * kTile;  // wave-uniform: the lane's part of every address is 32 bits
+    if constexpr (VOTES) {
+      if (tid < kTile / 8) m.v = ldg<NT>(reinterpret_cast<const u32x4p*>(base + 8u * tid));
     }
-  }
-
-  uint32_t n_changed = 0;  // wave-uniform
-  uint32_t won_lost = 0;   // per lane: won | lost << 16
-  if constexpr (COMMIT) {
+    if constexpr (COMMIT) {
 #pragma unroll
-    for (int j = 0; j < kRounds; ++j) {
-      const uint64_t g = tile0 + (uint64_t)(tid >> 6) * (64 * GPL) + (uint64_t)j * 128 + 2 * (tid & 63);
-      uint64_t v0[N], v1[N];
-#pragma unroll
-      for (int p = 0; p < N; ++p) {
-        v0[p] = r.m[j][p].x;
-        v1[p] = r.m[j][p].y;
+      for (int j = 0; j < GPL / 2; ++j) {
+        const uint32_t g = (tid >> 6) * (64 * GPL) + (uint32_t)j * 128 + 2 * (tid & 63);
+        m.c[j] = ldg<NT>(reinterpret_cast<const uint32_t*>(base + g));
       }
-      const uint64_t mci0 = select_quorum_voters<N>(v0, cmask[j] & 0xffffu);
-      const uint64_t mci1 = select_quorum_voters<N>(v1, cmask[j] >> 16);
-      u64x2 o;
-      o.x = maybe_commit<GATED>(mci0, r.c[j].x, GATED ? r.f[j].x : 0);
-      o.y = maybe_commit<GATED>(mci1, r.c[j].y, GATED ? r.f[j].y : 0);
-      const uint64_t b0 = __ballot(o.x != r.c[j].x);
-      const uint64_t b1 = __ballot(o.y != r.c[j].y);
-      n_changed += __popcll(b0) + __popcll(b1);
-      if (a.changed_bits != nullptr && (tid & 63) == 0) {  // word 2k = even groups, 2k+1 = odd groups of the k-th 128-group run
-        u64x2 w;
-        w.x = b0;
-        w.y = b1;
-        stg<false>(reinterpret_cast<u64x2*>(a.changed_bits + (g >> 6)), w);
-      }
-      stg<STNT>(reinterpret_cast<u64x2*>(a.committed_out + g), o);
     }
-  }
-
-  if constexpr (VOTES) {
-    if (vote_lane) {
-      const uint64_t g = tile0 + 8ull * tid;
-      uint32_t out = 0, n_won = 0, n_lost = 0;
+  } else {
+    m.v.x = m.v.y = m.v.z = m.v.w = kFullPair;
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        uint32_t w;
-        if constexpr (N <= 8) {
-          const uint32_t pair = k < 2 ? r.vw[0].x : k < 4 ? r.vw[0].y : k < 6 ? r.vw[0].z : r.vw[0].w;
-          w = (k & 1) ? pair >> 16 : pair & 0xffffu;
-        } else {
-          w = k == 0 ? r.vw[0].x : k == 1 ? r.vw[0].y : k == 2 ? r.vw[0].z : k == 3 ? r.vw[0].w
-            : k == 4 ? r.vw[1].x : k == 5 ? r.vw[1].y : k == 6 ? r.vw[1].z : r.vw[1].w;
-        }
-        const uint32_t mpair = k < 2 ? vmask.x : k < 4 ? vmask.y : k < 6 ? vmask.z : vmask.w;
-        const uint32_t oc = poll_word_voters(w, (k & 1) ? mpair >> 16 : mpair & 0xffffu);
-        out |= oc << (2 * k);
-        n_won += oc & 1u;
-        n_lost += oc >> 1;
-      }
-      stg<STNT>(reinterpret_cast<uint16_t*>(a.outcome + (g >> 2)), (uint16_t)out);  // 8 groups = 16 bits
-      won_lost = n_won | (n_lost << 16);
-    }
+    for (int j = 0; j < (COMMIT ? GPL / 2 : 1); ++j) m.c[j] = kFullPair;
   }
-
-  const uint32_t wl = VOTES ? wave_sum_u32(won_lost) : 0u;
-  if ((tid & 63) == 0) {
-    uint4 t;
-    t.x = n_changed;
-    t.y = wl & 0xffffu;
-    t.z = wl >> 16;
-    t.w = 0;
-    stg_u4(a.partials + ((uint64_t)tile * kWaves + (tid >> 6)), t);
-  }
+}
+template <int N, int GPL, bool COMMIT, bool GATED, bool VOTES, int POLICY>
+static __global__ __launch_bounds__(kBlock) void sweep_set_voters_kernel(const VoterSweepArgs* __restrict__ tab, uint32_t want_bits) {
+#define RAFTQ_VT_PROLOGUE                                 \
+  VoterSweepArgs va = tab[blockIdx.y];                    \
+  if (!want_bits) va.s.changed_bits = nullptr;            \
+  const SweepArgs& a = va.s;                              \
+  const uint32_t tid = threadIdx.x, tile = blockIdx.x;    \
+  TileMasks<GPL, COMMIT> tm;                              \
+  tile_masks<N, GPL, COMMIT, VOTES, NT>(tm, va.voters, tile);
+#define RAFTQ_VT_VMASK(at) tm.v
+#define RAFTQ_VT_CMASK(j, at) tm.c[j]
+#include "raftq_sweep_voters_tile.inc"
+#undef RAFTQ_VT_PROLOGUE
+#undef RAFTQ_VT_VMASK
+#undef RAFTQ_VT_CMASK
 }
 
 // "every slot votes" written out, for a handle whose first masks arrive as deltas: groups [0, n_groups) get `full`
@@ -1659,42 +1636,35 @@ static __global__ __launch_bounds__(kBlock) void tick_kernel(TickArgs a) { tick_
 // test is folded into `hup` in front of the ballot that decides whether the wave draws at all; no second pass, no LDS.
 // A kernel of its own, tick_tile<1>'s text restated, not a flag of tick_tile: the parents (tick_kernel, tick_set_kernel) keep
 // their assembly (profiles/r13/isa_unchanged.txt).
+// The block's statements live in raftq_tick_voters_block.inc, which is expanded here and in tick_set_voters_kernel below.
 static __global__ __launch_bounds__(kBlock) void tick_voters_kernel(TickArgs a, const uint16_t* __restrict__ voters /* [ld] */, uint32_t self) {
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint64_t key = tick_key(a.seed, a.tick_no);  // wave-uniform
-  const uint64_t blk = blockIdx.x;
-  const uint64_t g = (blk * kBlock + tid) * 4;
-  const uint32_t roles = ldg<false>(reinterpret_cast<const uint32_t*>(a.role + g));
-  const u32x4 el = ldg<false>(reinterpret_cast<const u32x4*>(a.elapsed + g));
-  const uint64_t vm = ldg<false>(reinterpret_cast<const uint64_t*>(voters + g));  // (padding groups hold 0: they never act anyway)
-  uint32_t e[4] = {el.x, el.y, el.z, el.w};
-  uint32_t acts = 0;
-  uint32_t n_hup = 0, n_beat = 0;  // wave-uniform
-  uint64_t hb[4], bb[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const uint32_t role = (roles >> (8 * k)) & 0xffu;
-    const bool valid = g + k < a.n_groups;
-    const bool mine = (((uint32_t)(vm >> (16 * k)) >> self) & 1u) != 0;
-    const bool idle = role != 2u && !mine;  // tickElection: `if !r.promotable() { r.elapsed = 0; return }`
-    uint32_t v = e[k] + 1;
-    const bool beat = role == 2u && v >= a.heartbeat_tick;
-    const int64_t d = (int64_t)v - (int64_t)a.election_tick;
-    bool hup = role != 2u && mine && d >= 0;
-    if (__ballot(hup) != 0) hup = hup && d > (int64_t)tick_mod(tick_rand(key, (uint32_t)g + k), a.election_tick, a.et_magic);
-    const uint32_t act = !valid ? 0u : (hup ? 1u : (beat ? 2u : 0u));
-    e[k] = !valid ? e[k] : ((act || idle) ? 0u : v);
-    acts |= act << (8 * k);
-    hb[k] = __ballot(act == 1u);
-    bb[k] = __ballot(act == 2u);
-    n_hup += __popcll(hb[k]);
-    n_beat += __popcll(bb[k]);
-  }
-  u32x4 out;
-  out.x = e[0]; out.y = e[1]; out.z = e[2]; out.w = e[3];
-  stg<false>(reinterpret_cast<u32x4*>(a.elapsed + g), out);
-  stg<false>(reinterpret_cast<uint32_t*>(a.action + g), acts);
-  tick_chunk_out(a, blk * kWaves + wave, lane, hb, bb, n_hup, n_beat);
+#define RAFTQ_TV_MASKS(at) ldg<false>(reinterpret_cast<const uint64_t*>(voters + at))
+#include "raftq_tick_voters_block.inc"
+#undef RAFTQ_TV_MASKS
+}
+
+// A Tick of every member of a sweep set in ONE dispatch when at least one member asks promotable() (raftq_set_create_voters with
+// raftq_tick_set_voters on a masked member): blockIdx.y = member, blockIdx.x = the 1,024-group block -- tick_voters_kernel's
+// shape, 4 groups per lane, one 8-byte mask load beside the elapsed load.  The table carries the member's TickArgs, its mask
+// pointer and its self slot; a null pointer (no masks, or the switch off) means `mine` is true everywhere, and the member ticks
+// exactly as tick_kernel would.  tick_no advances by `ticks_since` from what the table holds, as in tick_set_kernel.
+struct TickVotersArgs {
+  TickArgs t;
+  const uint16_t* voters;
+  uint32_t self, pad;
+};
+__device__ __forceinline__ uint64_t tick_masks_or_all(const uint16_t* voters /* wave-uniform */, uint64_t at) {
+  return voters != nullptr ? ldg<false>(reinterpret_cast<const uint64_t*>(voters + at)) : ~0ull;
+}
+static __global__ __launch_bounds__(kBlock) void tick_set_voters_kernel(const TickVotersArgs* __restrict__ tab, uint64_t ticks_since) {
+  const TickVotersArgs m = tab[blockIdx.y];
+  TickArgs a = m.t;
+  a.tick_no += ticks_since;
+  const uint16_t* const voters = m.voters;
+  const uint32_t self = m.self;
+#define RAFTQ_TV_MASKS(at) tick_masks_or_all(voters, at)
+#include "raftq_tick_voters_block.inc"
+#undef RAFTQ_TV_MASKS
 }
 
 // The set dispatch at the sweep's access shape: a WAVE owns whole 1,024-group blocks -- the four

@@ -532,15 +532,17 @@ class SweepSet:
 
     Results are those of sweeping every member on its own; the members stay usable
     (read-backs, deltas, per-member counts) between set sweeps.  Close the set before
-    its members."""
+    its members.  voters=True (raftq_set_create_voters): members may hold voter masks, and
+    load, change and drop them while the set lives; each is swept and ticked over its own voters."""
 
-    def __init__(self, engines):
+    def __init__(self, engines, voters: bool = False):
         self._lib = _lib.load()
         self.engines = list(engines)
         n = len(self.engines)
         arr = (C.c_void_p * max(n, 1))(*[e._h.value for e in self.engines])
         self._s = C.c_void_p(None)
-        rc = self._lib.raftq_set_create(arr if n else None, n, C.byref(self._s))
+        create = self._lib.raftq_set_create_voters if voters else self._lib.raftq_set_create
+        rc = create(arr if n else None, n, C.byref(self._s))
         if rc != 0:
             self._s = C.c_void_p(None)
             raise RaftqError(rc, (self._lib.raftq_set_last_error(None) or b"raftq_set_create failed").decode())
