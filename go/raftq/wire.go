@@ -352,12 +352,25 @@ func (e *Engine) SetBcastVoters(on bool) error {
 	return e.err(C.raftq_bcast_set_voters(e.h, v))
 }
 
+// SetRespondLead opts the engine in to (or out of) StepFramesRespond's answer to a won election (raftq_respond_set_lead): an
+// OutBecameLeader result inside its group's device-answered prefix is then flagged OutfAnswered and becomeLeader's broadcast --
+// one MsgApp{Index: lastIndex-1, LogTerm: the old lastTerm, Entries: [the empty entry]} per peer -- is in out; the caller still
+// appends the empty entry to its own log and WAL, sets every Next to lastIndex+1 and sends nothing.  len(out) must then be at
+// least n*(N-1)*RespondLeadFrameMax.  Off by default; no batch may be in flight.
+func (e *Engine) SetRespondLead(on bool) error {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	return e.err(C.raftq_respond_set_lead(e.h, v))
+}
+
 // StepFramesRespond is StepFrames plus the messages its results call for, built and marshalled on the device
 // (raftq_step_frames_respond; raft.go:268-270 -> :227-230): MsgAppResp / MsgVoteResp / MsgHeartbeatResp to the senders and the
 // commit broadcast of a group whose at-tail bit is set (atTail: one bit per group, nil = none).  out receives rafthttp frames,
 // peer-major: peerOff[p] .. peerOff[p+1] (len N + 1) are peer p's frames, respOff (nil, or len >= n*(N-1)+1) their byte
 // offsets.  A result flagged OutfAnswered is answered: send nothing for it.  len(out) must be at least
-// n*(N-1)*RespondFrameMax.  Every slice must be page-locked (HostAlloc).
+// n*(N-1)*RespondFrameMax (RespondLeadFrameMax after SetRespondLead(true)).  Every slice must be page-locked (HostAlloc).
 func (e *Engine) StepFramesRespond(stream []byte, frameOff []uint64, tailAppends bool, msgs []WireMsg, ents []WireEnt, atTail []uint64,
 	out []byte, respOff, peerOff []uint64) (nEnts, nResp, respBytes uint64, err error) {
 	n := len(frameOff) - 1
@@ -499,10 +512,12 @@ func (e *Engine) TickElectFrames(flags uint, hupCap, beatCap uint64, camp []Step
 	return t, uint64(c.n_msgs), uint64(c.bytes), nil
 }
 
-// OutfAnswered / RespondFrameMax:RAFTQ_OUTF_ANSWERED, RAFTQ_RESPOND_FRAME_MAX (include/raftq_wire.h)
+// OutfAnswered / RespondFrameMax / RespondLeadFrameMax: RAFTQ_OUTF_ANSWERED, RAFTQ_RESPOND_FRAME_MAX,
+// RAFTQ_RESPOND_LEAD_FRAME_MAX (include/raftq_wire.h)
 const (
-	OutfAnswered    = 0x10
-	RespondFrameMax = 83
+	OutfAnswered        = 0x10
+	RespondFrameMax     = 83
+	RespondLeadFrameMax = 109
 )
 
 // WalSaveBegin / WalSaveEnd: rc.wal.Save (raft.go:228) in two halves, so that a turn's WAL encode and its outbound marshal

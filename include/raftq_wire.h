@@ -254,8 +254,8 @@ int raftq_step_frames_packed(raftq_t* h, const void* stream, uint64_t nbytes, co
  *   RAFTQ_OUT_PROGRESS + RAFTQ_OUTF_COMMITTED after a non-rejecting MsgAppResp, at_tail bit still set (bcastAppend with every
  *                               follower at the tail): N - 1 empty MsgApp{Term, Index: lastIndex, LogTerm: lastTerm, Commit},
  *                               lastIndex / lastTerm / Commit as they stand AT THAT MESSAGE
- * Everything else stays the caller's and is not flagged: RAFTQ_OUT_APPEND, RAFTQ_OUT_BECAME_LEADER, resends and reject
- * backoff, HELD / DEFERRED / SKIPPED / NONE.  A result the caller may have to answer itself (any of those that sends, a
+ * Everything else stays the caller's and is not flagged: RAFTQ_OUT_APPEND, RAFTQ_OUT_BECAME_LEADER (unless raftq_respond_set_lead,
+ * below, opted the handle in), resends and reject backoff, HELD / DEFERRED / SKIPPED / NONE.  A result the caller may have to answer itself (any of those that sends, a
  * MsgAppResp while the group's bit is clear) ends its group's device-answered prefix: the group's later results of the batch
  * are not answered either, so per (peer, group) the frames keep the order the host's own answers would have.
  * at_tail ([ceil(G / 64)] words, bit g = group g; NULL = all clear): the caller's word that it leads g and every follower's
@@ -281,9 +281,28 @@ int raftq_step_frames_packed(raftq_t* h, const void* stream, uint64_t nbytes, co
  * with no member other than self is flagged RAFTQ_OUTF_ANSWERED and builds ZERO frames -- the host would have sent to nobody
  * either.  The device-answered prefix, the clearing of at_tail bits, stalls and the replay are untouched.  With the switch on
  * and no masks loaded the call is what it always was.  RAFTQ_ESTATE, before anything is applied: voter masks loaded on a handle
- * that did not opt in with raftq_bcast_set_voters -- whatever raftq_step_set_voters and raftq_tick_set_voters say. */
+ * that did not opt in with raftq_bcast_set_voters -- whatever raftq_step_set_voters and raftq_tick_set_voters say.
+ *
+ * becomeLeader's broadcast (raftq_respond_set_lead(h, 1), below): a RAFTQ_OUT_BECAME_LEADER inside its group's device-answered
+ * prefix is answered too, with one frame for every slot p != self:
+ *   MsgApp{Term, Index: lastIndex - 1, LogTerm: lastTerm as it stood BEFORE becomeLeader, Commit: committed after the message,
+ *          Entries: [Entry{Type: 0, Term, Index: lastIndex, Data: nil}]}          (lastIndex = the empty entry's, the result's index)
+ * -- byte for byte what raftq_wire_encode makes of the record bcastAppend builds after reset() put every Next at lastIndex.  The
+ * result carries RAFTQ_OUTF_ANSWERED: the caller still appends the empty entry to its own log and WAL, sets every Next to
+ * lastIndex + 1 and sends nothing.  Such a result does not end the prefix, and the broadcast leaves every follower at the tail: from
+ * that message on the group counts as at the tail, whatever at_tail said and with at_tail == NULL too, until a later message clears
+ * it as always (a rejection backed off for, a heartbeat response below the tail, a step-down) -- a committing ack later in the same
+ * batch gets the usual empty MsgApps, behind the entry frame in every peer's slice.  A win behind a result that ended the prefix is
+ * the caller's, like every other kind (the rule is stated for completeness: no sequence of frames reaches it through this call --
+ * only MsgHup makes a candidate, frames carry none, and the one thing that ends a candidate's prefix, a held MsgProp, defers the
+ * grant behind it).  Over members the broadcast goes to the slots of voters[g], a group with no member but self
+ * is flagged and builds zero frames.  The entry headers are written into the encoder's input in HBM, one slot per result; they never
+ * exist in host memory (a stalled batch's replay writes them again).  cap must then be at least n * (N - 1) *
+ * RAFTQ_RESPOND_LEAD_FRAME_MAX: RAFTQ_RESPOND_FRAME_MAX plus the entries field of one empty entry at its largest -- field tag and
+ * length (2), the tags of type, term and index (3), a one-byte type, term and index of ten bytes each. */
 #define RAFTQ_OUTF_ANSWERED 0x10u /* result flag: the messages this result calls for are in `out` (built on the device) */
 #define RAFTQ_RESPOND_FRAME_MAX 83u
+#define RAFTQ_RESPOND_LEAD_FRAME_MAX 109u /* = RAFTQ_RESPOND_FRAME_MAX + 26 */
 int raftq_step_frames_respond(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off /*[n+1]*/, uint64_t n, int tail_appends,
                               raftq_wire_msg_t* msgs /*[n]*/, raftq_wire_ent_t* ents /*[ents_cap]|NULL*/, uint64_t ents_cap,
                               const uint64_t* at_tail /*[ceil(G/64)] bitmap | NULL*/, void* out, uint64_t cap,
@@ -362,6 +381,16 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
  * own authority, as raftq_tick_elect_frames does.  With all three switches on every frame a node builds on the device goes to a
  * group's members; what remains of conf changes is host work (ConfChange entries through raftq_node: not built). */
 int raftq_bcast_set_voters(raftq_t* h, int on);
+
+/* raftq_step_frames_respond's fifth kind: becomeLeader's broadcast ("becomeLeader's broadcast" in that call's paragraph).  0, the
+ * default: RAFTQ_OUT_BECAME_LEADER stays the caller's and ends its group's prefix -- the call launches the kernels it always did and
+ * writes the bytes and flags it always did, under the cap rule it always had.  1: the win is answered on the device and cap must be
+ * at least n * (N - 1) * RAFTQ_RESPOND_LEAD_FRAME_MAX (below it: RAFTQ_EINVAL before anything is enqueued, nothing applied).
+ * Anything but 0 or 1 is RAFTQ_EINVAL; the handle must be idle (RAFTQ_ESTATE with a Step batch in flight); a NULL handle returns
+ * an error without touching a device.  A property of the handle, like the other switches: raftq_clone_state does not copy it.  Only
+ * raftq_step_frames_respond reads it: raftq_step_frames, raftq_tick_elect_frames (whose one-voter win has nobody to send to) and
+ * raftq_node's turns are what they were. */
+int raftq_respond_set_lead(raftq_t* h, int on);
 
 /* A node's heartbeat round (raft.go:223-224 -> :230: rc.node.Tick() -> tickHeartbeat -> Step(MsgBeat) -> bcastHeartbeat ->
  * rc.transport.Send) as ONE submission with one wait: the Tick, its lists, and the heartbeats the Tick calls for, built and

@@ -125,6 +125,8 @@ struct raftq {
                                    // device-built rounds go to each group's own members (the same kind of property as step_voters)
   bool bcast_voters = false;       // raftq_bcast_set_voters: with masks loaded raftq_step_frames_respond's commit broadcast and
                                    // raftq_propose_frames' bcastAppend go to each group's own members (the same kind of property)
+  bool resp_lead = false;          // raftq_respond_set_lead: raftq_step_frames_respond answers RAFTQ_OUT_BECAME_LEADER too (the *_lead_kernel
+                                   // walks, resp_scatter_lead_kernel); the same kind of property
   int step_walk_mode = 1;          // 1 = lists (default), 0 = always the sorted walk (RAFTQ_STEP_WALK=sort)
   uint32_t step_stalls_in_a_row = 0, step_sorted_left = 0;  // back-off from the list walk under hot-group traffic
   uint64_t step_replays = 0;       // batches that went through the sorted path after a stall
@@ -317,6 +319,7 @@ struct RespPlan {
   void* v_out = nullptr;
   uint64_t* v_resp_off = nullptr;
   uint64_t* peer_off = nullptr;        // the caller's (host) array, N + 1 words
+  bool lead = false;                   // raftq_respond_set_lead: the encoder's input has an entry array, one slot per result
 };
 int respond_prepare(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off, const void* msgs, const void* ents,
                     const uint64_t* at_tail, void* out, uint64_t cap, uint64_t* resp_off, uint64_t* peer_off, uint64_t n, RespPlan* p);

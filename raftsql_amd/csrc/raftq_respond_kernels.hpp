@@ -224,4 +224,77 @@ static __global__ __launch_bounds__(kBlock) void resp_scatter_voters_kernel(Resp
   }
 }
 
+// ---- the layout with becomeLeader's broadcast in it (raftq_respond_set_lead) -------------------------------------------------------
+// A twin of (3), over every slot (voters == nullptr) or over members; (1) and (2) are shared -- a win is kind == kMsgApp, which they
+// count as a broadcast already.  What is new: a record with pad == 1 carries the empty entry of the new term.  Its header goes into
+// the encoder's entry array in HBM at slot i, the result's own position (ent_first = i, n_ents = 1: no scan), and every frame of the
+// broadcast names that one slot.  Slots of results that carry no entry are never read.  A kernel of its own with the new arguments
+// behind the parents': those keep their kernarg offsets and their assembly.
+static __global__ __launch_bounds__(kBlock) void resp_scatter_lead_kernel(RespLayout L, WireMsg* __restrict__ enc, uint64_t n_max,
+                                                                          const uint16_t* __restrict__ voters, WireEnt* __restrict__ ents) {
+  __shared__ uint32_t wc[kWaves][kMaxPeers];
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  RespRec r{};
+  if (i < L.n) r = L.resp[i];
+  const bool valid = i < L.n && r.stamp == L.stamp && r.kind != 0;
+  uint32_t to = 0;
+  if (voters != nullptr) {
+    to = resp_to_voters(r, valid, L, voters);
+  } else {
+#pragma unroll
+    for (uint32_t p = 0; p < (uint32_t)kMaxPeers; ++p) to |= resp_to(r, valid, p, L) ? 1u << p : 0u;
+  }
+  const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
+  uint32_t in_wave[kMaxPeers];
+#pragma unroll
+  for (uint32_t p = 0; p < (uint32_t)kMaxPeers; ++p) {
+    const uint64_t b = __ballot(((to >> p) & 1u) != 0);
+    in_wave[p] = (uint32_t)__popcll(b & below);
+    if (lane == 0) wc[wave][p] = (uint32_t)__popcll(b);
+  }
+  __syncthreads();
+  if (to != 0) {
+    const bool lead = r.kind == kMsgApp && r.pad == 1;
+    if (lead) {  // (i < L.n: the array has one slot per result)
+      WireEnt e;
+      e.term = r.term;
+      e.index = r.index + 1;
+      e.data_off = 0;
+      e.data_len = 0;
+      e.type = 0;
+      ents[i] = e;
+    }
+    WireMsg m;
+    m.group = r.group;
+    m.term = r.term;
+    m.log_term = r.log_term;
+    m.index = r.index;
+    m.commit = r.commit;
+    m.reject_hint = 0;
+    m.from = L.self;
+    m.type = r.kind;
+    m.reject = r.reject;
+    m.flags = 0;
+    m.ent_first = lead ? (uint32_t)i : 0u;
+    m.n_ents = lead ? 1u : 0u;
+#pragma unroll
+    for (uint32_t p = 0; p < (uint32_t)kMaxPeers; ++p) {
+      if (((to >> p) & 1u) == 0) continue;
+      uint64_t at = L.peer_off[p] + L.blk_off[(uint64_t)blockIdx.x * kMaxPeers + p] + in_wave[p];
+      for (uint32_t w = 0; w < wave; ++w) at += wc[w][p];
+      m.to = (uint8_t)p;
+      enc[at] = m;
+    }
+  }
+  // fillers: the encoder counts them as refused and writes nothing for them
+  const uint64_t total = L.peer_off[L.n_peers];
+  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+  for (uint64_t k = total + i; k < n_max; k += stride) {
+    WireMsg f{};
+    f.to = 0xff;
+    enc[k] = f;
+  }
+}
+
 }  // namespace raftqk

@@ -385,6 +385,9 @@ struct WireSrc {
 // walks of a raftq_step_frames_respond call (resp_on: the first pass and a stalled batch's replay) on a handle that opted in to
 // raftq_bcast_set_voters -- on its own authority, as raftq_tick_elect_frames uses the masked Step
 static bool masked_step(const raftq_t* h) { return h->voters != nullptr && (h->step_voters || (h->resp_on && h->bcast_voters)); }
+// raftq_respond_set_lead: the walks of a raftq_step_frames_respond call (the first pass and a stalled batch's replay) are the
+// *_lead_kernel forms, whose respond() answers RAFTQ_OUT_BECAME_LEADER too; every other caller of the walks launches what it always did
+static bool lead_step(const raftq_t* h) { return h->resp_on && h->resp_lead; }
 
 // key -> stable radix sort -> walk, on the handle's stream (the path that takes runs of any length)
 static int enqueue_sorted_walk(raftq_t* h, const Scratch& s, uint64_t n, int end_bit, uint8_t recs, void* outs) {
@@ -396,7 +399,15 @@ static int enqueue_sorted_walk(raftq_t* h, const Scratch& s, uint64_t n, int end
   HIPCHK(h, hipGetLastError());
   int in_b = 0;  // which pair of buffers the sorted (group, batch position) pairs end up in
   HIPCHK(h, raftqk::radix_sort_pairs(h->stream, s.sort_scratch, s.keys_in, s.order_in, s.keys_out, s.order_out, n, end_bit, &in_b));
-  if (masked_step(h))
+  if (lead_step(h) && masked_step(h))
+    hipLaunchKernelGGL(step_lead_voters_kernel, grid, dim3(kBlock), 0, h->stream, node_arrays(h, recs), (const MsgRec*)s.msgs,
+                       (const uint64_t*)(in_b ? s.keys_out : s.keys_in), (const uint32_t*)(in_b ? s.order_out : s.order_in), outs,
+                       h->step_compact, n, s.n_heads, (const unsigned int*)bad, (const uint16_t*)h->voters);
+  else if (lead_step(h))
+    hipLaunchKernelGGL(step_lead_kernel, grid, dim3(kBlock), 0, h->stream, node_arrays(h, recs), (const MsgRec*)s.msgs,
+                       (const uint64_t*)(in_b ? s.keys_out : s.keys_in), (const uint32_t*)(in_b ? s.order_out : s.order_in), outs,
+                       h->step_compact, n, s.n_heads, (const unsigned int*)bad);
+  else if (masked_step(h))
     hipLaunchKernelGGL(step_voters_kernel, grid, dim3(kBlock), 0, h->stream, node_arrays(h, recs), (const MsgRec*)s.msgs,
                        (const uint64_t*)(in_b ? s.keys_out : s.keys_in), (const uint32_t*)(in_b ? s.order_out : s.order_in), outs,
                        h->step_compact, n, s.n_heads, (const unsigned int*)bad, (const uint16_t*)h->voters);
@@ -427,7 +438,17 @@ static int enqueue_list_walk(raftq_t* h, const Scratch& s, uint64_t n, uint8_t r
   }
   hipLaunchKernelGGL(step_link_kernel, dim3(blocks + in_link.blocks), dim3(kBlock), 0, h->stream, (const MsgRec*)s.msgs, n, h->G,
                      h->N, h->step_msg_flags, recs, (NodeRec*)h->node_rec, s.next, bad, h->step_stall, s.outs, h->step_compact, in_link);
-  if (masked_step(h)) {
+  if (lead_step(h)) {
+    HIPCHK(h, hipGetLastError());  // (the link kernel's, before the twin's launch can hide it)
+    if (masked_step(h))
+      hipLaunchKernelGGL(step_lists_lead_voters_kernel, dim3(blocks + in_walk.blocks), dim3(kBlock), 0, h->stream, node_arrays(h, recs),
+                         (const MsgRec*)s.msgs, s.outs, h->step_compact, n, h->G, (const uint32_t*)s.next, s.n_heads,
+                         skipped, (const unsigned int*)bad, (const unsigned int*)h->step_stall, in_walk, (const uint16_t*)h->voters);
+    else
+      hipLaunchKernelGGL(step_lists_lead_kernel, dim3(blocks + in_walk.blocks), dim3(kBlock), 0, h->stream, node_arrays(h, recs),
+                         (const MsgRec*)s.msgs, s.outs, h->step_compact, n, h->G, (const uint32_t*)s.next, s.n_heads,
+                         skipped, (const unsigned int*)bad, (const unsigned int*)h->step_stall, in_walk);
+  } else if (masked_step(h)) {
     HIPCHK(h, hipGetLastError());  // (the link kernel's, before the twin's launch can hide it)
     hipLaunchKernelGGL(step_lists_voters_kernel, dim3(blocks + in_walk.blocks), dim3(kBlock), 0, h->stream, node_arrays(h, recs),
                        (const MsgRec*)s.msgs, s.outs, h->step_compact, n, h->G, (const uint32_t*)s.next, s.n_heads,
@@ -931,13 +952,16 @@ int raftq_step_frames_respond(raftq_t* h, const void* stream, uint64_t nbytes, c
     return fail(h, RAFTQ_ESTATE, std::string(who) + ": the handle has not opted in to RAFTQ_MSGF_* (raftq_step_set_msg_flags)");
   if (h->N < 2) return fail(h, RAFTQ_EINVAL, std::string(who) + ": a single-peer group has nobody to answer -- use raftq_step_frames");
   // the exact worst case: every result a commit broadcast (N - 1 frames) of RAFTQ_RESPOND_FRAME_MAX bytes -- refused before
-  // anything runs, so a call that has stepped never fails for output space
+  // anything runs, so a call that has stepped never fails for output space.  With raftq_respond_set_lead on every result may be
+  // becomeLeader's broadcast instead, whose frames carry the empty entry: RAFTQ_RESPOND_LEAD_FRAME_MAX
   const uint64_t n_max = n * (h->N - 1);
-  if (n_max > 0x7ffffffeull || n_max > (((uint64_t)1 << 31) / RAFTQ_RESPOND_FRAME_MAX))
-    return fail(h, RAFTQ_EINVAL, std::string(who) + ": batch too large (n * (N - 1) * RAFTQ_RESPOND_FRAME_MAX must stay within 2^31 bytes)");
-  if (cap < n_max * RAFTQ_RESPOND_FRAME_MAX)
-    return fail(h, RAFTQ_EINVAL, std::string(who) + ": cap is below n * (N - 1) * RAFTQ_RESPOND_FRAME_MAX = " +
-                                     std::to_string(n_max * RAFTQ_RESPOND_FRAME_MAX) + " bytes -- nothing was applied");
+  const uint64_t frame_max = h->resp_lead ? RAFTQ_RESPOND_LEAD_FRAME_MAX : RAFTQ_RESPOND_FRAME_MAX;
+  const char* frame_max_name = h->resp_lead ? "RAFTQ_RESPOND_LEAD_FRAME_MAX" : "RAFTQ_RESPOND_FRAME_MAX";
+  if (n_max > 0x7ffffffeull || n_max > (((uint64_t)1 << 31) / frame_max))
+    return fail(h, RAFTQ_EINVAL, std::string(who) + ": batch too large (n * (N - 1) * " + frame_max_name + " must stay within 2^31 bytes)");
+  if (cap < n_max * frame_max)
+    return fail(h, RAFTQ_EINVAL, std::string(who) + ": cap is below n * (N - 1) * " + frame_max_name + " = " +
+                                     std::to_string(n_max * frame_max) + " bytes -- nothing was applied");
   raftq_detail::RespPlan rp;
   if (int rc = raftq_detail::respond_prepare(h, stream, nbytes, frame_off, msgs, ents, at_tail, out, cap, resp_off, peer_off, n, &rp)) return rc;
   // from here on: raftq_step_frames, with the walks answering (node_arrays), then the layout and the marshal behind them

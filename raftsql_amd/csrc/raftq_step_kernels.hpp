@@ -108,7 +108,8 @@ constexpr uint8_t kFlagAnswered = 0x10;  // RAFTQ_OUTF_ANSWERED: the messages th
 
 // What result i calls for, as the walk lane that stepped it saw the group (raftq_step_frames_respond; raftq_respond_kernels.hpp
 // lays the frames out).  kind = the raftpb type of the message(s) to send, 0 = none built on the device; kMsgApp is the commit
-// broadcast: one empty MsgApp to every peer but self.  Valid only with this call's stamp (stale records read as "none").
+// broadcast: one empty MsgApp to every peer but self; with pad = 1 (NodeT's LEAD form only) it is becomeLeader's broadcast and
+// carries the empty entry {Term: term, Index: index + 1}.  Valid only with this call's stamp (stale records read as "none").
 struct RespRec {
   uint64_t group, term, index, log_term, commit;
   uint32_t stamp;
@@ -248,7 +249,10 @@ constexpr uint32_t kNil = 0xffffffffu;
 // group and no dependent latency.  Everything else -- what is stored, reset()'s N slots, whose words are recorded -- is the
 // unmasked form's: a non-voter's Match and vote are kept as always and merely do not count.
 // `Node` stays the name of the unmasked form (elect_build_kernel, propose_build_kernel / propose_commit_kernel, the respond path).
-template <bool MASKED>
+// LEAD (raftq_respond_set_lead, raftq_step_frames_respond only): respond() answers RAFTQ_OUT_BECAME_LEADER too -- becomeLeader's
+// broadcast, one MsgApp with the empty entry to every peer.  The frame's LogTerm is the lastTerm become_leader() overwrites, so
+// that form keeps it (last_term_was).  Every `if constexpr (LEAD)` is empty in the other forms: they compile to what they were.
+template <bool MASKED, bool LEAD = false>
 struct NodeT {
   const NodeArrays& a;
   uint64_t g;
@@ -268,6 +272,7 @@ struct NodeT {
   uint8_t role0;
   bool vw_known = false, vw_dirty = false, elapsed_reset = false;
   uint32_t vmask = 0;  // MASKED only: voters[g], bit p = slot p votes in this group
+  uint64_t last_term_was = 0;  // LEAD only: lastTerm as it stood before the latest become_leader()
 
   __device__ NodeT(const NodeArrays& arr, uint64_t group, const uint16_t* voters = nullptr) : a(arr), g(group) {
     if constexpr (MASKED) vmask = voters[g];
@@ -412,6 +417,7 @@ struct NodeT {
   }
   // raft.becomeLeader incl. appendEntry(empty entry of the new term)
   __device__ void become_leader() {
+    if constexpr (LEAD) last_term_was = last_term;
     reset(term);
     lead = a.self + 1;
     role = kLeader;
@@ -493,7 +499,18 @@ struct NodeT {
           }
           break;
         case kOutNone: case kOutSkipped: break;
-        default: host_owns = true;  // MsgApp left to the log's owner, a new leader's broadcast, held / deferred messages
+        default:
+          if constexpr (LEAD) {
+            // becomeLeader's bcastAppend: reset() has put every Next at the empty entry's index, so every peer gets
+            // MsgApp{Index: lastIndex - 1, LogTerm: the old lastTerm, Entries: [the empty entry]} (pad = 1: the layout writes the
+            // entry header) -- which leaves every follower at the tail, whatever the caller's bitmap said
+            if (o.type == kOutBecameLeader) {
+              r.kind = kMsgApp; r.index = o.index - 1; r.log_term = last_term_was; r.commit = committed; r.pad = 1;
+              at_tail = true;
+              break;
+            }
+          }
+          host_owns = true;  // MsgApp left to the log's owner, a new leader's broadcast, held / deferred messages
       }
     }
     if (r.kind != 0) o.flags |= kFlagAnswered;
@@ -679,6 +696,28 @@ static __global__ __launch_bounds__(kBlock) void step_link_kernel(const MsgRec* 
 #undef RAFTQ_WALK_MASKED
 #undef RAFTQ_WALK_PARAM
 #undef RAFTQ_WALK_VOTERS
+// ... and the two walks twice more as *_lead_kernel / *_lead_voters_kernel: NodeT's LEAD form (raftq_respond_set_lead), launched by
+// raftq_step_frames_respond alone.  The tail reports answer nobody and have no such form.
+#define RAFTQ_WALK_NO_DELTAS
+#define RAFTQ_WALK_KERNEL(stem) stem##_lead_kernel
+#define RAFTQ_WALK_MASKED false, true
+#define RAFTQ_WALK_PARAM
+#define RAFTQ_WALK_VOTERS
+#include "raftq_step_walk_kernels.inc"
+#undef RAFTQ_WALK_KERNEL
+#undef RAFTQ_WALK_MASKED
+#undef RAFTQ_WALK_PARAM
+#undef RAFTQ_WALK_VOTERS
+#define RAFTQ_WALK_KERNEL(stem) stem##_lead_voters_kernel
+#define RAFTQ_WALK_MASKED true, true
+#define RAFTQ_WALK_PARAM , const uint16_t* __restrict__ voters
+#define RAFTQ_WALK_VOTERS , voters
+#include "raftq_step_walk_kernels.inc"
+#undef RAFTQ_WALK_KERNEL
+#undef RAFTQ_WALK_MASKED
+#undef RAFTQ_WALK_PARAM
+#undef RAFTQ_WALK_VOTERS
+#undef RAFTQ_WALK_NO_DELTAS
 
 // ---- the record array's bulk paths (raftq_load_node / raftq_read_node: set-up and test traffic, not the hot path) ----------
 static __global__ __launch_bounds__(kBlock) void node_init_kernel(NodeRec* rec, uint64_t n) {

@@ -1,11 +1,14 @@
 // raftq_step_walk_kernels.inc -- the three kernels that run Step's maybeCommit / poll: the sorted walk, the list walk and the log
-// owner's tail reports.  Included TWICE by raftq_step_kernels.hpp (inside namespace raftqk), which sets
-//   RAFTQ_WALK_KERNEL(stem)  the kernel's name: stem_kernel over every slot, stem_voters_kernel over each group's own voters
-//   RAFTQ_WALK_MASKED        NodeT's argument
+// owner's tail reports.  Included FOUR times by raftq_step_kernels.hpp (inside namespace raftqk): over every slot and over each
+// group's own voters, and both once more, without the tail reports, for raftq_respond_set_lead.  Each time it sets
+//   RAFTQ_WALK_KERNEL(stem)  the kernel's name: stem_kernel over every slot, stem_voters_kernel over each group's own voters,
+//                            stem_lead_kernel / stem_lead_voters_kernel for the forms that answer a won election too
+//   RAFTQ_WALK_MASKED        NodeT's argument list: MASKED, or "MASKED, true" for the LEAD forms
 //   RAFTQ_WALK_PARAM         the masked form's extra, LAST parameter (", const uint16_t* __restrict__ voters"): NodeArrays is a
 //                            by-value argument of every Step-family kernel and stays as it is
 //   RAFTQ_WALK_VOTERS        the same, handed to NodeT's constructor (", voters")
-// One text, two kernels each.  Why an include and not a template <bool MASKED> body the kernels call: the inliner simplifies such
+//   RAFTQ_WALK_NO_DELTAS     (optional) the two walks only: leave the tail reports out
+// One text, four walks of each kind and two tail-report kernels.  Why an include and not a template <bool MASKED> body the kernels call: the inliner simplifies such
 // a body BEFORE it meets the kernel (no launch bounds, no noalias arguments, NodeArrays behind a generic reference), and all three
 // unmasked kernels came out different from their parent's -- step_lists_kernel with other loads and another register count
 // (tools/isa_unchanged.py; profiles/r12/README.md).  As an include the unmasked expansion is token for token what it was.
@@ -105,6 +108,7 @@ static __global__ __launch_bounds__(kBlock) void RAFTQ_WALK_KERNEL(step_lists)(N
   node.store();
 }
 
+#ifndef RAFTQ_WALK_NO_DELTAS
 // the log owner's tail reports; records are unique per group within a launch (the host splits
 // repeated groups into successive launches)
 static __global__ __launch_bounds__(kBlock) void RAFTQ_WALK_KERNEL(log_deltas)(NodeArrays a, const LogDeltaRec* __restrict__ d,
@@ -124,3 +128,4 @@ static __global__ __launch_bounds__(kBlock) void RAFTQ_WALK_KERNEL(log_deltas)(N
   node.store(false);
   if (committed_out) committed_out[i] = node.committed;
 }
+#endif

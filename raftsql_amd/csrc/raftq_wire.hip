@@ -717,6 +717,8 @@ StreamCall resp_marshal_call(const raftq_detail::RespPlan& p) {
   StreamCall sc;
   sc.n_tiles = blocks_for(p.n_max);
   sc.seg[0] = {nullptr, 0, p.n_max * sizeof(WireMsg)};
+  // raftq_respond_set_lead: the entry headers too -- one slot per result, written by resp_scatter_lead_kernel
+  if (p.lead) sc.seg[1] = {nullptr, 0, p.n * sizeof(WireEnt)};
   sc.out_bytes = p.cap + 16;
   return sc;
 }
@@ -739,7 +741,9 @@ int raftq_detail::respond_prepare(raftq_t* h, const void* stream, uint64_t nbyte
   HIPCHK(h, h->resp_dev.grow_zeroed(resp_bytes, grown(resp_bytes), h->stream));  // (zeroed: stamp 0 is no call's)
   p->n = n;
   p->n_max = n * (h->N - 1);
-  p->cap = std::min<uint64_t>(cap, p->n_max * RAFTQ_RESPOND_FRAME_MAX);  // what the encoder may write: never more than the worst case
+  p->lead = h->resp_lead;
+  // what the encoder may write: never more than the worst case
+  p->cap = std::min<uint64_t>(cap, p->n_max * (p->lead ? RAFTQ_RESPOND_LEAD_FRAME_MAX : RAFTQ_RESPOND_FRAME_MAX));
   // everything the layout and the marshal will need is allocated NOW, before anything is stepped: a call that has stepped cannot
   // fail for memory (the calls behind the step find the control block, the scratch and the output buffer big enough)
   if (p->n_max != 0) {
@@ -768,11 +772,15 @@ int raftq_detail::respond_enqueue(raftq_t* h, const RespPlan& p) {
   if (p.n_max != 0) {
     StreamCall sc = resp_marshal_call(p);
     if (int rc = stream_prepare(h, sc)) return rc;  // (allocates nothing: respond_prepare reserved this very request)
-    if (members)
+    if (p.lead)  // (one twin for both: a null mask array is "every slot")
+      hipLaunchKernelGGL(resp_scatter_lead_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, (WireMsg*)sc.in.seg[0].dst, p.n_max,
+                         members ? (const uint16_t*)h->voters : (const uint16_t*)nullptr, (WireEnt*)sc.in.seg[1].dst);
+    else if (members)
       hipLaunchKernelGGL(resp_scatter_voters_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, (WireMsg*)sc.in.seg[0].dst, p.n_max, (const uint16_t*)h->voters);
     else
       hipLaunchKernelGGL(resp_scatter_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, (WireMsg*)sc.in.seg[0].dst, p.n_max);
-    if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, p.n_max, (uint64_t)0, (uint64_t)0, (uint8_t*)h->wire_out.d, (uint8_t*)p.v_out,
+    // (the entry array: p.n slots with the switch on, none otherwise)
+    if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, p.n_max, p.lead ? p.n : (uint64_t)0, (uint64_t)0, (uint8_t*)h->wire_out.d, (uint8_t*)p.v_out,
                                p.cap, p.v_resp_off, sc.ctl, h->wire_pin_d + kPinRespond, (const unsigned int*)nullptr, 0u))
       return rc;
   }

@@ -43,6 +43,7 @@ _FORM_DT = {FORM_40: WIRE_MSG40_DT, FORM_HEAD: WIRE_HEAD_DT}
 MSG_APP_RESP = 4
 OUTF_ANSWERED = 0x10  # result flag of raftq_step_frames_respond: the messages the result calls for were built on the device
 RESPOND_FRAME_MAX = 83  # bytes of the largest payload-free frame: cap >= n * (N - 1) * RESPOND_FRAME_MAX
+RESPOND_LEAD_FRAME_MAX = 109  # ... and of the largest frame with one empty entry: the bound once set_respond_lead is on
 
 
 def _u8(b) -> np.ndarray:
@@ -97,6 +98,8 @@ def expand_packed(narrow: np.ndarray, wide: np.ndarray, to_slot: int, form: int)
 
 class WireEngine(NodeEngine):
     """NodeEngine + the codecs of the byte formats either side of Step."""
+
+    _respond_lead = False  # set_respond_lead's word, for respond_cap
 
     # -- raftpb.Message <-> rafthttp stream frames -----------------------------------------
     def wire_encode(self, msgs: np.ndarray, ents: np.ndarray | None = None, pool=b"", out: np.ndarray | None = None,
@@ -229,9 +232,16 @@ class WireEngine(NodeEngine):
         set_tick_voters (no batch may be in flight)"""
         self._chk(self._lib.raftq_bcast_set_voters(self._h, int(on)))
 
+    def set_respond_lead(self, on=True) -> None:
+        """raftq_respond_set_lead: step_frames_respond answers RAFTQ_OUT_BECAME_LEADER too -- becomeLeader's broadcast, one MsgApp
+        with the empty entry per peer, flagged answered; respond_cap then asks for the larger frames (no batch may be in flight)"""
+        self._chk(self._lib.raftq_respond_set_lead(self._h, int(on)))
+        self._respond_lead = int(on) == 1
+
     def respond_cap(self, n: int) -> int:
-        """the `out` size raftq_step_frames_respond needs for n frames (the exact worst case)"""
-        return int(n) * (self.n_peers - 1) * RESPOND_FRAME_MAX
+        """the `out` size raftq_step_frames_respond needs for n frames (the exact worst case; follows set_respond_lead)"""
+        frame_max = RESPOND_LEAD_FRAME_MAX if self._respond_lead else RESPOND_FRAME_MAX
+        return int(n) * (self.n_peers - 1) * frame_max
 
     def step_frames_respond(self, stream: np.ndarray, frame_off: np.ndarray, msgs: np.ndarray, ents: np.ndarray | None, at_tail: np.ndarray | None,
                             out: np.ndarray, resp_off: np.ndarray | None, peer_off: np.ndarray, tail_appends: bool = True, copy: bool = True):
