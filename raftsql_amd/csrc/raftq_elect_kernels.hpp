@@ -7,7 +7,7 @@
 // reset()'s match rows, the vote word with self's grant.  All of it is stated ONCE, in Node (raftq_step_kernels.hpp): a lane
 // loads its group through Node, calls become_candidate() + poll(self, granted) -- the two calls step() makes for a local MsgHup
 // -- and store(), which writes the record and, where they changed, the dense arrays the sweep, the tally and the Tick read.
-// N >= 2 means a quorum of at least two: the candidate's own grant never wins, so becomeLeader is not reachable here.
+// N >= 2 means a quorum of at least two: the candidate's own grant never wins, so becomeLeader is not reachable without masks.
 //
 // Order comes from the Tick's own per-wave counts and popcounts, beat_build_kernel's shape: a workgroup owns one 1,024-group
 // block, ranks its MsgHup bits behind the sum of the earlier waves' counts (or the scan's offsets past 16K waves), compacts the
@@ -48,116 +48,16 @@ __device__ __forceinline__ void vote_store(WireMsg* dst, uint64_t group, uint64_
 }
 
 // One workgroup per 1,024-group block of the Tick (its four waves' 256-group chunks).
-static __global__ __launch_bounds__(kBlock) void elect_build_kernel(ElectArgs e) {
-  __shared__ uint64_t red[kWaves];
-  __shared__ uint32_t mine[kWaves];
-  __shared__ uint32_t ids[kBlock * 4];
-  __shared__ uint64_t n_hup_s, n_beat_s;
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint64_t first_wave = (uint64_t)blockIdx.x * kWaves;
-  // the block's exclusive offset among the MsgHup groups: the sum of the earlier waves' counts, or the scan's offsets
-  uint64_t acc = 0;
-  if (e.wave_off_hup == nullptr) {
-    uint32_t b0 = 0, b1 = 0;
-    uint64_t i = tid;
-    for (; i + kBlock < first_wave; i += 2 * kBlock) {
-      b0 += e.partials[i].x;
-      b1 += e.partials[i + kBlock].x;
-    }
-    if (i < first_wave) b0 += e.partials[i].x;
-    acc = (uint64_t)b0 + b1;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  } else if (lane == 0 && wave == 0) {
-    acc = e.wave_off_hup[first_wave];
-  }
-  if (lane == 0) red[wave] = acc;
-  if (tid < (uint32_t)kWaves) mine[tid] = first_wave + tid < e.n_chunks ? e.partials[first_wave + tid].x : 0u;
-  if (tid == 0) {
-    n_hup_s = e.totals[0];
-    n_beat_s = e.totals[1];
-  }
-  __syncthreads();
-  uint64_t pos = 0;  // rank of this block's first MsgHup group
-  uint32_t tot = 0;  // MsgHup groups of this block
-#pragma unroll
-  for (int k = 0; k < kWaves; ++k) {
-    pos += red[k];
-    tot += mine[k];
-  }
-  const uint64_t n_vb = n_hup_s < e.hup_cap ? n_hup_s : e.hup_cap;
-  const uint64_t n_bb = n_beat_s < e.beat_cap ? n_beat_s : e.beat_cap;
-  const uint64_t n_slices = e.a.n_peers - 1;
-  const uint64_t wv = first_wave + wave;
-  if (wv < e.n_chunks && pos < n_vb) {  // wave-uniform
-    uint32_t loc = 0;
-#pragma unroll
-    for (int k = 0; k < kWaves; ++k) loc += (uint32_t)k < wave ? mine[k] : 0u;
-    const uint64_t below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    uint64_t hb[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) hb[k] = e.hup_bits[wv * 4 + k];
-    uint32_t r = loc + __popcll(hb[0] & below) + __popcll(hb[1] & below) + __popcll(hb[2] & below) + __popcll(hb[3] & below);
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if ((hb[k] >> lane) & 1) ids[r++] = (uint32_t)(wv * 256 + 4ull * lane + k);
-  }
-  __syncthreads();
-  if (pos < n_vb) {
-    const uint64_t left = n_vb - pos;
-    const uint32_t take = left < tot ? (uint32_t)left : tot;  // this block's groups of rank < n_vb
-    WireMsg* const votes = e.enc + n_bb * n_slices;
-    for (uint32_t r = tid; r < take; r += kBlock) {
-      const uint64_t g = ids[r];
-      const uint64_t at = pos + r;
-      const bool known = g < e.a.n_groups;  // (the Tick flags no padding group)
-      uint64_t term = 0, last_index = 0, last_term = 0;
-      u64x2 c0, c1;
-      c0.x = c0.y = c1.x = c1.y = 0;
-      if (known) {
-        Node node(e.a, g);
-        // Step(MsgHup) -> campaign(): the two calls Node::step makes (a quorum is at least two: the own grant does not win)
-        node.become_candidate();
-        uint32_t granted, recorded;
-        node.poll(e.a.self, true, granted, recorded);
-        node.store();
-        term = node.term; last_index = node.last_index; last_term = node.last_term;
-        // == put_result(kFmtS32) of step()'s record: commit carries the candidate's lastTerm
-        c0.x = term; c0.y = last_index;
-        c1.x = last_term;
-        c1.y = (uint64_t)(uint8_t)node.vote | ((uint64_t)kOutCampaign << 16) | ((uint64_t)(kFlagHardState | kFlagAnswered) << 32) |
-               ((uint64_t)node.role << 40);
-      }
-      u64x2* cq = reinterpret_cast<u64x2*>(e.camp + at);
-      cq[0] = c0;
-      cq[1] = c1;
-#pragma unroll
-      for (uint32_t p = 0; p < (uint32_t)kMaxPeers; ++p) {
-        if (p >= e.a.n_peers || p == e.a.self) continue;
-        const uint64_t slice = p < e.a.self ? p : p - 1;
-        vote_store(votes + slice * n_vb + at, g, term, last_term, last_index, e.a.self, known ? p : 0xffu);
-      }
-    }
-  }
-  // fillers behind both sections: the encoder counts them as refused and writes nothing for them
-  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-  for (uint64_t k = (n_bb + n_vb) * n_slices + (uint64_t)blockIdx.x * kBlock + tid; k < (e.beat_cap + e.hup_cap) * n_slices; k += stride) {
-    WireMsg f{};
-    f.to = 0xff;
-    e.enc[k] = f;
-  }
-}
-
-// elect_build_kernel over voters (raftq_tick_set_voters on a handle with voter masks loaded; raftq_beat_kernels.hpp says what the
-// twins share and why the sections stay positional).  Every MsgHup group is promotable -- tick_voters_kernel flags no other --
-// and the lane runs the masked Node, the one step_voters_kernel uses: become_candidate(), poll(self, granted), then exactly the
-// two arms of Node::step's MsgHup case.
+// MASKED -- over voters (raftq_tick_set_voters on a handle with voter masks loaded; raftq_beat_kernels.hpp says why the sections
+// stay positional).  Every MsgHup group is promotable -- tick_voters_kernel flags no other -- and the lane runs the masked Node,
+// the one step_voters_kernel uses: become_candidate(), poll(self, granted), then exactly the two arms of Node::step's MsgHup case.
 //   granted == q_g: the group's only voter is self.  become_leader(), and camp[r] is Step's RAFTQ_OUT_BECAME_LEADER record for
 //     that message: index = the empty entry's, commit = committed (a one-voter group commits its own append), RAFTQ_OUTF_HARDSTATE
 //     (and _COMMITTED when the commit moved) and NOT RAFTQ_OUTF_ANSWERED -- the caller appends the empty entry, as after Step.
 //     Nobody is asked: every vote slot of the group is a filler.
-//   otherwise: RAFTQ_OUT_CAMPAIGN as in elect_build_kernel, a MsgVote to every member p != self, fillers in the other slots.
-static __global__ __launch_bounds__(kBlock) void elect_build_voters_kernel(ElectArgs e, const uint16_t* __restrict__ voters, unsigned long long* members) {
+//   otherwise: RAFTQ_OUT_CAMPAIGN as in the unmasked form, a MsgVote to every member p != self, fillers in the other slots.
+template <bool MASKED>
+__device__ __forceinline__ void elect_build_body(ElectArgs e, const uint16_t* __restrict__ voters, unsigned long long* members) {
   __shared__ uint64_t red[kWaves];
   __shared__ uint32_t mine[kWaves];
   __shared__ uint32_t ids[kBlock * 4];
@@ -168,8 +68,8 @@ static __global__ __launch_bounds__(kBlock) void elect_build_voters_kernel(Elect
   const uint64_t n_slices = e.a.n_peers - 1;
   uint64_t pos;  // rank of this block's first MsgHup group
   uint32_t tot;  // MsgHup groups of this block
-  members_rank<0>(e.hup_bits, e.partials, e.n_chunks, e.wave_off_hup, n_vb, red, mine, ids, pos, tot);
-  uint32_t wrote = 0;
+  tick_rank<0>(e.hup_bits, e.partials, e.n_chunks, e.wave_off_hup, n_vb, red, mine, ids, pos, tot);
+  [[maybe_unused]] uint32_t wrote = 0;
   if (pos < n_vb) {
     const uint64_t left = n_vb - pos;
     const uint32_t take = left < tot ? (uint32_t)left : tot;  // this block's groups of rank < n_vb
@@ -182,25 +82,35 @@ static __global__ __launch_bounds__(kBlock) void elect_build_voters_kernel(Elect
       u64x2 c0, c1;
       c0.x = c0.y = c1.x = c1.y = 0;
       if (g < e.a.n_groups) {  // (the Tick flags no padding group)
-        NodeT<true> node(e.a, g, voters);
-        const uint64_t commit0 = node.committed;
+        NodeT<MASKED> node(e.a, g, voters);
+        [[maybe_unused]] const uint64_t commit0 = node.committed;
         // Step(MsgHup) -> campaign(): the calls Node::step makes
         node.become_candidate();
         uint32_t granted, recorded;
         node.poll(e.a.self, true, granted, recorded);
-        const bool won = granted == node.quorum();  // the own grant is a quorum: self is the group's only voter
-        if (won) node.become_leader();
+        bool won = false;  // the own grant is a quorum: self is the group's only voter (unmasked, a quorum is at least two)
+        if constexpr (MASKED) {
+          won = granted == node.quorum();
+          if (won) node.become_leader();
+        }
         node.store();
         term = node.term; last_index = node.last_index; last_term = node.last_term;
         // == put_result(kFmtS32) of step()'s record: a campaign's commit carries the candidate's lastTerm
-        uint32_t flags = kFlagHardState;  // (the term moved)
-        if (won) flags |= node.committed != commit0 ? kFlagCommitted : 0u;
-        else flags |= kFlagAnswered;
         c0.x = term; c0.y = last_index;
-        c1.x = won ? node.committed : last_term;
-        c1.y = (uint64_t)(uint8_t)node.vote | ((uint64_t)(uint8_t)node.lead << 8) | ((uint64_t)(won ? kOutBecameLeader : kOutCampaign) << 16) |
-               ((uint64_t)flags << 32) | ((uint64_t)node.role << 40);
-        ask = won ? 0u : node.vmask;
+        if constexpr (MASKED) {
+          uint32_t flags = kFlagHardState;  // (the term moved)
+          if (won) flags |= node.committed != commit0 ? kFlagCommitted : 0u;
+          else flags |= kFlagAnswered;
+          c1.x = won ? node.committed : last_term;
+          c1.y = (uint64_t)(uint8_t)node.vote | ((uint64_t)(uint8_t)node.lead << 8) | ((uint64_t)(won ? kOutBecameLeader : kOutCampaign) << 16) |
+                 ((uint64_t)flags << 32) | ((uint64_t)node.role << 40);
+          ask = won ? 0u : node.vmask;
+        } else {
+          c1.x = last_term;
+          c1.y = (uint64_t)(uint8_t)node.vote | ((uint64_t)kOutCampaign << 16) | ((uint64_t)(kFlagHardState | kFlagAnswered) << 32) |
+                 ((uint64_t)node.role << 40);
+          ask = ~0u;
+        }
       }
       u64x2* cq = reinterpret_cast<u64x2*>(e.camp + at);
       cq[0] = c0;
@@ -211,18 +121,17 @@ static __global__ __launch_bounds__(kBlock) void elect_build_voters_kernel(Elect
         const uint64_t slice = p < e.a.self ? p : p - 1;
         const bool member = ((ask >> p) & 1u) != 0;
         vote_store(votes + slice * n_vb + at, g, term, last_term, last_index, e.a.self, member ? p : 0xffu);
-        wrote += member ? 1u : 0u;
+        if constexpr (MASKED) wrote += member ? 1u : 0u;
       }
     }
   }
-  // fillers behind both sections, as in elect_build_kernel
-  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-  for (uint64_t k = (n_bb + n_vb) * n_slices + (uint64_t)blockIdx.x * kBlock + tid; k < (e.beat_cap + e.hup_cap) * n_slices; k += stride) {
-    WireMsg f{};
-    f.to = 0xff;
-    e.enc[k] = f;
-  }
-  members_add(wrote, red, members);
+  fill_refused(e.enc, (n_bb + n_vb) * n_slices, (e.beat_cap + e.hup_cap) * n_slices);  // behind both sections
+  if constexpr (MASKED) members_add(wrote, red, members);
+}
+static __global__ __launch_bounds__(kBlock) void elect_build_kernel(ElectArgs e) { elect_build_body<false>(e, nullptr, nullptr); }
+static __global__ __launch_bounds__(kBlock) void elect_build_voters_kernel(ElectArgs e, const uint16_t* __restrict__ voters, unsigned long long* members) {
+  elect_build_body<true>(e, voters, members);
 }
 
 }  // namespace raftqk
+

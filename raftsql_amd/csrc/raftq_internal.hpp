@@ -126,7 +126,7 @@ struct raftq {
   bool bcast_voters = false;       // raftq_bcast_set_voters: with masks loaded raftq_step_frames_respond's commit broadcast and
                                    // raftq_propose_frames' bcastAppend go to each group's own members (the same kind of property)
   bool resp_lead = false;          // raftq_respond_set_lead: raftq_step_frames_respond answers RAFTQ_OUT_BECAME_LEADER too (the *_lead_kernel
-                                   // walks, resp_scatter_lead_kernel); the same kind of property
+                                   // walks, resp_scatter_lead[_voters]_kernel); the same kind of property
   int step_walk_mode = 1;          // 1 = lists (default), 0 = always the sorted walk (RAFTQ_STEP_WALK=sort)
   uint32_t step_stalls_in_a_row = 0, step_sorted_left = 0;  // back-off from the list walk under hot-group traffic
   uint64_t step_replays = 0;       // batches that went through the sorted path after a stall
@@ -283,10 +283,10 @@ int use_device_idle(raftq_t* h, const char* who);  // + no Step batch in flight 
 // raftq_propose_frames): let through once the handle opted in to raftq_bcast_set_voters -- their broadcasts then go to each group's
 // own members.  Each of the three switches opens its own calls and no others.
 int refuse_voters(raftq_t* h, const char* who, bool step_family = false, bool tick_rounds = false, bool bcast = false);
-// raftq_tick_set_voters on a handle with masks loaded: every Tick launch is tick_voters_kernel's, the rounds are the twins'
+// raftq_tick_set_voters on a handle with masks loaded: every Tick launch is tick_voters_kernel's, the rounds are beat_build_voters_kernel's and elect_build_voters_kernel's
 inline bool masked_tick(const raftq_t* h) { return h->voters != nullptr && h->tick_voters; }
 // raftq_bcast_set_voters on a handle with masks loaded: raftq_step_frames_respond walks with the masked Node and lays its answers
-// out with the resp_*_voters_kernel twins, raftq_propose_frames runs propose_check_voters_kernel / propose_build_voters_kernel
+// out with the resp_*_voters_kernel entry points, raftq_propose_frames runs propose_check_voters_kernel / propose_build_voters_kernel
 inline bool masked_bcast(const raftq_t* h) { return h->voters != nullptr && h->bcast_voters; }
 int self_max_check(raftq_t* h);                 // the self-max word re-derived from the rows for h->self_peer (enqueued)
 int narrow_build(raftq_t* h);                   // the narrow mirror and its word re-derived from the rows (enqueued)

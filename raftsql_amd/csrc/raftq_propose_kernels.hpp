@@ -7,6 +7,10 @@
 // them back over the link -- 2.9 ms of a 4.0 ms turn on one core for 32K groups (profiles/r05/one_node_phases.txt).  The records
 // are a pure function of the group's device-resident state (Term, lastIndex, lastTerm, committed) and of which entries were
 // proposed: nothing the host has to compute, and nothing that has to cross the link.
+//
+// MASKED -- proposals over each group's own members (raftq_bcast_set_voters on a handle with voter masks loaded), the masks as a
+// last argument.  One body per step, one instantiation per entry point (raftq_respond_kernels.hpp); propose_commit_kernel serves
+// both forms.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -28,6 +32,7 @@ struct PropEnt {  // == raftq_prop_ent_t
 static_assert(sizeof(PropRec) == 16 && sizeof(PropEnt) == 16, "record layout");
 
 constexpr uint32_t kPropPayload = 1, kPropGroup = 2, kPropCount = 3, kPropRange = 4, kPropNotLeader = 5, kPropTwice = 6;
+constexpr uint32_t kPropNoMember = 7, kPropCommits = 8;  // over members only
 constexpr uint32_t kPropMaxEnts = 1024;  // raft.Config.MaxSizePerMsg's share of entries (raft.go:157): more go out as the caller's own sends
 
 // Nothing is applied unless every record is sound: a group of this handle, led by this node, named once (the group's list
@@ -36,10 +41,22 @@ constexpr uint32_t kPropMaxEnts = 1024;  // raft.Config.MaxSizePerMsg's share of
 // The records lie in page-locked HOST memory: this kernel reads them there ONCE, coalesced (16 bytes a lane: 1 KB a wave
 // instruction over the link), and leaves a copy in device scratch for the kernel behind it -- round 6's first form had both
 // kernels read the host arrays: 33 + 36 us for 32K groups, all of it link latency (profiles/r06/node_kernel_stats_first.csv).
-static __global__ __launch_bounds__(kBlock) void propose_check_kernel(NodeArrays a, const PropRec* __restrict__ props, uint64_t n,
-                                                                      const PropEnt* __restrict__ pe, uint64_t n_pe, uint64_t pool_bytes,
-                                                                      unsigned int* bad, unsigned int stamp, PropRec* __restrict__ props_d,
-                                                                      PropEnt* __restrict__ pe_d, unsigned long long* why) {
+// MASKED: two more reasons, both read off the masked Node loaded from the record line the check touches anyway (its lst_cnt is
+// the "seen" mark):
+//   kPropNoMember  self's bit is clear in voters[g].  Upstream v2.2's appendEntry would dereference a missing Progress
+//                  (r.prs[r.id]); CHOICE: refuse.
+//   kPropCommits   the commit kernel's sentence "maybeCommit cannot move anything with more than one peer" does not hold over members: a
+//                  one-voter group commits on its own append, and under the 2015-era removeNode (which does not call
+//                  maybeCommit) so does a group whose membership shrank since its last acknowledgement.  Evaluated exactly --
+//                  Match[self] raised to last_index + n_ents as the commit will, then the masked maybe_commit() with its current-term
+//                  gate -- on the lane's copy, which is never stored.  The call has no channel for a commit:
+//                  raftq_apply_log_deltas has, and a tail report with the unchanged tail settles the commit first.
+// Both after the six shared reasons, so a record sound by those is marked (lst_cnt) whatever the new ones say; a refused call's
+// commit kernel takes every mark off again.
+template <bool MASKED>
+__device__ __forceinline__ void propose_check_body(NodeArrays a, const PropRec* __restrict__ props, uint64_t n, const PropEnt* __restrict__ pe,
+                                                   uint64_t n_pe, uint64_t pool_bytes, unsigned int* bad, unsigned int stamp, PropRec* __restrict__ props_d,
+                                                   PropEnt* __restrict__ pe_d, unsigned long long* why, const uint16_t* __restrict__ voters) {
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   // the entry records, one per lane of the first ceil(n_pe / kBlock) workgroups ... (the grid covers max(n, n_pe) lanes)
   uint32_t reason = 0;  // kProp*: what is wrong with record i (the largest (reason, record) of the call goes into *why for the error text)
@@ -56,9 +73,31 @@ static __global__ __launch_bounds__(kBlock) void propose_check_kernel(NodeArrays
     else if ((uint64_t)p.ent_first + p.n_ents > n_pe) reason = kPropRange;
     else if (a.role[p.group] != kLeader) reason = kPropNotLeader;
     else if (atomicAdd(&a.rec[p.group].lst_cnt, 1u) != 0) reason = kPropTwice;
+    else if constexpr (MASKED) {
+      NodeT<true> node(a, p.group, voters);
+      if (((node.vmask >> a.self) & 1u) == 0) reason = kPropNoMember;
+      else {
+        const uint64_t tail = node.last_index + p.n_ents;
+        if (node.match(a.self) < tail) node.set_match(a.self, tail);
+        if (node.maybe_commit()) reason = kPropCommits;
+      }
+    }
   }
   if (reason) atomicMax(why, ((unsigned long long)(stamp & 0xffffffu) << 40) | ((unsigned long long)reason << 32) | (uint32_t)i);
   if (__ballot(reason != 0) != 0 && (threadIdx.x & 63) == 0) atomicExch(bad, stamp);  // (the word holds this call's stamp: refused)
+}
+static __global__ __launch_bounds__(kBlock) void propose_check_kernel(NodeArrays a, const PropRec* __restrict__ props, uint64_t n,
+                                                                      const PropEnt* __restrict__ pe, uint64_t n_pe, uint64_t pool_bytes,
+                                                                      unsigned int* bad, unsigned int stamp, PropRec* __restrict__ props_d,
+                                                                      PropEnt* __restrict__ pe_d, unsigned long long* why) {
+  propose_check_body<false>(a, props, n, pe, n_pe, pool_bytes, bad, stamp, props_d, pe_d, why, nullptr);
+}
+static __global__ __launch_bounds__(kBlock) void propose_check_voters_kernel(NodeArrays a, const PropRec* __restrict__ props, uint64_t n,
+                                                                             const PropEnt* __restrict__ pe, uint64_t n_pe, uint64_t pool_bytes,
+                                                                             unsigned int* bad, unsigned int stamp, PropRec* __restrict__ props_d,
+                                                                             PropEnt* __restrict__ pe_d, unsigned long long* why,
+                                                                             const uint16_t* __restrict__ voters) {
+  propose_check_body<true>(a, props, n, pe, n_pe, pool_bytes, bad, stamp, props_d, pe_d, why, voters);
 }
 
 // The call has TWO verdicts -- this check's, and the marshal's (a queued message it refuses, a stream that does not fit `out`) --
@@ -69,47 +108,63 @@ static __global__ __launch_bounds__(kBlock) void propose_check_kernel(NodeArrays
 // props / pe: the check kernel's copies in device memory.  msgs_out: the device part of the encoder's message array -- (N - 1) runs of n records, run r = the MsgApps for the r-th peer
 // slot other than this node's; ents_out: the device part of its entry-header array, whose first element is entry `ent_base` of
 // the whole array (a message's ent_first counts from the array's start).
+// MASKED: every entry header is written; of the N - 1 MsgApps only those to a slot whose bit is set in voters[g] exist.  The
+// encoder's input stays POSITIONAL, as the heartbeats' (raftq_beat_kernels.hpp): the slot of a peer that is no member of its
+// group holds a filler (to = 0xff), which the encoder counts as refused and gives zero bytes.  The workgroup's member frames are
+// summed and added once to *members (members_add): the host checks `refused == n_dev - member frames`.
+template <bool MASKED>
+__device__ __forceinline__ void propose_build_body(NodeArrays a, const PropRec* __restrict__ props, uint64_t n, const PropEnt* __restrict__ pe,
+                                                   const unsigned int* __restrict__ bad, unsigned int stamp, WireMsg* __restrict__ msgs_out,
+                                                   WireEnt* __restrict__ ents_out, uint32_t ent_base, const uint16_t* __restrict__ voters,
+                                                   unsigned long long* members) {
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool refused = *bad == stamp;  // workgroup-uniform
+  [[maybe_unused]] uint32_t wrote = 0;
+  if (i < n && !refused) {  // (refused: nothing is built, no member frame counted -- the encoder counts every message as refused, the commit kernel takes the marks off)
+    const PropRec p = props[i];
+    const NodeT<MASKED> node(a, p.group, voters);
+    const uint64_t old_last = node.last_index, old_term = node.last_term;
+    // appendEntry's entries: `es[i].Term = r.Term; es[i].Index = li + 1 + i` (the append itself: propose_commit_kernel)
+    for (uint32_t k = 0; k < p.n_ents; ++k) {
+      const PropEnt e = pe[p.ent_first + k];
+      WireEnt w;
+      w.term = node.term;
+      w.index = old_last + 1 + k;
+      w.data_len = e.data_len;
+      w.data_off = e.data_len ? e.data_off : 0;
+      w.type = e.type;
+      ents_out[p.ent_first + k] = w;
+    }
+    // bcastAppend (over r.prs) -> sendAppend(to) with Progress.Next at the tail: MsgApp{Index: next - 1, LogTerm: term(next - 1), Entries, Commit}
+    WireMsg m = msg_head(p.group, node.term, old_term, old_last, node.committed, a.self, kMsgApp, 0, ent_base + p.ent_first, p.n_ents);
+    uint32_t run = 0;
+    for (uint32_t to = 0; to < a.n_peers; ++to) {
+      if (to == a.self) continue;
+      bool member = true;
+      if constexpr (MASKED) {
+        member = ((node.vmask >> to) & 1u) != 0;
+        wrote += member ? 1u : 0u;
+      }
+      m.to = member ? (uint8_t)to : (uint8_t)0xff;  // (a filler is any record addressed to 0xff, as beat_store's)
+      msgs_out[(uint64_t)run * n + i] = m;
+      ++run;
+    }
+  }
+  if constexpr (MASKED) {
+    __shared__ uint64_t red[kWaves];
+    members_add(wrote, red, members);
+  }
+}
 static __global__ __launch_bounds__(kBlock) void propose_build_kernel(NodeArrays a, const PropRec* __restrict__ props, uint64_t n,
                                                                       const PropEnt* __restrict__ pe, const unsigned int* __restrict__ bad,
                                                                       unsigned int stamp, WireMsg* __restrict__ msgs_out, WireEnt* __restrict__ ents_out, uint32_t ent_base) {
-  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  if (*bad == stamp) return;  // refused: nothing is built (the encoder counts every message as refused, the commit kernel takes the marks off)
-  const PropRec p = props[i];
-  const Node node(a, p.group);
-  const uint64_t old_last = node.last_index, old_term = node.last_term;
-  // appendEntry's entries: `es[i].Term = r.Term; es[i].Index = li + 1 + i` (the append itself: propose_commit_kernel)
-  for (uint32_t k = 0; k < p.n_ents; ++k) {
-    const PropEnt e = pe[p.ent_first + k];
-    WireEnt w;
-    w.term = node.term;
-    w.index = old_last + 1 + k;
-    w.data_len = e.data_len;
-    w.data_off = e.data_len ? e.data_off : 0;
-    w.type = e.type;
-    ents_out[p.ent_first + k] = w;
-  }
-  // bcastAppend -> sendAppend(to) with Progress.Next at the tail: MsgApp{Index: next - 1, LogTerm: term(next - 1), Entries, Commit}
-  WireMsg m;
-  m.group = p.group;
-  m.term = node.term;
-  m.log_term = old_term;
-  m.index = old_last;
-  m.commit = node.committed;
-  m.reject_hint = 0;
-  m.from = a.self;
-  m.type = kMsgApp;
-  m.reject = 0;
-  m.flags = 0;
-  m.ent_first = ent_base + p.ent_first;
-  m.n_ents = p.n_ents;
-  uint32_t run = 0;
-  for (uint32_t to = 0; to < a.n_peers; ++to) {
-    if (to == a.self) continue;
-    m.to = (uint8_t)to;
-    msgs_out[(uint64_t)run * n + i] = m;
-    ++run;
-  }
+  propose_build_body<false>(a, props, n, pe, bad, stamp, msgs_out, ents_out, ent_base, nullptr, nullptr);
+}
+static __global__ __launch_bounds__(kBlock) void propose_build_voters_kernel(NodeArrays a, const PropRec* __restrict__ props, uint64_t n,
+                                                                             const PropEnt* __restrict__ pe, const unsigned int* __restrict__ bad,
+                                                                             unsigned int stamp, WireMsg* __restrict__ msgs_out, WireEnt* __restrict__ ents_out,
+                                                                             uint32_t ent_base, const uint16_t* __restrict__ voters, unsigned long long* members) {
+  propose_build_body<true>(a, props, n, pe, bad, stamp, msgs_out, ents_out, ent_base, voters, members);
 }
 
 // appendEntry's state change, behind the encoder on the same stream: `r.raftLog.append(es...); r.prs[r.id].maybeUpdate(lastIndex)`.
@@ -142,112 +197,6 @@ static __global__ __launch_bounds__(kBlock) void propose_commit_kernel(NodeArray
   node.last_term = node.term;
   if (node.match(a.self) < node.last_index) node.set_match(a.self, node.last_index);
   node.store();  // (list words back to empty: the check's mark with them)
-}
-
-// ---- proposals over each group's own members (raftq_bcast_set_voters on a handle with voter masks loaded) ----------------------
-// Twins of the check and the build kernel, the masks as a last argument behind the parents' (propose_commit_kernel serves both).  Kernels of their own: the parents keep
-// their assembly (profiles/r14/isa_unchanged.txt).
-constexpr uint32_t kPropNoMember = 7, kPropCommits = 8;
-
-// propose_check_kernel plus two reasons, both read off the masked Node loaded from the record line the check touches anyway
-// (its lst_cnt is the "seen" mark):
-//   kPropNoMember  self's bit is clear in voters[g].  Upstream v2.2's appendEntry would dereference a missing Progress
-//                  (r.prs[r.id]); CHOICE: refuse.
-//   kPropCommits   the commit kernel's sentence "maybeCommit cannot move anything with more than one peer" does not hold over members: a
-//                  one-voter group commits on its own append, and under the 2015-era removeNode (which does not call
-//                  maybeCommit) so does a group whose membership shrank since its last acknowledgement.  Evaluated exactly --
-//                  Match[self] raised to last_index + n_ents as the commit will, then the masked maybe_commit() with its current-term
-//                  gate -- on the lane's copy, which is never stored.  The call has no channel for a commit:
-//                  raftq_apply_log_deltas has, and a tail report with the unchanged tail settles the commit first.
-// Both after the six old reasons, so a record sound by the old rules is marked (lst_cnt) whatever the new ones say; a refused
-// call's commit kernel takes every mark off again.
-static __global__ __launch_bounds__(kBlock) void propose_check_voters_kernel(NodeArrays a, const PropRec* __restrict__ props, uint64_t n,
-                                                                             const PropEnt* __restrict__ pe, uint64_t n_pe, uint64_t pool_bytes,
-                                                                             unsigned int* bad, unsigned int stamp, PropRec* __restrict__ props_d,
-                                                                             PropEnt* __restrict__ pe_d, unsigned long long* why,
-                                                                             const uint16_t* __restrict__ voters) {
-  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-  uint32_t reason = 0;
-  if (i < n_pe) {
-    const PropEnt e = pe[i];
-    pe_d[i] = e;
-    if (e.data_len != 0 && (e.data_off > pool_bytes || e.data_len > pool_bytes - e.data_off)) reason = kPropPayload;
-  }
-  if (i < n) {
-    const PropRec p = props[i];
-    props_d[i] = p;
-    if (p.group >= a.n_groups) reason = kPropGroup;
-    else if (p.n_ents == 0 || p.n_ents > kPropMaxEnts) reason = kPropCount;
-    else if ((uint64_t)p.ent_first + p.n_ents > n_pe) reason = kPropRange;
-    else if (a.role[p.group] != kLeader) reason = kPropNotLeader;
-    else if (atomicAdd(&a.rec[p.group].lst_cnt, 1u) != 0) reason = kPropTwice;
-    else {
-      NodeT<true> node(a, p.group, voters);
-      if (((node.vmask >> a.self) & 1u) == 0) reason = kPropNoMember;
-      else {
-        const uint64_t tail = node.last_index + p.n_ents;
-        if (node.match(a.self) < tail) node.set_match(a.self, tail);
-        if (node.maybe_commit()) reason = kPropCommits;
-      }
-    }
-  }
-  if (reason) atomicMax(why, ((unsigned long long)(stamp & 0xffffffu) << 40) | ((unsigned long long)reason << 32) | (uint32_t)i);
-  if (__ballot(reason != 0) != 0 && (threadIdx.x & 63) == 0) atomicExch(bad, stamp);
-}
-
-// propose_build_kernel over members: the entry headers are the parent's; of the N - 1 MsgApps only those
-// to a slot whose bit is set in voters[g] exist.  The encoder's input stays POSITIONAL, as in beat_build_voters_kernel
-// (raftq_beat_kernels.hpp): (N - 1) runs of n records where the parent puts them, and the slot of a peer that is no member of
-// its group holds a filler (to = 0xff), which the encoder counts as refused and gives zero bytes.  The workgroup's member frames
-// are summed and added once to *members (members_add): the host checks `refused == n_dev - member frames`.
-static __global__ __launch_bounds__(kBlock) void propose_build_voters_kernel(NodeArrays a, const PropRec* __restrict__ props, uint64_t n,
-                                                                             const PropEnt* __restrict__ pe, const unsigned int* __restrict__ bad,
-                                                                             unsigned int stamp, WireMsg* __restrict__ msgs_out, WireEnt* __restrict__ ents_out,
-                                                                             uint32_t ent_base, const uint16_t* __restrict__ voters, unsigned long long* members) {
-  __shared__ uint64_t red[kWaves];
-  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-  const bool refused = *bad == stamp;  // workgroup-uniform
-  uint32_t wrote = 0;
-  if (i < n && !refused) {  // (refused: nothing is built, no member frame counted)
-    const PropRec p = props[i];
-    const NodeT<true> node(a, p.group, voters);
-    const uint64_t old_last = node.last_index, old_term = node.last_term;
-    // appendEntry's entries, as in propose_build_kernel
-    for (uint32_t k = 0; k < p.n_ents; ++k) {
-      const PropEnt e = pe[p.ent_first + k];
-      WireEnt w;
-      w.term = node.term;
-      w.index = old_last + 1 + k;
-      w.data_len = e.data_len;
-      w.data_off = e.data_len ? e.data_off : 0;
-      w.type = e.type;
-      ents_out[p.ent_first + k] = w;
-    }
-    // bcastAppend over r.prs
-    WireMsg m;
-    m.group = p.group;
-    m.term = node.term;
-    m.log_term = old_term;
-    m.index = old_last;
-    m.commit = node.committed;
-    m.reject_hint = 0;
-    m.from = a.self;
-    m.type = kMsgApp;
-    m.reject = 0;
-    m.flags = 0;
-    m.ent_first = ent_base + p.ent_first;
-    m.n_ents = p.n_ents;
-    uint32_t run = 0;
-    for (uint32_t to = 0; to < a.n_peers; ++to) {
-      if (to == a.self) continue;
-      const bool member = ((node.vmask >> to) & 1u) != 0;
-      m.to = member ? (uint8_t)to : (uint8_t)0xff;  // (a filler is any record addressed to 0xff, as beat_store's)
-      msgs_out[(uint64_t)run * n + i] = m;
-      wrote += member ? 1u : 0u;
-      ++run;
-    }
-  }
-  members_add(wrote, red, members);
 }
 
 }  // namespace raftqk

@@ -26,22 +26,81 @@ struct RespLayout {
   uint64_t* peer_off;   // [kMaxPeers + 1]: peer_off[p] .. peer_off[p + 1] = p's slice; peer_off[n_peers] = total
 };
 
+// One text per step, one instantiation per entry point: a form's differences stand under `if constexpr`, and every __global__
+// below instantiates exactly one body (a kernel that chose between two at run time would carry both bodies' LDS and registers).
+
 // does result r send a frame to peer p?
 __device__ __forceinline__ bool resp_to(const RespRec& r, bool valid, uint32_t p, const RespLayout& L) {
   return valid && p < L.n_peers && p != L.self && (r.kind == kMsgApp || r.to == p);
 }
 
+// MASKED: the layout over each group's own members (raftq_bcast_set_voters on a handle with voter masks loaded).  One rule changes:
+// the commit broadcast (kind == kMsgApp) goes to slot p only if p's bit is set in voters[group] -- upstream's bcastAppend ranges
+// over r.prs, which IS the membership.  A response to a sender goes to r.to as always, member or not: upstream answers whoever
+// sent.  Everything else is the unmasked form's: peer-major, result order inside a slice, fillers only behind the total; a
+// broadcast of a group with no member but self has no frame at all.
+// The mask is a 2-byte gather of the dense `voters` array by the record's group, issued by broadcast records only.  (The walk lane
+// holds the mask in a register and could have written it into the record's `to` / `pad` bytes, which a broadcast does not use;
+// that would have changed NodeT<true>::respond and with it the masked walks, and the gather costs one 32-byte sector per broadcast.)
+
+// the slots result r sends a frame to, as a bit mask (bit p: resp_to's verdict over members)
+__device__ __forceinline__ uint32_t resp_to_voters(const RespRec& r, bool valid, const RespLayout& L, const uint16_t* __restrict__ voters) {
+  if (!valid) return 0u;
+  const uint32_t peers = ((1u << L.n_peers) - 1u) & ~(1u << L.self);
+  const uint32_t want = r.kind == kMsgApp ? (uint32_t)voters[r.group] : (1u << r.to);
+  return want & peers;
+}
+
+// the verdict per slot of either form (to: resp_to_voters' mask, MASKED only)
+template <bool MASKED>
+__device__ __forceinline__ bool resp_dest(const RespRec& r, bool valid, uint32_t p, const RespLayout& L, uint32_t to) {
+  if constexpr (MASKED) return ((to >> p) & 1u) != 0;
+  else return resp_to(r, valid, p, L);
+}
+
+// a record of the encoder's input but for its `to`
+__device__ __forceinline__ WireMsg msg_head(uint64_t group, uint64_t term, uint64_t log_term, uint64_t index, uint64_t commit, uint32_t from, uint8_t type,
+                                            uint8_t reject, uint32_t ent_first, uint32_t n_ents) {
+  WireMsg m;
+  m.group = group;
+  m.term = term;
+  m.log_term = log_term;
+  m.index = index;
+  m.commit = commit;
+  m.reject_hint = 0;
+  m.from = from;
+  m.type = type;
+  m.reject = reject;
+  m.flags = 0;
+  m.ent_first = ent_first;
+  m.n_ents = n_ents;
+  return m;
+}
+
+// fillers in enc[first .. end), by the whole grid: the encoder counts them as refused and writes nothing for them
+__device__ __forceinline__ void fill_refused(WireMsg* enc, uint64_t first, uint64_t end) {
+  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+  for (uint64_t k = first + (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < end; k += stride) {
+    WireMsg f{};
+    f.to = 0xff;
+    enc[k] = f;
+  }
+}
+
 // (1) frames per peer of every workgroup's kBlock results
-static __global__ __launch_bounds__(kBlock) void resp_count_kernel(RespLayout L) {
+template <bool MASKED>
+__device__ __forceinline__ void resp_count_body(RespLayout L, const uint16_t* __restrict__ voters) {
   __shared__ uint32_t wc[kWaves][kMaxPeers];
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   RespRec r{};
   if (i < L.n) r = L.resp[i];
   const bool valid = i < L.n && r.stamp == L.stamp && r.kind != 0;
+  uint32_t to = 0;
+  if constexpr (MASKED) to = resp_to_voters(r, valid, L, voters);
 #pragma unroll
   for (uint32_t p = 0; p < (uint32_t)kMaxPeers; ++p) {
-    const uint64_t b = __ballot(resp_to(r, valid, p, L));
+    const uint64_t b = __ballot(resp_dest<MASKED>(r, valid, p, L, to));
     if (lane == 0) wc[wave][p] = (uint32_t)__popcll(b);
   }
   __syncthreads();
@@ -50,6 +109,10 @@ static __global__ __launch_bounds__(kBlock) void resp_count_kernel(RespLayout L)
     for (int w = 0; w < kWaves; ++w) t += wc[w][threadIdx.x];
     L.blk_cnt[(uint64_t)blockIdx.x * kMaxPeers + threadIdx.x] = t;
   }
+}
+static __global__ __launch_bounds__(kBlock) void resp_count_kernel(RespLayout L) { resp_count_body<false>(L, nullptr); }
+static __global__ __launch_bounds__(kBlock) void resp_count_voters_kernel(RespLayout L, const uint16_t* __restrict__ voters) {
+  resp_count_body<true>(L, voters);
 }
 
 // (2) ONE workgroup: exclusive scan of every peer's workgroup counts, then the peers' slices one after the other
@@ -81,157 +144,13 @@ static __global__ __launch_bounds__(kBlock) void resp_scan_kernel(RespLayout L, 
 }
 
 // (3) the records, peer-major, into the encoder's input; then the fillers up to n_max
-static __global__ __launch_bounds__(kBlock) void resp_scatter_kernel(RespLayout L, WireMsg* __restrict__ enc, uint64_t n_max) {
-  __shared__ uint32_t wc[kWaves][kMaxPeers];
-  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  RespRec r{};
-  if (i < L.n) r = L.resp[i];
-  const bool valid = i < L.n && r.stamp == L.stamp && r.kind != 0;
-  const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
-  uint32_t in_wave[kMaxPeers];
-#pragma unroll
-  for (uint32_t p = 0; p < (uint32_t)kMaxPeers; ++p) {
-    const uint64_t b = __ballot(resp_to(r, valid, p, L));
-    in_wave[p] = (uint32_t)__popcll(b & below);
-    if (lane == 0) wc[wave][p] = (uint32_t)__popcll(b);
-  }
-  __syncthreads();
-  if (valid) {
-    WireMsg m;
-    m.group = r.group;
-    m.term = r.term;
-    m.log_term = r.log_term;
-    m.index = r.index;
-    m.commit = r.commit;
-    m.reject_hint = 0;
-    m.from = L.self;
-    m.type = r.kind;
-    m.reject = r.reject;
-    m.flags = 0;
-    m.ent_first = 0;
-    m.n_ents = 0;
-#pragma unroll
-    for (uint32_t p = 0; p < (uint32_t)kMaxPeers; ++p) {
-      if (!resp_to(r, valid, p, L)) continue;
-      uint64_t at = L.peer_off[p] + L.blk_off[(uint64_t)blockIdx.x * kMaxPeers + p] + in_wave[p];
-      for (uint32_t w = 0; w < wave; ++w) at += wc[w][p];
-      m.to = (uint8_t)p;
-      enc[at] = m;
-    }
-  }
-  // fillers: the encoder counts them as refused and writes nothing for them
-  const uint64_t total = L.peer_off[L.n_peers];
-  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-  for (uint64_t k = total + i; k < n_max; k += stride) {
-    WireMsg f{};
-    f.to = 0xff;
-    enc[k] = f;
-  }
-}
-
-// ---- the layout over each group's own members (raftq_bcast_set_voters on a handle with voter masks loaded) ------------------------
-// Twins of (1) and (3); (2) is shared.  One rule changes: the commit broadcast (kind == kMsgApp) goes to slot p only if p's bit
-// is set in voters[group] -- upstream's bcastAppend ranges over r.prs, which IS the membership.  A response to a sender goes to
-// r.to as always, member or not: upstream answers whoever sent.  Everything else is the parents': peer-major, result order inside
-// a slice, fillers only behind the total; a broadcast of a group with no member but self has no frame at all.
-// The mask is a 2-byte gather of the dense `voters` array by the record's group, issued by broadcast records only.  (The walk lane
-// holds the mask in a register and could have written it into the record's `to` / `pad` bytes, which a broadcast does not use;
-// that would have changed NodeT<true>::respond and with it the assembly of the masked walks -- profiles/r14/isa_unchanged.txt
-// keeps them what they were, and the gather costs one 32-byte sector per broadcast.)
-// Kernels of their own, with the masks as an argument behind the parents': RespLayout keeps its members and the parents their
-// kernarg offsets and their assembly.
-
-// the slots result r sends a frame to, as a bit mask (bit p: resp_to's verdict over members)
-__device__ __forceinline__ uint32_t resp_to_voters(const RespRec& r, bool valid, const RespLayout& L, const uint16_t* __restrict__ voters) {
-  if (!valid) return 0u;
-  const uint32_t peers = ((1u << L.n_peers) - 1u) & ~(1u << L.self);
-  const uint32_t want = r.kind == kMsgApp ? (uint32_t)voters[r.group] : (1u << r.to);
-  return want & peers;
-}
-
-// (1) over members
-static __global__ __launch_bounds__(kBlock) void resp_count_voters_kernel(RespLayout L, const uint16_t* __restrict__ voters) {
-  __shared__ uint32_t wc[kWaves][kMaxPeers];
-  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  RespRec r{};
-  if (i < L.n) r = L.resp[i];
-  const bool valid = i < L.n && r.stamp == L.stamp && r.kind != 0;
-  const uint32_t to = resp_to_voters(r, valid, L, voters);
-#pragma unroll
-  for (uint32_t p = 0; p < (uint32_t)kMaxPeers; ++p) {
-    const uint64_t b = __ballot(((to >> p) & 1u) != 0);
-    if (lane == 0) wc[wave][p] = (uint32_t)__popcll(b);
-  }
-  __syncthreads();
-  if (threadIdx.x < (uint32_t)kMaxPeers) {
-    uint32_t t = 0;
-    for (int w = 0; w < kWaves; ++w) t += wc[w][threadIdx.x];
-    L.blk_cnt[(uint64_t)blockIdx.x * kMaxPeers + threadIdx.x] = t;
-  }
-}
-
-// (3) over members
-static __global__ __launch_bounds__(kBlock) void resp_scatter_voters_kernel(RespLayout L, WireMsg* __restrict__ enc, uint64_t n_max,
-                                                                            const uint16_t* __restrict__ voters) {
-  __shared__ uint32_t wc[kWaves][kMaxPeers];
-  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  RespRec r{};
-  if (i < L.n) r = L.resp[i];
-  const bool valid = i < L.n && r.stamp == L.stamp && r.kind != 0;
-  const uint32_t to = resp_to_voters(r, valid, L, voters);
-  const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
-  uint32_t in_wave[kMaxPeers];
-#pragma unroll
-  for (uint32_t p = 0; p < (uint32_t)kMaxPeers; ++p) {
-    const uint64_t b = __ballot(((to >> p) & 1u) != 0);
-    in_wave[p] = (uint32_t)__popcll(b & below);
-    if (lane == 0) wc[wave][p] = (uint32_t)__popcll(b);
-  }
-  __syncthreads();
-  if (to != 0) {
-    WireMsg m;
-    m.group = r.group;
-    m.term = r.term;
-    m.log_term = r.log_term;
-    m.index = r.index;
-    m.commit = r.commit;
-    m.reject_hint = 0;
-    m.from = L.self;
-    m.type = r.kind;
-    m.reject = r.reject;
-    m.flags = 0;
-    m.ent_first = 0;
-    m.n_ents = 0;
-#pragma unroll
-    for (uint32_t p = 0; p < (uint32_t)kMaxPeers; ++p) {
-      if (((to >> p) & 1u) == 0) continue;
-      uint64_t at = L.peer_off[p] + L.blk_off[(uint64_t)blockIdx.x * kMaxPeers + p] + in_wave[p];
-      for (uint32_t w = 0; w < wave; ++w) at += wc[w][p];
-      m.to = (uint8_t)p;
-      enc[at] = m;
-    }
-  }
-  // fillers: the encoder counts them as refused and writes nothing for them
-  const uint64_t total = L.peer_off[L.n_peers];
-  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-  for (uint64_t k = total + i; k < n_max; k += stride) {
-    WireMsg f{};
-    f.to = 0xff;
-    enc[k] = f;
-  }
-}
-
-// ---- the layout with becomeLeader's broadcast in it (raftq_respond_set_lead) -------------------------------------------------------
-// A twin of (3), over every slot (voters == nullptr) or over members; (1) and (2) are shared -- a win is kind == kMsgApp, which they
-// count as a broadcast already.  What is new: a record with pad == 1 carries the empty entry of the new term.  Its header goes into
-// the encoder's entry array in HBM at slot i, the result's own position (ent_first = i, n_ents = 1: no scan), and every frame of the
-// broadcast names that one slot.  Slots of results that carry no entry are never read.  A kernel of its own with the new arguments
-// behind the parents': those keep their kernarg offsets and their assembly.
-static __global__ __launch_bounds__(kBlock) void resp_scatter_lead_kernel(RespLayout L, WireMsg* __restrict__ enc, uint64_t n_max,
-                                                                          const uint16_t* __restrict__ voters, WireEnt* __restrict__ ents) {
+// LEAD: the layout with becomeLeader's broadcast in it (raftq_respond_set_lead); (1) and (2) are shared -- a win is kind ==
+// kMsgApp, which they count as a broadcast already.  A record with pad == 1 carries the empty entry of the new term.  Its header
+// goes into the encoder's entry array in HBM at slot i, the result's own position (ent_first = i, n_ents = 1: no scan), and every
+// frame of the broadcast names that one slot.  Slots of results that carry no entry are never read.
+template <bool MASKED, bool LEAD>
+__device__ __forceinline__ void resp_scatter_body(RespLayout L, WireMsg* __restrict__ enc, uint64_t n_max, const uint16_t* __restrict__ voters,
+                                                  WireEnt* __restrict__ ents) {
   __shared__ uint32_t wc[kWaves][kMaxPeers];
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -239,62 +158,58 @@ static __global__ __launch_bounds__(kBlock) void resp_scatter_lead_kernel(RespLa
   if (i < L.n) r = L.resp[i];
   const bool valid = i < L.n && r.stamp == L.stamp && r.kind != 0;
   uint32_t to = 0;
-  if (voters != nullptr) {
-    to = resp_to_voters(r, valid, L, voters);
-  } else {
-#pragma unroll
-    for (uint32_t p = 0; p < (uint32_t)kMaxPeers; ++p) to |= resp_to(r, valid, p, L) ? 1u << p : 0u;
-  }
+  if constexpr (MASKED) to = resp_to_voters(r, valid, L, voters);
   const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
   uint32_t in_wave[kMaxPeers];
 #pragma unroll
   for (uint32_t p = 0; p < (uint32_t)kMaxPeers; ++p) {
-    const uint64_t b = __ballot(((to >> p) & 1u) != 0);
+    const uint64_t b = __ballot(resp_dest<MASKED>(r, valid, p, L, to));
     in_wave[p] = (uint32_t)__popcll(b & below);
     if (lane == 0) wc[wave][p] = (uint32_t)__popcll(b);
   }
   __syncthreads();
-  if (to != 0) {
-    const bool lead = r.kind == kMsgApp && r.pad == 1;
-    if (lead) {  // (i < L.n: the array has one slot per result)
-      WireEnt e;
-      e.term = r.term;
-      e.index = r.index + 1;
-      e.data_off = 0;
-      e.data_len = 0;
-      e.type = 0;
-      ents[i] = e;
+  if (MASKED ? to != 0 : valid) {
+    uint32_t ent_first = 0, n_ents = 0;
+    if constexpr (LEAD) {
+      if (r.kind == kMsgApp && r.pad == 1) {  // (i < L.n: the array has one slot per result)
+        WireEnt e;
+        e.term = r.term;
+        e.index = r.index + 1;
+        e.data_off = 0;
+        e.data_len = 0;
+        e.type = 0;
+        ents[i] = e;
+        ent_first = (uint32_t)i;
+        n_ents = 1;
+      }
     }
-    WireMsg m;
-    m.group = r.group;
-    m.term = r.term;
-    m.log_term = r.log_term;
-    m.index = r.index;
-    m.commit = r.commit;
-    m.reject_hint = 0;
-    m.from = L.self;
-    m.type = r.kind;
-    m.reject = r.reject;
-    m.flags = 0;
-    m.ent_first = lead ? (uint32_t)i : 0u;
-    m.n_ents = lead ? 1u : 0u;
+    WireMsg m = msg_head(r.group, r.term, r.log_term, r.index, r.commit, L.self, r.kind, r.reject, ent_first, n_ents);
 #pragma unroll
     for (uint32_t p = 0; p < (uint32_t)kMaxPeers; ++p) {
-      if (((to >> p) & 1u) == 0) continue;
+      if (!resp_dest<MASKED>(r, valid, p, L, to)) continue;
       uint64_t at = L.peer_off[p] + L.blk_off[(uint64_t)blockIdx.x * kMaxPeers + p] + in_wave[p];
       for (uint32_t w = 0; w < wave; ++w) at += wc[w][p];
       m.to = (uint8_t)p;
       enc[at] = m;
     }
   }
-  // fillers: the encoder counts them as refused and writes nothing for them
-  const uint64_t total = L.peer_off[L.n_peers];
-  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-  for (uint64_t k = total + i; k < n_max; k += stride) {
-    WireMsg f{};
-    f.to = 0xff;
-    enc[k] = f;
-  }
+  fill_refused(enc, L.peer_off[L.n_peers], n_max);
+}
+static __global__ __launch_bounds__(kBlock) void resp_scatter_kernel(RespLayout L, WireMsg* __restrict__ enc, uint64_t n_max) {
+  resp_scatter_body<false, false>(L, enc, n_max, nullptr, nullptr);
+}
+static __global__ __launch_bounds__(kBlock) void resp_scatter_voters_kernel(RespLayout L, WireMsg* __restrict__ enc, uint64_t n_max,
+                                                                            const uint16_t* __restrict__ voters) {
+  resp_scatter_body<true, false>(L, enc, n_max, voters, nullptr);
+}
+// (the unmasked form keeps the parameter list it had when it served both forms: it reads no mask)
+static __global__ __launch_bounds__(kBlock) void resp_scatter_lead_kernel(RespLayout L, WireMsg* __restrict__ enc, uint64_t n_max, const uint16_t*,
+                                                                          WireEnt* __restrict__ ents) {
+  resp_scatter_body<false, true>(L, enc, n_max, nullptr, ents);
+}
+static __global__ __launch_bounds__(kBlock) void resp_scatter_lead_voters_kernel(RespLayout L, WireMsg* __restrict__ enc, uint64_t n_max,
+                                                                                 const uint16_t* __restrict__ voters, WireEnt* __restrict__ ents) {
+  resp_scatter_body<true, true>(L, enc, n_max, voters, ents);
 }
 
 }  // namespace raftqk

@@ -451,7 +451,7 @@ int wire_decode_copying(raftq_t* h, const void* stream, uint64_t nbytes, const u
 }
 
 // Broadcasts over each group's own members (raftq_tick_set_voters / raftq_bcast_set_voters with masks loaded; raftq_beat_kernels.hpp,
-// raftq_propose_kernels.hpp): the twins add the frames they built for members to the fifth word of wire_flags, zeroed here in the same submission in front of them ...
+// raftq_propose_kernels.hpp): the masked build kernels add the frames they built for members to the fifth word of wire_flags, zeroed here in the same submission in front of them ...
 unsigned long long* members_word(raftq_t* h) { return h->wire_flags + 4; }
 int members_begin(raftq_t* h) {
   HIPCHK(h, hipMemsetAsync(members_word(h), 0, 8, h->stream));
@@ -557,7 +557,7 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
   const dim3 pg((unsigned)((n_props + kBlock - 1) / kBlock)), cg((unsigned)((std::max(n_props, n_prop_ents) + kBlock - 1) / kBlock));
   PropRec* props_d = (PropRec*)sc.carved[0];
   PropEnt* pe_d = (PropEnt*)sc.carved[1];
-  const bool members = raftq_detail::masked_bcast(h);  // the MsgApps go to each group's own members (the propose_*_voters_kernel twins)
+  const bool members = raftq_detail::masked_bcast(h);  // the MsgApps go to each group's own members (propose_check_voters_kernel, propose_build_voters_kernel)
   if (members) {
     if (int rc = members_begin(h)) return rc;
     hipLaunchKernelGGL(propose_check_voters_kernel, cg, dim3(kBlock), 0, h->stream, na, (const PropRec*)v_props, n_props, (const PropEnt*)v_pe, n_prop_ents,
@@ -764,7 +764,7 @@ int raftq_detail::respond_enqueue(raftq_t* h, const RespPlan& p) {
   const uint32_t blocks = blocks_for(p.n);
   RespLayout L{(const RespRec*)rd, p.n, h->N, h->self_peer, h->resp_stamp, (uint32_t*)(rd + rs.o_blk_cnt), (uint64_t*)(rd + rs.o_blk_off),
                (uint64_t*)(rd + rs.o_peer_off)};
-  const bool members = raftq_detail::masked_bcast(h);  // the commit broadcasts go to each group's own members (the resp_*_voters_kernel twins)
+  const bool members = raftq_detail::masked_bcast(h);  // the commit broadcasts go to each group's own members (the resp_*_voters_kernel entry points)
   if (members) hipLaunchKernelGGL(resp_count_voters_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, (const uint16_t*)h->voters);
   else hipLaunchKernelGGL(resp_count_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L);
   hipLaunchKernelGGL(resp_scan_kernel, dim3(1), dim3(kBlock), 0, h->stream, L, blocks);
@@ -772,13 +772,14 @@ int raftq_detail::respond_enqueue(raftq_t* h, const RespPlan& p) {
   if (p.n_max != 0) {
     StreamCall sc = resp_marshal_call(p);
     if (int rc = stream_prepare(h, sc)) return rc;  // (allocates nothing: respond_prepare reserved this very request)
-    if (p.lead)  // (one twin for both: a null mask array is "every slot")
-      hipLaunchKernelGGL(resp_scatter_lead_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, (WireMsg*)sc.in.seg[0].dst, p.n_max,
-                         members ? (const uint16_t*)h->voters : (const uint16_t*)nullptr, (WireEnt*)sc.in.seg[1].dst);
-    else if (members)
-      hipLaunchKernelGGL(resp_scatter_voters_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, (WireMsg*)sc.in.seg[0].dst, p.n_max, (const uint16_t*)h->voters);
-    else
-      hipLaunchKernelGGL(resp_scatter_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, (WireMsg*)sc.in.seg[0].dst, p.n_max);
+    WireMsg* const enc = (WireMsg*)sc.in.seg[0].dst;
+    WireEnt* const ents = (WireEnt*)sc.in.seg[1].dst;
+    const uint16_t* const voters = (const uint16_t*)h->voters;
+    // the two switches, one entry point each way
+    if (p.lead && members) hipLaunchKernelGGL(resp_scatter_lead_voters_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, enc, p.n_max, voters, ents);
+    else if (p.lead) hipLaunchKernelGGL(resp_scatter_lead_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, enc, p.n_max, (const uint16_t*)nullptr, ents);
+    else if (members) hipLaunchKernelGGL(resp_scatter_voters_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, enc, p.n_max, voters);
+    else hipLaunchKernelGGL(resp_scatter_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, enc, p.n_max);
     // (the entry array: p.n slots with the switch on, none otherwise)
     if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, p.n_max, p.lead ? p.n : (uint64_t)0, (uint64_t)0, (uint8_t*)h->wire_out.d, (uint8_t*)p.v_out,
                                p.cap, p.v_resp_off, sc.ctl, h->wire_pin_d + kPinRespond, (const unsigned int*)nullptr, 0u))
@@ -814,6 +815,15 @@ StreamCall beat_marshal_call(uint64_t n_max, uint64_t cap) {
   sc.seg[0] = {nullptr, 0, n_max * sizeof(WireMsg)};
   sc.out_bytes = cap + 16;
   return sc;
+}
+// the heartbeat round of both calls, over each group's own members where the Tick is (the caller has opened the members word)
+void beat_enqueue(raftq_t* h, const NodeArrays& na, const raftq_detail::TickLists& tl, bool members, uint64_t beat_cap, WireMsg* enc) {
+  const uint64_t nw = h->gpad / 256;
+  const dim3 grid((unsigned)((nw + kWaves - 1) / kWaves));
+  BeatArgs ba{(const uint64_t*)h->beat_bits, (const uint4*)h->tick_partials, nw, tl.off_beat, (const uint64_t*)h->d_total, na.rec, h->G, h->N,
+              h->self_peer, beat_cap, enc};
+  if (members) hipLaunchKernelGGL(beat_build_voters_kernel, grid, dim3(kBlock), 0, h->stream, ba, (const uint16_t*)h->voters, members_word(h));
+  else hipLaunchKernelGGL(beat_build_kernel, grid, dim3(kBlock), 0, h->stream, ba);
 }
 }  // namespace
 
@@ -858,16 +868,9 @@ extern "C" int raftq_tick_frames(raftq_t* h, unsigned flags, uint64_t hup_cap, u
   // Tick -> lists -> beat_build -> encoder -> flag, back to back; one wait
   if (int rc = raftq_detail::tick_lists_enqueue(h, &tl)) return rc;
   if (n_max != 0) {
-    const uint64_t nw = h->gpad / 256;
-    const dim3 grid((unsigned)((nw + kWaves - 1) / kWaves));
-    BeatArgs ba{(const uint64_t*)h->beat_bits, (const uint4*)h->tick_partials, nw, tl.off_beat, (const uint64_t*)h->d_total, na.rec, h->G, h->N,
-                h->self_peer, beat_cap, (WireMsg*)sc.in.seg[0].dst};
-    if (members) {
+    if (members)
       if (int rc = members_begin(h)) return rc;
-      hipLaunchKernelGGL(beat_build_voters_kernel, grid, dim3(kBlock), 0, h->stream, ba, (const uint16_t*)h->voters, members_word(h));
-    } else {
-      hipLaunchKernelGGL(beat_build_kernel, grid, dim3(kBlock), 0, h->stream, ba);
-    }
+    beat_enqueue(h, na, tl, members, beat_cap, (WireMsg*)sc.in.seg[0].dst);
     HIPCHK(h, hipGetLastError());
     if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, n_max, (uint64_t)0, (uint64_t)0, (uint8_t*)h->wire_out.d, (uint8_t*)v_out, enc_cap,
                                (uint64_t*)v_off, sc.ctl, h->wire_pin_d + kPinCall, (const unsigned int*)nullptr, 0u))
@@ -937,7 +940,7 @@ extern "C" int raftq_tick_elect_frames(raftq_t* h, unsigned flags, uint64_t hup_
   // refresh), the Tick's lists, the encoder's control block, scratch and output buffer
   NodeArrays na;
   if (int rc = raftq_detail::node_records_of(h, who, &na, true)) return rc;
-  const bool members = raftq_detail::masked_tick(h);  // both rounds go to each group's own members (the *_voters_kernel twins)
+  const bool members = raftq_detail::masked_tick(h);  // both rounds go to each group's own members (the *_voters_kernel entry points)
   raftq_detail::TickLists tl;
   if (int rc = raftq_detail::tick_lists_prepare(h, who, flags, hup_cap, beat_cap, &tl)) return rc;
   const uint64_t enc_cap = n_max * RAFTQ_RESPOND_FRAME_MAX;  // what the encoder may write: never more than the worst case
@@ -953,12 +956,7 @@ extern "C" int raftq_tick_elect_frames(raftq_t* h, unsigned flags, uint64_t hup_
     WireMsg* const enc = (WireMsg*)sc.in.seg[0].dst;
     if (members)
       if (int rc = members_begin(h)) return rc;
-    if (beat_cap != 0) {
-      BeatArgs ba{(const uint64_t*)h->beat_bits, (const uint4*)h->tick_partials, nw, tl.off_beat, (const uint64_t*)h->d_total, na.rec, h->G, h->N,
-                  h->self_peer, beat_cap, enc};
-      if (members) hipLaunchKernelGGL(beat_build_voters_kernel, grid, dim3(kBlock), 0, h->stream, ba, (const uint16_t*)h->voters, members_word(h));
-      else hipLaunchKernelGGL(beat_build_kernel, grid, dim3(kBlock), 0, h->stream, ba);
-    }
+    if (beat_cap != 0) beat_enqueue(h, na, tl, members, beat_cap, enc);
     // (hup_cap == 0: the fillers behind beat_cap * (N - 1) are beat_build_kernel's own -- the call is raftq_tick_frames)
     if (hup_cap != 0) {
       ElectArgs ea{(const uint64_t*)h->hup_bits, (const uint4*)h->tick_partials, nw, tl.off_h, (const uint64_t*)h->d_total, na, hup_cap, beat_cap,

@@ -1,5 +1,5 @@
 """GPU: raftq_respond_set_lead (include/raftq_wire.h) -- raftq_step_frames_respond answers RAFTQ_OUT_BECAME_LEADER with becomeLeader's
-broadcast, built on the device: the *_lead_kernel walks, resp_scatter_lead_kernel and the entry headers in the encoder's input.
+broadcast, built on the device: the *_lead_kernel walks, resp_scatter_lead_kernel (over members: resp_scatter_lead_voters_kernel) and the entry headers in the encoder's input.
 
 The expected frames come from tests/ref_respond_lead.py -- tests/test_respond_gpu.py::expected with the new rule restated from the
 header -- run over the oracle's Step results and marshalled by oracle/pywire.  Everything but "switch off" fails on a tree without

@@ -2,16 +2,16 @@
 """raftq_propose_frames and raftq_step_frames_respond over each group's own members (raftq_bcast_set_voters:
 propose_check_voters_kernel, propose_build_voters_kernel, resp_count_voters_kernel, resp_scatter_voters_kernel) against the same
 calls on a handle without masks -- the parent's path.  Three handles of one shape in the same state, in one process:
-  none     no masks loaded (the parent's kernels)
-  full     every slot votes, the switch on (the twins, the same frames)
+  none     no masks loaded (the unmasked instantiations)
+  full     every slot votes, the switch on (the masked instantiations, the same frames)
   random   masks uniform in [1, 2^N) -- for the proposals with self and one other slot made voters, or the call would refuse the
-           record -- the switch on (the twins, fewer frames)
+           record -- the switch on (the masked instantiations, fewer frames)
 Two calls:
   raftq_propose_frames       32,768 x 3, one statement per group behind 65,536 queued messages (the one-node leg's turn)
   raftq_step_frames_respond  1M x 5, 65,536 frames: two acks for each of 32,768 led groups whose tail was moved one entry on by an
                              (untimed) tail report, every at-tail bit set -- without masks the second ack commits and broadcasts
 The settings are ALTERNATED five times, 10 calls a turn after a warm-up turn; per setting the median and the range of the five
-turns' medians, wall time of the whole call (one submission, one wait).  What to hold the twins against is the `none` setting of
+turns' medians, wall time of the whole call (one submission, one wait).  What to hold the masked forms against is the `none` setting of
 the same run.
 What is expected, by construction: full masks move the same frames and add a 2-byte read per proposal or broadcast, for the
 proposals an 8-byte memset and a one-thread kernel: a few us.  Random masks send fewer bytes over the link and should be faster.
