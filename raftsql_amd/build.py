@@ -49,6 +49,8 @@ def lib_sources() -> list[str]:
         os.path.join(CSRC, "raftq_tick_voters_block.inc"),
         os.path.join(CSRC, "raftq_internal.hpp"),
         os.path.join(CSRC, "raftq_buffers.hpp"),
+        os.path.join(CSRC, "raftq_step_rounds.hpp"),
+        os.path.join(CSRC, "raftq_sort_kernels.hpp"),
         os.path.join(CSRC, "raftq_wire_kernels.hpp"),
         os.path.join(CSRC, "raftq_wire_parse.hpp"),
         os.path.join(CSRC, "raftq_propose_kernels.hpp"),

@@ -16,6 +16,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <unordered_set>
 #include <vector>
 
@@ -71,14 +72,61 @@ struct SweepLaunch {
   uint64_t gpad = 0;
 };
 
-// nt: 0 = cached loads and stores, 1 = non-temporal loads, normal stores, 3 = both non-temporal
+// The sweep kernels' compile-time parameters.  Each of the three helpers below turns one run-time value into a constant and hands
+// it to a generic callable; the launch functions behind them state only their kernel, grid, groups-per-lane rule and arguments.
+template <int V>
+using Const = std::integral_constant<int, V>;
+template <bool COMMIT, bool GATED, bool VOTES>
+struct FlagForm {
+  static constexpr bool commit = COMMIT, gated = GATED, votes = VOTES;
+};
+
+// the peer count, 1-9
+template <class F>
+hipError_t with_peers(uint32_t N, F f) {
+  switch (N) {
+    case 1: return f(Const<1>{});
+    case 2: return f(Const<2>{});
+    case 3: return f(Const<3>{});
+    case 4: return f(Const<4>{});
+    case 5: return f(Const<5>{});
+    case 6: return f(Const<6>{});
+    case 7: return f(Const<7>{});
+    case 8: return f(Const<8>{});
+    case 9: return f(Const<9>{});
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// the flag forms that exist: commit + gated with and without votes, commit with and without votes, votes alone.  (The LDS variant
+// sweeps commits only: of these it sees gated x votes.)
+template <class F>
+hipError_t with_flag_form(unsigned flags, F f) {
+  const bool commit = flags & (RAFTQ_SWEEP_COMMIT | RAFTQ_SWEEP_GATED);
+  const bool gated = flags & RAFTQ_SWEEP_GATED;
+  const bool votes = flags & RAFTQ_SWEEP_VOTES;
+  if (commit && gated) return votes ? f(FlagForm<true, true, true>{}) : f(FlagForm<true, true, false>{});
+  if (commit) return votes ? f(FlagForm<true, false, true>{}) : f(FlagForm<true, false, false>{});
+  return f(FlagForm<false, false, true>{});
+}
+
+// the load/store policy.  nt: 0 = cached loads and stores, 1 = non-temporal loads, normal stores, 3 = both non-temporal
+template <class F>
+hipError_t with_policy(int nt, F f) {
+  if (nt == 3) return f(Const<kLdNT | kStNT>{});
+  if (nt == 1) return f(Const<kLdNT>{});
+  return f(Const<0>{});
+}
+
 // Tile size of the K-deep set grid, per peer count (profiles/r02/tune3_focus_*.jsonl, medians of 9 interleaved
 // runs): 2048-group tiles (GPL 8) win for N <= 5 (10.92 vs 11.15 us per 1M x 5 batch), 512-group tiles (GPL 2)
 // from N = 6 up, where the 8-group register set would not fit 5 waves per SIMD (N = 7: 29.0 vs 30.2 us).
 constexpr int set_gpl(int n_peers) { return n_peers <= 5 ? 8 : 2; }
 
-template <int N, bool COMMIT, bool GATED, bool VOTES, int POLICY>
-hipError_t launch_pol(const SweepLaunch& L, hipStream_t s) {
+// the plain sweep: one handle, a set as a K-deep grid, or a set as a persistent walk
+template <int N, class Form, int POLICY>
+hipError_t launch_reg(const SweepLaunch& L, hipStream_t s) {
+  constexpr bool COMMIT = Form::commit, GATED = Form::gated, VOTES = Form::votes;
   const unsigned tiles = (unsigned)(L.gpad / kTile);
   if (L.tab == nullptr) {
     hipLaunchKernelGGL((sweep_kernel<N, kGPL, COMMIT, GATED, VOTES, POLICY, true>), dim3(tiles), dim3(kBlock), 0, s, *L.one);
@@ -94,68 +142,44 @@ hipError_t launch_pol(const SweepLaunch& L, hipStream_t s) {
   return hipGetLastError();
 }
 
-template <int N, bool COMMIT, bool GATED, bool VOTES>
-hipError_t launch_reg(const SweepLaunch& L, int nt, hipStream_t s) {
-  if (nt == 3) return launch_pol<N, COMMIT, GATED, VOTES, kLdNT | kStNT>(L, s);
-  if (nt == 1) return launch_pol<N, COMMIT, GATED, VOTES, kLdNT>(L, s);
-  return launch_pol<N, COMMIT, GATED, VOTES, 0>(L, s);
-}
-
-template <int N, bool GATED, bool VOTES>
+// the LDS A/B variant: commit sweeps of one handle
+template <int N, class Form>
 hipError_t launch_lds(const SweepArgs& a, uint64_t gpad, hipStream_t s) {
-  constexpr uint64_t tile = (uint64_t)kBlock * kLdsGPL;
-  constexpr int rows = N + 1 + (GATED ? 1 : 0);
-  constexpr size_t lds = (size_t)kWaves * (kLdsGPL / 2) * rows * 1024;
-  const dim3 grid((unsigned)(gpad / tile));
-  hipLaunchKernelGGL((sweep_lds_kernel<N, kLdsGPL, GATED, VOTES, true>), grid, dim3(kBlock), lds, s, a);
-  return hipGetLastError();
+  if constexpr (Form::commit) {
+    constexpr uint64_t tile = (uint64_t)kBlock * kLdsGPL;
+    constexpr int rows = N + 1 + (Form::gated ? 1 : 0);
+    constexpr size_t lds = (size_t)kWaves * (kLdsGPL / 2) * rows * 1024;
+    const dim3 grid((unsigned)(gpad / tile));
+    hipLaunchKernelGGL((sweep_lds_kernel<N, kLdsGPL, Form::gated, Form::votes, true>), grid, dim3(kBlock), lds, s, a);
+    return hipGetLastError();
+  } else {
+    return hipErrorInvalidValue;  // (not reached: launch_sweep takes this path for commit sweeps only)
+  }
 }
 
-template <int N>
-hipError_t launch_n(const SweepLaunch& L, unsigned flags, int nt, hipStream_t s) {
-  const bool commit = flags & (RAFTQ_SWEEP_COMMIT | RAFTQ_SWEEP_GATED);
-  const bool gated = flags & RAFTQ_SWEEP_GATED;
-  const bool votes = flags & RAFTQ_SWEEP_VOTES;
-  if ((flags & RAFTQ_SWEEP_LDS) && commit) {
-    if (L.tab) return hipErrorInvalidValue;  // the LDS A/B variant sweeps one handle at a time
-    if (gated) return votes ? launch_lds<N, true, true>(*L.one, L.gpad, s) : launch_lds<N, true, false>(*L.one, L.gpad, s);
-    return votes ? launch_lds<N, false, true>(*L.one, L.gpad, s) : launch_lds<N, false, false>(*L.one, L.gpad, s);
-  }
-  if (commit && gated) return votes ? launch_reg<N, true, true, true>(L, nt, s) : launch_reg<N, true, true, false>(L, nt, s);
-  if (commit) return votes ? launch_reg<N, true, false, true>(L, nt, s) : launch_reg<N, true, false, false>(L, nt, s);
-  return launch_reg<N, false, false, true>(L, nt, s);
+hipError_t launch_sweep(uint32_t N, const SweepLaunch& L, unsigned flags, int nt, hipStream_t s) {
+  const bool lds = (flags & RAFTQ_SWEEP_LDS) && (flags & (RAFTQ_SWEEP_COMMIT | RAFTQ_SWEEP_GATED));
+  if (lds && L.tab) return hipErrorInvalidValue;  // the LDS A/B variant sweeps one handle at a time
+  return with_peers(N, [&](auto n) {
+    return with_flag_form(flags, [&](auto form) {
+      if (lds) return launch_lds<decltype(n)::value, decltype(form)>(*L.one, L.gpad, s);
+      return with_policy(nt, [&](auto pol) { return launch_reg<decltype(n)::value, decltype(form), decltype(pol)::value>(L, s); });
+    });
+  });
 }
 
 // the segmented turn's sweep (sweep_segments_kernel): commit-only sweeps of one handle
-template <int N>
-hipError_t launch_segments_n(const SweepArgs& a, uint32_t n_tiles, bool gated, int nt, Advance16* list, unsigned int* counts_host, unsigned int* counts_dev,
-                             hipStream_t s) {
-  const dim3 grid(n_tiles), block(kBlock);
-  if (gated) {
-    if (nt == 3) hipLaunchKernelGGL((sweep_segments_kernel<N, kGPL, true, kLdNT | kStNT>), grid, block, 0, s, a, list, counts_host, counts_dev);
-    else if (nt == 1) hipLaunchKernelGGL((sweep_segments_kernel<N, kGPL, true, kLdNT>), grid, block, 0, s, a, list, counts_host, counts_dev);
-    else hipLaunchKernelGGL((sweep_segments_kernel<N, kGPL, true, 0>), grid, block, 0, s, a, list, counts_host, counts_dev);
-  } else {
-    if (nt == 3) hipLaunchKernelGGL((sweep_segments_kernel<N, kGPL, false, kLdNT | kStNT>), grid, block, 0, s, a, list, counts_host, counts_dev);
-    else if (nt == 1) hipLaunchKernelGGL((sweep_segments_kernel<N, kGPL, false, kLdNT>), grid, block, 0, s, a, list, counts_host, counts_dev);
-    else hipLaunchKernelGGL((sweep_segments_kernel<N, kGPL, false, 0>), grid, block, 0, s, a, list, counts_host, counts_dev);
-  }
-  return hipGetLastError();
-}
 hipError_t launch_segments(uint32_t N, const SweepArgs& a, uint32_t n_tiles, bool gated, int nt, Advance16* list, unsigned int* counts_host,
                            unsigned int* counts_dev, hipStream_t s) {
-  switch (N) {
-    case 1: return launch_segments_n<1>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s);
-    case 2: return launch_segments_n<2>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s);
-    case 3: return launch_segments_n<3>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s);
-    case 4: return launch_segments_n<4>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s);
-    case 5: return launch_segments_n<5>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s);
-    case 6: return launch_segments_n<6>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s);
-    case 7: return launch_segments_n<7>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s);
-    case 8: return launch_segments_n<8>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s);
-    case 9: return launch_segments_n<9>(a, n_tiles, gated, nt, list, counts_host, counts_dev, s);
-    default: return hipErrorInvalidValue;
-  }
+  const dim3 grid(n_tiles), block(kBlock);
+  return with_peers(N, [&](auto n) {
+    return with_policy(nt, [&](auto pol) {
+      constexpr int NP = decltype(n)::value, POLICY = decltype(pol)::value;
+      if (gated) hipLaunchKernelGGL((sweep_segments_kernel<NP, kGPL, true, POLICY>), grid, block, 0, s, a, list, counts_host, counts_dev);
+      else hipLaunchKernelGGL((sweep_segments_kernel<NP, kGPL, false, POLICY>), grid, block, 0, s, a, list, counts_host, counts_dev);
+      return hipGetLastError();
+    });
+  });
 }
 
 // The masked sweep of one handle (sweep_voters_kernel).  Groups per lane by peer count, read off the register report
@@ -164,39 +188,18 @@ hipError_t launch_segments(uint32_t N, const SweepArgs& a, uint32_t n_tiles, boo
 // (N <= 6: 48-73 VGPRs); from N = 7 it would be 80-113 VGPRs and 4-5 waves, so 2 groups per lane (46-63 VGPRs, 8 waves).
 constexpr int voters_gpl(int n_peers) { return n_peers <= 6 ? 4 : 2; }
 
-template <int N, bool COMMIT, bool GATED, bool VOTES>
-hipError_t launch_voters_reg(const VoterSweepArgs& a, uint64_t gpad, int nt, hipStream_t s) {
-  constexpr int G = voters_gpl(N);
-  const dim3 grid((unsigned)(gpad / ((uint64_t)kBlock * G))), block(kBlock);
-  if (nt == 3) hipLaunchKernelGGL((sweep_voters_kernel<N, G, COMMIT, GATED, VOTES, kLdNT | kStNT>), grid, block, 0, s, a);
-  else if (nt == 1) hipLaunchKernelGGL((sweep_voters_kernel<N, G, COMMIT, GATED, VOTES, kLdNT>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((sweep_voters_kernel<N, G, COMMIT, GATED, VOTES, 0>), grid, block, 0, s, a);
-  return hipGetLastError();
-}
-
-template <int N>
-hipError_t launch_voters_n(const VoterSweepArgs& a, uint64_t gpad, unsigned flags, int nt, hipStream_t s) {
-  const bool commit = flags & (RAFTQ_SWEEP_COMMIT | RAFTQ_SWEEP_GATED);
-  const bool gated = flags & RAFTQ_SWEEP_GATED;
-  const bool votes = flags & RAFTQ_SWEEP_VOTES;
-  if (commit && gated) return votes ? launch_voters_reg<N, true, true, true>(a, gpad, nt, s) : launch_voters_reg<N, true, true, false>(a, gpad, nt, s);
-  if (commit) return votes ? launch_voters_reg<N, true, false, true>(a, gpad, nt, s) : launch_voters_reg<N, true, false, false>(a, gpad, nt, s);
-  return launch_voters_reg<N, false, false, true>(a, gpad, nt, s);
-}
-
 hipError_t launch_voters(uint32_t N, const VoterSweepArgs& a, uint64_t gpad, unsigned flags, int nt, hipStream_t s) {
-  switch (N) {
-    case 1: return launch_voters_n<1>(a, gpad, flags, nt, s);
-    case 2: return launch_voters_n<2>(a, gpad, flags, nt, s);
-    case 3: return launch_voters_n<3>(a, gpad, flags, nt, s);
-    case 4: return launch_voters_n<4>(a, gpad, flags, nt, s);
-    case 5: return launch_voters_n<5>(a, gpad, flags, nt, s);
-    case 6: return launch_voters_n<6>(a, gpad, flags, nt, s);
-    case 7: return launch_voters_n<7>(a, gpad, flags, nt, s);
-    case 8: return launch_voters_n<8>(a, gpad, flags, nt, s);
-    case 9: return launch_voters_n<9>(a, gpad, flags, nt, s);
-    default: return hipErrorInvalidValue;
-  }
+  return with_peers(N, [&](auto n) {
+    return with_flag_form(flags, [&](auto form) {
+      return with_policy(nt, [&](auto pol) {
+        using Form = decltype(form);
+        constexpr int NP = decltype(n)::value, G = voters_gpl(NP);
+        const dim3 grid((unsigned)(gpad / ((uint64_t)kBlock * G))), block(kBlock);
+        hipLaunchKernelGGL((sweep_voters_kernel<NP, G, Form::commit, Form::gated, Form::votes, decltype(pol)::value>), grid, block, 0, s, a);
+        return hipGetLastError();
+      });
+    });
+  });
 }
 
 // The masked sweep of a set (sweep_set_voters_kernel): sweep_voters_kernel's tile and groups per lane, blockIdx.y = member.
@@ -206,54 +209,19 @@ struct VoterSetLaunch {
   uint64_t gpad;
 };
 
-template <int N, bool COMMIT, bool GATED, bool VOTES>
-hipError_t launch_set_voters_reg(const VoterSetLaunch& L, int nt, hipStream_t s) {
-  constexpr int G = voters_gpl(N);
-  const dim3 grid((unsigned)(L.gpad / ((uint64_t)kBlock * G)), L.members), block(kBlock);
-  if (nt == 3) hipLaunchKernelGGL((sweep_set_voters_kernel<N, G, COMMIT, GATED, VOTES, kLdNT | kStNT>), grid, block, 0, s, L.tab, L.want_bits);
-  else if (nt == 1) hipLaunchKernelGGL((sweep_set_voters_kernel<N, G, COMMIT, GATED, VOTES, kLdNT>), grid, block, 0, s, L.tab, L.want_bits);
-  else hipLaunchKernelGGL((sweep_set_voters_kernel<N, G, COMMIT, GATED, VOTES, 0>), grid, block, 0, s, L.tab, L.want_bits);
-  return hipGetLastError();
-}
-
-template <int N>
-hipError_t launch_set_voters_n(const VoterSetLaunch& L, unsigned flags, int nt, hipStream_t s) {
-  const bool commit = flags & (RAFTQ_SWEEP_COMMIT | RAFTQ_SWEEP_GATED);
-  const bool gated = flags & RAFTQ_SWEEP_GATED;
-  const bool votes = flags & RAFTQ_SWEEP_VOTES;
-  if (commit && gated) return votes ? launch_set_voters_reg<N, true, true, true>(L, nt, s) : launch_set_voters_reg<N, true, true, false>(L, nt, s);
-  if (commit) return votes ? launch_set_voters_reg<N, true, false, true>(L, nt, s) : launch_set_voters_reg<N, true, false, false>(L, nt, s);
-  return launch_set_voters_reg<N, false, false, true>(L, nt, s);
-}
-
 hipError_t launch_set_voters(uint32_t N, const VoterSetLaunch& L, unsigned flags, int nt, hipStream_t s) {
-  switch (N) {
-    case 1: return launch_set_voters_n<1>(L, flags, nt, s);
-    case 2: return launch_set_voters_n<2>(L, flags, nt, s);
-    case 3: return launch_set_voters_n<3>(L, flags, nt, s);
-    case 4: return launch_set_voters_n<4>(L, flags, nt, s);
-    case 5: return launch_set_voters_n<5>(L, flags, nt, s);
-    case 6: return launch_set_voters_n<6>(L, flags, nt, s);
-    case 7: return launch_set_voters_n<7>(L, flags, nt, s);
-    case 8: return launch_set_voters_n<8>(L, flags, nt, s);
-    case 9: return launch_set_voters_n<9>(L, flags, nt, s);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-hipError_t launch_sweep(uint32_t N, const SweepLaunch& L, unsigned flags, int nt, hipStream_t s) {
-  switch (N) {
-    case 1: return launch_n<1>(L, flags, nt, s);
-    case 2: return launch_n<2>(L, flags, nt, s);
-    case 3: return launch_n<3>(L, flags, nt, s);
-    case 4: return launch_n<4>(L, flags, nt, s);
-    case 5: return launch_n<5>(L, flags, nt, s);
-    case 6: return launch_n<6>(L, flags, nt, s);
-    case 7: return launch_n<7>(L, flags, nt, s);
-    case 8: return launch_n<8>(L, flags, nt, s);
-    case 9: return launch_n<9>(L, flags, nt, s);
-    default: return hipErrorInvalidValue;
-  }
+  return with_peers(N, [&](auto n) {
+    return with_flag_form(flags, [&](auto form) {
+      return with_policy(nt, [&](auto pol) {
+        using Form = decltype(form);
+        constexpr int NP = decltype(n)::value, G = voters_gpl(NP);
+        const dim3 grid((unsigned)(L.gpad / ((uint64_t)kBlock * G)), L.members), block(kBlock);
+        hipLaunchKernelGGL((sweep_set_voters_kernel<NP, G, Form::commit, Form::gated, Form::votes, decltype(pol)::value>), grid, block, 0, s,
+                           L.tab, L.want_bits);
+        return hipGetLastError();
+      });
+    });
+  });
 }
 
 }  // namespace

@@ -13,6 +13,7 @@
 
 #include "raftq_internal.hpp"
 #include "raftq_step_kernels.hpp"
+#include "raftq_step_rounds.hpp"
 #include "raftq_wire.h"
 #include "raftq_sort_kernels.hpp"
 #include "raftq_wire_kernels.hpp"
@@ -128,6 +129,59 @@ struct Scratch {
   size_t w_scan_bytes;
 };
 
+// the results of the last collected batch are no longer to be read (raftq_step_results*)
+void forget_results(raftq_t* h) {
+  h->step_last_out = nullptr;
+  h->step_last_n = 0;
+}
+
+// raftq_step_set_voters on a handle with masks loaded: the walks and the tail reports launch the *_voters_kernel twins.  So do the
+// walks of a raftq_step_frames_respond call (resp_on: the first pass and a stalled batch's replay) on a handle that opted in to
+// raftq_bcast_set_voters -- on its own authority, as raftq_tick_elect_frames uses the masked Step
+bool masked_step(const raftq_t* h) { return h->voters != nullptr && (h->step_voters || (h->resp_on && h->bcast_voters)); }
+// raftq_respond_set_lead: the walks of a raftq_step_frames_respond call (the first pass and a stalled batch's replay) are the
+// *_lead_kernel forms, whose respond() answers RAFTQ_OUT_BECAME_LEADER too; every other caller of the walks launches what it always did
+bool lead_step(const raftq_t* h) { return h->resp_on && h->resp_lead; }
+
+// One walk, launched in the form the handle's switches ask for.  raftq_step_walk_kernels.inc is expanded once per form, so a walk
+// comes as four entry points over one parameter list: plain, *_voters (masked_step: h->voters is appended), *_lead (lead_step) and
+// *_lead_voters.  The tail reports are never launched in a lead form and pass nullptr for those two.  The caller reads the launch's
+// error (hipGetLastError).
+template <class T>
+struct as_is {
+  using type = T;  // (keeps a parameter out of template argument deduction: A is what `plain` takes)
+};
+template <class... A>
+void launch_walk(const raftq_t* h, dim3 grid, void (*plain)(A...), typename as_is<void (*)(A..., const uint16_t*)>::type voters,
+                 typename as_is<void (*)(A...)>::type lead, typename as_is<void (*)(A..., const uint16_t*)>::type lead_voters,
+                 typename as_is<A>::type... args) {
+  const bool lead_form = lead != nullptr && lead_step(h);
+  if (masked_step(h))
+    hipLaunchKernelGGL((lead_form ? lead_voters : voters), grid, dim3(kBlock), 0, h->stream, args..., (const uint16_t*)h->voters);
+  else
+    hipLaunchKernelGGL((lead_form ? lead : plain), grid, dim3(kBlock), 0, h->stream, args...);
+}
+
+// The opening of the one-call entry points (raftq_step_batch, raftq_step_frames*): the device, the caller's counts zeroed, no
+// submitted batch in flight, the last results forgotten.
+template <class ZeroCounts>
+int one_call_open(raftq_t* h, const char* who, ZeroCounts zero_counts) {
+  if (int rc = use_device(h)) return rc;
+  zero_counts();
+  if (h->step_collected != h->step_submitted)
+    return fail(h, RAFTQ_ESTATE, std::string(who) + ": submitted batches are still in flight; collect them first");
+  forget_results(h);
+  return RAFTQ_OK;
+}
+
+// The closing of the frames calls, behind their collect: the decoder's verdict and counts.  A look-back that gave up overrides
+// Step's result: the records Step read are not to be trusted, nor is what it made of them
+int frames_close(raftq_t* h, const uint64_t* frame_off, uint64_t n, bool want_ents, uint64_t ents_cap, raftq_wire_counts_t* counts) {
+  const int rc_dec = raftq_detail::wire_frames_finish(h, frame_off, n, want_ents, ents_cap, counts);
+  if (rc_dec != RAFTQ_OK) forget_results(h);
+  return rc_dec;
+}
+
 size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 // result area: n records of `rec` bytes, then (16-byte aligned) the {touched count, bad, skipped} tail
 size_t tail_off(uint64_t n, uint32_t rec) { return ((size_t)n * rec + 15) / 16 * 16; }
@@ -173,7 +227,7 @@ int ensure_slot(raftq_t* h, raftq::StepSlot& sl, uint64_t n, Scratch* s, bool wi
   // the slot is idle (its previous batch was collected): safe to regrow
   HIPCHK(h, sl.dev.grow(off, std::max(off, (size_t)1 << 20) * 2, &h->stream));
   const size_t out_bytes = (size_t)n * sizeof(StepOutRec) + 16;
-  if (out_bytes > sl.out.cap && sl.out.h && h->step_last_out == sl.out.h) h->step_last_out = nullptr, h->step_last_n = 0;
+  if (out_bytes > sl.out.cap && sl.out.h && h->step_last_out == sl.out.h) forget_results(h);
   HIPCHK(h, sl.out.grow(out_bytes, std::max(out_bytes * 2, (size_t)1 << 20), nullptr));
   uint8_t* base = (uint8_t*)sl.dev.d;
   s->msgs = (MsgRec*)(base + o_msgs);
@@ -360,8 +414,7 @@ int raftq_step_set_compact(raftq_t* h, int on) {
   if (int rc = raftq_detail::use_device_idle(h, "raftq_step_set_compact")) return rc;
   if (on < 0 || on > 2) return fail(h, RAFTQ_EINVAL, "raftq_step_set_compact: 0 (64-byte records), 1 (40-byte) or 2 (32-byte)");
   h->step_compact = (uint8_t)on;
-  h->step_last_out = nullptr;
-  h->step_last_n = 0;
+  forget_results(h);
   return RAFTQ_OK;
 }
 
@@ -381,40 +434,18 @@ struct WireSrc {
   const raftq_detail::PackedDst* packed = nullptr;  // raftq_step_frames_packed: msgs_h is the narrow array
 };
 
-// raftq_step_set_voters on a handle with masks loaded: the walks and the tail reports launch the *_voters_kernel twins.  So do the
-// walks of a raftq_step_frames_respond call (resp_on: the first pass and a stalled batch's replay) on a handle that opted in to
-// raftq_bcast_set_voters -- on its own authority, as raftq_tick_elect_frames uses the masked Step
-static bool masked_step(const raftq_t* h) { return h->voters != nullptr && (h->step_voters || (h->resp_on && h->bcast_voters)); }
-// raftq_respond_set_lead: the walks of a raftq_step_frames_respond call (the first pass and a stalled batch's replay) are the
-// *_lead_kernel forms, whose respond() answers RAFTQ_OUT_BECAME_LEADER too; every other caller of the walks launches what it always did
-static bool lead_step(const raftq_t* h) { return h->resp_on && h->resp_lead; }
-
 // key -> stable radix sort -> walk, on the handle's stream (the path that takes runs of any length)
-static int enqueue_sorted_walk(raftq_t* h, const Scratch& s, uint64_t n, int end_bit, uint8_t recs, void* outs) {
+static int enqueue_sorted_walk(raftq_t* h, const Scratch& s, uint64_t n, int end_bit, uint8_t recs) {
   if (int rc = ensure_mirror(h)) return rc;
   unsigned int* bad = (unsigned int*)(s.n_heads + 1);
   const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
   hipLaunchKernelGGL(step_keys_kernel, grid, dim3(kBlock), 0, h->stream, (const MsgRec*)s.msgs, s.keys_in, s.order_in, n,
-                     h->G, h->N, bad, h->step_msg_flags, recs, outs, h->step_compact);
+                     h->G, h->N, bad, h->step_msg_flags, recs, s.outs, h->step_compact);
   HIPCHK(h, hipGetLastError());
   int in_b = 0;  // which pair of buffers the sorted (group, batch position) pairs end up in
   HIPCHK(h, raftqk::radix_sort_pairs(h->stream, s.sort_scratch, s.keys_in, s.order_in, s.keys_out, s.order_out, n, end_bit, &in_b));
-  if (lead_step(h) && masked_step(h))
-    hipLaunchKernelGGL(step_lead_voters_kernel, grid, dim3(kBlock), 0, h->stream, node_arrays(h, recs), (const MsgRec*)s.msgs,
-                       (const uint64_t*)(in_b ? s.keys_out : s.keys_in), (const uint32_t*)(in_b ? s.order_out : s.order_in), outs,
-                       h->step_compact, n, s.n_heads, (const unsigned int*)bad, (const uint16_t*)h->voters);
-  else if (lead_step(h))
-    hipLaunchKernelGGL(step_lead_kernel, grid, dim3(kBlock), 0, h->stream, node_arrays(h, recs), (const MsgRec*)s.msgs,
-                       (const uint64_t*)(in_b ? s.keys_out : s.keys_in), (const uint32_t*)(in_b ? s.order_out : s.order_in), outs,
-                       h->step_compact, n, s.n_heads, (const unsigned int*)bad);
-  else if (masked_step(h))
-    hipLaunchKernelGGL(step_voters_kernel, grid, dim3(kBlock), 0, h->stream, node_arrays(h, recs), (const MsgRec*)s.msgs,
-                       (const uint64_t*)(in_b ? s.keys_out : s.keys_in), (const uint32_t*)(in_b ? s.order_out : s.order_in), outs,
-                       h->step_compact, n, s.n_heads, (const unsigned int*)bad, (const uint16_t*)h->voters);
-  else
-    hipLaunchKernelGGL(step_kernel, grid, dim3(kBlock), 0, h->stream, node_arrays(h, recs), (const MsgRec*)s.msgs,
-                       (const uint64_t*)(in_b ? s.keys_out : s.keys_in), (const uint32_t*)(in_b ? s.order_out : s.order_in), outs,
-                       h->step_compact, n, s.n_heads, (const unsigned int*)bad);
+  launch_walk(h, grid, step_kernel, step_voters_kernel, step_lead_kernel, step_lead_voters_kernel, node_arrays(h, recs), s.msgs,
+              in_b ? s.keys_out : s.keys_in, in_b ? s.order_out : s.order_in, s.outs, h->step_compact, n, s.n_heads, bad);
   HIPCHK(h, hipGetLastError());
   return RAFTQ_OK;
 }
@@ -438,26 +469,10 @@ static int enqueue_list_walk(raftq_t* h, const Scratch& s, uint64_t n, uint8_t r
   }
   hipLaunchKernelGGL(step_link_kernel, dim3(blocks + in_link.blocks), dim3(kBlock), 0, h->stream, (const MsgRec*)s.msgs, n, h->G,
                      h->N, h->step_msg_flags, recs, (NodeRec*)h->node_rec, s.next, bad, h->step_stall, s.outs, h->step_compact, in_link);
-  if (lead_step(h)) {
-    HIPCHK(h, hipGetLastError());  // (the link kernel's, before the twin's launch can hide it)
-    if (masked_step(h))
-      hipLaunchKernelGGL(step_lists_lead_voters_kernel, dim3(blocks + in_walk.blocks), dim3(kBlock), 0, h->stream, node_arrays(h, recs),
-                         (const MsgRec*)s.msgs, s.outs, h->step_compact, n, h->G, (const uint32_t*)s.next, s.n_heads,
-                         skipped, (const unsigned int*)bad, (const unsigned int*)h->step_stall, in_walk, (const uint16_t*)h->voters);
-    else
-      hipLaunchKernelGGL(step_lists_lead_kernel, dim3(blocks + in_walk.blocks), dim3(kBlock), 0, h->stream, node_arrays(h, recs),
-                         (const MsgRec*)s.msgs, s.outs, h->step_compact, n, h->G, (const uint32_t*)s.next, s.n_heads,
-                         skipped, (const unsigned int*)bad, (const unsigned int*)h->step_stall, in_walk);
-  } else if (masked_step(h)) {
-    HIPCHK(h, hipGetLastError());  // (the link kernel's, before the twin's launch can hide it)
-    hipLaunchKernelGGL(step_lists_voters_kernel, dim3(blocks + in_walk.blocks), dim3(kBlock), 0, h->stream, node_arrays(h, recs),
-                       (const MsgRec*)s.msgs, s.outs, h->step_compact, n, h->G, (const uint32_t*)s.next, s.n_heads,
-                       skipped, (const unsigned int*)bad, (const unsigned int*)h->step_stall, in_walk, (const uint16_t*)h->voters);
-  } else {
-    hipLaunchKernelGGL(step_lists_kernel, dim3(blocks + in_walk.blocks), dim3(kBlock), 0, h->stream, node_arrays(h, recs),
-                       (const MsgRec*)s.msgs, s.outs, h->step_compact, n, h->G, (const uint32_t*)s.next, s.n_heads,
-                       skipped, (const unsigned int*)bad, (const unsigned int*)h->step_stall, in_walk);
-  }
+  HIPCHK(h, hipGetLastError());  // (the link kernel's, before the walk's launch can hide it)
+  launch_walk(h, dim3(blocks + in_walk.blocks), step_lists_kernel, step_lists_voters_kernel, step_lists_lead_kernel,
+              step_lists_lead_voters_kernel, node_arrays(h, recs), s.msgs, s.outs, h->step_compact, n, h->G, s.next, s.n_heads, skipped,
+              bad, h->step_stall, in_walk);
   HIPCHK(h, hipGetLastError());
   if (carry) {
     HIPCHK(h, hipEventRecord(carry->ev_out, h->stream));
@@ -466,46 +481,45 @@ static int enqueue_list_walk(raftq_t* h, const Scratch& s, uint64_t n, uint8_t r
   return RAFTQ_OK;
 }
 
-// the slot's result records (and tail) -> its pinned host buffer, as a kernel of its own
-static int enqueue_result_copy(raftq_t* h, raftq::StepSlot& sl, hipStream_t st) {
-  hipLaunchKernelGGL(step_d2h_kernel, dim3(d2h_blocks(sl.out_quads)), dim3(kBlock), 0, st, (const u64x2*)sl.outs_d, (u64x2*)sl.out.d,
-                     sl.out_quads, true);
+// the slot's result records (and tail) -> its pinned host buffer, as a kernel of its own on the handle's stream.  zero_tail: the
+// device copy of the tail is left zeroed behind the copy (step_d2h_kernel); whether the slot may count on that (tail_zeroed) is the
+// caller's to note
+static int enqueue_result_copy(raftq_t* h, raftq::StepSlot& sl, bool zero_tail) {
+  hipLaunchKernelGGL(step_d2h_kernel, dim3(d2h_blocks(sl.out_quads)), dim3(kBlock), 0, h->stream, (const u64x2*)sl.outs_d,
+                     (u64x2*)sl.out.d, sl.out_quads, zero_tail);
   HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipEventRecord(sl.ev_out, st));
+  HIPCHK(h, hipEventRecord(sl.ev_out, h->stream));
   sl.copy_pending = false;
   return RAFTQ_OK;
 }
 
-// rec_bytes: sizeof(raftq_msg_t), or sizeof(raftq_msg40_t) for packed records (widened on the device)
-static int submit_impl(raftq_t* h, const void* msgs, uint64_t n, const WireSrc* wire, const char* who,
-                       size_t rec_bytes = sizeof(raftq_msg_t)) {
-  const bool packed = rec_bytes != sizeof(raftq_msg_t);
-  if (int rc = use_device(h)) return rc;
-  if (int rc = raftq_detail::refuse_voters(h, who, !h->resp_on, false, h->resp_on)) return rc;  // (raftq_step_frames_respond: raftq_bcast_set_voters' call)
-  if (n == 0 || (!wire && !msgs)) return fail(h, RAFTQ_EINVAL, std::string(who) + ": empty batch");
-  if (n > 0x7ffffffeull) return fail(h, RAFTQ_EINVAL, std::string(who) + ": batch too large (2^31 - 2 messages at most)");
-  if (wire && ((!wire->stream && wire->nbytes) || !wire->frame_off))
-    return fail(h, RAFTQ_EINVAL, std::string(who) + ": null argument");
-  const int slot_no = (int)(h->step_submitted % raftq::kStepSlots);
-  raftq::StepSlot& sl = h->step_slot[slot_no];
-  if (sl.busy) return fail(h, RAFTQ_ESTATE, std::string(who) + ": three batches already in flight; collect one first");
-  if (int rc = ensure_node_state(h)) return rc;
-  int end_bit = 1;
-  while (end_bit < 64 && (h->G >> end_bit) != 0) ++end_bit;
-  size_t in_bytes;
-  bool staged_in_device = false;
-  const void* device_src = nullptr;
-  // raftq_step_stage_wire's arrays, filled in place: in device memory the decoder reads them where they lie; in pinned
-  // host memory two DMAs take them (the boundaries and the stream are not adjacent there)
-  bool wire_staged = false;
-  const bool frames = wire && wire->frames;
-  const uint8_t recs = frames ? raftqk::kRecsFrames : wire ? raftqk::kRecsWire : raftqk::kRecsCaller;
-  if (frames) {
-    if (!h->step_msg_flags)
-      return fail(h, RAFTQ_ESTATE, std::string(who) + ": the handle has not opted in to RAFTQ_MSGF_* (raftq_step_set_msg_flags)");
-    in_bytes = 0;  // nothing is staged: the decoder reads the caller's arrays where they lie
+// Where a batch's input lies when it is submitted.  Everything that differs between the forms follows from this one value: the host
+// copy (place_input), the DMA or the in-place routing and the slot's *_in_place fields (enqueue_input), and whether the result copy
+// may be deferred (in_device).
+enum class Input {
+  frames_in_place,  // raftq_step_frames*: page-locked arrays the streaming decoder reads where they lie; nothing is staged
+  wire_bar,         // raftq_step_stage_wire's arrays, filled in this slot's device (BAR) staging: the decoder reads them there
+  wire_pinned,      // ... filled in this slot's pinned staging: two DMAs (the boundaries and the stream are not adjacent there)
+  wire_copied,      // the caller's own arrays, copied into the pinned staging as [frame offsets][stream bytes]: one DMA moves both
+  recs_bar_own,     // records filled in this slot's device staging (raftq_step_stage): the kernels read them where they lie
+  recs_bar_other,   // records in another slot's device staging (a caller that kept an earlier batch's pointer): device to device
+  recs_pinned,      // records in, or copied into, this slot's pinned staging: one DMA
+};
+static bool in_device(Input where) { return where == Input::wire_bar || where == Input::recs_bar_own || where == Input::recs_bar_other; }
+
+struct Placed {
+  Input where;
+  size_t in_bytes;         // what a single DMA of the input moves
+  const void* device_src;  // the in_device forms: where in device memory the input lies
+};
+
+// Submit, phase 2: where the input lies, and for the copied forms the host copy into the slot's pinned staging.
+static int place_input(raftq_t* h, raftq::StepSlot& sl, const void* msgs, uint64_t n, const WireSrc* wire, size_t rec_bytes,
+                       const char* who, Placed* out) {
+  if (wire && wire->frames) {
+    *out = {Input::frames_in_place, 0, nullptr};
   } else if (wire) {
-    in_bytes = (size_t)(n + 1) * 8 + (size_t)wire->nbytes;
+    const size_t in_bytes = (size_t)(n + 1) * 8 + (size_t)wire->nbytes;
     const uint8_t* fo = (const uint8_t*)wire->frame_off;
     const uint8_t* sb = (const uint8_t*)wire->stream;
     auto inside = [&](const void* base, size_t cap) {
@@ -514,105 +528,120 @@ static int submit_impl(raftq_t* h, const void* msgs, uint64_t n, const WireSrc* 
              sl.w_stage_stream_off + (size_t)wire->nbytes <= cap;
     };
     if (inside(sl.in_bar.h, sl.in_bar.cap)) {
-      wire_staged = staged_in_device = true;
-      device_src = sl.in_bar.h;
       sl.in_bar.publish();
+      *out = {Input::wire_bar, in_bytes, sl.in_bar.h};
     } else if (inside(sl.in_h.h, sl.in_h.cap)) {
-      wire_staged = true;
+      *out = {Input::wire_pinned, in_bytes, nullptr};
     } else {
-      // staging = [frame offsets][stream bytes]: one DMA moves both
       if (int rc = ensure_slot_staging(h, sl, n, in_bytes)) return rc;
       std::memcpy(sl.in_h.h, wire->frame_off, (size_t)(n + 1) * 8);
       if (wire->nbytes) std::memcpy((uint8_t*)sl.in_h.h + (size_t)(n + 1) * 8, wire->stream, (size_t)wire->nbytes);
+      *out = {Input::wire_copied, in_bytes, nullptr};
     }
   } else {
-    in_bytes = (size_t)n * rec_bytes;
-    // unless the caller filled this slot's staging area in place (raftq_step_stage), copy into the pinned one
-    // (either slot's device staging counts: a caller that keeps filling the buffer raftq_step_stage gave it for an
-    // earlier batch must not be served by a host memcpy that READS device memory over the BAR -- 43 ms for 4 MB)
+    const size_t in_bytes = (size_t)n * rec_bytes;
+    // unless the caller filled a staging area in place (raftq_step_stage), copy into the pinned one.  Either slot's device staging
+    // counts: a caller that keeps filling the buffer raftq_step_stage gave it for an earlier batch must not be served by a host
+    // memcpy that READS device memory over the BAR -- 43 ms for 4 MB
+    const void* device_src = nullptr;
     for (const raftq::StepSlot& t : h->step_slot)
       if (t.in_bar.holds_in_device(msgs, in_bytes)) device_src = msgs, t.in_bar.publish();
     if (device_src) {
-      staged_in_device = true;
-    } else if ((const void*)msgs != sl.in_h.h) {
-      if (int rc = ensure_slot_staging(h, sl, n)) return rc;
-      std::memcpy(sl.in_h.h, msgs, in_bytes);
-    } else if (in_bytes > sl.in_h.cap) {
-      return fail(h, RAFTQ_EINVAL, std::string(who) + ": more messages than were staged");
+      *out = {sl.in_bar.holds_in_device(device_src, in_bytes) ? Input::recs_bar_own : Input::recs_bar_other, in_bytes, device_src};
+    } else {
+      if ((const void*)msgs != sl.in_h.h) {
+        if (int rc = ensure_slot_staging(h, sl, n)) return rc;
+        std::memcpy(sl.in_h.h, msgs, in_bytes);
+      } else if (in_bytes > sl.in_h.cap) {
+        return fail(h, RAFTQ_EINVAL, std::string(who) + ": more messages than were staged");
+      }
+      *out = {Input::recs_pinned, in_bytes, nullptr};
     }
   }
-  if (h->step_last_slot == slot_no) h->step_last_slot = -1;  // that batch's decoded records are about to be overwritten
-  sl.wire = false;
-  Scratch s;
-  if (int rc = ensure_slot(h, sl, n, &s, wire != nullptr && !frames, wire && !frames ? wire->nbytes : 0)) return rc;
-  // Step moves the live commit index: a what-if (NO_ADOPT) sweep's shadow values are no longer what
-  // raftq_read_committed should hand out
-  h->last_flags &= ~RAFTQ_SWEEP_NO_ADOPT;
-  // copy-in stream -> the handle's stream (state changes stay ordered with every other call on the handle; the result copy
-  // follows the compute there), chained by an event
+  return RAFTQ_OK;
+}
+
+// Submit, phase 3: the input onto the device, or the scratch pointers turned to where it already lies.
+// Copy-in stream -> the handle's stream (state changes stay ordered with every other call on the handle; the result copy follows the
+// compute there), chained by an event.  In: one DMA over PCIe from the pinned staging.  A batch the producer wrote straight into
+// device memory needs neither a DMA nor a copy: the kernels read it where it lies (the slot's staging stays untouched until the
+// slot's next batch, which is after this one's collect -- the replay path reads it there as well).  Round 2 first kept a
+// device-to-device copy into the slot's scratch; with the result copy inside the walk kernel that 3 us blit sat on the critical
+// path, held back like every other kernel while a kernel writes to host memory (rocprof: 2.4 .. 75 us).
+// *packed_src: where the unpack kernel finds packed records.
+static int enqueue_input(raftq_t* h, raftq::StepSlot& sl, Scratch& s, const Placed& in, const WireSrc* wire, uint64_t n, bool packed,
+                         const void** packed_src) {
   hipStream_t s_in = h->step_s_in;
-  // in: one DMA over PCIe from the pinned staging.  A batch the producer wrote straight into device memory needs neither
-  // a DMA nor a copy: the kernels read it where it lies (the slot's staging stays untouched until the slot's next batch,
-  // which is after this one's collect -- the replay path reads it there as well).  Round 2 first kept a device-to-device
-  // copy into the slot's scratch; with the result copy inside the walk kernel that 3 us blit sat on the critical path,
-  // held back like every other kernel while a kernel writes to host memory (rocprof: 2.4 .. 75 us).
+  const void* device_src = in.device_src;
+  const size_t in_bytes = in.in_bytes;
+  void* in_dst = wire ? (void*)s.w_off : packed ? s.msgs40 : (void*)s.msgs;
   sl.msgs_in_place = nullptr;
   sl.w_off_in_place = sl.w_stream_in_place = nullptr;
-  const void* packed_src = s.msgs40;
-  const bool own_staging = staged_in_device && sl.in_bar.holds_in_device(device_src, in_bytes);
-  if (frames) {
-    // (enqueued below, on the handle's stream, in front of Step's kernels)
-  } else if (wire && wire_staged && staged_in_device) {
-    s.w_off = (uint64_t*)const_cast<void*>(device_src);
-    s.w_stream = (uint8_t*)const_cast<void*>(device_src) + sl.w_stage_stream_off;
-    sl.w_off_in_place = s.w_off;
-    sl.w_stream_in_place = s.w_stream;
-  } else if (wire && wire_staged) {
-    HIPCHK(h, hipMemcpyAsync(s.w_off, sl.in_h.h, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s_in));
-    if (wire->nbytes)
-      HIPCHK(h, hipMemcpyAsync(s.w_stream, (const uint8_t*)sl.in_h.h + sl.w_stage_stream_off, (size_t)wire->nbytes,
-                               hipMemcpyHostToDevice, s_in));
-    HIPCHK(h, hipEventRecord(sl.ev_in, s_in));
-    HIPCHK(h, hipStreamWaitEvent(h->stream, sl.ev_in, 0));
-  } else if (own_staging) {
-    if (packed) packed_src = device_src;
-    else {
-      s.msgs = (MsgRec*)const_cast<void*>(device_src);
-      sl.msgs_in_place = device_src;
-    }
-  } else if (staged_in_device) {
-    // another slot's staging (a caller that kept an earlier batch's pointer): that buffer may be handed out again while
-    // this batch is in flight, so the records are copied into this slot's scratch, device to device
-    void* in_dst = packed ? s.msgs40 : (void*)s.msgs;
-    HIPCHK(h, hipMemcpyAsync(in_dst, device_src, in_bytes, hipMemcpyDeviceToDevice, s_in));
-    HIPCHK(h, hipEventRecord(sl.ev_in, s_in));
-    HIPCHK(h, hipStreamWaitEvent(h->stream, sl.ev_in, 0));
-  } else {
-    void* in_dst = wire ? (void*)s.w_off : packed ? s.msgs40 : (void*)s.msgs;
-    HIPCHK(h, hipMemcpyAsync(in_dst, sl.in_h.h, in_bytes, hipMemcpyHostToDevice, s_in));
-    HIPCHK(h, hipEventRecord(sl.ev_in, s_in));
-    HIPCHK(h, hipStreamWaitEvent(h->stream, sl.ev_in, 0));
+  *packed_src = s.msgs40;
+  switch (in.where) {
+    case Input::frames_in_place:  // (the decoder is enqueued in phase 5, on the handle's stream, in front of Step's kernels)
+      return RAFTQ_OK;
+    case Input::wire_bar:
+      s.w_off = (uint64_t*)const_cast<void*>(device_src);
+      s.w_stream = (uint8_t*)const_cast<void*>(device_src) + sl.w_stage_stream_off;
+      sl.w_off_in_place = s.w_off;
+      sl.w_stream_in_place = s.w_stream;
+      return RAFTQ_OK;
+    case Input::recs_bar_own:
+      if (packed) {
+        *packed_src = device_src;
+      } else {
+        s.msgs = (MsgRec*)const_cast<void*>(device_src);
+        sl.msgs_in_place = device_src;
+      }
+      return RAFTQ_OK;
+    case Input::wire_pinned:
+      HIPCHK(h, hipMemcpyAsync(s.w_off, sl.in_h.h, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s_in));
+      if (wire->nbytes)
+        HIPCHK(h, hipMemcpyAsync(s.w_stream, (const uint8_t*)sl.in_h.h + sl.w_stage_stream_off, (size_t)wire->nbytes,
+                                 hipMemcpyHostToDevice, s_in));
+      break;
+    case Input::recs_bar_other:
+      // that buffer may be handed out again while this batch is in flight, so the records are copied into this slot's scratch
+      HIPCHK(h, hipMemcpyAsync(in_dst, device_src, in_bytes, hipMemcpyDeviceToDevice, s_in));
+      break;
+    case Input::wire_copied:
+    case Input::recs_pinned:
+      HIPCHK(h, hipMemcpyAsync(in_dst, sl.in_h.h, in_bytes, hipMemcpyHostToDevice, s_in));
+      break;
   }
+  HIPCHK(h, hipEventRecord(sl.ev_in, s_in));
+  HIPCHK(h, hipStreamWaitEvent(h->stream, sl.ev_in, 0));
+  return RAFTQ_OK;
+}
+
+// Submit, phase 4: the tail behind the result records zeroed, packed records widened.  (packed_src == nullptr: not packed)
+static int enqueue_tail_reset_and_unpack(raftq_t* h, raftq::StepSlot& sl, const Scratch& s, uint64_t n, uint32_t rec, bool frames,
+                                         const void* packed_src) {
   // touched count + bad + skipped: the default result copy leaves them zeroed behind it (step_d2h_kernel zero_tail)
-  const uint32_t rec = result_rec_bytes(h);
   // (a frames batch: the decoder that heads the chain zeroes them)
   if (!frames && (!sl.tail_zeroed || sl.tail_n != n || sl.tail_rec != rec || sl.dev.d != sl.tail_dev)) {
     hipLaunchKernelGGL(step_reset_kernel, dim3(1), dim3(64), 0, h->stream, s.n_heads);
     HIPCHK(h, hipGetLastError());
   }
   sl.tail_zeroed = false;
-  if (packed) {
+  if (packed_src) {
     hipLaunchKernelGGL(raftqk::step_unpack40_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream,
                        (const raftqk::Msg40Rec*)packed_src, s.msgs, n);
     HIPCHK(h, hipGetLastError());
   }
-  if (frames) {
+  return RAFTQ_OK;
+}
+
+// Submit, phase 5: a wire batch's frames -> the batch's message records, on the handle's stream in front of Step's kernels.
+static int enqueue_decode(raftq_t* h, const Scratch& s, const WireSrc* wire, uint64_t n) {
+  if (wire && wire->frames) {
     // one kernel: readers pull boundaries + stream, workers parse, check, flag (RAFTQ_MSGF_*) and push records + entry headers
     // to the caller's arrays and the records once more into this slot's scratch
-    if (int rc = raftq_detail::wire_frames_enqueue(h, wire->stream, wire->nbytes, wire->frame_off, n, wire->msgs_h, wire->ents_h,
-                                                   wire->ents_cap, s.msgs, wire->tail_appends, s.n_heads, wire->packed))
-      return rc;
-  } else if (wire) {
+    return raftq_detail::wire_frames_enqueue(h, wire->stream, wire->nbytes, wire->frame_off, n, wire->msgs_h, wire->ents_h, wire->ents_cap,
+                                             s.msgs, wire->tail_appends, s.n_heads, wire->packed);
+  }
+  if (wire) {
     // frames -> the batch's message records, in HBM: the 64-byte records never cross PCIe.  (s.w_bad only counts
     // malformed frames for raftq_wire_decode's callers; here a malformed frame fails the batch through its flag byte.)
     const dim3 grid1((unsigned)((n + 1 + kBlock - 1) / kBlock));
@@ -622,37 +651,30 @@ static int submit_impl(raftq_t* h, const void* msgs, uint64_t n, const WireSrc* 
     // Step reads only the headers.  The entry headers (count -> scan -> second parse) are produced when
     // raftq_step_wire_msgs / _entries first asks for them: fetch_wire below.
   }
+  return RAFTQ_OK;
+}
+
+// Submit, phase 6: the walk, and with it the result copy of the batch submitted just before this one if that copy was deferred (phase
+// 7): it rides in the list walk's kernels, or goes as a kernel of its own in front of the sorted walk.  *lists: which walk it was.
+static int enqueue_walk(raftq_t* h, const Scratch& s, uint64_t n, int end_bit, uint8_t recs, bool* lists) {
   // traffic that keeps producing long runs (a few very hot groups) would stall and replay every batch: after two
   // stalls in a row the next 16 batches go straight to the sorted walk, then the list walk is tried again
   if (h->step_sorted_left) --h->step_sorted_left;
-  const bool lists = h->step_walk_mode == 1 && h->step_sorted_left == 0;
-  // Result copies.  With everything on the handle's stream (the default topology) a batch's copy is DEFERRED: it rides in
-  // the walk kernel of the batch submitted behind it, or is launched by its own collect if none is.  The batch submitted
-  // just before this one may be waiting for exactly that.
-  // Only for batches that arrived in device memory (raftq_step_stage behind a large BAR): a batch that needs an inbound
-  // DMA is better off with its own copy kernel -- the DMA of the batch after next cannot start while a kernel is writing
-  // to host memory either, and the fused kernel writes for longer (measured: caller-owned arrays 157 us per batch with
-  // their own copy kernels, 189 us deferred; staged batches 101 -> 77 us; profiles/r02/step_deferred_copy_ab.txt).
-  const bool defer = h->step_defer_copy && staged_in_device;
+  *lists = h->step_walk_mode == 1 && h->step_sorted_left == 0;
   raftq::StepSlot* carry = nullptr;
   if (h->step_submitted > h->step_collected) {
     raftq::StepSlot& prev = h->step_slot[(h->step_submitted - 1) % raftq::kStepSlots];
     if (prev.busy && prev.copy_pending) carry = &prev;
   }
-  if (lists) {
-    if (int rc = enqueue_list_walk(h, s, n, recs, carry)) return rc;
-  } else {
-    if (carry)
-      if (int rc = enqueue_result_copy(h, *carry, h->stream)) return rc;
-    if (int rc = enqueue_sorted_walk(h, s, n, end_bit, recs, s.outs)) return rc;
-  }
-  sl.outs_d = s.outs;
-  sl.out_quads = tail_off(n, rec) / 16 + 1;  // records + the 16-byte tail
-  if (defer) {
-    sl.copy_pending = true;
-  } else if (int rc = enqueue_result_copy(h, sl, h->stream)) {
-    return rc;
-  }
+  if (*lists) return enqueue_list_walk(h, s, n, recs, carry);
+  if (carry)
+    if (int rc = enqueue_result_copy(h, *carry, true)) return rc;
+  return enqueue_sorted_walk(h, s, n, end_bit, recs);
+}
+
+// Submit, phase 8: what collect, a replay and raftq_step_wire_* need to know of the batch now in flight in the slot.
+static void book_slot(raftq_t* h, raftq::StepSlot& sl, const Scratch& s, uint64_t n, const WireSrc* wire, uint8_t recs, uint32_t rec,
+                      int end_bit, bool lists) {
   sl.tail_zeroed = true;  // (once the copy has run) holds for the next batch of the same size and format in the same scratch
   sl.tail_n = n;
   sl.tail_rec = rec;
@@ -664,7 +686,7 @@ static int submit_impl(raftq_t* h, const void* msgs, uint64_t n, const WireSrc* 
   sl.end_bit = end_bit;
   sl.rec = rec;
   sl.w_nbytes = wire ? wire->nbytes : 0;
-  sl.wire = wire != nullptr && !frames;
+  sl.wire = wire != nullptr && !wire->frames;
   sl.recs = recs;
   sl.w_msgs_d = s.msgs;
   sl.w_ents_d = s.w_ents;
@@ -673,6 +695,63 @@ static int submit_impl(raftq_t* h, const void* msgs, uint64_t n, const WireSrc* 
   sl.w_msgs_fetched = sl.w_ents_fetched = false;
   sl.w_n_ents = 0;
   h->step_submitted++;
+}
+
+// One batch into the pipeline, in eight phases.  rec_bytes: sizeof(raftq_msg_t), or sizeof(raftq_msg40_t) for packed records
+// (widened on the device)
+static int submit_impl(raftq_t* h, const void* msgs, uint64_t n, const WireSrc* wire, const char* who,
+                       size_t rec_bytes = sizeof(raftq_msg_t)) {
+  const bool packed = rec_bytes != sizeof(raftq_msg_t);
+  const bool frames = wire && wire->frames;
+  // 1. refusals, in this order; a refused or failed call applies nothing
+  if (int rc = use_device(h)) return rc;
+  if (int rc = raftq_detail::refuse_voters(h, who, !h->resp_on, false, h->resp_on)) return rc;  // (raftq_step_frames_respond: raftq_bcast_set_voters' call)
+  if (n == 0 || (!wire && !msgs)) return fail(h, RAFTQ_EINVAL, std::string(who) + ": empty batch");
+  if (n > 0x7ffffffeull) return fail(h, RAFTQ_EINVAL, std::string(who) + ": batch too large (2^31 - 2 messages at most)");
+  if (wire && ((!wire->stream && wire->nbytes) || !wire->frame_off))
+    return fail(h, RAFTQ_EINVAL, std::string(who) + ": null argument");
+  const int slot_no = (int)(h->step_submitted % raftq::kStepSlots);
+  raftq::StepSlot& sl = h->step_slot[slot_no];
+  if (sl.busy) return fail(h, RAFTQ_ESTATE, std::string(who) + ": three batches already in flight; collect one first");
+  if (int rc = ensure_node_state(h)) return rc;
+  if (frames && !h->step_msg_flags)
+    return fail(h, RAFTQ_ESTATE, std::string(who) + ": the handle has not opted in to RAFTQ_MSGF_* (raftq_step_set_msg_flags)");
+  int end_bit = 1;
+  while (end_bit < 64 && (h->G >> end_bit) != 0) ++end_bit;
+  const uint8_t recs = frames ? raftqk::kRecsFrames : wire ? raftqk::kRecsWire : raftqk::kRecsCaller;
+  const uint32_t rec = result_rec_bytes(h);
+  // 2. input placement, host side
+  Placed in;
+  if (int rc = place_input(h, sl, msgs, n, wire, rec_bytes, who, &in)) return rc;
+  if (h->step_last_slot == slot_no) h->step_last_slot = -1;  // that batch's decoded records are about to be overwritten
+  sl.wire = false;
+  Scratch s;
+  if (int rc = ensure_slot(h, sl, n, &s, wire != nullptr && !frames, wire && !frames ? wire->nbytes : 0)) return rc;
+  // Step moves the live commit index: a what-if (NO_ADOPT) sweep's shadow values are no longer what
+  // raftq_read_committed should hand out
+  h->last_flags &= ~RAFTQ_SWEEP_NO_ADOPT;
+  // 3. input enqueue   4. tail reset and unpack   5. decode   6. walk, with the carried copy
+  const void* packed_src = nullptr;
+  bool lists = false;
+  if (int rc = enqueue_input(h, sl, s, in, wire, n, packed, &packed_src)) return rc;
+  if (int rc = enqueue_tail_reset_and_unpack(h, sl, s, n, rec, frames, packed ? packed_src : nullptr)) return rc;
+  if (int rc = enqueue_decode(h, s, wire, n)) return rc;
+  if (int rc = enqueue_walk(h, s, n, end_bit, recs, &lists)) return rc;
+  // 7. own copy or defer.  With everything on the handle's stream (the default topology) a batch's copy is DEFERRED: it rides in
+  // the walk kernel of the batch submitted behind it (phase 6 of that submit), or is launched by its own collect if none is.
+  // Only for batches that arrived in device memory (raftq_step_stage behind a large BAR): a batch that needs an inbound
+  // DMA is better off with its own copy kernel -- the DMA of the batch after next cannot start while a kernel is writing
+  // to host memory either, and the fused kernel writes for longer (measured: caller-owned arrays 157 us per batch with
+  // their own copy kernels, 189 us deferred; staged batches 101 -> 77 us; profiles/r02/step_deferred_copy_ab.txt).
+  sl.outs_d = s.outs;
+  sl.out_quads = tail_off(n, rec) / 16 + 1;  // records + the 16-byte tail
+  if (h->step_defer_copy && in_device(in.where)) {
+    sl.copy_pending = true;
+  } else if (int rc = enqueue_result_copy(h, sl, true)) {
+    return rc;
+  }
+  // 8. slot bookkeeping
+  book_slot(h, sl, s, n, wire, recs, rec, end_bit, lists);
   return RAFTQ_OK;
 }
 
@@ -796,13 +875,10 @@ static int replay_stalled(raftq_t* h, uint64_t first) {
     if (int rc = ensure_slot(h, sl, sl.n, &s, sl.wire, sl.w_nbytes)) return rc;
     if (sl.msgs_in_place) s.msgs = (MsgRec*)const_cast<void*>(sl.msgs_in_place);
     hipLaunchKernelGGL(step_reset_kernel, dim3(1), dim3(64), 0, h->stream, s.n_heads);
-    if (int rc = enqueue_sorted_walk(h, s, sl.n, sl.end_bit, sl.recs, s.outs)) return rc;
-    const uint64_t out_quads = tail_off(sl.n, sl.rec) / 16 + 1;
-    hipLaunchKernelGGL(step_d2h_kernel, dim3(d2h_blocks(out_quads)), dim3(kBlock), 0, h->stream, (const u64x2*)s.outs,
-                       (u64x2*)sl.out.d, out_quads);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(sl.ev_out, h->stream));
-    sl.copy_pending = false;
+    if (int rc = enqueue_sorted_walk(h, s, sl.n, sl.end_bit, sl.recs)) return rc;
+    sl.outs_d = s.outs;
+    sl.out_quads = tail_off(sl.n, sl.rec) / 16 + 1;
+    if (int rc = enqueue_result_copy(h, sl, /*zero_tail=*/false)) return rc;  // (the tail stays: no batch may count on a zeroed one)
     sl.tail_zeroed = false;
     sl.replayed = true;
     h->step_replays++;
@@ -818,7 +894,7 @@ int raftq_step_collect(raftq_t* h, raftq_step_out_t* out, raftq_step_counts_t* c
   if (h->step_collected == h->step_submitted) return fail(h, RAFTQ_ESTATE, "raftq_step_collect: nothing in flight");
   raftq::StepSlot& sl = h->step_slot[h->step_collected % raftq::kStepSlots];
   if (sl.copy_pending)  // nothing was submitted behind this batch: its results leave now
-    if (int rc = enqueue_result_copy(h, sl, h->stream)) return rc;
+    if (int rc = enqueue_result_copy(h, sl, true)) return rc;
   HIPCHK(h, hipEventSynchronize(sl.ev_out));
   sl.busy = false;
   h->step_last_slot = (int)(h->step_collected % raftq::kStepSlots);
@@ -839,8 +915,7 @@ int raftq_step_collect(raftq_t* h, raftq_step_out_t* out, raftq_step_counts_t* c
   std::memcpy(&heads, tail, 8);
   std::memcpy(&bad_h, tail + 8, 4);
   if (bad_h) {
-    h->step_last_out = nullptr;
-    h->step_last_n = 0;
+    forget_results(h);
     return fail(h, RAFTQ_EINVAL,
                 "raftq_step: a message is malformed (group or from out of range, or a type Step does not take); "
                 "nothing of that batch was applied");
@@ -862,12 +937,7 @@ int raftq_step_collect(raftq_t* h, raftq_step_out_t* out, raftq_step_counts_t* c
 
 int raftq_step_batch(raftq_t* h, const raftq_msg_t* msgs, uint64_t n, raftq_step_out_t* out,
                      raftq_step_counts_t* counts) {
-  if (int rc = use_device(h)) return rc;
-  if (counts) counts->n_msgs = counts->n_groups_touched = 0;
-  if (h->step_collected != h->step_submitted)
-    return fail(h, RAFTQ_ESTATE, "raftq_step_batch: submitted batches are still in flight; collect them first");
-  h->step_last_out = nullptr;
-  h->step_last_n = 0;
+  if (int rc = one_call_open(h, "raftq_step_batch", [&] { if (counts) counts->n_msgs = counts->n_groups_touched = 0; })) return rc;
   if (n == 0) return RAFTQ_OK;
   if (!msgs) return fail(h, RAFTQ_EINVAL, "raftq_step_batch: null messages");
   if (out && h->step_compact)
@@ -878,24 +948,14 @@ int raftq_step_batch(raftq_t* h, const raftq_msg_t* msgs, uint64_t n, raftq_step
 
 int raftq_step_frames(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off, uint64_t n, int tail_appends,
                       raftq_wire_msg_t* msgs, raftq_wire_ent_t* ents, uint64_t ents_cap, raftq_wire_counts_t* counts) {
-  if (int rc = use_device(h)) return rc;
-  if (counts) *counts = raftq_wire_counts_t{0, 0, 0, 0};
-  if (h->step_collected != h->step_submitted)
-    return fail(h, RAFTQ_ESTATE, "raftq_step_frames: submitted batches are still in flight; collect them first");
-  h->step_last_out = nullptr;
-  h->step_last_n = 0;
+  if (int rc = one_call_open(h, "raftq_step_frames", [&] { if (counts) *counts = raftq_wire_counts_t{0, 0, 0, 0}; })) return rc;
   if (n == 0) return RAFTQ_OK;
   if ((!stream && nbytes) || !frame_off || !msgs) return fail(h, RAFTQ_EINVAL, "raftq_step_frames: null argument");
   WireSrc w{stream, nbytes, frame_off, true, msgs, ents, ents ? ents_cap : 0, tail_appends};
   if (int rc = submit_impl(h, nullptr, n, &w, "raftq_step_frames")) return rc;
   // one wait: the result copy is the last kernel of the chain the decoder heads
   const int rc_step = raftq_step_collect(h, nullptr, nullptr);
-  const int rc_dec = raftq_detail::wire_frames_finish(h, frame_off, n, ents != nullptr, ents_cap, counts);
-  if (rc_dec != RAFTQ_OK) {  // a look-back gave up: the records Step read are not to be trusted, nor is what it made of them
-    h->step_last_out = nullptr;
-    h->step_last_n = 0;
-    return rc_dec;
-  }
+  if (int rc = frames_close(h, frame_off, n, ents != nullptr, ents_cap, counts)) return rc;
   return rc_step;
 }
 
@@ -903,13 +963,11 @@ int raftq_step_frames_packed(raftq_t* h, const void* stream, uint64_t nbytes, co
                              uint32_t head_types, void* narrow, raftq_wire_msg_t* wide, uint64_t wide_cap, raftq_wire_ent_t* ents, uint64_t ents_cap,
                              raftq_wire_counts_t* counts, uint64_t* n_wide) {
   const char* who = "raftq_step_frames_packed";
-  if (int rc = use_device(h)) return rc;
-  if (counts) *counts = raftq_wire_counts_t{0, 0, 0, 0};
-  if (n_wide) *n_wide = 0;
-  if (h->step_collected != h->step_submitted)
-    return fail(h, RAFTQ_ESTATE, std::string(who) + ": submitted batches are still in flight; collect them first");
-  h->step_last_out = nullptr;
-  h->step_last_n = 0;
+  auto zero_counts = [&] {
+    if (counts) *counts = raftq_wire_counts_t{0, 0, 0, 0};
+    if (n_wide) *n_wide = 0;
+  };
+  if (int rc = one_call_open(h, who, zero_counts)) return rc;
   if (form != RAFTQ_WIRE_FORM_40 && form != RAFTQ_WIRE_FORM_HEAD)
     return fail(h, RAFTQ_EINVAL, std::string(who) + ": form is neither RAFTQ_WIRE_FORM_40 nor RAFTQ_WIRE_FORM_HEAD");
   if (h->self_peer >= 255) return fail(h, RAFTQ_EINVAL, std::string(who) + ": the handle's own slot must be a peer slot (< 255)");
@@ -920,12 +978,7 @@ int raftq_step_frames_packed(raftq_t* h, const void* stream, uint64_t nbytes, co
   if (int rc = submit_impl(h, nullptr, n, &w, who)) return rc;
   // one wait, as raftq_step_frames
   const int rc_step = raftq_step_collect(h, nullptr, nullptr);
-  const int rc_dec = raftq_detail::wire_frames_finish(h, frame_off, n, ents != nullptr, ents_cap, counts);
-  if (rc_dec != RAFTQ_OK) {
-    h->step_last_out = nullptr;
-    h->step_last_n = 0;
-    return rc_dec;
-  }
+  if (int rc = frames_close(h, frame_off, n, ents != nullptr, ents_cap, counts)) return rc;
   if (n_wide) *n_wide = raftq_detail::wire_frames_n_wide(h);  // more than wide_cap is no error here: the frames have been stepped
   return rc_step;
 }
@@ -934,13 +987,11 @@ int raftq_step_frames_respond(raftq_t* h, const void* stream, uint64_t nbytes, c
                               raftq_wire_msg_t* msgs, raftq_wire_ent_t* ents, uint64_t ents_cap, const uint64_t* at_tail, void* out, uint64_t cap,
                               uint64_t* resp_off, uint64_t* peer_off, raftq_wire_counts_t* counts, raftq_wire_counts_t* resp_counts) {
   const char* who = "raftq_step_frames_respond";
-  if (int rc = use_device(h)) return rc;
-  if (counts) *counts = raftq_wire_counts_t{0, 0, 0, 0};
-  if (resp_counts) *resp_counts = raftq_wire_counts_t{0, 0, 0, 0};
-  if (h->step_collected != h->step_submitted)
-    return fail(h, RAFTQ_ESTATE, std::string(who) + ": submitted batches are still in flight; collect them first");
-  h->step_last_out = nullptr;
-  h->step_last_n = 0;
+  auto zero_counts = [&] {
+    if (counts) *counts = raftq_wire_counts_t{0, 0, 0, 0};
+    if (resp_counts) *resp_counts = raftq_wire_counts_t{0, 0, 0, 0};
+  };
+  if (int rc = one_call_open(h, who, zero_counts)) return rc;
   if (!peer_off) return fail(h, RAFTQ_EINVAL, std::string(who) + ": null argument");
   if (n == 0) {
     for (uint32_t p = 0; p <= h->N; ++p) peer_off[p] = 0;
@@ -988,12 +1039,7 @@ int raftq_step_frames_respond(raftq_t* h, const void* stream, uint64_t nbytes, c
     if (rc_step == RAFTQ_OK && raftq_detail::wait_call(h) != hipSuccess) rc_step = fail(h, RAFTQ_EHIP, std::string(who) + ": the replay's marshal failed");
   }
   h->resp_on = false;
-  const int rc_dec = raftq_detail::wire_frames_finish(h, frame_off, n, ents != nullptr, ents_cap, counts);
-  if (rc_dec != RAFTQ_OK) {
-    h->step_last_out = nullptr;
-    h->step_last_n = 0;
-    return rc_dec;
-  }
+  if (int rc = frames_close(h, frame_off, n, ents != nullptr, ents_cap, counts)) return rc;
   if (rc_step != RAFTQ_OK) return rc_step;
   return raftq_detail::respond_finish(h, rp, resp_counts);
 }
@@ -1028,82 +1074,29 @@ static int log_deltas_impl(raftq_t* h, const raftq_log_delta_t* d, uint64_t n, u
     stage_d = q.buf.d;
     stage_ev = q.ev;
   }
-  // The common batch names every group once: one round, caller order, no bookkeeping.  Whether it does is found
-  // with a per-group mark (epoch << 32 | records seen this call) -- an array lookup per record, not a hash map:
-  // the map this replaces was most of the call's host time at 10^4 records (raftq_node's "deltas" phase).
-  std::vector<uint32_t>& round = h->ld_round;    // per record: its round
-  std::vector<uint32_t>& pos_of = h->ld_pos;     // pos_of[staged position] = caller's index
-  std::vector<uint64_t>& round_start = h->ld_start;  // staged position where round r begins (+ the end)
+  // records of one group apply in order: the k-th record of a group goes into launch k (raftq_step_rounds.hpp).  The common batch
+  // names every group once: one launch, caller order
   uint32_t n_rounds = 1;
-  try {
-    if (h->ld_mark.size() != h->G) h->ld_mark.assign(h->G, 0);
-    if (++h->ld_epoch == 0) {
-      std::fill(h->ld_mark.begin(), h->ld_mark.end(), 0ull);
-      h->ld_epoch = 1;
-    }
-    const uint64_t ep = (uint64_t)h->ld_epoch << 32;
-    round.resize(n);
-    for (uint64_t i = 0; i < n; ++i) {
-      uint64_t& mk = h->ld_mark[d[i].group];
-      const uint32_t r = (mk >> 32) == h->ld_epoch ? (uint32_t)mk : 0;
-      mk = ep | (r + 1);
-      round[i] = r;
-      n_rounds = std::max(n_rounds, r + 1);
-    }
-    if (n_rounds > 1) {
-      pos_of.resize(n);
-      round_start.assign((size_t)n_rounds + 1, 0);
-      for (uint64_t i = 0; i < n; ++i) round_start[round[i] + 1]++;
-      for (uint32_t r = 0; r < n_rounds; ++r) round_start[r + 1] += round_start[r];
-    }
+  try {  // a bad_alloc must not cross the extern "C" boundary
+    n_rounds = raftq_rounds::plan(h->G, n, [d](uint64_t i) { return d[i].group; }, h->ld_mark, h->ld_epoch, h->ld_round, h->ld_start, h->ld_pos);
   } catch (...) {
     return fail(h, RAFTQ_ENOMEM, "raftq_apply_log_deltas: host allocation failed");
   }
+  const uint64_t whole[2] = {0, n};
+  const uint64_t* round_start = n_rounds == 1 ? whole : h->ld_start.data();  // staged position where round r begins (+ the end)
+  const uint32_t* pos_of = n_rounds == 1 ? nullptr : h->ld_pos.data();       // pos_of[staged position] = caller's index
   h->last_flags &= ~RAFTQ_SWEEP_NO_ADOPT;  // as in raftq_step_submit: the live commit index moves
   raftq_log_delta_t* dst = (raftq_log_delta_t*)stage_h;
   uint64_t* out_h = (uint64_t*)((uint8_t*)stage_h + off_out);
   uint64_t* out_d = (uint64_t*)((uint8_t*)stage_d + off_out);
-  auto launch = [&](uint64_t start, uint64_t m) {
-    if (masked_step(h))
-      hipLaunchKernelGGL(log_deltas_voters_kernel, dim3((unsigned)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream,
-                         node_arrays(h), (const LogDeltaRec*)stage_d + start, m,
-                         committed_out ? out_d + start : (uint64_t*)nullptr, (const uint16_t*)h->voters);
-    else
-      hipLaunchKernelGGL(log_deltas_kernel, dim3((unsigned)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream,
-                         node_arrays(h), (const LogDeltaRec*)stage_d + start, m,
-                         committed_out ? out_d + start : (uint64_t*)nullptr);
-  };
-  if (n_rounds == 1) {
-    std::memcpy(dst, d, (size_t)n * sizeof(raftq_log_delta_t));
-    launch(0, n);
-    HIPCHK(h, hipGetLastError());
-    if (!wait) {
-      HIPCHK(h, hipEventRecord(stage_ev, h->stream));
-      return RAFTQ_OK;
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (committed_out) std::memcpy(committed_out, out_h, (size_t)n * 8);
-    return RAFTQ_OK;
-  }
-  {
-    // records of one group apply in order: the k-th record of a group goes into launch k.  One counting sort on
-    // the round number buckets the batch in O(n) whatever the skew; stable, so caller order within a round
-    std::vector<uint64_t> fill;
-    try {  // a bad_alloc must not cross the extern "C" boundary
-      fill.assign(round_start.begin(), round_start.end() - 1);
-    } catch (...) {
-      return fail(h, RAFTQ_ENOMEM, "raftq_apply_log_deltas: host allocation failed");
-    }
-    for (uint64_t i = 0; i < n; ++i) {
-      const uint64_t pos = fill[round[i]]++;
-      pos_of[pos] = (uint32_t)i;
-      dst[pos] = d[i];
-    }
-  }
+  if (!pos_of) std::memcpy(dst, d, (size_t)n * sizeof(raftq_log_delta_t));
+  else
+    for (uint64_t k = 0; k < n; ++k) dst[k] = d[pos_of[k]];
   for (uint32_t r = 0; r < n_rounds; ++r) {
     const uint64_t start = round_start[r], m = round_start[r + 1] - start;
     if (m == 0) continue;
-    launch(start, m);
+    launch_walk(h, dim3((unsigned)((m + kBlock - 1) / kBlock)), log_deltas_kernel, log_deltas_voters_kernel, nullptr, nullptr, node_arrays(h),
+                (const LogDeltaRec*)stage_d + start, m, committed_out ? out_d + start : nullptr);
     HIPCHK(h, hipGetLastError());
   }
   if (!wait) {
@@ -1111,7 +1104,8 @@ static int log_deltas_impl(raftq_t* h, const raftq_log_delta_t* d, uint64_t n, u
     return RAFTQ_OK;
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (committed_out)
+  if (committed_out && !pos_of) std::memcpy(committed_out, out_h, (size_t)n * 8);
+  else if (committed_out)
     for (uint64_t k = 0; k < n; ++k) committed_out[pos_of[k]] = out_h[k];
   return RAFTQ_OK;
 }
