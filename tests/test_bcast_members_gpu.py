@@ -249,11 +249,17 @@ def test_full_masks_and_no_masks_are_the_unmasked_call(WireEngine, oracle):
 # ---- 5. propose against the restatement ----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("N,me,n_props,n_host", B.PROPOSE_SHAPES)
 def test_propose_matches_the_restatement(WireEngine, N, me, n_props, n_host):
+    G = 8192
+    _check_propose_members(WireEngine, *B.propose_input(B.propose_seed(N, n_props), G, N, me, n_props, n_host))
+
+
+def _check_propose_members(WireEngine, s, voters, props, pe, pool, hm, he):
+    """one raftq_propose_frames call over members against the restatement (s moves): the stream, the positional offsets, the
+    counts, the 0xEE behind the stream, the state after; then every other voter's ack commits the new tail"""
     from raftsql_amd import step as S_
     from raftsql_amd.engine import pinned_copy, pinned_empty
 
-    G = 8192
-    s, voters, props, pe, pool, hm, he = B.propose_input(B.propose_seed(N, n_props), G, N, me, n_props, n_host)
+    N, me = s.N, s.self_peer
     with _engine(WireEngine, s, voters) as e:
         committed0 = s.committed.copy()
         msgs, keep, ents = B.propose_expect(s, voters, props, pe, hm, he)  # (s moves)

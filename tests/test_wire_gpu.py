@@ -1182,6 +1182,26 @@ def _node_filter(wm, we, G, N, self_peer, tail_appends):
     return out, rec
 
 
+def _check_step_frames(e, st, s, off, tail_appends, what):
+    """one raftq_step_frames call against its parts, all from the oracle: decode, the node's checks (restated above), Step over
+    every frame with the flags the checks set -- decoded records, entry headers, counts, every result byte; st (the oracle state)
+    moves with it -> the result types"""
+    from raftsql_amd.engine import pinned_copy, pinned_empty
+
+    n = len(off) - 1
+    wm, we, _ = W.wire_decode(s, off)
+    want_m, rec = _node_filter(wm, we, st.G, st.N, st.self_peer, tail_appends)
+    want_o = st.step_batch(rec)
+    ps, po = pinned_copy(np.ascontiguousarray(s)), pinned_copy(np.ascontiguousarray(off, np.uint64))
+    msgs, ents = pinned_empty(n, W.WIRE_MSG_DT), pinned_empty(len(we) + 1, W.WIRE_ENT_DT)
+    gm, ge, go, c = e.step_frames(ps, po, msgs, ents, tail_appends=tail_appends)
+    assert (c.n_msgs, c.n_ents, c.bytes) == (n, len(we), len(s)) and c.n_malformed == int(((wm["flags"] & W.F_MALFORMED) != 0).sum())
+    _same(gm, want_m, f"records, {what}")
+    _same(ge, we, f"entry headers, {what}")
+    _same(go, want_o, f"results, {what}")
+    return set(int(t) for t in go["type"])
+
+
 @pytest.mark.parametrize("walk", ["lists", "sort"])
 @pytest.mark.parametrize("tail_appends", [True, False])
 def test_step_frames_equals_decode_filter_step(oracle, walk, tail_appends, monkeypatch):
@@ -1201,17 +1221,7 @@ def test_step_frames_equals_decode_filter_step(oracle, walk, tail_appends, monke
         _stepgen.load_engine(e, st)
         for it, n in enumerate([1, 255, 257, 4000, 9000, 700]):
             s, off = _node_frames(rng, n, st, me)
-            wm, we, _ = W.wire_decode(s, off)
-            want_m, rec = _node_filter(wm, we, G, N, me, tail_appends)
-            want_o = st.step_batch(rec)
-            ps, po = pinned_copy(np.ascontiguousarray(s)), pinned_copy(np.ascontiguousarray(off, np.uint64))
-            msgs, ents = pinned_empty(n, W.WIRE_MSG_DT), pinned_empty(len(we) + 1, W.WIRE_ENT_DT)
-            gm, ge, go, c = e.step_frames(ps, po, msgs, ents, tail_appends=tail_appends)
-            assert (c.n_msgs, c.n_ents, c.bytes) == (n, len(we), len(s)) and c.n_malformed == int(((wm["flags"] & W.F_MALFORMED) != 0).sum())
-            _same(gm, want_m, f"records, call {it}")
-            _same(ge, we, f"entry headers, call {it}")
-            _same(go, want_o, f"results, call {it}")
-            types = set(int(t) for t in go["type"])
+            types = _check_step_frames(e, st, s, off, tail_appends, f"call {it}")
             if n >= 4000:
                 assert {S.OUT_SKIPPED, S.OUT_HELD, S.OUT_DEFERRED} <= types and (not tail_appends or S.OUT_APPENDED in types)
         _stepgen.assert_same_state(e, st)
@@ -1477,11 +1487,16 @@ def test_propose_frames_is_append_entry_and_bcast_append(N, me, n_props, n_host)
     """raftq_propose_frames against the oracle's encoder over the messages bcastAppend would have built on the host: the stream
     and every frame offset byte for byte -- the caller's own messages first, then one run of MsgApps per peer --, and the
     device-resident state afterwards: lastIndex / lastTerm moved, the leader's own Match with them, nothing else touched."""
-    from raftsql_amd.engine import pinned_copy, pinned_empty
-
     G = 8192
     rng = np.random.default_rng(7000 + n_props + N)
-    st, props, pe, pool, hm, he = _propose_setup(rng, G, N, me, n_props, n_host)
+    _check_propose(G, N, me, *_propose_setup(rng, G, N, me, n_props, n_host))
+
+
+def _check_propose(G, N, me, st, props, pe, pool, hm, he):
+    """one raftq_propose_frames call on a handle loaded from st against _propose_expect + the oracle's encoder: the stream, the
+    offsets, the counts, the 0xEE behind the stream, the state after; then the quorum's acks commit the new tail"""
+    from raftsql_amd.engine import pinned_copy, pinned_empty
+
     want_m, want_e, new_last, new_last_term = _propose_expect(st, N, me, props, pe, hm, he)
     want, want_off = W.wire_encode(want_m, want_e, pool)
     with _propose_engine(G, N, me, st) as e:
