@@ -481,3 +481,122 @@ func TestStepVotersAgainstEtcd(t *testing.T) {
 		}
 	}
 }
+
+// TestStepPropsAgainstEtcd: forwarded proposals (raftq_step_set_props) beside a real raft.  A one-node group and a three-node
+// group are campaigned into leadership, then stepped with MsgProps of one to four entries between acknowledgements: after every
+// message the engine's term, commit index, leader and role are etcd's, and so is the log's tail.  Then the same on a follower
+// (the proposal is forwarded: nothing moves) and on a candidate (dropped).
+func TestStepPropsAgainstEtcd(t *testing.T) {
+	for _, n := range []int{1, 3} {
+		rng := rand.New(rand.NewSource(int64(0x9809 + n)))
+		peers := make([]raft.Peer, n)
+		for i := range peers {
+			peers[i] = raft.Peer{ID: uint64(i + 1)}
+		}
+		st := raft.NewMemoryStorage()
+		c := &raft.Config{ID: 1, ElectionTick: 10, HeartbeatTick: 1, Storage: st, MaxSizePerMsg: 1 << 20, MaxInflightMsgs: 256}
+		rn, err := raft.NewRawNode(c, peers)
+		if err != nil {
+			t.Fatal(err)
+		}
+		drain := func() {
+			for rn.HasReady() {
+				rd := rn.Ready()
+				st.Append(rd.Entries)
+				if !raft.IsEmptyHardState(rd.HardState) {
+					st.SetHardState(rd.HardState)
+				}
+				rn.Advance(rd)
+			}
+		}
+		drain()
+		e, err := New(0, 1, uint32(n))
+		if err != nil {
+			t.Skip(err) // no GPU here
+		}
+		defer e.Close()
+		for _, err := range []error{e.SetMsgFlags(true), e.SetStepProps(true)} {
+			if err != nil {
+				t.Fatal(err)
+			}
+		}
+		last, _ := st.LastIndex()
+		lt, _ := st.Term(last)
+		if err := e.LoadNode([]uint64{rn.Status().Term}, []uint32{0}, []uint32{0}, []uint64{last}, []uint64{lt}); err != nil {
+			t.Fatal(err)
+		}
+		check := func(what string) {
+			s := rn.Status()
+			ns, err := e.ReadNode()
+			if err != nil {
+				t.Fatal(err)
+			}
+			tail, _ := st.LastIndex()
+			role := map[raft.StateType]uint8{raft.StateFollower: 0, raft.StateCandidate: 1, raft.StateLeader: 2}[s.RaftState]
+			if ns.Term[0] != s.Term || ns.Committed[0] != s.Commit || uint64(ns.Lead[0]) != s.Lead || ns.Role[0] != role || ns.LastIndex[0] != tail {
+				t.Fatalf("n = %d after %s: etcd {term %d commit %d lead %d state %v tail %d}, restatement {term %d commit %d lead %d role %d tail %d}",
+					n, what, s.Term, s.Commit, s.Lead, s.RaftState, tail, ns.Term[0], ns.Committed[0], ns.Lead[0], ns.Role[0], ns.LastIndex[0])
+			}
+		}
+		step := func(m pb.Message, what string) StepOut {
+			rn.Step(m)
+			drain()
+			rec := Msg{Term: m.Term, LogTerm: m.LogTerm, Index: m.Index, Commit: m.Commit, From: uint32(m.From - 1), Type: uint8(m.Type)}
+			if m.Type == pb.MsgProp {
+				rec.Flags, rec.Resv = MsgfEntries, uint64(len(m.Entries))
+			}
+			out := make([]StepOut, 1)
+			if _, err := e.StepBatch([]Msg{rec}, out); err != nil {
+				t.Fatal(err)
+			}
+			check(what)
+			return out[0]
+		}
+		from := uint64(1) // (N = 1: the only possible sender is the node itself)
+		if n > 1 {
+			from = 2
+		}
+		prop := func(k int) pb.Message {
+			ents := make([]pb.Entry, k)
+			for i := range ents {
+				ents[i] = pb.Entry{Data: []byte{byte(i)}, Term: 77, Index: 99} // (appendEntry overwrites Term and Index)
+			}
+			return pb.Message{Type: pb.MsgProp, From: from, To: 1, Entries: ents}
+		}
+		// a follower without a leader drops it
+		if o := step(prop(1), "MsgProp on a leaderless follower"); o.Type != OutNone {
+			t.Fatalf("leaderless follower: type %d", o.Type)
+		}
+		rn.Campaign()
+		drain()
+		if _, err := e.StepBatch([]Msg{{Type: uint8(pb.MsgHup)}}, make([]StepOut, 1)); err != nil {
+			t.Fatal(err)
+		}
+		check("MsgHup")
+		term := rn.Status().Term
+		if n > 1 { // a candidate drops it, then wins
+			if o := step(prop(2), "MsgProp on a candidate"); o.Type != OutNone {
+				t.Fatalf("candidate: type %d", o.Type)
+			}
+			step(pb.Message{Type: pb.MsgVoteResp, From: 2, To: 1, Term: term}, "MsgVoteResp")
+		}
+		for i := 0; i < 100; i++ {
+			k := 1 + rng.Intn(4)
+			before, _ := st.LastIndex()
+			o := step(prop(k), "MsgProp on the leader")
+			if o.Type != OutProposed || o.Index != before+1 || o.LastIndex != before+uint64(k) || o.LogTerm != term {
+				t.Fatalf("leader: %+v, tail before %d, %d entries", o, before, k)
+			}
+			if n > 1 && rng.Intn(2) == 0 { // an acknowledgement somewhere at or below the new tail
+				tail, _ := st.LastIndex()
+				step(pb.Message{Type: pb.MsgAppResp, From: 2, To: 1, Term: term, Index: uint64(rng.Int63n(int64(tail) + 1))}, "MsgAppResp")
+			}
+		}
+		if n > 1 { // a heartbeat of a newer leader, then the proposal is forwarded to it
+			step(pb.Message{Type: pb.MsgHeartbeat, From: 3, To: 1, Term: term + 1}, "MsgHeartbeat of a newer term")
+			if o := step(prop(1), "MsgProp on a follower"); o.Type != OutForward || o.To != 2 {
+				t.Fatalf("follower: %+v", o)
+			}
+		}
+	}
+}

@@ -17,6 +17,7 @@ import "unsafe"
 const (
 	MsgHup           = C.RAFTQ_MSG_HUP
 	MsgBeat          = C.RAFTQ_MSG_BEAT
+	MsgProp          = C.RAFTQ_MSG_PROP // a follower's forwarded proposal: stepped only after SetStepProps(true), by its entry count
 	MsgApp           = C.RAFTQ_MSG_APP // header only: entries stay with the log's owner
 	MsgAppResp       = C.RAFTQ_MSG_APP_RESP
 	MsgVote          = C.RAFTQ_MSG_VOTE
@@ -33,13 +34,13 @@ type Msg struct {
 	From                                            uint32 // peer slot = raft ID - 1
 	Type, Reject                                    uint8
 	WireTo, Flags                                   uint8  // raftq_msg_t._pad: [1] = MsgfEntries | MsgfBarrier
-	Resv                                            uint64 // under MsgfEntries: low 32 bits = number of entries
+	Resv                                            uint64 // under MsgfEntries: low 32 bits = number of entries (MsgApp, MsgProp)
 }
 
 const (
-	MsgfEntries = C.RAFTQ_MSGF_ENTRIES // on a MsgApp: Resv = entry count, RejectHint = the last entry's term
+	MsgfEntries = C.RAFTQ_MSGF_ENTRIES // on a MsgApp: Resv = entry count, RejectHint = the last entry's term; required on a MsgProp: Resv = entry count
 	MsgfBarrier = C.RAFTQ_MSGF_BARRIER // on a MsgApp: what follows it in its group waits if it is left to the log's owner
-	MsgfHold    = C.RAFTQ_MSGF_HOLD    // not stepped (a MsgProp: the log owner's), answered OutHeld; the rest of its group is deferred
+	MsgfHold    = C.RAFTQ_MSGF_HOLD    // not stepped (a MsgProp without SetStepProps: the log owner's), answered OutHeld; the rest of its group is deferred
 	MsgfSkip    = C.RAFTQ_MSGF_SKIP    // nobody's: no field is looked at, answered OutSkipped
 )
 
@@ -62,6 +63,20 @@ func (e *Engine) SetStepVoters(on bool) error {
 		v = 1
 	}
 	return e.err(C.raftq_step_set_voters(e.h, v))
+}
+
+// SetStepProps opts the engine in to (or out of) Step for forwarded proposals (raftq_step_set_props): a Msg of type MsgProp with
+// Flags = MsgfEntries and Resv = its number of entries (at least one) is then stepped instead of failing its batch as an unknown
+// kind -- a leader answers OutProposed (Index = the first new index, LogTerm = the term every new entry is stamped with, LastIndex
+// = the new tail; the caller stores the entries and runs bcastAppend), a follower with a leader OutForward (To = Lead - 1, the one
+// result whose addressee is not the sender), a candidate or a leaderless follower OutNone -- and StepFrames* flag a MsgProp frame
+// MsgfEntries instead of MsgfHold.  Needs SetMsgFlags(true).  A property of the engine; no batch may be in flight.
+func (e *Engine) SetStepProps(on bool) error {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	return e.err(C.raftq_step_set_props(e.h, v))
 }
 
 // SetTickVoters opts the engine in to (or out of) Tick and its device-built rounds over each group's own members: with voter
@@ -97,6 +112,8 @@ const (
 	OutAppended       = C.RAFTQ_OUT_APPENDED // MsgApp flagged MsgfEntries that appended at the tail: store the entries, ack Index
 	OutSkipped        = C.RAFTQ_OUT_SKIPPED  // MsgfSkip
 	OutHeld           = C.RAFTQ_OUT_HELD     // MsgfHold
+	OutProposed       = C.RAFTQ_OUT_PROPOSED // SetStepProps: a leader took a MsgProp -- store its entries at Index .. LastIndex with Term LogTerm, then bcastAppend
+	OutForward        = C.RAFTQ_OUT_FORWARD  // SetStepProps: a follower's MsgProp goes on to its leader, To = Lead - 1
 
 	FlagHardState   = C.RAFTQ_OUTF_HARDSTATE // persist {Term, Vote, Commit} before sending (raft.go:228-230)
 	FlagCommitted   = C.RAFTQ_OUTF_COMMITTED

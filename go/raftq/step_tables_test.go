@@ -127,3 +127,58 @@ func TestUpstreamStepTablesAsRecalled(t *testing.T) {
 		e.Close()
 	}
 }
+
+// TestStepPropsTable: the MsgProp rows of include/raftq_step.h (raftq_step_set_props), one group each, N = 3, self = slot 0, at
+// term 5 with the log ending at (10, 4) and commit 7.  The Python twin is tests/test_step_props_ref.py's hand table.
+func TestStepPropsTable(t *testing.T) {
+	rows := []struct {
+		what               string
+		role               uint8
+		lead               uint32
+		term               uint64 // m.Term
+		n                  uint64 // entries
+		wantType           uint8
+		wantTo             uint32
+		wantIndex, wantLast uint64
+		wantRole           uint8
+	}{
+		{"leader", 2, 1, 0, 3, OutProposed, 1, 11, 13, 2},
+		{"follower with a leader", 0, 3, 0, 2, OutForward, 2, 0, 10, 0},
+		{"follower without a leader", 0, 0, 0, 2, OutNone, 1, 0, 10, 0},
+		{"candidate", 1, 0, 0, 2, OutNone, 1, 0, 10, 1},
+		{"leader, a higher term: follower of the sender, then forwarded to it", 2, 1, 6, 1, OutForward, 1, 0, 10, 0},
+		{"leader, a stale term: ignored", 2, 1, 4, 1, OutNone, 1, 0, 10, 2},
+	}
+	for _, r := range rows {
+		e, err := New(0, 1, 3)
+		if err != nil {
+			t.Skip(err) // no GPU: the engine has no CPU path
+		}
+		for _, err := range []error{e.SetSelf(0), e.SetMsgFlags(true), e.SetStepProps(true),
+			e.LoadMatch([]uint64{10, 8, 6}, []uint64{7}), e.LoadTerms([]uint64{5}, []uint64{9}), e.LoadRoles([]uint8{r.role}, nil),
+			e.LoadNode([]uint64{5}, []uint32{1}, []uint32{r.lead}, []uint64{10}, []uint64{4})} {
+			if err != nil {
+				t.Fatal(err)
+			}
+		}
+		out := make([]StepOut, 1)
+		if _, err := e.StepBatch([]Msg{{Term: r.term, From: 1, Type: MsgProp, Flags: MsgfEntries, Resv: r.n}}, out); err != nil {
+			t.Fatalf("%s: %v", r.what, err)
+		}
+		o := out[0]
+		if o.Type != r.wantType || o.To != r.wantTo || o.Index != r.wantIndex || o.LastIndex != r.wantLast || o.Role != r.wantRole {
+			t.Errorf("%s: got {type %d to %d index %d last %d role %d}, the header says {%d %d %d %d %d}", r.what, o.Type, o.To, o.Index,
+				o.LastIndex, o.Role, r.wantType, r.wantTo, r.wantIndex, r.wantLast, r.wantRole)
+		}
+		if r.wantType == OutProposed && (o.LogTerm != 5 || o.Commit != 7) {
+			t.Errorf("%s: log_term %d commit %d, want 5 and 7 (two of three peers do not hold the new entries)", r.what, o.LogTerm, o.Commit)
+		}
+		// a malformed MsgProp fails its batch: no flag, no entries
+		for _, bad := range []Msg{{From: 1, Type: MsgProp, Resv: 1}, {From: 1, Type: MsgProp, Flags: MsgfEntries}, {From: 3, Type: MsgProp, Flags: MsgfEntries, Resv: 1}} {
+			if _, err := e.StepBatch([]Msg{bad}, out); err == nil {
+				t.Errorf("%s: a malformed MsgProp %+v was accepted", r.what, bad)
+			}
+		}
+		e.Close()
+	}
+}

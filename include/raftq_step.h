@@ -14,11 +14,15 @@
  * clock (shared with raftq_tick), raftLog.committed / lastIndex / lastTerm,
  * every peer's Progress.Match, the candidate's vote map and the compact
  * current-term gate.  What stays with the caller: the log entries themselves
- * (so MsgProp / MsgSnap are not accepted and MsgApp is processed as a header:
- * the term / leader / clock handling happens here, raftLog.maybeAppend runs on
- * the caller's log and is reported back with raftq_apply_log_deltas), and the
+ * (so MsgSnap is refused and MsgApp is processed as a header: the term /
+ * leader / clock handling happens here, raftLog.maybeAppend runs on the
+ * caller's log and is reported back with raftq_apply_log_deltas), and the
  * replication flow control (Progress.Next / probe / replicate / inflights),
- * which decides what to send, not what is committed.
+ * which decides what to send, not what is committed.  A forwarded proposal
+ * (MsgProp) moves the state by its number of entries alone: Step takes it once
+ * the handle opted in (raftq_step_set_props below) -- the leader's appendEntry
+ * bookkeeping happens here, storing the entries and bcastAppend stay the
+ * caller's -- and refuses it as an unknown kind otherwise.
  *
  * Ordering: messages of one group are applied in batch order, exactly as if
  * Step had been called for them one after another; messages of different
@@ -40,6 +44,7 @@ extern "C" {
 /* raftpb.MessageType values of the message kinds Step accepts */
 #define RAFTQ_MSG_HUP 0            /* local: election timer fired (raftq_tick's MsgHup) */
 #define RAFTQ_MSG_BEAT 1           /* local: heartbeat timer fired (raftq_tick's MsgBeat) */
+#define RAFTQ_MSG_PROP 2           /* a follower's forwarded proposal: only under raftq_step_set_props, by its entry count */
 #define RAFTQ_MSG_APP 3            /* header only (see above) */
 #define RAFTQ_MSG_APP_RESP 4
 #define RAFTQ_MSG_VOTE 5
@@ -59,7 +64,7 @@ typedef struct raftq_msg {
   uint8_t type;         /* RAFTQ_MSG_* */
   uint8_t reject;       /* m.Reject */
   uint8_t _pad[2];      /* IGNORED unless the handle opted in (raftq_step_set_msg_flags): then _pad[1] = RAFTQ_MSGF_* */
-  uint64_t _resv;       /* IGNORED unless the handle opted in: then, under RAFTQ_MSGF_ENTRIES, low 32 bits = number of entries */
+  uint64_t _resv;       /* IGNORED unless the handle opted in: then, under RAFTQ_MSGF_ENTRIES, low 32 bits = number of entries (MsgApp, MsgProp) */
 } raftq_msg_t;          /* 64 bytes */
 
 /* The ten bytes behind `reject` are padding to every caller that has not said otherwise: raftq_step_stage hands out
@@ -106,13 +111,53 @@ int raftq_step_set_msg_flags(raftq_t* h, int on);
  * voters) and refuses them when made with raftq_set_create; raftq_node (which never loads masks) is as before. */
 int raftq_step_set_voters(raftq_t* h, int on);
 
+/* Step takes forwarded proposals.  In the reference every node has its own front end and calls node.Propose locally
+ * (raft.go:211-215); on a follower etcd's stepFollower forwards the proposal to the leader as a MsgProp frame, which reaches the
+ * leader through Process -> node.Step (raft.go:268-270): with three nodes, two thirds of all writes.
+ * 0 (default): type 2 is an unknown kind (a batch that holds one fails and applies nothing), and the frames calls of raftq_wire.h
+ *    flag every MsgProp frame RAFTQ_MSGF_HOLD -- the caller's, RAFTQ_OUT_HELD, the rest of its group RAFTQ_OUT_DEFERRED -- as before.
+ * 1: a record of type RAFTQ_MSG_PROP is stepped.  No batch in flight (RAFTQ_ESTATE); on other than 0 / 1: RAFTQ_EINVAL.  A
+ *    property of the handle, like raftq_step_set_voters: raftq_clone_state does not copy it.
+ * The switch matters only where a record's flag byte is read: without raftq_step_set_msg_flags type 2 stays an unknown kind
+ * (the switch itself is accepted).
+ *
+ * The record.  It carries RAFTQ_MSGF_ENTRIES and its number of entries where a MsgApp's is (the low 32 bits of _resv).  It is
+ * MALFORMED -- the batch fails and applies nothing -- without that flag, with a count of 0 (CHOICE: upstream's stepLeader panics on
+ * an empty MsgProp) or with `from` >= N.  RAFTQ_MSGF_HOLD and RAFTQ_MSGF_SKIP win over the type as on every record.  The entries'
+ * own Term and Index are not looked at (appendEntry overwrites them); no other field but group, term, from is read.  The caller
+ * keeps last_index + n below 2^64: nothing checks it.
+ *
+ * The rules (2015-era etcd/raft).  raft.send leaves a MsgProp's Term at 0, so it passes Step's term rules as a local message
+ * does; a record that does carry a term is judged by them as any message: a higher one makes the node a follower of `from` first,
+ * a lower one is ignored (RAFTQ_OUT_NONE).  Then, by role:
+ *   leader     appendEntry + the bookkeeping behind it: last_index += n, last_term = term, Progress[self].Match = last_index,
+ *              maybeCommit.  RAFTQ_OUT_PROPOSED: index = the FIRST new index, log_term = term (what every new entry is stamped
+ *              with), last_index = the new tail; RAFTQ_OUTF_COMMITTED | RAFTQ_OUTF_HARDSTATE when the commit index moved (N = 1,
+ *              or a one-voter group under raftq_step_set_voters).  It holds nobody up: the group's later messages of the batch
+ *              are stepped against the new tail, as upstream would (an acknowledgement's min(m.index, last_index) sees it).
+ *              Storing the entries and bcastAppend are the caller's.
+ *   follower   with a leader: RAFTQ_OUT_FORWARD, `to` = lead - 1 -- send the message on to the leader (`m.To = r.lead;
+ *              r.send(m)`).  Nothing changes.  Without a leader: dropped, RAFTQ_OUT_NONE.
+ *   candidate  dropped, RAFTQ_OUT_NONE.
+ *
+ * Where it does not reach: raftq_step_submit_wire (the pad bytes of its records are the decoder's, not RAFTQ_MSGF_*: type 2
+ * stays malformed there) and the 40-byte inbound raftq_msg40_t (it carries no count: type 2 is malformed there too).  The frames
+ * calls (raftq_step_frames, raftq_step_frames_packed, raftq_step_frames_respond; raftq_wire.h) with the switch on flag a MsgProp
+ * frame with entries RAFTQ_MSGF_ENTRIES (its count is the decoder's n_ents) and one without entries RAFTQ_MSGF_SKIP, as a frame
+ * of a kind a peer never sends; in the packed form a MsgProp with entries is a wide record, as every frame with entries is.
+ * raftq_step_frames_respond leaves both results to the host (no RAFTQ_OUTF_ANSWERED) and, behind a RAFTQ_OUT_PROPOSED, builds no
+ * commit broadcast for the group: its at-tail bit is cleared, no follower has the new entries yet.  raftq_node does not turn the
+ * switch on. */
+int raftq_step_set_props(raftq_t* h, int on);
+
 /* raftq_msg_t._pad[1] once the handle opted in.  RAFTQ_MSGF_ENTRIES on a MsgApp: the caller says what the message carries -- the low 32 bits of
  * _resv = its number of entries, reject_hint (a field MsgApp does not use) = the Term of the last one (unused with no
  * entries).  Step then runs raftLog.maybeAppend itself whenever the message appends at the TAIL of the log (m.Index ==
  * lastIndex and m.LogTerm == lastTerm: findConflict has nothing to look at): lastIndex / lastTerm move past the new
  * entries, commitTo(min(m.Commit, lastnewi)) runs, and the result is RAFTQ_OUT_APPENDED -- no raftq_apply_log_deltas
  * round trip for the common case of replication.  Every other MsgApp (a gap, a conflict, an index below the tail)
- * is answered RAFTQ_OUT_APPEND as without the flag.  Ignored on every other kind and on packed (40-byte) records. */
+ * is answered RAFTQ_OUT_APPEND as without the flag.  On a MsgProp (raftq_step_set_props) the flag is required and _resv says how
+ * many entries are proposed.  Ignored on every other kind and on packed (40-byte) records. */
 #define RAFTQ_MSGF_ENTRIES 0x80u
 /* RAFTQ_MSGF_BARRIER on a MsgApp: if Step leaves the append to the caller (RAFTQ_OUT_APPEND: the log's tail is about to change
  * in a way only the log's owner can work out), the messages of the same group that FOLLOW it in this batch are not applied --
@@ -120,8 +165,8 @@ int raftq_step_set_voters(raftq_t* h, int on);
  * raftq_apply_log_deltas.  With it a caller need not keep back everything behind a MsgApp: a batch may hold any number of
  * messages per group, and the ones that land on the tail (RAFTQ_OUT_APPENDED) hold nobody up. */
 #define RAFTQ_MSGF_BARRIER 0x40u
-/* RAFTQ_MSGF_HOLD on any record: the message is one Step does not take (raft.Propose's MsgProp, raft.go:211-215: appending is
- * the log owner's) but whose place in its group's arrival order matters.  It is NOT stepped -- its type and `from` are not even
+/* RAFTQ_MSGF_HOLD on any record: the message is one Step does not take (a MsgProp on a handle without raftq_step_set_props,
+ * raft.go:211-215) but whose place in its group's arrival order matters.  It is NOT stepped -- its type and `from` are not even
  * looked at -- and answered RAFTQ_OUT_HELD (the group's state as it stands at that point of the batch), whatever came before
  * it; every message of the group BEHIND it in this batch is answered RAFTQ_OUT_DEFERRED, as behind a barrier.  The caller
  * deals with the held message when it walks the results in order and steps the deferred ones in a later batch. */
@@ -146,6 +191,9 @@ int raftq_step_set_voters(raftq_t* h, int on);
                                      * the entries, send MsgAppResp{Index: index} (index = lastnewi = last_index); commit is final */
 #define RAFTQ_OUT_SKIPPED 10        /* RAFTQ_MSGF_SKIP: nothing looked at, nothing applied */
 #define RAFTQ_OUT_HELD 11           /* RAFTQ_MSGF_HOLD: not stepped; the group's later messages of this batch are RAFTQ_OUT_DEFERRED */
+#define RAFTQ_OUT_PROPOSED 12       /* leader took a MsgProp (raftq_step_set_props): store its n entries as {Term: log_term, Index: index ..
+                                     * last_index}, then bcastAppend */
+#define RAFTQ_OUT_FORWARD 13        /* follower's MsgProp: send it on to `to` = lead - 1, the one result whose addressee is not the sender */
 
 #define RAFTQ_OUTF_HARDSTATE 0x01u    /* Term, Vote or Commit changed: HardState must be persisted (wal.Save, raft.go:228) */
 #define RAFTQ_OUTF_COMMITTED 0x02u    /* raftLog.committed advanced (leader: bcastAppend carries it) */
@@ -159,7 +207,7 @@ typedef struct raftq_step_out {
   uint64_t log_term;   /* by type */
   uint64_t commit;     /* raftLog.committed after the message */
   uint64_t last_index; /* raftLog.lastIndex() after the message */
-  uint32_t to;         /* addressee of the response = sender of the message */
+  uint32_t to;         /* addressee of the response = sender of the message (RAFTQ_OUT_FORWARD: the leader's slot, lead - 1) */
   uint32_t vote;       /* r.Vote after: 0 = None, else peer slot + 1 */
   uint32_t lead;       /* r.lead after: 0 = None, else peer slot + 1 */
   uint8_t type;        /* RAFTQ_OUT_* */
@@ -252,7 +300,9 @@ int raftq_step_submit_packed(raftq_t* h, const raftq_msg40_t* msgs, uint64_t n);
 /* Compact result records: 40 instead of 64 bytes per message cross PCIe (the result copy is what a pipelined
  * batch waits for).  Record i answers msgs[i], so its group and addressee (= msgs[i].group, msgs[i].from) are not
  * repeated; `aux` is log_term for RAFTQ_OUT_CAMPAIGN / RAFTQ_OUT_BECAME_LEADER -- whose `index` is the last index --
- * and raftLog.lastIndex() for every other type (whose log_term is 0): the full record is recovered exactly.
+ * and raftLog.lastIndex() for every other type (whose log_term is 0, but for RAFTQ_OUT_PROPOSED, whose log_term IS its term):
+ * the full record is recovered exactly.  The addressee of a RAFTQ_OUT_FORWARD is not msgs[i].from: it is recovered from the
+ * record's `lead` (to = lead - 1), here and in the 32-byte record.
  * While the format is on, raftq_step_collect / _batch take out == NULL and the records are read in place through
  * raftq_step_results_c (valid until the next submit).  Switch only with no batch in flight. */
 typedef struct raftq_step_out_c {
@@ -272,7 +322,8 @@ typedef struct raftq_step_out_c {
  * needed by whoever applies a result (raftLog.lastIndex() after a message: the log's owner knows its own log) or recoverable:
  * log_term of a RAFTQ_OUT_BECAME_LEADER IS its term (becomeLeader appends the empty entry of the new term), and a
  * RAFTQ_OUT_CAMPAIGN -- which moves no commit index -- carries its log_term in `commit`.  The full record is recovered exactly
- * by a reader that tracks lastIndex / committed per group across the batch (tests/test_step_gpu.py does).  Why not the
+ * by a reader that tracks lastIndex / committed per group across the batch (tests/test_step_gpu.py does); behind a
+ * RAFTQ_OUT_PROPOSED the tail is index + n - 1, n being the count of the reader's own record, and its log_term is its term.  Why not the
  * 16-byte-per-message + 24-byte-per-touched-group form VERDICT r05 sketched: a result's term and commit are the state AFTER
  * THAT message (a vote response carries the term it was granted at, a leader broadcasts the commit index it had), so a group
  * needs a state record per CHANGE, not one per batch; with that, 16 + 24 k bytes per message (k = state changes per message)

@@ -66,7 +66,7 @@ extern "C" {
 #endif
 
 #define RAFTQ_MSG_SNAP 7 /* decoded, never accepted by Step */
-#define RAFTQ_MSG_PROP 2 /* decoded, never stepped: a follower forwarding a proposal to its leader -- the log owner's (raftq_step_frames holds it) */
+/* (RAFTQ_MSG_PROP = 2, a follower forwarding a proposal to its leader: raftq_step.h -- held by raftq_step_frames, or stepped under raftq_step_set_props) */
 
 /* raftq_wire_msg_t.flags */
 #define RAFTQ_WIRE_F_MALFORMED 0x01u /* frame did not parse: every other field of the record is 0 */
@@ -219,6 +219,9 @@ int raftq_step_wire_entries(raftq_t* h, const raftq_wire_ent_t** ents, uint64_t*
  *     the handle's own (raftq_set_self): RAFTQ_MSGF_SKIP -> RAFTQ_OUT_SKIPPED.  rafthttp would log and drop the stream; a node
  *     has to survive whatever bytes a peer throws at it.
  *   - MsgProp (appending is the log owner's): RAFTQ_MSGF_HOLD -> RAFTQ_OUT_HELD, the group's later frames RAFTQ_OUT_DEFERRED.
+ *     On a handle that opted in to raftq_step_set_props (raftq_step.h) instead: with entries RAFTQ_MSGF_ENTRIES -- Step takes it by
+ *     its count, RAFTQ_OUT_PROPOSED / RAFTQ_OUT_FORWARD / RAFTQ_OUT_NONE, and holds nobody up -- and without entries
+ *     RAFTQ_MSGF_SKIP, as a frame of a kind a peer never sends.
  *   - MsgApp: RAFTQ_MSGF_BARRIER, and with tail_appends != 0 RAFTQ_MSGF_ENTRIES (reject_hint, which a MsgApp does not use, is
  *     overwritten with the Term of its last entry) -- one that lands on the log's tail is RAFTQ_OUT_APPENDED.
  * Results: raftq_step_results (or _c), n records, out[i] answers frame i.  msgs / ents / counts as raftq_wire_decode, except
@@ -255,7 +258,8 @@ int raftq_step_frames_packed(raftq_t* h, const void* stream, uint64_t nbytes, co
  *                               follower at the tail): N - 1 empty MsgApp{Term, Index: lastIndex, LogTerm: lastTerm, Commit},
  *                               lastIndex / lastTerm / Commit as they stand AT THAT MESSAGE
  * Everything else stays the caller's and is not flagged: RAFTQ_OUT_APPEND, RAFTQ_OUT_BECAME_LEADER (unless raftq_respond_set_lead,
- * below, opted the handle in), resends and reject backoff, HELD / DEFERRED / SKIPPED / NONE.  A result the caller may have to answer itself (any of those that sends, a
+ * below, opted the handle in), resends and reject backoff, HELD / DEFERRED / SKIPPED / NONE, and under raftq_step_set_props RAFTQ_OUT_PROPOSED
+ * (which also clears the group's at_tail bit: no follower has the new entries before the host's bcastAppend) / RAFTQ_OUT_FORWARD.  A result the caller may have to answer itself (any of those that sends, a
  * MsgAppResp while the group's bit is clear) ends its group's device-answered prefix: the group's later results of the batch
  * are not answered either, so per (peer, group) the frames keep the order the host's own answers would have.
  * at_tail ([ceil(G / 64)] words, bit g = group g; NULL = all clear): the caller's word that it leads g and every follower's

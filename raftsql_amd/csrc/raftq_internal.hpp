@@ -121,6 +121,8 @@ struct raftq {
   bool step_msg_flags = false;     // raftq_msg_t._pad[1] / _resv carry RAFTQ_MSGF_* (raftq_step_set_msg_flags); padding otherwise
   bool step_voters = false;        // raftq_step_set_voters: with masks loaded the Step family runs the *_voters_kernel twins (a property of
                                    // the handle: raftq_clone_state and raftq_load_voters(h, NULL) leave it alone)
+  bool step_props = false;         // raftq_step_set_props: Step takes a forwarded proposal (MsgProp, by its entry count) and the frames calls
+                                   // flag one RAFTQ_MSGF_ENTRIES instead of RAFTQ_MSGF_HOLD (a property of the handle, as step_voters)
   bool tick_voters = false;        // raftq_tick_set_voters: with masks loaded Tick runs tick_voters_kernel (promotable()) and the two
                                    // device-built rounds go to each group's own members (the same kind of property as step_voters)
   bool bcast_voters = false;       // raftq_bcast_set_voters: with masks loaded raftq_step_frames_respond's commit broadcast and

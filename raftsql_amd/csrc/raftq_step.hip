@@ -71,6 +71,7 @@ NodeArrays node_arrays(raftq_t* h, uint8_t recs = raftqk::kRecsCaller) {
   a.self = h->self_peer;
   a.msg_flags = h->step_msg_flags;
   a.recs = recs;
+  a.props = h->step_props;
   a.n_groups = h->G;
   a.self_max = h->self_max;
   if (h->resp_on) {  // raftq_step_frames_respond: the walks (the list walk, the sorted one, a stalled batch's replay) answer too
@@ -410,6 +411,13 @@ int raftq_step_set_voters(raftq_t* h, int on) {
   return RAFTQ_OK;
 }
 
+int raftq_step_set_props(raftq_t* h, int on) {
+  if (int rc = raftq_detail::use_device_idle(h, "raftq_step_set_props")) return rc;
+  if (on != 0 && on != 1) return fail(h, RAFTQ_EINVAL, "raftq_step_set_props: 0 (MsgProp is an unknown kind; the frames calls hold it) or 1 (Step takes a forwarded proposal)");
+  h->step_props = on == 1;
+  return RAFTQ_OK;
+}
+
 int raftq_step_set_compact(raftq_t* h, int on) {
   if (int rc = raftq_detail::use_device_idle(h, "raftq_step_set_compact")) return rc;
   if (on < 0 || on > 2) return fail(h, RAFTQ_EINVAL, "raftq_step_set_compact: 0 (64-byte records), 1 (40-byte) or 2 (32-byte)");
@@ -440,7 +448,7 @@ static int enqueue_sorted_walk(raftq_t* h, const Scratch& s, uint64_t n, int end
   unsigned int* bad = (unsigned int*)(s.n_heads + 1);
   const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
   hipLaunchKernelGGL(step_keys_kernel, grid, dim3(kBlock), 0, h->stream, (const MsgRec*)s.msgs, s.keys_in, s.order_in, n,
-                     h->G, h->N, bad, h->step_msg_flags, recs, s.outs, h->step_compact);
+                     h->G, h->N, bad, h->step_msg_flags, recs, s.outs, h->step_compact, h->step_props);
   HIPCHK(h, hipGetLastError());
   int in_b = 0;  // which pair of buffers the sorted (group, batch position) pairs end up in
   HIPCHK(h, raftqk::radix_sort_pairs(h->stream, s.sort_scratch, s.keys_in, s.order_in, s.keys_out, s.order_out, n, end_bit, &in_b));
@@ -468,7 +476,7 @@ static int enqueue_list_walk(raftq_t* h, const Scratch& s, uint64_t n, uint8_t r
     in_walk = {(const u64x2*)carry->outs_d, (u64x2*)carry->out.d, cut, quads, quads - 1, d2h_blocks(quads - cut)};
   }
   hipLaunchKernelGGL(step_link_kernel, dim3(blocks + in_link.blocks), dim3(kBlock), 0, h->stream, (const MsgRec*)s.msgs, n, h->G,
-                     h->N, h->step_msg_flags, recs, (NodeRec*)h->node_rec, s.next, bad, h->step_stall, s.outs, h->step_compact, in_link);
+                     h->N, h->step_msg_flags, recs, (NodeRec*)h->node_rec, s.next, bad, h->step_stall, s.outs, h->step_compact, in_link, h->step_props);
   HIPCHK(h, hipGetLastError());  // (the link kernel's, before the walk's launch can hide it)
   launch_walk(h, dim3(blocks + in_walk.blocks), step_lists_kernel, step_lists_voters_kernel, step_lists_lead_kernel,
               step_lists_lead_voters_kernel, node_arrays(h, recs), s.msgs, s.outs, h->step_compact, n, h->G, s.next, s.n_heads, skipped,

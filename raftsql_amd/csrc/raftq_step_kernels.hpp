@@ -87,6 +87,7 @@ struct NodeArrays {
   bool msg_flags;   // the handle opted in to RAFTQ_MSGF_* (raftq_step_set_msg_flags): otherwise a record's pad bytes are padding
   uint8_t recs;     // whose records the batch holds: kRecsCaller, kRecsWire (raftq_step_submit_wire: the decoder's, strict) or
                     // kRecsFrames (raftq_step_frames: the decoder's, with RAFTQ_MSGF_* set by it)
+  bool props = false;  // raftq_step_set_props: a MsgProp that says how many entries it carries is stepped (it is an unknown kind otherwise)
   uint64_t n_groups;
   uint32_t* self_max = nullptr;  // the handle's self-max word (raftq_kernels.hpp): a store that breaks the fact clears it
   // raftq_step_frames_respond only (nullptr otherwise): the walk writes resp[i] for every message it steps, stamped resp_stamp,
@@ -97,11 +98,11 @@ struct NodeArrays {
 };
 constexpr uint8_t kRecsCaller = 0, kRecsWire = 1, kRecsFrames = 2;
 
-constexpr uint8_t kMsgHup = 0, kMsgBeat = 1, kMsgApp = 3, kMsgAppResp = 4, kMsgVote = 5, kMsgVoteResp = 6,
+constexpr uint8_t kMsgHup = 0, kMsgBeat = 1, kMsgProp = 2, kMsgApp = 3, kMsgAppResp = 4, kMsgVote = 5, kMsgVoteResp = 6,
                   kMsgHeartbeat = 8, kMsgHeartbeatResp = 9;
 constexpr uint8_t kOutNone = 0, kOutVoteResp = 1, kOutHeartbeatResp = 2, kOutCampaign = 3, kOutBecameLeader = 4,
                   kOutProgress = 5, kOutBcastHeartbeat = 6, kOutAppend = 7, kOutAppended = 8, kOutDeferred = 9, kOutSkipped = 10,
-                  kOutHeld = 11;
+                  kOutHeld = 11, kOutProposed = 12, kOutForward = 13;
 constexpr uint8_t kMsgfEntries = 0x80, kMsgfBarrier = 0x40, kMsgfHold = 0x20, kMsgfSkip = 0x10;  // raftq_msg_t._pad[1]: RAFTQ_MSGF_*
 constexpr uint8_t kFlagHardState = 1, kFlagCommitted = 2, kFlagUpdated = 4, kFlagSteppedDown = 8;
 constexpr uint8_t kFlagAnswered = 0x10;  // RAFTQ_OUTF_ANSWERED: the messages the result calls for were built on the device
@@ -193,12 +194,22 @@ static __global__ __launch_bounds__(kBlock) void step_unpack40_kernel(const Msg4
 // What the two grouping kernels make of record i.  kSkip: RAFTQ_MSGF_SKIP, nobody's (answered on the spot, never grouped);
 // kBad: fails the batch; kTake: goes to its group (a RAFTQ_MSGF_HOLD record too: only its group is looked at).
 enum RecClass : int { kTake = 0, kSkip = 1, kBad = 2 };
-__device__ __forceinline__ RecClass classify(const MsgRec& m, uint64_t n_groups, uint32_t n_peers, bool msg_flags, uint8_t recs) {
+// the number of entries a record says it carries under RAFTQ_MSGF_ENTRIES (the decoder's record keeps ent_first | n_ents << 32
+// where the caller's keeps the count)
+__device__ __forceinline__ uint64_t entry_count(const MsgRec& m, uint8_t recs) {
+  return recs == kRecsFrames ? m.resv >> 32 : m.resv & 0xffffffffull;
+}
+// props (raftq_step_set_props): a MsgProp is a known kind when it says how many entries it carries and carries at least one
+// (CHOICE: upstream's stepLeader panics on an empty one).  raftq_step_submit_wire's records carry no RAFTQ_MSGF_*: it stays
+// malformed there.
+__device__ __forceinline__ RecClass classify(const MsgRec& m, uint64_t n_groups, uint32_t n_peers, bool msg_flags, uint8_t recs, bool props) {
   const uint8_t fl = msg_flags ? m.pad[1] : (uint8_t)0;
   if (fl & kMsgfSkip) return kSkip;
   if (m.group >= n_groups) return kBad;
   if (fl & kMsgfHold) return kTake;
   const uint8_t t = m.type;
+  if (t == kMsgProp)
+    return props && recs != kRecsWire && (fl & kMsgfEntries) != 0 && entry_count(m, recs) != 0 && m.from < n_peers ? kTake : kBad;
   const bool local = t == kMsgHup || t == kMsgBeat;
   const bool known = local || t == kMsgApp || t == kMsgAppResp || t == kMsgVote || t == kMsgVoteResp ||
                      t == kMsgHeartbeat || t == kMsgHeartbeatResp;
@@ -224,11 +235,11 @@ static __global__ __launch_bounds__(kBlock) void step_keys_kernel(const MsgRec* 
                                                                   uint32_t* __restrict__ order, uint64_t n,
                                                                   uint64_t n_groups, uint32_t n_peers,
                                                                   unsigned int* bad, bool msg_flags, uint8_t recs,
-                                                                  void* __restrict__ out, uint8_t compact) {
+                                                                  void* __restrict__ out, uint8_t compact, bool props) {
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   bool is_bad = false;
   if (i < n) {
-    const RecClass c = classify(msgs[i], n_groups, n_peers, msg_flags, recs);
+    const RecClass c = classify(msgs[i], n_groups, n_peers, msg_flags, recs, props);
     is_bad = c == kBad;
     // a skipped record sorts behind every group (the key range has room for n_groups itself) and is answered here
     keys[i] = c == kTake ? msgs[i].group : c == kSkip ? n_groups : 0;  // (bad: keep the sort's key range valid)
@@ -454,8 +465,7 @@ struct NodeT {
   __device__ void handle_append(const MsgRec& m, StepOutRec& o) {
     o.type = kOutAppend;
     if (a.msg_flags && (m.pad[1] & kMsgfEntries) && m.index == last_index && m.log_term == last_term) {
-      // (the decoder's record keeps ent_first | n_ents << 32 where the caller's keeps the count)
-      const uint64_t k = a.recs == kRecsFrames ? m.resv >> 32 : m.resv & 0xffffffffull;
+      const uint64_t k = entry_count(m, a.recs);
       if (k) {
         last_index = m.index + k;
         last_term = m.reject_hint;
@@ -483,6 +493,9 @@ struct NodeT {
         if (o.index < last_index) at_tail = false;  // `if pr.Match < lastIndex { sendAppend }`
       }
     }
+    // a forwarded proposal the leader took: until the host's bcastAppend no follower is at the new tail (a device-built commit
+    // broadcast behind it would carry an index the followers do not have).  It and RAFTQ_OUT_FORWARD are the host's (default below).
+    if (o.type == kOutProposed) at_tail = false;
     if (!host_owns) {
       switch (o.type) {
         case kOutAppended: r.kind = kMsgAppResp; r.index = o.index; break;
@@ -510,7 +523,7 @@ struct NodeT {
               break;
             }
           }
-          host_owns = true;  // MsgApp left to the log's owner, a new leader's broadcast, held / deferred messages
+          host_owns = true;  // MsgApp left to the log's owner, a new leader's broadcast, held / deferred messages, a proposal taken or forwarded
       }
     }
     if (r.kind != 0) o.flags |= kFlagAnswered;
@@ -553,17 +566,33 @@ struct NodeT {
           o.type = kOutBcastHeartbeat;
         } else if (m.type == kMsgVote) {
           o.type = kOutVoteResp; o.reject = 1;
-        } else if (m.type == kMsgAppResp) {
-          o.type = kOutProgress; o.reject = m.reject;
-          if (!m.reject) {
-            const uint64_t idx = m.index > last_index ? last_index : m.index;
-            if (match(m.from) < idx) {
-              set_match(m.from, idx);
+        } else if (m.type == kMsgAppResp || m.type == kMsgProp) {
+          // the two messages that move a Match: an acknowledgement the sender's, a forwarded proposal (stepLeader MsgProp:
+          // appendEntry(m.Entries...) -- every entry stamped r.Term and the next index, whatever it carried -- then
+          // prs[self].maybeUpdate(lastIndex)) the leader's own.  ONE maybeCommit behind both (classify() let a MsgProp through only
+          // under raftq_step_set_props, with a count of at least one; the caller keeps last_index + n below 2^64).
+          const bool prop = m.type == kMsgProp;
+          uint32_t who = m.from;
+          uint64_t idx = m.index > last_index ? last_index : m.index;
+          bool moved = false;
+          if (prop) {
+            o.type = kOutProposed; o.index = last_index + 1; o.log_term = term;
+            last_index += entry_count(m, a.recs);
+            last_term = term;
+            who = a.self; idx = last_index;
+            moved = true;
+          } else {
+            o.type = kOutProgress; o.reject = m.reject;
+            if (!m.reject && match(who) < idx) {
               o.flags |= kFlagUpdated;
-              (void)maybe_commit();
+              moved = true;
             }
           }
-          o.index = match(m.from);
+          if (moved) {
+            set_match(who, idx);
+            (void)maybe_commit();
+          }
+          if (!prop) o.index = match(who);
         } else if (m.type == kMsgHeartbeatResp) {
           o.type = kOutProgress;
           o.index = match(m.from);
@@ -603,12 +632,14 @@ struct NodeT {
           const bool up_to_date = m.log_term > last_term || (m.log_term == last_term && m.index >= last_index);
           if ((vote == 0 || vote == m.from + 1) && up_to_date) { elapsed_reset = true; vote = m.from + 1; }
           else o.reject = 1;
+        } else if (m.type == kMsgProp && lead != 0) {
+          o.type = kOutForward;  // stepFollower MsgProp: `m.To = r.lead; r.send(m)` -- the one result addressed to somebody else
         }
       }
     }
     if (a.msg_flags && o.type == kOutAppend && m.type == kMsgApp && (m.pad[1] & kMsgfBarrier)) held = true;
     o.group = g; o.term = term; o.commit = committed; o.last_index = last_index;
-    o.to = m.from; o.vote = vote; o.lead = lead; o.role = role;
+    o.to = o.type == kOutForward ? lead - 1 : m.from; o.vote = vote; o.lead = lead; o.role = role;
     if (term != term0 || vote != vote0 || committed != commit0) o.flags |= kFlagHardState;
     if (committed != commit0) o.flags |= kFlagCommitted;
     if (role0 != kFollower && role == kFollower) o.flags |= kFlagSteppedDown;
@@ -651,7 +682,7 @@ static __global__ __launch_bounds__(kBlock) void step_link_kernel(const MsgRec* 
                                                                   uint64_t n_groups, uint32_t n_peers, bool msg_flags, uint8_t recs,
                                                                   NodeRec* rec, uint32_t* __restrict__ next,
                                                                   unsigned int* bad, unsigned int* stall,
-                                                                  void* __restrict__ out, uint8_t compact, CopyRide ride) {
+                                                                  void* __restrict__ out, uint8_t compact, CopyRide ride, bool props) {
   if (blockIdx.x < ride.blocks) {
     copy_ride(ride);
     return;
@@ -659,7 +690,7 @@ static __global__ __launch_bounds__(kBlock) void step_link_kernel(const MsgRec* 
   const uint64_t i = (uint64_t)(blockIdx.x - ride.blocks) * kBlock + threadIdx.x;
   bool is_bad = false, too_long = false;
   if (i < n) {
-    const RecClass c = classify(msgs[i], n_groups, n_peers, msg_flags, recs);
+    const RecClass c = classify(msgs[i], n_groups, n_peers, msg_flags, recs, props);
     is_bad = c == kBad;
     if (c == kTake) {
       NodeRec* r = rec + msgs[i].group;  // three atomics on one line

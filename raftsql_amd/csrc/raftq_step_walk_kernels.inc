@@ -57,7 +57,7 @@ static __global__ __launch_bounds__(kBlock) void RAFTQ_WALK_KERNEL(step_lists)(N
   const bool stalled = *stall != 0;  // this batch, or one before it that has not been replayed yet, needs the sorted path
   if (stalled || *bad) {             // (*bad: a malformed record somewhere in the batch) -- nothing is applied;
     if (stalled && i == 0) *tail_skipped = 1u;
-    if (i < n && classify(msgs[i], n_groups, a.n_peers, a.msg_flags, a.recs) == kTake) {  // every message empties its group's list words (idempotent)
+    if (i < n && classify(msgs[i], n_groups, a.n_peers, a.msg_flags, a.recs, a.props) == kTake) {  // every message empties its group's list words (idempotent)
       NodeRec* r = a.rec + msgs[i].group;
       r->lst_head = kNil;
       r->lst_cnt = 0;

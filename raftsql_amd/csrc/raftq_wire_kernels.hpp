@@ -1045,11 +1045,11 @@ __device__ __forceinline__ void tile_packed_out(const WireMsg& m, bool live, boo
 // raftq_step_frames (a node's inbound half-turn as one submission): `ff.on` -- the decoder also makes the checks a node makes on
 // what it received and says in the record's flag byte what Step is to do with it (RAFTQ_MSGF_*, raftq_step.h): a frame that did
 // not parse, is of a kind a peer never sends, names no group / sender of this cluster or is addressed to another slot is
-// RAFTQ_MSGF_SKIP; a MsgProp (the log owner's) RAFTQ_MSGF_HOLD; a MsgApp a barrier that says what it carries (reject_hint, which
+// RAFTQ_MSGF_SKIP; a MsgProp (the log owner's) RAFTQ_MSGF_HOLD -- or, under raftq_step_set_props, RAFTQ_MSGF_ENTRIES; a MsgApp a barrier that says what it carries (reject_hint, which
 // MsgApp does not use = the last entry's term).  msgs_d: the same records once more, in HBM, where Step's kernels -- enqueued
 // right behind this one -- read them.
 struct FrameFilter {
-  uint32_t on, n_peers, self, tail_appends;
+  uint32_t on, n_peers, self, tail_appends;  // on: bit 0 = the filter runs, bit 1 = raftq_step_set_props (a MsgProp is Step's, not held)
   uint64_t n_groups;
   unsigned long long* zero2;  // two words this kernel leaves zero for the kernels behind it (Step's {touched groups, bad | skipped}), or nullptr
 };
@@ -1130,7 +1130,9 @@ static __global__ __launch_bounds__(TB) void wire_dec_fused_kernel(InFeed in, ui
         if (malformed || !kind_ok || m.group >= ff.n_groups || m.from >= ff.n_peers || m.to != ff.self) {
           m.flags |= kFrameSkip;
         } else if (t == 2) {
-          m.flags |= kFrameHold;
+          // raftq_step_set_props (ff.on bit 1): Step takes a forwarded proposal by its entry count; an empty one is a frame of a
+          // kind a peer never sends (upstream's stepLeader panics on it)
+          m.flags |= (ff.on & 2u) == 0 ? kFrameHold : m.n_ents != 0 ? kFrameEntries : kFrameSkip;
         } else if (t == 3) {
           m.flags |= kFrameBarrier | (ff.tail_appends ? kFrameEntries : 0);
           m.reject_hint = m.n_ents ? f.get(14) : 0;  // (slot 14: Term of the Entry walked last)

@@ -18,12 +18,14 @@ from .engine import QuorumEngine, _ptr
 
 # raftpb.MessageType values Step accepts
 MSG_HUP, MSG_BEAT, MSG_APP, MSG_APP_RESP, MSG_VOTE, MSG_VOTE_RESP, MSG_HEARTBEAT, MSG_HEARTBEAT_RESP = 0, 1, 3, 4, 5, 6, 8, 9
+MSG_PROP = 2  # a follower's forwarded proposal: stepped only under set_step_props (MSGF_ENTRIES + its count in _resv)
 MSG_TYPES = (MSG_HUP, MSG_BEAT, MSG_APP, MSG_APP_RESP, MSG_VOTE, MSG_VOTE_RESP, MSG_HEARTBEAT, MSG_HEARTBEAT_RESP)
 
 OUT_NONE, OUT_VOTE_RESP, OUT_HEARTBEAT_RESP, OUT_CAMPAIGN, OUT_BECAME_LEADER, OUT_PROGRESS, OUT_BCAST_HEARTBEAT, OUT_APPEND = range(8)
 OUT_APPENDED = 8  # MsgApp with MSGF_ENTRIES that appended at the tail: Step did maybeAppend's bookkeeping itself
 OUT_DEFERRED = 9  # not applied: an earlier MsgApp of the group with MSGF_BARRIER was left to the caller (OUT_APPEND)
 OUT_SKIPPED, OUT_HELD = 10, 11  # MSGF_SKIP: nobody's, nothing looked at; MSGF_HOLD: the caller's (MsgProp), the rest of its group deferred
+OUT_PROPOSED, OUT_FORWARD = 12, 13  # set_step_props: the leader took a MsgProp (index = first new index); a follower's goes on to lead - 1
 MSGF_SKIP, MSGF_HOLD = 0x10, 0x20
 MSGF_BARRIER = 0x40  # on a MsgApp: if it is answered OUT_APPEND, the group's later messages of the batch are deferred
 MSGF_ENTRIES = 0x80  # msgs["_pad"][:, 1]: _resv = number of entries, reject_hint = the last one's term (raftq_step.h)
@@ -80,8 +82,10 @@ def expand_compact(msgs: np.ndarray, recs: np.ndarray) -> np.ndarray:
     for k in ("term", "index", "commit", "vote", "lead", "type", "reject", "flags", "role"):
         o[k] = recs[k]
     tip = (recs["type"] == OUT_CAMPAIGN) | (recs["type"] == OUT_BECAME_LEADER)  # index IS the last index there
-    o["log_term"] = np.where(tip, recs["aux"], 0)
+    o["log_term"] = np.where(tip, recs["aux"], np.where(recs["type"] == OUT_PROPOSED, recs["term"], 0))
     o["last_index"] = np.where(tip, recs["index"], recs["aux"])
+    fwd = recs["type"] == OUT_FORWARD  # the one result whose addressee is not the sender: the leader's slot
+    o["to"] = np.where(fwd, recs["lead"].astype(np.int64) - 1, o["to"])
     return o
 
 
@@ -89,7 +93,9 @@ def expand_short(msgs: np.ndarray, recs: np.ndarray, last_index: np.ndarray, com
     """raftq_step_out_s_t[] (32 bytes) + the batch it answers + every group's lastIndex / committed BEFORE the batch ->
     raftq_step_out_t[], exactly (include/raftq_step.h): what the 32-byte record leaves out is tracked per group across the
     batch -- lastIndex only moves with a result whose `index` IS the last index, a campaign moves no commit index and carries
-    its log_term in that slot, a new leader's log_term is its term.  (A loop over the records: tests and tools, not a hot path.)"""
+    its log_term in that slot, a new leader's log_term is its term; behind an OUT_PROPOSED the tail is index + n - 1 (n = the
+    count in the reader's own record, msgs["_resv"]'s low half) and its log_term is its term; an OUT_FORWARD goes to lead - 1.
+    (A loop over the records: tests and tools, not a hot path.)"""
     o = np.zeros(len(recs), dtype=OUT_DT)
     li, co = {}, {}
     tips = (OUT_CAMPAIGN, OUT_BECAME_LEADER, OUT_APPENDED)
@@ -104,10 +110,12 @@ def expand_short(msgs: np.ndarray, recs: np.ndarray, last_index: np.ndarray, com
             li[g], co[g] = int(last_index[g]), int(committed[g])
         if t in tips:
             li[g] = int(r["index"])
+        elif t == OUT_PROPOSED:
+            li[g] = int(r["index"]) + (int(msgs["_resv"][i]) & 0xFFFFFFFF) - 1
         if t != OUT_CAMPAIGN:
             co[g] = int(r["commit"])
-        o[i] = (g, r["term"], r["index"], r["commit"] if t == OUT_CAMPAIGN else (r["term"] if t == OUT_BECAME_LEADER else 0), co[g], li[g],
-                msgs["from"][i], r["vote"], r["lead"], t, r["reject"], r["flags"], r["role"])
+        o[i] = (g, r["term"], r["index"], r["commit"] if t == OUT_CAMPAIGN else (r["term"] if t in (OUT_BECAME_LEADER, OUT_PROPOSED) else 0), co[g], li[g],
+                int(r["lead"]) - 1 if t == OUT_FORWARD else msgs["from"][i], r["vote"], r["lead"], t, r["reject"], r["flags"], r["role"])
     return o
 
 
@@ -141,6 +149,12 @@ class NodeEngine(QuorumEngine):
         """raftq_step_set_voters: with voter masks loaded (load_voters / apply_voter_deltas) the Step-family calls run over each
         group's own voters instead of being refused; a property of the handle (no batch may be in flight)"""
         self._chk(self._lib.raftq_step_set_voters(self._h, int(on)))
+
+    def set_step_props(self, on=True) -> None:
+        """raftq_step_set_props: Step takes a forwarded proposal -- a record of type MSG_PROP with MSGF_ENTRIES and its number of
+        entries in _resv -- and the frames calls flag a MsgProp frame MSGF_ENTRIES instead of MSGF_HOLD; a property of the handle
+        (no batch may be in flight)"""
+        self._chk(self._lib.raftq_step_set_props(self._h, int(on)))
 
     def set_tick_voters(self, on=True) -> None:
         """raftq_tick_set_voters: with voter masks loaded the Tick applies promotable() (a group in which this node does not vote
