@@ -365,6 +365,21 @@ func (e *Engine) SetRespondLead(on bool) error {
 	return e.err(C.raftq_respond_set_lead(e.h, v))
 }
 
+// SetRespondProps opts the engine in to (or out of) StepFramesRespond's answer to a forwarded proposal (raftq_respond_set_props;
+// an effect only after SetStepProps(true)): an OutProposed result inside its group's device-answered prefix whose group is at the
+// tail is then flagged OutfAnswered and the leader's MsgApps -- one per peer, Index / LogTerm the tail before the proposal, the
+// frame's own entries stamped with the term and the next indices, their payloads gathered from the inbound stream on the device --
+// are in out; the caller still stores the entries in its own log and WAL, moves every Next to the new tail + 1 and sends nothing.
+// ents must then be non-nil and len(out) at least n*(N-1)*FRAME + (N-1)*(len(stream) + len(ents)*RespondEntMax), FRAME =
+// RespondLeadFrameMax after SetRespondLead(true), RespondFrameMax otherwise.  Off by default; no batch may be in flight.
+func (e *Engine) SetRespondProps(on bool) error {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	return e.err(C.raftq_respond_set_props(e.h, v))
+}
+
 // StepFramesRespond is StepFrames plus the messages its results call for, built and marshalled on the device
 // (raftq_step_frames_respond; raft.go:268-270 -> :227-230): MsgAppResp / MsgVoteResp / MsgHeartbeatResp to the senders and the
 // commit broadcast of a group whose at-tail bit is set (atTail: one bit per group, nil = none).  out receives rafthttp frames,
@@ -512,12 +527,13 @@ func (e *Engine) TickElectFrames(flags uint, hupCap, beatCap uint64, camp []Step
 	return t, uint64(c.n_msgs), uint64(c.bytes), nil
 }
 
-// OutfAnswered / RespondFrameMax / RespondLeadFrameMax: RAFTQ_OUTF_ANSWERED, RAFTQ_RESPOND_FRAME_MAX,
-// RAFTQ_RESPOND_LEAD_FRAME_MAX (include/raftq_wire.h)
+// OutfAnswered / RespondFrameMax / RespondLeadFrameMax / RespondEntMax: RAFTQ_OUTF_ANSWERED, RAFTQ_RESPOND_FRAME_MAX,
+// RAFTQ_RESPOND_LEAD_FRAME_MAX, RAFTQ_RESPOND_ENT_MAX (include/raftq_wire.h)
 const (
 	OutfAnswered        = 0x10
 	RespondFrameMax     = 83
 	RespondLeadFrameMax = 109
+	RespondEntMax       = 40
 )
 
 // WalSaveBegin / WalSaveEnd: rc.wal.Save (raft.go:228) in two halves, so that a turn's WAL encode and its outbound marshal

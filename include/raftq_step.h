@@ -146,8 +146,9 @@ int raftq_step_set_voters(raftq_t* h, int on);
  * frame with entries RAFTQ_MSGF_ENTRIES (its count is the decoder's n_ents) and one without entries RAFTQ_MSGF_SKIP, as a frame
  * of a kind a peer never sends; in the packed form a MsgProp with entries is a wide record, as every frame with entries is.
  * raftq_step_frames_respond leaves both results to the host (no RAFTQ_OUTF_ANSWERED) and, behind a RAFTQ_OUT_PROPOSED, builds no
- * commit broadcast for the group: its at-tail bit is cleared, no follower has the new entries yet.  raftq_node does not turn the
- * switch on. */
+ * commit broadcast for the group: its at-tail bit is cleared, no follower has the new entries yet -- unless
+ * raftq_respond_set_props (raftq_wire.h) opted the handle in: then a RAFTQ_OUT_PROPOSED of a group at the tail is answered with the
+ * leader's MsgApps, built on the device, and the bit stays.  raftq_node does not turn the switch on. */
 int raftq_step_set_props(raftq_t* h, int on);
 
 /* raftq_msg_t._pad[1] once the handle opted in.  RAFTQ_MSGF_ENTRIES on a MsgApp: the caller says what the message carries -- the low 32 bits of

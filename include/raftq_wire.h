@@ -259,7 +259,8 @@ int raftq_step_frames_packed(raftq_t* h, const void* stream, uint64_t nbytes, co
  *                               lastIndex / lastTerm / Commit as they stand AT THAT MESSAGE
  * Everything else stays the caller's and is not flagged: RAFTQ_OUT_APPEND, RAFTQ_OUT_BECAME_LEADER (unless raftq_respond_set_lead,
  * below, opted the handle in), resends and reject backoff, HELD / DEFERRED / SKIPPED / NONE, and under raftq_step_set_props RAFTQ_OUT_PROPOSED
- * (which also clears the group's at_tail bit: no follower has the new entries before the host's bcastAppend) / RAFTQ_OUT_FORWARD.  A result the caller may have to answer itself (any of those that sends, a
+ * (which also clears the group's at_tail bit: no follower has the new entries before the host's bcastAppend -- unless
+ * raftq_respond_set_props, below, opted the handle in) / RAFTQ_OUT_FORWARD.  A result the caller may have to answer itself (any of those that sends, a
  * MsgAppResp while the group's bit is clear) ends its group's device-answered prefix: the group's later results of the batch
  * are not answered either, so per (peer, group) the frames keep the order the host's own answers would have.
  * at_tail ([ceil(G / 64)] words, bit g = group g; NULL = all clear): the caller's word that it leads g and every follower's
@@ -303,7 +304,36 @@ int raftq_step_frames_packed(raftq_t* h, const void* stream, uint64_t nbytes, co
  * is flagged and builds zero frames.  The entry headers are written into the encoder's input in HBM, one slot per result; they never
  * exist in host memory (a stalled batch's replay writes them again).  cap must then be at least n * (N - 1) *
  * RAFTQ_RESPOND_LEAD_FRAME_MAX: RAFTQ_RESPOND_FRAME_MAX plus the entries field of one empty entry at its largest -- field tag and
- * length (2), the tags of type, term and index (3), a one-byte type, term and index of ten bytes each. */
+ * length (2), the tags of type, term and index (3), a one-byte type, term and index of ten bytes each.
+ *
+ * A forwarded proposal's MsgApps (raftq_respond_set_props(h, 1), below; it has an effect only where a RAFTQ_OUT_PROPOSED can arise,
+ * that is under raftq_step_set_props): a RAFTQ_OUT_PROPOSED inside its group's device-answered prefix is answered on the device
+ * when the group's at_tail bit is set at that message -- from the caller's bitmap, or from a device-answered becomeLeader earlier in
+ * the batch.  The answer is one frame for every slot p != self:
+ *   MsgApp{Term, Index: lastIndex BEFORE the proposal, LogTerm: lastTerm BEFORE the proposal, Commit: committed AFTER the message,
+ *          Entries: the frame's n entries, entry k = {Type and Data as received, Term: Term, Index: old lastIndex + 1 + k}}
+ * -- byte for byte what raftq_wire_encode makes of the records bcastAppend builds on the host with every Next at the old tail + 1,
+ * the entries' headers the decoder's with term / index overwritten, the pool the inbound stream; an entry with data_len == 0 has no
+ * Data field.  Over members the frames go to the slots of voters[g] only.  The result carries RAFTQ_OUTF_ANSWERED: the caller still
+ * stores the entries in its own log and WAL, moves every Next to the new tail + 1 and sends nothing.  The at_tail bit STAYS set (the
+ * optimistic state bcastAppend leaves, the assumption raftq_propose_frames states) and the prefix does not end: a second proposal of
+ * the group later in the batch is answered against the new tail, a committing ack behind it gets the usual empty MsgApps with
+ * Index = the new tail, behind the entry frames in every peer's slice.  A proposal that commits on its own append (a one-voter group
+ * over members) carries the new commit and is answered like any other; a group with no member but self is flagged and builds zero
+ * frames.  A RAFTQ_OUT_PROPOSED with the bit clear is the host's, as every proposal is without the switch: it ends the prefix and the
+ * bit stays clear; so is one whose entry headers the decoder could not hand back (its range ends beyond ents_cap: the host has not got
+ * them either).  RAFTQ_OUT_FORWARD stays the host's in every case.  Stalls keep their rules (the replay stamps the headers again).
+ * The stamped headers and the MsgApp records are written into the encoder's input in HBM and never exist in host memory; the
+ * payload bytes are gathered from the decoder's copy of the inbound stream in HBM and do not cross the link inbound a second time.
+ * The call then requires, before anything is enqueued (RAFTQ_EINVAL, nothing applied): ents != NULL (the device stamps the
+ * decoder's headers) and
+ *   cap >= n * (N - 1) * FRAME + (N - 1) * (nbytes + ents_cap * RAFTQ_RESPOND_ENT_MAX)
+ * with FRAME = RAFTQ_RESPOND_LEAD_FRAME_MAX under raftq_respond_set_lead and RAFTQ_RESPOND_FRAME_MAX otherwise (the bound must
+ * stay within 2^31 bytes).  Every payload lies inside the stream, so the payloads of one peer's slice sum to at most nbytes;
+ * RAFTQ_RESPOND_ENT_MAX is the most one entry adds beyond its payload, from the marshal's entry_size(): the entries field's tag and
+ * length (1 + 5: the length of an entry whose data_len fits 32 bits takes five bytes at most), the tags of type / term / index /
+ * data (4), a five-byte type (a 32-bit varint), term and index of ten bytes each, a five-byte data length: 6 + 4 + 5 + 20 + 5 = 40. */
+#define RAFTQ_RESPOND_ENT_MAX 40u
 #define RAFTQ_OUTF_ANSWERED 0x10u /* result flag: the messages this result calls for are in `out` (built on the device) */
 #define RAFTQ_RESPOND_FRAME_MAX 83u
 #define RAFTQ_RESPOND_LEAD_FRAME_MAX 109u /* = RAFTQ_RESPOND_FRAME_MAX + 26 */
@@ -395,6 +425,17 @@ int raftq_bcast_set_voters(raftq_t* h, int on);
  * raftq_step_frames_respond reads it: raftq_step_frames, raftq_tick_elect_frames (whose one-voter win has nobody to send to) and
  * raftq_node's turns are what they were. */
 int raftq_respond_set_lead(raftq_t* h, int on);
+
+/* raftq_step_frames_respond's sixth kind: a forwarded proposal's MsgApps ("A forwarded proposal's MsgApps" in that call's
+ * paragraph).  0, the default: RAFTQ_OUT_PROPOSED stays the caller's, clears its group's at_tail bit and ends its prefix -- the call
+ * launches the kernels it launches without the switch and writes the bytes and flags it writes without it, under the same cap rule.
+ * 1: a proposal of a group at the tail is answered on the device; the call needs ents and the larger cap of its paragraph (RAFTQ_EINVAL
+ * before anything is enqueued otherwise, nothing applied).  Anything but 0 or 1 is RAFTQ_EINVAL; the handle must be idle
+ * (RAFTQ_ESTATE with a Step batch in flight); a NULL handle returns an error without touching a device.  A property of the handle,
+ * like the other switches: raftq_clone_state does not copy it.  Only raftq_step_frames_respond reads it, and it has an effect only
+ * with raftq_step_set_props on (no RAFTQ_OUT_PROPOSED arises otherwise).  Independent of raftq_respond_set_lead and
+ * raftq_bcast_set_voters: all eight combinations work.  raftq_node does not turn it on. */
+int raftq_respond_set_props(raftq_t* h, int on);
 
 /* A node's heartbeat round (raft.go:223-224 -> :230: rc.node.Tick() -> tickHeartbeat -> Step(MsgBeat) -> bcastHeartbeat ->
  * rc.transport.Send) as ONE submission with one wait: the Tick, its lists, and the heartbeats the Tick calls for, built and

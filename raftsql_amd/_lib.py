@@ -198,6 +198,7 @@ _WIRE_SIGS = [
                                           C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(WireCounts)]),
     ("raftq_bcast_set_voters", C.c_int, [_H, C.c_int]),
     ("raftq_respond_set_lead", C.c_int, [_H, C.c_int]),
+    ("raftq_respond_set_props", C.c_int, [_H, C.c_int]),
     ("raftq_step_stage_wire", C.c_int, [_H, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("raftq_step_wire_msgs", C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     ("raftq_step_wire_entries", C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),

@@ -1160,6 +1160,15 @@ int raftq_respond_set_lead(raftq_t* h, int on) {
   return RAFTQ_OK;
 }
 
+int raftq_respond_set_props(raftq_t* h, int on) {
+  if (int rc = use_device_idle(h, "raftq_respond_set_props")) return rc;
+  if (on != 0 && on != 1)
+    return fail(h, RAFTQ_EINVAL, "raftq_respond_set_props: 0 (RAFTQ_OUT_PROPOSED stays the caller's) or 1 (raftq_step_frames_respond builds the "
+                                 "proposal's MsgApps for a group at the tail)");
+  h->resp_props = on == 1;
+  return RAFTQ_OK;
+}
+
 int raftq_tick(raftq_t* h, raftq_tick_counts_t* counts) {
   if (int rc = use_device_idle(h, "raftq_tick")) return rc;
   if (int rc = tick_voters_ready(h, "raftq_tick")) return rc;

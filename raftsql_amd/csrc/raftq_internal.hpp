@@ -129,6 +129,8 @@ struct raftq {
                                    // raftq_propose_frames' bcastAppend go to each group's own members (the same kind of property)
   bool resp_lead = false;          // raftq_respond_set_lead: raftq_step_frames_respond answers RAFTQ_OUT_BECAME_LEADER too (the *_lead_kernel
                                    // walks, resp_scatter_lead[_voters]_kernel); the same kind of property
+  bool resp_props = false;         // raftq_respond_set_props: raftq_step_frames_respond answers a RAFTQ_OUT_PROPOSED at the tail too (the same
+                                   // walks and scatter kernels, NodeArrays::ans_props); the same kind of property
   int step_walk_mode = 1;          // 1 = lists (default), 0 = always the sorted walk (RAFTQ_STEP_WALK=sort)
   uint32_t step_stalls_in_a_row = 0, step_sorted_left = 0;  // back-off from the list walk under hot-group traffic
   uint64_t step_replays = 0;       // batches that went through the sorted path after a stall
@@ -210,6 +212,7 @@ struct raftq {
   bool resp_on = false;
   uint32_t resp_stamp = 0;
   const uint64_t* resp_at_tail_d = nullptr;
+  uint32_t resp_ent_base = 0;  // raftq_respond_set_props: entry headers the call's decoder can hand back (a proposal whose entries lie beyond is the host's)
   // raftq_wal_encode_begin .. _end: enqueued, its totals in wire_pin[kPinWalPending ..]; `done`: a later wait has covered it and what _end
   // will report is kept here
   bool wal_pending = false, wal_pending_done = false;
@@ -322,9 +325,17 @@ struct RespPlan {
   uint64_t* v_resp_off = nullptr;
   uint64_t* peer_off = nullptr;        // the caller's (host) array, N + 1 words
   bool lead = false;                   // raftq_respond_set_lead: the encoder's input has an entry array, one slot per result
+  // raftq_respond_set_props: ... and in front of those slots one per entry header the decoder can hand back (ent_base); the
+  // encoder's pool is the decoder's copy of the inbound stream, which the marshal's scratch is laid out behind (keep)
+  bool props = false;
+  uint64_t ent_base = 0, nbytes = 0;
+  const void* v_ents = nullptr;        // the caller's entry headers as the device addresses them
+  const void* v_stream = nullptr;      // RAFTQ_RESPOND_PROPS_POOL=feed only: the caller's stream, which the encoder's readers bring in as the pool
+  size_t keep = 0, pool_off = 0;       // bytes of the codecs' scratch the marshal leaves alone; where the stream's copy lies in them
 };
 int respond_prepare(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off, const void* msgs, const void* ents,
-                    const uint64_t* at_tail, void* out, uint64_t cap, uint64_t* resp_off, uint64_t* peer_off, uint64_t n, RespPlan* p);
+                    uint64_t ents_cap, const uint64_t* at_tail, void* out, uint64_t cap, uint64_t* resp_off, uint64_t* peer_off, uint64_t n,
+                    RespPlan* p);
 int respond_enqueue(raftq_t* h, const RespPlan& p);
 int respond_finish(raftq_t* h, const RespPlan& p, ::raftq_wire_counts* resp_counts);
 // raftq_tick_collect_lists in three steps (raftq_capi.hip), for raftq_tick_frames (raftq_wire.hip), which puts its kernels between

@@ -144,13 +144,25 @@ static __global__ __launch_bounds__(kBlock) void resp_scan_kernel(RespLayout L, 
 }
 
 // (3) the records, peer-major, into the encoder's input; then the fillers up to n_max
-// LEAD: the layout with becomeLeader's broadcast in it (raftq_respond_set_lead); (1) and (2) are shared -- a win is kind ==
-// kMsgApp, which they count as a broadcast already.  A record with pad == 1 carries the empty entry of the new term.  Its header
-// goes into the encoder's entry array in HBM at slot i, the result's own position (ent_first = i, n_ents = 1: no scan), and every
-// frame of the broadcast names that one slot.  Slots of results that carry no entry are never read.
+// LEAD: the layout with the broadcasts that carry entries in it (raftq_respond_set_lead, raftq_respond_set_props); (1) and (2) are
+// shared -- such a result is kind == kMsgApp, which they count as a broadcast already.  The encoder's entry array in HBM has
+// P.ent_base + n slots:
+//   pad == 1, becomeLeader's: the empty entry of the new term goes to slot ent_base + i, behind every slot a proposal can name
+//       (ent_first = ent_base + i, n_ents = 1: no scan), and every frame of the broadcast names that one slot;
+//   pad == 2, a forwarded proposal's: the decoder has given the frame's entries the range ent_first .. ent_first + n_ents of an array
+//       of at most ent_base headers (its device-side record of position i says which; the headers lie in the caller's page-locked
+//       ents[]).  The stamped copy -- Term and Index overwritten, Type / data_off / data_len kept: the pool is the inbound stream --
+//       goes to the SAME positions: no scan either.  The wave stamps: for every proposal of its 64 results in turn, lane k takes
+//       header k, k + 64, ... (a 300-entry frame is five rounds of the wave, not 300 of one lane).
+// Slots no frame names are never read.
+struct RespProps {
+  const WireMsg* dec;    // [n] the decoder's records in HBM (ent_first / n_ents), or nullptr: no proposal is answered
+  const WireEnt* heads;  // the decoder's entry headers, as the device addresses the caller's array
+  uint32_t ent_base;     // slots the proposals' entries take in front of the empty entries'
+};
 template <bool MASKED, bool LEAD>
 __device__ __forceinline__ void resp_scatter_body(RespLayout L, WireMsg* __restrict__ enc, uint64_t n_max, const uint16_t* __restrict__ voters,
-                                                  WireEnt* __restrict__ ents) {
+                                                  WireEnt* __restrict__ ents, RespProps P = RespProps{nullptr, nullptr, 0}) {
   __shared__ uint32_t wc[kWaves][kMaxPeers];
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -168,19 +180,28 @@ __device__ __forceinline__ void resp_scatter_body(RespLayout L, WireMsg* __restr
     if (lane == 0) wc[wave][p] = (uint32_t)__popcll(b);
   }
   __syncthreads();
+  uint32_t ent_first = 0, n_ents = 0;
+  bool stamps = false;  // this result's frames carry the message's own entries
   if (MASKED ? to != 0 : valid) {
-    uint32_t ent_first = 0, n_ents = 0;
     if constexpr (LEAD) {
-      if (r.kind == kMsgApp && r.pad == 1) {  // (i < L.n: the array has one slot per result)
+      if (r.kind == kMsgApp && r.pad == 1) {  // (i < L.n: the array has one slot per result behind ent_base)
         WireEnt e;
         e.term = r.term;
         e.index = r.index + 1;
         e.data_off = 0;
         e.data_len = 0;
         e.type = 0;
-        ents[i] = e;
-        ent_first = (uint32_t)i;
+        ents[(uint64_t)P.ent_base + i] = e;
+        ent_first = P.ent_base + (uint32_t)i;
         n_ents = 1;
+      } else if (r.kind == kMsgApp && r.pad == 2 && P.dec != nullptr) {
+        const WireMsg d = P.dec[i];
+        // (a range the decoder could not store -- more entries than ents_cap: the call fails -- names no slot)
+        if ((uint64_t)d.ent_first + d.n_ents <= P.ent_base) {
+          ent_first = d.ent_first;
+          n_ents = d.n_ents;
+          stamps = n_ents != 0;
+        }
       }
     }
     WireMsg m = msg_head(r.group, r.term, r.log_term, r.index, r.commit, L.self, r.kind, r.reject, ent_first, n_ents);
@@ -191,6 +212,22 @@ __device__ __forceinline__ void resp_scatter_body(RespLayout L, WireMsg* __restr
       for (uint32_t w = 0; w < wave; ++w) at += wc[w][p];
       m.to = (uint8_t)p;
       enc[at] = m;
+    }
+  }
+  if constexpr (LEAD) {
+    // appendEntry's stamps, by the wave (every lane reaches this: the ballot and the broadcasts are wave-wide)
+    uint64_t todo = __ballot(stamps);
+    while (todo != 0) {
+      const int src = __ffsll((unsigned long long)todo) - 1;
+      todo &= todo - 1;
+      const uint32_t first = __builtin_amdgcn_readlane(ent_first, src), cnt = __builtin_amdgcn_readlane(n_ents, src);
+      const uint64_t term = wave_bcast_u64(r.term, src), index = wave_bcast_u64(r.index, src);
+      for (uint32_t k = lane; k < cnt; k += 64) {
+        WireEnt e = P.heads[first + k];
+        e.term = term;
+        e.index = index + 1 + k;
+        ents[first + k] = e;
+      }
     }
   }
   fill_refused(enc, L.peer_off[L.n_peers], n_max);
@@ -204,12 +241,13 @@ static __global__ __launch_bounds__(kBlock) void resp_scatter_voters_kernel(Resp
 }
 // (the unmasked form keeps the parameter list it had when it served both forms: it reads no mask)
 static __global__ __launch_bounds__(kBlock) void resp_scatter_lead_kernel(RespLayout L, WireMsg* __restrict__ enc, uint64_t n_max, const uint16_t*,
-                                                                          WireEnt* __restrict__ ents) {
-  resp_scatter_body<false, true>(L, enc, n_max, nullptr, ents);
+                                                                          WireEnt* __restrict__ ents, RespProps P) {
+  resp_scatter_body<false, true>(L, enc, n_max, nullptr, ents, P);
 }
 static __global__ __launch_bounds__(kBlock) void resp_scatter_lead_voters_kernel(RespLayout L, WireMsg* __restrict__ enc, uint64_t n_max,
-                                                                                 const uint16_t* __restrict__ voters, WireEnt* __restrict__ ents) {
-  resp_scatter_body<true, true>(L, enc, n_max, voters, ents);
+                                                                                 const uint16_t* __restrict__ voters, WireEnt* __restrict__ ents,
+                                                                                 RespProps P) {
+  resp_scatter_body<true, true>(L, enc, n_max, voters, ents, P);
 }
 
 }  // namespace raftqk

@@ -78,6 +78,9 @@ NodeArrays node_arrays(raftq_t* h, uint8_t recs = raftqk::kRecsCaller) {
     a.resp = (raftqk::RespRec*)h->resp_dev.d;
     a.at_tail = h->resp_at_tail_d;
     a.resp_stamp = h->resp_stamp;
+    a.ans_lead = h->resp_lead;
+    a.ans_props = h->resp_props;
+    a.resp_ent_base = h->resp_ent_base;
   }
   return a;
 }
@@ -142,7 +145,9 @@ void forget_results(raftq_t* h) {
 bool masked_step(const raftq_t* h) { return h->voters != nullptr && (h->step_voters || (h->resp_on && h->bcast_voters)); }
 // raftq_respond_set_lead: the walks of a raftq_step_frames_respond call (the first pass and a stalled batch's replay) are the
 // *_lead_kernel forms, whose respond() answers RAFTQ_OUT_BECAME_LEADER too; every other caller of the walks launches what it always did
-bool lead_step(const raftq_t* h) { return h->resp_on && h->resp_lead; }
+// raftq_respond_set_props: the same forms -- "the walks that answer broadcasts with entries" -- launched when either switch is on
+// (NodeArrays::ans_lead / ans_props say which of the two they answer)
+bool lead_step(const raftq_t* h) { return h->resp_on && (h->resp_lead || h->resp_props); }
 
 // One walk, launched in the form the handle's switches ask for.  raftq_step_walk_kernels.inc is expanded once per form, so a walk
 // comes as four entry points over one parameter list: plain, *_voters (masked_step: h->voters is appended), *_lead (lead_step) and
@@ -1021,8 +1026,21 @@ int raftq_step_frames_respond(raftq_t* h, const void* stream, uint64_t nbytes, c
   if (cap < n_max * frame_max)
     return fail(h, RAFTQ_EINVAL, std::string(who) + ": cap is below n * (N - 1) * " + frame_max_name + " = " +
                                      std::to_string(n_max * frame_max) + " bytes -- nothing was applied");
+  // raftq_respond_set_props: every entry of the batch may go out again to every peer -- its payload (all of them lie inside the
+  // stream) and at most RAFTQ_RESPOND_ENT_MAX bytes around it; the device stamps the decoder's headers, so there must be some
+  if (h->resp_props) {
+    if (!ents) return fail(h, RAFTQ_EINVAL, std::string(who) + ": raftq_respond_set_props needs ents (the device stamps the decoder's entry headers) -- nothing was applied");
+    const uint64_t per_peer = nbytes + (ents_cap > ((uint64_t)1 << 31) ? (uint64_t)1 << 40 : ents_cap * RAFTQ_RESPOND_ENT_MAX);
+    const uint64_t bound = n_max * frame_max + (h->N - 1) * per_peer;
+    if (bound > ((uint64_t)1 << 31))
+      return fail(h, RAFTQ_EINVAL, std::string(who) + ": batch too large (n * (N - 1) * " + frame_max_name +
+                                       " + (N - 1) * (nbytes + ents_cap * RAFTQ_RESPOND_ENT_MAX) must stay within 2^31 bytes)");
+    if (cap < bound)
+      return fail(h, RAFTQ_EINVAL, std::string(who) + ": cap is below n * (N - 1) * " + frame_max_name + " + (N - 1) * (nbytes + ents_cap * RAFTQ_RESPOND_ENT_MAX) = " +
+                                       std::to_string(bound) + " bytes -- nothing was applied");
+  }
   raftq_detail::RespPlan rp;
-  if (int rc = raftq_detail::respond_prepare(h, stream, nbytes, frame_off, msgs, ents, at_tail, out, cap, resp_off, peer_off, n, &rp)) return rc;
+  if (int rc = raftq_detail::respond_prepare(h, stream, nbytes, frame_off, msgs, ents, ents_cap, at_tail, out, cap, resp_off, peer_off, n, &rp)) return rc;
   // from here on: raftq_step_frames, with the walks answering (node_arrays), then the layout and the marshal behind them
   h->resp_on = true;
   WireSrc w{stream, nbytes, frame_off, true, msgs, ents, ents ? ents_cap : 0, tail_appends};

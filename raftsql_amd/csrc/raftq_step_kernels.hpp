@@ -88,6 +88,9 @@ struct NodeArrays {
   uint8_t recs;     // whose records the batch holds: kRecsCaller, kRecsWire (raftq_step_submit_wire: the decoder's, strict) or
                     // kRecsFrames (raftq_step_frames: the decoder's, with RAFTQ_MSGF_* set by it)
   bool props = false;  // raftq_step_set_props: a MsgProp that says how many entries it carries is stepped (it is an unknown kind otherwise)
+  // NodeT's LEAD form only (raftq_step_frames_respond): which broadcasts with entries respond() answers -- becomeLeader's
+  // (raftq_respond_set_lead) and a forwarded proposal's (raftq_respond_set_props).  The form is launched when either is set.
+  bool ans_lead = false, ans_props = false;
   uint64_t n_groups;
   uint32_t* self_max = nullptr;  // the handle's self-max word (raftq_kernels.hpp): a store that breaks the fact clears it
   // raftq_step_frames_respond only (nullptr otherwise): the walk writes resp[i] for every message it steps, stamped resp_stamp,
@@ -95,6 +98,7 @@ struct NodeArrays {
   struct RespRec* resp = nullptr;
   const uint64_t* at_tail = nullptr;
   uint32_t resp_stamp = 0;
+  uint32_t resp_ent_base = 0;  // ans_props: entry headers the decoder can hand back -- a proposal whose range ends beyond is the host's
 };
 constexpr uint8_t kRecsCaller = 0, kRecsWire = 1, kRecsFrames = 2;
 
@@ -110,7 +114,9 @@ constexpr uint8_t kFlagAnswered = 0x10;  // RAFTQ_OUTF_ANSWERED: the messages th
 // What result i calls for, as the walk lane that stepped it saw the group (raftq_step_frames_respond; raftq_respond_kernels.hpp
 // lays the frames out).  kind = the raftpb type of the message(s) to send, 0 = none built on the device; kMsgApp is the commit
 // broadcast: one empty MsgApp to every peer but self; with pad = 1 (NodeT's LEAD form only) it is becomeLeader's broadcast and
-// carries the empty entry {Term: term, Index: index + 1}.  Valid only with this call's stamp (stale records read as "none").
+// carries the empty entry {Term: term, Index: index + 1}; with pad = 2 (the same form) it is a forwarded proposal's bcastAppend and
+// carries the message's own entries, stamped {Term: term, Index: index + 1 + k} (the layout finds them through the decoder's
+// record of position i).  Valid only with this call's stamp (stale records read as "none").
 struct RespRec {
   uint64_t group, term, index, log_term, commit;
   uint32_t stamp;
@@ -263,6 +269,10 @@ constexpr uint32_t kNil = 0xffffffffu;
 // LEAD (raftq_respond_set_lead, raftq_step_frames_respond only): respond() answers RAFTQ_OUT_BECAME_LEADER too -- becomeLeader's
 // broadcast, one MsgApp with the empty entry to every peer.  The frame's LogTerm is the lastTerm become_leader() overwrites, so
 // that form keeps it (last_term_was).  Every `if constexpr (LEAD)` is empty in the other forms: they compile to what they were.
+// The LEAD form is "the form that answers broadcasts with entries": under raftq_respond_set_props it also answers a
+// RAFTQ_OUT_PROPOSED at the tail with the leader's bcastAppend -- the frame's Index / LogTerm are the tail appendEntry moved, so
+// the MsgProp arm keeps that lastTerm in last_term_was too.  Which of the two it answers is NodeArrays::ans_lead / ans_props (run
+// time: a third template axis would be four more walks).
 template <bool MASKED, bool LEAD = false>
 struct NodeT {
   const NodeArrays& a;
@@ -283,7 +293,7 @@ struct NodeT {
   uint8_t role0;
   bool vw_known = false, vw_dirty = false, elapsed_reset = false;
   uint32_t vmask = 0;  // MASKED only: voters[g], bit p = slot p votes in this group
-  uint64_t last_term_was = 0;  // LEAD only: lastTerm as it stood before the latest become_leader()
+  uint64_t last_term_was = 0;  // LEAD only: lastTerm as it stood before the latest become_leader() / the latest proposal's appendEntry
 
   __device__ NodeT(const NodeArrays& arr, uint64_t group, const uint16_t* voters = nullptr) : a(arr), g(group) {
     if constexpr (MASKED) vmask = voters[g];
@@ -495,7 +505,15 @@ struct NodeT {
     }
     // a forwarded proposal the leader took: until the host's bcastAppend no follower is at the new tail (a device-built commit
     // broadcast behind it would carry an index the followers do not have).  It and RAFTQ_OUT_FORWARD are the host's (default below).
-    if (o.type == kOutProposed) at_tail = false;
+    // LEAD under raftq_respond_set_props: inside the prefix and at the tail the proposal's bcastAppend is built below, which leaves
+    // the followers (optimistically, as bcastAppend does) at the new tail -- the bit stays.
+    if constexpr (LEAD) {
+      // (the decoder's record: resv = ent_first | n_ents << 32; headers beyond ents_cap were not handed back)
+      const bool prop_here = o.type == kOutProposed && a.ans_props && at_tail && !host_owns && (m.resv & 0xffffffffull) + (m.resv >> 32) <= a.resp_ent_base;
+      if (o.type == kOutProposed && !prop_here) at_tail = false;
+    } else {
+      if (o.type == kOutProposed) at_tail = false;
+    }
     if (!host_owns) {
       switch (o.type) {
         case kOutAppended: r.kind = kMsgAppResp; r.index = o.index; break;
@@ -517,9 +535,16 @@ struct NodeT {
             // becomeLeader's bcastAppend: reset() has put every Next at the empty entry's index, so every peer gets
             // MsgApp{Index: lastIndex - 1, LogTerm: the old lastTerm, Entries: [the empty entry]} (pad = 1: the layout writes the
             // entry header) -- which leaves every follower at the tail, whatever the caller's bitmap said
-            if (o.type == kOutBecameLeader) {
+            if (o.type == kOutBecameLeader && a.ans_lead) {
               r.kind = kMsgApp; r.index = o.index - 1; r.log_term = last_term_was; r.commit = committed; r.pad = 1;
               at_tail = true;
+              break;
+            }
+            // a forwarded proposal's bcastAppend with every Next at the old tail + 1: MsgApp{Index / LogTerm: the tail before
+            // appendEntry (o.index is the first new index), Commit after, Entries: the message's own} (pad = 2: the layout stamps them)
+            // (the bit is still set behind a proposal only where the test above found everything it asks for)
+            if (o.type == kOutProposed && at_tail) {
+              r.kind = kMsgApp; r.index = o.index - 1; r.log_term = last_term_was; r.commit = committed; r.pad = 2;
               break;
             }
           }
@@ -577,6 +602,7 @@ struct NodeT {
           bool moved = false;
           if (prop) {
             o.type = kOutProposed; o.index = last_index + 1; o.log_term = term;
+            if constexpr (LEAD) last_term_was = last_term;
             last_index += entry_count(m, a.recs);
             last_term = term;
             who = a.self; idx = last_index;

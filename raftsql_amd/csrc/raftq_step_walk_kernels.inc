@@ -1,8 +1,9 @@
 // raftq_step_walk_kernels.inc -- the three kernels that run Step's maybeCommit / poll: the sorted walk, the list walk and the log
 // owner's tail reports.  Included FOUR times by raftq_step_kernels.hpp (inside namespace raftqk): over every slot and over each
-// group's own voters, and both once more, without the tail reports, for raftq_respond_set_lead.  Each time it sets
+// group's own voters, and both once more, without the tail reports, for raftq_respond_set_lead / raftq_respond_set_props.  Each time it sets
 //   RAFTQ_WALK_KERNEL(stem)  the kernel's name: stem_kernel over every slot, stem_voters_kernel over each group's own voters,
-//                            stem_lead_kernel / stem_lead_voters_kernel for the forms that answer a won election too
+//                            stem_lead_kernel / stem_lead_voters_kernel for the forms that answer broadcasts with entries too (a won
+//                            election's, a forwarded proposal's: NodeArrays::ans_lead / ans_props)
 //   RAFTQ_WALK_MASKED        NodeT's argument list: MASKED, or "MASKED, true" for the LEAD forms
 //   RAFTQ_WALK_PARAM         the masked form's extra, LAST parameter (", const uint16_t* __restrict__ voters"): NodeArrays is a
 //                            by-value argument of every Step-family kernel and stays as it is

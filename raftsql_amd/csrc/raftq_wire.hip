@@ -147,6 +147,7 @@ struct StreamCall {
   size_t carve[2] = {0, 0};  // further scratch of the call's kernels, n_carves pieces
   int n_carves = 0;
   uint64_t out_bytes = 0;  // what h->wire_out.d has to hold (0: the kernel does not use it)
+  size_t keep = 0;         // bytes at the front of the scratch the call leaves alone: an earlier launch's, which a kernel of this one reads
   // -- the answer --
   InFeed in{};
   TileCtl ctl;
@@ -245,6 +246,7 @@ int stream_reserve(raftq_t* h, StreamCall& sc) {
     h->wire_chunk_unknown = false;
   }
   Carver c;
+  c.off = sc.keep;
   for (int k = 0; k < 3; ++k) sc.off[k] = c.take(sc.seg[k].bytes + sc.seg[k].extra);
   for (int k = 0; k < sc.n_carves; ++k) sc.off[3 + k] = c.take(sc.carve[k]);
   if (int rc = grow(h, h->wire_dev, c.off)) return rc;
@@ -374,6 +376,10 @@ int wire_encode_copying(raftq_t* h, const raftq_wire_msg_t* msgs, uint64_t n, co
 }
 
 // ---- raftq_wire_decode, raftq_wire_decode_packed, raftq_step_frames' decoder ------------------------------------------------
+// where the streaming decoder's request puts the stream's copy in the scratch, and where that copy ends (raftq_respond_set_props
+// lays its marshal out behind it: stream_reserve carves the segments in order)
+size_t decode_stream_off(uint64_t n) { return align256((size_t)(n + 1) * 8 + 16); }
+size_t decode_stream_end(uint64_t n, uint64_t nbytes) { return decode_stream_off(n) + align256((size_t)nbytes + 16); }
 // The streaming decode (raftq_wire_kernels.hpp "the streaming form"), enqueued on the handle's stream and NOT waited for;
 // v_*: the caller's arrays as the device addresses them.  msgs_d / ff: see wire_dec_fused_kernel (raftq_step_frames).
 // form: 0 -- v_msgs receives 64-byte records; RAFTQ_WIRE_FORM_40 / _HEAD -- v_msgs is the narrow array, pk the wide one.
@@ -718,20 +724,28 @@ StreamCall resp_marshal_call(const raftq_detail::RespPlan& p) {
   sc.n_tiles = blocks_for(p.n_max);
   sc.seg[0] = {nullptr, 0, p.n_max * sizeof(WireMsg)};
   // raftq_respond_set_lead: the entry headers too -- one slot per result, written by resp_scatter_lead_kernel
-  if (p.lead) sc.seg[1] = {nullptr, 0, p.n * sizeof(WireEnt)};
+  // raftq_respond_set_props: ... behind one slot per header the decoder handed back; and the whole request lies behind the
+  // decoder's copy of the stream, the encoder's pool (segment 2 has nothing to feed: respond_enqueue points it there)
+  if (p.lead || p.props) sc.seg[1] = {nullptr, 0, (p.ent_base + p.n) * sizeof(WireEnt)};
+  // (RAFTQ_RESPOND_PROPS_POOL=feed, the measured alternative: the encoder's readers bring the pool in from the caller's stream)
+  if (p.props && p.v_stream != nullptr) sc.seg[2] = {p.v_stream, p.nbytes, 0};
+  sc.keep = p.keep;
   sc.out_bytes = p.cap + 16;
   return sc;
 }
 }  // namespace
 
 int raftq_detail::respond_prepare(raftq_t* h, const void* stream, uint64_t nbytes, const uint64_t* frame_off, const void* msgs, const void* ents,
-                                  const uint64_t* at_tail, void* out, uint64_t cap, uint64_t* resp_off, uint64_t* peer_off, uint64_t n, RespPlan* p) {
+                                  uint64_t ents_cap, const uint64_t* at_tail, void* out, uint64_t cap, uint64_t* resp_off, uint64_t* peer_off,
+                                  uint64_t n, RespPlan* p) {
   const char* who = "raftq_step_frames_respond";
   if (n > kMaxItems) return fail(h, RAFTQ_EINVAL, std::string(who) + ": batch too large");
   if (int rc = ensure_pin(h)) return rc;
   // what raftq_step_frames' decoder takes, and what this call adds: all of it checked here, before anything is enqueued
   Views v(nbytes < (1ull << (kLbValueBits - 1)));
-  v.add(stream, nbytes != 0), v.add(frame_off), v.add(msgs), v.opt(ents);
+  void* v_stream = v.add(stream, nbytes != 0);
+  v.add(frame_off), v.add(msgs);
+  void* v_ents = v.opt(ents);
   void *v_tail = v.opt(at_tail), *v_out = v.add(out), *v_roff = v.opt(resp_off);
   v.add(peer_off);
   if (!v.ok)
@@ -742,8 +756,29 @@ int raftq_detail::respond_prepare(raftq_t* h, const void* stream, uint64_t nbyte
   p->n = n;
   p->n_max = n * (h->N - 1);
   p->lead = h->resp_lead;
-  // what the encoder may write: never more than the worst case
-  p->cap = std::min<uint64_t>(cap, p->n_max * (p->lead ? RAFTQ_RESPOND_LEAD_FRAME_MAX : RAFTQ_RESPOND_FRAME_MAX));
+  p->props = h->resp_props;
+  const uint64_t frame_max = p->lead ? RAFTQ_RESPOND_LEAD_FRAME_MAX : RAFTQ_RESPOND_FRAME_MAX;
+  if (p->props) {
+    // (the caller has checked cap against this very bound, and the bound against 2^31)
+    p->cap = std::min<uint64_t>(cap, p->n_max * frame_max + (h->N - 1) * (nbytes + ents_cap * RAFTQ_RESPOND_ENT_MAX));
+    // (an entry costs its frame two bytes at least: more headers than that the decoder cannot find)
+    p->ent_base = std::min<uint64_t>(ents_cap, nbytes / 2 + 1);
+    p->nbytes = nbytes;
+    p->v_ents = v_ents;
+    // The pool: the decoder's copy of the stream, kept alive in front of the marshal's scratch -- no payload byte crosses the link
+    // inbound twice.  RAFTQ_RESPOND_PROPS_POOL=feed (read per call, for the A/B of tools/profile_respond_props.py and one test):
+    // the marshal overlays the decoder's scratch as it always did and its readers pull the stream from the caller's array again.
+    const char* pool_env = std::getenv("RAFTQ_RESPOND_PROPS_POOL");
+    if (pool_env != nullptr && std::strcmp(pool_env, "feed") == 0) {
+      p->v_stream = v_stream;
+    } else {
+      p->pool_off = decode_stream_off(n);
+      p->keep = decode_stream_end(n, nbytes);
+    }
+  } else {
+    // what the encoder may write: never more than the worst case
+    p->cap = std::min<uint64_t>(cap, p->n_max * frame_max);
+  }
   // everything the layout and the marshal will need is allocated NOW, before anything is stepped: a call that has stepped cannot
   // fail for memory (the calls behind the step find the control block, the scratch and the output buffer big enough)
   if (p->n_max != 0) {
@@ -752,6 +787,7 @@ int raftq_detail::respond_prepare(raftq_t* h, const void* stream, uint64_t nbyte
   }
   if (++h->resp_stamp == 0) h->resp_stamp = 1;
   h->resp_at_tail_d = (const uint64_t*)v_tail;
+  h->resp_ent_base = (uint32_t)p->ent_base;
   p->v_out = v_out;
   p->v_resp_off = (uint64_t*)v_roff;
   p->peer_off = peer_off;
@@ -776,12 +812,23 @@ int raftq_detail::respond_enqueue(raftq_t* h, const RespPlan& p) {
     WireEnt* const ents = (WireEnt*)sc.in.seg[1].dst;
     const uint16_t* const voters = (const uint16_t*)h->voters;
     // the two switches, one entry point each way
-    if (p.lead && members) hipLaunchKernelGGL(resp_scatter_lead_voters_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, enc, p.n_max, voters, ents);
-    else if (p.lead) hipLaunchKernelGGL(resp_scatter_lead_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, enc, p.n_max, (const uint16_t*)nullptr, ents);
+    // raftq_respond_set_props: the decoder's records of this batch (its slot's, in HBM), its headers in the caller's array, and its
+    // copy of the stream -- still in the scratch in front of this request -- as the encoder's pool
+    RespProps rp{nullptr, nullptr, (uint32_t)p.ent_base};
+    uint64_t pool_bytes = 0;
+    if (p.props) {
+      rp.dec = (const WireMsg*)h->step_slot[(h->step_submitted - 1) % raftq::kStepSlots].w_msgs_d;
+      rp.heads = (const WireEnt*)p.v_ents;
+      if (p.v_stream == nullptr) sc.in.seg[2].dst = (uint8_t*)h->wire_dev.d + p.pool_off;
+      pool_bytes = p.nbytes;
+    }
+    const bool with_ents = p.lead || p.props;
+    if (with_ents && members) hipLaunchKernelGGL(resp_scatter_lead_voters_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, enc, p.n_max, voters, ents, rp);
+    else if (with_ents) hipLaunchKernelGGL(resp_scatter_lead_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, enc, p.n_max, (const uint16_t*)nullptr, ents, rp);
     else if (members) hipLaunchKernelGGL(resp_scatter_voters_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, enc, p.n_max, voters);
     else hipLaunchKernelGGL(resp_scatter_kernel, dim3(blocks), dim3(kBlock), 0, h->stream, L, enc, p.n_max);
-    // (the entry array: p.n slots with the switch on, none otherwise)
-    if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, p.n_max, p.lead ? p.n : (uint64_t)0, (uint64_t)0, (uint8_t*)h->wire_out.d, (uint8_t*)p.v_out,
+    // (the entry array: ent_base + p.n slots with either switch on, none otherwise)
+    if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, p.n_max, with_ents ? p.ent_base + p.n : (uint64_t)0, pool_bytes, (uint8_t*)h->wire_out.d, (uint8_t*)p.v_out,
                                p.cap, p.v_resp_off, sc.ctl, h->wire_pin_d + kPinRespond, (const unsigned int*)nullptr, 0u))
       return rc;
   }

@@ -43,6 +43,7 @@ _FORM_DT = {FORM_40: WIRE_MSG40_DT, FORM_HEAD: WIRE_HEAD_DT}
 MSG_APP_RESP = 4
 OUTF_ANSWERED = 0x10  # result flag of raftq_step_frames_respond: the messages the result calls for were built on the device
 RESPOND_FRAME_MAX = 83  # bytes of the largest payload-free frame: cap >= n * (N - 1) * RESPOND_FRAME_MAX
+RESPOND_ENT_MAX = 40  # the most one entry adds to a frame beyond its payload: set_respond_props' bound (RAFTQ_RESPOND_ENT_MAX)
 RESPOND_LEAD_FRAME_MAX = 109  # ... and of the largest frame with one empty entry: the bound once set_respond_lead is on
 
 
@@ -100,6 +101,7 @@ class WireEngine(NodeEngine):
     """NodeEngine + the codecs of the byte formats either side of Step."""
 
     _respond_lead = False  # set_respond_lead's word, for respond_cap
+    _respond_props = False  # set_respond_props', likewise
 
     # -- raftpb.Message <-> rafthttp stream frames -----------------------------------------
     def wire_encode(self, msgs: np.ndarray, ents: np.ndarray | None = None, pool=b"", out: np.ndarray | None = None,
@@ -238,10 +240,21 @@ class WireEngine(NodeEngine):
         self._chk(self._lib.raftq_respond_set_lead(self._h, int(on)))
         self._respond_lead = int(on) == 1
 
-    def respond_cap(self, n: int) -> int:
-        """the `out` size raftq_step_frames_respond needs for n frames (the exact worst case; follows set_respond_lead)"""
+    def set_respond_props(self, on=True) -> None:
+        """raftq_respond_set_props: step_frames_respond answers a RAFTQ_OUT_PROPOSED of a group at the tail too -- the leader's
+        MsgApps with the frame's entries, stamped and marshalled on the device, flagged answered; the call then needs ents and
+        respond_cap(n, nbytes, ents_cap) bytes of out (no batch may be in flight; an effect only under set_step_props)"""
+        self._chk(self._lib.raftq_respond_set_props(self._h, int(on)))
+        self._respond_props = int(on) == 1
+
+    def respond_cap(self, n: int, nbytes: int = 0, ents_cap: int = 0) -> int:
+        """the `out` size raftq_step_frames_respond needs for n frames (the exact worst case; follows set_respond_lead) -- and, under
+        set_respond_props, for a stream of nbytes bytes and an entry array of ents_cap headers"""
         frame_max = RESPOND_LEAD_FRAME_MAX if self._respond_lead else RESPOND_FRAME_MAX
-        return int(n) * (self.n_peers - 1) * frame_max
+        cap = int(n) * (self.n_peers - 1) * frame_max
+        if self._respond_props:
+            cap += (self.n_peers - 1) * (int(nbytes) + int(ents_cap) * RESPOND_ENT_MAX)
+        return cap
 
     def step_frames_respond(self, stream: np.ndarray, frame_off: np.ndarray, msgs: np.ndarray, ents: np.ndarray | None, at_tail: np.ndarray | None,
                             out: np.ndarray, resp_off: np.ndarray | None, peer_off: np.ndarray, tail_appends: bool = True, copy: bool = True):
