@@ -380,6 +380,26 @@ func (e *Engine) SetRespondProps(on bool) error {
 	return e.err(C.raftq_respond_set_props(e.h, v))
 }
 
+// SetProposeForward opts the engine in to (or out of) ProposeFrames for a node that does not lead every group it is asked about
+// (raftq_propose_set_forward; etcd stepFollower's MsgProp: m.To = r.lead; r.send(m)): a Prop whose group this node follows is then
+// ONE MsgProp{To: lead, From: self, Term: 0, Entries} frame in the run of its leader's slot (its other slots are frames of zero
+// length), one whose group knows no leader is dropped, and ProposeFrames returns what became of every Prop.  Off by default: such a
+// Prop fails the call.  No batch may be in flight.
+func (e *Engine) SetProposeForward(on bool) error {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	return e.err(C.raftq_propose_set_forward(e.h, v))
+}
+
+// PropAppended / PropForwarded / PropDropped: RAFTQ_PROP_* (include/raftq_wire.h), ProposeFrames' outcome bytes
+const (
+	PropAppended  = 0
+	PropForwarded = 1
+	PropDropped   = 2
+)
+
 // StepFramesRespond is StepFrames plus the messages its results call for, built and marshalled on the device
 // (raftq_step_frames_respond; raft.go:268-270 -> :227-230): MsgAppResp / MsgVoteResp / MsgHeartbeatResp to the senders and the
 // commit broadcast of a group whose at-tail bit is set (atTail: one bit per group, nil = none).  out receives rafthttp frames,
@@ -582,8 +602,9 @@ type PropEnt struct {
 // caller still owns the log (it appends the entries itself) and Progress.Next (it names only groups whose followers are all at
 // the tail, and moves Next past the new entries).  Every slice must be page-locked (HostAlloc).  A call that fails has appended
 // nothing: when out is too small, need is the size the stream takes and the same call with len(out) >= need is safe -- it appends
-// once.  SOURCE ONLY (round 6).
-func (e *Engine) ProposeFrames(props []Prop, propEnts []PropEnt, msgs []WireMsg, ents []WireEnt, pool, out []byte, frameOff []uint64) (need uint64, err error) {
+// once.  After SetProposeForward(true) outcomes holds one Prop* byte per Prop (raftq_propose_outcomes: a copy of the handle's own
+// bytes); it is nil otherwise and after a call that failed.  SOURCE ONLY (round 6).
+func (e *Engine) ProposeFrames(props []Prop, propEnts []PropEnt, msgs []WireMsg, ents []WireEnt, pool, out []byte, frameOff []uint64) (need uint64, outcomes []byte, err error) {
 	var pp *C.raftq_prop_t
 	var ppe *C.raftq_prop_ent_t
 	var pm *C.raftq_wire_msg_t
@@ -607,5 +628,16 @@ func (e *Engine) ProposeFrames(props []Prop, propEnts []PropEnt, msgs []WireMsg,
 	var c C.raftq_wire_counts_t
 	rc := C.raftq_propose_frames(e.h, pp, C.uint64_t(len(props)), ppe, C.uint64_t(len(propEnts)), pm, C.uint64_t(len(msgs)), pe, C.uint64_t(len(ents)),
 		bytesPtr(pool), C.uint64_t(len(pool)), bytesPtr(out), C.uint64_t(len(out)), po, &c)
-	return uint64(c.bytes), e.err(rc)
+	if rc != 0 {
+		return uint64(c.bytes), nil, e.err(rc)
+	}
+	var what *C.uint8_t
+	var nWhat C.uint64_t
+	if rc := C.raftq_propose_outcomes(e.h, &what, &nWhat); rc != 0 {
+		return uint64(c.bytes), nil, e.err(rc)
+	}
+	if nWhat != 0 {
+		outcomes = C.GoBytes(unsafe.Pointer(what), C.int(nWhat))
+	}
+	return uint64(c.bytes), outcomes, nil
 }

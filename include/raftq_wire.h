@@ -388,7 +388,31 @@ int raftq_step_frames_respond(raftq_t* h, const void* stream, uint64_t nbytes, c
  *     report with the UNCHANGED tail runs maybeCommit over the new membership and reports the commit.  Once the commit is
  *     settled maybeCommit cannot move on an append -- self is a voter and holds the largest Match -- and the proposal passes.
  * RAFTQ_ESTATE, before anything is applied: voter masks loaded on a handle that did not opt in with raftq_bcast_set_voters --
- * whatever raftq_step_set_voters and raftq_tick_set_voters say. */
+ * whatever raftq_step_set_voters and raftq_tick_set_voters say.
+ *
+ * A follower's proposals (raftq_propose_set_forward(h, 1), below): the reference calls node.Propose on whatever node the client
+ * reached (raft.go:211-215), and on a node that does not lead the group etcd's stepFollower turns the proposal into a MsgProp frame
+ * to the leader -- `m.To = r.lead; r.send(m)`.  With the switch on, "anything else fails the call" above no longer holds: record i,
+ * naming group g, is judged on the state as it stands at the call (nothing is in flight) --
+ *   - role == leader: exactly the above -- appendEntry, the N - 1 MsgApps, the store behind the marshal.  RAFTQ_PROP_APPENDED.
+ *   - role == follower, lead != 0 and lead - 1 != self: ONE frame,
+ *       MsgProp{To: lead - 1, From: self, Group: g, Term: 0, Entries: the record's n_ents entries}
+ *     (raft.send leaves a MsgProp's Term alone, so it is 0), entry k = {Type: prop_ents.type, Term: 0, Index: 0, Data}; an entry
+ *     with data_len == 0 has no Data field; every other field is zero -- byte for byte what raftq_wire_encode makes of the record
+ *     raftq_node's handle_proposal builds on the host.  Nothing of the group's state changes.  RAFTQ_PROP_FORWARDED.
+ *   - a candidate, a follower with lead == 0, or a follower whose lead - 1 == self: no frame, no state change (upstream logs
+ *     "no leader; dropping proposal").  The last is a loaded state upstream cannot reach; CHOICE: dropped, as handle_proposal
+ *     does.  RAFTQ_PROP_DROPPED.
+ * One call may mix all three.  Every other refusal stays and applies to every record whatever its role: a group out of range, 0
+ * entries or more than 1024, an entry range outside prop_ents[], a payload outside the pool, a group named twice, N < 2, arrays not
+ * page-locked and 16-byte aligned.  A refused call applies nothing, for forwarded and dropped records as for the leaders'.
+ * The layout stays POSITIONAL, as it is over members: (N - 1) runs of n_props slots behind msgs[], frame_off keeps its n_msgs +
+ * (N - 1) * n_props + 1 entries; a forwarded record has bytes only in the run of its leader's slot, its other slots and every slot
+ * of a dropped record are frames of ZERO length.  The entry headers are written for every record.  counts->n_msgs is n_msgs plus
+ * the frames that have bytes; counts->bytes and the "out is too small" retry keep their meaning.  A call whose records were all
+ * dropped succeeds with no frame of its own.  Over members (raftq_bcast_set_voters with masks loaded) a forward goes to lead
+ * whether or not lead or self is a member of the group -- upstream's send consults no prs -- and the two member refusals are judged
+ * for leader records only.  What became of each record: raftq_propose_outcomes, below. */
 typedef struct raftq_prop {
   uint64_t group;
   uint32_t ent_first; /* into prop_ents[] */
@@ -415,6 +439,27 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
  * own authority, as raftq_tick_elect_frames does.  With all three switches on every frame a node builds on the device goes to a
  * group's members; what remains of conf changes is host work (ConfChange entries through raftq_node: not built). */
 int raftq_bcast_set_voters(raftq_t* h, int on);
+
+/* raftq_propose_frames for a node that does not lead every group it is asked about ("A follower's proposals" in that call's
+ * paragraph).  0, the default: a record whose group this node does not lead fails the call ("this node does not lead its group") --
+ * the call launches the kernels it launches without the switch, writes the same bytes and fails on the same records with the same
+ * text.  1: such a record becomes a MsgProp frame to the group's leader, or is dropped where no leader is known.  Anything but 0 or
+ * 1 is RAFTQ_EINVAL; the handle must be idle (RAFTQ_ESTATE with a Step batch in flight); a NULL handle returns an error without
+ * touching a device.  A property of the handle, like the other switches: raftq_clone_state does not copy it.  Only
+ * raftq_propose_frames reads it.  Independent of raftq_bcast_set_voters.  raftq_node does not turn it on: its handle_proposal still
+ * builds a follower's MsgProp on the host.  (RAFTQ_OUT_FORWARD of raftq_step_frames_respond -- a follower handing on a MsgProp it
+ * RECEIVED, after a change of leader -- stays the host's too.) */
+int raftq_propose_set_forward(raftq_t* h, int on);
+
+/* What became of every record of the last raftq_propose_frames call that SUCCEEDED with raftq_propose_set_forward on: *n =
+ * n_props, (*what)[i] = RAFTQ_PROP_* of props[i].  The bytes live in page-locked memory the handle owns and are valid until the
+ * next call on the handle; they leave the device in the call's own submission under its single wait, packed by the wave (eight
+ * outcomes a store), not a byte a lane.  With the switch off, after a call that failed or was given no record, or before any such
+ * call: *n = 0 and *what = NULL.  A NULL handle returns an error without touching a device. */
+#define RAFTQ_PROP_APPENDED 0  /* this node leads the group: appended, N - 1 MsgApps (over members: one per member) */
+#define RAFTQ_PROP_FORWARDED 1 /* a follower that knows its leader: one MsgProp frame in the leader's run */
+#define RAFTQ_PROP_DROPPED 2   /* no leader known: no frame, nothing changed */
+int raftq_propose_outcomes(raftq_t* h, const uint8_t** what, uint64_t* n);
 
 /* raftq_step_frames_respond's fifth kind: becomeLeader's broadcast ("becomeLeader's broadcast" in that call's paragraph).  0, the
  * default: RAFTQ_OUT_BECAME_LEADER stays the caller's and ends its group's prefix -- the call launches the kernels it always did and

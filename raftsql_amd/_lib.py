@@ -199,6 +199,8 @@ _WIRE_SIGS = [
     ("raftq_bcast_set_voters", C.c_int, [_H, C.c_int]),
     ("raftq_respond_set_lead", C.c_int, [_H, C.c_int]),
     ("raftq_respond_set_props", C.c_int, [_H, C.c_int]),
+    ("raftq_propose_set_forward", C.c_int, [_H, C.c_int]),
+    ("raftq_propose_outcomes", C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     ("raftq_step_stage_wire", C.c_int, [_H, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("raftq_step_wire_msgs", C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     ("raftq_step_wire_entries", C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),

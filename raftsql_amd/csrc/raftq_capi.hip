@@ -1169,6 +1169,16 @@ int raftq_respond_set_props(raftq_t* h, int on) {
   return RAFTQ_OK;
 }
 
+int raftq_propose_set_forward(raftq_t* h, int on) {
+  if (int rc = use_device_idle(h, "raftq_propose_set_forward")) return rc;
+  if (on != 0 && on != 1)
+    return fail(h, RAFTQ_EINVAL, "raftq_propose_set_forward: 0 (raftq_propose_frames refuses a record whose group this node does not lead) or 1 (it "
+                                 "builds the MsgProp frame to the group's leader, or drops the record where no leader is known)");
+  h->prop_forward = on == 1;
+  h->prop_what_n = 0;  // (raftq_propose_outcomes: the last call's bytes are valid until the next call on the handle -- this is one)
+  return RAFTQ_OK;
+}
+
 int raftq_tick(raftq_t* h, raftq_tick_counts_t* counts) {
   if (int rc = use_device_idle(h, "raftq_tick")) return rc;
   if (int rc = tick_voters_ready(h, "raftq_tick")) return rc;

@@ -131,7 +131,9 @@ struct raftq {
                                    // walks, resp_scatter_lead[_voters]_kernel); the same kind of property
   bool resp_props = false;         // raftq_respond_set_props: raftq_step_frames_respond answers a RAFTQ_OUT_PROPOSED at the tail too (the same
                                    // walks and scatter kernels, NodeArrays::ans_props); the same kind of property
-  int step_walk_mode = 1;          // 1 = lists (default), 0 = always the sorted walk (RAFTQ_STEP_WALK=sort)
+  bool prop_forward = false;       // raftq_propose_set_forward: raftq_propose_frames turns a follower's record into a MsgProp frame to its
+                                   // leader (the *_fwd_kernel forms, raftq_propose_kernels.hpp); the same kind of property
+  int step_walk_mode = 1;         // 1 = lists (default), 0 = always the sorted walk (RAFTQ_STEP_WALK=sort)
   uint32_t step_stalls_in_a_row = 0, step_sorted_left = 0;  // back-off from the list walk under hot-group traffic
   uint64_t step_replays = 0;       // batches that went through the sorted path after a stall
   // raftq_step_batch / _submit / _collect: two batches may be in flight, each in its own slot
@@ -206,6 +208,10 @@ struct raftq {
   uint32_t wire_chunk_base = 0, wire_chunk_pending = 0;  // the readers' chunk tickets (the head's fourth word), accounted like the tiles'
   bool wire_chunk_unknown = false;           // the last launch had no reader workgroups: how far its chunk ticket got is not known
   unsigned int prop_stamp = 0;               // raftq_propose_frames: the call's stamp (its validation's verdict word holds it when a record was refused)
+  // raftq_propose_set_forward: the outcome bytes of the last raftq_propose_frames call that succeeded with the switch on
+  // (raftq_propose_outcomes) -- pinned and device-mapped, the check kernel stores them there by the wave
+  raftq_buf::Buffer<uint8_t> prop_what{raftq_buf::Kind::mapped};
+  uint64_t prop_what_n = 0;
   // raftq_step_frames_respond: the walk's response records + the layout's counts (device), and what the walk reads while the
   // call is on (resp_on): the call's stamp, the caller's at-tail bitmap as the device addresses it
   raftq_buf::Buffer<> resp_dev{raftq_buf::Kind::device};

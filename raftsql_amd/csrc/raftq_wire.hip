@@ -524,6 +524,7 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
                          uint64_t pool_bytes, void* out, uint64_t cap, uint64_t* frame_off, raftq_wire_counts_t* counts) {
   if (int rc = raftq_detail::use_device_idle(h, "raftq_propose_frames")) return rc;
   if (counts) *counts = raftq_wire_counts_t{0, 0, 0, 0};
+  h->prop_what_n = 0;  // (raftq_propose_outcomes: valid until the next call)
   if (n_props == 0)  // nothing proposed: the marshal of what the caller queued
     return raftq_wire_encode(h, msgs, n_msgs, ents, n_ents, pool, pool_bytes, out, cap, frame_off, counts);
   if (!props || !prop_ents || n_prop_ents == 0 || (n_msgs && !msgs) || (n_ents && !ents) || (pool_bytes && !pool) || !out || cap == 0)
@@ -533,6 +534,8 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
   const uint64_t n_dev = n_props * (h->N - 1), n = n_msgs + n_dev, n_e = n_ents + n_prop_ents;
   if (n > kMaxItems || n_e > kMaxItems) return fail(h, RAFTQ_EINVAL, "raftq_propose_frames: batch too large");
   if (int rc = ensure_pin(h)) return rc;
+  const bool fwd = h->prop_forward;  // raftq_propose_set_forward: the *_fwd_kernel forms, one outcome byte per record
+  if (fwd) HIPCHK(h, h->prop_what.grow((n_props + 7) / 8 * 8, std::max<size_t>((n_props + n_props / 2 + 7) / 8 * 8, 4096), &h->stream));
   Views v(cap <= ((uint64_t)1 << 31));
   void *v_props = v.add(props), *v_pe = v.add(prop_ents), *v_msgs = v.add(msgs, n_msgs != 0), *v_ents = v.add(ents, n_ents != 0),
        *v_pool = v.add(pool, pool_bytes != 0), *v_out = v.add(out), *v_off = v.opt(frame_off);
@@ -564,8 +567,20 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
   PropRec* props_d = (PropRec*)sc.carved[0];
   PropEnt* pe_d = (PropEnt*)sc.carved[1];
   const bool members = raftq_detail::masked_bcast(h);  // the MsgApps go to each group's own members (propose_check_voters_kernel, propose_build_voters_kernel)
-  if (members) {
+  const bool counted = members || fwd;  // fillers among the device's slots: the build kernel counts the frames that have bytes
+  if (counted)
     if (int rc = members_begin(h)) return rc;
+  if (fwd && members) {
+    hipLaunchKernelGGL(propose_check_fwd_voters_kernel, cg, dim3(kBlock), 0, h->stream, na, (const PropRec*)v_props, n_props, (const PropEnt*)v_pe, n_prop_ents,
+                       pool_bytes, bad, stamp, props_d, pe_d, h->wire_flags + 3, (const uint16_t*)h->voters, (uint64_t*)h->prop_what.d);
+    hipLaunchKernelGGL(propose_build_fwd_voters_kernel, pg, dim3(kBlock), 0, h->stream, na, (const PropRec*)props_d, n_props, (const PropEnt*)pe_d,
+                       (const unsigned int*)bad, stamp, msgs_dev, ents_dev, (uint32_t)n_ents, (const uint16_t*)h->voters, members_word(h));
+  } else if (fwd) {
+    hipLaunchKernelGGL(propose_check_fwd_kernel, cg, dim3(kBlock), 0, h->stream, na, (const PropRec*)v_props, n_props, (const PropEnt*)v_pe, n_prop_ents,
+                       pool_bytes, bad, stamp, props_d, pe_d, h->wire_flags + 3, (uint64_t*)h->prop_what.d);
+    hipLaunchKernelGGL(propose_build_fwd_kernel, pg, dim3(kBlock), 0, h->stream, na, (const PropRec*)props_d, n_props, (const PropEnt*)pe_d,
+                       (const unsigned int*)bad, stamp, msgs_dev, ents_dev, (uint32_t)n_ents, members_word(h));
+  } else if (members) {
     hipLaunchKernelGGL(propose_check_voters_kernel, cg, dim3(kBlock), 0, h->stream, na, (const PropRec*)v_props, n_props, (const PropEnt*)v_pe, n_prop_ents,
                        pool_bytes, bad, stamp, props_d, pe_d, h->wire_flags + 3, (const uint16_t*)h->voters);
     hipLaunchKernelGGL(propose_build_voters_kernel, pg, dim3(kBlock), 0, h->stream, na, (const PropRec*)props_d, n_props, (const PropEnt*)pe_d,
@@ -577,32 +592,33 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
                        (const unsigned int*)bad, stamp, msgs_dev, ents_dev, (uint32_t)n_ents);
   }
   // ... the marshal of everything right behind it ...
-  const unsigned long long* members_d = members ? (const unsigned long long*)members_word(h) : nullptr;
+  const unsigned long long* members_d = counted ? (const unsigned long long*)members_word(h) : nullptr;
+  const auto commit = fwd ? propose_commit_fwd_kernel : propose_commit_kernel;
   if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, n, n_e, pool_bytes, (uint8_t*)h->wire_out.d, (uint8_t*)v_out, cap, (uint64_t*)v_off,
                              sc.ctl, h->wire_pin_d + kPinCall, (const unsigned int*)bad, stamp)) {
     // no marshal, no verdict: the check's marks still come off (a null `pin` makes every lane of the commit kernel refuse)
-    hipLaunchKernelGGL(propose_commit_kernel, pg, dim3(kBlock), 0, h->stream, na, (const PropRec*)props_d, n_props, (const unsigned int*)bad, stamp,
+    hipLaunchKernelGGL(commit, pg, dim3(kBlock), 0, h->stream, na, (const PropRec*)props_d, n_props, (const unsigned int*)bad, stamp,
                        (const uint64_t*)nullptr, cap, n_dev, members_d);
     (void)hipGetLastError();
     return rc;
   }
   // ... and appendEntry's stores behind both verdicts, the check's and the marshal's, which the encoder's last tile has left in the
   // pinned words: a call that fails has applied nothing.  Still one submission and one wait
-  hipLaunchKernelGGL(propose_commit_kernel, pg, dim3(kBlock), 0, h->stream, na, (const PropRec*)props_d, n_props, (const unsigned int*)bad, stamp,
+  hipLaunchKernelGGL(commit, pg, dim3(kBlock), 0, h->stream, na, (const PropRec*)props_d, n_props, (const unsigned int*)bad, stamp,
                      (const uint64_t*)(h->wire_pin_d + kPinCall), cap, n_dev, members_d);
   HIPCHK(h, hipGetLastError());
-  if (members)
+  if (counted)
     if (int rc = members_end(h)) return rc;
   HIPCHK(h, raftq_detail::wait_call(h));
   if (int rc = tile_ctl_check(h, "raftq_propose_frames", kPinCall)) return rc;
   // (from here on the host reads the words propose_commit_kernel decided on: it fails exactly where that kernel stored nothing)
   const uint64_t total = h->wire_pin[kPinCall + kPinTotal];
-  // the MsgApps that have bytes: every slot, or -- over members -- what the build kernel counted
-  const uint64_t frames = members ? h->wire_pin[kPinCall + kPinMembers] : n_dev;
+  // the frames that have bytes: every slot, or -- over members, or with followers' records forwarded -- what the build kernel counted
+  const uint64_t frames = counted ? h->wire_pin[kPinCall + kPinMembers] : n_dev;
   // over members a non-member's slot is a filler the encoder refuses.  A refused call counted no member frame (its build kernel built
   // nothing), so a count above zero that accounts for every refusal needs no look at the check's word
   const uint64_t refused = h->wire_pin[kPinCall + kPinRefused];
-  const bool fillers_only = members && refused == n_dev - frames;
+  const bool fillers_only = counted && refused == n_dev - frames;
   if (refused != 0 && !(fillers_only && frames != 0)) {
     // which record, and why (the check kernel left the largest (stamp, reason, record) it met; an older call's stamp: the marshal refused)
     unsigned long long why = 0;
@@ -615,13 +631,22 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
     const uint32_t reason = (uint32_t)(why >> 32) & 0xffu;
     if ((why >> 40) == (stamp & 0xffffffu) && reason >= 1 && reason <= 8)
       return fail(h, RAFTQ_EINVAL, std::string("raftq_propose_frames: record ") + std::to_string((uint32_t)why) + ": " + kWhy[reason] + " -- nothing was appended");
-    // (over members: proposals whose groups have no member but this node build no frame at all)
+    // (over members: proposals whose groups have no member but this node build no frame at all; forwarding: neither do dropped ones)
     if (!fillers_only)
       return fail(h, RAFTQ_EINVAL, "raftq_propose_frames: a queued message has to / from >= 255, an entry range outside ents[] or a payload outside the pool -- "
                                    "nothing was appended, the output is not valid");
   }
   if (counts) *counts = raftq_wire_counts_t{n_msgs + frames, n_e, 0, total};
   if (total > cap) return fail(h, RAFTQ_EINVAL, "raftq_propose_frames: out is too small (counts->bytes is the size needed) -- nothing was appended");
+  if (fwd) h->prop_what_n = n_props;  // the check kernel's stores are behind the same wait
+  return RAFTQ_OK;
+}
+
+int raftq_propose_outcomes(raftq_t* h, const uint8_t** what, uint64_t* n) {
+  if (!h) return fail(nullptr, RAFTQ_EINVAL, "null handle");
+  if (!what || !n) return fail(h, RAFTQ_EINVAL, "raftq_propose_outcomes: null argument");
+  *what = h->prop_what_n ? h->prop_what.h : nullptr;
+  *n = h->prop_what_n;
   return RAFTQ_OK;
 }
 

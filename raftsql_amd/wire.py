@@ -43,6 +43,7 @@ _FORM_DT = {FORM_40: WIRE_MSG40_DT, FORM_HEAD: WIRE_HEAD_DT}
 MSG_APP_RESP = 4
 OUTF_ANSWERED = 0x10  # result flag of raftq_step_frames_respond: the messages the result calls for were built on the device
 RESPOND_FRAME_MAX = 83  # bytes of the largest payload-free frame: cap >= n * (N - 1) * RESPOND_FRAME_MAX
+PROP_APPENDED, PROP_FORWARDED, PROP_DROPPED = 0, 1, 2  # RAFTQ_PROP_*: propose_frames' outcome bytes under set_propose_forward
 RESPOND_ENT_MAX = 40  # the most one entry adds to a frame beyond its payload: set_respond_props' bound (RAFTQ_RESPOND_ENT_MAX)
 RESPOND_LEAD_FRAME_MAX = 109  # ... and of the largest frame with one empty entry: the bound once set_respond_lead is on
 
@@ -102,6 +103,7 @@ class WireEngine(NodeEngine):
 
     _respond_lead = False  # set_respond_lead's word, for respond_cap
     _respond_props = False  # set_respond_props', likewise
+    _propose_forward = False  # set_propose_forward's: propose_frames then returns the outcomes too
 
     # -- raftpb.Message <-> rafthttp stream frames -----------------------------------------
     def wire_encode(self, msgs: np.ndarray, ents: np.ndarray | None = None, pool=b"", out: np.ndarray | None = None,
@@ -247,6 +249,22 @@ class WireEngine(NodeEngine):
         self._chk(self._lib.raftq_respond_set_props(self._h, int(on)))
         self._respond_props = int(on) == 1
 
+    def set_propose_forward(self, on=True) -> None:
+        """raftq_propose_set_forward: propose_frames turns a record whose group this node follows into ONE MsgProp frame to the
+        group's leader (in the run of the leader's slot; the other slots have zero length) and drops one whose group knows no
+        leader, instead of refusing the call; it then returns one outcome byte per record too (no batch may be in flight)"""
+        self._chk(self._lib.raftq_propose_set_forward(self._h, int(on)))
+        self._propose_forward = int(on) == 1
+
+    def propose_outcomes(self) -> np.ndarray:
+        """raftq_propose_outcomes: PROP_* of every record of the last propose_frames call that succeeded under set_propose_forward
+        (a copy; empty with the switch off or before any such call)"""
+        p, k = C.c_void_p(None), C.c_uint64(0)
+        self._chk(self._lib.raftq_propose_outcomes(self._h, C.byref(p), C.byref(k)))
+        if k.value == 0:
+            return np.zeros(0, np.uint8)
+        return np.frombuffer((C.c_char * k.value).from_address(p.value), dtype=np.uint8, count=k.value).copy()
+
     def respond_cap(self, n: int, nbytes: int = 0, ents_cap: int = 0) -> int:
         """the `out` size raftq_step_frames_respond needs for n frames (the exact worst case; follows set_respond_lead) -- and, under
         set_respond_props, for a stream of nbytes bytes and an entry array of ents_cap headers"""
@@ -362,7 +380,8 @@ class WireEngine(NodeEngine):
         """raftq_propose_frames: appendEntry + bcastAppend for props[] on the device, written into the encoder's input, and the
         marshal of msgs[] + those MsgApps -- one submission, one wait.  All arrays page-locked (engine.pinned_*).
         -> (stream view of out, frame_off | None, counts).  A call that raises has appended nothing; pass `counts` (a
-        _lib.WireCounts) to learn counts.bytes, the size needed, when out was too small: retrying with an out of that size is safe"""
+        _lib.WireCounts) to learn counts.bytes, the size needed, when out was too small: retrying with an out of that size is safe.
+        Under set_propose_forward -> (stream, frame_off | None, counts, outcomes): one PROP_* byte per record"""
         assert props.dtype == PROP_DT and prop_ents.dtype == PROP_ENT_DT and msgs.dtype == WIRE_MSG_DT and ents.dtype == WIRE_ENT_DT
         c = _lib.WireCounts() if counts is None else counts
         self._chk(self._lib.raftq_propose_frames(self._h, props.ctypes.data if len(props) else None, len(props),
@@ -370,6 +389,8 @@ class WireEngine(NodeEngine):
                                                  msgs.ctypes.data if len(msgs) else None, len(msgs), ents.ctypes.data if len(ents) else None, len(ents),
                                                  pool.ctypes.data if len(pool) else None, len(pool), out.ctypes.data, len(out),
                                                  off.ctypes.data if off is not None else None, C.byref(c)))
+        if self._propose_forward:
+            return out[: int(c.bytes)], off, c, self.propose_outcomes()
         return out[: int(c.bytes)], off, c
 
     def step_stage_wire(self, n_cap: int, nbytes_cap: int):
