@@ -293,6 +293,58 @@ func (e *Engine) CollectBeats(out []uint64) (uint64, error) {
 	return uint64(n), e.err(rc)
 }
 
+// SetCheckQuorum opts the engine in to (or out of) upstream's checkQuorum (raftq_set_check_quorum; include/raftq.h "CheckQuorum"):
+// Tick then runs the leader's periodic check -- a group that fails it gets action 3, raises no beat that tick and is listed by
+// CollectChecks; step it with a Msg of type MsgCheckQuorum and Step decides (OutNone with OutfSteppedDown when the leader has
+// heard from less than a quorum) -- Step records which peers answered, and a node under a live leader ignores a MsgVote of a
+// higher term.  TickCollect, TickCollectLists, TickFrames, TickElectFrames and Set.Tick return ErrState while it is on.  Needs
+// SetSelf; election_tick must fit 16 bits.  A property of the engine; no batch may be in flight.
+func (e *Engine) SetCheckQuorum(on bool) error {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	return e.err(C.raftq_set_check_quorum(e.h, v))
+}
+
+// LoadActivity sets every group's activity word (bit p = peer slot p answered since the last check) and / or every leader's
+// electionElapsed; nil leaves that half alone (raftq_load_activity).
+func (e *Engine) LoadActivity(active []uint16, leadElapsed []uint32) error {
+	var a *C.uint16_t
+	var l *C.uint32_t
+	if active != nil {
+		a = (*C.uint16_t)(unsafe.Pointer(&active[0]))
+	}
+	if leadElapsed != nil {
+		l = (*C.uint32_t)(unsafe.Pointer(&leadElapsed[0]))
+	}
+	return e.err(C.raftq_load_activity(e.h, a, l))
+}
+
+// ReadActivity copies them back; either slice may be nil (raftq_read_activity).
+func (e *Engine) ReadActivity(active []uint16, leadElapsed []uint32) error {
+	var a *C.uint16_t
+	var l *C.uint32_t
+	if active != nil {
+		a = (*C.uint16_t)(unsafe.Pointer(&active[0]))
+	}
+	if leadElapsed != nil {
+		l = (*C.uint32_t)(unsafe.Pointer(&leadElapsed[0]))
+	}
+	return e.err(C.raftq_read_activity(e.h, a, l))
+}
+
+// CollectChecks lists the leader groups whose check the last Tick found failing (raftq_collect_checks); 0 with the switch off.
+func (e *Engine) CollectChecks(out []uint64) (uint64, error) {
+	var n C.uint64_t
+	var p *C.uint64_t
+	if len(out) > 0 {
+		p = (*C.uint64_t)(unsafe.Pointer(&out[0]))
+	}
+	rc := C.raftq_collect_checks(e.h, p, C.uint64_t(len(out)), &n)
+	return uint64(n), e.err(rc)
+}
+
 // VoterDelta is one applied conf change of one group (raftq_voter_delta_t: group, the new voter mask, the slots to reset).
 // Voters bit p set = peer slot p votes in the group; Reset bit p set = the slot's Match is zeroed and its vote cleared.
 type VoterDelta struct {

@@ -24,6 +24,7 @@ const (
 	MsgVoteResp      = C.RAFTQ_MSG_VOTE_RESP
 	MsgHeartbeat     = C.RAFTQ_MSG_HEARTBEAT
 	MsgHeartbeatResp = C.RAFTQ_MSG_HEARTBEAT_RESP
+	MsgCheckQuorum   = C.RAFTQ_MSG_CHECK_QUORUM // local: a leader's failed check (CollectChecks); stepped only after SetCheckQuorum(true)
 )
 
 // Msg is layout-identical to raftq_msg_t (64 bytes).  WireTo / Flags / Resv are padding -- ignored by the library --

@@ -255,7 +255,8 @@ int raftq_collect_changed(raftq_t* h, raftq_advance_t* out, uint64_t cap, uint64
 /* ---- batched Tick --------------------------------------
  * rc.node.Tick() (raft.go:223-224) for every group at once: etcd's
  * tickHeartbeat for leaders, tickElection + isElectionTimeout for the rest.
- * role: 0 follower, 1 candidate, 2 leader; action: 0 none, 1 MsgHup, 2 MsgBeat.
+ * role: 0 follower, 1 candidate, 2 leader; action: 0 none, 1 MsgHup, 2 MsgBeat (3: a leader's failed check, only under
+ * raftq_set_check_quorum, "CheckQuorum" below).
  * Timers default to the reference's ElectionTick 10 / HeartbeatTick 1
  * (raft.go:154-155).  The randomised election timeout draws from a
  * counter-based stream, not Go's math/rand (which cannot be reproduced
@@ -319,6 +320,49 @@ int raftq_tick_collect_lists(raftq_t* h, unsigned flags, uint64_t hup_cap, uint6
  * pointer argument may be NULL.  With the bitmap: *beats = NULL, *n_beats = 0, *bitmap_words = ceil(G / 64). */
 int raftq_last_tick_lists(raftq_t* h, const uint32_t** hups, uint64_t* n_hups, const uint32_t** beats, uint64_t* n_beats,
                           const uint64_t** beat_bitmap, uint64_t* bitmap_words);
+/* ---- CheckQuorum: the leader's lease (etcd/raft's checkQuorum, restated; PARITY UNPINNED) -------------------------------------
+ * Upstream added checkQuorum after the 2015 API the reference vendors; what follows is the specification (CHOICE marks what
+ * upstream has no counterpart for).  raftq_set_check_quorum(h, 1) opts the handle in: a leader that hears from less than a quorum
+ * of its group for election_tick ticks steps down, and (raftq_step.h "CheckQuorum") a node under a live leader ignores a MsgVote
+ * of a higher term.  0 is the default; anything but 0 or 1 is RAFTQ_EINVAL; the handle must be idle (RAFTQ_ESTATE with a Step
+ * batch in flight).  A property of the handle: raftq_clone_state does not copy it.  Turning it on allocates the state below,
+ * zeroed; turning it off frees it.
+ *
+ * The state, per group, on a handle that opted in: active[g], bit p set = Progress[p].RecentActive, and lead_elapsed[g], a
+ * leader's electionElapsed (elapsed[g] is a leader's heartbeat counter).  The device keeps both in ONE 32-bit word, lead_elapsed in
+ * 16 bits: with the switch on, raftq_set_check_quorum and raftq_set_timers refuse an election_tick above 65535 and
+ * raftq_load_activity a lead_elapsed above it (RAFTQ_EINVAL).
+ *
+ * Tick.  With the switch on only raftq_tick runs, and like the masked Tick it needs to know `self` (RAFTQ_ESTATE on a handle with
+ * neither raftq_set_self nor raftq_load_node).  For a leader group:
+ *   1. the heartbeat side as always: v = elapsed + 1, a beat is due when v >= heartbeat_tick;
+ *   2. le = lead_elapsed + 1; if le < election_tick, lead_elapsed = le and nothing more;
+ *   3. otherwise lead_elapsed = 0 and act = popcount((active | 1 << self) & members) is held against q = popcount(members) / 2 + 1,
+ *      members = voters[g] when raftq_tick_set_voters is on and masks are loaded, else all N slots (an empty mask: act 0 < q 1,
+ *      the check fails -- CHOICE; a non-voter's bit is stored and does not count -- CHOICE, as its Match):
+ *        pass   active = 0; the beat and the action byte are as always.  This is upstream's Step(MsgCheckQuorum) on a leader that
+ *               keeps its quorum -- nothing changes but the bits -- done on the device: no message for a healthy group.
+ *        fail   active stays; action 3, the group is listed by raftq_collect_checks, and NO beat is raised this tick: elapsed = v,
+ *               the group is absent from the beat list and from n_beat.  The caller steps it with a RAFTQ_MSG_CHECK_QUORUM record
+ *               (raftq_step.h), and Step applies the rule in full: an acknowledgement that lands in between saves the leader, as
+ *               it would upstream.  Such a leader misses exactly one heartbeat (CHOICE); a check that is not stepped leaves the
+ *               beat to the next tick.
+ * A non-leader group ticks bit for bit as without the switch (promotable() included); its active and lead_elapsed do not change.
+ * raftq_read_tick's action byte may be 3.  raftq_tick_counts_t keeps its two fields.
+ *
+ * What the switch closes (RAFTQ_ESTATE, "check quorum" in the text): raftq_tick_collect, raftq_tick_collect_lists,
+ * raftq_tick_frames, raftq_tick_elect_frames (raftq_wire.h) and raftq_set_tick on a set holding such a member -- their beat lists
+ * and device-built rounds do not know a suppressed beat.  raftq_campaign and raftq_load_roles do not touch the activity state. */
+int raftq_set_check_quorum(raftq_t* h, int on);
+/* bulk load / read-back ([G] each; either pointer may be NULL: that half is left alone / not read).  RAFTQ_ESTATE without the
+ * switch; a bit at or above N, or a lead_elapsed above 65535: RAFTQ_EINVAL, nothing loaded.  raftq_clone_state copies the arrays
+ * when both handles hold them. */
+int raftq_load_activity(raftq_t* h, const uint16_t* active /*[G]|NULL*/, const uint32_t* lead_elapsed /*[G]|NULL*/);
+int raftq_read_activity(raftq_t* h, uint16_t* active /*[G]|NULL*/, uint32_t* lead_elapsed /*[G]|NULL*/);
+/* ascending list of the leader groups whose check the last raftq_tick found failing (action 3); raftq_collect_hups's contract.
+ * *n = 0 with the switch off. */
+int raftq_collect_checks(raftq_t* h, uint64_t* groups, uint64_t cap, uint64_t* n);
+
 /* becomeCandidate for `n` distinct groups: role = candidate, elapsed = 0, votes
  * cleared, the candidate's own slot (`self_peer`) granted.  Term bookkeeping is
  * the caller's (raftq_apply_term_deltas). */

@@ -51,6 +51,8 @@ extern "C" {
 #define RAFTQ_MSG_VOTE_RESP 6
 #define RAFTQ_MSG_HEARTBEAT 8
 #define RAFTQ_MSG_HEARTBEAT_RESP 9
+#define RAFTQ_MSG_CHECK_QUORUM 12  /* local: the leader's check fell due and failed in raftq_tick (raftq_collect_checks); only under
+                                    * raftq_set_check_quorum, see "CheckQuorum" below */
 
 /* one inbound message: the fields of raftpb.Message that Step reads */
 typedef struct raftq_msg {
@@ -150,6 +152,28 @@ int raftq_step_set_voters(raftq_t* h, int on);
  * raftq_respond_set_props (raftq_wire.h) opted the handle in: then a RAFTQ_OUT_PROPOSED of a group at the tail is answered with the
  * leader's MsgApps, built on the device, and the bit stays.  raftq_node does not turn the switch on. */
 int raftq_step_set_props(raftq_t* h, int on);
+
+/* CheckQuorum in Step (raftq_set_check_quorum, raftq.h "CheckQuorum": the switch, the state and the Tick side).  With the switch
+ * off every call returns what it always did and type 12 is an unknown kind that fails its batch.  With it on, in every walk form
+ * and every Step-family call (etcd/raft's checkQuorum restated, PARITY UNPINNED; CHOICE marks what upstream has no counterpart for):
+ *   1. stepLeader, on MsgAppResp and MsgHeartbeatResp from p: active |= 1 << p -- in front of the reject branch, so a rejected
+ *      acknowledgement counts as activity.  Over masks (raftq_step_set_voters) a non-voter's bit is stored and does not count
+ *      (CHOICE, as its Match).
+ *   2. reset() -- becomeFollower, becomeCandidate, becomeLeader -- clears every activity bit and lead_elapsed.
+ *   3. The lease, in Step's `m.Term > r.Term` arm, for MsgVote only: with
+ *          inLease = role == leader || (lead != None && elapsed[g] < election_tick)
+ *      the message is IGNORED -- RAFTQ_OUT_NONE, no state change, no response.  A leader under the switch is always in lease
+ *      (upstream's electionElapsed wraps at electionTimeout); a candidate has no lead and never is.  Every other kind with a
+ *      higher term behaves as always.  elapsed[g] is the Tick's word (a MsgApp / MsgHeartbeat earlier in the batch has zeroed it).
+ *   4. RAFTQ_MSG_CHECK_QUORUM, a local kind: term 0, `from` ignored, like MsgHup and MsgBeat; the 64-byte and the 40-byte record
+ *      both take it (a frame of that type from a peer stays a frame of a kind a peer never sends).
+ *        leader   act = popcount((active | 1 << self) & members), members = the group's voter mask in the masked form, all N
+ *                 slots otherwise; q = that form's quorum().  All activity bits are cleared.  act < q: becomeFollower(term, None) --
+ *                 RAFTQ_OUT_NONE with RAFTQ_OUTF_STEPPED_DOWN, role follower, lead 0; Term and Vote do not change, so no
+ *                 RAFTQ_OUTF_HARDSTATE.  Otherwise RAFTQ_OUT_NONE and nothing else changes.  An empty mask: act 0 < q 1, the
+ *                 leader steps down (CHOICE).
+ *        other    ignored (RAFTQ_OUT_NONE).
+ * raftq_node does not turn the switch on. */
 
 /* raftq_msg_t._pad[1] once the handle opted in.  RAFTQ_MSGF_ENTRIES on a MsgApp: the caller says what the message carries -- the low 32 bits of
  * _resv = its number of entries, reject_hint (a field MsgApp does not use) = the Term of the last one (unused with no

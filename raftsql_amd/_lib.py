@@ -102,6 +102,10 @@ _SIGS = [
     ("raftq_tick_collect_lists", C.c_int, [_H, C.c_uint, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("raftq_last_tick_lists", C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    ("raftq_set_check_quorum", C.c_int, [_H, C.c_int]),
+    ("raftq_load_activity", C.c_int, [_H, C.c_void_p, C.c_void_p]),
+    ("raftq_read_activity", C.c_int, [_H, C.c_void_p, C.c_void_p]),
+    ("raftq_collect_checks", C.c_int, [_H, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("raftq_campaign", C.c_int, [_H, C.c_void_p, C.c_uint64, C.c_uint32]),
     ("raftq_cycle", C.c_int, [_H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint, C.c_void_p, C.c_uint64,
                               C.POINTER(C.c_uint64), C.POINTER(Counts)]),

@@ -469,7 +469,7 @@ void raftq_destroy(raftq_t* h) {
   // every wait is over: memory may go
   raftq_buf::free_device(h->match, h->committed[0], h->committed[1], h->first_idx, h->votes, h->voters, h->outcome, h->changed_bits,
                          h->partials, h->offsets, h->self_max, h->anchor, h->moff, h->claim, h->delta_bad, h->role, h->elapsed, h->action, h->hup_bits,
-                         h->beat_bits, h->tick_partials, h->tick_offsets2);
+                         h->beat_bits, h->tick_partials, h->tick_offsets2, h->cq, h->chk_bits);
   raftq_buf::free_host(h->h_partials, h->h_total);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -1072,6 +1072,13 @@ int raftq_detail::ensure_tick_state(raftq_t* h) {
   return RAFTQ_OK;
 }
 
+int raftq_detail::refuse_check_quorum(raftq_t* h, const char* who) {
+  if (!h->cq) return RAFTQ_OK;
+  return fail(h, RAFTQ_ESTATE, std::string(who) + ": raftq_set_check_quorum is on (check quorum): this call's beat lists and device-built rounds do not "
+                                                  "know a beat suppressed by a failing check -- use raftq_tick with raftq_collect_hups / _beats / _checks");
+}
+constexpr uint32_t kCheckQuorumMaxTick = 0xffffu;  // lead_elapsed shares its word with the activity bits (raftq_t::cq)
+
 static int ensure_tick_offsets2(raftq_t* h, uint64_t nw);
 static hipError_t wait_turn(raftq_t* h, uint64_t flag_epoch, int kind = 0);
 
@@ -1081,6 +1088,8 @@ int raftq_set_timers(raftq_t* h, uint32_t election_tick, uint32_t heartbeat_tick
   if (!h) return fail(nullptr, RAFTQ_EINVAL, "null handle");
   if (election_tick == 0 || heartbeat_tick == 0)
     return fail(h, RAFTQ_EINVAL, "raftq_set_timers: ticks must be >= 1");
+  if (h->cq && election_tick > kCheckQuorumMaxTick)
+    return fail(h, RAFTQ_EINVAL, "raftq_set_timers: raftq_set_check_quorum is on and keeps lead_elapsed in 16 bits: election_tick must be <= 65535");
   h->election_tick = election_tick;
   h->heartbeat_tick = heartbeat_tick;
   h->tick_seed = seed;
@@ -1124,13 +1133,77 @@ static int tick_voters_ready(raftq_t* h, const char* who) {
   return fail(h, RAFTQ_ESTATE, std::string(who) + ": raftq_tick_set_voters is on and voter masks are loaded, but the handle holds no node state "
                                                   "(raftq_set_self / raftq_load_node first): promotable() asks whether THIS node votes");
 }
-// Every Tick launch of the handle: tick_kernel, or -- raftq_tick_set_voters with masks loaded -- its masked twin
+// ... and so does the leader's check: the activity bits count self in
+static int tick_check_ready(raftq_t* h, const char* who) {
+  if (!h->cq || h->node_rec || h->self_set) return RAFTQ_OK;
+  return fail(h, RAFTQ_ESTATE, std::string(who) + ": raftq_set_check_quorum is on, but the handle holds no node state (raftq_set_self / raftq_load_node "
+                                                  "first): the check counts THIS node among the active");
+}
+// Every Tick launch of the handle: tick_kernel, or -- raftq_tick_set_voters with masks loaded -- its masked twin, or -- raftq_set_check_quorum
+// -- tick_check_kernel, masks optional
 static void launch_tick(raftq_t* h) {
   const dim3 grid((unsigned)(h->gpad / 1024));
-  if (raftq_detail::masked_tick(h))
+  if (h->cq) {
+    const TickCheckArgs c{h->cq, h->chk_bits, raftq_detail::masked_tick(h) ? h->voters : nullptr, h->self_peer, h->N};
+    hipLaunchKernelGGL(tick_check_kernel, grid, dim3(kBlock), 0, h->stream, tick_args(h, h->tick_no++), c);
+  } else if (raftq_detail::masked_tick(h))
     hipLaunchKernelGGL(tick_voters_kernel, grid, dim3(kBlock), 0, h->stream, tick_args(h, h->tick_no++), (const uint16_t*)h->voters, h->self_peer);
   else
     hipLaunchKernelGGL(tick_kernel, grid, dim3(kBlock), 0, h->stream, tick_args(h, h->tick_no++));
+}
+
+int raftq_set_check_quorum(raftq_t* h, int on) {
+  if (int rc = use_device_idle(h, "raftq_set_check_quorum")) return rc;
+  if (on != 0 && on != 1)
+    return fail(h, RAFTQ_EINVAL, "raftq_set_check_quorum: 0 (a leader never checks, a higher-term MsgVote always deposes) or 1 (the leader's check in "
+                                 "raftq_tick, activity bits and the lease in Step)");
+  if (on == 1 && h->election_tick > kCheckQuorumMaxTick)
+    return fail(h, RAFTQ_EINVAL, "raftq_set_check_quorum: lead_elapsed is kept in 16 bits: election_tick must be <= 65535 (raftq_set_timers)");
+  if ((on == 1) == (h->cq != nullptr)) return RAFTQ_OK;
+  if (on == 1) {
+    if (int rc = ensure_tick_state(h)) return rc;
+    HIPCHK(h, raftq_buf::alloc_group({{(void**)&h->cq, h->ld * 4}, {(void**)&h->chk_bits, h->gpad / 8}}, h->stream));
+    return RAFTQ_OK;
+  }
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // a Tick enqueued with counts == NULL may still use them
+  raftq_buf::free_device(h->cq, h->chk_bits);
+  return RAFTQ_OK;
+}
+
+// the activity state as the ABI speaks it (two arrays) and as the device keeps it (one word per group)
+int raftq_load_activity(raftq_t* h, const uint16_t* active, const uint32_t* lead_elapsed) {
+  if (int rc = use_device_idle(h, "raftq_load_activity")) return rc;
+  if (!h->cq) return fail(h, RAFTQ_ESTATE, "raftq_load_activity: raftq_set_check_quorum is off: the handle holds no activity state");
+  if (!active && !lead_elapsed) return RAFTQ_OK;
+  for (uint64_t g = 0; g < h->G; ++g) {
+    if (active && (active[g] >> h->N) != 0) return fail(h, RAFTQ_EINVAL, "raftq_load_activity: an activity word names a slot >= n_peers; nothing loaded");
+    if (lead_elapsed && lead_elapsed[g] > kCheckQuorumMaxTick)
+      return fail(h, RAFTQ_EINVAL, "raftq_load_activity: lead_elapsed is kept in 16 bits: a value above 65535; nothing loaded");
+  }
+  std::vector<uint32_t> w(h->G);
+  if (!active || !lead_elapsed) {
+    HIPCHK(h, hipMemcpyAsync(w.data(), h->cq, h->G * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  for (uint64_t g = 0; g < h->G; ++g)
+    w[g] = (active ? active[g] : w[g] & 0xffffu) | (lead_elapsed ? lead_elapsed[g] << 16 : w[g] & 0xffff0000u);
+  HIPCHK(h, hipMemcpyAsync(h->cq, w.data(), h->G * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return RAFTQ_OK;
+}
+
+int raftq_read_activity(raftq_t* h, uint16_t* active, uint32_t* lead_elapsed) {
+  if (int rc = use_device_idle(h, "raftq_read_activity")) return rc;
+  if (!h->cq) return fail(h, RAFTQ_ESTATE, "raftq_read_activity: raftq_set_check_quorum is off: the handle holds no activity state");
+  if (!active && !lead_elapsed) return RAFTQ_OK;
+  std::vector<uint32_t> w(h->G);
+  HIPCHK(h, hipMemcpyAsync(w.data(), h->cq, h->G * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (uint64_t g = 0; g < h->G; ++g) {
+    if (active) active[g] = (uint16_t)w[g];
+    if (lead_elapsed) lead_elapsed[g] = w[g] >> 16;
+  }
+  return RAFTQ_OK;
 }
 
 int raftq_tick_set_voters(raftq_t* h, int on) {
@@ -1182,6 +1255,7 @@ int raftq_propose_set_forward(raftq_t* h, int on) {
 int raftq_tick(raftq_t* h, raftq_tick_counts_t* counts) {
   if (int rc = use_device_idle(h, "raftq_tick")) return rc;
   if (int rc = tick_voters_ready(h, "raftq_tick")) return rc;
+  if (int rc = tick_check_ready(h, "raftq_tick")) return rc;
   if (int rc = ensure_tick_state(h)) return rc;
   h->tl_valid = false;  // (raftq_last_tick_lists must not hand out an older tick's lists as the last one's)
   launch_tick(h);
@@ -1206,6 +1280,7 @@ int raftq_tick(raftq_t* h, raftq_tick_counts_t* counts) {
 // and two waits).  The lists land in the pinned advance buffer (8 bytes of its 24-byte entries each) and are copied out.
 int raftq_tick_collect(raftq_t* h, uint64_t* hups, uint64_t hup_cap, uint64_t* n_hup, uint64_t* beats, uint64_t beat_cap, uint64_t* n_beat) {
   if (int rc = use_device_idle(h, "raftq_tick_collect")) return rc;
+  if (int rc = raftq_detail::refuse_check_quorum(h, "raftq_tick_collect")) return rc;
   if (!n_hup || !n_beat) return fail(h, RAFTQ_EINVAL, "raftq_tick_collect: null count");
   if ((hup_cap && !hups) || (beat_cap && !beats)) return fail(h, RAFTQ_EINVAL, "raftq_tick_collect: null list with cap > 0");
   if (int rc = tick_voters_ready(h, "raftq_tick_collect")) return rc;
@@ -1248,6 +1323,7 @@ int raftq_tick_collect(raftq_t* h, uint64_t* hups, uint64_t hup_cap, uint64_t* n
 // In three steps (raftq_detail::tick_lists_*, raftq_internal.hpp), so that raftq_tick_frames (raftq_wire.hip) can put its own
 // kernels between the lists and the flag: what is checked and allocated, what is enqueued, the wait and what it leaves.
 int raftq_detail::tick_lists_prepare(raftq_t* h, const char* who, unsigned flags, uint64_t hup_cap, uint64_t beat_cap, TickLists* tl) {
+  if (int rc = refuse_check_quorum(h, who)) return rc;
   if (flags & ~RAFTQ_TICK_BEAT_BITMAP) return fail(h, RAFTQ_EINVAL, std::string(who) + ": unknown flag");
   if (int rc = tick_voters_ready(h, who)) return rc;
   if (int rc = ensure_tick_state(h)) return rc;
@@ -1387,7 +1463,7 @@ int raftq_read_tick(raftq_t* h, uint8_t* action, uint32_t* elapsed, uint8_t* rol
   return RAFTQ_OK;
 }
 
-// ascending list of the groups the last raftq_tick flagged: field 0 = MsgHup, 1 = MsgBeat
+// ascending list of the groups the last raftq_tick flagged: field 0 = MsgHup, 1 = MsgBeat, 2 = a failed check (raftq_set_check_quorum)
 static int collect_tick_list(raftq_t* h, const char* who, int field, uint64_t* groups, uint64_t cap, uint64_t* n) {
   if (int rc = use_device_idle(h, who)) return rc;
   if (!n) return fail(h, RAFTQ_EINVAL, std::string(who) + ": null count");
@@ -1402,7 +1478,7 @@ static int collect_tick_list(raftq_t* h, const char* who, int field, uint64_t* g
                      h->d_total, field);
   if (take_cap)
     hipLaunchKernelGGL(compact_hups_kernel, dim3((unsigned)(h->gpad / 1024)), dim3(kBlock), 0, h->stream,
-                       field ? h->beat_bits : h->hup_bits, h->offsets, (uint64_t*)h->adv.d, take_cap);
+                       field == 2 ? h->chk_bits : field ? h->beat_bits : h->hup_bits, h->offsets, (uint64_t*)h->adv.d, take_cap);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipStreamSynchronize(h->stream));
   const uint64_t total = *h->h_total;
@@ -1419,6 +1495,17 @@ int raftq_collect_hups(raftq_t* h, uint64_t* groups, uint64_t cap, uint64_t* n) 
 
 int raftq_collect_beats(raftq_t* h, uint64_t* groups, uint64_t cap, uint64_t* n) {
   return collect_tick_list(h, "raftq_collect_beats", 1, groups, cap, n);
+}
+
+int raftq_collect_checks(raftq_t* h, uint64_t* groups, uint64_t cap, uint64_t* n) {
+  if (h && !h->cq) {  // the switch is off: no Tick of this handle gives action 3
+    if (int rc = use_device_idle(h, "raftq_collect_checks")) return rc;
+    if (!n) return fail(h, RAFTQ_EINVAL, "raftq_collect_checks: null count");
+    if (cap && !groups) return fail(h, RAFTQ_EINVAL, "raftq_collect_checks: null out with cap > 0");
+    *n = 0;
+    return RAFTQ_OK;
+  }
+  return collect_tick_list(h, "raftq_collect_checks", 2, groups, cap, n);
 }
 
 int raftq_campaign(raftq_t* h, const uint64_t* groups, uint64_t n, uint32_t self_peer) {
@@ -2133,6 +2220,7 @@ int raftq_set_tick(raftq_set_t* s) {
     if (h->step_collected != h->step_submitted)
       return sfail(s, RAFTQ_ESTATE, "raftq_set_tick: a member has Step batches in flight; collect them first");
     if (int rc = tick_voters_ready(h, "raftq_set_tick")) return sfail(s, rc, h->err);
+    if (int rc = raftq_detail::refuse_check_quorum(h, "raftq_set_tick")) return sfail(s, rc, h->err);
     masked = masked || raftq_detail::masked_tick(h);
   }
   if (masked) return set_tick_voters(s);
@@ -2285,6 +2373,8 @@ int raftq_clone_state(raftq_t* dst, raftq_t* src) {
     HIPCHK(dst, hipMemsetAsync(dst->narrow_word(), 0, sizeof(uint32_t), dst->stream));
   }
   if (src->voters) HIPCHK(dst, hipMemcpyAsync(dst->voters, src->voters, ld * sizeof(uint16_t), hipMemcpyDeviceToDevice, dst->stream));
+  // the activity words where both handles hold them (raftq_set_check_quorum is each handle's own)
+  if (src->cq && dst->cq) HIPCHK(dst, hipMemcpyAsync(dst->cq, src->cq, ld * sizeof(uint32_t), hipMemcpyDeviceToDevice, dst->stream));
   HIPCHK(dst, hipStreamSynchronize(dst->stream));
   dst->have_terms = src->have_terms;
   dense_changed(dst);

@@ -102,6 +102,11 @@ struct raftq {
   uint32_t election_tick = 10, heartbeat_tick = 1;  // reference raft.go:154-155
   uint64_t tick_seed = 0x1000, tick_no = 0;
   bool ticked = false;
+  // raftq_set_check_quorum: both or neither (`cq` stands for the switch).  One dense word per group -- activity bits (bit p =
+  // Progress[p].RecentActive) | lead_elapsed << 16 -- that tick_check_kernel streams and a Step lane reads lazily; the bitmap of the
+  // groups the last raftq_tick gave action 3 (raftq_collect_checks)
+  uint32_t* cq = nullptr;        // [ld]
+  uint64_t* chk_bits = nullptr;  // [gpad/64]
   uint64_t* d_total = nullptr;  // device alias of h_total
   bool have_terms = false;
   unsigned last_flags = 0;
@@ -299,6 +304,9 @@ inline bool masked_tick(const raftq_t* h) { return h->voters != nullptr && h->ti
 // raftq_bcast_set_voters on a handle with masks loaded: raftq_step_frames_respond walks with the masked Node and lays its answers
 // out with the resp_*_voters_kernel entry points, raftq_propose_frames runs propose_check_voters_kernel / propose_build_voters_kernel
 inline bool masked_bcast(const raftq_t* h) { return h->voters != nullptr && h->bcast_voters; }
+// RAFTQ_ESTATE, "check quorum" in the text, on a handle with raftq_set_check_quorum on: the fused Tick calls and the device-built
+// heartbeat / election rounds do not know a suppressed beat
+int refuse_check_quorum(raftq_t* h, const char* who);
 int self_max_check(raftq_t* h);                 // the self-max word re-derived from the rows for h->self_peer (enqueued)
 int narrow_build(raftq_t* h);                   // the narrow mirror and its word re-derived from the rows (enqueued)
 int ensure_staging(raftq_t* h, size_t bytes);   // pinned, device-mapped staging (term deltas, campaign lists, log deltas)

@@ -1667,6 +1667,102 @@ static __global__ __launch_bounds__(kBlock) void tick_set_voters_kernel(const Ti
 #undef RAFTQ_TV_MASKS
 }
 
+// tick_kernel with upstream's CheckQuorum (raftq_set_check_quorum; include/raftq.h "CheckQuorum"): a leader counts its own
+// electionElapsed beside the heartbeat counter and, when it reaches election_tick, asks whether a quorum of the group's members
+// has answered since the last check.  The new state is ONE dense word per group -- the activity bits (Progress.RecentActive, bit p)
+// in the low half, lead_elapsed in the high half -- so a lane's four words are one 16-byte load and one 16-byte store beside its
+// elapsed quad: 18 B per group where tick_kernel moves 10 (20 where tick_voters_kernel moves 12).  A group that passes has its
+// bits cleared here -- all upstream's Step(MsgCheckQuorum) does to a leader that keeps its quorum -- and no message crosses the
+// link for it; a group that fails keeps them, gets action 3, a bit in the third bitmap and a count in the partials' third word,
+// and raises no beat this tick: the caller steps it with RAFTQ_MSG_CHECK_QUORUM (raftq_collect_checks), and Step decides.
+// The popcounts run only where the wave holds a leader whose check is due (ballot), as the draw does.  `voters` is optional
+// (tick_masks_or_all): with it, members = voters[g] and a non-leader gets promotable() exactly as tick_voters_kernel applies it;
+// without, members = all N slots and a non-leader ticks as tick_kernel does.  Bitmaps, action bytes and partials keep the one
+// layout.  A kernel of its own: tick_kernel, tick_voters_kernel and the set kernels keep their text.
+struct TickCheckArgs {
+  uint32_t* cq;            // [ld] in/out: active | lead_elapsed << 16
+  uint64_t* chk_bits;      // [gpad/64] hup_bits' layout, the groups whose check failed
+  const uint16_t* voters;  // [ld] or nullptr
+  uint32_t self, n_peers;
+};
+__device__ __forceinline__ void tick_chunk_out3(const TickArgs& a, uint64_t* chk_bits, uint64_t chunk, uint32_t lane, const uint64_t (&hb)[4],
+                                                const uint64_t (&bb)[4], const uint64_t (&cb)[4], uint32_t n_hup, uint32_t n_beat, uint32_t n_chk) {
+  uint32_t v = 0;  // tick_chunk_out's register with the third bitmap behind the second: 28 dwords, one masked store
+  v = write_lane<0>(v, (uint32_t)hb[0]);  v = write_lane<1>(v, (uint32_t)(hb[0] >> 32));
+  v = write_lane<2>(v, (uint32_t)hb[1]);  v = write_lane<3>(v, (uint32_t)(hb[1] >> 32));
+  v = write_lane<4>(v, (uint32_t)hb[2]);  v = write_lane<5>(v, (uint32_t)(hb[2] >> 32));
+  v = write_lane<6>(v, (uint32_t)hb[3]);  v = write_lane<7>(v, (uint32_t)(hb[3] >> 32));
+  v = write_lane<8>(v, (uint32_t)bb[0]);  v = write_lane<9>(v, (uint32_t)(bb[0] >> 32));
+  v = write_lane<10>(v, (uint32_t)bb[1]); v = write_lane<11>(v, (uint32_t)(bb[1] >> 32));
+  v = write_lane<12>(v, (uint32_t)bb[2]); v = write_lane<13>(v, (uint32_t)(bb[2] >> 32));
+  v = write_lane<14>(v, (uint32_t)bb[3]); v = write_lane<15>(v, (uint32_t)(bb[3] >> 32));
+  v = write_lane<16>(v, (uint32_t)cb[0]); v = write_lane<17>(v, (uint32_t)(cb[0] >> 32));
+  v = write_lane<18>(v, (uint32_t)cb[1]); v = write_lane<19>(v, (uint32_t)(cb[1] >> 32));
+  v = write_lane<20>(v, (uint32_t)cb[2]); v = write_lane<21>(v, (uint32_t)(cb[2] >> 32));
+  v = write_lane<22>(v, (uint32_t)cb[3]); v = write_lane<23>(v, (uint32_t)(cb[3] >> 32));
+  v = write_lane<24>(v, n_hup);
+  v = write_lane<25>(v, n_beat);
+  v = write_lane<26>(v, n_chk);
+  const uint64_t at_hup = (uint64_t)(uintptr_t)a.hup_bits + chunk * 32 + 4ull * lane;
+  const uint64_t at_beat = (uint64_t)(uintptr_t)a.beat_bits + chunk * 32 + 4ull * lane - 32;
+  const uint64_t at_chk = (uint64_t)(uintptr_t)chk_bits + chunk * 32 + 4ull * lane - 64;
+  const uint64_t at_part = (uint64_t)(uintptr_t)a.partials + chunk * 16 + 4ull * lane - 96;
+  const uint64_t at = lane < 8 ? at_hup : (lane < 16 ? at_beat : (lane < 24 ? at_chk : at_part));
+  if (lane < 28) stg<false>(reinterpret_cast<uint32_t*>((uintptr_t)at), v);
+}
+static __global__ __launch_bounds__(kBlock) void tick_check_kernel(TickArgs a, TickCheckArgs c) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint64_t key = tick_key(a.seed, a.tick_no);  // wave-uniform
+  const uint64_t blk = blockIdx.x;
+  const uint64_t g = (blk * kBlock + tid) * 4;
+  const uint32_t roles = ldg<false>(reinterpret_cast<const uint32_t*>(a.role + g));
+  const u32x4 el = ldg<false>(reinterpret_cast<const u32x4*>(a.elapsed + g));
+  const u32x4 cw = ldg<false>(reinterpret_cast<const u32x4*>(c.cq + g));
+  const uint64_t vm = tick_masks_or_all(c.voters, g);
+  const uint32_t all = (1u << c.n_peers) - 1u;
+  uint32_t e[4] = {el.x, el.y, el.z, el.w};
+  uint32_t w[4] = {cw.x, cw.y, cw.z, cw.w};
+  uint32_t acts = 0;
+  uint32_t n_hup = 0, n_beat = 0, n_chk = 0;  // wave-uniform
+  uint64_t hb[4], bb[4], cb[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint32_t role = (roles >> (8 * k)) & 0xffu;
+    const bool valid = g + k < a.n_groups;
+    const uint32_t members = (uint32_t)(vm >> (16 * k)) & all;  // (no masks: every slot)
+    const bool mine = ((members >> c.self) & 1u) != 0;
+    const bool idle = role != 2u && !mine;  // promotable(), as in tick_voters_kernel
+    uint32_t v = e[k] + 1;
+    const bool beat = role == 2u && v >= a.heartbeat_tick;
+    const int64_t d = (int64_t)v - (int64_t)a.election_tick;
+    bool hup = role != 2u && mine && d >= 0;
+    if (__ballot(hup) != 0) hup = hup && d > (int64_t)tick_mod(tick_rand(key, (uint32_t)g + k), a.election_tick, a.et_magic);
+    // the leader's own electionElapsed; the check itself only where some leader of the wave is due one
+    const bool leads = valid && role == 2u;
+    const uint32_t le = (w[k] >> 16) + 1u, active = w[k] & 0xffffu;
+    const bool due = leads && le >= a.election_tick;
+    bool lost = false;
+    if (__ballot(due) != 0) lost = due && (uint32_t)__popc((active | (1u << c.self)) & members) < ((uint32_t)__popc(members) >> 1) + 1u;
+    w[k] = !leads ? w[k] : (due ? (lost ? active : 0u) : (active | (le << 16)));
+    const uint32_t act = !valid ? 0u : (hup ? 1u : (lost ? 3u : (beat ? 2u : 0u)));
+    e[k] = !valid ? e[k] : ((act == 1u || act == 2u || idle) ? 0u : v);
+    acts |= act << (8 * k);
+    hb[k] = __ballot(act == 1u);
+    bb[k] = __ballot(act == 2u);
+    cb[k] = __ballot(act == 3u);
+    n_hup += __popcll(hb[k]);
+    n_beat += __popcll(bb[k]);
+    n_chk += __popcll(cb[k]);
+  }
+  u32x4 out;
+  out.x = e[0]; out.y = e[1]; out.z = e[2]; out.w = e[3];
+  stg<false>(reinterpret_cast<u32x4*>(a.elapsed + g), out);
+  out.x = w[0]; out.y = w[1]; out.z = w[2]; out.w = w[3];
+  stg<false>(reinterpret_cast<u32x4*>(c.cq + g), out);
+  stg<false>(reinterpret_cast<uint32_t*>(a.action + g), acts);
+  tick_chunk_out3(a, c.chk_bits, blk * kWaves + wave, lane, hb, bb, cb, n_hup, n_beat, n_chk);
+}
+
 // The set dispatch at the sweep's access shape: a WAVE owns whole 1,024-group blocks -- the four
 // 256-group chunks tick_tile gives to four waves -- so that every global access of a lane is 16 bytes and every wave
 // instruction 1 KB: ONE 16-byte role load and ONE 16-byte action store per lane for the block's 1,024 groups (16 groups per

@@ -99,11 +99,16 @@ struct NodeArrays {
   const uint64_t* at_tail = nullptr;
   uint32_t resp_stamp = 0;
   uint32_t resp_ent_base = 0;  // ans_props: entry headers the decoder can hand back -- a proposal whose range ends beyond is the host's
+  // raftq_set_check_quorum (nullptr otherwise; read by NodeT's CQ form alone, which is what the handle then launches): the dense word Tick's
+  // tick_check_kernel streams -- activity bits (Progress.RecentActive, bit p) | lead_elapsed << 16 -- and the handle's election_tick,
+  // which the lease compares the Tick-owned elapsed[g] with
+  uint32_t* cq = nullptr;
+  uint32_t election_tick = 0;
 };
 constexpr uint8_t kRecsCaller = 0, kRecsWire = 1, kRecsFrames = 2;
 
 constexpr uint8_t kMsgHup = 0, kMsgBeat = 1, kMsgProp = 2, kMsgApp = 3, kMsgAppResp = 4, kMsgVote = 5, kMsgVoteResp = 6,
-                  kMsgHeartbeat = 8, kMsgHeartbeatResp = 9;
+                  kMsgHeartbeat = 8, kMsgHeartbeatResp = 9, kMsgCheckQuorum = 12;
 constexpr uint8_t kOutNone = 0, kOutVoteResp = 1, kOutHeartbeatResp = 2, kOutCampaign = 3, kOutBecameLeader = 4,
                   kOutProgress = 5, kOutBcastHeartbeat = 6, kOutAppend = 7, kOutAppended = 8, kOutDeferred = 9, kOutSkipped = 10,
                   kOutHeld = 11, kOutProposed = 12, kOutForward = 13;
@@ -208,7 +213,10 @@ __device__ __forceinline__ uint64_t entry_count(const MsgRec& m, uint8_t recs) {
 // props (raftq_step_set_props): a MsgProp is a known kind when it says how many entries it carries and carries at least one
 // (CHOICE: upstream's stepLeader panics on an empty one).  raftq_step_submit_wire's records carry no RAFTQ_MSGF_*: it stays
 // malformed there.
-__device__ __forceinline__ RecClass classify(const MsgRec& m, uint64_t n_groups, uint32_t n_peers, bool msg_flags, uint8_t recs, bool props) {
+// cq (raftq_set_check_quorum): RAFTQ_MSG_CHECK_QUORUM is a known, local kind in a caller's own records -- never in a record a
+// decoder made of a peer's frame.
+__device__ __forceinline__ RecClass classify(const MsgRec& m, uint64_t n_groups, uint32_t n_peers, bool msg_flags, uint8_t recs, bool props,
+                                             bool cq = false) {
   const uint8_t fl = msg_flags ? m.pad[1] : (uint8_t)0;
   if (fl & kMsgfSkip) return kSkip;
   if (m.group >= n_groups) return kBad;
@@ -216,7 +224,7 @@ __device__ __forceinline__ RecClass classify(const MsgRec& m, uint64_t n_groups,
   const uint8_t t = m.type;
   if (t == kMsgProp)
     return props && recs != kRecsWire && (fl & kMsgfEntries) != 0 && entry_count(m, recs) != 0 && m.from < n_peers ? kTake : kBad;
-  const bool local = t == kMsgHup || t == kMsgBeat;
+  const bool local = t == kMsgHup || t == kMsgBeat || (t == kMsgCheckQuorum && cq && recs == kRecsCaller);
   const bool known = local || t == kMsgApp || t == kMsgAppResp || t == kMsgVote || t == kMsgVoteResp ||
                      t == kMsgHeartbeat || t == kMsgHeartbeatResp;
   if (!known || (!local && m.from >= n_peers)) return kBad;
@@ -241,11 +249,11 @@ static __global__ __launch_bounds__(kBlock) void step_keys_kernel(const MsgRec* 
                                                                   uint32_t* __restrict__ order, uint64_t n,
                                                                   uint64_t n_groups, uint32_t n_peers,
                                                                   unsigned int* bad, bool msg_flags, uint8_t recs,
-                                                                  void* __restrict__ out, uint8_t compact, bool props) {
+                                                                  void* __restrict__ out, uint8_t compact, bool props, bool cq) {
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   bool is_bad = false;
   if (i < n) {
-    const RecClass c = classify(msgs[i], n_groups, n_peers, msg_flags, recs, props);
+    const RecClass c = classify(msgs[i], n_groups, n_peers, msg_flags, recs, props, cq);
     is_bad = c == kBad;
     // a skipped record sorts behind every group (the key range has room for n_groups itself) and is answered here
     keys[i] = c == kTake ? msgs[i].group : c == kSkip ? n_groups : 0;  // (bad: keep the sort's key range valid)
@@ -273,7 +281,11 @@ constexpr uint32_t kNil = 0xffffffffu;
 // RAFTQ_OUT_PROPOSED at the tail with the leader's bcastAppend -- the frame's Index / LogTerm are the tail appendEntry moved, so
 // the MsgProp arm keeps that lastTerm in last_term_was too.  Which of the two it answers is NodeArrays::ans_lead / ans_props (run
 // time: a third template axis would be four more walks).
-template <bool MASKED, bool LEAD = false>
+// CQ (raftq_set_check_quorum): checkQuorum's four rules -- activity bits, reset(), the lease, RAFTQ_MSG_CHECK_QUORUM (include/raftq_step.h
+// "CheckQuorum").  A template axis, not a run-time flag of NodeArrays: as a flag the rules cost every handle registers -- the sorted
+// walk went from 158 to 169 VGPRs and from 3 waves per SIMD to 2, the list walk from 190 to 199, with the switch off
+// (profiles/r24/README.md) -- and every `if constexpr (CQ)` is empty in the other forms: they compile to what they were.
+template <bool MASKED, bool LEAD = false, bool CQ = false>
 struct NodeT {
   const NodeArrays& a;
   uint64_t g;
@@ -294,6 +306,9 @@ struct NodeT {
   bool vw_known = false, vw_dirty = false, elapsed_reset = false;
   uint32_t vmask = 0;  // MASKED only: voters[g], bit p = slot p votes in this group
   uint64_t last_term_was = 0;  // LEAD only: lastTerm as it stood before the latest become_leader() / the latest proposal's appendEntry
+  // raftq_set_check_quorum only: the group's activity word (NodeArrays::cq), read lazily and written back when dirty, as the vote word
+  uint32_t cqw = 0;
+  bool cq_known = false, cq_dirty = false;
 
   __device__ NodeT(const NodeArrays& arr, uint64_t group, const uint16_t* voters = nullptr) : a(arr), g(group) {
     if constexpr (MASKED) vmask = voters[g];
@@ -347,6 +362,24 @@ struct NodeT {
       if (a.n_peers <= 8) reinterpret_cast<uint16_t*>(a.votes)[g] = (uint16_t)vw;
       else reinterpret_cast<uint32_t*>(a.votes)[g] = vw;
     }
+    if constexpr (CQ)
+      if (cq_dirty) a.cq[g] = cqw;
+  }
+  __device__ void set_cq(uint32_t w) {
+    cqw = w;
+    cq_known = cq_dirty = true;
+  }
+  __device__ uint32_t get_cq() {
+    if (!cq_known) {
+      cqw = a.cq[g];
+      cq_known = true;
+    }
+    return cqw;
+  }
+  // checkQuorum's lease (include/raftq_step.h): a leader always, a follower that has heard from its leader within election_tick
+  // ticks.  elapsed[g] is the Tick's dense word, read here alone; a reset of this batch that store() has yet to write counts as 0
+  __device__ bool in_lease() const {
+    return role == kLeader || (lead != 0 && (elapsed_reset ? 0u : a.elapsed[g]) < a.election_tick);
   }
   __device__ void set_first_idx(uint64_t v) { first_idx = v; }
   __device__ uint64_t get_first_idx() const { return first_idx; }
@@ -391,6 +424,7 @@ struct NodeT {
     lead = 0;
     elapsed_reset = true;
     set_votes(0);
+    if constexpr (CQ) set_cq(0);  // every Progress.RecentActive = false, electionElapsed = 0
 #pragma unroll
     for (uint32_t p = 0; p < (uint32_t)kMaxPeers; ++p)
       if (p < a.n_peers) {
@@ -582,13 +616,35 @@ struct NodeT {
         o.log_term = last_term;
       }
     } else if (m.term != 0) {
-      if (m.term > term) become_follower(m.term, m.type == kMsgVote ? 0u : m.from + 1);
-      else if (m.term < term) handled = true;  // stale: ignored
+      if (m.term > term) {
+        // checkQuorum: a MsgVote inside the lease is ignored -- no term change, no answer (a partitioned node coming back)
+        bool leased = false;
+        if constexpr (CQ) leased = m.type == kMsgVote && in_lease();
+        if (leased) handled = true;
+        else become_follower(m.term, m.type == kMsgVote ? 0u : m.from + 1);
+      } else if (m.term < term) handled = true;  // stale: ignored
     }
     if (!handled) {
       if (role == kLeader) {
+        // Progress[from].RecentActive = true, in front of the reject branch; a non-voter's bit is stored and does not count
+        if constexpr (CQ) {
+          if (m.type == kMsgAppResp || m.type == kMsgHeartbeatResp) {
+            const uint32_t w = get_cq();
+            if (((w >> m.from) & 1u) == 0) set_cq(w | (1u << m.from));
+          }
+        }
         if (m.type == kMsgBeat) {
           o.type = kOutBcastHeartbeat;
+        } else if (CQ && m.type == kMsgCheckQuorum) {
+          // (classify() lets the kind through only under raftq_set_check_quorum)  The members that answered since the last check,
+          // self included, against quorum(); the bits are cleared either way, and a leader without its quorum steps down
+          const uint32_t w = get_cq();
+          uint32_t members;
+          if constexpr (MASKED) members = vmask;
+          else members = (1u << a.n_peers) - 1u;
+          const uint32_t act = (uint32_t)__popc(((w & 0xffffu) | (1u << a.self)) & members);
+          set_cq(w & 0xffff0000u);
+          if (act < q) become_follower(term, 0);
         } else if (m.type == kMsgVote) {
           o.type = kOutVoteResp; o.reject = 1;
         } else if (m.type == kMsgAppResp || m.type == kMsgProp) {
@@ -708,7 +764,7 @@ static __global__ __launch_bounds__(kBlock) void step_link_kernel(const MsgRec* 
                                                                   uint64_t n_groups, uint32_t n_peers, bool msg_flags, uint8_t recs,
                                                                   NodeRec* rec, uint32_t* __restrict__ next,
                                                                   unsigned int* bad, unsigned int* stall,
-                                                                  void* __restrict__ out, uint8_t compact, CopyRide ride, bool props) {
+                                                                  void* __restrict__ out, uint8_t compact, CopyRide ride, bool props, bool cq) {
   if (blockIdx.x < ride.blocks) {
     copy_ride(ride);
     return;
@@ -716,7 +772,7 @@ static __global__ __launch_bounds__(kBlock) void step_link_kernel(const MsgRec* 
   const uint64_t i = (uint64_t)(blockIdx.x - ride.blocks) * kBlock + threadIdx.x;
   bool is_bad = false, too_long = false;
   if (i < n) {
-    const RecClass c = classify(msgs[i], n_groups, n_peers, msg_flags, recs, props);
+    const RecClass c = classify(msgs[i], n_groups, n_peers, msg_flags, recs, props, cq);
     is_bad = c == kBad;
     if (c == kTake) {
       NodeRec* r = rec + msgs[i].group;  // three atomics on one line
@@ -735,6 +791,7 @@ static __global__ __launch_bounds__(kBlock) void step_link_kernel(const MsgRec* 
 
 // ---- (3, 3b) the walks and the tail reports, each under its name over every slot and as *_voters_kernel over each group's own
 // voters (raftq_step_set_voters): one text, expanded twice
+#define RAFTQ_WALK_CQ false
 #define RAFTQ_WALK_KERNEL(stem) stem##_kernel
 #define RAFTQ_WALK_MASKED false
 #define RAFTQ_WALK_PARAM
@@ -774,6 +831,47 @@ static __global__ __launch_bounds__(kBlock) void step_link_kernel(const MsgRec* 
 #undef RAFTQ_WALK_MASKED
 #undef RAFTQ_WALK_PARAM
 #undef RAFTQ_WALK_VOTERS
+// ... and all four walks once more as *_cq_* over NodeT's CQ form (raftq_set_check_quorum): what a handle with the switch on launches.
+// The tail reports run none of the four rules and have no such form.
+#undef RAFTQ_WALK_CQ
+#define RAFTQ_WALK_CQ true
+#define RAFTQ_WALK_KERNEL(stem) stem##_cq_kernel
+#define RAFTQ_WALK_MASKED false, false, true
+#define RAFTQ_WALK_PARAM
+#define RAFTQ_WALK_VOTERS
+#include "raftq_step_walk_kernels.inc"
+#undef RAFTQ_WALK_KERNEL
+#undef RAFTQ_WALK_MASKED
+#undef RAFTQ_WALK_PARAM
+#undef RAFTQ_WALK_VOTERS
+#define RAFTQ_WALK_KERNEL(stem) stem##_cq_voters_kernel
+#define RAFTQ_WALK_MASKED true, false, true
+#define RAFTQ_WALK_PARAM , const uint16_t* __restrict__ voters
+#define RAFTQ_WALK_VOTERS , voters
+#include "raftq_step_walk_kernels.inc"
+#undef RAFTQ_WALK_KERNEL
+#undef RAFTQ_WALK_MASKED
+#undef RAFTQ_WALK_PARAM
+#undef RAFTQ_WALK_VOTERS
+#define RAFTQ_WALK_KERNEL(stem) stem##_cq_lead_kernel
+#define RAFTQ_WALK_MASKED false, true, true
+#define RAFTQ_WALK_PARAM
+#define RAFTQ_WALK_VOTERS
+#include "raftq_step_walk_kernels.inc"
+#undef RAFTQ_WALK_KERNEL
+#undef RAFTQ_WALK_MASKED
+#undef RAFTQ_WALK_PARAM
+#undef RAFTQ_WALK_VOTERS
+#define RAFTQ_WALK_KERNEL(stem) stem##_cq_lead_voters_kernel
+#define RAFTQ_WALK_MASKED true, true, true
+#define RAFTQ_WALK_PARAM , const uint16_t* __restrict__ voters
+#define RAFTQ_WALK_VOTERS , voters
+#include "raftq_step_walk_kernels.inc"
+#undef RAFTQ_WALK_KERNEL
+#undef RAFTQ_WALK_MASKED
+#undef RAFTQ_WALK_PARAM
+#undef RAFTQ_WALK_VOTERS
+#undef RAFTQ_WALK_CQ
 #undef RAFTQ_WALK_NO_DELTAS
 
 // ---- the record array's bulk paths (raftq_load_node / raftq_read_node: set-up and test traffic, not the hot path) ----------

@@ -904,6 +904,7 @@ extern "C" int raftq_tick_frames(raftq_t* h, unsigned flags, uint64_t hup_cap, u
   const char* who = "raftq_tick_frames";
   if (int rc = raftq_detail::use_device_idle(h, who)) return rc;
   if (counts) *counts = raftq_wire_counts_t{0, 0, 0, 0};
+  if (int rc = raftq_detail::refuse_check_quorum(h, who)) return rc;
   if (!n_hup || !n_beat || !peer_off) return fail(h, RAFTQ_EINVAL, std::string(who) + ": null argument");
   if (flags & ~RAFTQ_TICK_BEAT_BITMAP) return fail(h, RAFTQ_EINVAL, std::string(who) + ": unknown flag");
   if (h->N < 2) return fail(h, RAFTQ_EINVAL, std::string(who) + ": a single-peer group has nobody to send a heartbeat to -- use raftq_tick_collect_lists");
@@ -985,6 +986,7 @@ extern "C" int raftq_tick_elect_frames(raftq_t* h, unsigned flags, uint64_t hup_
   const char* who = "raftq_tick_elect_frames";
   if (int rc = raftq_detail::use_device_idle(h, who)) return rc;
   if (counts) *counts = raftq_wire_counts_t{0, 0, 0, 0};
+  if (int rc = raftq_detail::refuse_check_quorum(h, who)) return rc;
   if (!n_hup || !n_beat || !peer_off) return fail(h, RAFTQ_EINVAL, std::string(who) + ": null argument");
   if (flags & ~RAFTQ_TICK_BEAT_BITMAP) return fail(h, RAFTQ_EINVAL, std::string(who) + ": unknown flag");
   if (h->N < 2) return fail(h, RAFTQ_EINVAL, std::string(who) + ": a single-peer group has nobody to ask for a vote -- use raftq_tick_collect_lists");

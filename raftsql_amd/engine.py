@@ -477,6 +477,36 @@ class QuorumEngine:
         self._chk(self._lib.raftq_collect_beats(self._h, _ptr(out) if cap else None, cap, C.byref(n)))
         return out[: min(cap, int(n.value))], int(n.value)
 
+    # -- CheckQuorum (include/raftq.h "CheckQuorum") -----------------------
+    def set_check_quorum(self, on=True) -> None:
+        """raftq_set_check_quorum: the leader's check in tick() (action 3, collect_checks), activity bits and the lease in Step; a
+        property of the handle (no batch may be in flight).  Turning it on allocates the activity state, zeroed."""
+        self._chk(self._lib.raftq_set_check_quorum(self._h, int(on)))
+
+    def load_activity(self, active: Optional[np.ndarray] = None, lead_elapsed: Optional[np.ndarray] = None) -> None:
+        """active [G] u16 (bit p = peer p answered since the last check), lead_elapsed [G] u32 (a leader's electionElapsed)"""
+        a = None if active is None else np.ascontiguousarray(active, dtype=np.uint16)
+        le = None if lead_elapsed is None else np.ascontiguousarray(lead_elapsed, dtype=np.uint32)
+        for x in (a, le):
+            if x is not None and x.shape != (self.n_groups,):
+                raise ValueError("activity arrays must be [G]")
+        self._chk(self._lib.raftq_load_activity(self._h, _ptr(a) if a is not None else None, _ptr(le) if le is not None else None))
+
+    def read_activity(self):
+        """-> (active [G] u16, lead_elapsed [G] u32)"""
+        a = np.empty(self.n_groups, dtype=np.uint16)
+        le = np.empty(self.n_groups, dtype=np.uint32)
+        self._chk(self._lib.raftq_read_activity(self._h, _ptr(a), _ptr(le)))
+        return a, le
+
+    def collect_checks(self, cap: Optional[int] = None):
+        """-> (ascending leader groups whose check the last tick found failing, their count): step each with MSG_CHECK_QUORUM"""
+        cap = self.n_groups if cap is None else int(cap)
+        out = np.empty(cap, dtype=np.uint64)
+        n = C.c_uint64(0)
+        self._chk(self._lib.raftq_collect_checks(self._h, _ptr(out) if cap else None, cap, C.byref(n)))
+        return out[: min(cap, int(n.value))], int(n.value)
+
     def tick_collect(self, hup_cap: Optional[int] = None, beat_cap: Optional[int] = None):
         """raftq_tick_collect: one Tick and both of its lists, two launches and one wait
         -> (hups, n_hup, beats, n_beat)"""

@@ -19,6 +19,7 @@ from .engine import QuorumEngine, _ptr
 # raftpb.MessageType values Step accepts
 MSG_HUP, MSG_BEAT, MSG_APP, MSG_APP_RESP, MSG_VOTE, MSG_VOTE_RESP, MSG_HEARTBEAT, MSG_HEARTBEAT_RESP = 0, 1, 3, 4, 5, 6, 8, 9
 MSG_PROP = 2  # a follower's forwarded proposal: stepped only under set_step_props (MSGF_ENTRIES + its count in _resv)
+MSG_CHECK_QUORUM = 12  # local: a leader's check failed in tick() (collect_checks): stepped only under set_check_quorum
 MSG_TYPES = (MSG_HUP, MSG_BEAT, MSG_APP, MSG_APP_RESP, MSG_VOTE, MSG_VOTE_RESP, MSG_HEARTBEAT, MSG_HEARTBEAT_RESP)
 
 OUT_NONE, OUT_VOTE_RESP, OUT_HEARTBEAT_RESP, OUT_CAMPAIGN, OUT_BECAME_LEADER, OUT_PROGRESS, OUT_BCAST_HEARTBEAT, OUT_APPEND = range(8)
