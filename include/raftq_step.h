@@ -173,6 +173,8 @@ int raftq_step_set_props(raftq_t* h, int on);
  *                 RAFTQ_OUTF_HARDSTATE.  Otherwise RAFTQ_OUT_NONE and nothing else changes.  An empty mask: act 0 < q 1, the
  *                 leader steps down (CHOICE).
  *        other    ignored (RAFTQ_OUT_NONE).
+ * In raftq_step_frames_respond (raftq_wire.h) a lease-ignored MsgVote builds no frame and does not end its group's device-answered
+ * prefix, and a device-answered becomeLeader clears the activity word in the lane that builds its broadcast.
  * raftq_node does not turn the switch on. */
 
 /* raftq_msg_t._pad[1] once the handle opted in.  RAFTQ_MSGF_ENTRIES on a MsgApp: the caller says what the message carries -- the low 32 bits of

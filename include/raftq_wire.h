@@ -468,7 +468,8 @@ int raftq_propose_outcomes(raftq_t* h, const uint8_t** what, uint64_t* n);
  * Anything but 0 or 1 is RAFTQ_EINVAL; the handle must be idle (RAFTQ_ESTATE with a Step batch in flight); a NULL handle returns
  * an error without touching a device.  A property of the handle, like the other switches: raftq_clone_state does not copy it.  Only
  * raftq_step_frames_respond reads it: raftq_step_frames, raftq_tick_elect_frames (whose one-voter win has nobody to send to) and
- * raftq_node's turns are what they were. */
+ * raftq_node's turns are what they were.  Under raftq_set_check_quorum the answered win is a reset() like any other: the group's
+ * activity word is 0 behind it, and an acknowledgement later in the batch sets its sender's bit alone. */
 int raftq_respond_set_lead(raftq_t* h, int on);
 
 /* raftq_step_frames_respond's sixth kind: a forwarded proposal's MsgApps ("A forwarded proposal's MsgApps" in that call's
@@ -479,7 +480,9 @@ int raftq_respond_set_lead(raftq_t* h, int on);
  * (RAFTQ_ESTATE with a Step batch in flight); a NULL handle returns an error without touching a device.  A property of the handle,
  * like the other switches: raftq_clone_state does not copy it.  Only raftq_step_frames_respond reads it, and it has an effect only
  * with raftq_step_set_props on (no RAFTQ_OUT_PROPOSED arises otherwise).  Independent of raftq_respond_set_lead and
- * raftq_bcast_set_voters: all eight combinations work.  raftq_node does not turn it on. */
+ * raftq_bcast_set_voters: all eight combinations work.  Under raftq_set_check_quorum a MsgVote that the lease ignores builds no
+ * frame and does not end its group's prefix: the proposal and the committing acknowledgement behind it are still answered on the
+ * device.  raftq_node does not turn it on. */
 int raftq_respond_set_props(raftq_t* h, int on);
 
 /* A node's heartbeat round (raft.go:223-224 -> :230: rc.node.Tick() -> tickHeartbeat -> Step(MsgBeat) -> bcastHeartbeat ->

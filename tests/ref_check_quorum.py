@@ -74,15 +74,17 @@ class CVRaft(_CheckArms, V.VRaft):
     pass
 
 
-def from_node_state(s, g, mask, active, lead_elapsed, election_tick, leave_out=frozenset()):
+def from_node_state(s, g, mask, active, lead_elapsed, election_tick, leave_out=frozenset(), classes=None):
+    """classes: the (unmasked, masked) pair to build -- (CRaft, CVRaft) unless a module that composes more arms passes its own"""
+    plain, masked = classes or (CRaft, CVRaft)
     n = s.N
     kw = dict(id=s.self_peer + 1, peers=list(range(1, n + 1)), term=int(s.term[g]), vote=int(s.vote[g]), lead=int(s.lead[g]),
               state=int(s.role[g]), elapsed=int(s.elapsed[g]), committed=int(s.committed[g]), last_index=int(s.last_index[g]),
               last_term=int(s.last_term[g]), first_index_of_term=int(s.first_idx[g]))
     if mask is None:
-        r = CRaft(**kw)
+        r = plain(**kw)
     else:
-        r = CVRaft(voters=frozenset(p + 1 for p in range(n) if (int(mask) >> p) & 1), **kw)
+        r = masked(voters=frozenset(p + 1 for p in range(n) if (int(mask) >> p) & 1), **kw)
     r.prs = {p + 1: R.Progress(int(s.match[p, g])) for p in range(n)}
     r.votes = {p + 1: (int(s.votes[p, g]) == 1) for p in range(n) if int(s.votes[p, g]) in (1, 2)}
     r.active = frozenset(p + 1 for p in range(16) if (int(active) >> p) & 1)

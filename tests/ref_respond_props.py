@@ -122,12 +122,13 @@ def encode(w, e, pool):
     return np.asarray(s), np.asarray(off, np.uint64)
 
 
-def want(st, s, off, at_tail, voters=None, tail_appends=True, lead=True, props=True, ents_cap=None):
-    """st MOVES.  -> dict(m, ents, outs, stream, off, peer_off, answered, wins, taken, n_frames, sent, sent_ents, rec)"""
+def want(st, s, off, at_tail, voters=None, tail_appends=True, lead=True, props=True, ents_cap=None, step=P.step_batch):
+    """st MOVES.  step: the Step reference, called as step(st, voters, records) (a module that composes more arms passes its own).
+    -> dict(m, ents, outs, stream, off, peer_off, answered, wins, taken, n_frames, sent, sent_ents, rec)"""
     wm, we, _ = W.wire_decode(s, off)
     want_m, rec = P.node_filter(wm, we, st.G, st.N, st.self_peer, tail_appends, True)
     last_term0 = st.last_term.copy()
-    outs = P.step_batch(st, voters, rec)
+    outs = step(st, voters, rec)
     w, e, po, ans, wins, taken = expected(rec, want_m, we, outs, last_term0, at_tail, st.N, st.self_peer, voters, lead, props, ents_cap)
     stream, woff = encode(w, e, s)
     return dict(m=want_m, ents=we, outs=outs, stream=stream, off=woff, peer_off=po, answered=ans, wins=wins, taken=taken, n_frames=len(w),

@@ -147,6 +147,7 @@ SHAPES = ((1, 0), (3, 0), (5, 4), (9, 8))
 MAX_ENTS = 4
 N_LEAD, N_CAND, N_LOST = 30, 20, 17  # of G = 97 groups: led, campaigning, following nobody; the other 30 follow somebody
 PLANT = 12  # groups per planted outcome
+N_FRONT = 6 * PLANT  # the records props_batch plants in front of its random traffic: five kinds of proposal and PLANT acknowledgements
 
 
 def props_state(rng, n, self_peer, g=G):
@@ -209,6 +210,7 @@ def props_batch(rng, s, n=N_MSGS, hot=None, max_ents=MAX_ENTS):
     assert all(len(x) == PLANT for x in sets), [len(x) for x in sets]
     first = rng.permutation(np.concatenate(sets))
     n_front = len(first) + PLANT
+    assert n_front == N_FRONT
     m = WG.wide_batch(rng, s, n)
     k_front = rng.integers(2, max_ents + 1, len(first))  # (two at least: an index strictly inside the new entries exists)
     for at, (g, k) in enumerate(zip(first, k_front)):
