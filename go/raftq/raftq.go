@@ -307,6 +307,19 @@ func (e *Engine) SetCheckQuorum(on bool) error {
 	return e.err(C.raftq_set_check_quorum(e.h, v))
 }
 
+// SetPreVote opts the engine in to (or out of) upstream's preVote (raftq_set_pre_vote; include/raftq.h "PreVote"): Step's MsgHup
+// then starts a pre-election -- role RolePreCandidate, OutPreCampaign, no term moves until a quorum of MsgPreVoteResp grants --, Msgs
+// of type MsgPreVote / MsgPreVoteResp are stepped, and a stale leader's MsgApp / MsgHeartbeat is answered OutTermResp.  Requires
+// SetCheckQuorum(true) (ErrState otherwise, and SetCheckQuorum(false) returns ErrState while it is on); TickElectFrames returns
+// ErrState meanwhile.  A property of the engine; no batch may be in flight.
+func (e *Engine) SetPreVote(on bool) error {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	return e.err(C.raftq_set_pre_vote(e.h, v))
+}
+
 // LoadActivity sets every group's activity word (bit p = peer slot p answered since the last check) and / or every leader's
 // electionElapsed; nil leaves that half alone (raftq_load_activity).
 func (e *Engine) LoadActivity(active []uint16, leadElapsed []uint32) error {

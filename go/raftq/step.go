@@ -25,6 +25,8 @@ const (
 	MsgHeartbeat     = C.RAFTQ_MSG_HEARTBEAT
 	MsgHeartbeatResp = C.RAFTQ_MSG_HEARTBEAT_RESP
 	MsgCheckQuorum   = C.RAFTQ_MSG_CHECK_QUORUM // local: a leader's failed check (CollectChecks); stepped only after SetCheckQuorum(true)
+	MsgPreVote       = C.RAFTQ_MSG_PRE_VOTE      // a peer's pre-election, MsgVote's fields; stepped only after SetPreVote(true)
+	MsgPreVoteResp   = C.RAFTQ_MSG_PRE_VOTE_RESP
 )
 
 // Msg is layout-identical to raftq_msg_t (64 bytes).  WireTo / Flags / Resv are padding -- ignored by the library --
@@ -115,6 +117,9 @@ const (
 	OutHeld           = C.RAFTQ_OUT_HELD     // MsgfHold
 	OutProposed       = C.RAFTQ_OUT_PROPOSED // SetStepProps: a leader took a MsgProp -- store its entries at Index .. LastIndex with Term LogTerm, then bcastAppend
 	OutForward        = C.RAFTQ_OUT_FORWARD  // SetStepProps: a follower's MsgProp goes on to its leader, To = Lead - 1
+	OutPreCampaign    = C.RAFTQ_OUT_PRE_CAMPAIGN  // SetPreVote: became pre-candidate, send MsgPreVote{Term: Term + 1, Index, LogTerm} to every other peer
+	OutPreVoteResp    = C.RAFTQ_OUT_PRE_VOTE_RESP // SetPreVote: send MsgPreVoteResp{To, Term: Index, Reject}
+	OutTermResp       = C.RAFTQ_OUT_TERM_RESP     // SetPreVote: a stale leader's MsgApp / MsgHeartbeat, send MsgAppResp{To, Term}
 
 	FlagHardState   = C.RAFTQ_OUTF_HARDSTATE // persist {Term, Vote, Commit} before sending (raft.go:228-230)
 	FlagCommitted   = C.RAFTQ_OUTF_COMMITTED

@@ -286,6 +286,7 @@ int raftq_collect_changed(raftq_t* h, raftq_advance_t* out, uint64_t cap, uint64
 #define RAFTQ_ROLE_FOLLOWER 0
 #define RAFTQ_ROLE_CANDIDATE 1
 #define RAFTQ_ROLE_LEADER 2
+#define RAFTQ_ROLE_PRE_CANDIDATE 3 /* only under raftq_set_pre_vote ("PreVote" below) */
 typedef struct raftq_tick_counts {
   uint64_t n_hup;  /* groups whose election timer fired: they campaign */
   uint64_t n_beat; /* leader groups due a heartbeat */
@@ -362,6 +363,30 @@ int raftq_read_activity(raftq_t* h, uint16_t* active /*[G]|NULL*/, uint32_t* lea
 /* ascending list of the leader groups whose check the last raftq_tick found failing (action 3); raftq_collect_hups's contract.
  * *n = 0 with the switch off. */
 int raftq_collect_checks(raftq_t* h, uint64_t* groups, uint64_t cap, uint64_t* n);
+
+/* ---- PreVote: pre-elections, and an answer for a stale leader (etcd/raft's preVote, restated; PARITY UNPINNED) -----------------
+ * CheckQuorum alone locks a node out for good: cut off, it campaigns and inflates its term; back again, its MsgVote of the higher
+ * term is ignored under the lease and the leader's MsgApp / MsgHeartbeat of the lower term are dropped without an answer, so its
+ * timer never resets and it campaigns again.  Upstream closed this with PreVote -- a pre-election at term + 1 that moves no term
+ * until a quorum would grant -- and, under `checkQuorum || preVote`, a MsgAppResp that tells a stale leader the term it missed.
+ * raftq_set_pre_vote(h, 1) opts the handle in to both; the rules are Step's (raftq_step.h "PreVote").  0 is the default; anything but
+ * 0 or 1 is RAFTQ_EINVAL; the handle must be idle (RAFTQ_ESTATE with a Step batch in flight); a NULL handle is an error and no
+ * device is touched.  A property of the handle: raftq_clone_state does not copy it.  It holds no state of its own.
+ *
+ * CHOICE: it requires CheckQuorum.  raftq_set_pre_vote(h, 1) on a handle without raftq_set_check_quorum is RAFTQ_ESTATE ("check
+ * quorum" in the text), and raftq_set_check_quorum(h, 0) while it is on is RAFTQ_ESTATE ("pre vote").  Upstream's two options are
+ * independent; here the hole PreVote closes exists only under the lease, the pair is what upstream recommends, and the rules stay
+ * inside the walks a handle with the lease launches -- no new family of kernels.
+ *
+ * Roles.  raftq_load_roles accepts RAFTQ_ROLE_PRE_CANDIDATE with the switch on, and refuses it as any role above 2 otherwise.  The
+ * Tick needs no change: every Tick kernel tests role == 2 alone, so a pre-candidate's election timer runs as a follower's does.
+ * Turning the switch off leaves a role-3 group as it is: a Step without the switch takes it for a follower without a leader
+ * (the last arm of its role test) until a message gives it another role.
+ *
+ * What the switch closes (RAFTQ_ESTATE, "pre vote" in the text): raftq_tick_elect_frames (raftq_wire.h), whose device-built round
+ * makes a MsgHup a becomeCandidate and sends MsgVote (it is closed to CheckQuorum already).  raftq_campaign stays the real
+ * becomeCandidate.  raftq_node does not turn the switch on. */
+int raftq_set_pre_vote(raftq_t* h, int on);
 
 /* becomeCandidate for `n` distinct groups: role = candidate, elapsed = 0, votes
  * cleared, the candidate's own slot (`self_peer`) granted.  Term bookkeeping is

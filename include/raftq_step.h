@@ -53,6 +53,8 @@ extern "C" {
 #define RAFTQ_MSG_HEARTBEAT_RESP 9
 #define RAFTQ_MSG_CHECK_QUORUM 12  /* local: the leader's check fell due and failed in raftq_tick (raftq_collect_checks); only under
                                     * raftq_set_check_quorum, see "CheckQuorum" below */
+#define RAFTQ_MSG_PRE_VOTE 17      /* raftpb values; only under raftq_set_pre_vote, see "PreVote" below */
+#define RAFTQ_MSG_PRE_VOTE_RESP 18
 
 /* one inbound message: the fields of raftpb.Message that Step reads */
 typedef struct raftq_msg {
@@ -177,6 +179,43 @@ int raftq_step_set_props(raftq_t* h, int on);
  * prefix, and a device-answered becomeLeader clears the activity word in the lane that builds its broadcast.
  * raftq_node does not turn the switch on. */
 
+/* PreVote in Step (raftq_set_pre_vote, raftq.h "PreVote": the switch, what it requires and closes).  With the switch off every call
+ * returns what it always did and types 17 and 18 are unknown kinds that fail their batch.  With it on, in every walk form and every
+ * Step-family call (etcd/raft's preVote and its answer to a stale leader restated, PARITY UNPINNED; CHOICE marks where this differs
+ * from or adds to upstream).  raftq_msg_t and raftq_msg40_t take types 17 and 18 with MsgVote's fields (index / log_term = the
+ * sender's tail, reject); both are a peer's kinds: `from` >= N is malformed.
+ *   1. MsgHup on a non-leader is becomePreCandidate: role = RAFTQ_ROLE_PRE_CANDIDATE, lead = None, the vote word cleared and the
+ *      own grant recorded, elapsed[g] = 0 (CHOICE: zeroed as Step's MsgHup always has; upstream leaves the clock alone).  Term,
+ *      Vote, the Match words, the gate and the activity word do not change.  RAFTQ_OUT_PRE_CAMPAIGN: index / log_term = the log's
+ *      tail, term = the unchanged r.Term -- the frames carry term + 1 --, no RAFTQ_OUTF_HARDSTATE.  If the own grant already equals
+ *      quorum() (N = 1, a one-voter group) Step goes straight on through becomeCandidate and becomeLeader: the result is byte for
+ *      byte what MsgHup gives without the switch.  Over masks with self not a voter the grant is recorded but not counted and the
+ *      result is RAFTQ_OUT_PRE_CAMPAIGN (the existing CHOICE for MsgHup).  A leader ignores MsgHup, as always.
+ *   2. m.Term > r.Term.  A MsgPreVote inside the lease is ignored exactly as a MsgVote is (CheckQuorum's rule 3, for both kinds);
+ *      outside it, it changes no term and no role and goes on to rule 4.  A MsgPreVoteResp with reject == 0 changes no term and
+ *      goes on to the role's arm; with reject == 1 it is becomeFollower(m.Term, None) (CHOICE: lead is None, the sender is no
+ *      leader).  Every other kind behaves as always.
+ *   3. 0 < m.Term < r.Term.  A MsgPreVote: RAFTQ_OUT_PRE_VOTE_RESP, reject = 1, index = r.Term.  A MsgApp or MsgHeartbeat:
+ *      RAFTQ_OUT_TERM_RESP -- no state change, no clock reset; a RAFTQ_MSGF_BARRIER on it holds nobody up and RAFTQ_MSGF_ENTRIES is
+ *      not looked at.  Every other kind is ignored, as always.
+ *   4. A MsgPreVote that got this far is answered by one rule in every role (upstream moved vote handling in front of the role
+ *      functions with PreVote):
+ *          grant = (Vote == None || m.Term > r.Term || Vote == from + 1) && isUpToDate(m.Index, m.LogTerm)
+ *      RAFTQ_OUT_PRE_VOTE_RESP: granted, index = m.Term; rejected, reject = 1 and index = r.Term.  NOTHING changes -- not Term, Vote,
+ *      lead, role, elapsed or the activity bits -- and no flag is set.  A MsgVote is answered by the per-role rules it always had.
+ *   5. Role 3 is stepped by the candidate's arm, but: it polls MsgPreVoteResp and ignores MsgVoteResp (a candidate ignores
+ *      MsgPreVoteResp; so do a follower and a leader).  granted == quorum(): becomeCandidate -- term + 1, vote self, reset() incl.
+ *      the activity word, the own grant -- and the result is one of the two MsgHup has without the switch: RAFTQ_OUT_CAMPAIGN with
+ *      RAFTQ_OUTF_HARDSTATE, or RAFTQ_OUT_BECAME_LEADER if the own grant is the quorum.  recorded - granted == quorum():
+ *      becomeFollower(term, None), RAFTQ_OUTF_STEPPED_DOWN, Term and Vote kept.  Upstream's equality form, masked too.  A MsgApp /
+ *      MsgHeartbeat of the own term: becomeFollower(term, from) and handled, as a candidate does; a MsgVote of the own term is
+ *      rejected; a MsgProp is dropped.
+ * The compact records: RAFTQ_OUT_PRE_CAMPAIGN is packed as RAFTQ_OUT_CAMPAIGN is (below).  In raftq_step_frames_respond
+ * (raftq_wire.h) the three new results are the host's -- no RAFTQ_OUTF_ANSWERED, and they end their group's device-answered prefix --
+ * while a lease-ignored MsgPreVote builds no frame and does not end it, as a lease-ignored MsgVote does not.  Under the switch the
+ * frames calls take frames of types 17 and 18; without it they stay frames of a kind a peer never sends.  Device-built MsgPreVote
+ * rounds are not built yet: raftq_tick_elect_frames refuses the handle.  raftq_node does not turn the switch on. */
+
 /* raftq_msg_t._pad[1] once the handle opted in.  RAFTQ_MSGF_ENTRIES on a MsgApp: the caller says what the message carries -- the low 32 bits of
  * _resv = its number of entries, reject_hint (a field MsgApp does not use) = the Term of the last one (unused with no
  * entries).  Step then runs raftLog.maybeAppend itself whenever the message appends at the TAIL of the log (m.Index ==
@@ -221,6 +260,9 @@ int raftq_step_set_props(raftq_t* h, int on);
 #define RAFTQ_OUT_PROPOSED 12       /* leader took a MsgProp (raftq_step_set_props): store its n entries as {Term: log_term, Index: index ..
                                      * last_index}, then bcastAppend */
 #define RAFTQ_OUT_FORWARD 13        /* follower's MsgProp: send it on to `to` = lead - 1, the one result whose addressee is not the sender */
+#define RAFTQ_OUT_PRE_CAMPAIGN 14   /* became pre-candidate: send MsgPreVote{Term: term + 1, Index: index, LogTerm: log_term} to every other peer */
+#define RAFTQ_OUT_PRE_VOTE_RESP 15  /* send MsgPreVoteResp{To: to, Term: index, Reject: reject} -- `index` carries the response's Term */
+#define RAFTQ_OUT_TERM_RESP 16      /* a stale leader's MsgApp / MsgHeartbeat: send MsgAppResp{To: to, Term: term} (Index 0, no reject) */
 
 #define RAFTQ_OUTF_HARDSTATE 0x01u    /* Term, Vote or Commit changed: HardState must be persisted (wal.Save, raft.go:228) */
 #define RAFTQ_OUTF_COMMITTED 0x02u    /* raftLog.committed advanced (leader: bcastAppend carries it) */
@@ -326,7 +368,7 @@ int raftq_step_submit_packed(raftq_t* h, const raftq_msg40_t* msgs, uint64_t n);
 
 /* Compact result records: 40 instead of 64 bytes per message cross PCIe (the result copy is what a pipelined
  * batch waits for).  Record i answers msgs[i], so its group and addressee (= msgs[i].group, msgs[i].from) are not
- * repeated; `aux` is log_term for RAFTQ_OUT_CAMPAIGN / RAFTQ_OUT_BECAME_LEADER -- whose `index` is the last index --
+ * repeated; `aux` is log_term for RAFTQ_OUT_CAMPAIGN / RAFTQ_OUT_BECAME_LEADER / RAFTQ_OUT_PRE_CAMPAIGN -- whose `index` is the last index --
  * and raftLog.lastIndex() for every other type (whose log_term is 0, but for RAFTQ_OUT_PROPOSED, whose log_term IS its term):
  * the full record is recovered exactly.  The addressee of a RAFTQ_OUT_FORWARD is not msgs[i].from: it is recovered from the
  * record's `lead` (to = lead - 1), here and in the 32-byte record.
@@ -348,7 +390,7 @@ typedef struct raftq_step_out_c {
 /* The 32-byte record (round 6; raftq_step_set_compact(h, 2)): the 40-byte one without `aux`.  What aux carried is either not
  * needed by whoever applies a result (raftLog.lastIndex() after a message: the log's owner knows its own log) or recoverable:
  * log_term of a RAFTQ_OUT_BECAME_LEADER IS its term (becomeLeader appends the empty entry of the new term), and a
- * RAFTQ_OUT_CAMPAIGN -- which moves no commit index -- carries its log_term in `commit`.  The full record is recovered exactly
+ * RAFTQ_OUT_CAMPAIGN -- which moves no commit index -- carries its log_term in `commit`, and so does a RAFTQ_OUT_PRE_CAMPAIGN.  The full record is recovered exactly
  * by a reader that tracks lastIndex / committed per group across the batch (tests/test_step_gpu.py does); behind a
  * RAFTQ_OUT_PROPOSED the tail is index + n - 1, n being the count of the reader's own record, and its log_term is its term.  Why not the
  * 16-byte-per-message + 24-byte-per-touched-group form VERDICT r05 sketched: a result's term and commit are the state AFTER
@@ -360,7 +402,7 @@ typedef struct raftq_step_out_c {
 typedef struct raftq_step_out_s {
   uint64_t term;   /* r.Term after the message */
   uint64_t index;  /* by type, as raftq_step_out_t */
-  uint64_t commit; /* raftLog.committed after; RAFTQ_OUT_CAMPAIGN: the candidate's log_term */
+  uint64_t commit; /* raftLog.committed after; RAFTQ_OUT_CAMPAIGN / RAFTQ_OUT_PRE_CAMPAIGN: the candidate's log_term */
   uint8_t vote;    /* 0 = None, else peer slot + 1 */
   uint8_t lead;
   uint8_t type;    /* RAFTQ_OUT_* */

@@ -1077,6 +1077,11 @@ int raftq_detail::refuse_check_quorum(raftq_t* h, const char* who) {
   return fail(h, RAFTQ_ESTATE, std::string(who) + ": raftq_set_check_quorum is on (check quorum): this call's beat lists and device-built rounds do not "
                                                   "know a beat suppressed by a failing check -- use raftq_tick with raftq_collect_hups / _beats / _checks");
 }
+int raftq_detail::refuse_pre_vote(raftq_t* h, const char* who) {
+  if (!h->pre_vote) return RAFTQ_OK;
+  return fail(h, RAFTQ_ESTATE, std::string(who) + ": raftq_set_pre_vote is on (pre vote): this call's device-built round makes a MsgHup a becomeCandidate and "
+                                                  "sends MsgVote -- step the MsgHup (RAFTQ_OUT_PRE_CAMPAIGN) and send MsgPreVote");
+}
 constexpr uint32_t kCheckQuorumMaxTick = 0xffffu;  // lead_elapsed shares its word with the activity bits (raftq_t::cq)
 
 static int ensure_tick_offsets2(raftq_t* h, uint64_t nw);
@@ -1100,7 +1105,8 @@ int raftq_load_roles(raftq_t* h, const uint8_t* role, const uint32_t* elapsed) {
   if (int rc = use_device_idle(h, "raftq_load_roles")) return rc;
   if (!role) return fail(h, RAFTQ_EINVAL, "raftq_load_roles: null role array");
   for (uint64_t g = 0; g < h->G; ++g)
-    if (role[g] > RAFTQ_ROLE_LEADER) return fail(h, RAFTQ_EINVAL, "raftq_load_roles: role must be 0, 1 or 2");
+    if (role[g] > RAFTQ_ROLE_LEADER && !(h->pre_vote && role[g] == RAFTQ_ROLE_PRE_CANDIDATE))
+      return fail(h, RAFTQ_EINVAL, "raftq_load_roles: role must be 0, 1 or 2");  // (3 = pre-candidate under raftq_set_pre_vote alone)
   if (int rc = ensure_tick_state(h)) return rc;
   HIPCHK(h, hipMemcpyAsync(h->role, role, h->G, hipMemcpyHostToDevice, h->stream));
   dense_changed(h);
@@ -1160,6 +1166,8 @@ int raftq_set_check_quorum(raftq_t* h, int on) {
   if (on == 1 && h->election_tick > kCheckQuorumMaxTick)
     return fail(h, RAFTQ_EINVAL, "raftq_set_check_quorum: lead_elapsed is kept in 16 bits: election_tick must be <= 65535 (raftq_set_timers)");
   if ((on == 1) == (h->cq != nullptr)) return RAFTQ_OK;
+  if (on == 0 && h->pre_vote)
+    return fail(h, RAFTQ_ESTATE, "raftq_set_check_quorum: raftq_set_pre_vote is on (pre vote) and requires the lease: turn it off first");
   if (on == 1) {
     if (int rc = ensure_tick_state(h)) return rc;
     HIPCHK(h, raftq_buf::alloc_group({{(void**)&h->cq, h->ld * 4}, {(void**)&h->chk_bits, h->gpad / 8}}, h->stream));
@@ -1167,6 +1175,17 @@ int raftq_set_check_quorum(raftq_t* h, int on) {
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));  // a Tick enqueued with counts == NULL may still use them
   raftq_buf::free_device(h->cq, h->chk_bits);
+  return RAFTQ_OK;
+}
+
+int raftq_set_pre_vote(raftq_t* h, int on) {
+  if (int rc = use_device_idle(h, "raftq_set_pre_vote")) return rc;
+  if (on != 0 && on != 1)
+    return fail(h, RAFTQ_EINVAL, "raftq_set_pre_vote: 0 (MsgHup campaigns, types 17 and 18 are unknown kinds) or 1 (MsgHup starts a pre-election; a stale "
+                                 "leader's MsgApp / MsgHeartbeat is answered)");
+  if (on == 1 && !h->cq)
+    return fail(h, RAFTQ_ESTATE, "raftq_set_pre_vote: requires raftq_set_check_quorum (check quorum): the rules live beside the lease they complete");
+  h->pre_vote = on == 1;
   return RAFTQ_OK;
 }
 

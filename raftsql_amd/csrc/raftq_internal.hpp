@@ -107,6 +107,7 @@ struct raftq {
   // groups the last raftq_tick gave action 3 (raftq_collect_checks)
   uint32_t* cq = nullptr;        // [ld]
   uint64_t* chk_bits = nullptr;  // [gpad/64]
+  bool pre_vote = false;         // raftq_set_pre_vote: only ever true while cq is set
   uint64_t* d_total = nullptr;  // device alias of h_total
   bool have_terms = false;
   unsigned last_flags = 0;
@@ -307,6 +308,8 @@ inline bool masked_bcast(const raftq_t* h) { return h->voters != nullptr && h->b
 // RAFTQ_ESTATE, "check quorum" in the text, on a handle with raftq_set_check_quorum on: the fused Tick calls and the device-built
 // heartbeat / election rounds do not know a suppressed beat
 int refuse_check_quorum(raftq_t* h, const char* who);
+// RAFTQ_ESTATE, "pre vote" in the text, on a handle with raftq_set_pre_vote on: a call that turns a MsgHup into becomeCandidate on the device
+int refuse_pre_vote(raftq_t* h, const char* who);
 int self_max_check(raftq_t* h);                 // the self-max word re-derived from the rows for h->self_peer (enqueued)
 int narrow_build(raftq_t* h);                   // the narrow mirror and its word re-derived from the rows (enqueued)
 int ensure_staging(raftq_t* h, size_t bytes);   // pinned, device-mapped staging (term deltas, campaign lists, log deltas)

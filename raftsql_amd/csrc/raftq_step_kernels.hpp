@@ -104,14 +104,16 @@ struct NodeArrays {
   // which the lease compares the Tick-owned elapsed[g] with
   uint32_t* cq = nullptr;
   uint32_t election_tick = 0;
+  // raftq_set_pre_vote (only ever true beside cq, and read by NodeT's CQ form alone): the five rules of include/raftq_step.h "PreVote"
+  bool pv = false;
 };
 constexpr uint8_t kRecsCaller = 0, kRecsWire = 1, kRecsFrames = 2;
 
 constexpr uint8_t kMsgHup = 0, kMsgBeat = 1, kMsgProp = 2, kMsgApp = 3, kMsgAppResp = 4, kMsgVote = 5, kMsgVoteResp = 6,
-                  kMsgHeartbeat = 8, kMsgHeartbeatResp = 9, kMsgCheckQuorum = 12;
+                  kMsgHeartbeat = 8, kMsgHeartbeatResp = 9, kMsgCheckQuorum = 12, kMsgPreVote = 17, kMsgPreVoteResp = 18;
 constexpr uint8_t kOutNone = 0, kOutVoteResp = 1, kOutHeartbeatResp = 2, kOutCampaign = 3, kOutBecameLeader = 4,
                   kOutProgress = 5, kOutBcastHeartbeat = 6, kOutAppend = 7, kOutAppended = 8, kOutDeferred = 9, kOutSkipped = 10,
-                  kOutHeld = 11, kOutProposed = 12, kOutForward = 13;
+                  kOutHeld = 11, kOutProposed = 12, kOutForward = 13, kOutPreCampaign = 14, kOutPreVoteResp = 15, kOutTermResp = 16;
 constexpr uint8_t kMsgfEntries = 0x80, kMsgfBarrier = 0x40, kMsgfHold = 0x20, kMsgfSkip = 0x10;  // raftq_msg_t._pad[1]: RAFTQ_MSGF_*
 constexpr uint8_t kFlagHardState = 1, kFlagCommitted = 2, kFlagUpdated = 4, kFlagSteppedDown = 8;
 constexpr uint8_t kFlagAnswered = 0x10;  // RAFTQ_OUTF_ANSWERED: the messages the result calls for were built on the device
@@ -129,9 +131,13 @@ struct RespRec {
 };
 static_assert(sizeof(RespRec) == 48, "record layout");
 constexpr uint8_t kFollower = 0, kCandidate = 1, kLeader = 2;
+constexpr uint8_t kPreCandidate = 3;  // RAFTQ_ROLE_PRE_CANDIDATE: only under raftq_set_pre_vote; every other walk takes it for a follower without a leader
 
 // result record i, in the handle's format.  Compact drops group and addressee (= msgs[i].group / .from) and folds
 // log_term / last_index into one slot: log_term is only set by the two result types whose index IS last_index.
+// PV: the *_cq_* walks' form, in which RAFTQ_OUT_PRE_CAMPAIGN (raftq_set_pre_vote) is packed as RAFTQ_OUT_CAMPAIGN is; the other
+// walks never give that type and keep the form they had.
+template <bool PV = false>
 __device__ __forceinline__ void put_result(void* out, uint64_t i, const StepOutRec& o, uint8_t fmt) {
   if (fmt == kFmtFull) {
     static_cast<StepOutRec*>(out)[i] = o;
@@ -141,7 +147,7 @@ __device__ __forceinline__ void put_result(void* out, uint64_t i, const StepOutR
     StepOutS c;
     c.term = o.term;
     c.index = o.index;
-    c.commit = o.type == kOutCampaign ? o.log_term : o.commit;
+    c.commit = (o.type == kOutCampaign || (PV && o.type == kOutPreCampaign)) ? o.log_term : o.commit;
     c.vote = (uint8_t)o.vote;
     c.lead = (uint8_t)o.lead;
     c.type = o.type;
@@ -156,7 +162,7 @@ __device__ __forceinline__ void put_result(void* out, uint64_t i, const StepOutR
   c.term = o.term;
   c.index = o.index;
   c.commit = o.commit;
-  c.aux = (o.type == kOutCampaign || o.type == kOutBecameLeader) ? o.log_term : o.last_index;
+  c.aux = (o.type == kOutCampaign || o.type == kOutBecameLeader || (PV && o.type == kOutPreCampaign)) ? o.log_term : o.last_index;
   c.vote = (uint8_t)o.vote;
   c.lead = (uint8_t)o.lead;
   c.type = o.type;
@@ -215,8 +221,9 @@ __device__ __forceinline__ uint64_t entry_count(const MsgRec& m, uint8_t recs) {
 // malformed there.
 // cq (raftq_set_check_quorum): RAFTQ_MSG_CHECK_QUORUM is a known, local kind in a caller's own records -- never in a record a
 // decoder made of a peer's frame.
+// pv (raftq_set_pre_vote): MsgPreVote and MsgPreVoteResp are known kinds, a peer's like MsgVote and MsgVoteResp, in every kind of record.
 __device__ __forceinline__ RecClass classify(const MsgRec& m, uint64_t n_groups, uint32_t n_peers, bool msg_flags, uint8_t recs, bool props,
-                                             bool cq = false) {
+                                             bool cq = false, bool pv = false) {
   const uint8_t fl = msg_flags ? m.pad[1] : (uint8_t)0;
   if (fl & kMsgfSkip) return kSkip;
   if (m.group >= n_groups) return kBad;
@@ -226,7 +233,7 @@ __device__ __forceinline__ RecClass classify(const MsgRec& m, uint64_t n_groups,
     return props && recs != kRecsWire && (fl & kMsgfEntries) != 0 && entry_count(m, recs) != 0 && m.from < n_peers ? kTake : kBad;
   const bool local = t == kMsgHup || t == kMsgBeat || (t == kMsgCheckQuorum && cq && recs == kRecsCaller);
   const bool known = local || t == kMsgApp || t == kMsgAppResp || t == kMsgVote || t == kMsgVoteResp ||
-                     t == kMsgHeartbeat || t == kMsgHeartbeatResp;
+                     t == kMsgHeartbeat || t == kMsgHeartbeatResp || (pv && (t == kMsgPreVote || t == kMsgPreVoteResp));
   if (!known || (!local && m.from >= n_peers)) return kBad;
   // records decoded on the device from stream frames (raftq_step_submit_wire) also carry the addressee's slot and the
   // decoder's flags in the two pad bytes: a frame that did not parse, or one addressed to no peer of this cluster, fails
@@ -249,11 +256,11 @@ static __global__ __launch_bounds__(kBlock) void step_keys_kernel(const MsgRec* 
                                                                   uint32_t* __restrict__ order, uint64_t n,
                                                                   uint64_t n_groups, uint32_t n_peers,
                                                                   unsigned int* bad, bool msg_flags, uint8_t recs,
-                                                                  void* __restrict__ out, uint8_t compact, bool props, bool cq) {
+                                                                  void* __restrict__ out, uint8_t compact, bool props, bool cq, bool pv) {
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   bool is_bad = false;
   if (i < n) {
-    const RecClass c = classify(msgs[i], n_groups, n_peers, msg_flags, recs, props, cq);
+    const RecClass c = classify(msgs[i], n_groups, n_peers, msg_flags, recs, props, cq, pv);
     is_bad = c == kBad;
     // a skipped record sorts behind every group (the key range has room for n_groups itself) and is answered here
     keys[i] = c == kTake ? msgs[i].group : c == kSkip ? n_groups : 0;  // (bad: keep the sort's key range valid)
@@ -604,25 +611,71 @@ struct NodeT {
     }
     const uint32_t q = quorum();
     bool handled = false;
+    bool campaigns = false, won = false;  // CQ form only: campaign() / becomeLeader are due (one copy of each, behind the role arms)
     if (m.type == kMsgHup) {
       handled = true;
       if (role != kLeader) {  // campaign()
-        become_candidate();
-        uint32_t gr, rec;
-        poll(a.self, true, gr, rec);
-        if (gr == q) { become_leader(); o.type = kOutBecameLeader; }
-        else o.type = kOutCampaign;
-        o.index = last_index;
-        o.log_term = last_term;
+        if constexpr (CQ) {
+          // PreVote: becomePreCandidate -- no term, vote, Match, gate or activity word moves; the pre-election's grants use the vote
+          // word.  An own grant that is the quorum already goes straight on to the campaign, which starts from reset() as always.
+          // (The CQ form runs campaign() in ONE place, behind the role arms, for MsgHup and for a won pre-election.)
+          campaigns = true;
+          if (a.pv) {
+            role = kPreCandidate;
+            lead = 0;
+            elapsed_reset = true;  // CHOICE: zeroed as Step's MsgHup always has
+            set_votes(0);
+            uint32_t gr, rec;
+            poll(a.self, true, gr, rec);
+            if (gr != q) {
+              campaigns = false;
+              o.type = kOutPreCampaign; o.index = last_index; o.log_term = last_term;
+            }
+          }
+        } else {
+          become_candidate();
+          uint32_t gr, rec;
+          poll(a.self, true, gr, rec);
+          if (gr == q) { become_leader(); o.type = kOutBecameLeader; }
+          else o.type = kOutCampaign;
+          o.index = last_index;
+          o.log_term = last_term;
+        }
       }
     } else if (m.term != 0) {
       if (m.term > term) {
         // checkQuorum: a MsgVote inside the lease is ignored -- no term change, no answer (a partitioned node coming back)
-        bool leased = false;
-        if constexpr (CQ) leased = m.type == kMsgVote && in_lease();
-        if (leased) handled = true;
-        else become_follower(m.term, m.type == kMsgVote ? 0u : m.from + 1);
-      } else if (m.term < term) handled = true;  // stale: ignored
+        // PreVote: a MsgPreVote inside the lease likewise; outside it, and a granting MsgPreVoteResp, change no term and no role; a
+        // rejecting MsgPreVoteResp makes a follower without a leader (CHOICE: its sender is no leader)
+        if constexpr (CQ) {
+          const bool leased = (m.type == kMsgVote || (a.pv && m.type == kMsgPreVote)) && in_lease();
+          const bool keep = a.pv && (m.type == kMsgPreVote || (m.type == kMsgPreVoteResp && !m.reject));
+          if (leased) handled = true;
+          else if (!keep) become_follower(m.term, (m.type == kMsgVote || (a.pv && m.type == kMsgPreVoteResp)) ? 0u : m.from + 1);
+        } else {
+          become_follower(m.term, m.type == kMsgVote ? 0u : m.from + 1);
+        }
+      } else if (m.term < term) {
+        handled = true;  // stale: ignored
+        // PreVote: ... but for a MsgPreVote, which is rejected with the own term, and a stale leader's MsgApp / MsgHeartbeat, which
+        // is told the term it missed (nothing changes, no clock is reset, a barrier on it holds nobody up)
+        if constexpr (CQ) {
+          if (a.pv) {
+            if (m.type == kMsgPreVote) { o.type = kOutPreVoteResp; o.reject = 1; o.index = term; }
+            else if (m.type == kMsgApp || m.type == kMsgHeartbeat) o.type = kOutTermResp;
+          }
+        }
+      }
+    }
+    // PreVote: a MsgPreVote that got this far is answered by one rule in every role, and changes nothing
+    if constexpr (CQ) {
+      if (!handled && a.pv && m.type == kMsgPreVote) {
+        handled = true;
+        const bool up_to_date = m.log_term > last_term || (m.log_term == last_term && m.index >= last_index);
+        o.type = kOutPreVoteResp;
+        if ((vote == 0 || m.term > term || vote == m.from + 1) && up_to_date) o.index = m.term;
+        else { o.reject = 1; o.index = term; }
+      }
     }
     if (!handled) {
       if (role == kLeader) {
@@ -679,7 +732,7 @@ struct NodeT {
           o.type = kOutProgress;
           o.index = match(m.from);
         }
-      } else if (role == kCandidate) {
+      } else if (role == kCandidate || (CQ && a.pv && role == kPreCandidate)) {
         if (m.type == kMsgApp) {
           become_follower(term, m.from + 1);
           handle_append(m, o);
@@ -689,16 +742,31 @@ struct NodeT {
           o.type = kOutHeartbeatResp;
         } else if (m.type == kMsgVote) {
           o.type = kOutVoteResp; o.reject = 1;
-        } else if (m.type == kMsgVoteResp) {
+        } else if (m.type == kMsgVoteResp || (CQ && m.type == kMsgPreVoteResp)) {
           uint32_t gr, rec;
-          poll(m.from, !m.reject, gr, rec);
           // upstream's equality (`switch r.q()`), MASKED too: a mask that shrinks in the middle of an election can step over the
           // equal count -- upstream's behaviour, and the election timer's to repair
-          if (gr == q) {
-            become_leader();
-            o.type = kOutBecameLeader; o.index = last_index; o.log_term = last_term;
-          } else if (rec - gr == q) {
-            become_follower(term, 0);
+          if constexpr (CQ) {
+            // PreVote: a pre-candidate polls MsgPreVoteResp and ignores MsgVoteResp, a candidate the other way round.  A won
+            // pre-election is the campaign MsgHup runs without the switch (behind the role arms); a lost one is a lost election's
+            // becomeFollower(term, None) -- Term and Vote are kept
+            if ((m.type == kMsgPreVoteResp) == (role == kPreCandidate)) {
+              poll(m.from, !m.reject, gr, rec);
+              if (gr == q) {
+                if (role == kPreCandidate) campaigns = true;
+                else won = true;
+              } else if (rec - gr == q) {
+                become_follower(term, 0);
+              }
+            }
+          } else {
+            poll(m.from, !m.reject, gr, rec);
+            if (gr == q) {
+              become_leader();
+              o.type = kOutBecameLeader; o.index = last_index; o.log_term = last_term;
+            } else if (rec - gr == q) {
+              become_follower(term, 0);
+            }
           }
         }
       } else {
@@ -718,6 +786,20 @@ struct NodeT {
           o.type = kOutForward;  // stepFollower MsgProp: `m.To = r.lead; r.send(m)` -- the one result addressed to somebody else
         }
       }
+    }
+    if constexpr (CQ) {
+      if (campaigns) {  // raft.campaign: becomeCandidate and the own grant, which may be the quorum
+        become_candidate();
+        uint32_t gr, rec;
+        poll(a.self, true, gr, rec);
+        won = gr == q;
+        o.type = kOutCampaign;
+      }
+      if (won) {
+        become_leader();
+        o.type = kOutBecameLeader;
+      }
+      if (campaigns || won) { o.index = last_index; o.log_term = last_term; }
     }
     if (a.msg_flags && o.type == kOutAppend && m.type == kMsgApp && (m.pad[1] & kMsgfBarrier)) held = true;
     o.group = g; o.term = term; o.commit = committed; o.last_index = last_index;
@@ -764,7 +846,7 @@ static __global__ __launch_bounds__(kBlock) void step_link_kernel(const MsgRec* 
                                                                   uint64_t n_groups, uint32_t n_peers, bool msg_flags, uint8_t recs,
                                                                   NodeRec* rec, uint32_t* __restrict__ next,
                                                                   unsigned int* bad, unsigned int* stall,
-                                                                  void* __restrict__ out, uint8_t compact, CopyRide ride, bool props, bool cq) {
+                                                                  void* __restrict__ out, uint8_t compact, CopyRide ride, bool props, bool cq, bool pv) {
   if (blockIdx.x < ride.blocks) {
     copy_ride(ride);
     return;
@@ -772,7 +854,7 @@ static __global__ __launch_bounds__(kBlock) void step_link_kernel(const MsgRec* 
   const uint64_t i = (uint64_t)(blockIdx.x - ride.blocks) * kBlock + threadIdx.x;
   bool is_bad = false, too_long = false;
   if (i < n) {
-    const RecClass c = classify(msgs[i], n_groups, n_peers, msg_flags, recs, props, cq);
+    const RecClass c = classify(msgs[i], n_groups, n_peers, msg_flags, recs, props, cq, pv);
     is_bad = c == kBad;
     if (c == kTake) {
       NodeRec* r = rec + msgs[i].group;  // three atomics on one line

@@ -483,6 +483,12 @@ class QuorumEngine:
         property of the handle (no batch may be in flight).  Turning it on allocates the activity state, zeroed."""
         self._chk(self._lib.raftq_set_check_quorum(self._h, int(on)))
 
+    def set_pre_vote(self, on=True) -> None:
+        """raftq_set_pre_vote (include/raftq.h "PreVote"): Step's MsgHup starts a pre-election (role 3, OUT_PRE_CAMPAIGN), types 17
+        and 18 are stepped, and a stale leader's MsgApp / MsgHeartbeat is answered OUT_TERM_RESP.  Requires set_check_quorum; a
+        property of the handle (no batch may be in flight)."""
+        self._chk(self._lib.raftq_set_pre_vote(self._h, int(on)))
+
     def load_activity(self, active: Optional[np.ndarray] = None, lead_elapsed: Optional[np.ndarray] = None) -> None:
         """active [G] u16 (bit p = peer p answered since the last check), lead_elapsed [G] u32 (a leader's electionElapsed)"""
         a = None if active is None else np.ascontiguousarray(active, dtype=np.uint16)

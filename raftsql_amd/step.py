@@ -20,6 +20,7 @@ from .engine import QuorumEngine, _ptr
 MSG_HUP, MSG_BEAT, MSG_APP, MSG_APP_RESP, MSG_VOTE, MSG_VOTE_RESP, MSG_HEARTBEAT, MSG_HEARTBEAT_RESP = 0, 1, 3, 4, 5, 6, 8, 9
 MSG_PROP = 2  # a follower's forwarded proposal: stepped only under set_step_props (MSGF_ENTRIES + its count in _resv)
 MSG_CHECK_QUORUM = 12  # local: a leader's check failed in tick() (collect_checks): stepped only under set_check_quorum
+MSG_PRE_VOTE, MSG_PRE_VOTE_RESP = 17, 18  # a peer's pre-election (MsgVote's fields): stepped only under set_pre_vote
 MSG_TYPES = (MSG_HUP, MSG_BEAT, MSG_APP, MSG_APP_RESP, MSG_VOTE, MSG_VOTE_RESP, MSG_HEARTBEAT, MSG_HEARTBEAT_RESP)
 
 OUT_NONE, OUT_VOTE_RESP, OUT_HEARTBEAT_RESP, OUT_CAMPAIGN, OUT_BECAME_LEADER, OUT_PROGRESS, OUT_BCAST_HEARTBEAT, OUT_APPEND = range(8)
@@ -27,12 +28,15 @@ OUT_APPENDED = 8  # MsgApp with MSGF_ENTRIES that appended at the tail: Step did
 OUT_DEFERRED = 9  # not applied: an earlier MsgApp of the group with MSGF_BARRIER was left to the caller (OUT_APPEND)
 OUT_SKIPPED, OUT_HELD = 10, 11  # MSGF_SKIP: nobody's, nothing looked at; MSGF_HOLD: the caller's (MsgProp), the rest of its group deferred
 OUT_PROPOSED, OUT_FORWARD = 12, 13  # set_step_props: the leader took a MsgProp (index = first new index); a follower's goes on to lead - 1
+# set_pre_vote: became pre-candidate (send MsgPreVote at term + 1); send MsgPreVoteResp{Term: index}; tell a stale leader the term
+OUT_PRE_CAMPAIGN, OUT_PRE_VOTE_RESP, OUT_TERM_RESP = 14, 15, 16
 MSGF_SKIP, MSGF_HOLD = 0x10, 0x20
 MSGF_BARRIER = 0x40  # on a MsgApp: if it is answered OUT_APPEND, the group's later messages of the batch are deferred
 MSGF_ENTRIES = 0x80  # msgs["_pad"][:, 1]: _resv = number of entries, reject_hint = the last one's term (raftq_step.h)
 OUTF_HARDSTATE, OUTF_COMMITTED, OUTF_UPDATED, OUTF_STEPPED_DOWN = 1, 2, 4, 8
 
 ROLE_FOLLOWER, ROLE_CANDIDATE, ROLE_LEADER = 0, 1, 2
+ROLE_PRE_CANDIDATE = 3  # only under set_pre_vote
 
 MSG_DT = np.dtype([("group", "<u8"), ("term", "<u8"), ("log_term", "<u8"), ("index", "<u8"), ("commit", "<u8"),
                    ("reject_hint", "<u8"), ("from", "<u4"), ("type", "u1"), ("reject", "u1"), ("_pad", "u1", (2,)),
@@ -82,7 +86,7 @@ def expand_compact(msgs: np.ndarray, recs: np.ndarray) -> np.ndarray:
     o["group"], o["to"] = msgs["group"], msgs["from"]
     for k in ("term", "index", "commit", "vote", "lead", "type", "reject", "flags", "role"):
         o[k] = recs[k]
-    tip = (recs["type"] == OUT_CAMPAIGN) | (recs["type"] == OUT_BECAME_LEADER)  # index IS the last index there
+    tip = (recs["type"] == OUT_CAMPAIGN) | (recs["type"] == OUT_BECAME_LEADER) | (recs["type"] == OUT_PRE_CAMPAIGN)  # index IS the last index there
     o["log_term"] = np.where(tip, recs["aux"], np.where(recs["type"] == OUT_PROPOSED, recs["term"], 0))
     o["last_index"] = np.where(tip, recs["index"], recs["aux"])
     fwd = recs["type"] == OUT_FORWARD  # the one result whose addressee is not the sender: the leader's slot
@@ -93,8 +97,8 @@ def expand_compact(msgs: np.ndarray, recs: np.ndarray) -> np.ndarray:
 def expand_short(msgs: np.ndarray, recs: np.ndarray, last_index: np.ndarray, committed: np.ndarray) -> np.ndarray:
     """raftq_step_out_s_t[] (32 bytes) + the batch it answers + every group's lastIndex / committed BEFORE the batch ->
     raftq_step_out_t[], exactly (include/raftq_step.h): what the 32-byte record leaves out is tracked per group across the
-    batch -- lastIndex only moves with a result whose `index` IS the last index, a campaign moves no commit index and carries
-    its log_term in that slot, a new leader's log_term is its term; behind an OUT_PROPOSED the tail is index + n - 1 (n = the
+    batch -- lastIndex only moves with a result whose `index` IS the last index, a campaign (and a pre-campaign) moves no commit
+    index and carries its log_term in that slot, a new leader's log_term is its term; behind an OUT_PROPOSED the tail is index + n - 1 (n = the
     count in the reader's own record, msgs["_resv"]'s low half) and its log_term is its term; an OUT_FORWARD goes to lead - 1.
     (A loop over the records: tests and tools, not a hot path.)"""
     o = np.zeros(len(recs), dtype=OUT_DT)
@@ -113,9 +117,10 @@ def expand_short(msgs: np.ndarray, recs: np.ndarray, last_index: np.ndarray, com
             li[g] = int(r["index"])
         elif t == OUT_PROPOSED:
             li[g] = int(r["index"]) + (int(msgs["_resv"][i]) & 0xFFFFFFFF) - 1
-        if t != OUT_CAMPAIGN:
+        camp = t in (OUT_CAMPAIGN, OUT_PRE_CAMPAIGN)
+        if not camp:
             co[g] = int(r["commit"])
-        o[i] = (g, r["term"], r["index"], r["commit"] if t == OUT_CAMPAIGN else (r["term"] if t in (OUT_BECAME_LEADER, OUT_PROPOSED) else 0), co[g], li[g],
+        o[i] = (g, r["term"], r["index"], r["commit"] if camp else (r["term"] if t in (OUT_BECAME_LEADER, OUT_PROPOSED) else 0), co[g], li[g],
                 int(r["lead"]) - 1 if t == OUT_FORWARD else msgs["from"][i], r["vote"], r["lead"], t, r["reject"], r["flags"], r["role"])
     return o
 
