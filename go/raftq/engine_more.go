@@ -176,6 +176,27 @@ func (e *Engine) TickCollectLists(flags uint, hupCap, beatCap uint64) (TickLists
 	return t, nil
 }
 
+// TickSetChecks opens TickCollect, TickCollectLists, TickFrames and TickElectFrames on an engine with SetCheckQuorum on (the last
+// under SetPreVote too): chkCap > 0 is how many ids of groups whose check failed those calls list at most (LastTickChecks);
+// 0, the default, leaves them refusing such an engine (raftq_tick_set_checks).
+func (e *Engine) TickSetChecks(chkCap uint64) error {
+	return e.err(C.raftq_tick_set_checks(e.h, C.uint64_t(chkCap)))
+}
+
+// LastTickChecks is the third list the last fused Tick call left under TickSetChecks: the first min(total, chkCap) groups whose
+// check failed, ascending, read in place (page-locked memory, valid until the next call on the engine), and their total.
+func (e *Engine) LastTickChecks() (checks []uint32, total uint64, err error) {
+	var p *C.uint32_t
+	var n, tot C.uint64_t
+	if err := e.err(C.raftq_last_tick_checks(e.h, &p, &n, &tot)); err != nil {
+		return nil, 0, err
+	}
+	if n > 0 {
+		checks = unsafe.Slice((*uint32)(unsafe.Pointer(p)), int(n))
+	}
+	return checks, uint64(tot), nil
+}
+
 // Campaign is becomeCandidate for the groups named (distinct).
 func (e *Engine) Campaign(groups []uint64, selfPeer uint32) error {
 	if len(groups) == 0 {

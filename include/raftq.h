@@ -353,8 +353,28 @@ int raftq_last_tick_lists(raftq_t* h, const uint32_t** hups, uint64_t* n_hups, c
  *
  * What the switch closes (RAFTQ_ESTATE, "check quorum" in the text): raftq_tick_collect, raftq_tick_collect_lists,
  * raftq_tick_frames, raftq_tick_elect_frames (raftq_wire.h) and raftq_set_tick on a set holding such a member -- their beat lists
- * and device-built rounds do not know a suppressed beat.  raftq_campaign and raftq_load_roles do not touch the activity state. */
+ * and device-built rounds do not know a suppressed beat.  raftq_campaign and raftq_load_roles do not touch the activity state.
+ *
+ * What raftq_tick_set_checks opens again.  raftq_tick_set_checks(h, chk_cap) with chk_cap > 0 opts a handle with the switch on back
+ * in to four of them: raftq_tick_collect, raftq_tick_collect_lists, raftq_tick_frames and raftq_tick_elect_frames run the Tick above
+ * (the same kernel raftq_tick launches) and leave the hup and beat results they always left.  A group whose check failed has action
+ * 3 and NO beat: it is absent from the beat list, from the RAFTQ_TICK_BEAT_BITMAP bitmap, from *n_beat and from the heartbeat round.
+ * The three in-place forms also leave the groups whose check failed as a THIRD list, raftq_last_tick_checks: the first
+ * min(total, chk_cap) ids, ascending, 4 bytes each, in the same page-locked buffer as the hup and beat ids, valid until the next
+ * call on the handle and covered by the one wait the call makes anyway.  Groups beyond chk_cap -- and every group after
+ * raftq_tick_collect, the copying form, which has no slot for them -- come from raftq_collect_checks, which reads the bitmap of the
+ * last Tick whichever call made it.  Every allocation of the third list is made before the Tick is enqueued: a call that fails has
+ * not ticked.  raftq_tick_elect_frames' election round is then Step's own MsgHup arm under the switch (raftq_wire.h): a campaign's
+ * reset() clears the activity word too.  chk_cap == 0 is the default: every call is as described above, refusal texts included.  No
+ * effect while raftq_set_check_quorum is off.  The handle must be idle (RAFTQ_ESTATE with a Step batch in flight).  A property of
+ * the handle: raftq_clone_state does not copy it.  raftq_set_tick keeps refusing a set that holds a member with the switch on. */
 int raftq_set_check_quorum(raftq_t* h, int on);
+int raftq_tick_set_checks(raftq_t* h, uint64_t chk_cap);
+/* the third list of the last raftq_tick_collect_lists / raftq_tick_frames / raftq_tick_elect_frames under raftq_tick_set_checks:
+ * *checks = the ids, *n_listed = min(*n_total, chk_cap), *n_total = the groups whose check failed in that Tick; any pointer argument
+ * may be NULL.  RAFTQ_ESTATE when the last Tick call on the handle left no third list: none yet; a raftq_tick or raftq_tick_collect
+ * since; a fused call made while the switch or raftq_set_check_quorum was off; raftq_tick_set_checks itself since. */
+int raftq_last_tick_checks(raftq_t* h, const uint32_t** checks, uint64_t* n_listed, uint64_t* n_total);
 /* bulk load / read-back ([G] each; either pointer may be NULL: that half is left alone / not read).  RAFTQ_ESTATE without the
  * switch; a bit at or above N, or a lead_elapsed above 65535: RAFTQ_EINVAL, nothing loaded.  raftq_clone_state copies the arrays
  * when both handles hold them. */
@@ -385,7 +405,11 @@ int raftq_collect_checks(raftq_t* h, uint64_t* groups, uint64_t cap, uint64_t* n
  *
  * What the switch closes (RAFTQ_ESTATE, "pre vote" in the text): raftq_tick_elect_frames (raftq_wire.h), whose device-built round
  * makes a MsgHup a becomeCandidate and sends MsgVote (it is closed to CheckQuorum already).  raftq_campaign stays the real
- * becomeCandidate.  raftq_node does not turn the switch on. */
+ * becomeCandidate.  raftq_node does not turn the switch on.
+ *
+ * raftq_tick_set_checks(h, chk_cap > 0) ("CheckQuorum" above) opens raftq_tick_elect_frames under this switch as well: its round is
+ * then Step's MsgHup arm with the switch on -- a pre-election: role 3, no term moves, camp[r] is RAFTQ_OUT_PRE_CAMPAIGN and the frames
+ * are MsgPreVote at term + 1 (raftq_wire.h). */
 int raftq_set_pre_vote(raftq_t* h, int on);
 
 /* becomeCandidate for `n` distinct groups: role = candidate, elapsed = 0, votes

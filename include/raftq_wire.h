@@ -516,6 +516,11 @@ int raftq_respond_set_props(raftq_t* h, int on);
  * bytes.  Whether self is a member is not asked: a leader whose own bit is clear still beats its members.  A built group with an
  * empty mask gives no frame.  With the switch on and no masks loaded the call is what it always was.
  *
+ * Under raftq_set_check_quorum (raftq.h "CheckQuorum") the call is RAFTQ_ESTATE ("check quorum" in the text) unless
+ * raftq_tick_set_checks(h, chk_cap > 0) opened it.  Then the Tick is the switch's: a leader group whose check failed has action 3, is
+ * no MsgBeat group of this Tick -- not in *n_beat, the list or the bitmap -- and gets no frame; the groups whose check failed are
+ * raftq_last_tick_checks' list, under the same wait.
+ *
  * Refused before anything is enqueued -- a refused call has not ticked:
  *   RAFTQ_EINVAL  cap < beat_cap * (N - 1) * RAFTQ_RESPOND_FRAME_MAX (the largest payload-free frame, above);
  *                 out, frame_off or peer_off not page-locked and 16-byte aligned; N < 2; an unknown flag;
@@ -569,6 +574,19 @@ int raftq_tick_frames(raftq_t* h, unsigned flags, uint64_t hup_cap, uint64_t bea
  *     r.prs; the slots of the other peers have zero length.
  * Both sections stay positional, as raftq_tick_frames says: peer_off[0 .. 2 N + 1] is what it is without masks, frame_off keeps
  * (beat_cap + hup_cap) * (N - 1) + 1 entries, counts->n_msgs is the number of frames that have bytes.
+ *
+ * Under raftq_set_check_quorum and raftq_set_pre_vote (raftq.h) the call is RAFTQ_ESTATE ("pre vote", else "check quorum" in the text)
+ * unless raftq_tick_set_checks(h, chk_cap > 0) opened it.  Then the Tick and the heartbeat section are raftq_tick_frames' under that
+ * switch, and Step(MsgHup) is Step's with the switches on (raftq_step.h "CheckQuorum in Step", "PreVote in Step") -- the device calls
+ * the arm the walks call:
+ *   raftq_set_pre_vote off: the campaign above; its reset() also zeroes the group's activity word.  Over masks a one-voter group
+ *     wins at once, as above.
+ *   raftq_set_pre_vote on: becomePreCandidate -- role 3, lead = None, elapsed = 0, the vote word cleared and self's grant recorded;
+ *     term, vote, the Match rows, the gate and the activity word do not move.  camp[r] is the 32-byte RAFTQ_OUT_PRE_CAMPAIGN record
+ *     (index = lastIndex, commit = lastTerm, no RAFTQ_OUTF_HARDSTATE) with RAFTQ_OUTF_ANSWERED, and the vote section holds
+ *     MsgPreVote{type 17, term = Term + 1, index = lastIndex, log_term = lastTerm} to every peer slot p != self, or to every member
+ *     p != self over masks.  A group whose own grant is the quorum (one voter, over masks) goes straight on to the real campaign
+ *     and the win: RAFTQ_OUT_BECAME_LEADER without RAFTQ_OUTF_ANSWERED and no frame, as above.
  *
  * Refused before anything is enqueued -- a refused call has neither ticked nor campaigned:
  *   RAFTQ_EINVAL  cap < (beat_cap + hup_cap) * (N - 1) * RAFTQ_RESPOND_FRAME_MAX; camp, out, frame_off or peer_off not page-locked

@@ -94,6 +94,8 @@ _SIGS = [
     ("raftq_set_timers", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint64]),
     ("raftq_load_roles", C.c_int, [_H, C.c_void_p, C.c_void_p]),
     ("raftq_tick_set_voters", C.c_int, [_H, C.c_int]),
+    ("raftq_tick_set_checks", C.c_int, [_H, C.c_uint64]),
+    ("raftq_last_tick_checks", C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("raftq_tick", C.c_int, [_H, C.POINTER(TickCounts)]),
     ("raftq_read_tick", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("raftq_collect_hups", C.c_int, [_H, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),

@@ -47,6 +47,7 @@ def lib_sources() -> list[str]:
         os.path.join(CSRC, "raftq_step_walk_kernels.inc"),
         os.path.join(CSRC, "raftq_sweep_voters_tile.inc"),
         os.path.join(CSRC, "raftq_tick_voters_block.inc"),
+        os.path.join(CSRC, "raftq_tick_lists32.inc"),
         os.path.join(CSRC, "raftq_internal.hpp"),
         os.path.join(CSRC, "raftq_buffers.hpp"),
         os.path.join(CSRC, "raftq_step_rounds.hpp"),

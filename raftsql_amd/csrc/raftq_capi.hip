@@ -469,7 +469,7 @@ void raftq_destroy(raftq_t* h) {
   // every wait is over: memory may go
   raftq_buf::free_device(h->match, h->committed[0], h->committed[1], h->first_idx, h->votes, h->voters, h->outcome, h->changed_bits,
                          h->partials, h->offsets, h->self_max, h->anchor, h->moff, h->claim, h->delta_bad, h->role, h->elapsed, h->action, h->hup_bits,
-                         h->beat_bits, h->tick_partials, h->tick_offsets2, h->cq, h->chk_bits);
+                         h->beat_bits, h->tick_partials, h->tick_offsets2, h->tick_offsets3, h->cq, h->chk_bits);
   raftq_buf::free_host(h->h_partials, h->h_total);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -1072,19 +1072,20 @@ int raftq_detail::ensure_tick_state(raftq_t* h) {
   return RAFTQ_OK;
 }
 
-int raftq_detail::refuse_check_quorum(raftq_t* h, const char* who) {
-  if (!h->cq) return RAFTQ_OK;
+int raftq_detail::refuse_check_quorum(raftq_t* h, const char* who, bool fused) {
+  if (!h->cq || (fused && h->tick_chk_cap != 0)) return RAFTQ_OK;
   return fail(h, RAFTQ_ESTATE, std::string(who) + ": raftq_set_check_quorum is on (check quorum): this call's beat lists and device-built rounds do not "
                                                   "know a beat suppressed by a failing check -- use raftq_tick with raftq_collect_hups / _beats / _checks");
 }
-int raftq_detail::refuse_pre_vote(raftq_t* h, const char* who) {
-  if (!h->pre_vote) return RAFTQ_OK;
+int raftq_detail::refuse_pre_vote(raftq_t* h, const char* who, bool fused) {
+  if (!h->pre_vote || (fused && h->tick_chk_cap != 0)) return RAFTQ_OK;
   return fail(h, RAFTQ_ESTATE, std::string(who) + ": raftq_set_pre_vote is on (pre vote): this call's device-built round makes a MsgHup a becomeCandidate and "
                                                   "sends MsgVote -- step the MsgHup (RAFTQ_OUT_PRE_CAMPAIGN) and send MsgPreVote");
 }
 constexpr uint32_t kCheckQuorumMaxTick = 0xffffu;  // lead_elapsed shares its word with the activity bits (raftq_t::cq)
 
 static int ensure_tick_offsets2(raftq_t* h, uint64_t nw);
+static int ensure_tick_offsets3(raftq_t* h);
 static hipError_t wait_turn(raftq_t* h, uint64_t flag_epoch, int kind = 0);
 
 extern "C" {
@@ -1234,6 +1235,13 @@ int raftq_tick_set_voters(raftq_t* h, int on) {
   return RAFTQ_OK;
 }
 
+int raftq_tick_set_checks(raftq_t* h, uint64_t chk_cap) {
+  if (int rc = use_device_idle(h, "raftq_tick_set_checks")) return rc;
+  h->tick_chk_cap = chk_cap;
+  h->tl_valid = h->tl_chk_valid = false;  // (the lists a call left are valid until the next call on the handle -- this is one)
+  return RAFTQ_OK;
+}
+
 int raftq_bcast_set_voters(raftq_t* h, int on) {
   if (int rc = use_device_idle(h, "raftq_bcast_set_voters")) return rc;
   if (on != 0 && on != 1)
@@ -1276,7 +1284,7 @@ int raftq_tick(raftq_t* h, raftq_tick_counts_t* counts) {
   if (int rc = tick_voters_ready(h, "raftq_tick")) return rc;
   if (int rc = tick_check_ready(h, "raftq_tick")) return rc;
   if (int rc = ensure_tick_state(h)) return rc;
-  h->tl_valid = false;  // (raftq_last_tick_lists must not hand out an older tick's lists as the last one's)
+  h->tl_valid = h->tl_chk_valid = false;  // (raftq_last_tick_lists must not hand out an older tick's lists as the last one's)
   launch_tick(h);
   HIPCHK(h, hipGetLastError());
   h->ticked = true;
@@ -1299,17 +1307,18 @@ int raftq_tick(raftq_t* h, raftq_tick_counts_t* counts) {
 // and two waits).  The lists land in the pinned advance buffer (8 bytes of its 24-byte entries each) and are copied out.
 int raftq_tick_collect(raftq_t* h, uint64_t* hups, uint64_t hup_cap, uint64_t* n_hup, uint64_t* beats, uint64_t beat_cap, uint64_t* n_beat) {
   if (int rc = use_device_idle(h, "raftq_tick_collect")) return rc;
-  if (int rc = raftq_detail::refuse_check_quorum(h, "raftq_tick_collect")) return rc;
+  if (int rc = raftq_detail::refuse_check_quorum(h, "raftq_tick_collect", true)) return rc;
   if (!n_hup || !n_beat) return fail(h, RAFTQ_EINVAL, "raftq_tick_collect: null count");
   if ((hup_cap && !hups) || (beat_cap && !beats)) return fail(h, RAFTQ_EINVAL, "raftq_tick_collect: null list with cap > 0");
   if (int rc = tick_voters_ready(h, "raftq_tick_collect")) return rc;
+  if (int rc = tick_check_ready(h, "raftq_tick_collect")) return rc;
   if (int rc = ensure_tick_state(h)) return rc;
   const uint64_t cap_h = std::min<uint64_t>(hup_cap, h->G), cap_b = std::min<uint64_t>(beat_cap, h->G);
   if (int rc = ensure_adv(h, (cap_h + cap_b + 2) / 3 + 2)) return rc;
   const uint64_t nw = h->gpad / 256;
   if (nw > (1u << 14))
     if (int rc = ensure_tick_offsets2(h, nw)) return rc;  // (before the Tick: a call that fails has not ticked)
-  h->tl_valid = false;  // raftq_last_tick_lists hands out the lists of the LAST tick, and this is a newer one
+  h->tl_valid = h->tl_chk_valid = false;  // raftq_last_tick_lists hands out the lists of the LAST tick, and this is a newer one
   launch_tick(h);
   h->ticked = true;
   const uint64_t *off_h = nullptr, *off_b = nullptr;
@@ -1342,22 +1351,31 @@ int raftq_tick_collect(raftq_t* h, uint64_t* hups, uint64_t hup_cap, uint64_t* n
 // In three steps (raftq_detail::tick_lists_*, raftq_internal.hpp), so that raftq_tick_frames (raftq_wire.hip) can put its own
 // kernels between the lists and the flag: what is checked and allocated, what is enqueued, the wait and what it leaves.
 int raftq_detail::tick_lists_prepare(raftq_t* h, const char* who, unsigned flags, uint64_t hup_cap, uint64_t beat_cap, TickLists* tl) {
-  if (int rc = refuse_check_quorum(h, who)) return rc;
+  if (int rc = refuse_check_quorum(h, who, true)) return rc;
   if (flags & ~RAFTQ_TICK_BEAT_BITMAP) return fail(h, RAFTQ_EINVAL, std::string(who) + ": unknown flag");
   if (int rc = tick_voters_ready(h, who)) return rc;
+  if (int rc = tick_check_ready(h, who)) return rc;
   if (int rc = ensure_tick_state(h)) return rc;
   const bool bitmap = flags & RAFTQ_TICK_BEAT_BITMAP;
   const uint64_t cap_h = std::min<uint64_t>(hup_cap, h->G), cap_b = bitmap ? 0 : std::min<uint64_t>(beat_cap, h->G);
   const uint64_t beat_at = (cap_h + 3) & ~3ull;  // the MsgBeat ids start on a 16-byte boundary (the lists leave in whole quads)
   const uint64_t map_off = ((beat_at + cap_b) * 4 + 255) / 256 * 256;
-  const uint64_t need = map_off + h->gpad / 8 + 256;
-  h->tl_valid = false;
+  // raftq_tick_set_checks: the ids of the failed checks behind the bitmap's place, on a 256-byte boundary
+  const uint64_t cap_c = tick_checks(h) ? std::min<uint64_t>(h->tick_chk_cap, h->G) : 0;
+  const uint64_t chk_off = (map_off + h->gpad / 8 + 255) / 256 * 256;
+  const uint64_t need = cap_c ? chk_off + cap_c * 4 + 256 : map_off + h->gpad / 8 + 256;
+  h->tl_valid = h->tl_chk_valid = false;
   HIPCHK(h, h->tl.grow(need, std::max<uint64_t>(need, 1 << 16), &h->stream));
   // every allocation is made BEFORE the Tick is enqueued: a call that fails has not ticked (an allocation failure
   // behind the tick kernel left the timers advanced and the MsgHup / MsgBeat groups of that tick unreported)
-  if (h->gpad / 256 > (1u << 14))
+  if (h->gpad / 256 > (1u << 14)) {
     if (int rc = ensure_tick_offsets2(h, h->gpad / 256)) return rc;
+    if (cap_c)
+      if (int rc = ensure_tick_offsets3(h)) return rc;
+  }
   *tl = TickLists{flags, cap_h, cap_b, beat_at, map_off, nullptr};
+  tl->cap_c = cap_c;
+  tl->chk_off = chk_off;
   return RAFTQ_OK;
 }
 
@@ -1373,6 +1391,7 @@ int raftq_detail::tick_lists_enqueue(raftq_t* h, TickLists* tl) {
     hipLaunchKernelGGL(scan_partials_kernel, dim3(1), dim3(1024), 0, h->stream, h->tick_partials, nw, h->tick_offsets2, h->d_total + 1, 1);
     off_h = h->offsets;
     off_b = h->tick_offsets2;
+    if (tl->cap_c) hipLaunchKernelGGL(scan_partials_kernel, dim3(1), dim3(1024), 0, h->stream, h->tick_partials, nw, h->tick_offsets3, h->d_total + 4, 2);
   }
   tl->off_beat = off_b;
   tl->off_h = off_h;
@@ -1382,7 +1401,16 @@ int raftq_detail::tick_lists_enqueue(raftq_t* h, TickLists* tl) {
   // one block of 1,024 groups per workgroup of the lists kernel.  Four (runs of ~1,600 ids instead of ~400 at the bench's density)
   // measured no better: 47.1 against 46.5 us a call -- 1.6 MB of ids take the link 34 us however they are cut
   const dim3 grid((unsigned)((nw + kWaves - 1) / kWaves));
-  if (bitmap)
+  if (tl->cap_c) {  // the three-list form: the failed checks' ids too (raftq_tick_set_checks; launch_tick ran tick_check_kernel)
+    const TickChecksArgs c{(const uint64_t*)h->chk_bits, (uint32_t*)((uint8_t*)h->tl.d + tl->chk_off), tl->cap_c,
+                           off_h ? (const uint64_t*)h->tick_offsets3 : nullptr};
+    if (bitmap)
+      hipLaunchKernelGGL((tick_lists32_checks_kernel<true>), grid, dim3(kBlock), 0, h->stream, (const uint64_t*)h->hup_bits, (const uint64_t*)h->beat_bits,
+                         (const uint4*)h->tick_partials, nw, hup_d, cap_h, beat_d, cap_b, map_d, h->d_total, off_h, off_b, c);
+    else
+      hipLaunchKernelGGL((tick_lists32_checks_kernel<false>), grid, dim3(kBlock), 0, h->stream, (const uint64_t*)h->hup_bits, (const uint64_t*)h->beat_bits,
+                         (const uint4*)h->tick_partials, nw, hup_d, cap_h, beat_d, cap_b, map_d, h->d_total, off_h, off_b, c);
+  } else if (bitmap)
     hipLaunchKernelGGL((tick_lists32_kernel<true>), grid, dim3(kBlock), 0, h->stream, (const uint64_t*)h->hup_bits, (const uint64_t*)h->beat_bits,
                        (const uint4*)h->tick_partials, nw, hup_d, cap_h, beat_d, cap_b, map_d, h->d_total, off_h, off_b);
   else
@@ -1409,8 +1437,8 @@ int raftq_detail::tick_lists_finish(raftq_t* h, const char* who, const TickLists
   if (check) {
     auto digest = [&]() {
       const volatile uint64_t* tot = (const volatile uint64_t*)h->h_total;
-      const uint64_t t0 = tot[0], t1 = tot[1];
-      uint64_t d = (t0 * 0x9E3779B97F4A7C15ull) ^ t1;
+      const uint64_t t0 = tot[0], t1 = tot[1], t2 = tl.cap_c ? tot[4] : 0;
+      uint64_t d = (t0 * 0x9E3779B97F4A7C15ull) ^ t1 ^ (t2 * 0x94D049BB133111EBull);
       const volatile uint32_t* ids = (const volatile uint32_t*)h->tl.h;
       const uint64_t nh = std::min<uint64_t>(t0, cap_h), nb = std::min<uint64_t>(t1, cap_b);
       for (uint64_t i = 0; i < nh; ++i) d = (d ^ ids[i]) * 0xBF58476D1CE4E5B9ull;
@@ -1418,6 +1446,11 @@ int raftq_detail::tick_lists_finish(raftq_t* h, const char* who, const TickLists
       if (bitmap) {
         const volatile uint64_t* mw = (const volatile uint64_t*)((const uint8_t*)h->tl.h + map_off);
         for (uint64_t i = 0; i < h->gpad / 64; ++i) d = (d ^ mw[i]) * 0xBF58476D1CE4E5B9ull;
+      }
+      if (tl.cap_c) {  // the third list
+        const volatile uint32_t* cw = (const volatile uint32_t*)((const uint8_t*)h->tl.h + tl.chk_off);
+        const uint64_t nc = std::min<uint64_t>(t2, tl.cap_c);
+        for (uint64_t i = 0; i < nc; ++i) d = (d ^ cw[i]) * 0xBF58476D1CE4E5B9ull;
       }
       return d;
     };
@@ -1434,6 +1467,12 @@ int raftq_detail::tick_lists_finish(raftq_t* h, const char* who, const TickLists
   h->tl_map_off = map_off;
   h->tl_flags = tl.flags;
   h->tl_valid = true;
+  if (tl.cap_c) {
+    h->tl_n_chk = h->h_total[4];
+    h->tl_chk_cap = tl.cap_c;
+    h->tl_chk_off = tl.chk_off;
+    h->tl_chk_valid = true;
+  }
   return RAFTQ_OK;
 }
 
@@ -1463,7 +1502,23 @@ int raftq_last_tick_lists(raftq_t* h, const uint32_t** hups, uint64_t* n_hups, c
   return RAFTQ_OK;
 }
 
+int raftq_last_tick_checks(raftq_t* h, const uint32_t** checks, uint64_t* n_listed, uint64_t* n_total) {
+  if (!h) return fail(nullptr, RAFTQ_EINVAL, "null handle");
+  if (!h->tl_valid || !h->tl_chk_valid)
+    return fail(h, RAFTQ_ESTATE, "raftq_last_tick_checks: no raftq_tick_collect_lists / raftq_tick_frames / raftq_tick_elect_frames under "
+                                 "raftq_tick_set_checks (with raftq_set_check_quorum on) before it");
+  if (checks) *checks = (const uint32_t*)((const uint8_t*)h->tl.h + h->tl_chk_off);
+  if (n_listed) *n_listed = std::min(h->tl_n_chk, h->tl_chk_cap);
+  if (n_total) *n_total = h->tl_n_chk;
+  return RAFTQ_OK;
+}
+
 }  // extern "C"
+static int ensure_tick_offsets3(raftq_t* h) {
+  if (h->tick_offsets3) return RAFTQ_OK;
+  HIPCHK(h, raftq_buf::alloc_device((void**)&h->tick_offsets3, (h->gpad / 256 + 1) * 8));
+  return RAFTQ_OK;
+}
 static int ensure_tick_offsets2(raftq_t* h, uint64_t nw) {
   if (h->tick_offsets2) return RAFTQ_OK;
   (void)nw;

@@ -56,7 +56,62 @@ __device__ __forceinline__ void vote_store(WireMsg* dst, uint64_t group, uint64_
 //     (and _COMMITTED when the commit moved) and NOT RAFTQ_OUTF_ANSWERED -- the caller appends the empty entry, as after Step.
 //     Nobody is asked: every vote slot of the group is a filler.
 //   otherwise: RAFTQ_OUT_CAMPAIGN as in the unmasked form, a MsgVote to every member p != self, fillers in the other slots.
+// ... of either election kind: type = kMsgVote or kMsgPreVote (the CQ entry points)
+__device__ __forceinline__ void vote_store(WireMsg* dst, uint64_t group, uint64_t term, uint64_t log_term, uint64_t index, uint32_t from, uint32_t to,
+                                           uint32_t type) {
+  uint4* q = reinterpret_cast<uint4*>(dst);
+  q[0] = make_uint4((uint32_t)group, (uint32_t)(group >> 32), (uint32_t)term, (uint32_t)(term >> 32));
+  q[1] = make_uint4((uint32_t)log_term, (uint32_t)(log_term >> 32), (uint32_t)index, (uint32_t)(index >> 32));
+  q[2] = make_uint4(0u, 0u, 0u, 0u);
+  q[3] = make_uint4(from, type | (to << 16), 0u, 0u);
+}
+
+// One MsgHup group of the round under raftq_set_check_quorum (raftq_tick_set_checks; elect_build_cq_kernel, elect_build_cq_voters_kernel):
+// the lane runs Node's CQ form and states no rule of its own -- it steps a local MsgHup through Node::step, the call the *_cq_* walks
+// make for the caller's own MsgHup record, and packs step()'s result with put_result, as they do.  What step() gives decides the
+// frames: RAFTQ_OUT_CAMPAIGN sends MsgVote at the new term; RAFTQ_OUT_PRE_CAMPAIGN (raftq_set_pre_vote: nothing but role, lead and
+// the vote word moved) sends MsgPreVote at term + 1 to the same slots; RAFTQ_OUT_BECAME_LEADER (masked: the own grant was the quorum,
+// with or without a pre-election in front) sends nothing.  The first two get RAFTQ_OUTF_ANSWERED.  -> member frames written
 template <bool MASKED>
+__device__ __forceinline__ uint32_t elect_group_cq(const ElectArgs& e, const uint16_t* __restrict__ voters, WireMsg* votes, uint64_t n_vb, uint64_t g,
+                                                   uint64_t at) {
+  uint64_t term = 0, last_index = 0, last_term = 0;
+  uint32_t ask = 0;           // the slots a frame goes to
+  uint32_t type = kMsgVote;   // ... a MsgVote or a MsgPreVote
+  StepOutRec o;
+  if (g < e.a.n_groups) {  // (the Tick flags no padding group)
+    NodeT<MASKED, false, true> node(e.a, g, voters);
+    const MsgRec m{g, 0, 0, 0, 0, 0, e.a.self, kMsgHup, 0, {0, 0}, 0};  // the local MsgHup a caller would have stepped
+    node.step(m, o);
+    node.store();
+    if (o.type != kOutBecameLeader) {
+      o.flags |= kFlagAnswered;
+      if constexpr (MASKED) ask = node.vmask;
+      else ask = ~0u;
+    }
+    const bool pre = o.type == kOutPreCampaign;
+    type = pre ? kMsgPreVote : kMsgVote;
+    term = pre ? node.term + 1 : node.term;
+    last_index = node.last_index;
+    last_term = o.log_term;
+  } else {
+    o = StepOutRec{g, 0, 0, 0, 0, 0, 0, 0, 0, kOutNone, 0, 0, 0};
+  }
+  put_result<true>(e.camp, at, o, kFmtS32);
+  uint32_t wrote = 0;
+#pragma unroll
+  for (uint32_t p = 0; p < (uint32_t)kMaxPeers; ++p) {
+    if (p >= e.a.n_peers || p == e.a.self) continue;
+    const uint64_t slice = p < e.a.self ? p : p - 1;
+    const bool member = ((ask >> p) & 1u) != 0;
+    vote_store(votes + slice * n_vb + at, g, term, last_term, last_index, e.a.self, member ? p : 0xffu, type);
+    wrote += member ? 1u : 0u;
+  }
+  return wrote;
+}
+
+// CQ: every group of the round is elect_group_cq's; ranking, sections and fillers are the same.
+template <bool MASKED, bool CQ = false>
 __device__ __forceinline__ void elect_build_body(ElectArgs e, const uint16_t* __restrict__ voters, unsigned long long* members) {
   __shared__ uint64_t red[kWaves];
   __shared__ uint32_t mine[kWaves];
@@ -77,6 +132,10 @@ __device__ __forceinline__ void elect_build_body(ElectArgs e, const uint16_t* __
     for (uint32_t r = tid; r < take; r += kBlock) {
       const uint64_t g = ids[r];
       const uint64_t at = pos + r;
+      if constexpr (CQ) {
+        wrote += elect_group_cq<MASKED>(e, voters, votes, n_vb, g, at);
+        continue;
+      }
       uint64_t term = 0, last_index = 0, last_term = 0;
       uint32_t ask = 0;  // the slots a MsgVote goes to
       u64x2 c0, c1;
@@ -131,6 +190,11 @@ __device__ __forceinline__ void elect_build_body(ElectArgs e, const uint16_t* __
 static __global__ __launch_bounds__(kBlock) void elect_build_kernel(ElectArgs e) { elect_build_body<false>(e, nullptr, nullptr); }
 static __global__ __launch_bounds__(kBlock) void elect_build_voters_kernel(ElectArgs e, const uint16_t* __restrict__ voters, unsigned long long* members) {
   elect_build_body<true>(e, voters, members);
+}
+static __global__ __launch_bounds__(kBlock) void elect_build_cq_kernel(ElectArgs e) { elect_build_body<false, true>(e, nullptr, nullptr); }
+static __global__ __launch_bounds__(kBlock) void elect_build_cq_voters_kernel(ElectArgs e, const uint16_t* __restrict__ voters,
+                                                                              unsigned long long* members) {
+  elect_build_body<true, true>(e, voters, members);
 }
 
 }  // namespace raftqk

@@ -108,6 +108,13 @@ struct raftq {
   uint32_t* cq = nullptr;        // [ld]
   uint64_t* chk_bits = nullptr;  // [gpad/64]
   bool pre_vote = false;         // raftq_set_pre_vote: only ever true while cq is set
+  // raftq_tick_set_checks (0 = off): with cq set, the fused Tick calls run instead of refusing and leave the groups whose check failed as
+  // a third in-place list of at most this many ids behind the beat bitmap in `tl` (raftq_last_tick_checks).  A property of the handle,
+  // as tick_voters is: raftq_clone_state leaves it alone
+  uint64_t tick_chk_cap = 0;
+  uint64_t tl_chk_cap = 0, tl_chk_off = 0, tl_n_chk = 0;  // of the last fused call: ids listed at most, their byte offset in tl, the total
+  bool tl_chk_valid = false;     // the last call on the handle was a fused Tick call under the switch
+  uint64_t* tick_offsets3 = nullptr;  // [gpad/256 + 1]: the failed checks' offsets on handles of more than 16K waves
   uint64_t* d_total = nullptr;  // device alias of h_total
   bool have_terms = false;
   unsigned last_flags = 0;
@@ -307,9 +314,13 @@ inline bool masked_tick(const raftq_t* h) { return h->voters != nullptr && h->ti
 inline bool masked_bcast(const raftq_t* h) { return h->voters != nullptr && h->bcast_voters; }
 // RAFTQ_ESTATE, "check quorum" in the text, on a handle with raftq_set_check_quorum on: the fused Tick calls and the device-built
 // heartbeat / election rounds do not know a suppressed beat
-int refuse_check_quorum(raftq_t* h, const char* who);
+// fused: the call is one raftq_tick_set_checks opens (let through once chk_cap > 0)
+int refuse_check_quorum(raftq_t* h, const char* who, bool fused = false);
 // RAFTQ_ESTATE, "pre vote" in the text, on a handle with raftq_set_pre_vote on: a call that turns a MsgHup into becomeCandidate on the device
-int refuse_pre_vote(raftq_t* h, const char* who);
+int refuse_pre_vote(raftq_t* h, const char* who, bool fused = false);
+// raftq_tick_set_checks on a handle with raftq_set_check_quorum on: the fused calls launch tick_check_kernel, list the failed checks and
+// -- raftq_tick_elect_frames -- campaign through Node's CQ form (elect_build_cq_kernel / elect_build_cq_voters_kernel)
+inline bool tick_checks(const raftq_t* h) { return h->cq != nullptr && h->tick_chk_cap != 0; }
 int self_max_check(raftq_t* h);                 // the self-max word re-derived from the rows for h->self_peer (enqueued)
 int narrow_build(raftq_t* h);                   // the narrow mirror and its word re-derived from the rows (enqueued)
 int ensure_staging(raftq_t* h, size_t bytes);   // pinned, device-mapped staging (term deltas, campaign lists, log deltas)
@@ -364,6 +375,7 @@ struct TickLists {
   uint64_t cap_h, cap_b, beat_at, map_off;  // the in-place lists' layout (raftq_t::tl_*)
   const uint64_t* off_beat;                 // after _enqueue: scan_partials_kernel's MsgBeat offsets (more than 16K waves), or nullptr
   const uint64_t* off_h = nullptr;          // ... and its MsgHup offsets (raftq_tick_elect_frames)
+  uint64_t cap_c = 0, chk_off = 0;          // raftq_tick_set_checks: ids of failed checks listed at most (0: the two-list form), their byte offset
 };
 int tick_lists_prepare(raftq_t* h, const char* who, unsigned flags, uint64_t hup_cap, uint64_t beat_cap, TickLists* tl);
 int tick_lists_enqueue(raftq_t* h, TickLists* tl);

@@ -904,7 +904,8 @@ extern "C" int raftq_tick_frames(raftq_t* h, unsigned flags, uint64_t hup_cap, u
   const char* who = "raftq_tick_frames";
   if (int rc = raftq_detail::use_device_idle(h, who)) return rc;
   if (counts) *counts = raftq_wire_counts_t{0, 0, 0, 0};
-  if (int rc = raftq_detail::refuse_check_quorum(h, who)) return rc;
+  // (raftq_tick_set_checks opens the call: the beat bitmap beat_build_kernel ranks never held a group whose check failed)
+  if (int rc = raftq_detail::refuse_check_quorum(h, who, true)) return rc;
   if (!n_hup || !n_beat || !peer_off) return fail(h, RAFTQ_EINVAL, std::string(who) + ": null argument");
   if (flags & ~RAFTQ_TICK_BEAT_BITMAP) return fail(h, RAFTQ_EINVAL, std::string(who) + ": unknown flag");
   if (h->N < 2) return fail(h, RAFTQ_EINVAL, std::string(who) + ": a single-peer group has nobody to send a heartbeat to -- use raftq_tick_collect_lists");
@@ -986,8 +987,9 @@ extern "C" int raftq_tick_elect_frames(raftq_t* h, unsigned flags, uint64_t hup_
   const char* who = "raftq_tick_elect_frames";
   if (int rc = raftq_detail::use_device_idle(h, who)) return rc;
   if (counts) *counts = raftq_wire_counts_t{0, 0, 0, 0};
-  if (int rc = raftq_detail::refuse_pre_vote(h, who)) return rc;
-  if (int rc = raftq_detail::refuse_check_quorum(h, who)) return rc;
+  // (raftq_tick_set_checks opens the call under both switches: the round is then elect_build_cq_kernel's, Step's own MsgHup arm)
+  if (int rc = raftq_detail::refuse_pre_vote(h, who, true)) return rc;
+  if (int rc = raftq_detail::refuse_check_quorum(h, who, true)) return rc;
   if (!n_hup || !n_beat || !peer_off) return fail(h, RAFTQ_EINVAL, std::string(who) + ": null argument");
   if (flags & ~RAFTQ_TICK_BEAT_BITMAP) return fail(h, RAFTQ_EINVAL, std::string(who) + ": unknown flag");
   if (h->N < 2) return fail(h, RAFTQ_EINVAL, std::string(who) + ": a single-peer group has nobody to ask for a vote -- use raftq_tick_collect_lists");
@@ -1036,7 +1038,10 @@ extern "C" int raftq_tick_elect_frames(raftq_t* h, unsigned flags, uint64_t hup_
     if (hup_cap != 0) {
       ElectArgs ea{(const uint64_t*)h->hup_bits, (const uint4*)h->tick_partials, nw, tl.off_h, (const uint64_t*)h->d_total, na, hup_cap, beat_cap,
                    (StepOutS*)v_camp, enc};
-      if (members) hipLaunchKernelGGL(elect_build_voters_kernel, grid, dim3(kBlock), 0, h->stream, ea, (const uint16_t*)h->voters, members_word(h));
+      if (raftq_detail::tick_checks(h)) {  // Node's CQ form: na carries cq, election_tick and pv (node_records_of)
+        if (members) hipLaunchKernelGGL(elect_build_cq_voters_kernel, grid, dim3(kBlock), 0, h->stream, ea, (const uint16_t*)h->voters, members_word(h));
+        else hipLaunchKernelGGL(elect_build_cq_kernel, grid, dim3(kBlock), 0, h->stream, ea);
+      } else if (members) hipLaunchKernelGGL(elect_build_voters_kernel, grid, dim3(kBlock), 0, h->stream, ea, (const uint16_t*)h->voters, members_word(h));
       else hipLaunchKernelGGL(elect_build_kernel, grid, dim3(kBlock), 0, h->stream, ea);
     }
     HIPCHK(h, hipGetLastError());

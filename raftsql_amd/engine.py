@@ -545,6 +545,23 @@ class QuorumEngine:
         second = view(pm, lm.value, np.uint64) if beat_bitmap else view(pb, lb.value, np.uint32)
         return hups, int(nh.value), second, int(nb.value)
 
+    def set_tick_checks(self, chk_cap: int) -> None:
+        """raftq_tick_set_checks: chk_cap > 0 opens tick_collect, tick_collect_lists, tick_frames and tick_elect_frames on a handle
+        with set_check_quorum on (the last one under set_pre_vote too); they then leave the groups whose check failed as a third
+        in-place list of at most chk_cap ids (last_tick_checks).  0 (the default): those calls refuse such a handle.  A property of
+        the handle (no batch may be in flight)."""
+        self._chk(self._lib.raftq_tick_set_checks(self._h, int(chk_cap)))
+
+    def last_tick_checks(self):
+        """raftq_last_tick_checks: the third list of the last tick_collect_lists / tick_frames / tick_elect_frames under
+        set_tick_checks -> (ids view u32 [min(total, chk_cap)], total).  The view is the library's memory: valid until the next call
+        on the handle."""
+        p, n, tot = C.c_void_p(None), C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._lib.raftq_last_tick_checks(self._h, C.byref(p), C.byref(n), C.byref(tot)))
+        if not n.value:
+            return np.empty(0, dtype=np.uint32), int(tot.value)
+        return np.frombuffer((C.c_char * (int(n.value) * 4)).from_address(p.value), dtype=np.uint32), int(tot.value)
+
     def campaign(self, groups, self_peer: int = 0) -> None:
         g = np.ascontiguousarray(groups, dtype=np.uint64)
         self._chk(self._lib.raftq_campaign(self._h, _ptr(g) if len(g) else None, len(g), self_peer))
