@@ -320,6 +320,35 @@ func (e *Engine) SetPreVote(on bool) error {
 	return e.err(C.raftq_set_pre_vote(e.h, v))
 }
 
+// SetLeadTransfer opts the engine in to (or out of) upstream's leadership transfer (raftq_set_lead_transfer; include/raftq.h
+// "Leadership transfer"): Msgs of type MsgTransferLeader / MsgTimeoutNow are stepped, a MsgVote with Reject = 1 is a transfer's and
+// passes the lease, a leader with a transfer pending drops MsgProp.  Requires SetCheckQuorum(true) (ErrState otherwise, and
+// SetCheckQuorum(false) returns ErrState while it is on); ProposeFrames returns ErrState meanwhile.  A property of the engine; no
+// batch may be in flight.  Turning it off clears every pending transferee.
+func (e *Engine) SetLeadTransfer(on bool) error {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	return e.err(C.raftq_set_lead_transfer(e.h, v))
+}
+
+// LoadTransfer sets every group's leadTransferee: 0 = None, else peer slot + 1 (raftq_load_transfer).
+func (e *Engine) LoadTransfer(transferee []uint8) error {
+	if uint64(len(transferee)) != e.Groups || e.Groups == 0 {
+		return errors.New("raftq: LoadTransfer: transferee must hold G bytes")
+	}
+	return e.err(C.raftq_load_transfer(e.h, (*C.uint8_t)(unsafe.Pointer(&transferee[0]))))
+}
+
+// ReadTransfer reads every group's leadTransferee (raftq_read_transfer).
+func (e *Engine) ReadTransfer(transferee []uint8) error {
+	if uint64(len(transferee)) != e.Groups || e.Groups == 0 {
+		return errors.New("raftq: ReadTransfer: transferee must hold G bytes")
+	}
+	return e.err(C.raftq_read_transfer(e.h, (*C.uint8_t)(unsafe.Pointer(&transferee[0]))))
+}
+
 // LoadActivity sets every group's activity word (bit p = peer slot p answered since the last check) and / or every leader's
 // electionElapsed; nil leaves that half alone (raftq_load_activity).
 func (e *Engine) LoadActivity(active []uint16, leadElapsed []uint32) error {

@@ -25,6 +25,8 @@ const (
 	MsgHeartbeat     = C.RAFTQ_MSG_HEARTBEAT
 	MsgHeartbeatResp = C.RAFTQ_MSG_HEARTBEAT_RESP
 	MsgCheckQuorum   = C.RAFTQ_MSG_CHECK_QUORUM // local: a leader's failed check (CollectChecks); stepped only after SetCheckQuorum(true)
+	MsgTransferLeader = C.RAFTQ_MSG_TRANSFER_LEADER // From = the transferee (local at Term 0, or forwarded); stepped only after SetLeadTransfer(true)
+	MsgTimeoutNow     = C.RAFTQ_MSG_TIMEOUT_NOW
 	MsgPreVote       = C.RAFTQ_MSG_PRE_VOTE      // a peer's pre-election, MsgVote's fields; stepped only after SetPreVote(true)
 	MsgPreVoteResp   = C.RAFTQ_MSG_PRE_VOTE_RESP
 )
@@ -119,10 +121,12 @@ const (
 	OutForward        = C.RAFTQ_OUT_FORWARD  // SetStepProps: a follower's MsgProp goes on to its leader, To = Lead - 1
 	OutPreCampaign    = C.RAFTQ_OUT_PRE_CAMPAIGN  // SetPreVote: became pre-candidate, send MsgPreVote{Term: Term + 1, Index, LogTerm} to every other peer
 	OutPreVoteResp    = C.RAFTQ_OUT_PRE_VOTE_RESP // SetPreVote: send MsgPreVoteResp{To, Term: Index, Reject}
+	OutTransfer       = C.RAFTQ_OUT_TRANSFER      // SetLeadTransfer: leader took a MsgTransferLeader, To = the transferee, Index = its Match
 	OutTermResp       = C.RAFTQ_OUT_TERM_RESP     // SetPreVote: a stale leader's MsgApp / MsgHeartbeat, send MsgAppResp{To, Term}
 
 	FlagHardState   = C.RAFTQ_OUTF_HARDSTATE // persist {Term, Vote, Commit} before sending (raft.go:228-230)
 	FlagCommitted   = C.RAFTQ_OUTF_COMMITTED
+	FlagTimeoutNow  = C.RAFTQ_OUTF_TIMEOUT_NOW // SetLeadTransfer: the pending transferee To is at the tail, send MsgTimeoutNow{To, Term}
 	FlagUpdated     = C.RAFTQ_OUTF_UPDATED
 	FlagSteppedDown = C.RAFTQ_OUTF_STEPPED_DOWN
 )

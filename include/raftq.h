@@ -412,6 +412,39 @@ int raftq_collect_checks(raftq_t* h, uint64_t* groups, uint64_t cap, uint64_t* n
  * are MsgPreVote at term + 1 (raftq_wire.h). */
 int raftq_set_pre_vote(raftq_t* h, int on);
 
+/* ---- Leadership transfer: MsgTransferLeader, MsgTimeoutNow (etcd/raft's leadTransferee, restated; PARITY UNPINNED) ----------------
+ * Under the lease (raftq_set_check_quorum) a node under a live leader ignores a MsgVote of a higher term, so leadership cannot be
+ * moved off a node on purpose: the only route is to kill it and wait out an election timeout.  Upstream's transfer avoids that: the
+ * leader brings the transferee up to its tail and sends it MsgTimeoutNow; the transferee campaigns at once, with a MsgVote that is
+ * marked as a transfer's and passes the lease.  raftq_set_lead_transfer(h, 1) opts the handle in; the rules are Step's (raftq_step.h
+ * "Leadership transfer").  0 is the default; anything but 0 or 1 is RAFTQ_EINVAL; the handle must be idle (RAFTQ_ESTATE with a Step
+ * batch in flight); a NULL handle is an error and no device is touched.  A property of the handle: raftq_clone_state does not copy it.
+ *
+ * CHOICE: it requires CheckQuorum.  raftq_set_lead_transfer(h, 1) on a handle without raftq_set_check_quorum is RAFTQ_ESTATE ("check
+ * quorum" in the text), and raftq_set_check_quorum(h, 0) while it is on is RAFTQ_ESTATE ("lead transfer").  It is independent of
+ * raftq_set_pre_vote.
+ *
+ * State.  leadTransferee[g] -- 0 = None, else peer slot + 1 -- is bits 12..15 of the activity word raftq_set_check_quorum allocated:
+ * the activity bits stay in 0..8 (at most 9 peers, so a transferee of 9 fits in four bits), lead_elapsed in 16..31.  NO TICK KERNEL
+ * CHANGES: tick_check_kernel already does what upstream's tickHeartbeat does.  A check that falls due and passes writes the whole word
+ * 0 -- abortLeaderTransfer() at the election timeout; one that fails keeps the low half, and Step's RAFTQ_MSG_CHECK_QUORUM then clears
+ * the low 16 bits whether the leader steps down or not; a check that is not due, and a non-leader, leave the low half alone; and the
+ * check's popcount is over the members, at most 9 bits.  With the switch off no code path sets bits 12..15.
+ *   raftq_read_activity never shows bits 12..15 in `active`; raftq_load_activity with `active` given keeps them as they are (a word
+ *   that names a slot >= n_peers is refused as always).  raftq_set_lead_transfer(h, 0) clears them in every group.
+ *   raftq_load_transfer / raftq_read_transfer: the transferees as one byte per group.  RAFTQ_ESTATE without the switch; a value
+ *   above n_peers is RAFTQ_EINVAL and nothing is loaded.
+ *   raftq_clone_state copies the word as it always has: the transferee travels with it.
+ *
+ * What the switch closes (RAFTQ_ESTATE, "lead transfer" in the text): raftq_propose_frames (raftq_wire.h) -- a leader must drop its
+ * own proposals while a transfer is pending, and the proposal kernels do not read the word (a follow-up).  raftq_apply_log_deltas
+ * stays the caller's responsibility: the caller knows of the transfer from RAFTQ_OUT_TRANSFER and can ask raftq_read_transfer.
+ * Not modelled (CHOICE): a voter delta that removes the pending transferee does not abort the transfer; the Tick's timeout does.
+ * raftq_node does not turn the switch on. */
+int raftq_set_lead_transfer(raftq_t* h, int on);
+int raftq_load_transfer(raftq_t* h, const uint8_t* transferee /*[G]*/);
+int raftq_read_transfer(raftq_t* h, uint8_t* transferee /*[G]*/);
+
 /* becomeCandidate for `n` distinct groups: role = candidate, elapsed = 0, votes
  * cleared, the candidate's own slot (`self_peer`) granted.  Term bookkeeping is
  * the caller's (raftq_apply_term_deltas). */

@@ -53,6 +53,8 @@ extern "C" {
 #define RAFTQ_MSG_HEARTBEAT_RESP 9
 #define RAFTQ_MSG_CHECK_QUORUM 12  /* local: the leader's check fell due and failed in raftq_tick (raftq_collect_checks); only under
                                     * raftq_set_check_quorum, see "CheckQuorum" below */
+#define RAFTQ_MSG_TRANSFER_LEADER 13 /* raftpb values; only under raftq_set_lead_transfer, see "Leadership transfer" below */
+#define RAFTQ_MSG_TIMEOUT_NOW 14
 #define RAFTQ_MSG_PRE_VOTE 17      /* raftpb values; only under raftq_set_pre_vote, see "PreVote" below */
 #define RAFTQ_MSG_PRE_VOTE_RESP 18
 
@@ -216,6 +218,45 @@ int raftq_step_set_props(raftq_t* h, int on);
  * frames calls take frames of types 17 and 18; without it they stay frames of a kind a peer never sends.  Device-built MsgPreVote
  * rounds are not built yet: raftq_tick_elect_frames refuses the handle.  raftq_node does not turn the switch on. */
 
+/* Leadership transfer in Step (raftq_set_lead_transfer, raftq.h "Leadership transfer": the switch, its state, what it requires and
+ * closes).  With the switch off every call returns what it always did, types 13 and 14 are unknown kinds that fail their batch and
+ * apply nothing, and a MsgVote's `reject` byte is not looked at.  With it on, in every walk form and every Step-family call
+ * (etcd/raft's leadership transfer restated, PARITY UNPINNED; CHOICE marks where this differs from or adds to upstream).  The
+ * transferee is leadTransferee[g], bits 12..15 of the activity word (0 = None, else slot + 1); no Tick kernel changes.
+ *   1. The records.  Both kinds use group, term, from.  A MsgTransferLeader's `from` is the TRANSFEREE's slot in both of its forms:
+ *      the local one (term 0: what node.TransferLeadership steps) and the forwarded one (a follower sends it on with its own term).
+ *      `from` >= N is malformed even at term 0.  MsgTimeoutNow is a peer's kind.  raftq_msg_t and raftq_msg40_t both take them.
+ *   2. The mark.  CHOICE: a transfer's campaign marks its MsgVote with reject = 1 (upstream: Context == "CampaignTransfer"; this
+ *      wire has no Context field, and its field 12 is the group).  `reject` is carried by the 64-byte record, the 40-byte record
+ *      and the frame, and means nothing else on a request.
+ *   3. The lease.  CheckQuorum's rule 3 and PreVote's rule 2 ignore a MsgVote only if reject == 0.  A marked MsgVote of a higher
+ *      term is becomeFollower(m.Term, None) and is answered by the role's rule as always.  A MsgPreVote is never marked.
+ *   4. Leader, MsgTransferLeader, t = from.  t not a voter (the masked form; upstream's pr == nil): ignored.  A transfer to t
+ *      already pending: ignored.  One to another slot pending: aborted first.  Then t == self: stop (a transfer to self therefore
+ *      cancels a pending one, as upstream).  Otherwise leadTransferee = t + 1 and lead_elapsed = 0; RAFTQ_OUT_TRANSFER, to = t,
+ *      index = Match[t]; with RAFTQ_OUTF_TIMEOUT_NOW when Match[t] == last_index (send MsgTimeoutNow{To: t, Term: term}), without
+ *      it the caller runs sendAppend(t).  Every ignored case is RAFTQ_OUT_NONE and changes nothing.
+ *   5. Leader, MsgAppResp from the pending transferee for which maybeUpdate returned true (RAFTQ_OUTF_UPDATED) and whose Match now
+ *      equals last_index: its RAFTQ_OUT_PROGRESS also carries RAFTQ_OUTF_TIMEOUT_NOW.  An ack that does not update sends nothing
+ *      (upstream has it inside the update branch).
+ *   6. Leader, MsgProp with a transfer pending: dropped -- RAFTQ_OUT_NONE, nothing moves (upstream's ErrProposalDropped).
+ *   7. reset().  Every becomeFollower / becomeCandidate / becomeLeader clears the transferee (the activity word is zeroed as it
+ *      always was), and RAFTQ_MSG_CHECK_QUORUM clears it whether or not the check passes.
+ *   8. Follower, MsgTransferLeader: with a leader RAFTQ_OUT_FORWARD, to = lead - 1, nothing changes; without one RAFTQ_OUT_NONE.
+ *      A candidate or pre-candidate: RAFTQ_OUT_NONE.
+ *   9. MsgTimeoutNow.  The term rules come first, as for any message: a higher term makes the node a follower of `from`; a lower
+ *      one is ignored (under PreVote it is NOT one of the kinds answered RAFTQ_OUT_TERM_RESP).  A follower that is a voter --
+ *      the masked form asks promotable(), as upstream does; a follower that is not gives RAFTQ_OUT_NONE -- campaigns at once: the
+ *      real campaign even under PreVote, no pre-candidate step.  RAFTQ_OUT_CAMPAIGN with reject = 1 (send the MsgVotes marked), or
+ *      RAFTQ_OUT_BECAME_LEADER (reject = 0) if the own grant is the quorum.  A leader, candidate or pre-candidate ignores it.
+ * Not modelled (CHOICE): a voter delta that removes the pending transferee does not abort the transfer; the Tick's timeout does.
+ * The compact records: RAFTQ_OUT_TRANSFER packs as RAFTQ_OUT_PROGRESS does; `reject` and the new flag ride all three formats as
+ * they are.  In raftq_step_frames_respond (raftq_wire.h) RAFTQ_OUT_TRANSFER, a forwarded MsgTransferLeader and a campaign from
+ * MsgTimeoutNow are the host's -- no RAFTQ_OUTF_ANSWERED, and they end their group's device-answered prefix --;
+ * RAFTQ_OUTF_TIMEOUT_NOW is always the host's to send and does not stop a committing ack's commit broadcast from being built and
+ * flagged RAFTQ_OUTF_ANSWERED.  Under the switch the frames calls take frames of types 13 and 14; without it they stay frames of a
+ * kind a peer never sends.  No encoder builds the two kinds on the device.  raftq_node does not turn the switch on. */
+
 /* raftq_msg_t._pad[1] once the handle opted in.  RAFTQ_MSGF_ENTRIES on a MsgApp: the caller says what the message carries -- the low 32 bits of
  * _resv = its number of entries, reject_hint (a field MsgApp does not use) = the Term of the last one (unused with no
  * entries).  Step then runs raftLog.maybeAppend itself whenever the message appends at the TAIL of the log (m.Index ==
@@ -263,11 +304,15 @@ int raftq_step_set_props(raftq_t* h, int on);
 #define RAFTQ_OUT_PRE_CAMPAIGN 14   /* became pre-candidate: send MsgPreVote{Term: term + 1, Index: index, LogTerm: log_term} to every other peer */
 #define RAFTQ_OUT_PRE_VOTE_RESP 15  /* send MsgPreVoteResp{To: to, Term: index, Reject: reject} -- `index` carries the response's Term */
 #define RAFTQ_OUT_TERM_RESP 16      /* a stale leader's MsgApp / MsgHeartbeat: send MsgAppResp{To: to, Term: term} (Index 0, no reject) */
+#define RAFTQ_OUT_TRANSFER 17       /* leader took a MsgTransferLeader: `to` = the transferee, index = its Match; with RAFTQ_OUTF_TIMEOUT_NOW send
+                                     * MsgTimeoutNow{To: to, Term: term}, without it run sendAppend(to) */
 
 #define RAFTQ_OUTF_HARDSTATE 0x01u    /* Term, Vote or Commit changed: HardState must be persisted (wal.Save, raft.go:228) */
 #define RAFTQ_OUTF_COMMITTED 0x02u    /* raftLog.committed advanced (leader: bcastAppend carries it) */
 #define RAFTQ_OUTF_UPDATED 0x04u      /* Progress.maybeUpdate returned true */
 #define RAFTQ_OUTF_STEPPED_DOWN 0x08u /* was leader or candidate, is follower now */
+/* (0x10u is RAFTQ_OUTF_ANSWERED, raftq_wire.h) */
+#define RAFTQ_OUTF_TIMEOUT_NOW 0x20u  /* raftq_set_lead_transfer: the pending transferee `to` is at the tail -- send MsgTimeoutNow{To: to, Term: term} */
 
 typedef struct raftq_step_out {
   uint64_t group;

@@ -222,6 +222,10 @@ int raftq_step_wire_entries(raftq_t* h, const raftq_wire_ent_t** ents, uint64_t*
  *     On a handle that opted in to raftq_step_set_props (raftq_step.h) instead: with entries RAFTQ_MSGF_ENTRIES -- Step takes it by
  *     its count, RAFTQ_OUT_PROPOSED / RAFTQ_OUT_FORWARD / RAFTQ_OUT_NONE, and holds nobody up -- and without entries
  *     RAFTQ_MSGF_SKIP, as a frame of a kind a peer never sends.
+ *   - MsgTransferLeader, MsgTimeoutNow (types 13 and 14): on a handle that opted in to raftq_set_lead_transfer (raftq.h) kinds a
+ *     peer sends, checked as the others are and flagged as little; without it they stay frames of a kind a peer never sends.
+ *     (Likewise types 17 and 18 under raftq_set_pre_vote.)  raftq_step_frames_packed and raftq_step_submit_wire take them the same
+ *     way.  No encoder builds the two kinds on the device.
  *   - MsgApp: RAFTQ_MSGF_BARRIER, and with tail_appends != 0 RAFTQ_MSGF_ENTRIES (reject_hint, which a MsgApp does not use, is
  *     overwritten with the Term of its last entry) -- one that lands on the log's tail is RAFTQ_OUT_APPENDED.
  * Results: raftq_step_results (or _c), n records, out[i] answers frame i.  msgs / ents / counts as raftq_wire_decode, except
@@ -263,6 +267,10 @@ int raftq_step_frames_packed(raftq_t* h, const void* stream, uint64_t nbytes, co
  * raftq_respond_set_props, below, opted the handle in) / RAFTQ_OUT_FORWARD.  A result the caller may have to answer itself (any of those that sends, a
  * MsgAppResp while the group's bit is clear) ends its group's device-answered prefix: the group's later results of the batch
  * are not answered either, so per (peer, group) the frames keep the order the host's own answers would have.
+ * Under raftq_set_lead_transfer (raftq_step.h "Leadership transfer") RAFTQ_OUT_TRANSFER, a forwarded MsgTransferLeader
+ * (RAFTQ_OUT_FORWARD) and a campaign from MsgTimeoutNow are the host's in the same way: no RAFTQ_OUTF_ANSWERED, and they end their
+ * group's device-answered prefix.  RAFTQ_OUTF_TIMEOUT_NOW is always the host's to send; on a committing ack it does not stop the
+ * commit broadcast from being built and flagged RAFTQ_OUTF_ANSWERED -- the result then carries both flags.
  * at_tail ([ceil(G / 64)] words, bit g = group g; NULL = all clear): the caller's word that it leads g and every follower's
  * Progress.Next is lastIndex + 1 now (Next is the caller's, raftq_step.h).  A wrong set bit is the caller's bug, a clear one
  * only costs speed.  The device clears g's bit from g's first message on that makes the host move a Next away from the tail:

@@ -106,6 +106,9 @@ _SIGS = [
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     ("raftq_set_check_quorum", C.c_int, [_H, C.c_int]),
     ("raftq_set_pre_vote", C.c_int, [_H, C.c_int]),
+    ("raftq_set_lead_transfer", C.c_int, [_H, C.c_int]),
+    ("raftq_load_transfer", C.c_int, [_H, C.c_void_p]),
+    ("raftq_read_transfer", C.c_int, [_H, C.c_void_p]),
     ("raftq_load_activity", C.c_int, [_H, C.c_void_p, C.c_void_p]),
     ("raftq_read_activity", C.c_int, [_H, C.c_void_p, C.c_void_p]),
     ("raftq_collect_checks", C.c_int, [_H, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),

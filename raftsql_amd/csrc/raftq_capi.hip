@@ -1082,6 +1082,11 @@ int raftq_detail::refuse_pre_vote(raftq_t* h, const char* who, bool fused) {
   return fail(h, RAFTQ_ESTATE, std::string(who) + ": raftq_set_pre_vote is on (pre vote): this call's device-built round makes a MsgHup a becomeCandidate and "
                                                   "sends MsgVote -- step the MsgHup (RAFTQ_OUT_PRE_CAMPAIGN) and send MsgPreVote");
 }
+int raftq_detail::refuse_lead_transfer(raftq_t* h, const char* who) {
+  if (!h->lead_transfer) return RAFTQ_OK;
+  return fail(h, RAFTQ_ESTATE, std::string(who) + ": raftq_set_lead_transfer is on (lead transfer): a leader drops its own proposals while a transfer is "
+                                                  "pending, and this call's kernels do not read the word that says so");
+}
 constexpr uint32_t kCheckQuorumMaxTick = 0xffffu;  // lead_elapsed shares its word with the activity bits (raftq_t::cq)
 
 static int ensure_tick_offsets2(raftq_t* h, uint64_t nw);
@@ -1169,6 +1174,8 @@ int raftq_set_check_quorum(raftq_t* h, int on) {
   if ((on == 1) == (h->cq != nullptr)) return RAFTQ_OK;
   if (on == 0 && h->pre_vote)
     return fail(h, RAFTQ_ESTATE, "raftq_set_check_quorum: raftq_set_pre_vote is on (pre vote) and requires the lease: turn it off first");
+  if (on == 0 && h->lead_transfer)
+    return fail(h, RAFTQ_ESTATE, "raftq_set_check_quorum: raftq_set_lead_transfer is on (lead transfer) and keeps its state in the lease's word: turn it off first");
   if (on == 1) {
     if (int rc = ensure_tick_state(h)) return rc;
     HIPCHK(h, raftq_buf::alloc_group({{(void**)&h->cq, h->ld * 4}, {(void**)&h->chk_bits, h->gpad / 8}}, h->stream));
@@ -1190,6 +1197,55 @@ int raftq_set_pre_vote(raftq_t* h, int on) {
   return RAFTQ_OK;
 }
 
+// leadTransferee: bits 12..15 of the cq word (0 = None, else slot + 1), beside the activity bits 0..8 and below lead_elapsed
+constexpr uint32_t kTransfereeShift = 12, kTransfereeMask = 0xf000u;
+
+int raftq_set_lead_transfer(raftq_t* h, int on) {
+  if (int rc = use_device_idle(h, "raftq_set_lead_transfer")) return rc;
+  if (on != 0 && on != 1)
+    return fail(h, RAFTQ_EINVAL, "raftq_set_lead_transfer: 0 (types 13 and 14 are unknown kinds, a MsgVote's reject byte is not looked at) or 1 (Step runs "
+                                 "MsgTransferLeader and MsgTimeoutNow; a marked MsgVote passes the lease)");
+  if (on == 1 && !h->cq)
+    return fail(h, RAFTQ_ESTATE, "raftq_set_lead_transfer: requires raftq_set_check_quorum (check quorum): the transferee lives in the lease's word and the "
+                                 "Tick's check is what aborts a transfer");
+  if (on == 0 && h->lead_transfer) {  // no transfer outlives the switch: the bits are 0 on every handle without it
+    std::vector<uint32_t> w(h->G);
+    HIPCHK(h, hipMemcpyAsync(w.data(), h->cq, h->G * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (uint64_t g = 0; g < h->G; ++g) w[g] &= ~kTransfereeMask;
+    HIPCHK(h, hipMemcpyAsync(h->cq, w.data(), h->G * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  h->lead_transfer = on == 1;
+  return RAFTQ_OK;
+}
+
+int raftq_load_transfer(raftq_t* h, const uint8_t* transferee) {
+  if (int rc = use_device_idle(h, "raftq_load_transfer")) return rc;
+  if (!h->lead_transfer) return fail(h, RAFTQ_ESTATE, "raftq_load_transfer: raftq_set_lead_transfer is off (lead transfer): the handle holds no transferee");
+  if (!transferee) return fail(h, RAFTQ_EINVAL, "raftq_load_transfer: null transferee array");
+  for (uint64_t g = 0; g < h->G; ++g)
+    if (transferee[g] > h->N) return fail(h, RAFTQ_EINVAL, "raftq_load_transfer: a transferee is 0 (None) or a peer slot + 1 <= n_peers; nothing loaded");
+  std::vector<uint32_t> w(h->G);
+  HIPCHK(h, hipMemcpyAsync(w.data(), h->cq, h->G * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (uint64_t g = 0; g < h->G; ++g) w[g] = (w[g] & ~kTransfereeMask) | ((uint32_t)transferee[g] << kTransfereeShift);
+  HIPCHK(h, hipMemcpyAsync(h->cq, w.data(), h->G * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return RAFTQ_OK;
+}
+
+int raftq_read_transfer(raftq_t* h, uint8_t* transferee) {
+  if (int rc = use_device_idle(h, "raftq_read_transfer")) return rc;
+  if (!h->lead_transfer) return fail(h, RAFTQ_ESTATE, "raftq_read_transfer: raftq_set_lead_transfer is off (lead transfer): the handle holds no transferee");
+  if (!transferee) return fail(h, RAFTQ_EINVAL, "raftq_read_transfer: null transferee array");
+  std::vector<uint32_t> w(h->G);
+  HIPCHK(h, hipMemcpyAsync(w.data(), h->cq, h->G * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (uint64_t g = 0; g < h->G; ++g) transferee[g] = (uint8_t)((w[g] & kTransfereeMask) >> kTransfereeShift);
+  return RAFTQ_OK;
+}
+
 // the activity state as the ABI speaks it (two arrays) and as the device keeps it (one word per group)
 int raftq_load_activity(raftq_t* h, const uint16_t* active, const uint32_t* lead_elapsed) {
   if (int rc = use_device_idle(h, "raftq_load_activity")) return rc;
@@ -1201,12 +1257,12 @@ int raftq_load_activity(raftq_t* h, const uint16_t* active, const uint32_t* lead
       return fail(h, RAFTQ_EINVAL, "raftq_load_activity: lead_elapsed is kept in 16 bits: a value above 65535; nothing loaded");
   }
   std::vector<uint32_t> w(h->G);
-  if (!active || !lead_elapsed) {
+  if (!active || !lead_elapsed || h->lead_transfer) {  // (a pending transferee stays where it is: raftq_load_transfer's)
     HIPCHK(h, hipMemcpyAsync(w.data(), h->cq, h->G * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
   }
   for (uint64_t g = 0; g < h->G; ++g)
-    w[g] = (active ? active[g] : w[g] & 0xffffu) | (lead_elapsed ? lead_elapsed[g] << 16 : w[g] & 0xffff0000u);
+    w[g] = (active ? active[g] | (h->lead_transfer ? w[g] & kTransfereeMask : 0u) : w[g] & 0xffffu) | (lead_elapsed ? lead_elapsed[g] << 16 : w[g] & 0xffff0000u);
   HIPCHK(h, hipMemcpyAsync(h->cq, w.data(), h->G * 4, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return RAFTQ_OK;
@@ -1220,7 +1276,7 @@ int raftq_read_activity(raftq_t* h, uint16_t* active, uint32_t* lead_elapsed) {
   HIPCHK(h, hipMemcpyAsync(w.data(), h->cq, h->G * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   for (uint64_t g = 0; g < h->G; ++g) {
-    if (active) active[g] = (uint16_t)w[g];
+    if (active) active[g] = (uint16_t)(w[g] & ~kTransfereeMask);
     if (lead_elapsed) lead_elapsed[g] = w[g] >> 16;
   }
   return RAFTQ_OK;

@@ -108,6 +108,7 @@ struct raftq {
   uint32_t* cq = nullptr;        // [ld]
   uint64_t* chk_bits = nullptr;  // [gpad/64]
   bool pre_vote = false;         // raftq_set_pre_vote: only ever true while cq is set
+  bool lead_transfer = false;    // raftq_set_lead_transfer: likewise; leadTransferee is bits 12..15 of the cq word, which are 0 without it
   // raftq_tick_set_checks (0 = off): with cq set, the fused Tick calls run instead of refusing and leave the groups whose check failed as
   // a third in-place list of at most this many ids behind the beat bitmap in `tl` (raftq_last_tick_checks).  A property of the handle,
   // as tick_voters is: raftq_clone_state leaves it alone
@@ -318,6 +319,9 @@ inline bool masked_bcast(const raftq_t* h) { return h->voters != nullptr && h->b
 int refuse_check_quorum(raftq_t* h, const char* who, bool fused = false);
 // RAFTQ_ESTATE, "pre vote" in the text, on a handle with raftq_set_pre_vote on: a call that turns a MsgHup into becomeCandidate on the device
 int refuse_pre_vote(raftq_t* h, const char* who, bool fused = false);
+// RAFTQ_ESTATE, "lead transfer" in the text, on a handle with raftq_set_lead_transfer on: a call whose kernels append a leader's own
+// proposals without reading the word that says a transfer is pending
+int refuse_lead_transfer(raftq_t* h, const char* who);
 // raftq_tick_set_checks on a handle with raftq_set_check_quorum on: the fused calls launch tick_check_kernel, list the failed checks and
 // -- raftq_tick_elect_frames -- campaign through Node's CQ form (elect_build_cq_kernel / elect_build_cq_voters_kernel)
 inline bool tick_checks(const raftq_t* h) { return h->cq != nullptr && h->tick_chk_cap != 0; }

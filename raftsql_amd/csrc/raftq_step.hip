@@ -77,6 +77,7 @@ NodeArrays node_arrays(raftq_t* h, uint8_t recs = raftqk::kRecsCaller) {
   a.cq = h->cq;  // raftq_set_check_quorum: nullptr unless the switch is on
   a.election_tick = h->election_tick;
   a.pv = h->pre_vote;  // raftq_set_pre_vote: only ever on beside cq
+  a.lt = h->lead_transfer;  // raftq_set_lead_transfer: likewise
   if (h->resp_on) {  // raftq_step_frames_respond: the walks (the list walk, the sorted one, a stalled batch's replay) answer too
     a.resp = (raftqk::RespRec*)h->resp_dev.d;
     a.at_tail = h->resp_at_tail_d;
@@ -456,7 +457,7 @@ static int enqueue_sorted_walk(raftq_t* h, const Scratch& s, uint64_t n, int end
   unsigned int* bad = (unsigned int*)(s.n_heads + 1);
   const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
   hipLaunchKernelGGL(step_keys_kernel, grid, dim3(kBlock), 0, h->stream, (const MsgRec*)s.msgs, s.keys_in, s.order_in, n,
-                     h->G, h->N, bad, h->step_msg_flags, recs, s.outs, h->step_compact, h->step_props, h->cq != nullptr, h->pre_vote);
+                     h->G, h->N, bad, h->step_msg_flags, recs, s.outs, h->step_compact, h->step_props, h->cq != nullptr, h->pre_vote, h->lead_transfer);
   HIPCHK(h, hipGetLastError());
   int in_b = 0;  // which pair of buffers the sorted (group, batch position) pairs end up in
   HIPCHK(h, raftqk::radix_sort_pairs(h->stream, s.sort_scratch, s.keys_in, s.order_in, s.keys_out, s.order_out, n, end_bit, &in_b));
@@ -488,7 +489,7 @@ static int enqueue_list_walk(raftq_t* h, const Scratch& s, uint64_t n, uint8_t r
     in_walk = {(const u64x2*)carry->outs_d, (u64x2*)carry->out.d, cut, quads, quads - 1, d2h_blocks(quads - cut)};
   }
   hipLaunchKernelGGL(step_link_kernel, dim3(blocks + in_link.blocks), dim3(kBlock), 0, h->stream, (const MsgRec*)s.msgs, n, h->G,
-                     h->N, h->step_msg_flags, recs, (NodeRec*)h->node_rec, s.next, bad, h->step_stall, s.outs, h->step_compact, in_link, h->step_props, h->cq != nullptr, h->pre_vote);
+                     h->N, h->step_msg_flags, recs, (NodeRec*)h->node_rec, s.next, bad, h->step_stall, s.outs, h->step_compact, in_link, h->step_props, h->cq != nullptr, h->pre_vote, h->lead_transfer);
   HIPCHK(h, hipGetLastError());  // (the link kernel's, before the walk's launch can hide it)
   if (h->cq)  // raftq_set_check_quorum: NodeT's CQ form
     launch_walk(h, dim3(blocks + in_walk.blocks), step_lists_cq_kernel, step_lists_cq_voters_kernel, step_lists_cq_lead_kernel,

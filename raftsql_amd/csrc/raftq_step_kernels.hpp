@@ -106,16 +106,22 @@ struct NodeArrays {
   uint32_t election_tick = 0;
   // raftq_set_pre_vote (only ever true beside cq, and read by NodeT's CQ form alone): the five rules of include/raftq_step.h "PreVote"
   bool pv = false;
+  // raftq_set_lead_transfer (likewise): the rules of include/raftq_step.h "Leadership transfer"; leadTransferee is bits 12..15 of the cq word
+  bool lt = false;
 };
 constexpr uint8_t kRecsCaller = 0, kRecsWire = 1, kRecsFrames = 2;
 
 constexpr uint8_t kMsgHup = 0, kMsgBeat = 1, kMsgProp = 2, kMsgApp = 3, kMsgAppResp = 4, kMsgVote = 5, kMsgVoteResp = 6,
-                  kMsgHeartbeat = 8, kMsgHeartbeatResp = 9, kMsgCheckQuorum = 12, kMsgPreVote = 17, kMsgPreVoteResp = 18;
+                  kMsgHeartbeat = 8, kMsgHeartbeatResp = 9, kMsgCheckQuorum = 12, kMsgTransferLeader = 13, kMsgTimeoutNow = 14,
+                  kMsgPreVote = 17, kMsgPreVoteResp = 18;
 constexpr uint8_t kOutNone = 0, kOutVoteResp = 1, kOutHeartbeatResp = 2, kOutCampaign = 3, kOutBecameLeader = 4,
                   kOutProgress = 5, kOutBcastHeartbeat = 6, kOutAppend = 7, kOutAppended = 8, kOutDeferred = 9, kOutSkipped = 10,
-                  kOutHeld = 11, kOutProposed = 12, kOutForward = 13, kOutPreCampaign = 14, kOutPreVoteResp = 15, kOutTermResp = 16;
+                  kOutHeld = 11, kOutProposed = 12, kOutForward = 13, kOutPreCampaign = 14, kOutPreVoteResp = 15, kOutTermResp = 16,
+                  kOutTransfer = 17;
 constexpr uint8_t kMsgfEntries = 0x80, kMsgfBarrier = 0x40, kMsgfHold = 0x20, kMsgfSkip = 0x10;  // raftq_msg_t._pad[1]: RAFTQ_MSGF_*
 constexpr uint8_t kFlagHardState = 1, kFlagCommitted = 2, kFlagUpdated = 4, kFlagSteppedDown = 8;
+constexpr uint8_t kFlagTimeoutNow = 0x20;  // RAFTQ_OUTF_TIMEOUT_NOW: the transferee's Match is the tail -- send it MsgTimeoutNow
+constexpr uint32_t kCqTransfereeShift = 12, kCqTransfereeMask = 0xf000u;  // leadTransferee (0 = None, else slot + 1) in the cq word
 constexpr uint8_t kFlagAnswered = 0x10;  // RAFTQ_OUTF_ANSWERED: the messages the result calls for were built on the device
 
 // What result i calls for, as the walk lane that stepped it saw the group (raftq_step_frames_respond; raftq_respond_kernels.hpp
@@ -222,8 +228,10 @@ __device__ __forceinline__ uint64_t entry_count(const MsgRec& m, uint8_t recs) {
 // cq (raftq_set_check_quorum): RAFTQ_MSG_CHECK_QUORUM is a known, local kind in a caller's own records -- never in a record a
 // decoder made of a peer's frame.
 // pv (raftq_set_pre_vote): MsgPreVote and MsgPreVoteResp are known kinds, a peer's like MsgVote and MsgVoteResp, in every kind of record.
+// lt (raftq_set_lead_transfer): MsgTransferLeader and MsgTimeoutNow likewise -- a MsgTransferLeader's `from` is the transferee's slot in
+// its local form (term 0) too, so neither is a local kind: `from` >= N is malformed.
 __device__ __forceinline__ RecClass classify(const MsgRec& m, uint64_t n_groups, uint32_t n_peers, bool msg_flags, uint8_t recs, bool props,
-                                             bool cq = false, bool pv = false) {
+                                             bool cq = false, bool pv = false, bool lt = false) {
   const uint8_t fl = msg_flags ? m.pad[1] : (uint8_t)0;
   if (fl & kMsgfSkip) return kSkip;
   if (m.group >= n_groups) return kBad;
@@ -233,7 +241,8 @@ __device__ __forceinline__ RecClass classify(const MsgRec& m, uint64_t n_groups,
     return props && recs != kRecsWire && (fl & kMsgfEntries) != 0 && entry_count(m, recs) != 0 && m.from < n_peers ? kTake : kBad;
   const bool local = t == kMsgHup || t == kMsgBeat || (t == kMsgCheckQuorum && cq && recs == kRecsCaller);
   const bool known = local || t == kMsgApp || t == kMsgAppResp || t == kMsgVote || t == kMsgVoteResp ||
-                     t == kMsgHeartbeat || t == kMsgHeartbeatResp || (pv && (t == kMsgPreVote || t == kMsgPreVoteResp));
+                     t == kMsgHeartbeat || t == kMsgHeartbeatResp || (pv && (t == kMsgPreVote || t == kMsgPreVoteResp)) ||
+                     (lt && (t == kMsgTransferLeader || t == kMsgTimeoutNow));
   if (!known || (!local && m.from >= n_peers)) return kBad;
   // records decoded on the device from stream frames (raftq_step_submit_wire) also carry the addressee's slot and the
   // decoder's flags in the two pad bytes: a frame that did not parse, or one addressed to no peer of this cluster, fails
@@ -256,11 +265,11 @@ static __global__ __launch_bounds__(kBlock) void step_keys_kernel(const MsgRec* 
                                                                   uint32_t* __restrict__ order, uint64_t n,
                                                                   uint64_t n_groups, uint32_t n_peers,
                                                                   unsigned int* bad, bool msg_flags, uint8_t recs,
-                                                                  void* __restrict__ out, uint8_t compact, bool props, bool cq, bool pv) {
+                                                                  void* __restrict__ out, uint8_t compact, bool props, bool cq, bool pv, bool lt) {
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   bool is_bad = false;
   if (i < n) {
-    const RecClass c = classify(msgs[i], n_groups, n_peers, msg_flags, recs, props, cq, pv);
+    const RecClass c = classify(msgs[i], n_groups, n_peers, msg_flags, recs, props, cq, pv, lt);
     is_bad = c == kBad;
     // a skipped record sorts behind every group (the key range has room for n_groups itself) and is answered here
     keys[i] = c == kTake ? msgs[i].group : c == kSkip ? n_groups : 0;  // (bad: keep the sort's key range valid)
@@ -612,6 +621,7 @@ struct NodeT {
     const uint32_t q = quorum();
     bool handled = false;
     bool campaigns = false, won = false;  // CQ form only: campaign() / becomeLeader are due (one copy of each, behind the role arms)
+    bool transfer = false;                // ... and the campaign is a transfer's (MsgTimeoutNow): its MsgVotes go out marked
     if (m.type == kMsgHup) {
       handled = true;
       if (role != kLeader) {  // campaign()
@@ -648,7 +658,8 @@ struct NodeT {
         // PreVote: a MsgPreVote inside the lease likewise; outside it, and a granting MsgPreVoteResp, change no term and no role; a
         // rejecting MsgPreVoteResp makes a follower without a leader (CHOICE: its sender is no leader)
         if constexpr (CQ) {
-          const bool leased = (m.type == kMsgVote || (a.pv && m.type == kMsgPreVote)) && in_lease();
+          // Leadership transfer: a MsgVote marked as a transfer's (reject = 1) passes the lease
+          const bool leased = ((m.type == kMsgVote && !(a.lt && m.reject)) || (a.pv && m.type == kMsgPreVote)) && in_lease();
           const bool keep = a.pv && (m.type == kMsgPreVote || (m.type == kMsgPreVoteResp && !m.reject));
           if (leased) handled = true;
           else if (!keep) become_follower(m.term, (m.type == kMsgVote || (a.pv && m.type == kMsgPreVoteResp)) ? 0u : m.from + 1);
@@ -698,6 +709,23 @@ struct NodeT {
           const uint32_t act = (uint32_t)__popc(((w & 0xffffu) | (1u << a.self)) & members);
           set_cq(w & 0xffff0000u);
           if (act < q) become_follower(term, 0);
+        } else if (CQ && a.lt && m.type == kMsgTransferLeader) {
+          // stepLeader MsgTransferLeader: t = from.  A transfer to t already pending, or t no voter: ignored.  One to another slot is
+          // aborted first, and t == self stops there (which is how a pending transfer is cancelled); else leadTransferee = t + 1 and
+          // electionElapsed = 0, and the transferee gets MsgTimeoutNow if it is at the tail, sendAppend(t) -- the caller's -- if not
+          const uint32_t t = m.from, w = get_cq();
+          if (counts(t, a.n_peers) && (w & kCqTransfereeMask) >> kCqTransfereeShift != t + 1) {
+            uint32_t nw = w & ~kCqTransfereeMask;
+            if (t != a.self) {
+              nw = (nw & 0xffffu) | ((t + 1) << kCqTransfereeShift);
+              o.type = kOutTransfer;
+              o.index = match(t);
+              if (o.index == last_index) o.flags |= kFlagTimeoutNow;
+            }
+            if (nw != w) set_cq(nw);
+          }
+        } else if (CQ && a.lt && m.type == kMsgProp && (get_cq() & kCqTransfereeMask) != 0) {
+          // a transfer is pending: the proposal is dropped (ErrProposalDropped) -- RAFTQ_OUT_NONE, nothing moves
         } else if (m.type == kMsgVote) {
           o.type = kOutVoteResp; o.reject = 1;
         } else if (m.type == kMsgAppResp || m.type == kMsgProp) {
@@ -728,6 +756,11 @@ struct NodeT {
             (void)maybe_commit();
           }
           if (!prop) o.index = match(who);
+          // Leadership transfer: the pending transferee's ack that updated its Match to the tail -- send it MsgTimeoutNow
+          if constexpr (CQ) {
+            if (a.lt && (o.flags & kFlagUpdated) != 0 && (get_cq() & kCqTransfereeMask) >> kCqTransfereeShift == who + 1 && o.index == last_index)
+              o.flags |= kFlagTimeoutNow;
+          }
         } else if (m.type == kMsgHeartbeatResp) {
           o.type = kOutProgress;
           o.index = match(m.from);
@@ -782,8 +815,11 @@ struct NodeT {
           const bool up_to_date = m.log_term > last_term || (m.log_term == last_term && m.index >= last_index);
           if ((vote == 0 || vote == m.from + 1) && up_to_date) { elapsed_reset = true; vote = m.from + 1; }
           else o.reject = 1;
-        } else if (m.type == kMsgProp && lead != 0) {
-          o.type = kOutForward;  // stepFollower MsgProp: `m.To = r.lead; r.send(m)` -- the one result addressed to somebody else
+        } else if ((m.type == kMsgProp || (CQ && a.lt && m.type == kMsgTransferLeader)) && lead != 0) {
+          o.type = kOutForward;  // stepFollower MsgProp / MsgTransferLeader: `m.To = r.lead; r.send(m)` -- the one result addressed to somebody else
+        } else if (CQ && a.lt && m.type == kMsgTimeoutNow) {
+          // stepFollower MsgTimeoutNow: campaign(campaignTransfer) at once if promotable() -- the real campaign under PreVote too
+          campaigns = transfer = counts(a.self, a.n_peers);
         }
       }
     }
@@ -794,10 +830,12 @@ struct NodeT {
         poll(a.self, true, gr, rec);
         won = gr == q;
         o.type = kOutCampaign;
+        o.reject = transfer ? 1 : 0;
       }
       if (won) {
         become_leader();
         o.type = kOutBecameLeader;
+        o.reject = 0;
       }
       if (campaigns || won) { o.index = last_index; o.log_term = last_term; }
     }
@@ -846,7 +884,7 @@ static __global__ __launch_bounds__(kBlock) void step_link_kernel(const MsgRec* 
                                                                   uint64_t n_groups, uint32_t n_peers, bool msg_flags, uint8_t recs,
                                                                   NodeRec* rec, uint32_t* __restrict__ next,
                                                                   unsigned int* bad, unsigned int* stall,
-                                                                  void* __restrict__ out, uint8_t compact, CopyRide ride, bool props, bool cq, bool pv) {
+                                                                  void* __restrict__ out, uint8_t compact, CopyRide ride, bool props, bool cq, bool pv, bool lt) {
   if (blockIdx.x < ride.blocks) {
     copy_ride(ride);
     return;
@@ -854,7 +892,7 @@ static __global__ __launch_bounds__(kBlock) void step_link_kernel(const MsgRec* 
   const uint64_t i = (uint64_t)(blockIdx.x - ride.blocks) * kBlock + threadIdx.x;
   bool is_bad = false, too_long = false;
   if (i < n) {
-    const RecClass c = classify(msgs[i], n_groups, n_peers, msg_flags, recs, props, cq, pv);
+    const RecClass c = classify(msgs[i], n_groups, n_peers, msg_flags, recs, props, cq, pv, lt);
     is_bad = c == kBad;
     if (c == kTake) {
       NodeRec* r = rec + msgs[i].group;  // three atomics on one line

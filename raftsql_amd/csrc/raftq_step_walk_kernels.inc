@@ -10,7 +10,8 @@
 //   RAFTQ_WALK_VOTERS        the same, handed to NodeT's constructor (", voters")
 //   RAFTQ_WALK_NO_DELTAS     (optional) the two walks only: leave the tail reports out
 //   RAFTQ_WALK_CQ            true in the *_cq_* expansions (NodeT's CQ form, raftq_set_check_quorum): type 12 is a known kind there, and
-//                            under NodeArrays::pv (raftq_set_pre_vote) so are types 17 and 18 and RAFTQ_OUT_PRE_CAMPAIGN's packing
+//                            under NodeArrays::pv (raftq_set_pre_vote) so are types 17 and 18 and RAFTQ_OUT_PRE_CAMPAIGN's packing; under
+//                            NodeArrays::lt (raftq_set_lead_transfer) so are types 13 and 14
 // One text, four walks of each kind and two tail-report kernels.  Why an include and not a template <bool MASKED> body the kernels call: the inliner simplifies such
 // a body BEFORE it meets the kernel (no launch bounds, no noalias arguments, NodeArrays behind a generic reference), and all three
 // unmasked kernels came out different from their parent's -- step_lists_kernel with other loads and another register count
@@ -60,7 +61,7 @@ static __global__ __launch_bounds__(kBlock) void RAFTQ_WALK_KERNEL(step_lists)(N
   const bool stalled = *stall != 0;  // this batch, or one before it that has not been replayed yet, needs the sorted path
   if (stalled || *bad) {             // (*bad: a malformed record somewhere in the batch) -- nothing is applied;
     if (stalled && i == 0) *tail_skipped = 1u;
-    if (i < n && classify(msgs[i], n_groups, a.n_peers, a.msg_flags, a.recs, a.props, RAFTQ_WALK_CQ, RAFTQ_WALK_CQ && a.pv) == kTake) {  // every message empties its group's list words (idempotent)
+    if (i < n && classify(msgs[i], n_groups, a.n_peers, a.msg_flags, a.recs, a.props, RAFTQ_WALK_CQ, RAFTQ_WALK_CQ && a.pv, RAFTQ_WALK_CQ && a.lt) == kTake) {  // every message empties its group's list words (idempotent)
       NodeRec* r = a.rec + msgs[i].group;
       r->lst_head = kNil;
       r->lst_cnt = 0;

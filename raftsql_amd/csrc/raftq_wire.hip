@@ -524,6 +524,7 @@ int raftq_propose_frames(raftq_t* h, const raftq_prop_t* props, uint64_t n_props
                          uint64_t pool_bytes, void* out, uint64_t cap, uint64_t* frame_off, raftq_wire_counts_t* counts) {
   if (int rc = raftq_detail::use_device_idle(h, "raftq_propose_frames")) return rc;
   if (counts) *counts = raftq_wire_counts_t{0, 0, 0, 0};
+  if (int rc = raftq_detail::refuse_lead_transfer(h, "raftq_propose_frames")) return rc;
   h->prop_what_n = 0;  // (raftq_propose_outcomes: valid until the next call)
   if (n_props == 0)  // nothing proposed: the marshal of what the caller queued
     return raftq_wire_encode(h, msgs, n_msgs, ents, n_ents, pool, pool_bytes, out, cap, frame_off, counts);
@@ -716,7 +717,7 @@ int raftq_detail::wire_frames_enqueue(raftq_t* h, const void* stream, uint64_t n
   if (!v.ok)
     return fail(h, RAFTQ_EINVAL, "raftq_step_frames: the stream, the boundaries and the result arrays must be page-locked (raftq_host_alloc, "
                                  "hipHostMalloc, hipHostRegister) and 16-byte aligned -- decode and step in two calls otherwise");
-  const FrameFilter ff{(h->step_props ? 3u : 1u) | (h->pre_vote ? 4u : 0u), h->N, h->self_peer, tail_appends ? 1u : 0u, h->G, (unsigned long long*)zero2};
+  const FrameFilter ff{(h->step_props ? 3u : 1u) | (h->pre_vote ? 4u : 0u) | (h->lead_transfer ? 8u : 0u), h->N, h->self_peer, tail_appends ? 1u : 0u, h->G, (unsigned long long*)zero2};
   if (packed)
     return decode_streaming_enqueue(h, v_stream, nbytes, v_off, n, v_msgs, v_ents, ents ? ents_cap : 0, (WireMsg*)msgs_d, ff, packed->form,
                                     PackedOut{(WireMsg*)v_wide, wide ? packed->wide_cap : 0, packed->head_types, h->self_peer});

@@ -489,6 +489,25 @@ class QuorumEngine:
         property of the handle (no batch may be in flight)."""
         self._chk(self._lib.raftq_set_pre_vote(self._h, int(on)))
 
+    def set_lead_transfer(self, on=True) -> None:
+        """raftq_set_lead_transfer (include/raftq.h "Leadership transfer"): Step runs MsgTransferLeader (13) and MsgTimeoutNow (14), a
+        MsgVote marked reject = 1 passes the lease, a leader with a transfer pending drops MsgProp.  Requires set_check_quorum; a
+        property of the handle (no batch may be in flight).  Turning it off clears every pending transferee."""
+        self._chk(self._lib.raftq_set_lead_transfer(self._h, int(on)))
+
+    def load_transfer(self, transferee: np.ndarray) -> None:
+        """transferee [G] u8: 0 = None, else peer slot + 1 (raftq_load_transfer)"""
+        t = np.ascontiguousarray(transferee, dtype=np.uint8)
+        if t.shape != (self.n_groups,):
+            raise ValueError("transferee must be [G]")
+        self._chk(self._lib.raftq_load_transfer(self._h, _ptr(t)))
+
+    def read_transfer(self) -> np.ndarray:
+        """every group's leadTransferee: 0 = None, else peer slot + 1 (raftq_read_transfer)"""
+        t = np.empty(self.n_groups, dtype=np.uint8)
+        self._chk(self._lib.raftq_read_transfer(self._h, _ptr(t)))
+        return t
+
     def load_activity(self, active: Optional[np.ndarray] = None, lead_elapsed: Optional[np.ndarray] = None) -> None:
         """active [G] u16 (bit p = peer p answered since the last check), lead_elapsed [G] u32 (a leader's electionElapsed)"""
         a = None if active is None else np.ascontiguousarray(active, dtype=np.uint16)

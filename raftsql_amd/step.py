@@ -20,6 +20,7 @@ from .engine import QuorumEngine, _ptr
 MSG_HUP, MSG_BEAT, MSG_APP, MSG_APP_RESP, MSG_VOTE, MSG_VOTE_RESP, MSG_HEARTBEAT, MSG_HEARTBEAT_RESP = 0, 1, 3, 4, 5, 6, 8, 9
 MSG_PROP = 2  # a follower's forwarded proposal: stepped only under set_step_props (MSGF_ENTRIES + its count in _resv)
 MSG_CHECK_QUORUM = 12  # local: a leader's check failed in tick() (collect_checks): stepped only under set_check_quorum
+MSG_TRANSFER_LEADER, MSG_TIMEOUT_NOW = 13, 14  # from = the transferee (local at term 0, or forwarded); a peer's: stepped only under set_lead_transfer
 MSG_PRE_VOTE, MSG_PRE_VOTE_RESP = 17, 18  # a peer's pre-election (MsgVote's fields): stepped only under set_pre_vote
 MSG_TYPES = (MSG_HUP, MSG_BEAT, MSG_APP, MSG_APP_RESP, MSG_VOTE, MSG_VOTE_RESP, MSG_HEARTBEAT, MSG_HEARTBEAT_RESP)
 
@@ -30,10 +31,12 @@ OUT_SKIPPED, OUT_HELD = 10, 11  # MSGF_SKIP: nobody's, nothing looked at; MSGF_H
 OUT_PROPOSED, OUT_FORWARD = 12, 13  # set_step_props: the leader took a MsgProp (index = first new index); a follower's goes on to lead - 1
 # set_pre_vote: became pre-candidate (send MsgPreVote at term + 1); send MsgPreVoteResp{Term: index}; tell a stale leader the term
 OUT_PRE_CAMPAIGN, OUT_PRE_VOTE_RESP, OUT_TERM_RESP = 14, 15, 16
+OUT_TRANSFER = 17  # set_lead_transfer: the leader took a MsgTransferLeader (to = the transferee, index = its Match)
 MSGF_SKIP, MSGF_HOLD = 0x10, 0x20
 MSGF_BARRIER = 0x40  # on a MsgApp: if it is answered OUT_APPEND, the group's later messages of the batch are deferred
 MSGF_ENTRIES = 0x80  # msgs["_pad"][:, 1]: _resv = number of entries, reject_hint = the last one's term (raftq_step.h)
 OUTF_HARDSTATE, OUTF_COMMITTED, OUTF_UPDATED, OUTF_STEPPED_DOWN = 1, 2, 4, 8
+OUTF_TIMEOUT_NOW = 0x20  # set_lead_transfer: the pending transferee `to` is at the tail: send it MsgTimeoutNow
 
 ROLE_FOLLOWER, ROLE_CANDIDATE, ROLE_LEADER = 0, 1, 2
 ROLE_PRE_CANDIDATE = 3  # only under set_pre_vote

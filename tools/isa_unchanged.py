@@ -3,7 +3,9 @@
 compiled device-only for gfx950 (-S, the library's flags, -Rpass-analysis=kernel-resource-usage) at the parent and here; the
 assembly is cut into its functions and compared name by name, the resource remarks kernel by kernel.  Needs no GPU.
 
-usage: tools/isa_unchanged.py PARENT_REV out.txt   (the method of profiles/r09/isa_sweeps_unchanged.txt and profiles/r10/isa_unchanged.txt)
+usage: tools/isa_unchanged.py PARENT_REV out.txt [table.md]   (the method of profiles/r09/isa_sweeps_unchanged.txt and profiles/r10/isa_unchanged.txt)
+table.md, when given, receives one markdown row per kernel whose body or remarks differ: SGPRs, VGPRs, spills, scratch, occupancy and
+LDS, parent / here (what profiles/rNN/README.md tabulates).
 """
 import hashlib
 import os
@@ -55,6 +57,21 @@ def remarks(err):
     return {k: " ".join(v) for k, v in out.items()}
 
 
+def table(changed):
+    """markdown rows of [(demangled name, parent's remarks, this tree's)]"""
+    keys = ("TotalSGPRs", "VGPRs", "SGPRs Spill", "VGPRs Spill", "ScratchSize", "Occupancy", "LDS Size")
+    rows = ["| kernel | " + " | ".join(k + (" parent / here" if i == 0 else "") for i, k in enumerate(keys)) + " |", "|" + "---|" * (len(keys) + 1)]
+    seen = set()
+    for name, r0, r1 in changed:
+        if name in seen:  # (a kernel of a shared header is compiled into more than one unit)
+            continue
+        seen.add(name)
+        d0, d1 = ({k.strip(): v for k, v in re.findall(r"([A-Za-z][A-Za-z ]*)=(\S+)", r)} for r in (r0, r1))
+        get = lambda d, k: d.get(k, "-")  # noqa: E731
+        rows.append("| `%s` | " % name + " | ".join("%s / %s" % (get(d0, k), get(d1, k)) for k in keys) + " |")
+    return "\n".join(rows) + "\n"
+
+
 def digest(fns, names):
     h = hashlib.sha256()
     for n in sorted(names):
@@ -83,6 +100,7 @@ def main():
              "gives a function by its position in the file (.LBB<k>_, BB<k>_, .Lfunc_begin<k>, .Lfunc_end<k>, .Ltmp<k>) and making runs of",
              "blanks one blank; the resource remarks (SGPRs, VGPRs, AGPRs, scratch, occupancy, spills, LDS) compared kernel by kernel as text.", ""]
     bad = 0
+    changed = []
     for u in UNITS:
         (f0, r0), (f1, r1) = res[("parent", u)], res[("here", u)]
         missing = sorted(set(f0) - set(f1))
@@ -90,6 +108,13 @@ def main():
         rdiff = sorted(k for k in r0 if r1.get(k) != r0[k])
         new = sorted(set(f1) - set(f0))
         bad += len(missing) + len(differ) + len(rdiff)
+        base = lambda k: subprocess.run(["c++filt", k], capture_output=True, text=True).stdout.strip().split("(")[0]  # noqa: E731
+        for k in sorted(set(differ + rdiff) & set(r0) & set(r1)):
+            changed.append((base(k), r0[k], r1[k]))
+        renamed = {base(k): k for k in new if k in r1}  # a kernel whose signature changed has another mangled name
+        for k in missing:
+            if k in r0 and base(k) in renamed:
+                changed.append((base(k) + " (new signature)", r0[k], r1[renamed[base(k)]]))
         dem = subprocess.run(["c++filt"] + new, capture_output=True, text=True).stdout.split("\n") if new else []
         common = [n for n in f0 if n in f1]
         lines += ["%s: %d kernels with resource remarks at the parent, %d here; %d functions at the parent, %d here" % (u, len(r0), len(r1), len(f0), len(f1)),
@@ -102,6 +127,8 @@ def main():
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     open(out_path, "w").write("\n".join(lines) + "\n")
     print("\n".join(lines))
+    if len(sys.argv) > 3:
+        open(sys.argv[3], "w").write(table(changed))
     sys.exit(1 if bad else 0)
 
 
