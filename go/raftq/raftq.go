@@ -349,6 +349,54 @@ func (e *Engine) ReadTransfer(transferee []uint8) error {
 	return e.err(C.raftq_read_transfer(e.h, (*C.uint8_t)(unsafe.Pointer(&transferee[0]))))
 }
 
+// Read modes of SetReadIndex (raftq_set_read_index; include/raftq.h "ReadIndex").
+const (
+	ReadOff   = 0
+	ReadSafe  = C.RAFTQ_READ_SAFE  // a read waits for a quorum of heartbeat acknowledgements that carry its sequence number
+	ReadLease = C.RAFTQ_READ_LEASE // the CheckQuorum lease releases it at once
+)
+
+// SetReadIndex opts the engine in to (or, with ReadOff, out of) upstream's ReadIndex: Msgs of type MsgReadIndex / MsgReadIndexResp
+// are stepped, a leader answers OutReadIndex, a heartbeat's Index carries a read's context and is echoed.  Requires
+// SetCheckQuorum(true) (ErrState otherwise, and SetCheckQuorum(false) returns ErrState while it is on); with ReadSafe TickFrames and
+// TickElectFrames return ErrState meanwhile.  A property of the engine; no batch may be in flight.  Every change of mode zeroes the
+// read records.
+func (e *Engine) SetReadIndex(mode int) error {
+	v := C.int(mode)
+	return e.err(C.raftq_set_read_index(e.h, v))
+}
+
+// LoadReads sets every group's read record: seq [G], acked [N][G]; nil leaves that half alone (raftq_load_reads, ReadSafe only).
+func (e *Engine) LoadReads(seq []uint32, acked []uint32) error {
+	var s *C.uint32_t
+	var a *C.uint32_t
+	if seq != nil {
+		s = (*C.uint32_t)(unsafe.Pointer(&seq[0]))
+	}
+	if acked != nil {
+		a = (*C.uint32_t)(unsafe.Pointer(&acked[0]))
+	}
+	return e.err(C.raftq_load_reads(e.h, s, a))
+}
+
+// ReadReads copies them back with confirmed [G], the q-th largest acknowledgement over each group's members; any slice may be nil
+// (raftq_read_reads).
+func (e *Engine) ReadReads(seq []uint32, acked []uint32, confirmed []uint32) error {
+	var s *C.uint32_t
+	var a *C.uint32_t
+	var c *C.uint32_t
+	if seq != nil {
+		s = (*C.uint32_t)(unsafe.Pointer(&seq[0]))
+	}
+	if acked != nil {
+		a = (*C.uint32_t)(unsafe.Pointer(&acked[0]))
+	}
+	if confirmed != nil {
+		c = (*C.uint32_t)(unsafe.Pointer(&confirmed[0]))
+	}
+	return e.err(C.raftq_read_reads(e.h, s, a, c))
+}
+
 // LoadActivity sets every group's activity word (bit p = peer slot p answered since the last check) and / or every leader's
 // electionElapsed; nil leaves that half alone (raftq_load_activity).
 func (e *Engine) LoadActivity(active []uint16, leadElapsed []uint32) error {

@@ -27,6 +27,8 @@ const (
 	MsgCheckQuorum   = C.RAFTQ_MSG_CHECK_QUORUM // local: a leader's failed check (CollectChecks); stepped only after SetCheckQuorum(true)
 	MsgTransferLeader = C.RAFTQ_MSG_TRANSFER_LEADER // From = the transferee (local at Term 0, or forwarded); stepped only after SetLeadTransfer(true)
 	MsgTimeoutNow     = C.RAFTQ_MSG_TIMEOUT_NOW
+	MsgReadIndex      = C.RAFTQ_MSG_READ_INDEX      // From = the requester (local at Term 0, or forwarded); stepped only after SetReadIndex
+	MsgReadIndexResp  = C.RAFTQ_MSG_READ_INDEX_RESP // the leader's answer to a forwarded read, Index = the read's index
 	MsgPreVote       = C.RAFTQ_MSG_PRE_VOTE      // a peer's pre-election, MsgVote's fields; stepped only after SetPreVote(true)
 	MsgPreVoteResp   = C.RAFTQ_MSG_PRE_VOTE_RESP
 )
@@ -123,10 +125,13 @@ const (
 	OutPreVoteResp    = C.RAFTQ_OUT_PRE_VOTE_RESP // SetPreVote: send MsgPreVoteResp{To, Term: Index, Reject}
 	OutTransfer       = C.RAFTQ_OUT_TRANSFER      // SetLeadTransfer: leader took a MsgTransferLeader, To = the transferee, Index = its Match
 	OutTermResp       = C.RAFTQ_OUT_TERM_RESP     // SetPreVote: a stale leader's MsgApp / MsgHeartbeat, send MsgAppResp{To, Term}
+	OutReadIndex      = C.RAFTQ_OUT_READ_INDEX    // SetReadIndex: leader took a MsgReadIndex, To = the requester, Index = the read's index, LogTerm = its sequence number
+	OutReadState      = C.RAFTQ_OUT_READ_STATE    // SetReadIndex: the leader answered a read this node forwarded, good at Index
 
 	FlagHardState   = C.RAFTQ_OUTF_HARDSTATE // persist {Term, Vote, Commit} before sending (raft.go:228-230)
 	FlagCommitted   = C.RAFTQ_OUTF_COMMITTED
 	FlagTimeoutNow  = C.RAFTQ_OUTF_TIMEOUT_NOW // SetLeadTransfer: the pending transferee To is at the tail, send MsgTimeoutNow{To, Term}
+	FlagReadReady   = C.RAFTQ_OUTF_READ_READY  // SetReadIndex: release the read (OutReadIndex) / every queued read with sequence <= LogTerm (OutProgress)
 	FlagUpdated     = C.RAFTQ_OUTF_UPDATED
 	FlagSteppedDown = C.RAFTQ_OUTF_STEPPED_DOWN
 )

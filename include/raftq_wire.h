@@ -226,6 +226,10 @@ int raftq_step_wire_entries(raftq_t* h, const raftq_wire_ent_t** ents, uint64_t*
  *     peer sends, checked as the others are and flagged as little; without it they stay frames of a kind a peer never sends.
  *     (Likewise types 17 and 18 under raftq_set_pre_vote.)  raftq_step_frames_packed and raftq_step_submit_wire take them the same
  *     way.  No encoder builds the two kinds on the device.
+ *   - MsgReadIndex, MsgReadIndexResp (types 15 and 16): on a handle that opted in to raftq_set_read_index (raftq.h, either mode)
+ *     kinds a peer sends, in the same way; without it they stay frames of a kind a peer never sends.  A MsgReadIndex frame carries
+ *     its context as an entry: it is a wide record in the packed form, like every frame with entries, and is flagged no differently
+ *     from a MsgVote.  No encoder builds the two kinds on the device (the context bytes are host memory).
  *   - MsgApp: RAFTQ_MSGF_BARRIER, and with tail_appends != 0 RAFTQ_MSGF_ENTRIES (reject_hint, which a MsgApp does not use, is
  *     overwritten with the Term of its last entry) -- one that lands on the log's tail is RAFTQ_OUT_APPENDED.
  * Results: raftq_step_results (or _c), n records, out[i] answers frame i.  msgs / ents / counts as raftq_wire_decode, except
@@ -271,6 +275,11 @@ int raftq_step_frames_packed(raftq_t* h, const void* stream, uint64_t nbytes, co
  * (RAFTQ_OUT_FORWARD) and a campaign from MsgTimeoutNow are the host's in the same way: no RAFTQ_OUTF_ANSWERED, and they end their
  * group's device-answered prefix.  RAFTQ_OUTF_TIMEOUT_NOW is always the host's to send; on a committing ack it does not stop the
  * commit broadcast from being built and flagged RAFTQ_OUTF_ANSWERED -- the result then carries both flags.
+ * Under raftq_set_read_index (raftq_step.h "ReadIndex in Step") a device-built MsgHeartbeatResp carries Index = the heartbeat's
+ * Index, the read context it echoes (with a zero context the bytes are what they were); RAFTQ_OUT_READ_INDEX,
+ * RAFTQ_OUT_READ_STATE and a forwarded MsgReadIndex are the host's, as above; RAFTQ_OUTF_READ_READY on a progress result ends no
+ * prefix.  In RAFTQ_READ_SAFE raftq_tick_frames and raftq_tick_elect_frames return RAFTQ_ESTATE ("read index"): their heartbeats
+ * do not carry the pending context.
  * at_tail ([ceil(G / 64)] words, bit g = group g; NULL = all clear): the caller's word that it leads g and every follower's
  * Progress.Next is lastIndex + 1 now (Next is the caller's, raftq_step.h).  A wrong set bit is the caller's bug, a clear one
  * only costs speed.  The device clears g's bit from g's first message on that makes the host move a Next away from the tail:

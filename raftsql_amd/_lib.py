@@ -31,6 +31,7 @@ CYCLE_SEGMENTED = 0x200  # raftq_cycle_packed: the advance list may be left in s
 SET_GRID, SET_PERSISTENT = 0, 1
 
 MAX_PEERS = 9
+READ_SAFE, READ_LEASE = 1, 2  # raftq_set_read_index: a quorum of heartbeat acknowledgements | the CheckQuorum lease
 
 
 class Counts(C.Structure):
@@ -109,6 +110,9 @@ _SIGS = [
     ("raftq_set_lead_transfer", C.c_int, [_H, C.c_int]),
     ("raftq_load_transfer", C.c_int, [_H, C.c_void_p]),
     ("raftq_read_transfer", C.c_int, [_H, C.c_void_p]),
+    ("raftq_set_read_index", C.c_int, [_H, C.c_int]),
+    ("raftq_load_reads", C.c_int, [_H, C.c_void_p, C.c_void_p]),
+    ("raftq_read_reads", C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("raftq_load_activity", C.c_int, [_H, C.c_void_p, C.c_void_p]),
     ("raftq_read_activity", C.c_int, [_H, C.c_void_p, C.c_void_p]),
     ("raftq_collect_checks", C.c_int, [_H, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),

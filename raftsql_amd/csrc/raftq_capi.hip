@@ -469,7 +469,7 @@ void raftq_destroy(raftq_t* h) {
   // every wait is over: memory may go
   raftq_buf::free_device(h->match, h->committed[0], h->committed[1], h->first_idx, h->votes, h->voters, h->outcome, h->changed_bits,
                          h->partials, h->offsets, h->self_max, h->anchor, h->moff, h->claim, h->delta_bad, h->role, h->elapsed, h->action, h->hup_bits,
-                         h->beat_bits, h->tick_partials, h->tick_offsets2, h->tick_offsets3, h->cq, h->chk_bits);
+                         h->beat_bits, h->tick_partials, h->tick_offsets2, h->tick_offsets3, h->cq, h->chk_bits, h->reads);
   raftq_buf::free_host(h->h_partials, h->h_total);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -1087,6 +1087,11 @@ int raftq_detail::refuse_lead_transfer(raftq_t* h, const char* who) {
   return fail(h, RAFTQ_ESTATE, std::string(who) + ": raftq_set_lead_transfer is on (lead transfer): a leader drops its own proposals while a transfer is "
                                                   "pending, and this call's kernels do not read the word that says so");
 }
+int raftq_detail::refuse_read_index(raftq_t* h, const char* who) {
+  if (h->read_index != RAFTQ_READ_SAFE) return RAFTQ_OK;
+  return fail(h, RAFTQ_ESTATE, std::string(who) + ": raftq_set_read_index is RAFTQ_READ_SAFE (read index): this call's device-built heartbeats do not carry "
+                                                  "the pending read's context -- step the MsgBeat (RAFTQ_OUT_BCAST_HEARTBEAT, index) and send the round");
+}
 constexpr uint32_t kCheckQuorumMaxTick = 0xffffu;  // lead_elapsed shares its word with the activity bits (raftq_t::cq)
 
 static int ensure_tick_offsets2(raftq_t* h, uint64_t nw);
@@ -1176,6 +1181,8 @@ int raftq_set_check_quorum(raftq_t* h, int on) {
     return fail(h, RAFTQ_ESTATE, "raftq_set_check_quorum: raftq_set_pre_vote is on (pre vote) and requires the lease: turn it off first");
   if (on == 0 && h->lead_transfer)
     return fail(h, RAFTQ_ESTATE, "raftq_set_check_quorum: raftq_set_lead_transfer is on (lead transfer) and keeps its state in the lease's word: turn it off first");
+  if (on == 0 && h->read_index)
+    return fail(h, RAFTQ_ESTATE, "raftq_set_check_quorum: raftq_set_read_index is on (read index) and its rules live in the lease's walks: turn it off first");
   if (on == 1) {
     if (int rc = ensure_tick_state(h)) return rc;
     HIPCHK(h, raftq_buf::alloc_group({{(void**)&h->cq, h->ld * 4}, {(void**)&h->chk_bits, h->gpad / 8}}, h->stream));
@@ -1243,6 +1250,111 @@ int raftq_read_transfer(raftq_t* h, uint8_t* transferee) {
   HIPCHK(h, hipMemcpyAsync(w.data(), h->cq, h->G * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   for (uint64_t g = 0; g < h->G; ++g) transferee[g] = (uint8_t)((w[g] & kTransfereeMask) >> kTransfereeShift);
+  return RAFTQ_OK;
+}
+
+// ---- ReadIndex (include/raftq.h "ReadIndex"): the switch, and the safe mode's records in bulk
+int raftq_set_read_index(raftq_t* h, int mode) {
+  if (int rc = use_device_idle(h, "raftq_set_read_index")) return rc;
+  if (mode != 0 && mode != RAFTQ_READ_SAFE && mode != RAFTQ_READ_LEASE)
+    return fail(h, RAFTQ_EINVAL, "raftq_set_read_index: 0 (types 15 and 16 are unknown kinds), RAFTQ_READ_SAFE (a read waits for a quorum of heartbeat "
+                                 "acknowledgements that carry its number) or RAFTQ_READ_LEASE (the CheckQuorum lease releases it at once)");
+  if (mode != 0 && !h->cq)
+    return fail(h, RAFTQ_ESTATE, "raftq_set_read_index: requires raftq_set_check_quorum (check quorum): the lease mode reads under the lease, and the "
+                                 "safe mode's rules live in the same walks");
+  if (mode == h->read_index) return RAFTQ_OK;
+  // every change of mode zeroes the records; only the safe mode holds any
+  if (mode == RAFTQ_READ_SAFE) {
+    if (!h->reads) HIPCHK(h, raftq_buf::alloc_group({{&h->reads, h->ld * sizeof(raftqk::ReadRec)}}, h->stream));
+    else HIPCHK(h, hipMemsetAsync(h->reads, 0, h->ld * sizeof(raftqk::ReadRec), h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  } else if (h->reads) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    raftq_buf::free_device(h->reads);
+  }
+  h->read_index = (uint8_t)mode;
+  return RAFTQ_OK;
+}
+
+// confirmed(g): the q-th largest acknowledgement over the group's members -- every slot, or the loaded voters (q_g = popcount / 2 + 1)
+// where Step runs over them (NodeT::confirmed restated for the host)
+static uint32_t reads_confirmed(const raftqk::ReadRec& r, uint32_t members) {
+  const uint32_t q = (uint32_t)__builtin_popcount(members) / 2 + 1;
+  uint32_t best = 0;
+  for (uint32_t c = 0; c < (uint32_t)raftqk::kMaxPeers; ++c) {
+    if (!((members >> c) & 1u)) continue;
+    uint32_t ge = 0;
+    for (uint32_t p = 0; p < (uint32_t)raftqk::kMaxPeers; ++p) ge += ((members >> p) & 1u) != 0 && r.acked[p] >= r.acked[c];
+    if (ge >= q && r.acked[c] > best) best = r.acked[c];
+  }
+  return best;
+}
+
+// Set-up and test traffic, not a hot path: the records cross the link in slices of kReadsChunk groups (64 MB of pageable staging),
+// whatever the handle's size.
+constexpr uint64_t kReadsChunk = 1ull << 20;
+
+int raftq_load_reads(raftq_t* h, const uint32_t* seq, const uint32_t* acked) {
+  if (int rc = use_device_idle(h, "raftq_load_reads")) return rc;
+  if (h->read_index != RAFTQ_READ_SAFE)
+    return fail(h, RAFTQ_ESTATE, "raftq_load_reads: raftq_set_read_index is not RAFTQ_READ_SAFE (read index): the handle holds no read records");
+  if (!seq && !acked) return RAFTQ_OK;
+  const uint64_t chunk = std::min<uint64_t>(h->G, kReadsChunk);
+  std::vector<raftqk::ReadRec> w(chunk);
+  raftqk::ReadRec* dev = (raftqk::ReadRec*)h->reads;
+  // two passes, so that a refused call has loaded nothing: every slice is validated before the first one is written
+  for (int pass = 0; pass < 2; ++pass) {
+    for (uint64_t g0 = 0; g0 < h->G; g0 += chunk) {
+      const uint64_t n = std::min(chunk, h->G - g0);
+      if (!seq || !acked) {  // (one half stands: it is read back)
+        HIPCHK(h, hipMemcpyAsync(w.data(), dev + g0, n * sizeof(raftqk::ReadRec), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+      } else {
+        std::memset(w.data(), 0, n * sizeof(raftqk::ReadRec));
+      }
+      for (uint64_t k = 0; k < n; ++k) {
+        const uint64_t g = g0 + k;
+        if (seq) w[k].seq = seq[g];
+        for (uint32_t p = 0; p < h->N; ++p) {
+          if (acked) w[k].acked[p] = acked[(uint64_t)p * h->G + g];
+          if (w[k].acked[p] > w[k].seq)
+            return fail(h, RAFTQ_EINVAL, "raftq_load_reads: an acknowledged number above its group's seq (nobody acknowledges a request that was not made); nothing loaded");
+        }
+      }
+      if (pass == 1) {
+        HIPCHK(h, hipMemcpyAsync(dev + g0, w.data(), n * sizeof(raftqk::ReadRec), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));  // (w is reused by the next slice)
+      }
+    }
+  }
+  return RAFTQ_OK;
+}
+
+int raftq_read_reads(raftq_t* h, uint32_t* seq, uint32_t* acked, uint32_t* confirmed) {
+  if (int rc = use_device_idle(h, "raftq_read_reads")) return rc;
+  if (h->read_index != RAFTQ_READ_SAFE)
+    return fail(h, RAFTQ_ESTATE, "raftq_read_reads: raftq_set_read_index is not RAFTQ_READ_SAFE (read index): the handle holds no read records");
+  const uint64_t chunk = std::min<uint64_t>(h->G, kReadsChunk);
+  std::vector<raftqk::ReadRec> w(chunk);
+  std::vector<uint16_t> masks;
+  // the form Step launches on this handle (raftq_step.hip masked_step()): over the masks under raftq_step_set_voters, and in
+  // raftq_step_frames_respond under raftq_bcast_set_voters -- the one Step-family call a masked handle without the first switch runs
+  const bool masked = h->voters != nullptr && (h->step_voters || h->bcast_voters);
+  if (confirmed && masked) masks.resize(chunk);
+  for (uint64_t g0 = 0; g0 < h->G; g0 += chunk) {
+    const uint64_t n = std::min(chunk, h->G - g0);
+    if (confirmed && masked)
+      HIPCHK(h, hipMemcpyAsync(masks.data(), (const uint16_t*)h->voters + g0, n * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(w.data(), (const raftqk::ReadRec*)h->reads + g0, n * sizeof(raftqk::ReadRec), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (uint64_t k = 0; k < n; ++k) {
+      const uint64_t g = g0 + k;
+      if (seq) seq[g] = w[k].seq;
+      if (acked)
+        for (uint32_t p = 0; p < h->N; ++p) acked[(uint64_t)p * h->G + g] = w[k].acked[p];
+      if (confirmed) confirmed[g] = reads_confirmed(w[k], masked ? masks[k] : (1u << h->N) - 1u);
+    }
+  }
   return RAFTQ_OK;
 }
 
@@ -2505,6 +2617,8 @@ int raftq_clone_state(raftq_t* dst, raftq_t* src) {
   if (src->voters) HIPCHK(dst, hipMemcpyAsync(dst->voters, src->voters, ld * sizeof(uint16_t), hipMemcpyDeviceToDevice, dst->stream));
   // the activity words where both handles hold them (raftq_set_check_quorum is each handle's own)
   if (src->cq && dst->cq) HIPCHK(dst, hipMemcpyAsync(dst->cq, src->cq, ld * sizeof(uint32_t), hipMemcpyDeviceToDevice, dst->stream));
+  // ... and the read records likewise (raftq_set_read_index)
+  if (src->reads && dst->reads) HIPCHK(dst, hipMemcpyAsync(dst->reads, src->reads, ld * sizeof(raftqk::ReadRec), hipMemcpyDeviceToDevice, dst->stream));
   HIPCHK(dst, hipStreamSynchronize(dst->stream));
   dst->have_terms = src->have_terms;
   dense_changed(dst);

@@ -109,6 +109,10 @@ struct raftq {
   uint64_t* chk_bits = nullptr;  // [gpad/64]
   bool pre_vote = false;         // raftq_set_pre_vote: only ever true while cq is set
   bool lead_transfer = false;    // raftq_set_lead_transfer: likewise; leadTransferee is bits 12..15 of the cq word, which are 0 without it
+  // raftq_set_read_index: 0 = off, RAFTQ_READ_SAFE, RAFTQ_READ_LEASE; only ever non-zero while cq is set.  reads: [ld] 64-byte records
+  // {seq, acked[RAFTQ_MAX_PEERS], pad} (raftqk::ReadRec) that Step alone touches, allocated in the safe mode only
+  uint8_t read_index = 0;
+  void* reads = nullptr;
   // raftq_tick_set_checks (0 = off): with cq set, the fused Tick calls run instead of refusing and leave the groups whose check failed as
   // a third in-place list of at most this many ids behind the beat bitmap in `tl` (raftq_last_tick_checks).  A property of the handle,
   // as tick_voters is: raftq_clone_state leaves it alone
@@ -322,6 +326,9 @@ int refuse_pre_vote(raftq_t* h, const char* who, bool fused = false);
 // RAFTQ_ESTATE, "lead transfer" in the text, on a handle with raftq_set_lead_transfer on: a call whose kernels append a leader's own
 // proposals without reading the word that says a transfer is pending
 int refuse_lead_transfer(raftq_t* h, const char* who);
+// RAFTQ_ESTATE, "read index" in the text, on a handle with raftq_set_read_index(h, RAFTQ_READ_SAFE): a call whose device-built
+// heartbeat round would not carry the pending read's context
+int refuse_read_index(raftq_t* h, const char* who);
 // raftq_tick_set_checks on a handle with raftq_set_check_quorum on: the fused calls launch tick_check_kernel, list the failed checks and
 // -- raftq_tick_elect_frames -- campaign through Node's CQ form (elect_build_cq_kernel / elect_build_cq_voters_kernel)
 inline bool tick_checks(const raftq_t* h) { return h->cq != nullptr && h->tick_chk_cap != 0; }

@@ -31,6 +31,16 @@ constexpr int kWaves = kBlock / 64;
 constexpr int kMaxPeers = 9;
 constexpr int kTileMax = 2048;       // groups per block at GPL=8; ld granule
 
+// raftq_set_read_index(h, RAFTQ_READ_SAFE): one record per group, touched by Step alone (raftq_step_kernels.hpp NodeT::get_rd: read
+// lazily, written back when dirty) and by the host's bulk calls -- the read requests this leadership has taken and the largest of
+// them each peer has acknowledged
+struct __attribute__((aligned(64))) ReadRec {
+  uint32_t seq;
+  uint32_t acked[kMaxPeers];
+  uint32_t pad[15 - kMaxPeers];
+};
+static_assert(sizeof(ReadRec) == 64, "one record per group, half a line");
+
 struct SweepArgs {
   const uint64_t* match;       // [N][ld]
   const uint64_t* committed;   // [ld]   current commit index

@@ -78,6 +78,7 @@ NodeArrays node_arrays(raftq_t* h, uint8_t recs = raftqk::kRecsCaller) {
   a.election_tick = h->election_tick;
   a.pv = h->pre_vote;  // raftq_set_pre_vote: only ever on beside cq
   a.lt = h->lead_transfer;  // raftq_set_lead_transfer: likewise
+  a.ri = h->read_index;     // raftq_set_read_index: likewise (its records go to the *_cq_* walks as a parameter: launch_walk_cq)
   if (h->resp_on) {  // raftq_step_frames_respond: the walks (the list walk, the sorted one, a stalled batch's replay) answer too
     a.resp = (raftqk::RespRec*)h->resp_dev.d;
     a.at_tail = h->resp_at_tail_d;
@@ -170,6 +171,22 @@ void launch_walk(const raftq_t* h, dim3 grid, void (*plain)(A...), typename as_i
     hipLaunchKernelGGL((lead_form ? lead_voters : voters), grid, dim3(kBlock), 0, h->stream, args..., (const uint16_t*)h->voters);
   else
     hipLaunchKernelGGL((lead_form ? lead : plain), grid, dim3(kBlock), 0, h->stream, args...);
+}
+
+// ... and the *_cq_* forms (raftq_set_check_quorum), whose parameter lists end with raftq_set_read_index's records (nullptr unless
+// the mode is RAFTQ_READ_SAFE)
+template <class... A>
+void launch_walk_cq(const raftq_t* h, dim3 grid, typename as_is<void (*)(A..., raftqk::ReadRec*)>::type plain,
+                    typename as_is<void (*)(A..., const uint16_t*, raftqk::ReadRec*)>::type voters,
+                    typename as_is<void (*)(A..., raftqk::ReadRec*)>::type lead,
+                    typename as_is<void (*)(A..., const uint16_t*, raftqk::ReadRec*)>::type lead_voters,
+                    typename as_is<A>::type... args) {  // (A is given by the caller: a pack in front of other parameters is not deduced)
+  const bool lead_form = lead_step(h);
+  raftqk::ReadRec* reads = (raftqk::ReadRec*)h->reads;
+  if (masked_step(h))
+    hipLaunchKernelGGL((lead_form ? lead_voters : voters), grid, dim3(kBlock), 0, h->stream, args..., (const uint16_t*)h->voters, reads);
+  else
+    hipLaunchKernelGGL((lead_form ? lead : plain), grid, dim3(kBlock), 0, h->stream, args..., reads);
 }
 
 // The opening of the one-call entry points (raftq_step_batch, raftq_step_frames*): the device, the caller's counts zeroed, no
@@ -457,13 +474,14 @@ static int enqueue_sorted_walk(raftq_t* h, const Scratch& s, uint64_t n, int end
   unsigned int* bad = (unsigned int*)(s.n_heads + 1);
   const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
   hipLaunchKernelGGL(step_keys_kernel, grid, dim3(kBlock), 0, h->stream, (const MsgRec*)s.msgs, s.keys_in, s.order_in, n,
-                     h->G, h->N, bad, h->step_msg_flags, recs, s.outs, h->step_compact, h->step_props, h->cq != nullptr, h->pre_vote, h->lead_transfer);
+                     h->G, h->N, bad, h->step_msg_flags, recs, s.outs, h->step_compact, h->step_props, h->cq != nullptr, h->pre_vote, h->lead_transfer, h->read_index != 0);
   HIPCHK(h, hipGetLastError());
   int in_b = 0;  // which pair of buffers the sorted (group, batch position) pairs end up in
   HIPCHK(h, raftqk::radix_sort_pairs(h->stream, s.sort_scratch, s.keys_in, s.order_in, s.keys_out, s.order_out, n, end_bit, &in_b));
   if (h->cq)  // raftq_set_check_quorum: NodeT's CQ form
-    launch_walk(h, grid, step_cq_kernel, step_cq_voters_kernel, step_cq_lead_kernel, step_cq_lead_voters_kernel, node_arrays(h, recs), s.msgs,
-                in_b ? s.keys_out : s.keys_in, in_b ? s.order_out : s.order_in, s.outs, h->step_compact, n, s.n_heads, bad);
+    launch_walk_cq<NodeArrays, const MsgRec*, const uint64_t*, const uint32_t*, void*, uint8_t, uint64_t, unsigned long long*, const unsigned int*>(
+        h, grid, step_cq_kernel, step_cq_voters_kernel, step_cq_lead_kernel, step_cq_lead_voters_kernel, node_arrays(h, recs), s.msgs,
+        in_b ? s.keys_out : s.keys_in, in_b ? s.order_out : s.order_in, s.outs, h->step_compact, n, s.n_heads, bad);
   else
     launch_walk(h, grid, step_kernel, step_voters_kernel, step_lead_kernel, step_lead_voters_kernel, node_arrays(h, recs), s.msgs,
                 in_b ? s.keys_out : s.keys_in, in_b ? s.order_out : s.order_in, s.outs, h->step_compact, n, s.n_heads, bad);
@@ -489,12 +507,13 @@ static int enqueue_list_walk(raftq_t* h, const Scratch& s, uint64_t n, uint8_t r
     in_walk = {(const u64x2*)carry->outs_d, (u64x2*)carry->out.d, cut, quads, quads - 1, d2h_blocks(quads - cut)};
   }
   hipLaunchKernelGGL(step_link_kernel, dim3(blocks + in_link.blocks), dim3(kBlock), 0, h->stream, (const MsgRec*)s.msgs, n, h->G,
-                     h->N, h->step_msg_flags, recs, (NodeRec*)h->node_rec, s.next, bad, h->step_stall, s.outs, h->step_compact, in_link, h->step_props, h->cq != nullptr, h->pre_vote, h->lead_transfer);
+                     h->N, h->step_msg_flags, recs, (NodeRec*)h->node_rec, s.next, bad, h->step_stall, s.outs, h->step_compact, in_link, h->step_props, h->cq != nullptr, h->pre_vote, h->lead_transfer, h->read_index != 0);
   HIPCHK(h, hipGetLastError());  // (the link kernel's, before the walk's launch can hide it)
   if (h->cq)  // raftq_set_check_quorum: NodeT's CQ form
-    launch_walk(h, dim3(blocks + in_walk.blocks), step_lists_cq_kernel, step_lists_cq_voters_kernel, step_lists_cq_lead_kernel,
-                step_lists_cq_lead_voters_kernel, node_arrays(h, recs), s.msgs, s.outs, h->step_compact, n, h->G, s.next, s.n_heads, skipped,
-                bad, h->step_stall, in_walk);
+    launch_walk_cq<NodeArrays, const MsgRec*, void*, uint8_t, uint64_t, uint64_t, const uint32_t*, unsigned long long*, unsigned int*, const unsigned int*,
+                   const unsigned int*, raftqk::CopyRide>(h, dim3(blocks + in_walk.blocks), step_lists_cq_kernel, step_lists_cq_voters_kernel,
+                                                          step_lists_cq_lead_kernel, step_lists_cq_lead_voters_kernel, node_arrays(h, recs), s.msgs, s.outs,
+                                                          h->step_compact, n, h->G, s.next, s.n_heads, skipped, bad, h->step_stall, in_walk);
   else
     launch_walk(h, dim3(blocks + in_walk.blocks), step_lists_kernel, step_lists_voters_kernel, step_lists_lead_kernel,
                 step_lists_lead_voters_kernel, node_arrays(h, recs), s.msgs, s.outs, h->step_compact, n, h->G, s.next, s.n_heads, skipped,

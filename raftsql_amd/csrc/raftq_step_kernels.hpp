@@ -108,19 +108,27 @@ struct NodeArrays {
   bool pv = false;
   // raftq_set_lead_transfer (likewise): the rules of include/raftq_step.h "Leadership transfer"; leadTransferee is bits 12..15 of the cq word
   bool lt = false;
+  // raftq_set_read_index (likewise): 0 = off, kReadSafe, kReadLease -- the rules of include/raftq_step.h "ReadIndex in Step".  The read
+  // records themselves are no member: a pointer here would move every kernel's arguments behind NodeArrays, so the *_cq_* walks take
+  // them as a parameter of their own (RAFTQ_WALK_READS)
+  uint8_t ri = 0;
 };
+static_assert(sizeof(NodeArrays) == 136, "a by-value argument of every Step-family kernel: its size moves their other arguments");
+constexpr uint8_t kReadSafe = 1, kReadLease = 2;
+// (ReadRec, raftq_set_read_index's record, is raftq_kernels.hpp's: the host's bulk calls speak it too)
 constexpr uint8_t kRecsCaller = 0, kRecsWire = 1, kRecsFrames = 2;
 
 constexpr uint8_t kMsgHup = 0, kMsgBeat = 1, kMsgProp = 2, kMsgApp = 3, kMsgAppResp = 4, kMsgVote = 5, kMsgVoteResp = 6,
                   kMsgHeartbeat = 8, kMsgHeartbeatResp = 9, kMsgCheckQuorum = 12, kMsgTransferLeader = 13, kMsgTimeoutNow = 14,
-                  kMsgPreVote = 17, kMsgPreVoteResp = 18;
+                  kMsgReadIndex = 15, kMsgReadIndexResp = 16, kMsgPreVote = 17, kMsgPreVoteResp = 18;
 constexpr uint8_t kOutNone = 0, kOutVoteResp = 1, kOutHeartbeatResp = 2, kOutCampaign = 3, kOutBecameLeader = 4,
                   kOutProgress = 5, kOutBcastHeartbeat = 6, kOutAppend = 7, kOutAppended = 8, kOutDeferred = 9, kOutSkipped = 10,
                   kOutHeld = 11, kOutProposed = 12, kOutForward = 13, kOutPreCampaign = 14, kOutPreVoteResp = 15, kOutTermResp = 16,
-                  kOutTransfer = 17;
+                  kOutTransfer = 17, kOutReadIndex = 18, kOutReadState = 19;
 constexpr uint8_t kMsgfEntries = 0x80, kMsgfBarrier = 0x40, kMsgfHold = 0x20, kMsgfSkip = 0x10;  // raftq_msg_t._pad[1]: RAFTQ_MSGF_*
 constexpr uint8_t kFlagHardState = 1, kFlagCommitted = 2, kFlagUpdated = 4, kFlagSteppedDown = 8;
 constexpr uint8_t kFlagTimeoutNow = 0x20;  // RAFTQ_OUTF_TIMEOUT_NOW: the transferee's Match is the tail -- send it MsgTimeoutNow
+constexpr uint8_t kFlagReadReady = 0x40;   // RAFTQ_OUTF_READ_READY: a quorum has confirmed the read(s) -- release them
 constexpr uint32_t kCqTransfereeShift = 12, kCqTransfereeMask = 0xf000u;  // leadTransferee (0 = None, else slot + 1) in the cq word
 constexpr uint8_t kFlagAnswered = 0x10;  // RAFTQ_OUTF_ANSWERED: the messages the result calls for were built on the device
 
@@ -142,8 +150,15 @@ constexpr uint8_t kPreCandidate = 3;  // RAFTQ_ROLE_PRE_CANDIDATE: only under ra
 // result record i, in the handle's format.  Compact drops group and addressee (= msgs[i].group / .from) and folds
 // log_term / last_index into one slot: log_term is only set by the two result types whose index IS last_index.
 // PV: the *_cq_* walks' form, in which RAFTQ_OUT_PRE_CAMPAIGN (raftq_set_pre_vote) is packed as RAFTQ_OUT_CAMPAIGN is; the other
-// walks never give that type and keep the form they had.
-template <bool PV = false>
+// walks never give that type and keep the form they had.  Likewise RAFTQ_OUT_READ_INDEX and a RAFTQ_OUT_PROGRESS with
+// RAFTQ_OUTF_READ_READY (raftq_set_read_index): their log_term -- a read's sequence number -- rides the commit slot of both compact forms.
+// RD: the *_cq_* walks' alone -- the one other user of the PV form, elect_build_cq_kernel, gives neither result and keeps its code.
+template <bool RD>
+__device__ __forceinline__ bool carries_read(const StepOutRec& o) {
+  if constexpr (RD) return o.type == kOutReadIndex || (o.type == kOutProgress && (o.flags & kFlagReadReady) != 0);
+  return false;
+}
+template <bool PV = false, bool RD = false>
 __device__ __forceinline__ void put_result(void* out, uint64_t i, const StepOutRec& o, uint8_t fmt) {
   if (fmt == kFmtFull) {
     static_cast<StepOutRec*>(out)[i] = o;
@@ -153,7 +168,7 @@ __device__ __forceinline__ void put_result(void* out, uint64_t i, const StepOutR
     StepOutS c;
     c.term = o.term;
     c.index = o.index;
-    c.commit = (o.type == kOutCampaign || (PV && o.type == kOutPreCampaign)) ? o.log_term : o.commit;
+    c.commit = (o.type == kOutCampaign || (PV && o.type == kOutPreCampaign) || carries_read<RD>(o)) ? o.log_term : o.commit;
     c.vote = (uint8_t)o.vote;
     c.lead = (uint8_t)o.lead;
     c.type = o.type;
@@ -167,7 +182,7 @@ __device__ __forceinline__ void put_result(void* out, uint64_t i, const StepOutR
   StepOutC c;
   c.term = o.term;
   c.index = o.index;
-  c.commit = o.commit;
+  c.commit = carries_read<RD>(o) ? o.log_term : o.commit;
   c.aux = (o.type == kOutCampaign || o.type == kOutBecameLeader || (PV && o.type == kOutPreCampaign)) ? o.log_term : o.last_index;
   c.vote = (uint8_t)o.vote;
   c.lead = (uint8_t)o.lead;
@@ -230,8 +245,10 @@ __device__ __forceinline__ uint64_t entry_count(const MsgRec& m, uint8_t recs) {
 // pv (raftq_set_pre_vote): MsgPreVote and MsgPreVoteResp are known kinds, a peer's like MsgVote and MsgVoteResp, in every kind of record.
 // lt (raftq_set_lead_transfer): MsgTransferLeader and MsgTimeoutNow likewise -- a MsgTransferLeader's `from` is the transferee's slot in
 // its local form (term 0) too, so neither is a local kind: `from` >= N is malformed.
+// ri (raftq_set_read_index, either mode): MsgReadIndex and MsgReadIndexResp likewise -- a MsgReadIndex's `from` is the requester's slot
+// in its local form (term 0) too.
 __device__ __forceinline__ RecClass classify(const MsgRec& m, uint64_t n_groups, uint32_t n_peers, bool msg_flags, uint8_t recs, bool props,
-                                             bool cq = false, bool pv = false, bool lt = false) {
+                                             bool cq = false, bool pv = false, bool lt = false, bool ri = false) {
   const uint8_t fl = msg_flags ? m.pad[1] : (uint8_t)0;
   if (fl & kMsgfSkip) return kSkip;
   if (m.group >= n_groups) return kBad;
@@ -242,7 +259,7 @@ __device__ __forceinline__ RecClass classify(const MsgRec& m, uint64_t n_groups,
   const bool local = t == kMsgHup || t == kMsgBeat || (t == kMsgCheckQuorum && cq && recs == kRecsCaller);
   const bool known = local || t == kMsgApp || t == kMsgAppResp || t == kMsgVote || t == kMsgVoteResp ||
                      t == kMsgHeartbeat || t == kMsgHeartbeatResp || (pv && (t == kMsgPreVote || t == kMsgPreVoteResp)) ||
-                     (lt && (t == kMsgTransferLeader || t == kMsgTimeoutNow));
+                     (lt && (t == kMsgTransferLeader || t == kMsgTimeoutNow)) || (ri && (t == kMsgReadIndex || t == kMsgReadIndexResp));
   if (!known || (!local && m.from >= n_peers)) return kBad;
   // records decoded on the device from stream frames (raftq_step_submit_wire) also carry the addressee's slot and the
   // decoder's flags in the two pad bytes: a frame that did not parse, or one addressed to no peer of this cluster, fails
@@ -265,11 +282,11 @@ static __global__ __launch_bounds__(kBlock) void step_keys_kernel(const MsgRec* 
                                                                   uint32_t* __restrict__ order, uint64_t n,
                                                                   uint64_t n_groups, uint32_t n_peers,
                                                                   unsigned int* bad, bool msg_flags, uint8_t recs,
-                                                                  void* __restrict__ out, uint8_t compact, bool props, bool cq, bool pv, bool lt) {
+                                                                  void* __restrict__ out, uint8_t compact, bool props, bool cq, bool pv, bool lt, bool ri) {
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   bool is_bad = false;
   if (i < n) {
-    const RecClass c = classify(msgs[i], n_groups, n_peers, msg_flags, recs, props, cq, pv, lt);
+    const RecClass c = classify(msgs[i], n_groups, n_peers, msg_flags, recs, props, cq, pv, lt, ri);
     is_bad = c == kBad;
     // a skipped record sorts behind every group (the key range has room for n_groups itself) and is answered here
     keys[i] = c == kTake ? msgs[i].group : c == kSkip ? n_groups : 0;  // (bad: keep the sort's key range valid)
@@ -301,8 +318,71 @@ constexpr uint32_t kNil = 0xffffffffu;
 // "CheckQuorum").  A template axis, not a run-time flag of NodeArrays: as a flag the rules cost every handle registers -- the sorted
 // walk went from 158 to 169 VGPRs and from 3 waves per SIMD to 2, the list walk from 190 to 199, with the switch off
 // (profiles/r24/README.md) -- and every `if constexpr (CQ)` is empty in the other forms: they compile to what they were.
-template <bool MASKED, bool LEAD = false, bool CQ = false>
+// ---- raftq_set_read_index(h, RAFTQ_READ_SAFE): the rules that touch a group's read record, OUT OF LINE and on the record where it
+// lies.  NodeT::step is inlined twice into the list walk; with the record held in NodeT (ten more registers, read lazily and written
+// back when dirty, as the activity word is) and its rules inline, the inliner left maybe_commit(), respond() and become_follower()
+// of those forms out of line instead, and a NodeT whose address is taken lives in scratch -- 400 to 528 bytes a lane
+// (profiles/r30/README.md).  One call that takes what it needs by value costs the walks no register that lives across the role arms
+// and no scratch; the record is in memory either way: a lane owns its group, so it reads what it wrote.  A batch with no read
+// traffic and no reset() never gets here; a request stores two words, an acknowledgement that raises a word one, a reset() one
+// zeroed record (NodeT::rd_zeroed spares the second of two in a row).
+//   op kReadRequest   p = self: seq += 1, acked[p] = seq -> seq | (confirmed() >= seq) << 32; 0 = the counter is full, nothing moved
+//      kReadAck       c = the context, p = its sender: acked[p] = max(acked[p], c) unless c > seq -> confirmed() if it moved, else 0
+//      kReadBeat      -> seq if seq > confirmed(), else 0
+//      kReadClear     the record zeroed
+// confirmed(): the largest number >= q of the slots in `members` have acknowledged -- maybe_commit()'s counting form over the
+// acknowledgement words; an empty `members` gives 0, a slot outside it is stored and does not count.
+constexpr uint32_t kReadRequest = 0, kReadAck = 1, kReadBeat = 2, kReadClear = 3;
+__device__ __forceinline__ uint32_t read_confirmed(const uint32_t (&ack)[kMaxPeers], uint32_t members, uint32_t q) {
+  uint32_t best = 0;
+#pragma unroll
+  for (uint32_t c = 0; c < (uint32_t)kMaxPeers; ++c) {
+    uint32_t ge = 0;
+#pragma unroll
+    for (uint32_t p = 0; p < (uint32_t)kMaxPeers; ++p) ge += (((members >> p) & 1u) != 0 && ack[p] >= ack[c]) ? 1u : 0u;
+    if (((members >> c) & 1u) != 0 && ge >= q && ack[c] > best) best = ack[c];
+  }
+  return best;
+}
+static __device__ __noinline__ uint64_t read_rule(ReadRec* rec, uint32_t op, uint32_t p, uint32_t c, uint32_t members, uint32_t q) {
+  if (op == kReadClear) {
+    uint4* w = reinterpret_cast<uint4*>(rec);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) w[k] = uint4{0, 0, 0, 0};
+    return 0;
+  }
+  uint32_t seq = rec->seq;
+  uint32_t ack[kMaxPeers];
+#pragma unroll
+  for (int k = 0; k < kMaxPeers; ++k) ack[k] = rec->acked[k];
+  if (op == kReadBeat) return seq > read_confirmed(ack, members, q) ? seq : 0;
+  if (op == kReadRequest) {
+    if (seq == 0xffffffffu) return 0;
+    c = seq += 1;
+    rec->seq = seq;
+  } else if (c > seq) {
+    return 0;
+  }
+  const uint32_t before = read_confirmed(ack, members, q);
+  bool raised = false;
+#pragma unroll
+  for (uint32_t k = 0; k < (uint32_t)kMaxPeers; ++k)
+    if (k == p && ack[k] < c) {
+      ack[k] = c;
+      raised = true;
+    }
+  if (raised) rec->acked[p] = c;
+  const uint32_t after = read_confirmed(ack, members, q);
+  if (op == kReadRequest) return (uint64_t)seq | ((uint64_t)(after >= seq ? 1u : 0u) << 32);
+  return after > before ? after : 0;
+}
+
+// RI (raftq_set_read_index): the CQ form as the *_cq_* walks instantiate it, with the rules of include/raftq_step.h "ReadIndex in Step"
+// behind the run-time NodeArrays::ri.  An axis of its own so that the one other user of the CQ form -- elect_build_cq_kernel, which
+// has no read records to hand over -- compiles to what it was: every use of ri() folds to 0 there.
+template <bool MASKED, bool LEAD = false, bool CQ = false, bool RI = false>
 struct NodeT {
+  static_assert(CQ || !RI, "the read rules live in the CQ form");
   const NodeArrays& a;
   uint64_t g;
   uint64_t term, last_index, last_term, committed, first_idx;
@@ -325,8 +405,13 @@ struct NodeT {
   // raftq_set_check_quorum only: the group's activity word (NodeArrays::cq), read lazily and written back when dirty, as the vote word
   uint32_t cqw = 0;
   bool cq_known = false, cq_dirty = false;
+  // raftq_set_read_index(h, RAFTQ_READ_SAFE) only: the handle's read records (read_rule() below works on group g's in memory), and
+  // whether this lane has zeroed the group's and nothing has touched it since (reset() may run twice for one message)
+  ReadRec* reads = nullptr;
+  bool rd_zeroed = false;
 
-  __device__ NodeT(const NodeArrays& arr, uint64_t group, const uint16_t* voters = nullptr) : a(arr), g(group) {
+  __device__ NodeT(const NodeArrays& arr, uint64_t group, const uint16_t* voters = nullptr, ReadRec* read_recs = nullptr) : a(arr), g(group) {
+    if constexpr (RI) reads = read_recs;
     if constexpr (MASKED) vmask = voters[g];
     const NodeRec r = a.rec[g];  // one line: eight 16-byte loads
     term = r.term; last_index = r.last_index; last_term = r.last_term;
@@ -422,6 +507,19 @@ struct NodeT {
     for (uint32_t k = 0; k < (uint32_t)kMaxPeers; ++k) mt[k] = k == p ? v : mt[k];
     mt_dirty |= 1u << p;
   }
+  __device__ __forceinline__ uint8_t ri() const {
+    if constexpr (RI) return a.ri;
+    else return 0;
+  }
+  // the slots confirmed() counts, and read_rule() on this group's record
+  __device__ __forceinline__ uint32_t read_members() const {
+    if constexpr (MASKED) return vmask;
+    else return (1u << a.n_peers) - 1u;
+  }
+  __device__ __forceinline__ uint64_t read_op(uint32_t op, uint32_t p = 0, uint32_t c = 0) {
+    rd_zeroed = op == kReadClear;
+    return read_rule(reads + g, op, p, c, read_members(), quorum());
+  }
   // CHOICE where upstream has no counterpart (its prs map IS the membership): q_g = popcount(voters[g]) / 2 + 1; an empty mask
   // gives 1, which nothing reaches (no candidate, no counted grant)
   __device__ uint32_t quorum() const {
@@ -440,7 +538,10 @@ struct NodeT {
     lead = 0;
     elapsed_reset = true;
     set_votes(0);
-    if constexpr (CQ) set_cq(0);  // every Progress.RecentActive = false, electionElapsed = 0
+    if constexpr (CQ) {
+      set_cq(0);  // every Progress.RecentActive = false, electionElapsed = 0
+      if (ri() == kReadSafe && !rd_zeroed) (void)read_op(kReadClear);  // readOnly = newReadOnly: no request of the old leadership is ever confirmed
+    }
 #pragma unroll
     for (uint32_t p = 0; p < (uint32_t)kMaxPeers; ++p)
       if (p < a.n_peers) {
@@ -568,7 +669,10 @@ struct NodeT {
       switch (o.type) {
         case kOutAppended: r.kind = kMsgAppResp; r.index = o.index; break;
         case kOutVoteResp: r.kind = kMsgVoteResp; r.reject = o.reject; break;
-        case kOutHeartbeatResp: r.kind = kMsgHeartbeatResp; break;
+        case kOutHeartbeatResp:
+          r.kind = kMsgHeartbeatResp;
+          if constexpr (RI) r.index = o.index;  // raftq_set_read_index: the heartbeat's context, echoed (0 without the switch)
+          break;
         case kOutProgress:
           if (m.type == kMsgAppResp && !m.reject) {
             if (!at_tail) host_owns = true;  // the host knows Next: it may send
@@ -662,7 +766,9 @@ struct NodeT {
           const bool leased = ((m.type == kMsgVote && !(a.lt && m.reject)) || (a.pv && m.type == kMsgPreVote)) && in_lease();
           const bool keep = a.pv && (m.type == kMsgPreVote || (m.type == kMsgPreVoteResp && !m.reject));
           if (leased) handled = true;
-          else if (!keep) become_follower(m.term, (m.type == kMsgVote || (a.pv && m.type == kMsgPreVoteResp)) ? 0u : m.from + 1);
+          // ReadIndex: neither read kind is a leader's -- a MsgReadIndex's `from` is the requester, who leads nothing
+          else if (!keep)
+            become_follower(m.term, (m.type == kMsgVote || (a.pv && m.type == kMsgPreVoteResp) || (ri() != 0 && (m.type == kMsgReadIndex || m.type == kMsgReadIndexResp))) ? 0u : m.from + 1);
         } else {
           become_follower(m.term, m.type == kMsgVote ? 0u : m.from + 1);
         }
@@ -699,6 +805,29 @@ struct NodeT {
         }
         if (m.type == kMsgBeat) {
           o.type = kOutBcastHeartbeat;
+          // ReadIndex: the round carries the last pending request's sequence number (upstream's lastPendingRequestCtx) -- the
+          // resend of a round that was lost
+          if constexpr (CQ) {
+            if (ri() == kReadSafe) {
+              o.index = read_op(kReadBeat);
+            }
+          }
+        } else if (CQ && ri() != 0 && m.type == kMsgReadIndex) {
+          // stepLeader MsgReadIndex: dropped until the leader has committed an entry of its term (the gate's own words), else the
+          // read is good at `committed` once a quorum still takes this node for the leader -- the lease says so at once, the safe
+          // mode numbers the request and waits for a heartbeat round that carries the number
+          const uint64_t fi = get_first_idx();
+          if (fi != 0 && committed >= fi) {
+            if (ri() == kReadLease) {
+              o.type = kOutReadIndex; o.index = committed; o.flags |= kFlagReadReady;
+            } else {
+              const uint64_t took = read_op(kReadRequest, a.self);
+              if (took != 0) {
+                o.type = kOutReadIndex; o.index = committed; o.log_term = took & 0xffffffffull;
+                if (took >> 32) o.flags |= kFlagReadReady;
+              }
+            }
+          }
         } else if (CQ && m.type == kMsgCheckQuorum) {
           // (classify() lets the kind through only under raftq_set_check_quorum)  The members that answered since the last check,
           // self included, against quorum(); the bits are cleared either way, and a leader without its quorum steps down
@@ -764,6 +893,17 @@ struct NodeT {
         } else if (m.type == kMsgHeartbeatResp) {
           o.type = kOutProgress;
           o.index = match(m.from);
+          // ReadIndex: the response echoes the round's context c; it counts for every request <= c.  0, or a number this leadership
+          // has not handed out, is no context
+          if constexpr (CQ) {
+            if (ri() == kReadSafe && m.index != 0 && m.index <= 0xffffffffull) {  // (seq is 32 bits wide: a larger c is beyond it)
+              const uint64_t after = read_op(kReadAck, m.from, (uint32_t)m.index);
+              if (after != 0) {
+                o.flags |= kFlagReadReady;
+                o.log_term = after;
+              }
+            }
+          }
         }
       } else if (role == kCandidate || (CQ && a.pv && role == kPreCandidate)) {
         if (m.type == kMsgApp) {
@@ -773,6 +913,8 @@ struct NodeT {
           become_follower(term, m.from + 1);
           commit_to(m.commit);
           o.type = kOutHeartbeatResp;
+          if constexpr (CQ)
+            if (ri() != 0) o.index = m.index;  // ReadIndex: the round's context, echoed
         } else if (m.type == kMsgVote) {
           o.type = kOutVoteResp; o.reject = 1;
         } else if (m.type == kMsgVoteResp || (CQ && m.type == kMsgPreVoteResp)) {
@@ -810,13 +952,18 @@ struct NodeT {
           elapsed_reset = true; lead = m.from + 1;
           commit_to(m.commit);
           o.type = kOutHeartbeatResp;
+          if constexpr (CQ)
+            if (ri() != 0) o.index = m.index;  // ReadIndex: the round's context, echoed (either mode: the leader's may be the safe one)
         } else if (m.type == kMsgVote) {
           o.type = kOutVoteResp;
           const bool up_to_date = m.log_term > last_term || (m.log_term == last_term && m.index >= last_index);
           if ((vote == 0 || vote == m.from + 1) && up_to_date) { elapsed_reset = true; vote = m.from + 1; }
           else o.reject = 1;
-        } else if ((m.type == kMsgProp || (CQ && a.lt && m.type == kMsgTransferLeader)) && lead != 0) {
-          o.type = kOutForward;  // stepFollower MsgProp / MsgTransferLeader: `m.To = r.lead; r.send(m)` -- the one result addressed to somebody else
+        } else if ((m.type == kMsgProp || (CQ && a.lt && m.type == kMsgTransferLeader) || (CQ && ri() != 0 && m.type == kMsgReadIndex)) && lead != 0) {
+          o.type = kOutForward;  // stepFollower MsgProp / MsgTransferLeader / MsgReadIndex: `m.To = r.lead; r.send(m)` -- the one result addressed to somebody else
+        } else if (CQ && ri() != 0 && m.type == kMsgReadIndexResp) {
+          o.type = kOutReadState;  // stepFollower MsgReadIndexResp: the leader's answer to a read this node forwarded -- readStates gets {Index}
+          o.index = m.index;
         } else if (CQ && a.lt && m.type == kMsgTimeoutNow) {
           // stepFollower MsgTimeoutNow: campaign(campaignTransfer) at once if promotable() -- the real campaign under PreVote too
           campaigns = transfer = counts(a.self, a.n_peers);
@@ -884,7 +1031,7 @@ static __global__ __launch_bounds__(kBlock) void step_link_kernel(const MsgRec* 
                                                                   uint64_t n_groups, uint32_t n_peers, bool msg_flags, uint8_t recs,
                                                                   NodeRec* rec, uint32_t* __restrict__ next,
                                                                   unsigned int* bad, unsigned int* stall,
-                                                                  void* __restrict__ out, uint8_t compact, CopyRide ride, bool props, bool cq, bool pv, bool lt) {
+                                                                  void* __restrict__ out, uint8_t compact, CopyRide ride, bool props, bool cq, bool pv, bool lt, bool ri) {
   if (blockIdx.x < ride.blocks) {
     copy_ride(ride);
     return;
@@ -892,7 +1039,7 @@ static __global__ __launch_bounds__(kBlock) void step_link_kernel(const MsgRec* 
   const uint64_t i = (uint64_t)(blockIdx.x - ride.blocks) * kBlock + threadIdx.x;
   bool is_bad = false, too_long = false;
   if (i < n) {
-    const RecClass c = classify(msgs[i], n_groups, n_peers, msg_flags, recs, props, cq, pv, lt);
+    const RecClass c = classify(msgs[i], n_groups, n_peers, msg_flags, recs, props, cq, pv, lt, ri);
     is_bad = c == kBad;
     if (c == kTake) {
       NodeRec* r = rec + msgs[i].group;  // three atomics on one line
@@ -912,6 +1059,8 @@ static __global__ __launch_bounds__(kBlock) void step_link_kernel(const MsgRec* 
 // ---- (3, 3b) the walks and the tail reports, each under its name over every slot and as *_voters_kernel over each group's own
 // voters (raftq_step_set_voters): one text, expanded twice
 #define RAFTQ_WALK_CQ false
+#define RAFTQ_WALK_READS_PARAM
+#define RAFTQ_WALK_READS
 #define RAFTQ_WALK_KERNEL(stem) stem##_kernel
 #define RAFTQ_WALK_MASKED false
 #define RAFTQ_WALK_PARAM
@@ -954,9 +1103,13 @@ static __global__ __launch_bounds__(kBlock) void step_link_kernel(const MsgRec* 
 // ... and all four walks once more as *_cq_* over NodeT's CQ form (raftq_set_check_quorum): what a handle with the switch on launches.
 // The tail reports run none of the four rules and have no such form.
 #undef RAFTQ_WALK_CQ
+#undef RAFTQ_WALK_READS_PARAM
+#undef RAFTQ_WALK_READS
 #define RAFTQ_WALK_CQ true
+#define RAFTQ_WALK_READS_PARAM , ReadRec* __restrict__ reads
+#define RAFTQ_WALK_READS , nullptr, reads
 #define RAFTQ_WALK_KERNEL(stem) stem##_cq_kernel
-#define RAFTQ_WALK_MASKED false, false, true
+#define RAFTQ_WALK_MASKED false, false, true, true
 #define RAFTQ_WALK_PARAM
 #define RAFTQ_WALK_VOTERS
 #include "raftq_step_walk_kernels.inc"
@@ -964,8 +1117,10 @@ static __global__ __launch_bounds__(kBlock) void step_link_kernel(const MsgRec* 
 #undef RAFTQ_WALK_MASKED
 #undef RAFTQ_WALK_PARAM
 #undef RAFTQ_WALK_VOTERS
+#undef RAFTQ_WALK_READS
+#define RAFTQ_WALK_READS , reads
 #define RAFTQ_WALK_KERNEL(stem) stem##_cq_voters_kernel
-#define RAFTQ_WALK_MASKED true, false, true
+#define RAFTQ_WALK_MASKED true, false, true, true
 #define RAFTQ_WALK_PARAM , const uint16_t* __restrict__ voters
 #define RAFTQ_WALK_VOTERS , voters
 #include "raftq_step_walk_kernels.inc"
@@ -973,8 +1128,10 @@ static __global__ __launch_bounds__(kBlock) void step_link_kernel(const MsgRec* 
 #undef RAFTQ_WALK_MASKED
 #undef RAFTQ_WALK_PARAM
 #undef RAFTQ_WALK_VOTERS
+#undef RAFTQ_WALK_READS
+#define RAFTQ_WALK_READS , nullptr, reads
 #define RAFTQ_WALK_KERNEL(stem) stem##_cq_lead_kernel
-#define RAFTQ_WALK_MASKED false, true, true
+#define RAFTQ_WALK_MASKED false, true, true, true
 #define RAFTQ_WALK_PARAM
 #define RAFTQ_WALK_VOTERS
 #include "raftq_step_walk_kernels.inc"
@@ -982,8 +1139,10 @@ static __global__ __launch_bounds__(kBlock) void step_link_kernel(const MsgRec* 
 #undef RAFTQ_WALK_MASKED
 #undef RAFTQ_WALK_PARAM
 #undef RAFTQ_WALK_VOTERS
+#undef RAFTQ_WALK_READS
+#define RAFTQ_WALK_READS , reads
 #define RAFTQ_WALK_KERNEL(stem) stem##_cq_lead_voters_kernel
-#define RAFTQ_WALK_MASKED true, true, true
+#define RAFTQ_WALK_MASKED true, true, true, true
 #define RAFTQ_WALK_PARAM , const uint16_t* __restrict__ voters
 #define RAFTQ_WALK_VOTERS , voters
 #include "raftq_step_walk_kernels.inc"
@@ -992,6 +1151,8 @@ static __global__ __launch_bounds__(kBlock) void step_link_kernel(const MsgRec* 
 #undef RAFTQ_WALK_PARAM
 #undef RAFTQ_WALK_VOTERS
 #undef RAFTQ_WALK_CQ
+#undef RAFTQ_WALK_READS_PARAM
+#undef RAFTQ_WALK_READS
 #undef RAFTQ_WALK_NO_DELTAS
 
 // ---- the record array's bulk paths (raftq_load_node / raftq_read_node: set-up and test traffic, not the hot path) ----------

@@ -11,7 +11,12 @@
 //   RAFTQ_WALK_NO_DELTAS     (optional) the two walks only: leave the tail reports out
 //   RAFTQ_WALK_CQ            true in the *_cq_* expansions (NodeT's CQ form, raftq_set_check_quorum): type 12 is a known kind there, and
 //                            under NodeArrays::pv (raftq_set_pre_vote) so are types 17 and 18 and RAFTQ_OUT_PRE_CAMPAIGN's packing; under
-//                            NodeArrays::lt (raftq_set_lead_transfer) so are types 13 and 14
+//                            NodeArrays::lt (raftq_set_lead_transfer) so are types 13 and 14, under NodeArrays::ri (raftq_set_read_index)
+//                            types 15 and 16
+//   RAFTQ_WALK_READS_PARAM   the *_cq_* walks' extra, very last parameter (", ReadRec* __restrict__ reads": raftq_set_read_index's
+//                            records, nullptr unless the mode is RAFTQ_READ_SAFE); empty in every other expansion
+//   RAFTQ_WALK_READS         the same, handed to NodeT's constructor behind the voters (", reads", or ", nullptr, reads" where there
+//                            are none)
 // One text, four walks of each kind and two tail-report kernels.  Why an include and not a template <bool MASKED> body the kernels call: the inliner simplifies such
 // a body BEFORE it meets the kernel (no launch bounds, no noalias arguments, NodeArrays behind a generic reference), and all three
 // unmasked kernels came out different from their parent's -- step_lists_kernel with other loads and another register count
@@ -22,7 +27,7 @@ static __global__ __launch_bounds__(kBlock) void RAFTQ_WALK_KERNEL(step)(NodeArr
                                                       const uint64_t* __restrict__ keys_sorted,
                                                       const uint32_t* __restrict__ order, void* __restrict__ out,
                                                       uint8_t compact, uint64_t n, unsigned long long* n_heads,
-                                                      const unsigned int* bad RAFTQ_WALK_PARAM) {
+                                                      const unsigned int* bad RAFTQ_WALK_PARAM RAFTQ_WALK_READS_PARAM) {
   if (*bad) return;  // a malformed record somewhere in the batch: nothing is applied
   const uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   bool head = false;
@@ -34,14 +39,14 @@ static __global__ __launch_bounds__(kBlock) void RAFTQ_WALK_KERNEL(step)(NodeArr
   const uint64_t hb = __ballot(head);
   if ((threadIdx.x & 63) == 0 && hb) atomicAdd(n_heads, (unsigned long long)__popcll(hb));
   if (!head) return;
-  NodeT<RAFTQ_WALK_MASKED> node(a, g RAFTQ_WALK_VOTERS);
+  NodeT<RAFTQ_WALK_MASKED> node(a, g RAFTQ_WALK_VOTERS RAFTQ_WALK_READS);
   for (uint64_t j = k; j < n && keys_sorted[j] == g; ++j) {
     const uint32_t i = order[j];
     const MsgRec m = msgs[i];
     StepOutRec o;
     node.step(m, o);
     node.respond(m, o, i);
-    put_result<RAFTQ_WALK_CQ>(out, i, o, compact);
+    put_result<RAFTQ_WALK_CQ, RAFTQ_WALK_CQ>(out, i, o, compact);
   }
   node.store();
 }
@@ -52,7 +57,7 @@ static __global__ __launch_bounds__(kBlock) void RAFTQ_WALK_KERNEL(step_lists)(N
                                                                    uint64_t n_groups,
                                                                    const uint32_t* __restrict__ next,
                                                                    unsigned long long* n_heads, unsigned int* tail_skipped,
-                                                                   const unsigned int* bad, const unsigned int* stall, CopyRide ride RAFTQ_WALK_PARAM) {
+                                                                   const unsigned int* bad, const unsigned int* stall, CopyRide ride RAFTQ_WALK_PARAM RAFTQ_WALK_READS_PARAM) {
   if (blockIdx.x < ride.blocks) {  // the rest of the previous batch's results (see CopyRide)
     copy_ride(ride);
     return;
@@ -61,7 +66,7 @@ static __global__ __launch_bounds__(kBlock) void RAFTQ_WALK_KERNEL(step_lists)(N
   const bool stalled = *stall != 0;  // this batch, or one before it that has not been replayed yet, needs the sorted path
   if (stalled || *bad) {             // (*bad: a malformed record somewhere in the batch) -- nothing is applied;
     if (stalled && i == 0) *tail_skipped = 1u;
-    if (i < n && classify(msgs[i], n_groups, a.n_peers, a.msg_flags, a.recs, a.props, RAFTQ_WALK_CQ, RAFTQ_WALK_CQ && a.pv, RAFTQ_WALK_CQ && a.lt) == kTake) {  // every message empties its group's list words (idempotent)
+    if (i < n && classify(msgs[i], n_groups, a.n_peers, a.msg_flags, a.recs, a.props, RAFTQ_WALK_CQ, RAFTQ_WALK_CQ && a.pv, RAFTQ_WALK_CQ && a.lt, RAFTQ_WALK_CQ && a.ri != 0) == kTake) {  // every message empties its group's list words (idempotent)
       NodeRec* r = a.rec + msgs[i].group;
       r->lst_head = kNil;
       r->lst_cnt = 0;
@@ -79,14 +84,14 @@ static __global__ __launch_bounds__(kBlock) void RAFTQ_WALK_KERNEL(step_lists)(N
   const uint64_t ob = __ballot(owner);
   if ((threadIdx.x & 63) == 0 && ob) atomicAdd(n_heads, (unsigned long long)__popcll(ob));
   if (!owner) return;
-  NodeT<RAFTQ_WALK_MASKED> node(a, g RAFTQ_WALK_VOTERS);  // (the record's line is in the L1 already: the owner test read it)
+  NodeT<RAFTQ_WALK_MASKED> node(a, g RAFTQ_WALK_VOTERS RAFTQ_WALK_READS);  // (the record's line is in the L1 already: the owner test read it)
   const uint32_t c = node.lst_cnt;
   if (c == 1) {
     StepOutRec o;
     const MsgRec m = msgs[i];
     node.step(m, o);
     node.respond(m, o, i);
-    put_result<RAFTQ_WALK_CQ>(out, i, o, compact);
+    put_result<RAFTQ_WALK_CQ, RAFTQ_WALK_CQ>(out, i, o, compact);
   } else {
     uint32_t pos[kMaxRun];
     uint32_t p = node.lst_head;
@@ -104,7 +109,7 @@ static __global__ __launch_bounds__(kBlock) void RAFTQ_WALK_KERNEL(step_lists)(N
       StepOutRec o;
       node.step(m, o);
       node.respond(m, o, pos[k]);
-      put_result<RAFTQ_WALK_CQ>(out, pos[k], o, compact);
+      put_result<RAFTQ_WALK_CQ, RAFTQ_WALK_CQ>(out, pos[k], o, compact);
     }
   }
   // the record goes back with the group's list empty for the next batch.  Other lanes of this group only compare lst_min

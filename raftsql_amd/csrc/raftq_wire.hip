@@ -717,7 +717,7 @@ int raftq_detail::wire_frames_enqueue(raftq_t* h, const void* stream, uint64_t n
   if (!v.ok)
     return fail(h, RAFTQ_EINVAL, "raftq_step_frames: the stream, the boundaries and the result arrays must be page-locked (raftq_host_alloc, "
                                  "hipHostMalloc, hipHostRegister) and 16-byte aligned -- decode and step in two calls otherwise");
-  const FrameFilter ff{(h->step_props ? 3u : 1u) | (h->pre_vote ? 4u : 0u) | (h->lead_transfer ? 8u : 0u), h->N, h->self_peer, tail_appends ? 1u : 0u, h->G, (unsigned long long*)zero2};
+  const FrameFilter ff{(h->step_props ? 3u : 1u) | (h->pre_vote ? 4u : 0u) | (h->lead_transfer ? 8u : 0u) | (h->read_index ? 16u : 0u), h->N, h->self_peer, tail_appends ? 1u : 0u, h->G, (unsigned long long*)zero2};
   if (packed)
     return decode_streaming_enqueue(h, v_stream, nbytes, v_off, n, v_msgs, v_ents, ents ? ents_cap : 0, (WireMsg*)msgs_d, ff, packed->form,
                                     PackedOut{(WireMsg*)v_wide, wide ? packed->wide_cap : 0, packed->head_types, h->self_peer});
@@ -907,6 +907,7 @@ extern "C" int raftq_tick_frames(raftq_t* h, unsigned flags, uint64_t hup_cap, u
   if (counts) *counts = raftq_wire_counts_t{0, 0, 0, 0};
   // (raftq_tick_set_checks opens the call: the beat bitmap beat_build_kernel ranks never held a group whose check failed)
   if (int rc = raftq_detail::refuse_check_quorum(h, who, true)) return rc;
+  if (int rc = raftq_detail::refuse_read_index(h, who)) return rc;
   if (!n_hup || !n_beat || !peer_off) return fail(h, RAFTQ_EINVAL, std::string(who) + ": null argument");
   if (flags & ~RAFTQ_TICK_BEAT_BITMAP) return fail(h, RAFTQ_EINVAL, std::string(who) + ": unknown flag");
   if (h->N < 2) return fail(h, RAFTQ_EINVAL, std::string(who) + ": a single-peer group has nobody to send a heartbeat to -- use raftq_tick_collect_lists");
@@ -991,6 +992,7 @@ extern "C" int raftq_tick_elect_frames(raftq_t* h, unsigned flags, uint64_t hup_
   // (raftq_tick_set_checks opens the call under both switches: the round is then elect_build_cq_kernel's, Step's own MsgHup arm)
   if (int rc = raftq_detail::refuse_pre_vote(h, who, true)) return rc;
   if (int rc = raftq_detail::refuse_check_quorum(h, who, true)) return rc;
+  if (int rc = raftq_detail::refuse_read_index(h, who)) return rc;
   if (!n_hup || !n_beat || !peer_off) return fail(h, RAFTQ_EINVAL, std::string(who) + ": null argument");
   if (flags & ~RAFTQ_TICK_BEAT_BITMAP) return fail(h, RAFTQ_EINVAL, std::string(who) + ": unknown flag");
   if (h->N < 2) return fail(h, RAFTQ_EINVAL, std::string(who) + ": a single-peer group has nobody to ask for a vote -- use raftq_tick_collect_lists");

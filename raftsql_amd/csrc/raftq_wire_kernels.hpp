@@ -1051,7 +1051,8 @@ __device__ __forceinline__ void tile_packed_out(const WireMsg& m, bool live, boo
 struct FrameFilter {
   uint32_t on, n_peers, self, tail_appends;  // on: bit 0 = the filter runs, bit 1 = raftq_step_set_props (a MsgProp is Step's, not held),
                                              // bit 2 = raftq_set_pre_vote (MsgPreVote 17 and MsgPreVoteResp 18 are kinds a peer sends),
-                                             // bit 3 = raftq_set_lead_transfer (MsgTransferLeader 13 and MsgTimeoutNow 14 likewise)
+                                             // bit 3 = raftq_set_lead_transfer (MsgTransferLeader 13 and MsgTimeoutNow 14 likewise),
+                                             // bit 4 = raftq_set_read_index, either mode (MsgReadIndex 15 and MsgReadIndexResp 16 likewise)
   uint64_t n_groups;
   unsigned long long* zero2;  // two words this kernel leaves zero for the kernels behind it (Step's {touched groups, bad | skipped}), or nullptr
 };
@@ -1129,7 +1130,7 @@ static __global__ __launch_bounds__(TB) void wire_dec_fused_kernel(InFeed in, ui
       if (ff.on) {
         const uint8_t t = m.type;  // MsgProp 2, MsgApp 3, MsgAppResp 4, MsgVote 5, MsgVoteResp 6, MsgHeartbeat 8, MsgHeartbeatResp 9
         const bool kind_ok = t == 2 || t == 3 || t == 4 || t == 5 || t == 6 || t == 8 || t == 9 || ((ff.on & 4u) != 0 && (t == 17 || t == 18)) ||
-                             ((ff.on & 8u) != 0 && (t == 13 || t == 14));
+                             ((ff.on & 8u) != 0 && (t == 13 || t == 14)) || ((ff.on & 16u) != 0 && (t == 15 || t == 16));
         if (malformed || !kind_ok || m.group >= ff.n_groups || m.from >= ff.n_peers || m.to != ff.self) {
           m.flags |= kFrameSkip;
         } else if (t == 2) {

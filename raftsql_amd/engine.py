@@ -508,6 +508,33 @@ class QuorumEngine:
         self._chk(self._lib.raftq_read_transfer(self._h, _ptr(t)))
         return t
 
+    def set_read_index(self, mode=_lib.READ_SAFE) -> None:
+        """raftq_set_read_index (include/raftq.h "ReadIndex"): 0 off, READ_SAFE (a read waits for a quorum of heartbeat
+        acknowledgements that carry its sequence number) or READ_LEASE (the CheckQuorum lease releases it at once).  Step then runs
+        MsgReadIndex (15) and MsgReadIndexResp (16).  Requires set_check_quorum; a property of the handle (no batch may be in
+        flight).  Every change of mode zeroes the read records; READ_SAFE closes tick_frames / tick_elect_frames."""
+        self._chk(self._lib.raftq_set_read_index(self._h, int(mode)))
+
+    def load_reads(self, seq: Optional[np.ndarray] = None, acked: Optional[np.ndarray] = None) -> None:
+        """seq [G] u32 (read requests this leadership has taken), acked [N][G] u32 (the largest each peer has acknowledged); None
+        leaves that half alone (raftq_load_reads, READ_SAFE only)"""
+        s = None if seq is None else np.ascontiguousarray(seq, dtype=np.uint32)
+        a = None if acked is None else np.ascontiguousarray(acked, dtype=np.uint32)
+        if s is not None and s.shape != (self.n_groups,):
+            raise ValueError("seq must be [G]")
+        if a is not None and a.shape != (self.n_peers, self.n_groups):
+            raise ValueError("acked must be [N][G]")
+        self._chk(self._lib.raftq_load_reads(self._h, None if s is None else _ptr(s), None if a is None else _ptr(a)))
+
+    def read_reads(self):
+        """(seq [G], acked [N][G], confirmed [G]) u32: confirmed = the q-th largest acknowledgement over the group's members
+        (raftq_read_reads, READ_SAFE only)"""
+        seq = np.empty(self.n_groups, dtype=np.uint32)
+        acked = np.empty((self.n_peers, self.n_groups), dtype=np.uint32)
+        conf = np.empty(self.n_groups, dtype=np.uint32)
+        self._chk(self._lib.raftq_read_reads(self._h, _ptr(seq), _ptr(acked), _ptr(conf)))
+        return seq, acked, conf
+
     def load_activity(self, active: Optional[np.ndarray] = None, lead_elapsed: Optional[np.ndarray] = None) -> None:
         """active [G] u16 (bit p = peer p answered since the last check), lead_elapsed [G] u32 (a leader's electionElapsed)"""
         a = None if active is None else np.ascontiguousarray(active, dtype=np.uint16)

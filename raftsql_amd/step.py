@@ -21,6 +21,7 @@ MSG_HUP, MSG_BEAT, MSG_APP, MSG_APP_RESP, MSG_VOTE, MSG_VOTE_RESP, MSG_HEARTBEAT
 MSG_PROP = 2  # a follower's forwarded proposal: stepped only under set_step_props (MSGF_ENTRIES + its count in _resv)
 MSG_CHECK_QUORUM = 12  # local: a leader's check failed in tick() (collect_checks): stepped only under set_check_quorum
 MSG_TRANSFER_LEADER, MSG_TIMEOUT_NOW = 13, 14  # from = the transferee (local at term 0, or forwarded); a peer's: stepped only under set_lead_transfer
+MSG_READ_INDEX, MSG_READ_INDEX_RESP = 15, 16  # from = the requester (local at term 0, or forwarded) | the leader's answer: stepped only under set_read_index
 MSG_PRE_VOTE, MSG_PRE_VOTE_RESP = 17, 18  # a peer's pre-election (MsgVote's fields): stepped only under set_pre_vote
 MSG_TYPES = (MSG_HUP, MSG_BEAT, MSG_APP, MSG_APP_RESP, MSG_VOTE, MSG_VOTE_RESP, MSG_HEARTBEAT, MSG_HEARTBEAT_RESP)
 
@@ -31,11 +32,13 @@ OUT_SKIPPED, OUT_HELD = 10, 11  # MSGF_SKIP: nobody's, nothing looked at; MSGF_H
 OUT_PROPOSED, OUT_FORWARD = 12, 13  # set_step_props: the leader took a MsgProp (index = first new index); a follower's goes on to lead - 1
 # set_pre_vote: became pre-candidate (send MsgPreVote at term + 1); send MsgPreVoteResp{Term: index}; tell a stale leader the term
 OUT_PRE_CAMPAIGN, OUT_PRE_VOTE_RESP, OUT_TERM_RESP = 14, 15, 16
+OUT_READ_INDEX, OUT_READ_STATE = 18, 19  # set_read_index: the leader took a read (index = its index, log_term = its sequence number) | a forwarded read's answer
 OUT_TRANSFER = 17  # set_lead_transfer: the leader took a MsgTransferLeader (to = the transferee, index = its Match)
 MSGF_SKIP, MSGF_HOLD = 0x10, 0x20
 MSGF_BARRIER = 0x40  # on a MsgApp: if it is answered OUT_APPEND, the group's later messages of the batch are deferred
 MSGF_ENTRIES = 0x80  # msgs["_pad"][:, 1]: _resv = number of entries, reject_hint = the last one's term (raftq_step.h)
 OUTF_HARDSTATE, OUTF_COMMITTED, OUTF_UPDATED, OUTF_STEPPED_DOWN = 1, 2, 4, 8
+OUTF_READ_READY = 0x40  # set_read_index: release the read (OUT_READ_INDEX) / every queued read <= log_term (OUT_PROGRESS)
 OUTF_TIMEOUT_NOW = 0x20  # set_lead_transfer: the pending transferee `to` is at the tail: send it MsgTimeoutNow
 
 ROLE_FOLLOWER, ROLE_CANDIDATE, ROLE_LEADER = 0, 1, 2
@@ -84,13 +87,20 @@ def pack_msgs40(msgs: np.ndarray, out: np.ndarray | None = None) -> np.ndarray:
 
 
 def expand_compact(msgs: np.ndarray, recs: np.ndarray) -> np.ndarray:
-    """raftq_step_out_c_t[] + the batch it answers -> raftq_step_out_t[] (exact: see include/raftq_step.h)"""
+    """raftq_step_out_c_t[] + the batch it answers -> raftq_step_out_t[] (exact: see include/raftq_step.h -- but for the commit index
+    beside an OUT_PROGRESS with OUTF_READ_READY, whose slot carries log_term: it is left 0, a MsgHeartbeatResp moves none and
+    expand_short, which tracks the index, gives it)"""
     o = np.zeros(len(recs), dtype=OUT_DT)
     o["group"], o["to"] = msgs["group"], msgs["from"]
     for k in ("term", "index", "commit", "vote", "lead", "type", "reject", "flags", "role"):
         o[k] = recs[k]
     tip = (recs["type"] == OUT_CAMPAIGN) | (recs["type"] == OUT_BECAME_LEADER) | (recs["type"] == OUT_PRE_CAMPAIGN)  # index IS the last index there
     o["log_term"] = np.where(tip, recs["aux"], np.where(recs["type"] == OUT_PROPOSED, recs["term"], 0))
+    # set_read_index: a read's sequence number rides the commit slot; an OUT_READ_INDEX's commit IS its index
+    ready = (recs["type"] == OUT_PROGRESS) & ((recs["flags"] & OUTF_READ_READY) != 0)
+    read = recs["type"] == OUT_READ_INDEX
+    o["log_term"] = np.where(read | ready, recs["commit"], o["log_term"])
+    o["commit"] = np.where(read, recs["index"], np.where(ready, 0, o["commit"]))
     o["last_index"] = np.where(tip, recs["index"], recs["aux"])
     fwd = recs["type"] == OUT_FORWARD  # the one result whose addressee is not the sender: the leader's slot
     o["to"] = np.where(fwd, recs["lead"].astype(np.int64) - 1, o["to"])
@@ -102,7 +112,9 @@ def expand_short(msgs: np.ndarray, recs: np.ndarray, last_index: np.ndarray, com
     raftq_step_out_t[], exactly (include/raftq_step.h): what the 32-byte record leaves out is tracked per group across the
     batch -- lastIndex only moves with a result whose `index` IS the last index, a campaign (and a pre-campaign) moves no commit
     index and carries its log_term in that slot, a new leader's log_term is its term; behind an OUT_PROPOSED the tail is index + n - 1 (n = the
-    count in the reader's own record, msgs["_resv"]'s low half) and its log_term is its term; an OUT_FORWARD goes to lead - 1.
+    count in the reader's own record, msgs["_resv"]'s low half) and its log_term is its term; an OUT_FORWARD goes to lead - 1;
+    an OUT_READ_INDEX carries its log_term in the commit slot and its commit IS its index, an OUT_PROGRESS with OUTF_READ_READY
+    carries log_term there and moves no commit index.
     (A loop over the records: tests and tools, not a hot path.)"""
     o = np.zeros(len(recs), dtype=OUT_DT)
     li, co = {}, {}
@@ -120,8 +132,11 @@ def expand_short(msgs: np.ndarray, recs: np.ndarray, last_index: np.ndarray, com
             li[g] = int(r["index"])
         elif t == OUT_PROPOSED:
             li[g] = int(r["index"]) + (int(msgs["_resv"][i]) & 0xFFFFFFFF) - 1
-        camp = t in (OUT_CAMPAIGN, OUT_PRE_CAMPAIGN)
-        if not camp:
+        ready = t == OUT_PROGRESS and int(r["flags"]) & OUTF_READ_READY
+        camp = t in (OUT_CAMPAIGN, OUT_PRE_CAMPAIGN, OUT_READ_INDEX) or ready
+        if t == OUT_READ_INDEX:
+            co[g] = int(r["index"])
+        elif not camp:
             co[g] = int(r["commit"])
         o[i] = (g, r["term"], r["index"], r["commit"] if camp else (r["term"] if t in (OUT_BECAME_LEADER, OUT_PROPOSED) else 0), co[g], li[g],
                 int(r["lead"]) - 1 if t == OUT_FORWARD else msgs["from"][i], r["vote"], r["lead"], t, r["reject"], r["flags"], r["role"])
