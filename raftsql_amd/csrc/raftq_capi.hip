@@ -225,10 +225,6 @@ hipError_t launch_set_voters(uint32_t N, const VoterSetLaunch& L, unsigned flags
 }
 
 }  // namespace
-// something other than Step is about to change match / committed / first_idx / role on the device: the per-group records' copies
-// of them go stale (raftq_step_kernels.hpp NodeRec)
-static inline void dense_changed(raftq_t* h) { h->node_mirror_fresh = false; }
-
 int raftq_detail::ensure_staging(raftq_t* h, size_t bytes) {
   HIPCHK(h, h->stage.grow(bytes, std::max({bytes, h->stage.cap * 2, (size_t)1 << 20}), &h->stream));
   return RAFTQ_OK;
@@ -315,6 +311,7 @@ using raftq_detail::ensure_ingest;
 using raftq_detail::use_device;
 using raftq_detail::use_device_idle;
 using raftq_detail::ensure_tick_state;
+using raftq_detail::dense_changed;
 
 // host <-> device form of the RequestVote state.  The ABI speaks one byte per (peer, group); the device keeps one
 // word per group, 2 bits per peer.  Bytes other than 1 / 2 are "no response" (include/raftq.h) and load as 00.
@@ -1059,6 +1056,54 @@ int raftq_vote_tally(raftq_t* h, uint8_t* outcome_out, raftq_counts_t* counts) {
 
 }  // extern "C"
 
+// The end of a batching turn.  A turn is ~55 us of device work, so the wake-up of a blocking
+// hipStreamSynchronize (interrupt + reschedule, ~8 us) is a visible slice of it.  When the turn ends in a
+// compaction, a one-thread kernel behind it stores a completion epoch into pinned host memory:
+// the host polls the word -- bounded, then falls back to the blocking wait.
+// (Polling hipStreamQuery instead was measured SLOWER than blocking: 88 vs 80 us per turn, profiles/r02.)
+static hipError_t wait_turn(raftq_t* h, uint64_t flag_epoch, int kind = 0) {
+  // A miss (the flag did not land within 2 ms; a turn is ~50 us) is either a slow turn -- a huge handle, a contended
+  // GPU, a profiler -- or a stack on which the flag never reaches the host.  One slow turn must not change the handle's
+  // steady state (ADVICE r03), so the wake-up is only given up after kMisses misses IN A ROW, and then tried again every
+  // kRetry turns; RAFTQ_PROFILE prints how many turns fell back to the blocking wait.
+  constexpr uint32_t kMisses = 8, kRetry = 1024;
+  const bool try_flag = flag_epoch && (h->flag_misses[kind] < kMisses || (++h->flag_rested[kind] % kRetry) == 0);
+  if (try_flag) {
+    volatile uint64_t* flag = h->h_total + 3;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int i = 0;; ++i) {
+      if ((*flag & h->flag_mask) == flag_epoch) {
+        std::atomic_thread_fence(std::memory_order_acquire);
+        h->flag_misses[kind] = 0;
+        // the word says the stream's work is done; an asynchronous error of that work is only known to the runtime (ADVICE r05:
+        // the poll returned success without asking, and the error surfaced in a later call).  Whatever this thread has on
+        // record -- possibly a benign, older one -- is cleared and the stream itself is asked: its answer is the call's.
+        if (hipPeekAtLastError() == hipSuccess) return hipSuccess;
+        (void)hipGetLastError();
+        return hipStreamSynchronize(h->stream);
+      }
+      if ((i & 255) == 255 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(2000)) break;
+    }
+    ++h->flag_misses[kind];
+  }
+  if (flag_epoch) ++h->flag_fallbacks;
+  return hipStreamSynchronize(h->stream);
+}
+
+hipError_t raftq_detail::wait_call(raftq_t* h) {
+  hipError_t e;
+  if (!h->d_total) {
+    e = hipStreamSynchronize(h->stream);
+  } else {
+    const uint64_t epoch = ++h->compact_epoch;
+    h->flag_mask = ~0ull;
+    hipLaunchKernelGGL(raise_flag_kernel, dim3(1), dim3(64), 0, h->stream, h->d_total + 3, epoch);
+    e = hipGetLastError() != hipSuccess ? hipStreamSynchronize(h->stream) : wait_turn(h, epoch, 1);
+  }
+  if (e == hipSuccess && h->wal_pending && !h->wal_pending_done) h->wal_pending_waited = true;  // the begun WAL encode was enqueued before this wait
+  return e;
+}
+
 int raftq_detail::ensure_tick_state(raftq_t* h) {
   if (h->role) return RAFTQ_OK;
   // all six or none: `role` stands for the group
@@ -1092,11 +1137,36 @@ int raftq_detail::refuse_read_index(raftq_t* h, const char* who) {
   return fail(h, RAFTQ_ESTATE, std::string(who) + ": raftq_set_read_index is RAFTQ_READ_SAFE (read index): this call's device-built heartbeats do not carry "
                                                   "the pending read's context -- step the MsgBeat (RAFTQ_OUT_BCAST_HEARTBEAT, index) and send the round");
 }
-constexpr uint32_t kCheckQuorumMaxTick = 0xffffu;  // lead_elapsed shares its word with the activity bits (raftq_t::cq)
 
-static int ensure_tick_offsets2(raftq_t* h, uint64_t nw);
-static int ensure_tick_offsets3(raftq_t* h);
-static hipError_t wait_turn(raftq_t* h, uint64_t flag_epoch, int kind = 0);
+// ---- the cq word on the host (raftq_kernels.hpp kCq*: activity bits, leadTransferee, lead_elapsed) ------------------------------
+constexpr uint32_t kCheckQuorumMaxTick = 0xffffffffu >> kCqElapsedShift;  // lead_elapsed shares its word with the activity bits (raftq_t::cq)
+
+// Set-up and test traffic, not a hot path: the whole array comes down, and -- cq_update -- goes back up.
+static int cq_fetch(raftq_t* h, std::vector<uint32_t>& w) {
+  HIPCHK(h, hipMemcpyAsync(w.data(), h->cq, h->G * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return RAFTQ_OK;
+}
+// each(g, w) sees every group's word
+template <class Each>
+static int cq_read(raftq_t* h, Each each) {
+  std::vector<uint32_t> w(h->G);
+  if (int rc = cq_fetch(h, w)) return rc;
+  for (uint64_t g = 0; g < h->G; ++g) each(g, w[g]);
+  return RAFTQ_OK;
+}
+// every group's word becomes next(g, w); fetch == false: next gives every field, so w is 0 and nothing is read back first.  The
+// caller has validated its input: nothing here fails over a value, so a refused call has loaded nothing.
+template <class Next>
+static int cq_update(raftq_t* h, bool fetch, Next next) {
+  std::vector<uint32_t> w(h->G);
+  if (fetch)
+    if (int rc = cq_fetch(h, w)) return rc;
+  for (uint64_t g = 0; g < h->G; ++g) w[g] = next(g, w[g]);
+  HIPCHK(h, hipMemcpyAsync(h->cq, w.data(), h->G * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return RAFTQ_OK;
+}
 
 extern "C" {
 
@@ -1169,6 +1239,32 @@ static void launch_tick(raftq_t* h) {
     hipLaunchKernelGGL(tick_kernel, grid, dim3(kBlock), 0, h->stream, tick_args(h, h->tick_no++));
 }
 
+// Past 16K waves every workgroup of a lists kernel summing its predecessors itself would show: the partials are scanned first
+constexpr uint64_t kTickScanWaves = 1u << 14;
+static bool tick_scans(const raftq_t* h) { return h->gpad / 256 > kTickScanWaves; }
+// ... into h->offsets (MsgHup), which every handle has, and *arr = h->tick_offsets2 (MsgBeat) / h->tick_offsets3 (failed checks), made
+// here -- before the Tick: a call that fails has not ticked
+static int ensure_tick_offsets(raftq_t* h, uint64_t** arr) {
+  if (*arr) return RAFTQ_OK;
+  HIPCHK(h, raftq_buf::alloc_device((void**)arr, (h->gpad / 256 + 1) * 8));
+  return RAFTQ_OK;
+}
+// The handle's Tick and, where tick_scans(), the scans of its partials; checks: the third scan too (raftq_tick_set_checks).  What
+// comes back are the scanned offsets for the lists kernel behind it, or nulls.
+struct TickOffsets {
+  const uint64_t *hup = nullptr, *beat = nullptr, *chk = nullptr;
+};
+static TickOffsets tick_enqueue(raftq_t* h, bool checks) {
+  launch_tick(h);
+  h->ticked = true;
+  if (!tick_scans(h)) return {};
+  const uint64_t nw = h->gpad / 256;
+  hipLaunchKernelGGL(scan_partials_kernel, dim3(1), dim3(1024), 0, h->stream, h->tick_partials, nw, h->offsets, h->d_total, 0);
+  hipLaunchKernelGGL(scan_partials_kernel, dim3(1), dim3(1024), 0, h->stream, h->tick_partials, nw, h->tick_offsets2, h->d_total + 1, 1);
+  if (checks) hipLaunchKernelGGL(scan_partials_kernel, dim3(1), dim3(1024), 0, h->stream, h->tick_partials, nw, h->tick_offsets3, h->d_total + 4, 2);
+  return {h->offsets, h->tick_offsets2, checks ? h->tick_offsets3 : nullptr};
+}
+
 int raftq_set_check_quorum(raftq_t* h, int on) {
   if (int rc = use_device_idle(h, "raftq_set_check_quorum")) return rc;
   if (on != 0 && on != 1)
@@ -1204,9 +1300,6 @@ int raftq_set_pre_vote(raftq_t* h, int on) {
   return RAFTQ_OK;
 }
 
-// leadTransferee: bits 12..15 of the cq word (0 = None, else slot + 1), beside the activity bits 0..8 and below lead_elapsed
-constexpr uint32_t kTransfereeShift = 12, kTransfereeMask = 0xf000u;
-
 int raftq_set_lead_transfer(raftq_t* h, int on) {
   if (int rc = use_device_idle(h, "raftq_set_lead_transfer")) return rc;
   if (on != 0 && on != 1)
@@ -1215,14 +1308,8 @@ int raftq_set_lead_transfer(raftq_t* h, int on) {
   if (on == 1 && !h->cq)
     return fail(h, RAFTQ_ESTATE, "raftq_set_lead_transfer: requires raftq_set_check_quorum (check quorum): the transferee lives in the lease's word and the "
                                  "Tick's check is what aborts a transfer");
-  if (on == 0 && h->lead_transfer) {  // no transfer outlives the switch: the bits are 0 on every handle without it
-    std::vector<uint32_t> w(h->G);
-    HIPCHK(h, hipMemcpyAsync(w.data(), h->cq, h->G * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (uint64_t g = 0; g < h->G; ++g) w[g] &= ~kTransfereeMask;
-    HIPCHK(h, hipMemcpyAsync(h->cq, w.data(), h->G * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
+  if (on == 0 && h->lead_transfer)  // no transfer outlives the switch: the bits are 0 on every handle without it
+    if (int rc = cq_update(h, true, [](uint64_t, uint32_t w) { return w & ~kCqTransfereeMask; })) return rc;
   h->lead_transfer = on == 1;
   return RAFTQ_OK;
 }
@@ -1233,24 +1320,14 @@ int raftq_load_transfer(raftq_t* h, const uint8_t* transferee) {
   if (!transferee) return fail(h, RAFTQ_EINVAL, "raftq_load_transfer: null transferee array");
   for (uint64_t g = 0; g < h->G; ++g)
     if (transferee[g] > h->N) return fail(h, RAFTQ_EINVAL, "raftq_load_transfer: a transferee is 0 (None) or a peer slot + 1 <= n_peers; nothing loaded");
-  std::vector<uint32_t> w(h->G);
-  HIPCHK(h, hipMemcpyAsync(w.data(), h->cq, h->G * 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  for (uint64_t g = 0; g < h->G; ++g) w[g] = (w[g] & ~kTransfereeMask) | ((uint32_t)transferee[g] << kTransfereeShift);
-  HIPCHK(h, hipMemcpyAsync(h->cq, w.data(), h->G * 4, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return RAFTQ_OK;
+  return cq_update(h, true, [&](uint64_t g, uint32_t w) { return (w & ~kCqTransfereeMask) | ((uint32_t)transferee[g] << kCqTransfereeShift); });
 }
 
 int raftq_read_transfer(raftq_t* h, uint8_t* transferee) {
   if (int rc = use_device_idle(h, "raftq_read_transfer")) return rc;
   if (!h->lead_transfer) return fail(h, RAFTQ_ESTATE, "raftq_read_transfer: raftq_set_lead_transfer is off (lead transfer): the handle holds no transferee");
   if (!transferee) return fail(h, RAFTQ_EINVAL, "raftq_read_transfer: null transferee array");
-  std::vector<uint32_t> w(h->G);
-  HIPCHK(h, hipMemcpyAsync(w.data(), h->cq, h->G * 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  for (uint64_t g = 0; g < h->G; ++g) transferee[g] = (uint8_t)((w[g] & kTransfereeMask) >> kTransfereeShift);
-  return RAFTQ_OK;
+  return cq_read(h, [&](uint64_t g, uint32_t x) { transferee[g] = (uint8_t)((x & kCqTransfereeMask) >> kCqTransfereeShift); });
 }
 
 // ---- ReadIndex (include/raftq.h "ReadIndex"): the switch, and the safe mode's records in bulk
@@ -1368,30 +1445,21 @@ int raftq_load_activity(raftq_t* h, const uint16_t* active, const uint32_t* lead
     if (lead_elapsed && lead_elapsed[g] > kCheckQuorumMaxTick)
       return fail(h, RAFTQ_EINVAL, "raftq_load_activity: lead_elapsed is kept in 16 bits: a value above 65535; nothing loaded");
   }
-  std::vector<uint32_t> w(h->G);
-  if (!active || !lead_elapsed || h->lead_transfer) {  // (a pending transferee stays where it is: raftq_load_transfer's)
-    HIPCHK(h, hipMemcpyAsync(w.data(), h->cq, h->G * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  for (uint64_t g = 0; g < h->G; ++g)
-    w[g] = (active ? active[g] | (h->lead_transfer ? w[g] & kTransfereeMask : 0u) : w[g] & 0xffffu) | (lead_elapsed ? lead_elapsed[g] << 16 : w[g] & 0xffff0000u);
-  HIPCHK(h, hipMemcpyAsync(h->cq, w.data(), h->G * 4, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return RAFTQ_OK;
+  const bool transfers = h->lead_transfer;  // (a pending transferee stays where it is: raftq_load_transfer's)
+  return cq_update(h, !active || !lead_elapsed || transfers, [&](uint64_t g, uint32_t w) {
+    const uint32_t low = active ? active[g] | (transfers ? w & kCqTransfereeMask : 0u) : w & kCqLowMask;
+    return low | (lead_elapsed ? lead_elapsed[g] << kCqElapsedShift : w & ~kCqLowMask);
+  });
 }
 
 int raftq_read_activity(raftq_t* h, uint16_t* active, uint32_t* lead_elapsed) {
   if (int rc = use_device_idle(h, "raftq_read_activity")) return rc;
   if (!h->cq) return fail(h, RAFTQ_ESTATE, "raftq_read_activity: raftq_set_check_quorum is off: the handle holds no activity state");
   if (!active && !lead_elapsed) return RAFTQ_OK;
-  std::vector<uint32_t> w(h->G);
-  HIPCHK(h, hipMemcpyAsync(w.data(), h->cq, h->G * 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  for (uint64_t g = 0; g < h->G; ++g) {
-    if (active) active[g] = (uint16_t)(w[g] & ~kTransfereeMask);
-    if (lead_elapsed) lead_elapsed[g] = w[g] >> 16;
-  }
-  return RAFTQ_OK;
+  return cq_read(h, [&](uint64_t g, uint32_t x) {
+    if (active) active[g] = (uint16_t)(x & ~kCqTransfereeMask);
+    if (lead_elapsed) lead_elapsed[g] = x >> kCqElapsedShift;
+  });
 }
 
 int raftq_tick_set_voters(raftq_t* h, int on) {
@@ -1483,22 +1551,13 @@ int raftq_tick_collect(raftq_t* h, uint64_t* hups, uint64_t hup_cap, uint64_t* n
   if (int rc = ensure_tick_state(h)) return rc;
   const uint64_t cap_h = std::min<uint64_t>(hup_cap, h->G), cap_b = std::min<uint64_t>(beat_cap, h->G);
   if (int rc = ensure_adv(h, (cap_h + cap_b + 2) / 3 + 2)) return rc;
-  const uint64_t nw = h->gpad / 256;
-  if (nw > (1u << 14))
-    if (int rc = ensure_tick_offsets2(h, nw)) return rc;  // (before the Tick: a call that fails has not ticked)
+  if (tick_scans(h))
+    if (int rc = ensure_tick_offsets(h, &h->tick_offsets2)) return rc;
   h->tl_valid = h->tl_chk_valid = false;  // raftq_last_tick_lists hands out the lists of the LAST tick, and this is a newer one
-  launch_tick(h);
-  h->ticked = true;
-  const uint64_t *off_h = nullptr, *off_b = nullptr;
-  if (nw > (1u << 14)) {  // past 16K waves every workgroup summing its predecessors itself would show: scan first
-    hipLaunchKernelGGL(scan_partials_kernel, dim3(1), dim3(1024), 0, h->stream, h->tick_partials, nw, h->offsets, h->d_total, 0);
-    hipLaunchKernelGGL(scan_partials_kernel, dim3(1), dim3(1024), 0, h->stream, h->tick_partials, nw, h->tick_offsets2, h->d_total + 1, 1);
-    off_h = h->offsets;
-    off_b = h->tick_offsets2;
-  }
+  const TickOffsets off = tick_enqueue(h, false);
   uint64_t* list_d = (uint64_t*)h->adv.d;
   hipLaunchKernelGGL(tick_lists_kernel, dim3((unsigned)(h->gpad / 1024)), dim3(kBlock), 0, h->stream, (const uint64_t*)h->hup_bits,
-                     (const uint64_t*)h->beat_bits, (const uint4*)h->tick_partials, list_d, cap_h, list_d + cap_h, cap_b, h->d_total, off_h, off_b);
+                     (const uint64_t*)h->beat_bits, (const uint4*)h->tick_partials, list_d, cap_h, list_d + cap_h, cap_b, h->d_total, off.hup, off.beat);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipStreamSynchronize(h->stream));
   *n_hup = h->h_total[0];
@@ -1536,10 +1595,10 @@ int raftq_detail::tick_lists_prepare(raftq_t* h, const char* who, unsigned flags
   HIPCHK(h, h->tl.grow(need, std::max<uint64_t>(need, 1 << 16), &h->stream));
   // every allocation is made BEFORE the Tick is enqueued: a call that fails has not ticked (an allocation failure
   // behind the tick kernel left the timers advanced and the MsgHup / MsgBeat groups of that tick unreported)
-  if (h->gpad / 256 > (1u << 14)) {
-    if (int rc = ensure_tick_offsets2(h, h->gpad / 256)) return rc;
+  if (tick_scans(h)) {
+    if (int rc = ensure_tick_offsets(h, &h->tick_offsets2)) return rc;
     if (cap_c)
-      if (int rc = ensure_tick_offsets3(h)) return rc;
+      if (int rc = ensure_tick_offsets(h, &h->tick_offsets3)) return rc;
   }
   *tl = TickLists{flags, cap_h, cap_b, beat_at, map_off, nullptr};
   tl->cap_c = cap_c;
@@ -1548,42 +1607,27 @@ int raftq_detail::tick_lists_prepare(raftq_t* h, const char* who, unsigned flags
 }
 
 int raftq_detail::tick_lists_enqueue(raftq_t* h, TickLists* tl) {
-  const bool bitmap = tl->flags & RAFTQ_TICK_BEAT_BITMAP;
-  const uint64_t cap_h = tl->cap_h, cap_b = tl->cap_b;
   const uint64_t nw = h->gpad / 256;
-  launch_tick(h);
-  h->ticked = true;
-  const uint64_t *off_h = nullptr, *off_b = nullptr;
-  if (nw > (1u << 14)) {  // past 16K waves every workgroup summing its predecessors itself would show: scan first
-    hipLaunchKernelGGL(scan_partials_kernel, dim3(1), dim3(1024), 0, h->stream, h->tick_partials, nw, h->offsets, h->d_total, 0);
-    hipLaunchKernelGGL(scan_partials_kernel, dim3(1), dim3(1024), 0, h->stream, h->tick_partials, nw, h->tick_offsets2, h->d_total + 1, 1);
-    off_h = h->offsets;
-    off_b = h->tick_offsets2;
-    if (tl->cap_c) hipLaunchKernelGGL(scan_partials_kernel, dim3(1), dim3(1024), 0, h->stream, h->tick_partials, nw, h->tick_offsets3, h->d_total + 4, 2);
-  }
-  tl->off_beat = off_b;
-  tl->off_h = off_h;
+  const TickOffsets off = tick_enqueue(h, tl->cap_c != 0);
+  tl->off_beat = off.beat;
+  tl->off_h = off.hup;
   uint32_t* const hup_d = h->tl.d;
   uint32_t* const beat_d = h->tl.d + tl->beat_at;
   uint64_t* const map_d = (uint64_t*)((uint8_t*)h->tl.d + tl->map_off);
   // one block of 1,024 groups per workgroup of the lists kernel.  Four (runs of ~1,600 ids instead of ~400 at the bench's density)
   // measured no better: 47.1 against 46.5 us a call -- 1.6 MB of ids take the link 34 us however they are cut
   const dim3 grid((unsigned)((nw + kWaves - 1) / kWaves));
+  auto lists = [&](auto kernel, auto... checks) {
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, h->stream, (const uint64_t*)h->hup_bits, (const uint64_t*)h->beat_bits, (const uint4*)h->tick_partials,
+                       nw, hup_d, tl->cap_h, beat_d, tl->cap_b, map_d, h->d_total, off.hup, off.beat, checks...);
+  };
+  const bool bitmap = tl->flags & RAFTQ_TICK_BEAT_BITMAP;
   if (tl->cap_c) {  // the three-list form: the failed checks' ids too (raftq_tick_set_checks; launch_tick ran tick_check_kernel)
-    const TickChecksArgs c{(const uint64_t*)h->chk_bits, (uint32_t*)((uint8_t*)h->tl.d + tl->chk_off), tl->cap_c,
-                           off_h ? (const uint64_t*)h->tick_offsets3 : nullptr};
-    if (bitmap)
-      hipLaunchKernelGGL((tick_lists32_checks_kernel<true>), grid, dim3(kBlock), 0, h->stream, (const uint64_t*)h->hup_bits, (const uint64_t*)h->beat_bits,
-                         (const uint4*)h->tick_partials, nw, hup_d, cap_h, beat_d, cap_b, map_d, h->d_total, off_h, off_b, c);
-    else
-      hipLaunchKernelGGL((tick_lists32_checks_kernel<false>), grid, dim3(kBlock), 0, h->stream, (const uint64_t*)h->hup_bits, (const uint64_t*)h->beat_bits,
-                         (const uint4*)h->tick_partials, nw, hup_d, cap_h, beat_d, cap_b, map_d, h->d_total, off_h, off_b, c);
-  } else if (bitmap)
-    hipLaunchKernelGGL((tick_lists32_kernel<true>), grid, dim3(kBlock), 0, h->stream, (const uint64_t*)h->hup_bits, (const uint64_t*)h->beat_bits,
-                       (const uint4*)h->tick_partials, nw, hup_d, cap_h, beat_d, cap_b, map_d, h->d_total, off_h, off_b);
-  else
-    hipLaunchKernelGGL((tick_lists32_kernel<false>), grid, dim3(kBlock), 0, h->stream, (const uint64_t*)h->hup_bits, (const uint64_t*)h->beat_bits,
-                       (const uint4*)h->tick_partials, nw, hup_d, cap_h, beat_d, cap_b, map_d, h->d_total, off_h, off_b);
+    const TickChecksArgs c{(const uint64_t*)h->chk_bits, (uint32_t*)((uint8_t*)h->tl.d + tl->chk_off), tl->cap_c, off.chk};
+    if (bitmap) lists(tick_lists32_checks_kernel<true>, c);
+    else lists(tick_lists32_checks_kernel<false>, c);
+  } else if (bitmap) lists(tick_lists32_kernel<true>);
+  else lists(tick_lists32_kernel<false>);
   HIPCHK(h, hipGetLastError());
   return RAFTQ_OK;
 }
@@ -1680,20 +1724,6 @@ int raftq_last_tick_checks(raftq_t* h, const uint32_t** checks, uint64_t* n_list
   if (n_total) *n_total = h->tl_n_chk;
   return RAFTQ_OK;
 }
-
-}  // extern "C"
-static int ensure_tick_offsets3(raftq_t* h) {
-  if (h->tick_offsets3) return RAFTQ_OK;
-  HIPCHK(h, raftq_buf::alloc_device((void**)&h->tick_offsets3, (h->gpad / 256 + 1) * 8));
-  return RAFTQ_OK;
-}
-static int ensure_tick_offsets2(raftq_t* h, uint64_t nw) {
-  if (h->tick_offsets2) return RAFTQ_OK;
-  (void)nw;
-  HIPCHK(h, raftq_buf::alloc_device((void**)&h->tick_offsets2, (h->gpad / 256 + 1) * 8));
-  return RAFTQ_OK;
-}
-extern "C" {
 
 int raftq_read_tick(raftq_t* h, uint8_t* action, uint32_t* elapsed, uint8_t* role) {
   if (int rc = use_device_idle(h, "raftq_read_tick")) return rc;
@@ -1898,54 +1928,6 @@ int raftq_last_advances(raftq_t* h, const raftq_advance_t** list, uint64_t* n_li
 }
 
 }  // extern "C" (templates need C++ linkage)
-
-// The end of a batching turn.  A turn is ~55 us of device work, so the wake-up of a blocking
-// hipStreamSynchronize (interrupt + reschedule, ~8 us) is a visible slice of it.  When the turn ends in a
-// compaction, a one-thread kernel behind it stores a completion epoch into pinned host memory:
-// the host polls the word -- bounded, then falls back to the blocking wait.
-// (Polling hipStreamQuery instead was measured SLOWER than blocking: 88 vs 80 us per turn, profiles/r02.)
-static hipError_t wait_turn(raftq_t* h, uint64_t flag_epoch, int kind) {
-  // A miss (the flag did not land within 2 ms; a turn is ~50 us) is either a slow turn -- a huge handle, a contended
-  // GPU, a profiler -- or a stack on which the flag never reaches the host.  One slow turn must not change the handle's
-  // steady state (ADVICE r03), so the wake-up is only given up after kMisses misses IN A ROW, and then tried again every
-  // kRetry turns; RAFTQ_PROFILE prints how many turns fell back to the blocking wait.
-  constexpr uint32_t kMisses = 8, kRetry = 1024;
-  const bool try_flag = flag_epoch && (h->flag_misses[kind] < kMisses || (++h->flag_rested[kind] % kRetry) == 0);
-  if (try_flag) {
-    volatile uint64_t* flag = h->h_total + 3;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (int i = 0;; ++i) {
-      if ((*flag & h->flag_mask) == flag_epoch) {
-        std::atomic_thread_fence(std::memory_order_acquire);
-        h->flag_misses[kind] = 0;
-        // the word says the stream's work is done; an asynchronous error of that work is only known to the runtime (ADVICE r05:
-        // the poll returned success without asking, and the error surfaced in a later call).  Whatever this thread has on
-        // record -- possibly a benign, older one -- is cleared and the stream itself is asked: its answer is the call's.
-        if (hipPeekAtLastError() == hipSuccess) return hipSuccess;
-        (void)hipGetLastError();
-        return hipStreamSynchronize(h->stream);
-      }
-      if ((i & 255) == 255 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(2000)) break;
-    }
-    ++h->flag_misses[kind];
-  }
-  if (flag_epoch) ++h->flag_fallbacks;
-  return hipStreamSynchronize(h->stream);
-}
-
-hipError_t raftq_detail::wait_call(raftq_t* h) {
-  hipError_t e;
-  if (!h->d_total) {
-    e = hipStreamSynchronize(h->stream);
-  } else {
-    const uint64_t epoch = ++h->compact_epoch;
-    h->flag_mask = ~0ull;
-    hipLaunchKernelGGL(raise_flag_kernel, dim3(1), dim3(64), 0, h->stream, h->d_total + 3, epoch);
-    e = hipGetLastError() != hipSuccess ? hipStreamSynchronize(h->stream) : wait_turn(h, epoch, 1);
-  }
-  if (e == hipSuccess && h->wal_pending && !h->wal_pending_done) h->wal_pending_waited = true;  // the begun WAL encode was enqueued before this wait
-  return e;
-}
 
 // One batching turn (raft.go:227-235 for every group at once): ingest -> sweep -> advance list, one wait.
 // Rec / AbiRec: layout of the match deltas; Adv / AbiAdv: layout of the advance list.
@@ -2216,10 +2198,10 @@ hipError_t set_write_tables(raftq_set_t* s) {
   const size_t n = s->members.size();
   for (int k = 0; k < 2; ++k) {
     set_fill_table(s, k, s->tab_host);
-    if (hipError_t e = hipMemcpy(s->tab[k], s->tab_host.data(), n * sizeof(SweepArgs), hipMemcpyHostToDevice)) return e;
+    if (hipError_t e = hipMemcpy(s->tab[k].d, s->tab_host.data(), n * sizeof(SweepArgs), hipMemcpyHostToDevice)) return e;
     if (!s->allow_voters) continue;
     set_fill_vtable(s, k, s->vtab_host);
-    if (hipError_t e = hipMemcpy(s->vtab[k], s->vtab_host.data(), n * sizeof(VoterSweepArgs), hipMemcpyHostToDevice)) return e;
+    if (hipError_t e = hipMemcpy(s->vtab[k].d, s->vtab_host.data(), n * sizeof(VoterSweepArgs), hipMemcpyHostToDevice)) return e;
   }
   return hipSuccess;
 }
@@ -2269,11 +2251,14 @@ int set_create(raftq_t* const* handles, uint32_t n, raftq_set_t** out, bool allo
   };
   hipError_t e = hipSetDevice(s->device);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
-  for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipMalloc((void**)&s->tab[k], (size_t)n * sizeof(SweepArgs));
-  for (int k = 0; k < 3 && e == hipSuccess && allow_voters; ++k) e = hipMalloc((void**)&s->vtab[k], (size_t)n * sizeof(VoterSweepArgs));
-  if (e == hipSuccess) e = hipMalloc((void**)&s->counts_d, (size_t)n * 32);
-  if (e == hipSuccess) e = hipMalloc((void**)&s->np_d, (size_t)n * 8);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&s->counts_h, (size_t)n * 32, hipHostMallocDefault);
+  auto take = [&](auto& buf, size_t bytes) {  // (nothing is held yet: no wait)
+    if (e == hipSuccess) e = buf.grow(bytes, bytes, nullptr);
+  };
+  for (int k = 0; k < 3; ++k) take(s->tab[k], (size_t)n * sizeof(SweepArgs));
+  for (int k = 0; k < 3 && allow_voters; ++k) take(s->vtab[k], (size_t)n * sizeof(VoterSweepArgs));
+  take(s->counts, (size_t)n * 32);
+  take(s->np, (size_t)n * 8);
+  take(s->counts_h, (size_t)n * 32);
   if (e == hipSuccess) e = hipEventCreate(&s->ev0);
   if (e == hipSuccess) e = hipEventCreate(&s->ev1);
   if (e != hipSuccess)
@@ -2318,17 +2303,12 @@ void raftq_set_destroy(raftq_set_t* s) {
     h->own_stream = false;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess) h->own_stream = true;
   }
-  for (int k = 0; k < 3; ++k) (void)hipFree(s->tab[k]);
-  for (int k = 0; k < 3; ++k) (void)hipFree(s->vtab[k]);
-  (void)hipFree(s->tick_vtab);
-  (void)hipFree(s->counts_d);
-  (void)hipFree(s->np_d);
-  (void)hipFree(s->tick_tab);
-  if (s->counts_h) (void)hipHostFree(s->counts_h);
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
-  if (s->stream) (void)hipStreamDestroy(s->stream);
+  // as in raftq_destroy: every buffer is a member of the set, so `delete s` releases them -- after the wait above, before the stream goes
+  const hipStream_t stream = s->stream;
   delete s;
+  if (stream) (void)hipStreamDestroy(stream);
 }
 
 uint32_t raftq_set_size(const raftq_set_t* s) { return s ? (uint32_t)s->members.size() : 0; }
@@ -2376,20 +2356,20 @@ int raftq_set_sweep_async(raftq_set_t* s, unsigned flags) {
     // a null mask pointer.  The grid form whatever raftq_set_mode says (a persistent masked walk is not built).
     if (cur < 0) {  // members disagree on which commit buffer is current: build this launch's table
       set_fill_vtable(s, -1, s->vtab_host);
-      SETCHK(s, hipMemcpyAsync(s->vtab[2], s->vtab_host.data(), s->vtab_host.size() * sizeof(VoterSweepArgs), hipMemcpyHostToDevice,
+      SETCHK(s, hipMemcpyAsync(s->vtab[2].d, s->vtab_host.data(), s->vtab_host.size() * sizeof(VoterSweepArgs), hipMemcpyHostToDevice,
                                s->stream));
     }
-    const VoterSetLaunch V{s->vtab[cur < 0 ? 2 : cur], (uint32_t)s->members.size(), (flags & RAFTQ_SWEEP_CHANGED) ? 1u : 0u, s->gpad};
+    const VoterSetLaunch V{s->vtab[cur < 0 ? 2 : cur].d, (uint32_t)s->members.size(), (flags & RAFTQ_SWEEP_CHANGED) ? 1u : 0u, s->gpad};
     SETCHK(s, launch_set_voters(s->N, V, flags, nt, s->stream));
     for (raftq_t* h : s->members) sweep_done(h, flags, voters_gpl((int)s->N));
     s->swept = true;
     s->last_flags = flags;
     return RAFTQ_OK;
   }
-  const SweepArgs* tab = s->tab[cur < 0 ? 2 : cur];
+  const SweepArgs* tab = s->tab[cur < 0 ? 2 : cur].d;
   if (cur < 0) {  // members disagree on which commit buffer is current: build this launch's table
     set_fill_table(s, -1, s->tab_host);
-    SETCHK(s, hipMemcpyAsync(s->tab[2], s->tab_host.data(), s->tab_host.size() * sizeof(SweepArgs), hipMemcpyHostToDevice,
+    SETCHK(s, hipMemcpyAsync(s->tab[2].d, s->tab_host.data(), s->tab_host.size() * sizeof(SweepArgs), hipMemcpyHostToDevice,
                              s->stream));
   }
   SweepLaunch L;
@@ -2406,57 +2386,60 @@ int raftq_set_sweep_async(raftq_set_t* s, unsigned flags) {
   return RAFTQ_OK;
 }
 
-// raftq_set_tick when at least one member asks promotable(): tick_set_voters_kernel over a table of the members' TickArgs, mask
-// pointer and self slot.  A member that does not ask -- no masks, or the switch off -- has a null pointer there and ticks as
-// tick_kernel would.  The table is rebuilt whenever what it was built from differs from what the members hold now: a member
-// re-configured or ticked on its own (or by the plain dispatch), masks loaded, re-allocated or dropped, the switch or the self
-// slot changed.  It is written on the set's stream, behind every dispatch that read it.  RAFTQ_TICK_SHAPE does not apply.
-static int set_tick_voters(raftq_set_t* s) {
+}  // extern "C" (templates need C++ linkage)
+
+// An entry of a set Tick's table, as the member stands now: its TickArgs, or -- the dispatch in which a member asks promotable() --
+// those with its mask pointer and self slot.  A member that does not ask (no masks, or the switch off) has a null pointer there and
+// ticks as tick_kernel would.
+static void tick_entry(const raftq_t* h, TickArgs& a) { a = tick_args(h, h->tick_no); }
+static void tick_entry(const raftq_t* h, TickVotersArgs& a) {
+  tick_entry(h, a.t);
+  a.voters = raftq_detail::masked_tick(h) ? h->voters : nullptr;
+  a.self = h->self_peer;
+  a.pad = 0;
+}
+// ... differs from what the table was built from `since` set ticks ago: the member was re-configured, its tick state came into
+// being, it ticked on its own or through the other dispatch, its masks were loaded, re-allocated or dropped, the switch or the self
+// slot changed
+static bool tick_entry_moved(const TickArgs& now, const TickArgs& was, uint64_t since) {
+  return now.role != was.role || now.seed != was.seed || now.election_tick != was.election_tick || now.heartbeat_tick != was.heartbeat_tick ||
+         now.tick_no != was.tick_no + since;
+}
+static bool tick_entry_moved(const TickVotersArgs& now, const TickVotersArgs& was, uint64_t since) {
+  return tick_entry_moved(now.t, was.t, since) || now.voters != was.voters || now.self != was.self;
+}
+// The table of one of raftq_set_tick's two dispatches, rewritten whenever an entry moved: on the set's stream, behind every dispatch
+// that read it.  Each dispatch has a table and a count of its own, so either finds the other's stale by the tick numbers alone.
+template <class Entry>
+static int set_tick_table(raftq_set_t* s, raftq_set::Dev<Entry>& tab, std::vector<Entry>& host, uint64_t& since) {
   const size_t K = s->members.size();
-  for (raftq_t* h : s->members)
-    if (int rc = ensure_tick_state(h)) return sfail(s, rc, h->err);
-  auto entry = [](const raftq_t* h) {
-    TickVotersArgs a;
-    a.t = tick_args(h, h->tick_no);
-    a.voters = raftq_detail::masked_tick(h) ? h->voters : nullptr;
-    a.self = h->self_peer;
-    a.pad = 0;
-    return a;
-  };
-  bool stale = s->tick_vtab == nullptr || s->tick_vhost.size() != K;
+  bool stale = !tab.d || host.size() != K;
   for (size_t m = 0; m < K && !stale; ++m) {
-    const TickVotersArgs now = entry(s->members[m]), &was = s->tick_vhost[m];
-    stale = now.t.role != was.t.role || now.t.seed != was.t.seed || now.t.election_tick != was.t.election_tick ||
-            now.t.heartbeat_tick != was.t.heartbeat_tick || now.t.tick_no != was.t.tick_no + s->tick_vsince || now.voters != was.voters ||
-            now.self != was.self;
+    Entry now;
+    tick_entry(s->members[m], now);
+    stale = tick_entry_moved(now, host[m], since);
   }
-  if (stale) {
-    if (!s->tick_vtab) SETCHK(s, hipMalloc((void**)&s->tick_vtab, K * sizeof(TickVotersArgs)));
-    s->tick_vhost.resize(K);
-    for (size_t m = 0; m < K; ++m) s->tick_vhost[m] = entry(s->members[m]);
-    SETCHK(s, hipMemcpyAsync(s->tick_vtab, s->tick_vhost.data(), K * sizeof(TickVotersArgs), hipMemcpyHostToDevice, s->stream));  // (pageable: staged before it returns)
-    s->tick_vsince = 0;
-  }
-  hipLaunchKernelGGL(tick_set_voters_kernel, dim3((unsigned)(s->gpad / 1024), (unsigned)K), dim3(kBlock), 0, s->stream,
-                     (const TickVotersArgs*)s->tick_vtab, s->tick_vsince);
-  SETCHK(s, hipGetLastError());
-  ++s->tick_vsince;
-  for (raftq_t* h : s->members) {
-    h->tl_valid = false;
-    ++h->tick_no;
-    h->ticked = true;
-  }
+  if (!stale) return RAFTQ_OK;
+  // allocated once: a set's member count never changes (a destroyed member breaks the set, set_ready), so the table fits ever after
+  // and grow() frees nothing -- which is why no wait is passed although earlier dispatches may still read the table
+  SETCHK(s, tab.grow(K * sizeof(Entry), K * sizeof(Entry), nullptr));
+  host.resize(K);
+  for (size_t m = 0; m < K; ++m) tick_entry(s->members[m], host[m]);
+  SETCHK(s, hipMemcpyAsync(tab.d, host.data(), K * sizeof(Entry), hipMemcpyHostToDevice, s->stream));  // (pageable: staged before it returns)
+  since = 0;
   return RAFTQ_OK;
 }
+
+extern "C" {
 
 // rc.node.Tick() for every group of every member: ONE dispatch (blockIdx.y = member), enqueued on the set's stream.  The
 // members' per-handle results (action bytes, the MsgHup / MsgBeat bitmaps and counts behind raftq_collect_hups / _beats /
 // raftq_read_tick) are what raftq_tick on each member would have left.
 int raftq_set_tick(raftq_set_t* s) {
   if (int rc = set_ready(s, "raftq_set_tick")) return rc;
-  const size_t K = s->members.size();
+  const unsigned K = (unsigned)s->members.size();
   // promotable(): a member with masks loaded and raftq_tick_set_voters on (only ever in a set from raftq_set_create_voters).
-  // Checked for every member before anything is allocated or launched: a call that fails has ticked nobody.
+  // Every member is checked and has its tick state before anything is launched: a call that fails has ticked nobody.
   bool masked = false;
   for (raftq_t* h : s->members) {
     if (h->step_collected != h->step_submitted)
@@ -2465,56 +2448,41 @@ int raftq_set_tick(raftq_set_t* s) {
     if (int rc = raftq_detail::refuse_check_quorum(h, "raftq_set_tick")) return sfail(s, rc, h->err);
     masked = masked || raftq_detail::masked_tick(h);
   }
-  if (masked) return set_tick_voters(s);
-  bool stale = s->tick_tab == nullptr || s->tick_host.size() != K;
-  for (size_t m = 0; m < K; ++m) {
-    raftq_t* h = s->members[m];
-    if (h->step_collected != h->step_submitted)
-      return sfail(s, RAFTQ_ESTATE, "raftq_set_tick: a member has Step batches in flight; collect them first");
-    const bool fresh = h->role == nullptr;
+  for (raftq_t* h : s->members)
     if (int rc = ensure_tick_state(h)) return sfail(s, rc, h->err);
-    if (stale || fresh) {
-      stale = true;
-      continue;
-    }
-    const TickArgs now = tick_args(h, h->tick_no), &was = s->tick_host[m];
-    if (now.role != was.role || now.seed != was.seed || now.election_tick != was.election_tick || now.heartbeat_tick != was.heartbeat_tick ||
-        now.tick_no != was.tick_no + s->tick_since)
-      stale = true;  // a member was re-configured, or ticked on its own since the table was built
-  }
-  if (stale) {
-    if (!s->tick_tab) SETCHK(s, hipMalloc((void**)&s->tick_tab, K * sizeof(TickArgs)));
-    s->tick_host.resize(K);
-    for (size_t m = 0; m < K; ++m) s->tick_host[m] = tick_args(s->members[m], s->members[m]->tick_no);
-    SETCHK(s, hipMemcpyAsync(s->tick_tab, s->tick_host.data(), K * sizeof(TickArgs), hipMemcpyHostToDevice, s->stream));  // (pageable: staged before it returns)
-    s->tick_since = 0;
-  }
+  uint64_t& since = masked ? s->tick_vsince : s->tick_since;
   const uint64_t n_blocks = s->gpad / 1024;
-  // RAFTQ_TICK_SHAPE: wide1 (default: 16 groups per lane, one 1,024-group block per wave: 14.9 us per 8 x 1M groups = 0.70 of HBM
-  // in steady state, profiles/r05), wide2 / wide4 (two / four blocks per wave: 16.1 / 17.2), narrow (round 4's 4 groups per lane,
-  // four rounds per workgroup: 15.7).  Same results, byte for byte (tests/test_parity_gpu.py runs the set Tick in every shape).
-  // (read at every call -- a getenv is nothing beside a launch -- so that a test or the bench can A/B the shapes in one process)
-  int shape_now = 1;
-  if (const char* e = std::getenv("RAFTQ_TICK_SHAPE"))
-    shape_now = std::strcmp(e, "narrow") == 0 ? 0 : std::strcmp(e, "wide2") == 0 ? 2 : std::strcmp(e, "wide4") == 0 ? 4 : 1;
-  auto wide_grid = [&](int r) { return dim3((unsigned)((n_blocks + (uint64_t)kWaves * r - 1) / ((uint64_t)kWaves * r)), (unsigned)K); };
-  switch (shape_now) {
-    case 0:
-      hipLaunchKernelGGL(tick_set_kernel, dim3((unsigned)((n_blocks + kTickSetRounds - 1) / kTickSetRounds), (unsigned)K), dim3(kBlock), 0, s->stream,
-                         (const TickArgs*)s->tick_tab, s->tick_since, n_blocks);
-      break;
-    case 2:
-      hipLaunchKernelGGL((tick_set_wide_kernel<2>), wide_grid(2), dim3(kBlock), 0, s->stream, (const TickArgs*)s->tick_tab, s->tick_since, n_blocks);
-      break;
-    case 4:
-      hipLaunchKernelGGL((tick_set_wide_kernel<4>), wide_grid(4), dim3(kBlock), 0, s->stream, (const TickArgs*)s->tick_tab, s->tick_since, n_blocks);
-      break;
-    default:
-      hipLaunchKernelGGL((tick_set_wide_kernel<kTickWideBlocks>), wide_grid(kTickWideBlocks), dim3(kBlock), 0, s->stream, (const TickArgs*)s->tick_tab,
-                         s->tick_since, n_blocks);
+  if (masked) {  // tick_set_voters_kernel over the members' TickVotersArgs; RAFTQ_TICK_SHAPE does not apply
+    if (int rc = set_tick_table(s, s->tick_vtab, s->tick_vhost, since)) return rc;
+    hipLaunchKernelGGL(tick_set_voters_kernel, dim3((unsigned)n_blocks, K), dim3(kBlock), 0, s->stream, (const TickVotersArgs*)s->tick_vtab.d, since);
+  } else {
+    if (int rc = set_tick_table(s, s->tick_tab, s->tick_host, since)) return rc;
+    const TickArgs* tab = s->tick_tab.d;
+    // RAFTQ_TICK_SHAPE: wide1 (default: 16 groups per lane, one 1,024-group block per wave: 14.9 us per 8 x 1M groups = 0.70 of HBM
+    // in steady state, profiles/r05), wide2 / wide4 (two / four blocks per wave: 16.1 / 17.2), narrow (round 4's 4 groups per lane,
+    // four rounds per workgroup: 15.7).  Same results, byte for byte (tests/test_parity_gpu.py runs the set Tick in every shape).
+    // (read at every call -- a getenv is nothing beside a launch -- so that a test or the bench can A/B the shapes in one process)
+    int shape_now = 1;
+    if (const char* e = std::getenv("RAFTQ_TICK_SHAPE"))
+      shape_now = std::strcmp(e, "narrow") == 0 ? 0 : std::strcmp(e, "wide2") == 0 ? 2 : std::strcmp(e, "wide4") == 0 ? 4 : 1;
+    auto wide_grid = [&](int r) { return dim3((unsigned)((n_blocks + (uint64_t)kWaves * r - 1) / ((uint64_t)kWaves * r)), K); };
+    switch (shape_now) {
+      case 0:
+        hipLaunchKernelGGL(tick_set_kernel, dim3((unsigned)((n_blocks + kTickSetRounds - 1) / kTickSetRounds), K), dim3(kBlock), 0, s->stream, tab, since,
+                           n_blocks);
+        break;
+      case 2:
+        hipLaunchKernelGGL((tick_set_wide_kernel<2>), wide_grid(2), dim3(kBlock), 0, s->stream, tab, since, n_blocks);
+        break;
+      case 4:
+        hipLaunchKernelGGL((tick_set_wide_kernel<4>), wide_grid(4), dim3(kBlock), 0, s->stream, tab, since, n_blocks);
+        break;
+      default:
+        hipLaunchKernelGGL((tick_set_wide_kernel<kTickWideBlocks>), wide_grid(kTickWideBlocks), dim3(kBlock), 0, s->stream, tab, since, n_blocks);
+    }
   }
   SETCHK(s, hipGetLastError());
-  ++s->tick_since;
+  ++since;
   for (raftq_t* h : s->members) {
     h->tl_valid = false;
     ++h->tick_no;
@@ -2531,15 +2499,15 @@ int raftq_set_wait(raftq_set_t* s, raftq_counts_t* per_member, raftq_counts_t* t
     if (!s->swept) return sfail(s, RAFTQ_ESTATE, "raftq_set_wait: no set sweep to report on");
     // the tallies of the LAST sweep of every member (a member swept on its own since then reports that sweep)
     set_fill_table(s, -1, s->tab_host);
-    SETCHK(s, hipMemcpyAsync(s->tab[2], s->tab_host.data(), n * sizeof(SweepArgs), hipMemcpyHostToDevice, s->stream));
+    SETCHK(s, hipMemcpyAsync(s->tab[2].d, s->tab_host.data(), n * sizeof(SweepArgs), hipMemcpyHostToDevice, s->stream));
     // number of per-wave partials of every member's last sweep (pageable source: staged before the call returns)
     s->np_host.resize(n);
     for (size_t i = 0; i < n; ++i) s->np_host[i] = s->members[i]->n_partials;
-    SETCHK(s, hipMemcpyAsync(s->np_d, s->np_host.data(), n * 8, hipMemcpyHostToDevice, s->stream));
-    hipLaunchKernelGGL(set_counts_kernel, dim3((unsigned)n), dim3(kBlock), 0, s->stream, (const SweepArgs*)s->tab[2],
-                       (const uint64_t*)s->np_d, s->counts_d);
+    SETCHK(s, hipMemcpyAsync(s->np.d, s->np_host.data(), n * 8, hipMemcpyHostToDevice, s->stream));
+    hipLaunchKernelGGL(set_counts_kernel, dim3((unsigned)n), dim3(kBlock), 0, s->stream, (const SweepArgs*)s->tab[2].d,
+                       (const uint64_t*)s->np.d, s->counts.d);
     SETCHK(s, hipGetLastError());
-    SETCHK(s, hipMemcpyAsync(s->counts_h, s->counts_d, n * 32, hipMemcpyDeviceToHost, s->stream));
+    SETCHK(s, hipMemcpyAsync(s->counts_h.h, s->counts.d, n * 32, hipMemcpyDeviceToHost, s->stream));
   }
   SETCHK(s, hipStreamSynchronize(s->stream));
   if (want) {
@@ -2548,7 +2516,7 @@ int raftq_set_wait(raftq_set_t* s, raftq_counts_t* per_member, raftq_counts_t* t
       const unsigned f = s->members[i]->last_flags;
       const bool commit = f & (RAFTQ_SWEEP_COMMIT | RAFTQ_SWEEP_GATED);
       const bool votes = f & RAFTQ_SWEEP_VOTES;
-      raftq_counts_t c{commit ? s->counts_h[4 * i] : 0, votes ? s->counts_h[4 * i + 1] : 0, votes ? s->counts_h[4 * i + 2] : 0};
+      raftq_counts_t c{commit ? s->counts_h.h[4 * i] : 0, votes ? s->counts_h.h[4 * i + 1] : 0, votes ? s->counts_h.h[4 * i + 2] : 0};
       if (per_member) per_member[i] = c;
       t.n_changed += c.n_changed;
       t.n_won += c.n_won;

@@ -130,7 +130,8 @@ struct raftq {
   uint32_t self_peer = 0;
   bool self_set = false;  // raftq_set_self has been called: the handle is a node's (raftq_tick_frames asks)
   // the records' copies of the dense arrays (role, committed, first_idx, match) are what those arrays hold: false after anything but
-  // Step / tail reports / proposals wrote them; the next Step-family call re-reads them first (raftq_step.hip ensure_mirror)
+  // Step / tail reports / proposals wrote them -- every such writer calls raftq_detail::dense_changed --; the next Step-family call
+  // re-reads them first (raftq_step.hip ensure_mirror)
   bool node_mirror_fresh = false;
   uint64_t node_mirror_refreshes = 0;
   void* node_rec = nullptr;        // raftqk::NodeRec [ld]: term, vote, lead, last_index, last_term + the list words of the batch in flight
@@ -255,6 +256,11 @@ struct raftq {
 
 // A set of handles of one shape on one GPU, swept by a single dispatch (raftq_set_*).
 struct raftq_set {
+  // the set's device and pinned memory: members, so `delete s` releases them (raftq_set_destroy: after its wait, before the stream goes)
+  template <class T>
+  struct Dev : raftq_buf::Buffer<T> {
+    Dev() : raftq_buf::Buffer<T>(raftq_buf::Kind::device) {}
+  };
   int device = 0;
   uint32_t N = 0;
   uint64_t gpad = 0;
@@ -262,33 +268,33 @@ struct raftq_set {
   hipStream_t stream = nullptr;       // the set's stream; every member is re-homed onto it
   // device tables of the members' SweepArgs: [0] every member reads commit buffer 0, [1] buffer 1,
   // [2] rebuilt per launch when the members' buffers differ (someone swept a member on its own)
-  raftqk::SweepArgs* tab[3] = {nullptr, nullptr, nullptr};
+  Dev<raftqk::SweepArgs> tab[3];
   std::vector<raftqk::SweepArgs> tab_host;  // pageable on purpose: hipMemcpyAsync stages it before returning
-  uint64_t* counts_d = nullptr;       // [members][4] {changed, won, lost, 0}, reduced on the device
-  uint64_t* np_d = nullptr;           // [members] number of per-wave partials of each member's last sweep
+  Dev<uint64_t> counts;               // [members][4] {changed, won, lost, 0}, reduced on the device
+  Dev<uint64_t> np;                   // [members] number of per-wave partials of each member's last sweep
   std::vector<uint64_t> np_host;
-  uint64_t* counts_h = nullptr;       // pinned
+  raftq_buf::Buffer<uint64_t> counts_h{raftq_buf::Kind::pinned};  // counts, copied out
   bool swept = false;
   bool broken = false;                // a member was destroyed under the set
   bool tab_stale = false;             // a member allocated its narrow mirror -- or, in a set that admits masks, its mask array came
                                       // or went -- since tab[0] / tab[1] (and vtab[0] / vtab[1]) were filled
   // raftq_set_create_voters: members may hold voter masks.  vtab[k] is tab[k] with every member's mask pointer beside its
   // SweepArgs (null: no masks loaded); a dispatch with at least one masked member reads it (sweep_set_voters_kernel), every
-  // other dispatch reads tab[k] and launches what a plain set launches.  nullptr in a set from raftq_set_create.
+  // other dispatch reads tab[k] and launches what a plain set launches.  Empty in a set from raftq_set_create.
   bool allow_voters = false;
-  raftqk::VoterSweepArgs* vtab[3] = {nullptr, nullptr, nullptr};
+  Dev<raftqk::VoterSweepArgs> vtab[3];
   std::vector<raftqk::VoterSweepArgs> vtab_host;
   unsigned last_flags = 0;
   int mode = 0;                       // 0 = K-deep grid, 1 = persistent walk (raftq_set_mode)
   uint32_t persist_wgs = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // raftq_set_tick: device table of the members' TickArgs (as of tick_host), set ticks dispatched since it was built
-  raftqk::TickArgs* tick_tab = nullptr;
+  Dev<raftqk::TickArgs> tick_tab;
   std::vector<raftqk::TickArgs> tick_host;
   uint64_t tick_since = 0;
   // ... and of their TickVotersArgs, for the set ticks in which a member asks promotable() (tick_set_voters_kernel): a table and
   // a count of its own, so either dispatch finds the other's table stale by the tick numbers alone
-  raftqk::TickVotersArgs* tick_vtab = nullptr;
+  Dev<raftqk::TickVotersArgs> tick_vtab;
   std::vector<raftqk::TickVotersArgs> tick_vhost;
   uint64_t tick_vsince = 0;
   std::string err;
@@ -312,6 +318,9 @@ int use_device_idle(raftq_t* h, const char* who);  // + no Step batch in flight 
 // raftq_propose_frames): let through once the handle opted in to raftq_bcast_set_voters -- their broadcasts then go to each group's
 // own members.  Each of the three switches opens its own calls and no others.
 int refuse_voters(raftq_t* h, const char* who, bool step_family = false, bool tick_rounds = false, bool bcast = false);
+// Every writer of the dense arrays (role, committed, first_idx, match) outside Step calls this: the records' copies are stale
+// (raftq_t::node_mirror_fresh), and the next Step-family call re-reads them first
+inline void dense_changed(raftq_t* h) { h->node_mirror_fresh = false; }
 // raftq_tick_set_voters on a handle with masks loaded: every Tick launch is tick_voters_kernel's, the rounds are beat_build_voters_kernel's and elect_build_voters_kernel's
 inline bool masked_tick(const raftq_t* h) { return h->voters != nullptr && h->tick_voters; }
 // raftq_bcast_set_voters on a handle with masks loaded: raftq_step_frames_respond walks with the masked Node and lays its answers

@@ -1677,6 +1677,11 @@ static __global__ __launch_bounds__(kBlock) void tick_set_voters_kernel(const Ti
 #undef RAFTQ_TV_MASKS
 }
 
+// The cq word, spelled once for the kernels and the host: the activity bits 0..8 and -- raftq_set_lead_transfer -- leadTransferee
+// (0 = None, else slot + 1) in the low half, lead_elapsed above it.
+constexpr uint32_t kCqLowMask = 0xffffu, kCqElapsedShift = 16;
+constexpr uint32_t kCqTransfereeShift = 12, kCqTransfereeMask = 0xf000u;
+
 // tick_kernel with upstream's CheckQuorum (raftq_set_check_quorum; include/raftq.h "CheckQuorum"): a leader counts its own
 // electionElapsed beside the heartbeat counter and, when it reaches election_tick, asks whether a quorum of the group's members
 // has answered since the last check.  The new state is ONE dense word per group -- the activity bits (Progress.RecentActive, bit p)
@@ -1690,7 +1695,7 @@ static __global__ __launch_bounds__(kBlock) void tick_set_voters_kernel(const Ti
 // without, members = all N slots and a non-leader ticks as tick_kernel does.  Bitmaps, action bytes and partials keep the one
 // layout.  A kernel of its own: tick_kernel, tick_voters_kernel and the set kernels keep their text.
 struct TickCheckArgs {
-  uint32_t* cq;            // [ld] in/out: active | lead_elapsed << 16
+  uint32_t* cq;            // [ld] in/out: active | lead_elapsed << kCqElapsedShift
   uint64_t* chk_bits;      // [gpad/64] hup_bits' layout, the groups whose check failed
   const uint16_t* voters;  // [ld] or nullptr
   uint32_t self, n_peers;
@@ -1749,11 +1754,11 @@ static __global__ __launch_bounds__(kBlock) void tick_check_kernel(TickArgs a, T
     if (__ballot(hup) != 0) hup = hup && d > (int64_t)tick_mod(tick_rand(key, (uint32_t)g + k), a.election_tick, a.et_magic);
     // the leader's own electionElapsed; the check itself only where some leader of the wave is due one
     const bool leads = valid && role == 2u;
-    const uint32_t le = (w[k] >> 16) + 1u, active = w[k] & 0xffffu;
+    const uint32_t le = (w[k] >> kCqElapsedShift) + 1u, active = w[k] & kCqLowMask;
     const bool due = leads && le >= a.election_tick;
     bool lost = false;
     if (__ballot(due) != 0) lost = due && (uint32_t)__popc((active | (1u << c.self)) & members) < ((uint32_t)__popc(members) >> 1) + 1u;
-    w[k] = !leads ? w[k] : (due ? (lost ? active : 0u) : (active | (le << 16)));
+    w[k] = !leads ? w[k] : (due ? (lost ? active : 0u) : (active | (le << kCqElapsedShift)));
     const uint32_t act = !valid ? 0u : (hup ? 1u : (lost ? 3u : (beat ? 2u : 0u)));
     e[k] = !valid ? e[k] : ((act == 1u || act == 2u || idle) ? 0u : v);
     acts |= act << (8 * k);

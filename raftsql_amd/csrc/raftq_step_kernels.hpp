@@ -129,7 +129,6 @@ constexpr uint8_t kMsgfEntries = 0x80, kMsgfBarrier = 0x40, kMsgfHold = 0x20, kM
 constexpr uint8_t kFlagHardState = 1, kFlagCommitted = 2, kFlagUpdated = 4, kFlagSteppedDown = 8;
 constexpr uint8_t kFlagTimeoutNow = 0x20;  // RAFTQ_OUTF_TIMEOUT_NOW: the transferee's Match is the tail -- send it MsgTimeoutNow
 constexpr uint8_t kFlagReadReady = 0x40;   // RAFTQ_OUTF_READ_READY: a quorum has confirmed the read(s) -- release them
-constexpr uint32_t kCqTransfereeShift = 12, kCqTransfereeMask = 0xf000u;  // leadTransferee (0 = None, else slot + 1) in the cq word
 constexpr uint8_t kFlagAnswered = 0x10;  // RAFTQ_OUTF_ANSWERED: the messages the result calls for were built on the device
 
 // What result i calls for, as the walk lane that stepped it saw the group (raftq_step_frames_respond; raftq_respond_kernels.hpp
@@ -835,8 +834,8 @@ struct NodeT {
           uint32_t members;
           if constexpr (MASKED) members = vmask;
           else members = (1u << a.n_peers) - 1u;
-          const uint32_t act = (uint32_t)__popc(((w & 0xffffu) | (1u << a.self)) & members);
-          set_cq(w & 0xffff0000u);
+          const uint32_t act = (uint32_t)__popc(((w & kCqLowMask) | (1u << a.self)) & members);
+          set_cq(w & ~kCqLowMask);
           if (act < q) become_follower(term, 0);
         } else if (CQ && a.lt && m.type == kMsgTransferLeader) {
           // stepLeader MsgTransferLeader: t = from.  A transfer to t already pending, or t no voter: ignored.  One to another slot is
@@ -846,7 +845,7 @@ struct NodeT {
           if (counts(t, a.n_peers) && (w & kCqTransfereeMask) >> kCqTransfereeShift != t + 1) {
             uint32_t nw = w & ~kCqTransfereeMask;
             if (t != a.self) {
-              nw = (nw & 0xffffu) | ((t + 1) << kCqTransfereeShift);
+              nw = (nw & kCqLowMask) | ((t + 1) << kCqTransfereeShift);
               o.type = kOutTransfer;
               o.index = match(t);
               if (o.index == last_index) o.flags |= kFlagTimeoutNow;

@@ -879,7 +879,7 @@ int raftq_detail::respond_finish(raftq_t* h, const RespPlan& p, raftq_wire_count
   return RAFTQ_OK;
 }
 
-// ---- raftq_tick_frames ------------------------------------------------------------------------------------------------
+// ---- raftq_tick_frames, raftq_tick_elect_frames ------------------------------------------------------------------------
 namespace {
 // the marshal of the heartbeats: as resp_marshal_call, the records go into the scratch behind an empty feed
 StreamCall beat_marshal_call(uint64_t n_max, uint64_t cap) {
@@ -889,146 +889,65 @@ StreamCall beat_marshal_call(uint64_t n_max, uint64_t cap) {
   sc.out_bytes = cap + 16;
   return sc;
 }
-// the heartbeat round of both calls, over each group's own members where the Tick is (the caller has opened the members word)
-void beat_enqueue(raftq_t* h, const NodeArrays& na, const raftq_detail::TickLists& tl, bool members, uint64_t beat_cap, WireMsg* enc) {
-  const uint64_t nw = h->gpad / 256;
-  const dim3 grid((unsigned)((nw + kWaves - 1) / kWaves));
-  BeatArgs ba{(const uint64_t*)h->beat_bits, (const uint4*)h->tick_partials, nw, tl.off_beat, (const uint64_t*)h->d_total, na.rec, h->G, h->N,
-              h->self_peer, beat_cap, enc};
-  if (members) hipLaunchKernelGGL(beat_build_voters_kernel, grid, dim3(kBlock), 0, h->stream, ba, (const uint16_t*)h->voters, members_word(h));
-  else hipLaunchKernelGGL(beat_build_kernel, grid, dim3(kBlock), 0, h->stream, ba);
-}
-}  // namespace
-
-extern "C" int raftq_tick_frames(raftq_t* h, unsigned flags, uint64_t hup_cap, uint64_t beat_cap, uint64_t* n_hup, uint64_t* n_beat, void* out,
-                                 uint64_t cap, uint64_t* frame_off, uint64_t* peer_off, raftq_wire_counts_t* counts) {
-  const char* who = "raftq_tick_frames";
+// The device-built round of raftq_tick_frames and raftq_tick_elect_frames: Tick -> lists -> beat_build -> elect_build -> encoder ->
+// flag, back to back; one wait.  elect: the election round behind the heartbeat round.  The encoder's input then holds
+// (beat_cap + hup_cap) * (N - 1) records: beat_build_kernel runs over the first beat_cap * (N - 1) (its fillers start where the
+// heartbeats end), elect_build_kernel, behind it in stream order, puts the votes directly behind the heartbeats and the fillers
+// behind both; peer_off gets a second section of N + 1 words and camp the campaigns' results.  Without it -- and with hup_cap == 0,
+// which is the same call -- hup_cap bounds the MsgHup list alone, camp is not looked at and peer_off is N + 1 words.
+int tick_round(raftq_t* h, bool elect, unsigned flags, uint64_t hup_cap, uint64_t beat_cap, uint64_t* n_hup, uint64_t* n_beat, raftq_step_out_s_t* camp,
+               void* out, uint64_t cap, uint64_t* frame_off, uint64_t* peer_off, raftq_wire_counts_t* counts) {
+  const char* who = elect ? "raftq_tick_elect_frames" : "raftq_tick_frames";
+  const char *const caps = elect ? "beat_cap + hup_cap" : "beat_cap", *const product = elect ? "(beat_cap + hup_cap)" : "beat_cap";  // (in the refusals' texts)
   if (int rc = raftq_detail::use_device_idle(h, who)) return rc;
   if (counts) *counts = raftq_wire_counts_t{0, 0, 0, 0};
-  // (raftq_tick_set_checks opens the call: the beat bitmap beat_build_kernel ranks never held a group whose check failed)
+  // (raftq_tick_set_checks opens the call: the beat bitmap beat_build_kernel ranks never held a group whose check failed, and under
+  // both switches the election round is elect_build_cq_kernel's, Step's own MsgHup arm)
+  if (elect)
+    if (int rc = raftq_detail::refuse_pre_vote(h, who, true)) return rc;
   if (int rc = raftq_detail::refuse_check_quorum(h, who, true)) return rc;
   if (int rc = raftq_detail::refuse_read_index(h, who)) return rc;
   if (!n_hup || !n_beat || !peer_off) return fail(h, RAFTQ_EINVAL, std::string(who) + ": null argument");
   if (flags & ~RAFTQ_TICK_BEAT_BITMAP) return fail(h, RAFTQ_EINVAL, std::string(who) + ": unknown flag");
-  if (h->N < 2) return fail(h, RAFTQ_EINVAL, std::string(who) + ": a single-peer group has nobody to send a heartbeat to -- use raftq_tick_collect_lists");
-  // the exact worst case: beat_cap groups, N - 1 frames of RAFTQ_RESPOND_FRAME_MAX bytes each -- refused before anything runs, so a
-  // call that has ticked never fails for output space
-  const uint64_t slices = h->N - 1;
-  if (beat_cap >= ((uint64_t)1 << 31) || beat_cap * slices > kMaxItems || beat_cap * slices > (((uint64_t)1 << 31) / RAFTQ_RESPOND_FRAME_MAX))
-    return fail(h, RAFTQ_EINVAL, std::string(who) + ": beat_cap too large (beat_cap * (N - 1) * RAFTQ_RESPOND_FRAME_MAX must stay within 2^31 bytes)");
-  const uint64_t n_max = beat_cap * slices;
-  if (cap < n_max * RAFTQ_RESPOND_FRAME_MAX)
-    return fail(h, RAFTQ_EINVAL, std::string(who) + ": cap is below beat_cap * (N - 1) * RAFTQ_RESPOND_FRAME_MAX = " +
-                                     std::to_string(n_max * RAFTQ_RESPOND_FRAME_MAX) + " bytes -- the call has not ticked");
-  if (n_max != 0 && !out) return fail(h, RAFTQ_EINVAL, std::string(who) + ": null argument");
-  if (!h->node_rec && !h->self_set)
-    return fail(h, RAFTQ_ESTATE, std::string(who) + ": the handle holds no node state (raftq_set_self / raftq_load_node first)");
-  if (int rc = ensure_pin(h)) return rc;
-  Views v;
-  void *v_out = v.opt(out), *v_off = v.opt(frame_off);
-  v.add(peer_off);
-  if (!v.ok)
-    return fail(h, RAFTQ_EINVAL, std::string(who) + ": out, frame_off and peer_off must be page-locked (raftq_host_alloc, hipHostMalloc, hipHostRegister) "
-                                                    "and 16-byte aligned -- the call has not ticked");
-  // every allocation before the tick kernel: the records (and, where something other than Step wrote the dense arrays, their
-  // refresh), the Tick's lists, the encoder's control block, scratch and output buffer
-  NodeArrays na;
-  if (int rc = raftq_detail::node_records_of(h, who, &na, true)) return rc;
-  const bool members = raftq_detail::masked_tick(h);  // the round goes to each group's own members (beat_build_voters_kernel)
-  raftq_detail::TickLists tl;
-  if (int rc = raftq_detail::tick_lists_prepare(h, who, flags, hup_cap, beat_cap, &tl)) return rc;
-  const uint64_t enc_cap = n_max * RAFTQ_RESPOND_FRAME_MAX;  // what the encoder may write: never more than the worst case
-  StreamCall sc = beat_marshal_call(n_max, enc_cap);
-  if (n_max != 0)
-    if (int rc = stream_prepare(h, sc)) return rc;  // (the launch's epoch and feed: nothing of it runs before the encoder below)
-  // Tick -> lists -> beat_build -> encoder -> flag, back to back; one wait
-  if (int rc = raftq_detail::tick_lists_enqueue(h, &tl)) return rc;
-  if (n_max != 0) {
-    if (members)
-      if (int rc = members_begin(h)) return rc;
-    beat_enqueue(h, na, tl, members, beat_cap, (WireMsg*)sc.in.seg[0].dst);
-    HIPCHK(h, hipGetLastError());
-    if (int rc = stream_launch(h, sc, wire_enc_fused_kernel, kBlock, sc.in, n_max, (uint64_t)0, (uint64_t)0, (uint8_t*)h->wire_out.d, (uint8_t*)v_out, enc_cap,
-                               (uint64_t*)v_off, sc.ctl, h->wire_pin_d + kPinCall, (const unsigned int*)nullptr, 0u))
-      return rc;
-    if (members)
-      if (int rc = members_end(h)) return rc;
-  }
-  if (int rc = raftq_detail::tick_lists_finish(h, who, tl, n_hup, n_beat)) return rc;
-  const uint64_t n_built = std::min(*n_beat, beat_cap);
-  // the frames that have bytes: every slot of the section, or -- over members -- what the build kernel counted
-  const uint64_t frames = !members ? n_built * slices : n_max != 0 ? h->wire_pin[kPinCall + kPinMembers] : 0;
-  uint64_t at = 0;
-  for (uint32_t p = 0; p <= h->N; ++p) {
-    peer_off[p] = at;
-    if (p < h->N && p != h->self_peer) at += n_built;
-  }
-  uint64_t bytes = 0;
-  if (n_max != 0) {
-    if (int rc = tile_ctl_check(h, who, kPinCall)) return rc;
-    bytes = h->wire_pin[kPinCall + kPinTotal];
-    // every record past the last frame is a filler the encoder refuses, and so is -- over members -- every slot of a peer that is
-    // no member of its group; any other refusal, or bytes beyond the bound, is a bug here
-    if (h->wire_pin[kPinCall + kPinRefused] != n_max - frames || bytes > enc_cap)
-      return fail(h, RAFTQ_EHIP, std::string(who) + ": the marshal of the heartbeats disagrees with their layout; the output is not valid");
-  } else if (frame_off) {
-    frame_off[0] = 0;
-  }
-  if (counts) *counts = raftq_wire_counts_t{frames, 0, 0, bytes};
-  return RAFTQ_OK;
-}
-
-// ---- raftq_tick_elect_frames ------------------------------------------------------------------------------------------
-// raftq_tick_frames with the election round behind the heartbeat round: Tick -> lists -> beat_build -> elect_build -> encoder ->
-// flag.  The encoder's input holds (beat_cap + hup_cap) * (N - 1) records: beat_build_kernel runs as in raftq_tick_frames over the
-// first beat_cap * (N - 1) (its fillers start where the heartbeats end), elect_build_kernel, behind it in stream order, puts the
-// votes directly behind the heartbeats and the fillers behind both.
-extern "C" int raftq_tick_elect_frames(raftq_t* h, unsigned flags, uint64_t hup_cap, uint64_t beat_cap, uint64_t* n_hup, uint64_t* n_beat,
-                                       raftq_step_out_s_t* camp, void* out, uint64_t cap, uint64_t* frame_off, uint64_t* peer_off,
-                                       raftq_wire_counts_t* counts) {
-  const char* who = "raftq_tick_elect_frames";
-  if (int rc = raftq_detail::use_device_idle(h, who)) return rc;
-  if (counts) *counts = raftq_wire_counts_t{0, 0, 0, 0};
-  // (raftq_tick_set_checks opens the call under both switches: the round is then elect_build_cq_kernel's, Step's own MsgHup arm)
-  if (int rc = raftq_detail::refuse_pre_vote(h, who, true)) return rc;
-  if (int rc = raftq_detail::refuse_check_quorum(h, who, true)) return rc;
-  if (int rc = raftq_detail::refuse_read_index(h, who)) return rc;
-  if (!n_hup || !n_beat || !peer_off) return fail(h, RAFTQ_EINVAL, std::string(who) + ": null argument");
-  if (flags & ~RAFTQ_TICK_BEAT_BITMAP) return fail(h, RAFTQ_EINVAL, std::string(who) + ": unknown flag");
-  if (h->N < 2) return fail(h, RAFTQ_EINVAL, std::string(who) + ": a single-peer group has nobody to ask for a vote -- use raftq_tick_collect_lists");
-  // the exact worst case: beat_cap + hup_cap groups, N - 1 frames of RAFTQ_RESPOND_FRAME_MAX bytes each -- refused before anything
+  if (h->N < 2)
+    return fail(h, RAFTQ_EINVAL, std::string(who) + ": a single-peer group has nobody to " + (elect ? "ask for a vote" : "send a heartbeat to") +
+                                     " -- use raftq_tick_collect_lists");
+  // the exact worst case: beat_cap + vote_cap groups, N - 1 frames of RAFTQ_RESPOND_FRAME_MAX bytes each -- refused before anything
   // runs, so a call that has ticked never fails for output space
+  const uint64_t vote_cap = elect ? hup_cap : 0;  // the groups the election round is built for
   const uint64_t slices = h->N - 1;
   const uint64_t frames_cap = ((uint64_t)1 << 31) / RAFTQ_RESPOND_FRAME_MAX;
-  if (beat_cap >= ((uint64_t)1 << 31) || hup_cap >= ((uint64_t)1 << 31) || (beat_cap + hup_cap) * slices > kMaxItems || (beat_cap + hup_cap) * slices > frames_cap)
-    return fail(h, RAFTQ_EINVAL, std::string(who) + ": beat_cap + hup_cap too large ((beat_cap + hup_cap) * (N - 1) * RAFTQ_RESPOND_FRAME_MAX must stay within 2^31 bytes)");
-  const uint64_t n_max = (beat_cap + hup_cap) * slices;
+  if (beat_cap >= ((uint64_t)1 << 31) || vote_cap >= ((uint64_t)1 << 31) || (beat_cap + vote_cap) * slices > kMaxItems || (beat_cap + vote_cap) * slices > frames_cap)
+    return fail(h, RAFTQ_EINVAL, std::string(who) + ": " + caps + " too large (" + product + " * (N - 1) * RAFTQ_RESPOND_FRAME_MAX must stay within 2^31 bytes)");
+  const uint64_t n_max = (beat_cap + vote_cap) * slices;
   if (cap < n_max * RAFTQ_RESPOND_FRAME_MAX)
-    return fail(h, RAFTQ_EINVAL, std::string(who) + ": cap is below (beat_cap + hup_cap) * (N - 1) * RAFTQ_RESPOND_FRAME_MAX = " +
+    return fail(h, RAFTQ_EINVAL, std::string(who) + ": cap is below " + product + " * (N - 1) * RAFTQ_RESPOND_FRAME_MAX = " +
                                      std::to_string(n_max * RAFTQ_RESPOND_FRAME_MAX) + " bytes -- the call has not ticked");
-  if ((n_max != 0 && !out) || (hup_cap != 0 && !camp)) return fail(h, RAFTQ_EINVAL, std::string(who) + ": null argument");
+  if ((n_max != 0 && !out) || (vote_cap != 0 && !camp)) return fail(h, RAFTQ_EINVAL, std::string(who) + ": null argument");
   if (!h->node_rec && !h->self_set)
     return fail(h, RAFTQ_ESTATE, std::string(who) + ": the handle holds no node state (raftq_set_self / raftq_load_node first)");
   if (int rc = ensure_pin(h)) return rc;
   Views v;
-  void *v_out = v.opt(out), *v_off = v.opt(frame_off), *v_camp = v.add(camp, hup_cap != 0);
+  void *v_out = v.opt(out), *v_off = v.opt(frame_off), *v_camp = v.add(camp, vote_cap != 0);
   v.add(peer_off);
   if (!v.ok)
-    return fail(h, RAFTQ_EINVAL, std::string(who) + ": camp, out, frame_off and peer_off must be page-locked (raftq_host_alloc, hipHostMalloc, "
-                                                    "hipHostRegister) and 16-byte aligned -- the call has neither ticked nor campaigned");
+    return fail(h, RAFTQ_EINVAL,
+                std::string(who) + (elect ? ": camp, out, frame_off and peer_off must be page-locked (raftq_host_alloc, hipHostMalloc, "
+                                            "hipHostRegister) and 16-byte aligned -- the call has neither ticked nor campaigned"
+                                          : ": out, frame_off and peer_off must be page-locked (raftq_host_alloc, hipHostMalloc, hipHostRegister) "
+                                            "and 16-byte aligned -- the call has not ticked"));
   // every allocation before the tick kernel: the records (and, where something other than Step wrote the dense arrays, their
   // refresh), the Tick's lists, the encoder's control block, scratch and output buffer
   NodeArrays na;
   if (int rc = raftq_detail::node_records_of(h, who, &na, true)) return rc;
-  const bool members = raftq_detail::masked_tick(h);  // both rounds go to each group's own members (the *_voters_kernel entry points)
+  const bool members = raftq_detail::masked_tick(h);  // the rounds go to each group's own members (the *_voters_kernel entry points)
   raftq_detail::TickLists tl;
   if (int rc = raftq_detail::tick_lists_prepare(h, who, flags, hup_cap, beat_cap, &tl)) return rc;
   const uint64_t enc_cap = n_max * RAFTQ_RESPOND_FRAME_MAX;  // what the encoder may write: never more than the worst case
   StreamCall sc = beat_marshal_call(n_max, enc_cap);
   if (n_max != 0)
     if (int rc = stream_prepare(h, sc)) return rc;  // (the launch's epoch and feed: nothing of it runs before the encoder below)
-  if (hup_cap != 0) h->last_flags &= ~RAFTQ_SWEEP_NO_ADOPT;  // as in raftq_step_submit: the live state moves
-  // Tick -> lists -> beat_build -> elect_build -> encoder -> flag, back to back; one wait
+  if (vote_cap != 0) h->last_flags &= ~RAFTQ_SWEEP_NO_ADOPT;  // as in raftq_step_submit: the live state moves
   if (int rc = raftq_detail::tick_lists_enqueue(h, &tl)) return rc;
   if (n_max != 0) {
     const uint64_t nw = h->gpad / 256;
@@ -1036,10 +955,14 @@ extern "C" int raftq_tick_elect_frames(raftq_t* h, unsigned flags, uint64_t hup_
     WireMsg* const enc = (WireMsg*)sc.in.seg[0].dst;
     if (members)
       if (int rc = members_begin(h)) return rc;
-    if (beat_cap != 0) beat_enqueue(h, na, tl, members, beat_cap, enc);
-    // (hup_cap == 0: the fillers behind beat_cap * (N - 1) are beat_build_kernel's own -- the call is raftq_tick_frames)
-    if (hup_cap != 0) {
-      ElectArgs ea{(const uint64_t*)h->hup_bits, (const uint4*)h->tick_partials, nw, tl.off_h, (const uint64_t*)h->d_total, na, hup_cap, beat_cap,
+    if (beat_cap != 0) {  // the heartbeat round, over each group's own members where the Tick is
+      BeatArgs ba{(const uint64_t*)h->beat_bits, (const uint4*)h->tick_partials, nw, tl.off_beat, (const uint64_t*)h->d_total, na.rec, h->G, h->N,
+                  h->self_peer, beat_cap, enc};
+      if (members) hipLaunchKernelGGL(beat_build_voters_kernel, grid, dim3(kBlock), 0, h->stream, ba, (const uint16_t*)h->voters, members_word(h));
+      else hipLaunchKernelGGL(beat_build_kernel, grid, dim3(kBlock), 0, h->stream, ba);
+    }
+    if (vote_cap != 0) {  // (without it the fillers behind beat_cap * (N - 1) are beat_build_kernel's own)
+      ElectArgs ea{(const uint64_t*)h->hup_bits, (const uint4*)h->tick_partials, nw, tl.off_h, (const uint64_t*)h->d_total, na, vote_cap, beat_cap,
                    (StepOutS*)v_camp, enc};
       if (raftq_detail::tick_checks(h)) {  // Node's CQ form: na carries cq, election_tick and pv (node_records_of)
         if (members) hipLaunchKernelGGL(elect_build_cq_voters_kernel, grid, dim3(kBlock), 0, h->stream, ea, (const uint16_t*)h->voters, members_word(h));
@@ -1055,31 +978,40 @@ extern "C" int raftq_tick_elect_frames(raftq_t* h, unsigned flags, uint64_t hup_
       if (int rc = members_end(h)) return rc;
   }
   if (int rc = raftq_detail::tick_lists_finish(h, who, tl, n_hup, n_beat)) return rc;
-  const uint64_t n_bb = std::min(*n_beat, beat_cap), n_vb = std::min(*n_hup, hup_cap);
+  const uint64_t n_bb = std::min(*n_beat, beat_cap), n_vb = std::min(*n_hup, vote_cap);
   // the frames that have bytes: every slot of both sections, or -- over members -- what the build kernels counted
   const uint64_t frames = !members ? (n_bb + n_vb) * slices : n_max != 0 ? h->wire_pin[kPinCall + kPinMembers] : 0;
   uint64_t at = 0;
-  for (uint32_t p = 0; p <= h->N; ++p) {  // the heartbeat section's slices, then the vote section's
-    peer_off[p] = at;
-    if (p < h->N && p != h->self_peer) at += n_bb;
-  }
-  for (uint32_t p = 0; p <= h->N; ++p) {
-    peer_off[h->N + 1 + p] = at;
-    if (p < h->N && p != h->self_peer) at += n_vb;
-  }
+  for (int sec = 0; sec < (elect ? 2 : 1); ++sec)  // the heartbeat section's slices, then the vote section's
+    for (uint32_t p = 0; p <= h->N; ++p) {
+      peer_off[sec * (h->N + 1) + p] = at;
+      if (p < h->N && p != h->self_peer) at += sec ? n_vb : n_bb;
+    }
   uint64_t bytes = 0;
   if (n_max != 0) {
     if (int rc = tile_ctl_check(h, who, kPinCall)) return rc;
     bytes = h->wire_pin[kPinCall + kPinTotal];
     // every record past the last frame is a filler the encoder refuses, and so is -- over members -- every slot of a peer that is
-    // not asked; any other refusal, or bytes beyond the bound, is a bug here
+    // no member of its group or is not asked; any other refusal, or bytes beyond the bound, is a bug here
     if (h->wire_pin[kPinCall + kPinRefused] != n_max - frames || bytes > enc_cap)
-      return fail(h, RAFTQ_EHIP, std::string(who) + ": the marshal of the heartbeats and votes disagrees with their layout; the output is not valid");
+      return fail(h, RAFTQ_EHIP, std::string(who) + ": the marshal of the heartbeats" + (elect ? " and votes" : "") +
+                                     " disagrees with their layout; the output is not valid");
   } else if (frame_off) {
     frame_off[0] = 0;
   }
   if (counts) *counts = raftq_wire_counts_t{frames, 0, 0, bytes};
   return RAFTQ_OK;
+}
+}  // namespace
+
+extern "C" int raftq_tick_frames(raftq_t* h, unsigned flags, uint64_t hup_cap, uint64_t beat_cap, uint64_t* n_hup, uint64_t* n_beat, void* out,
+                                 uint64_t cap, uint64_t* frame_off, uint64_t* peer_off, raftq_wire_counts_t* counts) {
+  return tick_round(h, false, flags, hup_cap, beat_cap, n_hup, n_beat, nullptr, out, cap, frame_off, peer_off, counts);
+}
+extern "C" int raftq_tick_elect_frames(raftq_t* h, unsigned flags, uint64_t hup_cap, uint64_t beat_cap, uint64_t* n_hup, uint64_t* n_beat,
+                                       raftq_step_out_s_t* camp, void* out, uint64_t cap, uint64_t* frame_off, uint64_t* peer_off,
+                                       raftq_wire_counts_t* counts) {
+  return tick_round(h, true, flags, hup_cap, beat_cap, n_hup, n_beat, camp, out, cap, frame_off, peer_off, counts);
 }
 
 // ---- walpb.Record WAL frames --------------------------------------------------------------------------------------------------

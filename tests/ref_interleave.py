@@ -1,6 +1,6 @@
 """Every writer of a handle interleaved with Step, with the Step switches on: the schedules and the reference composed of what the
 suite already trusts.  A group's Step record holds copies of role, committed, the term gate and the match words (raftq_step_kernels.hpp
-NodeRec); every writer that is not Step marks them stale (raftq_capi.hip dense_changed) and Step writes back what it changed
+NodeRec); every writer that is not Step marks them stale (raftq_internal.hpp dense_changed) and Step writes back what it changed
 (NodeT::store).  A schedule is a seeded sequence of MOVES -- one call of one writer -- each followed by one Step batch that reads
 what the move changed, on ONE handle from the first move to the last.
 
