@@ -47,6 +47,25 @@ func (e *Engine) Narrow() (bool, error) {
 // NarrowRebuild runs the mirror's build pass on demand.
 func (e *Engine) NarrowRebuild() error { return e.err(C.raftq_narrow_rebuild(e.h)) }
 
+// Tally reports whether the device holds a valid tally byte (granted | rejected << 4) for every group's vote word; a sweep
+// with votes then reads the byte instead of the word.
+func (e *Engine) Tally() (bool, error) {
+	var valid C.int32_t
+	if err := e.err(C.raftq_tally(e.h, &valid)); err != nil {
+		return false, err
+	}
+	return valid != 0, nil
+}
+
+// TallyRebuild runs the tally mirror's build pass on demand and reports whether it holds afterwards.
+func (e *Engine) TallyRebuild() (bool, error) {
+	var valid C.int32_t
+	if err := e.err(C.raftq_tally_rebuild(e.h, &valid)); err != nil {
+		return false, err
+	}
+	return valid != 0, nil
+}
+
 // SetStream installs a caller-owned hipStream_t; Stream returns the one in use.
 func (e *Engine) SetStream(stream unsafe.Pointer) error { return e.err(C.raftq_set_stream(e.h, stream)) }
 func (e *Engine) Stream() unsafe.Pointer                { return C.raftq_get_stream(e.h) }

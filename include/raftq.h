@@ -247,6 +247,16 @@ int raftq_self_max(raftq_t* h, int32_t* slot_out);
  * word stays 0 where a group's values spread over 2^32 or more, no memory can be had, or the handle was created without). */
 int raftq_narrow(raftq_t* h, int32_t* valid_out);
 int raftq_narrow_rebuild(raftq_t* h);
+/* The tally mirror: one byte per group, tally[g] == granted | rejected << 4, the two counts poll() takes over the group's vote
+ * word.  While the device knows that to hold, a sweep with RAFTQ_SWEEP_VOTES reads the byte (1 B a group) instead of the word
+ * (2 B, 4 B at 9 peers) and compares the counts with the quorum itself.  Valid from raftq_create; raftq_load_votes rebuilds it,
+ * the batching turn's vote ingest and raftq_campaign keep it true; Step and a voter delta that resets a slot end it until the
+ * next build.  Costs 1 byte a group; RAFTQ_TALLY=0 in the environment at raftq_create keeps a handle from ever having one.
+ * Sweeps of a handle with voter masks read the words either way.  Results never depend on it.
+ * raftq_tally: *valid_out = 1 while the mirror holds, 0 otherwise.  raftq_tally_rebuild: the build pass on demand, then the
+ * same answer in *valid_out (may be NULL; 0 where the handle was created without, or Step batches are in flight). */
+int raftq_tally(raftq_t* h, int32_t* valid_out);
+int raftq_tally_rebuild(raftq_t* h, int32_t* valid_out);
 int raftq_read_votes(raftq_t* h, uint8_t* votes_out /*[N][G]*/);
 /* compacted list of the groups the last RAFTQ_SWEEP_CHANGED sweep advanced,
  * in ascending group order; returns the count in *n (<= cap entries stored). */

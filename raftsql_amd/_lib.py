@@ -90,6 +90,8 @@ _SIGS = [
     ("raftq_self_max", C.c_int, [_H, C.POINTER(C.c_int32)]),
     ("raftq_narrow", C.c_int, [_H, C.POINTER(C.c_int32)]),
     ("raftq_narrow_rebuild", C.c_int, [_H]),
+    ("raftq_tally", C.c_int, [_H, C.POINTER(C.c_int32)]),
+    ("raftq_tally_rebuild", C.c_int, [_H, C.POINTER(C.c_int32)]),
     ("raftq_read_votes", C.c_int, [_H, C.c_void_p]),
     ("raftq_collect_changed", C.c_int, [_H, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("raftq_set_timers", C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint64]),

@@ -292,6 +292,23 @@ int raftq_detail::narrow_build(raftq_t* h) {
   HIPCHK(h, hipGetLastError());
   return RAFTQ_OK;
 }
+// The tally word's full build (raftq_kernels.hpp): kTallyValid is stored, then a pass over the vote words writes the bytes.  On
+// the handle's stream, behind whatever wrote the words; with Step batches in flight only the clear, as above.  A handle created
+// under RAFTQ_TALLY=0 has no bytes: its word stays 0 and its sweeps read the words.
+int raftq_detail::tally_build(raftq_t* h) {
+  if (int rc = use_device(h)) return rc;
+  if (!h->tally) return RAFTQ_OK;
+  if (h->step_collected != h->step_submitted) {
+    HIPCHK(h, hipMemsetAsync(h->tally_word(), 0, sizeof(uint32_t), h->stream));
+    return RAFTQ_OK;
+  }
+  HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)h->tally_word(), (int)kTallyValid, 1, h->stream));
+  const uint64_t blocks = std::min<uint64_t>((h->G + kBlock - 1) / kBlock, 4096);
+  hipLaunchKernelGGL(tally_build_kernel, dim3((unsigned)std::max<uint64_t>(blocks, 1)), dim3(kBlock), 0, h->stream,
+                     (const uint8_t*)h->votes, h->G, h->N, h->tally);
+  HIPCHK(h, hipGetLastError());
+  return RAFTQ_OK;
+}
 int raftq_detail::use_device(raftq_t* h) {
   if (!h) return fail(nullptr, RAFTQ_EINVAL, "null handle");
   HIPCHK(h, hipSetDevice(h->device));
@@ -420,6 +437,18 @@ int raftq_create(int device, uint64_t n_groups, uint32_t n_peers, raftq_t** out)
     // (the narrow word, self_max[1], stays 0: there is no mirror yet)
     e = hipMemsetD32Async((hipDeviceptr_t)h->self_max, (int)(kSelfMaxValid | 0u), 1, h->stream);
     if (e != hipSuccess) { rc = fail(h, RAFTQ_EHIP, std::string("hipMemsetD32Async: ") + hipGetErrorString(e)); break; }
+    {  // the tally mirror: zeroed bytes are the tally of the zeroed vote words, so the word, self_max[2], starts valid
+      const char* tl = std::getenv("RAFTQ_TALLY");
+      if (!(tl && std::strcmp(tl, "0") == 0)) {
+        e = raftq_buf::alloc_group({{(void**)&h->tally, (size_t)ld}}, h->stream);
+        if (e != hipSuccess) {
+          rc = fail(h, e == hipErrorOutOfMemory ? RAFTQ_ENOMEM : RAFTQ_EHIP, std::string("device arrays: ") + hipGetErrorString(e));
+          break;
+        }
+        e = hipMemsetD32Async((hipDeviceptr_t)h->tally_word(), (int)kTallyValid, 1, h->stream);
+        if (e != hipSuccess) { rc = fail(h, RAFTQ_EHIP, std::string("hipMemsetD32Async: ") + hipGetErrorString(e)); break; }
+      }
+    }
     e = raftq_buf::alloc_group({{(void**)&h->h_partials, h->max_partials * sizeof(uint4), raftq_buf::Kind::pinned},
                                 {(void**)&h->h_total, 64, raftq_buf::Kind::mapped_coherent, (void**)&h->d_total}},
                                h->stream);
@@ -465,7 +494,7 @@ void raftq_destroy(raftq_t* h) {
   raftq_detail::free_wire_state(h);
   // every wait is over: memory may go
   raftq_buf::free_device(h->match, h->committed[0], h->committed[1], h->first_idx, h->votes, h->voters, h->outcome, h->changed_bits,
-                         h->partials, h->offsets, h->self_max, h->anchor, h->moff, h->claim, h->delta_bad, h->role, h->elapsed, h->action, h->hup_bits,
+                         h->partials, h->offsets, h->self_max, h->anchor, h->moff, h->tally, h->claim, h->delta_bad, h->role, h->elapsed, h->action, h->hup_bits,
                          h->beat_bits, h->tick_partials, h->tick_offsets2, h->tick_offsets3, h->cq, h->chk_bits, h->reads);
   raftq_buf::free_host(h->h_partials, h->h_total);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -545,6 +574,7 @@ int raftq_load_votes(raftq_t* h, const uint8_t* votes) {
   if (wb == 2) pack_votes(votes, h->G, h->N, reinterpret_cast<uint16_t*>(packed.data()));
   else pack_votes(votes, h->G, h->N, reinterpret_cast<uint32_t*>(packed.data()));
   HIPCHK(h, hipMemcpyAsync(h->votes, packed.data(), packed.size(), hipMemcpyHostToDevice, h->stream));
+  if (int rc = raftq_detail::tally_build(h)) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return RAFTQ_OK;
 }
@@ -638,7 +668,7 @@ static int enqueue_ingest(raftq_t* h, const AbiRec* d, uint64_t n, const raftq_v
     hipLaunchKernelGGL(vote_claim_kernel, gv, dim3(kBlock), 0, h->stream, h->claim, h->ld, (const VoteDeltaRec*)dev_v, nv, bad,
                        em_gate, ev, h->G, h->N, trusted ? 1 : 0);
     hipLaunchKernelGGL(vote_apply_kernel, gv, dim3(kBlock), 0, h->stream, h->votes, h->N > 8 ? 1 : 0, h->claim, h->ld,
-                       (const VoteDeltaRec*)dev_v, nv, bad, em_gate, ev, h->G, h->N, trusted ? 1 : 0);
+                       (const VoteDeltaRec*)dev_v, nv, bad, em_gate, ev, h->G, h->N, trusted ? 1 : 0, h->tally_mirror());
   }
   HIPCHK(h, hipGetLastError());
   return RAFTQ_OK;
@@ -797,7 +827,8 @@ int raftq_apply_voter_deltas(raftq_t* h, const raftq_voter_delta_t* d, uint64_t 
   }
   dense_changed(h);  // (match words are zeroed under Step's records)
   hipLaunchKernelGGL(apply_voter_deltas_kernel, dim3((unsigned)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, h->voters, h->match,
-                     h->ld, h->votes, h->N > 8 ? 1 : 0, h->N, (const VoterDeltaRec*)h->stage.d, m, h->self_max, h->narrow_word());
+                     h->ld, h->votes, h->N > 8 ? 1 : 0, h->N, (const VoterDeltaRec*)h->stage.d, m, h->self_max, h->narrow_word(),
+                     h->tally_word());
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipStreamSynchronize(h->stream));  // the staging area is reused by the next call
   return RAFTQ_OK;
@@ -839,6 +870,8 @@ static SweepArgs sweep_args(const raftq_t* h, int cur, bool want_bits) {
   a.narrow = h->anchor ? h->narrow_word() : nullptr;
   a.anchor = h->anchor;
   a.moff = h->moff;
+  a.tally_word = h->tally ? h->tally_word() : nullptr;
+  a.tally = h->tally;
   return a;
 }
 
@@ -1006,6 +1039,24 @@ int raftq_narrow(raftq_t* h, int32_t* valid) {
 int raftq_narrow_rebuild(raftq_t* h) {
   if (int rc = use_device_idle(h, "raftq_narrow_rebuild")) return rc;
   if (int rc = raftq_detail::narrow_build(h)) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return RAFTQ_OK;
+}
+
+int raftq_tally(raftq_t* h, int32_t* valid) {
+  if (int rc = use_device_idle(h, "raftq_tally")) return rc;
+  if (!valid) return fail(h, RAFTQ_EINVAL, "raftq_tally: null argument");
+  uint32_t w = 0;
+  HIPCHK(h, hipMemcpyAsync(&w, h->tally_word(), sizeof w, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  *valid = w == kTallyValid ? 1 : 0;
+  return RAFTQ_OK;
+}
+
+int raftq_tally_rebuild(raftq_t* h, int32_t* valid) {
+  if (int rc = use_device_idle(h, "raftq_tally_rebuild")) return rc;
+  if (int rc = raftq_detail::tally_build(h)) return rc;
+  if (valid) return raftq_tally(h, valid);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return RAFTQ_OK;
 }
@@ -1792,7 +1843,7 @@ int raftq_campaign(raftq_t* h, const uint64_t* groups, uint64_t n, uint32_t self
   if (int rc = ensure_staging(h, (size_t)n * 8)) return rc;
   std::memcpy(h->stage.h, groups, n * 8);
   hipLaunchKernelGGL(campaign_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream,
-                     h->role, h->elapsed, h->votes, h->N, self_peer, (const uint64_t*)h->stage.d, n);
+                     h->role, h->elapsed, h->votes, h->N, self_peer, (const uint64_t*)h->stage.d, n, h->tally);
   dense_changed(h);  // (role)
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2581,6 +2632,13 @@ int raftq_clone_state(raftq_t* dst, raftq_t* src) {
     HIPCHK(dst, hipMemcpyAsync(dst->narrow_word(), src->narrow_word(), sizeof(uint32_t), hipMemcpyDeviceToDevice, dst->stream));
   } else {
     HIPCHK(dst, hipMemsetAsync(dst->narrow_word(), 0, sizeof(uint32_t), dst->stream));
+  }
+  // the vote words are the source's, so are their tally bytes and what is known about them -- where both handles have the mirror
+  if (src->tally && dst->tally) {
+    HIPCHK(dst, hipMemcpyAsync(dst->tally, src->tally, ld, hipMemcpyDeviceToDevice, dst->stream));
+    HIPCHK(dst, hipMemcpyAsync(dst->tally_word(), src->tally_word(), sizeof(uint32_t), hipMemcpyDeviceToDevice, dst->stream));
+  } else {
+    HIPCHK(dst, hipMemsetAsync(dst->tally_word(), 0, sizeof(uint32_t), dst->stream));
   }
   if (src->voters) HIPCHK(dst, hipMemcpyAsync(dst->voters, src->voters, ld * sizeof(uint16_t), hipMemcpyDeviceToDevice, dst->stream));
   // the activity words where both handles hold them (raftq_set_check_quorum is each handle's own)

@@ -72,6 +72,11 @@ struct raftq {
   bool narrow_off = false;       // RAFTQ_NARROW=0 at raftq_create: never build the mirror
   uint32_t* narrow_word() const { return self_max + 1; }
   raftqk::NarrowMirror narrow_mirror() const { return raftqk::NarrowMirror{self_max + 1, anchor, moff}; }
+  // The tally mirror (raftq_kernels.hpp kTallyValid): its word is self_max[2]; the bytes are allocated, zeroed, by raftq_create
+  // with the word valid (all-zero vote words have an all-zero tally) -- or never, under RAFTQ_TALLY=0, and the word stays 0.
+  uint8_t* tally = nullptr;      // device u8 [ld]: granted | rejected << 4 of votes[g]
+  uint32_t* tally_word() const { return self_max + 2; }
+  raftqk::TallyMirror tally_mirror() const { return raftqk::TallyMirror{self_max + 2, tally}; }
   uint64_t compact_epoch = 0;  // completion-flag values handed to hipStreamWriteValue64 (h_total[3])
   uint64_t compact_epoch_armed = 0;  // epoch the current turn's wait may poll for (0 = blocking wait)
   // wait_turn: consecutive waits whose flag did not land in time and waits sat out since -- per KIND of wait ([0] the batching
@@ -343,6 +348,7 @@ int refuse_read_index(raftq_t* h, const char* who);
 inline bool tick_checks(const raftq_t* h) { return h->cq != nullptr && h->tick_chk_cap != 0; }
 int self_max_check(raftq_t* h);                 // the self-max word re-derived from the rows for h->self_peer (enqueued)
 int narrow_build(raftq_t* h);                   // the narrow mirror and its word re-derived from the rows (enqueued)
+int tally_build(raftq_t* h);                    // the tally bytes and their word re-derived from the vote words (enqueued)
 int ensure_staging(raftq_t* h, size_t bytes);   // pinned, device-mapped staging (term deltas, campaign lists, log deltas)
 int ensure_ingest(raftq_t* h, size_t bytes);    // the ack buffer of the batching turn: device memory behind a large BAR, else pinned
 int ensure_tick_state(raftq_t* h);              // role / elapsed / action (+ hup bitmap)

@@ -56,6 +56,9 @@ struct SweepArgs {
   const uint32_t* narrow = nullptr;
   const uint64_t* anchor = nullptr;
   const uint32_t* moff = nullptr;
+  // the handle's tally word and the bytes it vouches for (below): tally u8 [ld]; nullptr = no mirror
+  const uint32_t* tally_word = nullptr;
+  const uint8_t* tally = nullptr;
 };
 
 // The self-max word of a handle (one device u32): kSelfMaxValid | slot when row `slot` of match is known to be the
@@ -74,6 +77,15 @@ constexpr uint32_t kSelfMaxValid = 0x80000000u;
 // is the self-max word's: set only by a full build pass (narrow_build_kernel); cleared by every writer of match that
 // may break it -- the ingest kernels keep the mirror true instead while they can.  A clear costs speed, never correctness.
 constexpr uint32_t kNarrowValid = 1u;
+
+// The tally word of a handle (one device u32, the word behind the narrow word): kTallyValid when for every group g
+// tally[g] == granted | rejected << 4, the two counts poll_word takes over the N fields of votes[g] (a field of 11 counts as
+// neither), else 0.  The vote word changes only when a vote is ingested or an election starts, and the sweep reads it only to
+// count: while the word holds, a sweep with votes reads the byte (1 B a group instead of 2, or 4 at N = 9) and compares the
+// two nibbles with the quorum itself.  The rule is the narrow word's: set only by a full build pass (tally_build_kernel) --
+// and by raftq_create, whose all-zero words have an all-zero tally; cleared by every writer of votes that does not keep the
+// bytes true.  A clear costs speed, never correctness.
+constexpr uint32_t kTallyValid = 1u;
 
 // ---------------------------------------------------------------------------
 // uint64 compare-exchange, descending: a <- max, b <- min.  gfx950 has no
@@ -202,6 +214,19 @@ __device__ __forceinline__ uint32_t poll_word(uint32_t w) {
   return won | lost;
 }
 
+// The same two counts as a tally byte (granted | rejected << 4), and poll's outcome from one.
+__device__ __forceinline__ uint32_t tally_of_word(uint32_t w, uint32_t n_peers) {
+  const uint32_t low = 0x55555555u & (n_peers >= 16 ? 0xffffffffu : ((1u << (2 * n_peers)) - 1u));
+  return __popc(w & ~(w >> 1) & low) | (__popc((w >> 1) & ~w & low) << 4);
+}
+template <int N>
+__device__ __forceinline__ uint32_t poll_tally(uint32_t b) {
+  constexpr uint32_t q = N / 2 + 1;
+  const uint32_t won = (b & 15u) >= q ? 1u : 0u;
+  const uint32_t lost = (won == 0u && (b >> 4) >= q) ? 2u : 0u;
+  return won | lost;
+}
+
 template <typename T>
 __device__ __forceinline__ T ld_stream(const T* p) {
   return __builtin_nontemporal_load(p);
@@ -274,10 +299,12 @@ struct TileRegs {
   u64x2 m[COMMIT ? kRounds : 1][N];
   u64x2 c[COMMIT ? kRounds : 1];
   u64x2 f[COMMIT && GATED ? kRounds : 1];
-  u32x4p vw[VOTES ? (N <= 8 ? 1 : 2) : 1];  // the 8 vote words of the lane's 8 groups
+  u32x4p vw[VOTES ? (N <= 8 ? 1 : 2) : 1];  // the 8 vote words of the lane's 8 groups (tally: their 8 bytes in vw[0].x, .y)
   // tile_body() of the tile's handle (wave-uniform): 0 = every row, slot + 1 = tile_load<kBodySkip> leaves that row out,
   // kSkipNarrow = tile_load<kBodyNarrow> reads the mirror
   uint32_t skip = 0;
+  // the tile's vote part reads the handle's tally bytes instead of its vote words (wave-uniform: HandleWords::tally)
+  bool tally = false;
 };
 
 // The three straight-line bodies of a tile's commit part.  kBodyNarrow keeps its inputs in the SAME registers (so a
@@ -286,34 +313,62 @@ struct TileRegs {
 constexpr int kBodyAll = 0, kBodySkip = 1, kBodyNarrow = 2;
 constexpr uint32_t kSkipNarrow = 0x100u;
 
-// The row a sweep of this handle may leave out: 0 = none (read all N rows), else self slot + 1.  The word is read
-// once per workgroup and made wave-uniform; a commit sweep of N >= 2 (q >= 2) is the only one that can use it.
+// The handle's words as a tile sees them: the self-max word, the narrow word and the tally word sit side by side in one
+// allocation (raftq_create), so ONE 16-byte load at the top of a tile brings all three -- a workgroup waits for one round
+// trip before its streaming loads, not one per word.  Wave-uniform.  A word whose mirror the handle does not have reads 0;
+// a sweep form that can use none of them loads nothing.
+struct HandleWords {
+  uint32_t self_max = 0, narrow = 0, tally = 0;
+};
+template <int N, bool COMMIT, bool VOTES>
+__device__ __forceinline__ HandleWords handle_words(const SweepArgs& a) {
+  HandleWords hw;
+  if constexpr ((COMMIT && N >= 2) || VOTES) {
+    if (a.self_max == nullptr) return hw;
+    const u32x4p w = ldg<false>(reinterpret_cast<const u32x4p*>(a.self_max));
+    hw.self_max = __builtin_amdgcn_readfirstlane(w.x);
+    if (a.narrow != nullptr) hw.narrow = __builtin_amdgcn_readfirstlane(w.y);
+    if (VOTES && a.tally_word != nullptr) hw.tally = __builtin_amdgcn_readfirstlane(w.z);
+  }
+  return hw;
+}
+
+// The row a sweep of this handle may leave out: 0 = none (read all N rows), else self slot + 1.  A commit sweep of
+// N >= 2 (q >= 2) is the only one that can use it.
 template <int N, bool COMMIT>
-__device__ __forceinline__ uint32_t self_max_skip(const SweepArgs& a) {
+__device__ __forceinline__ uint32_t self_max_skip(const HandleWords& hw) {
   if constexpr (!COMMIT || N < 2) {
     return 0;
   } else {
-    if (a.self_max == nullptr) return 0;
-    const uint32_t w = __builtin_amdgcn_readfirstlane(ldg<false>(a.self_max));
-    return (w & kSelfMaxValid) != 0 ? (w & 0xffu) + 1 : 0;
+    return (hw.self_max & kSelfMaxValid) != 0 ? (hw.self_max & 0xffu) + 1 : 0;
   }
 }
 
 // Which body a tile of this handle takes: the one that moves the fewest bytes, a compile-time rule on N.  The narrow body
 // reads 8 + 4N bytes of match data per group, the self-row skip 8(N - 1), every row 8N: narrow beats the skip from N = 5
 // and every row from N = 3; N = 3 and 4 with a valid self-max word keep the skip.  (Both at once would be 8 + 4(N - 1):
-// left out)  The narrow word is read once per workgroup, wave-uniform, and only where it can decide.
-template <int N, bool COMMIT>
+// left out)  With VOTES, kBodyTally is set beside it when the vote part may read the tally bytes.  The handle's
+// three words are read here, once per tile, with one load (handle_words).
+constexpr uint32_t kBodyTally = 0x200u;
+template <int N, bool COMMIT, bool VOTES = false>
 __device__ __forceinline__ uint32_t tile_body(const SweepArgs& a) {
-  const uint32_t skip = self_max_skip<N, COMMIT>(a);
+  const HandleWords hw = handle_words<N, COMMIT, VOTES>(a);
+  const uint32_t tally = VOTES && hw.tally == kTallyValid ? kBodyTally : 0u;
+  const uint32_t skip = self_max_skip<N, COMMIT>(hw);
   if constexpr (!COMMIT || N < 3) {
-    return skip;
+    return skip | tally;
   } else {
-    if (N < 5 && skip != 0) return skip;
-    if (a.narrow == nullptr) return skip;
-    const uint32_t w = __builtin_amdgcn_readfirstlane(ldg<false>(a.narrow));
-    return w == kNarrowValid ? kSkipNarrow : skip;
+    if (N < 5 && skip != 0) return skip | tally;
+    return (hw.narrow == kNarrowValid ? kSkipNarrow : skip) | tally;
   }
+}
+// ... into the tile's registers: the four sites that dispatch on them (sweep_tile, the persistent kernel's load and finish,
+// sweep_segments_kernel) start here.
+template <int N, bool COMMIT, bool VOTES, typename Regs>
+__device__ __forceinline__ void tile_words(Regs& r, const SweepArgs& a) {
+  const uint32_t body = tile_body<N, COMMIT, VOTES>(a);
+  r.skip = body & ~kBodyTally;
+  r.tally = (body & kBodyTally) != 0;
 }
 
 // BODY = kBodySkip (with r.skip = self slot + 1): the tile's commit part reads the N - 1 rows other than the self row into
@@ -334,9 +389,15 @@ __device__ __forceinline__ void tile_load(TileRegs<N, GPL, COMMIT, GATED, VOTES>
   constexpr int kVoteLanes = kTile / 8;  // lanes that own 8 groups each
   if constexpr (VOTES) {
     if (tid < kVoteLanes) {  // wave-uniform (kVoteLanes % 64 == 0)
-      const uint8_t* src = a.votes + (tile0 + 8ull * tid) * vote_word_bytes(N);  // 16 B (N <= 8) or 32 B of words
-      r.vw[0] = ldg<NT>(reinterpret_cast<const u32x4p*>(src));
-      if constexpr (N > 8) r.vw[1] = ldg<NT>(reinterpret_cast<const u32x4p*>(src + 16));
+      if (r.tally) {  // wave-uniform: the 8 groups' tally bytes, one 8-byte load
+        const uint64_t t = ldg<NT>(reinterpret_cast<const uint64_t*>(a.tally + tile0 + 8ull * tid));
+        r.vw[0].x = (uint32_t)t;
+        r.vw[0].y = (uint32_t)(t >> 32);
+      } else {
+        const uint8_t* src = a.votes + (tile0 + 8ull * tid) * vote_word_bytes(N);  // 16 B (N <= 8) or 32 B of words
+        r.vw[0] = ldg<NT>(reinterpret_cast<const u32x4p*>(src));
+        if constexpr (N > 8) r.vw[1] = ldg<NT>(reinterpret_cast<const u32x4p*>(src + 16));
+      }
     }
   }
   if constexpr (COMMIT) {
@@ -488,20 +549,31 @@ __device__ __forceinline__ void tile_finish(const TileRegs<N, GPL, COMMIT, GATED
     if (vote_lane) {
       const uint64_t g = tile0 + 8ull * tid;
       uint32_t out = 0, n_won = 0, n_lost = 0;
+      if (r.tally) {  // wave-uniform, as in tile_load
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        uint32_t w;
-        if constexpr (N <= 8) {
-          const uint32_t pair = k < 2 ? r.vw[0].x : k < 4 ? r.vw[0].y : k < 6 ? r.vw[0].z : r.vw[0].w;
-          w = (k & 1) ? pair >> 16 : pair & 0xffffu;
-        } else {
-          w = k == 0 ? r.vw[0].x : k == 1 ? r.vw[0].y : k == 2 ? r.vw[0].z : k == 3 ? r.vw[0].w
-            : k == 4 ? r.vw[1].x : k == 5 ? r.vw[1].y : k == 6 ? r.vw[1].z : r.vw[1].w;
+        for (int k = 0; k < 8; ++k) {
+          const uint32_t b = ((k < 4 ? r.vw[0].x : r.vw[0].y) >> (8 * (k & 3))) & 0xffu;
+          const uint32_t oc = poll_tally<N>(b);
+          out |= oc << (2 * k);
+          n_won += oc & 1u;
+          n_lost += oc >> 1;
         }
-        const uint32_t oc = poll_word<N>(w);
-        out |= oc << (2 * k);
-        n_won += oc & 1u;
-        n_lost += oc >> 1;
+      } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          uint32_t w;
+          if constexpr (N <= 8) {
+            const uint32_t pair = k < 2 ? r.vw[0].x : k < 4 ? r.vw[0].y : k < 6 ? r.vw[0].z : r.vw[0].w;
+            w = (k & 1) ? pair >> 16 : pair & 0xffffu;
+          } else {
+            w = k == 0 ? r.vw[0].x : k == 1 ? r.vw[0].y : k == 2 ? r.vw[0].z : k == 3 ? r.vw[0].w
+              : k == 4 ? r.vw[1].x : k == 5 ? r.vw[1].y : k == 6 ? r.vw[1].z : r.vw[1].w;
+          }
+          const uint32_t oc = poll_word<N>(w);
+          out |= oc << (2 * k);
+          n_won += oc & 1u;
+          n_lost += oc >> 1;
+        }
       }
       uint16_t* dst = reinterpret_cast<uint16_t*>(a.outcome + (g >> 2));  // 8 groups = 16 bits
       if constexpr (NOSTORE) {
@@ -527,7 +599,7 @@ __device__ __forceinline__ void tile_finish(const TileRegs<N, GPL, COMMIT, GATED
 template <int N, int GPL, bool COMMIT, bool GATED, bool VOTES, int POLICY, bool BITS, int BLOCK = kBlock>
 __device__ __forceinline__ void sweep_tile(const SweepArgs& a, const uint32_t tile) {
   TileRegs<N, GPL, COMMIT, GATED, VOTES> r;
-  r.skip = tile_body<N, COMMIT>(a);
+  tile_words<N, COMMIT, VOTES>(r, a);
   // one uniform branch per tile: each arm is the straight-line load-all-then-finish of one body
   if constexpr (COMMIT && N >= 3) {
     if (r.skip == kSkipNarrow) {
@@ -582,7 +654,7 @@ static __global__ __launch_bounds__(kBlock, MINW) void sweep_persist_kernel(cons
   };
   // a member's tiles with and without its self row (uniform branches; a set may mix flagged and unflagged members)
   auto load = [&](Regs& r, const SweepArgs& a, uint32_t tile) {
-    r.skip = tile_body<N, COMMIT>(a);
+    tile_words<N, COMMIT, VOTES>(r, a);
     if constexpr (COMMIT && N >= 3) {
       if (r.skip == kSkipNarrow) {
         tile_load<N, GPL, COMMIT, GATED, VOTES, POLICY, kBlock, kBodyNarrow>(r, a, tile);
@@ -885,6 +957,24 @@ __device__ __forceinline__ bool narrow_follow(uint32_t w, const NarrowMirror& m,
 // one store per wave that met such a record (the lowest such lane), as clear_self_max_if
 __device__ __forceinline__ void clear_narrow_if(bool broken, uint32_t* word) { clear_self_max_if(broken, word); }
 
+// The tally word's full build: the host has just stored kTallyValid into *word (same stream).  Read the words, write the
+// bytes; nothing can fail, so the word is not touched here.  Grid-stride over the G groups; the padding keeps its zeros
+// (words 0, bytes 0).
+static __global__ __launch_bounds__(kBlock) void tally_build_kernel(const uint8_t* __restrict__ votes, uint64_t n_groups,
+                                                                    uint32_t n_peers, uint8_t* __restrict__ tally) {
+  for (uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x; g < n_groups; g += (uint64_t)gridDim.x * kBlock) {
+    const uint32_t w = n_peers <= 8 ? (uint32_t)reinterpret_cast<const uint16_t*>(votes)[g] : reinterpret_cast<const uint32_t*>(votes)[g];
+    tally[g] = (uint8_t)tally_of_word(w, n_peers);
+  }
+}
+// The handle's tally mirror as the vote ingest sees it: the word (read once) and the bytes; bytes == nullptr = no mirror.
+struct TallyMirror {
+  const uint32_t* word;
+  uint8_t* bytes;
+};
+// one store per wave that changed a vote field without keeping the bytes (the lowest such lane), as clear_self_max_if
+__device__ __forceinline__ void clear_tally_if(bool broken, uint32_t* word) { clear_self_max_if(broken, word); }
+
 // Progress.maybeUpdate only ever raises Match, so a batch of MsgAppResp
 // deltas is an order-independent atomic max.
 // Ingest, pass 1: the records sit in pinned, device-mapped host memory (the caller's batch buffer); one coalesced
@@ -1021,7 +1111,7 @@ static __global__ __launch_bounds__(kBlock) void vote_apply_kernel(uint8_t* vote
                                                             const VoteDeltaRec* __restrict__ d, uint64_t n,
                                                             const unsigned long long* bad, unsigned long long epoch_match,
                                                             unsigned long long epoch_votes, uint64_t n_groups,
-                                                            uint32_t n_peers, int each) {
+                                                            uint32_t n_peers, int each, TallyMirror tally) {
   if (!each && batch_is_bad(bad, epoch_match, epoch_votes)) return;
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
@@ -1029,6 +1119,7 @@ static __global__ __launch_bounds__(kBlock) void vote_apply_kernel(uint8_t* vote
   if (each && !vote_rec_ok(r, n_groups, n_peers)) return;
   const uint64_t slot = (uint64_t)r.peer * ld + r.group;
   if (claim[slot] != (uint32_t)i) return;  // an earlier record of this batch owns the slot
+  const bool follow = tally.bytes != nullptr && *tally.word == kTallyValid;
   // the group's vote word: 2 bits per peer.  Other peers' fields of the same word -- and, with 16-bit words, the
   // neighbouring group's word -- may be written by other lanes: CAS the field into the enclosing 32-bit word
   unsigned int* word = reinterpret_cast<unsigned int*>(votes) + (wide ? r.group : r.group >> 1);
@@ -1039,7 +1130,16 @@ static __global__ __launch_bounds__(kBlock) void vote_apply_kernel(uint8_t* vote
     const unsigned cur = (old >> sh) & 3u;
     if (cur == 1u || cur == 2u) break;  // answered in an earlier batch
     const unsigned seen = atomicCAS(word, old, (old & ~(3u << sh)) | nv);
-    if (seen == old) break;
+    if (seen == old) {
+      // The tally mirror follows: this lane alone turned the field into 01 / 10 (it holds the slot's claim, and an answered
+      // field is never written again), so the group's granted or rejected nibble gains exactly one -- as a 32-bit add into
+      // the word that holds the byte, next to other lanes' adds for its other peers and its three neighbours.  No carry
+      // leaves a nibble: each of the at most 9 peers is counted once.
+      if (follow)
+        atomicAdd(reinterpret_cast<unsigned int*>(tally.bytes) + (r.group >> 2),
+                  (r.vote == 1 ? 1u : 16u) << (8u * (unsigned)(r.group & 3ull)));
+      break;
+    }
     old = seen;
   }
   claim[slot] = 0xffffffffu;  // only the holder releases; later readers see "not mine" either way
@@ -1235,7 +1335,7 @@ static __global__ __launch_bounds__(kBlock) void sweep_segments_kernel(SweepArgs
   __shared__ uint32_t wave_cnt[kWaves];
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, tile = blockIdx.x;
   TileRegs<N, GPL, true, GATED, false> r;
-  r.skip = tile_body<N, true>(a);
+  tile_words<N, true, false>(r, a);
   const bool narrow = N >= 3 && r.skip == kSkipNarrow;  // wave-uniform
   if (narrow) {
     if constexpr (N >= 3) tile_load<N, GPL, true, GATED, false, POLICY, kBlock, kBodyNarrow>(r, a, tile);
@@ -1469,7 +1569,7 @@ static __global__ __launch_bounds__(kBlock) void fill_voters_kernel(uint16_t* vo
 // every bit of `reset` the slot's Match is zeroed and its field of the group's vote word cleared -- a slot reused for a new
 // replica must not inherit its predecessor's Match, and deltas only ever raise it.  A zeroed entry of the self row may end
 // the self-max fact: a batch that resets anything clears the word (always safe; the next full check restores it) -- and the
-// narrow word with it.
+// narrow word with it, and the tally word, whose bytes counted the cleared fields.
 struct VoterDeltaRec {  // == raftq_voter_delta_t
   uint64_t group;
   uint16_t voters, reset;
@@ -1477,7 +1577,8 @@ struct VoterDeltaRec {  // == raftq_voter_delta_t
 };
 static __global__ __launch_bounds__(kBlock) void apply_voter_deltas_kernel(uint16_t* voters, uint64_t* match, uint64_t ld, uint8_t* votes,
                                                                            int wide, uint32_t n_peers, const VoterDeltaRec* __restrict__ d,
-                                                                           uint64_t n, uint32_t* self_max, uint32_t* narrow) {
+                                                                           uint64_t n, uint32_t* self_max, uint32_t* narrow,
+                                                                           uint32_t* tally_word) {
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   bool resets = false;
   if (i < n) {
@@ -1495,6 +1596,7 @@ static __global__ __launch_bounds__(kBlock) void apply_voter_deltas_kernel(uint1
   }
   clear_self_max_if(resets, self_max);
   clear_narrow_if(resets, narrow);  // (a zeroed row entry may lie below its group's anchor)
+  clear_tally_if(resets, tally_word);  // (a cleared field may have been counted)
 }
 
 // ---------------------------------------------------------------------------
@@ -2040,10 +2142,11 @@ static __global__ __launch_bounds__(kBlock) void tick_set_wide_kernel(const Tick
 }
 
 // becomeCandidate for a list of (distinct) groups: role = candidate, elapsed = 0,
-// every vote slot cleared, the candidate's own slot granted: one store of the group's vote word.
+// every vote slot cleared, the candidate's own slot granted: one store of the group's vote word -- and one of its tally
+// byte (one grant, no rejection), which keeps the tally mirror true through the start of an election.
 static __global__ __launch_bounds__(kBlock) void campaign_kernel(uint8_t* role, uint32_t* elapsed, uint8_t* votes,
                                                           uint32_t n_peers, uint32_t self_peer,
-                                                          const uint64_t* __restrict__ groups, uint64_t n) {
+                                                          const uint64_t* __restrict__ groups, uint64_t n, uint8_t* tally) {
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   const uint64_t g = groups[i];
@@ -2052,6 +2155,7 @@ static __global__ __launch_bounds__(kBlock) void campaign_kernel(uint8_t* role, 
   // every slot cleared, the candidate's own granted: the whole vote word in one store
   if (n_peers <= 8) reinterpret_cast<uint16_t*>(votes)[g] = (uint16_t)(1u << (2 * self_peer));
   else reinterpret_cast<uint32_t*>(votes)[g] = 1u << (2 * self_peer);
+  if (tally != nullptr) tally[g] = 1;
 }
 
 }  // namespace raftqk

@@ -461,6 +461,8 @@ struct NodeT {
     if (vw_dirty) {
       if (a.n_peers <= 8) reinterpret_cast<uint16_t*>(a.votes)[g] = (uint16_t)vw;
       else reinterpret_cast<uint32_t*>(a.votes)[g] = vw;
+      // ... nor the tally mirror (the word behind the narrow word): a stored vote word ends it
+      if (a.self_max != nullptr && a.self_max[2] != 0u) a.self_max[2] = 0u;
     }
     if constexpr (CQ)
       if (cq_dirty) a.cq[g] = cqw;

@@ -420,6 +420,19 @@ class QuorumEngine:
         self._chk(self._lib.raftq_narrow_rebuild(self._h))
         return self.narrow()
 
+    def tally(self) -> bool:
+        """raftq_tally: the device knows tally[g] == granted | rejected << 4 of every group's vote word (a sweep with votes then
+        reads the byte instead of the word)"""
+        v = C.c_int32(0)
+        self._chk(self._lib.raftq_tally(self._h, C.byref(v)))
+        return bool(v.value)
+
+    def tally_rebuild(self) -> bool:
+        """raftq_tally_rebuild: the mirror's build pass on demand -> tally()"""
+        v = C.c_int32(0)
+        self._chk(self._lib.raftq_tally_rebuild(self._h, C.byref(v)))
+        return bool(v.value)
+
     def read_votes(self) -> np.ndarray:
         out = np.empty((self.n_peers, self.n_groups), dtype=np.uint8)
         self._chk(self._lib.raftq_read_votes(self._h, _ptr(out)))
