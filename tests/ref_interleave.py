@@ -13,6 +13,11 @@ what the move changed, on ONE handle from the first move to the last.
 The reference of every move is the one its own suite uses (oracle.pyoracle, ref_voters, ref_step_voters, ref_tick_members,
 ref_check_quorum, ref_propose_forward, ref_respond_props / ref_check_quorum_props, test_tick_frames_gpu.want_frames,
 test_tick_elect_gpu.want_round); Step is ref_step_props.step_batch, ref_check_quorum_props.step_batch under CheckQuorum.
+The cases with raftq_set_pre_vote, raftq_set_lead_transfer, raftq_set_read_index and raftq_tick_set_checks on (CASES' second half, "extended"
+below) carry a ref_read_index.Extra beside the node state; their Step is ref_read_index.step_batch, their Tick ref_lead_transfer.tick,
+their fused Tick calls ref_tick_checks' composition, and their batches hold the records that read the transferee, the read record
+and role 3 (follow_records_x, random_records_x).  The six cases of round 26 take none of those paths: their schedules are byte for
+byte what they were (python -m tests.interleave_digest).
 Nothing in here runs the code under test.  TEST INFRASTRUCTURE: nothing in the product imports it."""
 import functools
 from dataclasses import dataclass, field
@@ -25,11 +30,15 @@ from tests import _stepgen, _wiregen
 from tests import ref_bcast_members as B
 from tests import ref_check_quorum as Q
 from tests import ref_check_quorum_props as CP
+from tests import ref_lead_transfer as T
+from tests import ref_pre_vote as PV
 from tests import ref_propose_forward as RF
 from tests import ref_raft_py as R
+from tests import ref_read_index as RI
 from tests import ref_respond_props as RP
 from tests import ref_step_props as P
 from tests import ref_step_voters as V
+from tests import ref_tick_checks as RC
 from tests import ref_tick_members as TM
 from tests import ref_voters as RV
 
@@ -50,18 +59,86 @@ CASES = {
 }
 SEEDS = {"n3": 26003, "n9": 26009, "n5-masked": 26005, "n3-cq": 26103, "n5-masked-cq": 26105}
 
+# Round 33: the same writers crossed with raftq_set_pre_vote (pv), raftq_set_lead_transfer (lt), raftq_set_read_index (ri: its mode) and
+# the fused Tick calls raftq_tick_set_checks reopens (checks).  All of them run under CheckQuorum.  A case with these keys is
+# "extended" below (Ref.ext): its moves, batches and Step reference are the *_x forms; the six cases above take none of those paths.
+SAFE, LEASE = RI.SAFE, RI.LEASE
+CASES.update({
+    "n3-all-safe": dict(n=3, me=1, masks=False, cq=True, walk="lists", schedule="n3-all-safe", pv=True, lt=True, ri=SAFE, checks=False),
+    "n5-masked-all-safe": dict(n=5, me=4, masks=True, cq=True, walk="lists", schedule="n5-masked-all-safe", pv=True, lt=True, ri=SAFE, checks=False),
+    "n5-masked-all-safe-sort": dict(n=5, me=4, masks=True, cq=True, walk="sort", schedule="n5-masked-all-safe", pv=True, lt=True, ri=SAFE, checks=False),
+    "n9-lt-lease-checks": dict(n=9, me=8, masks=False, cq=True, walk="lists", schedule="n9-lt-lease-checks", pv=False, lt=True, ri=LEASE, checks=True),
+    "n3-pv-lease-checks": dict(n=3, me=1, masks=False, cq=True, walk="lists", schedule="n3-pv-lease-checks", pv=True, lt=False, ri=LEASE, checks=True),
+})
+SEEDS.update({"n3-all-safe": 33003, "n5-masked-all-safe": 33005, "n9-lt-lease-checks": 33009, "n3-pv-lease-checks": 33103})
+EXTENDED = tuple(k for k, c in CASES.items() if "pv" in c)
+PV_RULES = (1, 2, 3, 4, 5)  # tests/ref_pre_vote.py's
+
 # kinds that leave every word of the reference where it was (the issue's moves 13 to 15)
 NO_CHANGE = ("clone", "narrow_rebuild", "refused")
 # Tick without CheckQuorum and without the device's campaigns moves `elapsed` alone, a word Step neither reads nor reports with the
 # switch off: no Step record can tell such a move from its absence (tests/test_interleave_ref.py asserts exactly that instead)
 ELAPSED_ONLY = ("tick_lists", "tick_frames")
 TICKS = ("tick", "tick_lists", "tick_frames", "tick_elect")
-ONCE = ("unmask", "remask")
+ONCE = ("unmask", "remask", "pv_off", "pv_on")
+FORCED = {"unmask": "remask", "pv_off": "pv_on"}  # a window of one batch: the second kind comes right behind the first and nowhere else
+
+
+def no_change(case):
+    """the kinds that leave every word of a case's reference where it was: the lease mode holds no read record, so switching it
+    over and back clears nothing"""
+    c = CASES[case]
+    if "pv" not in c:
+        return NO_CHANGE
+    return NO_CHANGE + ("tally_rebuild", "closed") + (("ri_toggle",) if c["ri"] == LEASE else ())
+
+
+def closed_calls(case):
+    """-> [(call, the word its refusal names)] for every call the case's switches close (include/raftq.h "What the switch closes",
+    include/raftq_wire.h).  Without raftq_tick_set_checks the Tick forms are closed to CheckQuorum -- raftq_tick_elect_frames to
+    PreVote first --, so what the safe mode closes shows only behind raftq_tick_set_checks: the "+checks" forms are tried with that
+    switch turned on for the one call and off again.  raftq_set_check_quorum(0) names the first switch that needs it."""
+    c = CASES[case]
+    calls = []
+    if not c["checks"]:
+        calls += [("tick_collect", "check quorum"), ("tick_collect_lists", "check quorum"), ("tick_frames", "check quorum"),
+                  ("tick_elect_frames", "pre vote" if c["pv"] else "check quorum")]
+        if c["ri"] == SAFE:
+            calls += [("tick_frames+checks", "read index"), ("tick_elect_frames+checks", "read index")]
+    if c["lt"]:
+        calls.append(("propose_frames", "lead transfer"))
+    calls.append(("set_check_quorum(0)", "pre vote" if c["pv"] else "lead transfer" if c["lt"] else "read index"))
+    return calls
+
+
+def _kinds_x(c):
+    """the kinds of an extended case.  Left out: `respond` -- no reference of the suite builds raftq_step_frames_respond's streams
+    under these switches (ref_check_quorum_props.want knows CheckQuorum alone: no echoed context, no result kind above 13) --,
+    `propose` where a transfer closes raftq_propose_frames, and `cq_toggle`, which every one of the three switches refuses."""
+    k = dict.fromkeys(("deltas", "vote_deltas", "sweep", "cycle", "roles", "campaign", "term_deltas", "log_deltas", "log_deltas_nowait",
+                       "clone", "narrow_rebuild", "refused", "tally_rebuild", "closed", "activity", "ri_toggle"), 2)
+    if c["checks"]:
+        k.update(tick_lists=2, tick_frames=2, tick_elect=2)
+    else:
+        k.update(tick=3)
+    if c["lt"]:
+        k.update(transfer=2, lt_toggle=2)
+    else:
+        k.update(propose=2)
+    if c["ri"] == SAFE:
+        k.update(reads=2)
+    if c["pv"]:
+        k.update(pv_off=1, pv_on=1)
+    if c["masks"]:
+        k.update(voter_deltas=2, unmask=1, remask=1)
+    return k
 
 
 def kinds_of(case):
     """-> {kind: how often} for a case of CASES"""
     c = CASES[case]
+    if "pv" in c:
+        return _kinds_x(c)
     k = dict.fromkeys(("deltas", "vote_deltas", "sweep", "cycle", "roles", "campaign", "term_deltas", "log_deltas", "log_deltas_nowait",
                        "propose", "respond", "clone", "narrow_rebuild", "refused"), 2)
     if c["cq"]:
@@ -80,20 +157,63 @@ class Ref:
     def __init__(self, s, voters, cq, active, lead_elapsed):
         self.s, self.voters, self.cq, self.active, self.le, self.tick_no = s, voters, cq, active, lead_elapsed, 0
         self.saved = None  # the masks while they are dropped
+        # an extended case (extend()): the switches as they stand, the case's PreVote (pv is off inside the pv_off window), and a
+        # ref_read_index.Extra's other three arrays -- the transferees [G] u8, seq [G] u32 and acked [N][G] u32
+        self.ext, self.pv, self.pv_case, self.lt, self.ri, self.checks = False, False, False, False, 0, False
+        self.transferee = self.seq = self.acked = None
+
+    def extend(self, case, transferee, seq, acked):
+        c = CASES[case]
+        self.case = case
+        self.ext, self.pv, self.pv_case, self.lt, self.ri, self.checks = True, c["pv"], c["pv"], c["lt"], c["ri"], c["checks"]
+        self.transferee, self.seq, self.acked = transferee, seq, acked
+        return self
 
     def copy(self):
         c = Ref(V.copy_state(self.s), None if self.voters is None else self.voters.copy(), self.cq, self.active.copy(), self.le.copy())
         c.tick_no, c.saved = self.tick_no, self.saved
+        if self.ext:
+            c.case, c.ext, c.pv, c.pv_case, c.lt, c.ri, c.checks = self.case, True, self.pv, self.pv_case, self.lt, self.ri, self.checks
+            c.transferee, c.seq, c.acked = self.transferee.copy(), self.seq.copy(), self.acked.copy()
         return c
 
     @property
     def masks(self):
         return V.full_masks(self.s.N, self.s.G) if self.voters is None else self.voters
 
-    def step(self, m):
-        """Step for every record, in order -> raftq_step_out_t[]; a malformed batch raises ValueError and moves nothing"""
+    @property
+    def extra(self):
+        """the arrays as the ref_read_index.Extra Step moves (views: the Ref moves with it)"""
+        return RI.Extra(self.active, self.le, self.transferee, self.seq, self.acked)
+
+    def unknown(self, m):
+        """[len(m)] bool: records of a kind the handle's switches do not know (a batch that holds one is refused as a malformed one is)"""
+        looked = (m["_pad"][:, 1] & (V.MSGF_SKIP | V.MSGF_HOLD)) == 0
+        bad = np.zeros(len(m), bool)
+        if not self.pv:
+            bad |= np.isin(m["type"], (PV.MsgPreVote, PV.MsgPreVoteResp))
+        if not self.lt:
+            bad |= np.isin(m["type"], (T.MsgTransferLeader, T.MsgTimeoutNow))
+        if not self.ri:
+            bad |= np.isin(m["type"], (RI.MsgReadIndex, RI.MsgReadIndexResp))
+        return looked & bad
+
+    def step(self, m, ri_out=frozenset(), lt_out=frozenset(), pv_out=frozenset()):
+        """Step for every record, in order -> raftq_step_out_t[]; a malformed batch raises ValueError and moves nothing.
+        An extended case: ref_read_index.step_batch with the switches as they stand (*_out: rules of the three references left out,
+        tests only).  Inside the pv_off window the classes are PreVote's with all five of its rules left out -- ref_pre_vote's own
+        statement of a Step without the switch, under which a role-3 group is stepped by the follower's arm and keeps role 3 until a
+        message gives it another (include/raftq.h "PreVote", Roles); tests/test_interleave_ref.py holds that form to the classes
+        without PreVote on every group that is not in role 3."""
         if refuses(m, self.s.G, self.s.N):
             raise ValueError("malformed batch")
+        if self.ext:
+            if self.unknown(m).any():
+                raise ValueError("a kind the switches do not know")
+            if self.pv_case and not self.pv:
+                pv_out = frozenset(PV_RULES)
+            return RI.step_batch(self.s, self.voters, self.extra, m, mode=self.ri, pre_vote=self.pv_case, lead_transfer=self.lt, election_tick=ET,
+                                 leave_out=ri_out, lt_leave_out=lt_out, pv_leave_out=pv_out)
         if self.cq:
             return CP.step_batch(self.s, self.voters, self.active, self.le, m, election_tick=ET)
         return P.step_batch(self.s, self.voters, m)
@@ -101,6 +221,9 @@ class Ref:
     def same(self, o):
         a, b = self.s, o.s
         if not all(np.array_equal(getattr(a, k), getattr(b, k)) for k, _ in pyoracle.NodeState.FIELDS):
+            return False
+        if self.ext and not ((self.pv, self.lt, self.ri) == (o.pv, o.lt, o.ri) and np.array_equal(self.transferee, o.transferee)
+                             and np.array_equal(self.seq, o.seq) and np.array_equal(self.acked, o.acked)):
             return False
         return (np.array_equal(a.match, b.match) and np.array_equal(a.votes, b.votes) and np.array_equal(self.masks, o.masks)
                 and np.array_equal(self.active, o.active) and np.array_equal(self.le, o.le))
@@ -194,21 +317,107 @@ def random_records(ref, rng, n, keep_off, hot=None):
     return m
 
 
+def follow_records_x(ref, groups, rng, kind):
+    """follow_records for an extended case, with the records that read the new state put over it (the generators'
+    shapes are ref_lead_transfer.step_case's, ref_read_index.step_case's and ref_pre_vote.step_case's):
+      led, a transferee pending    a MsgProp, which must be dropped, or the transferee's acknowledgement of the tail (MsgTimeoutNow)
+      led, ReadIndex               a local MsgReadIndex (numbered behind seq, released at the commit index -- at once under the
+                                   lease), or a MsgHeartbeatResp whose context is one of the numbers handed out
+      role 3                       a MsgPreVoteResp from a slot that has not answered: a grant at term + 1 or a rejection at the term
+      followers, ReadIndex         a MsgReadIndex to forward, a context on the heartbeat to echo
+    pv_off / pv_on: what tells the two apart needs no kind the window does not know -- a MsgHup (a pre-election with the switch, a
+    campaign without) or a heartbeat of the term before (RAFTQ_OUT_TERM_RESP with the switch, nothing without)."""
+    s = ref.s
+    n, me = s.N, s.self_peer
+    others = _others(n, me)
+    m = follow_records(ref, groups, rng, timers=kind in TIMER_KINDS_X)
+    window = kind in ("pv_off", "pv_on")
+    for i, g in enumerate(np.asarray(groups, np.int64)):
+        g = int(g)
+        role, term, li = int(s.role[g]), int(s.term[g]), int(s.last_index[g])
+        u, p = rng.random(), int(rng.choice(others))
+        if role == 2:
+            if int(m["type"][i]) == Q.MsgCheckQuorum:
+                continue
+            t = int(ref.transferee[g]) if ref.lt else 0
+            if ref.lt and u < (0.7 if t else 0.35 if kind in TRANSFER_KINDS else 0.0):  # (none pending behind such a move: the MsgProp is taken)
+                if u < 0.35 or t - 1 == me:
+                    T._prop(m, i, g, 2, frm=p)
+                else:
+                    Q._rec(m, i, g, R.MsgAppResp, term=term, frm=t - 1, index=li)
+            elif u < (0.7 if kind in READ_KINDS else 0.3):
+                sq = int(ref.seq[g])
+                if ref.ri == SAFE and sq > 0 and rng.random() < 0.5:
+                    PV._rec(m, i, g, R.MsgHeartbeatResp, term=term, frm=p, index=int(rng.integers(1, sq + 1)))
+                else:
+                    PV._rec(m, i, g, RI.MsgReadIndex, frm=me)
+        elif window or (role == PV.PRE and not ref.pv):
+            if u < 0.5 or term < 2:
+                PV._rec(m, i, g, R.MsgHup)
+            else:
+                PV._rec(m, i, g, R.MsgHeartbeat, term=term - 1, frm=p)
+        elif role == PV.PRE:
+            free = [q for q in others if int(s.votes[q, g]) == 0]
+            grant = rng.random() < 0.7
+            PV._rec(m, i, g, PV.MsgPreVoteResp, term=term + 1 if grant else term, frm=int(rng.choice(free)) if free else p, reject=0 if grant else 1)
+        elif role == 0 and int(s.lead[g]) != 0 and u < 0.3:
+            if int(m["type"][i]) == R.MsgHeartbeat:
+                m["index"][i] = int(rng.integers(1, 7))
+            else:
+                PV._rec(m, i, g, RI.MsgReadIndex, frm=me)
+    return m
+
+
+def random_records_x(ref, rng, n, keep_off, hot=None):
+    """random_records, then -- among the records Step looks at -- the kinds of the switches that are on, in the three generators'
+    ways: half the MsgVote / MsgVoteResp records turned into their pre-election kinds; a small context on every MsgHeartbeat /
+    MsgHeartbeatResp and one record in eight turned into a MsgReadIndex or MsgReadIndexResp; one in twelve into a
+    MsgTransferLeader or MsgTimeoutNow (a MsgVote's reject byte, the transfer's mark, is drawn by _stepgen already)."""
+    s = ref.s
+    m = random_records(ref, rng, n, keep_off, hot=hot)
+    plain = np.flatnonzero((m["_pad"][:, 1] & (V.MSGF_SKIP | V.MSGF_HOLD)) == 0)
+    if ref.pv:
+        turn = plain[rng.random(len(plain)) < 0.5]
+        m["type"][turn] = np.where(m["type"][turn] == R.MsgVote, PV.MsgPreVote, np.where(m["type"][turn] == R.MsgVoteResp, PV.MsgPreVoteResp, m["type"][turn]))
+    beats = plain[np.isin(m["type"][plain], (R.MsgHeartbeat, R.MsgHeartbeatResp))]
+    m["index"][beats] = rng.integers(0, 7, len(beats))
+    for i in plain[rng.random(len(plain)) < 1 / 8]:
+        grp = int(m["group"][i])
+        kind = RI.MsgReadIndex if rng.random() < 0.6 else RI.MsgReadIndexResp
+        term = 0 if kind == RI.MsgReadIndex and rng.random() < 0.5 else max(1, int(s.term[grp]) + int(rng.choice([-1, 0, 0, 0, 1])))
+        PV._rec(m, i, grp, kind, term=term, frm=int(rng.integers(0, s.N)), index=int(rng.integers(0, 50)))
+    if ref.lt:
+        for i in plain[rng.random(len(plain)) < 1 / 12]:
+            grp = int(m["group"][i])
+            kind = T.MsgTransferLeader if rng.random() < 0.5 else T.MsgTimeoutNow
+            term = 0 if kind == T.MsgTransferLeader and rng.random() < 0.5 else max(1, int(s.term[grp]) + int(rng.choice([-1, 0, 0, 0, 1])))
+            PV._rec(m, i, grp, kind, term=term, frm=int(rng.integers(0, s.N)))
+    return m
+
+
 def make_batch(ref, mv, rng, hot=None):
     """the records of the move's changed groups (the move's own, where it made some), the random traffic, shuffled: at most 1,024"""
+    if ref.ext:
+        follow, random_part = (lambda groups: follow_records_x(ref, groups, rng, mv.kind)), random_records_x
+    else:
+        follow, random_part = (lambda groups: follow_records(ref, groups, rng, timers=ref.cq and mv.kind in TIMER_KINDS)), random_records
     changed = np.asarray(mv.changed, np.int64)[:MAX_CHANGED]
     if mv.records is not None:
         forced = np.unique(mv.records["group"].astype(np.int64))
         rest = changed[~np.isin(changed, forced)][: MAX_CHANGED - len(mv.records)]
-        own = np.concatenate([mv.records, follow_records(ref, rest, rng, timers=ref.cq and mv.kind in TIMER_KINDS)])
+        own = np.concatenate([mv.records, follow(rest)])
     else:
-        own = follow_records(ref, changed, rng, timers=ref.cq and mv.kind in TIMER_KINDS)
-    m = np.concatenate([own, random_records(ref, rng, N_RANDOM, own["group"][own["group"] < U(ref.s.G)], hot=hot)])
+        own = follow(changed)
+    m = np.concatenate([own, random_part(ref, rng, N_RANDOM, own["group"][own["group"] < U(ref.s.G)], hot=hot)])
     assert len(m) <= 1024
     return np.ascontiguousarray(m[rng.permutation(len(m))])
 
 
 TIMER_KINDS = ("tick", "activity", "cq_toggle", "roles")  # under CheckQuorum: the moves whose change Step reads through the lease or a check
+TIMER_KINDS_X = TIMER_KINDS + ("tick_lists", "tick_frames", "tick_elect")
+TRANSFER_KINDS = TIMER_KINDS_X + ("transfer", "lt_toggle", "clone")  # ... a transferee may be gone, or have come
+# an extended case: the moves behind which a led group's read record, commit index or term gate may stand elsewhere
+READ_KINDS = ("reads", "ri_toggle", "clone", "sweep", "cycle", "deltas", "term_deltas", "log_deltas", "log_deltas_nowait", "unmask", "remask", "voter_deltas")
 
 
 # ---- the moves: each applies itself to `ref` and returns the Move (inputs, expected outputs, changed groups) ----------------------
@@ -589,6 +798,192 @@ def mv_cq_toggle(ref, rng):
     return Move("cq_toggle", {}, {}, rng.permutation(ch))
 
 
+# ---- the moves of an extended case -------------------------------------------------------------------------------------------------
+def _holds_more(ref):
+    """[G] bool: a transferee or a read record stands in the group"""
+    return (ref.transferee != 0) | (ref.seq != 0) | (ref.acked != 0).any(axis=0)
+
+
+def mv_roles_x(ref, rng):
+    """mv_roles; under PreVote some of the groups that become candidates and know no leader become pre-candidates (role 3, what
+    becomePreCandidate leaves).  A led group that holds a transferee or a read record keeps its role: only a leader holds either
+    (ref_lead_transfer.tick_input, ref_read_index.step_case), and raftq_load_roles is no reset()."""
+    s = ref.s
+    pool = np.flatnonzero(~((s.role == 2) & _holds_more(ref)))
+    flip = rng.choice(pool, 50, replace=False)
+    new = ((s.role[flip] % 3) + rng.integers(1, 3, len(flip))) % 3
+    if ref.pv:
+        new[(new == 1) & (s.lead[flip] == 0) & (rng.random(len(flip)) < 0.6)] = PV.PRE
+    s.role[flip] = new
+    idle = np.flatnonzero(s.role != 2)
+    redraw = rng.choice(idle, min(300, len(idle)), replace=False)
+    s.elapsed[redraw] = rng.integers(0, 2 * ET, len(redraw))
+    leased = redraw[(s.role[redraw] == 0) & (s.lead[redraw] != 0)]
+    s.elapsed[leased[:30]] = ET - 1  # the next Tick ends their lease
+    return Move("roles", dict(role=s.role.copy(), elapsed=s.elapsed.copy()), {}, np.unique(np.concatenate([flip, leased])))
+
+
+def _tick_x(ref):
+    """ref_lead_transfer.tick on the reference (ref_check_quorum.tick_array over the word's low half: a check that passes clears
+    the transferee with the bits) -> (want, the groups whose change Step can read)"""
+    s = ref.s
+    role0, el0, ac0, tr0 = s.role.copy(), s.elapsed.copy(), ref.active.copy(), ref.transferee.copy()
+    el, act, ac, le, tr, nh, nb = T.tick(pyoracle, s.role, s.elapsed, ref.active, ref.le, ref.transferee, ref.voters, s.self_peer, s.N, ET, HB, SEED,
+                                         ref.tick_no)
+    s.elapsed[:], ref.active[:], ref.le[:], ref.transferee[:] = el, ac, le, tr
+    ref.tick_no += 1
+    hups, beats, checks = (np.flatnonzero(act == k) for k in (1, 2, 3))
+    crossed = np.flatnonzero((role0 != 2) & (s.lead != 0) & (el0 < ET) & (el >= ET))
+    cleared = np.flatnonzero((role0 == 2) & (((ac0 != 0) & (ac == 0)) | ((tr0 != 0) & (tr == 0))))
+    want = dict(n_hup=nh, n_beat=nb, action=act, hups=hups, beats=beats, checks=checks, crossed=len(crossed), aborted=int(((tr0 != 0) & (tr == 0)).sum()))
+    return want, np.concatenate([crossed, cleared, checks])
+
+
+def mv_tick_x(ref, rng):
+    """mv_tick with the transferee in the word"""
+    want, read = _tick_x(ref)
+    hups, checks = want["hups"], want["checks"]
+    want.update(hups=hups.astype(U), beats=want["beats"].astype(U), checks=checks.astype(U))
+    return Move("tick", {}, want, np.concatenate([read, hups]), records=_hup_check_records(hups[:200], checks[:200]))
+
+
+def _lists32(want):
+    want.update({k: want[k].astype(np.uint32) for k in ("hups", "beats", "checks")})
+    return want
+
+
+def mv_tick_lists_x(ref, rng):
+    """raftq_tick_collect_lists under raftq_tick_set_checks: the Tick and its three lists"""
+    want, read = _tick_x(ref)
+    hups, checks = want["hups"], want["checks"]
+    return Move("tick_lists", {}, _lists32(want), np.concatenate([read, hups]), records=_hup_check_records(hups[:200], checks[:200]))
+
+
+def mv_tick_frames_x(ref, rng):
+    """raftq_tick_frames under raftq_tick_set_checks: the Tick, its three lists and the heartbeats of the MsgBeat groups, none of them
+    a group whose check failed (ref_tick_checks.beats_round, as tests/test_tick_checks_gpu.py composes it)"""
+    s = ref.s
+    want, read = _tick_x(ref)
+    hups, checks = want["hups"], want["checks"]
+    w, keep, po = RC.beats_round(s, ref.voters, want["beats"].astype(np.uint32), s.G)
+    stream, off = TM.encode_members(w, keep, s.G * (s.N - 1))
+    want.update(stream=np.asarray(stream), off=off, peer_off=np.asarray(po, U), n_frames=int(np.asarray(keep).sum()))
+    return Move("tick_frames", {}, _lists32(want), np.concatenate([read, hups]), records=_hup_check_records(hups[:200], checks[:200]))
+
+
+def mv_tick_elect_x(ref, rng):
+    """raftq_tick_elect_frames under raftq_tick_set_checks: ref_tick_checks.round_'s composition with the Tick above and the election
+    round stepped by this case's Step -- MsgHup records of every MsgHup group: a campaign, whose reset() clears the activity word, or
+    under PreVote a pre-election that moves no term"""
+    s = ref.s
+    n, me = s.N, s.self_peer
+    want, read = _tick_x(ref)
+    bw, bkeep, bpo = RC.beats_round(s, ref.voters, want["beats"].astype(np.uint32), s.G)
+    vw, vkeep, camp, built, outs = RC.campaigns(s, ref.active, ref.le, ref.voters, want["hups"].astype(np.uint32), s.G, ref.pv, ET, step=ref.step)
+    po = np.zeros(2 * (n + 1), U)
+    po[: n + 1] = bpo
+    po[n + 1] = bpo[n]
+    po[n + 2:] = bpo[n] + np.cumsum([0 if p == me else len(built) for p in range(n)]).astype(U)
+    keep = np.concatenate([bkeep, vkeep])
+    stream, off = TM.encode_members(np.concatenate([bw, vw]), keep, 2 * s.G * (n - 1))
+    want.update(stream=np.asarray(stream), off=off, peer_off=po, n_frames=int(keep.sum()), camp=camp, built=built, outs=outs)
+    return Move("tick_elect", {}, _lists32(want), np.concatenate([read, built]), records=_hup_check_records([], want["checks"][:200]))
+
+
+def mv_activity_x(ref, rng):
+    """mv_activity; of the groups it rewrites, up to 12 that hold a transferee get every activity bit and lead_elapsed one short of
+    the timeout: the next Tick's check falls due, passes and aborts their transfer.  The transferees themselves stand."""
+    mv = mv_activity(ref, rng)
+    due = mv.changed[ref.transferee[mv.changed] != 0][:12]
+    ref.active[due], ref.le[due] = (1 << ref.s.N) - 1, ET - 1
+    mv.args = dict(active=ref.active.copy(), lead_elapsed=ref.le.copy())
+    return mv
+
+
+def mv_transfer(ref, rng):
+    """raftq_load_transfer: other transferees in about 150 led groups -- mostly another slot, sometimes none, seldom self"""
+    s = ref.s
+    n, me = s.N, s.self_peer
+    led = _led(ref)
+    g = rng.choice(led, min(150, len(led)), replace=False)
+    old = ref.transferee[g].copy()
+    u = rng.random(len(g))
+    new = np.where(u < 0.2, 0, np.where(u < 0.25, me + 1, 1 + _others(n, me)[rng.integers(0, n - 1, len(g))])).astype(np.uint8)
+    ref.transferee[g] = new
+    return Move("transfer", dict(transferee=ref.transferee.copy()), {}, g[new != old])
+
+
+def mv_reads(ref, rng):
+    """raftq_load_reads: other read records in about 150 led groups, every acked word at most its group's seq"""
+    n = ref.s.N
+    led = _led(ref)
+    g = rng.choice(led, min(150, len(led)), replace=False)
+    old = (ref.seq[g].copy(), ref.acked[:, g].copy())
+    ref.seq[g] = rng.integers(0, 7, len(g))
+    ref.acked[:, g] = (rng.random((n, len(g))) * (ref.seq[g] + 1)[None, :]).astype(np.uint32)
+    moved = (ref.seq[g] != old[0]) | (ref.acked[:, g] != old[1]).any(axis=0)
+    return Move("reads", dict(seq=ref.seq.copy(), acked=ref.acked.copy()), {}, g[moved])
+
+
+def mv_lt_toggle(ref, rng):
+    """raftq_set_lead_transfer(h, 0) then (h, 1): every transferee is 0, the activity bits and lead_elapsed stand"""
+    ch = np.flatnonzero(ref.transferee != 0)
+    ref.transferee[:] = 0
+    return Move("lt_toggle", {}, {}, rng.permutation(ch))
+
+
+def mv_ri_toggle(ref, rng):
+    """raftq_set_read_index to the other mode and back: the safe mode's records come back zeroed, everything else stands"""
+    other = LEASE if ref.ri == SAFE else SAFE
+    if ref.ri == LEASE:
+        return Move("ri_toggle", dict(other=other), {}, _sample(ref, rng))
+    ch = np.flatnonzero((ref.seq != 0) | (ref.acked != 0).any(axis=0))
+    ref.seq[:], ref.acked[:] = 0, 0
+    return Move("ri_toggle", dict(other=other), {}, rng.permutation(ch))
+
+
+def _window_groups(ref, rng):
+    pre = np.flatnonzero(ref.s.role == PV.PRE)
+    rest = np.flatnonzero((ref.s.role != PV.PRE) & (ref.s.role != 2))
+    return np.concatenate([rng.permutation(pre), rng.choice(rest, min(150, len(rest)), replace=False)])
+
+
+def mv_pv_off(ref, rng):
+    """raftq_set_pre_vote(h, 0): the batch behind runs without PreVote"""
+    ref.pv = False
+    return Move("pv_off", {}, {}, _window_groups(ref, rng))
+
+
+def mv_pv_on(ref, rng):
+    ref.pv = True
+    return Move("pv_on", {}, {}, _window_groups(ref, rng))
+
+
+def mv_tally_rebuild(ref, rng):
+    return Move("tally_rebuild", {}, {}, _sample(ref, rng))
+
+
+def mv_closed(ref, rng):
+    """every call the case's switches close, tried once: each is refused with its word and moves nothing.  The raftq_propose_frames
+    that a transfer closes gets sound proposals on three led groups."""
+    led = _led(ref)[:3]
+    props, pe = np.zeros(len(led), RF.PROP_DT), np.zeros(len(led), RF.PROP_ENT_DT)
+    props["group"], props["n_ents"], props["ent_first"] = led, 1, np.arange(len(led))
+    pe["data_len"], pe["data_off"] = 4, 4 * np.arange(len(led))
+    args = dict(calls=closed_calls(ref.case), props=props, pe=pe, pool=np.arange(4 * len(led) + 1, dtype=np.uint8),
+                hm=np.zeros(0, W.WIRE_MSG_DT), he=np.zeros(0, W.WIRE_ENT_DT))
+    return Move("closed", args, {}, _sample(ref, rng))
+
+
+MOVES_X = {"roles": mv_roles_x, "tick": mv_tick_x, "tick_lists": mv_tick_lists_x, "tick_frames": mv_tick_frames_x, "tick_elect": mv_tick_elect_x,
+           "transfer": mv_transfer, "reads": mv_reads, "lt_toggle": mv_lt_toggle, "ri_toggle": mv_ri_toggle, "pv_off": mv_pv_off, "pv_on": mv_pv_on,
+           "tally_rebuild": mv_tally_rebuild, "closed": mv_closed, "activity": mv_activity_x}
+
+
+def move_fn(ref, kind):
+    return MOVES_X[kind] if ref.ext and kind in MOVES_X else MOVES[kind]
+
+
 MOVES = {f.__name__[3:]: f for f in (mv_deltas, mv_vote_deltas, mv_sweep, mv_cycle, mv_roles, mv_campaign, mv_term_deltas, mv_log_deltas,
                                      mv_log_deltas_nowait, mv_voter_deltas, mv_unmask, mv_remask, mv_tick, mv_tick_lists, mv_tick_frames,
                                      mv_tick_elect, mv_propose, mv_respond, mv_clone, mv_narrow_rebuild, mv_refused, mv_activity, mv_cq_toggle)}
@@ -597,6 +992,20 @@ MOVES = {f.__name__[3:]: f for f in (mv_deltas, mv_vote_deltas, mv_sweep, mv_cyc
 def admissible(ref, kind):
     """the state holds what the move needs to change something"""
     s = ref.s
+    if ref.ext:
+        if kind in TICKS:  # a dry run: Step can read what the Tick moved, and the device's round has campaigns to build
+            w = move_fn(ref, kind)(ref.copy(), np.random.default_rng(0)).want
+            return w["crossed"] >= 3 and (kind != "tick_elect" or len(w["built"]) >= 4)
+        if kind in ("transfer", "reads"):
+            return int((s.role == 2).sum()) >= 32
+        if kind == "lt_toggle":
+            return int(((s.role == 2) & (ref.transferee != 0)).sum()) >= 16
+        if kind == "ri_toggle":
+            return ref.ri == LEASE or int(((s.role == 2) & (ref.seq != 0)).sum()) >= 16
+        if kind == "pv_off":
+            return int((s.role == PV.PRE).sum()) >= 8
+        if kind == "pv_on":
+            return False  # only right behind "pv_off"
     if kind in ("deltas", "cycle", "term_deltas", "activity"):
         return int((s.role == 2).sum()) >= 32
     if kind == "vote_deltas":
@@ -616,7 +1025,8 @@ def admissible(ref, kind):
 
 # what makes a kind admissible again when nothing that is left is: one more move of the feeding kind is put in front of it
 FEEDER = {"sweep": "deltas", "vote_deltas": "campaign", "cq_toggle": "activity", "tick": "roles", "tick_lists": "roles", "tick_frames": "roles",
-          "tick_elect": "roles", "deltas": "roles", "cycle": "roles", "term_deltas": "roles", "activity": "roles"}
+          "tick_elect": "roles", "deltas": "roles", "cycle": "roles", "term_deltas": "roles", "activity": "roles",
+          "lt_toggle": "transfer", "ri_toggle": "reads", "transfer": "roles", "reads": "roles", "pv_off": "roles"}
 
 
 # ---- a case's start and its schedule ----------------------------------------------------------------------------------------------
@@ -630,7 +1040,27 @@ def start_of(case):
     active = rng.integers(0, full + 1, G).astype(np.uint16) if c["cq"] else np.zeros(G, np.uint16)
     le = rng.integers(0, ET, G).astype(np.uint32) if c["cq"] else np.zeros(G, np.uint32)
     voters = B.propose_masks(rng, n, G, me, np.arange(G)) if c["masks"] else None  # self and one other slot vote everywhere
-    return Ref(s, voters, c["cq"], active, le), rng
+    ref = Ref(s, voters, c["cq"], active, le)
+    if "pv" in c:
+        _extend_start(ref, case, rng)
+    return ref, rng
+
+
+def _extend_start(ref, case, rng):
+    """the three generators' starts: under PreVote every third candidate a pre-candidate; under transfer a transferee in one led
+    group of three; in the safe mode a read record (seq up to 5, every acked word at most seq) in every led group"""
+    c, s = CASES[case], ref.s
+    n = s.N
+    if c["pv"]:
+        s.role[np.flatnonzero(s.role == 1)[::3]] = PV.PRE
+    led = np.flatnonzero(s.role == 2)
+    x = RI.zero_extra(G, n)
+    if c["lt"]:
+        x.transferee[led] = np.where(rng.random(len(led)) < 1 / 3, 1 + rng.integers(0, n, len(led)), 0)
+    if c["ri"] == SAFE:
+        x.seq[led] = rng.integers(0, 6, len(led))
+        x.acked[:, led] = (rng.random((n, len(led))) * (x.seq[led] + 1)[None, :]).astype(np.uint32)
+    ref.extend(case, x.transferee, x.seq, x.acked)
 
 
 @functools.lru_cache(maxsize=None)
@@ -655,9 +1085,9 @@ def _schedule(key):
             if not admissible(ref, kind):
                 kind = FEEDER.get(kind, "roles")
             assert len(moves) < 3 * total, ("the feeders do not help", left)
-        force = "remask" if kind == "unmask" else None
+        force = FORCED.get(kind)
         before = ref.copy()
-        mv = MOVES[kind](ref, rng)
+        mv = move_fn(ref, kind)(ref, rng)
         mv.before, mv.after = before, ref.copy()
         mv.changed = np.asarray(mv.changed, np.int64)
         if len(moves) in pairs:
@@ -701,10 +1131,45 @@ def discriminates(mv):
     independent in Step: the records of other groups are left out) -> the changed groups in which a record differs"""
     m, want = mv.batches[0], mv.wants[0]
     mine = ((m["_pad"][:, 1] & V.MSGF_SKIP) == 0) & np.isin(m["group"], mv.changed.astype(U))
+    if mv.before.ext:  # (pv_on: a kind the handle in front of the move would refuse the batch for tells nothing apart by its record)
+        mine &= ~mv.before.unknown(m)
     got = mv.before.copy().step(np.ascontiguousarray(m[mine]))
     k = got.dtype.itemsize
     differs = (got.view(np.uint8).reshape(-1, k) != np.ascontiguousarray(want[mine]).view(np.uint8).reshape(-1, k)).any(axis=1)
     return np.unique(m["group"][mine][differs])
+
+
+def case_rules(case):
+    """-> [(reference, rule)] every Step rule the switches of an extended case enable: "ri" ref_read_index's (the lease mode keeps no
+    record: 2 and 6 alone, ref_read_index.case_rules), "lt" ref_lead_transfer's, "pv" ref_pre_vote's"""
+    c = CASES[case]
+    rules = [("ri", r) for r in ((2, 6) if c["ri"] == LEASE else RI.RULES)]
+    rules += [("lt", r) for r in T.RULES] if c["lt"] else []
+    return rules + ([("pv", r) for r in PV_RULES] if c["pv"] else [])
+
+
+def batches_changed_without(sch, which, rule, stop_at=None):
+    """the schedule's batches stepped again, each from the state it was made for, with one rule left out -> how many of them give
+    another record or leave another word of state (the per-rule floor of the features' own suites, applied to the schedules).
+    stop_at: stop counting there.  The batch inside the pv_off window has no PreVote rule to leave out."""
+    n = 0
+    for mv in sch.moves:
+        for j, (m, w) in enumerate(zip(mv.batches, mv.wants)):
+            st = mv.after.copy()
+            if j:
+                st.step(mv.batches[0])
+            if which == "pv" and not st.pv:
+                continue
+            if len(mv.batches) == 1:
+                full = mv.after_step
+            else:
+                full = st.copy()
+                full.step(m)
+            got = st.step(m, **{which + "_out": frozenset({rule})})
+            n += got.tobytes() != w.tobytes() or not st.same(full)
+            if stop_at is not None and n >= stop_at:
+                return n
+    return n
 
 
 def counts(sch):

@@ -221,13 +221,15 @@ def confirmed_of(x, voters, n):
 
 
 def step_batch(s, voters, x, msgs, mode=SAFE, pre_vote=True, lead_transfer=True, election_tick=ELECTION_TICK, leave_out=frozenset(), frames=False,
-               arm_count=None):
+               arm_count=None, lt_leave_out=frozenset(), pv_leave_out=frozenset()):
     """Step for every message, in order, with raftq_set_check_quorum, raftq_step_set_props and raftq_set_read_index(mode) on (and
     raftq_set_pre_vote / raftq_set_lead_transfer as said) -> raftq_step_out_t[]; `s` and the Extra `x` move.  voters: the masks, or
-    None for a handle without them.  leave_out: this module's rule numbers or names."""
+    None for a handle without them.  leave_out: this module's rule numbers or names; lt_leave_out / pv_leave_out: ref_lead_transfer's
+    and ref_pre_vote's, for the classes that hold those arms."""
     out = np.zeros(len(msgs), dtype=pyoracle.STEP_OUT_DT)
     rafts = {}
-    ri_out = rules(leave_out)
+    ri_out, lt_out, pv_out = rules(leave_out), T.rules(lt_leave_out), frozenset(pv_leave_out)
+    assert (lead_transfer or not lt_out) and (pre_vote or not pv_out), "a rule of a switch that is off cannot be left out"
     n = s.N
     for i in range(len(msgs)):
         m = msgs[i]
@@ -242,6 +244,10 @@ def step_batch(s, voters, x, msgs, mode=SAFE, pre_vote=True, lead_transfer=True,
                                              classes=_CLASSES[(bool(pre_vote), bool(lead_transfer))])
             r.transferee = int(x.transferee[g])
             r.ri_mode, r.ri_out, r.arm_count = mode, ri_out, arm_count
+            if lt_out:
+                r.lt_out = lt_out
+            if pv_out:
+                r.pv_out = pv_out
             r.seq = int(x.seq[g])
             r.acked = {p + 1: int(x.acked[p, g]) for p in range(n) if x.acked[p, g]}
             r.held = False

@@ -48,10 +48,11 @@ def tick(st, active, lead_elapsed, voters, hb, tick_no, et=ET, seed=SEED):
     return act
 
 
-def campaigns(st, active, lead_elapsed, voters, hups, hup_cap, pre_vote, et=ET, plain_hup=False):
+def campaigns(st, active, lead_elapsed, voters, hups, hup_cap, pre_vote, et=ET, plain_hup=False, step=None):
     """Step(MsgHup) of the first hup_cap MsgHup groups with the switches on (the state MOVES) -> (every positional record of the vote
     section, keep [slots] bool, camp records, campaigned ids, the raw 64-byte results).
-    plain_hup (tests only): PreVote's rule 1 left out -- the MsgHup is stepped as a plain campaign."""
+    plain_hup (tests only): PreVote's rule 1 left out -- the MsgHup is stepped as a plain campaign.
+    step: msgs -> raftq_step_out_t[], for a caller whose handle has more switches on than the two (it moves the caller's state)."""
     from raftsql_amd import step as S
 
     N, me = st.N, st.self_peer
@@ -59,6 +60,8 @@ def campaigns(st, active, lead_elapsed, voters, hups, hup_cap, pre_vote, et=ET, 
     msgs = S.pack_msgs(built.astype(np.uint64), MSG_HUP)
     if len(built) == 0:
         outs = np.zeros(0, S.OUT_DT)
+    elif step is not None:
+        outs = step(msgs)
     elif active is None:  # both switches off: the statements the two references override
         outs = st.step_batch(msgs) if voters is None else V.step_batch(st, voters, msgs)
     elif pre_vote:

@@ -10,6 +10,11 @@ every move -- and holds, after EVERY move and after EVERY batch:
   the whole handle             tests/_stepgen.assert_same_state, read_voters, read_tick's role and elapsed, read_activity
   two what-if sweeps           RAFTQ_SWEEP_COMMIT | VOTES | CHANGED | NO_ADOPT, plain and gated: whole arrays, the changed list, the
                                tally -- what finds a self-max or narrow word left standing over rows that moved
+The cases with PreVote, leadership transfer, ReadIndex and the fused Tick calls on (ref_interleave.EXTENDED) also hold, after every
+move and every batch, raftq_read_transfer and -- in the safe mode -- raftq_read_reads' seq, acked and confirmed; their moves add
+raftq_load_transfer, raftq_load_reads, each switch turned off and on, a window without PreVote, raftq_tally_rebuild and every call the
+switches close.  The tally word is held one-sidedly in every case: true right behind its build, unchanged across every move whose
+contract keeps it, never asserted across a Step batch.
 That the batches can tell each move from its absence is shown on the reference alone by tests/test_interleave_ref.py."""
 import time
 
@@ -24,6 +29,9 @@ from tests import ref_interleave as I
 pytestmark = pytest.mark.gpu
 
 ANSWERED = 0x10  # RAFTQ_OUTF_ANSWERED
+# include/raftq.h, the tally mirror: Step and a voter delta that resets a slot end it until the next build.  Step is also what a
+# device-built election round and raftq_step_frames_respond run; a clone has its source's word; raftq_tally_rebuild may set it.
+TALLY_MAY_END = ("voter_deltas", "tick_elect", "respond", "clone", "tally_rebuild")
 STATE_FIELDS = ("term", "vote", "lead", "last_index", "last_term", "first_idx", "role", "elapsed", "committed")
 
 
@@ -43,12 +51,23 @@ def _engine(ref, loaded=True):
     s = ref.s
     e = WireEngine(s.G, s.N, s.self_peer)  # (msg_flags: raftq_step_set_msg_flags)
     e.set_timers(I.ET, I.HB, I.SEED)
+    if ref.ext:  # in front of the load: raftq_load_roles takes role 3 only under raftq_set_pre_vote
+        e.set_check_quorum(True)
+        e.set_pre_vote(ref.pv)
+        e.set_lead_transfer(ref.lt)
+        e.set_read_index(ref.ri)
+        if ref.checks:
+            e.set_tick_checks(s.G)
     if loaded:
         _stepgen.load_engine(e, s)
     if ref.cq:
         e.set_check_quorum(True)
         if loaded:
             e.load_activity(ref.active, ref.le)
+            if ref.lt:
+                e.load_transfer(ref.transferee)
+            if ref.ri == I.SAFE:
+                e.load_reads(ref.seq, ref.acked)
     e.set_step_props(True)
     e.set_respond_lead(True)
     e.set_respond_props(True)
@@ -77,6 +96,60 @@ def _held(e, ref, what):
         ac, le = e.read_activity()
         assert np.array_equal(ac, ref.active), f"{what}: active, {_first(ac, ref.active)}"
         assert np.array_equal(le, ref.le), f"{what}: lead_elapsed, {_first(le, ref.le)}"
+    _held_more(e, ref, what)
+
+
+def _held_more(e, ref, what):
+    """what the three switches hold: the transferees, and in the safe mode the read records with confirmed() over the voters Step runs over"""
+    if ref.lt:
+        tr = e.read_transfer()
+        assert np.array_equal(tr, ref.transferee), f"{what}: transferee, {_first(tr, ref.transferee)}"
+    if ref.ri == I.SAFE:
+        seq, acked, conf = e.read_reads()
+        assert np.array_equal(seq, ref.seq), f"{what}: seq, {_first(seq, ref.seq)}"
+        assert np.array_equal(acked, ref.acked), f"{what}: acked, {_first(acked, ref.acked)}"
+        want = I.RI.confirmed_of(ref.extra, ref.voters, ref.s.N)
+        assert np.array_equal(conf, want), f"{what}: confirmed, {_first(conf, want)}"
+
+
+def _refused_with(f, word, what):
+    from raftsql_amd._lib import RAFTQ_ESTATE
+    from raftsql_amd.engine import RaftqError
+
+    with pytest.raises(RaftqError) as ei:
+        f()
+    assert ei.value.code == RAFTQ_ESTATE and word in str(ei.value), f"{what}: expected RAFTQ_ESTATE naming '{word}', got {ei.value.code}: {ei.value}"
+
+
+def _closed(e, mv, ref, what):
+    """every call the case's switches close is refused with its word (the handle is then held unchanged by the caller's _held)"""
+    from tests import test_tick_elect_gpu as TE
+    from tests import test_tick_frames_gpu as TF
+
+    a, s = mv.args, ref.s
+    bf, be = TF.Bufs(e, s.G), TE.Bufs(e, s.G, s.G)
+    frames = lambda: e.tick_frames(bf.out, bf.off[: bf.n_max + 1], bf.po, s.G, cap=bf.cap)  # noqa: E731
+    elect = lambda: e.tick_elect_frames(be.camp[: s.G], be.out, be.off[: be.n_max + 1], be.po, s.G, s.G, cap=be.cap)  # noqa: E731
+
+    def propose():
+        room = (s.N - 1) * (len(a["pool"]) + 64 * len(a["pe"])) + 128 * len(a["props"]) * (s.N - 1) + 4096
+        _refusals.ProposeArgs(a["props"], a["pe"], a["pool"], a["hm"], a["he"], s.N, room).whole(e)
+
+    calls = {"tick_collect": e.tick_collect, "tick_collect_lists": e.tick_collect_lists, "tick_frames": frames, "tick_elect_frames": elect,
+             "propose_frames": propose, "set_check_quorum(0)": lambda: e.set_check_quorum(False)}
+    tick_before = e.read_tick()
+    for name, word in a["calls"]:
+        opened = name.endswith("+checks")
+        if opened:  # raftq_tick_set_checks lets the call past CheckQuorum and PreVote: what is left is the safe mode's refusal
+            e.set_tick_checks(s.G)
+        try:
+            _refused_with(calls[name.split("+")[0]], word, f"{what}: {name}")
+        finally:
+            if opened:
+                e.set_tick_checks(0)
+    for x, y in zip(tick_before, e.read_tick()):
+        assert np.array_equal(x, y), f"{what}: a refused Tick call ticked"
+    assert bf.canaries_ok() and (be.out == be.out[0]).all(), f"{what}: a refused call wrote"
 
 
 def _what_if(e, ref, what):
@@ -114,6 +187,9 @@ def _tick_lists(e, mv, hups, nh, second, nb, what):
     assert (nh, nb) == (w["n_hup"], w["n_beat"]), f"{what}: tick counts {(nh, nb)}, want {(w['n_hup'], w['n_beat'])}"
     assert np.array_equal(hups, w["hups"]) and np.array_equal(second, w["beats"]), f"{what}: tick lists"
     assert np.array_equal(e.read_tick()[0], w["action"]), f"{what}: tick actions, {_first(e.read_tick()[0], w['action'])}"
+    if "checks" in w:  # under raftq_tick_set_checks: the third list, left in place
+        ids, n = e.last_tick_checks()
+        assert n == len(w["checks"]) and np.array_equal(ids, w["checks"]), f"{what}: the list of failed checks, {n} of them, want {len(w['checks'])}"
 
 
 def _frames(got_s, got_po, c, b, n_max, mv, what):
@@ -216,6 +292,7 @@ def _apply(e, mv, ref, what):
         if ref.cq:
             ac, le = new.read_activity()
             assert np.array_equal(ac, ref.active) and np.array_equal(le, ref.le), f"{what}: the activity words the clone copied"
+        _held_more(new, ref, f"{what}: what the clone copied")  # (the transferee travels with the word, the records with the handle)
         new.load_roles(s.role, s.elapsed)
         new.load_node(s.term, s.vote, s.lead, s.last_index, s.last_term)
         if ref.cq:
@@ -235,6 +312,24 @@ def _apply(e, mv, ref, what):
     elif kind == "cq_toggle":
         e.set_check_quorum(False)
         e.set_check_quorum(True)
+    elif kind == "transfer":
+        e.load_transfer(a["transferee"])
+    elif kind == "reads":
+        e.load_reads(a["seq"], a["acked"])
+    elif kind == "lt_toggle":
+        e.set_lead_transfer(False)
+        e.set_lead_transfer(True)
+    elif kind == "ri_toggle":
+        e.set_read_index(a["other"])
+        e.set_read_index(ref.ri)
+    elif kind == "pv_off":
+        e.set_pre_vote(False)
+    elif kind == "pv_on":
+        e.set_pre_vote(True)
+    elif kind == "tally_rebuild":
+        assert e.tally_rebuild() and e.tally(), f"{what}: the tally word right behind its build"
+    elif kind == "closed":
+        _closed(e, mv, ref, what)
     else:
         raise AssertionError(kind)
     return e
@@ -253,7 +348,10 @@ def test_every_writer_interleaved_with_step(oracle, gpu_engine_cls, monkeypatch,
         _held(e, sch.start, f"{case}: the loaded state")
         for k, mv in enumerate(sch.moves):
             what = f"{case}, move {k} ({mv.kind})"
+            tally = e.tally()
             e = _apply(e, mv, mv.after, what)
+            if mv.kind not in TALLY_MAY_END:  # (never asserted across a Step batch: Step ends the mirror by contract)
+                assert e.tally() == tally, f"{what}: the tally word was {tally} in front of the move and is {e.tally()} behind it"
             _held(e, mv.after, f"{what}: behind the move")
             _what_if(e, mv.after, f"{what}: behind the move")
             if len(mv.batches) == 1:
