@@ -347,3 +347,87 @@ def step_run(band, N, me, hold_skip=False, G=STEP_G):
         batches.append((m, want, (pre.last_index, pre.committed), pre))
     guard(s.term, s.last_term, s.last_index, s.committed, s.first_idx, s.match)
     return start, batches, s
+
+
+# ---- what the switch suites' band cases share (tests/ref_check_quorum.py, ref_pre_vote.py, ref_lead_transfer.py, ref_read_index.py) -------
+MSG_U64 = ("term", "index", "log_term", "commit", "reject_hint")
+STATE_U64 = ("term", "last_term", "last_index", "committed", "first_idx")
+OWN_KINDS = tuple(range(12, 19))  # MsgCheckQuorum .. MsgPreVoteResp: the kinds only the *_cq_* kernels take
+DECIDED = ("type", "reject", "flags", "role")
+
+
+def band_edge(band):
+    """the band's boundary B, or -- "top" -- its lower edge"""
+    return TOP_LO if band == "top" else BANDS[band]
+
+
+def band_floor(band):
+    """what the largest term and index of a run in the band cannot lie below: lift() draws within 3 / 6 of B"""
+    return (TOP_LO, TOP_LO) if band == "top" else (BANDS[band] - 3, BANDS[band] - 6)
+
+
+def far(band, v):
+    """v + 2^32, or v - 2^32 where that would pass the guard ("top"): alias_table's"""
+    return v - 2**32 if band == "top" else v + 2**32
+
+
+def set_term(s, groups, term):
+    """groups' term := term, their last entry's term kept at or below it (a leader's: the term itself)"""
+    s.term[groups] = term
+    s.last_term[groups] = np.where(s.role[groups] == 2, s.term[groups], np.minimum(s.last_term[groups], s.term[groups]))
+
+
+def guard_case(s, m):
+    guard(*(getattr(s, k) for k in STATE_U64), s.match, *(m[k] for k in MSG_U64))
+
+
+def low32(s, m):
+    """-> copies of a state and a batch with every 64-bit word reduced mod 2^32: what a walk that kept 32 bits of them would read"""
+    lo = U(0xFFFFFFFF)
+    n = V.copy_state(s)
+    for k in STATE_U64:
+        getattr(n, k)[:] = getattr(s, k) & lo
+    n.match[:] = s.match & lo
+    m = np.array(m)
+    for k in MSG_U64:
+        m[k] = m[k] & lo
+    return n, m
+
+
+def decided_otherwise(a, b):
+    """-> bool[n]: the records of two runs that differ in (type, reject, flags, role)"""
+    return np.logical_or.reduce([a[k] != b[k] for k in DECIDED])
+
+
+def straddles(s, m, boundary=2**63):
+    """-> bool[n], from the inputs alone: m.term and the group's term, or m.index and the group's tail, on opposite sides of the
+    boundary.  A 0 is "none" on either side; a heartbeat's index is a context, not a position."""
+    g = m["group"].astype(np.int64)
+    b = U(boundary)
+    t = (m["term"] != 0) & (s.term[g] != 0) & ((m["term"] < b) != (s.term[g] < b))
+    pos = ~np.isin(m["type"], (8, 9))
+    i = pos & (m["index"] != 0) & (s.last_index[g] != 0) & ((m["index"] < b) != (s.last_index[g] < b))
+    return t | i
+
+
+def check_narrow_reading(m, want, want32, own_kinds, what=""):
+    """a b32 case: the reference over the same start and batch reduced mod 2^32 (want32) decides at least one record in ten
+    otherwise, eight of them of the switch's own kinds -> (share, own)"""
+    d = decided_otherwise(want, want32)
+    share, own = float(d.mean()), int((d & np.isin(m["type"], own_kinds)).sum())
+    assert share >= 0.10 and own >= 8, (what, share, own)
+    return share, own
+
+
+def check_straddles(s, m, own_kinds, plant, what=""):
+    """a b63 case, from the inputs alone: one record in twenty compares across 2^63, `plant` of them of the switch's own kinds"""
+    st = straddles(s, m)
+    share, own = float(st.mean()), int((st & np.isin(m["type"], own_kinds)).sum())
+    assert share >= 0.05 and own >= plant, (what, share, own)
+    return share, own
+
+
+def check_in_band(band, want, what=""):
+    """the case is where it says: the largest term and index of its results are at or above the band's lower edge"""
+    t, i = band_floor(band)
+    assert int(want["term"].max()) >= t and int(max(want["index"].max(), want["last_index"].max())) >= i, what

@@ -16,6 +16,7 @@ import numpy as np
 
 from oracle import pyoracle
 from tests import _stepgen
+from tests import _widegen as WG
 from tests import ref_raft_py as R
 from tests import ref_step_props as P
 from tests import ref_step_voters as V
@@ -217,6 +218,7 @@ def tick_input(g, n, self_peer, election_tick, seed, masks=False):
 
 # ---- the Step inputs ---------------------------------------------------------------------------------------------------------------
 G, N_MSGS = 194, 512  # (ref_step_props.props_state deals 60 led groups and 60 followers of a peer at this size)
+OWN_KINDS = (MsgCheckQuorum, R.MsgVote)  # the kinds its rules decide: the check itself, and the vote the lease rule (3) ignores
 SHAPES = ((1, 0), (3, 0), (5, 4), (9, 8))
 PLANT = 6
 
@@ -227,7 +229,7 @@ def _rec(m, at, group, type, term=0, frm=0, index=0, log_term=0, reject=0):
     m["index"][at], m["log_term"][at], m["reject"][at] = index, log_term, reject
 
 
-def step_case(n, self_peer, seed, masks=False, hot=False, g=G, n_msgs=N_MSGS):
+def step_case(n, self_peer, seed, masks=False, hot=False, g=G, n_msgs=N_MSGS, band=None, plants=None):
     """one (start state, voters | None, active, lead_elapsed, batch, the reference's records, (state, active, lead_elapsed) after).
     ref_step_props.props_state's dealt roles with elapsed on both sides of election_tick and random activity words; its traffic with one record in
     seven turned into a MsgCheckQuorum; in front, per kind PLANT groups with one directed exchange each:
@@ -238,9 +240,14 @@ def step_case(n, self_peer, seed, masks=False, hot=False, g=G, n_msgs=N_MSGS):
       led                       a MsgVote of the next term: in lease, ignored
       following, elapsed 0      a MsgVote of the next term: in lease, ignored
       following, elapsed past   the same: out of lease, answered
-    `hot`: a led group with 40 acknowledgements and checks in a row (a run longer than the list walk takes)."""
+    `hot`: a led group with 40 acknowledgements and checks in a row (a run longer than the list walk takes).
+    band: the state lifted by tests/_widegen first and the traffic drawn by its wide_batch; in
+    b32 / b63 the three MsgVote sets stand at term B - 1, so that the vote "of the next term" is B: ignored in the lease (the term
+    stays B - 1), granted past it (the term becomes B).  plants: a dict that is told these groups."""
     rng = np.random.default_rng(seed)
     s = P.props_state(rng, n, self_peer, g)
+    if band is not None:
+        s = WG.lift(s, band, rng)
     s.elapsed[:] = rng.integers(0, 2 * ELECTION_TICK, g)
     full = (1 << n) - 1
     active = rng.integers(0, full + 1, g).astype(np.uint16)
@@ -263,7 +270,16 @@ def step_case(n, self_peer, seed, masks=False, hot=False, g=G, n_msgs=N_MSGS):
     active[sets[0]], active[sets[1]], active[sets[2]], active[sets[3]] = full, 0, 0, full
     in_lease, out_lease = fol[:PLANT], fol[PLANT:2 * PLANT]
     s.elapsed[in_lease], s.elapsed[out_lease] = 0, ELECTION_TICK + 3
-    m = _stepgen.random_batch(rng, s, n_msgs)
+    planted = np.concatenate(sets + [in_lease, out_lease, led[5 * PLANT:5 * PLANT + 3]])
+    free = np.setdiff1d(np.arange(g), planted)
+    if band is None:
+        m = _stepgen.random_batch(rng, s, n_msgs)
+    else:
+        if WG.BANDS[band]:
+            WG.set_term(s, np.concatenate([sets[4], in_lease, out_lease]), WG.BANDS[band] - 1)
+        m = WG.wide_batch(rng, s, n_msgs)
+    if plants is not None:
+        plants.update(led=sets[4], in_lease=in_lease, out_lease=out_lease)
     others = [(self_peer + 1 + k) % n for k in range(n - 1)]
     at = 0
     for grp in sets[0]:
@@ -282,8 +298,6 @@ def step_case(n, self_peer, seed, masks=False, hot=False, g=G, n_msgs=N_MSGS):
         _rec(m, at, grp, MsgCheckQuorum); at += 1
     assert at < n_msgs // 2
     rest = np.arange(at, n_msgs)
-    planted = np.concatenate(sets + [in_lease, out_lease, led[5 * PLANT:5 * PLANT + 3]])
-    free = np.setdiff1d(np.arange(g), planted)
     m["group"][rest] = rng.choice(free, len(rest))  # (the directed exchanges stay undisturbed)
     if hot:
         for j, i in enumerate(rest[:40]):
@@ -295,7 +309,11 @@ def step_case(n, self_peer, seed, masks=False, hot=False, g=G, n_msgs=N_MSGS):
     for i in rest[rng.random(len(rest)) < 1 / 7]:
         _rec(m, i, int(m["group"][i]), MsgCheckQuorum, frm=int(rng.integers(0, 256)))  # (`from` is ignored on a local kind)
     start = (V.copy_state(s), active.copy(), lead_elapsed.copy())
+    if band is not None:
+        WG.guard_case(s, m)
     want = step_batch(s, voters, active, lead_elapsed, m)
+    if band is not None:
+        WG.guard_case(s, m)
     for a in (m, want):
         a.setflags(write=False)
     return start, voters, m, want, (s, active, lead_elapsed)
@@ -346,4 +364,12 @@ def case_list():
         cases.append(dict(n=n, self_peer=me, seed=9510 + n, masks=True))
     cases.append(dict(n=3, self_peer=1, seed=9520, hot=True))
     cases.append(dict(n=5, self_peer=0, seed=9521, hot=True, masks=True))
+    for k, band in enumerate(WG.BAND_NAMES):  # appended: the positions above are what the GPU tests pick by
+        cases.append(dict(n=3, self_peer=0, seed=9530 + k, band=band))
+        cases.append(dict(n=9, self_peer=8, seed=9540 + k, masks=True, band=band))
     return cases
+
+
+def case_id(c):
+    return "n%d-self%d%s%s%s" % (c["n"], c["self_peer"], "-masks" if c.get("masks") else "", "-hot" if c.get("hot") else "",
+                                 "-" + c["band"] if c.get("band") else "")

@@ -20,6 +20,7 @@ import numpy as np
 
 from oracle import pyoracle
 from tests import _stepgen
+from tests import _widegen as WG
 from tests import ref_check_quorum as Q
 from tests import ref_pre_vote as PV
 from tests import ref_raft_py as R
@@ -198,7 +199,7 @@ def _prop(m, at, group, k=1, frm=0):
     P._prop(m, at, group, k, frm=frm)
 
 
-def step_case(n, self_peer, seed, masks=False, pre_vote=True, hot=False, g=G, n_msgs=N_MSGS):
+def step_case(n, self_peer, seed, masks=False, pre_vote=True, hot=False, g=G, n_msgs=N_MSGS, band=None, plants=None):
     """one (start = (state, active, lead_elapsed, transferee), voters | None, batch, the reference's records, the four after).
     ref_step_props.props_state's dealt roles (with pre_vote every third candidate a pre-candidate), elapsed on both sides of
     election_tick, a pending transferee in one led group of three, and _stepgen's traffic with one record in six turned into a
@@ -224,9 +225,18 @@ def step_case(n, self_peer, seed, masks=False, pre_vote=True, hot=False, g=G, n_
       led                       MsgTimeoutNow: ignored
     masks: the planted groups vote in full, but for PLANT led groups whose `last` is no voter (ignored), PLANT followers in which
     self is no voter (MsgTimeoutNow: OUT_NONE) and PLANT in which self is the ONE voter (OUT_BECAME_LEADER).
-    `hot`: a led group with 40 records in a row -- MsgTransferLeader, acks from every peer, MsgProps, a cancel, again."""
+    `hot`: a led group with 40 records in a row -- MsgTransferLeader, acks from every peer, MsgProps, a cancel, again.
+    band: the state lifted by tests/_widegen first and the traffic drawn by its wide_batch.  Five
+    more led groups with the tail at B (b32 / b63; "top": where the lift put it) and none pending get MsgTransferLeader(last):
+      Match == tail             OUT_TRANSFER with TIMEOUT_NOW at once
+      Match == far(tail)        2^32 away (tests/_widegen.far), the low words equal: OUT_TRANSFER, no flag
+      Match == tail - 1         no flag; the acknowledgement that moves it to the tail carries TIMEOUT_NOW
+    and in b32 / b63 the `tn_up` followers stand at term B - 1: the MsgTimeoutNow of the next term is B.  plants: a dict that is
+    told these groups."""
     rng = np.random.default_rng(seed)
     s = P.props_state(rng, n, self_peer, g)
+    if band is not None:
+        s = WG.lift(s, band, rng)
     s.elapsed[:] = rng.integers(0, 2 * ELECTION_TICK, g)
     if pre_vote:
         cand = np.flatnonzero(s.role == 1)
@@ -261,8 +271,11 @@ def step_case(n, self_peer, seed, masks=False, pre_vote=True, hot=False, g=G, n_
     in_m, in_u, out_l, fwd, tn_own, tn_up = F[0][:H], F[0][H:], F[1], F[2], F[3], F[4]
     self_out, self_only = (F[5], F[6]) if masks else (fol[:0], fol[:0])
     lost_p, cnd_p = lost[:PLANT], cnd[:PLANT]
+    wide = rest_led[6 * T + 1 + len(non_voter_t):][:5] if band is not None else led[:0]
+    assert len(wide) == (5 if band is not None else 0), len(led)
+    at_tail, far_off, by_ack = wide[:1], wide[1:3], wide[3:]
     planted = np.concatenate([S1, S2, S3, S4, rst, chk_pass, chk_fail, [hot_group], led_vote_m, led_vote_u, led_tn, non_voter_t, F[0], out_l, fwd,
-                              tn_own, tn_up, self_out, self_only, lost_p, cnd_p])
+                              tn_own, tn_up, self_out, self_only, lost_p, cnd_p, wide])
     assert len(np.unique(planted)) == len(planted)
     if masks:
         voters[planted] = full
@@ -286,7 +299,22 @@ def step_case(n, self_peer, seed, masks=False, pre_vote=True, hot=False, g=G, n_
     s.elapsed[F[0]], s.elapsed[out_l] = 0, ELECTION_TICK + 3
     s.term[fwd] = np.maximum(s.term[fwd], 2)
     s.last_term[fwd] = np.minimum(s.last_term[fwd], s.term[fwd])
-    m = _stepgen.random_batch(rng, s, n_msgs)
+    free = np.setdiff1d(np.arange(g), planted)
+    if band is None:
+        m = _stepgen.random_batch(rng, s, n_msgs)
+    else:
+        if WG.BANDS[band]:
+            s.last_index[wide] = s.match[self_peer, wide] = WG.BANDS[band]
+            s.committed[wide] = np.minimum(s.committed[wide], s.last_index[wide])
+            WG.set_term(s, tn_up, WG.BANDS[band] - 1)
+        s.match[:, wide] = np.where(np.arange(n)[:, None] == self_peer, s.last_index[wide][None, :], s.last_index[wide][None, :] - np.uint64(3))
+        s.match[last, at_tail] = s.last_index[at_tail]
+        s.match[last, far_off] = [WG.far(band, int(v)) for v in s.last_index[far_off]]
+        s.match[last, by_ack] = s.last_index[by_ack] - np.uint64(1)
+        transferee[wide] = 0
+        m = WG.wide_batch(rng, s, n_msgs)
+    if plants is not None:
+        plants.update(at_tail=at_tail, far=far_off, by_ack=by_ack, tn_up=tn_up, last=last)
     at = 0
 
     def put(*a, **kw):
@@ -352,9 +380,12 @@ def step_case(n, self_peer, seed, masks=False, pre_vote=True, hot=False, g=G, n_
     for grp in cnd_p:
         put(grp, MsgTransferLeader, frm=last)
         put(grp, MsgTimeoutNow, term=int(s.term[grp]), frm=other)
+    for grp in wide:
+        put(grp, MsgTransferLeader, frm=last)
+    for grp in by_ack:
+        put(grp, R.MsgAppResp, term=int(s.term[grp]), frm=last, index=int(s.last_index[grp]))
     assert at < n_msgs * 3 // 5, at
     rest = np.arange(at, n_msgs)
-    free = np.setdiff1d(np.arange(g), planted)
     m["group"][rest] = rng.choice(free, len(rest))  # (the directed exchanges stay undisturbed)
     if hot:
         t0, li = int(s.term[hot_group]), int(s.last_index[hot_group])
@@ -381,7 +412,11 @@ def step_case(n, self_peer, seed, masks=False, pre_vote=True, hot=False, g=G, n_
     for i in rest[rng.random(len(rest)) < 0.1]:
         _prop(m, i, int(m["group"][i]), int(rng.integers(1, 4)), frm=int(rng.integers(0, n)))
     start = (V.copy_state(s), active.copy(), lead_elapsed.copy(), transferee.copy())
+    if band is not None:
+        WG.guard_case(s, m)
     want, _ = step_batch(s, voters, active, lead_elapsed, transferee, m, pre_vote)
+    if band is not None:
+        WG.guard_case(s, m)
     for a in (m, want):
         a.setflags(write=False)
     return start, voters, m, want, (s, active, lead_elapsed, transferee)
@@ -396,11 +431,14 @@ def case_list():
                 cases.append(dict(n=n, self_peer=me, seed=10500 + 4 * k + 2 * masks + pv, masks=masks, pre_vote=pv))
     cases.append(dict(n=3, self_peer=1, seed=10540, hot=True))
     cases.append(dict(n=9, self_peer=0, seed=10541, hot=True, masks=True, pre_vote=False))
+    for k, band in enumerate(WG.BAND_NAMES):  # appended: the positions above are what the GPU tests pick by
+        cases.append(dict(n=3, self_peer=0, seed=10550 + k, pre_vote=bool(k & 1), band=band))
+        cases.append(dict(n=9, self_peer=8, seed=10560 + k, masks=True, pre_vote=not k & 1, band=band))
     return cases
 
 
 def case_id(c):
-    return "n%d-self%d%s%s%s" % (c["n"], c["self_peer"], "-masks" if c.get("masks") else "", "-pv" if c.get("pre_vote", True) else "", "-hot" if c.get("hot") else "")
+    return "n%d-self%d%s%s%s" % (c["n"], c["self_peer"], "-masks" if c.get("masks") else "", "-pv" if c.get("pre_vote", True) else "", "-hot" if c.get("hot") else "") + ("-" + c["band"] if c.get("band") else "")
 
 
 def case_rules(c):

@@ -18,6 +18,7 @@ import numpy as np
 
 from oracle import pyoracle
 from tests import _stepgen
+from tests import _widegen as WG
 from tests import ref_check_quorum as Q
 from tests import ref_raft_py as R
 from tests import ref_step_props as P
@@ -153,7 +154,7 @@ def _rec(m, at, group, type, term=0, frm=0, index=0, log_term=0, reject=0, flags
     m["_pad"][at] = (0, flags)
 
 
-def step_case(n, self_peer, seed, masks=False, hot=False, g=G, n_msgs=N_MSGS):
+def step_case(n, self_peer, seed, masks=False, hot=False, g=G, n_msgs=N_MSGS, band=None, plants=None):
     """one (start state, voters | None, batch, the reference's records, (state, active, lead_elapsed) after).
     ref_step_props.props_state's dealt roles -- every third candidate made a pre-candidate --, elapsed on both sides of
     election_tick, and _stepgen's traffic with half the MsgVote / MsgVoteResp records turned into their pre-election kinds (so every
@@ -167,9 +168,15 @@ def step_case(n, self_peer, seed, masks=False, hot=False, g=G, n_msgs=N_MSGS):
       following             a MsgHeartbeat and a MsgApp (barrier, entries) of the term before, then a MsgPreVote of it: TERM_RESP twice, a rejection
       led                   a MsgPreVote of the next term (ignored) and one of the own (rejected: the log is behind)
       candidate             a MsgPreVoteResp (ignored) and a MsgPreVote of the own term
-    `hot`: a group following nobody with 40 records in a row -- MsgHup, then responses of both kinds from every peer, again and again."""
+    `hot`: a group following nobody with 40 records in a row -- MsgHup, then responses of both kinds from every peer, again and again.
+    band: the state lifted by tests/_widegen first and the traffic drawn by its wide_batch; in
+    b32 / b63 the `win`, `bump`, in-lease, out-of-lease and led groups stand at term B - 1 -- the MsgPreVote or MsgPreVoteResp "of the
+    next term" is B, "two up" beyond it -- and the stale groups at term B: their TERM_RESP answers the term before from across the
+    boundary.  plants: a dict that is told these groups."""
     rng = np.random.default_rng(seed)
     s = P.props_state(rng, n, self_peer, g)
+    if band is not None:
+        s = WG.lift(s, band, rng)
     s.elapsed[:] = rng.integers(0, 2 * ELECTION_TICK, g)
     cand = np.flatnonzero(s.role == 1)
     s.role[cand[::3]] = PRE
@@ -195,7 +202,16 @@ def step_case(n, self_peer, seed, masks=False, hot=False, g=G, n_msgs=N_MSGS):
     s.elapsed[in_lease], s.elapsed[out_lease] = 0, ELECTION_TICK + 3
     s.term[stale] = np.maximum(s.term[stale], 2)
     s.last_term[stale] = np.minimum(s.last_term[stale], s.term[stale])
-    m = _stepgen.random_batch(rng, s, n_msgs)
+    free = np.setdiff1d(np.arange(g), planted)
+    if band is None:
+        m = _stepgen.random_batch(rng, s, n_msgs)
+    else:
+        if WG.BANDS[band]:
+            WG.set_term(s, np.concatenate([win, bump, in_lease, out_lease, led_p]), WG.BANDS[band] - 1)
+            WG.set_term(s, stale, WG.BANDS[band])
+        m = WG.wide_batch(rng, s, n_msgs)
+    if plants is not None:
+        plants.update(win=win, bump=bump, in_lease=in_lease, out_lease=out_lease, stale=stale, led=led_p)
     others = [(self_peer + 1 + k) % n for k in range(n - 1)]
     peer = others[0] if others else 0
     q = n // 2 + 1
@@ -226,7 +242,6 @@ def step_case(n, self_peer, seed, masks=False, hot=False, g=G, n_msgs=N_MSGS):
         _rec(m, at, grp, MsgPreVote, term=int(s.term[grp]), frm=peer, index=int(s.last_index[grp]) + 5, log_term=int(s.term[grp])); at += 1
     assert at < n_msgs // 2, at
     rest = np.arange(at, n_msgs)
-    free = np.setdiff1d(np.arange(g), planted)
     m["group"][rest] = rng.choice(free, len(rest))  # (the directed exchanges stay undisturbed)
     if hot:
         t0 = int(s.term[hot_group])
@@ -245,7 +260,11 @@ def step_case(n, self_peer, seed, masks=False, hot=False, g=G, n_msgs=N_MSGS):
     for i in rest[rng.random(len(rest)) < 0.1]:
         _rec(m, i, int(m["group"][i]), Q.MsgCheckQuorum, frm=int(rng.integers(0, 256)))
     start = (V.copy_state(s), active.copy(), lead_elapsed.copy())
+    if band is not None:
+        WG.guard_case(s, m)
     want = step_batch(s, voters, active, lead_elapsed, m)
+    if band is not None:
+        WG.guard_case(s, m)
     for a in (m, want):
         a.setflags(write=False)
     return start, voters, m, want, (s, active, lead_elapsed)
@@ -259,7 +278,13 @@ def case_list():
         cases.append(dict(n=n, self_peer=me, seed=9810 + n, masks=True))
     cases.append(dict(n=3, self_peer=1, seed=9820, hot=True))
     cases.append(dict(n=5, self_peer=0, seed=9821, hot=True, masks=True))
+    for k, band in enumerate(WG.BAND_NAMES):  # appended: the positions above are what the GPU tests pick by
+        cases.append(dict(n=3, self_peer=0, seed=9830 + k, band=band))
+        cases.append(dict(n=9, self_peer=8, seed=9840 + k, masks=True, band=band))
     return cases
+
+
+case_id = Q.case_id
 
 
 def changed_records(start, voters, m, want, after, rule):

@@ -21,6 +21,7 @@ import numpy as np
 
 from oracle import pyoracle
 from tests import _stepgen
+from tests import _widegen as WG
 from tests import ref_check_quorum as Q
 from tests import ref_lead_transfer as T
 from tests import ref_pre_vote as PV
@@ -323,7 +324,7 @@ def _rec(m, at, group, type, term=0, frm=0, index=0, log_term=0, reject=0, flags
     PV._rec(m, at, group, type, term, frm, index, log_term, reject, flags)
 
 
-def step_case(n, self_peer, seed, mode=SAFE, masks=False, pre_vote=True, lead_transfer=True, hot=False, g=G, n_msgs=N_MSGS):
+def step_case(n, self_peer, seed, mode=SAFE, masks=False, pre_vote=True, lead_transfer=True, hot=False, g=G, n_msgs=N_MSGS, band=None, plants=None):
     """one (start = (state, Extra), voters | None, batch, the reference's records, (state, Extra) after).
     ref_step_props.props_state's dealt roles over g groups, led groups with a read record (seq up to 5, every acked word <= seq), and
     _stepgen's traffic in which every MsgHeartbeat / MsgHeartbeatResp carries a small context and one record in five is turned into
@@ -349,9 +350,20 @@ def step_case(n, self_peer, seed, mode=SAFE, masks=False, pre_vote=True, lead_tr
     masks: the planted groups vote in full, but for PLANT led groups in which self is the ONE voter (released at once; then a MsgApp
     of the next term, a MsgHup that wins on its own grant, and an acknowledgement that finds c > seq on the fresh record) and PLANT
     led groups whose `last` is no voter (its acknowledgement is stored and does not count).
-    `hot`: a led group with 40 records in a row -- three requests and their acknowledgements out of order, with a duplicate."""
+    `hot`: a led group with 40 records in a row -- three requests and their acknowledgements out of order, with a duplicate.
+    band: the state lifted by tests/_widegen first and the traffic drawn by its wide_batch, one
+    heartbeat context in eight moved up by 2^32, a MsgReadIndexResp's index around the group's tail.  The plants above, changed:
+      led, gate open            (the first two sets) committed = tail - 1; first_idx == committed in one half, == committed - 2^32 in
+                                the other (b32: the tail raised to 2^32 + 2 for it)
+      led, gate closed          the last group's first_idx == committed + 2^32 (not under "top": it would pass the guard)
+      led, seq 3                three more acknowledgements, of 2^32 + 1, 2^32 and 2^63 + 2: beyond seq, nothing stored or released
+      following, candidate      the MsgHeartbeat's context is 2^32 + 7: echoed whole
+      following                 the MsgReadIndexResp's index is the lifted committed (or, where that is below 2^32, the band's edge + k)
+    plants: a dict that is told these groups."""
     rng = np.random.default_rng(seed)
     s = P.props_state(rng, n, self_peer, g)
+    if band is not None:
+        s = WG.lift(s, band, rng)
     s.elapsed[:] = rng.integers(0, 2 * ELECTION_TICK, g)
     if pre_vote:
         cand = np.flatnonzero(s.role == 1)
@@ -405,7 +417,25 @@ def step_case(n, self_peer, seed, mode=SAFE, masks=False, pre_vote=True, lead_tr
     x.active[chk_pass], x.active[chk_fail] = full, 0
     s.term[rstate] = np.maximum(s.term[rstate], 2)
     s.last_term[rstate] = np.minimum(s.last_term[rstate], s.term[rstate])
-    m = _stepgen.random_batch(rng, s, n_msgs)
+    free = np.setdiff1d(np.arange(g), planted)
+    ctx = lambda small: small if band is None else 2**32 + 7  # noqa: E731
+    read_at = {int(grp): 11 + k for k, grp in enumerate(rstate)}
+    if band is None:
+        m = _stepgen.random_batch(rng, s, n_msgs)
+    else:
+        H = PLANT // 2
+        same, apart = np.concatenate([quorum[:H], resend[:H]]), np.concatenate([quorum[H:], resend[H:]])
+        s.last_index[apart] = np.maximum(s.last_index[apart], np.uint64(2**32 + 2))
+        s.match[self_peer, apart] = s.last_index[apart]
+        both = np.concatenate([same, apart])
+        s.committed[both] = s.last_index[both] - np.uint64(1)
+        s.first_idx[same], s.first_idx[apart] = s.committed[same], s.committed[apart] - np.uint64(2**32)
+        if band != "top":
+            s.first_idx[closed[-1]] = s.committed[closed[-1]] + np.uint64(2**32)
+        read_at = {int(grp): int(s.committed[grp]) if s.committed[grp] >= 2**32 else WG.band_edge(band) + k for k, grp in enumerate(rstate)}
+        m = WG.wide_batch(rng, s, n_msgs)
+        if plants is not None:
+            plants.update(same=same, apart=apart, closed=closed, beyond=beyond, fwd=fwd, cnd=cnd_p, rstate=rstate, read_at=read_at)
     at = 0
 
     def put(*a, **kw):
@@ -449,6 +479,9 @@ def step_case(n, self_peer, seed, mode=SAFE, masks=False, pre_vote=True, lead_tr
         t = int(s.term[grp])
         put(grp, R.MsgHeartbeatResp, term=t, frm=other, index=5)
         put(grp, R.MsgHeartbeatResp, term=t, frm=other, index=0)
+        if band is not None:
+            for c in (2**32 + 1, 2**32, 2**63 + 2):
+                put(grp, R.MsgHeartbeatResp, term=t, frm=last, index=c)
     for grp in distinct:
         t = int(s.term[grp])
         put(grp, R.MsgHeartbeatResp, term=t, frm=last, index=19)
@@ -470,21 +503,20 @@ def step_case(n, self_peer, seed, mode=SAFE, masks=False, pre_vote=True, lead_tr
     for k, grp in enumerate(fwd):
         t = int(s.term[grp])
         put(grp, MsgReadIndex, term=t if k % 2 else 0, frm=self_peer if k < 2 else other)
-        put(grp, R.MsgHeartbeat, term=t, frm=int(s.lead[grp]) - 1, index=7 + k)
+        put(grp, R.MsgHeartbeat, term=t, frm=int(s.lead[grp]) - 1, index=ctx(7 + k))
     for k, grp in enumerate(rstate):
         t = int(s.term[grp])
         put(grp, MsgReadIndexResp, term=t - 1, frm=other, index=9)
-        put(grp, MsgReadIndexResp, term=t + (k % 2), frm=int(s.lead[grp]) - 1, index=11 + k)
+        put(grp, MsgReadIndexResp, term=t + (k % 2), frm=int(s.lead[grp]) - 1, index=read_at[int(grp)])
     for grp in lost_p:
         put(grp, MsgReadIndex, frm=self_peer)
     for grp in cnd_p:
         t = int(s.term[grp])
         put(grp, MsgReadIndex, frm=self_peer)
         put(grp, MsgReadIndexResp, term=t, frm=other, index=3)
-        put(grp, R.MsgHeartbeat, term=t, frm=other, index=5)
+        put(grp, R.MsgHeartbeat, term=t, frm=other, index=ctx(5))
     assert at < n_msgs * 3 // 5, at
     rest = np.arange(at, n_msgs)
-    free = np.setdiff1d(np.arange(g), planted)
     m["group"][rest] = rng.choice(free, len(rest))  # (the directed exchanges stay undisturbed)
     if hot:
         t0 = int(s.term[hot_group])
@@ -499,11 +531,15 @@ def step_case(n, self_peer, seed, mode=SAFE, masks=False, pre_vote=True, lead_tr
         rest = rest[40:]
     beats = rest[np.isin(m["type"][rest], (R.MsgHeartbeat, R.MsgHeartbeatResp))]
     m["index"][beats] = rng.integers(0, 7, len(beats))
+    if band is not None:
+        m["index"][beats] += np.where(rng.random(len(beats)) < 0.125, np.uint64(2**32), np.uint64(0))
     for i in rest[rng.random(len(rest)) < 0.2]:
         grp = int(m["group"][i])
         kind = MsgReadIndex if rng.random() < 0.6 else MsgReadIndexResp
         term = 0 if kind == MsgReadIndex and rng.random() < 0.5 else max(1, int(s.term[grp]) + int(rng.choice([-1, 0, 0, 0, 1])))
-        _rec(m, i, grp, kind, term=term, frm=int(rng.integers(0, n)), index=int(rng.integers(0, 50)))
+        frm = int(rng.integers(0, n))
+        index = int(rng.integers(0, 50)) if band is None else int(WG.around(rng, s.last_index[grp:grp + 1], -3, 4, 1)[0])
+        _rec(m, i, grp, kind, term=term, frm=frm, index=index)
     if lead_transfer:
         for i in rest[rng.random(len(rest)) < 0.04]:
             _rec(m, i, int(m["group"][i]), T.MsgTransferLeader if rng.random() < 0.5 else T.MsgTimeoutNow, term=int(s.term[int(m["group"][i])]), frm=int(rng.integers(0, n)))
@@ -511,7 +547,11 @@ def step_case(n, self_peer, seed, mode=SAFE, masks=False, pre_vote=True, lead_tr
         P._prop(m, i, int(m["group"][i]), int(rng.integers(1, 4)), frm=int(rng.integers(0, n)))
         m["_pad"][i] = (0, V.MSGF_ENTRIES)
     start = (V.copy_state(s), x.copy())
+    if band is not None:
+        WG.guard_case(s, m)
     want = step_batch(s, voters, x, m, mode, pre_vote, lead_transfer)
+    if band is not None:
+        WG.guard_case(s, m)
     for a in (m, want):
         a.setflags(write=False)
     return start, voters, m, want, (s, x)
@@ -529,12 +569,17 @@ def case_list():
     cases.append(dict(n=9, self_peer=8, seed=11521, mode=LEASE, masks=True, pre_vote=False, lead_transfer=False))
     cases.append(dict(n=3, self_peer=1, seed=11530, hot=True))
     cases.append(dict(n=9, self_peer=0, seed=11531, hot=True, masks=True, pre_vote=False))
+    for k, band in enumerate(WG.BAND_NAMES):  # appended: the positions above are what the GPU tests pick by
+        cases.append(dict(n=3, self_peer=0, seed=11540 + k, pre_vote=bool(k & 1), lead_transfer=k != 1, band=band))
+        cases.append(dict(n=9, self_peer=8, seed=11550 + k, masks=True, pre_vote=not k & 1, lead_transfer=k != 2, band=band))
+    cases.append(dict(n=5, self_peer=4, seed=11560, mode=LEASE, band="b63"))
+    cases.append(dict(n=5, self_peer=0, seed=11561, hot=True, pre_vote=False, band="b32"))
     return cases
 
 
 def case_id(c):
     return "n%d-self%d-%s%s%s%s%s" % (c["n"], c["self_peer"], "lease" if c.get("mode", SAFE) == LEASE else "safe", "-masks" if c.get("masks") else "",
-                                     "-pv" if c.get("pre_vote", True) else "", "-lt" if c.get("lead_transfer", True) else "", "-hot" if c.get("hot") else "")
+                                     "-pv" if c.get("pre_vote", True) else "", "-lt" if c.get("lead_transfer", True) else "", "-hot" if c.get("hot") else "") + ("-" + c["band"] if c.get("band") else "")
 
 
 def case_switches(c):

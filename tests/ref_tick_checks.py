@@ -171,12 +171,15 @@ def _single_scenes(mode, n, me, rng):
     return scenes
 
 
-def _random_scene(mode, g, n, me, hb, rng):
+def _random_scene(mode, g, n, me, hb, rng, wide64=False):
+    """wide64: test_tick_frames_gpu.make_state's terms and indices in [2^62, 2^64), group 0 a leader at term 2^64 - 1 (no scene
+    campaigns from the top term)"""
     from tests import test_tick_elect_gpu as TE
 
     pv, masks = "pv" in mode, "masks" in mode
     full = (1 << n) - 1
-    st = TE.make_state(rng, g, n, me, hb)
+    st = TE.make_state(rng, g, n, me, hb, wide64)
+    assert not wide64 or (int(st.role[0]) == 2 and int(st.term[0]) == 2**64 - 1)
     if pv:  # some of the candidates are pre-candidates already
         cand = np.flatnonzero(st.role == 1)
         st.role[cand[::3]] = PV.PRE
@@ -212,20 +215,24 @@ def _self_of(mode, g, n):
 
 
 @functools.lru_cache(maxsize=None)
-def scenes(mode, g, n):
+def scenes(mode, g, n, wide64=False):
     """the scenes of one GPU case, never changed: each a start state (st, active, lead_elapsed, voters | None, hb, pre_vote) that the
-    test runs TICKS fused calls on.  G = 1: one planted group per scene; else one random scene per heartbeat_tick"""
+    test runs TICKS fused calls on.  G = 1: one planted group per scene; else one random scene per heartbeat_tick.  wide64 (a
+    case's fourth word, G > 1): 64-bit terms and indices"""
     me = _self_of(mode, g, n)
-    rng = np.random.default_rng(28000 + 1000 * MODES.index(mode) + 16 * n + g)
+    rng = np.random.default_rng(28000 + 1000 * MODES.index(mode) + 16 * n + g + (500 if wide64 else 0))
     if g == 1:
+        assert not wide64
         return tuple(_single_scenes(mode, n, me, rng))
-    return tuple(_random_scene(mode, g, n, me, hb, rng) for hb in (1, 3))
+    return tuple(_random_scene(mode, g, n, me, hb, rng, bool(wide64)) for hb in (1, 3))
 
 
 def case_list():
-    """(mode, G, N) of every case tests/test_tick_checks_gpu.py runs: the four switch settings over every shape, N = 9 once"""
+    """(mode, G, N) of every case tests/test_tick_checks_gpu.py runs: the four switch settings over every shape, N = 9 once; then
+    (mode, G, N, "wide64"): the device-built MsgPreVote and MsgVote rounds at term + 1 with every term and index above 2^62"""
     cases = [(mode, g, n) for mode in MODES for g in GS for n in NS]
     cases.append(("cq_pv_masks", 3149, 9))
+    cases += [("cq_pv", 129, 3, "wide64"), ("cq_pv_masks", 129, 5, "wide64")]
     return cases
 
 
@@ -245,9 +252,9 @@ def play(scene, hup_cap=None, beat_cap=None, plain_hup=False, ticks=TICKS):
 
 def shows(case):
     """what a case's inputs show of the feature, read off the reference alone -> dict of counts over all its scenes and ticks"""
-    mode, g, n = case
+    mode, g, n = case[:3]
     c = dict(passed=0, failed=0, failed_beats=0, hups=0, beats=0, pre_kept_term=0, cand_to_pre=0, solo_wins=0, empty_slots=0, campaigns=0)
-    for scene in scenes(mode, g, n):
+    for scene in scenes(*case):
         me = scene["st"].self_peer
         for r in play(scene):
             (s0, a0, le0), (s1, a1, le1) = r["before"], r["after"]

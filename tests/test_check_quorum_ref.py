@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from oracle import pyoracle
+from tests import _widegen as WG
 from tests import ref_check_quorum as Q
 from tests import ref_raft_py as R
 from tests import ref_step_voters as V
@@ -113,6 +114,7 @@ CASES = Q.case_list()
 
 @pytest.mark.parametrize("kw", CASES, ids=[str(sorted(k.items())) for k in CASES])
 def test_every_gpu_input_discriminates(kw):
+    """the band cases too, held to the same floors"""
     start, voters, m, want, after = Q.step_case(**kw)
     got = Q.outcomes(start, voters, m, want)
     can_fail = kw["n"] > 1 or kw.get("masks")  # N = 1 over every slot: the lone leader always passes (the rule itself)
@@ -123,3 +125,63 @@ def test_every_gpu_input_discriminates(kw):
         st = (V.copy_state(start[0]), start[1].copy(), start[2].copy())
         without = Q.step_batch(st[0], voters, st[1], st[2], m, leave_out={rule})
         assert without.tobytes() != want.tobytes() or Q.state_differs(st, after), ("rule %d makes no difference on this input" % rule, kw)
+
+
+# ---- the band cases: 64-bit terms and indices ----------------------------------------------------------------------------------------
+BAND_CASES = [kw for kw in CASES if kw.get("band")]
+B32 = [kw for kw in BAND_CASES if kw["band"] == "b32"]
+B63 = [kw for kw in BAND_CASES if kw["band"] == "b63"]
+
+
+def test_the_band_cases_are_the_issue_s():
+    assert [(kw["band"], kw["n"], bool(kw.get("masks"))) for kw in BAND_CASES] == [(b, n, mk) for b in WG.BAND_NAMES for n, mk in ((3, False), (9, True))]
+    assert CASES[-len(BAND_CASES):] == BAND_CASES and len({Q.case_id(kw) for kw in CASES}) == len(CASES)  # appended, ids of their own
+
+
+@pytest.mark.parametrize("kw", BAND_CASES, ids=Q.case_id)
+def test_band_cases_are_where_they_say(kw):
+    _, _, m, want, after = Q.step_case(**kw)
+    WG.check_in_band(kw["band"], want, kw)
+    WG.guard_case(after[0], m)
+
+
+@pytest.mark.parametrize("kw", B32, ids=Q.case_id)
+def test_a_32_bit_reading_of_the_b32_case_decides_differently(kw):
+    """the reference over the same start and batch with every 64-bit word reduced mod 2^32: measured 44.3 % / 43.2 % of the 512
+    records differ in (type, reject, flags, role), 48 / 50 of them MsgCheckQuorum or MsgVote records (7 / 12 MsgCheckQuorum alone: a
+    check carries no 64-bit word of its own and differs only where the group's role already did); the floors are 10 % and 8."""
+    start, voters, m, want, _ = Q.step_case(**kw)
+    s32, m32 = WG.low32(start[0], m)
+    want32 = Q.step_batch(s32, voters, start[1].copy(), start[2].copy(), m32)
+    WG.check_narrow_reading(m, want, want32, Q.OWN_KINDS, kw)
+
+
+@pytest.mark.parametrize("kw", B63, ids=Q.case_id)
+def test_the_b63_case_compares_across_the_sign_bit(kw):
+    """measured: 52.1 % / 53.3 % of the records have m.term : term or m.index : last_index on opposite sides of 2^63, 55 / 49 of them
+    MsgVote records (a MsgCheckQuorum carries no term); the floors are 5 % and PLANT"""
+    start, _, m, _, _ = Q.step_case(**kw)
+    WG.check_straddles(start[0], m, Q.OWN_KINDS, Q.PLANT, kw)
+
+
+@pytest.mark.parametrize("kw", B32 + B63, ids=Q.case_id)
+def test_the_vote_of_term_B_by_hand(kw):
+    """a MsgVote of term B to a leader and to followers of term B - 1: inside the lease it is ignored and the term stays B - 1, past
+    the lease it is granted and the term becomes B"""
+    B = WG.BANDS[kw["band"]]
+    plants = {}
+    start, _, m, want, after = Q.step_case(**kw, plants=plants)
+    s0, s1 = start[0], after[0]
+    for name, groups in plants.items():
+        assert len(groups) == Q.PLANT
+        for grp in groups:
+            at = np.flatnonzero(m["group"] == grp)
+            assert len(at) == 1 and int(m["type"][at[0]]) == R.MsgVote and int(m["term"][at[0]]) == B and int(s0.term[grp]) == B - 1
+            o = want[at[0]]
+            got = tuple(int(o[k]) for k in ("type", "reject", "index", "flags", "term", "role"))
+            if name == "out_lease":
+                assert got == (R.OutVoteResp, 0, 0, R.FlagHardState, B, F), (name, got)
+                assert (int(s1.term[grp]), int(s1.vote[grp]), int(s1.lead[grp])) == (B, int(m["from"][at[0]]) + 1, 0)
+            else:
+                assert got == (R.OutNone, 0, 0, 0, B - 1, L if name == "led" else F), (name, got)
+                assert (int(s1.term[grp]), int(s1.vote[grp]), int(s1.lead[grp])) == (B - 1, int(s0.vote[grp]), int(s0.lead[grp]))

@@ -132,7 +132,7 @@ def test_the_shapes_at_which_the_kernel_can_go_wrong():
 
 
 @pytest.mark.parametrize("kw", [_pick(n=(3, 0), masks=(False, False), pre_vote=(True, True)), _pick(n=(9, 0), self_peer=(0, 0), masks=(True, False), pre_vote=(False, True)),
-                                HOT[0]], ids=T.case_id)
+                                HOT[0], _pick(band=("top", None), masks=(True, False))], ids=T.case_id)
 def test_step_packed_records_and_result_formats(S, kw):
     """the 40-byte inbound record takes types 13 and 14 and a MsgVote's mark; the three result formats say the same (a packed record
     carries no RAFTQ_MSGF_*, so no MsgProp: the batch goes without them)"""
@@ -170,9 +170,9 @@ def test_step_both_walks(S, monkeypatch, walk):
         monkeypatch.setenv("RAFTQ_STEP_WALK", "sort")
     else:
         monkeypatch.delenv("RAFTQ_STEP_WALK", raising=False)
-    for kw in HOT:
+    for kw in HOT + [_pick(band=("b32", None), masks=(True, False))]:
         start, voters, m, want, after = _case(_key(kw))
-        assert np.bincount(m["group"].astype(np.int64)).max() > 32
+        assert not kw.get("hot") or np.bincount(m["group"].astype(np.int64)).max() > 32
         with _engine(S, start[0], voters, start[1], start[2], start[3], _pv(kw)) as e:
             got, _ = e.step_batch(np.array(m))
             _same_records(got, want, m, (kw, walk))
@@ -226,7 +226,8 @@ def _node_filter(wm, we, g, n, me):
 
 
 @pytest.mark.parametrize("kw", [_pick(n=(3, 0), self_peer=(2, 0), masks=(False, False), pre_vote=(True, True)),
-                                _pick(n=(9, 0), self_peer=(0, 0), masks=(True, False), pre_vote=(False, True))], ids=T.case_id)
+                                _pick(n=(9, 0), self_peer=(0, 0), masks=(True, False), pre_vote=(False, True)), _pick(band=("b63", None), masks=(False, False))],
+                         ids=T.case_id)
 def test_step_frames_and_packed(S, kw):
     """raftq_step_frames and raftq_step_frames_packed over a stream holding frames of types 13 and 14 among the usual kinds: the
     decoded records against the codec oracle (the filter's flags restated), results and state against the reference"""

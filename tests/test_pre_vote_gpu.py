@@ -28,6 +28,11 @@ ANSWERED = 0x10
 _ids = lambda kw: "-".join(str(v) for v in kw.values())  # noqa: E731
 
 
+def _band(band, masks=False):
+    """the band case (64-bit terms and indices, tests/_widegen.py) of the list with this band"""
+    return next(c for c in CASES if c.get("band") == band and bool(c.get("masks")) == masks)
+
+
 @pytest.fixture(scope="module")
 def S(gpu_engine_cls):
     from raftsql_amd import step
@@ -91,7 +96,7 @@ def test_step_batch_against_the_reference(S, kw):
         _same_after(e, after, kw)
 
 
-@pytest.mark.parametrize("kw", [CASES[2], CASES[7], CASES[8]], ids=_ids)
+@pytest.mark.parametrize("kw", [CASES[2], CASES[7], CASES[8], _band("b63", masks=True)], ids=_ids)
 def test_step_packed_records_and_result_formats(S, kw):
     """the 40-byte inbound record takes types 17 and 18 with MsgVote's fields; the three result formats say the same"""
     start, voters, m, _, _ = _case(_key(kw))
@@ -128,9 +133,9 @@ def test_step_both_walks(S, monkeypatch, walk):
         monkeypatch.setenv("RAFTQ_STEP_WALK", "sort")
     else:
         monkeypatch.delenv("RAFTQ_STEP_WALK", raising=False)
-    for kw in (CASES[8], CASES[9]):
+    for kw in (CASES[8], CASES[9], _band("top", masks=True)):
         start, voters, m, want, after = _case(_key(kw))
-        assert np.bincount(m["group"].astype(np.int64)).max() > 32
+        assert not kw.get("hot") or np.bincount(m["group"].astype(np.int64)).max() > 32
         with _engine(S, start[0], voters, start[1], start[2]) as e:
             got, _ = e.step_batch(np.array(m))
             _same_records(got, want, m, (kw, walk))
@@ -177,7 +182,7 @@ def _node_filter(wm, we, g, n, me):
     return out, rec
 
 
-@pytest.mark.parametrize("kw", [CASES[2], CASES[5], CASES[8]], ids=_ids)
+@pytest.mark.parametrize("kw", [CASES[2], CASES[5], CASES[8], _band("b32")], ids=_ids)
 def test_step_frames_and_packed(S, kw):
     """raftq_step_frames and raftq_step_frames_packed over a stream holding frames of types 17 and 18 among the usual kinds: the
     decoded records against the codec oracle (the filter's flags restated), results and state against the reference"""

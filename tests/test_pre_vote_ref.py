@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from oracle import pyoracle
+from tests import _widegen as WG
 from tests import ref_check_quorum as Q
 from tests import ref_pre_vote as PV
 from tests import ref_raft_py as R
@@ -207,3 +208,83 @@ def test_an_inflated_term_brings_the_leader_down_and_the_group_converges():
     assert (np.stack([s.term for s in c.s]).min(axis=0) >= 8).all()
     c.run(2 * 2 * c.et)
     assert c.converged()
+
+
+# ---- the band cases: 64-bit terms and indices ----------------------------------------------------------------------------------------
+BAND_CASES = [kw for kw in CASES if kw.get("band")]
+B32 = [kw for kw in BAND_CASES if kw["band"] == "b32"]
+B63 = [kw for kw in BAND_CASES if kw["band"] == "b63"]
+
+
+def test_the_band_cases_are_the_issue_s():
+    assert [(kw["band"], kw["n"], bool(kw.get("masks"))) for kw in BAND_CASES] == [(b, n, mk) for b in WG.BAND_NAMES for n, mk in ((3, False), (9, True))]
+    assert CASES[-len(BAND_CASES):] == BAND_CASES and len({PV.case_id(kw) for kw in CASES}) == len(CASES)  # appended, ids of their own
+
+
+@pytest.mark.parametrize("kw", BAND_CASES, ids=PV.case_id)
+def test_band_cases_are_where_they_say(kw):
+    _, _, m, want, after = PV.step_case(**kw)
+    WG.check_in_band(kw["band"], want, kw)
+    WG.guard_case(after[0], m)
+    new = np.isin(m["type"], (PRE_VOTE, PRE_RESP))  # what test_every_rule_discriminates_on_the_gpu_inputs asks of every case
+    assert new.sum() >= 40 and np.isin((PRE_CAMPAIGN, PV_RESP, TERM_RESP), want["type"]).all()
+
+
+@pytest.mark.parametrize("kw", B32, ids=PV.case_id)
+def test_a_32_bit_reading_of_the_b32_case_decides_differently(kw):
+    """the reference over the same start and batch with every 64-bit word reduced mod 2^32: measured 46.9 % / 43.4 % of the 512
+    records differ in (type, reject, flags, role), 55 / 54 of them of types 12..18; the floors are 10 % and 8"""
+    start, voters, m, want, _ = PV.step_case(**kw)
+    s32, m32 = WG.low32(start[0], m)
+    want32 = PV.step_batch(s32, voters, start[1].copy(), start[2].copy(), m32)
+    WG.check_narrow_reading(m, want, want32, WG.OWN_KINDS, kw)
+
+
+@pytest.mark.parametrize("kw", B63, ids=PV.case_id)
+def test_the_b63_case_compares_across_the_sign_bit(kw):
+    """measured: 58.8 % / 58.2 % of the records have m.term : term or m.index : last_index on opposite sides of 2^63, 81 / 85 of them
+    of types 12..18; the floors are 5 % and PLANT"""
+    start, _, m, _, _ = PV.step_case(**kw)
+    WG.check_straddles(start[0], m, WG.OWN_KINDS, PV.PLANT, kw)
+
+
+@pytest.mark.parametrize("kw", B32 + B63, ids=PV.case_id)
+def test_the_pre_elections_around_B_by_hand(kw):
+    """the planted groups of term B - 1 (and the stale ones of term B): per record (type, reject, index, flags, term, role), and the
+    term and role after, written out"""
+    B, q = WG.BANDS[kw["band"]], kw["n"] // 2 + 1
+    plants = {}
+    start, _, m, want, after = PV.step_case(**kw, plants=plants)
+    s0, s1 = start[0], after[0]
+
+    def got(grp):
+        at = np.flatnonzero(m["group"] == grp)
+        return [tuple(int(want[i][k]) for k in ("type", "reject", "index", "flags", "term", "role")) for i in at], [int(t) for t in m["term"][at]]
+
+    for name, groups in plants.items():
+        assert len(groups) == PV.PLANT
+        for grp in groups:
+            recs, terms = got(grp)
+            tail = int(s0.last_index[grp])
+            assert int(s0.term[grp]) == (B if name == "stale" else B - 1)
+            if name == "win":  # MsgHup, q - 2 grants that are not yet the quorum, the one that is: the campaign at term B
+                assert terms == [0] + [B] * (q - 1)
+                assert recs == [(PRE_CAMPAIGN, 0, tail, 0, B - 1, P)] + [(R.OutNone, 0, 0, 0, B - 1, P)] * (q - 2) + [(CAMPAIGN, 0, tail, HS, B, C)]
+                end = (B, C)
+            elif name == "bump":  # one rejection from two terms up: becomeFollower(B + 1, None)
+                assert terms == [0, B + 1]
+                assert recs == [(PRE_CAMPAIGN, 0, tail, 0, B - 1, P), (R.OutNone, 0, 0, HS | DOWN, B + 1, F)]
+                end = (B + 1, F)
+            elif name == "in_lease":
+                assert terms == [B] and recs == [(R.OutNone, 0, 0, 0, B - 1, F)]
+                end = (B - 1, F)
+            elif name == "out_lease":  # granted with the message's term; nothing changes
+                assert terms == [B] and recs == [(PV_RESP, 0, B, 0, B - 1, F)]
+                end = (B - 1, F)
+            elif name == "stale":  # the term before, from across the boundary: TERM_RESP twice, a rejection with the own term
+                assert terms == [B - 1] * 3 and recs == [(TERM_RESP, 0, 0, 0, B, F)] * 2 + [(PV_RESP, 1, B, 0, B, F)]
+                end = (B, F)
+            else:  # led: the next term's is ignored in the lease, the own term's rejected with the own term
+                assert terms == [B, B - 1] and recs == [(R.OutNone, 0, 0, 0, B - 1, L), (PV_RESP, 1, B - 1, 0, B - 1, L)]
+                end = (B - 1, L)
+            assert (int(s1.term[grp]), int(s1.role[grp])) == end, name

@@ -128,7 +128,7 @@ def _unpacked(S, m40):
 
 
 @pytest.mark.parametrize("kw", [_pick(n=(3, 0), self_peer=(0, 0), masks=(False, False)), _pick(n=(9, 0), self_peer=(8, 0), masks=(True, False)),
-                                _pick(mode=(RI.LEASE, RI.SAFE)), HOT[0]], ids=RI.case_id)
+                                _pick(mode=(RI.LEASE, RI.SAFE)), HOT[0], _pick(band=("b32", None), masks=(True, False))], ids=RI.case_id)
 def test_step_packed_records_and_result_formats(S, kw):
     """the 40-byte inbound record takes types 15 and 16 and a heartbeat's context; the three result formats say the same: log_term
     rides the commit slot of RAFTQ_OUT_READ_INDEX and of a RAFTQ_OUT_PROGRESS with RAFTQ_OUTF_READ_READY (a packed record carries no
@@ -170,7 +170,7 @@ def test_step_both_walks(S, monkeypatch, walk):
         monkeypatch.setenv("RAFTQ_STEP_WALK", "sort")
     else:
         monkeypatch.delenv("RAFTQ_STEP_WALK", raising=False)
-    for kw in HOT + [_pick(n=(5, 0), self_peer=(4, 0), masks=(True, False))]:
+    for kw in HOT + [_pick(n=(5, 0), self_peer=(4, 0), masks=(True, False)), _pick(band=("b63", None), masks=(False, False))]:  # (HOT: a b32 case too)
         start, voters, m, want, after = _case(_key(kw))
         sw = RI.case_switches(kw)
         assert not kw.get("hot") or np.bincount(m["group"].astype(np.int64)).max() > 32
@@ -180,11 +180,11 @@ def test_step_both_walks(S, monkeypatch, walk):
             _same_after(e, after, voters, sw["mode"], sw["lead_transfer"], (kw, walk))
 
 
-def _leaders(n, me, g):
+def _leaders(n, me, g, term=4, tail=9):
     """g led groups at term 4 with a log of 9 entries, 7 of them committed, the gate open"""
     s = pyoracle.NodeState(g, n, me)
-    s.term[:], s.vote[:], s.lead[:], s.role[:], s.last_index[:], s.last_term[:], s.first_idx[:], s.committed[:] = 4, me + 1, me + 1, 2, 9, 4, 1, 7
-    s.match[:] = 9
+    s.term[:], s.vote[:], s.lead[:], s.role[:], s.last_index[:], s.last_term[:], s.first_idx[:], s.committed[:] = term, me + 1, me + 1, 2, tail, term, 1, tail - 2
+    s.match[:] = tail
     return s
 
 
@@ -237,7 +237,8 @@ def _with_contexts(m):
     return m
 
 
-@pytest.mark.parametrize("kw", [_pick(n=(3, 0), self_peer=(2, 0), masks=(False, False)), _pick(n=(9, 0), self_peer=(0, 0), masks=(True, False))], ids=RI.case_id)
+@pytest.mark.parametrize("kw", [_pick(n=(3, 0), self_peer=(2, 0), masks=(False, False)), _pick(n=(9, 0), self_peer=(0, 0), masks=(True, False)),
+                                _pick(band=("top", None), masks=(True, False))], ids=RI.case_id)
 def test_step_frames_and_packed(S, kw):
     """raftq_step_frames and raftq_step_frames_packed over a stream holding frames of types 15 and 16 among the usual kinds: the
     decoded records against the codec oracle (the filter's flags restated), results and state against the reference"""
@@ -253,6 +254,9 @@ def test_step_frames_and_packed(S, kw):
     wm, we, bad = W.wire_decode(stream, off)
     assert bad == 0 and np.isin(wm["type"], NEW_KINDS).sum() >= 40
     assert (wm["n_ents"][wm["type"] == RI.MsgReadIndex] == 1).all()
+    if kw.get("band") == "top":  # every term on the wire and every position is a ten-byte varint
+        pos = np.isin(wm["type"], (R.MsgApp, R.MsgAppResp, R.MsgVote, RI.MsgReadIndexResp))
+        assert (wm["term"][wm["term"] != 0] >= 2**63).all() and (wm["index"][pos & (wm["index"] != 0)] >= 2**63).mean() > 0.9
     want_m, rec = _node_filter(wm, we, s0.G, s0.N, me)
     new = np.isin(want_m["type"], NEW_KINDS)
     assert ((want_m["flags"][new] & (V.MSGF_SKIP | V.MSGF_HOLD | V.MSGF_ENTRIES | V.MSGF_BARRIER)) == 0).all() and ((want_m["flags"] & V.MSGF_SKIP) != 0).any()
@@ -326,6 +330,16 @@ def test_frames_respond_echoes_the_context_and_leaves_reads_to_the_host(S):
     """raftq_step_frames_respond: a device-built MsgHeartbeatResp carries Index = the heartbeat's -- byte for byte raftq_wire_encode of
     host-built records, in both modes, a zero context among them --; RAFTQ_OUT_READ_INDEX, RAFTQ_OUT_READ_STATE and a forwarded read
     carry no RAFTQ_OUTF_ANSWERED and end their group's device-answered prefix; RAFTQ_OUTF_READ_READY ends none"""
+    _frames_respond(S, 4, 9, None)
+
+
+def test_frames_respond_echoes_the_context_at_b63(S):
+    """the same at a term of 2^63 + 1 over a log that ends at 2^63 + 2: every echoed frame holds the context 2^32 + 7 (or the
+    next one) in a five-byte varint beside a ten-byte term"""
+    _frames_respond(S, 2**63 + 1, 2**63 + 2, 2**32 + 7)
+
+
+def _frames_respond(S, term, tail, context):
     from oracle import pywire as W
     from raftsql_amd.engine import pinned_copy, pinned_empty
     from raftsql_amd.wire import WIRE_ENT_DT, WIRE_MSG_DT, WireEngine
@@ -333,20 +347,22 @@ def test_frames_respond_echoes_the_context_and_leaves_reads_to_the_host(S):
     n, me, g = 3, 1, 48
     kind = np.arange(g) % 6  # 0, 1: following, heartbeats only | 2: following, a read state first | 3: following, a forwarded read first
     led = kind >= 4          # 4: led, a request first | 5: led with a request pending, the completing acknowledgement first
-    s = _leaders(n, me, g)
+    s = _leaders(n, me, g, term, tail)
     s.role[~led], s.lead[~led], s.vote[~led], s.first_idx[~led] = 0, 3, 0, 0
     s.match[0, ~led] = s.match[2, ~led] = 0
     x = RI.zero_extra(g, n)
     x.seq[kind == 5], x.acked[me, kind == 5] = 1, 1
     ctx = (np.arange(g, dtype=np.uint64) + np.uint64(1)) * np.uint64(0x10000001)  # zero, small and beyond 2^32
+    if context is not None:
+        ctx[:] = context
     ctx[kind == 0] = 0
     first_index = ctx.copy()
-    first_index[kind == 2], first_index[kind == 3], first_index[kind == 4], first_index[kind == 5] = 7, 0, 0, 1
-    first = _wire_records(g, me, 2, 4, np.choose(kind, [R.MsgHeartbeat, R.MsgHeartbeat, RI.MsgReadIndexResp, RI.MsgReadIndex, RI.MsgReadIndex, R.MsgHeartbeatResp]),
+    first_index[kind == 2], first_index[kind == 3], first_index[kind == 4], first_index[kind == 5] = tail - 2, 0, 0, 1
+    first = _wire_records(g, me, 2, term, np.choose(kind, [R.MsgHeartbeat, R.MsgHeartbeat, RI.MsgReadIndexResp, RI.MsgReadIndex, RI.MsgReadIndex, R.MsgHeartbeatResp]),
                           first_index)
     second_index = ctx + np.uint64(1)
     second_index[led] = 0
-    second = _wire_records(g, me, 2, 4, np.where(led, R.MsgHeartbeatResp, R.MsgHeartbeat), second_index)
+    second = _wire_records(g, me, 2, term, np.where(led, R.MsgHeartbeatResp, R.MsgHeartbeat), second_index)
     w = np.concatenate([first, second])
     stream, off = W.wire_encode(w, np.zeros(0, W.WIRE_ENT_DT), np.zeros(1, np.uint8))
     at_tail = pinned_copy(np.full((g + 63) // 64, ~np.uint64(0), np.uint64))
@@ -368,7 +384,7 @@ def test_frames_respond_echoes_the_context_and_leaves_reads_to_the_host(S):
             # the frames: one slice, peer 2's, in result order
             answered = np.concatenate([np.flatnonzero(kind < 2), g + np.flatnonzero(kind < 2)])
             host = np.zeros(len(answered), W.WIRE_MSG_DT)
-            host["group"], host["to"], host["from"], host["term"], host["type"] = w["group"][answered], 2, me, 4, R.MsgHeartbeatResp
+            host["group"], host["to"], host["from"], host["term"], host["type"] = w["group"][answered], 2, me, term, R.MsgHeartbeatResp
             host["index"] = w["index"][answered]
             want_bytes, _ = W.wire_encode(host, np.zeros(0, W.WIRE_ENT_DT), np.zeros(1, np.uint8))
             assert int(rc.n_msgs) == len(answered) and bytes(got) == want_bytes.tobytes(), mode

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from oracle import pyoracle
+from tests import _widegen as WG
 from tests import ref_lead_transfer as T
 from tests import ref_raft_py as R
 from tests import ref_read_index as RI
@@ -324,3 +325,97 @@ def test_lost_round_needs_rule_5():
     c = RI.Cluster(G_SCENARIO, True, ri_leave_out={5}, **CLUSTER_KW)
     with pytest.raises(AssertionError):
         lost_round(c)
+
+
+# ---- the band cases: 64-bit terms, indices and contexts --------------------------------------------------------------------------------
+BAND_CASES = [kw for kw in CASES if kw.get("band")]
+B32 = [kw for kw in BAND_CASES if kw["band"] == "b32"]
+B63 = [kw for kw in BAND_CASES if kw["band"] == "b63"]
+
+
+def test_the_band_cases_are_the_issue_s():
+    per_band = [(kw["band"], kw["n"], bool(kw.get("masks"))) for kw in BAND_CASES[:6]]
+    assert per_band == [(b, n, mk) for b in WG.BAND_NAMES for n, mk in ((3, False), (9, True))]
+    assert [(kw["band"], kw.get("mode", RI.SAFE), bool(kw.get("hot"))) for kw in BAND_CASES[6:]] == [("b63", RI.LEASE, False), ("b32", RI.SAFE, True)]
+    assert CASES[-len(BAND_CASES):] == BAND_CASES and len({RI.case_id(kw) for kw in CASES}) == len(CASES)  # appended, ids of their own
+    assert {kw.get("pre_vote", True) for kw in BAND_CASES} == {kw.get("lead_transfer", True) for kw in BAND_CASES} == {False, True}
+
+
+@pytest.mark.parametrize("kw", BAND_CASES, ids=RI.case_id)
+def test_band_cases_are_where_they_say(kw):
+    _, _, m, want, after = RI.step_case(**kw)
+    WG.check_in_band(kw["band"], want, kw)
+    WG.guard_case(after[0], m)
+    beats = np.isin(m["type"], (R.MsgHeartbeat, R.MsgHeartbeatResp))
+    assert (m["index"][beats] >= 2**32).sum() >= RI.ARM_FLOOR  # contexts the 32-bit record cannot hold
+
+
+@pytest.mark.parametrize("kw", B32, ids=RI.case_id)
+def test_a_32_bit_reading_of_the_b32_case_decides_differently(kw):
+    """the reference over the same start and batch with every 64-bit word reduced mod 2^32 (a context of 2^32 + 1 then reads as round
+    1): measured 32.8 % / 28.1 % / 22.3 % (the hot case) of the 512 records differ in (type, reject, flags, role), 23 / 22 / 16 of them
+    of types 12..18; the floors are 10 % and 8"""
+    start, voters, m, want, _ = RI.step_case(**kw)
+    s32, m32 = WG.low32(start[0], m)
+    want32 = RI.step_batch(s32, voters, start[1].copy(), m32, **RI.case_switches(kw))
+    WG.check_narrow_reading(m, want, want32, WG.OWN_KINDS, kw)
+
+
+@pytest.mark.parametrize("kw", B63, ids=RI.case_id)
+def test_the_b63_case_compares_across_the_sign_bit(kw):
+    """measured: 37.5 % / 33.8 % / 36.9 % (the lease case) of the records have m.term : term or m.index : last_index on opposite sides
+    of 2^63, 23 / 19 / 16 of them of types 12..18; the floors are 5 % and PLANT"""
+    start, _, m, _, _ = RI.step_case(**kw)
+    WG.check_straddles(start[0], m, WG.OWN_KINDS, RI.PLANT, kw)
+
+
+@pytest.mark.parametrize("kw", BAND_CASES, ids=RI.case_id)
+def test_the_gate_the_contexts_and_the_read_states_by_hand(kw):
+    """the band-only plants: per record (type, index, log_term, READ_READY), and the read record after, written out"""
+    band, safe = kw["band"], kw.get("mode", RI.SAFE) == RI.SAFE
+    plants = {}
+    start, _, m, want, after = RI.step_case(**kw, plants=plants)
+    s0, x1 = start[0], after[1]
+    H = RI.PLANT // 2
+
+    def got(grp):
+        at = np.flatnonzero(m["group"] == grp)
+        return _got(want[at]), m[at]
+
+    # the gate: committed >= first_idx, as 64-bit words
+    assert len(plants["same"]) == len(plants["apart"]) == 2 * H
+    for name in ("same", "apart"):
+        for grp in plants[name]:
+            recs, sent = got(grp)
+            c, f = int(s0.committed[grp]), int(s0.first_idx[grp])
+            assert c >= (WG.band_floor(band)[1] - 1 if name == "same" else 2**32 + 1) and c == int(s0.last_index[grp]) - 1
+            assert f == (c if name == "same" else c - 2**32) and f >= 1
+            assert int(sent["type"][0]) == RI.MsgReadIndex
+            assert recs[0][:4] == ((RI.OutReadIndex, c, 1, 0) if safe else (RI.OutReadIndex, c, 0, READY)), (name, recs[0])  # open: the index whole
+    closed = plants["closed"]
+    assert [int(s0.first_idx[grp]) for grp in closed[::2]] == [0] * H and int(s0.first_idx[closed[1]]) == int(s0.committed[closed[1]]) + 1
+    if band != "top":
+        assert int(s0.first_idx[closed[-1]]) == int(s0.committed[closed[-1]]) + 2**32
+    for grp in closed:
+        recs, _ = got(grp)
+        assert [r[:4] for r in recs] == [(R.OutNone, 0, 0, 0)], recs  # closed: dropped
+    # contexts at and above 2^32 are beyond every seq: nothing stored, nothing released
+    for grp in plants["beyond"]:
+        recs, sent = got(grp)
+        assert [int(c) for c in sent["index"]] == [5, 0, 2**32 + 1, 2**32, 2**63 + 2] and (sent["type"] == R.MsgHeartbeatResp).all()
+        assert [r[:4] for r in recs] == [(R.OutProgress, int(s0.match[p, grp]), 0, 0) for p in sent["from"]]  # (the sender's Match, as always)
+        if safe:
+            assert int(start[1].seq[grp]) == int(x1.seq[grp]) == 3 and x1.acked[:, grp].tolist() == [3 if p == s0.self_peer else 0 for p in range(s0.N)]
+    # a heartbeat's context is echoed whole, by a follower and by a candidate (which follows the sender first)
+    for name in ("fwd", "cnd"):
+        for grp in plants[name]:
+            recs, sent = got(grp)
+            assert int(sent["type"][-1]) == R.MsgHeartbeat and int(sent["index"][-1]) == 2**32 + 7
+            assert recs[-1][:4] == (R.OutHeartbeatResp, 2**32 + 7, 0, 0) and int(after[0].role[grp]) == 0
+    # a MsgReadIndexResp's index -- the lifted committed -- arrives whole
+    for grp in plants["rstate"]:
+        recs, sent = got(grp)
+        idx = plants["read_at"][int(grp)]
+        assert idx >= 2**32 and idx in (int(s0.committed[grp]), WG.band_edge(band) + list(plants["rstate"]).index(grp))
+        assert int(sent["type"][1]) == RI.MsgReadIndexResp and int(sent["index"][1]) == idx
+        assert recs[0][:4] == (R.OutNone, 0, 0, 0) and recs[1][:4] == (RI.OutReadState, idx, 0, 0)

@@ -134,8 +134,8 @@ def check_round(e, twin, scene, r, hup_cap, beat_cap, chk_cap, bitmap, what, fra
 @pytest.mark.parametrize("case", CASES, ids=_ids)
 def test_rounds_match_the_reference_and_the_twin(oracle, case):
     """three fused calls in a row per scene: both flags values, with and without frame_off, every cap at G"""
-    mode, g, n = case
-    for k, scene in enumerate(R.scenes(mode, g, n)):
+    mode, g, n = case[:3]
+    for k, scene in enumerate(R.scenes(*case)):
         rounds = R.play(scene)
         with _engine(scene) as e, _engine(scene, checks=False) as twin:
             for t, r in enumerate(rounds):

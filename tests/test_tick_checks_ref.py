@@ -188,7 +188,7 @@ def test_the_literal_frames_are_what_they_say():
 # ---- 3. every GPU case discriminates -----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", CASES, ids=_ids)
 def test_every_case_discriminates(oracle, case):
-    mode, g, n = case
+    mode, g, n = case[:3]
     c = R.shows(case)
     assert c["passed"] >= 1, c        # a check that is due and passes, its bits cleared
     assert c["failed"] >= 1, c        # one that fails: action 3 ...
@@ -200,6 +200,25 @@ def test_every_case_discriminates(oracle, case):
         assert c["campaigns"] >= 1, c
     if "masks" in mode:
         assert c["solo_wins"] >= 1 and c["empty_slots"] >= 1, c
+
+
+@pytest.mark.parametrize("case", [c for c in CASES if len(c) == 4], ids=_ids)
+def test_the_wide_cases_ask_above_2_63(oracle, case):
+    """a wide64 case: device-built MsgPreVote frames -- asked at term + 1 -- with a term above 2^63, over tails and last terms above 2^62"""
+    assert case[3] == "wide64" and "pv" in case[0] and CASES[-2:] == [c for c in CASES if len(c) == 4]
+    high = asked = 0
+    for scene in R.scenes(*case):
+        st = scene["st"]
+        assert int(st.term[0]) == 2**64 - 1 and int(st.role[0]) == 2 and int(st.term.min()) >= 2**62 and int(st.last_index.min()) >= 2**62
+        for r in R.play(scene):
+            w = r["w"][r["keep"]]
+            pre = w[w["type"] == R.MSG_PRE_VOTE]
+            high += int((pre["term"] > 2**63).sum())
+            asked += int(((pre["index"] >= 2**62) & (pre["log_term"] >= 2**62)).sum())  # (under PreVote a Tick's MsgHup never asks by MsgVote)
+            assert 0 not in r["built"]  # nobody campaigns from the top term
+            before = r["before"][0].term[r["built"]]
+            assert np.array_equal(r["outs"]["term"] + (r["outs"]["type"] == R.OUT_PRE_CAMPAIGN), before + np.uint64(1))  # every round asks at term + 1
+    assert high >= 1 and asked >= 1, (high, asked)
 
 
 # ---- 4. the switch's effect left out -----------------------------------------------------------------------------------------------
